@@ -7,14 +7,22 @@ Workload: C4, the configuration the north-star target is quoted on ("the 6-D pos
           sym_linspace grid x the 9 thruster combinations, the reference's typing (single J and
           cost, DOUBLE query tables :299-327 = table_dtype float64; U_Optimal_id as one byte per state), zero terminal
           cost (Solver_pos_att.m:264-265), state axes relabelled (x, theta, w, v) = Solver_pos_att.FAST_AXIS_ORDER.
+Plain run: set up, `--warmup` stages, ONE timed region of `--steps` stages, the outputs if `--dump-outputs DIR` is given,
+          the line.  Everything below that the headline does not need - the repetitions, the counter passes, the other
+          workloads, the CPU baseline, the checksum, at N > 1 the other halo transport's leg and the weak-scaling figure -
+          runs with `--full` only.
+Outputs : `--dump-outputs DIR` writes what the last timed stage computed, in the global column-major state order, as
+          DIR/J.npy (the cost-to-go) and DIR/argmin.npy (the argmin labels, as floats): whole when the grid has at most
+          DUMP_SAMPLE states, else at DUMP_SAMPLE fixed, seeded states whose linear indices are DIR/state_index.npy.
+With --full:
           The other BASELINE configs are measured in the same run as extra keys of the line (`other_workloads`:
           C5 = C4 with float16 cost-to-go storage, C2 = Solver_position 101^3 x 21^3, 6D = the attitude model of
           Solver_attitude.run on 24^6 states x 11^3 torques - SURVEY 8(d)'s "6-D" figure - and C3 = that model on
           51^6 states with the next angles computed in the kernel: BASELINE configs[2], 176 GB resident, 1 warm-up + 2
           timed stages, skipped with the reason stated when less than 190 GB of HBM are free), each with its own
           roofline object from the same live counter passes; they are also parity tests.
-Timing  : the timed region (K steps between barriers) is repeated 3 times; `ms_per_step` / `value` are the MEDIAN
-          repetition, `ms_per_step_min` and `ms_per_step_reps` say what the others were.
+Timing  : the timed region (K steps between barriers) runs once; with --full it is repeated 3 times, `ms_per_step` /
+          `value` are the MEDIAN repetition, `ms_per_step_min` and `ms_per_step_reps` say what the others were.
 Step    : ONE stage of the backward sweep = one fused backup kernel over the whole grid (1.866e9 backups).
 N GPUs  : one process per GPU (torchrun), the FIXED grid sharded along its last state axis (v: next states move
           < 1 plane, so the halo is one plane each side) = STRONG scaling; neighbour halo exchange per stage over RCCL
@@ -23,8 +31,8 @@ N GPUs  : one process per GPU (torchrun), the FIXED grid sharded along its last 
 
 Prints ONE JSON line on rank 0.  `roofline`: the path is VALU-bound at every BASELINE config, so
 `achieved` = algorithmic flops F_alg(4) = 71 per backup / launch time against the 157.3 TFLOP/s fp32 vector peak; the
-executed-instruction view (`valu_issue_util`) and `traffic` come from rocprofv3 --pmc passes that THIS run makes on
-child processes of the same command (rank 0, N = 1; null when rocprofv3 is unavailable).  `cpu_baseline` times the
+executed-instruction view (`valu_issue_util`) and `traffic` come from rocprofv3 --pmc passes that a --full run makes on
+child processes of the same command (rank 0, N = 1; null when rocprofv3 is unavailable).  `cpu_baseline` (--full) times the
 oracle's C twin (oracle/hjb_oracle.c, OpenMP) on a bounded slab sample of the same workload IN THE SAME TYPING
 (float64-built queries, float32 blend: `cpu_baseline.typing`).
 """
@@ -62,6 +70,8 @@ KERNEL_FILTER = {"c4": ("k_backup_colsweep<float, float", None), "c5": ("k_backu
                  "c3": (("k_backup_uniwin<float, 6, true", "k_backup_packed2<float, 6, 6>", "k_backup_packed2<float, 6, 3>"), None)}      # on-the-fly model
 EXTRA_STEPS = {"c5": 20, "c2": 20, "6d": 4, "c3": 2}
 C3_NEEDS_GIB = 190          # J_k+1 + J_k (70.4 GB each) + uint16 labels (35.2 GB) = 176 GB resident
+DUMP_SAMPLE = 1 << 21       # --dump-outputs: states written (J + label + float64 index: 32 MB at most)
+DUMP_SEED = 20240601
 
 
 def f_alg(D):
@@ -271,9 +281,47 @@ def run_c3(args, steps, warmup, dev, n=51):
             "halo": (0, 0), "checksum": cs, "total_backups": spec.nS * spec.nU * steps, "walls": [wall]}
 
 
-def run_workload(args, workload, steps, warmup, world, rank, dev, dist, weak=False, reps=1, transport=None):
+def sample_outputs(sw, spec, dist, backend):
+    """What the last stage left for a caller - J and the argmin labels of every state, in global column-major order -
+    whole when the grid has at most DUMP_SAMPLE states, else at DUMP_SAMPLE seeded states (fixed by DUMP_SEED and the
+    grid size alone, sorted).  Every rank contributes its owned planes (N > 1: a sum over ranks of disjoint parts).
+    -> {name: float32 / float64 array}"""
+    import numpy as np
+    import torch
+    if spec.nS <= DUMP_SAMPLE:
+        pos = np.arange(spec.nS, dtype=np.int64)
+    else:
+        pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, spec.nS, DUMP_SAMPLE, dtype=np.int64))
+    lo, hi = sw.begin * sw.inner, sw.end * sw.inner
+    mine = (pos >= lo) & (pos < hi)
+    sel = torch.from_numpy(pos[mine] - lo).to(sw.device)
+    vals = torch.zeros((2, pos.size), dtype=torch.float64, device=sw.device)
+    where = torch.from_numpy(np.nonzero(mine)[0]).to(sw.device)
+    vals[0, where] = sw.owned_J().reshape(-1)[sel].double()
+    idx = sw.idx.reshape(-1)
+    if idx.dtype == torch.uint16:           # (gathered as int16: fewer kernels exist for the unsigned type)
+        lab = idx.view(torch.int16)[sel].to(torch.int64) & 0xFFFF
+    else:
+        lab = idx[sel].to(torch.int64)
+    vals[1, where] = lab.double()
+    if dist is not None:
+        if backend != "nccl":
+            vals = vals.cpu()
+        dist.all_reduce(vals)               # the parts are disjoint and the others' are zero: the sum is exact
+    vals = vals.cpu().numpy()
+    jt = np.float64 if np.dtype(spec.j_dtype) == np.float64 else np.float32
+    it = np.float64 if spec.idx_np_dtype.itemsize > 2 else np.float32
+    out = {"J": vals[0].astype(jt), "argmin": vals[1].astype(it)}
+    if pos.size < spec.nS:
+        out["state_index"] = pos.astype(np.float64)
+    return out
+
+
+def run_workload(args, workload, steps, warmup, world, rank, dev, dist, weak=False, reps=1, transport=None, checksum=True,
+                 dump=False):
     """Times `steps` stages of `workload` on this rank's slab, `reps` times over (each repetition bracketed by barriers;
-    the MEDIAN repetition is reported, all of them are returned).  -> dict of measurements."""
+    the MEDIAN repetition is reported, all of them are returned).  checksum: sum of J after the last stage (`checksum`
+    key, else None); dump: the last stage's outputs (`outputs` key, sample_outputs).  -> dict of measurements."""
     import torch
     from hjbdp.sharded import ShardedSweep
     n = {"c2": 101, "6d": 24, "c3": args.c3_n}.get(workload, args.grid_n)
@@ -315,13 +363,18 @@ def run_workload(args, workload, steps, warmup, world, rank, dev, dist, weak=Fal
     sw.check_device_status()
     med = sorted(range(len(walls)), key=lambda i: walls[i])[len(walls) // 2]      # the median repetition (by the max-over-ranks wall)
     wall, dev_ms = walls[med], devs[med]
-    cs = sw.owned_J().double().sum().reshape(1)
-    if world > 1:
-        cs = cs.cpu() if args.backend != "nccl" else cs
-        dist.all_reduce(cs)
+    cs = None
+    if checksum:
+        cs = sw.owned_J().double().sum().reshape(1)
+        if world > 1:
+            cs = cs.cpu() if args.backend != "nccl" else cs
+            dist.all_reduce(cs)
+        cs = float(cs[0])
     res = {"spec": spec, "name": name, "info": info, "wall": wall, "dev_ms": dev_ms, "steps": steps,
-           "states_rank": sw.owned * sw.inner, "halo": (sw.halo_lo, sw.halo_hi), "checksum": float(cs[0]),
+           "states_rank": sw.owned * sw.inner, "halo": (sw.halo_lo, sw.halo_hi), "checksum": cs,
            "total_backups": spec.nS * spec.nU * steps, "walls": walls}
+    if dump:
+        res["outputs"] = sample_outputs(sw, spec, dist if world > 1 else None, args.backend)
     sw.close()
     return res
 
@@ -400,9 +453,19 @@ def main():
                     help="N > 1: who moves the halo planes - torch.distributed P2P from Python (default), or the RCCL transport inside "
                          "libhjbdp (hjb_rank_step: one library call per stage; needs one GPU per rank)")
     ap.add_argument("--share-gpu", action="store_true", help="testing: every rank uses cuda:0")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: 3 repetitions of the timed region, the counter "
+                         "passes, the other workloads, the CPU baseline, the checksum; N > 1: the other halo transport's leg and "
+                         "weak scaling (the --no-* options above switch parts off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write J and the argmin labels of the last timed stage as DIR/*.npy (a seeded sample of large grids)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
+    if args.pmc_child:                       # a counter pass runs the workloads of the --full run that started it
+        args.full = True
+    if not args.full:                        # the plain run: the headline only
+        args.no_pmc = args.no_extras = args.no_cpu_baseline = True
     if args.workload == "c3":                # the 176 GB configuration as the headline: nothing else rides on the line
         args.no_extras = args.no_cpu_baseline = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -417,7 +480,7 @@ def main():
     extras = [w for w in ("c5", "c2", "6d", "c3") if w != args.workload] if (world == 1 and not args.no_extras and args.grid_n == 120) else []
     if args.no_c3 and "c3" in extras:
         extras.remove("c3")
-    pmc_all, pmc_note = None, "not collected"
+    pmc_all, pmc_note = None, "not collected" if args.full else "not collected (bench.py --full makes the counter passes)"
     if world == 1 and not args.pmc_child and not args.no_pmc:
         child = ["--workload", args.workload, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pmc",
                  "--grid-n", str(args.grid_n)]
@@ -449,7 +512,13 @@ def main():
         else:
             dist.init_process_group(args.backend, rank=rank, world_size=world)
 
-    head = run_workload(args, args.workload, args.steps, args.warmup, world, rank, dev, dist, reps=1 if args.pmc_child else 3)
+    head = run_workload(args, args.workload, args.steps, args.warmup, world, rank, dev, dist,
+                        reps=3 if args.full and not args.pmc_child else 1, checksum=args.full, dump=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, a in head.pop("outputs").items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), a)
     # N > 1 over RCCL: BOTH halo transports sweep the same grid under the same timing contract - `--transport`
     # first, then the other one (the RCCL calls inside libhjbdp, or torch.distributed's P2P from Python).  The line's HEADLINE is the
     # `--transport` leg, whatever the other one measures (the maximum of two noisy legs is biased upward and would not compare with
@@ -459,7 +528,7 @@ def main():
     legs, leg_error, chosen = {args.transport: head}, None, args.transport
     other = "lib" if args.transport == "torch" else "torch"
     watchdog = None
-    if world > 1 and not args.pmc_child:
+    if world > 1 and args.full and not args.pmc_child:
         def headline_only():
             sp = head["spec"]
             launch_ms = head["dev_ms"] / head["steps"]
@@ -481,7 +550,7 @@ def main():
         watchdog = OptionalLegsWatchdog(limit, rank, headline_only)
         if args.test_hang_optional == rank or args.test_hang_optional == -2:
             time.sleep(36000)
-    if world > 1 and args.backend == "nccl" and not args.pmc_child:
+    if world > 1 and args.backend == "nccl" and args.full and not args.pmc_child:
         ok = 1
         try:
             legs[other] = run_workload(args, args.workload, args.steps, args.warmup, world, rank, dev, dist, reps=3, transport=other)
@@ -583,7 +652,8 @@ def main():
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["wall"] * 1e3 / args.steps,
         "ms_per_step_min": min(head["walls"]) * 1e3 / args.steps,
         "ms_per_step_reps": [w * 1e3 / args.steps for w in head["walls"]],
-        "timing": "3 repetitions of the K-step timed region, each between barriers; value / ms_per_step = the median repetition",
+        "timing": ("3 repetitions of the K-step timed region, each between barriers; value / ms_per_step = the median repetition"
+                   if args.full else "1 K-step timed region between barriers (--full: 3 repetitions, the median reported)"),
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "f32" if spec.j_dtype.itemsize == 4 else "f32 (J stored as f16)", "data": "synthetic",
         "config": {"workload": head["name"], "states": spec.nS, "states_per_gpu": head["states_rank"], "controls": spec.nU,
@@ -594,8 +664,9 @@ def main():
                                    "" if args.no_overlap else ", overlapped with the interior planes")) if world > 1 else "none",
                    "kernel_variant": info["kernel_variant"]},
         "roofline": rf,
-        "checksum_sum_J": head["checksum"],
     }
+    if args.full:
+        out["checksum_sum_J"] = head["checksum"]
     if world > 1:
         # Both transports' legs (measured above): each carries the rank count its communicator ITSELF reports (ncclCommCount
         # through the library / the process group's size), so that a first multi-GPU run verifies what it measured.  Equal
@@ -609,7 +680,11 @@ def main():
             out["transports"][other] = {"error": leg_error}
         out["transports"]["headline"] = chosen
         out["transports"]["headline_rule"] = "the --transport leg (%s); the other leg is reported beside it, never chosen" % args.transport
-        out["transports"]["checksums_equal"] = len({r["checksum"] for r in legs.values()}) == 1
+        if args.full:
+            out["transports"]["checksums_equal"] = len({r["checksum"] for r in legs.values()}) == 1
+        else:                                # (no checksum in a plain run)
+            for r in legs:
+                out["transports"][r].pop("checksum_sum_J")
     if not args.no_extras:
         if world == 1:
             others = {}

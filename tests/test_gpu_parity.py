@@ -921,7 +921,7 @@ def test_two_rank_sharded_bench_matches_single_rank(env, overlap):
         pytest.skip("torch did not come up in a child process on this box (see test_device_buffer_entry_point_with_torch)")
     root = Path(__file__).resolve().parent.parent
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    common = ["--steps", "4", "--warmup", "1", "--grid-n", "34", "--variant", "7", "--no-cpu-baseline", "--no-pmc", "--no-extras"]
+    common = ["--full", "--steps", "4", "--warmup", "1", "--grid-n", "34", "--variant", "7", "--no-cpu-baseline", "--no-pmc", "--no-extras"]
     try:
         one = subprocess.run([sys.executable, str(root / "bench.py")] + common, capture_output=True, text=True, timeout=600)
         assert one.returncode == 0, one.stderr[-2000:]
@@ -965,7 +965,7 @@ def test_two_rank_bench_survives_a_hang_after_the_headline(env, who):
         pytest.skip("torch did not come up in a child process on this box")
     root = Path(__file__).resolve().parent.parent
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    common = ["--steps", "4", "--warmup", "1", "--grid-n", "34", "--variant", "7", "--no-cpu-baseline", "--no-pmc", "--no-extras"]
+    common = ["--full", "--steps", "4", "--warmup", "1", "--grid-n", "34", "--variant", "7", "--no-cpu-baseline", "--no-pmc", "--no-extras"]
     t0 = time.time()
     try:
         two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
@@ -998,7 +998,7 @@ def test_two_rank_c3_bench_matches_single_rank(env):
         pytest.skip("torch did not come up in a child process on this box (see test_device_buffer_entry_point_with_torch)")
     root = Path(__file__).resolve().parent.parent
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    common = ["--workload", "c3", "--c3-n", "16", "--steps", "3", "--warmup", "1", "--no-pmc"]
+    common = ["--full", "--workload", "c3", "--c3-n", "16", "--steps", "3", "--warmup", "1", "--no-pmc"]
     try:
         one = subprocess.run([sys.executable, str(root / "bench.py")] + common, capture_output=True, text=True, timeout=600)
         assert one.returncode == 0, one.stderr[-2000:]
@@ -1017,6 +1017,42 @@ def test_two_rank_c3_bench_matches_single_rank(env):
     assert a["config"]["kernel_variant"] == 4 and b["config"]["kernel_variant"] == 4
     assert "cpu_baseline" not in a and "other_workloads" not in a          # the 176 GB configuration as the headline: nothing rides on it
     assert abs(a["checksum_sum_J"] - b["checksum_sum_J"]) <= 1e-12 * abs(a["checksum_sum_J"]) and a["checksum_sum_J"] > 0
+
+
+@pytest.mark.order(96)
+@pytest.mark.watchdog(700)
+def test_plain_bench_run_times_the_headline_and_dumps_its_outputs(env, tmp_path):
+    """`bench.py` without --full: the headline workload alone, ONE timed region of --steps stages, and with --dump-outputs the J and
+    labels of the last timed stage - here the whole 34^4 grid - equal to hjb_solve's after warm-up + steps stages, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    hjbdp, _abi, c_oracle = env
+    if _TORCH_COLD:
+        pytest.skip("torch did not come up in a child process on this box")
+    root = Path(__file__).resolve().parent.parent
+    try:
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--grid-n", "34",
+                            "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    except subprocess.TimeoutExpired:
+        _TORCH_COLD.append(1)
+        pytest.skip("a torch child process did not finish within 600 s on this box (cold image)")
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "bellman_backups_per_s" and line["steps"] == 3 and line["dtype"] == "f32" and line["higher_is_better"]
+    assert len(line["ms_per_step_reps"]) == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 34 ** 4 * 9 * 3 / (line["ms_per_step"] * 3e-3)) <= 1e-9 * line["value"]
+    for key in ("other_workloads", "cpu_baseline", "checksum_sum_J"):
+        assert key not in line, key
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["J.npy", "argmin.npy"]
+    J, lab = np.load(tmp_path / "J.npy"), np.load(tmp_path / "argmin.npy")
+    assert J.dtype == np.float32 and lab.dtype == np.float32 and J.shape == lab.shape == (34 ** 4,)
+    import bench
+    spec, _ = bench.build_spec("c4", n=34)
+    with hjbdp.Backup(spec) as bk:
+        assert bk.info()["kernel_variant"] == line["config"]["kernel_variant"]
+        out = bk.solve(5)
+    assert np.array_equal(J, out["J"]) and np.array_equal(lab, out["idx"].astype(np.float32))
 
 
 F16 = [((9, 8), (3,), False), ((13, 11, 9), (4, 5), True), ((6, 5, 4, 5), (3, 4), False), ((7, 6), (70,), True)]

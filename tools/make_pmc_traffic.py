@@ -30,7 +30,7 @@ _, kw = pick(write, "k_backup_packed2")
 _, ks = pick(sq, "k_backup_packed2")
 out = {
     "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_* GRBM_GUI_ACTIVE (separate passes, --kernel-trace), "
-              "python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline",
+              "python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline",
     "kernel": kname,
     "unit_note": "rocprofv3 reports FETCH_SIZE/WRITE_SIZE in KiB",
     "FETCH_SIZE_KiB_per_launch": kf["FETCH_SIZE"][0], "FETCH_SIZE_launches": kf["FETCH_SIZE"][1],
