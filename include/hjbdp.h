@@ -278,7 +278,12 @@ int32_t hjb_get_option(hjb_handle h, const char *key, int64_t *value);
  * J_next [j_elems] -> J_out [j_elems] (owned planes written), idx_out [n_states]. */
 int32_t hjb_backup_stage(hjb_handle h, const void *J_next, void *J_out, void *idx_out);
 /* ONE backup on device buffers, asynchronous on `stream` (a hipStream_t; NULL =
- * default stream).  For host-driven loops and multi-GPU halo exchange. */
+ * default stream).  For host-driven loops and multi-GPU halo exchange.
+ * Streams: one handle may have launches in flight on several streams at once (from its one host thread), also beside a
+ * hjb_solve on the handle's own stream; the caller owns the ordering of the buffers it passes.  The device state a launch
+ * writes is per stream: the claim counters of kernel 15's chunk walk are kept per stream for the first 8 streams a handle
+ * sees, and launches on further streams take the walk's static form (the same results).  The halo flag
+ * (hjb_check_device_status) is shared: a fault on any stream is reported by the next check on any of them. */
 int32_t hjb_backup_stage_device(hjb_handle h, const void *dJ_next, void *dJ_out,
                                 void *d_idx_out, void *stream);
 /* Non-zero if a previous device-side backup hit HJB_E_HALO (synchronises). */

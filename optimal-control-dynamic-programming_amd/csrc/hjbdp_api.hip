@@ -462,7 +462,7 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
             uniwin_tiles(h);
             HIP_TRY(h, hipSetDevice(h->device));
             HIP_TRY(h, hipDeviceSynchronize());
-            { DUniwin tmp = h->huw; if (!h->uw_claim) tmp.counters = nullptr; HIP_TRY(h, hipMemcpy(h->duw, &tmp, sizeof(DUniwin), hipMemcpyHostToDevice)); }
+            { const int ust = uniwin_upload(h); if (ust) return ust; }
             choose_launch(h);
         }
         if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }   // the captured launches carry the old LDS size
@@ -509,9 +509,7 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
         h->uw_claim = (int)value;
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipDeviceSynchronize());
-        DUniwin tmp = h->huw;
-        if (!h->uw_claim) tmp.counters = nullptr;
-        HIP_TRY(h, hipMemcpy(h->duw, &tmp, sizeof(DUniwin), hipMemcpyHostToDevice));
+        { const int ust = uniwin_upload(h); if (ust) return ust; }
         if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
         return HJB_OK;
     }
@@ -524,7 +522,7 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
         uniwin_tiles(h);
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipDeviceSynchronize());
-        { DUniwin tmp = h->huw; if (!h->uw_claim) tmp.counters = nullptr; HIP_TRY(h, hipMemcpy(h->duw, &tmp, sizeof(DUniwin), hipMemcpyHostToDevice)); }
+        { const int ust = uniwin_upload(h); if (ust) return ust; }
         choose_launch(h);
         return HJB_OK;
     }

@@ -45,6 +45,9 @@ namespace hjbhost {
 using namespace hjb;
 
 constexpr int kGraphStages = 32;   // even: a replay starts and ends in dJ[0]
+// K15's claim counters: one set per stream a handle launches on (the first kUwSets streams; later ones take the static walk)
+constexpr int kUwSets = 8;
+constexpr int kUwSetWords = 8 * 16;  // one set: per XCD one 64-byte line
 
 extern thread_local std::string g_last_error;
 // fault injection for the tests, by explicit call only (hjb_test_hook; the environment never changes what the library does)
@@ -114,8 +117,10 @@ struct Handle {
     int uw_claim = 1;             // option "uw_claim": 1 = the chunk walk's positions are claimed from per-XCD counters, 0 = fixed stride
     int uw_block = 256;           // option "uw_block": states per chunk = threads per workgroup (256 or 64)
     size_t uw_lds = 0;
-    DUniwin huw{};
-    DUniwin *duw = nullptr;
+    DUniwin huw{};                // huw.counters: the first of kUwSets counter sets (8 x one 64-byte line each)
+    DUniwin *duw = nullptr;       // kUwSets + 1 device copies of huw: copy k claims from counter set k, the last one walks statically
+    hipStream_t uw_streams[kUwSets] = {};    // the stream each counter set serves (launches on one stream are ordered)
+    int uw_nstreams = 0;
     bool tabled_ok = false;       // variant 5: per-axis (cell, t) tables for every axis (built on first use)
     bool tabled_i32 = false;      // ... and every index of it fits 31 bits: the 32-bit form of the kernel runs (kernels_tabled.h)
     bool tabled_i32_on = true;    // option "tabled_i32" (0: the 64-bit form anyway - A/B timing, tests)
@@ -196,6 +201,7 @@ int rebuild_tables(Handle *h, bool mfma);
 int table_hash(Handle *h, uint64_t *out);
 int ensure_colsweep(Handle *h);
 void uniwin_tiles(Handle *h);        // workgroup size, chunk count, tile extents, LDS and launch grid -> Handle (the caller uploads Handle::huw)
+int uniwin_upload(Handle *h);        // Handle::huw -> the kUwSets + 1 device copies (Handle::duw); the caller has synchronised the device
 inline bool uniwin_active(const Handle *h) {
     return h->uniwin_ok && (h->packed_pre == 5 || h->packed_pre == 6) && (h->uniwin_on == 1 || (h->uniwin_on < 0 && h->uniwin_auto));
 }

@@ -1504,9 +1504,15 @@ int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t 
         case 4:
             if (!f32) return fail(h, HJB_E_UNSUPPORTED, "variant 4 is float32 only");
             if (uniwin_active(h)) {                  // modes 7 / 8 (K15, kernels_uniwin.h)
-                a.duw = h->duw;
+                // the claim counters are per stream: two launches in flight on different streams never share (and re-zero) a set.
+                // A stream is given a set on its first launch (host bookkeeping only: nothing is allocated, also under capture)
+                int set = 0;
+                while (set < h->uw_nstreams && h->uw_streams[set] != st) ++set;
+                if (set == h->uw_nstreams && set < kUwSets) h->uw_streams[h->uw_nstreams++] = st;
+                a.duw = h->duw + set;                // (set kUwSets: the static walk)
                 a.block = (unsigned)h->huw.block;
-                if (h->huw.counters) HIP_TRY(h, hipMemsetAsync(h->huw.counters, 0, 8 * 16 * sizeof(uint32_t), st));   // (a memset node under capture)
+                if (h->uw_claim && set < kUwSets)    // (a memset node under capture)
+                    HIP_TRY(h, hipMemsetAsync(h->huw.counters + (size_t)kUwSetWords * set, 0, kUwSetWords * sizeof(uint32_t), st));
                 a.lds = h->uw_lds + h->lds_pad;
                 miss = stage_uniwin(a, h->hp.model != 0);
                 break;
@@ -1658,6 +1664,16 @@ void uniwin_tiles(Handle *h) {
     h->uw_grid = (int)std::max<int64_t>(8, g - (g & 7));
 }
 
+int uniwin_upload(Handle *h) {
+    DUniwin sets[kUwSets + 1];
+    for (int k = 0; k <= kUwSets; ++k) {
+        sets[k] = h->huw;
+        sets[k].counters = (h->uw_claim && k < kUwSets) ? h->huw.counters + (size_t)kUwSetWords * k : nullptr;
+    }
+    HIP_TRY(h, hipMemcpy(h->duw, sets, sizeof sets, hipMemcpyHostToDevice));
+    return HJB_OK;
+}
+
 static int setup_uniwin(Handle *h, const hjb_problem *p) {
     const DParams &P = h->hp;
     const DNested &N = h->hn;
@@ -1706,19 +1722,20 @@ static int setup_uniwin(Handle *h, const hjb_problem *p) {
     HIP_TRY(h, hipMemcpy(&n_slow, cnt, sizeof n_slow, hipMemcpyDeviceToHost));
     h->uniwin_slow = n_slow;
     U.plan = (const int32_t *)plan;
-    {   // the per-XCD claim counters of the chunk walk (kernels_uniwin.h): 8 x one 64-byte line, zeroed before every launch
+    {   // the per-XCD claim counters of the chunk walk (kernels_uniwin.h): 8 x one 64-byte line per stream, zeroed before every launch
         void *ctr = nullptr;
-        st = dev_alloc(h, 8 * 16 * sizeof(uint32_t), &ctr);
+        st = dev_alloc(h, (size_t)kUwSets * kUwSetWords * sizeof(uint32_t), &ctr);
         if (st) return st;
-        HIP_TRY(h, hipMemset(ctr, 0, 8 * 16 * sizeof(uint32_t)));
+        HIP_TRY(h, hipMemset(ctr, 0, (size_t)kUwSets * kUwSetWords * sizeof(uint32_t)));
         U.counters = (uint32_t *)ctr;
     }
     uniwin_tiles(h);
     void *du = nullptr;
-    st = dev_alloc(h, sizeof(DUniwin), &du);
+    st = dev_alloc(h, (kUwSets + 1) * sizeof(DUniwin), &du);
     if (st) return st;
     h->duw = (DUniwin *)du;
-    HIP_TRY(h, hipMemcpy(h->duw, &U, sizeof U, hipMemcpyHostToDevice));
+    st = uniwin_upload(h);
+    if (st) return st;
     h->uniwin_ok = true;
     h->uniwin_auto = (int64_t)n_slow * 50 <= n_points;     // at most 2 % of the points on the slow path
     return HJB_OK;

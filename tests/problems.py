@@ -187,3 +187,28 @@ def rate_shared_problem(seed, n_so, n_rates, m=(11, 11, 11), gain=(0.55, 0.5, 0.
     for c in range(3):
         cost.append(Term((D + c,), 0.25 * np.round(rng.uniform(0, 3, m[c])) ** 2))
     return ProblemSpec(knots, list(m), nxt, cost, dtype=dtype, index_base=index_base, j_storage=j_storage)
+
+
+def pos_att_channel_spec(cost_mode="f64", n=120, j_storage=None, channel="x"):
+    """Solver_pos_att's channel on n^4 states exactly as bench.build_spec("c4") builds it (axes FAST_AXIS_ORDER =
+    (x, theta, w, v), float64-built query tables, uint8 labels) but with the stage cost typed by `cost_mode`: 'f64' is the
+    reference's own single(double sum) (Solver_pos_att.m:800-801, the mirror's default), 'terms' the bench's float32 terms.
+    channel: 'x', 'z' or 'failure' (the x channel with thruster 0 failed, Solver_pos_att.m:236-240).  j_storage=np.float16:
+    binary16 cost-to-go storage (C5)."""
+    import hjbdp
+    pa = hjbdp.Solver_pos_att()
+    pa.cost_mode = cost_mode
+    pa.n_mesh_x = pa.n_mesh_v = pa.n_mesh_t = pa.n_mesh_w = n
+    sx, sv, st, sw = pa.grids()
+    args = {"x": (st[0], pa.F_Thr0, pa.F_Thr1, pa.F_Thr6, pa.F_Thr7, pa.Qx1, pa.Qv1, pa.Qt1, pa.Qw1, pa.R1, pa.J2),
+            "z": (st[2], pa.F_Thr4, pa.F_Thr5, pa.F_Thr10, pa.F_Thr11, pa.Qx3, pa.Qv3, pa.Qt3, pa.Qw3, pa.R3, pa.J1),
+            "failure": (st[0], [0.0], pa.F_Thr1, pa.F_Thr6, pa.F_Thr7, pa.Qx1, pa.Qv1, pa.Qt1, pa.Qw1, pa.R1, pa.J2)}[channel]
+    spec, _ = pa.build_channel_spec(sx, sv, args[0], sw, *args[1:])
+    spec, _ = hjbdp.permute_state_axes(spec, hjbdp.Solver_pos_att.FAST_AXIS_ORDER)
+    if j_storage is not None:
+        spec = hjbdp.ProblemSpec(spec.knots, spec.m, spec.next_terms, spec.cost_terms, dtype=np.float32, index_base=1,
+                                 j_storage=j_storage, idx_dtype=spec.idx_dtype, table_dtype=spec.table_dtype,
+                                 cost_dtype=spec.cost_dtype)
+    assert spec.table_dtype == np.float64 and spec.idx_np_dtype == np.uint8
+    assert (spec.cost_dtype == np.float64) == (cost_mode == "f64")
+    return spec

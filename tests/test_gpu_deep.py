@@ -67,10 +67,12 @@ def test_c2_100_stages_deep(env):
     assert np.all(Js[:, :-1] >= Js[:, 1:] - 1e-5)               # J_k never decreases as the horizon grows
 
 
-def _c4_deep(env, workload, N, period):
+def _c4_deep(env, workload, N, period, spec=None):
+    """`spec`: a ready spec of `workload`'s shape (default: bench.build_spec(workload), the float32-terms typing)."""
     hjbdp, _abi, c_oracle = env
-    import bench
-    spec, _ = bench.build_spec(workload)
+    if spec is None:
+        import bench
+        spec, _ = bench.build_spec(workload)
     assert spec.n == (120,) * 4 and spec.nU == 9
     assert spec.table_dtype == np.float64 and spec.idx_np_dtype == np.uint8           # the bench's exact typing
     assert spec.j_dtype == (np.float16 if workload == "c5" else np.float32)
@@ -135,6 +137,29 @@ def test_c4_200_stages_deep_bench_typing(env):
     """BASELINE configs[3] exactly as bench.py runs it (float64-built query tables, uint8 labels, axes (x, theta, w, v)),
     200 stages with the reference's monitor."""
     full = _c4_deep(env, "c4", 200, 50)
+    assert float(np.min(full["J"])) >= 0.0 and np.all(np.isfinite(full["J"]))
+
+
+@pytest.mark.order(3)
+@pytest.mark.watchdog(900)
+def test_c4_200_stages_deep_reference_typing(env):
+    """C4 in the reference's own cost typing, single(double sum) (Solver_pos_att.m:800-801; cost_mode 'f64', the mirror's and
+    hjbdp_solve.m's default): otherwise bench.py's spec (120^4, axes (x, theta, w, v), float64-built query tables, uint8
+    labels).  The column-sweep kernel's float64-cost instantiation at full size: 200 stages with the reference's monitor,
+    planes of the last two stages and of a mid-sweep pair against the oracle, the monitor events and the stop decision."""
+    hjbdp, _abi, c_oracle = env
+    from problems import pos_att_channel_spec
+    spec = pos_att_channel_spec("f64")
+    n3 = 120 ** 3
+    with hjbdp.Backup(spec) as bk:
+        inf = bk.info()
+        assert inf["cost_dtype"] == _abi.HJB_COST_F64 and inf["kernel_variant"] == 7
+        first = bk.solve(1)["J"].reshape(n3, 120, order="F")[:, 0].copy()
+    with hjbdp.Backup(pos_att_channel_spec("terms")) as bk:
+        assert bk.info()["cost_dtype"] != _abi.HJB_COST_F64
+        first_terms = bk.solve(1)["J"].reshape(n3, 120, order="F")[:, 0].copy()
+    assert not np.array_equal(first, first_terms)            # the typing matters at this size: this is not the terms test again
+    full = _c4_deep(env, "c4", 200, 50, spec=spec)
     assert float(np.min(full["J"])) >= 0.0 and np.all(np.isfinite(full["J"]))
 
 

@@ -389,6 +389,42 @@ def test_solver_pos_att_all_channels_with_monitor(env, grid):
 
 
 @pytest.mark.order(7)
+def test_solver_pos_att_reference_run_stop_stages_default_vs_reference_order(env):
+    """simplified_run exactly as the reference runs it (Solver_pos_att.m:197-285: N_stage - 1 = 1,999 stages, monitor every 50
+    stages, |e| < 1e-2 on a single-precision sum) by default (axis_order "auto": the lerps in (x, theta, w, v) order) and in the
+    reference's own axis order, both with the reference's typing (cost_mode 'f64').  The stop test is nearly a test of bit-exact
+    convergence, so the two orders could stop at different stages: per channel the stop stage and the early-stop flag must
+    agree.  Channels x, y, z: J to 1e-4 of max J, labels on at least 99.9 % of the states.  The thruster-failure channel's
+    sweep diverges at the extrapolating corner (J reaches about -1.6e9 by stage 1,999, in either order and in the oracle's),
+    so there the lerp order's rounding is amplified without bound: it is held to the stop stage and to that divergence."""
+    hjbdp, _abi, c_oracle = env
+    runs = {}
+    for order in ("auto", None):
+        pa = hjbdp.Solver_pos_att()
+        assert pa.cost_mode == "f64" and pa.monitor_single and pa.axis_order == "auto"
+        assert (pa.monitor_period, pa.monitor_tol) == (50, 1e-2) and pa.N_stage - 1 == 1999
+        pa.axis_order = order
+        pa.simplified_run()
+        runs[order] = pa.controllers
+    assert set(runs["auto"]) == set(runs[None]) and len(runs["auto"]) == 4
+    stops = {}
+    for name in sorted(runs["auto"]):
+        a, r = runs["auto"][name], runs[None][name]
+        stops[name] = (a["stages_done"], a["stopped_early"], r["stages_done"], r["stopped_early"])
+        assert a["stages_done"] == r["stages_done"] and a["stopped_early"] == r["stopped_early"], (name, stops[name])
+        Ja, Jr = a["F_gI_Values"].astype(np.float64), r["F_gI_Values"].astype(np.float64)
+        assert np.all(np.isfinite(Ja)) and np.all(np.isfinite(Jr)), name
+        if name.endswith("_failure"):
+            assert Ja.min() < -1e6 and Jr.min() < -1e6, (name, Ja.min(), Jr.min())
+            continue
+        assert Jr.min() >= 0.0, name
+        assert np.max(np.abs(Ja - Jr)) <= 1e-4 * np.max(np.abs(Jr)), (name, np.max(np.abs(Ja - Jr)) / np.max(np.abs(Jr)))
+        assert np.mean(a["U_Optimal_id"] == r["U_Optimal_id"]) >= 0.999, (name, np.mean(a["U_Optimal_id"] == r["U_Optimal_id"]))
+    # on the reference's own run no channel stops early: all four sweep the full 1,999 stages in both orders
+    assert all(v == (1999, False, 1999, False) for v in stops.values()), stops
+
+
+@pytest.mark.order(7)
 def test_dynamic_solver_default_config_runs(env):
     """C1b: the committed constructor defaults (100x100x1000, N=200, single)."""
     hjbdp, _abi, c_oracle = env
@@ -508,6 +544,135 @@ def test_c4_bench_order_as_eight_slabs_full_size(env):
     assert [i["end"] - i["begin"] for i in infos] == [15] * 8 and all(i["split"] for i in infos)
     assert infos[3]["halo_lo"] == 1 and infos[3]["halo_hi"] == 1
     assert np.array_equal(multi["J"], whole["J"]) and np.array_equal(multi["idx"], whole["idx"])
+
+
+def _pos_att_terminal(spec_n=120):
+    """A smooth terminal cost on the 120^4 grid in the (x, theta, w, v) labelling, [120^3, 120] (v last)."""
+    import hjbdp
+    pa = hjbdp.Solver_pos_att()
+    pa.n_mesh_x = pa.n_mesh_v = pa.n_mesh_t = pa.n_mesh_w = spec_n
+    sx, sv, st, sw = pa.grids()
+    X, T, W = np.meshgrid(sx, st[0], sw, indexing="ij")
+    inner = (np.sin(7 * X) + 10.0 * W ** 2 + np.cos(5 * T)).astype(np.float32).reshape(-1, order="F")
+    return (inner[:, None] * (1.0 + 3.0 * sv[None, :] ** 2).astype(np.float32)).astype(np.float32)
+
+
+def _planes_vs_oracle(c_oracle, _abi, spec, J_prev, J, idx, planes):
+    """Planes of the last axis of one stage (J, idx) recomputed by the oracle from the stage before (J_prev), halo one plane."""
+    nl = spec.n[-1]
+    inner = spec.nS // nl
+    Jp, Jc, ic = (np.asarray(a).reshape(inner, nl, order="F") for a in (J_prev, J, idx))
+    for p in planes:
+        lo, hi = min(1, p), min(1, nl - 1 - p)
+        sub = np.asfortranarray(Jp[:, p - lo:p + 1 + hi]).reshape(-1, order="F")
+        Jo, io = c_oracle.backup_stage(_abi, spec, sub, slab=(p, p + 1, lo, hi))
+        assert np.array_equal(Jo.reshape(inner, -1, order="F")[:, lo], Jc[:, p]), ("J", p)
+        assert np.array_equal(io, ic[:, p]), ("labels", p)
+
+
+@pytest.mark.order(4)
+@pytest.mark.watchdog(600)
+def test_c4_reference_typing_every_part_count_full_size(env):
+    """The float64-cost column sweep at 120^4 (C4 in the reference's typing, the spec bench.py builds but cost_mode 'f64'),
+    columns swept in 1, 2, 3, 8, 20 parts and the automatic count, each with and without the DPP neighbour exchange: two
+    stages from a smooth terminal cost.  The first form's planes (both edges and the interior) of both stages equal the
+    oracle's; every other form equals it bit for bit on the whole grid - so every form's planes equal the oracle's too."""
+    hjbdp, _abi, c_oracle = env
+    from problems import pos_att_channel_spec
+    spec = pos_att_channel_spec("f64")
+    term = _pos_att_terminal().reshape(-1, order="F")
+    base, forms = None, []
+    with hjbdp.Backup(spec) as bk:
+        inf = bk.info()
+        assert inf["cost_dtype"] == _abi.HJB_COST_F64 and inf["kernel_variant"] == 7
+        for dpp in (1, 0):
+            for split in (1, 2, 3, 8, 20, 0):
+                bk.set_option("cs_dpp", dpp)
+                bk.set_option("cs_split", split)
+                assert bk.info()["kernel_variant"] == 7
+                got_dpp = bk.get_option("cs_dpp")                 # (1 only where the host check admits the exchange)
+                assert got_dpp <= dpp
+                got = bk.get_option("cs_split")
+                assert got == split if split else got >= 1
+                forms.append((got_dpp, split, got))
+                out = bk.solve(2, terminal=term, keep_J=True, keep_idx=True)
+                if base is None:
+                    base = out
+                    _planes_vs_oracle(c_oracle, _abi, spec, term, out["J_stages"][:, 1], out["idx_stages"][:, 1], (0, 61, 119))
+                    _planes_vs_oracle(c_oracle, _abi, spec, out["J_stages"][:, 1], out["J_stages"][:, 0], out["idx_stages"][:, 0],
+                                      (0, 61, 119))
+                else:
+                    for k in (0, 1):
+                        bad = np.flatnonzero(out["J_stages"][:, k] != base["J_stages"][:, k])
+                        assert bad.size == 0, (dpp, split, got, k, "J", bad[:8])
+                        bad = np.flatnonzero(out["idx_stages"][:, k] != base["idx_stages"][:, k])
+                        assert bad.size == 0, (dpp, split, got, k, "labels", bad[:8])
+                del out
+    assert len({f[2] for f in forms}) >= 5, forms
+    print("\n[c4 f64 part counts] (cs_dpp, cs_split asked, in effect):", forms)
+
+
+@pytest.mark.order(4)
+@pytest.mark.watchdog(600)
+def test_c5_reference_typing_full_size_planes_vs_oracle(env):
+    """float16 cost-to-go storage with the float64 cost at 120^4 (the column sweep's c64_f16 instantiation): two stages, planes
+    of both (edges, interior) against the oracle's binary16 stages."""
+    hjbdp, _abi, c_oracle = env
+    from problems import pos_att_channel_spec
+    spec = pos_att_channel_spec("f64", j_storage=np.float16)
+    assert spec.j_dtype == np.float16
+    term = _pos_att_terminal().astype(np.float16).reshape(-1, order="F")
+    with hjbdp.Backup(spec) as bk:
+        inf = bk.info()
+        assert inf["cost_dtype"] == _abi.HJB_COST_F64 and inf["kernel_variant"] == 7
+        out = bk.solve(2, terminal=term, keep_J=True, keep_idx=True)
+    assert out["J_stages"].dtype == np.float16
+    _planes_vs_oracle(c_oracle, _abi, spec, term, out["J_stages"][:, 1], out["idx_stages"][:, 1], (0, 64, 119))
+    _planes_vs_oracle(c_oracle, _abi, spec, out["J_stages"][:, 1], out["J_stages"][:, 0], out["idx_stages"][:, 0], (0, 64, 119))
+
+
+@pytest.mark.order(4)
+@pytest.mark.watchdog(600)
+def test_c4_reference_typing_as_eight_slabs_full_size(env):
+    """test_c4_bench_order_as_eight_slabs_full_size in the reference's typing (float64 cost): hjb_solve_multi with eight
+    slabs of 15 planes on the one GPU equals the whole-grid sweep bit for bit over two stages."""
+    hjbdp, _abi, c_oracle = env
+    from problems import pos_att_channel_spec
+    spec = pos_att_channel_spec("f64")
+    term = _pos_att_terminal().reshape(-1, order="F")
+    with hjbdp.Backup(spec) as bk:
+        need = bk.info()
+        assert need["cost_dtype"] == _abi.HJB_COST_F64 and need["kernel_variant"] == 7
+        assert need["halo_needed_lo"] == 1 and need["halo_needed_hi"] == 1
+        whole = bk.solve(2, terminal=term)
+    with hjbdp.MultiBackup(spec, [0] * 8) as mb:
+        infos = [mb.slab_info(i) for i in range(8)]
+        multi = mb.solve(2, terminal=term)
+    assert [i["end"] - i["begin"] for i in infos] == [15] * 8 and all(i["split"] for i in infos)
+    assert np.array_equal(multi["J"], whole["J"]) and np.array_equal(multi["idx"], whole["idx"])
+
+
+@pytest.mark.order(4)
+@pytest.mark.watchdog(600)
+def test_pos_att_reference_typing_batch_full_size(env):
+    """hjb_solve_batch at 120^4 in the reference's typing: the x, z and thruster-failure channels (one group axis: ONE launch
+    per stage, the batch's own column cut) over two stages; each equals its own hjb_solve bit for bit."""
+    hjbdp, _abi, c_oracle = env
+    from problems import pos_att_channel_spec
+    specs = [pos_att_channel_spec("f64", channel=c) for c in ("x", "z", "failure")]
+    outs, _, variants, groups = hjbdp.solve_batch(specs, 2)
+    assert variants == [7, 7, 7] and sorted(groups) == [3], (variants, groups)
+    for c, spec, o in zip(("x", "z", "failure"), specs, outs):
+        with hjbdp.Backup(spec) as bk:
+            assert bk.info()["cost_dtype"] == _abi.HJB_COST_F64
+            alone = bk.solve(2)
+        assert o["stages_done"] == 2
+        bad = np.flatnonzero(o["J"] != alone["J"])
+        assert bad.size == 0, (c, "J", bad[:8])
+        bad = np.flatnonzero(o["idx"] != alone["idx"])
+        assert bad.size == 0, (c, "labels", bad[:8])
+        del alone
+    outs.clear()
 
 
 def test_solver_position_closed_loop_rollout(env):

@@ -135,6 +135,30 @@ def test_slab_oracle_matches_whole_grid(orc):
     assert np.array_equal(io, iw.reshape(72, 12, order="F")[:, b:e].reshape(-1, order="F"))
 
 
+@pytest.mark.parametrize("j_storage", [None, np.float16])
+def test_slab_oracle_matches_whole_grid_f64_cost_f64_tables(orc, j_storage):
+    """The plane check of the full-size GPU tests in the reference's typing (cost_dtype float64 together with table_dtype
+    float64): the oracle's slab backup (slab + halos) equals its whole-grid backup on those planes, edges included, and the
+    float64 cost typing is not the float32-terms one."""
+    _abi, c_oracle, hjb_oracle = orc
+    from problems import pos_att_channel_spec
+    spec = pos_att_channel_spec("f64", n=12, j_storage=j_storage)
+    terms = pos_att_channel_spec("terms", n=12, j_storage=j_storage)
+    nl, inner = spec.n[-1], spec.nS // spec.n[-1]
+    term = (random_terminal(spec, 4) * 50.0).astype(spec.j_dtype)
+    Jw, iw = c_oracle.backup_stage(_abi, spec, term)
+    Jt, _ = c_oracle.backup_stage(_abi, terms, term)
+    if j_storage is None:
+        assert not np.array_equal(Jw, Jt)                          # the typing matters on this problem (binary16 storage hides it)
+    T = term.reshape(inner, nl, order="F")
+    W, I = Jw.reshape(inner, nl, order="F"), iw.reshape(inner, nl, order="F")
+    for b, e, lo, hi in ((0, 1, 0, 1), (5, 7, 1, 1), (11, 12, 1, 0), (3, 9, 2, 3)):
+        Jin = np.asfortranarray(T[:, b - lo:e + hi]).reshape(-1, order="F")
+        Jo, io = c_oracle.backup_stage(_abi, spec, Jin, slab=(b, e, lo, hi))
+        assert np.array_equal(Jo.reshape(inner, -1, order="F")[:, lo:lo + e - b], W[:, b:e]), (b, e)
+        assert np.array_equal(io, I[:, b:e].reshape(-1, order="F")), (b, e)
+
+
 @pytest.mark.parametrize("case", ["random3d", "random4d_f16", "kirk", "rows_of_5", "one_axis", "slab", "tab64_4d", "tab64_slab_f16"])
 def test_avx2_twin_equals_scalar_twin(orc, golden, case):
     """The row-vectorised C twin (bench.py's faster CPU baseline) performs the scalar twin's
