@@ -330,7 +330,9 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *handles, const hjb_solve_op
  * u_star(:,:,k) / J (Dynamic_Solver.m:132-135).  values: [n_1..n_D] column-major, dtype;
  * queries: [D x nq] column-major (point i = queries[D*i .. D*i+D-1]), dtype; out: [nq] dtype.
  * method HJB_LOOKUP_LINEAR: N-linear with linear extrapolation (same arithmetic as the sweep);
- * HJB_LOOKUP_NEAREST: per axis the nearer knot of the enclosing cell, the upper one at the midpoint. */
+ * HJB_LOOKUP_NEAREST: per axis the nearer knot of the enclosing cell, the upper one at the midpoint.  Knots and
+ * queries are rounded to dtype and every comparison is made in dtype; knots that are not strictly increasing after
+ * that rounding are HJB_E_INVALID (decided before any device work). */
 #define HJB_LOOKUP_NEAREST 0
 #define HJB_LOOKUP_LINEAR 1
 int32_t hjb_policy_lookup(int32_t device, int32_t dtype, int32_t D, const int32_t *n, const double *const *knots,

@@ -17,16 +17,7 @@ int policy_lookup_t(int32_t D, const int32_t *n, const double *const *knots, con
     for (int a = 0; a < D; ++a) {
         std::vector<T> kk(n[a]), rdx(n[a]);
         for (int i = 0; i < n[a]; ++i) kk[i] = (T)knots[a][i];
-        for (int i = 0; i + 1 < n[a]; ++i) {
-            if (!(kk[i + 1] > kk[i])) {
-                for (void *d : h->allocs) (void)hipFree(d);      // the axes uploaded so far
-                h->allocs.clear();
-                h->arena_left = 0;
-                g_last_error = "lookup: knots not strictly increasing";
-                return HJB_E_INVALID;
-            }
-            rdx[i] = (T)1 / (T)(kk[i + 1] - kk[i]);
-        }
+        for (int i = 0; i + 1 < n[a]; ++i) rdx[i] = (T)1 / (T)(kk[i + 1] - kk[i]);     // increasing: hjb_policy_lookup checked
         rdx[n[a] - 1] = (T)0;
         void *dk = nullptr, *dr = nullptr;
         int st = upload(h, kk, &dk);
@@ -868,8 +859,13 @@ int32_t hjb_policy_lookup(int32_t device, int32_t dtype, int32_t D, const int32_
     if (dtype != HJB_F32 && dtype != HJB_F64) return fail(nullptr, HJB_E_UNSUPPORTED, "dtype %d", dtype);
     if (method != HJB_LOOKUP_NEAREST && method != HJB_LOOKUP_LINEAR) return fail(nullptr, HJB_E_INVALID, "method %d", method);
     if (nq < 0) return fail(nullptr, HJB_E_INVALID, "nq < 0");
-    for (int a = 0; a < D; ++a)
+    for (int a = 0; a < D; ++a) {
         if (n[a] < 2 || !knots[a]) return fail(nullptr, HJB_E_INVALID, "axis %d: need >= 2 knots", a);
+        for (int i = 0; i + 1 < n[a]; ++i) {      // strictly increasing in the arithmetic type (float32 may merge close knots)
+            const bool up = dtype == HJB_F32 ? (float)knots[a][i + 1] > (float)knots[a][i] : knots[a][i + 1] > knots[a][i];
+            if (!up) return fail(nullptr, HJB_E_INVALID, "lookup: knots of axis %d not strictly increasing in the value type (at %d)", a, i);
+        }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         return fail(nullptr, HJB_E_DEVICE, "no HIP device visible (libhjbdp has no CPU fallback)");

@@ -1,7 +1,10 @@
 // kernels_lookup.h - K5: batched policy / value lookup on a grid.
 // One thread per query point.  'linear' uses the sweep's canonical interpolation
 // (exact cell search, t = (q-k[c])*rdx[c], fma lerps axis 0 first); 'nearest' picks,
-// per axis, the nearer knot of the enclosing cell (upper knot at the midpoint).
+// per axis, the nearer knot of the enclosing cell (upper knot at the midpoint).  Knots,
+// queries and the distances are all in T: with T = float a query near a midpoint can pick
+// the other knot than the host's float64 rule (matlab_compat.interp_nearest_point) would,
+// so NearestPolicy.lookup_many calls the T = double form whatever its values' type.
 #pragma once
 #include "hjbdp_dev.h"
 #include "kernels_generic.h"

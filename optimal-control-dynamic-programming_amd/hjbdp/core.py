@@ -74,7 +74,9 @@ def _check(lib, handle, st):
 
 def policy_lookup(knots, values, points, method="nearest", device=0):
     """Batched griddedInterpolant(knots, values, method) at `points` [nq, D] on the GPU
-    (hjb_policy_lookup).  values.dtype (float32/float64) is the arithmetic type."""
+    (hjb_policy_lookup).  values.dtype (float32/float64) is the arithmetic type: with float32 the knots and the
+    points are rounded to float32 and 'nearest' compares the distances in float32 (NearestPolicy.lookup_many does
+    not: it follows the host's float64 rule)."""
     lib = load_library()
     values = np.asarray(values)
     dt = values.dtype if values.dtype in (np.float32, np.float64) else np.dtype(np.float64)

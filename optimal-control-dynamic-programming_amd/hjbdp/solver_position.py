@@ -32,9 +32,13 @@ class NearestPolicy:
         return interp_nearest_point(self.GridVectors, self.Values, x)
 
     def lookup_many(self, points, device=0):
-        """Batched evaluation at points [nq, D] on the GPU (hjb_policy_lookup, 'nearest')."""
+        """Batched evaluation at points [nq, D] on the GPU (hjb_policy_lookup, 'nearest'), equal to __call__ at every
+        point: the knot is chosen in float64 as the host does (a float32 lookup rounds the query and the knots first
+        and can pick the other knot near a midpoint); the values come back in their own type."""
         from .core import policy_lookup
-        return policy_lookup(self.GridVectors, self.Values, points, "nearest", device=device)
+        V = np.asarray(self.Values)
+        out = policy_lookup(self.GridVectors, V.astype(np.float64), np.asarray(points, dtype=np.float64), "nearest", device=device)
+        return out.astype(V.dtype) if V.dtype == np.float32 else out
 
 
 class Solver_position:

@@ -489,3 +489,37 @@ def test_rccl_declarations_come_from_the_images_own_header():
     assert re.search(r"\bncclUint8\s*=\s*1\b", h) and re.search(r"\bncclFloat64\s*=\s*8\b", h) and re.search(r"\bncclSum\s*=\s*0\b", h)
     pub = (ROOT / "include" / "hjbdp.h").read_text()
     assert "128 bytes" in pub and "hjb_rank_comm_unique_id(void *id128_out)" in pub
+
+
+def test_policy_lookup_checks_its_arguments_before_any_device_work(lib):
+    """hjb_policy_lookup (include/hjbdp.h): D outside 1..6 and a dtype other than HJB_F32 / HJB_F64 are HJB_E_UNSUPPORTED;
+    an unknown method, a one-knot axis and knots that are not strictly increasing once rounded to the value type are
+    HJB_E_INVALID - decided without a device.  The same knots are fine in float64 (then only the device is missing here)."""
+    import hjbdp
+    from hjbdp import _abi
+    keep = []
+
+    def call(dtype, knots, method=_abi.HJB_LOOKUP_NEAREST, D=None):
+        D = len(knots) if D is None else D
+        ks = [np.ascontiguousarray(k, dtype=np.float64) for k in knots] or [np.zeros(2)]
+        keep.append(ks)
+        n = (C.c_int32 * max(len(ks), 7))(*[len(k) for k in ks])
+        kp = (C.POINTER(C.c_double) * max(len(ks), 7))(*[k.ctypes.data_as(C.POINTER(C.c_double)) for k in ks])
+        V, Q, out = np.zeros(4096), np.zeros(64), np.zeros(8)
+        return lib.hjb_policy_lookup(0, dtype, D, n, kp, V.ctypes.data, 1, Q.ctypes.data, method, out.ctypes.data)
+    k2 = np.array([0.0, 1.0])
+    assert call(_abi.HJB_F64, [k2], D=0) == _abi.HJB_E_UNSUPPORTED
+    assert call(_abi.HJB_F64, [k2] * 7) == _abi.HJB_E_UNSUPPORTED
+    assert call(_abi.HJB_F32, [k2] * 7) == _abi.HJB_E_UNSUPPORTED
+    for dtype in (_abi.HJB_F16S, 7, -1):
+        assert call(dtype, [k2]) == _abi.HJB_E_UNSUPPORTED, dtype
+    for method in (2, -1):
+        assert call(_abi.HJB_F32, [k2], method=method) == _abi.HJB_E_INVALID, method
+    assert call(_abi.HJB_F64, [k2, np.array([0.5])]) == _abi.HJB_E_INVALID
+    assert b"knots" in lib.hjb_last_error(None)
+    assert call(_abi.HJB_F64, [np.array([0.0, 1.0, 1.0])]) == _abi.HJB_E_INVALID
+    assert call(_abi.HJB_F64, [np.array([0.0, 2.0, 1.0])], method=_abi.HJB_LOOKUP_LINEAR) == _abi.HJB_E_INVALID
+    merge32 = np.array([0.0, 1.0, 1.0 + 1e-9])                  # distinct in float64, equal once rounded to float32
+    assert call(_abi.HJB_F32, [k2, merge32]) == _abi.HJB_E_INVALID
+    assert b"not strictly increasing" in lib.hjb_last_error(None)
+    assert call(_abi.HJB_F64, [k2, merge32]) == (_abi.HJB_OK if hjbdp.device_count() > 0 else _abi.HJB_E_DEVICE)

@@ -411,3 +411,57 @@ def test_oracle_float64_cost_equals_the_materialised_single_of_double_sum(orc):
     Je, i_e = c_oracle.backup_stage(_abi, specs["exact"], term)
     assert np.array_equal(Js.view(np.uint32), Jv.view(np.uint32)) and np.array_equal(i_s, i_v)
     assert np.array_equal(Js.view(np.uint32), Je.view(np.uint32)) and np.array_equal(i_s, i_e)
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+@pytest.mark.parametrize("D", [1, 2, 3, 4, 5, 6])
+def test_lookup_twin_every_D_against_float64_references(orc, D, dt):
+    """The lookup checker (the twin's orc_lookup) at every D the GPU lookup is built for, in both types, before the GPU
+    is held to it (tests/test_gpu_aux_kernels.py): 'linear' = scipy's RegularGridInterpolator with linear extrapolation
+    to linear_tol, 'nearest' = the float64 nearest-knot rule away from midpoints; on a dyadic grid the midpoint takes the
+    UPPER knot and an affine V is extended exactly in float64."""
+    from float64_refs import linear_ref, linear_tol, nearest_ref
+    _abi, c_oracle, hjb_oracle = orc
+    rng = np.random.default_rng(D)
+    sizes = [2, 5, 3, 7, 4, 6][:D]
+    knots = [(np.cumsum(rng.uniform(0.3, 1.7, n)) - 1.0).astype(dt).astype(np.float64) for n in sizes]
+    V = rng.standard_normal(tuple(sizes)).astype(dt)
+    lo, hi = np.array([k[0] for k in knots]), np.array([k[-1] for k in knots])
+    pts = (lo + (hi - lo) * rng.uniform(-3.0, 4.0, size=(4000, D))).astype(dt)
+    lin = c_oracle.lookup(_abi, knots, V, pts, "linear")
+    ref, w = linear_ref(knots, V, pts)
+    assert np.all(np.abs(lin - ref) <= linear_tol(dt, D, np.max(np.abs(V)), w))
+    near = c_oracle.lookup(_abi, knots, V, pts, "nearest")
+    refn, near_mid = nearest_ref(knots, V, pts)
+    assert near_mid.mean() < 0.05 and np.array_equal(near[~near_mid], refn[~near_mid])
+    # dyadic knots (cells 2^-10 and 1): exact midpoints, exact affine extension
+    dy = [np.array([-1.0, -1.0 + 2 ** -10, -1.0 + 2 ** -9, 2 ** -9, 1.0 + 2 ** -9][: 2 + a % 4]) for a in range(D)]
+    G = np.meshgrid(*dy, indexing="ij")
+    Va = (0.5 + sum((a + 1) * 0.25 * G[a] for a in range(D))).astype(dt)
+    mid = np.array([[0.5 * (k[0] + k[1]) for k in dy]])
+    up = Va[tuple(1 for _ in range(D))]
+    assert c_oracle.lookup(_abi, dy, Va, mid.astype(dt), "nearest")[0] == up
+    far = np.array([[k[0] - 10 * (k[1] - k[0]) for k in dy], [k[-1] + 25 * (k[-1] - k[-2]) for k in dy]])
+    aff = 0.5 + sum((a + 1) * 0.25 * far[:, a] for a in range(D))
+    got = c_oracle.lookup(_abi, dy, Va, far.astype(dt), "linear")
+    if dt == np.float64:
+        assert np.array_equal(got, aff)
+    else:
+        assert np.all(np.abs(got - aff) <= linear_tol(dt, D, np.max(np.abs(Va)), linear_ref(dy, Va, far)[1]))
+
+
+def test_float64_references_of_the_aux_kernel_tests():
+    """tests/float64_refs.py itself: the ordered sum rounds after every add (not once at the end), the separable fill
+    is column-major with axis 0 fastest, a term's block follows its dims, and nearest_ref flags near-midpoints."""
+    from hjbdp import Term
+    from float64_refs import nearest_ref, ordered_sum, separable_ref, term_block
+    a = [np.float32(1.0), np.float32(2.0 ** -24), np.float32(2.0 ** -24)]
+    assert ordered_sum(a, np.float32) == np.float32(1.0)                   # (1 + 2^-24) + 2^-24 rounds to 1 twice
+    assert np.float32(np.float64(1.0) + 2.0 ** -23) != ordered_sum(a, np.float32)
+    v = [np.array([0.0, 1.0]), np.array([0.0, 10.0, 20.0])]
+    assert np.array_equal(separable_ref(v, np.float64, np.float64), [0, 1, 10, 11, 20, 21])
+    t = Term((1, 3), np.arange(12.0).reshape(3, 4))                        # state dim 1 (3 points) x control dim 1 of C = 2
+    b = term_block(t, 2, (0, 1), (2, 3), (0, 2), np.float64)
+    assert b.shape == (2, 2) and np.array_equal(b, [[6.0, 10.0], [6.0, 10.0]])
+    vals, flag = nearest_ref([np.array([0.0, 1.0])], np.array([5.0, 7.0]), np.array([[0.5], [0.5 - 1e-17], [0.25], [0.75]]))
+    assert np.array_equal(vals, [7.0, 7.0, 5.0, 7.0]) and np.array_equal(flag, [True, True, False, False])
