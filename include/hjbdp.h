@@ -342,6 +342,34 @@ int32_t hjb_policy_lookup(int32_t device, int32_t dtype, int32_t D, const int32_
  * plane each (g [B], x_next [B, D], j_interp [B]).  J_next may be NULL when j_interp is NULL. */
 int32_t hjb_probe_stage(hjb_handle h, const void *J_next, const hjb_probe *probe);
 
+/* ---- batched closed-loop rollouts of a stored policy (test/Dynamic_Solver.m:108-181 get_optimal_path, 'Nssu' and 'ssu') ----
+ * A rollout object holds a per-stage policy on one device: the grid (D <= 6 axes, knots concatenated axis 0 first), the
+ * labels of n_planes stages ([nS, n_planes] column-major in HJB_IDX_I32 / _U8 / _U16: hjb_solve's idx_stages layout) and the
+ * control table u_table [n_labels, n_u] (column-major, n_u <= HJB_ROLLOUT_MAX_U).  Every label must lie in
+ * [index_base, index_base + n_labels); the whole array is checked in hjb_rollout_create before any device work.
+ * hjb_rollout_set_model gives the fixed-step affine closed loop x+ = A x + B u + c with stage cost x'diag(q)x + u'diag(r)u
+ * (A [D, D], B [D, n_u] column-major; c, q, r may be NULL: no offset, zero weights).  hjb_rollout_run steps n_traj
+ * trajectories n_steps times, one GPU thread each, all in double:
+ *   p = plane_of_step[k];  u_j = policy lookup of u_table[labels[:, p] - index_base, j] at x (HJB_LOOKUP_NEAREST / _LINEAR:
+ *       bit-identical to hjb_policy_lookup in double on those dense values);
+ *   cost += ((q0*(x0*x0) + q1*(x1*x1)) + ...) + r0*(u0*u0) + ...;
+ *   x+_a = ((A[a,0]*x0 + A[a,1]*x1) + ...) + B[a,0]*u0 + ... + c_a   (left to right, each product rounded).
+ * X0, X_final: [D, n_traj]; X_path [n_traj, D, n_steps+1] and U_path [n_traj, n_u, n_steps] (NULL: not kept); device_ms: the
+ * kernels' time.  Option "chunk" (default 1 << 20): trajectories per launch, which bounds the device memory of a run.
+ * One call at a time per object; different objects may run from different threads.  The handle is spelled void * (no typedef).
+ * hjb_rollout_last_error(NULL): the text of the calling thread's last failure (create's refusals). */
+#define HJB_ROLLOUT_MAX_U 4
+int32_t hjb_rollout_create(int32_t device, int32_t D, const int32_t *n, const double *knots, int32_t idx_dtype,
+                           int32_t index_base, int32_t n_planes, const void *labels, int32_t n_labels, int32_t n_u,
+                           const double *u_table, void **rollout_out);
+int32_t hjb_rollout_set_model(void *rollout, const double *A, const double *B, const double *c, const double *q,
+                              const double *r);
+int32_t hjb_rollout_set_option(void *rollout, const char *key, int64_t value);
+int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                        const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *device_ms);
+int32_t hjb_rollout_destroy(void *rollout);
+const char *hjb_rollout_last_error(void *rollout);
+
 /* ---- flat builder API -------------------------------------------------------------------------------------------
  * hjb_problem holds arrays of structs with pointers, which MATLAB's loadlibrary/calllib cannot marshal.  These entry
  * points take primitives and plain arrays only, copy what they are given (the caller may free it at once), and end in

@@ -81,4 +81,17 @@ int32_t hjb_device_copy(int32_t device, void *dst, const void *src, int64_t byte
 /* griddedInterpolant(..., 'nearest' | 'linear') lookups of the results (Solver_position.m:144-146, Dynamic_Solver.m:132-135) */
 int32_t hjb_policy_lookup(int32_t device, int32_t dtype, int32_t D, const int32_t *n, const double *const *knots,
                           const void *values, int64_t nq, const void *queries, int32_t method, void *out);
+
+/* batched closed-loop rollouts of the stored per-stage policy (test/Dynamic_Solver.m:108-181, get_optimal_path 'Nssu' / 'ssu');
+ * usage: matlab/Dynamic_Solver_hjbdp_get_optimal_paths.m */
+int32_t hjb_rollout_create(int32_t device, int32_t D, const int32_t *n, const double *knots, int32_t idx_dtype,
+                           int32_t index_base, int32_t n_planes, const void *labels, int32_t n_labels, int32_t n_u,
+                           const double *u_table, void **rollout_out);
+int32_t hjb_rollout_set_model(void *rollout, const double *A, const double *B, const double *c, const double *q,
+                              const double *r);
+int32_t hjb_rollout_set_option(void *rollout, const char *key, int64_t value);
+int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                        const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *device_ms);
+int32_t hjb_rollout_destroy(void *rollout);
+const char *hjb_rollout_last_error(void *rollout);
 #endif

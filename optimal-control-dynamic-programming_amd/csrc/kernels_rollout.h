@@ -1,0 +1,169 @@
+// kernels_rollout.h - K16: batched fixed-step closed-loop rollouts of a stored per-stage policy (hjb_rollout_*).
+//
+// One thread per trajectory; all n_steps steps run inside one launch (trajectories are independent).  Per step k:
+//   p = plane_of_step[k]; locate the cell on every axis (find_cell, exact); read the label(s) of plane p;
+//   u_j = u_table[L - index_base, j] at the nearer knot ('nearest': upper one at the midpoint, k_policy_lookup's rule)
+//         or the N-linear interpolation of u_table[label, j] over the 2^D corners ('linear': k_policy_lookup's arithmetic,
+//         fma lerps axis 0 first, pairwise);
+//   g = ((q0*(x0*x0) + q1*(x1*x1)) + ...) + r0*(u0*u0) + ...;  cost += g;
+//   x+_a = ((A[a,0]*x0 + A[a,1]*x1) + ...) + B[a,0]*u0 + ... + c_a   (every product rounded: -ffp-contract=off).
+// Everything is double.  The pairwise lerp tree is evaluated DEPTH-FIRST: corner c is a leaf, and after it the tree nodes it
+// completes (one per trailing 1-bit of c) are folded into a stack of D + 1 partials - the same operations on the same operands
+// as the breadth-first loop of k_policy_lookup, so the result is bit-identical to hjb_policy_lookup on the dense values
+// u_table[labels[:, p] - base, j], without 2^D x n_u doubles live (D = 6: 64 labels + 7 partials).
+// Knots, 1/dx and u_table are staged in LDS when they fit (LDS = true; hjb_rollout_run decides), else read from global memory.
+// Labels stay in global memory (nS x n_planes: one plane of a reference-sized grid is L2-resident).  Labels were range-checked by
+// hjb_rollout_create, so no read leaves u_table.  Offsets are int64 throughout; stores are plain, trajectory index fastest.
+#pragma once
+#include "hjbdp_dev.h"
+#include "kernels_generic.h"
+
+namespace hjb {
+
+struct DRollout {
+    int32_t n_u, n_labels, index_base, n_steps;
+    int32_t n_knots;                  // sum of n[a]: knots / rdx are concatenated, axis a at koff[a]
+    int32_t has_c;
+    int32_t n[HJB_MAX_D];
+    int32_t koff[HJB_MAX_D];
+    int32_t uniform[HJB_MAX_D];       // find_cell's arithmetic first guess (exact either way)
+    double x0[HJB_MAX_D], inv_h[HJB_MAX_D];
+    int64_t stride[HJB_MAX_D];        // state strides, axis 0 fastest
+    int64_t nS;                       // states per plane of the label array
+    const double *knots, *rdx;        // [n_knots] each (global)
+    const double *u_table;            // [n_labels, n_u] column-major (global)
+    const void *labels;               // [nS, n_planes] column-major, TL
+    const int32_t *plane_of_step;     // [n_steps]
+    double A[HJB_MAX_D * HJB_MAX_D];  // [D, D] column-major
+    double B[HJB_MAX_D * HJB_ROLLOUT_MAX_U];   // [D, n_u] column-major
+    double c[HJB_MAX_D], q[HJB_MAX_D], r[HJB_ROLLOUT_MAX_U];   // NULL on the host side = zeros (q, r) / no addition (c)
+};
+
+// number of trailing 1-bits of c: the tree nodes corner c completes
+__device__ __forceinline__ constexpr int trailing_ones(int c) { return (c & 1) ? 1 + trailing_ones(c >> 1) : 0; }
+
+template <int D, typename TL, int METHOD, bool LDS>
+__global__ void __launch_bounds__(256)
+k_rollout(const DRollout R, int64_t nc, const double *__restrict__ X0, double *__restrict__ Xf, double *__restrict__ cost,
+          double *__restrict__ Xp, double *__restrict__ Up) {
+    extern __shared__ double smem[];
+    const double *kn, *rd, *ut;
+    if constexpr (LDS) {
+        const int nk = R.n_knots, nut = R.n_labels * R.n_u;
+        for (int e = threadIdx.x; e < nk; e += blockDim.x) {
+            smem[e] = R.knots[e];
+            smem[nk + e] = R.rdx[e];
+        }
+        for (int e = threadIdx.x; e < nut; e += blockDim.x) smem[2 * nk + e] = R.u_table[e];
+        __syncthreads();
+        kn = smem;
+        rd = smem + nk;
+        ut = smem + 2 * nk;
+    } else {
+        kn = R.knots;
+        rd = R.rdx;
+        ut = R.u_table;
+    }
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= nc) return;
+    const TL *__restrict__ lab = static_cast<const TL *>(R.labels);
+    const int nu = R.n_u;
+    const int64_t nl = R.n_labels;
+    double x[D];
+#pragma unroll
+    for (int a = 0; a < D; ++a) x[a] = X0[a + (int64_t)D * i];
+    if (Xp) {
+#pragma unroll
+        for (int a = 0; a < D; ++a) Xp[i + nc * a] = x[a];
+    }
+    double J = 0.0;
+    for (int k = 0; k < R.n_steps; ++k) {
+        int64_t base = (int64_t)R.plane_of_step[k] * R.nS;
+        double tw[D];
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            const double *kk = kn + R.koff[a];
+            int cell = find_cell<double>(kk, R.n[a], x[a], R.uniform[a], R.x0[a], R.inv_h[a]);
+            if (METHOD == HJB_LOOKUP_NEAREST) {
+                if ((double)(x[a] - kk[cell]) >= (double)(kk[cell + 1] - x[a])) ++cell;
+                tw[a] = 0.0;
+            } else {
+                tw[a] = (double)((double)(x[a] - kk[cell]) * rd[R.koff[a] + cell]);
+            }
+            base += R.stride[a] * cell;
+        }
+        double u[HJB_ROLLOUT_MAX_U];
+        if (METHOD == HJB_LOOKUP_NEAREST) {
+            const int64_t L = (int64_t)lab[base] - R.index_base;
+#pragma unroll
+            for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j) {
+                u[j] = 0.0;
+                if (j < nu) u[j] = ut[L + nl * j];
+            }
+        } else {
+            int32_t L[1 << D];
+#pragma unroll
+            for (int c = 0; c < (1 << D); ++c) {     // every corner label in flight before the first is used
+                int64_t off = base;
+#pragma unroll
+                for (int a = 0; a < D; ++a)
+                    if (c & (1 << a)) off += R.stride[a];
+                L[c] = (int32_t)lab[off];
+            }
+#pragma unroll
+            for (int c = 0; c < (1 << D); ++c) L[c] -= R.index_base;
+#pragma unroll
+            for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j) {
+                u[j] = 0.0;
+                if (j < nu) {
+                    double s[D + 1];
+#pragma unroll
+                    for (int c = 0; c < (1 << D); ++c) {
+                        double v = ut[L[c] + nl * j];
+                        const int t1 = trailing_ones(c);
+#pragma unroll
+                        for (int a = 0; a < D; ++a)
+                            if (a < t1) v = fma_t<double>(tw[a], (double)(v - s[a]), s[a]);
+                        s[t1] = v;
+                    }
+                    u[j] = s[D];
+                }
+            }
+        }
+        double g = R.q[0] * (x[0] * x[0]);
+#pragma unroll
+        for (int a = 1; a < D; ++a) g = g + R.q[a] * (x[a] * x[a]);
+#pragma unroll
+        for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j)
+            if (j < nu) g = g + R.r[j] * (u[j] * u[j]);
+        J = J + g;
+        double xn[D];
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            double acc = R.A[a] * x[0];
+#pragma unroll
+            for (int b = 1; b < D; ++b) acc = acc + R.A[a + D * b] * x[b];
+#pragma unroll
+            for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j)
+                if (j < nu) acc = acc + R.B[a + D * j] * u[j];
+            if (R.has_c) acc = acc + R.c[a];
+            xn[a] = acc;
+        }
+        if (Up) {
+#pragma unroll
+            for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j)
+                if (j < nu) Up[i + nc * (j + (int64_t)nu * k)] = u[j];
+        }
+#pragma unroll
+        for (int a = 0; a < D; ++a) x[a] = xn[a];
+        if (Xp) {
+#pragma unroll
+            for (int a = 0; a < D; ++a) Xp[i + nc * (a + (int64_t)D * (k + 1))] = x[a];
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < D; ++a) Xf[a + (int64_t)D * i] = x[a];
+    if (cost) cost[i] = J;
+}
+
+}  // namespace hjb

@@ -213,7 +213,18 @@ SYMBOLS = {
     "hjb_rank_check_status": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "hjb_rank_destroy": (C.c_int32, [C.c_void_p]),
     "hjb_rank_last_error": (C.c_char_p, [C.c_void_p]),
+    # batched closed-loop rollouts of a stored policy
+    "hjb_rollout_create": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_void_p)]),
+    "hjb_rollout_set_model": (C.c_int32, [C.c_void_p] + [C.POINTER(C.c_double)] * 5),
+    "hjb_rollout_set_option": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_int64]),
+    "hjb_rollout_run": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double)]),
+    "hjb_rollout_destroy": (C.c_int32, [C.c_void_p]),
+    "hjb_rollout_last_error": (C.c_char_p, [C.c_void_p]),
 }
+HJB_ROLLOUT_MAX_U = 4
 HJB_LOOKUP_NEAREST = 0
 HJB_LOOKUP_LINEAR = 1
 

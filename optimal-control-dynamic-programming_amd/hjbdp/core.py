@@ -95,6 +95,121 @@ def policy_lookup(knots, values, points, method="nearest", device=0):
     return out
 
 
+_IDX_OF_DTYPE = {np.dtype(np.uint8): _abi.HJB_IDX_U8, np.dtype(np.uint16): _abi.HJB_IDX_U16, np.dtype(np.int32): _abi.HJB_IDX_I32}
+
+
+def _f64p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+class Rollout:
+    """A stored per-stage policy resident on one GPU, for batched fixed-step closed-loop rollouts (hjb_rollout_*):
+
+        with Rollout(knots, labels, u_table, index_base=1) as ro:
+            ro.set_model(A, B, c=None, q=None, r=None)
+            out = ro.run(X0, plane_of_step, method="linear", keep_path=False)
+
+    knots: D grid vectors.  labels: the argmin labels of n_planes stages, nS states each, column-major (hjb_solve's
+    idx_stages, e.g. [n_1, .., n_D, n_planes] or [nS, n_planes]) in uint8, uint16 or int32.  u_table: [n_labels, n_u] (n_u <= 4)
+    controls per label.  Step k of a trajectory looks plane plane_of_step[k] up at x ('nearest' / 'linear', bit-identical to
+    policy_lookup in float64 on the dense values u_table[labels[:, p] - index_base]), adds the stage cost
+    x'diag(q)x + u'diag(r)u and steps x <- A x + B u + c.  X0: [D, n_traj].  run returns X_final [D, n_traj], cost [n_traj],
+    X_path [n_traj, D, n_steps+1] and U_path [n_traj, n_u, n_steps] (None unless keep_path) and device_ms."""
+
+    def __init__(self, knots, labels, u_table, index_base=1, device=0):
+        self.lib = load_library()
+        self._ro = C.c_void_p()
+        ks = [np.ascontiguousarray(k, dtype=np.float64).reshape(-1) for k in knots]
+        self.D = len(ks)
+        self.n = [len(k) for k in ks]
+        nS = int(np.prod(self.n, dtype=np.int64)) if ks else 1
+        lab = np.asarray(labels)
+        if lab.dtype not in _IDX_OF_DTYPE:
+            if lab.dtype.kind not in "iu":
+                raise TypeError("labels must be integers (uint8, uint16 or int32), got %s" % lab.dtype)
+            if lab.size and (lab.min() < np.iinfo(np.int32).min or lab.max() > np.iinfo(np.int32).max):
+                raise ValueError("labels do not fit int32")
+            lab = lab.astype(np.int32)
+        lab = np.ascontiguousarray(lab.reshape(-1, order="F"))
+        if nS < 1 or lab.size % nS or lab.size == 0:
+            raise ValueError("labels: %d elements are not a whole number of %d-state planes" % (lab.size, nS))
+        self.n_planes = lab.size // nS
+        ut = np.asarray(u_table, dtype=np.float64)
+        ut = ut.reshape(-1, 1) if ut.ndim == 1 else ut
+        self.n_labels, self.n_u = ut.shape
+        ut = np.ascontiguousarray(ut.reshape(-1, order="F"))
+        kcat = np.ascontiguousarray(np.concatenate(ks) if ks else np.zeros(0))
+        n = (C.c_int32 * max(self.D, 1))(*self.n)
+        self._keep = (kcat, lab, ut)
+        st = self.lib.hjb_rollout_create(int(device), self.D, n, _f64p(kcat), _IDX_OF_DTYPE[lab.dtype], int(index_base),
+                                         int(self.n_planes), lab.ctypes.data, int(self.n_labels), int(self.n_u), _f64p(ut),
+                                         C.byref(self._ro))
+        self._keep = None
+        if st != _abi.HJB_OK:
+            self._ro = C.c_void_p()
+            self._raise(st)
+        self.device = int(device)
+
+    def _raise(self, st):
+        msg = self.lib.hjb_rollout_last_error(self._ro if self._ro.value else None)
+        raise HjbError(st, (msg or b"").decode() or self.lib.hjb_status_string(st).decode())
+
+    def _check(self, st):
+        if st != _abi.HJB_OK:
+            self._raise(st)
+
+    def close(self):
+        if getattr(self, "_ro", None) and self._ro.value:
+            self.lib.hjb_rollout_destroy(self._ro)
+            self._ro = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_option(self, key, value):
+        self._check(self.lib.hjb_rollout_set_option(self._ro, key.encode(), int(value)))
+
+    def set_model(self, A, B, c=None, q=None, r=None):
+        D, nu = self.D, self.n_u
+        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64).reshape(D, D).reshape(-1, order="F"))
+        B = np.ascontiguousarray(np.asarray(B, dtype=np.float64).reshape(D, nu).reshape(-1, order="F"))
+        vec = lambda v, m: None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(m))
+        c, q, r = vec(c, D), vec(q, D), vec(r, nu)
+        self._check(self.lib.hjb_rollout_set_model(self._ro, _f64p(A), _f64p(B), _f64p(c), _f64p(q), _f64p(r)))
+
+    def run(self, X0, plane_of_step, method="linear", keep_path=False):
+        D, nu = self.D, self.n_u
+        X = np.asarray(X0, dtype=np.float64)
+        X = np.ascontiguousarray((X.reshape(D, 1) if X.ndim == 1 else X).reshape(D, -1).T)     # [n_traj, D] = [D, n_traj] column-major
+        nt = X.shape[0]
+        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
+        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
+            raise ValueError("plane_of_step does not fit int32")
+        ps = ps.astype(np.int32)
+        K = int(ps.size)
+        meth = {"nearest": _abi.HJB_LOOKUP_NEAREST, "linear": _abi.HJB_LOOKUP_LINEAR}[method]
+        Xf = np.empty((nt, D))
+        cost = np.empty(nt)
+        Xp = np.empty(nt * D * (K + 1)) if keep_path else None
+        Up = np.empty(nt * nu * K) if keep_path else None
+        ms = C.c_double(0.0)
+        self._check(self.lib.hjb_rollout_run(self._ro, meth, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X), _f64p(Xf),
+                                             _f64p(cost), _f64p(Xp), _f64p(Up), C.byref(ms)))
+        return {"X_final": Xf.T, "cost": cost,
+                "X_path": None if Xp is None else Xp.reshape((nt, D, K + 1), order="F"),
+                "U_path": None if Up is None else Up.reshape((nt, nu, K), order="F"),
+                "device_ms": ms.value}
+
+
 class DeviceBuffer:
     """A device allocation owned through the library (hjb_device_malloc): what a host without a HIP binding of its
     own hands to Backup.backup_stage_device.  `ptr` is an ordinary HIP device pointer."""

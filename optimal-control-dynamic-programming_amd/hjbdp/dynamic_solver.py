@@ -52,6 +52,7 @@ class Dynamic_Solver:
         self.sweep_ms = None
         self.X_path = None
         self.U_path = None
+        self.u_star_idxs = None
 
     # ------------------------------------------------------------------
     def build_spec(self):
@@ -112,6 +113,7 @@ class Dynamic_Solver:
         idx = out["idx_stages"].reshape((self.dx, self.dx, n_st), order="F")  # 1-based
         self.u_star[:, :, : n_st] = U_mesh[idx - 1].astype(dt)               # u_star(:,:,k_s) = U_mesh(u_star_idx)
         self.u_star_idx = idx[:, :, 0].copy()      # value left in obj.u_star_idx after the loop (k_s = 1)
+        self.u_star_idxs = idx                     # every stage's labels, [dx, dx, N-1] (:100)
         self.F_values = self.J_star[:, :, 0].copy()
         return self
 
@@ -144,6 +146,38 @@ class Dynamic_Solver:
             self.ssu_tol = float(np.sum(np.sum(USTAR_OPT - USM, axis=0) ** 2))
             self.ssu_err_first = abs(interp_linear_point(knots, USTAR_OPT, X[:, 0]) -
                                      interp_linear_point(knots, USM, X[:, 0]))
+        return X, U
+
+    def get_optimal_paths(self, X0s, mode="Nssu", ssu_num=1, method="linear"):
+        """get_optimal_path (Dynamic_Solver.m:108-181) for many initial states at once, on the GPU (hjbdp.Rollout): X0s [S, n]
+        (one initial state per column).  Returns X [S, N, n] and U [N, n] (U[N-1] = 0, as get_optimal_path leaves it); the
+        closed-loop costs sum_k x'Qx + R u^2 over the N-1 steps are left in self.paths_cost [n].  The policy of stage k_s is
+        U_mesh(u_star_idxs(:,:,k_s)) in the problem's precision, looked up in double on the double grid vectors, as
+        get_optimal_path does; mode 'ssu' freezes stage ssu_num (1..N-1)."""
+        from .core import Rollout
+        if self.u_star_idxs is None:
+            raise RuntimeError("run() first")
+        N, S = self.N, self.S
+        n_st = N - 1
+        if mode == "ssu":
+            if not 1 <= int(ssu_num) <= n_st:
+                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
+            planes = np.full(n_st, int(ssu_num) - 1, dtype=np.int32)
+        elif mode == "Nssu":
+            planes = np.arange(n_st, dtype=np.int32)
+        else:
+            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        X0s = np.asarray(X0s, dtype=np.float64)
+        X0s = X0s.reshape(S, -1)
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
+        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
+            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+            out = ro.run(X0s, planes, method=method, keep_path=True)
+        X = np.ascontiguousarray(out["X_path"].transpose(1, 2, 0))     # [n, S, N] -> [S, N, n]
+        U = np.zeros((N, X0s.shape[1]))
+        U[:n_st] = out["U_path"][:, 0, :].T
+        self.paths_cost = out["cost"]
         return X, U
 
     @staticmethod

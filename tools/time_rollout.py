@@ -1,0 +1,118 @@
+"""Throughput of the batched closed-loop rollout (hjb_rollout_run, csrc/kernels_rollout.h) against the host's scalar loop.
+
+Two cases, one JSON line:
+  (a) kirk:    the fixture problem (Dynamic_Solver, double, 35 x 35 states, 100 controls, N = 130: 129 planes), 'linear',
+               'Nssu', 10^6 initial states; host rate: Dynamic_Solver.get_optimal_path over 100 of them.
+  (b) pos_att: the reference's pos-att x channel (30 x 30 x 20 x 15 states, 9 thruster combinations x 4 thruster outputs, uint8
+               labels) swept over 1,999 stages, rolled out 'nearest' for 1,999 steps on its affine design model
+               (x+ = x + h v, v+ = v + h/M sum f, theta+ = theta + h w, w+ = w + h d/J (f1 - f2 + f3 - f4)) from 2.7 * 10^5
+               initial states; host rate: the same loop scalar in Python (interp_nearest_point + the update) over 100 of them.
+Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT / "optimal-control-dynamic-programming_amd"))
+
+
+def _timed(ro, X0, planes, method):
+    ro.run(X0, planes, method)                      # warm-up, same shape
+    out = ro.run(X0, planes, method)
+    nt, K = X0.shape[1], len(planes)
+    return out, {"n_traj": int(nt), "n_steps": int(K), "device_ms": round(out["device_ms"], 3),
+                 "traj_steps_per_s": nt * K / (out["device_ms"] * 1e-3)}
+
+
+def case_kirk(host=True, n_traj=1000000):
+    import hjbdp
+    ds = hjbdp.Dynamic_Solver(precision="double")
+    ds.N, ds.dx, ds.du = 130, 35, 100
+    ds.run()
+    s_r = np.asarray(ds.s_r, dtype=np.float64)
+    rng = np.random.default_rng(1)
+    X0 = rng.uniform(s_r[0], s_r[-1], size=(2, n_traj))
+    planes = np.arange(ds.N - 1)
+    with hjbdp.Rollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro:
+        ro.set_model(ds.A, ds.B, q=np.diag(ds.Q), r=[ds.R])
+        _, res = _timed(ro, X0, planes, "linear")
+    res.update(grid="35x35", planes=int(ds.N - 1), method="linear", labels="int32")
+    if host:
+        t0 = time.perf_counter()
+        for i in range(100):
+            ds.get_optimal_path(X0[:, i])
+        dt = time.perf_counter() - t0
+        res["host_traj_steps_per_s"] = 100 * (ds.N - 1) / dt
+        res["speedup_vs_host"] = res["traj_steps_per_s"] / res["host_traj_steps_per_s"]
+    return res
+
+
+def case_pos_att(host=True, n_traj=270000, n_stages=1999):
+    import hjbdp
+    from hjbdp.matlab_compat import interp_nearest_point
+    pa = hjbdp.Solver_pos_att()
+    sx, sv, st, sw = pa.grids()
+    spec, combos = pa.build_channel_spec(sx, sv, st[0], sw, pa.F_Thr0, pa.F_Thr1, pa.F_Thr6, pa.F_Thr7,
+                                         pa.Qx1, pa.Qv1, pa.Qt1, pa.Qw1, pa.R1, pa.J2)
+    t0 = time.perf_counter()
+    with hjbdp.Backup(spec, device=0) as bk:
+        out = bk.solve(n_stages, keep_idx=True)
+    sweep_s = time.perf_counter() - t0
+    labels = out["idx_stages"]
+    u_table = np.stack(combos, axis=1)                                       # [9, 4]: thruster levels per combination
+    h, d, M, J = pa.h, pa.T_dist, pa.Mass, pa.J2
+    A = np.array([[1, h, 0, 0], [0, 1, 0, 0], [0, 0, 1, h], [0, 0, 0, 1]], dtype=np.float64)
+    B = np.array([[0, 0, 0, 0], [h / M] * 4, [0, 0, 0, 0], [h * d / J, -h * d / J, h * d / J, -h * d / J]])
+    q = [pa.Qx1, pa.Qv1, pa.Qt1, pa.Qw1]
+    r = [pa.R1] * 4
+    knots = [sx, sv, st[0], sw]
+    rng = np.random.default_rng(2)
+    X0 = np.stack([rng.uniform(k[0], k[-1], n_traj) for k in knots])
+    planes = np.arange(n_stages)
+    with hjbdp.Rollout(knots, labels, u_table, index_base=1) as ro:
+        ro.set_model(A, B, q=q, r=r)
+        _, res = _timed(ro, X0, planes, "nearest")
+    res.update(grid="30x30x20x15", planes=int(n_stages), method="nearest", labels=str(labels.dtype), n_labels=int(u_table.shape[0]),
+               n_u=4, sweep_wall_s=round(sweep_s, 3))
+    if host:
+        nS = int(np.prod([len(k) for k in knots]))
+        lab = labels.reshape(nS, -1, order="F")
+        shape = tuple(len(k) for k in knots)
+        t0 = time.perf_counter()
+        for i in range(100):
+            x = X0[:, i].copy()
+            for k in planes:
+                li = interp_nearest_point(knots, lab[:, k].reshape(shape, order="F"), x)
+                u = u_table[int(li) - 1]
+                x = A @ x + B @ u
+        dt = time.perf_counter() - t0
+        res["host_loop"] = "Python scalar loop: interp_nearest_point + A x + B u"
+        res["host_traj_steps_per_s"] = 100 * n_stages / dt
+        res["speedup_vs_host"] = res["traj_steps_per_s"] / res["host_traj_steps_per_s"]
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--cases", default="kirk,pos_att")
+    a = ap.parse_args()
+    import hjbdp
+    if hjbdp.device_count() < 1:
+        raise SystemExit("time_rollout needs a HIP device")
+    res = {"tool": "time_rollout"}
+    for c in a.cases.split(","):
+        res[c] = {"kirk": case_kirk, "pos_att": case_pos_att}[c](host=not a.no_host)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
