@@ -250,16 +250,10 @@ int32_t hjb_create(const hjb_problem *p, int32_t device, hjb_handle *out) {
     }
     for (int k = 0; k < HJB_MAX_TERMS; ++k) h->prob.cost_terms[k].data = nullptr;
     choose_launch(h);
-    const bool tab64_bad = h->tab64 && (h->launch_status != HJB_OK || h->variant < 5);
-    const bool cost64_bad = h->cost64 && (h->launch_status != HJB_OK || (h->variant != 5 && h->variant != 7));
-    if (tab64_bad || cost64_bad) {
-        // the caller asked for float64 queries / a float64 stage cost: a handle that cannot serve them is not handed out
-        st = h->launch_status != HJB_OK ? h->launch_status : HJB_E_UNSUPPORTED;
-        if (h->err.empty()) {
-            if (tab64_bad) (void)fail(h, st, "table_dtype HJB_TAB_F64: the (cell, t) tables could not be built; table_dtype = HJB_TAB_DEFAULT (Python: table_dtype=None) runs float32 queries");
-            else (void)fail(h, st, "cost_dtype HJB_COST_F64: the tables of the kernels that serve it (5, 7) could not be built (status %d); cost_dtype = HJB_COST_DEFAULT sums the cost terms in float32", h->launch_status);
-        }
-        g_last_error = h->err;
+    if (h->L.status != HJB_OK) {
+        // float64 queries / a float64 stage cost whose tables could not be built: the handle is not handed out (the build said why)
+        st = fail(h, h->L.status, "%s: the tables of kernel variant %d could not be built: %s", h->tab64 ? "table_dtype HJB_TAB_F64"
+                  : "cost_dtype HJB_COST_F64", h->L.variant, h->err.c_str());
         if (h->gexec) (void)hipGraphExecDestroy(h->gexec);
         for (void *d : h->allocs) (void)hipFree(d);
         delete h;
@@ -288,12 +282,10 @@ int32_t hjb_get_info(hjb_handle hh, hjb_info *info) {
     info->n_states = h->n_owned;
     info->n_controls = h->nU;
     info->j_elems = h->j_elems;
-    info->kernel_variant = h->variant;
-    info->lds_bytes = h->variant == 4 ? (int32_t)(uniwin_active(h) ? h->uw_lds : h->packed2_lds) : h->variant == 2 ? (int32_t)h->packed_lds
-                      : (h->variant == 1 ? (int32_t)h->nested_lds
-                      : (h->variant == 3 && h->split_j_in_lds ? (int32_t)(h->j_elems * h->esz) : 0));
-    info->block = h->block;
-    info->grid = h->grid;
+    info->kernel_variant = h->L.variant;
+    info->lds_bytes = (int32_t)h->L.lds;
+    info->block = h->L.block;
+    info->grid = h->L.grid;
     info->halo_needed_lo = h->halo_need_lo;
     info->halo_needed_hi = h->halo_need_hi;
     info->idx_bytes = h->idx_bytes;
@@ -320,148 +312,64 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
     }
     if (!strcmp(key, "variant")) {
         if (value < -1 || value > 7) return fail(h, HJB_E_INVALID, "variant %lld unknown", (long long)value);
-        if (value == 7) {
-            const int cst = ensure_colsweep(h);
-            if (cst) return cst;
-            if (h->cs_state != 1)
-                return fail(h, HJB_E_UNSUPPORTED, "variant 7 (column sweep) needs D = 4, one control dim, float32 arithmetic, axes 0/1 "
-                            "independent of the control (and of each other's state dim), axes 2/3 depending on state dims 2, 3 and the "
-                            "control only, control terms of the cost involving the control only, and <= %d groups of corner rows per (i2, i3)", kCsGMax);
-        }
-        if (value == 6 && !h->row_ok)
-            return fail(h, HJB_E_UNSUPPORTED, "variant 6 (one wave per grid row) needs D >= 2, per-axis tables that fit, and "
-                        "no axis other than axis 0 depending on state dim 0");
-        if (h->dtype == HJB_F16S && value >= 1 && value <= 3)
-            return fail(h, HJB_E_UNSUPPORTED, "variant %lld does not support float16 J storage (use 0, 4, 5 or 6)", (long long)value);
-        if (h->tab64 && value >= 0 && value <= 4)
-            return fail(h, HJB_E_UNSUPPORTED, "variant %lld evaluates the next-state terms in the kernel, in float32; a problem with "
-                        "table_dtype HJB_TAB_F64 runs on the table-driven kernels (5, 6, 7)", (long long)value);
-        if (h->cost64 && value >= 0 && value != 5 && value != 7)
-            return fail(h, HJB_E_UNSUPPORTED, "variant %lld sums the stage cost in float32; a problem with cost_dtype HJB_COST_F64 runs on "
-                        "the tabled kernel (5) or the column sweep (7)", (long long)value);
-        if (h->hp.model && value != -1 && value != 4)
-            return fail(h, HJB_E_UNSUPPORTED, "a problem with a state model runs on variant 4 only");
-        if (value == 5 && !h->tabled_ok)
-            return fail(h, HJB_E_UNSUPPORTED, "variant 5 (tabled) needs per-axis tables that fit (see hjbdp.hip)");
-        if (value == 4 && !h->packed_mode)
-            return fail(h, HJB_E_UNSUPPORTED, "variant 4 (packed, control pairs) needs float32 and the canonical spacecraft structure");
-        if (value == 2 && h->packed_mode != 1)
-            return fail(h, HJB_E_UNSUPPORTED, "variant 2 (packed) needs float32 and the canonical spacecraft structure (see kernels_packed.h)");
-        if (value == 2) { const int ast = ensure_axis0_table(h); if (ast) return ast; }     // variant 2 reads every axis from its table
-        if (value == 1 && !h->nested_ok)
-            return fail(h, HJB_E_UNSUPPORTED, "variant 1 (control-nested) needs: only the last state axis depends on the innermost control dim");
+        const char *why = nullptr;
+        const int st = value < 0 ? HJB_OK : variant_status(h, (int)value, &why);
+        if (st) return fail(h, st, "variant %lld: %s", (long long)value, why);
         h->forced_variant = (int)value;
         choose_launch(h);
-        if (value >= 0 && h->variant != (int)value) {      // e.g. the tables of a forced variant 5/6 could not be built
-            const int lst = h->launch_status != HJB_OK ? h->launch_status : HJB_E_UNSUPPORTED;
-            h->forced_variant = -1;
-            choose_launch(h);
-            return fail(h, lst, "variant %lld could not be set up (%s); the automatic choice is in effect", (long long)value,
-                        h->err.empty() ? "not applicable" : h->err.c_str());
-        }
         return HJB_OK;
     }
     if (!strcmp(key, "prep_mfma")) {       // rebuild every (cell, weight) table: 1 = MFMA outer-sum form where it applies
-        if (h->variant == 5 || h->variant == 6 || h->variant == 7) { const int tst = ensure_tabled(h); if (tst) return tst; }
         HIP_TRY(h, hipSetDevice(h->device));
-        const int rst = rebuild_tables(h, value != 0);
-        if (rst) return rst;
-        if (h->cs_state == 1) {            // variant 7's plan is derived from the tables: same bits, nothing to redo
-        }
-        return HJB_OK;
+        return rebuild_tables(h, value != 0);      // (variant 7's plan is derived from the tables: same bits, nothing to redo)
     }
-    if (!strcmp(key, "cs_dpp")) {                                    // 0: variant 7 loads both axis-0 neighbours (testing)
-        h->cs_dpp = value != 0;
+    if (!strcmp(key, "cs_dpp") || !strcmp(key, "cs_split") || !strcmp(key, "cs_coop") || !strcmp(key, "cs_xcd_axis") ||
+        !strcmp(key, "cs_xcd_mod")) {
+        // variant 7: cs_dpp 0 loads both axis-0 neighbours, cs_coop 0 runs one wave per column (testing); cs_split: parts a column is
+        // swept in (0 = automatic); cs_xcd_axis: which axis the XCDs split (0 = group axis, 1 = window axis); cs_xcd_mod: residue
+        // modulus of the column -> XCD assignment (0 = automatic)
+        const bool xcd = !strcmp(key, "cs_xcd_axis") || !strcmp(key, "cs_xcd_mod");
+        if (!strcmp(key, "cs_dpp")) h->cs_dpp = value != 0;
+        else if (!strcmp(key, "cs_coop")) h->cs_coop = value != 0;
+        else if (!strcmp(key, "cs_split") && value >= 0 && value <= 64) h->cs_split = (int)value;
+        else if (!strcmp(key, "cs_xcd_axis") && value >= 0 && value <= 1) h->cs_xcd_axis = (int)value;
+        else if (!strcmp(key, "cs_xcd_mod") && value >= -1 && value <= 4096) h->cs_xcd_mod = (int)value;
+        else return fail(h, HJB_E_INVALID, "%s out of range", key);
         if (h->cs_state == 1) {
-            bool dok = false;
-            const int cst = colsweep_dpp_ok_f32(h, &dok);
+            const int cst = colsweep_options(h, xcd);
             if (cst) return cst;
-            h->hcs.dpp = (dok && h->cs_dpp) ? 1 : 0;
-            colsweep_split(h);
-            { const int ust = colsweep_upload(h); if (ust) return ust; }
             choose_launch(h);
         }
         return HJB_OK;
     }
     if (!strcmp(key, "block")) {                                     // variant 3: threads per workgroup = 64 x the states a workgroup sweeps side by side
-        if (h->variant != 3 || (value != 256 && value != 512 && value != 1024)) return fail(h, HJB_E_UNSUPPORTED, "block: 256, 512 or 1024 on kernel variant 3");
-        if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-        h->block = (int)value;
+        if (h->L.variant != 3 || (value != 256 && value != 512 && value != 1024)) return fail(h, HJB_E_UNSUPPORTED, "block: 256, 512 or 1024 on kernel variant 3");
+        h->L.block = (int)value;
+        launch_changed(h);
         return HJB_OK;
     }
     if (!strcmp(key, "grid")) {                                      // workgroups per launch of the grid-stride stage kernels (timing experiments)
         if (value < 1 || value > (1 << 20)) return fail(h, HJB_E_INVALID, "%s out of range", key);
-        if (h->variant == 7 || (h->variant == 4 && uniwin_active(h)) || h->variant == 1)
-            return fail(h, HJB_E_UNSUPPORTED, "the launch size of kernel variant %d is part of its plan", h->variant);
-        if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-        h->grid = (int)value;                                        // (until the next option that re-chooses the launch)
-        return HJB_OK;
-    }
-    if (!strcmp(key, "cs_split")) {                                  // variant 7: parts a column is swept in (0 = automatic)
-        if (value < 0 || value > 64) return fail(h, HJB_E_INVALID, "%s out of range", key);
-        h->cs_split = (int)value;
-        if (h->cs_state == 1) {
-            colsweep_split(h);
-            { const int ust = colsweep_upload(h); if (ust) return ust; }
-            choose_launch(h);
-        }
+        if (h->L.variant == 7 || h->L.mode >= 7 || h->L.variant == 1)
+            return fail(h, HJB_E_UNSUPPORTED, "the launch size of kernel variant %d is part of its plan", h->L.variant);
+        h->L.grid = (int)value;                                      // (until the next option that re-chooses the launch)
+        launch_changed(h);
         return HJB_OK;
     }
     if (!strcmp(key, "tabled_i32")) {                                // 0: variant 5 in its 64-bit form whatever the sizes (A/B timing, tests)
         h->tabled_i32_on = value != 0;
-        return HJB_OK;
-    }
-    if (!strcmp(key, "cs_coop")) {                                   // 0: variant 7 runs one wave per column (testing)
-        h->cs_coop = value != 0;
-        if (h->cs_state == 1) {
-            h->hcs.coop = h->cs_coop ? h->cs_coop_epl : 0;
-            { const int ust = colsweep_upload(h); if (ust) return ust; }
-            choose_launch(h);
-        }
-        return HJB_OK;
-    }
-    if (!strcmp(key, "cs_xcd_axis")) {     // variant 7: which axis the XCDs split (0 = group axis, 1 = window axis)
-        if (value < 0 || value > 1) return fail(h, HJB_E_INVALID, "%s out of range", key);
-        h->cs_xcd_axis = (int)value;
-        if (h->cs_state == 1) {
-            std::vector<int32_t> plan((size_t)h->hp.n[2] * h->hp.n[3] * kCsPlanWords);
-            HIP_TRY(h, hipMemcpy(plan.data(), h->hcs.plan, plan.size() * 4, hipMemcpyDeviceToHost));
-            const int cst = colsweep_map(h, plan);
-            if (cst) return cst;
-            { const int ust = colsweep_upload(h); if (ust) return ust; }
-            choose_launch(h);
-        }
-        return HJB_OK;
-    }
-    if (!strcmp(key, "cs_xcd_mod")) {      // variant 7: residue modulus of the column -> XCD assignment (0 = automatic)
-        if (value < -1 || value > 4096) return fail(h, HJB_E_INVALID, "%s out of range", key);
-        h->cs_xcd_mod = (int)value;
-        if (h->cs_state == 1) {
-            std::vector<int32_t> plan((size_t)h->hp.n[2] * h->hp.n[3] * kCsPlanWords);
-            HIP_TRY(h, hipMemcpy(plan.data(), h->hcs.plan, plan.size() * 4, hipMemcpyDeviceToHost));
-            const int cst = colsweep_map(h, plan);
-            if (cst) return cst;
-            { const int ust = colsweep_upload(h); if (ust) return ust; }
-            choose_launch(h);
-        }
+        launch_changed(h);
         return HJB_OK;
     }
     if (!strcmp(key, "lds_pad")) {
         if (value < 0 || value > 128 * 1024) return fail(h, HJB_E_INVALID, "lds_pad out of range");
         h->lds_pad = (size_t)value;
-        if (h->uniwin_ok) {          // K15 launches ONE generation of workgroups: its grid follows the occupancy
-            uniwin_tiles(h);
-            HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipDeviceSynchronize());
-            { const int ust = uniwin_upload(h); if (ust) return ust; }
-            choose_launch(h);
-        }
-        if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }   // the captured launches carry the old LDS size
+        choose_launch(h);            // (K15 launches ONE generation of workgroups: its grid follows the occupancy)
         return HJB_OK;
     }
     if (!strcmp(key, "row_lean")) {
         h->row_lean = value != 0;
-        if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }   // the captured launches are the other form
+        choose_launch(h);
         return HJB_OK;
     }
     if (!strcmp(key, "temporal")) {
@@ -474,7 +382,11 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
         return HJB_OK;
     }
     if (!strcmp(key, "axis0_table")) {      // 1: build the axis-0 (cell, t) table a mode-1 problem runs without (A/B timing, tests)
-        if (value) { const int ast = ensure_axis0_table(h); if (ast) return ast; }
+        if (value) {
+            const int ast = ensure_axis0_table(h);
+            if (ast) return ast;
+            choose_launch(h);        // (mode 4 became mode 1)
+        }
         return HJB_OK;
     }
     if (!strcmp(key, "window_planes")) {    // 4 / 3: variant 4's window modes with four planes (modes 2 / 3) or three (5 / 6)
@@ -496,12 +408,10 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
     if (!strcmp(key, "uw_claim")) {         // K15: 1 = dynamic claim of the chunk walk's positions (default), 0 = fixed stride (A/B)
         if (!h->uniwin_ok) return fail(h, HJB_E_UNSUPPORTED, "uw_claim: K15 only");
         if (value != 0 && value != 1) return fail(h, HJB_E_INVALID, "uw_claim must be 0 or 1");
-        static_assert(sizeof(void *) == 8, "");
         h->uw_claim = (int)value;
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipDeviceSynchronize());
-        { const int ust = uniwin_upload(h); if (ust) return ust; }
-        if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+        const int ust = uniwin_options(h);
+        if (ust) return ust;
+        launch_changed(h);           // (the captured launches zero the other counters)
         return HJB_OK;
     }
     if (!strcmp(key, "uw_tile") || !strcmp(key, "uw_block")) {
@@ -510,10 +420,8 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
         if (tile ? (value < 0 || value > 511) : (value != 64 && value != 256)) return fail(h, HJB_E_INVALID, "%s out of range", key);
         if (!h->uniwin_ok) return fail(h, HJB_E_UNSUPPORTED, "%s: K15 only", key);
         if (tile) h->uw_tile = (int)value; else h->uw_block = (int)value;
-        uniwin_tiles(h);
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipDeviceSynchronize());
-        { const int ust = uniwin_upload(h); if (ust) return ust; }
+        const int ust = uniwin_options(h);
+        if (ust) return ust;
         choose_launch(h);
         return HJB_OK;
     }
@@ -535,7 +443,7 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
 int32_t hjb_get_option(hjb_handle hh, const char *key, int64_t *value) {
     Handle *h = (Handle *)hh;
     if (!h || !key || !value) return fail(h, HJB_E_INVALID, "null argument");
-    if (!strcmp(key, "variant")) *value = h->variant;
+    if (!strcmp(key, "variant")) *value = h->L.variant;
     else if (!strcmp(key, "graph")) *value = h->use_graph ? 1 : 0;
     else if (!strcmp(key, "axis0_table")) *value = h->axis0_inline ? 0 : 1;       // 0: mode 1 forms axis 0's (cell, t) in the kernel
     else if (!strcmp(key, "monitor_single")) *value = h->monitor_single ? 1 : 0;
@@ -546,7 +454,7 @@ int32_t hjb_get_option(hjb_handle hh, const char *key, int64_t *value) {
     else if (!strcmp(key, "uw_block")) *value = h->uniwin_ok ? h->huw.block : 0;
     else if (!strcmp(key, "uw_claim")) *value = h->uniwin_ok ? h->uw_claim : 0;
     else if (!strcmp(key, "uniwin_slow_points")) *value = h->uniwin_ok ? h->uniwin_slow : -1;
-    else if (!strcmp(key, "grid")) *value = h->grid;
+    else if (!strcmp(key, "grid")) *value = h->L.grid;
     else if (!strcmp(key, "idx_bytes")) *value = h->idx_bytes;
     else if (!strcmp(key, "temporal")) *value = h->use_temporal;
     else if (!strcmp(key, "chunk_order")) *value = h->dn ? h->hn.chunk_order : 0;
@@ -554,10 +462,10 @@ int32_t hjb_get_option(hjb_handle hh, const char *key, int64_t *value) {
     else if (!strcmp(key, "lds_pad")) *value = (int64_t)h->lds_pad;
     else if (!strcmp(key, "cs_xcd_mod")) *value = h->cs_xcd_mod;
     else if (!strcmp(key, "cs_xcd_axis")) *value = h->cs_xcd_axis;
-    else if (!strcmp(key, "cs_split")) *value = h->variant == 7 ? h->hcs.split : 0;       // the value in effect
+    else if (!strcmp(key, "cs_split")) *value = h->L.variant == 7 ? h->hcs.split : 0;       // the value in effect
     else if (!strcmp(key, "tabled_i32")) *value = (h->tabled_i32 && h->tabled_i32_on) ? 1 : 0;      // the form variant 5 would run
     else if (!strcmp(key, "cs_coop_why")) *value = h->cs_coop_why;
-    else if (!strcmp(key, "cs_rows")) *value = h->variant == 7 ? h->cs_rows_mid : 0;
+    else if (!strcmp(key, "cs_rows")) *value = h->L.variant == 7 ? h->cs_rows_mid : 0;
     else if (!strcmp(key, "prep_mfma")) *value = h->prep_mfma;
     else if (!strcmp(key, "prep_mfma_tables")) *value = h->prep_mfma_axes;
     else if (!strcmp(key, "prep_tables")) *value = (int64_t)h->preps.size();
@@ -570,10 +478,10 @@ int32_t hjb_get_option(hjb_handle hh, const char *key, int64_t *value) {
         if (hst) return hst;
         *value = (int64_t)(hv & 0x7fffffffffffffffull);
     }
-    else if (!strcmp(key, "cs_dpp")) *value = (h->variant == 7 && h->hcs.dpp) ? 1 : 0;          // the form in effect
-    else if (!strcmp(key, "cs_coop")) *value = (h->variant == 7 && h->hcs.coop && h->cc_grid > 0) ? 1 : 0;   // the form in effect
-    else if (!strcmp(key, "cs_groups")) *value = h->variant == 7 ? h->hcs.ng : 0;
-    else if (!strcmp(key, "cs_group_axis")) *value = h->variant == 7 ? h->hcs.gax : -1;
+    else if (!strcmp(key, "cs_dpp")) *value = (h->L.variant == 7 && h->L.dpp) ? 1 : 0;          // the form in effect
+    else if (!strcmp(key, "cs_coop")) *value = (h->L.variant == 7 && h->L.coop_grid > 0) ? 1 : 0;   // the form in effect
+    else if (!strcmp(key, "cs_groups")) *value = h->L.variant == 7 ? h->hcs.ng : 0;
+    else if (!strcmp(key, "cs_group_axis")) *value = h->L.variant == 7 ? h->hcs.gax : -1;
     else return fail(h, HJB_E_INVALID, "unknown option '%s'", key);
     return HJB_OK;
 }

@@ -29,24 +29,22 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
     //   channels in the reference's own axis order
     const hjb_solve_opts &o0 = *opts[0];
     if (o0.n_stages < 1) return fail(H[0], HJB_E_INVALID, "n_stages=%d", o0.n_stages);
-    const bool tabled = H[0]->variant == 5;
+    const bool tabled = H[0]->L.variant == 5;
     int ng = 0;
     for (int i = 0; i < n; ++i) {
         Handle *h = H[i];
         const hjb_solve_opts &o = *opts[i];
+        const Launch &L = h->L;
         if (tabled) {
-            const bool i32 = h->tabled_i32 && h->tabled_i32_on && (int64_t)h->grid * h->block <= kTab32MaxThreads;
-            if (h->variant != 5 || !h->dtb || !i32 || h->j_elems != h->n_owned || h->hp.D > 4)
+            if (L.variant != 5 || !L.idx32 || h->j_elems != h->n_owned || h->hp.D > 4)
                 return fail(h, HJB_E_UNSUPPORTED, "hjb_solve_batch: problem %d does not run on the table kernel's 32-bit form (variant %d); "
-                            "sweep the problems side by side with hjb_solve on threads of their own", i, h->variant);
-            if (h->device != H[0]->device || h->dtype != H[0]->dtype || h->hp.D != H[0]->hp.D || h->block != H[0]->block)
+                            "sweep the problems side by side with hjb_solve on threads of their own", i, L.variant);
+            if (h->device != H[0]->device || h->dtype != H[0]->dtype || h->hp.D != H[0]->hp.D || L.block != H[0]->L.block)
                 return fail(h, HJB_E_UNSUPPORTED, "hjb_solve_batch: problem %d has another device, dtype, dimension or block size than problem 0", i);
         } else {
-            const bool fastcost = h->hcs.ncu == 1 && h->hp.n_cost_prefix > 0;
-            if (h->variant != 7 || !h->dcs || !h->dtb || h->dtype != HJB_F32 || h->j_elems != h->n_owned || !h->hcs.dpp || !fastcost ||
-                (h->hcs.coop && h->cc_grid > 0))
+            if (L.variant != 7 || h->dtype != HJB_F32 || h->j_elems != h->n_owned || !L.dpp || L.cost_form == 0 || L.coop_grid > 0)
                 return fail(h, HJB_E_UNSUPPORTED, "hjb_solve_batch: problem %d does not run on the column-sweep kernel in its usual form (variant %d); "
-                            "sweep the problems side by side with hjb_solve on threads of their own", i, h->variant);
+                            "sweep the problems side by side with hjb_solve on threads of their own", i, L.variant);
             if (h->device != H[0]->device || h->hcs.gax != H[0]->hcs.gax || h->cost64 != H[0]->cost64)
                 return fail(h, HJB_E_UNSUPPORTED, "hjb_solve_batch: problem %d has another device, group axis or cost typing than problem 0", i);
             ng = std::max(ng, (int)h->hcs.ng);
@@ -77,8 +75,7 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
             Handle *h = H[i];
             if (h->cs_split == old_split[i]) continue;
             h->cs_split = old_split[i];
-            colsweep_split(h);
-            (void)colsweep_upload(h);
+            (void)colsweep_options(h, false);
             choose_launch(h);
         }
     };
@@ -95,8 +92,7 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
             if (h->cs_split == 0 && s_batch < (int)h->hcs.split) {      // (an explicit option "cs_split" stands)
                 h->cs_split = s_batch;
                 resplit = true;
-                colsweep_split(h);
-                const int ust = colsweep_upload(h);
+                const int ust = colsweep_options(h, false);
                 if (ust) { restore_split(); return ust; }
                 choose_launch(h);
             }
@@ -115,8 +111,8 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
         hb.P[i] = h->dp; hb.TB[i] = h->dtb; hb.CS[i] = h->dcs;
         hb.J[i][0] = h->dJ[0]; hb.J[i][1] = h->dJ[1];
         hb.idx[i] = h->d_idx;
-        hb.grid[i] = (uint32_t)h->grid;
-        gmax = std::max(gmax, (unsigned)h->grid);
+        hb.grid[i] = (uint32_t)h->L.grid;
+        gmax = std::max(gmax, (unsigned)h->L.grid);
         const size_t jb = (size_t)h->n_owned * h->esz;
         const hipError_t te = opts[i]->terminal ? hipMemcpy(h->dJ[0], opts[i]->terminal, jb, hipMemcpyHostToDevice) : hipMemset(h->dJ[0], 0, jb);
         if (te != hipSuccess) { restore_split(); return fail(h, HJB_E_DEVICE, "terminal cost of problem %d: %s", i, hipGetErrorString(te)); }
@@ -147,7 +143,7 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
     BATCH_TRY(sync_setup());
     StageArgs a;
     a.grid = gmax;
-    a.block = tabled ? (unsigned)h0->block : 256u;
+    a.block = tabled ? (unsigned)h0->L.block : 256u;
     a.st = stream;
     a.dtype = tabled ? h0->dtype : HJB_F32;
     a.D = h0->hp.D;

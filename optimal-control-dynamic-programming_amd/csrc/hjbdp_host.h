@@ -60,6 +60,23 @@ extern std::atomic<int> g_test_rccl_only_env;        // "rccl_only_env": the RCC
 // graph launches and waits on a handle's own stream need no lock and overlap freely.
 extern std::shared_mutex g_capture_mu;
 
+// The launch of one stage: which kernel variant, in which form, with which geometry.  choose_launch alone fills it (launch_changed
+// derives what depends on the final grid); launch_stage dispatches on it, hjb_get_info and hjb_solve_batch read it.
+struct Launch {
+    int variant = 0;
+    int status = HJB_OK;          // variant_status of `variant`: not HJB_OK only for a float64-typed handle whose tables failed (refused)
+    int grid = 1, block = 256;
+    size_t lds = 0;               // dynamic LDS per workgroup
+    int mode = 0;                 // variant 4: K3's contraction mode (kernels_packed2.h MODE), 7 / 8: K15 (kernels_uniwin.h)
+    bool idx32 = false;           // variant 5: the 32-bit form of the table kernel (needs grid * block <= kTab32MaxThreads)
+    bool lean = false;            // variant 6: the lean form (kernels_rowwise.h)
+    bool j_in_lds = false;        // variant 3: the whole J buffer staged in LDS
+    bool fast = false;            // variant 1: the fast inner term
+    int cost_form = 0;            // variant 7: 0 general, 1 the usual shape (state terms + one control term), 2 that in float64
+    bool dpp = false;             // variant 7: the one-load form
+    int coop_grid = 0;            // variant 7: the cooperative form's grid (0: it does not apply); it runs where J is 16-byte aligned
+};
+
 struct Handle {
     hjb_problem prob{};  // scalar fields only (pointers are not kept)
     int device = 0;
@@ -87,11 +104,9 @@ struct Handle {
     bool nested_ok = false;
     bool nested_fast = false;
     int packed_mode = 0;          // variant 2 eligibility
-    bool split_j_in_lds = false;  // variant 3: whole J buffer staged in LDS
     // launch-bound sweeps: the ping-pong stage loop captured once into a hipGraph of kGraphStages launches
     hipStream_t stream = nullptr;
     hipGraphExec_t gexec = nullptr;
-    int gexec_variant = -1;
     bool gexec_tiled = false;
     bool use_graph = true;
     bool monitor_single = false;  // option "monitor_single" (see hjb_solve_opts.monitor_single)
@@ -113,7 +128,6 @@ struct Handle {
     int uniwin_on = -1;           // option "uniwin": -1 automatic, 0 never, 1 whenever uniwin_ok
     int uniwin_slow = 0;          // points of the plan that take the slow path
     int uw_tile = 0;              // option "uw_tile": log2 tile extents lA + 8 * lB + 64 * lC (0: the default 3, 2, 2)
-    int uw_grid = 0;
     int uw_claim = 1;             // option "uw_claim": 1 = the chunk walk's positions are claimed from per-XCD counters, 0 = fixed stride
     int uw_block = 256;           // option "uw_block": states per chunk = threads per workgroup (256 or 64)
     size_t uw_lds = 0;
@@ -151,11 +165,9 @@ struct Handle {
     std::vector<double> cs_cu64;  // cost_dtype F64: the control term of the cost in float64, per control (plan building)
     int cs_coop_why = 0;          // why it does not: 1 groups, 2 axis 1 sees the window axis, 3 n0 / storage, 4 cells, 5 window knots, 6 axis-0 knots
     int cs_coop_epl = 0;          // ... it applies: elements per staging load (0 = does not apply)
-    int cc_grid = 0;              // its launch grid
-    int variant = 0;
-    int launch_status = HJB_OK;   // status of the table build inside choose_launch
-    int forced_variant = -1;
-    int block = 256, grid = 0;
+    bool cs_dpp_ok = false;       // the axis-0 cells permit the DPP form (colsweep_dpp_ok)
+    int forced_variant = -1;      // option "variant"
+    Launch L;
     int halo_need_lo = 0, halo_need_hi = 0;
     std::string err;
 };
@@ -193,23 +205,19 @@ int dev_alloc(Handle *h, size_t bytes, void **out);
 int64_t term_elems(const hjb_problem *p, uint32_t mask);
 int build_handle(Handle *h, const hjb_problem *p);       // upload + analysis of a validated problem (float32 / float64 arithmetic by p->dtype)
 void halo_of_problem(const hjb_problem *p, bool tab64, int *lo, int *hi);     // the halo the last axis' terms imply
-int colsweep_map(Handle *h, const std::vector<int32_t> &plan);
-int colsweep_dpp_ok_f32(Handle *h, bool *ok);
 int ensure_axis0_table(Handle *h);
-int ensure_tabled(Handle *h);
 int rebuild_tables(Handle *h, bool mfma);
 int table_hash(Handle *h, uint64_t *out);
-int ensure_colsweep(Handle *h);
-void uniwin_tiles(Handle *h);        // workgroup size, chunk count, tile extents, LDS and launch grid -> Handle (the caller uploads Handle::huw)
-int uniwin_upload(Handle *h);        // Handle::huw -> the kUwSets + 1 device copies (Handle::duw); the caller has synchronised the device
+int uniwin_options(Handle *h);       // K15's tiling from the options, uploaded (the device is synchronised first)
 inline bool uniwin_active(const Handle *h) {
     return h->uniwin_ok && (h->packed_pre == 5 || h->packed_pre == 6) && (h->uniwin_on == 1 || (h->uniwin_on < 0 && h->uniwin_auto));
 }
-void colsweep_split(Handle *h);
-int colsweep_upload(Handle *h);      // the device copy of Handle::hcs, launch record included
+int colsweep_options(Handle *h, bool remap);   // variant 7's launch-time fields from the options, uploaded (remap: the XCD map too)
 int examine_tile2d(Handle *h);
 int launch_tile2d(Handle *h, const void *dJn, void *dJo, void *didx, int K, hipStream_t st);
-void choose_launch(Handle *h);
+int variant_status(Handle *h, int v, const char **why);   // what variant v needs of the handle (builds what it reads)
+void choose_launch(Handle *h);       // the variant, its form and geometry -> Handle::L
+void launch_changed(Handle *h);      // after a change to Handle::L: what depends on the grid; the captured graph is dropped
 int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t st);
 int ensure_work(Handle *h);
 int check_status(Handle *h, hipStream_t st);

@@ -173,7 +173,7 @@ int32_t hjb_multi_slab_info(hjb_multi m, int32_t slab, int32_t *begin, int32_t *
     if (halo_lo) *halo_lo = S.hlo;
     if (halo_hi) *halo_hi = S.hhi;
     if (split) *split = S.part[0] ? 1 : 0;
-    if (kernel_variant) *kernel_variant = (S.part[0] ? S.part[0] : S.whole)->variant;
+    if (kernel_variant) *kernel_variant = (S.part[0] ? S.part[0] : S.whole)->L.variant;
     return HJB_OK;
 }
 

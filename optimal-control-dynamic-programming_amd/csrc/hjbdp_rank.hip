@@ -173,7 +173,7 @@ int32_t hjb_rank_info(hjb_rank r, int32_t *out10) {
     if (!r || !out10) return rfail(r, HJB_E_INVALID, "null argument");
     out10[0] = r->begin; out10[1] = r->end; out10[2] = r->hlo; out10[3] = r->hhi;
     out10[4] = r->part[0] ? 1 : 0;
-    out10[5] = (r->part[0] ? r->part[0] : r->whole)->variant;
+    out10[5] = (r->part[0] ? r->part[0] : r->whole)->L.variant;
     out10[6] = r->need_lo; out10[7] = r->need_hi;
     out10[8] = (int32_t)r->isz; out10[9] = r->nl;
     return HJB_OK;

@@ -172,8 +172,7 @@ int ensure_axis0_table(Handle *h) {
     const int st = build_axis_table<float>(h, &h->prob, 0, h->axis0_dom, h->axis0_nent);
     if (st) return st;
     h->axis0_inline = false;
-    if (h->packed_pre == 4) h->packed_pre = 1;
-    if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }      // captured launches are the other instantiation
+    if (h->packed_pre == 4) h->packed_pre = 1;          // (the caller chooses the launch again: mode 1 is the other instantiation)
     if (h->dn) HIP_TRY(h, hipMemcpy(h->dn, &h->hn, sizeof(DNested), hipMemcpyHostToDevice));
     return HJB_OK;
 }
@@ -751,7 +750,7 @@ int ensure_tabled_t(Handle *h) {
     return HJB_OK;
 }
 
-int ensure_tabled(Handle *h) {
+static int ensure_tabled(Handle *h) {
     return h->dtype != HJB_F64 ? ensure_tabled_t<float>(h) : ensure_tabled_t<double>(h);
 }
 
@@ -980,7 +979,7 @@ bool colsweep_plan(Handle *h, int gax, const std::vector<TabEntry<T>> (&tab)[2],
 // Column -> XCD assignment of variant 7 (DColSweep::xcd_ig): group-axis indices sorted by (index mod M, index), cut
 // into 8 equal parts.  Default M = 1: plain contiguous ranges; option "cs_xcd_mod" sets M, -1 = the spacing of the
 // groups' cells in a mid-grid plan.
-int colsweep_map(Handle *h, const std::vector<int32_t> &plan) {
+static int colsweep_map(Handle *h, const std::vector<int32_t> &plan) {
     const DParams &P = h->hp;
     DColSweep &CSh = h->hcs;
     const int gax = CSh.gax, n2 = P.n[2], n3 = P.n[3];
@@ -1152,7 +1151,7 @@ int colcoop_plan(Handle *h, std::vector<int32_t> &plan, const std::vector<int32_
 // 1.527 / 1.516; 80 steps: equal; profiles/r04_c4_split.log) - so a column is also cut into round(n1 / 60) parts.
 // The device copy of the column-sweep parameters, with the launch record at its head (kernels_colsweep.h CsRec): every
 // scalar a wave reads before it knows its column, copied from the structures that own them.
-int colsweep_upload(Handle *h) {
+static int colsweep_upload(Handle *h) {
     DColSweep &C = h->hcs;
     const DParams &P = h->hp;
     const DTabled &T = h->htb;
@@ -1194,7 +1193,7 @@ int colsweep_upload(Handle *h) {
     return HJB_OK;
 }
 
-void colsweep_split(Handle *h) {
+static void colsweep_split(Handle *h) {
     const DParams &P = h->hp;
     DColSweep &CSh = h->hcs;
     const int lanes = CSh.dpp ? kCsDppLanes : 64;
@@ -1276,7 +1275,6 @@ int ensure_colsweep_t(Handle *h) {
             if (st) return st;
             CSh.wg = (const int32_t *)d;
         }
-        CSh.coop = h->cs_coop ? h->cs_coop_epl : 0;
     }
     st = upload(h, plan[pick], &d);
     if (st) return st;
@@ -1286,26 +1284,31 @@ int ensure_colsweep_t(Handle *h) {
     CSh.ncu = ncu;
     CSh.s1_bytes = (uint32_t)(P.jstride[1] * (int64_t)h->esz);
     st = colsweep_map(h, plan[pick]);
-    if (st) return st;
-    {
-        bool dok = false;
-        st = colsweep_dpp_ok<T>(h, &dok);
-        if (st) return st;
-        CSh.dpp = (dok && h->cs_dpp) ? 1 : 0;
-    }
-    colsweep_split(h);
-    st = dev_alloc(h, sizeof(DColSweep), &d);
+    if (!st) st = colsweep_dpp_ok<T>(h, &h->cs_dpp_ok);
+    if (!st) st = dev_alloc(h, sizeof(DColSweep), &d);
     if (st) return st;
     h->dcs = (DColSweep *)d;
-    st = colsweep_upload(h);
+    st = colsweep_options(h, false);
     if (st) return st;
     h->cs_state = 1;
     return HJB_OK;
 }
 
-int ensure_colsweep(Handle *h) {
-    if (h->dtype == HJB_F64) { if (h->cs_state < 0) h->cs_state = 0; return HJB_OK; }   // float32 arithmetic only
-    return ensure_colsweep_t<float>(h);
+// Variant 7's launch-time fields from the option values - the one-load (DPP) form (cs_dpp), the cooperative form (cs_coop), the parts a
+// column is swept in (cs_split) and, with `remap`, the column -> XCD assignment (cs_xcd_axis, cs_xcd_mod) - uploaded with the launch
+// record.  The caller chooses the launch again.
+int colsweep_options(Handle *h, bool remap) {
+    DColSweep &CSh = h->hcs;
+    if (remap) {
+        std::vector<int32_t> plan((size_t)h->hp.n[2] * h->hp.n[3] * kCsPlanWords);
+        HIP_TRY(h, hipMemcpy(plan.data(), CSh.plan, plan.size() * 4, hipMemcpyDeviceToHost));
+        const int st = colsweep_map(h, plan);
+        if (st) return st;
+    }
+    CSh.dpp = (h->cs_dpp_ok && h->cs_dpp) ? 1 : 0;
+    CSh.coop = h->cs_coop ? h->cs_coop_epl : 0;
+    colsweep_split(h);
+    return colsweep_upload(h);
 }
 
 // K9 applies when, for every state and control, each axis' interpolation cell is the state's own cell or the one
@@ -1371,40 +1374,122 @@ int launch_tile2d(Handle *h, const void *dJn, void *dJo, void *didx, int K, hipS
     return HJB_OK;
 }
 
+// ---- the launch: which variant serves, in which form, with which grid, block and LDS ------------------------------------------------
+
+static bool colsweep_usual_cost(const Handle *h) { return h->hcs.ncu == 1 && h->hp.n_cost_prefix > 0; }   // state terms + one control term
+
+// What kernel variant v needs of the handle - the one statement of it: HJB_OK, or the status and (*why) the reason it cannot serve.
+// Once the typing and the structure admit v, the tables or plan it reads are built here (never inside a launch: launches may be under
+// graph capture); a failed build gives the build's status.
+int variant_status(Handle *h, int v, const char **why) {
+    auto no = [&](const char *reason) { *why = reason; return (int)HJB_E_UNSUPPORTED; };
+    if (h->hp.model && v != 4) return no("a problem with a state model runs on variant 4 only");
+    if (h->tab64 && v < 5)
+        return no("it evaluates the next-state terms in the kernel, in float32; a problem with table_dtype HJB_TAB_F64 runs on the "
+                  "table-driven kernels (5, 6, 7)");
+    if (h->cost64 && v != 5 && v != 7)
+        return no("it sums the stage cost in float32; a problem with cost_dtype HJB_COST_F64 runs on the tabled kernel (5) or the column sweep (7)");
+    if (h->dtype == HJB_F16S && v >= 1 && v <= 3) return no("it does not support float16 J storage (use 0, 4, 5, 6 or 7)");
+    if (h->dtype == HJB_F64 && (v == 2 || v == 4 || v == 7)) return no("it is float32 arithmetic only");
+    int st = HJB_OK;
+    switch (v) {
+        case 1:
+            if (!h->nested_ok) return no("variant 1 (control-nested) needs: only the last state axis depends on the innermost control dim");
+            break;
+        case 2:
+            if (h->packed_mode != 1) return no("variant 2 (packed) needs the canonical spacecraft structure (see kernels_packed.h)");
+            st = ensure_axis0_table(h);          // variant 2 reads every axis from its table
+            break;
+        case 4:
+            if (!h->packed_mode) return no("variant 4 (packed, control pairs) needs the canonical spacecraft structure");
+            break;
+        case 5:
+            if (!h->tabled_ok) return no("variant 5 (tabled) needs per-axis tables that fit");
+            st = ensure_tabled(h);
+            break;
+        case 6:
+            if (!h->row_ok)
+                return no("variant 6 (one wave per grid row) needs D >= 2, per-axis tables that fit, and no axis other than axis 0 depending "
+                          "on state dim 0");
+            st = ensure_tabled(h);
+            break;
+        case 7:
+            if ((st = ensure_colsweep_t<float>(h)) != HJB_OK) break;
+            if (h->cs_state != 1)
+                return no("variant 7 (column sweep) needs D = 4, one control dim, axes 0/1 independent of the control (and of each other's "
+                          "state dim), axes 2/3 depending on state dims 2, 3 and the control only, control terms of the cost involving the "
+                          "control only, and at most kCsGMax groups of corner rows per (i2, i3)");
+            if (h->cost64 && !(colsweep_usual_cost(h) && !h->hcs.coop))
+                return no("it sums float64 cost terms in its usual cost shape only (state terms + one control term), not in the cooperative form");
+            break;
+        default:
+            break;
+    }
+    if (st) *why = h->err.c_str();       // the build's own message
+    return st;
+}
+
+// The automatic choice: the first of variants 4, 1, 3 that applies by structure and serves, else 7, 6, 5, 0.  Variant 7 wants what 6
+// wants - long axis-0 rows on a large grid - plus its own structure; its plan is examined only where 4, 1 and 3 do not apply by structure.
+static int auto_variant(Handle *h) {
+    const char *why = nullptr;
+    // few states x many controls (Kirk): one wave per state, controls across lanes (too many controls for variant 7)
+    const bool want_split = h->nU >= 64 && h->n_owned < 512 * 1024;
+    const int first = h->packed_mode ? 4 : (h->nested_ok ? 1 : (want_split ? 3 : -1));
+    if (first >= 0 && variant_status(h, first, &why) == HJB_OK) return first;
+    if (first < 0 && h->row_auto && variant_status(h, 7, &why) == HJB_OK) return 7;
+    return h->row_auto ? 6 : (h->tabled_ok ? 5 : 0);
+}
+
+// Handle::L: the variant in effect (the model's 4, the forced one, or the automatic choice), its form, grid, block and LDS.  A variant
+// that does not serve falls to the tabled kernel (float64 cost terms in a shape or form variant 7 does not sum them in), and one whose
+// tables could not be built to the generic kernel - where that serves: a float64-typed handle keeps its variant and the build's status
+// instead, and hjb_create refuses it.
 void choose_launch(Handle *h) {
-    if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-    // few states x many controls (Kirk): one wave per state, controls across lanes
-    const bool want_split = h->nU >= 64 && h->n_owned < 512 * 1024 && !h->tab64;
-    // variant 7 (column sweep) wants what variant 6 wants - long axis-0 rows on a large grid - plus its own structure;
-    // its plan is built here (never inside a launch: launches may be under graph capture)
-    bool cs_auto = false;
-    if (h->hp.D == 4 && h->hp.C == 1 && !h->hp.model && (h->forced_variant == 7 || (h->forced_variant < 0 && h->row_auto && !h->packed_mode && !h->nested_ok && !want_split))) {
-        if (h->cs_state < 0 && ensure_colsweep(h) != HJB_OK) h->cs_state = 0;
-        cs_auto = h->cs_state == 1;
+    const char *why = nullptr;
+    int v = h->hp.model ? 4 : (h->forced_variant >= 0 ? h->forced_variant : auto_variant(h));
+    int st = variant_status(h, v, &why);
+    if (st == HJB_E_UNSUPPORTED) st = variant_status(h, v = 5, &why);
+    if (st != HJB_OK && variant_status(h, 0, &why) == HJB_OK) { v = 0; st = HJB_OK; }
+    const DParams &P = h->hp;
+    Launch L;
+    L.variant = v;
+    L.status = st;
+    switch (v) {
+        case 1:
+            L.fast = h->nested_fast;
+            L.lds = h->nested_lds;
+            break;
+        case 2:
+            L.lds = h->packed_lds;
+            break;
+        case 3:
+            // J staged in LDS: eight waves share one copy of J (Kirk: 40 KB), so four workgroups fill a CU's 32 wave slots instead of half
+            // of them (Kirk's default problem 16.1 -> 13.4 ms per 199 stages: profiles/r06_xcd_shares_and_spans.log)
+            L.j_in_lds = (size_t)h->j_elems * h->esz <= 64 * 1024;
+            if (L.j_in_lds) { L.block = 512; L.lds = (size_t)h->j_elems * h->esz; }
+            break;
+        case 4:
+            L.mode = uniwin_active(h) ? h->packed_pre + 2 : h->packed_pre;      // 7 / 8: K15
+            if (L.mode >= 7) L.block = h->huw.block;
+            L.lds = (L.mode >= 7 ? h->uw_lds : h->packed2_lds) + h->lds_pad;
+            break;
+        case 6: {
+            L.lean = h->row_lean && h->row_lean_ok && !h->htb.ax[0].has_ctrl;
+            const size_t tsz = h->dtype != HJB_F64 ? 4 : 8;
+            const size_t lean_wave = (((size_t)h->nU * 4 + 15) & ~(size_t)15) + (((size_t)h->nU * (P.D - 1 + kLeanMaxCu) * tsz + 15) & ~(size_t)15);
+            if (L.lean) L.lds = 4 * lean_wave + (size_t)h->nU * 12;
+            break;
+        }
+        case 7:
+            L.cost_form = h->cost64 ? 2 : (colsweep_usual_cost(h) ? 1 : 0);
+            L.dpp = h->hcs.dpp != 0;
+            break;
+        default:
+            break;
     }
-    h->variant = h->forced_variant >= 0 ? h->forced_variant
-                                        : (h->packed_mode ? 4 : (h->nested_ok ? 1 : (want_split ? 3 : (cs_auto ? 7 : (h->row_auto ? 6 : (h->tabled_ok ? 5 : 0))))));
-    if (h->hp.model) h->variant = 4;
-    if (h->dtype == HJB_F16S && h->variant >= 1 && h->variant <= 3)     // float16 J storage: variants 0, 4, 5, 6, 7 only
-        h->variant = h->forced_variant >= 0 ? h->forced_variant : (cs_auto ? 7 : (h->row_auto ? 6 : (h->tabled_ok ? 5 : 0)));
-    if (h->variant == 7 && h->cs_state != 1) h->variant = h->row_ok ? 6 : (h->tabled_ok ? 5 : 0);
-    if (h->tab64 && h->variant < 5) h->variant = 5;       // float64-built tables: the table-driven kernels only (tabled_ok holds)
-    // float64 cost terms: the tabled kernel, or the column sweep in its usual cost shape (state terms + one control term)
-    if (h->cost64 && !(h->variant == 5 || (h->variant == 7 && h->hcs.ncu == 1 && h->hp.n_cost_prefix > 0 && !h->hcs.coop))) h->variant = 5;
-    // build the variant 5/6 tables now (never inside a launch: launches may be under graph capture)
-    h->launch_status = HJB_OK;
-    if ((h->variant == 5 || h->variant == 6) && (h->launch_status = ensure_tabled(h)) != HJB_OK) {
-        // a float64-table handle never falls back to a kernel that evaluates the float32 copies of its terms:
-        // it keeps its variant and every launch reports the build's status (hjb_create fails on it)
-        if (!h->tab64 && !h->cost64) h->variant = 0;          // ... and neither does a float64-cost handle (kernels 5 / 7 only)
-    }
-    h->block = 256;
-    h->split_j_in_lds = (size_t)h->j_elems * h->esz <= 64 * 1024;
-    // the control-split kernel with J staged in LDS: eight waves share one copy of J (Kirk: 40 KB), so four workgroups fill a CU's 32
-    // wave slots instead of half of them (Kirk's default problem 16.1 -> 13.4 ms per 199 stages: profiles/r06_xcd_shares_and_spans.log)
-    if (h->variant == 3 && h->split_j_in_lds) h->block = 512;
-    const int per_block = h->variant == 2 ? 512 : (h->variant == 3 ? h->block / 64 : 256);   // states per workgroup pass (variant 4: 256)
-    int64_t blocks = (h->n_owned + per_block - 1) / per_block;
+    const int per_block = v == 2 ? 512 : (v == 3 ? L.block / 64 : 256);   // states per workgroup pass (variant 4: 256)
+    const int64_t blocks = (h->n_owned + per_block - 1) / per_block;
     // A launch smaller than the work walks it in grid-sized spans.  Equally long spans: a short last span runs on part of the chip
     // (Solver_attitude.run's 5199 chunks as 4096 + 1103: 3.63 ms per 19 stages; as 2 x 2600: 2.53), and the kernels that give XCD x
     // the x-th contiguous share of every span (kernels_packed2.h, kernels_tabled.h) would hand a short one to the first XCDs alone.
@@ -1417,46 +1502,64 @@ void choose_launch(Handle *h) {
     // per 199 stages against 16.3 with a short last span that overlaps the tail of the one before)
     // The table kernel takes its whole grid as ONE span where its 32-bit form allows (XCD x then sweeps one contiguous eighth of the
     // grid: 13M states 0.671 -> 0.630 ms, Solver_attitude.run in the reference's order 13.7 -> 12.9 ms per 19 stages; 2e8 states: equal)
-    const int64_t cap = h->variant == 5 ? kTab32MaxThreads / 256 : 256 * 16;
-    h->grid = h->variant == 3 ? (int)std::min<int64_t>(blocks, h->block == 512 ? 2048 : 1024) : (int)spans_of(blocks, cap);
-    if (h->variant == 6) {       // one wave per (64-state chunk of a) grid row, four waves per workgroup
-        const int64_t n0 = h->hp.n[0];
-        const int64_t items = (h->n_owned / n0) * ((n0 + 63) / 64);
-        h->grid = (int)spans_of((items + 3) / 4, 1 << 20);        // (one span where it can: C4 in the reference's order 6.49 -> 6.15 ms per stage)
+    const int64_t cap = v == 5 ? kTab32MaxThreads / 256 : 256 * 16;
+    L.grid = v == 3 ? (int)std::min<int64_t>(blocks, L.block == 512 ? 2048 : 1024) : (int)spans_of(blocks, cap);
+    if (v == 6) {       // one wave per (64-state chunk of a) grid row, four waves per workgroup
+        const int64_t items = (h->n_owned / P.n[0]) * ((P.n[0] + 63) / 64);
+        L.grid = (int)spans_of((items + 3) / 4, 1 << 20);        // (one span where it can: C4 in the reference's order 6.49 -> 6.15 ms per stage)
     }
-    if (h->variant == 7) {       // one wave per (chunk of axis 0, i2, i3) column; workgroup b serves XCD b % 8
-        const DParams &P = h->hp;
-        const int lanes = h->hcs.dpp ? kCsDppLanes : 64;
+    if (v == 7) {       // one wave per (chunk of axis 0, i2, i3) column; workgroup b serves XCD b % 8
+        const DColSweep &CS = h->hcs;
+        const int lanes = CS.dpp ? kCsDppLanes : 64;
         const int64_t chunks = (P.n[0] + lanes - 1) / lanes;
-        const int64_t nwax = P.n[5 - h->hcs.gax];
+        const int64_t nwax = P.n[5 - CS.gax];
         int64_t most = 0;
-        const int64_t nfull = h->hcs.xcd_win ? P.n[h->hcs.gax] : nwax;      // the axis every XCD walks in full
-        for (int x = 0; x < 8; ++x) most = std::max<int64_t>(most, (int64_t)h->hcs.xcd_cnt[x] * chunks * nfull * h->hcs.split);
-        h->grid = (int)(8 * ((most + 3) / 4));
-        h->cc_grid = 0;
-        if (h->hcs.coop && !h->hcs.xcd_win) {       // cooperative form: one workgroup of kCcW waves per (group-axis index, 64-state chunk, kCcW columns)
+        const int64_t nfull = CS.xcd_win ? P.n[CS.gax] : nwax;      // the axis every XCD walks in full
+        for (int x = 0; x < 8; ++x) most = std::max<int64_t>(most, (int64_t)CS.xcd_cnt[x] * chunks * nfull * CS.split);
+        L.grid = (int)(8 * ((most + 3) / 4));
+        if (CS.coop && !CS.xcd_win) {       // cooperative form: one workgroup of kCcW waves per (group-axis index, 64-state chunk, kCcW columns)
             const int64_t c64 = (P.n[0] + 63) / 64, nblk = (nwax + kCcW - 1) / kCcW;
             int64_t mostc = 0;
-            for (int x = 0; x < 8; ++x) mostc = std::max<int64_t>(mostc, (int64_t)h->hcs.xcd_cnt[x] * c64 * nblk);
-            h->cc_grid = (int)(8 * mostc);
+            for (int x = 0; x < 8; ++x) mostc = std::max<int64_t>(mostc, (int64_t)CS.xcd_cnt[x] * c64 * nblk);
+            L.coop_grid = (int)(8 * mostc);
         }
     }
-    if (h->variant == 4 && uniwin_active(h)) h->grid = h->uw_grid;      // K15: one generation of workgroups
-    if (h->grid < 1) h->grid = 1;
+    if (L.mode >= 7) {  // K15: as many workgroups as the device holds at once (a persistent walk: a second generation would run alone)
+        const DUniwin &U = h->huw;
+        int occ = stage_uniwin_occupancy(h->dtype, P.D, P.model != 0, U.block, L.lds);
+        if (occ < 1) occ = U.block == 64 ? 16 : 4;
+        hipDeviceProp_t prop;
+        int cus = 256;
+        if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+        const int64_t g = std::min<int64_t>((int64_t)occ * cus, (int64_t)((U.n_v + 7) / 8) * 8);
+        L.grid = (int)std::max<int64_t>(8, g - (g & 7));
+    }
+    if (L.grid < 1) L.grid = 1;
+    h->L = L;
+    launch_changed(h);
 }
 
-// One stage: the handle's variant on (dJn -> dJo, didx).  The kernels live in translation units of their own
-// (stage_*.hip behind hjbdp_launch.h); this is the only place that knows which family serves which variant.
+// After every change to Handle::L (choose_launch, options "grid", "block", "tabled_i32"): the fields that depend on the final grid, and
+// the captured stage loop - it holds the old launches - is dropped.
+void launch_changed(Handle *h) {
+    Launch &L = h->L;
+    L.idx32 = L.variant == 5 && h->tabled_i32 && h->tabled_i32_on && (int64_t)L.grid * L.block <= kTab32MaxThreads;
+    if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+}
+
+// One stage: the launch Handle::L on (dJn -> dJo, didx).  The kernels live in translation units of their own (stage_*.hip behind
+// hjbdp_launch.h); this is the only place that knows which family serves which variant.
 int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t st) {
-    const int D = h->hp.D;
-    const bool f32 = h->dtype != HJB_F64;              // float32 arithmetic (J stored as float32 or binary16)
-    const bool same = h->dtype != HJB_F16S;            // J stored in the arithmetic type
+    const Launch &L = h->L;
+    if (L.status != HJB_OK) return fail(h, L.status, "kernel variant %d cannot run on this handle (status %d)", L.variant, L.status);
     StageArgs a;
-    a.grid = (unsigned)h->grid;
-    a.block = (unsigned)h->block;
+    a.grid = (unsigned)L.grid;
+    a.block = (unsigned)L.block;
+    a.lds = L.lds;
+    a.idx32 = L.idx32;
     a.st = st;
     a.dtype = h->dtype;
-    a.D = D;
+    a.D = h->hp.D;
     a.dp = h->dp;
     a.dn = h->dn;
     a.dtb = h->dtb;
@@ -1465,84 +1568,42 @@ int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t 
     a.Jo = dJo;
     a.idx = didx;
     int miss = 0;
-    if (h->tab64 && (h->variant < 5 || h->launch_status != HJB_OK))
-        return fail(h, h->launch_status != HJB_OK ? h->launch_status : HJB_E_UNSUPPORTED,
-                    "table_dtype HJB_TAB_F64 is served by the table-driven kernels only (variant %d, table build status %d)", h->variant, h->launch_status);
-    if (h->cost64 && h->variant != 5 && h->variant != 7)
-        return fail(h, HJB_E_UNSUPPORTED, "cost_dtype HJB_COST_F64 is served by stage kernels 5 and 7 only (variant %d)", h->variant);
-    switch (h->variant) {
-        case 7: {
-            if (!h->dtb || !h->dcs) return fail(h, HJB_E_DEVICE, "variant 7 plan missing");
-            if (!f32) return fail(h, HJB_E_UNSUPPORTED, "variant 7 is float32 arithmetic only");
-            const bool fastcost = h->hcs.ncu == 1 && h->hp.n_cost_prefix > 0;    // state terms + one control term
-            if (h->cost64 && !fastcost) return fail(h, HJB_E_UNSUPPORTED, "variant 7 sums float64 cost terms in its usual cost shape only");
-            const int costform = h->cost64 ? 2 : (fastcost ? 1 : 0);
+    switch (L.variant) {
+        case 7:
             // cooperative form: its staging loads are 16 bytes wide (a J pointer handed in unaligned runs the other form)
-            if (!h->cost64 && h->hcs.coop && h->cc_grid > 0 && h->hcs.ng <= kCcNCG && ((uintptr_t)dJn & 15u) == 0) {
-                a.grid = (unsigned)h->cc_grid;
-                miss = stage_colcoop(a, h->hcs.gax, h->hcs.ng, fastcost);
+            if (L.coop_grid > 0 && ((uintptr_t)dJn & 15u) == 0) {
+                a.grid = (unsigned)L.coop_grid;
+                miss = stage_colcoop(a, h->hcs.gax, h->hcs.ng, L.cost_form == 1);
             } else {
-                miss = stage_colsweep(a, h->hcs.gax, h->hcs.ng, costform, h->hcs.dpp != 0);
+                miss = stage_colsweep(a, h->hcs.gax, h->hcs.ng, L.cost_form, L.dpp);
             }
             if (miss) return fail(h, HJB_E_DEVICE, "variant 7: %d groups", h->hcs.ng);
             break;
-        }
-        case 6: {
-            if (!h->dtb) return fail(h, HJB_E_DEVICE, "variant 6 tables missing");
-            const bool lean = h->row_lean && h->row_lean_ok && !h->htb.ax[0].has_ctrl;
-            const size_t tsz = f32 ? 4 : 8;
-            const size_t lean_wave = (((size_t)h->nU * 4 + 15) & ~(size_t)15) + (((size_t)h->nU * (D - 1 + kLeanMaxCu) * tsz + 15) & ~(size_t)15);
-            a.lds = lean ? 4 * lean_wave + (size_t)h->nU * 12 : 0;
-            miss = stage_rowwise(a, lean);
-            break;
-        }
-        case 5:
-            if (!h->dtb) return fail(h, HJB_E_DEVICE, "variant 5 tables missing");
-            a.idx32 = h->tabled_i32 && h->tabled_i32_on && (int64_t)a.grid * a.block <= kTab32MaxThreads;
-            miss = stage_tabled(a);
-            break;
+        case 6: miss = stage_rowwise(a, L.lean); break;
+        case 5: miss = stage_tabled(a); break;
         case 4:
-            if (!f32) return fail(h, HJB_E_UNSUPPORTED, "variant 4 is float32 only");
-            if (uniwin_active(h)) {                  // modes 7 / 8 (K15, kernels_uniwin.h)
+            if (L.mode >= 7) {                       // K15 (kernels_uniwin.h)
                 // the claim counters are per stream: two launches in flight on different streams never share (and re-zero) a set.
                 // A stream is given a set on its first launch (host bookkeeping only: nothing is allocated, also under capture)
                 int set = 0;
                 while (set < h->uw_nstreams && h->uw_streams[set] != st) ++set;
                 if (set == h->uw_nstreams && set < kUwSets) h->uw_streams[h->uw_nstreams++] = st;
                 a.duw = h->duw + set;                // (set kUwSets: the static walk)
-                a.block = (unsigned)h->huw.block;
                 if (h->uw_claim && set < kUwSets)    // (a memset node under capture)
                     HIP_TRY(h, hipMemsetAsync(h->huw.counters + (size_t)kUwSetWords * set, 0, kUwSetWords * sizeof(uint32_t), st));
-                a.lds = h->uw_lds + h->lds_pad;
                 miss = stage_uniwin(a, h->hp.model != 0);
-                break;
+            } else {
+                miss = stage_packed2(a, L.mode);
             }
-            a.lds = h->packed2_lds + h->lds_pad;
-            miss = stage_packed2(a, h->packed_pre);
             break;
-        case 3:
-            if (!same) return fail(h, HJB_E_UNSUPPORTED, "variant 3 does not support float16 J storage (use 0, 4 or 5)");
-            a.lds = h->split_j_in_lds ? (size_t)h->j_elems * h->esz : 0;
-            miss = stage_ctrlsplit(a, h->split_j_in_lds);
-            break;
-        case 2:
-            if (!same) return fail(h, HJB_E_UNSUPPORTED, "variant 2 does not support float16 J storage (use 0, 4 or 5)");
-            if (!f32) return fail(h, HJB_E_UNSUPPORTED, "variant 2 is float32 only");
-            a.lds = h->packed_lds;
-            miss = stage_packed(a);
-            break;
-        case 1:
-            if (!same) return fail(h, HJB_E_UNSUPPORTED, "variant 1 does not support float16 J storage (use 0, 4 or 5)");
-            a.lds = h->nested_lds;
-            miss = stage_nested(a, h->nested_fast);
-            break;
-        case 0:
-            miss = stage_generic(a);
-            break;
+        case 3: miss = stage_ctrlsplit(a, L.j_in_lds); break;
+        case 2: miss = stage_packed(a); break;
+        case 1: miss = stage_nested(a, L.fast); break;
+        case 0: miss = stage_generic(a); break;
         default:    // never fall through to the generic kernel silently
-            return fail(h, HJB_E_DEVICE, "internal: kernel variant %d was not dispatched", h->variant);
+            return fail(h, HJB_E_DEVICE, "internal: kernel variant %d was not dispatched", L.variant);
     }
-    if (miss) return fail(h, HJB_E_UNSUPPORTED, "variant %d has no kernel for D=%d, dtype %d", h->variant, D, h->dtype);
+    if (miss) return fail(h, HJB_E_UNSUPPORTED, "variant %d has no kernel for D=%d, dtype %d", L.variant, a.D, h->dtype);
     HIP_TRY(h, hipGetLastError());
     return HJB_OK;
 }
@@ -1631,7 +1692,8 @@ int launch_probe(Handle *h, const DProbe &pr, const void *dJn, hipStream_t st) {
 // Applies when, beyond modes 5 / 6, nothing the level axes and the last axis need depends on the state-only axes: their tables'
 // domains, the last axis' state terms and its inner term (Solver_attitude.m:423-425: the next rates are functions of the rates
 // and the torque).  The plan is built here; `uniwin_auto` says whether the usual shape holds on (nearly) every point.
-void uniwin_tiles(Handle *h) {
+// The chunk walk's tiling and workgroup size from the options (uw_tile, uw_block) -> Handle::huw, Handle::uw_lds.
+static void uniwin_tiles(Handle *h) {
     DUniwin &U = h->huw;
     U.block = h->uw_block == 64 ? 64 : 256;
     U.cpp = (int32_t)((U.inner + U.block - 1) / U.block);
@@ -1653,18 +1715,10 @@ void uniwin_tiles(Handle *h) {
     U.tile_chunks = (uint32_t)U.cpp << (U.lA + U.lB + U.lC);
     const uint64_t nv = (uint64_t)U.tile_chunks * (uint64_t)U.ntA * (uint64_t)U.ntB * (uint64_t)U.ntC;
     U.n_v = (uint32_t)std::min<uint64_t>(nv, 0xfffffff0u);
-    // the launch: as many workgroups as the device holds at once (a persistent walk: a second generation would run alone)
-    int occ = stage_uniwin_occupancy(h->dtype, h->hp.D, h->hp.model != 0, U.block, h->uw_lds + h->lds_pad);
-    if (occ < 1) occ = U.block == 64 ? 16 : 4;
-    hipDeviceProp_t prop;
-    int cus = 256;
-    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    int64_t g = (int64_t)occ * cus;
-    g = std::min<int64_t>(g, (int64_t)((U.n_v + 7) / 8) * 8);
-    h->uw_grid = (int)std::max<int64_t>(8, g - (g & 7));
 }
 
-int uniwin_upload(Handle *h) {
+// Handle::huw -> the kUwSets + 1 device copies (Handle::duw); the device is idle (hjb_create) or has been synchronised
+static int uniwin_upload(Handle *h) {
     DUniwin sets[kUwSets + 1];
     for (int k = 0; k <= kUwSets; ++k) {
         sets[k] = h->huw;
@@ -1672,6 +1726,13 @@ int uniwin_upload(Handle *h) {
     }
     HIP_TRY(h, hipMemcpy(h->duw, sets, sizeof sets, hipMemcpyHostToDevice));
     return HJB_OK;
+}
+
+int uniwin_options(Handle *h) {
+    uniwin_tiles(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    return uniwin_upload(h);
 }
 
 static int setup_uniwin(Handle *h, const hjb_problem *p) {
@@ -1752,7 +1813,5 @@ void halo_of_problem(const hjb_problem *p, bool tab64, int *lo, int *hi) {
     if (p->dtype != HJB_F64) halo_from_terms<float>(p, tab64, lo, hi);
     else halo_from_terms<double>(p, tab64, lo, hi);
 }
-
-int colsweep_dpp_ok_f32(Handle *h, bool *ok) { return colsweep_dpp_ok<float>(h, ok); }
 
 }  // namespace hjbhost
