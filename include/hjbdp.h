@@ -370,6 +370,29 @@ int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const in
 int32_t hjb_rollout_destroy(void *rollout);
 const char *hjb_rollout_last_error(void *rollout);
 
+/* The 6-D attitude closed loop (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run) on the same object.
+ * hjb_rollout_set_attitude_model and hjb_rollout_set_model replace each other: the last one set wins.  It needs D == 6, n_u == 3
+ * and the grid axes in the reference's order (w1, w2, w3, yaw, pitch, roll); inertia = [J1 J2 J3] and h finite and > 0,
+ * integrator HJB_ATT_TAYLOR / _RK4, q [7] and r [3] finite (NULL = zeros).  hjb_rollout_run_attitude steps the 7-state
+ * X = [w1 w2 w3 q1 q2 q3 q4] (q4 scalar), all in double, left to right, every product rounded; step k, p = plane_of_step[k]:
+ *   yaw = atan2c(2*(X6*X5 + X7*X4), ((X7*X7 + X6*X6) - X5*X5) - X4*X4),  pitch = asinc(clamp(-2*(X6*X4 - X7*X5), -1, 1)),
+ *   roll = atan2c(2*(X5*X4 + X7*X6), ((X7*X7 - X6*X6) - X5*X5) + X4*X4)   (fdlibm's forms in + - * / sqrt only: <= 2 ulp of libm, tested);
+ *   u = the policy lookup of plane p at (X1, X2, X3, yaw, pitch, roll), as in hjb_rollout_run;
+ *   cost += ((q1*(X1*X1) + q2*(X2*X2)) + ... + q7*(X7*X7)) + r1*(u1*u1) + r2*(u2*u2) + r3*(u3*u3);
+ *   X+ = X + h f(X, u) (taylor) or classical RK4 with u held over the step, f the rigid body with diagonal inertia and the
+ *   quaternion kinematics (:600-620); then X4..X7 are divided by sqrt(((X4*X4 + X5*X5) + X6*X6) + X7*X7).
+ * X0, X_final [7, n_traj]; cost [n_traj]; X_path [n_traj, 7, n_steps+1]; U_path [n_traj, 3, n_steps]; A_path [n_traj, 3, n_steps]
+ * (the yaw, pitch, roll in radians that step k looked up at).  Every output but X_final may be NULL.  An X0 column whose
+ * quaternion is all zeros is HJB_E_INVALID; so are hjb_rollout_run on an attitude object and hjb_rollout_run_attitude on an
+ * affine one. */
+#define HJB_ATT_TAYLOR 0   /* X+ = X + h f(X,u)                  (Solver_attitude.m:688, used by get_optimal_path :778) */
+#define HJB_ATT_RK4 1      /* classical RK4, u held over the step (:679-686, next_stage_states' default) */
+int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, double h, int32_t integrator, const double *q,
+                                       const double *r);
+int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                 const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *A_path,
+                                 double *device_ms);
+
 /* ---- flat builder API -------------------------------------------------------------------------------------------
  * hjb_problem holds arrays of structs with pointers, which MATLAB's loadlibrary/calllib cannot marshal.  These entry
  * points take primitives and plain arrays only, copy what they are given (the caller may free it at once), and end in

@@ -94,4 +94,11 @@ int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const in
                         const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *device_ms);
 int32_t hjb_rollout_destroy(void *rollout);
 const char *hjb_rollout_last_error(void *rollout);
+/* the 6-D attitude loop on the same object (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run);
+ * usage: matlab/Solver_attitude_hjbdp_get_optimal_paths.m */
+int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, double h, int32_t integrator, const double *q,
+                                       const double *r);
+int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                 const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *A_path,
+                                 double *device_ms);
 #endif

@@ -42,6 +42,57 @@ struct DRollout {
 // number of trailing 1-bits of c: the tree nodes corner c completes
 __device__ __forceinline__ constexpr int trailing_ones(int c) { return (c & 1) ? 1 + trailing_ones(c >> 1) : 0; }
 
+// One step's policy lookup, the ONE definition K16 and K17 (kernels_rollout_attitude.h) share: declares u_[NU_] = the controls at
+// x_ on plane plane_of_step[k_] (u_[nu_ .. NU_) = 0).  kn_ / rd_ / ut_: knots, 1/dx and u_table (LDS or global); nl_ = R_.n_labels.
+// A macro, not a __device__ function: routed through a function (force-inlined, R by reference or by value) the compiler schedules
+// K16 differently and its pos-att case ran 6 % slower; expanded in place, K16's code object is byte for byte the one it was.
+// Names it declares in the caller's scope: `base` (int64_t), `tw` (double[D_]) and the output array named by u_; its loop
+// variables (a, j, c) and the temporaries kk, cell, L, off, s, v, t1 live inside its own blocks.  It reads the caller's
+// find_cell, fma_t and trailing_ones.  One expansion per scope (a step-loop body).
+#define HJB_ROLLOUT_LOOKUP(D_, NU_, METHOD_, R_, kn_, rd_, ut_, lab_, k_, x_, nu_, nl_, u_)                                          \
+    int64_t base = (int64_t)R_.plane_of_step[k_] * R_.nS;                                                                       \
+    double tw[D_];                                                                                                              \
+    _Pragma("unroll") for (int a = 0; a < D_; ++a) {                                                                            \
+        const double *kk = kn_ + R_.koff[a];                                                                                    \
+        int cell = find_cell<double>(kk, R_.n[a], x_[a], R_.uniform[a], R_.x0[a], R_.inv_h[a]);                                 \
+        if (METHOD_ == HJB_LOOKUP_NEAREST) {                                                                                    \
+            if ((double)(x_[a] - kk[cell]) >= (double)(kk[cell + 1] - x_[a])) ++cell;                                           \
+            tw[a] = 0.0;                                                                                                        \
+        } else {                                                                                                                \
+            tw[a] = (double)((double)(x_[a] - kk[cell]) * rd_[R_.koff[a] + cell]);                                              \
+        }                                                                                                                       \
+        base += R_.stride[a] * cell;                                                                                            \
+    }                                                                                                                           \
+    double u_[NU_];                                                                                                             \
+    if (METHOD_ == HJB_LOOKUP_NEAREST) {                                                                                        \
+        const int64_t L = (int64_t)lab_[base] - R_.index_base;                                                                  \
+        _Pragma("unroll") for (int j = 0; j < NU_; ++j) {                                                                       \
+            u_[j] = 0.0;                                                                                                        \
+            if (j < nu_) u_[j] = ut_[L + nl_ * j];                                                                              \
+        }                                                                                                                       \
+    } else {                                                                                                                    \
+        int32_t L[1 << D_];                                                                                                     \
+        _Pragma("unroll") for (int c = 0; c < (1 << D_); ++c) { /* every corner label in flight before the first is used */  \
+            int64_t off = base;                                                                                                 \
+            _Pragma("unroll") for (int a = 0; a < D_; ++a) if (c & (1 << a)) off += R_.stride[a];                               \
+            L[c] = (int32_t)lab_[off];                                                                                          \
+        }                                                                                                                       \
+        _Pragma("unroll") for (int c = 0; c < (1 << D_); ++c) L[c] -= R_.index_base;                                            \
+        _Pragma("unroll") for (int j = 0; j < NU_; ++j) {                                                                       \
+            u_[j] = 0.0;                                                                                                        \
+            if (j < nu_) {                                                                                                      \
+                double s[D_ + 1];                                                                                               \
+                _Pragma("unroll") for (int c = 0; c < (1 << D_); ++c) {                                                         \
+                    double v = ut_[L[c] + nl_ * j];                                                                             \
+                    const int t1 = trailing_ones(c);                                                                            \
+                    _Pragma("unroll") for (int a = 0; a < D_; ++a) if (a < t1) v = fma_t<double>(tw[a], (double)(v - s[a]), s[a]); \
+                    s[t1] = v;                                                                                                  \
+                }                                                                                                               \
+                u_[j] = s[D_];                                                                                                  \
+            }                                                                                                                   \
+        }                                                                                                                       \
+    }
+
 template <int D, typename TL, int METHOD, bool LDS>
 __global__ void __launch_bounds__(256)
 k_rollout(const DRollout R, int64_t nc, const double *__restrict__ X0, double *__restrict__ Xf, double *__restrict__ cost,
@@ -78,58 +129,7 @@ k_rollout(const DRollout R, int64_t nc, const double *__restrict__ X0, double *_
     }
     double J = 0.0;
     for (int k = 0; k < R.n_steps; ++k) {
-        int64_t base = (int64_t)R.plane_of_step[k] * R.nS;
-        double tw[D];
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-            const double *kk = kn + R.koff[a];
-            int cell = find_cell<double>(kk, R.n[a], x[a], R.uniform[a], R.x0[a], R.inv_h[a]);
-            if (METHOD == HJB_LOOKUP_NEAREST) {
-                if ((double)(x[a] - kk[cell]) >= (double)(kk[cell + 1] - x[a])) ++cell;
-                tw[a] = 0.0;
-            } else {
-                tw[a] = (double)((double)(x[a] - kk[cell]) * rd[R.koff[a] + cell]);
-            }
-            base += R.stride[a] * cell;
-        }
-        double u[HJB_ROLLOUT_MAX_U];
-        if (METHOD == HJB_LOOKUP_NEAREST) {
-            const int64_t L = (int64_t)lab[base] - R.index_base;
-#pragma unroll
-            for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j) {
-                u[j] = 0.0;
-                if (j < nu) u[j] = ut[L + nl * j];
-            }
-        } else {
-            int32_t L[1 << D];
-#pragma unroll
-            for (int c = 0; c < (1 << D); ++c) {     // every corner label in flight before the first is used
-                int64_t off = base;
-#pragma unroll
-                for (int a = 0; a < D; ++a)
-                    if (c & (1 << a)) off += R.stride[a];
-                L[c] = (int32_t)lab[off];
-            }
-#pragma unroll
-            for (int c = 0; c < (1 << D); ++c) L[c] -= R.index_base;
-#pragma unroll
-            for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j) {
-                u[j] = 0.0;
-                if (j < nu) {
-                    double s[D + 1];
-#pragma unroll
-                    for (int c = 0; c < (1 << D); ++c) {
-                        double v = ut[L[c] + nl * j];
-                        const int t1 = trailing_ones(c);
-#pragma unroll
-                        for (int a = 0; a < D; ++a)
-                            if (a < t1) v = fma_t<double>(tw[a], (double)(v - s[a]), s[a]);
-                        s[t1] = v;
-                    }
-                    u[j] = s[D];
-                }
-            }
-        }
+        HJB_ROLLOUT_LOOKUP(D, HJB_ROLLOUT_MAX_U, METHOD, R, kn, rd, ut, lab, k, x, nu, nl, u)
         double g = R.q[0] * (x[0] * x[0]);
 #pragma unroll
         for (int a = 1; a < D; ++a) g = g + R.q[a] * (x[a] * x[a]);

@@ -1,17 +1,22 @@
-// rollout.hip - hjb_rollout_*: batched closed-loop rollouts of a stored per-stage policy (include/hjbdp.h; kernel: kernels_rollout.h).
+// rollout.hip - hjb_rollout_*: batched closed-loop rollouts of a stored per-stage policy (include/hjbdp.h; kernels:
+// kernels_rollout.h for the affine model, kernels_rollout_attitude.h / rollout_attitude.hip for the attitude model).
 #include "hjbdp_host.h"
 #include "kernels_rollout.h"
+#include "kernels_rollout_attitude.h"
 
 using namespace hjbhost;
 
 namespace {
 
+enum { kModelNone = 0, kModelAffine = 1, kModelAttitude = 2 };    // the last setter called wins
+
 struct Rollout {
     std::mutex mu;                  // one call at a time per object
     int device = 0, D = 0, idx_bytes = 4, n_planes = 0;
-    bool model_set = false;
+    int model = kModelNone, integrator = HJB_ATT_TAYLOR;
     int64_t chunk = (int64_t)1 << 20;
     DRollout R{};                   // device pointers filled by create; model by set_model
+    DAttitude M{};                  // the attitude model (set_attitude_model)
     std::vector<void *> allocs;
     hipStream_t stream = nullptr;
     std::string err;
@@ -79,6 +84,106 @@ void launch_m(int D, int method, bool lds_on, const DRollout &R, int64_t nc, siz
 }
 
 bool all_finite(const double *p, int64_t n) { return !p || first_nonfinite(p, n, true) < 0; }
+
+// The argument checks both run functions make before any device work: method, sizes, that the object holds the model this
+// entry point runs (`want`), plane_of_step.
+int check_run(Rollout *ro, int want, int method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj) {
+    if (method != HJB_LOOKUP_NEAREST && method != HJB_LOOKUP_LINEAR) return rfail(ro, HJB_E_INVALID, "rollout: method %d", method);
+    if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
+    if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
+    if (ro->model == kModelNone)
+        return rfail(ro, HJB_E_INVALID, want == kModelAffine ? "rollout: run before hjb_rollout_set_model"
+                                                             : "rollout: run before hjb_rollout_set_attitude_model");
+    if (ro->model != want)
+        return rfail(ro, HJB_E_INVALID, want == kModelAffine
+                     ? "rollout: the object holds the attitude model (hjb_rollout_set_attitude_model): call hjb_rollout_run_attitude"
+                     : "rollout: the object holds the affine model (hjb_rollout_set_model): call hjb_rollout_run");
+    if (n_steps > 0 && !plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null plane_of_step");
+    for (int k = 0; k < n_steps; ++k)
+        if (plane_of_step[k] < 0 || plane_of_step[k] >= ro->n_planes)
+            return rfail(ro, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d)", k, plane_of_step[k], ro->n_planes);
+    return HJB_OK;
+}
+
+// The chunk loop both run functions share: W doubles of state per trajectory; per step n_u controls and n_e more path rows
+// (E_path: the attitude loop's angles).  Per chunk: upload X0, launch(R, nc, lds, lds_on, stream, X0, Xf, cost, Xp, Up, Ep) (the
+// kernel of the entry point `who`), download X_final / cost and the paths ([nc, rows] on the device -> columns i0 .. i0+nc of
+// [n_traj, rows] on the host); device_ms sums the launches' event times.
+template <typename Launch>
+int run_chunks(Rollout *ro, const char *who, int W, int n_e, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+               const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *E_path, double *device_ms,
+               Launch launch) {
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
+    const int nu = ro->R.n_u;
+    const int64_t nc_max = std::min(n_traj, ro->chunk);
+    const size_t xb = (size_t)nc_max * W * sizeof(double);
+    const size_t xpb = X_path ? (size_t)nc_max * W * ((size_t)n_steps + 1) * sizeof(double) : 0;
+    const size_t upb = U_path ? (size_t)nc_max * nu * (size_t)n_steps * sizeof(double) : 0;
+    const size_t epb = E_path ? (size_t)nc_max * n_e * (size_t)n_steps * sizeof(double) : 0;
+    const size_t cb = cost ? (size_t)nc_max * sizeof(double) : 0;
+    const size_t pb = (size_t)std::max(n_steps, 1) * sizeof(int32_t);
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipMemGetInfo failed");
+    const size_t need = 2 * xb + xpb + upb + epb + cb + pb;
+    if (need + ((size_t)64 << 20) > fr)
+        return rfail(ro, HJB_E_NOMEM, "rollout: a chunk of %lld trajectories needs %zu bytes, %zu free (lower option \"chunk\")",
+                     (long long)nc_max, need, fr);
+    void *bufs[7] = {};
+    auto done = [&](int code) {
+        for (void *p : bufs) if (p) (void)hipFree(p);
+        return code;
+    };
+    const size_t sizes[7] = {xb, xb, cb, xpb, upb, pb, epb};
+    for (int b = 0; b < 7; ++b)
+        if (sizes[b] && hipMalloc(&bufs[b], sizes[b]) != hipSuccess) return done(rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", sizes[b]));
+    double *dX0 = (double *)bufs[0], *dXf = (double *)bufs[1], *dC = (double *)bufs[2], *dXp = (double *)bufs[3], *dUp = (double *)bufs[4];
+    double *dEp = (double *)bufs[6];
+    hipStream_t st = ro->stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess && n_steps > 0) e = hipMemcpyAsync(bufs[5], plane_of_step, pb, hipMemcpyHostToDevice, st);
+    DRollout R = ro->R;
+    R.plane_of_step = (const int32_t *)bufs[5];
+    R.n_steps = n_steps;
+    const size_t lds = (size_t)(2 * (int64_t)R.n_knots + (int64_t)R.n_labels * nu) * sizeof(double);
+    const bool lds_on = lds <= kLdsMax;
+    double ms_total = 0;
+    for (int64_t i0 = 0; e == hipSuccess && i0 < n_traj; i0 += nc_max) {
+        const int64_t nc = std::min(nc_max, n_traj - i0);
+        e = hipMemcpyAsync(dX0, X0 + W * i0, (size_t)nc * W * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) break;
+        (void)hipEventRecord(e0, st);
+        e = launch(R, nc, lds, lds_on, st, dX0, dXf, dC, dXp, dUp, dEp);
+        if (e != hipSuccess) break;
+        (void)hipEventRecord(e1, st);
+        e = hipMemcpyAsync(X_final + W * i0, dXf, (size_t)nc * W * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && cost) e = hipMemcpyAsync(cost + i0, dC, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, st);
+        // paths: [nc, rows] on the device -> columns i0 .. i0+nc of [n_traj, rows] on the host
+        if (e == hipSuccess && X_path)
+            e = hipMemcpy2DAsync(X_path + i0, (size_t)n_traj * sizeof(double), dXp, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double),
+                                 (size_t)W * (n_steps + 1), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && U_path && n_steps > 0)
+            e = hipMemcpy2DAsync(U_path + i0, (size_t)n_traj * sizeof(double), dUp, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double),
+                                 (size_t)nu * n_steps, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && E_path && n_steps > 0)
+            e = hipMemcpy2DAsync(E_path + i0, (size_t)n_traj * sizeof(double), dEp, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double),
+                                 (size_t)n_e * n_steps, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        ms_total += ms;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        return done(rfail(ro, HJB_E_DEVICE, "%s: %s", who, hipGetErrorString(e)));
+    }
+    if (device_ms) *device_ms = ms_total;
+    return done(HJB_OK);
+}
 
 }  // namespace
 
@@ -215,7 +320,39 @@ int32_t hjb_rollout_set_model(void *rollout, const double *A, const double *B, c
     if (q) std::memcpy(R.q, q, sizeof(double) * D);
     if (r) std::memcpy(R.r, r, sizeof(double) * nu);
     R.has_c = c ? 1 : 0;
-    ro->model_set = true;
+    ro->model = kModelAffine;
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, double h, int32_t integrator, const double *q,
+                                       const double *r) {
+    Rollout *ro = (Rollout *)rollout;
+    if (!ro || !inertia) return rfail(ro, HJB_E_INVALID, "rollout: null argument (inertia is required)");
+    std::lock_guard<std::mutex> g(ro->mu);
+    if (ro->D != 6 || ro->R.n_u != HJB_ATT_U)
+        return rfail(ro, HJB_E_INVALID, "rollout: the attitude model needs D == 6 and n_u == 3 (this object: D=%d, n_u=%d)", ro->D, ro->R.n_u);
+    for (int a = 0; a < 3; ++a)
+        if (!(std::isfinite(inertia[a]) && inertia[a] > 0))
+            return rfail(ro, HJB_E_INVALID, "rollout: inertia J%d = %g is not finite and > 0", a + 1, inertia[a]);
+    if (!(std::isfinite(h) && h > 0)) return rfail(ro, HJB_E_INVALID, "rollout: h = %g is not finite and > 0", h);
+    if (integrator != HJB_ATT_TAYLOR && integrator != HJB_ATT_RK4)
+        return rfail(ro, HJB_E_INVALID, "rollout: integrator %d is not HJB_ATT_TAYLOR / HJB_ATT_RK4", integrator);
+    if (!all_finite(q, HJB_ATT_W)) return rfail(ro, HJB_E_INVALID, "rollout: q is not finite");
+    if (!all_finite(r, HJB_ATT_U)) return rfail(ro, HJB_E_INVALID, "rollout: r is not finite");
+    DAttitude &M = ro->M;
+    M = DAttitude{};
+    M.h = h;
+    const double J1 = inertia[0], J2 = inertia[1], J3 = inertia[2];
+    M.J[0] = J1;
+    M.J[1] = J2;
+    M.J[2] = J3;
+    M.c[0] = (J2 - J3) / J1;                          // spacecraft_dynamics_list :600-620
+    M.c[1] = (J3 - J1) / J2;
+    M.c[2] = (J1 - J2) / J3;
+    if (q) std::memcpy(M.q, q, sizeof M.q);
+    if (r) std::memcpy(M.r, r, sizeof M.r);
+    ro->integrator = integrator;
+    ro->model = kModelAttitude;
     return HJB_OK;
 }
 
@@ -236,91 +373,57 @@ int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const in
     Rollout *ro = (Rollout *)rollout;
     if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
     std::lock_guard<std::mutex> g(ro->mu);
-    if (method != HJB_LOOKUP_NEAREST && method != HJB_LOOKUP_LINEAR) return rfail(ro, HJB_E_INVALID, "rollout: method %d", method);
-    if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
-    if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
-    if (!ro->model_set) return rfail(ro, HJB_E_INVALID, "rollout: run before hjb_rollout_set_model");
-    if (n_steps > 0 && !plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null plane_of_step");
-    for (int k = 0; k < n_steps; ++k)
-        if (plane_of_step[k] < 0 || plane_of_step[k] >= ro->n_planes)
-            return rfail(ro, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d)", k, plane_of_step[k], ro->n_planes);
+    const int bad_arg = check_run(ro, kModelAffine, method, n_steps, plane_of_step, n_traj);
+    if (bad_arg) return bad_arg;
     if (device_ms) *device_ms = 0.0;
     if (n_traj == 0) return HJB_OK;
     if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final");
-    const int D = ro->D, nu = ro->R.n_u;
+    const int D = ro->D;
     if (n_traj > INT64_MAX / (D * ((int64_t)n_steps + 1)) / 8) return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x D x n_steps)");
     const int64_t bad = first_nonfinite(X0, (int64_t)D * n_traj, true);
     if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    const int idx_bytes = ro->idx_bytes;
+    return run_chunks(ro, "hjb_rollout_run", D, 0, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, nullptr, device_ms,
+                      [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t st, double *dX0, double *dXf, double *dC,
+                          double *dXp, double *dUp, double *) {
+                          switch (idx_bytes) {
+                              case 1: launch_m<uint8_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
+                              case 2: launch_m<uint16_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
+                              default: launch_m<int32_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
+                          }
+                          return hipGetLastError();
+                      });
+}
 
-    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-    if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
-    const int64_t nc_max = std::min(n_traj, ro->chunk);
-    const size_t xb = (size_t)nc_max * D * sizeof(double);
-    const size_t xpb = X_path ? (size_t)nc_max * D * ((size_t)n_steps + 1) * sizeof(double) : 0;
-    const size_t upb = U_path ? (size_t)nc_max * nu * (size_t)n_steps * sizeof(double) : 0;
-    const size_t cb = cost ? (size_t)nc_max * sizeof(double) : 0;
-    const size_t pb = (size_t)std::max(n_steps, 1) * sizeof(int32_t);
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipMemGetInfo failed");
-    const size_t need = 2 * xb + xpb + upb + cb + pb;
-    if (need + ((size_t)64 << 20) > fr)
-        return rfail(ro, HJB_E_NOMEM, "rollout: a chunk of %lld trajectories needs %zu bytes, %zu free (lower option \"chunk\")",
-                     (long long)nc_max, need, fr);
-    void *bufs[6] = {};
-    auto done = [&](int code) {
-        for (void *p : bufs) if (p) (void)hipFree(p);
-        return code;
-    };
-    const size_t sizes[6] = {xb, xb, cb, xpb, upb, pb};
-    for (int b = 0; b < 6; ++b)
-        if (sizes[b] && hipMalloc(&bufs[b], sizes[b]) != hipSuccess) return done(rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", sizes[b]));
-    double *dX0 = (double *)bufs[0], *dXf = (double *)bufs[1], *dC = (double *)bufs[2], *dXp = (double *)bufs[3], *dUp = (double *)bufs[4];
-    hipStream_t st = ro->stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess && n_steps > 0) e = hipMemcpyAsync(bufs[5], plane_of_step, pb, hipMemcpyHostToDevice, st);
-    DRollout R = ro->R;
-    R.plane_of_step = (const int32_t *)bufs[5];
-    R.n_steps = n_steps;
-    const size_t lds = (size_t)(2 * (int64_t)R.n_knots + (int64_t)R.n_labels * nu) * sizeof(double);
-    const bool lds_on = lds <= kLdsMax;
-    double ms_total = 0;
-    for (int64_t i0 = 0; e == hipSuccess && i0 < n_traj; i0 += nc_max) {
-        const int64_t nc = std::min(nc_max, n_traj - i0);
-        e = hipMemcpyAsync(dX0, X0 + D * i0, (size_t)nc * D * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) break;
-        (void)hipEventRecord(e0, st);
-        switch (ro->idx_bytes) {
-            case 1: launch_m<uint8_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
-            case 2: launch_m<uint16_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
-            default: launch_m<int32_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
-        }
-        e = hipGetLastError();
-        if (e != hipSuccess) break;
-        (void)hipEventRecord(e1, st);
-        e = hipMemcpyAsync(X_final + D * i0, dXf, (size_t)nc * D * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && cost) e = hipMemcpyAsync(cost + i0, dC, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, st);
-        // paths: [nc, rows] on the device -> columns i0 .. i0+nc of [n_traj, rows] on the host
-        if (e == hipSuccess && X_path)
-            e = hipMemcpy2DAsync(X_path + i0, (size_t)n_traj * sizeof(double), dXp, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double),
-                                 (size_t)D * (n_steps + 1), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && U_path && n_steps > 0)
-            e = hipMemcpy2DAsync(U_path + i0, (size_t)n_traj * sizeof(double), dUp, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double),
-                                 (size_t)nu * n_steps, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        ms_total += ms;
+int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                 const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *A_path,
+                                 double *device_ms) {
+    Rollout *ro = (Rollout *)rollout;
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    const int bad_arg = check_run(ro, kModelAttitude, method, n_steps, plane_of_step, n_traj);
+    if (bad_arg) return bad_arg;
+    if (device_ms) *device_ms = 0.0;
+    if (n_traj == 0) return HJB_OK;
+    if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final");
+    if (n_traj > INT64_MAX / (HJB_ATT_W * ((int64_t)n_steps + 1)) / 8)
+        return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x 7 x n_steps)");
+    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_ATT_W * n_traj, true);
+    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    for (int64_t i = 0; i < n_traj; ++i) {
+        const double *q = X0 + HJB_ATT_W * i + 3;
+        if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)
+            return rfail(ro, HJB_E_INVALID, "rollout: X0 column %lld has an all-zero quaternion (0/0 at the first renormalisation)",
+                         (long long)i);
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return done(rfail(ro, HJB_E_DEVICE, "hjb_rollout_run: %s", hipGetErrorString(e)));
-    }
-    if (device_ms) *device_ms = ms_total;
-    return done(HJB_OK);
+    const int idx_bytes = ro->idx_bytes, integ = ro->integrator;
+    const DAttitude M = ro->M;
+    return run_chunks(ro, "hjb_rollout_run_attitude", HJB_ATT_W, 3, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path,
+                      A_path, device_ms,
+                      [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t st, double *dX0, double *dXf, double *dC,
+                          double *dXp, double *dUp, double *dAp) {
+                          return launch_rollout_attitude(idx_bytes, method, lds_on, integ, R, M, nc, lds, st, dX0, dXf, dC, dXp, dUp, dAp);
+                      });
 }
 
 int32_t hjb_rollout_destroy(void *rollout) {

@@ -223,8 +223,14 @@ SYMBOLS = {
                                     C.POINTER(C.c_double)]),
     "hjb_rollout_destroy": (C.c_int32, [C.c_void_p]),
     "hjb_rollout_last_error": (C.c_char_p, [C.c_void_p]),
+    "hjb_rollout_set_attitude_model": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_int32, C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_double)]),
+    "hjb_rollout_run_attitude": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]
+                                 + [C.POINTER(C.c_double)] * 7),
 }
 HJB_ROLLOUT_MAX_U = 4
+HJB_ATT_TAYLOR = 0
+HJB_ATT_RK4 = 1
 HJB_LOOKUP_NEAREST = 0
 HJB_LOOKUP_LINEAR = 1
 

@@ -134,6 +134,7 @@ class Rollout:
         if nS < 1 or lab.size % nS or lab.size == 0:
             raise ValueError("labels: %d elements are not a whole number of %d-state planes" % (lab.size, nS))
         self.n_planes = lab.size // nS
+        self.labels_dtype = lab.dtype
         ut = np.asarray(u_table, dtype=np.float64)
         ut = ut.reshape(-1, 1) if ut.ndim == 1 else ut
         self.n_labels, self.n_u = ut.shape
@@ -207,6 +208,40 @@ class Rollout:
         return {"X_final": Xf.T, "cost": cost,
                 "X_path": None if Xp is None else Xp.reshape((nt, D, K + 1), order="F"),
                 "U_path": None if Up is None else Up.reshape((nt, nu, K), order="F"),
+                "device_ms": ms.value}
+
+    def set_attitude_model(self, inertia, h, integrator="taylor", q=None, r=None):
+        """The 6-D attitude loop instead of the affine one (hjb_rollout_set_attitude_model; the last model set wins):
+        inertia = (J1, J2, J3), step h, integrator 'taylor' or 'RK4', stage-cost weights q [7] and r [3] (None: zeros).
+        Needs D = 6 axes in the order (w1, w2, w3, yaw, pitch, roll) and n_u = 3."""
+        integ = {"taylor": _abi.HJB_ATT_TAYLOR, "RK4": _abi.HJB_ATT_RK4, "rk4": _abi.HJB_ATT_RK4}[integrator]
+        J = np.ascontiguousarray(np.asarray(inertia, dtype=np.float64).reshape(3))
+        vec = lambda v, m: None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(m))
+        self._check(self.lib.hjb_rollout_set_attitude_model(self._ro, _f64p(J), float(h), integ, _f64p(vec(q, 7)), _f64p(vec(r, 3))))
+
+    def run_attitude(self, X0, plane_of_step, method="nearest", keep_path=False):
+        """hjb_rollout_run_attitude: X0 [7, n_traj] (X = [w1 w2 w3 q1 q2 q3 q4], q4 scalar).  Returns X_final [7, n_traj],
+        cost [n_traj], X_path [n_traj, 7, n_steps+1], U_path [n_traj, 3, n_steps], A_path [n_traj, 3, n_steps] (the yaw, pitch,
+        roll in radians each step looked up at; the paths None unless keep_path) and device_ms."""
+        X = np.asarray(X0, dtype=np.float64)
+        X = np.ascontiguousarray((X.reshape(7, 1) if X.ndim == 1 else X).reshape(7, -1).T)
+        nt = X.shape[0]
+        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
+        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
+            raise ValueError("plane_of_step does not fit int32")
+        ps = ps.astype(np.int32)
+        K = int(ps.size)
+        meth = {"nearest": _abi.HJB_LOOKUP_NEAREST, "linear": _abi.HJB_LOOKUP_LINEAR}[method]
+        Xf = np.empty((nt, 7))
+        cost = np.empty(nt)
+        Xp = np.empty(nt * 7 * (K + 1)) if keep_path else None
+        Up = np.empty(nt * 3 * K) if keep_path else None
+        Ap = np.empty(nt * 3 * K) if keep_path else None
+        ms = C.c_double(0.0)
+        self._check(self.lib.hjb_rollout_run_attitude(self._ro, meth, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X),
+                                                      _f64p(Xf), _f64p(cost), _f64p(Xp), _f64p(Up), _f64p(Ap), C.byref(ms)))
+        path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
+        return {"X_final": Xf.T, "cost": cost, "X_path": path(Xp, 7, K + 1), "U_path": path(Up, 3, K), "A_path": path(Ap, 3, K),
                 "device_ms": ms.value}
 
 

@@ -9,7 +9,8 @@ n_mesh_w = 1000); its intended semantics are the specification here, with small
 default sizes taken from the .asv revision.  The argmin returned is the true joint
 minimiser (i1,i2,i3) in cascade order; the reference's index composition at
 :290-292 is a linear-indexing bug and J is unaffected by it.
-Forward simulations (:508-591, :670-696, :744-925) are out of scope.
+Forward simulations (:508-591, :670-696, :744-925) run host-side in hjbdp/rollout.py; get_optimal_paths runs the
+closed loop of get_optimal_path (:744-833) for many initial attitudes at once on the GPU.
 """
 from __future__ import annotations
 
@@ -285,6 +286,55 @@ class Solver_attitude:
     def get_optimal_path(self, X0=None, method="nearest", n_steps=None):
         from . import rollout
         return rollout.attitude_optimal_path(self, X0, method, n_steps)       # :744-833 (after run)
+
+    def attitude_rollout(self, integrator="taylor"):
+        """The policy run() leaves, resident on the GPU with the attitude model set (hjbdp.Rollout, K17): the grid vectors
+        (w1, w2, w3, yaw, pitch, roll) in double (:759-764), one stationary plane of labels (i1-1) + nu (i2-1) + nu^2 (i3-1) + 1
+        built from U_idx (uint8 for the reference's 27), u_table [nu^3, 3] = the torque triples of U_vector rounded to float32 as
+        U1_Opt..U3_Opt hold them (:296-298), inertia (J1, J2, J3) and step h.  What get_optimal_paths runs; close it (or use it
+        as a context manager) when done."""
+        from .core import Rollout
+        if self.U_idx is None or self.U1_Opt is None or np.ndim(self.U1_Opt) != 6:
+            raise RuntimeError("run() first")
+        nu = len(self.U_vector)
+        i1, i2, i3 = (np.asarray(i, dtype=np.int64) - 1 for i in self.U_idx)
+        n_lab = nu ** 3
+        labels = (i1 + nu * i2 + nu * nu * i3 + 1).astype(np.uint8 if n_lab < 256 else np.uint16 if n_lab < 65536 else np.int32)
+        uv = self.U_vector.astype(f32).astype(np.float64)
+        c = np.arange(n_lab)
+        u_table = np.stack([uv[c % nu], uv[(c // nu) % nu], uv[c // (nu * nu)]], axis=1)
+        ro = Rollout(self.grid_vectors_full(), labels, u_table, index_base=1, device=self.device)
+        try:
+            ro.set_attitude_model([self.J1, self.J2, self.J3], self.h, integrator)
+        except Exception:
+            ro.close()
+            raise
+        return ro
+
+    def get_optimal_paths(self, X0s=None, method="nearest", n_steps=None, integrator="taylor"):
+        """get_optimal_path (:744-833) for many initial attitudes at once on the GPU (hjbdp.Rollout.run_attitude, K17), after
+        run().  X0s [7, n] (None: the reference's X0, :160-164).  Returns X [7, N, n], U [3, N, n] (last column zero) and
+        X_ANGLES [9, N, n] = [w; roll; pitch; yaw in degrees; U] (:780-782; last column zero), N = N_stage (or n_steps + 1).
+        The policy is the stationary plane the run leaves: labels (i1-1) + 3 (i2-1) + 9 (i3-1) + 1 from U_idx, u_table
+        U_vector rounded to float32 as U1_Opt..U3_Opt hold it (:296-298) - see attitude_rollout.  The angles come from the
+        library's fixed atan2 / asin (<= 2 ulp of libm, tested), so with 'nearest' X and U equal the host mirror's
+        get_optimal_path bit for bit wherever no angle lies within a few ulp of a cell midpoint."""
+        from .rollout import DEFAULT_X0_ATTITUDE
+        X0s = DEFAULT_X0_ATTITUDE.reshape(7, 1) if X0s is None else np.asarray(X0s, dtype=np.float64).reshape(7, -1)
+        N = self.N_stage if n_steps is None else min(self.N_stage, int(n_steps) + 1)
+        with self.attitude_rollout(integrator) as ro:
+            out = ro.run_attitude(X0s, np.zeros(N - 1, np.int32), method, keep_path=True)
+        n = X0s.shape[1]
+        X = np.ascontiguousarray(out["X_path"].transpose(1, 2, 0))
+        U = np.zeros((3, N, n))
+        U[:, :N - 1] = out["U_path"].transpose(1, 2, 0)
+        ang = out["A_path"].transpose(1, 2, 0)                                # yaw, pitch, roll [3, N-1, n]
+        XA = np.zeros((9, N, n))
+        XA[0:3, :N - 1] = X[0:3, :N - 1]
+        XA[3, :N - 1], XA[4, :N - 1], XA[5, :N - 1] = np.rad2deg(ang[2]), np.rad2deg(ang[1]), np.rad2deg(ang[0])
+        XA[6:9, :N - 1] = U[:, :N - 1]
+        self.paths_device_ms = out["device_ms"]
+        return X, U, XA
 
     def get_optimal_path_simplified_testode45(self, X0=None, n_steps=None):
         from . import rollout

@@ -7,8 +7,9 @@ Two cases, one JSON line:
                labels) swept over 1,999 stages, rolled out 'nearest' for 1,999 steps on its affine design model
                (x+ = x + h v, v+ = v + h/M sum f, theta+ = theta + h w, w+ = w + h d/J (f1 - f2 + f3 - f4)) from 2.7 * 10^5
                initial states; host rate: the same loop scalar in Python (interp_nearest_point + the update) over 100 of them.
+  (c) attitude: the 6-D attitude policy (K17, hjb_rollout_run_attitude), see case_attitude.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude] [--out FILE]
 """
 from __future__ import annotations
 
@@ -100,18 +101,59 @@ def case_pos_att(host=True, n_traj=270000, n_stages=1999):
     return res
 
 
+def case_attitude(host=True, n_traj=262144, n_steps=5999):
+    """(c) attitude: the reference-size 6-D policy (11^3 x 10^3 states, 27 labels in u8) from Solver_attitude.run(n_stages=19),
+    rolled out over the whole horizon (5,999 steps, 'taylor') with both methods from 2.6e5 initial attitudes (4 waves per SIMD
+    on 256 CUs); host rate: Solver_attitude.get_optimal_path (the scalar mirror) over 500 steps from 3 starts."""
+    import hjbdp
+    sa = hjbdp.Solver_attitude(11, 10)
+    t0 = time.perf_counter()
+    sa.run(n_stages=19)
+    sweep_s = time.perf_counter() - t0
+    rng = np.random.default_rng(3)
+    X0 = np.empty((7, n_traj))
+    X0[0:3] = rng.uniform(-0.5, 0.5, size=(3, n_traj))
+    ax = rng.normal(size=(3, n_traj))
+    ax /= np.sqrt((ax ** 2).sum(axis=0))
+    th = rng.uniform(0, 0.6, size=n_traj)
+    X0[3:6] = ax * np.sin(th / 2)
+    X0[6] = np.cos(th / 2)
+    planes = np.zeros(n_steps, np.int32)
+    res = {"grid": "11x11x11x10x10x10", "integrator": "taylor", "sweep_wall_s": round(sweep_s, 3)}
+    with sa.attitude_rollout("taylor") as ro:                    # the policy and model get_optimal_paths runs
+        res.update(labels=str(ro.labels_dtype), n_labels=int(ro.n_labels))
+        for method in ("nearest", "linear"):
+            ro.run_attitude(X0, planes, method)                   # warm-up, same shape
+            out = ro.run_attitude(X0, planes, method)
+            res[method] = {"n_traj": int(n_traj), "n_steps": int(n_steps), "device_ms": round(out["device_ms"], 3),
+                           "traj_steps_per_s": n_traj * n_steps / (out["device_ms"] * 1e-3)}
+    if host:
+        t0 = time.perf_counter()
+        for i in range(3):
+            sa.get_optimal_path(X0[:, i], "nearest", n_steps=500)
+        dt = time.perf_counter() - t0
+        res["host_loop"] = "Solver_attitude.get_optimal_path (scalar Python mirror), nearest"
+        res["host_traj_steps_per_s"] = 3 * 500 / dt
+        res["speedup_vs_host_nearest"] = res["nearest"]["traj_steps_per_s"] / res["host_traj_steps_per_s"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--cases", default="kirk,pos_att")
+    ap.add_argument("--out", default=None, help="also write the JSON to this file")
     a = ap.parse_args()
     import hjbdp
     if hjbdp.device_count() < 1:
         raise SystemExit("time_rollout needs a HIP device")
     res = {"tool": "time_rollout"}
     for c in a.cases.split(","):
-        res[c] = {"kirk": case_kirk, "pos_att": case_pos_att}[c](host=not a.no_host)
+        res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude}[c](host=not a.no_host)
     print(json.dumps(res))
+    if a.out:
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
 
 
 if __name__ == "__main__":
