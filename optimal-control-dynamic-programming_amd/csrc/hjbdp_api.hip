@@ -19,12 +19,9 @@ int policy_lookup_t(int32_t D, const int32_t *n, const double *const *knots, con
         for (int i = 0; i < n[a]; ++i) kk[i] = (T)knots[a][i];
         for (int i = 0; i + 1 < n[a]; ++i) rdx[i] = (T)1 / (T)(kk[i + 1] - kk[i]);     // increasing: hjb_policy_lookup checked
         rdx[n[a] - 1] = (T)0;
-        void *dk = nullptr, *dr = nullptr;
-        int st = upload(h, kk, &dk);
-        if (!st) st = upload(h, rdx, &dr);
+        int st = upload(h, kk, &L.knots[a]);
+        if (!st) st = upload(h, rdx, &L.rdx[a]);
         if (st) { for (void *d : h->allocs) (void)hipFree(d); return st; }
-        L.knots[a] = dk;
-        L.rdx[a] = dr;
         L.n[a] = n[a];
         L.stride[a] = s;
         s *= n[a];
@@ -38,8 +35,7 @@ int policy_lookup_t(int32_t D, const int32_t *n, const double *const *knots, con
         e = hipMemcpy(dV, values, (size_t)s * sizeof(T), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(dQ, queries, (size_t)nq * D * sizeof(T), hipMemcpyHostToDevice);
         if (e == hipSuccess) {
-            const int grid = (int)std::min<int64_t>((nq + 255) / 256, 65536);
-            dim3 g(std::max(grid, 1)), b(256);
+            dim3 g(std::max(prep_grid(nq), 1)), b(256);
             switch (D) {
                 case 1: hipLaunchKernelGGL((k_policy_lookup<T, 1>), g, b, 0, nullptr, L, (const T *)dV, nq, (const T *)dQ, (T *)dO); break;
                 case 2: hipLaunchKernelGGL((k_policy_lookup<T, 2>), g, b, 0, nullptr, L, (const T *)dV, nq, (const T *)dQ, (T *)dO); break;

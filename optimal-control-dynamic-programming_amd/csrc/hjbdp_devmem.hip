@@ -98,7 +98,7 @@ int32_t hjb_device_gather(int32_t device, const void *d_src, int32_t elem_bytes,
     if (e == hipSuccess) e = hipMalloc(&dout, (size_t)n_sel * elem_bytes);
     if (e == hipSuccess) e = hipMemcpy(dsel, sel, (size_t)n_sel * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_gather_bytes, dim3((unsigned)std::min<int64_t>((n_sel + 255) / 256, 65536)), dim3(256), 0, nullptr,
+        hipLaunchKernelGGL(k_gather_bytes, dim3((unsigned)prep_grid(n_sel)), dim3(256), 0, nullptr,
                            (const unsigned char *)d_src, elem_bytes, (const int64_t *)dsel, n_sel, (unsigned char *)dout);
         e = hipGetLastError();
     }

@@ -1,11 +1,17 @@
 // hjbdp_host.h - what the host-side translation units of libhjbdp share (internal; include/hjbdp.h is the public ABI):
 // the handle, error reporting, the process-wide locks and switches, and the entry points one unit offers the others.
-//   hjbdp_setup.hip    problem upload, stage-invariant tables, kernel choice and plans, the stage launch (hjb_create's work)
+//   hjbdp_setup.hip    process-wide state, device allocation, the problem upload, hjb_create's work as a list of steps, work buffers, probe
+//   hjbdp_tables.hip   the (cell, weight) tables: domains, builds, rebuild, hash; eligibility of variants 5 / 6; K9's examination and launch
+//   hjbdp_packed.hip   variant 1's analysis, variants 2 / 4 (outer terms, axis tables, contraction mode), the DNested upload, K15's set-up
+//   hjbdp_colsweep.hip variant 7's host side: plan, XCD map, DPP test, cooperative plan, launch record, split rule
+//   hjbdp_choose.hip   which variant serves, in which form and geometry (Handle::L), and the stage launch
 //   hjbdp_api.hip      hjb_create .. hjb_solve, options, probe, policy lookup (the single-device C ABI)
+//   hjbdp_batch.hip    hjb_solve_batch (several sweeps of one kernel shape, one launch per stage)
 //   hjbdp_builder.hip  the flat builder API (MATLAB loadlibrary / calllib)
 //   hjbdp_multi.hip    hjb_create_multi / hjb_solve_multi (one process, several GPUs)
 //   hjbdp_rank.hip     hjb_rank_* (one process per GPU) and the RCCL transport inside the library
 //   hjbdp_devmem.hip   device-buffer helpers
+//   rollout.hip, rollout_attitude.hip   hjb_rollout_*: closed-loop rollouts of stored policies (error reporting and locks only)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -189,40 +195,88 @@ inline hipError_t sync_setup() { return hipStreamSynchronize(nullptr); }
     } while (0)
 
 int dev_alloc(Handle *h, size_t bytes, void **out);
-template <typename T>
-int upload(Handle *h, const std::vector<T> &v, void **out) {
+template <typename X>           // ... into a typed pointer (assigned on success only)
+int dev_alloc(Handle *h, size_t bytes, X **out) {
+    void *d = nullptr;
+    const int st = dev_alloc(h, bytes, &d);
+    if (!st) *out = (X *)d;
+    return st;
+}
+template <typename T, typename X>
+int upload(Handle *h, const std::vector<T> &v, X **out) {
     void *d = nullptr;
     const int ast = dev_alloc(h, std::max<size_t>(v.size(), 1) * sizeof(T), &d);
     if (ast) return ast;
     if (!v.empty()) HIP_TRY(h, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = d;
+    *out = (X *)d;
     return HJB_OK;
 }
 
-int dev_alloc(Handle *h, size_t bytes, void **out);
-
 // hjbdp_setup.hip
 int64_t term_elems(const hjb_problem *p, uint32_t mask);
+inline int first_term(const hjb_term *t, int lo, int hi, uint32_t bits) {      // the first of terms [lo, hi) that depends on a dim of `bits`
+    int k = lo;                                                                 // (none: max(lo, hi))
+    while (k < hi && !(t[k].mask & bits)) ++k;
+    return k;
+}
 int build_handle(Handle *h, const hjb_problem *p);       // upload + analysis of a validated problem (float32 / float64 arithmetic by p->dtype)
 void halo_of_problem(const hjb_problem *p, bool tab64, int *lo, int *hi);     // the halo the last axis' terms imply
-int ensure_axis0_table(Handle *h);
-int rebuild_tables(Handle *h, bool mfma);
-int table_hash(Handle *h, uint64_t *out);
-int uniwin_options(Handle *h);       // K15's tiling from the options, uploaded (the device is synchronised first)
-inline bool uniwin_active(const Handle *h) {
-    return h->uniwin_ok && (h->packed_pre == 5 || h->packed_pre == 6) && (h->uniwin_on == 1 || (h->uniwin_on < 0 && h->uniwin_auto));
-}
-int colsweep_options(Handle *h, bool remap);   // variant 7's launch-time fields from the options, uploaded (remap: the XCD map too)
-int examine_tile2d(Handle *h);
-int launch_tile2d(Handle *h, const void *dJn, void *dJo, void *didx, int K, hipStream_t st);
-int variant_status(Handle *h, int v, const char **why);   // what variant v needs of the handle (builds what it reads)
-void choose_launch(Handle *h);       // the variant, its form and geometry -> Handle::L
-void launch_changed(Handle *h);      // after a change to Handle::L: what depends on the grid; the captured graph is dropped
-int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t st);
 int ensure_work(Handle *h);
 int check_status(Handle *h, hipStream_t st);
 int make_probe(Handle *h, const hjb_probe *pb, DProbe *out);
 int launch_probe(Handle *h, const DProbe &pr, const void *dJn, hipStream_t st);
+
+// hjbdp_tables.hip
+// An axis' broadcast domain: the dims (states, then controls) its next-state terms depend on, dense and column-major over the grid
+// this handle sweeps.  dsz: each dim's size (1 outside the domain), stride: its entry stride (0 outside).
+struct AxisDomain {
+    uint32_t mask = 0;
+    int64_t entries = 1;
+    std::vector<int32_t> dsz;
+    int32_t stride[HJB_MAX_G] = {0};
+    bool has(int d) const { return (mask >> d) & 1u; }
+};
+uint32_t axis_mask(const hjb_problem *p, int a);              // union of the masks of axis a's next-state terms
+AxisDomain axis_domain(const Handle *h, uint32_t mask);
+inline int prep_grid(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 65536); }      // 256-thread blocks of a grid-stride kernel over n items
+int build_axis_table(Handle *h, int a, const AxisDomain &dom, bool wait);     // variants 2 / 4: axis a's table allocated, launched, registered
+int ensure_axis0_table(Handle *h);
+int ensure_tabled(Handle *h);
+void analyse_tabled(Handle *h, const hjb_problem *p, size_t entry_bytes);     // variants 5 / 6 eligibility (build_handle's step)
+int rebuild_tables(Handle *h, bool mfma);
+int table_hash(Handle *h, uint64_t *out);
+int examine_tile2d(Handle *h);
+int launch_tile2d(Handle *h, const void *dJn, void *dJo, void *didx, int K, hipStream_t st);
+
+// hjbdp_packed.hip (analyse_nested .. setup_uniwin: build_handle's steps, in its order)
+void analyse_nested(Handle *h, const hjb_problem *p, size_t elem_bytes);
+void analyse_packed(Handle *h, const hjb_problem *p);
+int build_packed_tables(Handle *h, const hjb_problem *p);
+int upload_nested(Handle *h);
+int setup_uniwin(Handle *h, const hjb_problem *p);
+int uniwin_options(Handle *h);       // K15's tiling from the options, uploaded (the device is synchronised first)
+inline bool uniwin_active(const Handle *h) {
+    return h->uniwin_ok && (h->packed_pre == 5 || h->packed_pre == 6) && (h->uniwin_on == 1 || (h->uniwin_on < 0 && h->uniwin_auto));
+}
+
+// hjbdp_colsweep.hip
+int ensure_colsweep(Handle *h);                // variant 7's eligibility and plan, examined once (Handle::cs_state)
+int colsweep_options(Handle *h, bool remap);   // variant 7's launch-time fields from the options, uploaded (remap: the XCD map too)
+bool colsweep_usual_cost(const Handle *h);     // state terms + one control term
+
+// hjbdp_choose.hip
+int variant_status(Handle *h, int v, const char **why);   // what variant v needs of the handle (builds what it reads)
+void choose_launch(Handle *h);       // the variant, its form and geometry -> Handle::L
+void launch_changed(Handle *h);      // after a change to Handle::L: what depends on the grid; the captured graph is dropped
+int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t st);
+// the handle's part of a stage launch: stream, typing, parameter records, buffers (grid, block, LDS and the form are the caller's)
+inline StageArgs stage_args(const Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t st) {
+    StageArgs a;
+    a.st = st; a.dtype = h->dtype; a.D = h->hp.D;
+    a.dp = h->dp; a.dn = h->dn; a.dtb = h->dtb; a.dcs = h->dcs;
+    a.Jn = dJn; a.Jo = dJo; a.idx = didx;
+    return a;
+}
 
 // First element of a term / table array that is not finite (-1: all finite).  The kernels' contract covers finite data only
 // (DESIGN.md section 2): a NaN in a table is refused where it enters, with its place named, not found in J 2000 stages later.
