@@ -393,6 +393,33 @@ int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps,
                                  const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *A_path,
                                  double *device_ms);
 
+/* The 13-state pos-att closed loop (pos-att/Solver_pos_att.m:452-730, get_optimal_path after simplified_run) on three rollout
+ * objects, one per channel (x, y, z), each D == 4 over (position, velocity, angle, rate) with n_u == 4 thruster levels per label
+ * (f0 f1 f6 f7 / f2 f3 f8 f9 / f4 f5 f10 f11), on one device, in one label type.  hjb_rollout_set_pos_att_model attaches the model
+ * to rollout_x (it replaces, and is replaced by, the other two models: the last one set wins) and takes a share of rollout_y's
+ * and rollout_z's device data as they are at the call: destroying those two afterwards is SAFE, rollout_x keeps what it reads
+ * alive until it is destroyed or given another model; they stay ordinary objects.  inertia [3, 3] and rsw2eci [3, 3] (RSW2ECI of
+ * the target's R0, V0, :831-847) column-major, finite, determinant not 0; mass, h finite and > 0; t_dist finite; substeps >= 1;
+ * orbit_coef [5, n_nodes] column-major, finite, n_nodes == 2 * substeps * k + 1: node j holds, at t = j * h / (2 * substeps),
+ *   2mu/|R|^3 + H^2/|R|^4,  2 (R.V) H/|R|^4,  2H/|R|^2,  mu/|R|^3 - H^2/|R|^4,  mu/|R|^3     (R, V the target's state, H = |R x V|):
+ * all the right-hand side (:705-727) needs of the orbit.  hjb_rollout_run_pos_att steps X = [x(3) v(3) q(4) w(3)] (q4 scalar)
+ * n_steps <= (n_nodes - 1) / (2 * substeps) stages, all in double, left to right, every product rounded; stage k:
+ *   t_i = 2 * asinc(clamp(X[6+i], -1, 1));  xb = (ECI2body(q) * rsw2eci) x,  vb likewise (:411-415);
+ *   the 'nearest' lookups of plane plane_of_step[k]: channel x at (xb0, vb0, t_y, w_y), y at (xb1, vb1, t_z, w_z), z at
+ *   (xb2, vb2, t_x, w_x) (:434-447); U_M and a = rsw2eci^-1 (ECI2body(q)^-1 a_body) (:804-823), each inverse the adjugate over
+ *   the determinant (q is not renormalised, as in the reference, so ECI2body(q) is only nearly orthogonal);
+ *   `substeps` classical RK4 steps of h / substeps with a and U_M held, w_dot = inertia^-1 (U_M - w x (inertia w)).
+ * X0, X_final [13, n_traj]; X_path [n_traj, 13, n_steps+1]; F_path [n_traj, 12, n_steps] (f0..f11); FM_path [n_traj, 6, n_steps]
+ * (a_x a_y a_z U_M, :502); NULL paths are not written.  plane_of_step indexes the planes of all three channels.  A non-finite
+ * X0 is HJB_E_INVALID; a state that leaves the grids or stops being finite during the run is looked up at the clamped cell
+ * (NaN: cell 0) and the run completes.  hjb_rollout_run / hjb_rollout_run_attitude on a pos-att object, and
+ * hjb_rollout_run_pos_att on any other, are HJB_E_INVALID. */
+int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *rollout_z, const double *inertia, double mass,
+                                      double t_dist, double h, int32_t substeps, const double *rsw2eci, int32_t n_nodes,
+                                      const double *orbit_coef);
+int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
+                                double *X_final, double *X_path, double *F_path, double *FM_path);
+
 /* ---- flat builder API -------------------------------------------------------------------------------------------
  * hjb_problem holds arrays of structs with pointers, which MATLAB's loadlibrary/calllib cannot marshal.  These entry
  * points take primitives and plain arrays only, copy what they are given (the caller may free it at once), and end in

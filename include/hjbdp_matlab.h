@@ -101,4 +101,11 @@ int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, dou
 int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                                  const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *A_path,
                                  double *device_ms);
+/* the 13-state pos-att loop on three channel objects (pos-att/Solver_pos_att.m:452-730, get_optimal_path after simplified_run);
+ * usage: matlab/Solver_pos_att_hjbdp_get_optimal_paths.m */
+int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *rollout_z, const double *inertia, double mass,
+                                      double t_dist, double h, int32_t substeps, const double *rsw2eci, int32_t n_nodes,
+                                      const double *orbit_coef);
+int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
+                                double *X_final, double *X_path, double *F_path, double *FM_path);
 #endif

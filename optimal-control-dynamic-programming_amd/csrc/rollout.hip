@@ -1,14 +1,38 @@
 // rollout.hip - hjb_rollout_*: batched closed-loop rollouts of a stored per-stage policy (include/hjbdp.h; kernels:
-// kernels_rollout.h for the affine model, kernels_rollout_attitude.h / rollout_attitude.hip for the attitude model).
+// kernels_rollout.h for the affine model, kernels_rollout_attitude.h / rollout_attitude.hip for the attitude model,
+// kernels_rollout_pos_att.h / rollout_pos_att.hip for the pos-att model).
 #include "hjbdp_host.h"
 #include "kernels_rollout.h"
 #include "kernels_rollout_attitude.h"
+#include "kernels_rollout_pos_att.h"
+#include <memory>
 
 using namespace hjbhost;
 
 namespace {
 
-enum { kModelNone = 0, kModelAffine = 1, kModelAttitude = 2 };    // the last setter called wins
+enum { kModelNone = 0, kModelAffine = 1, kModelAttitude = 2, kModelPosAtt = 3 };    // the last setter called wins
+
+// Device allocations with shared ownership: an object's grid, table and labels live as long as the object or a pos-att model that
+// reads them (hjb_rollout_set_pos_att_model on another object) does.  Freed under the last owner's locks (destroy / set_*model).
+struct DevData {
+    int device = 0;
+    std::vector<void *> allocs;
+    ~DevData() {
+        if (allocs.empty()) return;
+        (void)hipSetDevice(device);
+        for (void *p : allocs) (void)hipFree(p);
+    }
+};
+
+// The pos-att model of channel x's object: the y and z channels' descriptors with their device data kept alive, the constants
+struct PosAtt {
+    DPaChan cy{}, cz{};
+    std::shared_ptr<DevData> data_y, data_z, coef;
+    DPosAtt M{};
+    int n_planes = 0;               // of the three channels, the fewest
+    int max_steps = 0;              // (n_nodes - 1) / (2 substeps)
+};
 
 struct Rollout {
     std::mutex mu;                  // one call at a time per object
@@ -17,7 +41,8 @@ struct Rollout {
     int64_t chunk = (int64_t)1 << 20;
     DRollout R{};                   // device pointers filled by create; model by set_model
     DAttitude M{};                  // the attitude model (set_attitude_model)
-    std::vector<void *> allocs;
+    std::unique_ptr<PosAtt> pa;     // the pos-att model (set_pos_att_model)
+    std::shared_ptr<DevData> data;
     hipStream_t stream = nullptr;
     std::string err;
 };
@@ -37,8 +62,8 @@ int rfail(Rollout *ro, int code, const char *fmt, ...) {
 }
 
 void release(Rollout *ro) {
-    for (void *p : ro->allocs) (void)hipFree(p);
-    ro->allocs.clear();
+    ro->pa.reset();
+    ro->data.reset();
     if (ro->stream) (void)hipStreamDestroy(ro->stream);
     ro->stream = nullptr;
 }
@@ -91,31 +116,54 @@ int check_run(Rollout *ro, int want, int method, int32_t n_steps, const int32_t 
     if (method != HJB_LOOKUP_NEAREST && method != HJB_LOOKUP_LINEAR) return rfail(ro, HJB_E_INVALID, "rollout: method %d", method);
     if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
     if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
-    if (ro->model == kModelNone)
-        return rfail(ro, HJB_E_INVALID, want == kModelAffine ? "rollout: run before hjb_rollout_set_model"
-                                                             : "rollout: run before hjb_rollout_set_attitude_model");
+    static const char *const setter[] = {"", "hjb_rollout_set_model", "hjb_rollout_set_attitude_model", "hjb_rollout_set_pos_att_model"};
+    static const char *const runner[] = {"", "hjb_rollout_run", "hjb_rollout_run_attitude", "hjb_rollout_run_pos_att"};
+    static const char *const held[] = {"", "affine", "attitude", "pos-att"};
+    if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: run before %s", setter[want]);
     if (ro->model != want)
-        return rfail(ro, HJB_E_INVALID, want == kModelAffine
-                     ? "rollout: the object holds the attitude model (hjb_rollout_set_attitude_model): call hjb_rollout_run_attitude"
-                     : "rollout: the object holds the affine model (hjb_rollout_set_model): call hjb_rollout_run");
+        return rfail(ro, HJB_E_INVALID, "rollout: the object holds the %s model (%s): call %s", held[ro->model], setter[ro->model],
+                     runner[ro->model]);
     if (n_steps > 0 && !plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null plane_of_step");
+    const int n_planes = want == kModelPosAtt ? ro->pa->n_planes : ro->n_planes;
     for (int k = 0; k < n_steps; ++k)
-        if (plane_of_step[k] < 0 || plane_of_step[k] >= ro->n_planes)
-            return rfail(ro, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d)", k, plane_of_step[k], ro->n_planes);
+        if (plane_of_step[k] < 0 || plane_of_step[k] >= n_planes)
+            return rfail(ro, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d)", k, plane_of_step[k], n_planes);
     return HJB_OK;
 }
 
-// The chunk loop both run functions share: W doubles of state per trajectory; per step n_u controls and n_e more path rows
-// (E_path: the attitude loop's angles).  Per chunk: upload X0, launch(R, nc, lds, lds_on, stream, X0, Xf, cost, Xp, Up, Ep) (the
+// what K18 reads of an object's policy (kernels_rollout_pos_att.h)
+DPaChan pa_channel(const DRollout &R) {
+    DPaChan c{};
+    for (int a = 0; a < 4; ++a) {
+        c.n[a] = R.n[a];
+        c.koff[a] = R.koff[a];
+        c.uniform[a] = R.uniform[a];
+        c.x0[a] = R.x0[a];
+        c.inv_h[a] = R.inv_h[a];
+        c.stride[a] = R.stride[a];
+    }
+    c.nS = R.nS;
+    c.n_knots = R.n_knots;
+    c.n_labels = R.n_labels;
+    c.index_base = R.index_base;
+    c.knots = R.knots;
+    c.rdx = R.rdx;
+    c.u_table = R.u_table;
+    c.labels = R.labels;
+    return c;
+}
+
+// The chunk loop the run functions share: W doubles of state per trajectory; per step n_up control rows (U_path) and n_e more
+// path rows (E_path: the attitude loop's angles, the pos-att loop's Force_Moment).  Per chunk: upload X0, launch(R, nc, lds, lds_on, stream, X0, Xf, cost, Xp, Up, Ep) (the
 // kernel of the entry point `who`), download X_final / cost and the paths ([nc, rows] on the device -> columns i0 .. i0+nc of
 // [n_traj, rows] on the host); device_ms sums the launches' event times.
 template <typename Launch>
-int run_chunks(Rollout *ro, const char *who, int W, int n_e, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *E_path, double *device_ms,
                Launch launch) {
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
-    const int nu = ro->R.n_u;
+    const int nu = n_up;
     const int64_t nc_max = std::min(n_traj, ro->chunk);
     const size_t xb = (size_t)nc_max * W * sizeof(double);
     const size_t xpb = X_path ? (size_t)nc_max * W * ((size_t)n_steps + 1) * sizeof(double) : 0;
@@ -147,7 +195,7 @@ int run_chunks(Rollout *ro, const char *who, int W, int n_e, int32_t n_steps, co
     DRollout R = ro->R;
     R.plane_of_step = (const int32_t *)bufs[5];
     R.n_steps = n_steps;
-    const size_t lds = (size_t)(2 * (int64_t)R.n_knots + (int64_t)R.n_labels * nu) * sizeof(double);
+    const size_t lds = (size_t)(2 * (int64_t)R.n_knots + (int64_t)R.n_labels * R.n_u) * sizeof(double);
     const bool lds_on = lds <= kLdsMax;
     double ms_total = 0;
     for (int64_t i0 = 0; e == hipSuccess && i0 < n_traj; i0 += nc_max) {
@@ -248,6 +296,8 @@ int32_t hjb_rollout_create(int32_t device, int32_t D, const int32_t *n, const do
     ro->D = D;
     ro->idx_bytes = idx_bytes;
     ro->n_planes = n_planes;
+    ro->data = std::make_shared<DevData>();
+    ro->data->device = device;
     DRollout &R = ro->R;
     R.n_u = n_u;
     R.n_labels = n_labels;
@@ -274,7 +324,7 @@ int32_t hjb_rollout_create(int32_t device, int32_t D, const int32_t *n, const do
     auto dev_upload = [&](const void *src, size_t bytes, void **out) -> int {
         void *d = nullptr;
         if (hipMalloc(&d, std::max<size_t>(bytes, 16)) != hipSuccess) return rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", bytes);
-        ro->allocs.push_back(d);
+        ro->data->allocs.push_back(d);
         if (hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "rollout: upload failed");
         *out = d;
         return HJB_OK;
@@ -321,6 +371,10 @@ int32_t hjb_rollout_set_model(void *rollout, const double *A, const double *B, c
     if (r) std::memcpy(R.r, r, sizeof(double) * nu);
     R.has_c = c ? 1 : 0;
     ro->model = kModelAffine;
+    if (ro->pa) {                                     // the pos-att model goes, and with it its hold on the other two channels
+        std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+        ro->pa.reset();
+    }
     return HJB_OK;
 }
 
@@ -353,6 +407,90 @@ int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, dou
     if (r) std::memcpy(M.r, r, sizeof M.r);
     ro->integrator = integrator;
     ro->model = kModelAttitude;
+    if (ro->pa) {                                     // the pos-att model goes, and with it its hold on the other two channels
+        std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+        ro->pa.reset();
+    }
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *rollout_z, const double *inertia, double mass,
+                                      double t_dist, double h, int32_t substeps, const double *rsw2eci, int32_t n_nodes,
+                                      const double *orbit_coef) {
+    Rollout *rx = (Rollout *)rollout_x, *ry = (Rollout *)rollout_y, *rz = (Rollout *)rollout_z;
+    // the arguments that need no object first (decided without a device), then the objects
+    if (!inertia || !rsw2eci || !orbit_coef) return rfail(rx, HJB_E_INVALID, "rollout: null argument (inertia, rsw2eci and orbit_coef are required)");
+    if (!all_finite(inertia, 9)) return rfail(rx, HJB_E_INVALID, "rollout: inertia is not finite");
+    if (!all_finite(rsw2eci, 9)) return rfail(rx, HJB_E_INVALID, "rollout: rsw2eci is not finite");
+    if (!(std::isfinite(mass) && mass > 0)) return rfail(rx, HJB_E_INVALID, "rollout: mass = %g is not finite and > 0", mass);
+    if (!std::isfinite(t_dist)) return rfail(rx, HJB_E_INVALID, "rollout: t_dist = %g is not finite", t_dist);
+    if (!(std::isfinite(h) && h > 0)) return rfail(rx, HJB_E_INVALID, "rollout: h = %g is not finite and > 0", h);
+    if (substeps < 1) return rfail(rx, HJB_E_INVALID, "rollout: substeps = %d < 1", substeps);
+    if (n_nodes < 1 || (n_nodes - 1) % (2 * (int64_t)substeps) != 0)
+        return rfail(rx, HJB_E_INVALID, "rollout: n_nodes = %d is not 2 * substeps * k + 1 (substeps = %d)", n_nodes, substeps);
+    const int64_t bad = first_nonfinite(orbit_coef, 5 * (int64_t)n_nodes, true);
+    if (bad >= 0) return rfail(rx, HJB_E_INVALID, "rollout: orbit_coef element %lld is not finite", (long long)bad);
+    DPosAtt M{};
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {                       // column-major in, row-major kept
+            M.J[3 * r + c] = inertia[r + 3 * c];
+            M.RSW[3 * r + c] = rsw2eci[r + 3 * c];
+        }
+    const double dj = pa_det3(M.J), dr = pa_det3(M.RSW);
+    if (!(std::isfinite(dj) && dj != 0.0)) return rfail(rx, HJB_E_INVALID, "rollout: inertia is singular (determinant %g)", dj);
+    if (!(std::isfinite(dr) && dr != 0.0)) return rfail(rx, HJB_E_INVALID, "rollout: rsw2eci is singular (determinant %g)", dr);
+    pa_inv3(M.J, M.Jinv);
+    pa_inv3(M.RSW, M.RSWinv);
+    if (!all_finite(M.Jinv, 9)) return rfail(rx, HJB_E_INVALID, "rollout: inertia is singular (its inverse is not finite)");
+    if (!all_finite(M.RSWinv, 9)) return rfail(rx, HJB_E_INVALID, "rollout: rsw2eci is singular (its inverse is not finite)");
+    M.mass = mass;
+    M.t_dist = t_dist;
+    M.hs = h / substeps;
+    M.substeps = substeps;
+    if (!rx || !ry || !rz) return rfail(rx, HJB_E_INVALID, "rollout: null handle (three channel objects are required)");
+    if (rx == ry || rx == rz || ry == rz) return rfail(rx, HJB_E_INVALID, "rollout: the same object passed for two channels");
+    auto pa = std::make_unique<PosAtt>();
+    pa->M = M;
+    pa->max_steps = (int)((n_nodes - 1) / (2 * (int64_t)substeps));
+    // y and z: a snapshot of the policy with a share of its device data, taken under that object's own lock
+    int dev_o[2] = {0, 0}, idx_o[2] = {0, 0}, planes_o[2] = {0, 0};
+    Rollout *others[2] = {ry, rz};
+    const char *names[2] = {"rollout_y", "rollout_z"};
+    for (int t = 0; t < 2; ++t) {
+        Rollout *o = others[t];
+        std::lock_guard<std::mutex> g(o->mu);
+        if (o->D != 4 || o->R.n_u != 4)
+            return rfail(rx, HJB_E_INVALID, "rollout: the pos-att model needs D == 4 and n_u == 4 (%s: D=%d, n_u=%d)", names[t], o->D, o->R.n_u);
+        (t == 0 ? pa->cy : pa->cz) = pa_channel(o->R);
+        (t == 0 ? pa->data_y : pa->data_z) = o->data;
+        dev_o[t] = o->device;
+        idx_o[t] = o->idx_bytes;
+        planes_o[t] = o->n_planes;
+    }
+    std::lock_guard<std::mutex> g(rx->mu);
+    if (rx->D != 4 || rx->R.n_u != 4)
+        return rfail(rx, HJB_E_INVALID, "rollout: the pos-att model needs D == 4 and n_u == 4 (rollout_x: D=%d, n_u=%d)", rx->D, rx->R.n_u);
+    for (int t = 0; t < 2; ++t) {
+        if (dev_o[t] != rx->device)
+            return rfail(rx, HJB_E_INVALID, "rollout: %s is on device %d, rollout_x on device %d", names[t], dev_o[t], rx->device);
+        if (idx_o[t] != rx->idx_bytes)
+            return rfail(rx, HJB_E_INVALID, "rollout: %s has %d-byte labels, rollout_x %d-byte labels (the three channels share one label type)",
+                         names[t], idx_o[t], rx->idx_bytes);
+    }
+    pa->n_planes = std::min(rx->n_planes, std::min(planes_o[0], planes_o[1]));
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    if (hipSetDevice(rx->device) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "hipSetDevice failed");
+    pa->coef = std::make_shared<DevData>();
+    pa->coef->device = rx->device;
+    const size_t cb = (size_t)5 * n_nodes * sizeof(double);
+    void *d = nullptr;
+    if (hipMalloc(&d, cb) != hipSuccess) return rfail(rx, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", cb);
+    pa->coef->allocs.push_back(d);
+    if (hipMemcpy(d, orbit_coef, cb, hipMemcpyHostToDevice) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "rollout: upload failed");
+    pa->M.coef = (const double *)d;
+    if (rx->stream) (void)hipStreamSynchronize(rx->stream);
+    rx->pa = std::move(pa);                                 // replaces (and releases) a model set earlier
+    rx->model = kModelPosAtt;
     return HJB_OK;
 }
 
@@ -383,7 +521,7 @@ int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const in
     const int64_t bad = first_nonfinite(X0, (int64_t)D * n_traj, true);
     if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
     const int idx_bytes = ro->idx_bytes;
-    return run_chunks(ro, "hjb_rollout_run", D, 0, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, nullptr, device_ms,
+    return run_chunks(ro, "hjb_rollout_run", D, ro->R.n_u, 0, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, nullptr, device_ms,
                       [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t st, double *dX0, double *dXf, double *dC,
                           double *dXp, double *dUp, double *) {
                           switch (idx_bytes) {
@@ -418,11 +556,45 @@ int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps,
     }
     const int idx_bytes = ro->idx_bytes, integ = ro->integrator;
     const DAttitude M = ro->M;
-    return run_chunks(ro, "hjb_rollout_run_attitude", HJB_ATT_W, 3, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path,
+    return run_chunks(ro, "hjb_rollout_run_attitude", HJB_ATT_W, HJB_ATT_U, 3, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path,
                       A_path, device_ms,
                       [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t st, double *dX0, double *dXf, double *dC,
                           double *dXp, double *dUp, double *dAp) {
                           return launch_rollout_attitude(idx_bytes, method, lds_on, integ, R, M, nc, lds, st, dX0, dXf, dC, dXp, dUp, dAp);
+                      });
+}
+
+int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
+                                double *X_final, double *X_path, double *F_path, double *FM_path) {
+    Rollout *ro = (Rollout *)rollout_x;
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    const int bad_arg = check_run(ro, kModelPosAtt, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
+    if (bad_arg) return bad_arg;
+    const PosAtt &pa = *ro->pa;
+    if (n_steps > pa.max_steps)
+        return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the orbit table covers %d stages ((n_nodes - 1) / (2 substeps))", n_steps,
+                     pa.max_steps);
+    if (n_traj == 0) return HJB_OK;
+    if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final");
+    if (n_traj > INT64_MAX / (HJB_PA_W * ((int64_t)n_steps + 1)) / 8)
+        return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x 13 x n_steps)");
+    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_PA_W * n_traj, true);
+    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    const int idx_bytes = ro->idx_bytes;
+    const DPaChan cx0 = pa_channel(ro->R);
+    const size_t lds3 = (size_t)(2 * ((int64_t)cx0.n_knots + pa.cy.n_knots + pa.cz.n_knots) +
+                                 4 * ((int64_t)cx0.n_labels + pa.cy.n_labels + pa.cz.n_labels)) * sizeof(double);
+    const bool lds3_on = lds3 <= kLdsMax;
+    return run_chunks(ro, "hjb_rollout_run_pos_att", HJB_PA_W, HJB_PA_F, HJB_PA_FM, n_steps, plane_of_step, n_traj, X0, X_final, nullptr,
+                      X_path, F_path, FM_path, nullptr,
+                      [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *, double *dXp,
+                          double *dFp, double *dFMp) {
+                          DPaChan cx = cx0, cy = pa.cy, cz = pa.cz;
+                          cx.plane_of_step = cy.plane_of_step = cz.plane_of_step = R.plane_of_step;
+                          DPosAtt M = pa.M;
+                          M.n_steps = R.n_steps;
+                          return launch_rollout_pos_att(idx_bytes, lds3_on, cx, cy, cz, M, nc, lds3, st, dX0, dXf, dXp, dFp, dFMp);
                       });
 }
 

@@ -227,6 +227,9 @@ SYMBOLS = {
                                                    C.POINTER(C.c_double)]),
     "hjb_rollout_run_attitude": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]
                                  + [C.POINTER(C.c_double)] * 7),
+    "hjb_rollout_set_pos_att_model": (C.c_int32, [C.c_void_p] * 3 + [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_int32,
+                                                  C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)]),
+    "hjb_rollout_run_pos_att": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64] + [C.POINTER(C.c_double)] * 5),
 }
 HJB_ROLLOUT_MAX_U = 4
 HJB_ATT_TAYLOR = 0

@@ -244,6 +244,41 @@ class Rollout:
         return {"X_final": Xf.T, "cost": cost, "X_path": path(Xp, 7, K + 1), "U_path": path(Up, 3, K), "A_path": path(Ap, 3, K),
                 "device_ms": ms.value}
 
+    def set_pos_att_model(self, rollout_y, rollout_z, inertia, mass, t_dist, h, rsw2eci, orbit_coef, substeps=1):
+        """The 13-state pos-att loop (hjb_rollout_set_pos_att_model; the last model set wins) with this object as channel x and
+        two more Rollout objects as channels y and z (each D = 4 over (position, velocity, angle, rate), n_u = 4, one device, one
+        label type).  inertia [3, 3], rsw2eci [3, 3] and orbit_coef [n_nodes, 5] as hjbdp.rollout.pos_att_orbit_table builds them
+        (n_nodes = 2 * substeps * k + 1).  The model keeps what it reads of the other two alive: they may be closed afterwards."""
+        m3 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(3, 3).reshape(-1, order="F"))
+        J, rsw = m3(inertia), m3(rsw2eci)
+        coef = np.ascontiguousarray(np.asarray(orbit_coef, dtype=np.float64).reshape(-1, 5))
+        self._check(self.lib.hjb_rollout_set_pos_att_model(self._ro, rollout_y._ro, rollout_z._ro, _f64p(J), float(mass), float(t_dist),
+                                                           float(h), int(substeps), _f64p(rsw), int(coef.shape[0]), _f64p(coef)))
+        self._pa_steps = (coef.shape[0] - 1) // (2 * int(substeps))
+
+    def run_pos_att(self, X0, plane_of_step=None, keep_path=False):
+        """hjb_rollout_run_pos_att: X0 [13, n_traj] (X = [x(3) v(3) q(4) w(3)], q4 scalar).  plane_of_step None: every stage the
+        orbit table covers, on plane 0 (stationary policies).  Returns X_final [13, n_traj] and X_path [n_traj, 13, n_steps+1], F_path [n_traj, 12, n_steps]
+        (f0..f11), FM_path [n_traj, 6, n_steps] (a_x a_y a_z U_M); the paths None unless keep_path."""
+        X = np.asarray(X0, dtype=np.float64)
+        X = np.ascontiguousarray((X.reshape(13, 1) if X.ndim == 1 else X).reshape(13, -1).T)
+        nt = X.shape[0]
+        if plane_of_step is None:
+            plane_of_step = np.zeros(getattr(self, "_pa_steps", 0), np.int32)
+        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
+        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
+            raise ValueError("plane_of_step does not fit int32")
+        ps = ps.astype(np.int32)
+        K = int(ps.size)
+        Xf = np.empty((nt, 13))
+        Xp = np.empty(nt * 13 * (K + 1)) if keep_path else None
+        Fp = np.empty(nt * 12 * K) if keep_path else None
+        FMp = np.empty(nt * 6 * K) if keep_path else None
+        self._check(self.lib.hjb_rollout_run_pos_att(self._ro, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X), _f64p(Xf),
+                                                     _f64p(Xp), _f64p(Fp), _f64p(FMp)))
+        path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
+        return {"X_final": Xf.T, "X_path": path(Xp, 13, K + 1), "F_path": path(Fp, 12, K), "FM_path": path(FMp, 6, K)}
+
 
 class DeviceBuffer:
     """A device allocation owned through the library (hjb_device_malloc): what a host without a HIP binding of its

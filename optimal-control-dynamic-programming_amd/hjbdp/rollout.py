@@ -273,3 +273,190 @@ def pos_att_optimal_path(pa, X0=None, n_steps=None):
                 rigid_body_rates_full(y[10:13], pa.InertiaM, U_M)])
         X[k + 1] = _ode45_step(rates, k * pa.h, (k + 1) * pa.h, xs)
     return np.arange(N) * pa.h, X, F, FM
+
+
+# ---- Solver_pos_att, fixed step: the arithmetic of the GPU loop (K18, csrc/kernels_rollout_pos_att.h) -----------------
+# At h = 0.005 s a classical RK4 step per stage and ode45 both sit at round-off (tests/test_rollout_pos_att_abi.py holds the
+# two loops together to 1e-12 over the whole horizon), so this is the reference's simulator in a form that can be batched
+# and pinned: every operation below is one IEEE double operation in the kernel's order.
+def pos_att_default_X0():
+    """Solver_pos_att.m:457-466."""
+    q0 = angle_to_quat(math.radians(0.0), math.radians(3.0), math.radians(0.0))[::-1]
+    return np.concatenate([[-0.1, 0.0, 0.0], [0.0, 0.0, 0.0], q0, [0.0, 0.0, 0.0]])
+
+
+def pos_att_orbit_table(n_steps, h, substeps=1, R0=None, V0=None, mu=MU_EARTH):
+    """What the pos-att right-hand side (:695-715) needs of the target's orbit, at the times a fixed-step integrator asks:
+    node j = 0 .. 2 * substeps * n_steps at t_j = j * h / (2 * substeps).  Returns (rsw2eci [3, 3] = RSW2ECI(R0, V0),
+    coef [n_nodes, 5]) with coef[j] = [2mu/|R|^3 + H^2/|R|^4, 2 (R.V) H/|R|^4, 2H/|R|^2, mu/|R|^3 - H^2/|R|^4, mu/|R|^3]
+    from propagate_kepler(R0, V0, t_j).  R0, V0 None: the reference's target (:734-753)."""
+    if R0 is None or V0 is None:
+        R0, V0 = target_R0V0()
+    S = int(substeps)
+    if S < 1 or int(n_steps) < 0:
+        raise ValueError("pos_att_orbit_table needs substeps >= 1 and n_steps >= 0")
+    n_nodes = 2 * S * int(n_steps) + 1
+    coef = np.empty((n_nodes, 5))
+    for j in range(n_nodes):
+        R, V = propagate_kepler(R0, V0, j * h / (2 * S), mu)
+        nR = math.sqrt(float(R @ R))
+        RdV = float(R @ V)
+        H = float(np.linalg.norm(np.cross(R, V)))
+        coef[j] = [2 * mu / nR ** 3 + H * H / nR ** 4, 2 * RdV / nR ** 4 * H, 2 * H / nR ** 2,
+                   mu / nR ** 3 - H * H / nR ** 4, mu / nR ** 3]
+    return RSW2ECI(R0, V0), coef
+
+
+def canon_asin(x):
+    """The library's asin (csrc/kernels_rollout_attitude.h canon_asin): fdlibm's e_asin.c in + - * /, sqrt, comparisons and
+    selects, |x| <= 1; within 2 ulp of libm."""
+    x = float(x)
+    ax = abs(x)
+
+    def pq(t):
+        p = t * (1.66666666666666657415e-01 + t * (-3.25565818622400915405e-01 + t * (2.01212532134862925881e-01 +
+                 t * (-4.00555345006794114027e-02 + t * (7.91534994289814532176e-04 + t * 3.47933107596021167570e-05)))))
+        q = 1.0 + t * (-2.40339491173441421878e+00 + t * (2.02094576023350569471e+00 + t * (-6.88283971605453293030e-01 +
+                       t * 7.70381505559019352791e-02)))
+        return p, q
+    if ax < 0.5:
+        p, q = pq(ax * ax)
+        v = ax + ax * (p / q)
+    else:
+        t = (1.0 - ax) * 0.5
+        p, q = pq(t)
+        s = math.sqrt(t) if t >= 0.0 else math.nan
+        if ax >= 0.975:
+            v = 1.57079632679489655800e+00 - (2.0 * (s + s * (p / q)) - 6.12323399573676603587e-17)
+        else:
+            cs = s * 134217729.0
+            sh = cs - (cs - s)
+            c = (t - sh * sh) / (s + sh)
+            pp = 2.0 * s * (p / q) - (6.12323399573676603587e-17 - 2.0 * c)
+            qq = 7.85398163397448278999e-01 - 2.0 * sh
+            v = 7.85398163397448278999e-01 - (pp - qq)
+    return -v if math.copysign(1.0, x) < 0 else v
+
+
+def inv3_adjugate(m):
+    """3 x 3 inverse as the adjugate over the determinant, in the library's operation order (pa_inv3)."""
+    m = [float(v) for v in np.asarray(m, dtype=np.float64).reshape(9)]
+    c00, c01, c02 = m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4]
+    c10, c11, c12 = m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5]
+    c20, c21, c22 = m[3] * m[7] - m[4] * m[6], m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]
+    det = (m[0] * c00 + m[1] * c10) + m[2] * c20
+    with np.errstate(all="ignore"):
+        return (np.array([c00, c01, c02, c10, c11, c12, c20, c21, c22]) / np.float64(det)).reshape(3, 3)
+
+
+def _mul3(m, v0, v1, v2):
+    return [(m[r][0] * v0 + m[r][1] * v1) + m[r][2] * v2 for r in range(3)]
+
+
+def _eci2body_list(q1, q2, q3, q4):
+    return [[1.0 - 2.0 * (q2 * q2 + q3 * q3), 2.0 * (q1 * q2 + q3 * q4), 2.0 * (q1 * q3 - q2 * q4)],
+            [2.0 * (q2 * q1 - q3 * q4), 1.0 - 2.0 * (q1 * q1 + q3 * q3), 2.0 * (q2 * q3 + q1 * q4)],
+            [2.0 * (q3 * q1 + q2 * q4), 2.0 * (q3 * q2 - q1 * q4), 1.0 - 2.0 * (q1 * q1 + q2 * q2)]]
+
+
+def _nearest_index(k, x):
+    """Index of the knot nearest to x: the cell by bisection, clamped to the grid (NaN: cell 0), then the upper knot when
+    x - k[cell] >= k[cell + 1] - x (the library's find_cell and 'nearest' rule)."""
+    lo, hi = 0, len(k) - 1
+    while hi - lo > 1:
+        mid = (lo + hi) >> 1
+        if k[mid] <= x:
+            lo = mid
+        else:
+            hi = mid
+    return lo + 1 if (x - k[lo]) >= (k[lo + 1] - x) else lo
+
+
+def pos_att_channels(pa, channel_x="channel_x_controller_1"):
+    """The three channel policies simplified_run left, as the GPU loop takes them: per channel (knots [4], labels as stored
+    (1-based, [n_x, n_v, n_t, n_w]), thruster table [n_comb, 4] = [f0 f1 f6 f7]_allcomb)."""
+    if not pa.controllers:
+        raise RuntimeError("simplified_run() first")
+    out = []
+    for name in (channel_x, "channel_y_controller_1", "channel_z_controller_1"):
+        c = pa.controllers[name]
+        knots = [np.ascontiguousarray(g, dtype=np.float64) for g in c["GridVectors"]]
+        table = np.stack([np.asarray(c[key], dtype=np.float64) for key in ("f0_allcomb", "f1_allcomb", "f6_allcomb", "f7_allcomb")], axis=1)
+        out.append((knots, np.asarray(c["U_Optimal_id"]), table))
+    return out
+
+
+def pos_att_optimal_path_fixed(pa, X0=None, n_steps=None, substeps=1, channel_x="channel_x_controller_1"):
+    """pos_att_optimal_path with `substeps` classical RK4 steps of h / substeps per stage in place of ode45, forces and moments
+    held over the stage: the scalar host loop in the operation order of the GPU kernel (K18), which it equals bit for bit.
+    Returns what pos_att_optimal_path returns: (T [N], X [N, 13], F_Th_Opt [N, 12], Force_Moment [N, 6])."""
+    chans = pos_att_channels(pa, channel_x)
+    X0 = pos_att_default_X0() if X0 is None else np.asarray(X0, dtype=np.float64).reshape(13)
+    N = pa.N_stage if n_steps is None else min(pa.N_stage, int(n_steps) + 1)
+    S = int(substeps)
+    rsw, coef = pos_att_orbit_table(N - 1, pa.h, S)
+    rsw = [[float(v) for v in row] for row in rsw]
+    rswi = [[float(v) for v in row] for row in inv3_adjugate(rsw)]
+    Jm = [[float(v) for v in row] for row in np.asarray(pa.InertiaM, dtype=np.float64)]
+    Ji = [[float(v) for v in row] for row in inv3_adjugate(Jm)]
+    mass, d, hs = float(pa.Mass), float(pa.T_dist), float(pa.h) / S
+    coef = coef.tolist()
+    kn = [[k.tolist() for k in ch[0]] for ch in chans]
+    lab = [np.asarray(ch[1]) for ch in chans]
+    tab = [ch[2].tolist() for ch in chans]
+    slots = ((0, 1, 6, 7), (2, 3, 8, 9), (4, 5, 10, 11))
+    axis = (1, 2, 0)                                   # channel x uses the angle / rate about y, y about z, z about x
+
+    def rates(c, a, um, y):
+        c0, c1, c2, c3, c4 = c
+        q1, q2, q3, q4, w1, w2, w3 = y[6:13]
+        jw = _mul3(Jm, w1, w2, w3)
+        t = [um[0] - (w2 * jw[2] - w3 * jw[1]), um[1] - (w3 * jw[0] - w1 * jw[2]), um[2] - (w1 * jw[1] - w2 * jw[0])]
+        return [y[3], y[4], y[5],
+                ((c0 * y[0] - c1 * y[1]) + c2 * y[4]) + a[0],
+                ((c1 * y[0] - c3 * y[1]) - c2 * y[3]) + a[1],
+                a[2] - c4 * y[2],
+                0.5 * (((w3 * q2) - (w2 * q3)) + (w1 * q4)),
+                0.5 * (((w1 * q3) - (w3 * q1)) + (w2 * q4)),
+                0.5 * (((w2 * q1) - (w1 * q2)) + (w3 * q4)),
+                0.5 * (((-(w1 * q1)) - (w2 * q2)) - (w3 * q3))] + _mul3(Ji, t[0], t[1], t[2])
+
+    X = np.zeros((N, 13))
+    F = np.zeros((N, 12))
+    FM = np.zeros((N, 6))
+    X[0] = X0
+    x = [float(v) for v in X0]
+    for k in range(N - 1):
+        th = [2.0 * canon_asin(1.0 if x[6 + j] > 1.0 else -1.0 if x[6 + j] < -1.0 else x[6 + j]) for j in range(3)]
+        E = _eci2body_list(x[6], x[7], x[8], x[9])
+        M = [[(E[r][0] * rsw[0][c] + E[r][1] * rsw[1][c]) + E[r][2] * rsw[2][c] for c in range(3)] for r in range(3)]
+        xb, vb = _mul3(M, x[0], x[1], x[2]), _mul3(M, x[3], x[4], x[5])
+        f = [0.0] * 12
+        for ch in range(3):
+            p = (xb[ch], vb[ch], th[axis[ch]], x[10 + axis[ch]])
+            idx = tuple(_nearest_index(kn[ch][a], p[a]) for a in range(4))
+            row = tab[ch][int(lab[ch][idx]) - 1]
+            for s_, v in zip(slots[ch], row):
+                f[s_] = v
+        um = [(((f[4] - f[5]) + f[10]) - f[11]) * d, (((f[0] - f[1]) + f[6]) - f[7]) * d, (((f[2] - f[3]) + f[8]) - f[9]) * d]
+        ab = [(((f[0] + f[1]) + f[6]) + f[7]) / mass, (((f[2] + f[3]) + f[8]) + f[9]) / mass, (((f[4] + f[5]) + f[10]) + f[11]) / mass]
+        Ei = inv3_adjugate(E).tolist()
+        ae = _mul3(Ei, ab[0], ab[1], ab[2])
+        a = _mul3(rswi, ae[0], ae[1], ae[2])
+        F[k] = f
+        FM[k] = a + um
+        for s in range(S):
+            j = 2 * (S * k + s)
+            r = rates(coef[j], a, um, x)
+            acc = r
+            xt = [x[i] + (r[i] * hs) / 2.0 for i in range(13)]
+            r = rates(coef[j + 1], a, um, xt)
+            acc = [acc[i] + 2.0 * r[i] for i in range(13)]
+            xt = [x[i] + (r[i] * hs) / 2.0 for i in range(13)]
+            r = rates(coef[j + 1], a, um, xt)
+            acc = [acc[i] + 2.0 * r[i] for i in range(13)]
+            xt = [x[i] + r[i] * hs for i in range(13)]
+            r = rates(coef[j + 2], a, um, xt)
+            x = [x[i] + (hs * (acc[i] + r[i])) / 6.0 for i in range(13)]
+        X[k + 1] = x
+    return np.arange(N) * pa.h, X, F, FM

@@ -26,7 +26,8 @@ mapped back; axis_order=None runs the reference's own (x, v, theta, w).
 of a single array is a single-precision sum in MATLAB (:274); its order there is
 not documented, the library's is (csrc/kernels_reduce.h).  U_Optimal_id is kept
 in the narrowest label type (uint8: nine thruster combinations).
-Policy use / forward simulation (:404-847): hjbdp/rollout.py (host-side, get_optimal_path below).
+Policy use / forward simulation (:404-847): hjbdp/rollout.py (host-side, get_optimal_path below) and, for many initial states at
+once on the GPU, get_optimal_paths (hjbdp.Rollout.run_pos_att, csrc/kernels_rollout_pos_att.h).
 """
 from __future__ import annotations
 
@@ -278,3 +279,36 @@ class Solver_pos_att:
         from . import rollout
         return rollout.pos_att_optimal_path(self, X0, n_steps)
 
+    def get_optimal_paths(self, X0s=None, n_steps=None, substeps=1, channel_x="channel_x_controller_1", keep_path=False, device=None):
+        """get_optimal_path (:452-730) for many initial states at once on the GPU (hjbdp.Rollout.run_pos_att, K18), after
+        simplified_run().  X0s [13, n] (None: the reference's X0, :457-466).  The three channel policies are built once from
+        self.controllers (labels as stored, thruster table [f0 f1 f6 f7]_allcomb); channel_x = "channel_x_controller_1_failure"
+        simulates the failed thruster.  Each stage is `substeps` classical RK4 steps of h / substeps with the forces held, which
+        at the reference's h equals its ode45 stage to round-off (hjbdp/rollout.py::pos_att_optimal_path_fixed is the same
+        loop on the host, bit for bit).  Returns X_final [13, n], or with keep_path (T [N], X [N, 13, n], F_Th_Opt [N, 12, n],
+        Force_Moment [N, 6, n]) laid out as get_optimal_path's, last F / Force_Moment row zero; N = N_stage (or n_steps + 1)."""
+        from . import rollout
+        from .core import Rollout
+        chans = rollout.pos_att_channels(self, channel_x)                     # RuntimeError without simplified_run()
+        X0s = rollout.pos_att_default_X0().reshape(13, 1) if X0s is None else np.asarray(X0s, dtype=np.float64).reshape(13, -1)
+        N = self.N_stage if n_steps is None else min(self.N_stage, int(n_steps) + 1)
+        rsw, coef = rollout.pos_att_orbit_table(N - 1, self.h, substeps)
+        dev = self.device if device is None else int(device)
+        ros = []
+        try:
+            for knots, labels, table in chans:
+                ros.append(Rollout(knots, labels, table, index_base=1, device=dev))
+            ros[0].set_pos_att_model(ros[1], ros[2], self.InertiaM, self.Mass, self.T_dist, self.h, rsw, coef, substeps)
+            out = ros[0].run_pos_att(X0s, keep_path=keep_path)
+        finally:
+            for ro in ros:
+                ro.close()
+        if not keep_path:
+            return out["X_final"]
+        n = X0s.shape[1]
+        X = np.ascontiguousarray(out["X_path"].transpose(2, 1, 0))
+        F = np.zeros((N, 12, n))
+        FM = np.zeros((N, 6, n))
+        F[:N - 1] = out["F_path"].transpose(2, 1, 0)
+        FM[:N - 1] = out["FM_path"].transpose(2, 1, 0)
+        return np.arange(N) * self.h, X, F, FM

@@ -8,8 +8,9 @@ Two cases, one JSON line:
                (x+ = x + h v, v+ = v + h/M sum f, theta+ = theta + h w, w+ = w + h d/J (f1 - f2 + f3 - f4)) from 2.7 * 10^5
                initial states; host rate: the same loop scalar in Python (interp_nearest_point + the update) over 100 of them.
   (c) attitude: the 6-D attitude policy (K17, hjb_rollout_run_attitude), see case_attitude.
+  (d) pos_att_loop: the 13-state pos-att closed loop (K18, hjb_rollout_run_pos_att), see case_pos_att_loop.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop] [--out FILE]
 """
 from __future__ import annotations
 
@@ -138,6 +139,57 @@ def case_attitude(host=True, n_traj=262144, n_steps=5999):
     return res
 
 
+def case_pos_att_loop(host=True, n_stages=None):
+    """(d) pos_att_loop: the three channel policies of Solver_pos_att.simplified_run (30 x 30 x 20 x 15 states, 9 thruster
+    combinations, uint8 labels, stationary) driving the 13-state loop over all N_stage - 1 = 1,999 stages, paths off: 2^18 starts
+    and 2^12 starts (the latency end) at substeps 1, 2^18 at substeps 4.  The launch is timed with host clocks around the whole
+    call (upload, kernel, download of X_final; the entry point reports no kernel time of its own), best of 3 after a warm-up.  Host
+    rates from the default X0: pos_att_optimal_path (scipy RK45 per stage, 300 stages) and pos_att_optimal_path_fixed (all stages)."""
+    import hjbdp
+    from hjbdp import rollout
+    pa = hjbdp.Solver_pos_att()
+    t0 = time.perf_counter()
+    pa.simplified_run()
+    sweep_s = time.perf_counter() - t0
+    K = pa.N_stage - 1 if n_stages is None else int(n_stages)
+    rng = np.random.default_rng(4)
+    res = {"grid": "30x30x20x15 per channel", "labels": "uint8", "n_steps": int(K), "sweep_wall_s": round(sweep_s, 3),
+           "timing": "host wall clock around hjb_rollout_run_pos_att (upload + kernel + download of X_final), best of 3"}
+    chans = rollout.pos_att_channels(pa)
+    x0 = rollout.pos_att_default_X0()
+    ros = [hjbdp.Rollout(k, l, t, index_base=1) for k, l, t in chans]
+    try:
+        for name, n_traj, S in (("n262144_s1", 1 << 18, 1), ("n4096_s1", 1 << 12, 1), ("n262144_s4", 1 << 18, 4)):
+            X0 = np.tile(x0.reshape(13, 1), (1, n_traj))
+            X0[0:3] += rng.uniform(-0.05, 0.05, size=(3, n_traj))
+            X0[3:6] += rng.uniform(-0.02, 0.02, size=(3, n_traj))
+            X0[10:13] += rng.uniform(-0.01, 0.01, size=(3, n_traj))
+            rsw, coef = rollout.pos_att_orbit_table(K, pa.h, S)
+            ros[0].set_pos_att_model(ros[1], ros[2], pa.InertiaM, pa.Mass, pa.T_dist, pa.h, rsw, coef, S)
+            ros[0].run_pos_att(X0)                                # warm-up, same shape
+            best = None
+            for _ in range(3):
+                t0 = time.perf_counter()
+                ros[0].run_pos_att(X0)
+                dt = time.perf_counter() - t0
+                best = dt if best is None else min(best, dt)
+            res[name] = {"n_traj": int(n_traj), "substeps": S, "ms_per_launch": round(best * 1e3, 3),
+                         "traj_stages_per_s": n_traj * K / best}
+    finally:
+        for ro in ros:
+            ro.close()
+    if host:
+        t0 = time.perf_counter()
+        rollout.pos_att_optimal_path(pa, n_steps=300)
+        res["host_ode45_stages_per_s"] = 300 / (time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        rollout.pos_att_optimal_path_fixed(pa, n_steps=K)
+        res["host_fixed_stages_per_s"] = K / (time.perf_counter() - t0)
+        res["host_loop"] = "pos_att_optimal_path (scipy RK45 per stage) / pos_att_optimal_path_fixed (scalar RK4), default X0"
+        res["speedup_vs_host_ode45"] = res["n262144_s1"]["traj_stages_per_s"] / res["host_ode45_stages_per_s"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -149,7 +201,7 @@ def main():
         raise SystemExit("time_rollout needs a HIP device")
     res = {"tool": "time_rollout"}
     for c in a.cases.split(","):
-        res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude}[c](host=not a.no_host)
+        res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude, "pos_att_loop": case_pos_att_loop}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
