@@ -1,6 +1,7 @@
 // hjbdp_choose.hip - libhjbdp host side: which kernel variant serves a handle, in which form, with which grid, block and LDS
 // (variant_status, choose_launch -> Handle::L), and the stage launch that dispatches on it.
 #include "hjbdp_host.h"
+#include "hjbdp_walk.h"
 
 namespace hjbhost {
 
@@ -116,23 +117,16 @@ void choose_launch(Handle *h) {
     }
     const int per_block = v == 2 ? 512 : (v == 3 ? L.block / 64 : 256);   // states per workgroup pass (variant 4: 256)
     const int64_t blocks = (h->n_owned + per_block - 1) / per_block;
-    // A launch smaller than the work walks it in grid-sized spans.  Equally long spans: a short last span runs on part of the chip
-    // (Solver_attitude.run's 5199 chunks as 4096 + 1103: 3.63 ms per 19 stages; as 2 x 2600: 2.53), and the kernels that give XCD x
-    // the x-th contiguous share of every span (kernels_packed2.h, kernels_tabled.h) would hand a short one to the first XCDs alone.
-    auto spans_of = [](int64_t work, int64_t cap) {
-        if (work <= cap) return work;
-        const int64_t spans = (work + cap - 1) / cap;
-        return std::min<int64_t>(cap, ((work + spans - 1) / spans + 7) / 8 * 8);      // (a multiple of 8: the window modes' walk asks for it)
-    };
+    // A launch smaller than the work walks it in equally long, grid-sized spans (hjbdp_walk.h, launch_spans)
     // (the control-split kernel keeps its 1024 workgroups: one wave per state and few states - Kirk's 2500 blocks as 3 x 840 ran 19.3 ms
     // per 199 stages against 16.3 with a short last span that overlaps the tail of the one before)
     // The table kernel takes its whole grid as ONE span where its 32-bit form allows (XCD x then sweeps one contiguous eighth of the
     // grid: 13M states 0.671 -> 0.630 ms, Solver_attitude.run in the reference's order 13.7 -> 12.9 ms per 19 stages; 2e8 states: equal)
     const int64_t cap = v == 5 ? kTab32MaxThreads / 256 : 256 * 16;
-    L.grid = v == 3 ? (int)std::min<int64_t>(blocks, L.block == 512 ? 2048 : 1024) : (int)spans_of(blocks, cap);
+    L.grid = v == 3 ? (int)std::min<int64_t>(blocks, L.block == 512 ? 2048 : 1024) : (int)hjb::launch_spans(blocks, cap);
     if (v == 6) {       // one wave per (64-state chunk of a) grid row, four waves per workgroup
         const int64_t items = (h->n_owned / P.n[0]) * ((P.n[0] + 63) / 64);
-        L.grid = (int)spans_of((items + 3) / 4, 1 << 20);        // (one span where it can: C4 in the reference's order 6.49 -> 6.15 ms per stage)
+        L.grid = (int)hjb::launch_spans((items + 3) / 4, 1 << 20);        // (one span where it can: C4 in the reference's order 6.49 -> 6.15 ms per stage)
     }
     if (v == 7) {       // one wave per (chunk of axis 0, i2, i3) column; workgroup b serves XCD b % 8
         const DColSweep &CS = h->hcs;

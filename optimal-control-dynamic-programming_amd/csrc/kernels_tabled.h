@@ -10,6 +10,7 @@
 // Any D <= 6, C <= 3, float32/float64, slabs.  Bit-identical to variants 0-4.
 #pragma once
 #include "hjbdp_dev.h"
+#include "hjbdp_walk.h"          // xcd_share
 #include "kernels_generic.h"
 
 namespace hjb {
@@ -32,15 +33,6 @@ __device__ __forceinline__ void tab_load_pair(const _Float16 *__restrict__ Jn, i
 __device__ __forceinline__ void tab_load_pair(const double *__restrict__ Jn, int64_t off, double &a, double &b) {
     const tab_d2u p = *reinterpret_cast<const tab_d2u *>(Jn + off);
     a = p.x; b = p.y;
-}
-
-// Workgroup b runs on XCD b % 8 (each XCD has its own L2).  With "workgroup b takes states [256 b, 256 b + 256)" every XCD walks the
-// whole grid and its L2 holds all of J; here XCD x takes the x-th CONTIGUOUS share of every grid-sized span of workgroups instead
-// (its workgroups b = x, x + 8, ...: G / 8 of them, one more for x < G % 8), so an L2 holds one region of J and its halo.  The host
-// sizes the launch so that the spans are equally long (choose_launch): a short last span would fall to the first XCDs alone.
-__device__ __forceinline__ unsigned xcd_share(unsigned b, unsigned G) {
-    const unsigned x = b & 7u, q = G >> 3, r = G & 7u;
-    return x * q + (x < r ? x : r) + (b >> 3);
 }
 
 struct DTabled {

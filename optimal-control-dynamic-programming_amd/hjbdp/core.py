@@ -705,12 +705,14 @@ def suggest_axis_order(spec):
         lib.hjb_problem_free(b)
 
 
-def solve_batch(specs, n_stages, device=0, monitor_period=0, monitor_tol=0.0, progress=None, monitor_single=False, cs_split=None):
+def solve_batch(specs, n_stages, device=0, monitor_period=0, monitor_tol=0.0, progress=None, monitor_single=False, cs_split=None,
+                options=None):
     """Independent sweeps side by side with as few launch chains as the library can make of them (the four channels of
     Solver_pos_att.simplified_run, pos-att/Solver_pos_att.m:197-242): problems that run on the column-sweep kernel with the same group
     axis, or on the table kernel's 32-bit form with one (dtype, D), share ONE launch per stage (hjb_solve_batch); each such group, and
     every problem that is alone in its shape, gets a host thread and a stream of its own (the device runs two launch chains at full rate: three channels + one is two chains).  Every
     problem keeps its own monitor sums and stop decision; results equal Backup.solve's bit for bit.
+    options: one dict per problem of hjb_set_option keys and values, set on its handle right after it is created.
     -> (outs, wall_ms, variants, group sizes)"""
     import time
     from concurrent.futures import ThreadPoolExecutor
@@ -723,6 +725,9 @@ def solve_batch(specs, n_stages, device=0, monitor_period=0, monitor_tol=0.0, pr
     t_made = time.perf_counter()
     t_run = t_made
     try:
+        for bk, o in zip(bks, options or ()):
+            for k, v in (o or {}).items():
+                bk.set_option(k, v)
         variants = [bk.info()["kernel_variant"] for bk in bks]
         groups = {}
         for i, bk in enumerate(bks):

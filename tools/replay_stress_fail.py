@@ -1,5 +1,5 @@
 """Replay the case tools/stress_parity.py dumped at a mismatch (default: the seed-11 case kept as tests/golden/runaway_60x9x9x8.pkl; or the path given): every
-applicable variant against the oracle, with the count of differing states.  usage: python tools/replay_stress_fail.py [pkl]"""
+applicable variant against the oracle, with the count of differing states, under the launch size ("grid") the dump names where a variant takes one.  usage: python tools/replay_stress_fail.py [pkl]"""
 import os, pickle, sys
 import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -22,6 +22,12 @@ for v in (None, 0, 1, 2, 3, 4, 5, 6, 7):
     except hjbdp.HjbError:
         continue
     with bk:
+        if d.get("grid") is not None:        # the launch size the failing run was forced to (dumps before it existed have none)
+            try:
+                bk.set_option("grid", d["grid"])
+            except hjbdp.HjbError:
+                pass                          # this variant's launch is part of its plan
+        bk_grid = bk.get_option("grid")
         out = bk.solve(d["stages"], terminal=d["term"], **d["mon"])
     same = (out["J"] == ref["J"]) | (np.isnan(out["J"].astype(np.float64)) & np.isnan(ref["J"].astype(np.float64)))
-    print("variant", v, "J differs at", int((~same).sum()), "idx at", int((out["idx"] != ref["idx"]).sum()), "of", spec.nS)
+    print("variant", v, "grid", bk_grid, "J differs at", int((~same).sum()), "idx at", int((out["idx"] != ref["idx"]).sum()), "of", spec.nS)

@@ -1,6 +1,7 @@
 """Randomised GPU-vs-oracle parity stress: random shapes (D, C, grid sizes, dtype, knot spacing, displacement
 spread, J storage, argmin label width, float64-built query tables, float64 cost terms, the monitor in float32 or float64), every applicable
-stage-kernel variant plus hjb_solve's multi-stage paths, whole grids and slabs.
+stage-kernel variant plus hjb_solve's multi-stage paths, whole grids and slabs; every handle that takes option "grid" sweeps a second
+time under a launch drawn from [1, 2 x its automatic grid] (a walk of several passes, or idle workgroups).
 Every result must equal the C oracle's bit for bit.  usage: python tools/stress_parity.py [seconds=120] [seed=0]"""
 import os, sys, time
 import numpy as np
@@ -30,6 +31,7 @@ while time.time() < t_end:
     nonuniform = bool(rng.random() < 0.4)
     spread = float(rng.choice([0.02, 0.1, 0.3, 0.8]))
     seed = int(rng.integers(1 << 30))
+    grid_rng = np.random.default_rng([seed, 0x67726964])      # the forced launch sizes: a sequence of its own per problem
     kind = rng.choice(["nested", "nested_mixed", "random", "rowwise", "local2d", "colsweep", "colsweep"]) if C <= D else "random"
     try:
         if kind == "local2d":         # every query within one cell of its state: hjb_solve's several-stages-per-launch path
@@ -121,37 +123,49 @@ while time.time() < t_end:
             kv = bk.info()["kernel_variant"]
             out = bk.solve(stages, terminal=term, **mon)
             assert out["idx"].dtype == spec.idx_np_dtype
-        ok = np.array_equal(out["J"], ref["J"], equal_nan=True) and np.array_equal(out["idx"], ref["idx"])
-        if mon:
-            # float32 sums: the library's stated order, bit for bit; float64 sums: order-free to rounding
-            exact = mon["monitor_single"] and spec.dtype == np.float32
-            close = (out["last_e"] == ref["last_e"]) if exact else (abs(out["last_e"] - ref["last_e"]) <= 1e-9 * max(abs(ref["last_e"]), 1e-300) + 1e-9)
-            ok = ok and out["stages_done"] == ref["stages_done"] and (close or not np.isfinite(ref["last_e"])) and out["last_e2"] == ref["last_e2"]   # (f16 J may overflow to inf/NaN over many stages - on both sides alike)
-        seen[(v, kv)] = seen.get((v, kv), 0) + 1
-        n_runs += 1
-        if not ok:
-            dj = np.flatnonzero(~((out["J"] == ref["J"]) | (np.isnan(out["J"].astype(np.float64)) & np.isnan(ref["J"].astype(np.float64)))))
-            di = np.flatnonzero(out["idx"] != ref["idx"])
-            print("  J differs at %d of %d states (first %s), idx at %d (first %s)" % (dj.size, spec.nS, dj[:6], di.size, di[:6]), flush=True)
-            if dj.size:
-                print("  J gpu", out["J"][dj[:4]], "oracle", ref["J"][dj[:4]], flush=True)
-            if di.size:
-                print("  idx gpu", out["idx"][di[:4]], "oracle", ref["idx"][di[:4]], "J there", out["J"][di[:4]], ref["J"][di[:4]], flush=True)
-            print("  stages_done", out.get("stages_done"), ref.get("stages_done"), "info", bk.info() if False else kv, flush=True)
+            runs = [(None, out)]
+            # ... and once more under a launch of another size (the kernels that walk their work in grid-sized passes: fewer workgroups
+            # than the work, or idle ones), drawn from a generator of its own: the sequence of problems does not depend on it
+            auto_grid = bk.get_option("grid")
+            grid = int(grid_rng.integers(1, min(2 * auto_grid, 1 << 20) + 1))
             try:
-                import pickle
-                os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-                with open(os.path.join(ROOT, "gpurun_out", "stress_fail.pkl"), "wb") as fh:
-                    pickle.dump(dict(knots=[np.asarray(k) for k in spec.knots], m=list(spec.m),
-                                     next_terms=[[(t.dims, np.asarray(t.data)) for t in ts] for ts in spec.next_terms],
-                                     cost_terms=[(t.dims, np.asarray(t.data)) for t in spec.cost_terms], dtype=str(spec.dtype),
-                                     j_dtype=str(spec.j_dtype), idx_dtype=str(idx_dtype), tab64=tab64, cost64=cost64, term=term, stages=stages,
-                                     mon=mon, forced=v), fh)
-            except Exception as e:
-                print("  (dump failed: %s)" % e)
-            print("MISMATCH", dict(D=D, C=C, n=n, m=m, dtype=str(np.dtype(dtype)), j=str(spec.j_dtype), nonuniform=nonuniform,
-                                   spread=spread, seed=seed, kind=str(kind), stages=stages, forced=v, ran=kv, idx=str(idx_dtype), tab64=tab64, cost64=cost64, mon=mon), flush=True)
-            sys.exit(1)
+                bk.set_option("grid", grid)
+            except hjbdp.HjbError as e:       # the launch is part of the kernel's plan (variants 7 and 1, K15)
+                assert e.status == _abi.HJB_E_UNSUPPORTED, (v, str(e))
+            else:
+                runs.append((grid, bk.solve(stages, terminal=term, **mon)))
+        for grid, out in runs:
+            ok = np.array_equal(out["J"], ref["J"], equal_nan=True) and np.array_equal(out["idx"], ref["idx"])
+            if mon:
+                # float32 sums: the library's stated order, bit for bit; float64 sums: order-free to rounding
+                exact = mon["monitor_single"] and spec.dtype == np.float32
+                close = (out["last_e"] == ref["last_e"]) if exact else (abs(out["last_e"] - ref["last_e"]) <= 1e-9 * max(abs(ref["last_e"]), 1e-300) + 1e-9)
+                ok = ok and out["stages_done"] == ref["stages_done"] and (close or not np.isfinite(ref["last_e"])) and out["last_e2"] == ref["last_e2"]   # (f16 J may overflow to inf/NaN over many stages - on both sides alike)
+            seen[(v, kv)] = seen.get((v, kv), 0) + 1
+            n_runs += 1
+            if not ok:
+                dj = np.flatnonzero(~((out["J"] == ref["J"]) | (np.isnan(out["J"].astype(np.float64)) & np.isnan(ref["J"].astype(np.float64)))))
+                di = np.flatnonzero(out["idx"] != ref["idx"])
+                print("  J differs at %d of %d states (first %s), idx at %d (first %s)" % (dj.size, spec.nS, dj[:6], di.size, di[:6]), flush=True)
+                if dj.size:
+                    print("  J gpu", out["J"][dj[:4]], "oracle", ref["J"][dj[:4]], flush=True)
+                if di.size:
+                    print("  idx gpu", out["idx"][di[:4]], "oracle", ref["idx"][di[:4]], "J there", out["J"][di[:4]], ref["J"][di[:4]], flush=True)
+                print("  stages_done", out.get("stages_done"), ref.get("stages_done"), "info", bk.info() if False else kv, flush=True)
+                try:
+                    import pickle
+                    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+                    with open(os.path.join(ROOT, "gpurun_out", "stress_fail.pkl"), "wb") as fh:
+                        pickle.dump(dict(knots=[np.asarray(k) for k in spec.knots], m=list(spec.m),
+                                         next_terms=[[(t.dims, np.asarray(t.data)) for t in ts] for ts in spec.next_terms],
+                                         cost_terms=[(t.dims, np.asarray(t.data)) for t in spec.cost_terms], dtype=str(spec.dtype),
+                                         j_dtype=str(spec.j_dtype), idx_dtype=str(idx_dtype), tab64=tab64, cost64=cost64, term=term, stages=stages,
+                                         mon=mon, forced=v, grid=grid), fh)
+                except Exception as e:
+                    print("  (dump failed: %s)" % e)
+                print("MISMATCH", dict(D=D, C=C, n=n, m=m, dtype=str(np.dtype(dtype)), j=str(spec.j_dtype), nonuniform=nonuniform,
+                                       spread=spread, seed=seed, kind=str(kind), stages=stages, forced=v, ran=kv, grid=grid, idx=str(idx_dtype), tab64=tab64, cost64=cost64, mon=mon), flush=True)
+                sys.exit(1)
     # a random slab of the last axis with the halos the library asks for, one stage
     nl = spec.n[-1]
     if nl >= 4:
