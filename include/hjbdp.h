@@ -420,6 +420,35 @@ int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *ro
 int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
                                 double *X_final, double *X_path, double *F_path, double *FM_path);
 
+/* Solver_position's closed loop (position-control/Solver_position.m:189-311, get_optimal_path after simplified_run) on three rollout
+ * objects, one per channel (x, y, z), each D == 2 over (position, velocity) with n_u == 1 (the acceleration per label), on one device,
+ * in one label type.  Sharing and lifetime are those of the pos-att model: hjb_rollout_set_position_model attaches the model to
+ * rollout_x (the last model set wins) and takes a share of rollout_y's and rollout_z's device data, so destroying those two
+ * afterwards is safe.  The stage integrator is private/rkf45.m ON ITS SCHEDULE: at the reference's h = 0.005 s every error test
+ * passes with room to spare, every step is accepted and grows fourfold, and the steps depend on the stage's t0 and tf alone.  The
+ * host lists them: n_sub [n_steps] sub-steps per stage, 1 <= n_sub[k] <= max_sub <= 8, and table [32, max_sub, n_steps] column-major,
+ * finite, row (s, k) = [h_form, h_apply, then at each of the six times t_s + a_j h_form (a = 0, 1/4, 3/8, 12/13, 1, 1/2) the five
+ * orbit scalars of hjb_rollout_set_pos_att_model's orbit_coef]; tol finite and > 0 (rkf45's 1e-8).  hjb_rollout_run_position
+ * steps y = [x(3) v(3)] n_steps <= the table's stages, all in double, left to right, every product rounded; stage k:
+ *   a_i = the 'nearest' lookup of channel i on plane plane_of_step[k] at (y_i, y_3+i), held over the stage (:215-217);
+ *   per sub-step, with B, C4, C5 Fehlberg's tableau and F the right-hand side f_0..2 = y_3..5,
+ *   f_3 = ((c0 y0 - c1 y1) + c2 y4) + a_0, f_4 = ((c1 y0 - c3 y1) - c2 y3) + a_1, f_5 = a_2 - c4 y2:
+ *     f_0 = F(y), f_i = F((..(y + (h_form B_i0) f_0) + ..) + (h_form B_i,i-1) f_i-1);
+ *     te = max_i |h_form ((((f_0i d_0 + f_2i d_2) + f_3i d_3) + f_4i d_4) + f_5i d_5)|, d = C4 - C5;
+ *     allowed = tol * max(max_i |y_i|, 1);  the sub-step is on schedule iff allowed >= 1100 * (te + 2^-52) (false for NaN): rkf45
+ *     grows the step fourfold when allowed / (te + eps) >= 1024, and 1100 leaves room for the rounding of its pow(., 0.2);
+ *     y_i += h_apply ((((f_0i C5_0 + f_2i C5_2) + f_3i C5_3) + f_4i C5_4) + f_5i C5_5)   (h_apply < h_form in a stage's last
+ *     sub-step: rkf45 clips an accepted step after forming its stage derivatives, and so does this).
+ * off_schedule [n_traj] (required): the first stage with a sub-step off schedule, -1 if none; such a trajectory is NOT what rkf45
+ * computes from that stage on and is for the caller to recompute; the run completes on the schedule either way.  X0, X_final
+ * [6, n_traj]; X_path [n_traj, 6, n_steps+1]; A_path [n_traj, 3, n_steps]; NULL paths are not written.  A non-finite X0 is
+ * HJB_E_INVALID; a state that leaves the grids is looked up at the clamped cell (the reference's default start does).  The other
+ * hjb_rollout_run_* calls on a position object, and hjb_rollout_run_position on any other, are HJB_E_INVALID. */
+int32_t hjb_rollout_set_position_model(void *rollout_x, void *rollout_y, void *rollout_z, double tol, int32_t n_steps, int32_t max_sub,
+                                       const int32_t *n_sub, const double *table);
+int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
+                                 double *X_final, double *X_path, double *A_path, int32_t *off_schedule);
+
 /* ---- flat builder API -------------------------------------------------------------------------------------------
  * hjb_problem holds arrays of structs with pointers, which MATLAB's loadlibrary/calllib cannot marshal.  These entry
  * points take primitives and plain arrays only, copy what they are given (the caller may free it at once), and end in

@@ -108,4 +108,10 @@ int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *ro
                                       const double *orbit_coef);
 int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
                                 double *X_final, double *X_path, double *F_path, double *FM_path);
+/* Solver_position's RKF45 loop on three channel objects (position-control/Solver_position.m:189-311, get_optimal_path after
+ * simplified_run), on rkf45's fixed schedule with a per-trajectory off-schedule flag (hjbdp.h) */
+int32_t hjb_rollout_set_position_model(void *rollout_x, void *rollout_y, void *rollout_z, double tol, int32_t n_steps, int32_t max_sub,
+                                       const int32_t *n_sub, const double *table);
+int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
+                                 double *X_final, double *X_path, double *A_path, int32_t *off_schedule);
 #endif

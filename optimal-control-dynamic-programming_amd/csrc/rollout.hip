@@ -1,20 +1,23 @@
 // rollout.hip - hjb_rollout_*: batched closed-loop rollouts of a stored per-stage policy (include/hjbdp.h; kernels:
 // kernels_rollout.h for the affine model, kernels_rollout_attitude.h / rollout_attitude.hip for the attitude model,
-// kernels_rollout_pos_att.h / rollout_pos_att.hip for the pos-att model).
+// kernels_rollout_pos_att.h / rollout_pos_att.hip for the pos-att model, kernels_rollout_position.h / rollout_position.hip for the
+// position model).
 #include "hjbdp_host.h"
 #include "kernels_rollout.h"
 #include "kernels_rollout_attitude.h"
 #include "kernels_rollout_pos_att.h"
+#include "kernels_rollout_position.h"
 #include <memory>
 
 using namespace hjbhost;
 
 namespace {
 
-enum { kModelNone = 0, kModelAffine = 1, kModelAttitude = 2, kModelPosAtt = 3 };    // the last setter called wins
+enum { kModelNone = 0, kModelAffine = 1, kModelAttitude = 2, kModelPosAtt = 3, kModelPosition = 4 };    // the last setter called wins
 
-// Device allocations with shared ownership: an object's grid, table and labels live as long as the object or a pos-att model that
-// reads them (hjb_rollout_set_pos_att_model on another object) does.  Freed under the last owner's locks (destroy / set_*model).
+// Device allocations with shared ownership: an object's grid, table and labels live as long as the object or a pos-att or position
+// model that reads them (hjb_rollout_set_pos_att_model / hjb_rollout_set_position_model on another object) does.  Freed under the
+// last owner's locks (destroy / set_*model).
 struct DevData {
     int device = 0;
     std::vector<void *> allocs;
@@ -34,6 +37,15 @@ struct PosAtt {
     int max_steps = 0;              // (n_nodes - 1) / (2 substeps)
 };
 
+// The position model of channel x's object: the y and z channels' descriptors with their device data kept alive, the RKF45 table
+struct Position {
+    DPaChan cy{}, cz{};
+    std::shared_ptr<DevData> data_y, data_z, table;     // table: n_sub and the sub-step rows
+    DPosition M{};
+    int n_planes = 0;               // of the three channels, the fewest
+    int max_steps = 0;              // stages the table holds
+};
+
 struct Rollout {
     std::mutex mu;                  // one call at a time per object
     int device = 0, D = 0, idx_bytes = 4, n_planes = 0;
@@ -42,6 +54,7 @@ struct Rollout {
     DRollout R{};                   // device pointers filled by create; model by set_model
     DAttitude M{};                  // the attitude model (set_attitude_model)
     std::unique_ptr<PosAtt> pa;     // the pos-att model (set_pos_att_model)
+    std::unique_ptr<Position> ps;   // the position model (set_position_model)
     std::shared_ptr<DevData> data;
     hipStream_t stream = nullptr;
     std::string err;
@@ -63,6 +76,7 @@ int rfail(Rollout *ro, int code, const char *fmt, ...) {
 
 void release(Rollout *ro) {
     ro->pa.reset();
+    ro->ps.reset();
     ro->data.reset();
     if (ro->stream) (void)hipStreamDestroy(ro->stream);
     ro->stream = nullptr;
@@ -116,22 +130,32 @@ int check_run(Rollout *ro, int want, int method, int32_t n_steps, const int32_t 
     if (method != HJB_LOOKUP_NEAREST && method != HJB_LOOKUP_LINEAR) return rfail(ro, HJB_E_INVALID, "rollout: method %d", method);
     if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
     if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
-    static const char *const setter[] = {"", "hjb_rollout_set_model", "hjb_rollout_set_attitude_model", "hjb_rollout_set_pos_att_model"};
-    static const char *const runner[] = {"", "hjb_rollout_run", "hjb_rollout_run_attitude", "hjb_rollout_run_pos_att"};
-    static const char *const held[] = {"", "affine", "attitude", "pos-att"};
+    static const char *const setter[] = {"", "hjb_rollout_set_model", "hjb_rollout_set_attitude_model", "hjb_rollout_set_pos_att_model",
+                                         "hjb_rollout_set_position_model"};
+    static const char *const runner[] = {"", "hjb_rollout_run", "hjb_rollout_run_attitude", "hjb_rollout_run_pos_att",
+                                         "hjb_rollout_run_position"};
+    static const char *const held[] = {"", "affine", "attitude", "pos-att", "position"};
     if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: run before %s", setter[want]);
     if (ro->model != want)
         return rfail(ro, HJB_E_INVALID, "rollout: the object holds the %s model (%s): call %s", held[ro->model], setter[ro->model],
                      runner[ro->model]);
     if (n_steps > 0 && !plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null plane_of_step");
-    const int n_planes = want == kModelPosAtt ? ro->pa->n_planes : ro->n_planes;
+    const int n_planes = want == kModelPosAtt ? ro->pa->n_planes : want == kModelPosition ? ro->ps->n_planes : ro->n_planes;
     for (int k = 0; k < n_steps; ++k)
         if (plane_of_step[k] < 0 || plane_of_step[k] >= n_planes)
             return rfail(ro, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d)", k, plane_of_step[k], n_planes);
     return HJB_OK;
 }
 
-// what K18 reads of an object's policy (kernels_rollout_pos_att.h)
+// a pos-att or position model goes, and with it its hold on the other two channels
+void drop_attached(Rollout *ro) {
+    if (!ro->pa && !ro->ps) return;
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    ro->pa.reset();
+    ro->ps.reset();
+}
+
+// what K18 and K19 read of an object's policy (kernels_rollout_pos_att.h)
 DPaChan pa_channel(const DRollout &R) {
     DPaChan c{};
     for (int a = 0; a < 4; ++a) {
@@ -154,13 +178,14 @@ DPaChan pa_channel(const DRollout &R) {
 }
 
 // The chunk loop the run functions share: W doubles of state per trajectory; per step n_up control rows (U_path) and n_e more
-// path rows (E_path: the attitude loop's angles, the pos-att loop's Force_Moment).  Per chunk: upload X0, launch(R, nc, lds, lds_on, stream, X0, Xf, cost, Xp, Up, Ep) (the
-// kernel of the entry point `who`), download X_final / cost and the paths ([nc, rows] on the device -> columns i0 .. i0+nc of
+// path rows (E_path: the attitude loop's angles, the pos-att loop's Force_Moment).  Per chunk: upload X0, launch(R, nc, lds, lds_on, stream, X0, Xf, cost, Xp, Up, Ep, Fl) (the
+// kernel of the entry point `who`; Fl: nc int32 flags, allocated when `flags` is asked for: the position loop's off_schedule),
+// download X_final / cost / flags and the paths ([nc, rows] on the device -> columns i0 .. i0+nc of
 // [n_traj, rows] on the host); device_ms sums the launches' event times.
 template <typename Launch>
 int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
-               const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *E_path, double *device_ms,
-               Launch launch) {
+               const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *E_path, int32_t *flags,
+               double *device_ms, Launch launch) {
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
     const int nu = n_up;
@@ -173,20 +198,22 @@ int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n
     const size_t pb = (size_t)std::max(n_steps, 1) * sizeof(int32_t);
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipMemGetInfo failed");
-    const size_t need = 2 * xb + xpb + upb + epb + cb + pb;
+    const size_t fb = flags ? (size_t)nc_max * sizeof(int32_t) : 0;
+    const size_t need = 2 * xb + xpb + upb + epb + cb + pb + fb;
     if (need + ((size_t)64 << 20) > fr)
         return rfail(ro, HJB_E_NOMEM, "rollout: a chunk of %lld trajectories needs %zu bytes, %zu free (lower option \"chunk\")",
                      (long long)nc_max, need, fr);
-    void *bufs[7] = {};
+    void *bufs[8] = {};
     auto done = [&](int code) {
         for (void *p : bufs) if (p) (void)hipFree(p);
         return code;
     };
-    const size_t sizes[7] = {xb, xb, cb, xpb, upb, pb, epb};
-    for (int b = 0; b < 7; ++b)
+    const size_t sizes[8] = {xb, xb, cb, xpb, upb, pb, epb, fb};
+    for (int b = 0; b < 8; ++b)
         if (sizes[b] && hipMalloc(&bufs[b], sizes[b]) != hipSuccess) return done(rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", sizes[b]));
     double *dX0 = (double *)bufs[0], *dXf = (double *)bufs[1], *dC = (double *)bufs[2], *dXp = (double *)bufs[3], *dUp = (double *)bufs[4];
     double *dEp = (double *)bufs[6];
+    int32_t *dFl = (int32_t *)bufs[7];
     hipStream_t st = ro->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t e = hipEventCreate(&e0);
@@ -203,11 +230,12 @@ int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n
         e = hipMemcpyAsync(dX0, X0 + W * i0, (size_t)nc * W * sizeof(double), hipMemcpyHostToDevice, st);
         if (e != hipSuccess) break;
         (void)hipEventRecord(e0, st);
-        e = launch(R, nc, lds, lds_on, st, dX0, dXf, dC, dXp, dUp, dEp);
+        e = launch(R, nc, lds, lds_on, st, dX0, dXf, dC, dXp, dUp, dEp, dFl);
         if (e != hipSuccess) break;
         (void)hipEventRecord(e1, st);
         e = hipMemcpyAsync(X_final + W * i0, dXf, (size_t)nc * W * sizeof(double), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && cost) e = hipMemcpyAsync(cost + i0, dC, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && flags) e = hipMemcpyAsync(flags + i0, dFl, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, st);
         // paths: [nc, rows] on the device -> columns i0 .. i0+nc of [n_traj, rows] on the host
         if (e == hipSuccess && X_path)
             e = hipMemcpy2DAsync(X_path + i0, (size_t)n_traj * sizeof(double), dXp, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double),
@@ -371,10 +399,7 @@ int32_t hjb_rollout_set_model(void *rollout, const double *A, const double *B, c
     if (r) std::memcpy(R.r, r, sizeof(double) * nu);
     R.has_c = c ? 1 : 0;
     ro->model = kModelAffine;
-    if (ro->pa) {                                     // the pos-att model goes, and with it its hold on the other two channels
-        std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-        ro->pa.reset();
-    }
+    drop_attached(ro);
     return HJB_OK;
 }
 
@@ -407,10 +432,7 @@ int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, dou
     if (r) std::memcpy(M.r, r, sizeof M.r);
     ro->integrator = integrator;
     ro->model = kModelAttitude;
-    if (ro->pa) {                                     // the pos-att model goes, and with it its hold on the other two channels
-        std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-        ro->pa.reset();
-    }
+    drop_attached(ro);
     return HJB_OK;
 }
 
@@ -490,7 +512,76 @@ int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *ro
     pa->M.coef = (const double *)d;
     if (rx->stream) (void)hipStreamSynchronize(rx->stream);
     rx->pa = std::move(pa);                                 // replaces (and releases) a model set earlier
+    rx->ps.reset();
     rx->model = kModelPosAtt;
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_set_position_model(void *rollout_x, void *rollout_y, void *rollout_z, double tol, int32_t n_steps, int32_t max_sub,
+                                       const int32_t *n_sub, const double *table) {
+    Rollout *rx = (Rollout *)rollout_x, *ry = (Rollout *)rollout_y, *rz = (Rollout *)rollout_z;
+    // the arguments that need no object first (decided without a device), then the objects
+    if (!n_sub || !table) return rfail(rx, HJB_E_INVALID, "rollout: null argument (n_sub and table are required)");
+    if (!(std::isfinite(tol) && tol > 0)) return rfail(rx, HJB_E_INVALID, "rollout: tol = %g is not finite and > 0", tol);
+    if (n_steps < 1) return rfail(rx, HJB_E_INVALID, "rollout: n_steps = %d < 1 (the stages the table holds)", n_steps);
+    if (max_sub < 1 || max_sub > HJB_POS_MAX_SUB)
+        return rfail(rx, HJB_E_INVALID, "rollout: max_sub = %d not in 1..%d", max_sub, HJB_POS_MAX_SUB);
+    for (int k = 0; k < n_steps; ++k)
+        if (n_sub[k] < 1 || n_sub[k] > max_sub)
+            return rfail(rx, HJB_E_INVALID, "rollout: n_sub[%d] = %d not in 1..%d (max_sub)", k, n_sub[k], max_sub);
+    const int64_t n_tab = (int64_t)HJB_POS_ROW * max_sub * n_steps;
+    const int64_t bad = first_nonfinite(table, n_tab, true);
+    if (bad >= 0) return rfail(rx, HJB_E_INVALID, "rollout: table element %lld is not finite", (long long)bad);
+    if (!rx || !ry || !rz) return rfail(rx, HJB_E_INVALID, "rollout: null handle (three channel objects are required)");
+    if (rx == ry || rx == rz || ry == rz) return rfail(rx, HJB_E_INVALID, "rollout: the same object passed for two channels");
+    auto ps = std::make_unique<Position>();
+    ps->M.tol = tol;
+    ps->M.max_sub = max_sub;
+    ps->max_steps = n_steps;
+    // y and z: a snapshot of the policy with a share of its device data, taken under that object's own lock
+    int dev_o[2] = {0, 0}, idx_o[2] = {0, 0}, planes_o[2] = {0, 0};
+    Rollout *others[2] = {ry, rz};
+    const char *names[2] = {"rollout_y", "rollout_z"};
+    for (int t = 0; t < 2; ++t) {
+        Rollout *o = others[t];
+        std::lock_guard<std::mutex> g(o->mu);
+        if (o->D != 2 || o->R.n_u != 1)
+            return rfail(rx, HJB_E_INVALID, "rollout: the position model needs D == 2 and n_u == 1 (%s: D=%d, n_u=%d)", names[t], o->D, o->R.n_u);
+        (t == 0 ? ps->cy : ps->cz) = pa_channel(o->R);
+        (t == 0 ? ps->data_y : ps->data_z) = o->data;
+        dev_o[t] = o->device;
+        idx_o[t] = o->idx_bytes;
+        planes_o[t] = o->n_planes;
+    }
+    std::lock_guard<std::mutex> g(rx->mu);
+    if (rx->D != 2 || rx->R.n_u != 1)
+        return rfail(rx, HJB_E_INVALID, "rollout: the position model needs D == 2 and n_u == 1 (rollout_x: D=%d, n_u=%d)", rx->D, rx->R.n_u);
+    for (int t = 0; t < 2; ++t) {
+        if (dev_o[t] != rx->device)
+            return rfail(rx, HJB_E_INVALID, "rollout: %s is on device %d, rollout_x on device %d", names[t], dev_o[t], rx->device);
+        if (idx_o[t] != rx->idx_bytes)
+            return rfail(rx, HJB_E_INVALID, "rollout: %s has %d-byte labels, rollout_x %d-byte labels (the three channels share one label type)",
+                         names[t], idx_o[t], rx->idx_bytes);
+    }
+    ps->n_planes = std::min(rx->n_planes, std::min(planes_o[0], planes_o[1]));
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    if (hipSetDevice(rx->device) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "hipSetDevice failed");
+    ps->table = std::make_shared<DevData>();
+    ps->table->device = rx->device;
+    const size_t tb = (size_t)n_tab * sizeof(double), nb = (size_t)n_steps * sizeof(int32_t);
+    void *dt = nullptr, *dn = nullptr;
+    if (hipMalloc(&dt, tb) != hipSuccess) return rfail(rx, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", tb);
+    ps->table->allocs.push_back(dt);
+    if (hipMalloc(&dn, nb) != hipSuccess) return rfail(rx, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", nb);
+    ps->table->allocs.push_back(dn);
+    if (hipMemcpy(dt, table, tb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dn, n_sub, nb, hipMemcpyHostToDevice) != hipSuccess)
+        return rfail(rx, HJB_E_DEVICE, "rollout: upload failed");
+    ps->M.table = (const double *)dt;
+    ps->M.n_sub = (const int32_t *)dn;
+    if (rx->stream) (void)hipStreamSynchronize(rx->stream);
+    rx->ps = std::move(ps);                                 // replaces (and releases) a model set earlier
+    rx->pa.reset();
+    rx->model = kModelPosition;
     return HJB_OK;
 }
 
@@ -521,9 +612,10 @@ int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const in
     const int64_t bad = first_nonfinite(X0, (int64_t)D * n_traj, true);
     if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
     const int idx_bytes = ro->idx_bytes;
-    return run_chunks(ro, "hjb_rollout_run", D, ro->R.n_u, 0, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, nullptr, device_ms,
+    return run_chunks(ro, "hjb_rollout_run", D, ro->R.n_u, 0, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, nullptr, nullptr,
+                      device_ms,
                       [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t st, double *dX0, double *dXf, double *dC,
-                          double *dXp, double *dUp, double *) {
+                          double *dXp, double *dUp, double *, int32_t *) {
                           switch (idx_bytes) {
                               case 1: launch_m<uint8_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
                               case 2: launch_m<uint16_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
@@ -557,9 +649,9 @@ int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps,
     const int idx_bytes = ro->idx_bytes, integ = ro->integrator;
     const DAttitude M = ro->M;
     return run_chunks(ro, "hjb_rollout_run_attitude", HJB_ATT_W, HJB_ATT_U, 3, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path,
-                      A_path, device_ms,
+                      A_path, nullptr, device_ms,
                       [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t st, double *dX0, double *dXf, double *dC,
-                          double *dXp, double *dUp, double *dAp) {
+                          double *dXp, double *dUp, double *dAp, int32_t *) {
                           return launch_rollout_attitude(idx_bytes, method, lds_on, integ, R, M, nc, lds, st, dX0, dXf, dC, dXp, dUp, dAp);
                       });
 }
@@ -587,14 +679,47 @@ int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t 
                                  4 * ((int64_t)cx0.n_labels + pa.cy.n_labels + pa.cz.n_labels)) * sizeof(double);
     const bool lds3_on = lds3 <= kLdsMax;
     return run_chunks(ro, "hjb_rollout_run_pos_att", HJB_PA_W, HJB_PA_F, HJB_PA_FM, n_steps, plane_of_step, n_traj, X0, X_final, nullptr,
-                      X_path, F_path, FM_path, nullptr,
+                      X_path, F_path, FM_path, nullptr, nullptr,
                       [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *, double *dXp,
-                          double *dFp, double *dFMp) {
+                          double *dFp, double *dFMp, int32_t *) {
                           DPaChan cx = cx0, cy = pa.cy, cz = pa.cz;
                           cx.plane_of_step = cy.plane_of_step = cz.plane_of_step = R.plane_of_step;
                           DPosAtt M = pa.M;
                           M.n_steps = R.n_steps;
                           return launch_rollout_pos_att(idx_bytes, lds3_on, cx, cy, cz, M, nc, lds3, st, dX0, dXf, dXp, dFp, dFMp);
+                      });
+}
+
+int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
+                                 double *X_final, double *X_path, double *A_path, int32_t *off_schedule) {
+    Rollout *ro = (Rollout *)rollout_x;
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    const int bad_arg = check_run(ro, kModelPosition, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
+    if (bad_arg) return bad_arg;
+    const Position &ps = *ro->ps;
+    if (n_steps > ps.max_steps)
+        return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the RKF45 table covers %d stages", n_steps, ps.max_steps);
+    if (n_traj == 0) return HJB_OK;
+    if (!X0 || !X_final || !off_schedule) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final / off_schedule");
+    if (n_traj > INT64_MAX / (HJB_POS_W * ((int64_t)n_steps + 1)) / 8)
+        return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x 6 x n_steps)");
+    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_POS_W * n_traj, true);
+    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    const int idx_bytes = ro->idx_bytes;
+    const DPaChan cx0 = pa_channel(ro->R);
+    const size_t lds3 = (size_t)(2 * ((int64_t)cx0.n_knots + ps.cy.n_knots + ps.cz.n_knots) +
+                                 ((int64_t)cx0.n_labels + ps.cy.n_labels + ps.cz.n_labels)) * sizeof(double);
+    const bool lds3_on = lds3 <= kLdsMax;
+    return run_chunks(ro, "hjb_rollout_run_position", HJB_POS_W, HJB_POS_A, 0, n_steps, plane_of_step, n_traj, X0, X_final, nullptr,
+                      X_path, A_path, nullptr, off_schedule, nullptr,
+                      [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *, double *dXp,
+                          double *dAp, double *, int32_t *dOff) {
+                          DPaChan cx = cx0, cy = ps.cy, cz = ps.cz;
+                          cx.plane_of_step = cy.plane_of_step = cz.plane_of_step = R.plane_of_step;
+                          DPosition M = ps.M;
+                          M.n_steps = R.n_steps;
+                          return launch_rollout_position(idx_bytes, lds3_on, cx, cy, cz, M, nc, lds3, st, dX0, dXf, dXp, dAp, dOff);
                       });
 }
 

@@ -230,6 +230,10 @@ SYMBOLS = {
     "hjb_rollout_set_pos_att_model": (C.c_int32, [C.c_void_p] * 3 + [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_int32,
                                                   C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)]),
     "hjb_rollout_run_pos_att": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64] + [C.POINTER(C.c_double)] * 5),
+    "hjb_rollout_set_position_model": (C.c_int32, [C.c_void_p] * 3 + [C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_double)]),
+    "hjb_rollout_run_position": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64] + [C.POINTER(C.c_double)] * 4
+                                 + [C.POINTER(C.c_int32)]),
 }
 HJB_ROLLOUT_MAX_U = 4
 HJB_ATT_TAYLOR = 0

@@ -279,6 +279,42 @@ class Rollout:
         path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
         return {"X_final": Xf.T, "X_path": path(Xp, 13, K + 1), "F_path": path(Fp, 12, K), "FM_path": path(FMp, 6, K)}
 
+    def set_position_model(self, rollout_y, rollout_z, n_sub, table, tol=1e-8):
+        """Solver_position's RKF45 loop (hjb_rollout_set_position_model; the last model set wins) with this object as channel x and
+        two more Rollout objects as channels y and z (each D = 2 over (position, velocity), n_u = 1, one device, one label type).
+        n_sub [n_steps] and table [n_steps, max_sub, 32] as hjbdp.rollout.position_rkf45_table builds them; tol is rkf45's.  The
+        model keeps what it reads of the other two alive: they may be closed afterwards."""
+        ns = np.ascontiguousarray(np.asarray(n_sub).reshape(-1).astype(np.int32))
+        tab = np.ascontiguousarray(np.asarray(table, dtype=np.float64))
+        if tab.ndim != 3 or tab.shape[0] != ns.size or tab.shape[2] != 32:
+            raise ValueError("table must be [n_steps, max_sub, 32] with one n_sub per stage, got %r for %d stages" % (tab.shape, ns.size))
+        self._check(self.lib.hjb_rollout_set_position_model(self._ro, rollout_y._ro, rollout_z._ro, float(tol), int(ns.size),
+                                                            int(tab.shape[1]), ns.ctypes.data_as(C.POINTER(C.c_int32)), _f64p(tab)))
+        self._pos_steps = int(ns.size)
+
+    def run_position(self, X0, plane_of_step=None, keep_path=False):
+        """hjb_rollout_run_position: X0 [6, n_traj] (y = [x(3) v(3)]).  plane_of_step None: every stage the table covers, on plane 0
+        (stationary policies).  Returns X_final [6, n_traj], off_schedule [n_traj] (int32: the first stage that left rkf45's
+        schedule, -1 if none) and X_path [n_traj, 6, n_steps+1], A_path [n_traj, 3, n_steps]; the paths None unless keep_path."""
+        X = np.asarray(X0, dtype=np.float64)
+        X = np.ascontiguousarray((X.reshape(6, 1) if X.ndim == 1 else X).reshape(6, -1).T)
+        nt = X.shape[0]
+        if plane_of_step is None:
+            plane_of_step = np.zeros(getattr(self, "_pos_steps", 0), np.int32)
+        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
+        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
+            raise ValueError("plane_of_step does not fit int32")
+        ps = ps.astype(np.int32)
+        K = int(ps.size)
+        Xf = np.empty((nt, 6))
+        Xp = np.empty(nt * 6 * (K + 1)) if keep_path else None
+        Ap = np.empty(nt * 3 * K) if keep_path else None
+        off = np.full(nt, -1, np.int32)
+        self._check(self.lib.hjb_rollout_run_position(self._ro, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X), _f64p(Xf),
+                                                      _f64p(Xp), _f64p(Ap), off.ctypes.data_as(C.POINTER(C.c_int32))))
+        path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
+        return {"X_final": Xf.T, "off_schedule": off, "X_path": path(Xp, 6, K + 1), "A_path": path(Ap, 3, K)}
+
 
 class DeviceBuffer:
     """A device allocation owned through the library (hjb_device_malloc): what a host without a HIP binding of its

@@ -1,4 +1,4 @@
-"""Closed-loop rollouts of the attitude and pos-att solvers with the policies the sweeps leave.
+"""Closed-loop rollouts of the attitude, pos-att and position solvers with the policies the sweeps leave.
 
 Host-side, scalar, O(N_stage) - the reference's own forward simulators restated without their plots:
 
@@ -8,6 +8,7 @@ Host-side, scalar, O(N_stage) - the reference's own forward simulators restated 
   pos-att/Solver_pos_att.m             get_thruster_on_off_optimal :404-449, get_optimal_path :452-730,
                                        get_target_R0V0 :734-753, update_RV_target :755-782,
                                        to_Moments_Forces :804-823, ECI2body :825-829, RSW2ECI :831-847
+  position-control/Solver_position.m   get_optimal_path :189-311 on private/rkf45.m's schedule (position_optimal_path_fixed)
 
 State conventions of the reference: the attitude state is X = [w1 w2 w3 q1 q2 q3 q4] with q4 the scalar part; the
 pos-att state is X = [x(3) v(3) q(4) w(3)].  MATLAB's ode45 is Dormand-Prince 5(4) with RelTol 1e-3 / AbsTol 1e-6:
@@ -460,3 +461,151 @@ def pos_att_optimal_path_fixed(pa, X0=None, n_steps=None, substeps=1, channel_x=
             x = [x[i] + (hs * (acc[i] + r[i])) / 6.0 for i in range(13)]
         X[k + 1] = x
     return np.arange(N) * pa.h, X, F, FM
+
+
+# ---- Solver_position, RKF45 on its schedule: the arithmetic of the GPU loop (K19, csrc/kernels_rollout_position.h) ------------
+# Solver_position.get_optimal_path integrates each stage with orbit.rkf45.  At h = 0.005 s its error tests pass with a ratio
+# allowed / (err + eps) of some 1e7 where fourfold growth needs 4^5 = 1024, so every step is accepted and grows fourfold: the
+# steps of a stage follow from its t0 and tf alone (position_rkf45_schedule).  A classical RK4 stage does NOT reproduce the loop:
+# rkf45 clips an accepted step to the end of the interval after forming its stage derivatives with the unclipped step, so a
+# stage's last sub-step is no consistent Runge-Kutta step, and the loop below keeps that.  Every operation is one IEEE double
+# operation in the kernel's order; a sub-step whose error test does not leave rkf45 its fourfold growth is flagged.
+POSITION_MAX_SUB = 8                  # sub-steps per stage the table may hold (csrc HJB_POS_MAX_SUB)
+POSITION_GROWTH_MARGIN = 1100.0       # > 4^5 = 1024: room for the rounding of rkf45's pow(., 0.2)
+
+
+def position_rkf45_schedule(t0, tf):
+    """The steps orbit.rkf45 takes from t0 to tf when every step is accepted and grows fourfold, in its own double arithmetic:
+    [(t_i, h_form, h_apply)], h_form the step the six stage derivatives are formed with, h_apply = min(h_form, tf - t_i) the
+    step that is applied."""
+    t = float(t0)
+    h = (tf - t0) / 100.0
+    out = []
+    while t < tf:
+        ha = min(h, tf - t)
+        out.append((t, h, ha))
+        t = t + ha
+        h = 4.0 * ha
+    return out
+
+
+def position_rkf45_table(n_steps, h, R0=None, V0=None, mu=MU_EARTH):
+    """What K19 reads: (n_sub [n_steps] int32, table [n_steps, max_sub, 32]).  Stage k runs from k*h to (k+1)*h on
+    position_rkf45_schedule; row (k, s) = [h_form, h_apply, then for each of Fehlberg's six times t_s + a_j*h_form the five orbit
+    scalars of pos_att_orbit_table from propagate_kepler(R0, V0, t)]; rows beyond n_sub[k] are zero.  R0, V0 None: the
+    reference's target.  More than POSITION_MAX_SUB sub-steps in a stage are refused."""
+    from .orbit import _A
+    if R0 is None or V0 is None:
+        R0, V0 = target_R0V0()
+    K = int(n_steps)
+    if K < 0:
+        raise ValueError("position_rkf45_table needs n_steps >= 0")
+    sched = [position_rkf45_schedule(k * h, (k + 1) * h) for k in range(K)]
+    n_sub = np.array([len(s) for s in sched], dtype=np.int32)
+    if K and (n_sub.max() > POSITION_MAX_SUB or n_sub.min() < 1):
+        k = int(np.argmax((n_sub > POSITION_MAX_SUB) | (n_sub < 1)))
+        raise ValueError("stage %d takes %d sub-steps (1..%d supported)" % (k, n_sub[k], POSITION_MAX_SUB))
+    table = np.zeros((K, int(n_sub.max()) if K else 1, 32))
+    for k, steps in enumerate(sched):
+        for s, (t, hf, ha) in enumerate(steps):
+            row = table[k, s]
+            row[0], row[1] = hf, ha
+            for j in range(6):
+                R, V = propagate_kepler(R0, V0, t + _A[j] * hf, mu)
+                nR = math.sqrt(float(R @ R))
+                RdV = float(R @ V)
+                H = float(np.linalg.norm(np.cross(R, V)))
+                row[2 + 5 * j:7 + 5 * j] = [2 * mu / nR ** 3 + H * H / nR ** 4, 2 * RdV / nR ** 4 * H, 2 * H / nR ** 2,
+                                            mu / nR ** 3 - H * H / nR ** 4, mu / nR ** 3]
+    return n_sub, table
+
+
+def position_channels(sp):
+    """The three channel policies simplified_run left, as the GPU loop takes them: per channel (knots [s_x, s_v], labels as
+    stored (1-based, [n_x, n_v]), acceleration table [n_u, 1] = U_vector; get_optimal_path takes the policy's value as the
+    acceleration, :215-222)."""
+    if sp.U_idx[0] is None:
+        raise RuntimeError("simplified_run() first")
+    ut = np.asarray(sp.U_vector, dtype=np.float64).reshape(-1, 1)
+    return [([np.ascontiguousarray(g, dtype=np.float64) for g in getattr(sp, "U%d_Opt" % (ch + 1)).GridVectors], np.asarray(sp.U_idx[ch]), ut)
+            for ch in range(3)]
+
+
+def _absmax(m, v):
+    """max(m, |v|) that keeps a NaN once met, as numpy's max does"""
+    v = abs(v)
+    return v if (v > m or v != v) else m
+
+
+def position_optimal_path_fixed(sp, y0=None, n_steps=None, tol=1e-8, table=None):
+    """Solver_position.get_optimal_path with every stage's rkf45 call replaced by its schedule (position_rkf45_table): the scalar
+    host loop in the operation order of the GPU kernel (K19), which it equals bit for bit.  Returns what get_optimal_path
+    returns plus off_schedule: (T [N], X [6, N], F_Opt_history [3, N], off_schedule), off_schedule the first stage with a
+    sub-step where allowed >= 1100 * (te_max + eps) does not hold (rkf45 might not have grown its step fourfold there, or NaN),
+    -1 if none; the loop goes on along the schedule either way.  table: (n_sub, table) of position_rkf45_table for at least the
+    stages asked for, to spare building it once per start; None builds it."""
+    from .orbit import _B, _C4, _C5
+    chans = position_channels(sp)
+    y = [-1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if y0 is None else [float(v) for v in np.asarray(y0, dtype=np.float64).reshape(6)]
+    N = int(math.ceil(sp.T_final / sp.h))
+    if n_steps is not None:
+        N = min(N, int(n_steps) + 1)
+    R0, V0 = sp.get_target_R0V0()
+    n_sub, table = position_rkf45_table(N - 1, sp.h, R0, V0) if table is None else table
+    if len(n_sub) < N - 1:
+        raise ValueError("the table holds %d stages, %d asked for" % (len(n_sub), N - 1))
+    table = np.asarray(table)[:N - 1].tolist()
+    kn = [[k.tolist() for k in ch[0]] for ch in chans]
+    lab = [ch[1] for ch in chans]
+    ut = [ch[2][:, 0].tolist() for ch in chans]
+    eps = float(np.finfo(np.float64).eps)
+    tol = float(tol)
+    d = [float(v) for v in (_C4 - _C5)]
+    c5 = [float(v) for v in _C5]
+    used = (0, 2, 3, 4, 5)                            # d_1 = C5_1 = 0: no term
+
+    def rates(c, a, y):
+        c0, c1, c2, c3, c4 = c
+        return [y[3], y[4], y[5],
+                ((c0 * y[0] - c1 * y[1]) + c2 * y[4]) + a[0],
+                ((c1 * y[0] - c3 * y[1]) - c2 * y[3]) + a[1],
+                a[2] - c4 * y[2]]
+
+    X = np.zeros((6, N))
+    F = np.zeros((3, N))
+    X[:, 0] = y
+    off = -1
+    for k in range(N - 1):
+        a = [ut[ch][int(lab[ch][_nearest_index(kn[ch][0], y[ch]), _nearest_index(kn[ch][1], y[3 + ch])]) - 1] for ch in range(3)]
+        F[:, k] = a
+        on = True
+        for s in range(int(n_sub[k])):
+            row = table[k][s]
+            hf, ha = row[0], row[1]
+            f = [rates(row[2:7], a, y)]
+            for st in range(1, 6):
+                yin = list(y)
+                for j in range(st):
+                    hb = hf * _B[st][j]
+                    yin = [yin[i] + hb * f[j][i] for i in range(6)]
+                f.append(rates(row[2 + 5 * st:7 + 5 * st], a, yin))
+            te, ym = 0.0, 1.0
+            for i in range(6):
+                e = f[0][i] * d[0]
+                for j in used[1:]:
+                    e = e + f[j][i] * d[j]
+                te = _absmax(te, hf * e)
+                ym = _absmax(ym, y[i])
+            if not (tol * ym >= POSITION_GROWTH_MARGIN * (te + eps)):
+                on = False
+            yn = []
+            for i in range(6):
+                s5 = f[0][i] * c5[0]
+                for j in used[1:]:
+                    s5 = s5 + f[j][i] * c5[j]
+                yn.append(y[i] + ha * s5)
+            y = yn
+        if not on and off < 0:
+            off = k
+        X[:, k + 1] = y
+    return np.arange(N) * sp.h, X, F, off

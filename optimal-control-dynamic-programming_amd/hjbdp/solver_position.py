@@ -3,7 +3,9 @@
 `simplified_run` (:94-150): three independent 2-D (x_i, v_i) sweeps with the three
 thrust levels U_vector = [-0.26 0 0.26]; the `for k_s = N_stage-1:-1:1` loop
 (:132-141) runs in libhjbdp.  The forward simulation `get_optimal_path`
-(:189-311, RKF45 + orbital dynamics) is out of scope.
+(:189-311, RKF45 + orbital dynamics) is the scalar host loop below; for many
+initial states at once on the GPU, `get_optimal_paths` (hjbdp.Rollout.run_position,
+csrc/kernels_rollout_position.h).
 
 Reference quirk kept bit for bit (:157-186): RK4_x integrates xdynamics(v) = v but
 feeds V + k*h/2 back as the "state", so x+ = x + h*(k1+2k2+2k3+k4)/6 with
@@ -153,3 +155,60 @@ class Solver_position:
         self.X_path, self.F_Opt_history = X, F
         return np.arange(N) * self.h, X, F
 
+
+    def get_optimal_paths(self, y0s=None, n_steps=None, keep_path=False, tol=1e-8, device=None):
+        """get_optimal_path (:189-311) for many initial states at once on the GPU (hjbdp.Rollout.run_position, K19), after
+        simplified_run() (with or without keep_policy: the policies are the stationary U1_Opt .. U3_Opt get_optimal_path reads).
+        y0s [6, n] (None: the reference's start, :195-197).  Every stage runs rkf45's sub-steps on the schedule they follow at this
+        h (hjbdp/rollout.py::position_rkf45_schedule; position_optimal_path_fixed is the same loop on the host, bit for bit).
+        self.off_schedule [n] is the first stage at which a trajectory's error test no longer guaranteed that schedule (-1: none).
+        Flagged trajectories whose state at that stage is finite (entering and leaving it) are recomputed with the scalar
+        get_optimal_path(y0=...), the adaptive loop itself; self.off_schedule_recomputed counts them.  Flagged trajectories that
+        are not finite there keep the GPU's values (rkf45 does not end on a NaN).  Returns X_final [6, n], or with keep_path (T [N], X [6, N, n], F_Opt_history [3, N, n]) laid out as
+        get_optimal_path's, last F column zero; N = ceil(T_final / h) (or n_steps + 1)."""
+        from . import rollout
+        from .core import Rollout
+        chans = rollout.position_channels(self)                               # RuntimeError without simplified_run()
+        y0s = np.array([[-1.0], [0.0], [0.0], [0.0], [0.0], [0.0]]) if y0s is None else np.asarray(y0s, dtype=np.float64).reshape(6, -1)
+        N = int(math.ceil(self.T_final / self.h))
+        if n_steps is not None:
+            N = min(N, int(n_steps) + 1)
+        R0, V0 = self.get_target_R0V0()
+        n_sub, table = rollout.position_rkf45_table(N - 1, self.h, R0, V0)
+        dev = self.device if device is None else int(device)
+        n = y0s.shape[1]
+        ros = []
+        try:
+            for knots, labels, ut in chans:
+                ros.append(Rollout(knots, labels, ut, index_base=1, device=dev))
+            if N > 1:
+                ros[0].set_position_model(ros[1], ros[2], n_sub, table, tol)
+                out = ros[0].run_position(y0s, keep_path=keep_path)
+            else:
+                out = {"X_final": y0s.copy(), "off_schedule": np.full(n, -1, np.int32), "X_path": y0s.T[:, :, None].copy(), "A_path": np.zeros((n, 3, 0))}
+            off = out["off_schedule"]
+            flagged = np.flatnonzero(off >= 0)
+            redo = []
+            if flagged.size:
+                # the state each flagged trajectory had when it left the schedule: from the path, or from a short run that keeps one
+                Xp = out["X_path"] if keep_path else ros[0].run_position(y0s[:, flagged], np.zeros(int(off[flagged].max()) + 1, np.int32), keep_path=True)["X_path"]
+                rows = flagged if keep_path else np.arange(flagged.size)
+                redo = [int(i) for i, r in zip(flagged, rows) if np.isfinite(Xp[r, :, off[i]:off[i] + 2]).all()]
+        finally:
+            for ro in ros:
+                ro.close()
+        self.off_schedule = off
+        self.off_schedule_recomputed = len(redo)
+        Xf = np.array(out["X_final"])
+        if keep_path:
+            X = np.ascontiguousarray(out["X_path"].transpose(1, 2, 0))
+            F = np.zeros((3, N, n))
+            F[:, :N - 1] = out["A_path"].transpose(1, 2, 0)
+        for i in redo:
+            _, Xi, Fi = self.get_optimal_path(n_steps=N - 1, y0=y0s[:, i])
+            Xf[:, i] = Xi[:, N - 1]
+            if keep_path:
+                X[:, :, i], F[:, :, i] = Xi, Fi
+        if not keep_path:
+            return Xf
+        return np.arange(N) * self.h, X, F

@@ -9,8 +9,10 @@ Two cases, one JSON line:
                initial states; host rate: the same loop scalar in Python (interp_nearest_point + the update) over 100 of them.
   (c) attitude: the 6-D attitude policy (K17, hjb_rollout_run_attitude), see case_attitude.
   (d) pos_att_loop: the 13-state pos-att closed loop (K18, hjb_rollout_run_pos_att), see case_pos_att_loop.
+  (e) position_loop: Solver_position's RKF45 loop on its schedule (K19, hjb_rollout_run_position), see case_position_loop; alone,
+      it also writes its line to profiles/rollout_position_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop] [--out FILE]
 """
 from __future__ import annotations
 
@@ -190,6 +192,56 @@ def case_pos_att_loop(host=True, n_stages=None):
     return res
 
 
+def case_position_loop(host=True, n_traj=100000, n_stages=None):
+    """(e) position_loop: the three channel policies of Solver_position.simplified_run (201 x 201 states, 3 thrust levels,
+    stationary) driving the 6-state loop over all N_stage - 1 = 5,999 stages of five RKF45 sub-steps each, paths off, from 10^5
+    starts inside and outside the grid (the reference's own start among them).  The launch is timed with host clocks around the
+    whole call (upload, kernel, download of X_final and off_schedule; the entry point reports no kernel time of its own), best of
+    3 after a warm-up.  Host rates from the reference's start: get_optimal_path (orbit.rkf45 per stage) and
+    position_optimal_path_fixed (the schedule, scalar), 300 stages each, the table built beforehand."""
+    import hjbdp
+    from hjbdp import rollout
+    sp = hjbdp.Solver_position()
+    t0 = time.perf_counter()
+    sp.simplified_run()
+    sweep_s = time.perf_counter() - t0
+    K = sp.N_stage - 1 if n_stages is None else int(n_stages)
+    rng = np.random.default_rng(6)
+    X0 = np.concatenate([rng.uniform(-0.6, 0.6, size=(3, n_traj)), rng.uniform(-0.3, 0.3, size=(3, n_traj))])
+    X0[:, 0] = [-1.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+    t0 = time.perf_counter()
+    n_sub, table = rollout.position_rkf45_table(K, sp.h, *sp.get_target_R0V0())
+    table_s = time.perf_counter() - t0
+    res = {"grid": "201x201 per channel", "n_traj": int(n_traj), "n_steps": int(K), "sub_steps_per_stage": int(n_sub.max()),
+           "sweep_wall_s": round(sweep_s, 3), "table_build_s": round(table_s, 3),
+           "timing": "host wall clock around hjb_rollout_run_position (upload + kernel + download of X_final and off_schedule), best of 3"}
+    ros = [hjbdp.Rollout(k, l, t, index_base=1) for k, l, t in rollout.position_channels(sp)]
+    try:
+        res["labels"] = str(ros[0].labels_dtype)
+        ros[0].set_position_model(ros[1], ros[2], n_sub, table)
+        out = ros[0].run_position(X0)                            # warm-up, same shape
+        best = None
+        for _ in range(3):
+            t0 = time.perf_counter()
+            ros[0].run_position(X0)
+            dt = time.perf_counter() - t0
+            best = dt if best is None else min(best, dt)
+    finally:
+        for ro in ros:
+            ro.close()
+    res.update(ms_per_launch=round(best * 1e3, 3), traj_stages_per_s=n_traj * K / best, off_schedule=int((out["off_schedule"] >= 0).sum()))
+    if host:
+        t0 = time.perf_counter()
+        sp.get_optimal_path(n_steps=300)
+        res["host_rkf45_ms_per_stage"] = (time.perf_counter() - t0) / 300 * 1e3
+        t0 = time.perf_counter()
+        rollout.position_optimal_path_fixed(sp, n_steps=300, table=(n_sub, table))
+        res["host_fixed_ms_per_stage"] = (time.perf_counter() - t0) / 300 * 1e3
+        res["host_loop"] = "Solver_position.get_optimal_path (orbit.rkf45 per stage) / position_optimal_path_fixed (scalar, on the schedule)"
+        res["speedup_vs_host_rkf45"] = res["traj_stages_per_s"] * res["host_rkf45_ms_per_stage"] * 1e-3
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -201,8 +253,11 @@ def main():
         raise SystemExit("time_rollout needs a HIP device")
     res = {"tool": "time_rollout"}
     for c in a.cases.split(","):
-        res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude, "pos_att_loop": case_pos_att_loop}[c](host=not a.no_host)
+        res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude, "pos_att_loop": case_pos_att_loop,
+                  "position_loop": case_position_loop}[c](host=not a.no_host)
     print(json.dumps(res))
+    if a.cases == "position_loop" and not a.out:                  # its own record: one line
+        (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
