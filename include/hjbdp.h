@@ -449,6 +449,37 @@ int32_t hjb_rollout_set_position_model(void *rollout_x, void *rollout_y, void *r
 int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
                                  double *X_final, double *X_path, double *A_path, int32_t *off_schedule);
 
+/* The simplified attitude closed loop (attitude-control/Solver_attitude.m:835-925, get_optimal_path_simplified_testode45 after
+ * simplified_run; attitude-control/test/test_simplified.m:188-218) on three rollout objects, one per channel, each D == 2 over
+ * (w_i, theta_i) with n_u == 1 (the torque per label), on one device, in one label type.  Sharing and lifetime are those of the
+ * pos-att and position models: hjb_rollout_set_attitude_simplified_model attaches the model to rollout_1 (the last model set wins)
+ * and takes a share of rollout_2's and rollout_3's device data, so destroying those two afterwards is safe.  inertia [3, 3]
+ * column-major, finite, non-singular; h finite and > 0; substeps >= 1; qw, qt, r [3] finite (NULL = zeros).
+ * hjb_rollout_run_attitude_simplified steps X = [w1 w2 w3 q1 q2 q3 q4] (q4 scalar), all in double, left to right, every product
+ * rounded; stage k, p = plane_of_step[k]:
+ *   t_i = 2 asin(clamp(X[3+i], -1, 1)) (the library's fixed asin, <= 2 ulp of libm; the clamp is ours);
+ *   u_i = the 'nearest' lookup of channel i on plane p at (X[i], t_i), i = 0, 1, 2, held over the stage;
+ *   g_i = (qw_i (X[i] X[i]) + qt_i (t_i t_i)) + r_i (u_i u_i);  cost += (g_0 + g_1) + g_2   (the 2-D sweeps' stage cost, :220);
+ *   HJB_ATTS_FULL: `substeps` classical RK4 steps of h / substeps of w_dot = inertia^-1 (u - w x (inertia w)) (the inverse is the
+ *     adjugate over the determinant, formed once) and the quaternion kinematics (:902-922), quaternion NOT renormalised.  This
+ *     stands in for the reference's ode45: on the solver's default grids it differs from a Dormand-Prince 5(4) stage integrator
+ *     (rtol 1e-3, atol 1e-6) by RK4's truncation error, max |dX| 4.9e-13 over 5,999 stages at substeps 1 and 1.4e-14 at 2
+ *     (tests/test_rollout_attitude_simplified_abi.py), with every torque equal;
+ *   HJB_ATTS_DIAGONAL: the attitude model's RK4 step (hjb_rollout_set_attitude_model, HJB_ATT_RK4) at (J1, J2, J3) =
+ *     diag(inertia) > 0, ONE step of h, then q / |q| (test_simplified.m:195-217, :317-356); substeps must be 1.
+ * X0, X_final [7, n_traj]; cost [n_traj]; X_path [n_traj, 7, n_steps+1]; U_path, A_path [n_traj, 3, n_steps] (A_path: the three
+ * t_i the stage looked up at); every output but X_final may be NULL.  A non-finite X0 is HJB_E_INVALID; a state that leaves the
+ * grids or stops being finite is looked up at the clamped cell (NaN: cell 0) and the run completes.  The other hjb_rollout_run_*
+ * calls on such an object, and hjb_rollout_run_attitude_simplified on any other, are HJB_E_INVALID. */
+#define HJB_ATTS_FULL 0      /* full inertia matrix, RK4 sub-steps, no renormalisation (Solver_attitude.m:835-925) */
+#define HJB_ATTS_DIAGONAL 1  /* diagonal inertia, one RK4 step, q / |q| (test_simplified.m:195-217) */
+int32_t hjb_rollout_set_attitude_simplified_model(void *rollout_1, void *rollout_2, void *rollout_3, const double *inertia, double h,
+                                                  int32_t substeps, int32_t dynamics, const double *qw, const double *qt,
+                                                  const double *r);
+int32_t hjb_rollout_run_attitude_simplified(void *rollout_1, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                            const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
+                                            double *A_path);
+
 /* ---- flat builder API -------------------------------------------------------------------------------------------
  * hjb_problem holds arrays of structs with pointers, which MATLAB's loadlibrary/calllib cannot marshal.  These entry
  * points take primitives and plain arrays only, copy what they are given (the caller may free it at once), and end in

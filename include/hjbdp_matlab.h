@@ -114,4 +114,13 @@ int32_t hjb_rollout_set_position_model(void *rollout_x, void *rollout_y, void *r
                                        const int32_t *n_sub, const double *table);
 int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
                                  double *X_final, double *X_path, double *A_path, int32_t *off_schedule);
+/* the simplified attitude loop on three channel objects (attitude-control/Solver_attitude.m:835-925,
+ * get_optimal_path_simplified_testode45 after simplified_run); dynamics 0 = full inertia matrix, RK4 sub-steps, 1 = diagonal
+ * inertia, one RK4 step and q / |q| (hjbdp.h); usage: matlab/Solver_attitude_hjbdp_get_optimal_paths_simplified.m */
+int32_t hjb_rollout_set_attitude_simplified_model(void *rollout_1, void *rollout_2, void *rollout_3, const double *inertia, double h,
+                                                  int32_t substeps, int32_t dynamics, const double *qw, const double *qt,
+                                                  const double *r);
+int32_t hjb_rollout_run_attitude_simplified(void *rollout_1, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                            const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
+                                            double *A_path);
 #endif

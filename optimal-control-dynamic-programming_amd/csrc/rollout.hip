@@ -1,22 +1,24 @@
 // rollout.hip - hjb_rollout_*: batched closed-loop rollouts of a stored per-stage policy (include/hjbdp.h; kernels:
 // kernels_rollout.h for the affine model, kernels_rollout_attitude.h / rollout_attitude.hip for the attitude model,
 // kernels_rollout_pos_att.h / rollout_pos_att.hip for the pos-att model, kernels_rollout_position.h / rollout_position.hip for the
-// position model).
+// position model, kernels_rollout_attitude_simplified.h / rollout_attitude_simplified.hip for the simplified attitude model).
 #include "hjbdp_host.h"
 #include "kernels_rollout.h"
 #include "kernels_rollout_attitude.h"
 #include "kernels_rollout_pos_att.h"
 #include "kernels_rollout_position.h"
+#include "kernels_rollout_attitude_simplified.h"
 #include <memory>
 
 using namespace hjbhost;
 
 namespace {
 
-enum { kModelNone = 0, kModelAffine = 1, kModelAttitude = 2, kModelPosAtt = 3, kModelPosition = 4 };    // the last setter called wins
+enum { kModelNone = 0, kModelAffine = 1, kModelAttitude = 2, kModelPosAtt = 3, kModelPosition = 4, kModelAttSimplified = 5 };    // the last setter called wins
 
-// Device allocations with shared ownership: an object's grid, table and labels live as long as the object or a pos-att or position
-// model that reads them (hjb_rollout_set_pos_att_model / hjb_rollout_set_position_model on another object) does.  Freed under the
+// Device allocations with shared ownership: an object's grid, table and labels live as long as the object or a pos-att, position
+// or simplified attitude model that reads them (hjb_rollout_set_pos_att_model / hjb_rollout_set_position_model /
+// hjb_rollout_set_attitude_simplified_model on another object) does.  Freed under the
 // last owner's locks (destroy / set_*model).
 struct DevData {
     int device = 0;
@@ -46,6 +48,15 @@ struct Position {
     int max_steps = 0;              // stages the table holds
 };
 
+// The simplified attitude model of channel 1's object: channels 2 and 3's descriptors with their device data kept alive, the constants
+struct AttSimplified {
+    DPaChan c2{}, c3{};
+    std::shared_ptr<DevData> data_2, data_3;
+    DAttSimplified M{};
+    int dynamics = HJB_ATTS_FULL;
+    int n_planes = 0;               // of the three channels, the fewest
+};
+
 struct Rollout {
     std::mutex mu;                  // one call at a time per object
     int device = 0, D = 0, idx_bytes = 4, n_planes = 0;
@@ -55,6 +66,7 @@ struct Rollout {
     DAttitude M{};                  // the attitude model (set_attitude_model)
     std::unique_ptr<PosAtt> pa;     // the pos-att model (set_pos_att_model)
     std::unique_ptr<Position> ps;   // the position model (set_position_model)
+    std::unique_ptr<AttSimplified> as;   // the simplified attitude model (set_attitude_simplified_model)
     std::shared_ptr<DevData> data;
     hipStream_t stream = nullptr;
     std::string err;
@@ -77,6 +89,7 @@ int rfail(Rollout *ro, int code, const char *fmt, ...) {
 void release(Rollout *ro) {
     ro->pa.reset();
     ro->ps.reset();
+    ro->as.reset();
     ro->data.reset();
     if (ro->stream) (void)hipStreamDestroy(ro->stream);
     ro->stream = nullptr;
@@ -131,31 +144,33 @@ int check_run(Rollout *ro, int want, int method, int32_t n_steps, const int32_t 
     if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
     if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
     static const char *const setter[] = {"", "hjb_rollout_set_model", "hjb_rollout_set_attitude_model", "hjb_rollout_set_pos_att_model",
-                                         "hjb_rollout_set_position_model"};
+                                         "hjb_rollout_set_position_model", "hjb_rollout_set_attitude_simplified_model"};
     static const char *const runner[] = {"", "hjb_rollout_run", "hjb_rollout_run_attitude", "hjb_rollout_run_pos_att",
-                                         "hjb_rollout_run_position"};
-    static const char *const held[] = {"", "affine", "attitude", "pos-att", "position"};
+                                         "hjb_rollout_run_position", "hjb_rollout_run_attitude_simplified"};
+    static const char *const held[] = {"", "affine", "attitude", "pos-att", "position", "simplified attitude"};
     if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: run before %s", setter[want]);
     if (ro->model != want)
         return rfail(ro, HJB_E_INVALID, "rollout: the object holds the %s model (%s): call %s", held[ro->model], setter[ro->model],
                      runner[ro->model]);
     if (n_steps > 0 && !plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null plane_of_step");
-    const int n_planes = want == kModelPosAtt ? ro->pa->n_planes : want == kModelPosition ? ro->ps->n_planes : ro->n_planes;
+    const int n_planes = want == kModelPosAtt ? ro->pa->n_planes : want == kModelPosition ? ro->ps->n_planes
+                       : want == kModelAttSimplified ? ro->as->n_planes : ro->n_planes;
     for (int k = 0; k < n_steps; ++k)
         if (plane_of_step[k] < 0 || plane_of_step[k] >= n_planes)
             return rfail(ro, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d)", k, plane_of_step[k], n_planes);
     return HJB_OK;
 }
 
-// a pos-att or position model goes, and with it its hold on the other two channels
+// a pos-att, position or simplified attitude model goes, and with it its hold on the other two channels
 void drop_attached(Rollout *ro) {
-    if (!ro->pa && !ro->ps) return;
+    if (!ro->pa && !ro->ps && !ro->as) return;
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     ro->pa.reset();
     ro->ps.reset();
+    ro->as.reset();
 }
 
-// what K18 and K19 read of an object's policy (kernels_rollout_pos_att.h)
+// what K18, K19 and K20 read of an object's policy (kernels_rollout_pos_att.h)
 DPaChan pa_channel(const DRollout &R) {
     DPaChan c{};
     for (int a = 0; a < 4; ++a) {
@@ -513,6 +528,7 @@ int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *ro
     if (rx->stream) (void)hipStreamSynchronize(rx->stream);
     rx->pa = std::move(pa);                                 // replaces (and releases) a model set earlier
     rx->ps.reset();
+    rx->as.reset();
     rx->model = kModelPosAtt;
     return HJB_OK;
 }
@@ -581,7 +597,89 @@ int32_t hjb_rollout_set_position_model(void *rollout_x, void *rollout_y, void *r
     if (rx->stream) (void)hipStreamSynchronize(rx->stream);
     rx->ps = std::move(ps);                                 // replaces (and releases) a model set earlier
     rx->pa.reset();
+    rx->as.reset();
     rx->model = kModelPosition;
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_set_attitude_simplified_model(void *rollout_1, void *rollout_2, void *rollout_3, const double *inertia, double h,
+                                                  int32_t substeps, int32_t dynamics, const double *qw, const double *qt,
+                                                  const double *r) {
+    Rollout *r1 = (Rollout *)rollout_1, *r2 = (Rollout *)rollout_2, *r3 = (Rollout *)rollout_3;
+    // the arguments that need no object first (decided without a device), then the objects
+    if (!inertia) return rfail(r1, HJB_E_INVALID, "rollout: null argument (inertia is required)");
+    if (!all_finite(inertia, 9)) return rfail(r1, HJB_E_INVALID, "rollout: inertia is not finite");
+    if (!(std::isfinite(h) && h > 0)) return rfail(r1, HJB_E_INVALID, "rollout: h = %g is not finite and > 0", h);
+    if (substeps < 1) return rfail(r1, HJB_E_INVALID, "rollout: substeps = %d < 1", substeps);
+    if (dynamics != HJB_ATTS_FULL && dynamics != HJB_ATTS_DIAGONAL)
+        return rfail(r1, HJB_E_INVALID, "rollout: dynamics %d is not HJB_ATTS_FULL / HJB_ATTS_DIAGONAL", dynamics);
+    if (dynamics == HJB_ATTS_DIAGONAL && substeps != 1)
+        return rfail(r1, HJB_E_INVALID, "rollout: substeps = %d with HJB_ATTS_DIAGONAL (one RK4 step per stage: substeps must be 1)", substeps);
+    if (!all_finite(qw, 3)) return rfail(r1, HJB_E_INVALID, "rollout: qw is not finite");
+    if (!all_finite(qt, 3)) return rfail(r1, HJB_E_INVALID, "rollout: qt is not finite");
+    if (!all_finite(r, 3)) return rfail(r1, HJB_E_INVALID, "rollout: r is not finite");
+    DAttSimplified M{};
+    for (int a = 0; a < 3; ++a)
+        for (int c = 0; c < 3; ++c) M.J[3 * a + c] = inertia[a + 3 * c];       // column-major in, row-major kept
+    const double dj = pa_det3(M.J);
+    if (!(std::isfinite(dj) && dj != 0.0)) return rfail(r1, HJB_E_INVALID, "rollout: inertia is singular (determinant %g)", dj);
+    pa_inv3(M.J, M.Jinv);
+    if (!all_finite(M.Jinv, 9)) return rfail(r1, HJB_E_INVALID, "rollout: inertia is singular (its inverse is not finite)");
+    const double J1 = M.J[0], J2 = M.J[4], J3 = M.J[8];
+    if (dynamics == HJB_ATTS_DIAGONAL && !(J1 > 0 && J2 > 0 && J3 > 0))
+        return rfail(r1, HJB_E_INVALID, "rollout: inertia has diagonal (%g, %g, %g), HJB_ATTS_DIAGONAL needs it > 0", J1, J2, J3);
+    M.A.h = h;
+    M.A.J[0] = J1;
+    M.A.J[1] = J2;
+    M.A.J[2] = J3;
+    M.A.c[0] = (J2 - J3) / J1;                        // as hjb_rollout_set_attitude_model forms them
+    M.A.c[1] = (J3 - J1) / J2;
+    M.A.c[2] = (J1 - J2) / J3;
+    if (qw) std::memcpy(M.qw, qw, sizeof M.qw);
+    if (qt) std::memcpy(M.qt, qt, sizeof M.qt);
+    if (r) std::memcpy(M.r, r, sizeof M.r);
+    M.hs = h / substeps;
+    M.substeps = substeps;
+    if (!r1 || !r2 || !r3) return rfail(r1, HJB_E_INVALID, "rollout: null handle (three channel objects are required)");
+    if (r1 == r2 || r1 == r3 || r2 == r3) return rfail(r1, HJB_E_INVALID, "rollout: the same object passed for two channels");
+    auto as = std::make_unique<AttSimplified>();
+    as->M = M;
+    as->dynamics = dynamics;
+    // channels 2 and 3: a snapshot of the policy with a share of its device data, taken under that object's own lock
+    int dev_o[2] = {0, 0}, idx_o[2] = {0, 0}, planes_o[2] = {0, 0};
+    Rollout *others[2] = {r2, r3};
+    const char *names[2] = {"rollout_2", "rollout_3"};
+    for (int t = 0; t < 2; ++t) {
+        Rollout *o = others[t];
+        std::lock_guard<std::mutex> g(o->mu);
+        if (o->D != 2 || o->R.n_u != 1)
+            return rfail(r1, HJB_E_INVALID, "rollout: the simplified attitude model needs D == 2 and n_u == 1 (%s: D=%d, n_u=%d)", names[t], o->D,
+                         o->R.n_u);
+        (t == 0 ? as->c2 : as->c3) = pa_channel(o->R);
+        (t == 0 ? as->data_2 : as->data_3) = o->data;
+        dev_o[t] = o->device;
+        idx_o[t] = o->idx_bytes;
+        planes_o[t] = o->n_planes;
+    }
+    std::lock_guard<std::mutex> g(r1->mu);
+    if (r1->D != 2 || r1->R.n_u != 1)
+        return rfail(r1, HJB_E_INVALID, "rollout: the simplified attitude model needs D == 2 and n_u == 1 (rollout_1: D=%d, n_u=%d)", r1->D,
+                     r1->R.n_u);
+    for (int t = 0; t < 2; ++t) {
+        if (dev_o[t] != r1->device)
+            return rfail(r1, HJB_E_INVALID, "rollout: %s is on device %d, rollout_1 on device %d", names[t], dev_o[t], r1->device);
+        if (idx_o[t] != r1->idx_bytes)
+            return rfail(r1, HJB_E_INVALID, "rollout: %s has %d-byte labels, rollout_1 %d-byte labels (the three channels share one label type)",
+                         names[t], idx_o[t], r1->idx_bytes);
+    }
+    as->n_planes = std::min(r1->n_planes, std::min(planes_o[0], planes_o[1]));
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    if (hipSetDevice(r1->device) != hipSuccess) return rfail(r1, HJB_E_DEVICE, "hipSetDevice failed");
+    if (r1->stream) (void)hipStreamSynchronize(r1->stream);
+    r1->as = std::move(as);                                 // replaces (and releases) a model set earlier
+    r1->pa.reset();
+    r1->ps.reset();
+    r1->model = kModelAttSimplified;
     return HJB_OK;
 }
 
@@ -720,6 +818,39 @@ int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t
                           DPosition M = ps.M;
                           M.n_steps = R.n_steps;
                           return launch_rollout_position(idx_bytes, lds3_on, cx, cy, cz, M, nc, lds3, st, dX0, dXf, dXp, dAp, dOff);
+                      });
+}
+
+int32_t hjb_rollout_run_attitude_simplified(void *rollout_1, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                            const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
+                                            double *A_path) {
+    Rollout *ro = (Rollout *)rollout_1;
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    const int bad_arg = check_run(ro, kModelAttSimplified, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
+    if (bad_arg) return bad_arg;
+    const AttSimplified &as = *ro->as;
+    if (n_traj == 0) return HJB_OK;
+    if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final");
+    if (n_traj > INT64_MAX / (HJB_ATT_W * ((int64_t)n_steps + 1)) / 8)
+        return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x 7 x n_steps)");
+    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_ATT_W * n_traj, true);
+    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    const int idx_bytes = ro->idx_bytes;
+    const DPaChan c10 = pa_channel(ro->R);
+    const size_t lds3 = (size_t)(2 * ((int64_t)c10.n_knots + as.c2.n_knots + as.c3.n_knots) +
+                                 ((int64_t)c10.n_labels + as.c2.n_labels + as.c3.n_labels)) * sizeof(double);
+    const bool lds3_on = lds3 <= kLdsMax;
+    return run_chunks(ro, "hjb_rollout_run_attitude_simplified", HJB_ATT_W, HJB_ATT_U, 3, n_steps, plane_of_step, n_traj, X0, X_final, cost,
+                      X_path, U_path, A_path, nullptr, nullptr,
+                      [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *dC, double *dXp,
+                          double *dUp, double *dAp, int32_t *) {
+                          DPaChan c1 = c10, c2 = as.c2, c3 = as.c3;
+                          c1.plane_of_step = c2.plane_of_step = c3.plane_of_step = R.plane_of_step;
+                          DAttSimplified M = as.M;
+                          M.n_steps = R.n_steps;
+                          return launch_rollout_attitude_simplified(idx_bytes, lds3_on, as.dynamics, c1, c2, c3, M, nc, lds3, st, dX0, dXf,
+                                                                    dC, dXp, dUp, dAp);
                       });
 }
 

@@ -315,6 +315,42 @@ class Rollout:
         path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
         return {"X_final": Xf.T, "off_schedule": off, "X_path": path(Xp, 6, K + 1), "A_path": path(Ap, 3, K)}
 
+    def set_attitude_simplified_model(self, rollout_2, rollout_3, inertia, h, substeps=1, dynamics="full", qw=None, qt=None, r=None):
+        """The simplified attitude loop (hjb_rollout_set_attitude_simplified_model; the last model set wins) with this object as
+        channel 1 and two more Rollout objects as channels 2 and 3 (each D = 2 over (w_i, theta_i), n_u = 1, one device, one label
+        type).  inertia [3, 3]; dynamics 'full' (full inertia matrix, `substeps` RK4 steps of h / substeps per stage in place of
+        the reference's ode45, quaternion not renormalised: max |dX| against a Dormand-Prince stage integrator 4.9e-13 over 5,999
+        stages at substeps 1, 1.4e-14 at 2) or 'diagonal' (diag(inertia), one RK4 step, q / |q|: the reference's own arithmetic,
+        substeps must be 1).  qw, qt, r [3]: the stage-cost weights on w_i^2, theta_i^2, u_i^2 (None: zeros).  The model keeps what
+        it reads of the other two alive: they may be closed afterwards."""
+        dyn = {"full": _abi.HJB_ATTS_FULL, "diagonal": _abi.HJB_ATTS_DIAGONAL}[dynamics]
+        J = np.ascontiguousarray(np.asarray(inertia, dtype=np.float64).reshape(3, 3).reshape(-1, order="F"))
+        vec = lambda v: None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(3))
+        self._check(self.lib.hjb_rollout_set_attitude_simplified_model(self._ro, rollout_2._ro, rollout_3._ro, _f64p(J), float(h),
+                                                                       int(substeps), dyn, _f64p(vec(qw)), _f64p(vec(qt)), _f64p(vec(r))))
+
+    def run_attitude_simplified(self, X0, plane_of_step, keep_path=False):
+        """hjb_rollout_run_attitude_simplified: X0 [7, n_traj] (X = [w1 w2 w3 q1 q2 q3 q4], q4 scalar).  Returns X_final [7, n_traj],
+        cost [n_traj], X_path [n_traj, 7, n_steps+1], U_path [n_traj, 3, n_steps], A_path [n_traj, 3, n_steps] (the three
+        theta_i = 2 asin(q_i) in radians each stage looked up at); the paths None unless keep_path."""
+        X = np.asarray(X0, dtype=np.float64)
+        X = np.ascontiguousarray((X.reshape(7, 1) if X.ndim == 1 else X).reshape(7, -1).T)
+        nt = X.shape[0]
+        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
+        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
+            raise ValueError("plane_of_step does not fit int32")
+        ps = ps.astype(np.int32)
+        K = int(ps.size)
+        Xf = np.empty((nt, 7))
+        cost = np.empty(nt)
+        Xp = np.empty(nt * 7 * (K + 1)) if keep_path else None
+        Up = np.empty(nt * 3 * K) if keep_path else None
+        Ap = np.empty(nt * 3 * K) if keep_path else None
+        self._check(self.lib.hjb_rollout_run_attitude_simplified(self._ro, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X),
+                                                                 _f64p(Xf), _f64p(cost), _f64p(Xp), _f64p(Up), _f64p(Ap)))
+        path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
+        return {"X_final": Xf.T, "cost": cost, "X_path": path(Xp, 7, K + 1), "U_path": path(Up, 3, K), "A_path": path(Ap, 3, K)}
+
 
 class DeviceBuffer:
     """A device allocation owned through the library (hjb_device_malloc): what a host without a HIP binding of its

@@ -9,6 +9,7 @@ Host-side, scalar, O(N_stage) - the reference's own forward simulators restated 
                                        get_target_R0V0 :734-753, update_RV_target :755-782,
                                        to_Moments_Forces :804-823, ECI2body :825-829, RSW2ECI :831-847
   position-control/Solver_position.m   get_optimal_path :189-311 on private/rkf45.m's schedule (position_optimal_path_fixed)
+  attitude-control/test/test_simplified.m   "test on REAL SYSTEM DYNAMICS" :188-218 (attitude_optimal_path_simplified_fixed)
 
 State conventions of the reference: the attitude state is X = [w1 w2 w3 q1 q2 q3 q4] with q4 the scalar part; the
 pos-att state is X = [x(3) v(3) q(4) w(3)].  MATLAB's ode45 is Dormand-Prince 5(4) with RelTol 1e-3 / AbsTol 1e-6:
@@ -461,6 +462,115 @@ def pos_att_optimal_path_fixed(pa, X0=None, n_steps=None, substeps=1, channel_x=
             x = [x[i] + (hs * (acc[i] + r[i])) / 6.0 for i in range(13)]
         X[k + 1] = x
     return np.arange(N) * pa.h, X, F, FM
+
+
+# ---- Solver_attitude, simplified policies on the rigid body: the arithmetic of the GPU loop (K20, --------------------------------
+# csrc/kernels_rollout_attitude_simplified.h) ---------------------------------------------------------------------------------------
+def attitude_simplified_channels(sa, per_stage=False):
+    """The three channel policies simplified_run left, as the GPU loop takes them: per channel (knots [s_w, s_t], labels as stored
+    (1-based; [n_w, n_t]: the stationary plane of sa.U_idx, or with per_stage [n_w, n_t, n_stages] from sa.U_idx_stages, which
+    simplified_run(keep_policy=True) leaves: step k reads plane k as attitude-control/test/test_simplified.m:137-139 indexes
+    U_Opt(:,:,k_stage)), torque table [n_u, 1] = U_vector)."""
+    if getattr(sa, "U_idx", None) is None or sa.U1_Opt is None or not callable(sa.U1_Opt) or any(i is None for i in sa.U_idx):
+        raise RuntimeError("simplified_run() first")
+    if per_stage and getattr(sa, "U_idx_stages", None) is None:
+        raise RuntimeError("simplified_run() first (keep_policy=True for per_stage)")
+    ut = np.asarray(sa.U_vector, dtype=np.float64).reshape(-1, 1)
+    src = sa.U_idx_stages if per_stage else sa.U_idx
+    return [([np.ascontiguousarray(g, dtype=np.float64) for g in getattr(sa, "U%d_Opt" % (ch + 1)).GridVectors], np.asarray(src[ch]), ut)
+            for ch in range(3)]
+
+
+def attitude_optimal_path_simplified_fixed(sa, X0=None, n_steps=None, substeps=1, dynamics="full", per_stage=False):
+    """attitude_optimal_path_simplified with the stage integrator fixed: the scalar host loop in the operation order of the GPU
+    kernel (K20), which it equals bit for bit.  Per stage theta_i = 2 canon_asin(clamp(X[3+i], -1, 1)), the three 'nearest'
+    torques at (w_i, theta_i), the stage cost (Q_i w_i^2 + Qt_i theta_i^2) + R_i u_i^2 of the 2-D sweeps, then
+      dynamics 'full' (Solver_attitude.m:835-925): `substeps` classical RK4 steps of h / substeps of the full-inertia rigid body
+        in place of ode45, quaternion not renormalised.  NOT round-off: the gap to the ode45 loop is RK4's truncation error
+        against Dormand-Prince's 5th-order solution, measured on the default grids with a switching policy as max |dX| = 4.9e-13
+        over 5,999 stages (2.1e-12 over 2,000 stages from a fast tumbling start) with substeps = 1 and 1.4e-14 (1.4e-13) with
+        substeps = 2, every torque equal (tests/test_rollout_attitude_simplified_abi.py);
+      dynamics 'diagonal' (test/test_simplified.m:188-218): next_stage_states(., 'RK4') - diagonal inertia, one RK4 step,
+        q / |q| - the reference's own arithmetic; substeps must be 1.
+    per_stage: step k reads plane k of sa.U_idx_stages (simplified_run(keep_policy=True)).
+    Returns (T [N], X [N, 7], U [N, 3], TH [N, 3] (the theta_i looked up at), cost); the last U / TH row is zero."""
+    chans = attitude_simplified_channels(sa, per_stage)
+    if dynamics not in ("full", "diagonal"):
+        raise ValueError("dynamics must be 'full' or 'diagonal'")
+    S = int(substeps)
+    if S < 1 or (dynamics == "diagonal" and S != 1):
+        raise ValueError("substeps must be >= 1, and 1 with dynamics='diagonal'")
+    X0 = DEFAULT_X0_ATTITUDE if X0 is None else np.asarray(X0, dtype=np.float64).reshape(7)
+    N = sa.N_stage if n_steps is None else min(sa.N_stage, int(n_steps) + 1)
+    if per_stage and N - 1 > chans[0][1].shape[2]:
+        raise ValueError("%d steps, the stored policy has %d stages" % (N - 1, chans[0][1].shape[2]))
+    kn = [[k.tolist() for k in ch[0]] for ch in chans]
+    lab = [ch[1] for ch in chans]
+    tab = [ch[2][:, 0].tolist() for ch in chans]
+    Jm = [[float(v) for v in row] for row in np.asarray(sa.InertiaM, dtype=np.float64)]
+    Ji = [[float(v) for v in row] for row in inv3_adjugate(Jm)]
+    J1, J2, J3 = Jm[0][0], Jm[1][1], Jm[2][2]
+    c1, c2, c3 = (J2 - J3) / J1, (J3 - J1) / J2, (J1 - J2) / J3
+    qw = [float(sa.Q1), float(sa.Q2), float(sa.Q3)]
+    qt = [float(sa.Qt1), float(sa.Qt2), float(sa.Qt3)]
+    rr = [float(sa.R1), float(sa.R2), float(sa.R3)]
+    h = float(sa.h)
+    hs = h / S
+
+    def full(u, y):
+        w1, w2, w3, q1, q2, q3, q4 = y
+        jw = _mul3(Jm, w1, w2, w3)
+        t = [u[0] - (w2 * jw[2] - w3 * jw[1]), u[1] - (w3 * jw[0] - w1 * jw[2]), u[2] - (w1 * jw[1] - w2 * jw[0])]
+        return _mul3(Ji, t[0], t[1], t[2]) + [0.5 * (((w3 * q2) - (w2 * q3)) + (w1 * q4)),
+                                              0.5 * (((w1 * q3) - (w3 * q1)) + (w2 * q4)),
+                                              0.5 * (((w2 * q1) - (w1 * q2)) + (w3 * q4)),
+                                              0.5 * (((-(w1 * q1)) - (w2 * q2)) - (w3 * q3))]
+
+    def diag(u, y):
+        x1, x2, x3, x4, x5, x6, x7 = y
+        return [((c1 * x2) * x3) + u[0] / J1, ((c2 * x3) * x1) + u[1] / J2, ((c3 * x1) * x2) + u[2] / J3,
+                0.5 * (((x3 * x5) - (x2 * x6)) + (x1 * x7)), 0.5 * (((-x3 * x4) + (x1 * x6)) + (x2 * x7)),
+                0.5 * (((x2 * x4) - (x1 * x5)) + (x3 * x7)), 0.5 * (((-x1 * x4) - (x2 * x5)) - (x3 * x6))]
+
+    def rk4(rates, u, x, hh):
+        r = rates(u, x)
+        acc = r
+        xt = [x[i] + (r[i] * hh) / 2.0 for i in range(7)]
+        r = rates(u, xt)
+        acc = [acc[i] + 2.0 * r[i] for i in range(7)]
+        xt = [x[i] + (r[i] * hh) / 2.0 for i in range(7)]
+        r = rates(u, xt)
+        acc = [acc[i] + 2.0 * r[i] for i in range(7)]
+        xt = [x[i] + r[i] * hh for i in range(7)]
+        r = rates(u, xt)
+        return [x[i] + (hh * (acc[i] + r[i])) / 6.0 for i in range(7)]
+
+    X = np.zeros((N, 7))
+    U = np.zeros((N, 3))
+    TH = np.zeros((N, 3))
+    X[0] = X0
+    x = [float(v) for v in X0]
+    cost = 0.0
+    with np.errstate(all="ignore"):
+        for k in range(N - 1):
+            th = [2.0 * canon_asin(1.0 if x[3 + j] > 1.0 else -1.0 if x[3 + j] < -1.0 else x[3 + j]) for j in range(3)]
+            u = []
+            for ch in range(3):
+                idx = (_nearest_index(kn[ch][0], x[ch]), _nearest_index(kn[ch][1], th[ch]))
+                u.append(tab[ch][int(lab[ch][idx + (k,)] if per_stage else lab[ch][idx]) - 1])
+            g = [(qw[j] * (x[j] * x[j]) + qt[j] * (th[j] * th[j])) + rr[j] * (u[j] * u[j]) for j in range(3)]
+            cost = cost + ((g[0] + g[1]) + g[2])
+            U[k] = u
+            TH[k] = th
+            if dynamics == "full":
+                for _ in range(S):
+                    x = rk4(full, u, x, hs)
+            else:
+                x = rk4(diag, u, x, h)
+                nrm = np.float64(math.sqrt(((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]) + x[6] * x[6]))
+                x = x[:3] + [float(np.float64(v) / nrm) for v in x[3:]]       # numpy's division: 0 / 0 is NaN, not an exception
+            X[k + 1] = x
+    return np.arange(N) * sa.h, X, U, TH, cost
 
 
 # ---- Solver_position, RKF45 on its schedule: the arithmetic of the GPU loop (K19, csrc/kernels_rollout_position.h) ------------

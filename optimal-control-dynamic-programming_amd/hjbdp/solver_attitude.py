@@ -10,7 +10,8 @@ default sizes taken from the .asv revision.  The argmin returned is the true joi
 minimiser (i1,i2,i3) in cascade order; the reference's index composition at
 :290-292 is a linear-indexing bug and J is unaffected by it.
 Forward simulations (:508-591, :670-696, :744-925) run host-side in hjbdp/rollout.py; get_optimal_paths runs the
-closed loop of get_optimal_path (:744-833) for many initial attitudes at once on the GPU.
+closed loop of get_optimal_path (:744-833) for many initial attitudes at once on the GPU, get_optimal_paths_simplified that of
+get_optimal_path_simplified_testode45 (:835-925).
 """
 from __future__ import annotations
 
@@ -340,3 +341,52 @@ class Solver_attitude:
         from . import rollout
         return rollout.attitude_optimal_path_simplified(self, X0, n_steps)    # :835-925 (after simplified_run)
 
+    def get_optimal_paths_simplified(self, X0s=None, n_steps=None, substeps=1, dynamics="full", per_stage=False, keep_path=False,
+                                     device=None):
+        """get_optimal_path_simplified_testode45 (:835-925) for many initial attitudes at once on the GPU
+        (hjbdp.Rollout.run_attitude_simplified, K20), after simplified_run().  X0s [7, n] (None: the reference's X0, :160-164).
+        dynamics 'full': the full inertia matrix with `substeps` RK4 steps of h / substeps per stage in place of ode45, quaternion
+        not renormalised; against a Dormand-Prince stage integrator this differs by RK4's truncation error (measured on the
+        default grids: max |dX| = 4.9e-13 over 5,999 stages with substeps = 1, 1.4e-14 with 2; 2.1e-12 and 1.4e-13 over 2,000
+        stages from a fast tumbling start), with every torque equal.  dynamics 'diagonal': the development script's loop
+        (test/test_simplified.m:188-218): diagonal inertia, one RK4 step per stage, q / |q| - the reference's arithmetic itself.
+        per_stage: step k reads the policy of stage k (simplified_run(keep_policy=True)) instead of the stationary one.
+        The cost summed is the 2-D sweeps' (:220) with (Q1..3, Qt1..3, R1..3), so it compares with F_values.
+        Returns (X_final [7, n], cost [n]), or with keep_path (T [N], X [N, 7, n], U [N, 3, n], ANG [N, 3, n]) in the layout of
+        get_optimal_path_simplified_testode45, N = N_stage (or n_steps + 1): the last U / ANG row is zero and ANG is yaw, pitch,
+        roll in degrees from quat2angle([X7 X6 X5 X4]) (:856), computed on the host from X."""
+        from .core import Rollout
+        from .rollout import DEFAULT_X0_ATTITUDE, attitude_simplified_channels
+        chans = attitude_simplified_channels(self, per_stage)
+        X0s = DEFAULT_X0_ATTITUDE.reshape(7, 1) if X0s is None else np.asarray(X0s, dtype=np.float64).reshape(7, -1)
+        N = self.N_stage if n_steps is None else min(self.N_stage, int(n_steps) + 1)
+        if per_stage and N - 1 > chans[0][1].shape[2]:
+            raise ValueError("%d steps, the stored policy has %d stages" % (N - 1, chans[0][1].shape[2]))
+        dev = self.device if device is None else int(device)
+        n_lab = len(self.U_vector)
+        dt = np.uint8 if n_lab < 255 else np.uint16 if n_lab < 65535 else np.int32
+        ros = []
+        try:
+            for knots, labels, ut in chans:
+                ros.append(Rollout(knots, np.asarray(labels).astype(dt, copy=False), ut, index_base=1, device=dev))
+            ros[0].set_attitude_simplified_model(ros[1], ros[2], self.InertiaM, self.h, substeps, dynamics,
+                                                 qw=[self.Q1, self.Q2, self.Q3], qt=[self.Qt1, self.Qt2, self.Qt3],
+                                                 r=[self.R1, self.R2, self.R3])
+            planes = np.arange(N - 1, dtype=np.int32) if per_stage else np.zeros(N - 1, np.int32)
+            out = ros[0].run_attitude_simplified(X0s, planes, keep_path=keep_path)
+        finally:
+            for ro in ros:
+                ro.close()
+        if not keep_path:
+            return out["X_final"], out["cost"]
+        n = X0s.shape[1]
+        X = np.ascontiguousarray(out["X_path"].transpose(2, 1, 0))            # [N, 7, n]
+        U = np.zeros((N, 3, n))
+        U[:N - 1] = out["U_path"].transpose(2, 1, 0)
+        q0, q1, q2, q3 = X[:N - 1, 6], X[:N - 1, 5], X[:N - 1, 4], X[:N - 1, 3]       # quat2angle([X7 X6 X5 X4]), 'ZYX'
+        ANG = np.zeros((N, 3, n))
+        with np.errstate(all="ignore"):
+            ANG[:N - 1, 0] = np.degrees(np.arctan2(2.0 * (q1 * q2 + q0 * q3), q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3))
+            ANG[:N - 1, 1] = np.degrees(np.arcsin(np.clip(-2.0 * (q1 * q3 - q0 * q2), -1.0, 1.0)))
+            ANG[:N - 1, 2] = np.degrees(np.arctan2(2.0 * (q2 * q3 + q0 * q1), q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3))
+        return np.arange(N) * self.h, X, U, ANG

@@ -11,8 +11,10 @@ Two cases, one JSON line:
   (d) pos_att_loop: the 13-state pos-att closed loop (K18, hjb_rollout_run_pos_att), see case_pos_att_loop.
   (e) position_loop: Solver_position's RKF45 loop on its schedule (K19, hjb_rollout_run_position), see case_position_loop; alone,
       it also writes its line to profiles/rollout_position_time.json.
+  (f) attitude_simplified_loop: the simplified attitude policies on the rigid body (K20, hjb_rollout_run_attitude_simplified), see
+      case_attitude_simplified_loop; alone, it also writes its line to profiles/rollout_attitude_simplified_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop] [--out FILE]
 """
 from __future__ import annotations
 
@@ -242,6 +244,64 @@ def case_position_loop(host=True, n_traj=100000, n_stages=None):
     return res
 
 
+def case_attitude_simplified_loop(host=True, n_traj=100000, n_stages=None):
+    """(f) attitude_simplified_loop: the three channel policies of Solver_attitude.simplified_run (1000 x 300 states, 3 torque
+    levels, stationary) driving the full rigid body (dynamics 'full', substeps 1) over all N_stage - 1 = 5,999 stages, paths off,
+    from 10^5 starts drawn inside the grids (the reference's own start among them).  The launch is timed with host clocks around the
+    whole call (upload, kernel, download of X_final and cost; the call ends in a stream synchronise and reports no kernel time of
+    its own): five calls after a warm-up of the same shape, all five listed, the median quoted.  Host rates from the reference's
+    start: attitude_optimal_path_simplified (scipy RK45 per stage) and attitude_optimal_path_simplified_fixed (the scalar twin),
+    600 stages each."""
+    import hjbdp
+    from hjbdp import rollout
+    sa = hjbdp.Solver_attitude()
+    t0 = time.perf_counter()
+    sa.simplified_run()
+    sweep_s = time.perf_counter() - t0
+    K = sa.N_stage - 1 if n_stages is None else int(n_stages)
+    chans = rollout.attitude_simplified_channels(sa)
+    rng = np.random.default_rng(20)
+    X0 = np.empty((7, n_traj))
+    for ch, (knots, _, _) in enumerate(chans):
+        X0[ch] = rng.uniform(knots[0][0], knots[0][-1], n_traj)
+        X0[3 + ch] = np.sin(rng.uniform(knots[1][0], knots[1][-1], n_traj) / 2)
+    X0[6] = np.sqrt(1.0 - (X0[3:6] ** 2).sum(axis=0))
+    X0[:, 0] = rollout.DEFAULT_X0_ATTITUDE
+    res = {"grid": "%dx%d per channel" % (len(chans[0][0][0]), len(chans[0][0][1])), "n_traj": int(n_traj), "n_steps": int(K),
+           "dynamics": "full", "substeps": 1, "sweep_wall_s": round(sweep_s, 3),
+           "timing": "host wall clock around hjb_rollout_run_attitude_simplified (upload + kernel + download of X_final and cost), "
+                     "5 calls after a warm-up"}
+    ros = [hjbdp.Rollout(k, np.asarray(l).astype(np.uint8), t, index_base=1) for k, l, t in chans]
+    try:
+        res["labels"] = str(ros[0].labels_dtype)
+        ros[0].set_attitude_simplified_model(ros[1], ros[2], sa.InertiaM, sa.h, 1, "full", qw=[sa.Q1, sa.Q2, sa.Q3],
+                                             qt=[sa.Qt1, sa.Qt2, sa.Qt3], r=[sa.R1, sa.R2, sa.R3])
+        planes = np.zeros(K, np.int32)
+        out = ros[0].run_attitude_simplified(X0, planes)         # warm-up, same shape
+        times = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            ros[0].run_attitude_simplified(X0, planes)
+            times.append(time.perf_counter() - t0)
+    finally:
+        for ro in ros:
+            ro.close()
+    med = float(np.median(times))
+    res.update(ms_per_call=[round(t * 1e3, 3) for t in times], ms_per_call_median=round(med * 1e3, 3), traj_stages_per_s=n_traj * K / med,
+               finite_final=int(np.isfinite(out["X_final"]).all(axis=0).sum()))
+    if host:
+        t0 = time.perf_counter()
+        rollout.attitude_optimal_path_simplified(sa, n_steps=600)
+        res["host_ode45_stages_per_s"] = 600 / (time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        rollout.attitude_optimal_path_simplified_fixed(sa, n_steps=600)
+        res["host_fixed_stages_per_s"] = 600 / (time.perf_counter() - t0)
+        res["host_loop"] = ("attitude_optimal_path_simplified (scipy RK45 per stage) / attitude_optimal_path_simplified_fixed "
+                            "(scalar RK4), default X0")
+        res["speedup_vs_host_ode45"] = res["traj_stages_per_s"] / res["host_ode45_stages_per_s"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -254,10 +314,12 @@ def main():
     res = {"tool": "time_rollout"}
     for c in a.cases.split(","):
         res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude, "pos_att_loop": case_pos_att_loop,
-                  "position_loop": case_position_loop}[c](host=not a.no_host)
+                  "position_loop": case_position_loop, "attitude_simplified_loop": case_attitude_simplified_loop}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.cases == "position_loop" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "attitude_simplified_loop" and not a.out:       # its own record: one line
+        (ROOT / "profiles" / "rollout_attitude_simplified_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
