@@ -480,6 +480,33 @@ int32_t hjb_rollout_run_attitude_simplified(void *rollout_1, int32_t n_steps, co
                                             const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
                                             double *A_path);
 
+/* The linear attitude controller's closed loop (attitude-control/Solver_attitude.m:508-591, linear_control_response: the PD law
+ * U = -K qe(1:3) - C w the DP controllers are judged against) for many initial attitudes at once.  Stateless: there is no policy,
+ * so no object; the plant is the attitude model's (hjb_rollout_set_attitude_model: inertia = [J1 J2 J3], h, HJB_ATT_TAYLOR /
+ * HJB_ATT_RK4, then q / |q|), which with HJB_ATT_RK4 is next_stage_states(., 'RK4') operation for operation.  K, C [3, 3] and
+ * qc [4, 4] (NULL = identity) column-major; u_limit [3] >= 0 (NULL = none); weights [10] (NULL = zeros).  All in double, left to
+ * right, every product rounded; step k, X = [w1 w2 w3 q1 q2 q3 q4] (q4 scalar):
+ *   qe_i = ((qc[i,0]*X4 + qc[i,1]*X5) + qc[i,2]*X6) + qc[i,3]*X7, i = 0, 1, 2 (:536; row 3 of qc is not used by the law);
+ *   u_i = (-((K[i,0]*qe_0 + K[i,1]*qe_1) + K[i,2]*qe_2)) - ((C[i,0]*X1 + C[i,1]*X2) + C[i,2]*X3)   (:538);
+ *   with u_limit: u_i = u_i > L_i ? L_i : u_i < -L_i ? -L_i : u_i (a NaN passes through);
+ *   A_path[., k] = (yaw, pitch, roll) of X as hjb_rollout_run_attitude forms them (:540);
+ *   HJB_ATTL_COST_QUAT, weights = q[7] then r[3]: hjb_rollout_run_attitude's stage cost;
+ *   HJB_ATTL_COST_ANGLE, weights = qw[3], qt[3], r[3], one unused: hjb_rollout_run_attitude_simplified's, t_i = 2 asin(clamp(X[3+i], -1, 1));
+ *   X+ = the attitude model's step with u held, then X4..X7 / sqrt(((X4*X4 + X5*X5) + X6*X6) + X7*X7).
+ * X0, X_final [7, n_traj]; cost [n_traj]; X_path [n_traj, 7, n_steps+1]; U_path, A_path [n_traj, 3, n_steps]; every output but
+ * X_final may be NULL.  chunk: trajectories per launch (0 = 1 << 20, at most 1 << 30); device_ms (may be NULL): the launches'
+ * event times summed.  HJB_E_INVALID, with a text in hjb_rollout_last_error(NULL), decided before any device work: a null inertia,
+ * K, C, X0 or X_final; inertia or h not finite and > 0; an unknown integrator or cost_form; a non-finite entry of K, C, qc,
+ * u_limit, weights or X0; a negative limit; an X0 column whose quaternion is all zeros; n_steps < 0; n_traj < 0; chunk outside
+ * 0 .. 1 << 30; a negative device; size overflow.  n_traj == 0 is HJB_OK without touching a device; after the checks, no device
+ * visible is HJB_E_DEVICE. */
+#define HJB_ATTL_COST_QUAT 0    /* weights = q[7] then r[3]:           hjb_rollout_run_attitude's stage cost */
+#define HJB_ATTL_COST_ANGLE 1   /* weights = qw[3], qt[3], r[3], one unused: hjb_rollout_run_attitude_simplified's */
+int32_t hjb_attitude_linear_response(int32_t device, const double *inertia, double h, int32_t integrator, const double *K,
+                                     const double *C, const double *qc, const double *u_limit, int32_t cost_form,
+                                     const double *weights, int32_t n_steps, int64_t n_traj, const double *X0, double *X_final,
+                                     double *cost, double *X_path, double *U_path, double *A_path, int64_t chunk, double *device_ms);
+
 /* ---- flat builder API -------------------------------------------------------------------------------------------
  * hjb_problem holds arrays of structs with pointers, which MATLAB's loadlibrary/calllib cannot marshal.  These entry
  * points take primitives and plain arrays only, copy what they are given (the caller may free it at once), and end in

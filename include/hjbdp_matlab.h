@@ -123,4 +123,11 @@ int32_t hjb_rollout_set_attitude_simplified_model(void *rollout_1, void *rollout
 int32_t hjb_rollout_run_attitude_simplified(void *rollout_1, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                                             const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
                                             double *A_path);
+/* the linear attitude controller's closed loop (attitude-control/Solver_attitude.m:508-591, linear_control_response), stateless;
+ * integrator 0 = taylor, 1 = RK4; cost_form 0 = weights q[7] r[3], 1 = weights qw[3] qt[3] r[3] and one unused (hjbdp.h); usage:
+ * matlab/Solver_attitude_hjbdp_linear_control_responses.m */
+int32_t hjb_attitude_linear_response(int32_t device, const double *inertia, double h, int32_t integrator, const double *K,
+                                     const double *C, const double *qc, const double *u_limit, int32_t cost_form,
+                                     const double *weights, int32_t n_steps, int64_t n_traj, const double *X0, double *X_final,
+                                     double *cost, double *X_path, double *U_path, double *A_path, int64_t chunk, double *device_ms);
 #endif

@@ -1,13 +1,15 @@
 // rollout.hip - hjb_rollout_*: batched closed-loop rollouts of a stored per-stage policy (include/hjbdp.h; kernels:
 // kernels_rollout.h for the affine model, kernels_rollout_attitude.h / rollout_attitude.hip for the attitude model,
 // kernels_rollout_pos_att.h / rollout_pos_att.hip for the pos-att model, kernels_rollout_position.h / rollout_position.hip for the
-// position model, kernels_rollout_attitude_simplified.h / rollout_attitude_simplified.hip for the simplified attitude model).
+// position model, kernels_rollout_attitude_simplified.h / rollout_attitude_simplified.hip for the simplified attitude model,
+// kernels_rollout_attitude_linear.h / rollout_attitude_linear.hip for the stateless linear attitude controller).
 #include "hjbdp_host.h"
 #include "kernels_rollout.h"
 #include "kernels_rollout_attitude.h"
 #include "kernels_rollout_pos_att.h"
 #include "kernels_rollout_position.h"
 #include "kernels_rollout_attitude_simplified.h"
+#include "kernels_rollout_attitude_linear.h"
 #include <memory>
 
 using namespace hjbhost;
@@ -196,7 +198,8 @@ DPaChan pa_channel(const DRollout &R) {
 // path rows (E_path: the attitude loop's angles, the pos-att loop's Force_Moment).  Per chunk: upload X0, launch(R, nc, lds, lds_on, stream, X0, Xf, cost, Xp, Up, Ep, Fl) (the
 // kernel of the entry point `who`; Fl: nc int32 flags, allocated when `flags` is asked for: the position loop's off_schedule),
 // download X_final / cost / flags and the paths ([nc, rows] on the device -> columns i0 .. i0+nc of
-// [n_traj, rows] on the host); device_ms sums the launches' event times.
+// [n_traj, rows] on the host); device_ms sums the launches' event times.  plane_of_step may be null for a loop without a policy
+// (hjb_attitude_linear_response): nothing is uploaded then.
 template <typename Launch>
 int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *E_path, int32_t *flags,
@@ -233,7 +236,7 @@ int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess && n_steps > 0) e = hipMemcpyAsync(bufs[5], plane_of_step, pb, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_steps > 0 && plane_of_step) e = hipMemcpyAsync(bufs[5], plane_of_step, pb, hipMemcpyHostToDevice, st);
     DRollout R = ro->R;
     R.plane_of_step = (const int32_t *)bufs[5];
     R.n_steps = n_steps;
@@ -852,6 +855,98 @@ int32_t hjb_rollout_run_attitude_simplified(void *rollout_1, int32_t n_steps, co
                           return launch_rollout_attitude_simplified(idx_bytes, lds3_on, as.dynamics, c1, c2, c3, M, nc, lds3, st, dX0, dXf,
                                                                     dC, dXp, dUp, dAp);
                       });
+}
+
+int32_t hjb_attitude_linear_response(int32_t device, const double *inertia, double h, int32_t integrator, const double *K,
+                                     const double *C, const double *qc, const double *u_limit, int32_t cost_form,
+                                     const double *weights, int32_t n_steps, int64_t n_traj, const double *X0, double *X_final,
+                                     double *cost, double *X_path, double *U_path, double *A_path, int64_t chunk, double *device_ms) {
+    const char *const who = "hjb_attitude_linear_response";
+    if (device_ms) *device_ms = 0.0;
+    // every refusal first: none of them needs a device
+    if (!inertia || !K || !C) return rfail(nullptr, HJB_E_INVALID, "%s: null argument (inertia, K and C are required)", who);
+    if (device < 0) return rfail(nullptr, HJB_E_INVALID, "%s: device %d", who, device);
+    for (int a = 0; a < 3; ++a)
+        if (!(std::isfinite(inertia[a]) && inertia[a] > 0))
+            return rfail(nullptr, HJB_E_INVALID, "%s: inertia J%d = %g is not finite and > 0", who, a + 1, inertia[a]);
+    if (!(std::isfinite(h) && h > 0)) return rfail(nullptr, HJB_E_INVALID, "%s: h = %g is not finite and > 0", who, h);
+    if (integrator != HJB_ATT_TAYLOR && integrator != HJB_ATT_RK4)
+        return rfail(nullptr, HJB_E_INVALID, "%s: integrator %d is not HJB_ATT_TAYLOR / HJB_ATT_RK4", who, integrator);
+    if (cost_form != HJB_ATTL_COST_QUAT && cost_form != HJB_ATTL_COST_ANGLE)
+        return rfail(nullptr, HJB_E_INVALID, "%s: cost_form %d is not HJB_ATTL_COST_QUAT / HJB_ATTL_COST_ANGLE", who, cost_form);
+    if (!all_finite(K, 9)) return rfail(nullptr, HJB_E_INVALID, "%s: K is not finite", who);
+    if (!all_finite(C, 9)) return rfail(nullptr, HJB_E_INVALID, "%s: C is not finite", who);
+    if (!all_finite(qc, 16)) return rfail(nullptr, HJB_E_INVALID, "%s: qc is not finite", who);
+    if (!all_finite(u_limit, 3)) return rfail(nullptr, HJB_E_INVALID, "%s: u_limit is not finite", who);
+    for (int a = 0; u_limit && a < 3; ++a)
+        if (u_limit[a] < 0) return rfail(nullptr, HJB_E_INVALID, "%s: u_limit[%d] = %g < 0", who, a, u_limit[a]);
+    if (!all_finite(weights, 10)) return rfail(nullptr, HJB_E_INVALID, "%s: weights is not finite", who);
+    if (n_steps < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_steps=%d < 0", who, n_steps);
+    if (n_traj < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_traj=%lld < 0", who, (long long)n_traj);
+    if (chunk < 0 || chunk > kMaxChunk)
+        return rfail(nullptr, HJB_E_INVALID, "%s: chunk %lld not in 0..%lld", who, (long long)chunk, (long long)kMaxChunk);
+    if (n_traj == 0) return HJB_OK;
+    if (!X0 || !X_final) return rfail(nullptr, HJB_E_INVALID, "%s: null X0 / X_final", who);
+    if (n_traj > INT64_MAX / (HJB_ATT_W * ((int64_t)n_steps + 1)) / 8)
+        return rfail(nullptr, HJB_E_INVALID, "%s: size overflow (n_traj x 7 x n_steps)", who);
+    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_ATT_W * n_traj, true);
+    if (bad >= 0) return rfail(nullptr, HJB_E_INVALID, "%s: X0 element %lld is not finite", who, (long long)bad);
+    for (int64_t i = 0; i < n_traj; ++i) {
+        const double *q = X0 + HJB_ATT_W * i + 3;
+        if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)
+            return rfail(nullptr, HJB_E_INVALID, "%s: X0 column %lld has an all-zero quaternion (0/0 at the first renormalisation)", who,
+                         (long long)i);
+    }
+    DAttLinear M{};
+    M.A.h = h;
+    const double J1 = inertia[0], J2 = inertia[1], J3 = inertia[2];
+    M.A.J[0] = J1;
+    M.A.J[1] = J2;
+    M.A.J[2] = J3;
+    M.A.c[0] = (J2 - J3) / J1;                        // as hjb_rollout_set_attitude_model forms them
+    M.A.c[1] = (J3 - J1) / J2;
+    M.A.c[2] = (J1 - J2) / J3;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) {                 // column-major in, row-major kept
+            M.K[3 * r + c] = K[r + 3 * c];
+            M.C[3 * r + c] = C[r + 3 * c];
+        }
+        for (int c = 0; c < 4; ++c) M.qc[4 * r + c] = qc ? qc[r + 4 * c] : (r == c ? 1.0 : 0.0);
+    }
+    if (u_limit) std::memcpy(M.L, u_limit, sizeof M.L);
+    M.has_limit = u_limit ? 1 : 0;
+    if (weights) std::memcpy(M.w, weights, sizeof M.w);
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return rfail(nullptr, HJB_E_DEVICE, "no HIP device visible (libhjbdp has no CPU fallback)");
+    if (device >= ndev) return rfail(nullptr, HJB_E_INVALID, "%s: device %d (%d visible)", who, device, ndev);
+    // a transient object without a policy: run_chunks reads its device, chunk and stream only
+    Rollout ro;
+    ro.device = device;
+    if (chunk > 0) ro.chunk = chunk;
+    {
+        std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+        if (hipSetDevice(device) != hipSuccess) return rfail(nullptr, HJB_E_DEVICE, "hipSetDevice failed");
+        if (hipStreamCreateWithFlags(&ro.stream, hipStreamNonBlocking) != hipSuccess) {
+            ro.stream = nullptr;
+            return rfail(nullptr, HJB_E_DEVICE, "%s: stream creation failed", who);
+        }
+    }
+    const int st = run_chunks(&ro, who, HJB_ATT_W, HJB_ATT_U, 3, n_steps, nullptr, n_traj, X0, X_final, cost, X_path, U_path, A_path,
+                              nullptr, device_ms,
+                              [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t s, double *dX0, double *dXf, double *dC,
+                                  double *dXp, double *dUp, double *dAp, int32_t *) {
+                                  DAttLinear Mk = M;
+                                  Mk.n_steps = R.n_steps;
+                                  return launch_rollout_attitude_linear(integrator, cost_form, Mk, nc, s, dX0, dXf, dC, dXp, dUp, dAp);
+                              });
+    {
+        std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+        (void)hipSetDevice(device);
+        release(&ro);
+    }
+    return st;
 }
 
 int32_t hjb_rollout_destroy(void *rollout) {

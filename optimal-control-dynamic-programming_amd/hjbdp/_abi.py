@@ -238,12 +238,18 @@ SYMBOLS = {
                                                   + [C.POINTER(C.c_double)] * 3),
     "hjb_rollout_run_attitude_simplified": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64]
                                             + [C.POINTER(C.c_double)] * 6),
+    # the linear attitude controller's closed loop: stateless
+    "hjb_attitude_linear_response": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_int32] + [C.POINTER(C.c_double)] * 4
+                                     + [C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int64] + [C.POINTER(C.c_double)] * 6
+                                     + [C.c_int64, C.POINTER(C.c_double)]),
 }
 HJB_ROLLOUT_MAX_U = 4
 HJB_ATT_TAYLOR = 0
 HJB_ATT_RK4 = 1
 HJB_ATTS_FULL = 0
 HJB_ATTS_DIAGONAL = 1
+HJB_ATTL_COST_QUAT = 0
+HJB_ATTL_COST_ANGLE = 1
 HJB_LOOKUP_NEAREST = 0
 HJB_LOOKUP_LINEAR = 1
 

@@ -352,6 +352,52 @@ class Rollout:
         return {"X_final": Xf.T, "cost": cost, "X_path": path(Xp, 7, K + 1), "U_path": path(Up, 3, K), "A_path": path(Ap, 3, K)}
 
 
+def attitude_linear_response(inertia, h, K, C_gain, X0, n_steps, qc=None, u_limit=None, integrator="RK4", cost_form="quat",
+                             weights=None, keep_path=False, chunk=0, device=0):
+    """hjb_attitude_linear_response: the closed loop of the linear attitude controller U = -K qe(1:3) - C w
+    (attitude-control/Solver_attitude.m:508-591) from many initial attitudes at once on the GPU (K21).  No policy, so no object.
+    inertia = (J1, J2, J3), step h, K and C_gain [3, 3], qc [4, 4] (None: identity), u_limit [3] >= 0 (None: no limit), integrator
+    'taylor' or 'RK4', X0 [7, n_traj] (X = [w1 w2 w3 q1 q2 q3 q4], q4 scalar).  cost_form 'quat': weights = q [7] then r [3], the
+    stage cost of Rollout.run_attitude; 'angle': weights = qw [3], qt [3], r [3] (a tenth entry is ignored), that of
+    Rollout.run_attitude_simplified; None: zeros.  Returns what Rollout.run_attitude returns: X_final [7, n_traj], cost [n_traj],
+    X_path [n_traj, 7, n_steps+1], U_path [n_traj, 3, n_steps], A_path [n_traj, 3, n_steps] (yaw, pitch, roll in radians; the
+    paths None unless keep_path) and device_ms."""
+    lib = load_library()
+    integ = {"taylor": _abi.HJB_ATT_TAYLOR, "RK4": _abi.HJB_ATT_RK4, "rk4": _abi.HJB_ATT_RK4}[integrator]
+    form = {"quat": _abi.HJB_ATTL_COST_QUAT, "angle": _abi.HJB_ATTL_COST_ANGLE}[cost_form]
+    J = np.ascontiguousarray(np.asarray(inertia, dtype=np.float64).reshape(3))
+    mat = lambda v, m: None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(m, m).reshape(-1, order="F"))
+    Km, Cm, qcm = mat(K, 3), mat(C_gain, 3), mat(qc, 4)
+    lim = None if u_limit is None else np.ascontiguousarray(np.asarray(u_limit, dtype=np.float64).reshape(3))
+    wt = None
+    if weights is not None:
+        wt = np.zeros(10)
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.size not in ((10,) if form == _abi.HJB_ATTL_COST_QUAT else (9, 10)):
+            raise ValueError("weights: %d entries (cost_form 'quat' takes 10, 'angle' 9 or 10)" % w.size)
+        wt[:w.size] = w
+    X = np.asarray(X0, dtype=np.float64)
+    X = np.ascontiguousarray((X.reshape(7, 1) if X.ndim == 1 else X).reshape(7, -1).T)
+    nt = X.shape[0]
+    Kn = int(n_steps)
+    Xf = np.empty((nt, 7))
+    cost = np.empty(nt)
+    keep = keep_path and Kn >= 0
+    Xp = np.empty(nt * 7 * (Kn + 1)) if keep else None
+    Up = np.empty(nt * 3 * Kn) if keep else None
+    Ap = np.empty(nt * 3 * Kn) if keep else None
+    ms = C.c_double(0.0)
+    st = lib.hjb_attitude_linear_response(int(device), _f64p(J), float(h), integ, _f64p(Km), _f64p(Cm), _f64p(qcm), _f64p(lim), form,
+                                          _f64p(wt), Kn, nt, _f64p(X), _f64p(Xf), _f64p(cost), _f64p(Xp), _f64p(Up), _f64p(Ap),
+                                          int(chunk), C.byref(ms))
+    if st != _abi.HJB_OK:
+        msg = lib.hjb_rollout_last_error(None)
+        raise HjbError(st, (msg or b"").decode() or lib.hjb_status_string(st).decode())
+    path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
+    return {"X_final": Xf.T, "cost": cost, "X_path": path(Xp, 7, Kn + 1), "U_path": path(Up, 3, Kn), "A_path": path(Ap, 3, Kn),
+            "device_ms": ms.value}
+
+
 class DeviceBuffer:
     """A device allocation owned through the library (hjb_device_malloc): what a host without a HIP binding of its
     own hands to Backup.backup_stage_device.  `ptr` is an ordinary HIP device pointer."""

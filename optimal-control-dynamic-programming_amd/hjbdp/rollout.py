@@ -107,7 +107,8 @@ def next_stage_states(sa, X1, U, h, mode="RK4"):
 
 def linear_control_response(sa, X0=None, T_final=None, dt=None):
     """Solver_attitude.m:508-591: the PD reference controller U = -K qe(1:3) - C w (K = 0.2 I, C = I) rolled out with
-    RK4 steps.  Returns (X [7, N+1], U [3, N], angles [3, N] = yaw, pitch, roll)."""
+    RK4 steps.  Returns (X [7, N+1], U [3, N], angles [3, N] = yaw, pitch, roll).  Many starts at once on the GPU:
+    Solver_attitude.linear_control_responses (K21), whose X and U equal this loop's."""
     X0 = DEFAULT_X0_ATTITUDE if X0 is None else np.asarray(X0, dtype=np.float64)
     T_final = sa.T_final if T_final is None else T_final
     dt = sa.h if dt is None else dt

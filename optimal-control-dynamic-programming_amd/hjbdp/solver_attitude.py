@@ -11,7 +11,7 @@ minimiser (i1,i2,i3) in cascade order; the reference's index composition at
 :290-292 is a linear-indexing bug and J is unaffected by it.
 Forward simulations (:508-591, :670-696, :744-925) run host-side in hjbdp/rollout.py; get_optimal_paths runs the
 closed loop of get_optimal_path (:744-833) for many initial attitudes at once on the GPU, get_optimal_paths_simplified that of
-get_optimal_path_simplified_testode45 (:835-925).
+get_optimal_path_simplified_testode45 (:835-925), linear_control_responses that of linear_control_response (:508-591).
 """
 from __future__ import annotations
 
@@ -284,16 +284,61 @@ class Solver_attitude:
         from . import rollout
         return rollout.linear_control_response(self, X0, T_final, dt)         # :508-591
 
+    def run_cost_weights(self):
+        """(q [7], r [3]): the stage cost of run()'s sweep (:316-321) as the attitude rollout sums it - Q1..Q3 on w^2, Q4..Q6 on
+        q1..q3^2, nothing on q4, R1..R3 on the torques."""
+        return (np.array([self.Q1, self.Q2, self.Q3, self.Q4, self.Q5, self.Q6, 0.0], dtype=np.float64),
+                np.array([self.R1, self.R2, self.R3], dtype=np.float64))
+
+    def linear_control_responses(self, X0s=None, T_final=None, dt=None, K=None, C=None, qc=None, u_limit=None, integrator="RK4",
+                                 cost=None, keep_path=True, device=None):
+        """linear_control_response (:508-591) for many initial attitudes at once on the GPU (hjbdp.attitude_linear_response, K21):
+        the PD law U = -K qe(1:3) - C w, qe = qc q, on next_stage_states(., integrator).  It needs neither run() nor
+        simplified_run().  X0s [7, n] (None: the reference's X0, :160-164); the defaults are the reference's: K = 0.2 I, C = I,
+        qc = I (:523-528), N = round(T_final / dt) steps of dt = h, no torque limit.  u_limit [3] (or a scalar): the torques are
+        clipped to +-u_limit, as the DP controllers' are to +-max(U_vector).  cost: None (zero weights), 'run' (run_cost_weights():
+        give attitude_rollout the same q and r and Rollout.run_attitude sums the same) or 'simplified' ((Q1..3, Qt1..3, R1..3) on
+        (w_i, 2 asin q_i, u_i), what get_optimal_paths_simplified sums).
+        Returns, with keep_path, (X [7, N+1, n], U [3, N, n], angles [3, N, n] = yaw, pitch, roll in radians): per trajectory the
+        layout of linear_control_response; without it (X_final [7, n], cost [n])."""
+        from .core import attitude_linear_response
+        from .rollout import DEFAULT_X0_ATTITUDE
+        X0s = DEFAULT_X0_ATTITUDE.reshape(7, 1) if X0s is None else np.asarray(X0s, dtype=np.float64).reshape(7, -1)
+        T_final = self.T_final if T_final is None else T_final
+        dt = self.h if dt is None else dt
+        N = int(round(T_final / dt))
+        K = 0.2 * np.eye(3) if K is None else K
+        C = np.eye(3) if C is None else C
+        if u_limit is not None:
+            u_limit = np.broadcast_to(np.asarray(u_limit, dtype=np.float64), (3,))
+        if cost is None:
+            form, weights = "quat", None
+        elif cost == "run":
+            form, weights = "quat", np.concatenate(self.run_cost_weights())
+        elif cost == "simplified":
+            form, weights = "angle", np.array([self.Q1, self.Q2, self.Q3, self.Qt1, self.Qt2, self.Qt3, self.R1, self.R2, self.R3, 0.0])
+        else:
+            raise ValueError("cost must be None, 'run' or 'simplified'")
+        out = attitude_linear_response([self.J1, self.J2, self.J3], dt, K, C, X0s, N, qc=qc, u_limit=u_limit, integrator=integrator,
+                                       cost_form=form, weights=weights, keep_path=keep_path,
+                                       device=self.device if device is None else int(device))
+        self.linear_device_ms = out["device_ms"]
+        if not keep_path:
+            return out["X_final"], out["cost"]
+        tr = lambda a: np.ascontiguousarray(a.transpose(1, 2, 0))
+        return tr(out["X_path"]), tr(out["U_path"]), tr(out["A_path"])
+
     def get_optimal_path(self, X0=None, method="nearest", n_steps=None):
         from . import rollout
         return rollout.attitude_optimal_path(self, X0, method, n_steps)       # :744-833 (after run)
 
-    def attitude_rollout(self, integrator="taylor"):
+    def attitude_rollout(self, integrator="taylor", q=None, r=None):
         """The policy run() leaves, resident on the GPU with the attitude model set (hjbdp.Rollout, K17): the grid vectors
         (w1, w2, w3, yaw, pitch, roll) in double (:759-764), one stationary plane of labels (i1-1) + nu (i2-1) + nu^2 (i3-1) + 1
         built from U_idx (uint8 for the reference's 27), u_table [nu^3, 3] = the torque triples of U_vector rounded to float32 as
         U1_Opt..U3_Opt hold them (:296-298), inertia (J1, J2, J3) and step h.  What get_optimal_paths runs; close it (or use it
-        as a context manager) when done."""
+        as a context manager) when done.  q [7], r [3]: the stage-cost weights run_attitude sums (None: zeros; run_cost_weights()
+        gives the sweep's)."""
         from .core import Rollout
         if self.U_idx is None or self.U1_Opt is None or np.ndim(self.U1_Opt) != 6:
             raise RuntimeError("run() first")
@@ -306,7 +351,7 @@ class Solver_attitude:
         u_table = np.stack([uv[c % nu], uv[(c // nu) % nu], uv[c // (nu * nu)]], axis=1)
         ro = Rollout(self.grid_vectors_full(), labels, u_table, index_base=1, device=self.device)
         try:
-            ro.set_attitude_model([self.J1, self.J2, self.J3], self.h, integrator)
+            ro.set_attitude_model([self.J1, self.J2, self.J3], self.h, integrator, q=q, r=r)
         except Exception:
             ro.close()
             raise

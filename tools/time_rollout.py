@@ -13,8 +13,10 @@ Two cases, one JSON line:
       it also writes its line to profiles/rollout_position_time.json.
   (f) attitude_simplified_loop: the simplified attitude policies on the rigid body (K20, hjb_rollout_run_attitude_simplified), see
       case_attitude_simplified_loop; alone, it also writes its line to profiles/rollout_attitude_simplified_time.json.
+  (g) attitude_linear_loop: the linear attitude controller (K21, hjb_attitude_linear_response) beside K17's 'nearest' RK4 loop, see
+      case_attitude_linear_loop; alone, it also writes its line to profiles/rollout_attitude_linear_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop] [--out FILE]
 """
 from __future__ import annotations
 
@@ -302,6 +304,64 @@ def case_attitude_simplified_loop(host=True, n_traj=100000, n_stages=None):
     return res
 
 
+def case_attitude_linear_loop(host=True, n_traj=262144, n_steps=5999):
+    """(g) attitude_linear_loop: the reference's PD law (K = 0.2 I, C = I, qc = I, no limit) on the RK4 step from 2^18 initial
+    attitudes (the starts of case_attitude) over 5,999 steps, paths off, no cost weights; beside it, in the same run and from the
+    same starts, K17's 'nearest' loop on the same RK4 step with the reference-size 6-D policy of Solver_attitude.run(n_stages=19).
+    Both report device_ms (the launches' event times) of five calls after a warm-up of the same shape, all five listed, the median
+    quoted; the linear loop also its host wall clock around the whole call (upload, kernel, download of X_final and cost).  Host
+    rate: hjbdp.rollout.linear_control_response (the scalar mirror) over 2,000 steps from the reference's start."""
+    import hjbdp
+    from hjbdp import rollout
+    sa = hjbdp.Solver_attitude(11, 10)
+    t0 = time.perf_counter()
+    sa.run(n_stages=19)
+    sweep_s = time.perf_counter() - t0
+    rng = np.random.default_rng(3)
+    X0 = np.empty((7, n_traj))
+    X0[0:3] = rng.uniform(-0.5, 0.5, size=(3, n_traj))
+    ax = rng.normal(size=(3, n_traj))
+    ax /= np.sqrt((ax ** 2).sum(axis=0))
+    th = rng.uniform(0, 0.6, size=n_traj)
+    X0[3:6] = ax * np.sin(th / 2)
+    X0[6] = np.cos(th / 2)
+    J = [sa.J1, sa.J2, sa.J3]
+    Kg, Cg = 0.2 * np.eye(3), np.eye(3)
+    res = {"n_traj": int(n_traj), "n_steps": int(n_steps), "integrator": "RK4", "gains": "K = 0.2 I, C = I, qc = I, no limit",
+           "timing": "device_ms: event times around the launches; wall_ms: host clock around hjb_attitude_linear_response (upload + "
+                     "kernel + download of X_final and cost); 5 calls after a warm-up"}
+
+    def quote(ms):
+        med = float(np.median(ms))
+        return {"device_ms": [round(m, 3) for m in ms], "device_ms_median": round(med, 3), "traj_steps_per_s": n_traj * n_steps / (med * 1e-3)}
+
+    out = hjbdp.attitude_linear_response(J, sa.h, Kg, Cg, X0, n_steps)          # warm-up, same shape
+    ms, wall = [], []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        out = hjbdp.attitude_linear_response(J, sa.h, Kg, Cg, X0, n_steps)
+        wall.append(time.perf_counter() - t0)
+        ms.append(out["device_ms"])
+    res["linear"] = quote(ms)
+    res["linear"].update(wall_ms=[round(t * 1e3, 3) for t in wall], wall_ms_median=round(float(np.median(wall)) * 1e3, 3),
+                         finite_final=int(np.isfinite(out["X_final"]).all(axis=0).sum()))
+    planes = np.zeros(n_steps, np.int32)
+    with sa.attitude_rollout("RK4") as ro:
+        ro.run_attitude(X0, planes, "nearest")                    # warm-up, same shape
+        ms = [ro.run_attitude(X0, planes, "nearest")["device_ms"] for _ in range(5)]
+        res["k17_nearest_rk4"] = quote(ms)
+        res["k17_nearest_rk4"].update(grid="11x11x11x10x10x10", labels=str(ro.labels_dtype), n_labels=int(ro.n_labels),
+                                      sweep_wall_s=round(sweep_s, 3))
+    res["linear_over_k17_device_time"] = res["linear"]["device_ms_median"] / res["k17_nearest_rk4"]["device_ms_median"]
+    if host:
+        t0 = time.perf_counter()
+        rollout.linear_control_response(sa, T_final=2000 * sa.h)
+        res["host_loop"] = "hjbdp.rollout.linear_control_response (scalar Python mirror), default X0, 2,000 steps"
+        res["host_traj_steps_per_s"] = 2000 / (time.perf_counter() - t0)
+        res["speedup_vs_host"] = res["linear"]["traj_steps_per_s"] / res["host_traj_steps_per_s"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -314,12 +374,15 @@ def main():
     res = {"tool": "time_rollout"}
     for c in a.cases.split(","):
         res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude, "pos_att_loop": case_pos_att_loop,
-                  "position_loop": case_position_loop, "attitude_simplified_loop": case_attitude_simplified_loop}[c](host=not a.no_host)
+                  "position_loop": case_position_loop, "attitude_simplified_loop": case_attitude_simplified_loop,
+                  "attitude_linear_loop": case_attitude_linear_loop}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.cases == "position_loop" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
     if a.cases == "attitude_simplified_loop" and not a.out:       # its own record: one line
         (ROOT / "profiles" / "rollout_attitude_simplified_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "attitude_linear_loop" and not a.out:           # its own record: one line
+        (ROOT / "profiles" / "rollout_attitude_linear_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
