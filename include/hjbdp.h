@@ -342,6 +342,36 @@ int32_t hjb_policy_lookup(int32_t device, int32_t dtype, int32_t D, const int32_
  * plane each (g [B], x_next [B, D], j_interp [B]).  J_next may be NULL when j_interp is NULL. */
 int32_t hjb_probe_stage(hjb_handle h, const void *J_next, const hjb_probe *probe);
 
+/* ---- the cost of a GIVEN policy on the grid (the fixed-label stage and its sweep) ---------------------------------------------
+ *   J_k(x) = g(x, u_k(x)) + F_{k+1}(x_next(x, u_k(x)))          (no min: u_k is given)
+ * `labels` are argmin labels as hjb_backup_stage / hjb_solve write them: one per OWNED state, of the handle's idx_dtype
+ * (hjb_info.idx_bytes wide), in [index_base, index_base + n_controls), column-major over the control dims (control dim 0 fastest).
+ * For every state the value is bit-identical to the candidate the backup kernels compare for that control, under every typing
+ * (HJB_F32 / _F64 / _F16S, HJB_TAB_F64, HJB_COST_F64), so hjb_evaluate_stage on hjb_backup_stage's own labels returns its J.
+ * Uses: the cost of the stationary controller the reference flies (the last stage's labels kept by simplified_run), a policy
+ * judged under another handle's cost terms.  A handle with a state model (HJB_MODEL_QUAT_EULER321) is HJB_E_UNSUPPORTED.
+ * hjb_evaluate_stage: host buffers, J_next and J_out [j_elems] in the (haloed) J layout (the owned planes are written; halo planes
+ * of J_out repeat J_next), labels [n_states].  hjb_evaluate_stage_device: the same on device buffers, asynchronous on `stream`
+ * (the stream rules of hjb_backup_stage_device); dJ_out's halo planes are not touched.  A handle's first evaluation builds the
+ * (cell, weight) tables it reads if no stage kernel has yet (synchronous, on the null stream): call it once before a stream capture.
+ * hjb_evaluate: the sweep of a fixed policy on a whole-grid handle (the handles hjb_solve accepts): n_stages >= 1 evaluations
+ * from `terminal` (NULL = zeros).  labels_per_stage 0: labels [nS], one stationary policy used at every stage; 1: labels
+ * [nS * n_stages], the stage with reference index k_s reads plane k_s - 1 (what hjb_solve's idx_stages holds).  J_final [nS] and
+ * J_stages [nS * n_stages] (plane k_s - 1) may be NULL; sweep_ms (may be NULL) = device time of the loop.
+ * HJB_E_INVALID, decided before any device work: a null handle, J_next, labels or J_out; n_stages < 1; labels_per_stage not 0 or
+ * 1; and, for the two host-buffer calls, ANY label out of range anywhere in the array (the outputs are then left untouched).
+ * The device-buffer call cannot look first: for a label out of range the kernel reads nothing, stores NaN for that state (every
+ * other state gets its value) and raises a flag of its own, which the next hjb_check_device_status reports as HJB_E_INVALID
+ * (once: reporting clears it; a left slab, HJB_E_HALO, is reported first when both are raised).
+ * Options (hjb_set_option): "eval_grid" workgroups per launch (0 = one per 256 states; the kernel strides), "eval_tables" the
+ * source of cells and weights: -1 the handle's (cell, weight) tables where they fit, 0 the terms summed in the kernel, 1 tables;
+ * "eval_i32" 0 runs the kernel's 64-bit form even where every index fits 31 bits, "eval_m24" 0 its 32-bit form without 24-bit
+ * index products even where every factor fits 24 bits (same bits either way; timing experiments, tests). */
+int32_t hjb_evaluate_stage(hjb_handle h, const void *J_next, const void *labels, void *J_out);
+int32_t hjb_evaluate_stage_device(hjb_handle h, const void *dJ_next, const void *d_labels, void *dJ_out, void *stream);
+int32_t hjb_evaluate(hjb_handle h, int32_t n_stages, const void *terminal, const void *labels, int32_t labels_per_stage,
+                     void *J_final, void *J_stages, double *sweep_ms);
+
 /* ---- batched closed-loop rollouts of a stored policy (test/Dynamic_Solver.m:108-181 get_optimal_path, 'Nssu' and 'ssu') ----
  * A rollout object holds a per-stage policy on one device: the grid (D <= 6 axes, knots concatenated axis 0 first), the
  * labels of n_planes stages ([nS, n_planes] column-major in HJB_IDX_I32 / _U8 / _U16: hjb_solve's idx_stages layout) and the

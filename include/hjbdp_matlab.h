@@ -41,6 +41,12 @@ int32_t hjb_backup_stage(void *handle, const void *J_next, void *J_out, void *id
  * (hjbdp_solve.m 'on_stage'); stream NULL = the default stream.  hjb_check_device_status synchronises and reports a left slab. */
 int32_t hjb_backup_stage_device(void *handle, const void *dJ_next, void *dJ_out, void *d_idx_out, void *stream);
 int32_t hjb_check_device_status(void *handle, void *stream);
+/* the cost of a GIVEN policy (labels as hjb_backup_stage / hjb_solve_flat write them): one stage on host buffers, one stage on
+ * device buffers, and the sweep (labels_per_stage 0: one stationary policy, 1: one plane per stage); usage: matlab/hjbdp_evaluate.m */
+int32_t hjb_evaluate_stage(void *handle, const void *J_next, const void *labels, void *J_out);
+int32_t hjb_evaluate_stage_device(void *handle, const void *dJ_next, const void *d_labels, void *dJ_out, void *stream);
+int32_t hjb_evaluate(void *handle, int32_t n_stages, const void *terminal, const void *labels, int32_t labels_per_stage,
+                     void *J_final, void *J_stages, double *sweep_ms);
 int32_t hjb_get_info_flat(void *handle, int64_t *out8);
 int32_t hjb_set_option(void *handle, const char *key, int64_t value);
 int32_t hjb_get_option(void *handle, const char *key, int64_t *value);

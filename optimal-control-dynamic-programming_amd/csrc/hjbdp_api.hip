@@ -429,6 +429,26 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
         HIP_TRY(h, hipMemcpy(h->dn, &h->hn, sizeof(DNested), hipMemcpyHostToDevice));
         return HJB_OK;
     }
+    if (!strcmp(key, "eval_grid")) {        // workgroups per launch of the fixed-label stage (0: one per 256 states); "grid" is the stage kernels'
+        if (value < 0 || value > (1 << 22)) return fail(h, HJB_E_INVALID, "%s out of range", key);
+        h->eval_grid = (int)value;
+        return HJB_OK;
+    }
+    if (!strcmp(key, "eval_i32")) {         // 0: the fixed-label stage in its 64-bit form whatever the sizes (A/B timing, tests)
+        h->eval_i32 = value != 0;
+        return HJB_OK;
+    }
+    if (!strcmp(key, "eval_m24")) {         // 0: the fixed-label stage's 32-bit form without the 24-bit index products (A/B timing, tests)
+        h->eval_m24 = value != 0;
+        return HJB_OK;
+    }
+    if (!strcmp(key, "eval_tables")) {      // the fixed-label stage's cells and weights: -1 automatic, 0 terms summed on the fly, 1 the (cell, t) tables
+        if (value < -1 || value > 1) return fail(h, HJB_E_INVALID, "eval_tables must be -1, 0 or 1");
+        if (value == 0 && h->tab64) return fail(h, HJB_E_UNSUPPORTED, "eval_tables 0: table_dtype HJB_TAB_F64 is evaluated from the tables only");
+        if (value == 1 && !h->tabled_ok) return fail(h, HJB_E_UNSUPPORTED, "eval_tables 1: this grid's per-axis (cell, weight) tables do not fit");
+        h->eval_tables = (int)value;
+        return HJB_OK;
+    }
     if (!strcmp(key, "monitor_single")) {   // hjb_solve_opts.monitor_single for callers of the flat API (hjb_solve_flat)
         h->monitor_single = value != 0;
         return HJB_OK;
@@ -451,6 +471,10 @@ int32_t hjb_get_option(hjb_handle hh, const char *key, int64_t *value) {
     else if (!strcmp(key, "uw_claim")) *value = h->uniwin_ok ? h->uw_claim : 0;
     else if (!strcmp(key, "uniwin_slow_points")) *value = h->uniwin_ok ? h->uniwin_slow : -1;
     else if (!strcmp(key, "grid")) *value = h->L.grid;
+    else if (!strcmp(key, "eval_grid")) *value = h->eval_grid;
+    else if (!strcmp(key, "eval_m24")) *value = h->eval_m24 ? 1 : 0;
+    else if (!strcmp(key, "eval_i32")) *value = eval_runs_i32(h) ? 1 : 0;     // the form that would run
+    else if (!strcmp(key, "eval_tables")) *value = h->eval_tables < 0 ? (h->tabled_ok ? 1 : 0) : h->eval_tables;      // the source in effect
     else if (!strcmp(key, "idx_bytes")) *value = h->idx_bytes;
     else if (!strcmp(key, "temporal")) *value = h->use_temporal;
     else if (!strcmp(key, "chunk_order")) *value = h->dn ? h->hn.chunk_order : 0;

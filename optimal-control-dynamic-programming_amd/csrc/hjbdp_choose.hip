@@ -2,6 +2,7 @@
 // (variant_status, choose_launch -> Handle::L), and the stage launch that dispatches on it.
 #include "hjbdp_host.h"
 #include "hjbdp_walk.h"
+#include "kernels_evaluate.h"      // EvalDiv
 
 namespace hjbhost {
 
@@ -214,6 +215,50 @@ int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t 
             return fail(h, HJB_E_DEVICE, "internal: kernel variant %d was not dispatched", L.variant);
     }
     if (miss) return fail(h, HJB_E_UNSUPPORTED, "variant %d has no kernel for D=%d, dtype %d", L.variant, a.D, h->dtype);
+    HIP_TRY(h, hipGetLastError());
+    return HJB_OK;
+}
+
+// The fixed-label stage (kernels_evaluate.h) - the one place its launch is decided.  Source of cells and weights: the handle's
+// stage-invariant (cell, t) tables where it can hold them (a HJB_TAB_F64 handle always does: its float32 terms are copies for the
+// host's analysis), else the terms summed on the fly; option "eval_tables" forces either where both exist (same bits).
+int prepare_evaluate(Handle *h, bool *tabled) {
+    if (h->hp.model)
+        return fail(h, HJB_E_UNSUPPORTED, "the fixed-label stage does not evaluate a state model (HJB_MODEL_QUAT_EULER321): its next states are formed in variant 4 only");
+    *tabled = h->eval_tables < 0 ? h->tabled_ok : h->eval_tables == 1;
+    if (!*tabled && h->tab64) return fail(h, HJB_E_UNSUPPORTED, "table_dtype HJB_TAB_F64 is evaluated from the (cell, weight) tables only");
+    return *tabled ? ensure_tabled(h) : HJB_OK;
+}
+
+int launch_evaluate(Handle *h, const void *dJn, const void *dlabels, void *dJo, hipStream_t st) {
+    bool tabled = false;
+    const int pst = prepare_evaluate(h, &tabled);
+    if (pst) return pst;
+    StageArgs a = stage_args(h, dJn, dJo, nullptr, st);
+    a.grid = (unsigned)eval_grid_of(h);
+    a.block = 256;
+    a.idx32 = eval_runs_i32(h);
+    EvalDiv dv{};                                          // the divisors the kernel takes a state index and a label apart by
+    for (int d = 0; d < HJB_MAX_D; ++d) dv.n[d] = hjb::magic_div(d < h->hp.D ? (uint32_t)h->hp.n[d] : 1u);
+    for (int c = 0; c < 2; ++c) dv.m[c] = hjb::magic_div((uint32_t)h->hp.m[c]);
+    // 24-bit index products: every factor the 32-bit form multiplies below 2^24 - sizes, the quotients of the state index (the
+    // first is the largest), the J strides, the strides of the tables or terms it reads and of the cost terms.  Strides are never
+    // negative: make_term and axis_domain form them as products of sizes (0 = broadcast), so an upper bound is a bound
+    bool mul24 = a.idx32 && h->eval_m24;
+    {
+        constexpr int64_t k24 = (int64_t)1 << 24;
+        const DParams &P = h->hp;
+        auto small = [&](const DTerm &t) { for (int d = 0; d < HJB_MAX_G; ++d) if (t.stride[d] >= k24) return false; return true; };
+        mul24 = mul24 && h->n_owned / P.n[0] < k24 && h->nU < k24;
+        for (int d = 0; d < P.D && mul24; ++d) {
+            mul24 = h->prob.n[d] < k24 && P.jstride[d] < k24 && h->nplanes < k24;      // (prob.n: the GLOBAL sizes the terms are indexed by)
+            for (int k = 0; k < HJB_MAX_D && mul24 && tabled; ++k) mul24 = h->htb.ax[d].sstride[k] < k24;
+            for (int k = 0; k < HJB_MAX_C && mul24 && tabled; ++k) mul24 = h->htb.ax[d].cstride[k] < k24;
+            for (int k = 0; k < P.axis[d].n_terms && mul24 && !tabled; ++k) mul24 = small(P.axis[d].t[k]);
+        }
+        for (int k = 0; k < P.n_cost && mul24; ++k) mul24 = small(P.cost[k]);      // (cost64[] has the same strides)
+    }
+    if (stage_evaluate(a, tabled, mul24, dlabels, h->d_status + 1, dv)) return fail(h, HJB_E_UNSUPPORTED, "the fixed-label stage has no kernel for D=%d, dtype %d", a.D, h->dtype);
     HIP_TRY(h, hipGetLastError());
     return HJB_OK;
 }

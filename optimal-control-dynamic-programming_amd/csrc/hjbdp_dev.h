@@ -76,5 +76,12 @@ __device__ __forceinline__ void st_idx(void *__restrict__ base, int64_t i, int32
     else if (bytes == 1) ((uint8_t *)base)[i] = (uint8_t)v;
     else ((uint16_t *)base)[i] = (uint16_t)v;
 }
+// ... and read back as an integer (the fixed-label stage, kernels_evaluate.h): the narrow widths are unsigned.  (kernels_reduce.h's
+// ld_idx reads the same bytes as a double for the monitor's sums.)
+__device__ __forceinline__ int32_t ld_label(const void *__restrict__ base, int64_t i, int32_t bytes) {
+    if (bytes == 4) return ((const int32_t *)base)[i];
+    if (bytes == 1) return (int32_t)((const uint8_t *)base)[i];
+    return (int32_t)((const uint16_t *)base)[i];
+}
 
 }  // namespace hjb

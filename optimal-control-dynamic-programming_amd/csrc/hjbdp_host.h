@@ -6,6 +6,7 @@
 //   hjbdp_colsweep.hip variant 7's host side: plan, XCD map, DPP test, cooperative plan, launch record, split rule
 //   hjbdp_choose.hip   which variant serves, in which form and geometry (Handle::L), and the stage launch
 //   hjbdp_api.hip      hjb_create .. hjb_solve, options, probe, policy lookup (the single-device C ABI)
+//   hjbdp_evaluate.hip hjb_evaluate_stage, hjb_evaluate_stage_device, hjb_evaluate (the cost of a given policy on the grid)
 //   hjbdp_batch.hip    hjb_solve_batch (several sweeps of one kernel shape, one launch per stage)
 //   hjbdp_builder.hip  the flat builder API (MATLAB loadlibrary / calllib)
 //   hjbdp_multi.hip    hjb_create_multi / hjb_solve_multi (one process, several GPUs)
@@ -95,7 +96,7 @@ struct Handle {
     std::vector<void *> allocs;   // every device allocation (freed in destroy): large ones and the chunks the small ones are carved from
     char *arena = nullptr;        // dev_alloc: the current chunk's free part
     size_t arena_left = 0;
-    int32_t *d_status = nullptr;
+    int32_t *d_status = nullptr;  // two device words: [0] a query left the slab (DParams::status), [1] the evaluation kernel met a label out of range
     // work buffers (lazy)
     void *dJ[2] = {nullptr, nullptr};
     char *d_idx = nullptr;        // argmin labels of the owned states, idx_bytes each
@@ -173,6 +174,11 @@ struct Handle {
     int cs_coop_epl = 0;          // ... it applies: elements per staging load (0 = does not apply)
     bool cs_dpp_ok = false;       // the axis-0 cells permit the DPP form (colsweep_dpp_ok)
     int forced_variant = -1;      // option "variant"
+    // the fixed-label stage (kernels_evaluate.h, hjb_evaluate*)
+    int eval_tables = -1;         // option "eval_tables": -1 the (cell, t) tables where the handle can hold them, 0 terms summed on the fly, 1 tables
+    bool eval_i32 = true;         // option "eval_i32": 0 = the 64-bit form of the evaluation kernel whatever the sizes (A/B timing, tests)
+    bool eval_m24 = true;         // option "eval_m24": 0 = the 32-bit form with 32-bit index products whatever the sizes (A/B timing, tests)
+    int eval_grid = 0;            // option "eval_grid": workgroups per launch of the grid-stride evaluation kernel (0 = one per 256 states)
     Launch L;
     int halo_need_lo = 0, halo_need_hi = 0;
     std::string err;
@@ -269,6 +275,23 @@ int variant_status(Handle *h, int v, const char **why);   // what variant v need
 void choose_launch(Handle *h);       // the variant, its form and geometry -> Handle::L
 void launch_changed(Handle *h);      // after a change to Handle::L: what depends on the grid; the captured graph is dropped
 int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t st);
+// The fixed-label stage.  prepare_evaluate: whether the handle is served and from which source of cells and weights; a handle's FIRST
+// evaluation builds the (cell, t) tables it reads if no stage kernel has yet - allocation and a wait on the null stream, so that
+// first call must not sit inside a stream capture (include/hjbdp.h says so); later calls find them built and do no such work.
+// launch_evaluate: one stage (dJn, dlabels -> dJo) on st; it calls prepare_evaluate itself.
+// eval_grid_of / eval_runs_i32: the launch size and whether the kernel's 32-bit index form runs - the one statement of each.
+int prepare_evaluate(Handle *h, bool *tabled);
+int launch_evaluate(Handle *h, const void *dJn, const void *dlabels, void *dJo, hipStream_t st);
+// one workgroup per 256 states; beyond 2^22 workgroups (2^30 states) equally long grid-stride spans; option "eval_grid" overrides
+inline int64_t eval_grid_of(const Handle *h) {
+    return h->eval_grid > 0 ? h->eval_grid : std::max<int64_t>(1, hjb::launch_spans((h->n_owned + 255) / 256, (int64_t)1 << 22));
+}
+// the 32-bit form: owned states and the haloed J below 2^31 - 2^26 (kTab32Lim) and a grid-stride step of at most 2^31, so that the
+// step on top of the last index stays below 2^32; every axis table is below 2^31 entries (part of tabled_ok), every term and cost
+// table below 2^31 elements (hjb_create)
+inline bool eval_runs_i32(const Handle *h) {
+    return h->eval_i32 && h->n_owned < kTab32Lim && h->j_elems < kTab32Lim && eval_grid_of(h) * 256 <= ((int64_t)1 << 31);
+}
 // the handle's part of a stage launch: stream, typing, parameter records, buffers (grid, block, LDS and the form are the caller's)
 inline StageArgs stage_args(const Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t st) {
     StageArgs a;

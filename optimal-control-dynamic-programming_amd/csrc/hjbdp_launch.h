@@ -13,6 +13,7 @@ struct DTabled;
 struct DColSweep;
 struct DUniwin;
 struct DCsBatch;
+struct EvalDiv;
 
 struct StageArgs {
     unsigned grid = 1, block = 256;
@@ -47,6 +48,8 @@ int stage_colsweep(const StageArgs &a, int gax, int ng, int costform, bool dpp);
 int stage_colcoop(const StageArgs &a, int gax, int ng, bool fastcost);           // variant 7, cooperative form
 int stage_colsweep_batch(const StageArgs &a, int n, const DCsBatch *dB, uint32_t mask, int parity, int gax, int ng, bool c64);   // variant 7, n problems in one launch
 int stage_tile2d(const StageArgs &a, const void *plan, int K);                   // K9 (several stages per launch)
+// the fixed-label stage (kernels_evaluate.h): labels -> a.Jo; tabled: cells and weights from a.dtb, else the terms summed on the fly
+int stage_evaluate(const StageArgs &a, bool tabled, bool mul24, const void *labels, int32_t *bad_label, const EvalDiv &dv);
 int stage_tile2d_plan(int dtype, const DParams *dp, const DTabled *dtb, void *plan, int64_t n_entries);
 
 }  // namespace hjb

@@ -232,12 +232,12 @@ static int upload_model(Handle *h, const hjb_problem *p) {
     return HJB_OK;
 }
 
-// the status word and hp -> d_status, dp; table_dtype F64: the axes once more, in float64 -> dp64
+// the status words and hp -> d_status, dp; table_dtype F64: the axes once more, in float64 -> dp64
 static int upload_params(Handle *h, const hjb_problem *p) {
     DParams &P = h->hp;
-    int st = dev_alloc(h, sizeof(int32_t), &h->d_status);
+    int st = dev_alloc(h, 2 * sizeof(int32_t), &h->d_status);
     if (st) return st;
-    HIP_TRY(h, hipMemset(h->d_status, 0, sizeof(int32_t)));
+    HIP_TRY(h, hipMemset(h->d_status, 0, 2 * sizeof(int32_t)));
     P.status = h->d_status;
     st = dev_alloc(h, sizeof(DParams), &h->dp);
     if (st) return st;
@@ -317,14 +317,21 @@ int ensure_work(Handle *h) {
     return st;
 }
 
+// The two status words, read in one copy.  A left slab is reported first (and alone cleared: a bad label met by the evaluation kernel
+// is then reported by the next call); each flag is cleared when it is reported.
 int check_status(Handle *h, hipStream_t st) {
-    int32_t flag = 0;
-    HIP_TRY(h, hipMemcpyAsync(&flag, h->d_status, sizeof flag, hipMemcpyDeviceToHost, st));
+    int32_t flag[2] = {0, 0};
+    HIP_TRY(h, hipMemcpyAsync(flag, h->d_status, sizeof flag, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
-    if (flag) {
+    if (flag[0]) {
         HIP_TRY(h, hipMemsetAsync(h->d_status, 0, sizeof(int32_t), st));
         return fail(h, HJB_E_HALO, "a next-state query left the slab's halo (halo_lo=%d halo_hi=%d; tables imply lo=%d hi=%d)",
                     h->hp.halo_lo, h->nplanes - h->hp.n[h->hp.D - 1] - h->hp.halo_lo, h->halo_need_lo, h->halo_need_hi);
+    }
+    if (flag[1]) {
+        HIP_TRY(h, hipMemsetAsync(h->d_status + 1, 0, sizeof(int32_t), st));
+        return fail(h, HJB_E_INVALID, "hjb_evaluate_stage_device met a label outside [%d, %lld): NaN was stored for those states",
+                    h->hp.index_base, (long long)(h->hp.index_base + h->nU));
     }
     return HJB_OK;
 }

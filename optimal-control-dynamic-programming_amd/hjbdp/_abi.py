@@ -162,6 +162,10 @@ SYMBOLS = {
     "hjb_rank_fill_separable": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     "hjb_device_gather": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_void_p]),
     "hjb_probe_stage": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(hjb_probe)]),
+    # the cost of a given policy: the fixed-label stage and its sweep
+    "hjb_evaluate_stage": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hjb_evaluate_stage_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hjb_evaluate": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     # flat builder API (primitives and plain arrays only: what MATLAB's calllib can marshal)
     "hjb_problem_new": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                     C.POINTER(C.c_void_p)]),

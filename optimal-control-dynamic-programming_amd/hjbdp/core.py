@@ -587,6 +587,62 @@ class Backup:
                 "stopped_early": bool(res.stopped_early), "sweep_ms": res.sweep_ms, "last_e": res.last_e,
                 "last_e2": res.last_e2, "probe": pout}
 
+    # -- the cost of a GIVEN policy -------------------------------------------
+    def _labels(self, labels, shapes):
+        """labels as a flat column-major array after the checks evaluate* share: dtype spec.idx_np_dtype, one of `shapes`."""
+        lab = np.asarray(labels)
+        if lab.dtype != np.dtype(self.spec.idx_np_dtype):
+            raise ValueError("labels must be %s (spec.idx_np_dtype), got %s" % (np.dtype(self.spec.idx_np_dtype), lab.dtype))
+        if lab.shape not in shapes:
+            raise ValueError("labels of shape %r: expected %s" % (lab.shape, " or ".join(repr(s) for s in shapes)))
+        return np.ascontiguousarray(lab.reshape(-1, order="F"))
+
+    def evaluate_stage(self, J_next, labels):
+        """J_k = g(x, u(x)) + F(x_next(x, u(x))) for the given labels (hjb_evaluate_stage): no min.  J_next / J_k in the (haloed)
+        column-major J layout; labels [n_states] of spec.idx_np_dtype as backup_stage returns them.  On backup_stage's own
+        labels the result is backup_stage's J, bit for bit."""
+        inf = self.info()
+        lab = self._labels(labels, [(int(inf["n_states"]),)])
+        dt = self.spec.j_dtype
+        Jn = np.ascontiguousarray(np.asarray(J_next, dtype=dt).reshape(-1, order="F"))
+        if Jn.size != inf["j_elems"]:
+            raise ValueError("J_next has %d elements, the handle's J layout has %d" % (Jn.size, inf["j_elems"]))
+        Jo = np.empty_like(Jn)
+        _check(self.lib, self._h, self.lib.hjb_evaluate_stage(self._h, Jn.ctypes.data, lab.ctypes.data, Jo.ctypes.data))
+        return Jo
+
+    def evaluate_stage_device(self, dJ_next, d_labels, dJ_out, stream=0):
+        """hjb_evaluate_stage_device: the same on device buffers (torch tensors, DeviceBuffers or raw pointers), asynchronous.
+        A label out of range stores NaN for its state and makes the next check_device_status raise (HJB_E_INVALID)."""
+        def ptr(x):
+            if x is None:
+                return None
+            return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+        st = self.lib.hjb_evaluate_stage_device(self._h, ptr(dJ_next), ptr(d_labels), ptr(dJ_out), int(stream) or None)
+        _check(self.lib, self._h, st)
+
+    def evaluate(self, n_stages, labels, terminal=None, keep_J=False):
+        """The sweep of a fixed policy (hjb_evaluate): n_stages evaluations from `terminal` (None: zeros).  labels [nS]: one
+        stationary policy used at every stage; labels [nS, n_stages]: the stage with reference index k_s reads column k_s - 1
+        (solve's idx_stages).  Returns {"J": the last stage's cost [nS], "J_stages": [nS, n_stages] (column k_s - 1) or None,
+        "sweep_ms"}."""
+        nS, dt = self.spec.nS, self.spec.j_dtype
+        n_stages = int(n_stages)
+        lab = self._labels(labels, [(nS,), (nS, n_stages)])
+        per_stage = 1 if np.ndim(labels) == 2 else 0
+        t = None
+        if terminal is not None:
+            t = np.ascontiguousarray(np.asarray(terminal, dtype=dt).reshape(-1, order="F"))
+            if t.size != nS:
+                raise ValueError("terminal cost must have nS elements")
+        J = np.empty(nS, dtype=dt)
+        Js = np.zeros((nS, max(n_stages, 0)), dtype=dt, order="F") if keep_J else None
+        ms = C.c_double(0.0)
+        st = self.lib.hjb_evaluate(self._h, n_stages, None if t is None else t.ctypes.data, lab.ctypes.data, per_stage,
+                                   J.ctypes.data, None if Js is None else Js.ctypes.data, C.byref(ms))
+        _check(self.lib, self._h, st)
+        return {"J": J, "J_stages": Js, "sweep_ms": ms.value}
+
     def _make_probe(self, probe, n_planes):
         D, Cc = self.spec.D, self.spec.C
         pb = _abi.hjb_probe()
@@ -932,6 +988,34 @@ def solve_batch(specs, n_stages, device=0, monitor_period=0, monitor_tol=0.0, pr
     t_end = time.perf_counter()
     solve_batch.last_phases_ms = {"create": (t_made - t0) * 1e3, "sweep": (t_run - t_made) * 1e3, "close": (t_end - t_run) * 1e3}
     return outs, (t_end - t0) * 1e3, variants, sizes
+
+
+def channel_policy_cost(solver, build, n_stages, stationary):
+    """Shared body of Solver_position.policy_cost and Solver_attitude.policy_cost_simplified: the cost over the grid of flying the
+    labels a simplified_run left on `solver`, per channel (Backup.evaluate; no min, terminal cost zero).  build(ch) -> the channel's
+    ProblemSpec ON THE GRID THE RUN USED.  stationary: U_idx[ch] at every one of n_stages stages (None: N_stage - 1); else the
+    per-stage U_idx_stages of simplified_run(keep_policy=True).  The three channels run in turn: an evaluation stage is a fraction
+    of a backup.  Leaves the device times in solver.policy_cost_ms."""
+    if stationary:
+        n_st = solver.N_stage - 1 if n_stages is None else int(n_stages)
+        labels = [np.asarray(solver.U_idx[ch]) for ch in range(3)]
+    else:
+        if solver.U_idx_stages is None:
+            raise RuntimeError("stationary=False needs simplified_run(keep_policy=True)")
+        n_st = solver.U_idx_stages[0].shape[-1]
+        if n_stages is not None and int(n_stages) != n_st:
+            raise ValueError("the run kept %d stages of labels, n_stages=%d" % (n_st, int(n_stages)))
+        labels = [np.asarray(ix) for ix in solver.U_idx_stages]
+    out = []
+    solver.policy_cost_ms = [None] * 3
+    for ch in range(3):
+        spec = build(ch)
+        lab = labels[ch].reshape((spec.nS,) if stationary else (spec.nS, n_st), order="F").astype(spec.idx_np_dtype)
+        with Backup(spec, device=solver.device) as bk:
+            res = bk.evaluate(n_st, np.asfortranarray(lab))
+        solver.policy_cost_ms[ch] = res["sweep_ms"]
+        out.append(res["J"].reshape(spec.n, order="F"))
+    return out
 
 
 def solve_many(specs, n_stages, device=0, **solve_kw):

@@ -117,6 +117,22 @@ class Dynamic_Solver:
         self.F_values = self.J_star[:, :, 0].copy()
         return self
 
+    def policy_cost(self):
+        """The cost of the stored per-stage policy (u_star_idxs) over the whole grid, from the terminal cost run() used (zeros):
+        [dx, dx, N-1] with stage k_s in plane k_s - 1, by the fixed-label sweep (Backup.evaluate) - no min is taken.  On the
+        policy run() itself left it equals J_star[:, :, :N-1] bit for bit; edit u_star_idxs (or the cost weights) first to
+        judge another policy (or this one under another cost)."""
+        if self.u_star_idxs is None:
+            raise RuntimeError("run() first")
+        spec = self.build_spec()
+        idx = np.asarray(self.u_star_idxs)
+        n_st = idx.shape[-1]
+        lab = np.ascontiguousarray(idx.reshape(-1, n_st, order="F").astype(spec.idx_np_dtype), dtype=spec.idx_np_dtype)
+        with Backup(spec, device=self.device) as bk:
+            out = bk.evaluate(n_st, np.asfortranarray(lab), keep_J=True)
+        self.policy_cost_ms = out["sweep_ms"]
+        return out["J_stages"].reshape((self.dx, self.dx, n_st), order="F")
+
     # ------------------------------------------------------------------
     def a_D(self, X1, X2, Ui):
         # Dynamic_Solver.m:191-194

@@ -19,7 +19,7 @@ import math
 
 import numpy as np
 
-from .core import Backup, solve_batch, solve_many
+from .core import Backup, channel_policy_cost, solve_batch, solve_many
 from .matlab_compat import deg2rad, linspace
 from .problem import ProblemSpec, Term
 from .solver_position import NearestPolicy
@@ -113,6 +113,17 @@ class Solver_attitude:
             self.sweep_ms[ch] = out["sweep_ms"]
             setattr(self, "U%d_Opt" % (ch + 1), NearestPolicy([s_w, s_t], self.U_vector[self.U_idx[ch] - 1]))  # :249-251
         return self
+
+    def policy_cost_simplified(self, n_stages=None, stationary=True):
+        """The cost over the grid of FLYING the policy simplified_run left, per channel: a list of three [n_w, n_t] arrays.
+        stationary=True (default): the kept last-stage labels U_idx[ch] - the one table the reference's closed loop flies for
+        the whole horizon (Solver_attitude.m:249-251) - used at every one of n_stages stages (default N_stage - 1).
+        F_values is the cost of the time-varying optimum instead; the two agree only for n_stages = 1.  stationary=False: the
+        per-stage labels U_idx_stages of simplified_run(keep_policy=True) (n_stages must be the number kept, or None), which
+        reproduces F_values.  No min is taken (Backup.evaluate); terminal cost zero, as in simplified_run."""
+        if not isinstance(self.U_idx, list) or self.U_idx[0] is None or np.ndim(self.U_idx[0]) != 2:
+            raise RuntimeError("simplified_run() first")
+        return channel_policy_cost(self, lambda ch: self.build_spec_simplified(ch)[0], n_stages, stationary)
 
     # ------------------------------------------------------------------ 6-D
     def build_spec_full(self):

@@ -18,7 +18,7 @@ import math
 
 import numpy as np
 
-from .core import Backup, solve_many
+from .core import Backup, channel_policy_cost, solve_many
 from .matlab_compat import interp_nearest_point, sym_linspace_position
 from .problem import ProblemSpec, Term
 
@@ -83,12 +83,17 @@ class Solver_position:
         k = U / self.Mass
         return h * (k + 2 * k + 2 * k + k) / 6
 
-    def build_spec(self, channel):
+    def build_spec(self, channel, grid=None):
+        """grid=(s_x, s_v): the grid vectors to use instead of new ones (sym_linspace grows n to 2*ceil(n/2)+1 and simplified_run
+        writes that back to n_mesh_x / n_mesh_v, so a second build would be on another grid: policy_cost passes the run's own)."""
         Qx = (self.Qx1, self.Qx2, self.Qx3)[channel]
         Qv = (self.Qv1, self.Qv2, self.Qv3)[channel]
         R = (self.R1, self.R2, self.R3)[channel]
-        s_x = sym_linspace_position(self.x_min, self.x_max, self.n_mesh_x)   # :97-104
-        s_v = sym_linspace_position(self.v_min, self.v_max, self.n_mesh_v)
+        if grid is not None:
+            s_x, s_v = (np.asarray(g, dtype=np.float64) for g in grid)
+        else:
+            s_x = sym_linspace_position(self.x_min, self.x_max, self.n_mesh_x)   # :97-104
+            s_v = sym_linspace_position(self.v_min, self.v_max, self.n_mesh_v)
         U = np.asarray(self.U_vector, dtype=np.float64)
         nxt = [[Term((0,), s_x), Term((1,), self._dx_of_v(s_v, self.h))],     # RK4_x :157-167
                [Term((1,), s_v), Term((2,), self._dv_of_u(U, self.h))]]       # RK4_v :173-182
@@ -119,6 +124,19 @@ class Solver_position:
             setattr(self, "U%d_Opt" % (ch + 1), pol)
         self.n_mesh_x, self.n_mesh_v = len(s_x), len(s_v)                     # :100,:104
         return self
+
+    def policy_cost(self, n_stages=None, stationary=True):
+        """The cost over the grid of FLYING the policy simplified_run left, per channel: a list of three [n_x, n_v] arrays.
+        stationary=True (default): the kept last-stage labels U_idx[ch] - the one table the reference's closed loop flies for
+        the whole horizon (Solver_position.m:144-146, :215-217) - used at every one of n_stages stages (default N_stage - 1).
+        F_values is the cost of the time-varying optimum instead; the two agree only for n_stages = 1.  stationary=False: the
+        per-stage labels U_idx_stages of simplified_run(keep_policy=True) (n_stages must be the number kept, or None), which
+        reproduces F_values.  No min is taken (Backup.evaluate); terminal cost zero, as in simplified_run."""
+        if self.U_idx[0] is None:
+            raise RuntimeError("simplified_run() first")
+        # the grid the run was on (build_spec alone would grow the mesh again)
+        on_run_grid = lambda ch: self.build_spec(ch, grid=getattr(self, "U%d_Opt" % (ch + 1)).GridVectors)[0]
+        return channel_policy_cost(self, on_run_grid, n_stages, stationary)
 
     # ------------------------------------------------------------------ closed-loop rollout (SURVEY 8f-4)
     def get_target_R0V0(self):
