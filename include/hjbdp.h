@@ -386,6 +386,8 @@ int32_t hjb_evaluate(hjb_handle h, int32_t n_stages, const void *terminal, const
  *   x+_a = ((A[a,0]*x0 + A[a,1]*x1) + ...) + B[a,0]*u0 + ... + c_a   (left to right, each product rounded).
  * X0, X_final: [D, n_traj]; X_path [n_traj, D, n_steps+1] and U_path [n_traj, n_u, n_steps] (NULL: not kept); device_ms: the
  * kernels' time.  Option "chunk" (default 1 << 20): trajectories per launch, which bounds the device memory of a run.
+ * Option "lds" (default 1): 1 stages knots, 1/dx and u_table in LDS when they fit 32 KiB, 0 never stages (every run function of
+ * the object then reads them from global memory: same bits; tests, timing experiments); any other value is HJB_E_INVALID.
  * One call at a time per object; different objects may run from different threads.  The handle is spelled void * (no typedef).
  * hjb_rollout_last_error(NULL): the text of the calling thread's last failure (create's refusals). */
 #define HJB_ROLLOUT_MAX_U 4

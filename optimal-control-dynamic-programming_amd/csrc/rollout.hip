@@ -64,6 +64,7 @@ struct Rollout {
     int device = 0, D = 0, idx_bytes = 4, n_planes = 0;
     int model = kModelNone, integrator = HJB_ATT_TAYLOR;
     int64_t chunk = (int64_t)1 << 20;
+    bool lds = true;                // option "lds": stage the tables in LDS when they fit (false: never)
     DRollout R{};                   // device pointers filled by create; model by set_model
     DAttitude M{};                  // the attitude model (set_attitude_model)
     std::unique_ptr<PosAtt> pa;     // the pos-att model (set_pos_att_model)
@@ -241,7 +242,7 @@ int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n
     R.plane_of_step = (const int32_t *)bufs[5];
     R.n_steps = n_steps;
     const size_t lds = (size_t)(2 * (int64_t)R.n_knots + (int64_t)R.n_labels * R.n_u) * sizeof(double);
-    const bool lds_on = lds <= kLdsMax;
+    const bool lds_on = ro->lds && lds <= kLdsMax;
     double ms_total = 0;
     for (int64_t i0 = 0; e == hipSuccess && i0 < n_traj; i0 += nc_max) {
         const int64_t nc = std::min(nc_max, n_traj - i0);
@@ -695,6 +696,11 @@ int32_t hjb_rollout_set_option(void *rollout, const char *key, int64_t value) {
         ro->chunk = value;
         return HJB_OK;
     }
+    if (!strcmp(key, "lds")) {
+        if (value != 0 && value != 1) return rfail(ro, HJB_E_INVALID, "rollout: lds %lld is not 0 or 1", (long long)value);
+        ro->lds = value == 1;
+        return HJB_OK;
+    }
     return rfail(ro, HJB_E_INVALID, "rollout: unknown option '%s'", key);
 }
 
@@ -778,7 +784,7 @@ int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t 
     const DPaChan cx0 = pa_channel(ro->R);
     const size_t lds3 = (size_t)(2 * ((int64_t)cx0.n_knots + pa.cy.n_knots + pa.cz.n_knots) +
                                  4 * ((int64_t)cx0.n_labels + pa.cy.n_labels + pa.cz.n_labels)) * sizeof(double);
-    const bool lds3_on = lds3 <= kLdsMax;
+    const bool lds3_on = ro->lds && lds3 <= kLdsMax;
     return run_chunks(ro, "hjb_rollout_run_pos_att", HJB_PA_W, HJB_PA_F, HJB_PA_FM, n_steps, plane_of_step, n_traj, X0, X_final, nullptr,
                       X_path, F_path, FM_path, nullptr, nullptr,
                       [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *, double *dXp,
@@ -811,7 +817,7 @@ int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t
     const DPaChan cx0 = pa_channel(ro->R);
     const size_t lds3 = (size_t)(2 * ((int64_t)cx0.n_knots + ps.cy.n_knots + ps.cz.n_knots) +
                                  ((int64_t)cx0.n_labels + ps.cy.n_labels + ps.cz.n_labels)) * sizeof(double);
-    const bool lds3_on = lds3 <= kLdsMax;
+    const bool lds3_on = ro->lds && lds3 <= kLdsMax;
     return run_chunks(ro, "hjb_rollout_run_position", HJB_POS_W, HJB_POS_A, 0, n_steps, plane_of_step, n_traj, X0, X_final, nullptr,
                       X_path, A_path, nullptr, off_schedule, nullptr,
                       [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *, double *dXp,
@@ -843,7 +849,7 @@ int32_t hjb_rollout_run_attitude_simplified(void *rollout_1, int32_t n_steps, co
     const DPaChan c10 = pa_channel(ro->R);
     const size_t lds3 = (size_t)(2 * ((int64_t)c10.n_knots + as.c2.n_knots + as.c3.n_knots) +
                                  ((int64_t)c10.n_labels + as.c2.n_labels + as.c3.n_labels)) * sizeof(double);
-    const bool lds3_on = lds3 <= kLdsMax;
+    const bool lds3_on = ro->lds && lds3 <= kLdsMax;
     return run_chunks(ro, "hjb_rollout_run_attitude_simplified", HJB_ATT_W, HJB_ATT_U, 3, n_steps, plane_of_step, n_traj, X0, X_final, cost,
                       X_path, U_path, A_path, nullptr, nullptr,
                       [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *dC, double *dXp,

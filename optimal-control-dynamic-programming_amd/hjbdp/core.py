@@ -177,6 +177,9 @@ class Rollout:
         self.close()
 
     def set_option(self, key, value):
+        """hjb_rollout_set_option.  "chunk" (default 2^20): trajectories per launch, which bounds the device memory of a run.
+        "lds" (default 1): 1 stages knots, 1/dx and u_table in LDS when they fit 32 KiB; 0 never stages, so every run_* of this
+        object reads them from global memory (same bits).  Any other key or value raises HjbError (HJB_E_INVALID)."""
         self._check(self.lib.hjb_rollout_set_option(self._ro, key.encode(), int(value)))
 
     def set_model(self, A, B, c=None, q=None, r=None):

@@ -1,6 +1,7 @@
 """GPU tests of the batched closed-loop rollout (hjb_rollout_*, csrc/kernels_rollout.h; hjbdp.Rollout,
-Dynamic_Solver.get_optimal_paths): the Kirk fixture path, bit-equality with tests/rollout_refs.py at every instantiation,
-chunking, a real per-stage policy, and validation / concurrency with a device."""
+Dynamic_Solver.get_optimal_paths): the Kirk fixture path, bit-equality with tests/rollout_refs.py at every instantiation (LDS and
+global-memory form), chunking, a real per-stage policy, and validation / concurrency with a device.  The global-memory form as the
+library chooses it, label and placement edges and far label offsets: tests/test_gpu_rollout_forms.py."""
 import threading
 from pathlib import Path
 
@@ -141,6 +142,12 @@ def test_every_instantiation_is_bit_equal_to_the_restatement(built, D, dtype):
                     ref = rollout_refs.rollout(knots, labels, ut, base, A, B, X0, planes, method, c=c if nu == 4 else None, q=q, r=r)
                     _check_bits(out, ref)
                     assert np.isfinite(out["cost"]).all()
+                    # the same object's global-memory form (option "lds" = 0: the LDS = false instantiation): the twin's bits, the LDS form's bits
+                    ro.set_option("lds", 0)
+                    glob = ro.run(X0, planes, method=method, keep_path=True)
+                    ro.set_option("lds", 1)
+                    _check_bits(glob, ref)
+                    _check_bits(glob, (out["X_final"], out["cost"], out["X_path"], out["U_path"]))
 
 
 def test_chunking_and_batch_sizes(built):

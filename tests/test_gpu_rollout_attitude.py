@@ -117,6 +117,13 @@ def test_every_instantiation_is_bit_equal_to_the_twin(built, dtype):
                     # on the 2,100-knot axis 'linear' extrapolates with slopes of ~20 per unit: a start that drifts out of the
                     # grid there may overflow (bit-equal on both sides all the same); the short grids stay finite
                     assert np.isfinite(out["cost"]).mean() > (0.5 if long_axis else 0.999999)
+                    if n_labels == 40 and not long_axis:        # the LDS-sized problem once more, forced into the global-memory form
+                        ro.set_option("lds", 0)
+                        glob = ro.run_attitude(X0, planes, method, keep_path=True)
+                        ro.set_option("lds", 1)
+                        _check_bits(glob, ref)
+                        for key in ("X_final", "cost", "X_path", "U_path", "A_path"):
+                            assert _same(glob[key], out[key]), key
 
 
 @pytest.fixture(scope="module")

@@ -140,6 +140,15 @@ def test_every_instantiation_is_bit_equal_to_the_twin(built, dtype, long_axis):
                 _check_bits(r1.run_attitude_simplified(X0[:, :n], planes, keep_path=True), _head(ref, n))
                 _check_bits(r1.run_attitude_simplified(X0[:, :n], planes), _head(ref, n), paths=False)
             assert np.isfinite(ref[0]).all()
+            if not long_axis:           # the LDS-sized problem once more, forced into the global-memory form (option "lds" of channel 1's object)
+                staged = r1.run_attitude_simplified(X0, planes, keep_path=True)
+                r1.set_option("lds", 0)
+                glob = r1.run_attitude_simplified(X0, planes, keep_path=True)
+                r1.set_option("lds", 1)
+                _check_bits(glob, ref)
+                for key in staged:
+                    if key != "device_ms":
+                        assert _same(glob[key], staged[key]), key
 
 
 def _cost_null(ro, X0, planes):

@@ -120,6 +120,13 @@ def test_every_instantiation_is_bit_equal_to_the_twin(built, dtype):
                 _check_bits(out, ref)
                 assert np.isfinite(out["X_final"]).all()
                 assert len({out["F_path"][i].tobytes() for i in range(0, 4096, 64)}) > 32      # the starts do not fire alike
+                if n_labels == 40 and not long_axis:            # the LDS-sized problem once more, forced into the global-memory form
+                    rx.set_option("lds", 0)                     # channel x's object: the one the loop is run on
+                    glob = rx.run_pos_att(X0, planes, keep_path=True)
+                    rx.set_option("lds", 1)
+                    _check_bits(glob, ref)
+                    for key in KEYS:
+                        assert _same(glob[key], out[key]), key
 
 
 @pytest.fixture(scope="module")

@@ -131,6 +131,7 @@ def test_rollout_calls_on_a_null_object_are_statuses(lib):
     p = A.ctypes.data_as(C.POINTER(C.c_double))
     assert lib.hjb_rollout_set_model(None, p, p, None, None, None) == _abi.HJB_E_INVALID
     assert lib.hjb_rollout_set_option(None, b"chunk", 64) == _abi.HJB_E_INVALID
+    assert lib.hjb_rollout_set_option(None, b"lds", 0) == _abi.HJB_E_INVALID
     X = np.zeros(2)
     xp = X.ctypes.data_as(C.POINTER(C.c_double))
     assert lib.hjb_rollout_run(None, 1, 0, None, 1, xp, xp, None, None, None, None) == _abi.HJB_E_INVALID
