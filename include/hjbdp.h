@@ -452,6 +452,35 @@ int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *ro
 int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
                                 double *X_final, double *X_path, double *F_path, double *FM_path);
 
+/* Thruster-fault campaigns in the pos-att loop (K23): the loop above with a dead thruster in the plant and a hand-over to the fault
+ * controller of channel x (pos-att/Solver_pos_att.m:235-240, channel_x_controller_1_failure), both per trajectory, and two scalars
+ * per trajectory beside X_final.  hjb_rollout_set_pos_att_fault_controller attaches rollout_xf (an ordinary object, D == 4,
+ * n_u == 4 = f0 f1 f6 f7, rollout_x's device and label type, a grid of its own) to the pos-att model rollout_x holds (without
+ * one: HJB_E_INVALID, call hjb_rollout_set_pos_att_model first) and takes a share of its device data, as the model does of y's
+ * and z's: destroying rollout_xf afterwards is SAFE.  rollout_xf NULL detaches.  Setting the pos-att model again, or another
+ * model, drops the attachment; hjb_rollout_run_pos_att ignores it and stays bit for bit what it is.
+ * hjb_rollout_run_pos_att_faults, trajectory i at stage k: channel x is looked up in the fault controller when
+ * switch_stage[i] <= k, else in rollout_x (one lookup, on plane plane_of_step[k] like y and z); the commanded forces f0..f11 as
+ * in hjb_rollout_run_pos_att; the APPLIED forces fa_j = (fault_stage[i] <= k and bit j of fault_mask[i]) ? +0.0 : f_j; U_M, a
+ * and the RK4 sub-steps are hjb_rollout_run_pos_att's operations on fa.  F_path holds fa (what the plant got), FM_path is
+ * formed from fa.  With no fault and no hand-over X_final and the paths are hjb_rollout_run_pos_att's, bit for bit.
+ *   impulse[i] = (sum over the stages, in stage order, of ((((|fa0| + |fa1|) + |fa2|) + ...) + |fa11|)) * h, h as given to
+ *     hjb_rollout_set_pos_att_model;
+ *   settle_stage[i]: with X_0 = X0 and X_k+1 the state after stage k, X_m is inside when ((x0^2 + x1^2) + x2^2) <= pos_tol^2 and
+ *     ((q1^2 + q2^2) + q3^2) <= att_tol^2 (a NaN state is not inside); the smallest s such that X_m is inside for every m in
+ *     [s, n_steps], n_steps + 1 when X_n_steps is outside.
+ * fault_mask, fault_stage, switch_stage [n_traj] int32, each may be NULL: no fault / stage 0 / never.  A stage >= n_steps never
+ * comes.  impulse [n_traj], settle_stage [n_traj], the paths (laid out as hjb_rollout_run_pos_att's) and device_ms (the kernels'
+ * time by HIP events) may be NULL.  HJB_E_INVALID, decided before any device work and with the outputs untouched: a mask bit
+ * above 11, a negative stage, a switch_stage[i] < n_steps with no fault controller attached, a tolerance that is NaN or negative
+ * (+Inf is allowed), a non-finite X0, plane_of_step outside the planes of any of the four objects, and hjb_rollout_run_pos_att's
+ * own refusals.  Option "lds" and the 32 KiB rule cover the four controllers' tables together; option "chunk" as everywhere. */
+int32_t hjb_rollout_set_pos_att_fault_controller(void *rollout_x, void *rollout_xf);
+int32_t hjb_rollout_run_pos_att_faults(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                       const double *X0, const int32_t *fault_mask, const int32_t *fault_stage,
+                                       const int32_t *switch_stage, double pos_tol, double att_tol, double *X_final, double *impulse,
+                                       int32_t *settle_stage, double *X_path, double *F_path, double *FM_path, double *device_ms);
+
 /* Solver_position's closed loop (position-control/Solver_position.m:189-311, get_optimal_path after simplified_run) on three rollout
  * objects, one per channel (x, y, z), each D == 2 over (position, velocity) with n_u == 1 (the acceleration per label), on one device,
  * in one label type.  Sharing and lifetime are those of the pos-att model: hjb_rollout_set_position_model attaches the model to

@@ -114,6 +114,14 @@ int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *ro
                                       const double *orbit_coef);
 int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
                                 double *X_final, double *X_path, double *F_path, double *FM_path);
+/* thruster-fault campaigns in that loop (:235-240, channel_x_controller_1_failure): a fault controller for channel x attached to
+ * the model (rollout_xf NULL detaches), a dead thruster and a hand-over per trajectory, impulse and settling stage per trajectory;
+ * NULL ([]) for an input or output that is not wanted (hjbdp.h); usage: matlab/Solver_pos_att_hjbdp_fault_campaign.m */
+int32_t hjb_rollout_set_pos_att_fault_controller(void *rollout_x, void *rollout_xf);
+int32_t hjb_rollout_run_pos_att_faults(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                       const double *X0, const int32_t *fault_mask, const int32_t *fault_stage,
+                                       const int32_t *switch_stage, double pos_tol, double att_tol, double *X_final, double *impulse,
+                                       int32_t *settle_stage, double *X_path, double *F_path, double *FM_path, double *device_ms);
 /* Solver_position's RKF45 loop on three channel objects (position-control/Solver_position.m:189-311, get_optimal_path after
  * simplified_run), on rkf45's fixed schedule with a per-trajectory off-schedule flag (hjbdp.h) */
 int32_t hjb_rollout_set_position_model(void *rollout_x, void *rollout_y, void *rollout_z, double tol, int32_t n_steps, int32_t max_sub,

@@ -1,12 +1,14 @@
 // rollout.hip - hjb_rollout_*: batched closed-loop rollouts of a stored per-stage policy (include/hjbdp.h; kernels:
 // kernels_rollout.h for the affine model, kernels_rollout_attitude.h / rollout_attitude.hip for the attitude model,
 // kernels_rollout_pos_att.h / rollout_pos_att.hip for the pos-att model, kernels_rollout_position.h / rollout_position.hip for the
-// position model, kernels_rollout_attitude_simplified.h / rollout_attitude_simplified.hip for the simplified attitude model,
+// position model, kernels_rollout_pos_att_faults.h / rollout_pos_att_faults.hip for the pos-att model's fault campaigns,
+// kernels_rollout_attitude_simplified.h / rollout_attitude_simplified.hip for the simplified attitude model,
 // kernels_rollout_attitude_linear.h / rollout_attitude_linear.hip for the stateless linear attitude controller).
 #include "hjbdp_host.h"
 #include "kernels_rollout.h"
 #include "kernels_rollout_attitude.h"
 #include "kernels_rollout_pos_att.h"
+#include "kernels_rollout_pos_att_faults.h"
 #include "kernels_rollout_position.h"
 #include "kernels_rollout_attitude_simplified.h"
 #include "kernels_rollout_attitude_linear.h"
@@ -39,6 +41,12 @@ struct PosAtt {
     DPosAtt M{};
     int n_planes = 0;               // of the three channels, the fewest
     int max_steps = 0;              // (n_nodes - 1) / (2 substeps)
+    double h = 0;                   // as given (M.hs is h / substeps)
+    // the fault controller of channel x (hjb_rollout_set_pos_att_fault_controller): read by hjb_rollout_run_pos_att_faults alone
+    bool has_xf = false;
+    DPaChan cxf{};
+    std::shared_ptr<DevData> data_xf;
+    int planes_xf = 0;
 };
 
 // The position model of channel x's object: the y and z channels' descriptors with their device data kept alive, the RKF45 table
@@ -200,11 +208,12 @@ DPaChan pa_channel(const DRollout &R) {
 // kernel of the entry point `who`; Fl: nc int32 flags, allocated when `flags` is asked for: the position loop's off_schedule),
 // download X_final / cost / flags and the paths ([nc, rows] on the device -> columns i0 .. i0+nc of
 // [n_traj, rows] on the host); device_ms sums the launches' event times.  plane_of_step may be null for a loop without a policy
-// (hjb_attitude_linear_response): nothing is uploaded then.
-template <typename Launch>
+// (hjb_attitude_linear_response): nothing is uploaded then.  pre(i0, nc, stream) runs per chunk after X0's upload and before the
+// launch's first event (hjb_rollout_run_pos_att_faults uploads its per-trajectory inputs there, at the chunk's own offset).
+template <typename Launch, typename Pre>
 int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *E_path, int32_t *flags,
-               double *device_ms, Launch launch) {
+               double *device_ms, Launch launch, Pre pre) {
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
     const int nu = n_up;
@@ -248,6 +257,8 @@ int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n
         const int64_t nc = std::min(nc_max, n_traj - i0);
         e = hipMemcpyAsync(dX0, X0 + W * i0, (size_t)nc * W * sizeof(double), hipMemcpyHostToDevice, st);
         if (e != hipSuccess) break;
+        e = pre(i0, nc, st);
+        if (e != hipSuccess) break;
         (void)hipEventRecord(e0, st);
         e = launch(R, nc, lds, lds_on, st, dX0, dXf, dC, dXp, dUp, dEp, dFl);
         if (e != hipSuccess) break;
@@ -278,6 +289,14 @@ int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n
     }
     if (device_ms) *device_ms = ms_total;
     return done(HJB_OK);
+}
+
+template <typename Launch>
+int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+               const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *E_path, int32_t *flags,
+               double *device_ms, Launch launch) {
+    return run_chunks(ro, who, W, n_up, n_e, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, E_path, flags, device_ms,
+                      launch, [](int64_t, int64_t, hipStream_t) { return hipSuccess; });
 }
 
 }  // namespace
@@ -492,6 +511,7 @@ int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *ro
     if (rx == ry || rx == rz || ry == rz) return rfail(rx, HJB_E_INVALID, "rollout: the same object passed for two channels");
     auto pa = std::make_unique<PosAtt>();
     pa->M = M;
+    pa->h = h;
     pa->max_steps = (int)((n_nodes - 1) / (2 * (int64_t)substeps));
     // y and z: a snapshot of the policy with a share of its device data, taken under that object's own lock
     int dev_o[2] = {0, 0}, idx_o[2] = {0, 0}, planes_o[2] = {0, 0};
@@ -534,6 +554,47 @@ int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *ro
     rx->ps.reset();
     rx->as.reset();
     rx->model = kModelPosAtt;
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_set_pos_att_fault_controller(void *rollout_x, void *rollout_xf) {
+    Rollout *rx = (Rollout *)rollout_x, *rf = (Rollout *)rollout_xf;
+    if (!rx) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    if (rx == rf) return rfail(rx, HJB_E_INVALID, "rollout: the same object passed as channel x and as its fault controller");
+    // the fault controller: a snapshot of the policy with a share of its device data, taken under that object's own lock
+    DPaChan cxf{};
+    std::shared_ptr<DevData> data_xf;
+    int dev_f = 0, idx_f = 0, planes_f = 0, D_f = 0, nu_f = 0;
+    if (rf) {
+        std::lock_guard<std::mutex> g(rf->mu);
+        D_f = rf->D;
+        nu_f = rf->R.n_u;
+        cxf = pa_channel(rf->R);
+        data_xf = rf->data;
+        dev_f = rf->device;
+        idx_f = rf->idx_bytes;
+        planes_f = rf->n_planes;
+    }
+    std::lock_guard<std::mutex> g(rx->mu);
+    if (rx->model != kModelPosAtt || !rx->pa)
+        return rfail(rx, HJB_E_INVALID, "rollout: the fault controller attaches to the pos-att model: call hjb_rollout_set_pos_att_model first");
+    if (rf) {
+        if (D_f != 4 || nu_f != 4)
+            return rfail(rx, HJB_E_INVALID, "rollout: the fault controller needs D == 4 and n_u == 4 (rollout_xf: D=%d, n_u=%d)", D_f, nu_f);
+        if (dev_f != rx->device)
+            return rfail(rx, HJB_E_INVALID, "rollout: rollout_xf is on device %d, rollout_x on device %d", dev_f, rx->device);
+        if (idx_f != rx->idx_bytes)
+            return rfail(rx, HJB_E_INVALID, "rollout: rollout_xf has %d-byte labels, rollout_x %d-byte labels (the four controllers share one label type)",
+                         idx_f, rx->idx_bytes);
+    }
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    if (hipSetDevice(rx->device) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "hipSetDevice failed");
+    if (rx->stream) (void)hipStreamSynchronize(rx->stream);
+    PosAtt &pa = *rx->pa;
+    pa.has_xf = rf != nullptr;
+    pa.cxf = cxf;
+    pa.data_xf = std::move(data_xf);                        // replaces (and releases) a fault controller attached earlier
+    pa.planes_xf = planes_f;
     return HJB_OK;
 }
 
@@ -795,6 +856,98 @@ int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t 
                           M.n_steps = R.n_steps;
                           return launch_rollout_pos_att(idx_bytes, lds3_on, cx, cy, cz, M, nc, lds3, st, dX0, dXf, dXp, dFp, dFMp);
                       });
+}
+
+int32_t hjb_rollout_run_pos_att_faults(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                       const double *X0, const int32_t *fault_mask, const int32_t *fault_stage,
+                                       const int32_t *switch_stage, double pos_tol, double att_tol, double *X_final, double *impulse,
+                                       int32_t *settle_stage, double *X_path, double *F_path, double *FM_path, double *device_ms) {
+    Rollout *ro = (Rollout *)rollout_x;
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    // every refusal before any device work, the outputs untouched
+    const int bad_arg = check_run(ro, kModelPosAtt, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
+    if (bad_arg) return bad_arg;
+    const PosAtt &pa = *ro->pa;
+    if (n_steps > pa.max_steps)
+        return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the orbit table covers %d stages ((n_nodes - 1) / (2 substeps))", n_steps,
+                     pa.max_steps);
+    if (pa.has_xf)
+        for (int k = 0; k < n_steps; ++k)
+            if (plane_of_step[k] >= pa.planes_xf)
+                return rfail(ro, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d) (the fault controller's planes)", k,
+                             plane_of_step[k], pa.planes_xf);
+    if (!(pos_tol >= 0)) return rfail(ro, HJB_E_INVALID, "rollout: pos_tol = %g is NaN or negative", pos_tol);
+    if (!(att_tol >= 0)) return rfail(ro, HJB_E_INVALID, "rollout: att_tol = %g is NaN or negative", att_tol);
+    if (n_traj == 0) {
+        if (device_ms) *device_ms = 0.0;
+        return HJB_OK;
+    }
+    if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final");
+    if (n_traj > INT64_MAX / (HJB_PA_W * ((int64_t)n_steps + 1)) / 8)
+        return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x 13 x n_steps)");
+    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_PA_W * n_traj, true);
+    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    for (int64_t i = 0; i < n_traj; ++i) {
+        if (fault_mask && (fault_mask[i] & ~0xFFF))
+            return rfail(ro, HJB_E_INVALID, "rollout: fault_mask[%lld] = 0x%x has a bit above 11 (twelve thrusters)", (long long)i,
+                         (unsigned)fault_mask[i]);
+        if (fault_stage && fault_stage[i] < 0)
+            return rfail(ro, HJB_E_INVALID, "rollout: fault_stage[%lld] = %d < 0", (long long)i, fault_stage[i]);
+        if (switch_stage && switch_stage[i] < 0)
+            return rfail(ro, HJB_E_INVALID, "rollout: switch_stage[%lld] = %d < 0", (long long)i, switch_stage[i]);
+        if (switch_stage && switch_stage[i] < n_steps && !pa.has_xf)
+            return rfail(ro, HJB_E_INVALID, "rollout: switch_stage[%lld] = %d hands over within the %d stages, but no fault controller is "
+                         "attached (hjb_rollout_set_pos_att_fault_controller)", (long long)i, switch_stage[i], n_steps);
+    }
+    const int idx_bytes = ro->idx_bytes;
+    const DPaChan cx0 = pa_channel(ro->R);
+    const size_t lds4 = (size_t)(2 * ((int64_t)cx0.n_knots + pa.cy.n_knots + pa.cz.n_knots + pa.cxf.n_knots) +
+                                 4 * ((int64_t)cx0.n_labels + pa.cy.n_labels + pa.cz.n_labels + pa.cxf.n_labels)) * sizeof(double);
+    const bool lds4_on = ro->lds && lds4 <= kLdsMax;
+    DPaFault Q{};
+    Q.h = pa.h;
+    Q.p2 = pos_tol * pos_tol;
+    Q.a2 = att_tol * att_tol;
+    // the per-trajectory inputs on the device: allocated at the first chunk (for the largest), uploaded per chunk at its offset
+    const int32_t *const host_in[3] = {fault_mask, fault_stage, switch_stage};
+    int32_t *dev_in[3] = {nullptr, nullptr, nullptr};
+    const int64_t nc_max = std::min(n_traj, ro->chunk);
+    const int st = run_chunks(ro, "hjb_rollout_run_pos_att_faults", HJB_PA_W, HJB_PA_F, HJB_PA_FM, n_steps, plane_of_step, n_traj, X0, X_final,
+                              impulse, X_path, F_path, FM_path, settle_stage, device_ms,
+                              [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t s, double *dX0, double *dXf, double *dImp, double *dXp,
+                                  double *dFp, double *dFMp, int32_t *dSettle) {
+                                  DPaChan cx = cx0, cy = pa.cy, cz = pa.cz, cxf = pa.cxf;
+                                  cx.plane_of_step = cy.plane_of_step = cz.plane_of_step = cxf.plane_of_step = R.plane_of_step;
+                                  DPosAtt M = pa.M;
+                                  M.n_steps = R.n_steps;
+                                  DPaFault Qc = Q;
+                                  Qc.mask = dev_in[0];
+                                  Qc.fault_stage = dev_in[1];
+                                  Qc.switch_stage = dev_in[2];
+                                  Qc.impulse = dImp;
+                                  Qc.settle = dSettle;
+                                  return launch_rollout_pos_att_faults(idx_bytes, lds4_on, cx, cy, cz, cxf, M, Qc, nc, lds4, s, dX0, dXf, dXp,
+                                                                       dFp, dFMp);
+                              },
+                              [&](int64_t i0, int64_t nc, hipStream_t s) {
+                                  for (int t = 0; t < 3; ++t) {
+                                      if (!host_in[t]) continue;
+                                      hipError_t e = hipSuccess;
+                                      if (!dev_in[t]) e = hipMalloc((void **)&dev_in[t], (size_t)nc_max * sizeof(int32_t));
+                                      if (e == hipSuccess)
+                                          e = hipMemcpyAsync(dev_in[t], host_in[t] + i0, (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, s);
+                                      if (e != hipSuccess) return e;
+                                  }
+                                  return hipSuccess;
+                              });
+    {
+        std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+        (void)hipSetDevice(ro->device);
+        for (int32_t *p : dev_in)
+            if (p) (void)hipFree(p);
+    }
+    return st;
 }
 
 int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,

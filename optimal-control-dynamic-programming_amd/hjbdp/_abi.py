@@ -234,6 +234,10 @@ SYMBOLS = {
     "hjb_rollout_set_pos_att_model": (C.c_int32, [C.c_void_p] * 3 + [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_int32,
                                                   C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)]),
     "hjb_rollout_run_pos_att": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64] + [C.POINTER(C.c_double)] * 5),
+    "hjb_rollout_set_pos_att_fault_controller": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "hjb_rollout_run_pos_att_faults": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_double)]
+                                       + [C.POINTER(C.c_int32)] * 3 + [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                                       C.POINTER(C.c_int32)] + [C.POINTER(C.c_double)] * 4),
     "hjb_rollout_set_position_model": (C.c_int32, [C.c_void_p] * 3 + [C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                                    C.POINTER(C.c_double)]),
     "hjb_rollout_run_position": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64] + [C.POINTER(C.c_double)] * 4

@@ -282,6 +282,59 @@ class Rollout:
         path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
         return {"X_final": Xf.T, "X_path": path(Xp, 13, K + 1), "F_path": path(Fp, 12, K), "FM_path": path(FMp, 6, K)}
 
+    def set_pos_att_fault_controller(self, other):
+        """hjb_rollout_set_pos_att_fault_controller: attach `other` (a Rollout with D = 4, n_u = 4 = [f0 f1 f6 f7], this object's
+        device and label type, a grid of its own) as the fault controller of channel x to the pos-att model this object holds;
+        None detaches.  The model keeps what it reads of `other` alive: it may be closed afterwards.  Setting a model again drops
+        the attachment; run_pos_att ignores it."""
+        self._check(self.lib.hjb_rollout_set_pos_att_fault_controller(self._ro, None if other is None else other._ro))
+
+    def run_pos_att_faults(self, X0, plane_of_step=None, fault_mask=None, fault_stage=None, switch_stage=None, pos_tol=np.inf,
+                           att_tol=np.inf, keep_path=False):
+        """hjb_rollout_run_pos_att_faults (K23): run_pos_att with, per trajectory, the thrusters of fault_mask (bit j = thruster j)
+        dead in the plant from stage fault_stage on and channel x handed over to the attached fault controller from stage
+        switch_stage on.  fault_mask / fault_stage / switch_stage: None (no fault / stage 0 / never), a scalar or [n_traj]; a stage
+        >= n_steps never comes.  Returns a dict: X_final [13, n_traj]; impulse [n_traj] = h * sum over stages and thrusters of
+        |applied force|; settle_stage [n_traj] (int32): the first state index from which the path stays within pos_tol of the
+        origin and |q(1:3)| within att_tol to the end, n_steps + 1 if the last state is outside; X_path, F_path (the APPLIED
+        forces), FM_path as run_pos_att's, None unless keep_path; device_ms."""
+        X = np.asarray(X0, dtype=np.float64)
+        X = np.ascontiguousarray((X.reshape(13, 1) if X.ndim == 1 else X).reshape(13, -1).T)
+        nt = X.shape[0]
+        if plane_of_step is None:
+            plane_of_step = np.zeros(getattr(self, "_pa_steps", 0), np.int32)
+        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
+        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
+            raise ValueError("plane_of_step does not fit int32")
+        ps = ps.astype(np.int32)
+        K = int(ps.size)
+
+        def per_traj(v, name):
+            if v is None:
+                return None
+            a = np.asarray(v)
+            if a.dtype.kind not in "iu":
+                raise TypeError("%s must be integers, got %s" % (name, a.dtype))
+            a = np.broadcast_to(a.reshape(-1) if a.ndim else a, (nt,))
+            if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
+                raise ValueError("%s does not fit int32" % name)
+            return np.ascontiguousarray(a, dtype=np.int32)
+        fm, fs, sw = per_traj(fault_mask, "fault_mask"), per_traj(fault_stage, "fault_stage"), per_traj(switch_stage, "switch_stage")
+        i32p = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        Xf = np.empty((nt, 13))
+        imp = np.empty(nt)
+        settle = np.empty(nt, np.int32)
+        Xp = np.empty(nt * 13 * (K + 1)) if keep_path else None
+        Fp = np.empty(nt * 12 * K) if keep_path else None
+        FMp = np.empty(nt * 6 * K) if keep_path else None
+        ms = C.c_double(0.0)
+        self._check(self.lib.hjb_rollout_run_pos_att_faults(self._ro, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X), i32p(fm),
+                                                            i32p(fs), i32p(sw), float(pos_tol), float(att_tol), _f64p(Xf), _f64p(imp),
+                                                            i32p(settle), _f64p(Xp), _f64p(Fp), _f64p(FMp), C.byref(ms)))
+        path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
+        return {"X_final": Xf.T, "impulse": imp, "settle_stage": settle, "X_path": path(Xp, 13, K + 1), "F_path": path(Fp, 12, K),
+                "FM_path": path(FMp, 6, K), "device_ms": ms.value}
+
     def set_position_model(self, rollout_y, rollout_z, n_sub, table, tol=1e-8):
         """Solver_position's RKF45 loop (hjb_rollout_set_position_model; the last model set wins) with this object as channel x and
         two more Rollout objects as channels y and z (each D = 2 over (position, velocity), n_u = 1, one device, one label type).

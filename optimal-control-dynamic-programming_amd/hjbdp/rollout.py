@@ -465,6 +465,111 @@ def pos_att_optimal_path_fixed(pa, X0=None, n_steps=None, substeps=1, channel_x=
     return np.arange(N) * pa.h, X, F, FM
 
 
+def pos_att_fault_path_fixed(pa, X0, fault_mask, fault_stage, switch_stage, n_steps=None, substeps=1, pos_tol=math.inf,
+                             att_tol=math.inf):
+    """pos_att_optimal_path_fixed with a thruster fault in the plant and a hand-over of channel x to channel_x_controller_1_failure
+    (:235-240): the scalar host loop in the operation order of the GPU kernel (K23, csrc/kernels_rollout_pos_att_faults.h), which it
+    equals bit for bit.  From stage fault_stage (None: 0) on, the thrusters whose bit is set in fault_mask (None or 0: no fault)
+    apply +0.0 whatever was commanded; from stage switch_stage (None: never) on, channel x is looked up in the failure controller.
+    Returns (T [N], X [N, 13], F_applied [N, 12], Force_Moment [N, 6], impulse, settle_stage): impulse = h * the sum over stages
+    of ((|fa0| + |fa1|) + ...) + |fa11|; settle_stage the smallest s such that rows s .. N - 1 of X all have
+    (x0^2 + x1^2) + x2^2 <= pos_tol^2 and (q1^2 + q2^2) + q3^2 <= att_tol^2, N when the last row has not.  With no fault and no
+    hand-over the four arrays are pos_att_optimal_path_fixed's."""
+    chans = pos_att_channels(pa)
+    mask = 0 if fault_mask is None else int(fault_mask)
+    f_at = 0 if fault_stage is None else int(fault_stage)
+    X0 = pos_att_default_X0() if X0 is None else np.asarray(X0, dtype=np.float64).reshape(13)
+    N = pa.N_stage if n_steps is None else min(pa.N_stage, int(n_steps) + 1)
+    s_at = N - 1 if switch_stage is None else int(switch_stage)
+    if mask < 0 or mask >> 12 or f_at < 0 or s_at < 0:
+        raise ValueError("fault_mask has twelve bits and the stages are >= 0")
+    if s_at < N - 1:
+        chans = chans + pos_att_channels(pa, "channel_x_controller_1_failure")[:1]
+    S = int(substeps)
+    rsw, coef = pos_att_orbit_table(N - 1, pa.h, S)
+    rsw = [[float(v) for v in row] for row in rsw]
+    rswi = [[float(v) for v in row] for row in inv3_adjugate(rsw)]
+    Jm = [[float(v) for v in row] for row in np.asarray(pa.InertiaM, dtype=np.float64)]
+    Ji = [[float(v) for v in row] for row in inv3_adjugate(Jm)]
+    mass, d, hs = float(pa.Mass), float(pa.T_dist), float(pa.h) / S
+    p2, a2 = float(pos_tol) * float(pos_tol), float(att_tol) * float(att_tol)
+    coef = coef.tolist()
+    kn = [[k.tolist() for k in ch[0]] for ch in chans]
+    lab = [np.asarray(ch[1]) for ch in chans]
+    tab = [ch[2].tolist() for ch in chans]
+    slots = ((0, 1, 6, 7), (2, 3, 8, 9), (4, 5, 10, 11))
+    axis = (1, 2, 0)                                   # channel x uses the angle / rate about y, y about z, z about x
+
+    def rates(c, a, um, y):
+        c0, c1, c2, c3, c4 = c
+        q1, q2, q3, q4, w1, w2, w3 = y[6:13]
+        jw = _mul3(Jm, w1, w2, w3)
+        t = [um[0] - (w2 * jw[2] - w3 * jw[1]), um[1] - (w3 * jw[0] - w1 * jw[2]), um[2] - (w1 * jw[1] - w2 * jw[0])]
+        return [y[3], y[4], y[5],
+                ((c0 * y[0] - c1 * y[1]) + c2 * y[4]) + a[0],
+                ((c1 * y[0] - c3 * y[1]) - c2 * y[3]) + a[1],
+                a[2] - c4 * y[2],
+                0.5 * (((w3 * q2) - (w2 * q3)) + (w1 * q4)),
+                0.5 * (((w1 * q3) - (w3 * q1)) + (w2 * q4)),
+                0.5 * (((w2 * q1) - (w1 * q2)) + (w3 * q4)),
+                0.5 * (((-(w1 * q1)) - (w2 * q2)) - (w3 * q3))] + _mul3(Ji, t[0], t[1], t[2])
+
+    def inside(y):
+        return ((y[0] * y[0] + y[1] * y[1]) + y[2] * y[2]) <= p2 and ((y[6] * y[6] + y[7] * y[7]) + y[8] * y[8]) <= a2
+
+    X = np.zeros((N, 13))
+    F = np.zeros((N, 12))
+    FM = np.zeros((N, 6))
+    X[0] = X0
+    x = [float(v) for v in X0]
+    imp = 0.0
+    last_outside = -1 if inside(x) else 0
+    with np.errstate(all="ignore"):
+        for k in range(N - 1):
+            th = [2.0 * canon_asin(1.0 if x[6 + j] > 1.0 else -1.0 if x[6 + j] < -1.0 else x[6 + j]) for j in range(3)]
+            E = _eci2body_list(x[6], x[7], x[8], x[9])
+            M = [[(E[r][0] * rsw[0][c] + E[r][1] * rsw[1][c]) + E[r][2] * rsw[2][c] for c in range(3)] for r in range(3)]
+            xb, vb = _mul3(M, x[0], x[1], x[2]), _mul3(M, x[3], x[4], x[5])
+            f = [0.0] * 12
+            for ch in range(3):
+                src = 3 if (ch == 0 and s_at <= k) else ch              # the failure controller has taken over channel x
+                p = (xb[ch], vb[ch], th[axis[ch]], x[10 + axis[ch]])
+                idx = tuple(_nearest_index(kn[src][a], p[a]) for a in range(4))
+                row = tab[src][int(lab[src][idx]) - 1]
+                for s_, v in zip(slots[ch], row):
+                    f[s_] = v
+            if f_at <= k:                                               # what the plant gets
+                f = [0.0 if (mask >> j) & 1 else f[j] for j in range(12)]
+            sk = abs(f[0]) + abs(f[1])
+            for j in range(2, 12):
+                sk = sk + abs(f[j])
+            imp = imp + sk
+            um = [(((f[4] - f[5]) + f[10]) - f[11]) * d, (((f[0] - f[1]) + f[6]) - f[7]) * d, (((f[2] - f[3]) + f[8]) - f[9]) * d]
+            ab = [(((f[0] + f[1]) + f[6]) + f[7]) / mass, (((f[2] + f[3]) + f[8]) + f[9]) / mass, (((f[4] + f[5]) + f[10]) + f[11]) / mass]
+            Ei = inv3_adjugate(E).tolist()
+            ae = _mul3(Ei, ab[0], ab[1], ab[2])
+            a = _mul3(rswi, ae[0], ae[1], ae[2])
+            F[k] = f
+            FM[k] = a + um
+            for s in range(S):
+                j = 2 * (S * k + s)
+                r = rates(coef[j], a, um, x)
+                acc = r
+                xt = [x[i] + (r[i] * hs) / 2.0 for i in range(13)]
+                r = rates(coef[j + 1], a, um, xt)
+                acc = [acc[i] + 2.0 * r[i] for i in range(13)]
+                xt = [x[i] + (r[i] * hs) / 2.0 for i in range(13)]
+                r = rates(coef[j + 1], a, um, xt)
+                acc = [acc[i] + 2.0 * r[i] for i in range(13)]
+                xt = [x[i] + r[i] * hs for i in range(13)]
+                r = rates(coef[j + 2], a, um, xt)
+                x = [x[i] + (hs * (acc[i] + r[i])) / 6.0 for i in range(13)]
+            X[k + 1] = x
+            if not inside(x):
+                last_outside = k + 1
+    return np.arange(N) * pa.h, X, F, FM, imp * float(pa.h), last_outside + 1
+
+
 # ---- Solver_attitude, simplified policies on the rigid body: the arithmetic of the GPU loop (K20, --------------------------------
 # csrc/kernels_rollout_attitude_simplified.h) ---------------------------------------------------------------------------------------
 def attitude_simplified_channels(sa, per_stage=False):

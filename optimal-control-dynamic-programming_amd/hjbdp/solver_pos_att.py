@@ -312,3 +312,32 @@ class Solver_pos_att:
         F[:N - 1] = out["F_path"].transpose(2, 1, 0)
         FM[:N - 1] = out["FM_path"].transpose(2, 1, 0)
         return np.arange(N) * self.h, X, F, FM
+
+    def get_fault_campaign(self, X0s=None, fault_mask=0, fault_stage=0, switch_stage=None, n_steps=None, substeps=1,
+                           pos_tol=np.inf, att_tol=np.inf, keep_path=False, device=None):
+        """The scenario channel_x_controller_1_failure (:235-240) was solved for, for many initial states at once on the GPU
+        (hjbdp.Rollout.run_pos_att_faults, K23), after simplified_run(): the closed loop of get_optimal_paths (:452-730) in which,
+        per trajectory, the thrusters of fault_mask (bit j = thruster j) die in the plant at stage fault_stage and channel x is
+        handed over from channel_x_controller_1 to channel_x_controller_1_failure at stage switch_stage (None: never).  X0s
+        [13, n] (None: the reference's X0); fault_mask, fault_stage, switch_stage scalars or [n], scalars broadcast over the
+        starts; a stage >= the number of stages never comes.  Returns run_pos_att_faults' dict: X_final [13, n], impulse [n] (N s),
+        settle_stage [n] (the first state index from which the path stays within pos_tol (m) of the target and |q(1:3)| within
+        att_tol to the end; the number of states when it has not settled), X_path / F_path (applied forces) / FM_path ([n, rows,
+        stages], None unless keep_path) and device_ms."""
+        from . import rollout
+        from .core import Rollout
+        chans = rollout.pos_att_channels(self) + rollout.pos_att_channels(self, "channel_x_controller_1_failure")[:1]
+        X0s = rollout.pos_att_default_X0().reshape(13, 1) if X0s is None else np.asarray(X0s, dtype=np.float64).reshape(13, -1)
+        N = self.N_stage if n_steps is None else min(self.N_stage, int(n_steps) + 1)
+        rsw, coef = rollout.pos_att_orbit_table(N - 1, self.h, substeps)
+        dev = self.device if device is None else int(device)
+        ros = []
+        try:
+            for knots, labels, table in chans:
+                ros.append(Rollout(knots, labels, table, index_base=1, device=dev))
+            ros[0].set_pos_att_model(ros[1], ros[2], self.InertiaM, self.Mass, self.T_dist, self.h, rsw, coef, substeps)
+            ros[0].set_pos_att_fault_controller(ros[3])
+            return ros[0].run_pos_att_faults(X0s, None, fault_mask, fault_stage, switch_stage, pos_tol, att_tol, keep_path)
+        finally:
+            for ro in ros:
+                ro.close()

@@ -15,8 +15,10 @@ Two cases, one JSON line:
       case_attitude_simplified_loop; alone, it also writes its line to profiles/rollout_attitude_simplified_time.json.
   (g) attitude_linear_loop: the linear attitude controller (K21, hjb_attitude_linear_response) beside K17's 'nearest' RK4 loop, see
       case_attitude_linear_loop; alone, it also writes its line to profiles/rollout_attitude_linear_time.json.
+  (h) pos_att_faults: the pos-att fault campaign (K23, hjb_rollout_run_pos_att_faults) beside K18 in one process, see
+      case_pos_att_faults; alone, it also writes its line to profiles/rollout_pos_att_faults_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults] [--out FILE]
 """
 from __future__ import annotations
 
@@ -362,6 +364,71 @@ def case_attitude_linear_loop(host=True, n_traj=262144, n_steps=5999):
     return res
 
 
+def case_pos_att_faults(host=True, n_traj=1 << 18, n_stages=None):
+    """(h) pos_att_faults: the four policies of Solver_pos_att.simplified_run (nominal x, y, z and channel_x_controller_1_failure)
+    on the 13-state loop over all N_stage - 1 = 1,999 stages at substeps 1, paths off, 2^18 starts around the default X0, in one
+    process.  Three runs alternate, five rounds after a warm-up round of the same shapes:
+      (a) hjb_rollout_run_pos_att (K18);
+      (b) hjb_rollout_run_pos_att_faults with every per-trajectory array NULL (K23 doing K18's work);
+      (c) a mixed campaign: thruster 0 dead from a stage uniform in [0, 1999), hand-over 0 to 400 stages later, per trajectory.
+    Each call is timed with host clocks around the whole call (upload, kernel, download: K18 reports no kernel time of its own);
+    (b) and (c) also list device_ms, the kernels' event times.  All five of each are listed, the medians quoted, and the ratios
+    b/a and c/a of the wall-clock medians.  `host` is not used: the host loops are timed by case_pos_att_loop."""
+    import hjbdp
+    from hjbdp import rollout
+    pa = hjbdp.Solver_pos_att()
+    t0 = time.perf_counter()
+    pa.simplified_run()
+    sweep_s = time.perf_counter() - t0
+    K = pa.N_stage - 1 if n_stages is None else int(n_stages)
+    rng = np.random.default_rng(23)
+    X0 = np.tile(rollout.pos_att_default_X0().reshape(13, 1), (1, n_traj))
+    X0[0:3] += rng.uniform(-0.05, 0.05, size=(3, n_traj))
+    X0[3:6] += rng.uniform(-0.02, 0.02, size=(3, n_traj))
+    X0[10:13] += rng.uniform(-0.01, 0.01, size=(3, n_traj))
+    mask = np.ones(n_traj, np.int32)
+    f_at = rng.integers(0, K, size=n_traj).astype(np.int32)
+    s_at = (f_at + rng.integers(0, 401, size=n_traj)).astype(np.int32)
+    chans = rollout.pos_att_channels(pa) + rollout.pos_att_channels(pa, "channel_x_controller_1_failure")[:1]
+    rsw, coef = rollout.pos_att_orbit_table(K, pa.h, 1)
+    res = {"grid": "30x30x20x15 per channel", "labels": "uint8", "n_traj": int(n_traj), "n_steps": int(K), "substeps": 1,
+           "sweep_wall_s": round(sweep_s, 3),
+           "timing": "wall_ms: host clock around the whole call (upload + kernel + download); device_ms: event times around the "
+                     "launches (K23 only); the three runs alternate in one process, 5 rounds after a warm-up round"}
+    ros = [hjbdp.Rollout(k, l, t, index_base=1) for k, l, t in chans]
+    try:
+        ros[0].set_pos_att_model(ros[1], ros[2], pa.InertiaM, pa.Mass, pa.T_dist, pa.h, rsw, coef, 1)
+        ros[0].set_pos_att_fault_controller(ros[3])
+        runs = (("a_run_pos_att", lambda: ros[0].run_pos_att(X0)),
+                ("b_faults_all_null", lambda: ros[0].run_pos_att_faults(X0)),
+                ("c_faults_mixed", lambda: ros[0].run_pos_att_faults(X0, None, mask, f_at, s_at, 0.05, 0.02)))
+        wall = {name: [] for name, _ in runs}
+        dev = {name: [] for name, _ in runs}
+        for rnd in range(6):
+            for name, fn in runs:
+                t0 = time.perf_counter()
+                out = fn()
+                dt = time.perf_counter() - t0
+                if rnd:                                           # round 0 is the warm-up
+                    wall[name].append(dt * 1e3)
+                    dev[name].append(out.get("device_ms"))
+                if rnd == 5 and name == "c_faults_mixed":
+                    res["c_settled"] = int((out["settle_stage"] <= K).sum())
+                    res["c_impulse_median_Ns"] = float(np.median(out["impulse"]))
+    finally:
+        for ro in ros:
+            ro.close()
+    for name, _ in runs:
+        med = float(np.median(wall[name]))
+        res[name] = {"wall_ms": [round(t, 3) for t in wall[name]], "wall_ms_median": round(med, 3),
+                     "traj_stages_per_s": n_traj * K / (med * 1e-3)}
+        if dev[name][0] is not None:
+            res[name].update(device_ms=[round(t, 3) for t in dev[name]], device_ms_median=round(float(np.median(dev[name])), 3))
+    res["b_over_a"] = res["b_faults_all_null"]["wall_ms_median"] / res["a_run_pos_att"]["wall_ms_median"]
+    res["c_over_a"] = res["c_faults_mixed"]["wall_ms_median"] / res["a_run_pos_att"]["wall_ms_median"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -375,7 +442,7 @@ def main():
     for c in a.cases.split(","):
         res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude, "pos_att_loop": case_pos_att_loop,
                   "position_loop": case_position_loop, "attitude_simplified_loop": case_attitude_simplified_loop,
-                  "attitude_linear_loop": case_attitude_linear_loop}[c](host=not a.no_host)
+                  "attitude_linear_loop": case_attitude_linear_loop, "pos_att_faults": case_pos_att_faults}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.cases == "position_loop" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
@@ -383,6 +450,8 @@ def main():
         (ROOT / "profiles" / "rollout_attitude_simplified_time.json").write_text(json.dumps(res) + "\n")
     if a.cases == "attitude_linear_loop" and not a.out:           # its own record: one line
         (ROOT / "profiles" / "rollout_attitude_linear_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "pos_att_faults" and not a.out:                 # its own record: one line
+        (ROOT / "profiles" / "rollout_pos_att_faults_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
