@@ -93,28 +93,78 @@ __device__ __forceinline__ constexpr int trailing_ones(int c) { return (c & 1) ?
         }                                                                                                                       \
     }
 
+// One channel's tables for the lookup, the ONE staging every rollout kernel uses, in two steps (t_: a name for the channel; c_: a
+// DRollout or a DPaChan; width_: u_table doubles per label).
+//   HJB_ROLLOUT_PLACE: the channel's place in LDS, [knots | 1/dx | u_table] from at_ on; HJB_ROLLOUT_PLACE_END(t_) is where the
+//     next channel goes.
+//   HJB_ROLLOUT_STAGE: LDS_: the block copies the channel to its place and kn_ / rd_ / ut_ point into the copy (the caller issues
+//     ONE __syncthreads() after its last channel); otherwise kn_ / rd_ / ut_ are the channel's global pointers.
+// Every PLACE of a kernel comes before its first STAGE, and the end of a place is an expression, not a variable: with a channel's
+// counts read between two copy loops, or with the end held in a pointer of its own, the compiler allocates the registers of the
+// LDS kernels differently.  Macros for HJB_ROLLOUT_LOOKUP's reason: behind a force-inlined function K16's registers move too.
+// Names: PLACE declares nk_<t_>, nu_<t_> and lds_<t_> in the CALLER's scope, in the global-memory form of a kernel too (where
+// only the discarded branch of STAGE reads them and they cost nothing): leave them there, moving them into the branch is the
+// change of order described above.  STAGE's loop variable is stage_e_, inside its own blocks.
+#define HJB_ROLLOUT_PLACE(t_, c_, width_, at_)                                                                                 \
+    const int nk_##t_ = c_.n_knots, nu_##t_ = c_.n_labels * width_;                                                            \
+    double *lds_##t_ = at_;
+#define HJB_ROLLOUT_PLACE_END(t_) (lds_##t_ + 2 * nk_##t_ + nu_##t_)
+#define HJB_ROLLOUT_STAGE(LDS_, t_, c_, kn_, rd_, ut_)                                                                         \
+    if constexpr (LDS_) {                                                                                                      \
+        for (int stage_e_ = threadIdx.x; stage_e_ < nk_##t_; stage_e_ += blockDim.x) {                                         \
+            lds_##t_[stage_e_] = c_.knots[stage_e_];                                                                           \
+            lds_##t_[nk_##t_ + stage_e_] = c_.rdx[stage_e_];                                                                   \
+        }                                                                                                                      \
+        for (int stage_e_ = threadIdx.x; stage_e_ < nu_##t_; stage_e_ += blockDim.x)                                           \
+            lds_##t_[2 * nk_##t_ + stage_e_] = c_.u_table[stage_e_];                                                           \
+        kn_ = lds_##t_;                                                                                                        \
+        rd_ = lds_##t_ + nk_##t_;                                                                                              \
+        ut_ = lds_##t_ + 2 * nk_##t_;                                                                                          \
+    } else {                                                                                                                   \
+        kn_ = c_.knots;                                                                                                        \
+        rd_ = c_.rdx;                                                                                                          \
+        ut_ = c_.u_table;                                                                                                      \
+    }
+
+// One classical RK4 step of hs_ from x_ into xo_ (W_ doubles each; xo_ may be x_ itself), the ONE definition the rollout kernels
+// share.  RHS_(j, y, r) is a macro of the caller's that writes the right-hand side at the state y into r; j = 0..3 is the
+// evaluation (k1..k4), for a right-hand side that reads a table node per evaluation (K18).  One fixed operation order:
+// (r*hs)/2.0, acc + 2.0*r, (hs*(acc+r))/6.0.  A macro: as a force-inlined function taking a lambda the same operations come out
+// with the operands of some commutative instructions swapped - equal results, but not the code objects that were measured.
+// Its locals are rk_r_, rk_acc_, rk_xt_ and the loop variable rk_a_, inside its own block: no name of the caller's (x_, hs_, what
+// RHS_ reads) may be one of these four.
+#define HJB_ROLLOUT_RK4_STEP(W_, x_, xo_, hs_, RHS_)                                                                           \
+    {                                                                                                                          \
+        double rk_r_[W_], rk_acc_[W_], rk_xt_[W_];                                                                             \
+        RHS_(0, x_, rk_r_);                                       /* k1 */                                                     \
+        _Pragma("unroll") for (int rk_a_ = 0; rk_a_ < W_; ++rk_a_) {                                                           \
+            rk_acc_[rk_a_] = rk_r_[rk_a_];                                                                                     \
+            rk_xt_[rk_a_] = x_[rk_a_] + (rk_r_[rk_a_] * hs_) / 2.0;                                                            \
+        }                                                                                                                      \
+        RHS_(1, rk_xt_, rk_r_);                                   /* k2 */                                                     \
+        _Pragma("unroll") for (int rk_a_ = 0; rk_a_ < W_; ++rk_a_) {                                                           \
+            rk_acc_[rk_a_] = rk_acc_[rk_a_] + 2.0 * rk_r_[rk_a_];                                                              \
+            rk_xt_[rk_a_] = x_[rk_a_] + (rk_r_[rk_a_] * hs_) / 2.0;                                                            \
+        }                                                                                                                      \
+        RHS_(2, rk_xt_, rk_r_);                                   /* k3 */                                                     \
+        _Pragma("unroll") for (int rk_a_ = 0; rk_a_ < W_; ++rk_a_) {                                                           \
+            rk_acc_[rk_a_] = rk_acc_[rk_a_] + 2.0 * rk_r_[rk_a_];                                                              \
+            rk_xt_[rk_a_] = x_[rk_a_] + rk_r_[rk_a_] * hs_;                                                                    \
+        }                                                                                                                      \
+        RHS_(3, rk_xt_, rk_r_);                                   /* k4 */                                                     \
+        _Pragma("unroll") for (int rk_a_ = 0; rk_a_ < W_; ++rk_a_)                                                             \
+            xo_[rk_a_] = x_[rk_a_] + (hs_ * (rk_acc_[rk_a_] + rk_r_[rk_a_])) / 6.0;                                            \
+    }
+
 template <int D, typename TL, int METHOD, bool LDS>
 __global__ void __launch_bounds__(256)
 k_rollout(const DRollout R, int64_t nc, const double *__restrict__ X0, double *__restrict__ Xf, double *__restrict__ cost,
           double *__restrict__ Xp, double *__restrict__ Up) {
     extern __shared__ double smem[];
     const double *kn, *rd, *ut;
-    if constexpr (LDS) {
-        const int nk = R.n_knots, nut = R.n_labels * R.n_u;
-        for (int e = threadIdx.x; e < nk; e += blockDim.x) {
-            smem[e] = R.knots[e];
-            smem[nk + e] = R.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nut; e += blockDim.x) smem[2 * nk + e] = R.u_table[e];
-        __syncthreads();
-        kn = smem;
-        rd = smem + nk;
-        ut = smem + 2 * nk;
-    } else {
-        kn = R.knots;
-        rd = R.rdx;
-        ut = R.u_table;
-    }
+    HJB_ROLLOUT_PLACE(p, R, R.n_u, smem)
+    HJB_ROLLOUT_STAGE(LDS, p, R, kn, rd, ut)
+    if constexpr (LDS) __syncthreads();
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= nc) return;
     const TL *__restrict__ lab = static_cast<const TL *>(R.labels);

@@ -138,22 +138,9 @@ k_rollout_attitude(const DRollout R, const DAttitude M, int64_t nc, const double
                    double *__restrict__ cost, double *__restrict__ Xp, double *__restrict__ Up, double *__restrict__ Ap) {
     extern __shared__ double smem[];
     const double *kn, *rd, *ut;
-    if constexpr (LDS) {
-        const int nk = R.n_knots, nut = R.n_labels * HJB_ATT_U;
-        for (int e = threadIdx.x; e < nk; e += blockDim.x) {
-            smem[e] = R.knots[e];
-            smem[nk + e] = R.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nut; e += blockDim.x) smem[2 * nk + e] = R.u_table[e];
-        __syncthreads();
-        kn = smem;
-        rd = smem + nk;
-        ut = smem + 2 * nk;
-    } else {
-        kn = R.knots;
-        rd = R.rdx;
-        ut = R.u_table;
-    }
+    HJB_ROLLOUT_PLACE(p, R, HJB_ATT_U, smem)
+    HJB_ROLLOUT_STAGE(LDS, p, R, kn, rd, ut)
+    if constexpr (LDS) __syncthreads();
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= nc) return;
     const TL *__restrict__ lab = static_cast<const TL *>(R.labels);
@@ -184,33 +171,16 @@ k_rollout_attitude(const DRollout R, const DAttitude M, int64_t nc, const double
 #pragma unroll
         for (int j = 0; j < HJB_ATT_U; ++j) g = g + M.r[j] * (u[j] * u[j]);
         J = J + g;
-        double f[HJB_ATT_W], xn[HJB_ATT_W];
-        attitude_rates(M, x, u, f);
+        double xn[HJB_ATT_W];
         if constexpr (INTEG == HJB_ATT_TAYLOR) {
+            double f[HJB_ATT_W];
+            attitude_rates(M, x, u, f);
 #pragma unroll
             for (int a = 0; a < HJB_ATT_W; ++a) xn[a] = x[a] + h * f[a];
         } else {
-            double acc[HJB_ATT_W], xt[HJB_ATT_W];
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) {
-                acc[a] = f[a];                                        // k1
-                xt[a] = x[a] + (f[a] * h) / 2.0;
-            }
-            attitude_rates(M, xt, u, f);                              // k2
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) {
-                acc[a] = acc[a] + 2.0 * f[a];
-                xt[a] = x[a] + (f[a] * h) / 2.0;
-            }
-            attitude_rates(M, xt, u, f);                              // k3
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) {
-                acc[a] = acc[a] + 2.0 * f[a];
-                xt[a] = x[a] + f[a] * h;
-            }
-            attitude_rates(M, xt, u, f);                              // k4
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) xn[a] = x[a] + (h * (acc[a] + f[a])) / 6.0;
+#define HJB_ATT_RHS(j_, y_, r_) attitude_rates(M, y_, u, r_)
+            HJB_ROLLOUT_RK4_STEP(HJB_ATT_W, x, xn, h, HJB_ATT_RHS)
+#undef HJB_ATT_RHS
         }
         const double nrm = __builtin_sqrt(((xn[3] * xn[3] + xn[4] * xn[4]) + xn[5] * xn[5]) + xn[6] * xn[6]);
 #pragma unroll

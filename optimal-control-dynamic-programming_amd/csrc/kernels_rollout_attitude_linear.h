@@ -88,33 +88,16 @@ k_rollout_attitude_linear(const DAttLinear M, int64_t nc, const double *__restri
 #pragma unroll
             for (int j = 0; j < HJB_ATT_U; ++j) Up[i + nc * (j + (int64_t)HJB_ATT_U * k)] = u[j];
         }
-        double f[HJB_ATT_W], xn[HJB_ATT_W];
-        attitude_rates(M.A, x, u, f);
+        double xn[HJB_ATT_W];
         if constexpr (INTEG == HJB_ATT_TAYLOR) {
+            double f[HJB_ATT_W];
+            attitude_rates(M.A, x, u, f);
 #pragma unroll
             for (int a = 0; a < HJB_ATT_W; ++a) xn[a] = x[a] + h * f[a];
         } else {
-            double acc[HJB_ATT_W], xt[HJB_ATT_W];
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) {
-                acc[a] = f[a];                                        // k1
-                xt[a] = x[a] + (f[a] * h) / 2.0;
-            }
-            attitude_rates(M.A, xt, u, f);                            // k2
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) {
-                acc[a] = acc[a] + 2.0 * f[a];
-                xt[a] = x[a] + (f[a] * h) / 2.0;
-            }
-            attitude_rates(M.A, xt, u, f);                            // k3
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) {
-                acc[a] = acc[a] + 2.0 * f[a];
-                xt[a] = x[a] + f[a] * h;
-            }
-            attitude_rates(M.A, xt, u, f);                            // k4
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) xn[a] = x[a] + (h * (acc[a] + f[a])) / 6.0;
+#define HJB_ATTL_RHS(j_, y_, r_) attitude_rates(M.A, y_, u, r_)
+            HJB_ROLLOUT_RK4_STEP(HJB_ATT_W, x, xn, h, HJB_ATTL_RHS)
+#undef HJB_ATTL_RHS
         }
         const double nrm = __builtin_sqrt(((xn[3] * xn[3] + xn[4] * xn[4]) + xn[5] * xn[5]) + xn[6] * xn[6]);
 #pragma unroll

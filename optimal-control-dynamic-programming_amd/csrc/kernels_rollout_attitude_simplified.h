@@ -61,47 +61,14 @@ k_rollout_attitude_simplified(const DPaChan C1, const DPaChan C2, const DPaChan 
                               double *__restrict__ Xp, double *__restrict__ Up, double *__restrict__ Ap) {
     extern __shared__ double smem[];
     const double *kn1, *rd1, *ut1, *kn2, *rd2, *ut2, *kn3, *rd3, *ut3;
-    if constexpr (LDS) {
-        // per channel [knots | 1/dx | u_table], 1 then 2 then 3
-        const int nk1 = C1.n_knots, nk2 = C2.n_knots, nk3 = C3.n_knots;
-        const int nu1 = C1.n_labels, nu2 = C2.n_labels, nu3 = C3.n_labels;
-        double *s1 = smem, *s2 = s1 + 2 * nk1 + nu1, *s3 = s2 + 2 * nk2 + nu2;
-        for (int e = threadIdx.x; e < nk1; e += blockDim.x) {
-            s1[e] = C1.knots[e];
-            s1[nk1 + e] = C1.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nu1; e += blockDim.x) s1[2 * nk1 + e] = C1.u_table[e];
-        for (int e = threadIdx.x; e < nk2; e += blockDim.x) {
-            s2[e] = C2.knots[e];
-            s2[nk2 + e] = C2.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nu2; e += blockDim.x) s2[2 * nk2 + e] = C2.u_table[e];
-        for (int e = threadIdx.x; e < nk3; e += blockDim.x) {
-            s3[e] = C3.knots[e];
-            s3[nk3 + e] = C3.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nu3; e += blockDim.x) s3[2 * nk3 + e] = C3.u_table[e];
-        __syncthreads();
-        kn1 = s1;
-        rd1 = s1 + nk1;
-        ut1 = s1 + 2 * nk1;
-        kn2 = s2;
-        rd2 = s2 + nk2;
-        ut2 = s2 + 2 * nk2;
-        kn3 = s3;
-        rd3 = s3 + nk3;
-        ut3 = s3 + 2 * nk3;
-    } else {
-        kn1 = C1.knots;
-        rd1 = C1.rdx;
-        ut1 = C1.u_table;
-        kn2 = C2.knots;
-        rd2 = C2.rdx;
-        ut2 = C2.u_table;
-        kn3 = C3.knots;
-        rd3 = C3.rdx;
-        ut3 = C3.u_table;
-    }
+    // per channel [knots | 1/dx | u_table], 1 then 2 then 3
+    HJB_ROLLOUT_PLACE(1, C1, 1, smem)
+    HJB_ROLLOUT_PLACE(2, C2, 1, HJB_ROLLOUT_PLACE_END(1))
+    HJB_ROLLOUT_PLACE(3, C3, 1, HJB_ROLLOUT_PLACE_END(2))
+    HJB_ROLLOUT_STAGE(LDS, 1, C1, kn1, rd1, ut1)
+    HJB_ROLLOUT_STAGE(LDS, 2, C2, kn2, rd2, ut2)
+    HJB_ROLLOUT_STAGE(LDS, 3, C3, kn3, rd3, ut3)
+    if constexpr (LDS) __syncthreads();
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= nc) return;
     const TL *__restrict__ lab1 = static_cast<const TL *>(C1.labels);
@@ -156,53 +123,15 @@ k_rollout_attitude_simplified(const DPaChan C1, const DPaChan C2, const DPaChan 
         if constexpr (DYN == HJB_ATTS_FULL) {
             const double hs = M.hs;
             for (int s = 0; s < M.substeps; ++s) {
-                double f[HJB_ATT_W], acc[HJB_ATT_W], xt[HJB_ATT_W];
-                atts_rates(M, u, x, f);                               // k1
-#pragma unroll
-                for (int a = 0; a < HJB_ATT_W; ++a) {
-                    acc[a] = f[a];
-                    xt[a] = x[a] + (f[a] * hs) / 2.0;
-                }
-                atts_rates(M, u, xt, f);                              // k2
-#pragma unroll
-                for (int a = 0; a < HJB_ATT_W; ++a) {
-                    acc[a] = acc[a] + 2.0 * f[a];
-                    xt[a] = x[a] + (f[a] * hs) / 2.0;
-                }
-                atts_rates(M, u, xt, f);                              // k3
-#pragma unroll
-                for (int a = 0; a < HJB_ATT_W; ++a) {
-                    acc[a] = acc[a] + 2.0 * f[a];
-                    xt[a] = x[a] + f[a] * hs;
-                }
-                atts_rates(M, u, xt, f);                              // k4
-#pragma unroll
-                for (int a = 0; a < HJB_ATT_W; ++a) x[a] = x[a] + (hs * (acc[a] + f[a])) / 6.0;
+#define HJB_ATTS_RHS(j_, y_, r_) atts_rates(M, u, y_, r_)
+                HJB_ROLLOUT_RK4_STEP(HJB_ATT_W, x, x, hs, HJB_ATTS_RHS)
+#undef HJB_ATTS_RHS
             }
         } else {
             const double h = M.A.h;
-            double f[HJB_ATT_W], acc[HJB_ATT_W], xt[HJB_ATT_W];
-            attitude_rates(M.A, x, u, f);                             // k1
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) {
-                acc[a] = f[a];
-                xt[a] = x[a] + (f[a] * h) / 2.0;
-            }
-            attitude_rates(M.A, xt, u, f);                            // k2
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) {
-                acc[a] = acc[a] + 2.0 * f[a];
-                xt[a] = x[a] + (f[a] * h) / 2.0;
-            }
-            attitude_rates(M.A, xt, u, f);                            // k3
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) {
-                acc[a] = acc[a] + 2.0 * f[a];
-                xt[a] = x[a] + f[a] * h;
-            }
-            attitude_rates(M.A, xt, u, f);                            // k4
-#pragma unroll
-            for (int a = 0; a < HJB_ATT_W; ++a) x[a] = x[a] + (h * (acc[a] + f[a])) / 6.0;
+#define HJB_ATTS_RHS(j_, y_, r_) attitude_rates(M.A, y_, u, r_)
+            HJB_ROLLOUT_RK4_STEP(HJB_ATT_W, x, x, h, HJB_ATTS_RHS)
+#undef HJB_ATTS_RHS
             const double nrm = __builtin_sqrt(((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]) + x[6] * x[6]);
 #pragma unroll
             for (int a = 3; a < HJB_ATT_W; ++a) x[a] = x[a] / nrm;

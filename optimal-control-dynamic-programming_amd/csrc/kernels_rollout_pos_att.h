@@ -18,7 +18,8 @@
 // Neither an RK4 temporary nor E is live across the lookups (E is formed again for the inverse).  Labels were range-checked by
 // hjb_rollout_create and find_cell clamps every query (NaN -> cell 0), so a state that leaves the grids or stops being finite
 // reads inside the label arrays.  The numpy restatement is tests/pos_att_rollout_refs.py, the scalar host loop
-// hjbdp/rollout.py::pos_att_optimal_path_fixed.
+// hjbdp/rollout.py::pos_att_optimal_path_fixed.  The stage itself is kernels_rollout_pos_att_body.inc, shared with K23
+// (kernels_rollout_pos_att_faults.h); this header keeps the structs, the helpers and the kernel's declaration.
 #pragma once
 #include "hjbdp_dev.h"
 #include "kernels_rollout.h"
@@ -122,165 +123,9 @@ template <typename TL, bool LDS>
 __global__ void __launch_bounds__(256)
 k_rollout_pos_att(const DPaChan CX, const DPaChan CY, const DPaChan CZ, const DPosAtt M, int64_t nc, const double *__restrict__ X0,
                   double *__restrict__ Xf, double *__restrict__ Xp, double *__restrict__ Fp, double *__restrict__ FMp) {
-    extern __shared__ double smem[];
-    const double *knx, *rdx_, *utx, *kny, *rdy, *uty, *knz, *rdz, *utz;
-    if constexpr (LDS) {
-        // per channel [knots | 1/dx | u_table], x then y then z
-        const int nkx = CX.n_knots, nky = CY.n_knots, nkz = CZ.n_knots;
-        const int nux = CX.n_labels * 4, nuy = CY.n_labels * 4, nuz = CZ.n_labels * 4;
-        double *sx = smem, *sy = sx + 2 * nkx + nux, *sz = sy + 2 * nky + nuy;
-        for (int e = threadIdx.x; e < nkx; e += blockDim.x) {
-            sx[e] = CX.knots[e];
-            sx[nkx + e] = CX.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nux; e += blockDim.x) sx[2 * nkx + e] = CX.u_table[e];
-        for (int e = threadIdx.x; e < nky; e += blockDim.x) {
-            sy[e] = CY.knots[e];
-            sy[nky + e] = CY.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nuy; e += blockDim.x) sy[2 * nky + e] = CY.u_table[e];
-        for (int e = threadIdx.x; e < nkz; e += blockDim.x) {
-            sz[e] = CZ.knots[e];
-            sz[nkz + e] = CZ.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nuz; e += blockDim.x) sz[2 * nkz + e] = CZ.u_table[e];
-        __syncthreads();
-        knx = sx;
-        rdx_ = sx + nkx;
-        utx = sx + 2 * nkx;
-        kny = sy;
-        rdy = sy + nky;
-        uty = sy + 2 * nky;
-        knz = sz;
-        rdz = sz + nkz;
-        utz = sz + 2 * nkz;
-    } else {
-        knx = CX.knots;
-        rdx_ = CX.rdx;
-        utx = CX.u_table;
-        kny = CY.knots;
-        rdy = CY.rdx;
-        uty = CY.u_table;
-        knz = CZ.knots;
-        rdz = CZ.rdx;
-        utz = CZ.u_table;
-    }
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i >= nc) return;
-    const TL *__restrict__ labx = static_cast<const TL *>(CX.labels);
-    const TL *__restrict__ laby = static_cast<const TL *>(CY.labels);
-    const TL *__restrict__ labz = static_cast<const TL *>(CZ.labels);
-    const int64_t nlx = CX.n_labels, nly = CY.n_labels, nlz = CZ.n_labels;
-    const double hs = M.hs;
-    const int S = M.substeps;
-    double x[HJB_PA_W];
-#pragma unroll
-    for (int a = 0; a < HJB_PA_W; ++a) x[a] = X0[a + (int64_t)HJB_PA_W * i];
-    if (Xp) {
-#pragma unroll
-        for (int a = 0; a < HJB_PA_W; ++a) Xp[i + nc * a] = x[a];
-    }
-    for (int k = 0; k < M.n_steps; ++k) {
-        double th[3], xb[3], vb[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double s = x[6 + j];
-            s = s > 1.0 ? 1.0 : s < -1.0 ? -1.0 : s;
-            th[j] = 2.0 * canon_asin(s);
-        }
-        {
-            double E[9], R[9];
-            pa_eci2body(x[6], x[7], x[8], x[9], E);
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) R[3 * r + c] = (E[3 * r] * M.RSW[c] + E[3 * r + 1] * M.RSW[3 + c]) + E[3 * r + 2] * M.RSW[6 + c];
-            }
-            pa_mul3(R, x[0], x[1], x[2], xb);
-            pa_mul3(R, x[3], x[4], x[5], vb);
-        }
-        double f[HJB_PA_F];
-        {
-            const double p[4] = {xb[0], vb[0], th[1], x[11]};
-            HJB_ROLLOUT_LOOKUP(4, 4, HJB_LOOKUP_NEAREST, CX, knx, rdx_, utx, labx, k, p, 4, nlx, u)
-            f[0] = u[0];
-            f[1] = u[1];
-            f[6] = u[2];
-            f[7] = u[3];
-        }
-        {
-            const double p[4] = {xb[1], vb[1], th[2], x[12]};
-            HJB_ROLLOUT_LOOKUP(4, 4, HJB_LOOKUP_NEAREST, CY, kny, rdy, uty, laby, k, p, 4, nly, u)
-            f[2] = u[0];
-            f[3] = u[1];
-            f[8] = u[2];
-            f[9] = u[3];
-        }
-        {
-            const double p[4] = {xb[2], vb[2], th[0], x[10]};
-            HJB_ROLLOUT_LOOKUP(4, 4, HJB_LOOKUP_NEAREST, CZ, knz, rdz, utz, labz, k, p, 4, nlz, u)
-            f[4] = u[0];
-            f[5] = u[1];
-            f[10] = u[2];
-            f[11] = u[3];
-        }
-        double um[3], acc3[3];
-        um[0] = (((f[4] - f[5]) + f[10]) - f[11]) * M.t_dist;
-        um[1] = (((f[0] - f[1]) + f[6]) - f[7]) * M.t_dist;
-        um[2] = (((f[2] - f[3]) + f[8]) - f[9]) * M.t_dist;
-        {
-            const double ab0 = (((f[0] + f[1]) + f[6]) + f[7]) / M.mass;
-            const double ab1 = (((f[2] + f[3]) + f[8]) + f[9]) / M.mass;
-            const double ab2 = (((f[4] + f[5]) + f[10]) + f[11]) / M.mass;
-            double E[9], Ei[9], ae[3];
-            pa_eci2body(x[6], x[7], x[8], x[9], E);
-            pa_inv3(E, Ei);
-            pa_mul3(Ei, ab0, ab1, ab2, ae);
-            pa_mul3(M.RSWinv, ae[0], ae[1], ae[2], acc3);
-        }
-        if (Fp) {
-#pragma unroll
-            for (int j = 0; j < HJB_PA_F; ++j) Fp[i + nc * (j + (int64_t)HJB_PA_F * k)] = f[j];
-        }
-        if (FMp) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                FMp[i + nc * (j + (int64_t)HJB_PA_FM * k)] = acc3[j];
-                FMp[i + nc * (3 + j + (int64_t)HJB_PA_FM * k)] = um[j];
-            }
-        }
-        for (int s = 0; s < S; ++s) {
-            const double *c = M.coef + 5 * (2 * ((int64_t)S * k + s));
-            double r[HJB_PA_W], acc[HJB_PA_W], xt[HJB_PA_W];
-            pa_rates(M, c, acc3, um, x, r);                           // k1
-#pragma unroll
-            for (int a = 0; a < HJB_PA_W; ++a) {
-                acc[a] = r[a];
-                xt[a] = x[a] + (r[a] * hs) / 2.0;
-            }
-            pa_rates(M, c + 5, acc3, um, xt, r);                      // k2
-#pragma unroll
-            for (int a = 0; a < HJB_PA_W; ++a) {
-                acc[a] = acc[a] + 2.0 * r[a];
-                xt[a] = x[a] + (r[a] * hs) / 2.0;
-            }
-            pa_rates(M, c + 5, acc3, um, xt, r);                      // k3
-#pragma unroll
-            for (int a = 0; a < HJB_PA_W; ++a) {
-                acc[a] = acc[a] + 2.0 * r[a];
-                xt[a] = x[a] + r[a] * hs;
-            }
-            pa_rates(M, c + 10, acc3, um, xt, r);                     // k4
-#pragma unroll
-            for (int a = 0; a < HJB_PA_W; ++a) x[a] = x[a] + (hs * (acc[a] + r[a])) / 6.0;
-        }
-        if (Xp) {
-#pragma unroll
-            for (int a = 0; a < HJB_PA_W; ++a) Xp[i + nc * (a + (int64_t)HJB_PA_W * (k + 1))] = x[a];
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < HJB_PA_W; ++a) Xf[a + (int64_t)HJB_PA_W * i] = x[a];
+#define HJB_PA_BODY_FAULTS 0
+#include "kernels_rollout_pos_att_body.inc"
+#undef HJB_PA_BODY_FAULTS
 }
 
 // rollout_pos_att.hip instantiates the 6 kernels (label type x LDS) and launches the one asked for

@@ -74,47 +74,14 @@ k_rollout_position(const DPaChan CX, const DPaChan CY, const DPaChan CZ, const D
     constexpr double EPS = 2.220446049250313e-16;
     extern __shared__ double smem[];
     const double *knx, *rdx_, *utx, *kny, *rdy, *uty, *knz, *rdz, *utz;
-    if constexpr (LDS) {
-        // per channel [knots | 1/dx | u_table], x then y then z
-        const int nkx = CX.n_knots, nky = CY.n_knots, nkz = CZ.n_knots;
-        const int nux = CX.n_labels, nuy = CY.n_labels, nuz = CZ.n_labels;
-        double *sx = smem, *sy = sx + 2 * nkx + nux, *sz = sy + 2 * nky + nuy;
-        for (int e = threadIdx.x; e < nkx; e += blockDim.x) {
-            sx[e] = CX.knots[e];
-            sx[nkx + e] = CX.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nux; e += blockDim.x) sx[2 * nkx + e] = CX.u_table[e];
-        for (int e = threadIdx.x; e < nky; e += blockDim.x) {
-            sy[e] = CY.knots[e];
-            sy[nky + e] = CY.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nuy; e += blockDim.x) sy[2 * nky + e] = CY.u_table[e];
-        for (int e = threadIdx.x; e < nkz; e += blockDim.x) {
-            sz[e] = CZ.knots[e];
-            sz[nkz + e] = CZ.rdx[e];
-        }
-        for (int e = threadIdx.x; e < nuz; e += blockDim.x) sz[2 * nkz + e] = CZ.u_table[e];
-        __syncthreads();
-        knx = sx;
-        rdx_ = sx + nkx;
-        utx = sx + 2 * nkx;
-        kny = sy;
-        rdy = sy + nky;
-        uty = sy + 2 * nky;
-        knz = sz;
-        rdz = sz + nkz;
-        utz = sz + 2 * nkz;
-    } else {
-        knx = CX.knots;
-        rdx_ = CX.rdx;
-        utx = CX.u_table;
-        kny = CY.knots;
-        rdy = CY.rdx;
-        uty = CY.u_table;
-        knz = CZ.knots;
-        rdz = CZ.rdx;
-        utz = CZ.u_table;
-    }
+    // per channel [knots | 1/dx | u_table], x then y then z
+    HJB_ROLLOUT_PLACE(x, CX, 1, smem)
+    HJB_ROLLOUT_PLACE(y, CY, 1, HJB_ROLLOUT_PLACE_END(x))
+    HJB_ROLLOUT_PLACE(z, CZ, 1, HJB_ROLLOUT_PLACE_END(y))
+    HJB_ROLLOUT_STAGE(LDS, x, CX, knx, rdx_, utx)
+    HJB_ROLLOUT_STAGE(LDS, y, CY, kny, rdy, uty)
+    HJB_ROLLOUT_STAGE(LDS, z, CZ, knz, rdz, utz)
+    if constexpr (LDS) __syncthreads();
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= nc) return;
     const TL *__restrict__ labx = static_cast<const TL *>(CX.labels);

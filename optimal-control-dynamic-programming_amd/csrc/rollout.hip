@@ -1,9 +1,13 @@
-// rollout.hip - hjb_rollout_*: batched closed-loop rollouts of a stored per-stage policy (include/hjbdp.h; kernels:
-// kernels_rollout.h for the affine model, kernels_rollout_attitude.h / rollout_attitude.hip for the attitude model,
-// kernels_rollout_pos_att.h / rollout_pos_att.hip for the pos-att model, kernels_rollout_position.h / rollout_position.hip for the
-// position model, kernels_rollout_pos_att_faults.h / rollout_pos_att_faults.hip for the pos-att model's fault campaigns,
-// kernels_rollout_attitude_simplified.h / rollout_attitude_simplified.hip for the simplified attitude model,
-// kernels_rollout_attitude_linear.h / rollout_attitude_linear.hip for the stateless linear attitude controller).
+// rollout.hip - hjb_rollout_* and hjb_attitude_linear_response: the host side of the batched closed-loop rollouts
+// (include/hjbdp.h).  An object holds one stored policy (hjb_rollout_create) and one model, the last one set:
+//   affine (K16, kernels_rollout.h, launched from this unit), attitude (K17, kernels_rollout_attitude.h / rollout_attitude.hip),
+//   and the three that attach two more objects' policies as channels: pos-att (K18, kernels_rollout_pos_att.h /
+//   rollout_pos_att.hip; its fault campaigns K23, kernels_rollout_pos_att_faults.h / rollout_pos_att_faults.hip), position (K19,
+//   kernels_rollout_position.h / rollout_position.hip), simplified attitude (K20, kernels_rollout_attitude_simplified.h /
+//   rollout_attitude_simplified.hip).
+// The linear attitude controller (K21, kernels_rollout_attitude_linear.h / rollout_attitude_linear.hip) needs no object.
+// Shared here: the attached-channels record and attach_channels (the three attaching setters), check_run / check_traj /
+// check_quaternions (the run functions' refusals, all before any device work), lds_bytes, run_chunks (the chunk loop).
 #include "hjbdp_host.h"
 #include "kernels_rollout.h"
 #include "kernels_rollout_attitude.h"
@@ -12,13 +16,15 @@
 #include "kernels_rollout_position.h"
 #include "kernels_rollout_attitude_simplified.h"
 #include "kernels_rollout_attitude_linear.h"
+#include "rollout_dispatch.h"
 #include <memory>
 
 using namespace hjbhost;
 
 namespace {
 
-enum { kModelNone = 0, kModelAffine = 1, kModelAttitude = 2, kModelPosAtt = 3, kModelPosition = 4, kModelAttSimplified = 5 };    // the last setter called wins
+// the model an object holds: the last setter called wins.  The last three keep an Attached record in Rollout::att, the others none
+enum { kModelNone = 0, kModelAffine = 1, kModelAttitude = 2, kModelPosAtt = 3, kModelPosition = 4, kModelAttSimplified = 5 };
 
 // Device allocations with shared ownership: an object's grid, table and labels live as long as the object or a pos-att, position
 // or simplified attitude model that reads them (hjb_rollout_set_pos_att_model / hjb_rollout_set_position_model /
@@ -34,12 +40,19 @@ struct DevData {
     }
 };
 
-// The pos-att model of channel x's object: the y and z channels' descriptors with their device data kept alive, the constants
-struct PosAtt {
-    DPaChan cy{}, cz{};
-    std::shared_ptr<DevData> data_y, data_z, coef;
-    DPosAtt M{};
+// What a model of three channels holds of the two other objects (y and z, or 2 and 3): their policies' descriptors, with the
+// device data kept alive.  The model's own members sit on top (PosAtt, Position, AttSimplified).
+struct Attached {
+    DPaChan c[2]{};
+    std::shared_ptr<DevData> data[2];
     int n_planes = 0;               // of the three channels, the fewest
+    virtual ~Attached() = default;
+};
+
+// The pos-att model of channel x's object
+struct PosAtt : Attached {
+    std::shared_ptr<DevData> coef;
+    DPosAtt M{};
     int max_steps = 0;              // (n_nodes - 1) / (2 substeps)
     double h = 0;                   // as given (M.hs is h / substeps)
     // the fault controller of channel x (hjb_rollout_set_pos_att_fault_controller): read by hjb_rollout_run_pos_att_faults alone
@@ -49,22 +62,17 @@ struct PosAtt {
     int planes_xf = 0;
 };
 
-// The position model of channel x's object: the y and z channels' descriptors with their device data kept alive, the RKF45 table
-struct Position {
-    DPaChan cy{}, cz{};
-    std::shared_ptr<DevData> data_y, data_z, table;     // table: n_sub and the sub-step rows
+// The position model of channel x's object
+struct Position : Attached {
+    std::shared_ptr<DevData> table;     // n_sub and the sub-step rows
     DPosition M{};
-    int n_planes = 0;               // of the three channels, the fewest
     int max_steps = 0;              // stages the table holds
 };
 
-// The simplified attitude model of channel 1's object: channels 2 and 3's descriptors with their device data kept alive, the constants
-struct AttSimplified {
-    DPaChan c2{}, c3{};
-    std::shared_ptr<DevData> data_2, data_3;
+// The simplified attitude model of channel 1's object
+struct AttSimplified : Attached {
     DAttSimplified M{};
     int dynamics = HJB_ATTS_FULL;
-    int n_planes = 0;               // of the three channels, the fewest
 };
 
 struct Rollout {
@@ -75,9 +83,7 @@ struct Rollout {
     bool lds = true;                // option "lds": stage the tables in LDS when they fit (false: never)
     DRollout R{};                   // device pointers filled by create; model by set_model
     DAttitude M{};                  // the attitude model (set_attitude_model)
-    std::unique_ptr<PosAtt> pa;     // the pos-att model (set_pos_att_model)
-    std::unique_ptr<Position> ps;   // the position model (set_position_model)
-    std::unique_ptr<AttSimplified> as;   // the simplified attitude model (set_attitude_simplified_model)
+    std::unique_ptr<Attached> att;  // the PosAtt / Position / AttSimplified of model kModelPosAtt / kModelPosition / kModelAttSimplified
     std::shared_ptr<DevData> data;
     hipStream_t stream = nullptr;
     std::string err;
@@ -98,9 +104,7 @@ int rfail(Rollout *ro, int code, const char *fmt, ...) {
 }
 
 void release(Rollout *ro) {
-    ro->pa.reset();
-    ro->ps.reset();
-    ro->as.reset();
+    ro->att.reset();
     ro->data.reset();
     if (ro->stream) (void)hipStreamDestroy(ro->stream);
     ro->stream = nullptr;
@@ -114,71 +118,82 @@ int64_t first_bad_label(const void *labels, int64_t count, int64_t lo, int64_t h
     return -1;
 }
 
-template <int D, typename TL, int M, bool LDS>
-void launch_d(const DRollout &R, int64_t nc, size_t lds, hipStream_t st, const double *X0, double *Xf, double *cost, double *Xp,
-              double *Up) {
-    dim3 b(256), g((unsigned)((nc + 255) / 256));
-    hipLaunchKernelGGL((k_rollout<D, TL, M, LDS>), g, b, LDS ? lds : 0, st, R, nc, X0, Xf, cost, Xp, Up);
-}
-
-template <typename TL, int M, bool LDS>
-void launch_t(int D, const DRollout &R, int64_t nc, size_t lds, hipStream_t st, const double *X0, double *Xf, double *cost,
-              double *Xp, double *Up) {
-    switch (D) {
-        case 1: launch_d<1, TL, M, LDS>(R, nc, lds, st, X0, Xf, cost, Xp, Up); break;
-        case 2: launch_d<2, TL, M, LDS>(R, nc, lds, st, X0, Xf, cost, Xp, Up); break;
-        case 3: launch_d<3, TL, M, LDS>(R, nc, lds, st, X0, Xf, cost, Xp, Up); break;
-        case 4: launch_d<4, TL, M, LDS>(R, nc, lds, st, X0, Xf, cost, Xp, Up); break;
-        case 5: launch_d<5, TL, M, LDS>(R, nc, lds, st, X0, Xf, cost, Xp, Up); break;
-        default: launch_d<6, TL, M, LDS>(R, nc, lds, st, X0, Xf, cost, Xp, Up); break;
-    }
-}
-
-template <typename TL>
-void launch_m(int D, int method, bool lds_on, const DRollout &R, int64_t nc, size_t lds, hipStream_t st, const double *X0,
-              double *Xf, double *cost, double *Xp, double *Up) {
-    if (method == HJB_LOOKUP_NEAREST) {
-        if (lds_on) launch_t<TL, HJB_LOOKUP_NEAREST, true>(D, R, nc, lds, st, X0, Xf, cost, Xp, Up);
-        else launch_t<TL, HJB_LOOKUP_NEAREST, false>(D, R, nc, lds, st, X0, Xf, cost, Xp, Up);
-    } else {
-        if (lds_on) launch_t<TL, HJB_LOOKUP_LINEAR, true>(D, R, nc, lds, st, X0, Xf, cost, Xp, Up);
-        else launch_t<TL, HJB_LOOKUP_LINEAR, false>(D, R, nc, lds, st, X0, Xf, cost, Xp, Up);
-    }
+// K16's 72 instantiations (label type x method x LDS x D) and the launch of the one asked for
+hipError_t launch_rollout(int idx_bytes, int method, bool lds_on, int D, const DRollout &R, int64_t nc, size_t lds, hipStream_t st,
+                          const double *X0, double *Xf, double *cost, double *Xp, double *Up) {
+    const dim3 b(256), g((unsigned)((nc + 255) / 256));
+    with_label_type(idx_bytes, [&](auto tl) {
+        with_int<HJB_LOOKUP_NEAREST, HJB_LOOKUP_LINEAR>(method, [&](auto m) {
+            with_bool(lds_on, [&](auto l) {
+                with_dim(D, [&](auto d) {
+                    using TL = typename decltype(tl)::type;
+                    constexpr bool LDS = decltype(l)::value;
+                    hipLaunchKernelGGL((k_rollout<decltype(d)::value, TL, decltype(m)::value, LDS>), g, b, LDS ? lds : 0, st, R, nc, X0,
+                                       Xf, cost, Xp, Up);
+                });
+            });
+        });
+    });
+    return hipGetLastError();
 }
 
 bool all_finite(const double *p, int64_t n) { return !p || first_nonfinite(p, n, true) < 0; }
 
-// The argument checks both run functions make before any device work: method, sizes, that the object holds the model this
-// entry point runs (`want`), plane_of_step.
+// The argument checks every run function of an object makes before any device work: method, sizes, that the object holds the
+// model this entry point runs (`want`), plane_of_step against the planes all of the model's channels have.
 int check_run(Rollout *ro, int want, int method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj) {
     if (method != HJB_LOOKUP_NEAREST && method != HJB_LOOKUP_LINEAR) return rfail(ro, HJB_E_INVALID, "rollout: method %d", method);
     if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
     if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
-    static const char *const setter[] = {"", "hjb_rollout_set_model", "hjb_rollout_set_attitude_model", "hjb_rollout_set_pos_att_model",
-                                         "hjb_rollout_set_position_model", "hjb_rollout_set_attitude_simplified_model"};
-    static const char *const runner[] = {"", "hjb_rollout_run", "hjb_rollout_run_attitude", "hjb_rollout_run_pos_att",
-                                         "hjb_rollout_run_position", "hjb_rollout_run_attitude_simplified"};
-    static const char *const held[] = {"", "affine", "attitude", "pos-att", "position", "simplified attitude"};
-    if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: run before %s", setter[want]);
+    static const struct { const char *held, *setter, *runner; } names[] = {
+        {"", "", ""},
+        {"affine", "hjb_rollout_set_model", "hjb_rollout_run"},
+        {"attitude", "hjb_rollout_set_attitude_model", "hjb_rollout_run_attitude"},
+        {"pos-att", "hjb_rollout_set_pos_att_model", "hjb_rollout_run_pos_att"},
+        {"position", "hjb_rollout_set_position_model", "hjb_rollout_run_position"},
+        {"simplified attitude", "hjb_rollout_set_attitude_simplified_model", "hjb_rollout_run_attitude_simplified"}};
+    if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: run before %s", names[want].setter);
     if (ro->model != want)
-        return rfail(ro, HJB_E_INVALID, "rollout: the object holds the %s model (%s): call %s", held[ro->model], setter[ro->model],
-                     runner[ro->model]);
+        return rfail(ro, HJB_E_INVALID, "rollout: the object holds the %s model (%s): call %s", names[ro->model].held,
+                     names[ro->model].setter, names[ro->model].runner);
     if (n_steps > 0 && !plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null plane_of_step");
-    const int n_planes = want == kModelPosAtt ? ro->pa->n_planes : want == kModelPosition ? ro->ps->n_planes
-                       : want == kModelAttSimplified ? ro->as->n_planes : ro->n_planes;
+    // att is set exactly while the model is one of the three attaching ones: their setters install it with the model
+    // (install_attached), every other setter ends in drop_attached.  A new setter has to do one or the other.
+    const int n_planes = ro->att ? ro->att->n_planes : ro->n_planes;
     for (int k = 0; k < n_steps; ++k)
         if (plane_of_step[k] < 0 || plane_of_step[k] >= n_planes)
             return rfail(ro, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d)", k, plane_of_step[k], n_planes);
     return HJB_OK;
 }
 
+// The checks on the trajectories every run function makes next (pre: "rollout", or the entry point's name where there is no
+// object): null X0 / X_final, the sizes of W doubles per trajectory and stage (wname: how the message spells W), a finite X0.
+int check_traj(Rollout *ro, const char *pre, int W, const char *wname, int32_t n_steps, int64_t n_traj, const double *X0,
+               const double *X_final) {
+    if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "%s: null X0 / X_final", pre);
+    if (n_traj > INT64_MAX / (W * ((int64_t)n_steps + 1)) / 8)
+        return rfail(ro, HJB_E_INVALID, "%s: size overflow (n_traj x %s x n_steps)", pre, wname);
+    const int64_t bad = first_nonfinite(X0, (int64_t)W * n_traj, true);
+    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "%s: X0 element %lld is not finite", pre, (long long)bad);
+    return HJB_OK;
+}
+
+// K17 and K21 renormalise the quaternion X0[3..6] of a 7-state column after the first step: all zeros would be 0/0
+int check_quaternions(Rollout *ro, const char *pre, int64_t n_traj, const double *X0) {
+    for (int64_t i = 0; i < n_traj; ++i) {
+        const double *q = X0 + HJB_ATT_W * i + 3;
+        if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)
+            return rfail(ro, HJB_E_INVALID, "%s: X0 column %lld has an all-zero quaternion (0/0 at the first renormalisation)", pre,
+                         (long long)i);
+    }
+    return HJB_OK;
+}
+
 // a pos-att, position or simplified attitude model goes, and with it its hold on the other two channels
 void drop_attached(Rollout *ro) {
-    if (!ro->pa && !ro->ps && !ro->as) return;
+    if (!ro->att) return;
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-    ro->pa.reset();
-    ro->ps.reset();
-    ro->as.reset();
+    ro->att.reset();
 }
 
 // what K18, K19 and K20 read of an object's policy (kernels_rollout_pos_att.h)
@@ -201,6 +216,89 @@ DPaChan pa_channel(const DRollout &R) {
     c.u_table = R.u_table;
     c.labels = R.labels;
     return c;
+}
+
+DPaChan on_planes(DPaChan c, const int32_t *plane_of_step) {
+    c.plane_of_step = plane_of_step;
+    return c;
+}
+
+// the LDS bytes of the channels' [knots | 1/dx | u_table], `width` u_table doubles per label
+size_t lds_bytes(std::initializer_list<const DPaChan *> chans, int width) {
+    int64_t nk = 0, nl = 0;
+    for (const DPaChan *c : chans) {
+        nk += c->n_knots;
+        nl += c->n_labels;
+    }
+    return (size_t)(2 * nk + width * nl) * sizeof(double);
+}
+
+// Another object's policy as a channel: a snapshot with a share of its device data, taken under that object's own lock
+struct ChanSnap {
+    DPaChan c{};
+    std::shared_ptr<DevData> data;
+    int D = 0, n_u = 0, device = 0, idx_bytes = 0, n_planes = 0;
+};
+
+ChanSnap snap_channel(Rollout *o) {
+    std::lock_guard<std::mutex> g(o->mu);
+    ChanSnap s;
+    s.c = pa_channel(o->R);
+    s.data = o->data;
+    s.D = o->D;
+    s.n_u = o->R.n_u;
+    s.device = o->device;
+    s.idx_bytes = o->idx_bytes;
+    s.n_planes = o->n_planes;
+    return s;
+}
+
+// a snapshot against the object rx it is attached to (under rx's lock): one device, one label type
+int check_channel(Rollout *rx, const ChanSnap &s, const char *name, const char *rx_name, const char *sharers) {
+    if (s.device != rx->device)
+        return rfail(rx, HJB_E_INVALID, "rollout: %s is on device %d, %s on device %d", name, s.device, rx_name, rx->device);
+    if (s.idx_bytes != rx->idx_bytes)
+        return rfail(rx, HJB_E_INVALID, "rollout: %s has %d-byte labels, %s %d-byte labels (the %s share one label type)", name,
+                     s.idx_bytes, rx_name, rx->idx_bytes, sharers);
+    return HJB_OK;
+}
+
+// What the setters of a three-channel model share.  rs: the three objects, names: their handles' names in the messages, model:
+// the model's name there; every channel needs D == D and n_u == n_u.  Snapshots the two other channels under their own locks
+// (in order), then takes rs[0]'s lock into lk - the caller holds it to its end - and checks the three against each other;
+// at gets the snapshots and the fewest planes.  On a refusal the snapshots' shares of the other objects' device data go with
+// this frame, under rs[0]'s lock when it was taken and without g_capture_mu: a share frees device memory only as the last owner,
+// that is when the other object was destroyed in between (a refused setter of the earlier form freed the same way).
+int attach_channels(Rollout *const (&rs)[3], const char *const (&names)[3], const char *model, int D, int n_u, Attached &at,
+                    std::unique_lock<std::mutex> &lk) {
+    Rollout *rx = rs[0];
+    if (!rs[0] || !rs[1] || !rs[2]) return rfail(rx, HJB_E_INVALID, "rollout: null handle (three channel objects are required)");
+    if (rs[0] == rs[1] || rs[0] == rs[2] || rs[1] == rs[2]) return rfail(rx, HJB_E_INVALID, "rollout: the same object passed for two channels");
+    const char *const needs = "rollout: the %s model needs D == %d and n_u == %d (%s: D=%d, n_u=%d)";
+    ChanSnap sn[2];
+    for (int t = 0; t < 2; ++t) {
+        sn[t] = snap_channel(rs[1 + t]);
+        if (sn[t].D != D || sn[t].n_u != n_u) return rfail(rx, HJB_E_INVALID, needs, model, D, n_u, names[1 + t], sn[t].D, sn[t].n_u);
+    }
+    lk = std::unique_lock<std::mutex>(rx->mu);
+    if (rx->D != D || rx->R.n_u != n_u) return rfail(rx, HJB_E_INVALID, needs, model, D, n_u, names[0], rx->D, rx->R.n_u);
+    for (int t = 0; t < 2; ++t) {
+        const int bad = check_channel(rx, sn[t], names[1 + t], names[0], "three channels");
+        if (bad) return bad;
+    }
+    at.n_planes = std::min(rx->n_planes, std::min(sn[0].n_planes, sn[1].n_planes));
+    for (int t = 0; t < 2; ++t) {
+        at.c[t] = sn[t].c;
+        at.data[t] = std::move(sn[t].data);
+    }
+    return HJB_OK;
+}
+
+// under rx's lock and g_capture_mu, on rx's device: the model takes the place of (and releases) whatever was attached
+void install_attached(Rollout *rx, std::unique_ptr<Attached> at, int model) {
+    if (rx->stream) (void)hipStreamSynchronize(rx->stream);
+    rx->att = std::move(at);
+    rx->model = model;
 }
 
 // The chunk loop the run functions share: W doubles of state per trajectory; per step n_up control rows (U_path) and n_e more
@@ -507,38 +605,13 @@ int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *ro
     M.t_dist = t_dist;
     M.hs = h / substeps;
     M.substeps = substeps;
-    if (!rx || !ry || !rz) return rfail(rx, HJB_E_INVALID, "rollout: null handle (three channel objects are required)");
-    if (rx == ry || rx == rz || ry == rz) return rfail(rx, HJB_E_INVALID, "rollout: the same object passed for two channels");
     auto pa = std::make_unique<PosAtt>();
     pa->M = M;
     pa->h = h;
     pa->max_steps = (int)((n_nodes - 1) / (2 * (int64_t)substeps));
-    // y and z: a snapshot of the policy with a share of its device data, taken under that object's own lock
-    int dev_o[2] = {0, 0}, idx_o[2] = {0, 0}, planes_o[2] = {0, 0};
-    Rollout *others[2] = {ry, rz};
-    const char *names[2] = {"rollout_y", "rollout_z"};
-    for (int t = 0; t < 2; ++t) {
-        Rollout *o = others[t];
-        std::lock_guard<std::mutex> g(o->mu);
-        if (o->D != 4 || o->R.n_u != 4)
-            return rfail(rx, HJB_E_INVALID, "rollout: the pos-att model needs D == 4 and n_u == 4 (%s: D=%d, n_u=%d)", names[t], o->D, o->R.n_u);
-        (t == 0 ? pa->cy : pa->cz) = pa_channel(o->R);
-        (t == 0 ? pa->data_y : pa->data_z) = o->data;
-        dev_o[t] = o->device;
-        idx_o[t] = o->idx_bytes;
-        planes_o[t] = o->n_planes;
-    }
-    std::lock_guard<std::mutex> g(rx->mu);
-    if (rx->D != 4 || rx->R.n_u != 4)
-        return rfail(rx, HJB_E_INVALID, "rollout: the pos-att model needs D == 4 and n_u == 4 (rollout_x: D=%d, n_u=%d)", rx->D, rx->R.n_u);
-    for (int t = 0; t < 2; ++t) {
-        if (dev_o[t] != rx->device)
-            return rfail(rx, HJB_E_INVALID, "rollout: %s is on device %d, rollout_x on device %d", names[t], dev_o[t], rx->device);
-        if (idx_o[t] != rx->idx_bytes)
-            return rfail(rx, HJB_E_INVALID, "rollout: %s has %d-byte labels, rollout_x %d-byte labels (the three channels share one label type)",
-                         names[t], idx_o[t], rx->idx_bytes);
-    }
-    pa->n_planes = std::min(rx->n_planes, std::min(planes_o[0], planes_o[1]));
+    std::unique_lock<std::mutex> g;
+    const int bad_chan = attach_channels({rx, ry, rz}, {"rollout_x", "rollout_y", "rollout_z"}, "pos-att", 4, 4, *pa, g);
+    if (bad_chan) return bad_chan;
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(rx->device) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "hipSetDevice failed");
     pa->coef = std::make_shared<DevData>();
@@ -549,11 +622,7 @@ int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *ro
     pa->coef->allocs.push_back(d);
     if (hipMemcpy(d, orbit_coef, cb, hipMemcpyHostToDevice) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "rollout: upload failed");
     pa->M.coef = (const double *)d;
-    if (rx->stream) (void)hipStreamSynchronize(rx->stream);
-    rx->pa = std::move(pa);                                 // replaces (and releases) a model set earlier
-    rx->ps.reset();
-    rx->as.reset();
-    rx->model = kModelPosAtt;
+    install_attached(rx, std::move(pa), kModelPosAtt);
     return HJB_OK;
 }
 
@@ -561,40 +630,26 @@ int32_t hjb_rollout_set_pos_att_fault_controller(void *rollout_x, void *rollout_
     Rollout *rx = (Rollout *)rollout_x, *rf = (Rollout *)rollout_xf;
     if (!rx) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
     if (rx == rf) return rfail(rx, HJB_E_INVALID, "rollout: the same object passed as channel x and as its fault controller");
-    // the fault controller: a snapshot of the policy with a share of its device data, taken under that object's own lock
-    DPaChan cxf{};
-    std::shared_ptr<DevData> data_xf;
-    int dev_f = 0, idx_f = 0, planes_f = 0, D_f = 0, nu_f = 0;
-    if (rf) {
-        std::lock_guard<std::mutex> g(rf->mu);
-        D_f = rf->D;
-        nu_f = rf->R.n_u;
-        cxf = pa_channel(rf->R);
-        data_xf = rf->data;
-        dev_f = rf->device;
-        idx_f = rf->idx_bytes;
-        planes_f = rf->n_planes;
-    }
+    // the fault controller's snapshot first (its own lock), then channel x's lock
+    ChanSnap sf;
+    if (rf) sf = snap_channel(rf);
     std::lock_guard<std::mutex> g(rx->mu);
-    if (rx->model != kModelPosAtt || !rx->pa)
+    if (rx->model != kModelPosAtt || !rx->att)
         return rfail(rx, HJB_E_INVALID, "rollout: the fault controller attaches to the pos-att model: call hjb_rollout_set_pos_att_model first");
     if (rf) {
-        if (D_f != 4 || nu_f != 4)
-            return rfail(rx, HJB_E_INVALID, "rollout: the fault controller needs D == 4 and n_u == 4 (rollout_xf: D=%d, n_u=%d)", D_f, nu_f);
-        if (dev_f != rx->device)
-            return rfail(rx, HJB_E_INVALID, "rollout: rollout_xf is on device %d, rollout_x on device %d", dev_f, rx->device);
-        if (idx_f != rx->idx_bytes)
-            return rfail(rx, HJB_E_INVALID, "rollout: rollout_xf has %d-byte labels, rollout_x %d-byte labels (the four controllers share one label type)",
-                         idx_f, rx->idx_bytes);
+        if (sf.D != 4 || sf.n_u != 4)
+            return rfail(rx, HJB_E_INVALID, "rollout: the fault controller needs D == 4 and n_u == 4 (rollout_xf: D=%d, n_u=%d)", sf.D, sf.n_u);
+        const int bad = check_channel(rx, sf, "rollout_xf", "rollout_x", "four controllers");
+        if (bad) return bad;
     }
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(rx->device) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "hipSetDevice failed");
     if (rx->stream) (void)hipStreamSynchronize(rx->stream);
-    PosAtt &pa = *rx->pa;
+    PosAtt &pa = static_cast<PosAtt &>(*rx->att);
     pa.has_xf = rf != nullptr;
-    pa.cxf = cxf;
-    pa.data_xf = std::move(data_xf);                        // replaces (and releases) a fault controller attached earlier
-    pa.planes_xf = planes_f;
+    pa.cxf = sf.c;
+    pa.data_xf = std::move(sf.data);                        // replaces (and releases) a fault controller attached earlier
+    pa.planes_xf = sf.n_planes;
     return HJB_OK;
 }
 
@@ -613,38 +668,13 @@ int32_t hjb_rollout_set_position_model(void *rollout_x, void *rollout_y, void *r
     const int64_t n_tab = (int64_t)HJB_POS_ROW * max_sub * n_steps;
     const int64_t bad = first_nonfinite(table, n_tab, true);
     if (bad >= 0) return rfail(rx, HJB_E_INVALID, "rollout: table element %lld is not finite", (long long)bad);
-    if (!rx || !ry || !rz) return rfail(rx, HJB_E_INVALID, "rollout: null handle (three channel objects are required)");
-    if (rx == ry || rx == rz || ry == rz) return rfail(rx, HJB_E_INVALID, "rollout: the same object passed for two channels");
     auto ps = std::make_unique<Position>();
     ps->M.tol = tol;
     ps->M.max_sub = max_sub;
     ps->max_steps = n_steps;
-    // y and z: a snapshot of the policy with a share of its device data, taken under that object's own lock
-    int dev_o[2] = {0, 0}, idx_o[2] = {0, 0}, planes_o[2] = {0, 0};
-    Rollout *others[2] = {ry, rz};
-    const char *names[2] = {"rollout_y", "rollout_z"};
-    for (int t = 0; t < 2; ++t) {
-        Rollout *o = others[t];
-        std::lock_guard<std::mutex> g(o->mu);
-        if (o->D != 2 || o->R.n_u != 1)
-            return rfail(rx, HJB_E_INVALID, "rollout: the position model needs D == 2 and n_u == 1 (%s: D=%d, n_u=%d)", names[t], o->D, o->R.n_u);
-        (t == 0 ? ps->cy : ps->cz) = pa_channel(o->R);
-        (t == 0 ? ps->data_y : ps->data_z) = o->data;
-        dev_o[t] = o->device;
-        idx_o[t] = o->idx_bytes;
-        planes_o[t] = o->n_planes;
-    }
-    std::lock_guard<std::mutex> g(rx->mu);
-    if (rx->D != 2 || rx->R.n_u != 1)
-        return rfail(rx, HJB_E_INVALID, "rollout: the position model needs D == 2 and n_u == 1 (rollout_x: D=%d, n_u=%d)", rx->D, rx->R.n_u);
-    for (int t = 0; t < 2; ++t) {
-        if (dev_o[t] != rx->device)
-            return rfail(rx, HJB_E_INVALID, "rollout: %s is on device %d, rollout_x on device %d", names[t], dev_o[t], rx->device);
-        if (idx_o[t] != rx->idx_bytes)
-            return rfail(rx, HJB_E_INVALID, "rollout: %s has %d-byte labels, rollout_x %d-byte labels (the three channels share one label type)",
-                         names[t], idx_o[t], rx->idx_bytes);
-    }
-    ps->n_planes = std::min(rx->n_planes, std::min(planes_o[0], planes_o[1]));
+    std::unique_lock<std::mutex> g;
+    const int bad_chan = attach_channels({rx, ry, rz}, {"rollout_x", "rollout_y", "rollout_z"}, "position", 2, 1, *ps, g);
+    if (bad_chan) return bad_chan;
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(rx->device) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "hipSetDevice failed");
     ps->table = std::make_shared<DevData>();
@@ -659,11 +689,7 @@ int32_t hjb_rollout_set_position_model(void *rollout_x, void *rollout_y, void *r
         return rfail(rx, HJB_E_DEVICE, "rollout: upload failed");
     ps->M.table = (const double *)dt;
     ps->M.n_sub = (const int32_t *)dn;
-    if (rx->stream) (void)hipStreamSynchronize(rx->stream);
-    rx->ps = std::move(ps);                                 // replaces (and releases) a model set earlier
-    rx->pa.reset();
-    rx->as.reset();
-    rx->model = kModelPosition;
+    install_attached(rx, std::move(ps), kModelPosition);
     return HJB_OK;
 }
 
@@ -705,46 +731,15 @@ int32_t hjb_rollout_set_attitude_simplified_model(void *rollout_1, void *rollout
     if (r) std::memcpy(M.r, r, sizeof M.r);
     M.hs = h / substeps;
     M.substeps = substeps;
-    if (!r1 || !r2 || !r3) return rfail(r1, HJB_E_INVALID, "rollout: null handle (three channel objects are required)");
-    if (r1 == r2 || r1 == r3 || r2 == r3) return rfail(r1, HJB_E_INVALID, "rollout: the same object passed for two channels");
     auto as = std::make_unique<AttSimplified>();
     as->M = M;
     as->dynamics = dynamics;
-    // channels 2 and 3: a snapshot of the policy with a share of its device data, taken under that object's own lock
-    int dev_o[2] = {0, 0}, idx_o[2] = {0, 0}, planes_o[2] = {0, 0};
-    Rollout *others[2] = {r2, r3};
-    const char *names[2] = {"rollout_2", "rollout_3"};
-    for (int t = 0; t < 2; ++t) {
-        Rollout *o = others[t];
-        std::lock_guard<std::mutex> g(o->mu);
-        if (o->D != 2 || o->R.n_u != 1)
-            return rfail(r1, HJB_E_INVALID, "rollout: the simplified attitude model needs D == 2 and n_u == 1 (%s: D=%d, n_u=%d)", names[t], o->D,
-                         o->R.n_u);
-        (t == 0 ? as->c2 : as->c3) = pa_channel(o->R);
-        (t == 0 ? as->data_2 : as->data_3) = o->data;
-        dev_o[t] = o->device;
-        idx_o[t] = o->idx_bytes;
-        planes_o[t] = o->n_planes;
-    }
-    std::lock_guard<std::mutex> g(r1->mu);
-    if (r1->D != 2 || r1->R.n_u != 1)
-        return rfail(r1, HJB_E_INVALID, "rollout: the simplified attitude model needs D == 2 and n_u == 1 (rollout_1: D=%d, n_u=%d)", r1->D,
-                     r1->R.n_u);
-    for (int t = 0; t < 2; ++t) {
-        if (dev_o[t] != r1->device)
-            return rfail(r1, HJB_E_INVALID, "rollout: %s is on device %d, rollout_1 on device %d", names[t], dev_o[t], r1->device);
-        if (idx_o[t] != r1->idx_bytes)
-            return rfail(r1, HJB_E_INVALID, "rollout: %s has %d-byte labels, rollout_1 %d-byte labels (the three channels share one label type)",
-                         names[t], idx_o[t], r1->idx_bytes);
-    }
-    as->n_planes = std::min(r1->n_planes, std::min(planes_o[0], planes_o[1]));
+    std::unique_lock<std::mutex> g;
+    const int bad_chan = attach_channels({r1, r2, r3}, {"rollout_1", "rollout_2", "rollout_3"}, "simplified attitude", 2, 1, *as, g);
+    if (bad_chan) return bad_chan;
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(r1->device) != hipSuccess) return rfail(r1, HJB_E_DEVICE, "hipSetDevice failed");
-    if (r1->stream) (void)hipStreamSynchronize(r1->stream);
-    r1->as = std::move(as);                                 // replaces (and releases) a model set earlier
-    r1->pa.reset();
-    r1->ps.reset();
-    r1->model = kModelAttSimplified;
+    install_attached(r1, std::move(as), kModelAttSimplified);
     return HJB_OK;
 }
 
@@ -774,22 +769,15 @@ int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const in
     if (bad_arg) return bad_arg;
     if (device_ms) *device_ms = 0.0;
     if (n_traj == 0) return HJB_OK;
-    if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final");
     const int D = ro->D;
-    if (n_traj > INT64_MAX / (D * ((int64_t)n_steps + 1)) / 8) return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x D x n_steps)");
-    const int64_t bad = first_nonfinite(X0, (int64_t)D * n_traj, true);
-    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
+    if (bad_traj) return bad_traj;
     const int idx_bytes = ro->idx_bytes;
     return run_chunks(ro, "hjb_rollout_run", D, ro->R.n_u, 0, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, nullptr, nullptr,
                       device_ms,
                       [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t st, double *dX0, double *dXf, double *dC,
                           double *dXp, double *dUp, double *, int32_t *) {
-                          switch (idx_bytes) {
-                              case 1: launch_m<uint8_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
-                              case 2: launch_m<uint16_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
-                              default: launch_m<int32_t>(D, method, lds_on, R, nc, lds, st, dX0, dXf, dC, dXp, dUp); break;
-                          }
-                          return hipGetLastError();
+                          return launch_rollout(idx_bytes, method, lds_on, D, R, nc, lds, st, dX0, dXf, dC, dXp, dUp);
                       });
 }
 
@@ -803,17 +791,9 @@ int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps,
     if (bad_arg) return bad_arg;
     if (device_ms) *device_ms = 0.0;
     if (n_traj == 0) return HJB_OK;
-    if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final");
-    if (n_traj > INT64_MAX / (HJB_ATT_W * ((int64_t)n_steps + 1)) / 8)
-        return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x 7 x n_steps)");
-    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_ATT_W * n_traj, true);
-    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
-    for (int64_t i = 0; i < n_traj; ++i) {
-        const double *q = X0 + HJB_ATT_W * i + 3;
-        if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)
-            return rfail(ro, HJB_E_INVALID, "rollout: X0 column %lld has an all-zero quaternion (0/0 at the first renormalisation)",
-                         (long long)i);
-    }
+    int bad_traj = check_traj(ro, "rollout", HJB_ATT_W, "7", n_steps, n_traj, X0, X_final);
+    if (!bad_traj) bad_traj = check_quaternions(ro, "rollout", n_traj, X0);
+    if (bad_traj) return bad_traj;
     const int idx_bytes = ro->idx_bytes, integ = ro->integrator;
     const DAttitude M = ro->M;
     return run_chunks(ro, "hjb_rollout_run_attitude", HJB_ATT_W, HJB_ATT_U, 3, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path,
@@ -831,30 +811,26 @@ int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t 
     std::lock_guard<std::mutex> g(ro->mu);
     const int bad_arg = check_run(ro, kModelPosAtt, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
     if (bad_arg) return bad_arg;
-    const PosAtt &pa = *ro->pa;
+    const PosAtt &pa = static_cast<const PosAtt &>(*ro->att);
     if (n_steps > pa.max_steps)
         return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the orbit table covers %d stages ((n_nodes - 1) / (2 substeps))", n_steps,
                      pa.max_steps);
     if (n_traj == 0) return HJB_OK;
-    if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final");
-    if (n_traj > INT64_MAX / (HJB_PA_W * ((int64_t)n_steps + 1)) / 8)
-        return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x 13 x n_steps)");
-    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_PA_W * n_traj, true);
-    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    const int bad_traj = check_traj(ro, "rollout", HJB_PA_W, "13", n_steps, n_traj, X0, X_final);
+    if (bad_traj) return bad_traj;
     const int idx_bytes = ro->idx_bytes;
     const DPaChan cx0 = pa_channel(ro->R);
-    const size_t lds3 = (size_t)(2 * ((int64_t)cx0.n_knots + pa.cy.n_knots + pa.cz.n_knots) +
-                                 4 * ((int64_t)cx0.n_labels + pa.cy.n_labels + pa.cz.n_labels)) * sizeof(double);
+    const size_t lds3 = lds_bytes({&cx0, &pa.c[0], &pa.c[1]}, 4);
     const bool lds3_on = ro->lds && lds3 <= kLdsMax;
     return run_chunks(ro, "hjb_rollout_run_pos_att", HJB_PA_W, HJB_PA_F, HJB_PA_FM, n_steps, plane_of_step, n_traj, X0, X_final, nullptr,
                       X_path, F_path, FM_path, nullptr, nullptr,
                       [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *, double *dXp,
                           double *dFp, double *dFMp, int32_t *) {
-                          DPaChan cx = cx0, cy = pa.cy, cz = pa.cz;
-                          cx.plane_of_step = cy.plane_of_step = cz.plane_of_step = R.plane_of_step;
+                          const int32_t *pl = R.plane_of_step;
                           DPosAtt M = pa.M;
                           M.n_steps = R.n_steps;
-                          return launch_rollout_pos_att(idx_bytes, lds3_on, cx, cy, cz, M, nc, lds3, st, dX0, dXf, dXp, dFp, dFMp);
+                          return launch_rollout_pos_att(idx_bytes, lds3_on, on_planes(cx0, pl), on_planes(pa.c[0], pl), on_planes(pa.c[1], pl),
+                                                        M, nc, lds3, st, dX0, dXf, dXp, dFp, dFMp);
                       });
 }
 
@@ -868,7 +844,7 @@ int32_t hjb_rollout_run_pos_att_faults(void *rollout_x, int32_t n_steps, const i
     // every refusal before any device work, the outputs untouched
     const int bad_arg = check_run(ro, kModelPosAtt, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
     if (bad_arg) return bad_arg;
-    const PosAtt &pa = *ro->pa;
+    const PosAtt &pa = static_cast<const PosAtt &>(*ro->att);
     if (n_steps > pa.max_steps)
         return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the orbit table covers %d stages ((n_nodes - 1) / (2 substeps))", n_steps,
                      pa.max_steps);
@@ -883,11 +859,8 @@ int32_t hjb_rollout_run_pos_att_faults(void *rollout_x, int32_t n_steps, const i
         if (device_ms) *device_ms = 0.0;
         return HJB_OK;
     }
-    if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final");
-    if (n_traj > INT64_MAX / (HJB_PA_W * ((int64_t)n_steps + 1)) / 8)
-        return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x 13 x n_steps)");
-    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_PA_W * n_traj, true);
-    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    const int bad_traj = check_traj(ro, "rollout", HJB_PA_W, "13", n_steps, n_traj, X0, X_final);
+    if (bad_traj) return bad_traj;
     for (int64_t i = 0; i < n_traj; ++i) {
         if (fault_mask && (fault_mask[i] & ~0xFFF))
             return rfail(ro, HJB_E_INVALID, "rollout: fault_mask[%lld] = 0x%x has a bit above 11 (twelve thrusters)", (long long)i,
@@ -902,8 +875,7 @@ int32_t hjb_rollout_run_pos_att_faults(void *rollout_x, int32_t n_steps, const i
     }
     const int idx_bytes = ro->idx_bytes;
     const DPaChan cx0 = pa_channel(ro->R);
-    const size_t lds4 = (size_t)(2 * ((int64_t)cx0.n_knots + pa.cy.n_knots + pa.cz.n_knots + pa.cxf.n_knots) +
-                                 4 * ((int64_t)cx0.n_labels + pa.cy.n_labels + pa.cz.n_labels + pa.cxf.n_labels)) * sizeof(double);
+    const size_t lds4 = lds_bytes({&cx0, &pa.c[0], &pa.c[1], &pa.cxf}, 4);
     const bool lds4_on = ro->lds && lds4 <= kLdsMax;
     DPaFault Q{};
     Q.h = pa.h;
@@ -917,8 +889,7 @@ int32_t hjb_rollout_run_pos_att_faults(void *rollout_x, int32_t n_steps, const i
                               impulse, X_path, F_path, FM_path, settle_stage, device_ms,
                               [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t s, double *dX0, double *dXf, double *dImp, double *dXp,
                                   double *dFp, double *dFMp, int32_t *dSettle) {
-                                  DPaChan cx = cx0, cy = pa.cy, cz = pa.cz, cxf = pa.cxf;
-                                  cx.plane_of_step = cy.plane_of_step = cz.plane_of_step = cxf.plane_of_step = R.plane_of_step;
+                                  const int32_t *pl = R.plane_of_step;
                                   DPosAtt M = pa.M;
                                   M.n_steps = R.n_steps;
                                   DPaFault Qc = Q;
@@ -927,8 +898,9 @@ int32_t hjb_rollout_run_pos_att_faults(void *rollout_x, int32_t n_steps, const i
                                   Qc.switch_stage = dev_in[2];
                                   Qc.impulse = dImp;
                                   Qc.settle = dSettle;
-                                  return launch_rollout_pos_att_faults(idx_bytes, lds4_on, cx, cy, cz, cxf, M, Qc, nc, lds4, s, dX0, dXf, dXp,
-                                                                       dFp, dFMp);
+                                  return launch_rollout_pos_att_faults(idx_bytes, lds4_on, on_planes(cx0, pl), on_planes(pa.c[0], pl),
+                                                                       on_planes(pa.c[1], pl), on_planes(pa.cxf, pl), M, Qc, nc, lds4, s,
+                                                                       dX0, dXf, dXp, dFp, dFMp);
                               },
                               [&](int64_t i0, int64_t nc, hipStream_t s) {
                                   for (int t = 0; t < 3; ++t) {
@@ -957,29 +929,27 @@ int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t
     std::lock_guard<std::mutex> g(ro->mu);
     const int bad_arg = check_run(ro, kModelPosition, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
     if (bad_arg) return bad_arg;
-    const Position &ps = *ro->ps;
+    const Position &ps = static_cast<const Position &>(*ro->att);
     if (n_steps > ps.max_steps)
         return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the RKF45 table covers %d stages", n_steps, ps.max_steps);
     if (n_traj == 0) return HJB_OK;
+    // this entry point's own null check (off_schedule is required): check_traj's of X0 / X_final cannot fire after it
     if (!X0 || !X_final || !off_schedule) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final / off_schedule");
-    if (n_traj > INT64_MAX / (HJB_POS_W * ((int64_t)n_steps + 1)) / 8)
-        return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x 6 x n_steps)");
-    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_POS_W * n_traj, true);
-    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    const int bad_traj = check_traj(ro, "rollout", HJB_POS_W, "6", n_steps, n_traj, X0, X_final);
+    if (bad_traj) return bad_traj;
     const int idx_bytes = ro->idx_bytes;
     const DPaChan cx0 = pa_channel(ro->R);
-    const size_t lds3 = (size_t)(2 * ((int64_t)cx0.n_knots + ps.cy.n_knots + ps.cz.n_knots) +
-                                 ((int64_t)cx0.n_labels + ps.cy.n_labels + ps.cz.n_labels)) * sizeof(double);
+    const size_t lds3 = lds_bytes({&cx0, &ps.c[0], &ps.c[1]}, 1);
     const bool lds3_on = ro->lds && lds3 <= kLdsMax;
     return run_chunks(ro, "hjb_rollout_run_position", HJB_POS_W, HJB_POS_A, 0, n_steps, plane_of_step, n_traj, X0, X_final, nullptr,
                       X_path, A_path, nullptr, off_schedule, nullptr,
                       [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *, double *dXp,
                           double *dAp, double *, int32_t *dOff) {
-                          DPaChan cx = cx0, cy = ps.cy, cz = ps.cz;
-                          cx.plane_of_step = cy.plane_of_step = cz.plane_of_step = R.plane_of_step;
+                          const int32_t *pl = R.plane_of_step;
                           DPosition M = ps.M;
                           M.n_steps = R.n_steps;
-                          return launch_rollout_position(idx_bytes, lds3_on, cx, cy, cz, M, nc, lds3, st, dX0, dXf, dXp, dAp, dOff);
+                          return launch_rollout_position(idx_bytes, lds3_on, on_planes(cx0, pl), on_planes(ps.c[0], pl), on_planes(ps.c[1], pl),
+                                                         M, nc, lds3, st, dX0, dXf, dXp, dAp, dOff);
                       });
 }
 
@@ -991,28 +961,23 @@ int32_t hjb_rollout_run_attitude_simplified(void *rollout_1, int32_t n_steps, co
     std::lock_guard<std::mutex> g(ro->mu);
     const int bad_arg = check_run(ro, kModelAttSimplified, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
     if (bad_arg) return bad_arg;
-    const AttSimplified &as = *ro->as;
+    const AttSimplified &as = static_cast<const AttSimplified &>(*ro->att);
     if (n_traj == 0) return HJB_OK;
-    if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final");
-    if (n_traj > INT64_MAX / (HJB_ATT_W * ((int64_t)n_steps + 1)) / 8)
-        return rfail(ro, HJB_E_INVALID, "rollout: size overflow (n_traj x 7 x n_steps)");
-    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_ATT_W * n_traj, true);
-    if (bad >= 0) return rfail(ro, HJB_E_INVALID, "rollout: X0 element %lld is not finite", (long long)bad);
+    const int bad_traj = check_traj(ro, "rollout", HJB_ATT_W, "7", n_steps, n_traj, X0, X_final);
+    if (bad_traj) return bad_traj;
     const int idx_bytes = ro->idx_bytes;
     const DPaChan c10 = pa_channel(ro->R);
-    const size_t lds3 = (size_t)(2 * ((int64_t)c10.n_knots + as.c2.n_knots + as.c3.n_knots) +
-                                 ((int64_t)c10.n_labels + as.c2.n_labels + as.c3.n_labels)) * sizeof(double);
+    const size_t lds3 = lds_bytes({&c10, &as.c[0], &as.c[1]}, 1);
     const bool lds3_on = ro->lds && lds3 <= kLdsMax;
     return run_chunks(ro, "hjb_rollout_run_attitude_simplified", HJB_ATT_W, HJB_ATT_U, 3, n_steps, plane_of_step, n_traj, X0, X_final, cost,
                       X_path, U_path, A_path, nullptr, nullptr,
                       [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *dC, double *dXp,
                           double *dUp, double *dAp, int32_t *) {
-                          DPaChan c1 = c10, c2 = as.c2, c3 = as.c3;
-                          c1.plane_of_step = c2.plane_of_step = c3.plane_of_step = R.plane_of_step;
+                          const int32_t *pl = R.plane_of_step;
                           DAttSimplified M = as.M;
                           M.n_steps = R.n_steps;
-                          return launch_rollout_attitude_simplified(idx_bytes, lds3_on, as.dynamics, c1, c2, c3, M, nc, lds3, st, dX0, dXf,
-                                                                    dC, dXp, dUp, dAp);
+                          return launch_rollout_attitude_simplified(idx_bytes, lds3_on, as.dynamics, on_planes(c10, pl), on_planes(as.c[0], pl),
+                                                                    on_planes(as.c[1], pl), M, nc, lds3, st, dX0, dXf, dC, dXp, dUp, dAp);
                       });
 }
 
@@ -1045,17 +1010,9 @@ int32_t hjb_attitude_linear_response(int32_t device, const double *inertia, doub
     if (chunk < 0 || chunk > kMaxChunk)
         return rfail(nullptr, HJB_E_INVALID, "%s: chunk %lld not in 0..%lld", who, (long long)chunk, (long long)kMaxChunk);
     if (n_traj == 0) return HJB_OK;
-    if (!X0 || !X_final) return rfail(nullptr, HJB_E_INVALID, "%s: null X0 / X_final", who);
-    if (n_traj > INT64_MAX / (HJB_ATT_W * ((int64_t)n_steps + 1)) / 8)
-        return rfail(nullptr, HJB_E_INVALID, "%s: size overflow (n_traj x 7 x n_steps)", who);
-    const int64_t bad = first_nonfinite(X0, (int64_t)HJB_ATT_W * n_traj, true);
-    if (bad >= 0) return rfail(nullptr, HJB_E_INVALID, "%s: X0 element %lld is not finite", who, (long long)bad);
-    for (int64_t i = 0; i < n_traj; ++i) {
-        const double *q = X0 + HJB_ATT_W * i + 3;
-        if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)
-            return rfail(nullptr, HJB_E_INVALID, "%s: X0 column %lld has an all-zero quaternion (0/0 at the first renormalisation)", who,
-                         (long long)i);
-    }
+    int bad_traj = check_traj(nullptr, who, HJB_ATT_W, "7", n_steps, n_traj, X0, X_final);
+    if (!bad_traj) bad_traj = check_quaternions(nullptr, who, n_traj, X0);
+    if (bad_traj) return bad_traj;
     DAttLinear M{};
     M.A.h = h;
     const double J1 = inertia[0], J2 = inertia[1], J3 = inertia[2];

@@ -1,35 +1,21 @@
 // rollout_pos_att.hip - K18's 6 instantiations (kernels_rollout_pos_att.h: label type x LDS) in a unit of their own, behind
 // launch_rollout_pos_att (called by hjb_rollout_run_pos_att in rollout.hip).
 #include "kernels_rollout_pos_att.h"
+#include "rollout_dispatch.h"
 
 namespace hjb {
-
-namespace {
-
-template <typename TL, bool LDS>
-void launch_i(const DPaChan &CX, const DPaChan &CY, const DPaChan &CZ, const DPosAtt &M, int64_t nc, size_t lds, hipStream_t st,
-              const double *X0, double *Xf, double *Xp, double *Fp, double *FMp) {
-    dim3 b(256), g((unsigned)((nc + 255) / 256));
-    hipLaunchKernelGGL((k_rollout_pos_att<TL, LDS>), g, b, LDS ? lds : 0, st, CX, CY, CZ, M, nc, X0, Xf, Xp, Fp, FMp);
-}
-
-template <typename TL>
-void launch_l(bool lds_on, const DPaChan &CX, const DPaChan &CY, const DPaChan &CZ, const DPosAtt &M, int64_t nc, size_t lds,
-              hipStream_t st, const double *X0, double *Xf, double *Xp, double *Fp, double *FMp) {
-    if (lds_on) launch_i<TL, true>(CX, CY, CZ, M, nc, lds, st, X0, Xf, Xp, Fp, FMp);
-    else launch_i<TL, false>(CX, CY, CZ, M, nc, lds, st, X0, Xf, Xp, Fp, FMp);
-}
-
-}  // namespace
 
 hipError_t launch_rollout_pos_att(int idx_bytes, bool lds_on, const DPaChan &CX, const DPaChan &CY, const DPaChan &CZ, const DPosAtt &M,
                                   int64_t nc, size_t lds, hipStream_t st, const double *X0, double *Xf, double *Xp, double *Fp,
                                   double *FMp) {
-    switch (idx_bytes) {
-        case 1: launch_l<uint8_t>(lds_on, CX, CY, CZ, M, nc, lds, st, X0, Xf, Xp, Fp, FMp); break;
-        case 2: launch_l<uint16_t>(lds_on, CX, CY, CZ, M, nc, lds, st, X0, Xf, Xp, Fp, FMp); break;
-        default: launch_l<int32_t>(lds_on, CX, CY, CZ, M, nc, lds, st, X0, Xf, Xp, Fp, FMp); break;
-    }
+    const dim3 b(256), g((unsigned)((nc + 255) / 256));
+    with_label_type(idx_bytes, [&](auto tl) {
+        with_bool(lds_on, [&](auto l) {
+            using TL = typename decltype(tl)::type;
+            constexpr bool LDS = decltype(l)::value;
+            hipLaunchKernelGGL((k_rollout_pos_att<TL, LDS>), g, b, LDS ? lds : 0, st, CX, CY, CZ, M, nc, X0, Xf, Xp, Fp, FMp);
+        });
+    });
     return hipGetLastError();
 }
 
