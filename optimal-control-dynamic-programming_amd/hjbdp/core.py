@@ -4,6 +4,7 @@ missing, or no HIP device is visible, every compute call raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from pathlib import Path
@@ -102,6 +103,58 @@ def _f64p(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _i32p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+# ---- the marshalling of the rollout entry points (pure numpy): each run* is the starts, the planes, the outputs, one library
+# call, the dict -------------------------------------------------------------------------------------------------------------
+def _f64_vec(v, m):
+    """v as m contiguous doubles; None stays None (the library's "not given")."""
+    return None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(m))
+
+
+def _f64_colmajor(v, r, c):
+    """v as an [r, c] matrix of doubles laid out column-major, flat; None stays None."""
+    return None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(r, c).reshape(-1, order="F"))
+
+
+def _starts(X0, rows):
+    """The initial states as the library reads them: [n_traj, rows] C-contiguous float64 = [rows, n_traj] column-major.  A 1-D
+    X0 is one start."""
+    X = np.asarray(X0, dtype=np.float64)
+    return np.ascontiguousarray((X.reshape(rows, 1) if X.ndim == 1 else X).reshape(rows, -1).T)
+
+
+def _int32_vector(values, name, n_traj=None):
+    """values as a contiguous int32 vector, refused when an element does not fit.  n_traj None: flattened as it comes (a list of
+    planes).  n_traj given: one value per trajectory - None stays None, integer types only, a scalar or one element broadcasts."""
+    if values is None and n_traj is not None:
+        return None
+    a = np.asarray(values)
+    if n_traj is None:
+        a = a.reshape(-1)
+    else:
+        if a.dtype.kind not in "iu":
+            raise TypeError("%s must be integers, got %s" % (name, a.dtype))
+        a = np.broadcast_to(a.reshape(-1) if a.ndim else a, (n_traj,))
+    if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
+        raise ValueError("%s does not fit int32" % name)
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _path_buffers(nt, keep_path, *specs):
+    """The optional per-step outputs of a run, specs = (name, rows, cols) each.  Returns (flat, views): flat the buffers to hand
+    to the library in the order given (every one None without keep_path), views {name: the same memory as [nt, rows, cols] in
+    Fortran order, or None}, valid once the call has filled them."""
+    flat = [np.empty(nt * rows * cols) if keep_path else None for _, rows, cols in specs]
+    return flat, {name: None if a is None else a.reshape((nt, rows, cols), order="F") for (name, rows, cols), a in zip(specs, flat)}
+
+
+_LOOKUP = {"nearest": _abi.HJB_LOOKUP_NEAREST, "linear": _abi.HJB_LOOKUP_LINEAR}
+_ATT_INTEGRATOR = {"taylor": _abi.HJB_ATT_TAYLOR, "RK4": _abi.HJB_ATT_RK4, "rk4": _abi.HJB_ATT_RK4}
+
+
 class Rollout:
     """A stored per-stage policy resident on one GPU, for batched fixed-step closed-loop rollouts (hjb_rollout_*):
 
@@ -114,11 +167,15 @@ class Rollout:
     controls per label.  Step k of a trajectory looks plane plane_of_step[k] up at x ('nearest' / 'linear', bit-identical to
     policy_lookup in float64 on the dense values u_table[labels[:, p] - index_base]), adds the stage cost
     x'diag(q)x + u'diag(r)u and steps x <- A x + B u + c.  X0: [D, n_traj].  run returns X_final [D, n_traj], cost [n_traj],
-    X_path [n_traj, D, n_steps+1] and U_path [n_traj, n_u, n_steps] (None unless keep_path) and device_ms."""
+    X_path [n_traj, D, n_steps+1] and U_path [n_traj, n_u, n_steps] (None unless keep_path) and device_ms.
+
+    The loops that take one policy per channel (pos-att, position, simplified attitude) are a model set on the first of several
+    Rollout objects: Rollout.open_channels opens and closes such a set."""
 
     def __init__(self, knots, labels, u_table, index_base=1, device=0):
         self.lib = load_library()
         self._ro = C.c_void_p()
+        self._pa_steps = self._pos_steps = 0              # the stages the pos-att / position model set last covers
         ks = [np.ascontiguousarray(k, dtype=np.float64).reshape(-1) for k in knots]
         self.D = len(ks)
         self.n = [len(k) for k in ks]
@@ -150,6 +207,23 @@ class Rollout:
             self._ro = C.c_void_p()
             self._raise(st)
         self.device = int(device)
+
+    @classmethod
+    @contextlib.contextmanager
+    def open_channels(cls, channels, device=0, index_base=1, label_dtype=None):
+        """with Rollout.open_channels(channels) as ros: one Rollout per (knots, labels, table) of `channels`, in order, on one
+        device (label_dtype: the labels cast to it first).  All that were created are closed on the way out, also when a later
+        one cannot be created.  The model goes on ros[0]: ros[0].set_pos_att_model(ros[1], ros[2], ...)."""
+        ros = []
+        try:
+            for knots, labels, table in channels:
+                if label_dtype is not None:
+                    labels = np.asarray(labels).astype(label_dtype, copy=False)
+                ros.append(cls(knots, labels, table, index_base=index_base, device=device))
+            yield ros
+        finally:
+            for ro in ros:
+                ro.close()
 
     def _raise(self, st):
         msg = self.lib.hjb_rollout_last_error(self._ro if self._ro.value else None)
@@ -184,76 +258,52 @@ class Rollout:
 
     def set_model(self, A, B, c=None, q=None, r=None):
         D, nu = self.D, self.n_u
-        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64).reshape(D, D).reshape(-1, order="F"))
-        B = np.ascontiguousarray(np.asarray(B, dtype=np.float64).reshape(D, nu).reshape(-1, order="F"))
-        vec = lambda v, m: None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(m))
-        c, q, r = vec(c, D), vec(q, D), vec(r, nu)
-        self._check(self.lib.hjb_rollout_set_model(self._ro, _f64p(A), _f64p(B), _f64p(c), _f64p(q), _f64p(r)))
+        self._check(self.lib.hjb_rollout_set_model(self._ro, _f64p(_f64_colmajor(A, D, D)), _f64p(_f64_colmajor(B, D, nu)),
+                                                   _f64p(_f64_vec(c, D)), _f64p(_f64_vec(q, D)), _f64p(_f64_vec(r, nu))))
 
     def run(self, X0, plane_of_step, method="linear", keep_path=False):
         D, nu = self.D, self.n_u
-        X = np.asarray(X0, dtype=np.float64)
-        X = np.ascontiguousarray((X.reshape(D, 1) if X.ndim == 1 else X).reshape(D, -1).T)     # [n_traj, D] = [D, n_traj] column-major
+        X = _starts(X0, D)
         nt = X.shape[0]
-        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
-        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
-            raise ValueError("plane_of_step does not fit int32")
-        ps = ps.astype(np.int32)
+        ps = _int32_vector(plane_of_step, "plane_of_step")
         K = int(ps.size)
-        meth = {"nearest": _abi.HJB_LOOKUP_NEAREST, "linear": _abi.HJB_LOOKUP_LINEAR}[method]
         Xf = np.empty((nt, D))
         cost = np.empty(nt)
-        Xp = np.empty(nt * D * (K + 1)) if keep_path else None
-        Up = np.empty(nt * nu * K) if keep_path else None
+        flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K))
         ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run(self._ro, meth, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X), _f64p(Xf),
-                                             _f64p(cost), _f64p(Xp), _f64p(Up), C.byref(ms)))
-        return {"X_final": Xf.T, "cost": cost,
-                "X_path": None if Xp is None else Xp.reshape((nt, D, K + 1), order="F"),
-                "U_path": None if Up is None else Up.reshape((nt, nu, K), order="F"),
-                "device_ms": ms.value}
+        self._check(self.lib.hjb_rollout_run(self._ro, _LOOKUP[method], K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
+                                             *map(_f64p, flat), C.byref(ms)))
+        return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
 
     def set_attitude_model(self, inertia, h, integrator="taylor", q=None, r=None):
         """The 6-D attitude loop instead of the affine one (hjb_rollout_set_attitude_model; the last model set wins):
         inertia = (J1, J2, J3), step h, integrator 'taylor' or 'RK4', stage-cost weights q [7] and r [3] (None: zeros).
         Needs D = 6 axes in the order (w1, w2, w3, yaw, pitch, roll) and n_u = 3."""
-        integ = {"taylor": _abi.HJB_ATT_TAYLOR, "RK4": _abi.HJB_ATT_RK4, "rk4": _abi.HJB_ATT_RK4}[integrator]
-        J = np.ascontiguousarray(np.asarray(inertia, dtype=np.float64).reshape(3))
-        vec = lambda v, m: None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(m))
-        self._check(self.lib.hjb_rollout_set_attitude_model(self._ro, _f64p(J), float(h), integ, _f64p(vec(q, 7)), _f64p(vec(r, 3))))
+        self._check(self.lib.hjb_rollout_set_attitude_model(self._ro, _f64p(_f64_vec(inertia, 3)), float(h), _ATT_INTEGRATOR[integrator],
+                                                            _f64p(_f64_vec(q, 7)), _f64p(_f64_vec(r, 3))))
 
     def run_attitude(self, X0, plane_of_step, method="nearest", keep_path=False):
         """hjb_rollout_run_attitude: X0 [7, n_traj] (X = [w1 w2 w3 q1 q2 q3 q4], q4 scalar).  Returns X_final [7, n_traj],
         cost [n_traj], X_path [n_traj, 7, n_steps+1], U_path [n_traj, 3, n_steps], A_path [n_traj, 3, n_steps] (the yaw, pitch,
         roll in radians each step looked up at; the paths None unless keep_path) and device_ms."""
-        X = np.asarray(X0, dtype=np.float64)
-        X = np.ascontiguousarray((X.reshape(7, 1) if X.ndim == 1 else X).reshape(7, -1).T)
+        X = _starts(X0, 7)
         nt = X.shape[0]
-        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
-        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
-            raise ValueError("plane_of_step does not fit int32")
-        ps = ps.astype(np.int32)
+        ps = _int32_vector(plane_of_step, "plane_of_step")
         K = int(ps.size)
-        meth = {"nearest": _abi.HJB_LOOKUP_NEAREST, "linear": _abi.HJB_LOOKUP_LINEAR}[method]
         Xf = np.empty((nt, 7))
         cost = np.empty(nt)
-        Xp = np.empty(nt * 7 * (K + 1)) if keep_path else None
-        Up = np.empty(nt * 3 * K) if keep_path else None
-        Ap = np.empty(nt * 3 * K) if keep_path else None
+        flat, paths = _path_buffers(nt, keep_path, ("X_path", 7, K + 1), ("U_path", 3, K), ("A_path", 3, K))
         ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run_attitude(self._ro, meth, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X),
-                                                      _f64p(Xf), _f64p(cost), _f64p(Xp), _f64p(Up), _f64p(Ap), C.byref(ms)))
-        path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
-        return {"X_final": Xf.T, "cost": cost, "X_path": path(Xp, 7, K + 1), "U_path": path(Up, 3, K), "A_path": path(Ap, 3, K),
-                "device_ms": ms.value}
+        self._check(self.lib.hjb_rollout_run_attitude(self._ro, _LOOKUP[method], K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
+                                                      *map(_f64p, flat), C.byref(ms)))
+        return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
 
     def set_pos_att_model(self, rollout_y, rollout_z, inertia, mass, t_dist, h, rsw2eci, orbit_coef, substeps=1):
         """The 13-state pos-att loop (hjb_rollout_set_pos_att_model; the last model set wins) with this object as channel x and
         two more Rollout objects as channels y and z (each D = 4 over (position, velocity, angle, rate), n_u = 4, one device, one
         label type).  inertia [3, 3], rsw2eci [3, 3] and orbit_coef [n_nodes, 5] as hjbdp.rollout.pos_att_orbit_table builds them
         (n_nodes = 2 * substeps * k + 1).  The model keeps what it reads of the other two alive: they may be closed afterwards."""
-        m3 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(3, 3).reshape(-1, order="F"))
-        J, rsw = m3(inertia), m3(rsw2eci)
+        J, rsw = _f64_colmajor(inertia, 3, 3), _f64_colmajor(rsw2eci, 3, 3)
         coef = np.ascontiguousarray(np.asarray(orbit_coef, dtype=np.float64).reshape(-1, 5))
         self._check(self.lib.hjb_rollout_set_pos_att_model(self._ro, rollout_y._ro, rollout_z._ro, _f64p(J), float(mass), float(t_dist),
                                                            float(h), int(substeps), _f64p(rsw), int(coef.shape[0]), _f64p(coef)))
@@ -263,24 +313,14 @@ class Rollout:
         """hjb_rollout_run_pos_att: X0 [13, n_traj] (X = [x(3) v(3) q(4) w(3)], q4 scalar).  plane_of_step None: every stage the
         orbit table covers, on plane 0 (stationary policies).  Returns X_final [13, n_traj] and X_path [n_traj, 13, n_steps+1], F_path [n_traj, 12, n_steps]
         (f0..f11), FM_path [n_traj, 6, n_steps] (a_x a_y a_z U_M); the paths None unless keep_path."""
-        X = np.asarray(X0, dtype=np.float64)
-        X = np.ascontiguousarray((X.reshape(13, 1) if X.ndim == 1 else X).reshape(13, -1).T)
+        X = _starts(X0, 13)
         nt = X.shape[0]
-        if plane_of_step is None:
-            plane_of_step = np.zeros(getattr(self, "_pa_steps", 0), np.int32)
-        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
-        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
-            raise ValueError("plane_of_step does not fit int32")
-        ps = ps.astype(np.int32)
+        ps = _int32_vector(np.zeros(self._pa_steps, np.int32) if plane_of_step is None else plane_of_step, "plane_of_step")
         K = int(ps.size)
         Xf = np.empty((nt, 13))
-        Xp = np.empty(nt * 13 * (K + 1)) if keep_path else None
-        Fp = np.empty(nt * 12 * K) if keep_path else None
-        FMp = np.empty(nt * 6 * K) if keep_path else None
-        self._check(self.lib.hjb_rollout_run_pos_att(self._ro, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X), _f64p(Xf),
-                                                     _f64p(Xp), _f64p(Fp), _f64p(FMp)))
-        path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
-        return {"X_final": Xf.T, "X_path": path(Xp, 13, K + 1), "F_path": path(Fp, 12, K), "FM_path": path(FMp, 6, K)}
+        flat, paths = _path_buffers(nt, keep_path, ("X_path", 13, K + 1), ("F_path", 12, K), ("FM_path", 6, K))
+        self._check(self.lib.hjb_rollout_run_pos_att(self._ro, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), *map(_f64p, flat)))
+        return {"X_final": Xf.T, **paths}
 
     def set_pos_att_fault_controller(self, other):
         """hjb_rollout_set_pos_att_fault_controller: attach `other` (a Rollout with D = 4, n_u = 4 = [f0 f1 f6 f7], this object's
@@ -298,42 +338,21 @@ class Rollout:
         |applied force|; settle_stage [n_traj] (int32): the first state index from which the path stays within pos_tol of the
         origin and |q(1:3)| within att_tol to the end, n_steps + 1 if the last state is outside; X_path, F_path (the APPLIED
         forces), FM_path as run_pos_att's, None unless keep_path; device_ms."""
-        X = np.asarray(X0, dtype=np.float64)
-        X = np.ascontiguousarray((X.reshape(13, 1) if X.ndim == 1 else X).reshape(13, -1).T)
+        X = _starts(X0, 13)
         nt = X.shape[0]
-        if plane_of_step is None:
-            plane_of_step = np.zeros(getattr(self, "_pa_steps", 0), np.int32)
-        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
-        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
-            raise ValueError("plane_of_step does not fit int32")
-        ps = ps.astype(np.int32)
+        ps = _int32_vector(np.zeros(self._pa_steps, np.int32) if plane_of_step is None else plane_of_step, "plane_of_step")
         K = int(ps.size)
-
-        def per_traj(v, name):
-            if v is None:
-                return None
-            a = np.asarray(v)
-            if a.dtype.kind not in "iu":
-                raise TypeError("%s must be integers, got %s" % (name, a.dtype))
-            a = np.broadcast_to(a.reshape(-1) if a.ndim else a, (nt,))
-            if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
-                raise ValueError("%s does not fit int32" % name)
-            return np.ascontiguousarray(a, dtype=np.int32)
-        fm, fs, sw = per_traj(fault_mask, "fault_mask"), per_traj(fault_stage, "fault_stage"), per_traj(switch_stage, "switch_stage")
-        i32p = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        fm, fs, sw = (_int32_vector(v, name, nt) for v, name in ((fault_mask, "fault_mask"), (fault_stage, "fault_stage"),
+                                                                 (switch_stage, "switch_stage")))
         Xf = np.empty((nt, 13))
         imp = np.empty(nt)
         settle = np.empty(nt, np.int32)
-        Xp = np.empty(nt * 13 * (K + 1)) if keep_path else None
-        Fp = np.empty(nt * 12 * K) if keep_path else None
-        FMp = np.empty(nt * 6 * K) if keep_path else None
+        flat, paths = _path_buffers(nt, keep_path, ("X_path", 13, K + 1), ("F_path", 12, K), ("FM_path", 6, K))
         ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run_pos_att_faults(self._ro, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X), i32p(fm),
-                                                            i32p(fs), i32p(sw), float(pos_tol), float(att_tol), _f64p(Xf), _f64p(imp),
-                                                            i32p(settle), _f64p(Xp), _f64p(Fp), _f64p(FMp), C.byref(ms)))
-        path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
-        return {"X_final": Xf.T, "impulse": imp, "settle_stage": settle, "X_path": path(Xp, 13, K + 1), "F_path": path(Fp, 12, K),
-                "FM_path": path(FMp, 6, K), "device_ms": ms.value}
+        self._check(self.lib.hjb_rollout_run_pos_att_faults(self._ro, K, _i32p(ps), nt, _f64p(X), _i32p(fm), _i32p(fs), _i32p(sw),
+                                                            float(pos_tol), float(att_tol), _f64p(Xf), _f64p(imp), _i32p(settle),
+                                                            *map(_f64p, flat), C.byref(ms)))
+        return {"X_final": Xf.T, "impulse": imp, "settle_stage": settle, **paths, "device_ms": ms.value}
 
     def set_position_model(self, rollout_y, rollout_z, n_sub, table, tol=1e-8):
         """Solver_position's RKF45 loop (hjb_rollout_set_position_model; the last model set wins) with this object as channel x and
@@ -345,31 +364,22 @@ class Rollout:
         if tab.ndim != 3 or tab.shape[0] != ns.size or tab.shape[2] != 32:
             raise ValueError("table must be [n_steps, max_sub, 32] with one n_sub per stage, got %r for %d stages" % (tab.shape, ns.size))
         self._check(self.lib.hjb_rollout_set_position_model(self._ro, rollout_y._ro, rollout_z._ro, float(tol), int(ns.size),
-                                                            int(tab.shape[1]), ns.ctypes.data_as(C.POINTER(C.c_int32)), _f64p(tab)))
+                                                            int(tab.shape[1]), _i32p(ns), _f64p(tab)))
         self._pos_steps = int(ns.size)
 
     def run_position(self, X0, plane_of_step=None, keep_path=False):
         """hjb_rollout_run_position: X0 [6, n_traj] (y = [x(3) v(3)]).  plane_of_step None: every stage the table covers, on plane 0
         (stationary policies).  Returns X_final [6, n_traj], off_schedule [n_traj] (int32: the first stage that left rkf45's
         schedule, -1 if none) and X_path [n_traj, 6, n_steps+1], A_path [n_traj, 3, n_steps]; the paths None unless keep_path."""
-        X = np.asarray(X0, dtype=np.float64)
-        X = np.ascontiguousarray((X.reshape(6, 1) if X.ndim == 1 else X).reshape(6, -1).T)
+        X = _starts(X0, 6)
         nt = X.shape[0]
-        if plane_of_step is None:
-            plane_of_step = np.zeros(getattr(self, "_pos_steps", 0), np.int32)
-        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
-        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
-            raise ValueError("plane_of_step does not fit int32")
-        ps = ps.astype(np.int32)
+        ps = _int32_vector(np.zeros(self._pos_steps, np.int32) if plane_of_step is None else plane_of_step, "plane_of_step")
         K = int(ps.size)
         Xf = np.empty((nt, 6))
-        Xp = np.empty(nt * 6 * (K + 1)) if keep_path else None
-        Ap = np.empty(nt * 3 * K) if keep_path else None
         off = np.full(nt, -1, np.int32)
-        self._check(self.lib.hjb_rollout_run_position(self._ro, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X), _f64p(Xf),
-                                                      _f64p(Xp), _f64p(Ap), off.ctypes.data_as(C.POINTER(C.c_int32))))
-        path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
-        return {"X_final": Xf.T, "off_schedule": off, "X_path": path(Xp, 6, K + 1), "A_path": path(Ap, 3, K)}
+        flat, paths = _path_buffers(nt, keep_path, ("X_path", 6, K + 1), ("A_path", 3, K))
+        self._check(self.lib.hjb_rollout_run_position(self._ro, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), *map(_f64p, flat), _i32p(off)))
+        return {"X_final": Xf.T, "off_schedule": off, **paths}
 
     def set_attitude_simplified_model(self, rollout_2, rollout_3, inertia, h, substeps=1, dynamics="full", qw=None, qt=None, r=None):
         """The simplified attitude loop (hjb_rollout_set_attitude_simplified_model; the last model set wins) with this object as
@@ -380,32 +390,24 @@ class Rollout:
         substeps must be 1).  qw, qt, r [3]: the stage-cost weights on w_i^2, theta_i^2, u_i^2 (None: zeros).  The model keeps what
         it reads of the other two alive: they may be closed afterwards."""
         dyn = {"full": _abi.HJB_ATTS_FULL, "diagonal": _abi.HJB_ATTS_DIAGONAL}[dynamics]
-        J = np.ascontiguousarray(np.asarray(inertia, dtype=np.float64).reshape(3, 3).reshape(-1, order="F"))
-        vec = lambda v: None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(3))
-        self._check(self.lib.hjb_rollout_set_attitude_simplified_model(self._ro, rollout_2._ro, rollout_3._ro, _f64p(J), float(h),
-                                                                       int(substeps), dyn, _f64p(vec(qw)), _f64p(vec(qt)), _f64p(vec(r))))
+        self._check(self.lib.hjb_rollout_set_attitude_simplified_model(self._ro, rollout_2._ro, rollout_3._ro, _f64p(_f64_colmajor(inertia, 3, 3)),
+                                                                       float(h), int(substeps), dyn, _f64p(_f64_vec(qw, 3)),
+                                                                       _f64p(_f64_vec(qt, 3)), _f64p(_f64_vec(r, 3))))
 
     def run_attitude_simplified(self, X0, plane_of_step, keep_path=False):
         """hjb_rollout_run_attitude_simplified: X0 [7, n_traj] (X = [w1 w2 w3 q1 q2 q3 q4], q4 scalar).  Returns X_final [7, n_traj],
         cost [n_traj], X_path [n_traj, 7, n_steps+1], U_path [n_traj, 3, n_steps], A_path [n_traj, 3, n_steps] (the three
         theta_i = 2 asin(q_i) in radians each stage looked up at); the paths None unless keep_path."""
-        X = np.asarray(X0, dtype=np.float64)
-        X = np.ascontiguousarray((X.reshape(7, 1) if X.ndim == 1 else X).reshape(7, -1).T)
+        X = _starts(X0, 7)
         nt = X.shape[0]
-        ps = np.ascontiguousarray(np.asarray(plane_of_step).reshape(-1))
-        if ps.size and (ps.min() < np.iinfo(np.int32).min or ps.max() > np.iinfo(np.int32).max):
-            raise ValueError("plane_of_step does not fit int32")
-        ps = ps.astype(np.int32)
+        ps = _int32_vector(plane_of_step, "plane_of_step")
         K = int(ps.size)
         Xf = np.empty((nt, 7))
         cost = np.empty(nt)
-        Xp = np.empty(nt * 7 * (K + 1)) if keep_path else None
-        Up = np.empty(nt * 3 * K) if keep_path else None
-        Ap = np.empty(nt * 3 * K) if keep_path else None
-        self._check(self.lib.hjb_rollout_run_attitude_simplified(self._ro, K, ps.ctypes.data_as(C.POINTER(C.c_int32)), nt, _f64p(X),
-                                                                 _f64p(Xf), _f64p(cost), _f64p(Xp), _f64p(Up), _f64p(Ap)))
-        path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
-        return {"X_final": Xf.T, "cost": cost, "X_path": path(Xp, 7, K + 1), "U_path": path(Up, 3, K), "A_path": path(Ap, 3, K)}
+        flat, paths = _path_buffers(nt, keep_path, ("X_path", 7, K + 1), ("U_path", 3, K), ("A_path", 3, K))
+        self._check(self.lib.hjb_rollout_run_attitude_simplified(self._ro, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
+                                                                 *map(_f64p, flat)))
+        return {"X_final": Xf.T, "cost": cost, **paths}
 
 
 def attitude_linear_response(inertia, h, K, C_gain, X0, n_steps, qc=None, u_limit=None, integrator="RK4", cost_form="quat",
@@ -419,12 +421,7 @@ def attitude_linear_response(inertia, h, K, C_gain, X0, n_steps, qc=None, u_limi
     X_path [n_traj, 7, n_steps+1], U_path [n_traj, 3, n_steps], A_path [n_traj, 3, n_steps] (yaw, pitch, roll in radians; the
     paths None unless keep_path) and device_ms."""
     lib = load_library()
-    integ = {"taylor": _abi.HJB_ATT_TAYLOR, "RK4": _abi.HJB_ATT_RK4, "rk4": _abi.HJB_ATT_RK4}[integrator]
     form = {"quat": _abi.HJB_ATTL_COST_QUAT, "angle": _abi.HJB_ATTL_COST_ANGLE}[cost_form]
-    J = np.ascontiguousarray(np.asarray(inertia, dtype=np.float64).reshape(3))
-    mat = lambda v, m: None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(m, m).reshape(-1, order="F"))
-    Km, Cm, qcm = mat(K, 3), mat(C_gain, 3), mat(qc, 4)
-    lim = None if u_limit is None else np.ascontiguousarray(np.asarray(u_limit, dtype=np.float64).reshape(3))
     wt = None
     if weights is not None:
         wt = np.zeros(10)
@@ -432,26 +429,21 @@ def attitude_linear_response(inertia, h, K, C_gain, X0, n_steps, qc=None, u_limi
         if w.size not in ((10,) if form == _abi.HJB_ATTL_COST_QUAT else (9, 10)):
             raise ValueError("weights: %d entries (cost_form 'quat' takes 10, 'angle' 9 or 10)" % w.size)
         wt[:w.size] = w
-    X = np.asarray(X0, dtype=np.float64)
-    X = np.ascontiguousarray((X.reshape(7, 1) if X.ndim == 1 else X).reshape(7, -1).T)
+    X = _starts(X0, 7)
     nt = X.shape[0]
     Kn = int(n_steps)
     Xf = np.empty((nt, 7))
     cost = np.empty(nt)
-    keep = keep_path and Kn >= 0
-    Xp = np.empty(nt * 7 * (Kn + 1)) if keep else None
-    Up = np.empty(nt * 3 * Kn) if keep else None
-    Ap = np.empty(nt * 3 * Kn) if keep else None
+    flat, paths = _path_buffers(nt, keep_path and Kn >= 0, ("X_path", 7, Kn + 1), ("U_path", 3, Kn), ("A_path", 3, Kn))
     ms = C.c_double(0.0)
-    st = lib.hjb_attitude_linear_response(int(device), _f64p(J), float(h), integ, _f64p(Km), _f64p(Cm), _f64p(qcm), _f64p(lim), form,
-                                          _f64p(wt), Kn, nt, _f64p(X), _f64p(Xf), _f64p(cost), _f64p(Xp), _f64p(Up), _f64p(Ap),
-                                          int(chunk), C.byref(ms))
+    st = lib.hjb_attitude_linear_response(int(device), _f64p(_f64_vec(inertia, 3)), float(h), _ATT_INTEGRATOR[integrator],
+                                          _f64p(_f64_colmajor(K, 3, 3)), _f64p(_f64_colmajor(C_gain, 3, 3)), _f64p(_f64_colmajor(qc, 4, 4)),
+                                          _f64p(_f64_vec(u_limit, 3)), form, _f64p(wt), Kn, nt, _f64p(X), _f64p(Xf), _f64p(cost),
+                                          *map(_f64p, flat), int(chunk), C.byref(ms))
     if st != _abi.HJB_OK:
         msg = lib.hjb_rollout_last_error(None)
         raise HjbError(st, (msg or b"").decode() or lib.hjb_status_string(st).decode())
-    path = lambda a, rows, cols: None if a is None else a.reshape((nt, rows, cols), order="F")
-    return {"X_final": Xf.T, "cost": cost, "X_path": path(Xp, 7, Kn + 1), "U_path": path(Up, 3, Kn), "A_path": path(Ap, 3, Kn),
-            "device_ms": ms.value}
+    return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
 
 
 class DeviceBuffer:

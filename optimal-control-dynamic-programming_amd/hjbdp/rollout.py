@@ -190,6 +190,15 @@ def RSW2ECI(pos, vel):
     return np.column_stack([R, S, W])
 
 
+def _orbit_scalars(R, V, mu):
+    """What the relative-motion right-hand side (:695-715) needs of the target's state: [2mu/|R|^3 + H^2/|R|^4, 2 (R.V) H/|R|^4,
+    2H/|R|^2, mu/|R|^3 - H^2/|R|^4, mu/|R|^3] with H = |R x V|."""
+    nR = math.sqrt(float(R @ R))
+    RdV = float(R @ V)
+    H = float(np.linalg.norm(np.cross(R, V)))
+    return [2 * mu / nR ** 3 + H * H / nR ** 4, 2 * RdV / nR ** 4 * H, 2 * H / nR ** 2, mu / nR ** 3 - H * H / nR ** 4, mu / nR ** 3]
+
+
 def ECI2body(q):
     """Solver_pos_att.m:825-829 (scalar-last quaternion)."""
     q1, q2, q3, q4 = q
@@ -243,8 +252,7 @@ def pos_att_optimal_path(pa, X0=None, n_steps=None):
     if not pa.controllers:
         raise RuntimeError("simplified_run() first")
     if X0 is None:
-        q0 = angle_to_quat(math.radians(0.0), math.radians(3.0), math.radians(0.0))[::-1]      # :461-462
-        X0 = np.concatenate([[-0.1, 0.0, 0.0], [0.0, 0.0, 0.0], q0, [0.0, 0.0, 0.0]])
+        X0 = pos_att_default_X0()                                                              # :457-466
     pol = thruster_policies(pa)
     N = pa.N_stage if n_steps is None else min(pa.N_stage, int(n_steps) + 1)
     X = np.zeros((N, 13))
@@ -262,16 +270,13 @@ def pos_att_optimal_path(pa, X0=None, n_steps=None):
         FM[k] = np.concatenate([acc, U_M])
 
         def rates(t, y, acc=acc, U_M=U_M):
-            R, V = propagate_kepler(R0, V0, t, mu)
-            nR = math.sqrt(float(R @ R))
-            RdV = float(R @ V)
-            H = float(np.linalg.norm(np.cross(R, V)))
+            c0, c1, c2, c3, c4 = _orbit_scalars(*propagate_kepler(R0, V0, t, mu), mu)
             x1, x2, x3, v1, v2, v3 = y[0:6]
             return np.concatenate([
                 [v1, v2, v3,
-                 (2 * mu / nR ** 3 + H * H / nR ** 4) * x1 - 2 * RdV / nR ** 4 * H * x2 + 2 * H / nR ** 2 * v2 + acc[0],
-                 -(mu / nR ** 3 - H * H / nR ** 4) * x2 + 2 * RdV / nR ** 4 * H * x1 - 2 * H / nR ** 2 * v1 + acc[1],
-                 -mu / nR ** 3 * x3 + acc[2]],
+                 c0 * x1 - c1 * x2 + c2 * v2 + acc[0],
+                 -c3 * x2 + c1 * x1 - c2 * v1 + acc[1],
+                 -c4 * x3 + acc[2]],
                 quat_rates(y[6:10], y[10:13]),
                 rigid_body_rates_full(y[10:13], pa.InertiaM, U_M)])
         X[k + 1] = _ode45_step(rates, k * pa.h, (k + 1) * pa.h, xs)
@@ -301,12 +306,7 @@ def pos_att_orbit_table(n_steps, h, substeps=1, R0=None, V0=None, mu=MU_EARTH):
     n_nodes = 2 * S * int(n_steps) + 1
     coef = np.empty((n_nodes, 5))
     for j in range(n_nodes):
-        R, V = propagate_kepler(R0, V0, j * h / (2 * S), mu)
-        nR = math.sqrt(float(R @ R))
-        RdV = float(R @ V)
-        H = float(np.linalg.norm(np.cross(R, V)))
-        coef[j] = [2 * mu / nR ** 3 + H * H / nR ** 4, 2 * RdV / nR ** 4 * H, 2 * H / nR ** 2,
-                   mu / nR ** 3 - H * H / nR ** 4, mu / nR ** 3]
+        coef[j] = _orbit_scalars(*propagate_kepler(R0, V0, j * h / (2 * S), mu), mu)
     return RSW2ECI(R0, V0), coef
 
 
@@ -389,102 +389,48 @@ def pos_att_channels(pa, channel_x="channel_x_controller_1"):
     return out
 
 
-def pos_att_optimal_path_fixed(pa, X0=None, n_steps=None, substeps=1, channel_x="channel_x_controller_1"):
-    """pos_att_optimal_path with `substeps` classical RK4 steps of h / substeps per stage in place of ode45, forces and moments
-    held over the stage: the scalar host loop in the operation order of the GPU kernel (K18), which it equals bit for bit.
-    Returns what pos_att_optimal_path returns: (T [N], X [N, 13], F_Th_Opt [N, 12], Force_Moment [N, 6])."""
-    chans = pos_att_channels(pa, channel_x)
-    X0 = pos_att_default_X0() if X0 is None else np.asarray(X0, dtype=np.float64).reshape(13)
-    N = pa.N_stage if n_steps is None else min(pa.N_stage, int(n_steps) + 1)
-    S = int(substeps)
-    rsw, coef = pos_att_orbit_table(N - 1, pa.h, S)
-    rsw = [[float(v) for v in row] for row in rsw]
-    rswi = [[float(v) for v in row] for row in inv3_adjugate(rsw)]
-    Jm = [[float(v) for v in row] for row in np.asarray(pa.InertiaM, dtype=np.float64)]
-    Ji = [[float(v) for v in row] for row in inv3_adjugate(Jm)]
-    mass, d, hs = float(pa.Mass), float(pa.T_dist), float(pa.h) / S
-    coef = coef.tolist()
-    kn = [[k.tolist() for k in ch[0]] for ch in chans]
-    lab = [np.asarray(ch[1]) for ch in chans]
-    tab = [ch[2].tolist() for ch in chans]
-    slots = ((0, 1, 6, 7), (2, 3, 8, 9), (4, 5, 10, 11))
-    axis = (1, 2, 0)                                   # channel x uses the angle / rate about y, y about z, z about x
-
-    def rates(c, a, um, y):
-        c0, c1, c2, c3, c4 = c
-        q1, q2, q3, q4, w1, w2, w3 = y[6:13]
-        jw = _mul3(Jm, w1, w2, w3)
-        t = [um[0] - (w2 * jw[2] - w3 * jw[1]), um[1] - (w3 * jw[0] - w1 * jw[2]), um[2] - (w1 * jw[1] - w2 * jw[0])]
-        return [y[3], y[4], y[5],
-                ((c0 * y[0] - c1 * y[1]) + c2 * y[4]) + a[0],
-                ((c1 * y[0] - c3 * y[1]) - c2 * y[3]) + a[1],
-                a[2] - c4 * y[2],
-                0.5 * (((w3 * q2) - (w2 * q3)) + (w1 * q4)),
-                0.5 * (((w1 * q3) - (w3 * q1)) + (w2 * q4)),
-                0.5 * (((w2 * q1) - (w1 * q2)) + (w3 * q4)),
-                0.5 * (((-(w1 * q1)) - (w2 * q2)) - (w3 * q3))] + _mul3(Ji, t[0], t[1], t[2])
-
-    X = np.zeros((N, 13))
-    F = np.zeros((N, 12))
-    FM = np.zeros((N, 6))
-    X[0] = X0
-    x = [float(v) for v in X0]
-    for k in range(N - 1):
-        th = [2.0 * canon_asin(1.0 if x[6 + j] > 1.0 else -1.0 if x[6 + j] < -1.0 else x[6 + j]) for j in range(3)]
-        E = _eci2body_list(x[6], x[7], x[8], x[9])
-        M = [[(E[r][0] * rsw[0][c] + E[r][1] * rsw[1][c]) + E[r][2] * rsw[2][c] for c in range(3)] for r in range(3)]
-        xb, vb = _mul3(M, x[0], x[1], x[2]), _mul3(M, x[3], x[4], x[5])
-        f = [0.0] * 12
-        for ch in range(3):
-            p = (xb[ch], vb[ch], th[axis[ch]], x[10 + axis[ch]])
-            idx = tuple(_nearest_index(kn[ch][a], p[a]) for a in range(4))
-            row = tab[ch][int(lab[ch][idx]) - 1]
-            for s_, v in zip(slots[ch], row):
-                f[s_] = v
-        um = [(((f[4] - f[5]) + f[10]) - f[11]) * d, (((f[0] - f[1]) + f[6]) - f[7]) * d, (((f[2] - f[3]) + f[8]) - f[9]) * d]
-        ab = [(((f[0] + f[1]) + f[6]) + f[7]) / mass, (((f[2] + f[3]) + f[8]) + f[9]) / mass, (((f[4] + f[5]) + f[10]) + f[11]) / mass]
-        Ei = inv3_adjugate(E).tolist()
-        ae = _mul3(Ei, ab[0], ab[1], ab[2])
-        a = _mul3(rswi, ae[0], ae[1], ae[2])
-        F[k] = f
-        FM[k] = a + um
-        for s in range(S):
-            j = 2 * (S * k + s)
-            r = rates(coef[j], a, um, x)
-            acc = r
-            xt = [x[i] + (r[i] * hs) / 2.0 for i in range(13)]
-            r = rates(coef[j + 1], a, um, xt)
-            acc = [acc[i] + 2.0 * r[i] for i in range(13)]
-            xt = [x[i] + (r[i] * hs) / 2.0 for i in range(13)]
-            r = rates(coef[j + 1], a, um, xt)
-            acc = [acc[i] + 2.0 * r[i] for i in range(13)]
-            xt = [x[i] + r[i] * hs for i in range(13)]
-            r = rates(coef[j + 2], a, um, xt)
-            x = [x[i] + (hs * (acc[i] + r[i])) / 6.0 for i in range(13)]
-        X[k + 1] = x
-    return np.arange(N) * pa.h, X, F, FM
+def _stage_angles(x, first):
+    """theta_j = 2 canon_asin(clamp(x[first + j], -1, 1)), j = 0..2: the angles a stage looks its policies up at."""
+    return [2.0 * canon_asin(1.0 if x[first + j] > 1.0 else -1.0 if x[first + j] < -1.0 else x[first + j]) for j in range(3)]
 
 
-def pos_att_fault_path_fixed(pa, X0, fault_mask, fault_stage, switch_stage, n_steps=None, substeps=1, pos_tol=math.inf,
-                             att_tol=math.inf):
-    """pos_att_optimal_path_fixed with a thruster fault in the plant and a hand-over of channel x to channel_x_controller_1_failure
-    (:235-240): the scalar host loop in the operation order of the GPU kernel (K23, csrc/kernels_rollout_pos_att_faults.h), which it
-    equals bit for bit.  From stage fault_stage (None: 0) on, the thrusters whose bit is set in fault_mask (None or 0: no fault)
-    apply +0.0 whatever was commanded; from stage switch_stage (None: never) on, channel x is looked up in the failure controller.
-    Returns (T [N], X [N, 13], F_applied [N, 12], Force_Moment [N, 6], impulse, settle_stage): impulse = h * the sum over stages
-    of ((|fa0| + |fa1|) + ...) + |fa11|; settle_stage the smallest s such that rows s .. N - 1 of X all have
-    (x0^2 + x1^2) + x2^2 <= pos_tol^2 and (q1^2 + q2^2) + q3^2 <= att_tol^2, N when the last row has not.  With no fault and no
-    hand-over the four arrays are pos_att_optimal_path_fixed's."""
-    chans = pos_att_channels(pa)
-    mask = 0 if fault_mask is None else int(fault_mask)
-    f_at = 0 if fault_stage is None else int(fault_stage)
-    X0 = pos_att_default_X0() if X0 is None else np.asarray(X0, dtype=np.float64).reshape(13)
-    N = pa.N_stage if n_steps is None else min(pa.N_stage, int(n_steps) + 1)
-    s_at = N - 1 if switch_stage is None else int(switch_stage)
-    if mask < 0 or mask >> 12 or f_at < 0 or s_at < 0:
-        raise ValueError("fault_mask has twelve bits and the stages are >= 0")
-    if s_at < N - 1:
-        chans = chans + pos_att_channels(pa, "channel_x_controller_1_failure")[:1]
+def _rk4_step(rates, x, hs, c_first, c_mid, c_last):
+    """One classical RK4 step of size hs in the kernels' operation order (HJB_ROLLOUT_RK4_STEP); rates(c, y) gets c_first at the
+    start of the step, c_mid at both midpoints and c_last at its end."""
+    n = range(len(x))
+    r = rates(c_first, x)
+    acc = r
+    xt = [x[i] + (r[i] * hs) / 2.0 for i in n]
+    r = rates(c_mid, xt)
+    acc = [acc[i] + 2.0 * r[i] for i in n]
+    xt = [x[i] + (r[i] * hs) / 2.0 for i in n]
+    r = rates(c_mid, xt)
+    acc = [acc[i] + 2.0 * r[i] for i in n]
+    xt = [x[i] + r[i] * hs for i in n]
+    r = rates(c_last, xt)
+    return [x[i] + (hs * (acc[i] + r[i])) / 6.0 for i in n]
+
+
+def _pos_att_rates(Jm, Ji, a, um, c, y):
+    """The 13-state right-hand side (:695-715) with the five orbit scalars c, the RSW acceleration a and the body moments um held."""
+    c0, c1, c2, c3, c4 = c
+    q1, q2, q3, q4, w1, w2, w3 = y[6:13]
+    jw = _mul3(Jm, w1, w2, w3)
+    t = [um[0] - (w2 * jw[2] - w3 * jw[1]), um[1] - (w3 * jw[0] - w1 * jw[2]), um[2] - (w1 * jw[1] - w2 * jw[0])]
+    return [y[3], y[4], y[5],
+            ((c0 * y[0] - c1 * y[1]) + c2 * y[4]) + a[0],
+            ((c1 * y[0] - c3 * y[1]) - c2 * y[3]) + a[1],
+            a[2] - c4 * y[2],
+            0.5 * (((w3 * q2) - (w2 * q3)) + (w1 * q4)),
+            0.5 * (((w1 * q3) - (w3 * q1)) + (w2 * q4)),
+            0.5 * (((w2 * q1) - (w1 * q2)) + (w3 * q4)),
+            0.5 * (((-(w1 * q1)) - (w2 * q2)) - (w3 * q3))] + _mul3(Ji, t[0], t[1], t[2])
+
+
+def _pos_att_stages(pa, chans, X0, N, substeps, mask, f_at, s_at, pos_tol, att_tol):
+    """The stage loop of pos_att_optimal_path_fixed and pos_att_fault_path_fixed, in the operation order of K18 / K23: chans the
+    channels x, y, z and, when s_at < N - 1, the failure controller of channel x; from stage f_at on the thrusters of mask apply
+    +0.0, from stage s_at on channel x is looked up in chans[3].  Returns pos_att_fault_path_fixed's six results."""
     S = int(substeps)
     rsw, coef = pos_att_orbit_table(N - 1, pa.h, S)
     rsw = [[float(v) for v in row] for row in rsw]
@@ -500,20 +446,6 @@ def pos_att_fault_path_fixed(pa, X0, fault_mask, fault_stage, switch_stage, n_st
     slots = ((0, 1, 6, 7), (2, 3, 8, 9), (4, 5, 10, 11))
     axis = (1, 2, 0)                                   # channel x uses the angle / rate about y, y about z, z about x
 
-    def rates(c, a, um, y):
-        c0, c1, c2, c3, c4 = c
-        q1, q2, q3, q4, w1, w2, w3 = y[6:13]
-        jw = _mul3(Jm, w1, w2, w3)
-        t = [um[0] - (w2 * jw[2] - w3 * jw[1]), um[1] - (w3 * jw[0] - w1 * jw[2]), um[2] - (w1 * jw[1] - w2 * jw[0])]
-        return [y[3], y[4], y[5],
-                ((c0 * y[0] - c1 * y[1]) + c2 * y[4]) + a[0],
-                ((c1 * y[0] - c3 * y[1]) - c2 * y[3]) + a[1],
-                a[2] - c4 * y[2],
-                0.5 * (((w3 * q2) - (w2 * q3)) + (w1 * q4)),
-                0.5 * (((w1 * q3) - (w3 * q1)) + (w2 * q4)),
-                0.5 * (((w2 * q1) - (w1 * q2)) + (w3 * q4)),
-                0.5 * (((-(w1 * q1)) - (w2 * q2)) - (w3 * q3))] + _mul3(Ji, t[0], t[1], t[2])
-
     def inside(y):
         return ((y[0] * y[0] + y[1] * y[1]) + y[2] * y[2]) <= p2 and ((y[6] * y[6] + y[7] * y[7]) + y[8] * y[8]) <= a2
 
@@ -526,7 +458,7 @@ def pos_att_fault_path_fixed(pa, X0, fault_mask, fault_stage, switch_stage, n_st
     last_outside = -1 if inside(x) else 0
     with np.errstate(all="ignore"):
         for k in range(N - 1):
-            th = [2.0 * canon_asin(1.0 if x[6 + j] > 1.0 else -1.0 if x[6 + j] < -1.0 else x[6 + j]) for j in range(3)]
+            th = _stage_angles(x, 6)
             E = _eci2body_list(x[6], x[7], x[8], x[9])
             M = [[(E[r][0] * rsw[0][c] + E[r][1] * rsw[1][c]) + E[r][2] * rsw[2][c] for c in range(3)] for r in range(3)]
             xb, vb = _mul3(M, x[0], x[1], x[2]), _mul3(M, x[3], x[4], x[5])
@@ -551,23 +483,49 @@ def pos_att_fault_path_fixed(pa, X0, fault_mask, fault_stage, switch_stage, n_st
             a = _mul3(rswi, ae[0], ae[1], ae[2])
             F[k] = f
             FM[k] = a + um
+
+            def rates(c, y, a=a, um=um):
+                return _pos_att_rates(Jm, Ji, a, um, c, y)
             for s in range(S):
                 j = 2 * (S * k + s)
-                r = rates(coef[j], a, um, x)
-                acc = r
-                xt = [x[i] + (r[i] * hs) / 2.0 for i in range(13)]
-                r = rates(coef[j + 1], a, um, xt)
-                acc = [acc[i] + 2.0 * r[i] for i in range(13)]
-                xt = [x[i] + (r[i] * hs) / 2.0 for i in range(13)]
-                r = rates(coef[j + 1], a, um, xt)
-                acc = [acc[i] + 2.0 * r[i] for i in range(13)]
-                xt = [x[i] + r[i] * hs for i in range(13)]
-                r = rates(coef[j + 2], a, um, xt)
-                x = [x[i] + (hs * (acc[i] + r[i])) / 6.0 for i in range(13)]
+                x = _rk4_step(rates, x, hs, coef[j], coef[j + 1], coef[j + 2])
             X[k + 1] = x
             if not inside(x):
                 last_outside = k + 1
     return np.arange(N) * pa.h, X, F, FM, imp * float(pa.h), last_outside + 1
+
+
+def pos_att_optimal_path_fixed(pa, X0=None, n_steps=None, substeps=1, channel_x="channel_x_controller_1"):
+    """pos_att_optimal_path with `substeps` classical RK4 steps of h / substeps per stage in place of ode45, forces and moments
+    held over the stage: the scalar host loop in the operation order of the GPU kernel (K18), which it equals bit for bit.
+    Returns what pos_att_optimal_path returns: (T [N], X [N, 13], F_Th_Opt [N, 12], Force_Moment [N, 6])."""
+    chans = pos_att_channels(pa, channel_x)
+    X0 = pos_att_default_X0() if X0 is None else np.asarray(X0, dtype=np.float64).reshape(13)
+    N = pa.N_stage if n_steps is None else min(pa.N_stage, int(n_steps) + 1)
+    return _pos_att_stages(pa, chans, X0, N, substeps, 0, 0, N - 1, math.inf, math.inf)[:4]
+
+
+def pos_att_fault_path_fixed(pa, X0, fault_mask, fault_stage, switch_stage, n_steps=None, substeps=1, pos_tol=math.inf,
+                             att_tol=math.inf):
+    """pos_att_optimal_path_fixed with a thruster fault in the plant and a hand-over of channel x to channel_x_controller_1_failure
+    (:235-240): the scalar host loop in the operation order of the GPU kernel (K23, csrc/kernels_rollout_pos_att_faults.h), which it
+    equals bit for bit.  From stage fault_stage (None: 0) on, the thrusters whose bit is set in fault_mask (None or 0: no fault)
+    apply +0.0 whatever was commanded; from stage switch_stage (None: never) on, channel x is looked up in the failure controller.
+    Returns (T [N], X [N, 13], F_applied [N, 12], Force_Moment [N, 6], impulse, settle_stage): impulse = h * the sum over stages
+    of ((|fa0| + |fa1|) + ...) + |fa11|; settle_stage the smallest s such that rows s .. N - 1 of X all have
+    (x0^2 + x1^2) + x2^2 <= pos_tol^2 and (q1^2 + q2^2) + q3^2 <= att_tol^2, N when the last row has not.  With no fault and no
+    hand-over the four arrays are pos_att_optimal_path_fixed's (one stage loop, _pos_att_stages, serves both)."""
+    chans = pos_att_channels(pa)
+    mask = 0 if fault_mask is None else int(fault_mask)
+    f_at = 0 if fault_stage is None else int(fault_stage)
+    X0 = pos_att_default_X0() if X0 is None else np.asarray(X0, dtype=np.float64).reshape(13)
+    N = pa.N_stage if n_steps is None else min(pa.N_stage, int(n_steps) + 1)
+    s_at = N - 1 if switch_stage is None else int(switch_stage)
+    if mask < 0 or mask >> 12 or f_at < 0 or s_at < 0:
+        raise ValueError("fault_mask has twelve bits and the stages are >= 0")
+    if s_at < N - 1:
+        chans = chans + pos_att_channels(pa, "channel_x_controller_1_failure")[:1]
+    return _pos_att_stages(pa, chans, X0, N, substeps, mask, f_at, s_at, pos_tol, att_tol)
 
 
 # ---- Solver_attitude, simplified policies on the rigid body: the arithmetic of the GPU loop (K20, --------------------------------
@@ -638,19 +596,6 @@ def attitude_optimal_path_simplified_fixed(sa, X0=None, n_steps=None, substeps=1
                 0.5 * (((x3 * x5) - (x2 * x6)) + (x1 * x7)), 0.5 * (((-x3 * x4) + (x1 * x6)) + (x2 * x7)),
                 0.5 * (((x2 * x4) - (x1 * x5)) + (x3 * x7)), 0.5 * (((-x1 * x4) - (x2 * x5)) - (x3 * x6))]
 
-    def rk4(rates, u, x, hh):
-        r = rates(u, x)
-        acc = r
-        xt = [x[i] + (r[i] * hh) / 2.0 for i in range(7)]
-        r = rates(u, xt)
-        acc = [acc[i] + 2.0 * r[i] for i in range(7)]
-        xt = [x[i] + (r[i] * hh) / 2.0 for i in range(7)]
-        r = rates(u, xt)
-        acc = [acc[i] + 2.0 * r[i] for i in range(7)]
-        xt = [x[i] + r[i] * hh for i in range(7)]
-        r = rates(u, xt)
-        return [x[i] + (hh * (acc[i] + r[i])) / 6.0 for i in range(7)]
-
     X = np.zeros((N, 7))
     U = np.zeros((N, 3))
     TH = np.zeros((N, 3))
@@ -659,7 +604,7 @@ def attitude_optimal_path_simplified_fixed(sa, X0=None, n_steps=None, substeps=1
     cost = 0.0
     with np.errstate(all="ignore"):
         for k in range(N - 1):
-            th = [2.0 * canon_asin(1.0 if x[3 + j] > 1.0 else -1.0 if x[3 + j] < -1.0 else x[3 + j]) for j in range(3)]
+            th = _stage_angles(x, 3)
             u = []
             for ch in range(3):
                 idx = (_nearest_index(kn[ch][0], x[ch]), _nearest_index(kn[ch][1], th[ch]))
@@ -670,9 +615,9 @@ def attitude_optimal_path_simplified_fixed(sa, X0=None, n_steps=None, substeps=1
             TH[k] = th
             if dynamics == "full":
                 for _ in range(S):
-                    x = rk4(full, u, x, hs)
+                    x = _rk4_step(full, x, hs, u, u, u)
             else:
-                x = rk4(diag, u, x, h)
+                x = _rk4_step(diag, x, h, u, u, u)
                 nrm = np.float64(math.sqrt(((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]) + x[6] * x[6]))
                 x = x[:3] + [float(np.float64(v) / nrm) for v in x[3:]]       # numpy's division: 0 / 0 is NaN, not an exception
             X[k + 1] = x
@@ -727,12 +672,7 @@ def position_rkf45_table(n_steps, h, R0=None, V0=None, mu=MU_EARTH):
             row = table[k, s]
             row[0], row[1] = hf, ha
             for j in range(6):
-                R, V = propagate_kepler(R0, V0, t + _A[j] * hf, mu)
-                nR = math.sqrt(float(R @ R))
-                RdV = float(R @ V)
-                H = float(np.linalg.norm(np.cross(R, V)))
-                row[2 + 5 * j:7 + 5 * j] = [2 * mu / nR ** 3 + H * H / nR ** 4, 2 * RdV / nR ** 4 * H, 2 * H / nR ** 2,
-                                            mu / nR ** 3 - H * H / nR ** 4, mu / nR ** 3]
+                row[2 + 5 * j:7 + 5 * j] = _orbit_scalars(*propagate_kepler(R0, V0, t + _A[j] * hf, mu), mu)
     return n_sub, table
 
 

@@ -421,18 +421,12 @@ class Solver_attitude:
         dev = self.device if device is None else int(device)
         n_lab = len(self.U_vector)
         dt = np.uint8 if n_lab < 255 else np.uint16 if n_lab < 65535 else np.int32
-        ros = []
-        try:
-            for knots, labels, ut in chans:
-                ros.append(Rollout(knots, np.asarray(labels).astype(dt, copy=False), ut, index_base=1, device=dev))
+        with Rollout.open_channels(chans, device=dev, label_dtype=dt) as ros:
             ros[0].set_attitude_simplified_model(ros[1], ros[2], self.InertiaM, self.h, substeps, dynamics,
                                                  qw=[self.Q1, self.Q2, self.Q3], qt=[self.Qt1, self.Qt2, self.Qt3],
                                                  r=[self.R1, self.R2, self.R3])
             planes = np.arange(N - 1, dtype=np.int32) if per_stage else np.zeros(N - 1, np.int32)
             out = ros[0].run_attitude_simplified(X0s, planes, keep_path=keep_path)
-        finally:
-            for ro in ros:
-                ro.close()
         if not keep_path:
             return out["X_final"], out["cost"]
         n = X0s.shape[1]

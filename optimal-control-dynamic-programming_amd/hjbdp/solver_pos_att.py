@@ -279,6 +279,16 @@ class Solver_pos_att:
         from . import rollout
         return rollout.pos_att_optimal_path(self, X0, n_steps)
 
+    def _paths_setup(self, X0s, n_steps, substeps, device):
+        """What get_optimal_paths and get_fault_campaign open with: the starts [13, n] (None: the reference's X0), N, the arguments
+        of Rollout.set_pos_att_model after the two channels, and the device."""
+        from . import rollout
+        X0s = rollout.pos_att_default_X0().reshape(13, 1) if X0s is None else np.asarray(X0s, dtype=np.float64).reshape(13, -1)
+        N = self.N_stage if n_steps is None else min(self.N_stage, int(n_steps) + 1)
+        rsw, coef = rollout.pos_att_orbit_table(N - 1, self.h, substeps)
+        model = (self.InertiaM, self.Mass, self.T_dist, self.h, rsw, coef, substeps)
+        return X0s, N, model, self.device if device is None else int(device)
+
     def get_optimal_paths(self, X0s=None, n_steps=None, substeps=1, channel_x="channel_x_controller_1", keep_path=False, device=None):
         """get_optimal_path (:452-730) for many initial states at once on the GPU (hjbdp.Rollout.run_pos_att, K18), after
         simplified_run().  X0s [13, n] (None: the reference's X0, :457-466).  The three channel policies are built once from
@@ -290,19 +300,10 @@ class Solver_pos_att:
         from . import rollout
         from .core import Rollout
         chans = rollout.pos_att_channels(self, channel_x)                     # RuntimeError without simplified_run()
-        X0s = rollout.pos_att_default_X0().reshape(13, 1) if X0s is None else np.asarray(X0s, dtype=np.float64).reshape(13, -1)
-        N = self.N_stage if n_steps is None else min(self.N_stage, int(n_steps) + 1)
-        rsw, coef = rollout.pos_att_orbit_table(N - 1, self.h, substeps)
-        dev = self.device if device is None else int(device)
-        ros = []
-        try:
-            for knots, labels, table in chans:
-                ros.append(Rollout(knots, labels, table, index_base=1, device=dev))
-            ros[0].set_pos_att_model(ros[1], ros[2], self.InertiaM, self.Mass, self.T_dist, self.h, rsw, coef, substeps)
+        X0s, N, model, dev = self._paths_setup(X0s, n_steps, substeps, device)
+        with Rollout.open_channels(chans, device=dev) as ros:
+            ros[0].set_pos_att_model(ros[1], ros[2], *model)
             out = ros[0].run_pos_att(X0s, keep_path=keep_path)
-        finally:
-            for ro in ros:
-                ro.close()
         if not keep_path:
             return out["X_final"]
         n = X0s.shape[1]
@@ -327,17 +328,8 @@ class Solver_pos_att:
         from . import rollout
         from .core import Rollout
         chans = rollout.pos_att_channels(self) + rollout.pos_att_channels(self, "channel_x_controller_1_failure")[:1]
-        X0s = rollout.pos_att_default_X0().reshape(13, 1) if X0s is None else np.asarray(X0s, dtype=np.float64).reshape(13, -1)
-        N = self.N_stage if n_steps is None else min(self.N_stage, int(n_steps) + 1)
-        rsw, coef = rollout.pos_att_orbit_table(N - 1, self.h, substeps)
-        dev = self.device if device is None else int(device)
-        ros = []
-        try:
-            for knots, labels, table in chans:
-                ros.append(Rollout(knots, labels, table, index_base=1, device=dev))
-            ros[0].set_pos_att_model(ros[1], ros[2], self.InertiaM, self.Mass, self.T_dist, self.h, rsw, coef, substeps)
+        X0s, _, model, dev = self._paths_setup(X0s, n_steps, substeps, device)
+        with Rollout.open_channels(chans, device=dev) as ros:
+            ros[0].set_pos_att_model(ros[1], ros[2], *model)
             ros[0].set_pos_att_fault_controller(ros[3])
             return ros[0].run_pos_att_faults(X0s, None, fault_mask, fault_stage, switch_stage, pos_tol, att_tol, keep_path)
-        finally:
-            for ro in ros:
-                ro.close()

@@ -195,10 +195,7 @@ class Solver_position:
         n_sub, table = rollout.position_rkf45_table(N - 1, self.h, R0, V0)
         dev = self.device if device is None else int(device)
         n = y0s.shape[1]
-        ros = []
-        try:
-            for knots, labels, ut in chans:
-                ros.append(Rollout(knots, labels, ut, index_base=1, device=dev))
+        with Rollout.open_channels(chans, device=dev) as ros:
             if N > 1:
                 ros[0].set_position_model(ros[1], ros[2], n_sub, table, tol)
                 out = ros[0].run_position(y0s, keep_path=keep_path)
@@ -212,9 +209,6 @@ class Solver_position:
                 Xp = out["X_path"] if keep_path else ros[0].run_position(y0s[:, flagged], np.zeros(int(off[flagged].max()) + 1, np.int32), keep_path=True)["X_path"]
                 rows = flagged if keep_path else np.arange(flagged.size)
                 redo = [int(i) for i, r in zip(flagged, rows) if np.isfinite(Xp[r, :, off[i]:off[i] + 2]).all()]
-        finally:
-            for ro in ros:
-                ro.close()
         self.off_schedule = off
         self.off_schedule_recomputed = len(redo)
         Xf = np.array(out["X_final"])

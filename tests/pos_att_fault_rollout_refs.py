@@ -14,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 
 from attitude_rollout_refs import asinc
-from pos_att_rollout_refs import AXIS, SLOTS, eci2body, inv3, mul3, rates
+from pos_att_rollout_refs import AXIS, SLOTS, eci2body, inv3, moments_and_acceleration, mul3, prepare_channels, rk4_stage
 
 
 def rollout(channels, fault_channel, inertia, mass, t_dist, h, substeps, rsw2eci, coef, X0, plane_of_step, fault_mask=None,
@@ -27,12 +27,7 @@ def rollout(channels, fault_channel, inertia, mass, t_dist, h, substeps, rsw2eci
     nominal controller of channel x gives at the same state)."""
     from hjbdp import _abi
     from oracle import c_oracle
-    chans = []
-    for knots, labels, ut, base in list(channels) + ([fault_channel] if fault_channel is not None else []):
-        ks = [np.asarray(k, dtype=np.float64) for k in knots]
-        nS = int(np.prod([len(k) for k in ks]))
-        lab = np.asarray(labels).reshape(-1, order="F").reshape((nS, -1), order="F")
-        chans.append((ks, lab, np.asarray(ut, dtype=np.float64).reshape(-1, 4), int(base), {}))
+    chans = prepare_channels(list(channels) + ([fault_channel] if fault_channel is not None else []))
     J = [float(v) for v in np.asarray(inertia, dtype=np.float64).reshape(9)]
     Ji = [float(v) for v in inv3(np.array(J))]
     RSW = [float(v) for v in np.asarray(rsw2eci, dtype=np.float64).reshape(9)]
@@ -95,27 +90,10 @@ def rollout(channels, fault_channel, inertia, mass, t_dist, h, substeps, rsw2eci
             for j in range(2, 12):
                 sk = sk + np.abs(f[j])
             imp = imp + sk
-            um = [(((f[4] - f[5]) + f[10]) - f[11]) * t_dist, (((f[0] - f[1]) + f[6]) - f[7]) * t_dist,
-                  (((f[2] - f[3]) + f[8]) - f[9]) * t_dist]
-            ab = [(((f[0] + f[1]) + f[6]) + f[7]) / mass, (((f[2] + f[3]) + f[8]) + f[9]) / mass, (((f[4] + f[5]) + f[10]) + f[11]) / mass]
-            Ei = inv3(np.stack(E))
-            ae = mul3(Ei, ab[0], ab[1], ab[2])
-            a = mul3(RSWi, ae[0], ae[1], ae[2])
+            um, a = moments_and_acceleration(f, E, RSWi, mass, t_dist)
             F_path[:, :, k] = f.T
             FM_path[:, :, k] = np.stack(a + um, axis=1)
-            for sub in range(S):
-                j = 2 * (S * k + sub)
-                r = rates(J, Ji, coef[j], a, um, x)
-                acc = r
-                xt = x + (r * hs) / 2.0
-                r = rates(J, Ji, coef[j + 1], a, um, xt)
-                acc = acc + 2.0 * r
-                xt = x + (r * hs) / 2.0
-                r = rates(J, Ji, coef[j + 1], a, um, xt)
-                acc = acc + 2.0 * r
-                xt = x + r * hs
-                r = rates(J, Ji, coef[j + 2], a, um, xt)
-                x = x + (hs * (acc + r)) / 6.0
+            x = rk4_stage(J, Ji, coef, k, S, hs, a, um, x)
             X_path[:, :, k + 1] = x.T
             last_outside = np.where(outside(x), k + 1, last_outside)
         impulse = imp * np.float64(h)

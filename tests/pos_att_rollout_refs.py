@@ -53,18 +53,53 @@ def rates(J, Ji, c, a, um, y):
                      0.5 * (((-(w1 * q1)) - (w2 * q2)) - (w3 * q3))] + mul3(Ji, t[0], t[1], t[2]))
 
 
-def rollout(channels, inertia, mass, t_dist, h, substeps, rsw2eci, coef, X0, plane_of_step):
-    """channels: for x, y, z (knots [4 grid vectors], labels nS x n_planes (column-major, any shape), u_table [n_labels, 4],
-    index_base); inertia, rsw2eci [3, 3]; coef [n_nodes, 5]; X0 [13, n].
-    Returns X_final [13, n], X_path [n, 13, K+1], F_path [n, 12, K], FM_path [n, 6, K]."""
-    from hjbdp import _abi
-    from oracle import c_oracle
+def prepare_channels(channels):
+    """(knots, labels, u_table, index_base) per channel -> (knots, labels [nS, n_planes], u_table [n_labels, 4], index_base, a cache
+    of the planes as dense double values)."""
     chans = []
     for knots, labels, ut, base in channels:
         ks = [np.asarray(k, dtype=np.float64) for k in knots]
         nS = int(np.prod([len(k) for k in ks]))
         lab = np.asarray(labels).reshape(-1, order="F").reshape((nS, -1), order="F")
         chans.append((ks, lab, np.asarray(ut, dtype=np.float64).reshape(-1, 4), int(base), {}))
+    return chans
+
+
+def moments_and_acceleration(f, E, RSWi, mass, t_dist):
+    """Thruster levels f [12, n] at attitude E = eci2body(q) -> (U_M [3], a [3]): the body moments and the acceleration in RSW."""
+    um = [(((f[4] - f[5]) + f[10]) - f[11]) * t_dist, (((f[0] - f[1]) + f[6]) - f[7]) * t_dist,
+          (((f[2] - f[3]) + f[8]) - f[9]) * t_dist]
+    ab = [(((f[0] + f[1]) + f[6]) + f[7]) / mass, (((f[2] + f[3]) + f[8]) + f[9]) / mass, (((f[4] + f[5]) + f[10]) + f[11]) / mass]
+    Ei = inv3(np.stack(E))
+    ae = mul3(Ei, ab[0], ab[1], ab[2])
+    return um, mul3(RSWi, ae[0], ae[1], ae[2])
+
+
+def rk4_stage(J, Ji, coef, k, S, hs, a, um, x):
+    """Stage k: S classical RK4 sub-steps of hs with a and um held, the orbit scalars from nodes 2 (S k + s) + {0, 1, 1, 2}."""
+    for sub in range(S):
+        j = 2 * (S * k + sub)
+        r = rates(J, Ji, coef[j], a, um, x)
+        acc = r
+        xt = x + (r * hs) / 2.0
+        r = rates(J, Ji, coef[j + 1], a, um, xt)
+        acc = acc + 2.0 * r
+        xt = x + (r * hs) / 2.0
+        r = rates(J, Ji, coef[j + 1], a, um, xt)
+        acc = acc + 2.0 * r
+        xt = x + r * hs
+        r = rates(J, Ji, coef[j + 2], a, um, xt)
+        x = x + (hs * (acc + r)) / 6.0
+    return x
+
+
+def rollout(channels, inertia, mass, t_dist, h, substeps, rsw2eci, coef, X0, plane_of_step):
+    """channels: for x, y, z (knots [4 grid vectors], labels nS x n_planes (column-major, any shape), u_table [n_labels, 4],
+    index_base); inertia, rsw2eci [3, 3]; coef [n_nodes, 5]; X0 [13, n].
+    Returns X_final [13, n], X_path [n, 13, K+1], F_path [n, 12, K], FM_path [n, 6, K]."""
+    from hjbdp import _abi
+    from oracle import c_oracle
+    chans = prepare_channels(channels)
     J = [float(v) for v in np.asarray(inertia, dtype=np.float64).reshape(9)]
     Ji = [float(v) for v in inv3(np.array(J))]
     RSW = [float(v) for v in np.asarray(rsw2eci, dtype=np.float64).reshape(9)]
@@ -96,26 +131,9 @@ def rollout(channels, inertia, mass, t_dist, h, substeps, rsw2eci, coef, X0, pla
                 L = c_oracle.lookup(_abi, ks, dense[p], pts, "nearest").astype(np.int64) - base
                 for j, slot in enumerate(SLOTS[ch]):
                     f[slot] = ut[L, j]
-            um = [(((f[4] - f[5]) + f[10]) - f[11]) * t_dist, (((f[0] - f[1]) + f[6]) - f[7]) * t_dist,
-                  (((f[2] - f[3]) + f[8]) - f[9]) * t_dist]
-            ab = [(((f[0] + f[1]) + f[6]) + f[7]) / mass, (((f[2] + f[3]) + f[8]) + f[9]) / mass, (((f[4] + f[5]) + f[10]) + f[11]) / mass]
-            Ei = inv3(np.stack(E))
-            ae = mul3(Ei, ab[0], ab[1], ab[2])
-            a = mul3(RSWi, ae[0], ae[1], ae[2])
+            um, a = moments_and_acceleration(f, E, RSWi, mass, t_dist)
             F_path[:, :, k] = f.T
             FM_path[:, :, k] = np.stack(a + um, axis=1)
-            for sub in range(S):
-                j = 2 * (S * k + sub)
-                r = rates(J, Ji, coef[j], a, um, x)
-                acc = r
-                xt = x + (r * hs) / 2.0
-                r = rates(J, Ji, coef[j + 1], a, um, xt)
-                acc = acc + 2.0 * r
-                xt = x + (r * hs) / 2.0
-                r = rates(J, Ji, coef[j + 1], a, um, xt)
-                acc = acc + 2.0 * r
-                xt = x + r * hs
-                r = rates(J, Ji, coef[j + 2], a, um, xt)
-                x = x + (hs * (acc + r)) / 6.0
+            x = rk4_stage(J, Ji, coef, k, S, hs, a, um, x)
             X_path[:, :, k + 1] = x.T
     return x, X_path, F_path, FM_path

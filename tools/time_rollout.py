@@ -165,8 +165,7 @@ def case_pos_att_loop(host=True, n_stages=None):
            "timing": "host wall clock around hjb_rollout_run_pos_att (upload + kernel + download of X_final), best of 3"}
     chans = rollout.pos_att_channels(pa)
     x0 = rollout.pos_att_default_X0()
-    ros = [hjbdp.Rollout(k, l, t, index_base=1) for k, l, t in chans]
-    try:
+    with hjbdp.Rollout.open_channels(chans) as ros:
         for name, n_traj, S in (("n262144_s1", 1 << 18, 1), ("n4096_s1", 1 << 12, 1), ("n262144_s4", 1 << 18, 4)):
             X0 = np.tile(x0.reshape(13, 1), (1, n_traj))
             X0[0:3] += rng.uniform(-0.05, 0.05, size=(3, n_traj))
@@ -183,9 +182,6 @@ def case_pos_att_loop(host=True, n_stages=None):
                 best = dt if best is None else min(best, dt)
             res[name] = {"n_traj": int(n_traj), "substeps": S, "ms_per_launch": round(best * 1e3, 3),
                          "traj_stages_per_s": n_traj * K / best}
-    finally:
-        for ro in ros:
-            ro.close()
     if host:
         t0 = time.perf_counter()
         rollout.pos_att_optimal_path(pa, n_steps=300)
@@ -221,8 +217,7 @@ def case_position_loop(host=True, n_traj=100000, n_stages=None):
     res = {"grid": "201x201 per channel", "n_traj": int(n_traj), "n_steps": int(K), "sub_steps_per_stage": int(n_sub.max()),
            "sweep_wall_s": round(sweep_s, 3), "table_build_s": round(table_s, 3),
            "timing": "host wall clock around hjb_rollout_run_position (upload + kernel + download of X_final and off_schedule), best of 3"}
-    ros = [hjbdp.Rollout(k, l, t, index_base=1) for k, l, t in rollout.position_channels(sp)]
-    try:
+    with hjbdp.Rollout.open_channels(rollout.position_channels(sp)) as ros:
         res["labels"] = str(ros[0].labels_dtype)
         ros[0].set_position_model(ros[1], ros[2], n_sub, table)
         out = ros[0].run_position(X0)                            # warm-up, same shape
@@ -232,9 +227,6 @@ def case_position_loop(host=True, n_traj=100000, n_stages=None):
             ros[0].run_position(X0)
             dt = time.perf_counter() - t0
             best = dt if best is None else min(best, dt)
-    finally:
-        for ro in ros:
-            ro.close()
     res.update(ms_per_launch=round(best * 1e3, 3), traj_stages_per_s=n_traj * K / best, off_schedule=int((out["off_schedule"] >= 0).sum()))
     if host:
         t0 = time.perf_counter()
@@ -275,8 +267,7 @@ def case_attitude_simplified_loop(host=True, n_traj=100000, n_stages=None):
            "dynamics": "full", "substeps": 1, "sweep_wall_s": round(sweep_s, 3),
            "timing": "host wall clock around hjb_rollout_run_attitude_simplified (upload + kernel + download of X_final and cost), "
                      "5 calls after a warm-up"}
-    ros = [hjbdp.Rollout(k, np.asarray(l).astype(np.uint8), t, index_base=1) for k, l, t in chans]
-    try:
+    with hjbdp.Rollout.open_channels(chans, label_dtype=np.uint8) as ros:
         res["labels"] = str(ros[0].labels_dtype)
         ros[0].set_attitude_simplified_model(ros[1], ros[2], sa.InertiaM, sa.h, 1, "full", qw=[sa.Q1, sa.Q2, sa.Q3],
                                              qt=[sa.Qt1, sa.Qt2, sa.Qt3], r=[sa.R1, sa.R2, sa.R3])
@@ -287,9 +278,6 @@ def case_attitude_simplified_loop(host=True, n_traj=100000, n_stages=None):
             t0 = time.perf_counter()
             ros[0].run_attitude_simplified(X0, planes)
             times.append(time.perf_counter() - t0)
-    finally:
-        for ro in ros:
-            ro.close()
     med = float(np.median(times))
     res.update(ms_per_call=[round(t * 1e3, 3) for t in times], ms_per_call_median=round(med * 1e3, 3), traj_stages_per_s=n_traj * K / med,
                finite_final=int(np.isfinite(out["X_final"]).all(axis=0).sum()))
@@ -395,8 +383,7 @@ def case_pos_att_faults(host=True, n_traj=1 << 18, n_stages=None):
            "sweep_wall_s": round(sweep_s, 3),
            "timing": "wall_ms: host clock around the whole call (upload + kernel + download); device_ms: event times around the "
                      "launches (K23 only); the three runs alternate in one process, 5 rounds after a warm-up round"}
-    ros = [hjbdp.Rollout(k, l, t, index_base=1) for k, l, t in chans]
-    try:
+    with hjbdp.Rollout.open_channels(chans) as ros:
         ros[0].set_pos_att_model(ros[1], ros[2], pa.InertiaM, pa.Mass, pa.T_dist, pa.h, rsw, coef, 1)
         ros[0].set_pos_att_fault_controller(ros[3])
         runs = (("a_run_pos_att", lambda: ros[0].run_pos_att(X0)),
@@ -415,9 +402,6 @@ def case_pos_att_faults(host=True, n_traj=1 << 18, n_stages=None):
                 if rnd == 5 and name == "c_faults_mixed":
                     res["c_settled"] = int((out["settle_stage"] <= K).sum())
                     res["c_impulse_median_Ns"] = float(np.median(out["impulse"]))
-    finally:
-        for ro in ros:
-            ro.close()
     for name, _ in runs:
         med = float(np.median(wall[name]))
         res[name] = {"wall_ms": [round(t, 3) for t in wall[name]], "wall_ms_median": round(med, 3),
