@@ -366,7 +366,9 @@ int32_t hjb_probe_stage(hjb_handle h, const void *J_next, const hjb_probe *probe
  * Options (hjb_set_option): "eval_grid" workgroups per launch (0 = one per 256 states; the kernel strides), "eval_tables" the
  * source of cells and weights: -1 the handle's (cell, weight) tables where they fit, 0 the terms summed in the kernel, 1 tables;
  * "eval_i32" 0 runs the kernel's 64-bit form even where every index fits 31 bits, "eval_m24" 0 its 32-bit form without 24-bit
- * index products even where every factor fits 24 bits (same bits either way; timing experiments, tests). */
+ * index products even where every factor fits 24 bits (same bits either way; timing experiments, tests).  hjb_get_option
+ * "eval_form" (read-only: setting it is HJB_E_INVALID) is the form the next launch runs from the source in effect: 0 64-bit,
+ * 1 32-bit, 2 32-bit with 24-bit index products. */
 int32_t hjb_evaluate_stage(hjb_handle h, const void *J_next, const void *labels, void *J_out);
 int32_t hjb_evaluate_stage_device(hjb_handle h, const void *dJ_next, const void *d_labels, void *dJ_out, void *stream);
 int32_t hjb_evaluate(hjb_handle h, int32_t n_stages, const void *terminal, const void *labels, int32_t labels_per_stage,

@@ -442,6 +442,7 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
         h->eval_m24 = value != 0;
         return HJB_OK;
     }
+    if (!strcmp(key, "eval_form")) return fail(h, HJB_E_INVALID, "eval_form is read-only: the form follows from the sizes, eval_i32, eval_m24 and eval_tables");
     if (!strcmp(key, "eval_tables")) {      // the fixed-label stage's cells and weights: -1 automatic, 0 terms summed on the fly, 1 the (cell, t) tables
         if (value < -1 || value > 1) return fail(h, HJB_E_INVALID, "eval_tables must be -1, 0 or 1");
         if (value == 0 && h->tab64) return fail(h, HJB_E_UNSUPPORTED, "eval_tables 0: table_dtype HJB_TAB_F64 is evaluated from the tables only");
@@ -474,6 +475,7 @@ int32_t hjb_get_option(hjb_handle hh, const char *key, int64_t *value) {
     else if (!strcmp(key, "eval_grid")) *value = h->eval_grid;
     else if (!strcmp(key, "eval_m24")) *value = h->eval_m24 ? 1 : 0;
     else if (!strcmp(key, "eval_i32")) *value = eval_runs_i32(h) ? 1 : 0;     // the form that would run
+    else if (!strcmp(key, "eval_form")) *value = eval_form(h);                // 0 64-bit, 1 32-bit, 2 32-bit with 24-bit products: the next launch's
     else if (!strcmp(key, "eval_tables")) *value = h->eval_tables < 0 ? (h->tabled_ok ? 1 : 0) : h->eval_tables;      // the source in effect
     else if (!strcmp(key, "idx_bytes")) *value = h->idx_bytes;
     else if (!strcmp(key, "temporal")) *value = h->use_temporal;

@@ -241,26 +241,37 @@ int launch_evaluate(Handle *h, const void *dJn, const void *dlabels, void *dJo, 
     EvalDiv dv{};                                          // the divisors the kernel takes a state index and a label apart by
     for (int d = 0; d < HJB_MAX_D; ++d) dv.n[d] = hjb::magic_div(d < h->hp.D ? (uint32_t)h->hp.n[d] : 1u);
     for (int c = 0; c < 2; ++c) dv.m[c] = hjb::magic_div((uint32_t)h->hp.m[c]);
-    // 24-bit index products: every factor the 32-bit form multiplies below 2^24 - sizes, the quotients of the state index (the
-    // first is the largest), the J strides, the strides of the tables or terms it reads and of the cost terms.  Strides are never
-    // negative: make_term and axis_domain form them as products of sizes (0 = broadcast), so an upper bound is a bound
-    bool mul24 = a.idx32 && h->eval_m24;
-    {
-        constexpr int64_t k24 = (int64_t)1 << 24;
-        const DParams &P = h->hp;
-        auto small = [&](const DTerm &t) { for (int d = 0; d < HJB_MAX_G; ++d) if (t.stride[d] >= k24) return false; return true; };
-        mul24 = mul24 && h->n_owned / P.n[0] < k24 && h->nU < k24;
-        for (int d = 0; d < P.D && mul24; ++d) {
-            mul24 = h->prob.n[d] < k24 && P.jstride[d] < k24 && h->nplanes < k24;      // (prob.n: the GLOBAL sizes the terms are indexed by)
-            for (int k = 0; k < HJB_MAX_D && mul24 && tabled; ++k) mul24 = h->htb.ax[d].sstride[k] < k24;
-            for (int k = 0; k < HJB_MAX_C && mul24 && tabled; ++k) mul24 = h->htb.ax[d].cstride[k] < k24;
-            for (int k = 0; k < P.axis[d].n_terms && mul24 && !tabled; ++k) mul24 = small(P.axis[d].t[k]);
-        }
-        for (int k = 0; k < P.n_cost && mul24; ++k) mul24 = small(P.cost[k]);      // (cost64[] has the same strides)
-    }
-    if (stage_evaluate(a, tabled, mul24, dlabels, h->d_status + 1, dv)) return fail(h, HJB_E_UNSUPPORTED, "the fixed-label stage has no kernel for D=%d, dtype %d", a.D, h->dtype);
+    if (stage_evaluate(a, tabled, eval_runs_m24(h, tabled), dlabels, h->d_status + 1, dv)) return fail(h, HJB_E_UNSUPPORTED, "the fixed-label stage has no kernel for D=%d, dtype %d", a.D, h->dtype);
     HIP_TRY(h, hipGetLastError());
     return HJB_OK;
+}
+
+// 24-bit index products: every factor the 32-bit form multiplies below 2^24 - sizes, the quotients of the state index (the
+// first is the largest), the J strides, the strides of the tables or terms it reads and of the cost terms.  Strides are never
+// negative: make_term and axis_domain form them as products of sizes (0 = broadcast), so an upper bound is a bound.  The table
+// strides are axis_domain's, which ensure_tabled copies into the tables it builds: the answer is the same before and after the
+// first launch has built them.  cost64[] is made from the same hjb_term as cost[] (upload_cost): the same strides.
+bool eval_runs_m24(const Handle *h, bool tabled) {
+    constexpr int64_t k24 = (int64_t)1 << 24;
+    const DParams &P = h->hp;
+    auto small = [&](const DTerm &t) { for (int d = 0; d < HJB_MAX_G; ++d) if (t.stride[d] >= k24) return false; return true; };
+    bool mul24 = eval_runs_i32(h) && h->eval_m24;
+    mul24 = mul24 && h->n_owned / P.n[0] < k24 && h->nU < k24;
+    for (int d = 0; d < P.D && mul24; ++d) {
+        mul24 = h->prob.n[d] < k24 && P.jstride[d] < k24 && h->nplanes < k24;      // (prob.n: the GLOBAL sizes the terms are indexed by)
+        if (mul24 && tabled) {
+            const AxisDomain dom = axis_domain(h, h->dom_mask[d]);
+            for (int k = 0; k < P.D + P.C && mul24; ++k) mul24 = dom.stride[k] < k24;      // (DTabled::Axis sstride[], cstride[])
+        }
+        for (int k = 0; k < P.axis[d].n_terms && mul24 && !tabled; ++k) mul24 = small(P.axis[d].t[k]);
+    }
+    for (int k = 0; k < P.n_cost && mul24; ++k) mul24 = small(P.cost[k]);
+    return mul24;
+}
+
+int eval_form(const Handle *h) {
+    const bool tabled = h->eval_tables < 0 ? h->tabled_ok : h->eval_tables == 1;      // (prepare_evaluate's source, nothing built)
+    return eval_runs_m24(h, tabled) ? 2 : eval_runs_i32(h) ? 1 : 0;
 }
 
 }  // namespace hjbhost

@@ -279,7 +279,7 @@ int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t 
 // evaluation builds the (cell, t) tables it reads if no stage kernel has yet - allocation and a wait on the null stream, so that
 // first call must not sit inside a stream capture (include/hjbdp.h says so); later calls find them built and do no such work.
 // launch_evaluate: one stage (dJn, dlabels -> dJo) on st; it calls prepare_evaluate itself.
-// eval_grid_of / eval_runs_i32: the launch size and whether the kernel's 32-bit index form runs - the one statement of each.
+// eval_grid_of / eval_runs_i32 / eval_runs_m24: the launch size and which index form of the kernel runs - the one statement of each.
 int prepare_evaluate(Handle *h, bool *tabled);
 int launch_evaluate(Handle *h, const void *dJn, const void *dlabels, void *dJo, hipStream_t st);
 // one workgroup per 256 states; beyond 2^22 workgroups (2^30 states) equally long grid-stride spans; option "eval_grid" overrides
@@ -292,6 +292,11 @@ inline int64_t eval_grid_of(const Handle *h) {
 inline bool eval_runs_i32(const Handle *h) {
     return h->eval_i32 && h->n_owned < kTab32Lim && h->j_elems < kTab32Lim && eval_grid_of(h) * 256 <= ((int64_t)1 << 31);
 }
+// the 32-bit form with 24-bit index products (hjbdp_choose.hip): eval_runs_i32 and every factor the kernel multiplies below 2^24.
+// tabled: the source of cells and weights the launch reads (prepare_evaluate) - tables and terms have strides of their own.
+// eval_form: what the next launch runs from the source in effect (option "eval_form"): 0 64-bit, 1 32-bit, 2 32-bit with 24-bit products
+bool eval_runs_m24(const Handle *h, bool tabled);
+int eval_form(const Handle *h);
 // the handle's part of a stage launch: stream, typing, parameter records, buffers (grid, block, LDS and the form are the caller's)
 inline StageArgs stage_args(const Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t st) {
     StageArgs a;

@@ -11,6 +11,9 @@ Problem._sum, cell_and_weight, interp_linear).  Two lerp forms:
                  own.  Fed the C twin's labels it reproduces the C twin's J bit for bit (tests/test_evaluate_abi.py), which is what
                  makes it the bit-exact reference for arbitrary labels on the GPU: the two oracles differ by a few ulp exactly
                  because of this one rounding (tests/test_oracle_golden.py).
+
+evaluate_ref forms whole-grid arrays; evaluate_ref_states is the same canonical form for a list of states, with J_next behind a
+callable (grids too large for the host: tests/test_gpu_evaluate_forms.py).
 """
 from __future__ import annotations
 
@@ -86,3 +89,44 @@ def evaluate_ref(p, J_next, labels, lerp="oracle"):
     for a in range(p.D):                                             # axis 0 first, as interp_linear
         vals = [fma(ts[a], (vals[j + 1] - vals[j]).astype(dt, copy=False), vals[j]) for j in range(0, len(vals), 2)]
     return (g[at] + vals[0]).astype(dt, copy=False)
+
+
+def evaluate_ref_states(p, states, labels_at_states, jnext_at):
+    """evaluate_ref's canonical (fma) form for a LIST of states - nothing of the grid's size is formed, so it serves grids of 10^7
+    .. 10^10 states.  states: flat whole-grid state indices (column-major, axis 0 fastest); labels_at_states: the 0-based flat
+    control label of each listed state; jnext_at(idx): J_next, in p.dtype, at the tuple idx of D integer index arrays (an array
+    lookup for a J the host holds, the ordered float32 sum of float64_refs.ordered_sum for fill_separable's terminal cost).
+    -> J [len(states)] in p.dtype.  Same arithmetic as evaluate_ref(lerp="fma"): ordered term sums, cell_and_weight, the 2^D corners
+    lerped axis 0 first with the exact fma, then g + v (tests/test_evaluate_abi.py holds the two equal, and this one to the C twin)."""
+    dt = p.dtype
+    states = np.asarray(states, dtype=np.int64)
+    lab = np.asarray(labels_at_states).astype(np.int64)
+    assert states.shape == lab.shape and states.ndim == 1
+    assert states.min() >= 0 and states.max() < int(np.prod([int(x) for x in p.n], dtype=object))
+    assert lab.min() >= 0 and lab.max() < p.nU
+    at = tuple(np.unravel_index(states, p.n, order="F")) + tuple(np.unravel_index(lab, p.m, order="F"))
+
+    def osum(terms):                                                 # Problem._sum at the listed (state, control) pairs
+        acc = None
+        for t in terms:
+            x = np.broadcast_to(t.data[tuple(at[d] for d in t.dims)], states.shape)
+            acc = x if acc is None else (acc + x).astype(dt, copy=False)
+        return acc
+    fma = _fma32 if dt == np.float32 else _fma64
+    cells, ts = [], []
+    for a in range(p.D):
+        i, t = hjb_oracle.cell_and_weight(p.knots[a], osum(p.next_terms[a]))
+        cells.append(i)
+        ts.append(t)
+    vals = [np.asarray(jnext_at(tuple(cells[a] + ((corner >> a) & 1) for a in range(p.D))), dtype=dt) for corner in range(1 << p.D)]
+    for a in range(p.D):                                             # axis 0 first, as interp_linear
+        vals = [fma(ts[a], (vals[j + 1] - vals[j]).astype(dt, copy=False), vals[j]) for j in range(0, len(vals), 2)]
+    return (osum(p.cost_terms) + vals[0]).astype(dt, copy=False)
+
+
+def separable_jnext(vecs, dtype, storage):
+    """jnext_at for fill_separable's terminal cost: ((v0[i0] + v1[i1]) + ...) in `dtype`, rounded once to `storage` (what the
+    device buffer holds) and widened back to `dtype` (what the kernels read)."""
+    from float64_refs import ordered_sum
+    vs = [np.asarray(v, dtype=dtype) for v in vecs]
+    return lambda idx: ordered_sum([v[i] for v, i in zip(vs, idx)], dtype).astype(storage).astype(dtype)

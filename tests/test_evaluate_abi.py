@@ -122,6 +122,40 @@ def test_evaluate_ref_reproduces_both_oracles_on_their_own_labels(built, n, m, d
         assert not np.array_equal(evaluate_ref(p, term, swapped), Jn)
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("n,m", CASES)
+def test_evaluate_ref_states_is_the_whole_grid_reference_state_by_state(built, n, m, dtype):
+    """evaluate_ref_states over every state = evaluate_ref(lerp='fma') bit for bit, on seeded random labels, in a shuffled state
+    order and on a subset; on the C twin's own labels = the C twin's J; and with J_next behind separable_jnext = the same with the
+    separable array (float32 arithmetic, float32 and binary16 storage: what fill_separable leaves on the device)."""
+    from hjbdp import _abi
+    from oracle import c_oracle
+    from evaluate_refs import evaluate_ref, evaluate_ref_states, oracle_problem, separable_jnext
+    from float64_refs import separable_ref
+    from problems import random_problem, random_terminal
+    spec = random_problem(40 + len(n) + 7 * len(m), n, m, dtype=dtype, nonuniform=len(n) % 2 == 0, index_base=1)
+    term = random_terminal(spec, 5)
+    p = oracle_problem(spec)
+    rng = np.random.default_rng(12)
+    lab = rng.integers(0, spec.nU, spec.nS)
+    Jn = term.reshape(n, order="F")
+    whole = evaluate_ref(p, term, lab, lerp="fma").reshape(-1, order="F")
+    states = np.arange(spec.nS)
+    got = evaluate_ref_states(p, states, lab, lambda idx: Jn[idx])
+    assert got.dtype == np.dtype(dtype) and np.array_equal(got, whole)
+    sel = rng.permutation(spec.nS)[:max(3, spec.nS // 3)]
+    assert np.array_equal(evaluate_ref_states(p, sel, lab[sel], lambda idx: Jn[idx]), whole[sel])
+    Jc, labc = c_oracle.backup_stage(_abi, spec, term)
+    assert np.array_equal(evaluate_ref_states(p, states, labc - spec.index_base, lambda idx: Jn[idx]), Jc)
+    if dtype == np.float32:
+        vecs = [rng.random(k).astype(np.float32) * (1.0 + a) for a, k in enumerate(n)]
+        for storage in (np.float32, np.float16):
+            sep = separable_ref(vecs, np.float32, storage).astype(np.float32)
+            want = evaluate_ref(p, sep, lab, lerp="fma").reshape(-1, order="F")
+            assert np.array_equal(evaluate_ref_states(p, states, lab, separable_jnext(vecs, np.float32, storage)), want)
+            assert not np.array_equal(want, whole)
+
+
 def test_fma32_repairs_a_double_rounding():
     """(1 + 2^-12)^2 = 1 + 2^-11 + 2^-24 is exactly a float32 midpoint; adding 2^-60 is lost in float64, and rounding that sum
     to float32 ties to even (1 + 2^-11), while the exact value lies above the midpoint."""

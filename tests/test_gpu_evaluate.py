@@ -59,6 +59,7 @@ IDX = [(np.int32, 0), (np.uint8, 1), (np.uint16, 0), (np.int32, 1), (np.uint8, 0
 
 # the kernel's index forms: 32-bit with 24-bit products (what these sizes run by default), 32-bit with 32-bit products, 64-bit
 FORMS = [(1, 1), (1, 0), (0, 1)]
+EVAL_FORM = {(1, 1): 2, (1, 0): 1, (0, 1): 0}        # get_option("eval_form"): the form the next launch runs
 
 
 def _own_labels_case(env, spec, variants=(None, 0, 5), seed=3):
@@ -81,6 +82,7 @@ def _own_labels_case(env, spec, variants=(None, 0, 5), seed=3):
                     bk.set_option("eval_i32", i32)
                     bk.set_option("eval_m24", m24)
                     assert bk.get_option("eval_i32") == i32 and bk.get_option("eval_m24") == m24
+                    assert bk.get_option("eval_form") == EVAL_FORM[(i32, m24)], (v, s, i32, m24)
                     got = bk.evaluate_stage(term, idx)
                     assert got.dtype == J.dtype
                     assert np.array_equal(got, J), (v, s, i32, m24, int(np.sum(got != J)))
@@ -150,6 +152,7 @@ def test_random_labels_equal_the_reference(env, storage, n, m, nonuniform):
                 bk.set_option("eval_i32", i32)
                 bk.set_option("eval_m24", m24)
                 assert bk.get_option("eval_grid") == grid and bk.get_option("eval_i32") == i32
+                assert bk.get_option("eval_form") == EVAL_FORM[(i32, m24)], (s, grid, i32, m24)
                 got = bk.evaluate_stage(term, labels)
                 assert np.array_equal(got, ref), (s, grid, i32, m24, int(np.sum(got != ref)))
         bk.set_option("eval_grid", 0)
