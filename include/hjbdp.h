@@ -374,6 +374,46 @@ int32_t hjb_evaluate_stage_device(hjb_handle h, const void *dJ_next, const void 
 int32_t hjb_evaluate(hjb_handle h, int32_t n_stages, const void *terminal, const void *labels, int32_t labels_per_stage,
                      void *J_final, void *J_stages, double *sweep_ms);
 
+/* ---- a disturbance in the backup: expected-value and worst-case stages (kernel variant 8) ----------------------------------------
+ *   J_k(x) = min_u  g(x, u) + E_w[ F_{k+1}(x_next(x, u) + d_w) ]          (HJB_DIST_EXPECT: sum_w p_w (.))
+ *   J_k(x) = min_u  g(x, u) + max_w F_{k+1}(x_next(x, u) + d_w)           (HJB_DIST_WORST)
+ * The stochastic and minimax backups of the textbooks (Kirk; Bertsekas) over n_nodes additive offsets of the next state, the same
+ * for every (state, control).  The setting lives on the handle: while it is set EVERY entry point that launches a stage -
+ * hjb_backup_stage(_device), hjb_solve, hjb_solve_flat, hjb_evaluate_stage(_device), hjb_evaluate - serves the disturbed problem on
+ * kernel variant 8 (hjb_info.kernel_variant reads 8) and no other variant serves the handle.  n_nodes == 0 detaches: the handle goes
+ * back to the launch it had and gives the same bits as before.  A handle on which the call was never made is not affected at all.
+ * offsets: [D, n_nodes] column-major (node w's offset of axis a at offsets[a + D * w]); weights: [n_nodes], HJB_DIST_EXPECT only,
+ * NULL = 1 / n_nodes each.  T is the arithmetic type (float for HJB_F32 / HJB_F16S, double for HJB_F64), TQ the query type (double
+ * under HJB_TAB_F64, else T).  Offsets are rounded once to TQ at the call, weights once to T; the NULL default is (T)(1.0 / n_nodes).
+ * For each (state, control), visited in the generic kernel's order (control dim 0 slowest, first minimum wins, label written
+ * column-major plus index_base):
+ *   1. q_a = the ordered term sum of axis a in TQ, as in every kernel; for node w  q_aw = (TQ)(q_a + d[a][w]).  An axis whose
+ *      offsets are all exactly zero is not offset at all: its query, cell and weight are formed once per control and shared by
+ *      the nodes.  Option "dist_axes" (read-only) is the mask of the offset axes.
+ *   2. cell and weight of q_aw as everywhere: the exact cell search, t = (q - k[c]) * (1 / dx[c]) formed in TQ and rounded to float
+ *      once under HJB_TAB_F64; linear extrapolation outside the grid.
+ *   3. v_w = the N-linear blend of J_{k+1}: the fma cascade, axis 0 first.
+ *   4. HJB_DIST_EXPECT: acc = (T)(p_0 * v_0), then acc = fma(p_w, v_w, acc) for w = 1 .. n_nodes - 1 in node order.
+ *      HJB_DIST_WORST:  acc = v_0, then acc = v_w > acc ? v_w : acc (the first maximum; a NaN never replaces).
+ *   5. candidate = (T)(g + acc), g formed as everywhere (HJB_COST_F64: state part summed once in double, each control adds its
+ *      part and rounds once).
+ * With labels given (hjb_evaluate*) the same kernel forms that one candidate and takes no min; a label out of range follows the
+ * rules above (NaN for that state, the flag hjb_check_device_status reports; the host-buffer calls look first).
+ * Consequences: with ONE node, offset 0 and weight 1, in either mode, J and labels equal the undisturbed backup's bit for bit under
+ * every typing; hjb_evaluate_stage on the disturbed backup's own labels returns its J bit for bit, and on ANY labels values >= it.
+ * Refused before any device work, the handle left as it was (text: hjb_last_error) - HJB_E_INVALID: a null handle; a mode other than
+ * the two; n_nodes < 0 or > HJB_DIST_MAX_NODES; null offsets with n_nodes > 0; an offset that is not finite; a weight that is not
+ * finite or is negative; weights given with HJB_DIST_WORST.  HJB_E_UNSUPPORTED: a slab handle (any slab field non-zero: an offset
+ * last axis changes the halo), a handle with a state model.  While a disturbance is set: hjb_solve with a probe, hjb_solve_batch
+ * with such a handle among its members and option "temporal" = 2 are HJB_E_UNSUPPORTED ("temporal" = 1 runs plain stages);
+ * option "graph" works as ever.  The multi-GPU objects take no disturbance.
+ * Options: read-only "dist_nodes", "dist_mode", "dist_axes", "dist_form" (the index form the next launch runs: 0 64-bit, 1 32-bit,
+ * where "eval_form" would be at least 1); settable "dist_i32" (0: the 64-bit form whatever the sizes; same bits - timing, tests). */
+#define HJB_DIST_EXPECT 0
+#define HJB_DIST_WORST 1
+#define HJB_DIST_MAX_NODES 128
+int32_t hjb_set_disturbance(hjb_handle h, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights);
+
 /* ---- batched closed-loop rollouts of a stored policy (test/Dynamic_Solver.m:108-181 get_optimal_path, 'Nssu' and 'ssu') ----
  * A rollout object holds a per-stage policy on one device: the grid (D <= 6 axes, knots concatenated axis 0 first), the
  * labels of n_planes stages ([nS, n_planes] column-major in HJB_IDX_I32 / _U8 / _U16: hjb_solve's idx_stages layout) and the

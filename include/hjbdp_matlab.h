@@ -47,6 +47,10 @@ int32_t hjb_evaluate_stage(void *handle, const void *J_next, const void *labels,
 int32_t hjb_evaluate_stage_device(void *handle, const void *dJ_next, const void *d_labels, void *dJ_out, void *stream);
 int32_t hjb_evaluate(void *handle, int32_t n_stages, const void *terminal, const void *labels, int32_t labels_per_stage,
                      void *J_final, void *J_stages, double *sweep_ms);
+/* a disturbance in the backup (kernel variant 8): mode 0 expected value / 1 worst case over n_nodes additive offsets of the next
+ * state (offsets [D, n_nodes] column-major; weights [n_nodes], expected value only, NULL = equal); n_nodes 0 detaches.  Every stage
+ * the handle launches afterwards carries it; usage: matlab/hjbdp_set_disturbance.m, hjbdp_solve's 'disturbance' pair */
+int32_t hjb_set_disturbance(void *handle, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights);
 int32_t hjb_get_info_flat(void *handle, int64_t *out8);
 int32_t hjb_set_option(void *handle, const char *key, int64_t value);
 int32_t hjb_get_option(void *handle, const char *key, int64_t *value);

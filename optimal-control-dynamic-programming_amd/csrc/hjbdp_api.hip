@@ -307,7 +307,7 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
             }
     }
     if (!strcmp(key, "variant")) {
-        if (value < -1 || value > 7) return fail(h, HJB_E_INVALID, "variant %lld unknown", (long long)value);
+        if (value < -1 || value > 7) return fail(h, HJB_E_INVALID, "variant %lld unknown", (long long)value);      // (8 is not forced: hjb_set_disturbance)
         const char *why = nullptr;
         const int st = value < 0 ? HJB_OK : variant_status(h, (int)value, &why);
         if (st) return fail(h, st, "variant %lld: %s", (long long)value, why);
@@ -442,6 +442,13 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
         h->eval_m24 = value != 0;
         return HJB_OK;
     }
+    if (!strcmp(key, "dist_i32")) {         // 0: variant 8 in its 64-bit form whatever the sizes (A/B timing, tests)
+        h->dist_i32 = value != 0;
+        launch_changed(h);           // (the captured launches are the other form)
+        return HJB_OK;
+    }
+    if (!strcmp(key, "dist_nodes") || !strcmp(key, "dist_mode") || !strcmp(key, "dist_axes") || !strcmp(key, "dist_form"))
+        return fail(h, HJB_E_INVALID, "%s is read-only: hjb_set_disturbance sets the disturbance, the form follows from the sizes and dist_i32", key);
     if (!strcmp(key, "eval_form")) return fail(h, HJB_E_INVALID, "eval_form is read-only: the form follows from the sizes, eval_i32, eval_m24 and eval_tables");
     if (!strcmp(key, "eval_tables")) {      // the fixed-label stage's cells and weights: -1 automatic, 0 terms summed on the fly, 1 the (cell, t) tables
         if (value < -1 || value > 1) return fail(h, HJB_E_INVALID, "eval_tables must be -1, 0 or 1");
@@ -477,6 +484,11 @@ int32_t hjb_get_option(hjb_handle hh, const char *key, int64_t *value) {
     else if (!strcmp(key, "eval_i32")) *value = eval_runs_i32(h) ? 1 : 0;     // the form that would run
     else if (!strcmp(key, "eval_form")) *value = eval_form(h);                // 0 64-bit, 1 32-bit, 2 32-bit with 24-bit products: the next launch's
     else if (!strcmp(key, "eval_tables")) *value = h->eval_tables < 0 ? (h->tabled_ok ? 1 : 0) : h->eval_tables;      // the source in effect
+    else if (!strcmp(key, "dist_nodes")) *value = h->dist_nodes;
+    else if (!strcmp(key, "dist_mode")) *value = h->dist_mode;
+    else if (!strcmp(key, "dist_axes")) *value = h->dist_axes;
+    else if (!strcmp(key, "dist_form")) *value = dist_runs_i32(h) ? 1 : 0;    // 0 64-bit, 1 32-bit: the next launch's
+    else if (!strcmp(key, "dist_i32")) *value = h->dist_i32 ? 1 : 0;
     else if (!strcmp(key, "idx_bytes")) *value = h->idx_bytes;
     else if (!strcmp(key, "temporal")) *value = h->use_temporal;
     else if (!strcmp(key, "chunk_order")) *value = h->dn ? h->hn.chunk_order : 0;
@@ -549,6 +561,8 @@ int32_t hjb_solve(hjb_handle hh, const hjb_solve_opts *o, hjb_result *res) {
     if (o->n_stages < 1) return fail(h, HJB_E_INVALID, "n_stages=%d", o->n_stages);
     if (h->j_elems != h->n_owned)
         return fail(h, HJB_E_UNSUPPORTED, "hjb_solve runs whole grids; drive slabs with hjb_backup_stage_device + a halo exchange");
+    if (o->probe && h->dist_nodes > 0)
+        return fail(h, HJB_E_UNSUPPORTED, "the probe block taps the nominal next state: not available while a disturbance is set (hjb_set_disturbance)");
     HIP_TRY(h, hipSetDevice(h->device));
     std::shared_lock<std::shared_mutex> unsafe_lk(g_capture_mu);    // allocation, synchronous copies, device sync
     int st = ensure_work(h);
@@ -628,7 +642,7 @@ int32_t hjb_solve(hjb_handle hh, const hjb_solve_opts *o, hjb_result *res) {
     const bool graph_ok = h->use_graph && !dJst && !dIst && !o->probe && !every_stage && o->n_stages >= 2 * kGraphStages;
     // K9: several stages per launch for local 2-D problems (no per-stage outputs, no monitor read-backs)
     bool tiled = false;
-    if (h->use_temporal && !h->cost64 && !dJst && !dIst && !o->probe && !every_stage && o->monitor_period <= 0 && o->n_stages >= 2 * kTileK && h->forced_variant < 0) {
+    if (h->use_temporal && !h->cost64 && !dJst && !dIst && !o->probe && !every_stage && o->monitor_period <= 0 && o->n_stages >= 2 * kTileK && h->forced_variant < 0 && h->dist_nodes == 0) {
         if (h->tile2d < 0) {
             const int tst = examine_tile2d(h);
             if (tst) { cleanup(); return tst; }
@@ -638,7 +652,7 @@ int32_t hjb_solve(hjb_handle hh, const hjb_solve_opts *o, hjb_result *res) {
     if (h->use_temporal == 2 && !tiled) {
         cleanup();
         return fail(h, HJB_E_UNSUPPORTED, "option temporal=2: several stages per launch do not apply (needs D=2, whole grid, "
-                    "every query within one cell of its state, no per-stage outputs or monitor, >= %d stages)", 2 * kTileK);
+                    "every query within one cell of its state, no per-stage outputs or monitor, no disturbance, >= %d stages)", 2 * kTileK);
     }
     if (h->gexec && h->gexec_tiled != tiled) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
     unsafe_lk.unlock();

@@ -35,6 +35,8 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
         Handle *h = H[i];
         const hjb_solve_opts &o = *opts[i];
         const Launch &L = h->L;
+        if (h->dist_nodes > 0)
+            return fail(h, HJB_E_UNSUPPORTED, "hjb_solve_batch: problem %d has a disturbance set (kernel variant 8 is not batched); sweep it with hjb_solve", i);
         if (tabled) {
             if (L.variant != 5 || !L.idx32 || h->j_elems != h->n_owned || h->hp.D > 4)
                 return fail(h, HJB_E_UNSUPPORTED, "hjb_solve_batch: problem %d does not run on the table kernel's 32-bit form (variant %d); "

@@ -11,6 +11,8 @@ namespace hjbhost {
 // graph capture); a failed build gives the build's status.
 int variant_status(Handle *h, int v, const char **why) {
     auto no = [&](const char *reason) { *why = reason; return (int)HJB_E_UNSUPPORTED; };
+    if (h->dist_nodes > 0) return v == 8 ? (int)HJB_OK : no("a handle with a disturbance runs on variant 8 only");
+    if (v == 8) return no("variant 8 serves a handle with a disturbance (hjb_set_disturbance)");
     if (h->hp.model && v != 4) return no("a problem with a state model runs on variant 4 only");
     if (h->tab64 && v < 5)
         return no("it evaluates the next-state terms in the kernel, in float32; a problem with table_dtype HJB_TAB_F64 runs on the "
@@ -69,13 +71,13 @@ static int auto_variant(Handle *h) {
     return h->row_auto ? 6 : (h->tabled_ok ? 5 : 0);
 }
 
-// Handle::L: the variant in effect (the model's 4, the forced one, or the automatic choice), its form, grid, block and LDS.  A variant
+// Handle::L: the variant in effect (8 while a disturbance is set, the model's 4, the forced one, or the automatic choice), its form, grid, block and LDS.  A variant
 // that does not serve falls to the tabled kernel (float64 cost terms in a shape or form variant 7 does not sum them in), and one whose
 // tables could not be built to the generic kernel - where that serves: a float64-typed handle keeps its variant and the build's status
 // instead, and hjb_create refuses it.
 void choose_launch(Handle *h) {
     const char *why = nullptr;
-    int v = h->hp.model ? 4 : (h->forced_variant >= 0 ? h->forced_variant : auto_variant(h));
+    int v = h->dist_nodes > 0 ? 8 : h->hp.model ? 4 : (h->forced_variant >= 0 ? h->forced_variant : auto_variant(h));
     int st = variant_status(h, v, &why);
     if (st == HJB_E_UNSUPPORTED) st = variant_status(h, v = 5, &why);
     if (st != HJB_OK && variant_status(h, 0, &why) == HJB_OK) { v = 0; st = HJB_OK; }
@@ -211,6 +213,10 @@ int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t 
         case 2: miss = stage_packed(a); break;
         case 1: miss = stage_nested(a, L.fast); break;
         case 0: miss = stage_generic(a); break;
+        case 8:
+            a.idx32 = dist_runs_i32(h);
+            miss = stage_disturb(a, h->tab64, h->tab64 ? h->dp64 : h->dp, h->d_dist, nullptr, nullptr);
+            break;
         default:    // never fall through to the generic kernel silently
             return fail(h, HJB_E_DEVICE, "internal: kernel variant %d was not dispatched", L.variant);
     }
@@ -226,6 +232,7 @@ int prepare_evaluate(Handle *h, bool *tabled) {
     if (h->hp.model)
         return fail(h, HJB_E_UNSUPPORTED, "the fixed-label stage does not evaluate a state model (HJB_MODEL_QUAT_EULER321): its next states are formed in variant 4 only");
     *tabled = h->eval_tables < 0 ? h->tabled_ok : h->eval_tables == 1;
+    if (h->dist_nodes > 0) { *tabled = false; return HJB_OK; }      // variant 8's fixed-label form: an offset query has no table entry, nothing is built
     if (!*tabled && h->tab64) return fail(h, HJB_E_UNSUPPORTED, "table_dtype HJB_TAB_F64 is evaluated from the (cell, weight) tables only");
     return *tabled ? ensure_tabled(h) : HJB_OK;
 }
@@ -238,6 +245,13 @@ int launch_evaluate(Handle *h, const void *dJn, const void *dlabels, void *dJo, 
     a.grid = (unsigned)eval_grid_of(h);
     a.block = 256;
     a.idx32 = eval_runs_i32(h);
+    if (h->dist_nodes > 0) {                               // the same kernel as the disturbed backup, one candidate per state
+        a.idx32 = dist_runs_i32(h);
+        if (stage_disturb(a, h->tab64, h->tab64 ? h->dp64 : h->dp, h->d_dist, dlabels, h->d_status + 1))
+            return fail(h, HJB_E_UNSUPPORTED, "variant 8 has no fixed-label kernel for D=%d, dtype %d", a.D, h->dtype);
+        HIP_TRY(h, hipGetLastError());
+        return HJB_OK;
+    }
     EvalDiv dv{};                                          // the divisors the kernel takes a state index and a label apart by
     for (int d = 0; d < HJB_MAX_D; ++d) dv.n[d] = hjb::magic_div(d < h->hp.D ? (uint32_t)h->hp.n[d] : 1u);
     for (int c = 0; c < 2; ++c) dv.m[c] = hjb::magic_div((uint32_t)h->hp.m[c]);

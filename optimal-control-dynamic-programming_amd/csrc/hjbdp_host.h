@@ -7,6 +7,7 @@
 //   hjbdp_choose.hip   which variant serves, in which form and geometry (Handle::L), and the stage launch
 //   hjbdp_api.hip      hjb_create .. hjb_solve, options, probe, policy lookup (the single-device C ABI)
 //   hjbdp_evaluate.hip hjb_evaluate_stage, hjb_evaluate_stage_device, hjb_evaluate (the cost of a given policy on the grid)
+//   hjbdp_disturb.hip  hjb_set_disturbance (the disturbance a handle's stages carry: kernel variant 8)
 //   hjbdp_batch.hip    hjb_solve_batch (several sweeps of one kernel shape, one launch per stage)
 //   hjbdp_builder.hip  the flat builder API (MATLAB loadlibrary / calllib)
 //   hjbdp_multi.hip    hjb_create_multi / hjb_solve_multi (one process, several GPUs)
@@ -179,6 +180,12 @@ struct Handle {
     bool eval_i32 = true;         // option "eval_i32": 0 = the 64-bit form of the evaluation kernel whatever the sizes (A/B timing, tests)
     bool eval_m24 = true;         // option "eval_m24": 0 = the 32-bit form with 32-bit index products whatever the sizes (A/B timing, tests)
     int eval_grid = 0;            // option "eval_grid": workgroups per launch of the grid-stride evaluation kernel (0 = one per 256 states)
+    // the disturbance (hjb_set_disturbance; kernels_disturb.h, variant 8): dist_nodes > 0 while one is set
+    int dist_nodes = 0;
+    int dist_mode = HJB_DIST_EXPECT;
+    uint32_t dist_axes = 0;       // bit a: some node offsets axis a (option "dist_axes")
+    bool dist_i32 = true;         // option "dist_i32": 0 = the 64-bit form of the kernel whatever the sizes (A/B timing, tests)
+    void *d_dist = nullptr;       // the DDisturb block on the device (allocated by the first call, rewritten by later ones)
     Launch L;
     int halo_need_lo = 0, halo_need_hi = 0;
     std::string err;
@@ -292,6 +299,8 @@ inline int64_t eval_grid_of(const Handle *h) {
 inline bool eval_runs_i32(const Handle *h) {
     return h->eval_i32 && h->n_owned < kTab32Lim && h->j_elems < kTab32Lim && eval_grid_of(h) * 256 <= ((int64_t)1 << 31);
 }
+// variant 8's index form follows the same predicate (its strides are smaller: at most 2^20 workgroups, or eval_grid_of for labels)
+inline bool dist_runs_i32(const Handle *h) { return h->dist_i32 && eval_runs_i32(h); }
 // the 32-bit form with 24-bit index products (hjbdp_choose.hip): eval_runs_i32 and every factor the kernel multiplies below 2^24.
 // tabled: the source of cells and weights the launch reads (prepare_evaluate) - tables and terms have strides of their own.
 // eval_form: what the next launch runs from the source in effect (option "eval_form"): 0 64-bit, 1 32-bit, 2 32-bit with 24-bit products

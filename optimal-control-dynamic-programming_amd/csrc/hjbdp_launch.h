@@ -50,6 +50,9 @@ int stage_colsweep_batch(const StageArgs &a, int n, const DCsBatch *dB, uint32_t
 int stage_tile2d(const StageArgs &a, const void *plan, int K);                   // K9 (several stages per launch)
 // the fixed-label stage (kernels_evaluate.h): labels -> a.Jo; tabled: cells and weights from a.dtb, else the terms summed on the fly
 int stage_evaluate(const StageArgs &a, bool tabled, bool mul24, const void *labels, int32_t *bad_label, const EvalDiv &dv);
+// variant 8 (K24, kernels_disturb.h): the stage of a handle with a disturbance.  q64: HJB_TAB_F64 (dpq = the float64 shadow of the axes,
+// else a.dp); dist: the handle's DDisturb block; labels: non-null runs the fixed-label form (a.idx not written, *bad_label as stage_evaluate)
+int stage_disturb(const StageArgs &a, bool q64, const DParams *dpq, const void *dist, const void *labels, int32_t *bad_label);
 int stage_tile2d_plan(int dtype, const DParams *dp, const DTabled *dtb, void *plan, int64_t n_entries);
 
 }  // namespace hjb

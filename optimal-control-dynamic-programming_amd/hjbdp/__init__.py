@@ -12,9 +12,10 @@ there is no CPU fallback.
 from . import _abi
 from .core import Backup, DeviceBuffer, HjbError, MultiBackup, RankSlab, Rollout, attitude_linear_response, device_count, device_mem_info, load_library, policy_lookup, solve_batch, solve_many, suggest_axis_order
 from .problem import ProblemSpec, Term, permute_state_axes
+from .disturbance import box_nodes, gaussian_nodes
 from .dynamic_solver import Dynamic_Solver
 from .solver_position import Solver_position
 from .solver_attitude import Solver_attitude
 from .solver_pos_att import Solver_pos_att
 
-__all__ = ["Backup", "DeviceBuffer", "device_mem_info", "MultiBackup", "RankSlab", "Rollout", "HjbError", "ProblemSpec", "Term", "permute_state_axes", "Dynamic_Solver", "Solver_position", "Solver_attitude", "Solver_pos_att", "attitude_linear_response", "device_count", "load_library", "policy_lookup", "solve_batch", "solve_many", "suggest_axis_order", "_abi"]
+__all__ = ["Backup", "DeviceBuffer", "device_mem_info", "MultiBackup", "RankSlab", "Rollout", "HjbError", "ProblemSpec", "Term", "permute_state_axes", "Dynamic_Solver", "Solver_position", "Solver_attitude", "Solver_pos_att", "attitude_linear_response", "device_count", "load_library", "policy_lookup", "solve_batch", "solve_many", "suggest_axis_order", "gaussian_nodes", "box_nodes", "_abi"]

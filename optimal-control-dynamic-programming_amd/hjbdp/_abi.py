@@ -166,6 +166,8 @@ SYMBOLS = {
     "hjb_evaluate_stage": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hjb_evaluate_stage_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hjb_evaluate": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    # a disturbance in the backup (kernel variant 8): expected-value and worst-case stages
+    "hjb_set_disturbance": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # flat builder API (primitives and plain arrays only: what MATLAB's calllib can marshal)
     "hjb_problem_new": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                     C.POINTER(C.c_void_p)]),
@@ -251,6 +253,9 @@ SYMBOLS = {
                                      + [C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int64] + [C.POINTER(C.c_double)] * 6
                                      + [C.c_int64, C.POINTER(C.c_double)]),
 }
+HJB_DIST_EXPECT = 0
+HJB_DIST_WORST = 1
+HJB_DIST_MAX_NODES = 128
 HJB_ROLLOUT_MAX_U = 4
 HJB_ATT_TAYLOR = 0
 HJB_ATT_RK4 = 1

@@ -12,7 +12,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _abi
-from .problem import ProblemSpec
+from .problem import ProblemSpec, check_disturbance
 
 _LIB = None
 LIB_PATH = Path(__file__).resolve().parent / "libhjbdp.so"
@@ -519,6 +519,12 @@ class Backup:
         self.device = int(device)
         if variant is not None:
             self.set_option("variant", variant)
+        if spec.disturbance is not None:
+            try:
+                self.set_disturbance(*spec.disturbance)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -540,9 +546,30 @@ class Backup:
 
     # -- queries ----------------------------------------------------------
     def info(self):
+        """hjb_get_info's fields, plus the disturbance in effect: dist_nodes (0: none), dist_mode ("expect" / "worst" / None), dist_axes."""
         inf = _abi.hjb_info()
         _check(self.lib, self._h, self.lib.hjb_get_info(self._h, C.byref(inf)))
-        return {k: getattr(inf, k) for k, _ in inf._fields_}
+        out = {k: getattr(inf, k) for k, _ in inf._fields_}
+        out["dist_nodes"] = self.get_option("dist_nodes")
+        out["dist_mode"] = ("expect", "worst")[self.get_option("dist_mode")] if out["dist_nodes"] else None
+        out["dist_axes"] = self.get_option("dist_axes")
+        return out
+
+    # -- the disturbance the handle's stages carry (hjb_set_disturbance: kernel variant 8) ----------------------------
+    def set_disturbance(self, offsets, weights=None, mode="expect"):
+        """Every stage this handle launches from now on - backup_stage, solve, evaluate* - takes the expected value
+        (mode "expect", weights [W] or None = equal) or the worst case ("worst") of J_next over the W next states
+        x_next + offsets[:, w].  offsets [D, W], row a for state axis a of THIS handle's spec."""
+        off, w, mode = check_disturbance(self.spec.D, offsets, weights, mode)
+        offc = np.asfortranarray(off)
+        st = self.lib.hjb_set_disturbance(self._h, _abi.HJB_DIST_WORST if mode == "worst" else _abi.HJB_DIST_EXPECT, off.shape[1],
+                                          offc.ctypes.data_as(C.POINTER(C.c_double)),
+                                          None if w is None else w.ctypes.data_as(C.POINTER(C.c_double)))
+        _check(self.lib, self._h, st)
+
+    def clear_disturbance(self):
+        """Back to the nominal backup: the launch the handle had, the same bits as before."""
+        _check(self.lib, self._h, self.lib.hjb_set_disturbance(self._h, _abi.HJB_DIST_EXPECT, 0, None, None))
 
     def set_option(self, key, value):
         _check(self.lib, self._h, self.lib.hjb_set_option(self._h, key.encode(), int(value)))

@@ -41,6 +41,7 @@ class Dynamic_Solver:
         self.H = None  # unused by the reference too (terminal cost is 0, :83-84)
         self.precision = precision
         self.device = 0
+        self.disturbance = None   # (offsets [2, W], weights or None, 'expect' / 'worst'): run() and policy_cost() under it (ProblemSpec.disturbance)
         # results
         self.s_r = None
         self.u_star = None
@@ -79,7 +80,7 @@ class Dynamic_Solver:
             raise ValueError("precision must be 'single' or 'double'")
         self.s_r = s_r
         self._U_mesh = U_mesh
-        return ProblemSpec([s_r, s_r], [self.du], nxt, cost, dtype=dt, index_base=1)
+        return ProblemSpec([s_r, s_r], [self.du], nxt, cost, dtype=dt, index_base=1, disturbance=self.disturbance)
 
     def run(self):
         spec = self.build_spec()
@@ -91,7 +92,7 @@ class Dynamic_Solver:
         # (hjb_probe).  MATLAB raises an index error when dx < 57 or du < 105; the mirror leaves the taps None instead
         # (the fixture revision test/test_coder.m has no taps and runs at dx = 35).
         probe = None
-        if self.checkstagesXJF and self.dx >= 57 and self.du >= 105:
+        if self.checkstagesXJF and self.dx >= 57 and self.du >= 105 and self.disturbance is None:    # (the taps are the nominal next state's)
             probe = {"lo": (49, 51), "hi": (55, 57), "control": (104,), "want": ("g", "x_next", "j_interp")}
         with Backup(spec, device=self.device) as bk:
             out = bk.solve(n_st, keep_J=True, keep_idx=True, probe=probe)

@@ -49,10 +49,12 @@ class ProblemSpec:
     is formed, located and weighted in double and the weight rounded to float32 once (hjbdp.h HJB_TAB_F64).
     cost_dtype: None, or np.float64 with float32 arithmetic: cost_terms are kept in float64 and the stage cost of a
     (state, control) is their ordered sum in double rounded to float32 once - `single(double expression)` of
-    Solver_pos_att.m:800-801 without the nS x nU array (hjbdp.h HJB_COST_F64)."""
+    Solver_pos_att.m:800-801 without the nS x nU array (hjbdp.h HJB_COST_F64).
+    disturbance: None, or (offsets [D, W], weights [W] or None, mode "expect" / "worst"): additive offsets of the next state
+    the backup takes the expected value or the worst case over (hjbdp.h hjb_set_disturbance; row a belongs to state axis a)."""
 
     def __init__(self, knots, m, next_terms, cost_terms, dtype=np.float64, index_base=0, j_storage=None, model=None,
-                 idx_dtype=None, table_dtype=None, cost_dtype=None):
+                 idx_dtype=None, table_dtype=None, cost_dtype=None, disturbance=None):
         self.dtype = np.dtype(dtype)
         self.cost_dtype = None if cost_dtype is None else np.dtype(cost_dtype)
         if self.cost_dtype is not None and not (self.cost_dtype == np.float64 and self.dtype == np.float32 and model is None):
@@ -105,6 +107,9 @@ class ProblemSpec:
             lo = 0 if a in model_axes else 1
             if not (lo <= len(ts) <= (0 if a in model_axes else _abi.HJB_MAX_TERMS)):
                 raise ValueError("1..%d terms per quantity (none for model axes)" % _abi.HJB_MAX_TERMS)
+        self.disturbance = None if disturbance is None else check_disturbance(self.D, *disturbance)
+        if self.disturbance is not None and self.model is not None:
+            raise ValueError("a spec with a state model takes no disturbance")
         self.index_base = int(index_base)
         self.nS = int(np.prod(self.n))
         self.nU = int(np.prod(self.m))
@@ -164,6 +169,32 @@ class ProblemSpec:
         return p, keep
 
 
+def check_disturbance(D, offsets, weights=None, mode="expect"):
+    """(offsets [D, W] float64, weights [W] float64 or None, mode) after the checks hjb_set_disturbance makes: the one
+    statement of them on the Python side (ProblemSpec, Backup.set_disturbance)."""
+    off = np.array(offsets, dtype=np.float64, ndmin=2)
+    if off.ndim != 2 or off.shape[0] != D or not (1 <= off.shape[1] <= _abi.HJB_DIST_MAX_NODES):
+        raise ValueError("disturbance offsets must be [D=%d, W] with 1 <= W <= %d, got %r" % (D, _abi.HJB_DIST_MAX_NODES, off.shape))
+    if not np.all(np.isfinite(off)):
+        raise ValueError("disturbance offsets must be finite")
+    if mode not in ("expect", "worst"):
+        raise ValueError("disturbance mode must be 'expect' or 'worst'")
+    w = None
+    if weights is not None:
+        if mode == "worst":
+            raise ValueError("the worst-case mode takes no weights")
+        w = np.array(weights, dtype=np.float64).reshape(-1)
+        if w.shape != (off.shape[1],) or not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("disturbance weights must be W finite, non-negative values")
+    return off, w, mode
+
+
+def channel_disturbance(disturbance, channel):
+    """The solver mirrors' `disturbance` attribute for one channel: None, ONE (offsets, weights, mode) tuple for every channel,
+    or a LIST with one such tuple (or None) per channel - rows in the channel's own axis order, as its build_spec lists the axes."""
+    return disturbance[channel] if isinstance(disturbance, list) else disturbance
+
+
 def permute_state_axes(spec: ProblemSpec, order):
     """Relabel the state axes: new axis i = old axis order[i].  Pure bookkeeping (which
     axis is "last" decides which stage kernel applies and the order of the 1-D lerps);
@@ -186,9 +217,12 @@ def permute_state_axes(spec: ProblemSpec, order):
     knots = [spec.knots[a] for a in order]
     nxt = [[remap(t) for t in spec.next_terms[a]] for a in order]
     cost = [remap(t) for t in spec.cost_terms]
+    dist = spec.disturbance
+    if dist is not None:             # the offset rows travel with their axes
+        dist = (dist[0][list(order), :], dist[1], dist[2])
     new = ProblemSpec(knots, spec.m, nxt, cost, dtype=spec.dtype, index_base=spec.index_base,
                       j_storage=None if spec.j_dtype == spec.dtype else spec.j_dtype,
-                      idx_dtype=spec.idx_dtype, table_dtype=spec.table_dtype, cost_dtype=spec.cost_dtype)
+                      idx_dtype=spec.idx_dtype, table_dtype=spec.table_dtype, cost_dtype=spec.cost_dtype, disturbance=dist)
     inv = [order.index(a) for a in range(D)]
 
     def to_old(flat):

@@ -21,7 +21,7 @@ import numpy as np
 
 from .core import Backup, channel_policy_cost, solve_batch, solve_many
 from .matlab_compat import deg2rad, linspace
-from .problem import ProblemSpec, Term
+from .problem import ProblemSpec, Term, channel_disturbance
 from .solver_position import NearestPolicy
 
 f32 = np.float32
@@ -53,6 +53,7 @@ class Solver_attitude:
         self.J1, self.J2, self.J3 = self.InertiaM[0, 0], self.InertiaM[1, 1], self.InertiaM[2, 2]   # InertiaM(1),(5),(9)
         self.U_vector = np.array([-0.11, 0.0, 0.11])
         self.device = 0
+        self.disturbance = None   # simplified_run / policy_cost_simplified: one (offsets [2, W] rows (w, t), weights or None, mode) for every channel, or a list of three
         self.batch_channels = True     # simplified_run: the three channels as one launch per stage (False: three chains on threads)
         self.batch_groups = None
         self.U1_Opt = self.U2_Opt = self.U3_Opt = None
@@ -84,7 +85,8 @@ class Solver_attitude:
         nxt = [[Term((0,), s_w), Term((2,), self._dw_of_u(U, Jc, self.h))],                     # w_next
                [Term((1,), s_t), Term((0,), self._dt_of_w(s_w, self.h))]]                       # t_next = T + f(W)
         cost = [Term((0,), Qw * s_w ** 2), Term((1,), Qt * s_t ** 2), Term((2,), R * U ** 2)]   # :220
-        return ProblemSpec([s_w, s_t], [len(U)], nxt, cost, dtype=np.float64, index_base=1), s_w, s_t
+        return ProblemSpec([s_w, s_t], [len(U)], nxt, cost, dtype=np.float64, index_base=1,
+                           disturbance=channel_disturbance(self.disturbance, channel)), s_w, s_t
 
     def simplified_run(self, n_stages=None, keep_policy=False):
         """keep_policy=True also leaves the policy of EVERY stage, as the reference's development script stores it
@@ -243,6 +245,9 @@ class Solver_attitude:
     def run(self, n_stages=None, relabel=True, on_the_fly=False):
         """on_the_fly=True: the next angles are computed inside the library (build_spec_model) instead of being
         tabulated over the whole 6-D grid - the form that scales to 51^6."""
+        if self.disturbance is not None:
+            raise ValueError("Solver_attitude.run solves the 6-D problem (a state model when on_the_fly): `disturbance` serves simplified_run and "
+                             "policy_cost_simplified only - set it to None for run()")
         n_st = self.N_stage - 1 if n_stages is None else int(n_stages)
         if on_the_fly:
             pspec = self.build_spec_model()

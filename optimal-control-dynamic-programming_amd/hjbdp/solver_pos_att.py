@@ -104,6 +104,7 @@ class Solver_pos_att:
         self.idx_dtype = "auto"       # U_Optimal_id storage: uint8 for the 9 (6) thruster combinations
         self.monitor_single = True    # sum(F_gI.Values(:)) as a single-precision sum (:274)
         self.device = 0
+        self.disturbance = None       # (offsets [4, W] rows (x, v, theta, w), weights or None, mode): every channel solved under it; relabelling permutes the rows
         self.batch_channels = True    # simplified_run: the four channels as one launch per stage where the library can (hjb_solve_batch)
         self.batched = False          # ... whether the last simplified_run did (batch_groups: how many channels each launch chain carried)
         self.batch_groups = None
@@ -150,7 +151,7 @@ class Solver_pos_att:
             raise ValueError("cost_mode must be 'exact', 'terms' or 'f64'")
         spec = ProblemSpec([s_x, s_v, s_t, s_w], [len(fa)], nxt, cost, dtype=np.float32, index_base=1,
                            idx_dtype=self.idx_dtype, table_dtype=self.table_dtype,
-                           cost_dtype=np.float64 if self.cost_mode == "f64" else None)
+                           cost_dtype=np.float64 if self.cost_mode == "f64" else None, disturbance=self.disturbance)
         return spec, (fa, fb, fc, fd)
 
     def calculate_one_channel_U_Opt(self, s_x, s_v, s_t, s_w, f0, f1, f6, f7, Qx, Qv, Qt, Qw, R, J, file_name,

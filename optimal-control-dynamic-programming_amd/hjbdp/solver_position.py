@@ -20,7 +20,7 @@ import numpy as np
 
 from .core import Backup, channel_policy_cost, solve_many
 from .matlab_compat import interp_nearest_point, sym_linspace_position
-from .problem import ProblemSpec, Term
+from .problem import ProblemSpec, Term, channel_disturbance
 
 
 class NearestPolicy:
@@ -61,6 +61,7 @@ class Solver_position:
         self.U_vector = np.array([-0.13, 0.0, 0.13]) * 2.0
         self.U1_Opt = self.U2_Opt = self.U3_Opt = None
         self.device = 0
+        self.disturbance = None   # one (offsets [2, W] rows (x, v), weights or None, mode) for every channel, or a list of three
         self.F_values = [None, None, None]   # F_i.Values after the sweep
         self.U_idx = [None, None, None]      # U_i_idx (1-based)
         self.sweep_ms = [None, None, None]
@@ -98,7 +99,8 @@ class Solver_position:
         nxt = [[Term((0,), s_x), Term((1,), self._dx_of_v(s_v, self.h))],     # RK4_x :157-167
                [Term((1,), s_v), Term((2,), self._dv_of_u(U, self.h))]]       # RK4_v :173-182
         cost = [Term((0,), Qx * s_x ** 2), Term((1,), Qv * s_v ** 2), Term((2,), R * U ** 2)]  # :113
-        return ProblemSpec([s_x, s_v], [len(U)], nxt, cost, dtype=np.float64, index_base=1), s_x, s_v
+        return ProblemSpec([s_x, s_v], [len(U)], nxt, cost, dtype=np.float64, index_base=1,
+                           disturbance=channel_disturbance(self.disturbance, channel)), s_x, s_v
 
     def simplified_run(self, n_stages=None, keep_policy=False):
         """n_stages overrides N_stage-1 (tests).  keep_policy=True also leaves every stage's policy - the per-stage store of

@@ -42,6 +42,11 @@ function out = hjbdp_solve(prob, n_stages, varargin)
 %   MATLAB on device-resident buffers (hjb_device_malloc / hjb_backup_stage_device: one asynchronous launch per stage, J never
 %   crosses PCIe between stages, unlike hjb_backup_stage on host arrays) and calls stop = on_stage(k_s) after stage k_s is
 %   enqueued (k_s = n_stages .. 1 as in Dynamic_Solver.m:86); a true return value ends the sweep.  No monitor, no keep_stages.
+%   'disturbance' (default []; a struct with fields offsets [D x W], weights [W] or [], mode 'expect' | 'worst'; single device):
+%   the sweep takes the expected value (weights; [] = equal) or the worst case of the cost-to-go over the W next states
+%   x_next + offsets(:, w) (hjbdp.h hjb_set_disturbance, kernel variant 8).  Row a belongs to the caller's state axis a; the
+%   rows are permuted with the axes under 'fast_axes'.  Set through hjbdp_set_disturbance.m right after the handle is created;
+%   without the pair the call sequence is unchanged.
 %   out: J (final values), idx (1-based argmin labels), and with keep_stages J_stages / idx_stages
 %        [nS x n_stages] with stage k_s in column k_s, stages_done, stopped_early, sweep_ms.
 %
@@ -58,6 +63,7 @@ function out = hjbdp_solve(prob, n_stages, varargin)
     addParameter(p, 'double_cost', false);
     addParameter(p, 'labels', 'int32');
     addParameter(p, 'on_stage', []);
+    addParameter(p, 'disturbance', []);
     parse(p, varargin{:});
     o = p.Results;
     L = 'libhjbdp';
@@ -136,6 +142,10 @@ function out = hjbdp_solve(prob, n_stages, varargin)
         hv = h.Value;
         freeh = onCleanup(@() calllib(L, 'hjb_destroy', hv));
         if o.monitor_single, check(calllib(L, 'hjb_set_option', hv, 'monitor_single', int64(1)), hv, 'handle'); end
+        if ~isempty(o.disturbance)      % rows follow the axes the library runs: row i = the caller's axis order(i)
+            dw = o.disturbance;  if ~isfield(dw, 'weights'), dw.weights = []; end
+            hjbdp_set_disturbance(hv, dw.offsets(order, :), dw.weights, dw.mode);
+        end
         Js = [];  Is = [];
         if o.keep_stages
             Js = libpointer(ptr, zeros(nS * n_stages, 1, cls));  Is = libpointer(iptr, zeros(nS * n_stages, 1, icls));
@@ -170,6 +180,7 @@ function out = hjbdp_solve(prob, n_stages, varargin)
         end
     else
         if o.keep_stages, error('hjbdp:multi', 'keep_stages needs a single device'); end
+        if ~isempty(o.disturbance), error('hjbdp:multi', 'a disturbance needs a single device (slabs take none)'); end
         check(calllib(L, 'hjb_create_multi_from', bv, int32(numel(o.devices)), int32(o.devices), h), bv, 'builder');
         hv = h.Value;
         freeh = onCleanup(@() calllib(L, 'hjb_destroy_multi', hv));
