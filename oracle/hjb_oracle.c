@@ -714,6 +714,34 @@ static float single_sum(int dtype, const void *A, int64_t n) {
     return fin[0];
 }
 
+/* The same tree carried in double: the library's default monitor sum (TA = double in csrc/kernels_reduce.h).  Over a float32 or
+ * binary16 J every partial sum is exact, so any order gives these bits; over a float64 J it is not, and the tree is the order. */
+static double double_tree_sum(const double *A, int64_t n) {
+    enum { NB = 512, NT = 256 };
+    double *acc = (double *)calloc((size_t)NB * NT, sizeof(double));
+    double part[NB], fin[NT];
+    for (int64_t a = 0; a < (int64_t)NB * NT; ++a) {
+        double s = 0.0;
+        for (int64_t i = a; i < n; i += (int64_t)NB * NT) s = s + A[i];
+        acc[a] = s;
+    }
+    for (int b = 0; b < NB; ++b) {
+        double *v = acc + (size_t)b * NT;
+        for (int s = NT / 2; s > 0; s >>= 1)
+            for (int t = 0; t < s; ++t) v[t] = v[t] + v[t + s];
+        part[b] = v[0];
+    }
+    for (int t = 0; t < NT; ++t) {
+        double s = 0.0;
+        for (int b = t; b < NB; b += NT) s = s + part[b];
+        fin[t] = s;
+    }
+    for (int s = NT / 2; s > 0; s >>= 1)
+        for (int t = 0; t < s; ++t) fin[t] = fin[t] + fin[t + s];
+    free(acc);
+    return fin[0];
+}
+
 /* The monitor's two sums (Solver_pos_att.m:274-275) of a given J / label array, exactly as orc_sweep forms them:
  * out[0] = sum(J) in float64 (single != 0 and a float32 / binary16 J: the stated float32 tree, widened), out[1] = the
  * exact label sum.  For tests that check the library's monitor on a J the GPU produced (grids too big to sweep here). */
@@ -725,6 +753,7 @@ int orc_monitor_sums(int dtype, const void *J, const int32_t *idx, int64_t n, in
         if (idx) is += (double)idx[i];
     }
     if (single && dtype != HJB_F64) fs = (double)single_sum(dtype, J, n);
+    if (dtype == HJB_F64) fs = double_tree_sum((const double *)J, n);
     out2[0] = fs; out2[1] = is;
     return 0;
 }
@@ -760,6 +789,7 @@ int orc_sweep(const hjb_problem *p, const hjb_solve_opts *o, hjb_result *res, in
             }
             const int msingle = o->monitor_single && p->dtype != HJB_F64;
             if (msingle) fs = (double)single_sum(p->dtype, A, nS);
+            if (p->dtype == HJB_F64) fs = double_tree_sum((const double *)A, nS);
             /* Solver_pos_att.m:276-282: single fsum50 => single subtraction, and abs(e) < tol compared in single */
             e = msingle ? (double)((float)fs - (float)fprev) : fs - fprev;
             e2 = is - iprev;
