@@ -10,8 +10,9 @@
 //   hjbdp_disturb.hip  hjb_set_disturbance (the disturbance a handle's stages carry: kernel variant 8)
 //   hjbdp_batch.hip    hjb_solve_batch (several sweeps of one kernel shape, one launch per stage)
 //   hjbdp_builder.hip  the flat builder API (MATLAB loadlibrary / calllib)
-//   hjbdp_multi.hip    hjb_create_multi / hjb_solve_multi (one process, several GPUs)
-//   hjbdp_rank.hip     hjb_rank_* (one process per GPU) and the RCCL transport inside the library
+//   hjbdp_slab.hip     one device's slab of a partitioned grid: its handles, strip streams, and the enqueue of one stage (hjbdp_slab.h: the arithmetic)
+//   hjbdp_multi.hip    hjb_create_multi / hjb_solve_multi (one process, several GPUs): the slabs, the halo copies, the stage loop
+//   hjbdp_rank.hip     hjb_rank_* (one process per GPU: one slab) and the RCCL transport inside the library
 //   hjbdp_devmem.hip   device-buffer helpers
 //   rollout.hip, rollout_attitude.hip   hjb_rollout_*: closed-loop rollouts of stored policies (error reporting and locks only)
 #pragma once
@@ -35,6 +36,7 @@
 #include "../../include/hjbdp.h"
 #include "hjbdp_dev.h"
 #include "hjbdp_launch.h"
+#include "hjbdp_slab.h"
 #include "kernels_generic.h"
 #include "kernels_nested.h"
 #include "kernels_packed.h"
@@ -322,6 +324,50 @@ constexpr int64_t kMaxStates = (int64_t)1 << 40;     // more grid points than an
 
 // hjbdp_api.hip: everything hjb_create checks or derives WITHOUT touching a device (the partitioners use it)
 int analyse_problem(const hjb_problem *p, int *idx_bytes_out, int64_t *n_states_out, int *halo_lo, int *halo_hi);
+
+// hjbdp_slab.hip: one device's slab of a grid partitioned along its last state axis - what hjb_solve_multi keeps per device and
+// hjb_rank_* per process.  The numbers come from hjbdp_slab.h.
+// What a partitioner learns of the whole problem WITHOUT a whole-grid handle or whole-grid tables (a problem whose slabs fit must
+// not be refused because the whole grid would not): the halo the last axis' terms imply, and the sizes of a plane.
+struct SlabGrid {
+    int need_lo = 0, need_hi = 0, nl = 0, dtype = HJB_F32;
+    int64_t inner = 0;            // states per plane of the last axis
+    size_t esz = 4, isz = 4;      // bytes per J element / per argmin label
+};
+int slab_grid(const hjb_problem *p, SlabGrid *g);      // p->D is valid (the caller's check); analyse_problem's status
+struct Slab {
+    int device = 0, begin = 0, end = 0, hlo = 0, hhi = 0;
+    SlabSplit cut{};                                   // the interior / strip arithmetic (cut.split: part[0] exists)
+    Handle *whole = nullptr;                           // sees planes [begin - hlo, end + hhi)
+    Handle *part[3] = {nullptr, nullptr, nullptr};     // interior, low strip, high strip over the same buffers (null: no such part)
+    size_t plane_b = 0, label_plane_b = 0;             // bytes of one plane of J / of the labels
+    hipStream_t ss[2] = {nullptr, nullptr};            // the two boundary strips run beside the interior
+    hipEvent_t fork = nullptr, sdone[2] = {nullptr, nullptr};
+    Handle *lead() const { return part[0] ? part[0] : whole; }      // the handle whose kernel choice stands for the slab's
+};
+// Slab k of n_slabs on `device`: the handles (slab fields set when n_slabs > 1), the strip streams and events.  split: divide it
+// where hjbdp_slab.h allows.  On failure nothing is left behind and g_last_error says why.
+int slab_create(Slab *S, const hjb_problem *p, const SlabGrid &g, int device, int k, int n_slabs, bool split);
+void slab_destroy(Slab *S);      // (the caller has made the device idle)
+// f(handle) for `whole` and every part, until one fails: -> its status, *failed = that handle
+template <typename F>
+int slab_each_handle(const Slab &S, Handle **failed, F f) {
+    Handle *hs[4] = {S.whole, S.part[0], S.part[1], S.part[2]};
+    for (Handle *h : hs)
+        if (h) {
+            const int st = f(h);
+            if (st) { *failed = h; return st; }
+        }
+    return HJB_OK;
+}
+// One stage of the slab, enqueued: J_in -> J_out (the slab's haloed buffers), idx = the owned states' labels (may be null).
+// `halo`: the event behind which J_in's halo planes are in place, recorded by the caller BEFORE this call (null: nothing to
+// wait for).  Without a split: `cs` waits for it, then one launch.  With one, the strips run on streams of their own beside the
+// interior - each launch of the column-sweep kernel lasts at least one column (~0.2 ms); in line behind the interior two strips
+// would cost more than the transfers hide.  A strip starts behind everything cs held at the call (event `fork`) and behind
+// `halo`, and records sdone[k]; when the call returns cs has waited for both.  strips_first: the strips are enqueued before the
+// interior (their halos are there already).  The current device is S.device.  On failure *err and g_last_error say why.
+int slab_enqueue_stage(Slab &S, const void *J_in, void *J_out, void *idx, hipStream_t cs, hipEvent_t halo, bool strips_first, std::string *err);
 
 }  // namespace hjbhost
 

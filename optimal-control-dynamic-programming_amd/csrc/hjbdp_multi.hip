@@ -8,26 +8,17 @@ extern "C" {
 
 // ---- single-process multi-GPU sweep ------------------------------------------------------------------------------
 // The reference's stage loop (pos-att/Solver_pos_att.m:270-286) over a grid partitioned along its LAST state axis into
-// one slab per device.  Per stage and slab: the halo planes of J_{k+1} are copied from the neighbouring slabs
-// (hipMemcpyPeerAsync on a copy stream; xGMI between GPUs), the INTERIOR planes - whose next states stay inside the
-// owned planes - are backed up while the copies are in flight, the two boundary strips afterwards.  Interior and strips
-// are slab handles over the same buffers (a slab handle sees planes [begin - halo_lo, end + halo_hi)).
+// one slab per device (hjbdp_slab.hip).  Per stage and slab: the halo planes of J_{k+1} are copied from the neighbouring
+// slabs (hipMemcpyPeerAsync on a copy stream; xGMI between GPUs) while the slab's interior is backed up; its boundary
+// strips follow the copies.  What is kept here: each slab's compute and copy streams and the events that order the
+// stages of neighbouring slabs.
 struct hjb_multi_s {
-    struct Slab {
-        int device = 0, begin = 0, end = 0, hlo = 0, hhi = 0;
-        Handle *whole = nullptr;             // owns the J buffers (dJ[0], dJ[1]) and idx
-        Handle *part[3] = {nullptr, nullptr, nullptr};     // interior, low strip, high strip (null: no split)
-        int64_t part_row0[3] = {0, 0, 0};    // first plane of the part's view inside the slab's J buffer
-        int64_t part_own0[3] = {0, 0, 0};    // first owned plane of the part, relative to `begin`
-        hipStream_t sc = nullptr, sx = nullptr;
-        hipStream_t ss[2] = {nullptr, nullptr};              // the two boundary strips run beside the interior
-        hipEvent_t done[2] = {nullptr, nullptr}, halo[2] = {nullptr, nullptr};
-        hipEvent_t fork = nullptr, sdone[2] = {nullptr, nullptr};
+    struct Dev : Slab {
+        hipStream_t sc = nullptr, sx = nullptr;              // compute, halo copies
+        hipEvent_t done[2] = {nullptr, nullptr}, halo[2] = {nullptr, nullptr};      // by stage parity: my stage enqueued / my halos copied
     };
-    std::vector<Slab> slabs;
-    int need_lo = 0, need_hi = 0, nl = 0, dtype = HJB_F32;
-    int64_t inner = 0;
-    size_t esz = 4, isz = 4;                 // bytes per J element / per argmin label
+    std::vector<Dev> slabs;
+    SlabGrid g;
     std::string err;
 };
 
@@ -52,14 +43,10 @@ int32_t hjb_destroy_multi(hjb_multi m) {
         for (int i = 0; i < 2; ++i) {
             if (S.done[i]) (void)hipEventDestroy(S.done[i]);
             if (S.halo[i]) (void)hipEventDestroy(S.halo[i]);
-            if (S.sdone[i]) (void)hipEventDestroy(S.sdone[i]);
-            if (S.ss[i]) (void)hipStreamDestroy(S.ss[i]);
         }
-        if (S.fork) (void)hipEventDestroy(S.fork);
         if (S.sc) (void)hipStreamDestroy(S.sc);
         if (S.sx) (void)hipStreamDestroy(S.sx);
-        for (int i = 0; i < 3; ++i) if (S.part[i]) (void)hjb_destroy((hjb_handle)S.part[i]);
-        if (S.whole) (void)hjb_destroy((hjb_handle)S.whole);
+        slab_destroy(&S);
     }
     delete m;
     return HJB_OK;
@@ -71,72 +58,19 @@ int32_t hjb_create_multi(const hjb_problem *p, int32_t n_dev, const int32_t *dev
     if (n_dev < 1 || n_dev > 64) return mfail(nullptr, HJB_E_INVALID, "n_dev=%d", n_dev);
     if (p->slab_begin || p->slab_end || p->halo_lo || p->halo_hi) return mfail(nullptr, HJB_E_INVALID, "hjb_create_multi partitions the grid itself: pass the whole problem");
     if (p->D < 1 || p->D > HJB_MAX_D) return mfail(nullptr, HJB_E_UNSUPPORTED, "D=%d", p->D);
-    const int nl = p->n[p->D - 1];
-    if (n_dev > nl) return mfail(nullptr, HJB_E_INVALID, "more devices (%d) than planes of the last axis (%d)", n_dev, nl);
-    // the halo the tables imply and the label width: host arithmetic on the last axis' terms - no whole-grid handle, no
-    // whole-grid tables (a problem whose slabs fit must not be refused because the whole grid would not)
-    hjb_info pin{};
-    int st;
-    {
-        int ib = 4, hl = 0, hh = 0;
-        int64_t ns = 0;
-        st = analyse_problem(p, &ib, &ns, &hl, &hh);
-        if (st) return st;
-        pin.idx_bytes = ib; pin.n_states = ns; pin.halo_needed_lo = hl; pin.halo_needed_hi = hh;
-    }
+    if (n_dev > p->n[p->D - 1]) return mfail(nullptr, HJB_E_INVALID, "more devices (%d) than planes of the last axis (%d)", n_dev, p->n[p->D - 1]);
+    SlabGrid g;
+    int st = slab_grid(p, &g);
+    if (st) return st;
+    if (slab_partition_check(g.nl, n_dev, g.need_lo, g.need_hi))
+        return mfail(nullptr, HJB_E_INVALID, "halo (%d/%d planes) wider than a neighbouring slab: use fewer devices or relabel the "
+                     "state axes so that the last axis moves less", g.need_lo, g.need_hi);
     hjb_multi m = new hjb_multi_s();
-    m->need_lo = pin.halo_needed_lo;
-    m->need_hi = pin.halo_needed_hi;
-    m->nl = nl;
-    m->dtype = p->dtype;
-    m->esz = p->dtype == HJB_F16S ? 2 : (p->dtype == HJB_F32 ? 4 : 8);
-    m->inner = pin.n_states / nl;
-    m->isz = (size_t)pin.idx_bytes;
+    m->g = g;
     m->slabs.resize((size_t)n_dev);
-    const int base = nl / n_dev, rem = nl % n_dev;
-    int b = 0;
-    for (int i = 0; i < n_dev; ++i) {
-        auto &S = m->slabs[(size_t)i];
-        S.device = devices[i];
-        S.begin = b;
-        S.end = b + base + (i < rem ? 1 : 0);
-        b = S.end;
-        S.hlo = std::min(m->need_lo, S.begin);
-        S.hhi = std::min(m->need_hi, nl - S.end);
-    }
-    for (int i = 0; i < n_dev; ++i) {       // a halo must come from the immediate neighbour only
-        const auto &S = m->slabs[(size_t)i];
-        if ((i > 0 && S.hlo > m->slabs[(size_t)i - 1].end - m->slabs[(size_t)i - 1].begin) ||
-            (i + 1 < n_dev && S.hhi > m->slabs[(size_t)i + 1].end - m->slabs[(size_t)i + 1].begin)) {
-            (void)hjb_destroy_multi(m);
-            return mfail(nullptr, HJB_E_INVALID, "halo (%d/%d planes) wider than a neighbouring slab: use fewer devices or relabel the "
-                         "state axes so that the last axis moves less", m->need_lo, m->need_hi);
-        }
-    }
-    auto make = [&](int dev, int sb, int se, int hl, int hh, Handle **hout) {
-        hjb_problem q = *p;
-        if (n_dev > 1) { q.slab_begin = sb; q.slab_end = se; q.halo_lo = hl; q.halo_hi = hh; }
-        hjb_handle h = nullptr;
-        const int s2 = hjb_create(&q, dev, &h);
-        *hout = (Handle *)h;
-        return s2;
-    };
     for (int i = 0; i < n_dev && !st; ++i) {
         auto &S = m->slabs[(size_t)i];
-        st = make(S.device, S.begin, S.end, S.hlo, S.hhi, &S.whole);
-        if (st) break;
-        const int lo_w = S.hlo ? m->need_lo : 0, hi_w = S.hhi ? m->need_hi : 0, owned = S.end - S.begin;
-        if (n_dev > 1 && owned - lo_w - hi_w >= 1 && (lo_w || hi_w)) {
-            const int view0 = S.begin - S.hlo;
-            auto sub = [&](int k, int sb, int se, int hl, int hh) {
-                S.part_row0[k] = (sb - hl) - view0;
-                S.part_own0[k] = sb - S.begin;
-                return make(S.device, sb, se, hl, hh, &S.part[k]);
-            };
-            st = sub(0, S.begin + lo_w, S.end - hi_w, std::min(m->need_lo, lo_w), std::min(m->need_hi, hi_w));
-            if (!st && lo_w) st = sub(1, S.begin, S.begin + lo_w, S.hlo, std::min(m->need_hi, S.end - (S.begin + lo_w)));
-            if (!st && hi_w) st = sub(2, S.end - hi_w, S.end, std::min(m->need_lo, (S.end - hi_w) - S.begin), S.hhi);
-        }
+        st = slab_create(&S, p, g, devices[i], i, n_dev, true);
         if (st) break;
         if (hipSetDevice(S.device) != hipSuccess) { st = mfail(nullptr, HJB_E_DEVICE, "hipSetDevice(%d)", S.device); break; }
         {
@@ -146,9 +80,7 @@ int32_t hjb_create_multi(const hjb_problem *p, int32_t n_dev, const int32_t *dev
         if (st) break;
         bool ok = hipStreamCreateWithFlags(&S.sc, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&S.sx, hipStreamNonBlocking) == hipSuccess;
         for (int k = 0; k < 2 && ok; ++k)
-            ok = hipEventCreateWithFlags(&S.done[k], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&S.halo[k], hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&S.sdone[k], hipEventDisableTiming) == hipSuccess && hipStreamCreateWithFlags(&S.ss[k], hipStreamNonBlocking) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&S.fork, hipEventDisableTiming) == hipSuccess;
+            ok = hipEventCreateWithFlags(&S.done[k], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&S.halo[k], hipEventDisableTiming) == hipSuccess;
         if (!ok) { st = mfail(nullptr, HJB_E_DEVICE, "stream / event creation failed on device %d", S.device); break; }
         for (int j = 0; j < n_dev; ++j)          // direct peer copies where the platform allows them (errors: staged copies still work)
             if (devices[j] != S.device) { int can = 0; if (hipDeviceCanAccessPeer(&can, S.device, devices[j]) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(devices[j], 0); }
@@ -173,19 +105,16 @@ int32_t hjb_multi_slab_info(hjb_multi m, int32_t slab, int32_t *begin, int32_t *
     if (halo_lo) *halo_lo = S.hlo;
     if (halo_hi) *halo_hi = S.hhi;
     if (split) *split = S.part[0] ? 1 : 0;
-    if (kernel_variant) *kernel_variant = (S.part[0] ? S.part[0] : S.whole)->L.variant;
+    if (kernel_variant) *kernel_variant = S.lead()->L.variant;
     return HJB_OK;
 }
 
 int32_t hjb_multi_set_option(hjb_multi m, const char *key, int64_t value) {
     if (!m || !key) return mfail(m, HJB_E_INVALID, "null argument");
     for (auto &S : m->slabs) {
-        Handle *hs[4] = {S.whole, S.part[0], S.part[1], S.part[2]};
-        for (Handle *h : hs)
-            if (h) {
-                const int st = hjb_set_option((hjb_handle)h, key, value);
-                if (st) return mfail(m, st, "%s", hjb_last_error((hjb_handle)h));
-            }
+        Handle *h = nullptr;
+        const int st = slab_each_handle(S, &h, [&](Handle *x) { return hjb_set_option((hjb_handle)x, key, value); });
+        if (st) return mfail(m, st, "%s", hjb_last_error((hjb_handle)h));
     }
     return HJB_OK;
 }
@@ -200,8 +129,8 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
                      "hjb_solve_multi adds exact float64 sums over the slabs");
     const bool every_stage = o->progress && o->progress_every_stage;
     const int n = (int)m->slabs.size();
-    const int64_t inner = m->inner;
-    const size_t esz = m->esz, plane_b = (size_t)inner * esz;
+    const int64_t inner = m->g.inner;
+    const size_t esz = m->g.esz, isz = m->g.isz, plane_b = (size_t)inner * esz;
 #define MULTI_TRY(expr)                                                                         \
     do {                                                                                       \
         hipError_t e_ = (expr);                                                                \
@@ -217,15 +146,6 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
         else MULTI_TRY(hipMemset(J0, 0, plane_b * (size_t)(S.end - S.begin + S.hlo + S.hhi)));
         MULTI_TRY(hipDeviceSynchronize());
     }
-    auto stage_part = [&](hjb_multi_s::Slab &S, int k, int cur, hipStream_t stream) -> int {
-        Handle *h = k < 0 ? S.whole : S.part[k];
-        const int64_t row0 = k < 0 ? 0 : S.part_row0[k], own0 = k < 0 ? 0 : S.part_own0[k];
-        const char *in = (const char *)S.whole->dJ[cur] + plane_b * row0;
-        char *outp = (char *)S.whole->dJ[cur ^ 1] + plane_b * row0;
-        const int st = launch_stage(h, in, outp, S.whole->d_idx + (size_t)(inner * own0) * m->isz, stream);
-        if (st) m->err = h->err;
-        return st;
-    };
     const auto t0 = std::chrono::steady_clock::now();
     int cur = 0, done = 0, early = 0;
     double fprev = 0, iprev = 0, e = 0, e2 = 0;
@@ -254,7 +174,7 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
             }
             MULTI_TRY(hipEventRecord(S.halo[par], S.sx));
         }
-        // ---- phase B: interior, then (halos landed) the strips, on the compute streams --------------------------------
+        // ---- phase B: the stage of every slab, on the compute streams ------------------------------------------------------
         for (int i = 0; i < n; ++i) {
             auto &S = m->slabs[(size_t)i];
             MULTI_TRY(hipSetDevice(S.device));
@@ -262,28 +182,10 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
                 if (i > 0 && m->slabs[(size_t)i - 1].hhi) MULTI_TRY(hipStreamWaitEvent(S.sc, m->slabs[(size_t)i - 1].halo[ppar], 0));
                 if (i + 1 < n && m->slabs[(size_t)i + 1].hlo) MULTI_TRY(hipStreamWaitEvent(S.sc, m->slabs[(size_t)i + 1].halo[ppar], 0));
             }
-            int st = HJB_OK;
-            if (S.part[0]) {
-                // the strips on streams of their own, beside the interior: each launch of the column-sweep kernel lasts at
-                // least one column (~0.2 ms), in line behind the interior two strips would cost more than the copies hide.
-                // A strip stream waits for what the compute stream has waited for so far (event `fork`), and for the halos.
-                MULTI_TRY(hipEventRecord(S.fork, S.sc));          // fork point: everything this stage depends on, before the interior
-                for (int k = 1; k <= 2 && !st; ++k)
-                    if (S.part[k]) MULTI_TRY(hipStreamWaitEvent(S.ss[k - 1], S.fork, 0));
-                st = stage_part(S, 0, cur, S.sc);
-                for (int k = 1; k <= 2 && !st; ++k)
-                    if (S.part[k]) {
-                        if (S.hlo || S.hhi) MULTI_TRY(hipStreamWaitEvent(S.ss[k - 1], S.halo[par], 0));
-                        st = stage_part(S, k, cur, S.ss[k - 1]);
-                        if (!st) {
-                            MULTI_TRY(hipEventRecord(S.sdone[k - 1], S.ss[k - 1]));
-                            MULTI_TRY(hipStreamWaitEvent(S.sc, S.sdone[k - 1], 0));
-                        }
-                    }
-            } else {
-                if (S.hlo || S.hhi) MULTI_TRY(hipStreamWaitEvent(S.sc, S.halo[par], 0));
-                st = stage_part(S, -1, cur, S.sc);
-            }
+            // interior, strips behind this stage's halo copies (a slab without the split: the copies, then one kernel); the
+            // compute stream has joined the strips when done[par] is recorded
+            const int st = slab_enqueue_stage(S, S.whole->dJ[cur], S.whole->dJ[cur ^ 1], S.whole->d_idx, S.sc,
+                                              (S.hlo || S.hhi) ? S.halo[par] : nullptr, false, &m->err);
             if (st) return mfail(m, st, "stage launch on slab %d: %s", i, m->err.c_str());
             MULTI_TRY(hipEventRecord(S.done[par], S.sc));
         }
@@ -295,12 +197,12 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
                 auto &S = m->slabs[(size_t)i];
                 MULTI_TRY(hipSetDevice(S.device));
                 const size_t own = (size_t)(S.end - S.begin);
-                const size_t at = (size_t)(k_s - 1) * (size_t)inner * (size_t)m->nl + (size_t)inner * (size_t)S.begin;
+                const size_t at = (size_t)(k_s - 1) * (size_t)inner * (size_t)m->g.nl + (size_t)inner * (size_t)S.begin;
                 if (o->J_stages)
                     MULTI_TRY(hipMemcpyAsync((char *)o->J_stages + at * esz, (const char *)S.whole->dJ[cur ^ 1] + plane_b * S.hlo, plane_b * own,
                                              hipMemcpyDeviceToHost, S.sc));
                 if (o->idx_stages)
-                    MULTI_TRY(hipMemcpyAsync((char *)o->idx_stages + at * m->isz, S.whole->d_idx, (size_t)inner * own * m->isz, hipMemcpyDeviceToHost, S.sc));
+                    MULTI_TRY(hipMemcpyAsync((char *)o->idx_stages + at * isz, S.whole->d_idx, (size_t)inner * own * isz, hipMemcpyDeviceToHost, S.sc));
             }
         if (every_stage && !(o->monitor_period > 0 && (k_s % o->monitor_period) == 0)) {    // Dynamic_Solver.m:101: one line per stage
             for (auto &S : m->slabs) {
@@ -316,7 +218,7 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
             for (auto &S : m->slabs) {
                 MULTI_TRY(hipSetDevice(S.device));
                 const char *Jown = (const char *)S.whole->dJ[cur] + plane_b * S.hlo;
-                if (launch_monitor_sums(m->dtype, false, Jown, S.whole->d_idx, (int32_t)m->isz, inner * (S.end - S.begin), S.whole->d_partials, S.whole->d_sums, S.sc) != HJB_OK)
+                if (launch_monitor_sums(m->g.dtype, false, Jown, S.whole->d_idx, (int32_t)isz, inner * (S.end - S.begin), S.whole->d_partials, S.whole->d_sums, S.sc) != HJB_OK)
                     return mfail(m, HJB_E_DEVICE, "monitor reduction launch failed");
             }
             for (auto &S : m->slabs) {
@@ -341,16 +243,13 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
     }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     for (auto &S : m->slabs) {
-        Handle *hs[4] = {S.whole, S.part[0], S.part[1], S.part[2]};
         MULTI_TRY(hipSetDevice(S.device));
-        for (Handle *h : hs)
-            if (h) {
-                const int st = check_status(h, S.sc);
-                if (st) return mfail(m, st, "%s", h->err.c_str());
-            }
+        Handle *h = nullptr;
+        const int st = slab_each_handle(S, &h, [&](Handle *x) { return check_status(x, S.sc); });
+        if (st) return mfail(m, st, "%s", h->err.c_str());
         const size_t own = (size_t)(S.end - S.begin);
         if (o->J_final) MULTI_TRY(hipMemcpy((char *)o->J_final + plane_b * S.begin, (const char *)S.whole->dJ[cur] + plane_b * S.hlo, plane_b * own, hipMemcpyDeviceToHost));
-        if (o->idx_final) MULTI_TRY(hipMemcpy((char *)o->idx_final + (size_t)(inner * S.begin) * m->isz, S.whole->d_idx, (size_t)inner * own * m->isz, hipMemcpyDeviceToHost));
+        if (o->idx_final) MULTI_TRY(hipMemcpy((char *)o->idx_final + (size_t)(inner * S.begin) * isz, S.whole->d_idx, (size_t)inner * own * isz, hipMemcpyDeviceToHost));
     }
     if (res) {
         res->stages_done = done;

@@ -15,21 +15,16 @@ static_assert(NCCL_UNIQUE_ID_BYTES == 128 && sizeof(ncclUniqueId) == 128,
 
 extern "C" {
 
-// ---- one process per GPU: a rank's slab as interior + boundary strips ------------------------------------------------
-// What hjb_solve_multi does per slab and stage, for a host that runs ONE PROCESS PER GPU and moves the halo planes itself
-// (MPI, RCCL through torch.distributed: hjbdp/sharded.py, bench.py --gpus N).  The library partitions the last state axis
-// exactly as hjb_create_multi does, creates this rank's slab handle and - when the slab has an interior - the interior
-// and strip handles over the same buffers, and enqueues a whole stage (fork, interior, strips behind the halos, join) in
-// ONE call: the per-stage host work of a rank is the exchange plus this call.
+// ---- one process per GPU ---------------------------------------------------------------------------------------------------
+// hjb_solve_multi's slab (hjbdp_slab.hip) for a host that runs ONE PROCESS PER GPU and moves the halo planes itself (MPI, RCCL
+// through torch.distributed: hjbdp/sharded.py, bench.py --gpus N) or lets the library move them (the RCCL transport below).
+// The library partitions the last state axis exactly as hjb_create_multi does and enqueues a whole stage in ONE call: the
+// per-stage host work of a rank is the exchange plus this call.
 struct hjb_rank_s {
-    int device = 0, rank = 0, world = 1, begin = 0, end = 0, hlo = 0, hhi = 0, need_lo = 0, need_hi = 0, nl = 0;
-    Handle *whole = nullptr;
-    Handle *part[3] = {nullptr, nullptr, nullptr};     // interior, low strip, high strip (null: no split)
-    int64_t part_row0[3] = {0, 0, 0}, part_own0[3] = {0, 0, 0};
-    hipStream_t ss[2] = {nullptr, nullptr};
-    hipEvent_t fork = nullptr, halo = nullptr, sdone[2] = {nullptr, nullptr};
-    int64_t inner = 0;
-    size_t esz = 4, isz = 4;
+    Slab S;
+    SlabGrid g;
+    int rank = 0, world = 1;
+    hipEvent_t halo = nullptr;        // recorded on the caller's halo stream: the strips wait for it
     std::string err;
     // RCCL transport (hjb_rank_comm_init): the communicator, the transfer stream, an event that orders it behind the
     // compute stream, the monitor's reduction scratch, and the loopback switch of the one-GPU transport test
@@ -38,7 +33,7 @@ struct hjb_rank_s {
     hipEvent_t xready = nullptr;
     double *d_partials = nullptr, *d_sums = nullptr;
     bool loopback = false;
-    int dtype = HJB_F32, up_needs = 0, dn_needs = 0;
+    int up_needs = 0, dn_needs = 0;   // planes rank + 1 / rank - 1 need of this rank's output (hjbdp_slab.h)
     int64_t xfer_delay_ticks = 0;     // option "xfer_delay_us": a spin of that length behind every exchange (link-latency emulation)
     bool monitor_single = false;      // option "monitor_single": hjb_rank_sweep's monitor in single precision (see there)
     hipEvent_t xdone = nullptr;       // recorded on the transfer stream behind every exchange (hjb_rank_step_post's strips wait for it)
@@ -55,23 +50,22 @@ static int rfail(hjb_rank r, int code, const char *fmt, ...) {
     g_last_error = buf;
     return code;
 }
+#define RANK_TRY(r, expr)                                                                                     \
+    do {                                                                                                      \
+        const hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess) return rfail(r, HJB_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
+    } while (0)
 
 const char *hjb_rank_last_error(hjb_rank r) { return r ? r->err.c_str() : g_last_error.c_str(); }
 static void rank_comm_release(hjb_rank r);
 
 int32_t hjb_rank_destroy(hjb_rank r) {
     if (!r) return HJB_OK;
-    (void)hipSetDevice(r->device);
+    (void)hipSetDevice(r->S.device);
     (void)hipDeviceSynchronize();
-    for (int i = 0; i < 2; ++i) {
-        if (r->sdone[i]) (void)hipEventDestroy(r->sdone[i]);
-        if (r->ss[i]) (void)hipStreamDestroy(r->ss[i]);
-    }
-    if (r->fork) (void)hipEventDestroy(r->fork);
     if (r->halo) (void)hipEventDestroy(r->halo);
     rank_comm_release(r);
-    for (int i = 0; i < 3; ++i) if (r->part[i]) (void)hjb_destroy((hjb_handle)r->part[i]);
-    if (r->whole) (void)hjb_destroy((hjb_handle)r->whole);
+    slab_destroy(&r->S);
     delete r;
     return HJB_OK;
 }
@@ -82,78 +76,26 @@ int32_t hjb_rank_create(const hjb_problem *p, int32_t device, int32_t rank, int3
     if (world < 1 || rank < 0 || rank >= world) return rfail(nullptr, HJB_E_INVALID, "rank %d of %d", rank, world);
     if (p->slab_begin || p->slab_end || p->halo_lo || p->halo_hi) return rfail(nullptr, HJB_E_INVALID, "hjb_rank_create partitions the grid itself: pass the whole problem");
     if (p->D < 1 || p->D > HJB_MAX_D) return rfail(nullptr, HJB_E_UNSUPPORTED, "D=%d", p->D);
-    const int nl = p->n[p->D - 1];
-    if (world > nl) return rfail(nullptr, HJB_E_INVALID, "more ranks (%d) than planes of the last axis (%d)", world, nl);
-    hjb_info pin{};                              // the halo the tables imply + the label width: host arithmetic only
-    int st;
-    {
-        int ib = 4, hl = 0, hh = 0;
-        int64_t ns = 0;
-        st = analyse_problem(p, &ib, &ns, &hl, &hh);
-        if (st) return st;
-        pin.idx_bytes = ib; pin.n_states = ns; pin.halo_needed_lo = hl; pin.halo_needed_hi = hh;
-    }
+    if (world > p->n[p->D - 1]) return rfail(nullptr, HJB_E_INVALID, "more ranks (%d) than planes of the last axis (%d)", world, p->n[p->D - 1]);
+    SlabGrid g;
+    int st = slab_grid(p, &g);
+    if (st) return st;
+    if (slab_partition_check(g.nl, world, g.need_lo, g.need_hi))
+        return rfail(nullptr, HJB_E_INVALID, "halo (%d/%d planes) wider than a neighbouring slab: use fewer ranks or relabel the "
+                     "state axes so that the last axis moves less", g.need_lo, g.need_hi);
     hjb_rank r = new hjb_rank_s();
-    r->device = device; r->rank = rank; r->world = world; r->nl = nl;
-    r->need_lo = pin.halo_needed_lo; r->need_hi = pin.halo_needed_hi;
-    r->esz = p->dtype == HJB_F16S ? 2 : (p->dtype == HJB_F32 ? 4 : 8);
-    r->isz = (size_t)pin.idx_bytes;
-    r->inner = pin.n_states / nl;
-    const int base = nl / world, rem = nl % world;
-    auto range = [&](int k, int *b, int *e) { *b = k * base + std::min(k, rem); *e = *b + base + (k < rem ? 1 : 0); };
-    range(rank, &r->begin, &r->end);
-    r->hlo = std::min(r->need_lo, r->begin);
-    r->hhi = std::min(r->need_hi, nl - r->end);
-    r->dtype = p->dtype;
-    r->up_needs = rank + 1 < world ? std::min(r->need_lo, r->end) : 0;        // my top planes -> rank + 1's lower halo
-    r->dn_needs = rank > 0 ? std::min(r->need_hi, nl - r->begin) : 0;         // my bottom planes -> rank - 1's upper halo
-    for (int k = 0; k < world; ++k) {            // a halo must come from the immediate neighbour only
-        int b, e;
-        range(k, &b, &e);
-        int pb = 0, pe = 0, nb = 0, ne = 0;
-        if (k > 0) range(k - 1, &pb, &pe);
-        if (k + 1 < world) range(k + 1, &nb, &ne);
-        if ((k > 0 && std::min(r->need_lo, b) > pe - pb) || (k + 1 < world && std::min(r->need_hi, nl - e) > ne - nb)) {
-            (void)hjb_rank_destroy(r);
-            return rfail(nullptr, HJB_E_INVALID, "halo (%d/%d planes) wider than a neighbouring slab: use fewer ranks or relabel the "
-                         "state axes so that the last axis moves less", pin.halo_needed_lo, pin.halo_needed_hi);
-        }
-    }
-    auto make = [&](int sb, int se, int hl, int hh, Handle **hout) {
-        hjb_problem q = *p;
-        if (world > 1) { q.slab_begin = sb; q.slab_end = se; q.halo_lo = hl; q.halo_hi = hh; }
-        hjb_handle h = nullptr;
-        const int s2 = hjb_create(&q, device, &h);
-        *hout = (Handle *)h;
-        return s2;
-    };
-    st = make(r->begin, r->end, r->hlo, r->hhi, &r->whole);
-    const int lo_w = r->hlo ? r->need_lo : 0, hi_w = r->hhi ? r->need_hi : 0, owned = r->end - r->begin;
-    if (!st && overlap && world > 1 && owned - lo_w - hi_w >= 1 && (lo_w || hi_w)) {
-        const int view0 = r->begin - r->hlo;
-        auto sub = [&](int k, int sb, int se, int hl, int hh) {
-            r->part_row0[k] = (sb - hl) - view0;
-            r->part_own0[k] = sb - r->begin;
-            return make(sb, se, hl, hh, &r->part[k]);
-        };
-        st = sub(0, r->begin + lo_w, r->end - hi_w, std::min(r->need_lo, lo_w), std::min(r->need_hi, hi_w));
-        if (!st && lo_w) st = sub(1, r->begin, r->begin + lo_w, r->hlo, std::min(r->need_hi, r->end - (r->begin + lo_w)));
-        if (!st && hi_w) st = sub(2, r->end - hi_w, r->end, std::min(r->need_lo, (r->end - hi_w) - r->begin), r->hhi);
-    }
-    if (!st) {
-        bool ok = hipSetDevice(device) == hipSuccess && hipEventCreateWithFlags(&r->fork, hipEventDisableTiming) == hipSuccess &&
-                  hipEventCreateWithFlags(&r->halo, hipEventDisableTiming) == hipSuccess;
-        for (int k = 0; k < 2 && ok; ++k)
-            ok = hipEventCreateWithFlags(&r->sdone[k], hipEventDisableTiming) == hipSuccess &&
-                 hipStreamCreateWithFlags(&r->ss[k], hipStreamNonBlocking) == hipSuccess;
-        if (!ok) st = rfail(nullptr, HJB_E_DEVICE, "stream / event creation failed on device %d", device);
-    }
+    r->g = g; r->rank = rank; r->world = world;
+    st = slab_create(&r->S, p, g, device, rank, world, overlap != 0);
+    if (!st && hipEventCreateWithFlags(&r->halo, hipEventDisableTiming) != hipSuccess)
+        st = rfail(nullptr, HJB_E_DEVICE, "stream / event creation failed on device %d", device);
     if (st) {
         const std::string keep = g_last_error;
         (void)hjb_rank_destroy(r);
         g_last_error = keep;
         return st;
     }
+    r->up_needs = slab_up_needs(g.need_lo, r->S.end, rank, world);
+    r->dn_needs = slab_dn_needs(g.need_hi, r->S.begin, g.nl, rank);
     *out = r;
     return HJB_OK;
 }
@@ -171,11 +113,12 @@ int32_t hjb_rank_create_from(hjb_builder b, int32_t device, int32_t rank, int32_
 
 int32_t hjb_rank_info(hjb_rank r, int32_t *out10) {
     if (!r || !out10) return rfail(r, HJB_E_INVALID, "null argument");
-    out10[0] = r->begin; out10[1] = r->end; out10[2] = r->hlo; out10[3] = r->hhi;
-    out10[4] = r->part[0] ? 1 : 0;
-    out10[5] = (r->part[0] ? r->part[0] : r->whole)->L.variant;
-    out10[6] = r->need_lo; out10[7] = r->need_hi;
-    out10[8] = (int32_t)r->isz; out10[9] = r->nl;
+    const Slab &S = r->S;
+    out10[0] = S.begin; out10[1] = S.end; out10[2] = S.hlo; out10[3] = S.hhi;
+    out10[4] = S.part[0] ? 1 : 0;
+    out10[5] = S.lead()->L.variant;
+    out10[6] = r->g.need_lo; out10[7] = r->g.need_hi;
+    out10[8] = (int32_t)r->g.isz; out10[9] = r->g.nl;
     return HJB_OK;
 }
 
@@ -183,7 +126,7 @@ int32_t hjb_rank_set_option(hjb_rank r, const char *key, int64_t value) {
     if (!r || !key) return rfail(r, HJB_E_INVALID, "null argument");
     if (!strcmp(key, "xfer_delay_us")) {      // emulation only: every halo exchange takes this much longer (tools/emulate_ranks.py)
         int khz = 0;
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, r->device) != hipSuccess || khz <= 0) khz = 100000;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, r->S.device) != hipSuccess || khz <= 0) khz = 100000;
         r->xfer_delay_ticks = value > 0 ? value * (int64_t)khz / 1000 : 0;
         return HJB_OK;
     }
@@ -191,102 +134,50 @@ int32_t hjb_rank_set_option(hjb_rank r, const char *key, int64_t value) {
         if (r->comm) return rfail(r, HJB_E_INVALID, "comm_loopback must be set before hjb_rank_comm_init");
         r->loopback = value != 0;
         if (r->loopback) {                    // this rank plays both neighbours: it needs what it would have received
-            r->up_needs = r->hlo;
-            r->dn_needs = r->hhi;
+            r->up_needs = r->S.hlo;
+            r->dn_needs = r->S.hhi;
         }
         return HJB_OK;
     }
     if (!strcmp(key, "post_exchange")) { r->post_exchange = value != 0; return HJB_OK; }      // hjb_rank_sweep: hjb_rank_step_post (1) / hjb_rank_step (0)
     if (!strcmp(key, "monitor_single")) r->monitor_single = value != 0;      // ... and on to the handles (hjb_rank_get_option reads it there)
-    Handle *hs[4] = {r->whole, r->part[0], r->part[1], r->part[2]};
-    for (Handle *h : hs)
-        if (h) {
-            const int st = hjb_set_option((hjb_handle)h, key, value);
-            if (st) return rfail(r, st, "%s", hjb_last_error((hjb_handle)h));
-        }
+    Handle *h = nullptr;
+    const int st = slab_each_handle(r->S, &h, [&](Handle *x) { return hjb_set_option((hjb_handle)x, key, value); });
+    if (st) return rfail(r, st, "%s", hjb_last_error((hjb_handle)h));
     return HJB_OK;
 }
 
 int32_t hjb_rank_get_option(hjb_rank r, const char *key, int64_t *value) {
     if (!r) return rfail(r, HJB_E_INVALID, "null argument");
-    return hjb_get_option((hjb_handle)(r->part[0] ? r->part[0] : r->whole), key, value);
+    return hjb_get_option((hjb_handle)r->S.lead(), key, value);
 }
 
 // a separable terminal cost built on the device in this rank's haloed buffer (owned planes AND halo planes: a grid like C3's
 // never exists in host memory) - hjb_device_fill_separable on the rank's slab handle
 int32_t hjb_rank_fill_separable(hjb_rank r, const void *const *vecs, void *dJ, void *stream) {
-    if (!r || !r->whole) return rfail(r, HJB_E_INVALID, "null argument");
-    const int st = hjb_device_fill_separable((hjb_handle)r->whole, vecs, dJ, stream);
-    if (st) return rfail(r, st, "%s", r->whole->err.c_str());
+    if (!r || !r->S.whole) return rfail(r, HJB_E_INVALID, "null argument");
+    const int st = hjb_device_fill_separable((hjb_handle)r->S.whole, vecs, dJ, stream);
+    if (st) return rfail(r, st, "%s", r->S.whole->err.c_str());
     return HJB_OK;
 }
 
 int32_t hjb_rank_check_status(hjb_rank r, void *stream) {
     if (!r) return rfail(r, HJB_E_INVALID, "null argument");
-    if (hipSetDevice(r->device) != hipSuccess) return rfail(r, HJB_E_DEVICE, "hipSetDevice failed");
-    Handle *hs[4] = {r->whole, r->part[0], r->part[1], r->part[2]};
-    for (Handle *h : hs)
-        if (h) {
-            const int st = check_status(h, (hipStream_t)stream);
-            if (st) return rfail(r, st, "%s", h->err.c_str());
-        }
+    if (hipSetDevice(r->S.device) != hipSuccess) return rfail(r, HJB_E_DEVICE, "hipSetDevice failed");
+    Handle *h = nullptr;
+    const int st = slab_each_handle(r->S, &h, [&](Handle *x) { return check_status(x, (hipStream_t)stream); });
+    if (st) return rfail(r, st, "%s", h->err.c_str());
     return HJB_OK;
 }
 
 }  // extern "C"
-// strips_first: the boundary strips are enqueued before the interior (their halos are there already: hjb_rank_step_post)
+// one stage of the rank's slab behind what halo_stream holds (null: nothing to wait for); strips_first: hjb_rank_step_post's order
 static int rank_stage(hjb_rank r, const void *dJ_in, void *dJ_out, void *d_idx, void *compute_stream, void *halo_stream, bool strips_first) {
     if (!r || !dJ_in || !dJ_out) return rfail(r, HJB_E_INVALID, "null argument");
-    hipStream_t cs = (hipStream_t)compute_stream, hs = (hipStream_t)halo_stream;
-    const size_t plane_b = (size_t)r->inner * r->esz;
-#define RANK_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return rfail(r, HJB_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-    RANK_TRY(hipSetDevice(r->device));
-    auto stage_part = [&](int k, hipStream_t stream) -> int {
-        Handle *h = k < 0 ? r->whole : r->part[k];
-        const int64_t row0 = k < 0 ? 0 : r->part_row0[k], own0 = k < 0 ? 0 : r->part_own0[k];
-        const int st = launch_stage(h, (const char *)dJ_in + plane_b * row0, (char *)dJ_out + plane_b * row0,
-                                    d_idx ? (char *)d_idx + (size_t)(r->inner * own0) * r->isz : nullptr, stream);
-        if (st) r->err = h->err;
-        return st;
-    };
-    const bool halos = hs != nullptr && (r->hlo || r->hhi);
-    if (!r->part[0]) {                       // no interior to overlap with: the halos first, then one kernel
-        if (halos) {
-            RANK_TRY(hipEventRecord(r->halo, hs));
-            RANK_TRY(hipStreamWaitEvent(cs, r->halo, 0));
-        }
-        return stage_part(-1, cs);
-    }
-    // the strips run on streams of their own, beside the interior (see hjb_solve_multi): a strip stream waits for what the
-    // compute stream holds so far (J_in complete) and for the halos; the compute stream joins them at the end
-    RANK_TRY(hipEventRecord(r->fork, cs));
-    for (int k = 1; k <= 2; ++k)
-        if (r->part[k]) RANK_TRY(hipStreamWaitEvent(r->ss[k - 1], r->fork, 0));
-    int st = HJB_OK;
-    if (!strips_first) {
-        st = stage_part(0, cs);
-        if (st) return st;
-    }
-    if (halos) RANK_TRY(hipEventRecord(r->halo, hs));
-    for (int k = 1; k <= 2; ++k)
-        if (r->part[k]) {
-            if (halos) RANK_TRY(hipStreamWaitEvent(r->ss[k - 1], r->halo, 0));
-            st = stage_part(k, r->ss[k - 1]);
-            if (st) return st;
-            RANK_TRY(hipEventRecord(r->sdone[k - 1], r->ss[k - 1]));
-        }
-    if (strips_first) {
-        st = stage_part(0, cs);
-        if (st) return st;
-    }
-    for (int k = 1; k <= 2; ++k)
-        if (r->part[k]) RANK_TRY(hipStreamWaitEvent(cs, r->sdone[k - 1], 0));
-    return HJB_OK;
-#undef RANK_TRY
+    RANK_TRY(r, hipSetDevice(r->S.device));
+    const bool halos = halo_stream != nullptr && (r->S.hlo || r->S.hhi);
+    if (halos) RANK_TRY(r, hipEventRecord(r->halo, (hipStream_t)halo_stream));
+    return slab_enqueue_stage(r->S, dJ_in, dJ_out, d_idx, (hipStream_t)compute_stream, halos ? r->halo : nullptr, strips_first, &r->err);
 }
 extern "C" {
 
@@ -303,19 +194,27 @@ int32_t hjb_rank_stage_post(hjb_rank r, const void *dJ_in, void *dJ_out, void *d
     return rank_stage(r, dJ_in, dJ_out, d_idx, compute_stream, halo_stream, true);
 }
 
+}  // extern "C"
+// `stream` waits for the last stage's strips where they cover every plane a neighbour needs (-> *covered)
+static int rank_wait_strips(hjb_rank r, hipStream_t stream, bool *covered) {
+    *covered = slab_strips_cover(r->S.cut, r->dn_needs, r->up_needs);
+    if (!*covered) return HJB_OK;
+    for (int k = 0; k < 2; ++k)
+        if (r->S.part[k + 1]) RANK_TRY(r, hipStreamWaitEvent(stream, r->S.sdone[k], 0));
+    // ... and, like the strips themselves, behind everything the compute stream held before that stage (J_out's halo planes
+    // were the previous stage's input)
+    RANK_TRY(r, hipStreamWaitEvent(stream, r->S.fork, 0));
+    return HJB_OK;
+}
+extern "C" {
+
 int32_t hjb_rank_wait_strips(hjb_rank r, void *stream, int32_t *covered) {
     if (!r) return rfail(r, HJB_E_INVALID, "null argument");
-    const int owned = r->end - r->begin;
-    const int lo_w = r->part[1] ? r->need_lo : 0, hi_w = r->part[2] ? r->need_hi : 0;
-    const bool cover = r->part[0] && r->dn_needs <= (r->part[1] ? lo_w : (r->dn_needs ? 0 : owned)) &&
-                       r->up_needs <= (r->part[2] ? hi_w : (r->up_needs ? 0 : owned));
+    if (hipSetDevice(r->S.device) != hipSuccess) return rfail(r, HJB_E_DEVICE, "hipSetDevice failed");
+    bool cover = false;
+    const int st = rank_wait_strips(r, (hipStream_t)stream, &cover);
     if (covered) *covered = cover ? 1 : 0;
-    if (!cover) return HJB_OK;
-    if (hipSetDevice(r->device) != hipSuccess) return rfail(r, HJB_E_DEVICE, "hipSetDevice failed");
-    for (int k = 0; k < 2; ++k)
-        if (r->part[k + 1] && hipStreamWaitEvent((hipStream_t)stream, r->sdone[k], 0) != hipSuccess) return rfail(r, HJB_E_DEVICE, "hipStreamWaitEvent failed");
-    if (hipStreamWaitEvent((hipStream_t)stream, r->fork, 0) != hipSuccess) return rfail(r, HJB_E_DEVICE, "hipStreamWaitEvent failed");
-    return HJB_OK;
+    return st;
 }
 
 // ---- RCCL inside the library: the halo exchange and the monitor's all-reduce of a rank, no torch, no MPI ------------------
@@ -394,11 +293,6 @@ bool rccl_load() {
         const ncclResult_t e_ = (expr);                                                                       \
         if (e_ != ncclSuccess) return rfail(r, HJB_E_DEVICE, "%s failed: %s", #expr, g_rccl.GetErrorString(e_)); \
     } while (0)
-#define RANKH_TRY(r, expr)                                                                                    \
-    do {                                                                                                      \
-        const hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return rfail(r, HJB_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
 
 // a fixed wall-clock delay on a stream (wall_clock64: the constant-rate counter): option "xfer_delay_us"
 __global__ void k_spin(long long ticks) {
@@ -434,7 +328,7 @@ int32_t hjb_rank_comm_init(hjb_rank r, const void *id128) {
     if (!r || !id128) return rfail(r, HJB_E_INVALID, "null argument");
     if (r->comm) return rfail(r, HJB_E_INVALID, "this rank already has a communicator");
     if (!rccl_load()) return rfail(r, HJB_E_UNSUPPORTED, "RCCL is not available: %s", g_rccl.why.c_str());
-    RANKH_TRY(r, hipSetDevice(r->device));
+    RANK_TRY(r, hipSetDevice(r->S.device));
     ncclUniqueId id;
     memcpy(id.internal, id128, sizeof id.internal);
     // loopback (option "comm_loopback", the one-GPU transport test): a communicator of ONE rank, both neighbours = this rank
@@ -472,29 +366,29 @@ int32_t hjb_rank_comm_info(hjb_rank r, int32_t *n_ranks, int32_t *comm_rank) {
 // the grouped send / recv of dJ's boundary planes on the transfer stream, which the caller has ordered behind the stage
 // (or the strips) that wrote them; xdone is recorded behind it
 static int rank_exchange_on_xfer(hjb_rank r, void *dJ) {
-    const size_t plane_b = (size_t)r->inner * r->esz;
-    const int owned = r->end - r->begin;
+    const size_t plane_b = (size_t)r->g.inner * r->g.esz;
+    const int owned = r->S.end - r->S.begin;
     char *J = (char *)dJ;
     const int dn = r->loopback ? 0 : r->rank - 1, up = r->loopback ? 0 : r->rank + 1;
-    if (!(r->dn_needs || r->hlo || r->up_needs || r->hhi)) { RANKH_TRY(r, hipEventRecord(r->xdone, r->xfer)); return HJB_OK; }
+    if (!(r->dn_needs || r->S.hlo || r->up_needs || r->S.hhi)) { RANK_TRY(r, hipEventRecord(r->xdone, r->xfer)); return HJB_OK; }
     RCCL_TRY(r, g_rccl.GroupStart());
     ncclResult_t e1 = ncclSuccess;
     // towards rank - 1: my lowest owned planes are its upper halo; its top planes are my lower halo
-    if (r->dn_needs && !e1) e1 = g_rccl.Send(J + plane_b * r->hlo, plane_b * r->dn_needs, kNcclUint8, dn, r->comm, r->xfer);
-    if (r->up_needs && !e1) e1 = g_rccl.Send(J + plane_b * (r->hlo + owned - r->up_needs), plane_b * r->up_needs, kNcclUint8, up, r->comm, r->xfer);
+    if (r->dn_needs && !e1) e1 = g_rccl.Send(J + plane_b * r->S.hlo, plane_b * r->dn_needs, kNcclUint8, dn, r->comm, r->xfer);
+    if (r->up_needs && !e1) e1 = g_rccl.Send(J + plane_b * (r->S.hlo + owned - r->up_needs), plane_b * r->up_needs, kNcclUint8, up, r->comm, r->xfer);
     // loopback: what goes "down" comes back as my own upper halo, what goes "up" as my lower halo (receives posted in the
     // order the one peer's sends were)
     if (r->loopback) {
-        if (r->hhi && !e1) e1 = g_rccl.Recv(J + plane_b * (r->hlo + owned), plane_b * r->hhi, kNcclUint8, 0, r->comm, r->xfer);
-        if (r->hlo && !e1) e1 = g_rccl.Recv(J, plane_b * r->hlo, kNcclUint8, 0, r->comm, r->xfer);
+        if (r->S.hhi && !e1) e1 = g_rccl.Recv(J + plane_b * (r->S.hlo + owned), plane_b * r->S.hhi, kNcclUint8, 0, r->comm, r->xfer);
+        if (r->S.hlo && !e1) e1 = g_rccl.Recv(J, plane_b * r->S.hlo, kNcclUint8, 0, r->comm, r->xfer);
     } else {
-        if (r->hlo && !e1) e1 = g_rccl.Recv(J, plane_b * r->hlo, kNcclUint8, dn, r->comm, r->xfer);
-        if (r->hhi && !e1) e1 = g_rccl.Recv(J + plane_b * (r->hlo + owned), plane_b * r->hhi, kNcclUint8, up, r->comm, r->xfer);
+        if (r->S.hlo && !e1) e1 = g_rccl.Recv(J, plane_b * r->S.hlo, kNcclUint8, dn, r->comm, r->xfer);
+        if (r->S.hhi && !e1) e1 = g_rccl.Recv(J + plane_b * (r->S.hlo + owned), plane_b * r->S.hhi, kNcclUint8, up, r->comm, r->xfer);
     }
     const ncclResult_t e2 = g_rccl.GroupEnd();
     if (e1 != ncclSuccess || e2 != ncclSuccess) return rfail(r, HJB_E_DEVICE, "halo exchange: %s", g_rccl.GetErrorString(e1 != ncclSuccess ? e1 : e2));
     if (r->xfer_delay_ticks > 0) hipLaunchKernelGGL(k_spin, dim3(1), dim3(1), 0, r->xfer, (long long)r->xfer_delay_ticks);
-    RANKH_TRY(r, hipEventRecord(r->xdone, r->xfer));
+    RANK_TRY(r, hipEventRecord(r->xdone, r->xfer));
     return HJB_OK;
 }
 extern "C" {
@@ -502,9 +396,9 @@ extern "C" {
 int32_t hjb_rank_exchange(hjb_rank r, void *dJ, void *compute_stream) {
     if (!r || !dJ) return rfail(r, HJB_E_INVALID, "null argument");
     if (!r->comm) return rfail(r, HJB_E_INVALID, "hjb_rank_comm_init first");
-    RANKH_TRY(r, hipSetDevice(r->device));
-    RANKH_TRY(r, hipEventRecord(r->xready, (hipStream_t)compute_stream));
-    RANKH_TRY(r, hipStreamWaitEvent(r->xfer, r->xready, 0));
+    RANK_TRY(r, hipSetDevice(r->S.device));
+    RANK_TRY(r, hipEventRecord(r->xready, (hipStream_t)compute_stream));
+    RANK_TRY(r, hipStreamWaitEvent(r->xfer, r->xready, 0));
     return rank_exchange_on_xfer(r, dJ);
 }
 
@@ -534,24 +428,17 @@ int32_t hjb_rank_step_post(hjb_rank r, void *dJ_in, void *dJ_out, void *d_idx, v
     const bool comm = r->world > 1 || r->loopback;
     if (!comm) return rank_stage(r, dJ_in, dJ_out, d_idx, compute_stream, nullptr, false);
     if (!r->comm) return rfail(r, HJB_E_INVALID, "hjb_rank_comm_init first");
-    RANKH_TRY(r, hipSetDevice(r->device));
+    RANK_TRY(r, hipSetDevice(r->S.device));
     hipStream_t cs = (hipStream_t)compute_stream;
     // the strips (or, without the split, the one kernel) wait for the previous exchange: halo_stream = the transfer stream
     int st = rank_stage(r, dJ_in, dJ_out, d_idx, compute_stream, (void *)r->xfer, true);
     if (st) return st;
-    const int owned = r->end - r->begin;
-    const int lo_w = r->part[1] ? r->need_lo : 0, hi_w = r->part[2] ? r->need_hi : 0;       // planes the strips cover
-    const bool strips_cover = r->part[0] && r->dn_needs <= (r->part[1] ? lo_w : (r->dn_needs ? 0 : owned)) &&
-                              r->up_needs <= (r->part[2] ? hi_w : (r->up_needs ? 0 : owned));
-    if (strips_cover) {
-        for (int k = 0; k < 2; ++k)
-            if (r->part[k + 1]) RANKH_TRY(r, hipStreamWaitEvent(r->xfer, r->sdone[k], 0));
-        // ... and, like the strips themselves, behind everything the compute stream held before this stage (J_out's halo
-        // planes were the previous stage's input)
-        RANKH_TRY(r, hipStreamWaitEvent(r->xfer, r->fork, 0));
-    } else {
-        RANKH_TRY(r, hipEventRecord(r->xready, cs));
-        RANKH_TRY(r, hipStreamWaitEvent(r->xfer, r->xready, 0));
+    bool covered = false;                   // the strips cover what the neighbours need: the transfer stream goes behind them alone
+    st = rank_wait_strips(r, r->xfer, &covered);
+    if (st) return st;
+    if (!covered) {
+        RANK_TRY(r, hipEventRecord(r->xready, cs));
+        RANK_TRY(r, hipStreamWaitEvent(r->xfer, r->xready, 0));
     }
     return rank_exchange_on_xfer(r, dJ_out);
 }
@@ -561,24 +448,24 @@ int32_t hjb_rank_step_post(hjb_rank r, void *dJ_in, void *dJ_out, void *d_idx, v
 int32_t hjb_rank_monitor_sums(hjb_rank r, const void *dJ, const void *d_idx, void *compute_stream, double *sums2) {
     if (!r || !dJ || !sums2) return rfail(r, HJB_E_INVALID, "null argument");
     if (!r->comm) return rfail(r, HJB_E_INVALID, "hjb_rank_comm_init first");
-    RANKH_TRY(r, hipSetDevice(r->device));
+    RANK_TRY(r, hipSetDevice(r->S.device));
     hipStream_t cs = (hipStream_t)compute_stream;
-    const size_t plane_b = (size_t)r->inner * r->esz;
-    const int64_t n = r->inner * (int64_t)(r->end - r->begin);
+    const size_t plane_b = (size_t)r->g.inner * r->g.esz;
+    const int64_t n = r->g.inner * (int64_t)(r->S.end - r->S.begin);
     // option "monitor_single" at world == 1: the library's stated float32 tree over the whole grid, exactly hjb_solve's sum.
     // Over several ranks a float32 running sum in one fixed order does not exist: each rank sums its planes in float64 (fixed
     // tree) and the all-reduce adds the ranks in ITS order - reproducible for a given world size, not bit-identical to
     // hjb_solve's sum; hjb_rank_sweep then forms the difference and the comparison in single (below).
-    const bool single_tree = r->monitor_single && r->world == 1 && !r->loopback && r->dtype != HJB_F64;
-    if (launch_monitor_sums(r->dtype, single_tree, (const char *)dJ + plane_b * r->hlo, d_idx, (int32_t)r->isz, n, r->d_partials, r->d_sums, cs) != HJB_OK)
+    const bool single_tree = r->monitor_single && r->world == 1 && !r->loopback && r->g.dtype != HJB_F64;
+    if (launch_monitor_sums(r->g.dtype, single_tree, (const char *)dJ + plane_b * r->S.hlo, d_idx, (int32_t)r->g.isz, n, r->d_partials, r->d_sums, cs) != HJB_OK)
         return rfail(r, HJB_E_DEVICE, "monitor reduction launch failed");
-    if (!d_idx) RANKH_TRY(r, hipMemsetAsync(r->d_sums + 1, 0, sizeof(double), cs));
+    if (!d_idx) RANK_TRY(r, hipMemsetAsync(r->d_sums + 1, 0, sizeof(double), cs));
     // one communicator, one order: the all-reduce goes behind whatever exchange is still pending on the transfer stream
     // (post-exchange order; include/hjbdp.h "concurrent use of the communicator") - once per monitor period
-    if (r->xdone) RANKH_TRY(r, hipStreamWaitEvent(cs, r->xdone, 0));
+    if (r->xdone) RANK_TRY(r, hipStreamWaitEvent(cs, r->xdone, 0));
     RCCL_TRY(r, g_rccl.AllReduce(r->d_sums, r->d_sums, 2, kNcclFloat64, kNcclSum, r->comm, cs));
-    RANKH_TRY(r, hipMemcpyAsync(sums2, r->d_sums, 2 * sizeof(double), hipMemcpyDeviceToHost, cs));
-    RANKH_TRY(r, hipStreamSynchronize(cs));
+    RANK_TRY(r, hipMemcpyAsync(sums2, r->d_sums, 2 * sizeof(double), hipMemcpyDeviceToHost, cs));
+    RANK_TRY(r, hipStreamSynchronize(cs));
     return HJB_OK;
 }
 
@@ -591,14 +478,14 @@ int32_t hjb_rank_sweep(hjb_rank r, int32_t n_stages, int32_t monitor_period, dou
     if (!r || !dJ0 || !dJ1 || n_stages < 0) return rfail(r, HJB_E_INVALID, "bad argument");
     if (r->world > 1 && !r->comm) return rfail(r, HJB_E_INVALID, "hjb_rank_comm_init first (world > 1)");
     if (monitor_period > 0 && !r->comm) return rfail(r, HJB_E_INVALID, "the monitor needs a communicator (hjb_rank_comm_init), also at world == 1");
-    RANKH_TRY(r, hipSetDevice(r->device));
+    RANK_TRY(r, hipSetDevice(r->S.device));
     hipStream_t cs = (hipStream_t)compute_stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     void *J[2] = {dJ0, dJ1};
     int cur = 0, done = 0, early = 0, st = HJB_OK;
     double fprev = 0.0;
     // Solver_pos_att.m:276-282 with a single fsum50: the difference and `abs(e) < tol` are single-precision (hjb_solve's rule)
-    const bool msingle = r->monitor_single && r->dtype != HJB_F64;
+    const bool msingle = r->monitor_single && r->g.dtype != HJB_F64;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, cs) != hipSuccess)
         st = rfail(r, HJB_E_DEVICE, "sweep: event set-up failed: %s", hipGetErrorString(hipGetLastError()));
     const bool post = r->post_exchange && (r->world > 1 || r->loopback);

@@ -149,6 +149,22 @@ def colsweep_problem(seed, n, nU=9, nonuniform=False, gax=3, big=2.7, small=0.6,
     return ProblemSpec(knots, [nU], nxt, ct, dtype=dtype, index_base=index_base, j_storage=j_storage)
 
 
+def uphill_problem(seed=0, n=(8, 6, 17), dtype=np.float32, index_base=1):
+    """A problem whose LAST axis drifts upward only - the halo a slab needs is not symmetric (hjbdp.sharded.required_halo:
+    (1, 2) planes; the one low plane is the last cell's clamp).  D = 3, one control dim of 4 levels: axis 0 moves with dim 1 and
+    axis 1 with dim 2 by at most 0.4 cells, axis 2 by (0.2, 0.7, 1.3, 1.8) cells with the control.  cost = per-axis quadratics
+    + 0.3 u^2."""
+    rng = np.random.default_rng(seed)
+    assert len(n) == 3
+    knots = [np.linspace(-1.0, 1.0, n[a]).astype(dtype).astype(np.float64) for a in range(3)]
+    hs = [2.0 / (n[a] - 1) for a in range(3)]
+    nxt = [[Term((0,), knots[0].copy()), Term((1,), 0.4 * hs[0] * rng.uniform(-1, 1, n[1]))],
+           [Term((1,), knots[1].copy()), Term((2,), 0.4 * hs[1] * rng.uniform(-1, 1, n[2]))],
+           [Term((2,), knots[2].copy()), Term((3,), hs[2] * np.array([0.2, 0.7, 1.3, 1.8]))]]
+    cost = [Term((a,), (1.0 + a) * knots[a] ** 2) for a in range(3)] + [Term((3,), 0.3 * np.arange(4.0) ** 2)]
+    return ProblemSpec(knots, [4], nxt, cost, dtype=dtype, index_base=index_base)
+
+
 def rate_shared_problem(seed, n_so, n_rates, m=(11, 11, 11), gain=(0.55, 0.5, 0.6), nonuniform=False, so_move=0.7,
                         dtype=np.float32, index_base=1, j_storage=None):
     """The shape of K15 (kernels_uniwin.h; Solver_attitude.run with the angle axes first): the state-only axes `n_so`, whose

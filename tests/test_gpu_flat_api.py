@@ -188,14 +188,16 @@ def test_progress_after_every_stage(env):
     assert np.array_equal(out["J"], ref["J"])
 
 
-@pytest.mark.parametrize("case", ["colsweep", "nested3", "monitor", "f16"])
+@pytest.mark.parametrize("case", ["colsweep", "nested3", "monitor", "f16", "uphill3", "uphill5"])
 def test_solve_multi_matches_single_device(env, case):
     """hjb_create_multi / hjb_solve_multi (the single-process multi-GPU sweep a MATLAB host would call): the grid in
     several slabs with per-stage device-to-device halo copies overlapped with the interior planes.  The 1-GPU box
     gives every slab the same device (the copies are then plain device-to-device); bit-equal to the oracle's whole
-    grid sweep, including the early-stop monitor's decision."""
+    grid sweep, including the early-stop monitor's decision.  uphill3 / uphill5: a halo of (1, 2) planes - the strips of a
+    middle slab differ in width, and among five slabs those of three planes have no interior: they wait for their halos, then
+    run one kernel, beside neighbours that split."""
     hjbdp, _abi, c_oracle = env
-    from problems import colsweep_problem, nested_problem, random_terminal
+    from problems import colsweep_problem, nested_problem, random_terminal, uphill_problem
     kw = {}
     if case == "colsweep":        # window axis last: halo of one plane; interior + strips
         spec, devs, stages = colsweep_problem(5, (36, 7, 9, 14), gax=2), [0, 0, 0], 5
@@ -204,6 +206,8 @@ def test_solve_multi_matches_single_device(env, case):
     elif case == "monitor":
         spec, devs, stages = colsweep_problem(6, (20, 6, 8, 12), gax=2, cost="multi"), [0, 0], 11
         kw = {"monitor_period": 3, "monitor_tol": 1e12}      # stops at the first monitor point, k_s = 9, after 3 stages
+    elif case.startswith("uphill"):
+        spec, devs, stages = uphill_problem(), [0] * int(case[-1]), 4
     else:
         spec, devs, stages = colsweep_problem(7, (33, 6, 8, 15), gax=2, j_storage=np.float16), [0, 0, 0, 0], 3
     term = random_terminal(spec, 4)
@@ -216,6 +220,11 @@ def test_solve_multi_matches_single_device(env, case):
     assert all(a["end"] == b["begin"] for a, b in zip(infos, infos[1:]))
     if case != "nested3":
         assert any(i["split"] for i in infos), infos          # the overlapped form was exercised
+    if case.startswith("uphill"):
+        assert np.all(np.isfinite(ref["J_stages"]))
+        assert (infos[1]["halo_lo"], infos[1]["halo_hi"]) == (1, 2)      # an inner slab's halos are the need
+        assert [i["end"] - i["begin"] for i in infos] == {"uphill3": [6, 6, 5], "uphill5": [4, 4, 3, 3, 3]}[case]
+        assert [i["split"] for i in infos] == {"uphill3": [1, 1, 1], "uphill5": [1, 1, 0, 0, 1]}[case], infos
     assert out["stages_done"] == ref["stages_done"] and out["stopped_early"] == ref["stopped_early"]
     assert np.array_equal(out["J"], ref["J"]) and np.array_equal(out["idx"], ref["idx"])
     assert np.array_equal(out["J_stages"], ref["J_stages"]) and np.array_equal(out["idx_stages"], ref["idx_stages"])   # every stage's planes
@@ -223,6 +232,51 @@ def test_solve_multi_matches_single_device(env, case):
     if kw:
         assert out["stopped_early"] and out["stages_done"] == 3
         assert abs(out["last_e"] - ref["last_e"]) <= 1e-9 * abs(ref["last_e"])
+
+
+# (the colsweep cases keep the ids they had before the spec was a parameter)
+_OVERLAP_AND_SPEC = [pytest.param(True, "colsweep", id="True"), pytest.param(False, "colsweep", id="False"),
+                     pytest.param(True, "uphill", id="True-uphill"), pytest.param(False, "uphill", id="False-uphill")]
+
+
+def _rank_test_spec(hjbdp, kind):
+    """colsweep: the column-sweep shape, halo (1, 1); uphill: problems.uphill_problem, halo (1, 2)."""
+    from problems import colsweep_problem, uphill_problem
+    if kind == "uphill":
+        return uphill_problem()
+    spec0 = colsweep_problem(15, (36, 7, 9, 14), gax=2)
+    return hjbdp.ProblemSpec(spec0.knots, spec0.m, spec0.next_terms, spec0.cost_terms, dtype=np.float32, index_base=1, idx_dtype="auto")
+
+
+def test_multi_and_rank_partition_alike(env):
+    """hjb_create_multi and hjb_rank_create cut the last axis alike - ranges, clipped halos, which slabs split - and as
+    hjbdp.sharded.partition does, for every number of slabs; both refuse the same partitions with the same words.  No stage runs.
+    17 planes, halo (1, 2).  Nine slabs are 2, ..., 2, 1 planes: the one-plane slab is the LAST, the high halo of the slab below
+    it is clipped to that one plane, so every halo still comes from the immediate neighbour and both constructors accept it (as
+    they did before the slab record).  Ten slabs are the first refused: 2 x 7 then 1, 1, 1 - slab 6 needs two planes of slab 7's one."""
+    hjbdp, _abi, c_oracle = env
+    from hjbdp.sharded import partition
+    from problems import uphill_problem
+    spec = uphill_problem()
+    keys = ("begin", "end", "halo_lo", "halo_hi", "split")
+    for w in range(1, 10):
+        with hjbdp.MultiBackup(spec, [0] * w) as mb:
+            multi = [tuple(mb.slab_info(i)[k] for k in keys) for i in range(w)]
+        rank = []
+        for i in range(w):
+            r = hjbdp.RankSlab(spec, 0, i, w)
+            assert (r.need_lo, r.need_hi, r.n_planes) == (1, 2, 17)
+            rank.append((r.begin, r.end, r.halo_lo, r.halo_hi, r.split))
+            r.close()
+        assert multi == rank, w
+        assert [m[:2] for m in multi] == partition(17, w), w
+        assert [m[2:4] for m in multi] == [(min(1, b), min(2, 17 - e)) for b, e in partition(17, w)], w
+    assert [m[1] - m[0] for m in multi] == [2] * 8 + [1] and multi[7][2:4] == (1, 1) and not any(m[4] for m in multi)
+    for w, words in ((10, "halo (1/2 planes) wider than a neighbouring slab"), (18, "more ")):
+        for make in (lambda: hjbdp.MultiBackup(spec, [0] * w), lambda: hjbdp.RankSlab(spec, 0, 0, w)):
+            with pytest.raises(hjbdp.HjbError) as e:
+                make()
+            assert e.value.status == _abi.HJB_E_INVALID and str(e.value).startswith("libhjbdp: " + words), str(e.value)
 
 
 def test_solve_multi_refuses_what_it_cannot_do(env):
@@ -235,21 +289,24 @@ def test_solve_multi_refuses_what_it_cannot_do(env):
         hjbdp.MultiBackup(spec, [0] * 17)                     # more slabs than planes
 
 
-@pytest.mark.parametrize("overlap", [True, False])
-def test_rank_api_three_ranks_in_one_process(env, overlap):
+@pytest.mark.parametrize("overlap, kind", _OVERLAP_AND_SPEC)
+def test_rank_api_three_ranks_in_one_process(env, overlap, kind):
     """hjb_rank_create / hjb_rank_stage (one process per GPU; here three ranks driven from one process, all on this box's
     GPU): library-owned buffers, the halo planes moved by the caller with device-to-device copies between the ranks'
     buffers before each stage - the role MPI / RCCL play in a real run - and every stage one hjb_rank_stage call per rank
     (interior + strips with overlap).  All planes of every stage equal the oracle's whole-grid sweep."""
     hjbdp, _abi, c_oracle = env
-    from problems import colsweep_problem, random_terminal
-    spec0 = colsweep_problem(15, (36, 7, 9, 14), gax=2)
-    spec = hjbdp.ProblemSpec(spec0.knots, spec0.m, spec0.next_terms, spec0.cost_terms, dtype=np.float32, index_base=1, idx_dtype="auto")
+    from problems import random_terminal
+    spec = _rank_test_spec(hjbdp, kind)
     term = random_terminal(spec, 8)
     stages, world = 4, 3
     ref = c_oracle.sweep(_abi, spec, stages, terminal=term, keep_J=True, keep_idx=True)
     inner = spec.nS // spec.n[-1]
     ranks = [hjbdp.RankSlab(spec, 0, r, world, overlap=overlap) for r in range(world)]
+    if kind == "uphill":
+        assert np.all(np.isfinite(ref["J_stages"]))
+        assert all((r.need_lo, r.need_hi) == (1, 2) for r in ranks)
+        assert [(r.begin, r.end, r.halo_lo, r.halo_hi) for r in ranks] == [(0, 6, 0, 2), (6, 12, 1, 2), (12, 17, 1, 0)]
     assert ranks[0].begin == 0 and ranks[-1].end == spec.n[-1] and all(a.end == b.begin for a, b in zip(ranks, ranks[1:]))
     assert any(r.split for r in ranks) == overlap
     lib = ranks[0].lib
@@ -507,22 +564,24 @@ def _rccl_unique_id(lib, _abi):
     return uid
 
 
-@pytest.mark.parametrize("overlap", [True, False])
-def test_rccl_transport_inside_the_library_loopback(env, overlap):
+@pytest.mark.parametrize("overlap, kind", _OVERLAP_AND_SPEC)
+def test_rccl_transport_inside_the_library_loopback(env, overlap, kind):
     """hjb_rank_comm_init / hjb_rank_exchange / hjb_rank_step / hjb_rank_monitor_sums: the RCCL calls of a middle rank
     (ncclGroupStart, two ncclSend, two ncclRecv, ncclGroupEnd on the library's transfer stream; a 2-double ncclAllReduce)
     executed for real on this box's ONE GPU through the loopback option - a communicator of one rank that is both of its
     neighbours: the planes it sends down arrive in its own upper halo, those it sends up in its lower halo.  After the
     exchange the halos hold exactly those planes, and the stage that follows (interior beside the transfer, strips behind
-    it) equals the oracle's backup of that buffer bit for bit."""
+    it) equals the oracle's backup of that buffer bit for bit.  On the uphill spec (halo (1, 2)) the loopback rank needs 2
+    planes below of a low strip 1 plane wide: the strips do not cover it, and hjb_rank_step_post's exchange goes behind the
+    whole stage."""
     hjbdp, _abi, c_oracle = env
-    from problems import colsweep_problem, random_terminal
-    spec0 = colsweep_problem(15, (36, 7, 9, 14), gax=2)
-    spec = hjbdp.ProblemSpec(spec0.knots, spec0.m, spec0.next_terms, spec0.cost_terms, dtype=np.float32, index_base=1, idx_dtype="auto")
+    spec = _rank_test_spec(hjbdp, kind)
     inner = spec.nS // spec.n[-1]
     rk = hjbdp.core.RankSlab(spec, 0, 1, 3, overlap=overlap)
     lib = rk.lib
     assert rk.halo_lo > 0 and rk.halo_hi > 0 and rk.split == (1 if overlap else 0)
+    if kind == "uphill":
+        assert (rk.need_lo, rk.need_hi) == (1, 2) and (rk.begin, rk.end, rk.halo_lo, rk.halo_hi) == (6, 12, 1, 2)
     owned, hlo, hhi = rk.end - rk.begin, rk.halo_lo, rk.halo_hi
     planes = owned + hlo + hhi
     rk.set_option("comm_loopback", 1)
@@ -551,6 +610,7 @@ def test_rccl_transport_inside_the_library_loopback(env, overlap):
         rk.check_device_status()
         Jo, io = c_oracle.backup_stage(_abi, spec, np.asfortranarray(want).reshape(-1, order="F"), slab=(rk.begin, rk.end, hlo, hhi))
         mine = dOut.download(np.float32).reshape(inner, planes, order="F")[:, hlo:hlo + owned]
+        assert np.all(np.isfinite(Jo))
         assert np.array_equal(mine, Jo.reshape(inner, planes, order="F")[:, hlo:hlo + owned])
         assert np.array_equal(dI.download(spec.idx_np_dtype), io)
         # the monitor's two sums through ncclAllReduce (one rank: the local sums)
@@ -571,6 +631,9 @@ def test_rccl_transport_inside_the_library_loopback(env, overlap):
         own = Jo.reshape(inner, planes, order="F")[:, hlo:hlo + owned]
         assert np.array_equal(got[:, hlo:hlo + owned], own) and np.array_equal(dI.download(spec.idx_np_dtype), io)
         assert np.array_equal(got[:, :hlo], own[:, owned - hlo:]) and np.array_equal(got[:, hlo + owned:], own[:, :hhi])
+        # whether that exchange went behind the strips alone: with the split, and the needs (loopback: hhi below, hlo above) within
+        # the strips (need_lo, need_hi wide)
+        assert rk.wait_strips(0) == (overlap and kind == "colsweep")
         # the whole loop both ways (option "post_exchange"): the same sweep, equal to the oracle driven stage by stage with the
         # loopback's halos (each stage's input halos = that buffer's own boundary planes)
         cur = init.copy()
