@@ -444,6 +444,47 @@ int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const in
 int32_t hjb_rollout_destroy(void *rollout);
 const char *hjb_rollout_last_error(void *rollout);
 
+/* ---- noisy rollouts: the affine loop under sampled additive process noise (kernel K25) --------------------------------------
+ *   x+ = A x + B u + c + d_w,   node w of a finite set (d_w, p_w) drawn per trajectory and step
+ * - the model class of hjb_set_disturbance's additive next-state offsets, with the same layout (offsets [D, n_nodes] column-major,
+ * weights [n_nodes] or NULL = equal) and the same limit HJB_DIST_MAX_NODES, so one node set serves both: design under it
+ * (hjb_solve on a disturbed handle), price the policy under it (hjb_evaluate on that handle), fly it under it (here), compare.
+ * hjb_rollout_set_noise gives the object a node set (n_nodes == 0 detaches).  The noise is a property of the object, independent
+ * of the model; ONLY hjb_rollout_run_noisy reads it: hjb_rollout_run and every other run function of an object that holds noise
+ * give the bits they gave before.  hjb_rollout_run_noisy is hjb_rollout_run (the affine model, the same arguments, the same
+ * arithmetic in the same order) with, per step k after the affine update acc_a:
+ *   w = the drawn node (below);  x+_a = acc_a + d[a][w] for every axis a of the offset mask - the axes with at least one offset
+ *   that is not +-0; an axis outside the mask is not touched, not even by adding 0.0.
+ * So with ONE node of zero offsets it equals hjb_rollout_run bit for bit.  W_path [n_traj, n_steps] (NULL: not kept): the drawn
+ * node of every step, as a double.  The cost is the cost of the states actually visited.
+ * The random stream and the sampler (csrc/hjbdp_noise.h, shared by the kernel and the two host twins below):
+ *   generator   Philox4x32-10: multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85, ten rounds;
+ *   addressing  counter-based, no state between calls: the stream of a trajectory is s = first_stream + i, a uint64, i the
+ *               trajectory's index in the CALL (not in the chunk: option "chunk" does not change a bit); step k reads word k & 3
+ *               of Philox(counter = (lo32 s, hi32 s, k >> 2, 0), key = (lo32 seed, hi32 seed)): one Philox call per four steps.
+ *               One run of 2n trajectories equals two runs of n at first_stream and first_stream + n;
+ *   thresholds  W - 1 doubles built once on the host, T[w] = floor(2^32 * (S_w / S_{W-1})), S_w = p_0 + ... + p_w summed left
+ *               to right in double (NULL weights: p_w = 1.0 each); the drawn node is the number of w in [0, W-2] with
+ *               T[w] <= (double)word.  Doubles keep T = 2^32 representable, so a trailing zero-weight node is never drawn; a
+ *               zero-weight node anywhere is never drawn; W = 1 draws node 0.  Probabilities resolve to 2^-32.
+ * hjb_rollout_noise_table writes the W - 1 thresholds of a weight vector; hjb_rollout_noise_draw writes the nodes n_traj streams
+ * draw over n_steps steps (nodes [n_traj, n_steps], trajectory fastest) from thresholds in [0, 2^32] that do not decrease.  Both
+ * run without a device and call the functions the kernel calls.
+ * Refused before any device work, outputs untouched (text: hjb_rollout_last_error) - HJB_E_INVALID: a null handle; n_nodes outside
+ * 0..HJB_DIST_MAX_NODES; null offsets with n_nodes > 0; an offset that is not finite; a weight that is not finite or is negative,
+ * or weights that sum to 0; hjb_rollout_run_noisy with no noise set or with a model other than the affine one, and everything
+ * hjb_rollout_run refuses; first_stream < 0 or first_stream + n_traj overflowing.  In the LDS form the node block (thresholds,
+ * then the masked axes' offsets) is staged behind knots, 1/dx and u_table; the 32 KiB rule of option "lds" applies to the sum.
+ * Out of scope: noise that depends on the control or the state, and continuous distributions (discretise them into nodes:
+ * the Gauss-Hermite and box helpers of the host packages). */
+int32_t hjb_rollout_set_noise(void *rollout, int32_t n_nodes, const double *offsets, const double *weights);
+int32_t hjb_rollout_run_noisy(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                              const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost, double *X_path,
+                              double *U_path, double *W_path, double *device_ms);
+int32_t hjb_rollout_noise_table(int32_t n_nodes, const double *weights, double *thresholds);
+int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_traj, int32_t n_steps, int32_t n_nodes,
+                               const double *thresholds, int32_t *nodes);
+
 /* The 6-D attitude closed loop (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run) on the same object.
  * hjb_rollout_set_attitude_model and hjb_rollout_set_model replace each other: the last one set wins.  It needs D == 6, n_u == 3
  * and the grid axes in the reference's order (w1, w2, w3, yaw, pitch, roll); inertia = [J1 J2 J3] and h finite and > 0,

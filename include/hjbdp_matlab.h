@@ -104,6 +104,17 @@ int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const in
                         const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *device_ms);
 int32_t hjb_rollout_destroy(void *rollout);
 const char *hjb_rollout_last_error(void *rollout);
+/* the affine loop under sampled additive process noise (kernel K25): a node set as hjb_set_disturbance takes it (offsets
+ * [D, n_nodes] column-major, weights [n_nodes] or NULL = equal; n_nodes 0 detaches), one Philox4x32-10 stream per trajectory
+ * (first_stream + its index in the call), W_path the drawn node of every step; the two host twins of the sampler need no device
+ * (hjbdp.h); usage: matlab/Dynamic_Solver_hjbdp_get_noisy_paths.m */
+int32_t hjb_rollout_set_noise(void *rollout, int32_t n_nodes, const double *offsets, const double *weights);
+int32_t hjb_rollout_run_noisy(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                              const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost, double *X_path,
+                              double *U_path, double *W_path, double *device_ms);
+int32_t hjb_rollout_noise_table(int32_t n_nodes, const double *weights, double *thresholds);
+int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_traj, int32_t n_steps, int32_t n_nodes,
+                               const double *thresholds, int32_t *nodes);
 /* the 6-D attitude loop on the same object (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run);
  * usage: matlab/Solver_attitude_hjbdp_get_optimal_paths.m */
 int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, double h, int32_t integrator, const double *q,

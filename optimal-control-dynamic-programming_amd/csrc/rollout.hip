@@ -6,6 +6,9 @@
 //   kernels_rollout_position.h / rollout_position.hip), simplified attitude (K20, kernels_rollout_attitude_simplified.h /
 //   rollout_attitude_simplified.hip).
 // The linear attitude controller (K21, kernels_rollout_attitude_linear.h / rollout_attitude_linear.hip) needs no object.
+// Beside the model an object may hold a noise node set (hjb_rollout_set_noise): hjb_rollout_run_noisy (K25,
+// kernels_rollout_noisy.h / rollout_noisy.hip) flies the affine loop under it, and no other run function reads it.  The sampler's
+// host twins hjb_rollout_noise_table / hjb_rollout_noise_draw (hjbdp_noise.h) need no device.
 // Shared here: the attached-channels record and attach_channels (the three attaching setters), check_run / check_traj /
 // check_quaternions (the run functions' refusals, all before any device work), lds_bytes, run_chunks (the chunk loop).
 #include "hjbdp_host.h"
@@ -16,6 +19,7 @@
 #include "kernels_rollout_position.h"
 #include "kernels_rollout_attitude_simplified.h"
 #include "kernels_rollout_attitude_linear.h"
+#include "kernels_rollout_noisy.h"
 #include "rollout_dispatch.h"
 #include <memory>
 
@@ -85,6 +89,9 @@ struct Rollout {
     DAttitude M{};                  // the attitude model (set_attitude_model)
     std::unique_ptr<Attached> att;  // the PosAtt / Position / AttSimplified of model kModelPosAtt / kModelPosition / kModelAttSimplified
     std::shared_ptr<DevData> data;
+    // the noise node set (hjb_rollout_set_noise): N.n_nodes > 0 while one is set; read by hjb_rollout_run_noisy alone
+    DNoise N{};
+    std::shared_ptr<DevData> noise;     // N.tab: thresholds, then the masked axes' offsets
     hipStream_t stream = nullptr;
     std::string err;
 };
@@ -105,6 +112,7 @@ int rfail(Rollout *ro, int code, const char *fmt, ...) {
 
 void release(Rollout *ro) {
     ro->att.reset();
+    ro->noise.reset();
     ro->data.reset();
     if (ro->stream) (void)hipStreamDestroy(ro->stream);
     ro->stream = nullptr;
@@ -395,6 +403,19 @@ int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n
                double *device_ms, Launch launch) {
     return run_chunks(ro, who, W, n_up, n_e, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, E_path, flags, device_ms,
                       launch, [](int64_t, int64_t, hipStream_t) { return hipSuccess; });
+}
+
+// What hjb_rollout_set_noise and hjb_rollout_noise_table refuse of a weight vector (null: equal weights), said in `who`'s name:
+// a weight that is not finite or is negative, weights that sum to 0.  HJB_OK otherwise.
+int check_weights(Rollout *ro, const char *who, int32_t n_nodes, const double *weights) {
+    if (!weights) return HJB_OK;
+    double sum = 0.0;
+    for (int w = 0; w < n_nodes; ++w) {
+        if (!std::isfinite(weights[w]) || weights[w] < 0) return rfail(ro, HJB_E_INVALID, "%s: weight %d is not finite or is negative", who, w);
+        sum = sum + weights[w];
+    }
+    if (!(sum > 0) || !std::isfinite(sum)) return rfail(ro, HJB_E_INVALID, "%s: the %d weights sum to 0 (or their sum overflows)", who, n_nodes);
+    return HJB_OK;
 }
 
 }  // namespace
@@ -779,6 +800,137 @@ int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const in
                           double *dXp, double *dUp, double *, int32_t *) {
                           return launch_rollout(idx_bytes, method, lds_on, D, R, nc, lds, st, dX0, dXf, dC, dXp, dUp);
                       });
+}
+
+int32_t hjb_rollout_set_noise(void *rollout, int32_t n_nodes, const double *offsets, const double *weights) {
+    Rollout *ro = (Rollout *)rollout;
+    // the arguments that need no object first, then the object; every refusal before any device work
+    if (n_nodes < 0 || n_nodes > HJB_DIST_MAX_NODES)
+        return rfail(ro, HJB_E_INVALID, "hjb_rollout_set_noise: n_nodes=%d not in 0..%d", n_nodes, HJB_DIST_MAX_NODES);
+    if (n_nodes > 0 && !offsets) return rfail(ro, HJB_E_INVALID, "hjb_rollout_set_noise: null offsets with n_nodes=%d", n_nodes);
+    if (const int bad = n_nodes > 0 ? check_weights(ro, "hjb_rollout_set_noise", n_nodes, weights) : HJB_OK) return bad;
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "hjb_rollout_set_noise: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    const int D = ro->D;
+    int mask = 0;
+    for (int w = 0; w < n_nodes; ++w)
+        for (int a = 0; a < D; ++a) {
+            const double d = offsets[a + (int64_t)D * w];
+            if (!std::isfinite(d)) return rfail(ro, HJB_E_INVALID, "hjb_rollout_set_noise: offset of axis %d, node %d is not finite", a, w);
+            if (d != 0.0) mask |= 1 << a;
+        }
+    // the node block as K25 reads it: [T (W - 1) | d (W x n_axes, node index fastest)]
+    int n_axes = 0;
+    for (int a = 0; a < D; ++a) n_axes += (mask >> a) & 1;
+    std::vector<double> tab((size_t)std::max(n_nodes - 1, 0) + (size_t)n_nodes * n_axes);
+    if (n_nodes > 0) {
+        (void)noise_table(n_nodes, weights, tab.data());
+        double *row = tab.data() + (n_nodes - 1);
+        for (int a = 0; a < D; ++a) {
+            if (!((mask >> a) & 1)) continue;
+            for (int w = 0; w < n_nodes; ++w) row[w] = offsets[a + (int64_t)D * w];
+            row += n_nodes;
+        }
+    }
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
+    std::shared_ptr<DevData> nd;
+    void *d = nullptr;
+    if (n_nodes > 0) {
+        nd = std::make_shared<DevData>();
+        nd->device = ro->device;
+        const size_t tb = tab.size() * sizeof(double);
+        if (hipMalloc(&d, std::max<size_t>(tb, 16)) != hipSuccess) return rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", tb);
+        nd->allocs.push_back(d);
+        if (tb && hipMemcpy(d, tab.data(), tb, hipMemcpyHostToDevice) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "rollout: upload failed");
+    }
+    if (ro->stream) (void)hipStreamSynchronize(ro->stream);
+    ro->noise = std::move(nd);                                // replaces (and releases) a node set given earlier
+    ro->N = DNoise{};
+    ro->N.n_nodes = n_nodes;
+    ro->N.mask = mask;
+    ro->N.n_axes = n_axes;
+    ro->N.n_tab = (int32_t)tab.size();
+    ro->N.tab = (const double *)d;
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_run_noisy(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                              const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost, double *X_path,
+                              double *U_path, double *W_path, double *device_ms) {
+    Rollout *ro = (Rollout *)rollout;
+    // every refusal before any device work, the outputs untouched; the one that needs no object first
+    if (first_stream < 0) return rfail(ro, HJB_E_INVALID, "hjb_rollout_run_noisy: first_stream=%lld < 0", (long long)first_stream);
+    if (n_traj > 0 && first_stream > INT64_MAX - n_traj)
+        return rfail(ro, HJB_E_INVALID, "hjb_rollout_run_noisy: first_stream + n_traj overflows (%lld + %lld)", (long long)first_stream,
+                     (long long)n_traj);
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    const int bad_arg = check_run(ro, kModelAffine, method, n_steps, plane_of_step, n_traj);
+    if (bad_arg) return bad_arg;
+    if (ro->N.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: hjb_rollout_run_noisy before hjb_rollout_set_noise");
+    if (n_traj == 0) {
+        if (device_ms) *device_ms = 0.0;
+        return HJB_OK;
+    }
+    const int D = ro->D;
+    const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
+    if (bad_traj) return bad_traj;
+    if (device_ms) *device_ms = 0.0;
+    const int idx_bytes = ro->idx_bytes;
+    const bool lds_wanted = ro->lds;
+    DNoise N = ro->N;
+    N.seed = seed;
+    int64_t chunk_i0 = 0;                                     // the chunk's offset in the call: streams count through the call
+    return run_chunks(ro, "hjb_rollout_run_noisy", D, ro->R.n_u, 1, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, W_path,
+                      nullptr, device_ms,
+                      [&](const DRollout &R, int64_t nc, size_t lds, bool, hipStream_t st, double *dX0, double *dXf, double *dC, double *dXp,
+                          double *dUp, double *dWp, int32_t *) {
+                          DNoise Nc = N;
+                          Nc.first = (uint64_t)first_stream + (uint64_t)chunk_i0;
+                          Nc.Wp = dWp;
+                          const size_t lds_all = lds + (size_t)N.n_tab * sizeof(double);
+                          return launch_rollout_noisy(idx_bytes, method, lds_wanted && lds_all <= kLdsMax, D, R, Nc, nc, lds_all, st, dX0,
+                                                      dXf, dC, dXp, dUp);
+                      },
+                      [&](int64_t i0, int64_t, hipStream_t) {
+                          chunk_i0 = i0;
+                          return hipSuccess;
+                      });
+}
+
+int32_t hjb_rollout_noise_table(int32_t n_nodes, const double *weights, double *thresholds) {
+    if (n_nodes < 1 || n_nodes > HJB_DIST_MAX_NODES)
+        return rfail(nullptr, HJB_E_INVALID, "hjb_rollout_noise_table: n_nodes=%d not in 1..%d", n_nodes, HJB_DIST_MAX_NODES);
+    if (n_nodes > 1 && !thresholds) return rfail(nullptr, HJB_E_INVALID, "hjb_rollout_noise_table: null thresholds");
+    if (const int bad = check_weights(nullptr, "hjb_rollout_noise_table", n_nodes, weights)) return bad;
+    (void)noise_table(n_nodes, weights, thresholds);
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_traj, int32_t n_steps, int32_t n_nodes,
+                               const double *thresholds, int32_t *nodes) {
+    const char *const who = "hjb_rollout_noise_draw";
+    if (first_stream < 0) return rfail(nullptr, HJB_E_INVALID, "%s: first_stream=%lld < 0", who, (long long)first_stream);
+    if (n_traj < 0 || n_steps < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_traj=%lld, n_steps=%d (both >= 0)", who, (long long)n_traj, n_steps);
+    if (n_traj > 0 && first_stream > INT64_MAX - n_traj)
+        return rfail(nullptr, HJB_E_INVALID, "%s: first_stream + n_traj overflows (%lld + %lld)", who, (long long)first_stream, (long long)n_traj);
+    if (n_nodes < 1 || n_nodes > HJB_DIST_MAX_NODES) return rfail(nullptr, HJB_E_INVALID, "%s: n_nodes=%d not in 1..%d", who, n_nodes, HJB_DIST_MAX_NODES);
+    if (n_nodes > 1 && !thresholds) return rfail(nullptr, HJB_E_INVALID, "%s: null thresholds", who);
+    if (n_traj > 0 && n_steps > 0 && !nodes) return rfail(nullptr, HJB_E_INVALID, "%s: null nodes", who);
+    for (int w = 0; w + 1 < n_nodes; ++w)
+        if (!(thresholds[w] >= 0 && thresholds[w] <= 4294967296.0) || (w > 0 && thresholds[w] < thresholds[w - 1]))
+            return rfail(nullptr, HJB_E_INVALID, "%s: thresholds[%d] = %g is outside [0, 2^32] or below its predecessor", who, w, thresholds[w]);
+    // the kernel's own loop: a Philox call when (k & 3) == 0, one word per step
+    for (int64_t i = 0; i < n_traj; ++i) {
+        const uint64_t s = (uint64_t)first_stream + (uint64_t)i;
+        uint32_t rw[4] = {0u, 0u, 0u, 0u};
+        for (int k = 0; k < n_steps; ++k) {
+            if ((k & 3) == 0) noise_block(seed, s, (uint32_t)k >> 2, rw);
+            nodes[i + n_traj * k] = noise_node(thresholds, n_nodes - 1, noise_next_word(rw));
+        }
+    }
+    return HJB_OK;
 }
 
 int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,

@@ -229,6 +229,13 @@ SYMBOLS = {
                                     C.POINTER(C.c_double)]),
     "hjb_rollout_destroy": (C.c_int32, [C.c_void_p]),
     "hjb_rollout_last_error": (C.c_char_p, [C.c_void_p]),
+    # the affine loop under sampled process noise, and the sampler's host twins
+    "hjb_rollout_set_noise": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "hjb_rollout_run_noisy": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_double),
+                                          C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 6),
+    "hjb_rollout_noise_table": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "hjb_rollout_noise_draw": (C.c_int32, [C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_int32)]),
     "hjb_rollout_set_attitude_model": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_int32, C.POINTER(C.c_double),
                                                    C.POINTER(C.c_double)]),
     "hjb_rollout_run_attitude": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]

@@ -275,6 +275,39 @@ class Rollout:
                                              *map(_f64p, flat), C.byref(ms)))
         return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
 
+    def set_noise(self, offsets, weights=None):
+        """A node set for run_noisy (hjb_rollout_set_noise): offsets [D, W] (row a: the additive offsets of state axis a), weights
+        [W] non-negative with a positive sum, or None = equal - what Backup.set_disturbance takes, so one node set serves the
+        solve, the policy's price and the flight.  A property of the object, independent of the model; run and every other run_*
+        do not read it."""
+        off, w, _ = check_disturbance(self.D, offsets, weights, "expect")
+        offc = np.ascontiguousarray(off.reshape(-1, order="F"))
+        self._check(self.lib.hjb_rollout_set_noise(self._ro, off.shape[1], _f64p(offc), _f64p(w)))
+
+    def clear_noise(self):
+        """Detach the node set (hjb_rollout_set_noise with n_nodes = 0)."""
+        self._check(self.lib.hjb_rollout_set_noise(self._ro, 0, None, None))
+
+    def run_noisy(self, X0, plane_of_step, seed=0, first_stream=0, method="linear", keep_path=False):
+        """run under the node set of set_noise (hjb_rollout_run_noisy): after every step's affine update a node w is drawn and
+        offsets[:, w] added on the axes that have an offset.  Trajectory i of the call reads the Philox4x32-10 stream
+        first_stream + i under `seed` (both unsigned 64-bit; chunking does not change a bit).  Returns run's dict plus W_path
+        [n_traj, n_steps] int32, the drawn nodes (None unless keep_path)."""
+        D, nu = self.D, self.n_u
+        X = _starts(X0, D)
+        nt = X.shape[0]
+        ps = _int32_vector(plane_of_step, "plane_of_step")
+        K = int(ps.size)
+        Xf = np.empty((nt, D))
+        cost = np.empty(nt)
+        flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K), ("W_path", 1, K))
+        ms = C.c_double(0.0)
+        self._check(self.lib.hjb_rollout_run_noisy(self._ro, _LOOKUP[method], K, _i32p(ps), nt, _f64p(X), int(seed) & (2 ** 64 - 1),
+                                                   int(first_stream), _f64p(Xf), _f64p(cost), *map(_f64p, flat), C.byref(ms)))
+        if paths["W_path"] is not None:
+            paths["W_path"] = paths["W_path"][:, 0, :].astype(np.int32)
+        return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
+
     def set_attitude_model(self, inertia, h, integrator="taylor", q=None, r=None):
         """The 6-D attitude loop instead of the affine one (hjb_rollout_set_attitude_model; the last model set wins):
         inertia = (J1, J2, J3), step h, integrator 'taylor' or 'RK4', stage-cost weights q [7] and r [3] (None: zeros).
@@ -408,6 +441,30 @@ class Rollout:
         self._check(self.lib.hjb_rollout_run_attitude_simplified(self._ro, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
                                                                  *map(_f64p, flat)))
         return {"X_final": Xf.T, "cost": cost, **paths}
+
+
+def noise_thresholds(weights, n_nodes=None):
+    """The sampler's W - 1 thresholds of a weight vector (hjb_rollout_noise_table; no device): weights [W], or None with
+    n_nodes = W for equal weights.  Node w is drawn when T[w-1] <= word < T[w] (T[-1] = 0, T[W-1] = 2^32)."""
+    lib = load_library()
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+    W = int(n_nodes) if n_nodes is not None else (0 if w is None else w.size)
+    if w is not None and w.size != W:
+        raise ValueError("weights: %d values for n_nodes = %d" % (w.size, W))
+    T = np.empty(max(W - 1, 0))
+    _check(lib, None, lib.hjb_rollout_noise_table(W, _f64p(w), _f64p(T)))
+    return T
+
+
+def noise_draw(thresholds, n_traj, n_steps, seed=0, first_stream=0):
+    """The nodes run_noisy draws (hjb_rollout_noise_draw; no device): [n_traj, n_steps] int32, row i from the stream
+    first_stream + i under `seed`, for the node set whose thresholds (noise_thresholds) are given (W = len + 1)."""
+    lib = load_library()
+    T = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    nodes = np.empty((int(n_steps), int(n_traj)), dtype=np.int32)
+    _check(lib, None, lib.hjb_rollout_noise_draw(int(seed) & (2 ** 64 - 1), int(first_stream), int(n_traj), int(n_steps), T.size + 1,
+                                                 _f64p(T), _i32p(nodes)))
+    return np.ascontiguousarray(nodes.T)
 
 
 def attitude_linear_response(inertia, h, K, C_gain, X0, n_steps, qc=None, u_limit=None, integrator="RK4", cost_form="quat",

@@ -197,6 +197,44 @@ class Dynamic_Solver:
         self.paths_cost = out["cost"]
         return X, U
 
+    def get_noisy_paths(self, X0s, n_samples, seed=0, mode="Nssu", ssu_num=1, method="linear"):
+        """The stored policy flown under sampled process noise, on the GPU (hjbdp.Rollout.run_noisy): every start of X0s [S, n]
+        n_samples times under self.disturbance's nodes - x+ = A x + B u + d_w, node w drawn per step with the set's weights; a
+        'worst' set (no weights) is sampled uniformly.  Sample j of start i runs on stream i * n_samples + j of `seed`.
+        Returns the closed-loop costs [n, n_samples] (sum_k x'Qx + R u^2 over the N-1 steps, of the states actually visited) and
+        leaves their mean, standard deviation and maximum per start in self.noisy_cost_mean / _std / _max [n].  Beside
+        policy_cost() on the same disturbance this is "promised against paid" in two calls."""
+        from .core import Rollout
+        if self.u_star_idxs is None:
+            raise RuntimeError("run() first")
+        if self.disturbance is None:
+            raise RuntimeError("get_noisy_paths needs self.disturbance = (offsets [2, W], weights or None, mode)")
+        offsets, weights = self.disturbance[0], self.disturbance[1]
+        n_st = self.N - 1
+        if mode == "ssu":
+            if not 1 <= int(ssu_num) <= n_st:
+                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
+            planes = np.full(n_st, int(ssu_num) - 1, dtype=np.int32)
+        elif mode == "Nssu":
+            planes = np.arange(n_st, dtype=np.int32)
+        else:
+            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError("n_samples must be at least 1")
+        X0s = np.asarray(X0s, dtype=np.float64).reshape(self.S, -1)
+        n = X0s.shape[1]
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
+        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
+            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+            ro.set_noise(offsets, weights)
+            out = ro.run_noisy(np.repeat(X0s, n_samples, axis=1), planes, seed=seed, first_stream=0, method=method)
+        cost = out["cost"].reshape(n, n_samples)
+        self.noisy_cost_mean, self.noisy_cost_std, self.noisy_cost_max = cost.mean(axis=1), cost.std(axis=1), cost.max(axis=1)
+        self.noisy_paths_ms = out["device_ms"]
+        return cost
+
     @staticmethod
     def compare_data(obj1, obj2):
         # Dynamic_Solver.m:266-280

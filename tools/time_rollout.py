@@ -17,8 +17,10 @@ Two cases, one JSON line:
       case_attitude_linear_loop; alone, it also writes its line to profiles/rollout_attitude_linear_time.json.
   (h) pos_att_faults: the pos-att fault campaign (K23, hjb_rollout_run_pos_att_faults) beside K18 in one process, see
       case_pos_att_faults; alone, it also writes its line to profiles/rollout_pos_att_faults_time.json.
+  (i) kirk_noisy: the noisy rollout (K25, hjb_rollout_run_noisy) beside K16 on the same object and starts, see case_kirk_noisy;
+      alone, it also writes its line to profiles/rollout_noisy_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy] [--out FILE]
 """
 from __future__ import annotations
 
@@ -413,6 +415,103 @@ def case_pos_att_faults(host=True, n_traj=1 << 18, n_stages=None):
     return res
 
 
+def step_loop_vector_instructions(kernels):
+    """{name: vector instructions in the step loop} for the kernels whose mangled names are given, counted from the built library's
+    disassembly (llvm-objdump --offloading, then -d on the gfx950 code objects).  The step loop is the kernel's outermost loop:
+    the backward branch with the longest span; every instruction between its target and itself counts once (an inner loop's body
+    once: a static count) when it issues to a vector pipeline (v_*, ds_*, global_*, flat_*, buffer_*)."""
+    import re
+    import shutil
+    import subprocess
+    import tempfile
+    from hjbdp.core import LIB_PATH
+    tools = "/opt/rocm/lib/llvm/bin"
+    objdump = shutil.which("llvm-objdump", path=tools) or shutil.which("llvm-objdump")
+    if not objdump:
+        raise RuntimeError("llvm-objdump of the ROCm toolchain not found")
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        lib = Path(tmp) / "libhjbdp.so"
+        shutil.copy(LIB_PATH, lib)
+        subprocess.run([objdump, "--offloading", lib.name], cwd=tmp, check=True, capture_output=True)
+        for co in sorted(Path(tmp).glob("libhjbdp.so.*gfx950*")):
+            text = subprocess.run([objdump, "-d", co.name], cwd=tmp, check=True, capture_output=True, text=True).stdout
+            for name in kernels:
+                m = re.search(r"^([0-9a-f]+) <%s>:\n((?:\t.*\n)+)" % re.escape(name), text, flags=re.M)
+                if not m:
+                    continue
+                start = int(m.group(1), 16)
+                ins = []                                          # (offset, mnemonic, branch target offset or None)
+                for ln in m.group(2).splitlines():
+                    mm = re.match(r"\t(\S+).*// ([0-9A-F]+):[^<]*(?:<\S+?\+0x([0-9a-f]+)>)?", ln)
+                    if mm:
+                        ins.append((int(mm.group(2), 16) - start, mm.group(1), int(mm.group(3), 16) if mm.group(3) and mm.group(1).startswith(("s_branch", "s_cbranch")) else None))
+                back = [(o - t, t, o) for o, _, t in ins if t is not None and t < o]
+                if not back:
+                    raise RuntimeError("no loop found in %s" % name)
+                _, lo, hi = max(back)
+                out[name] = sum(1 for o, mn, _ in ins if lo <= o <= hi and mn.startswith(("v_", "ds_", "global_", "flat_", "buffer_")))
+    missing = [k for k in kernels if k not in out]
+    if missing:
+        raise RuntimeError("kernels not found in the built library: %s" % missing)
+    return out
+
+
+def case_kirk_noisy(host=True, n_traj=1000000):
+    """(i) kirk_noisy: case_kirk's problem and starts (10^6 trajectories x 129 steps, 'linear') under a 9-node Gauss-Hermite set on
+    both axes (sigma = 0.02, 0.05), K25 beside K16 on the same object and starts in one process: the two runs alternate, five
+    rounds after a warm-up round of the same shapes, device_ms (the launches' event times) of all five listed, the medians and
+    their ratio quoted; a third run in the same rounds, K25 with one node of zero offsets, prices the stream alone (no search, no
+    offsets; K16's results).  Beside the measured ratio the static one: the vector instructions in the step loops of the two D = 2
+    'linear' LDS kernels (int32 labels), counted from the built library's disassembly (step_loop_vector_instructions).  `pass`:
+    measured ratio <= static ratio x 1.15 - the 15 % covers the +-3 % spread between machines and the dependent LDS reads of the
+    node search, which a static count does not price.  `host` is not used."""
+    import hjbdp
+    ds = hjbdp.Dynamic_Solver(precision="double")
+    ds.N, ds.dx, ds.du = 130, 35, 100
+    ds.run()
+    s_r = np.asarray(ds.s_r, dtype=np.float64)
+    rng = np.random.default_rng(1)
+    X0 = rng.uniform(s_r[0], s_r[-1], size=(2, n_traj))
+    planes = np.arange(ds.N - 1)
+    off, w = hjbdp.gaussian_nodes([0.02, 0.05], order=3)
+    res = {"grid": "35x35", "planes": int(ds.N - 1), "method": "linear", "labels": "int32", "n_traj": int(n_traj), "n_steps": int(ds.N - 1),
+           "nodes": int(off.shape[1]), "noise": "gaussian_nodes(sigma = (0.02, 0.05), order 3) on both axes",
+           "timing": "device_ms: event times around the launches; the two runs alternate in one process, 5 rounds after a warm-up round"}
+    ms = {"k16": [], "k25": [], "k25_one_zero_node": []}
+    with hjbdp.Rollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro, \
+            hjbdp.Rollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro1:
+        ro.set_model(ds.A, ds.B, q=np.diag(ds.Q), r=[ds.R])
+        ro.set_noise(off, w)
+        ro1.set_model(ds.A, ds.B, q=np.diag(ds.Q), r=[ds.R])
+        ro1.set_noise(np.zeros((2, 1)))                           # the stream without the search and the offsets: K16's bits
+        for rnd in range(6):
+            a = ro.run(X0, planes, "linear")
+            b = ro.run_noisy(X0, planes, seed=1, method="linear")
+            z = ro1.run_noisy(X0, planes, seed=1, method="linear")
+            if rnd:                                               # round 0 is the warm-up
+                ms["k16"].append(a["device_ms"])
+                ms["k25"].append(b["device_ms"])
+                ms["k25_one_zero_node"].append(z["device_ms"])
+        ok = np.isfinite(a["cost"]) & np.isfinite(b["cost"])      # starts far from the origin leave the grid on Kirk's unstable loop
+        res["finite_in_both"] = int(ok.sum())
+        res["nominal_cost_mean"], res["noisy_cost_mean"] = float(np.mean(a["cost"][ok])), float(np.mean(b["cost"][ok]))
+        res["one_zero_node_equals_k16"] = bool(np.array_equal(a["X_final"], z["X_final"], equal_nan=True))
+    for key in ms:
+        med = float(np.median(ms[key]))
+        res[key] = {"device_ms": [round(t, 3) for t in ms[key]], "device_ms_median": round(med, 3),
+                    "traj_steps_per_s": n_traj * (ds.N - 1) / (med * 1e-3)}
+    res["k25_over_k16_measured"] = res["k25"]["device_ms_median"] / res["k16"]["device_ms_median"]
+    names = {"k16": "_ZN3hjb9k_rolloutILi2EiLi1ELb1EEEvNS_8DRolloutElPKdPdS4_S4_S4_",
+             "k25": "_ZN3hjb15k_rollout_noisyILi2EiLi1ELb1EEEvNS_8DRolloutENS_6DNoiseElPKdPdS5_S5_S5_"}
+    counts = step_loop_vector_instructions(list(names.values()))
+    res["step_loop_vector_instructions"] = {k: counts[v] for k, v in names.items()}
+    res["k25_over_k16_static"] = counts[names["k25"]] / counts[names["k16"]]
+    res["bound"] = res["k25_over_k16_static"] * 1.15
+    res["pass"] = bool(res["k25_over_k16_measured"] <= res["bound"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -426,7 +525,8 @@ def main():
     for c in a.cases.split(","):
         res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude, "pos_att_loop": case_pos_att_loop,
                   "position_loop": case_position_loop, "attitude_simplified_loop": case_attitude_simplified_loop,
-                  "attitude_linear_loop": case_attitude_linear_loop, "pos_att_faults": case_pos_att_faults}[c](host=not a.no_host)
+                  "attitude_linear_loop": case_attitude_linear_loop, "pos_att_faults": case_pos_att_faults,
+                  "kirk_noisy": case_kirk_noisy}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.cases == "position_loop" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
@@ -436,6 +536,8 @@ def main():
         (ROOT / "profiles" / "rollout_attitude_linear_time.json").write_text(json.dumps(res) + "\n")
     if a.cases == "pos_att_faults" and not a.out:                 # its own record: one line
         (ROOT / "profiles" / "rollout_pos_att_faults_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "kirk_noisy" and not a.out:                     # its own record: one line
+        (ROOT / "profiles" / "rollout_noisy_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
