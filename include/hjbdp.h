@@ -485,6 +485,48 @@ int32_t hjb_rollout_noise_table(int32_t n_nodes, const double *weights, double *
 int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_traj, int32_t n_steps, int32_t n_nodes,
                                const double *thresholds, int32_t *nodes);
 
+/* ---- greedy rollouts: the affine loop flown by one-step lookahead on a stored cost-to-go (kernel K26) ---------------------------
+ *   u_k(x) = argmin_l  g(x, u_l) + J_{k+1}(A x + B u_l + c)   over the rows u_l of the object's u_table, at the state visited
+ * - the textbook DP controller: the other half of what hjb_solve(keep_J) returns.  It reads no label (the object's labels are not
+ * touched) and does not interpolate between the labels of different controls.
+ * hjb_rollout_set_values gives the object value planes: values [nS, n_planes] column-major in HJB_F32 or HJB_F64, hjb_solve's
+ * J_stages layout, widened to double exactly on read (n_planes == 0 detaches).  The values are a property of the object, like the
+ * noise; ONLY hjb_rollout_run_greedy reads them: every other run function of an object that holds values gives the bits it gave
+ * before.  hjb_rollout_run_greedy steps n_traj trajectories n_steps times under the affine model of hjb_rollout_set_model, one
+ * GPU thread each, all in double, every product rounded.  Step k at the state x:
+ *   1. p = value_plane_of_step[k]: a plane of values, or -1 for the zero function (a terminal cost of zeros: v = +0.0 for every
+ *      candidate and nothing is read);
+ *   2. the state parts, once:  gs = (q0*(x0*x0) + q1*(x1*x1)) + ...;  as_a = (A[a,0]*x0 + A[a,1]*x1) + ...;
+ *   3. for label l = 0 .. n_labels-1 in this order, u_j = u_table[l, j]:
+ *        g_l  = gs + r0*(u0*u0) + ...;   xn_a = as_a + B[a,0]*u0 + ... (+ c_a if given)        (hjb_rollout_run's g and x+)
+ *        v_l  = the N-linear blend of plane p at xn: the cell by exact search, clamped to [0, n-2] (outside the grid the blend
+ *               extrapolates linearly; NaN: cell 0), t_a = (xn_a - k[cell]) * rdx[cell], fma lerps axis 0 first, pairwise:
+ *               bit-identical to hjb_policy_lookup(..., HJB_LOOKUP_LINEAR) in double on that plane;
+ *        cand_l = g_l + v_l;
+ *   4. best = cand_0; label l >= 1 replaces iff cand_l < best: the first minimum wins, a NaN candidate never replaces;
+ *   5. the chosen label applied: cost += g_best, x = xn_best - the bits step 3 formed.
+ * X0, X_final, cost, X_path, U_path: hjb_rollout_run's.  L_path [n_traj, n_steps]: the chosen label + index_base, as a double;
+ * V_path [n_traj, n_steps]: best, the cost-to-go the controller believed (NULL: not kept).  Options "chunk" (no bit changes with
+ * it) and "lds" (knots, 1/dx and u_table staged when they fit 32 KiB; the value planes stay in global memory) as in
+ * hjb_rollout_run.  hjb_rollout_greedy_host runs the same functions (csrc/hjbdp_greedy.h) on the CPU, with no device and no
+ * object: the grid and table as hjb_rollout_create takes them, the model as hjb_rollout_set_model, the values as
+ * hjb_rollout_set_values; its L_path holds the 0-based label.
+ * Refused before any device work, outputs untouched (text: hjb_rollout_last_error) - HJB_E_INVALID: a null handle; a dtype other
+ * than the two (HJB_F16S included: convert on the host); n_planes < 0; null values with n_planes > 0; hjb_rollout_run_greedy with
+ * no affine model, with another model set, or with no values unless every plane index is -1; a plane index outside
+ * -1 .. n_planes-1; and everything hjb_rollout_run refuses of n_steps, n_traj, X0 and X_final.
+ * Out of scope: lookahead under a disturbance (hjb_set_disturbance's E_w / max_w inside the candidate), flying greedy under
+ * hjb_rollout_set_noise's sampled noise, the integrated plants of the other models, float16 value planes. */
+int32_t hjb_rollout_set_values(void *rollout, int32_t dtype, int32_t n_planes, const void *values);
+int32_t hjb_rollout_run_greedy(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj,
+                               const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
+                               double *L_path, double *V_path, double *device_ms);
+int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u,
+                                const double *u_table, const double *A, const double *B, const double *c, const double *q,
+                                const double *r, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
+                                const int32_t *value_plane_of_step, int64_t n_traj, const double *X0, double *X_final,
+                                double *cost, double *X_path, double *U_path, double *L_path, double *V_path);
+
 /* The 6-D attitude closed loop (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run) on the same object.
  * hjb_rollout_set_attitude_model and hjb_rollout_set_model replace each other: the last one set wins.  It needs D == 6, n_u == 3
  * and the grid axes in the reference's order (w1, w2, w3, yaw, pitch, roll); inertia = [J1 J2 J3] and h finite and > 0,

@@ -115,6 +115,19 @@ int32_t hjb_rollout_run_noisy(void *rollout, int32_t method, int32_t n_steps, co
 int32_t hjb_rollout_noise_table(int32_t n_nodes, const double *weights, double *thresholds);
 int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_traj, int32_t n_steps, int32_t n_nodes,
                                const double *thresholds, int32_t *nodes);
+/* the affine loop flown by one-step lookahead on stored value planes (kernel K26): values [nS, n_planes] column-major, dtype 0 =
+ * single, 1 = double (n_planes 0 detaches); value_plane_of_step -1 = the zero terminal; L_path the chosen label + index_base,
+ * V_path the minimum, per step; the host twin needs no device and no object (hjbdp.h); usage:
+ * matlab/Dynamic_Solver_hjbdp_get_greedy_paths.m */
+int32_t hjb_rollout_set_values(void *rollout, int32_t dtype, int32_t n_planes, const void *values);
+int32_t hjb_rollout_run_greedy(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj,
+                               const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
+                               double *L_path, double *V_path, double *device_ms);
+int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u,
+                                const double *u_table, const double *A, const double *B, const double *c, const double *q,
+                                const double *r, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
+                                const int32_t *value_plane_of_step, int64_t n_traj, const double *X0, double *X_final,
+                                double *cost, double *X_path, double *U_path, double *L_path, double *V_path);
 /* the 6-D attitude loop on the same object (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run);
  * usage: matlab/Solver_attitude_hjbdp_get_optimal_paths.m */
 int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, double h, int32_t integrator, const double *q,

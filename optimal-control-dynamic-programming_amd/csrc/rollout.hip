@@ -9,6 +9,9 @@
 // Beside the model an object may hold a noise node set (hjb_rollout_set_noise): hjb_rollout_run_noisy (K25,
 // kernels_rollout_noisy.h / rollout_noisy.hip) flies the affine loop under it, and no other run function reads it.  The sampler's
 // host twins hjb_rollout_noise_table / hjb_rollout_noise_draw (hjbdp_noise.h) need no device.
+// And it may hold value planes (hjb_rollout_set_values): hjb_rollout_run_greedy (K26, kernels_rollout_greedy.h /
+// rollout_greedy.hip) flies the affine loop by one-step lookahead on them, and no other run function reads them.  Its host twin
+// hjb_rollout_greedy_host (hjbdp_greedy.h) needs no device and no object.
 // Shared here: the attached-channels record and attach_channels (the three attaching setters), check_run / check_traj /
 // check_quaternions (the run functions' refusals, all before any device work), lds_bytes, run_chunks (the chunk loop).
 #include "hjbdp_host.h"
@@ -20,6 +23,7 @@
 #include "kernels_rollout_attitude_simplified.h"
 #include "kernels_rollout_attitude_linear.h"
 #include "kernels_rollout_noisy.h"
+#include "kernels_rollout_greedy.h"
 #include "rollout_dispatch.h"
 #include <memory>
 
@@ -92,6 +96,10 @@ struct Rollout {
     // the noise node set (hjb_rollout_set_noise): N.n_nodes > 0 while one is set; read by hjb_rollout_run_noisy alone
     DNoise N{};
     std::shared_ptr<DevData> noise;     // N.tab: thresholds, then the masked axes' offsets
+    // the value planes (hjb_rollout_set_values): val_planes > 0 while some are set; read by hjb_rollout_run_greedy alone
+    std::shared_ptr<DevData> values;
+    const void *dvalues = nullptr;      // [nS, val_planes] column-major, float or double
+    int val_planes = 0, val_bytes = 8;
     hipStream_t stream = nullptr;
     std::string err;
 };
@@ -113,6 +121,7 @@ int rfail(Rollout *ro, int code, const char *fmt, ...) {
 void release(Rollout *ro) {
     ro->att.reset();
     ro->noise.reset();
+    ro->values.reset();
     ro->data.reset();
     if (ro->stream) (void)hipStreamDestroy(ro->stream);
     ro->stream = nullptr;
@@ -930,6 +939,167 @@ int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_tr
             nodes[i + n_traj * k] = noise_node(thresholds, n_nodes - 1, noise_next_word(rw));
         }
     }
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_set_values(void *rollout, int32_t dtype, int32_t n_planes, const void *values) {
+    Rollout *ro = (Rollout *)rollout;
+    const char *const who = "hjb_rollout_set_values";
+    // the arguments that need no object first, then the object; every refusal before any device work
+    if (dtype != HJB_F32 && dtype != HJB_F64)
+        return rfail(ro, HJB_E_INVALID, "%s: dtype %d is not HJB_F32 / HJB_F64 (convert float16 planes on the host)", who, dtype);
+    if (n_planes < 0) return rfail(ro, HJB_E_INVALID, "%s: n_planes=%d < 0", who, n_planes);
+    if (n_planes > 0 && !values) return rfail(ro, HJB_E_INVALID, "%s: null values with n_planes=%d", who, n_planes);
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "%s: null handle", who);
+    std::lock_guard<std::mutex> g(ro->mu);
+    const int64_t nS = ro->R.nS;
+    if ((int64_t)n_planes > kMaxStates / nS)
+        return rfail(ro, HJB_E_INVALID, "%s: size overflow (%lld states x %d planes)", who, (long long)nS, n_planes);
+    const int vb = dtype == HJB_F32 ? 4 : 8;
+    const size_t bytes = (size_t)nS * (size_t)n_planes * vb;
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
+    std::shared_ptr<DevData> vd;
+    void *d = nullptr;
+    if (n_planes > 0) {
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipMemGetInfo failed");
+        if (bytes + ((size_t)64 << 20) > fr)
+            return rfail(ro, HJB_E_NOMEM, "%s: %zu bytes of value planes, %zu free on device %d", who, bytes, fr, ro->device);
+        vd = std::make_shared<DevData>();
+        vd->device = ro->device;
+        if (hipMalloc(&d, std::max<size_t>(bytes, 16)) != hipSuccess) return rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", bytes);
+        vd->allocs.push_back(d);
+        if (hipMemcpy(d, values, bytes, hipMemcpyHostToDevice) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "rollout: upload failed");
+    }
+    if (ro->stream) (void)hipStreamSynchronize(ro->stream);
+    ro->values = std::move(vd);                               // replaces (and releases) planes given earlier
+    ro->dvalues = d;
+    ro->val_planes = n_planes;
+    ro->val_bytes = vb;
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_run_greedy(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj, const double *X0,
+                               double *X_final, double *cost, double *X_path, double *U_path, double *L_path, double *V_path,
+                               double *device_ms) {
+    Rollout *ro = (Rollout *)rollout;
+    const char *const who = "hjb_rollout_run_greedy";
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    // every refusal before any device work, the outputs untouched
+    if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
+    if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
+    if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_model", who);
+    if (ro->model != kModelAffine)
+        return rfail(ro, HJB_E_INVALID, "rollout: %s needs the affine model (hjb_rollout_set_model); the object holds another", who);
+    if (n_steps > 0 && !value_plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null value_plane_of_step");
+    for (int k = 0; k < n_steps; ++k) {
+        const int32_t p = value_plane_of_step[k];
+        if (p >= 0 && ro->val_planes < 1)
+            return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_values (value_plane_of_step[%d] = %d; only -1 needs no values)",
+                         who, k, p);
+        if (p < -1 || p >= ro->val_planes)
+            return rfail(ro, HJB_E_INVALID, "rollout: value_plane_of_step[%d] = %d outside [-1, %d)", k, p, ro->val_planes);
+    }
+    if (n_traj == 0) {
+        if (device_ms) *device_ms = 0.0;
+        return HJB_OK;
+    }
+    const int D = ro->D;
+    const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
+    if (bad_traj) return bad_traj;
+    if (device_ms) *device_ms = 0.0;
+    // the two per-step scalars share run_chunks' extra path rows: [L | V], each [n_traj, n_steps]; one of them asked for goes
+    // straight to its buffer, both go through one host block
+    const int n_e = (L_path ? 1 : 0) + (V_path ? 1 : 0);
+    const size_t per = (size_t)n_traj * (size_t)n_steps;
+    std::vector<double> both;
+    double *E_path = L_path ? L_path : V_path;
+    if (n_e == 2) {
+        both.resize(2 * per);
+        E_path = both.data();
+    }
+    const int val_bytes = ro->val_bytes;
+    const void *dvalues = ro->dvalues;
+    const int st = run_chunks(ro, who, D, ro->R.n_u, n_e, n_steps, value_plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, E_path,
+                              nullptr, device_ms,
+                              [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t s, double *dX0, double *dXf, double *dC,
+                                  double *dXp, double *dUp, double *dEp, int32_t *) {
+                                  DGreedy G{};
+                                  G.R = R;
+                                  G.values = dvalues;
+                                  G.nc = nc;
+                                  G.X0 = dX0;
+                                  G.Xf = dXf;
+                                  G.cost = dC;
+                                  G.Xp = dXp;
+                                  G.Up = dUp;
+                                  G.Lp = L_path ? dEp : nullptr;
+                                  G.Vp = V_path ? dEp + (L_path ? (size_t)nc * n_steps : 0) : nullptr;
+                                  return launch_rollout_greedy(val_bytes, lds_on, D, G, lds, s);
+                              });
+    if (st == HJB_OK && n_e == 2) {
+        std::memcpy(L_path, both.data(), per * sizeof(double));
+        std::memcpy(V_path, both.data() + per, per * sizeof(double));
+    }
+    return st;
+}
+
+int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
+                                const double *A, const double *B, const double *c, const double *q, const double *r, int32_t dtype,
+                                int32_t n_value_planes, const void *values, int32_t n_steps, const int32_t *value_plane_of_step,
+                                int64_t n_traj, const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
+                                double *L_path, double *V_path) {
+    const char *const who = "hjb_rollout_greedy_host";
+    if (D < 1 || D > HJB_MAX_D) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, HJB_MAX_D);
+    if (n_u < 1 || n_u > HJB_ROLLOUT_MAX_U) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: n_u=%d not in 1..%d", who, n_u, HJB_ROLLOUT_MAX_U);
+    if (!n || !knots || !u_table || !A || !B) return rfail(nullptr, HJB_E_INVALID, "%s: null argument (n, knots, u_table, A and B are required)", who);
+    if (n_labels < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_labels=%d < 1", who, n_labels);
+    if (dtype != HJB_F32 && dtype != HJB_F64) return rfail(nullptr, HJB_E_INVALID, "%s: dtype %d is not HJB_F32 / HJB_F64", who, dtype);
+    if (n_value_planes < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_value_planes=%d < 0", who, n_value_planes);
+    if (n_value_planes > 0 && !values) return rfail(nullptr, HJB_E_INVALID, "%s: null values with n_value_planes=%d", who, n_value_planes);
+    if (n_steps < 0 || n_traj < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_steps=%d, n_traj=%lld (both >= 0)", who, n_steps, (long long)n_traj);
+    int64_t nS = 1, n_knots = 0;
+    for (int a = 0; a < D; ++a) {
+        if (n[a] < 2) return rfail(nullptr, HJB_E_INVALID, "%s: axis %d has %d knots (need >= 2)", who, a, n[a]);
+        const double *kk = knots + n_knots;
+        for (int i = 0; i < n[a]; ++i)
+            if (!std::isfinite(kk[i])) return rfail(nullptr, HJB_E_INVALID, "%s: knot %d of axis %d is not finite", who, i, a);
+        for (int i = 0; i + 1 < n[a]; ++i)
+            if (!(kk[i + 1] > kk[i])) return rfail(nullptr, HJB_E_INVALID, "%s: knots of axis %d not strictly increasing (at %d)", who, a, i);
+        n_knots += n[a];
+        if (n_knots > INT32_MAX || nS > kMaxStates / n[a]) return rfail(nullptr, HJB_E_INVALID, "%s: size overflow (grid)", who);
+        nS *= n[a];
+    }
+    if (!all_finite(u_table, (int64_t)n_labels * n_u)) return rfail(nullptr, HJB_E_INVALID, "%s: u_table is not finite", who);
+    if (!all_finite(A, (int64_t)D * D) || !all_finite(B, (int64_t)D * n_u) || !all_finite(c, D) || !all_finite(q, D) || !all_finite(r, n_u))
+        return rfail(nullptr, HJB_E_INVALID, "%s: the model (A, B, c, q, r) is not finite", who);
+    if (n_steps > 0 && !value_plane_of_step) return rfail(nullptr, HJB_E_INVALID, "%s: null value_plane_of_step", who);
+    for (int k = 0; k < n_steps; ++k)
+        if (value_plane_of_step[k] < -1 || value_plane_of_step[k] >= n_value_planes)
+            return rfail(nullptr, HJB_E_INVALID, "%s: value_plane_of_step[%d] = %d outside [-1, %d)", who, k, value_plane_of_step[k], n_value_planes);
+    if (n_traj == 0) return HJB_OK;
+    const int bad_traj = check_traj(nullptr, who, D, "D", n_steps, n_traj, X0, X_final);
+    if (bad_traj) return bad_traj;
+    GreedyModel M{};
+    std::vector<double> rdx((size_t)n_knots);
+    greedy_grid(D, n, knots, M, rdx.data());
+    M.n_u = n_u;
+    M.n_labels = n_labels;
+    M.has_c = c ? 1 : 0;
+    std::memcpy(M.A, A, sizeof(double) * D * D);
+    std::memcpy(M.B, B, sizeof(double) * D * n_u);
+    if (c) std::memcpy(M.c, c, sizeof(double) * D);
+    if (q) std::memcpy(M.q, q, sizeof(double) * D);
+    if (r) std::memcpy(M.r, r, sizeof(double) * n_u);
+    with_bool(dtype == HJB_F32, [&](auto f) {
+        with_dim(D, [&](auto d) {
+            using TV = std::conditional_t<decltype(f)::value, float, double>;
+            greedy_rollout_host<decltype(d)::value, TV>(M, knots, rdx.data(), u_table, static_cast<const TV *>(values), n_steps,
+                                                        value_plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, L_path, V_path);
+        });
+    });
     return HJB_OK;
 }
 

@@ -236,6 +236,12 @@ SYMBOLS = {
     "hjb_rollout_noise_table": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "hjb_rollout_noise_draw": (C.c_int32, [C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                            C.POINTER(C.c_int32)]),
+    # the affine loop flown by one-step lookahead on stored value planes, and its host twin
+    "hjb_rollout_set_values": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "hjb_rollout_run_greedy": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64] + [C.POINTER(C.c_double)] * 8),
+    "hjb_rollout_greedy_host": (C.c_int32, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32]
+                                + [C.POINTER(C.c_double)] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
+                                                                  C.c_int64] + [C.POINTER(C.c_double)] * 7),
     "hjb_rollout_set_attitude_model": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_int32, C.POINTER(C.c_double),
                                                    C.POINTER(C.c_double)]),
     "hjb_rollout_run_attitude": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]

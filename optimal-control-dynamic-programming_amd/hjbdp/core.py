@@ -151,6 +151,18 @@ def _path_buffers(nt, keep_path, *specs):
     return flat, {name: None if a is None else a.reshape((nt, rows, cols), order="F") for (name, rows, cols), a in zip(specs, flat)}
 
 
+def _value_planes(J, nS):
+    """Value planes as the library reads them: (flat float32 or float64 vector in Fortran order, its HJB_F32 / HJB_F64).  Any
+    other floating type is refused (float16: convert first), as is a size that is not a whole number of nS-state planes."""
+    v = np.asarray(J)
+    if v.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("value planes must be float32 or float64, got %s" % v.dtype)
+    v = np.ascontiguousarray(v.reshape(-1, order="F"))
+    if nS < 1 or v.size == 0 or v.size % nS:
+        raise ValueError("values: %d elements are not a whole number of %d-state planes" % (v.size, nS))
+    return v, (_abi.HJB_F32 if v.dtype == np.float32 else _abi.HJB_F64)
+
+
 _LOOKUP = {"nearest": _abi.HJB_LOOKUP_NEAREST, "linear": _abi.HJB_LOOKUP_LINEAR}
 _ATT_INTEGRATOR = {"taylor": _abi.HJB_ATT_TAYLOR, "RK4": _abi.HJB_ATT_RK4, "rk4": _abi.HJB_ATT_RK4}
 
@@ -306,6 +318,42 @@ class Rollout:
                                                    int(first_stream), _f64p(Xf), _f64p(cost), *map(_f64p, flat), C.byref(ms)))
         if paths["W_path"] is not None:
             paths["W_path"] = paths["W_path"][:, 0, :].astype(np.int32)
+        return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
+
+    def set_values(self, J):
+        """Value planes for run_greedy (hjb_rollout_set_values): J float32 or float64, [nS, n_planes] or grid-shaped with a
+        trailing plane axis, Fortran order (hjb_solve's J_stages; Dynamic_Solver's J_star).  A property of the object,
+        independent of the model and of the labels; run and every other run_* do not read it."""
+        nS = int(np.prod(self.n, dtype=np.int64))
+        v, dtype = _value_planes(J, nS)
+        self._check(self.lib.hjb_rollout_set_values(self._ro, dtype, v.size // nS, v.ctypes.data))
+        self.n_value_planes = v.size // nS
+
+    def clear_values(self):
+        """Detach the value planes (hjb_rollout_set_values with n_planes = 0)."""
+        self._check(self.lib.hjb_rollout_set_values(self._ro, _abi.HJB_F64, 0, None))
+        self.n_value_planes = 0
+
+    def run_greedy(self, X0, value_plane_of_step, keep_path=False):
+        """The affine model flown by one-step lookahead on the planes of set_values (hjb_rollout_run_greedy): at every step the
+        row of u_table that minimises g(x, u) + J(A x + B u + c), J the plane value_plane_of_step[k] blended N-linearly at the
+        next state (-1: the zero function), first minimum.  The labels of the object are not read.  Returns run's dict plus
+        L_path [n_traj, n_steps] int32, the chosen labels (index_base added), and V_path [n_traj, n_steps], the minima - the
+        cost-to-go the controller believed (both None unless keep_path)."""
+        D, nu = self.D, self.n_u
+        X = _starts(X0, D)
+        nt = X.shape[0]
+        ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
+        K = int(ps.size)
+        Xf = np.empty((nt, D))
+        cost = np.empty(nt)
+        flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K), ("L_path", 1, K), ("V_path", 1, K))
+        ms = C.c_double(0.0)
+        self._check(self.lib.hjb_rollout_run_greedy(self._ro, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost), *map(_f64p, flat),
+                                                    C.byref(ms)))
+        if keep_path:
+            paths["L_path"] = paths["L_path"][:, 0, :].astype(np.int32)
+            paths["V_path"] = paths["V_path"][:, 0, :]
         return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
 
     def set_attitude_model(self, inertia, h, integrator="taylor", q=None, r=None):
@@ -465,6 +513,39 @@ def noise_draw(thresholds, n_traj, n_steps, seed=0, first_stream=0):
     _check(lib, None, lib.hjb_rollout_noise_draw(int(seed) & (2 ** 64 - 1), int(first_stream), int(n_traj), int(n_steps), T.size + 1,
                                                  _f64p(T), _i32p(nodes)))
     return np.ascontiguousarray(nodes.T)
+
+
+def greedy_host(knots, u_table, A, B, J, X0, value_plane_of_step, c=None, q=None, r=None, index_base=0, keep_path=False):
+    """Rollout.run_greedy on the CPU (hjb_rollout_greedy_host; no device, no object): the functions the kernel calls, in a
+    plain loop over the trajectories.  knots, u_table: as Rollout takes them; A, B, c, q, r: as set_model; J: as set_values, or
+    None when every plane index is -1.  Returns run_greedy's dict without device_ms; L_path holds label + index_base."""
+    lib = load_library()
+    ks = [np.ascontiguousarray(k, dtype=np.float64).reshape(-1) for k in knots]
+    D = len(ks)
+    n = [len(k) for k in ks]
+    nS = int(np.prod(n, dtype=np.int64)) if ks else 1
+    ut = np.asarray(u_table, dtype=np.float64)
+    ut = ut.reshape(-1, 1) if ut.ndim == 1 else ut
+    n_labels, nu = ut.shape
+    ut = np.ascontiguousarray(ut.reshape(-1, order="F"))
+    kcat = np.ascontiguousarray(np.concatenate(ks) if ks else np.zeros(0))
+    v, dtype = (None, _abi.HJB_F64) if J is None else _value_planes(J, nS)
+    X = _starts(X0, D)
+    nt = X.shape[0]
+    ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
+    K = int(ps.size)
+    Xf = np.empty((nt, D))
+    cost = np.empty(nt)
+    flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K), ("L_path", 1, K), ("V_path", 1, K))
+    _check(lib, None, lib.hjb_rollout_greedy_host(D, (C.c_int32 * max(D, 1))(*n), _f64p(kcat), int(n_labels), int(nu), _f64p(ut),
+                                                  _f64p(_f64_colmajor(A, D, D)), _f64p(_f64_colmajor(B, D, nu)), _f64p(_f64_vec(c, D)),
+                                                  _f64p(_f64_vec(q, D)), _f64p(_f64_vec(r, nu)), dtype, 0 if v is None else v.size // nS,
+                                                  None if v is None else v.ctypes.data, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
+                                                  *map(_f64p, flat)))
+    if keep_path:
+        paths["L_path"] = paths["L_path"][:, 0, :].astype(np.int32) + np.int32(index_base)
+        paths["V_path"] = paths["V_path"][:, 0, :]
+    return {"X_final": Xf.T, "cost": cost, **paths}
 
 
 def attitude_linear_response(inertia, h, K, C_gain, X0, n_steps, qc=None, u_limit=None, integrator="RK4", cost_form="quat",

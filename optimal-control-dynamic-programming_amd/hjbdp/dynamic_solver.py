@@ -235,6 +235,42 @@ class Dynamic_Solver:
         self.noisy_paths_ms = out["device_ms"]
         return cost
 
+    def get_greedy_paths(self, X0s, mode="Nssu", ssu_num=1):
+        """The closed loop of the cost-to-go itself, on the GPU (hjbdp.Rollout.run_greedy): at every step the control of U_mesh
+        that minimises x'Qx + R u^2 + J_{k+1}(A x + B u), J_{k+1} the plane of J_star behind the step blended linearly at the
+        next state - one-step lookahead at the state actually visited, with no label table in between.  X0s [S, n].  Step k
+        (0-based) reads plane k + 1 of J_star, whose last plane is the zero terminal; mode 'ssu' freezes plane ssu_num
+        (1..N-1).  Returns X [S, N, n] and U [N, n] as get_optimal_paths does (U[N-1] = 0); leaves the closed-loop costs in
+        self.greedy_cost [n] - beside self.paths_cost what the stored labels lose to the value function they came from - and
+        the kernel's time in self.greedy_paths_ms.  The lookahead is NOMINAL even when self.disturbance is set: J_star then
+        is the disturbed handle's cost-to-go, but the candidate's next state carries no node."""
+        from .core import Rollout
+        if self.J_star is None or self.u_star_idxs is None:
+            raise RuntimeError("run() first")
+        N, S = self.N, self.S
+        n_st = N - 1
+        if mode == "ssu":
+            if not 1 <= int(ssu_num) <= n_st:
+                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
+            planes = np.full(n_st, int(ssu_num), dtype=np.int32)
+        elif mode == "Nssu":
+            planes = np.arange(1, N, dtype=np.int32)
+        else:
+            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        X0s = np.asarray(X0s, dtype=np.float64).reshape(S, -1)
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
+        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
+            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+            ro.set_values(self.J_star)
+            out = ro.run_greedy(X0s, planes, keep_path=True)
+        X = np.ascontiguousarray(out["X_path"].transpose(1, 2, 0))     # [n, S, N] -> [S, N, n]
+        U = np.zeros((N, X0s.shape[1]))
+        U[:n_st] = out["U_path"][:, 0, :].T
+        self.greedy_cost = out["cost"]
+        self.greedy_paths_ms = out["device_ms"]
+        return X, U
+
     @staticmethod
     def compare_data(obj1, obj2):
         # Dynamic_Solver.m:266-280

@@ -19,8 +19,10 @@ Two cases, one JSON line:
       case_pos_att_faults; alone, it also writes its line to profiles/rollout_pos_att_faults_time.json.
   (i) kirk_noisy: the noisy rollout (K25, hjb_rollout_run_noisy) beside K16 on the same object and starts, see case_kirk_noisy;
       alone, it also writes its line to profiles/rollout_noisy_time.json.
+  (j) greedy: the greedy rollout (K26, hjb_rollout_run_greedy) beside K16 'linear' on the same object and starts, see case_greedy;
+      alone, it also writes its line to profiles/rollout_greedy_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy] [--out FILE]
 """
 from __future__ import annotations
 
@@ -512,6 +514,54 @@ def case_kirk_noisy(host=True, n_traj=1000000):
     return res
 
 
+def case_greedy(host=True, n_traj=1000000):
+    """(j) greedy: case_kirk's problem and starts (10^6 trajectories x 129 steps, 100 controls), the stored labels' loop (K16,
+    'linear') beside the value function's own loop (K26: one-step lookahead on J_star, step k on plane k + 1, the last on the zero
+    terminal) on one object in one process: the two runs alternate, five rounds after a warm-up round of the same shapes,
+    device_ms (the launches' event times) of all five listed, the medians and their ratio quoted, and K26's time per (trajectory,
+    step, candidate).  Beside the times the number the feature exists for: the mean closed-loop cost of both controllers over
+    the starts whose cost is finite under both (Kirk's plant is unstable: starts far from the origin leave the grid).  No pass
+    condition: nothing comparable has been measured.  `host` is not used."""
+    import hjbdp
+    ds = hjbdp.Dynamic_Solver(precision="double")
+    ds.N, ds.dx, ds.du = 130, 35, 100
+    ds.run()
+    s_r = np.asarray(ds.s_r, dtype=np.float64)
+    rng = np.random.default_rng(1)
+    X0 = rng.uniform(s_r[0], s_r[-1], size=(2, n_traj))
+    K = ds.N - 1
+    planes = np.arange(K)
+    vplanes = np.arange(1, K + 1)                                 # J_star's last plane is the zero terminal
+    res = {"grid": "35x35", "planes": int(K), "labels": "int32", "values": str(ds.J_star.dtype), "n_traj": int(n_traj), "n_steps": int(K),
+           "n_candidates": int(ds.du), "k16_method": "linear",
+           "timing": "device_ms: event times around the launches; the two runs alternate in one process, 5 rounds after a warm-up round"}
+    ms = {"k16": [], "k26": []}
+    with hjbdp.Rollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro:
+        ro.set_model(ds.A, ds.B, q=np.diag(ds.Q), r=[ds.R])
+        ro.set_values(ds.J_star)
+        for rnd in range(6):
+            a = ro.run(X0, planes, "linear")
+            b = ro.run_greedy(X0, vplanes)
+            if rnd:                                               # round 0 is the warm-up
+                ms["k16"].append(a["device_ms"])
+                ms["k26"].append(b["device_ms"])
+        ok = np.isfinite(a["cost"]) & np.isfinite(b["cost"])
+        res["finite_in_both"] = int(ok.sum())
+        res["k16_cost_mean"], res["k26_cost_mean"] = float(np.mean(a["cost"][ok])), float(np.mean(b["cost"][ok]))
+        res["k26_cheaper_or_equal_share"] = float(np.mean(b["cost"][ok] <= a["cost"][ok]))
+        inside = ok & (np.abs(a["X_final"]).max(axis=0) < 1.0) & (np.abs(b["X_final"]).max(axis=0) < 1.0)
+        res["regulated_in_both"] = int(inside.sum())              # flights that end near the origin under both controllers
+        res["k16_cost_mean_regulated"], res["k26_cost_mean_regulated"] = float(np.mean(a["cost"][inside])), float(np.mean(b["cost"][inside]))
+    for key in ms:
+        med = float(np.median(ms[key]))
+        res[key] = {"device_ms": [round(t, 3) for t in ms[key]], "device_ms_median": round(med, 3),
+                    "traj_steps_per_s": n_traj * K / (med * 1e-3)}
+    res["k26_over_k16"] = res["k26"]["device_ms_median"] / res["k16"]["device_ms_median"]
+    res["k26_ns_per_traj_step_candidate"] = res["k26"]["device_ms_median"] * 1e6 / (n_traj * K * ds.du)
+    res["lds_plane_form"] = "not built: the value planes are read from global memory"
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -526,7 +576,7 @@ def main():
         res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude, "pos_att_loop": case_pos_att_loop,
                   "position_loop": case_position_loop, "attitude_simplified_loop": case_attitude_simplified_loop,
                   "attitude_linear_loop": case_attitude_linear_loop, "pos_att_faults": case_pos_att_faults,
-                  "kirk_noisy": case_kirk_noisy}[c](host=not a.no_host)
+                  "kirk_noisy": case_kirk_noisy, "greedy": case_greedy}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.cases == "position_loop" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
@@ -538,6 +588,8 @@ def main():
         (ROOT / "profiles" / "rollout_pos_att_faults_time.json").write_text(json.dumps(res) + "\n")
     if a.cases == "kirk_noisy" and not a.out:                     # its own record: one line
         (ROOT / "profiles" / "rollout_noisy_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "greedy" and not a.out:                         # its own record: one line
+        (ROOT / "profiles" / "rollout_greedy_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
