@@ -45,10 +45,11 @@ struct GreedyModel {
     double c[HJB_MAX_D], q[HJB_MAX_D], r[HJB_ROLLOUT_MAX_U];
 };
 
-// The grid half of a GreedyModel and 1/dx, exactly as hjb_rollout_create forms them: rdx[i] = 1 / (k[i+1] - k[i]) (0 at an axis'
-// last knot), the arithmetic first guess of the cell search on axes whose knots are uniform to 1.5 steps.  knots: the axes'
-// vectors concatenated; rdx: as many doubles.
-inline void greedy_grid(int D, const int32_t *n, const double *knots, GreedyModel &M, double *rdx) {
+// The grid half of a MODEL and 1/dx, the one place they are formed (hjb_rollout_create calls it on its DRollout): rdx[i] =
+// 1 / (k[i+1] - k[i]) (0 at an axis' last knot), the arithmetic first guess of the cell search on axes whose knots are uniform
+// to 1.5 steps.  knots: the axes' vectors concatenated; rdx: as many doubles.
+template <typename MODEL>
+inline void greedy_grid(int D, const int32_t *n, const double *knots, MODEL &M, double *rdx) {
     int64_t s = 1;
     int32_t off = 0;
     for (int a = 0; a < D; ++a) {

@@ -14,7 +14,7 @@
 //   hjbdp_multi.hip    hjb_create_multi / hjb_solve_multi (one process, several GPUs): the slabs, the halo copies, the stage loop
 //   hjbdp_rank.hip     hjb_rank_* (one process per GPU: one slab) and the RCCL transport inside the library
 //   hjbdp_devmem.hip   device-buffer helpers
-//   rollout.hip, rollout_attitude.hip   hjb_rollout_*: closed-loop rollouts of stored policies (error reporting and locks only)
+//   rollout.hip, rollout_channels.hip (rollout_host.h)   hjb_rollout_*: closed-loop rollouts of stored policies (error reporting and locks only)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -216,4 +216,8 @@ k_rollout(const DRollout R, int64_t nc, const double *__restrict__ X0, double *_
     if (cost) cost[i] = J;
 }
 
+// rollout_affine.hip instantiates the 72 kernels (label type x method x LDS x D) and launches the one asked for
+hipError_t launch_rollout(int idx_bytes, int method, bool lds_on, int D, const DRollout &R, int64_t nc, size_t lds, hipStream_t st,
+                          const double *X0, double *Xf, double *cost, double *Xp, double *Up);
+
 }  // namespace hjb

@@ -1,10 +1,8 @@
 // rollout.hip - hjb_rollout_* and hjb_attitude_linear_response: the host side of the batched closed-loop rollouts
 // (include/hjbdp.h).  An object holds one stored policy (hjb_rollout_create) and one model, the last one set:
-//   affine (K16, kernels_rollout.h, launched from this unit), attitude (K17, kernels_rollout_attitude.h / rollout_attitude.hip),
-//   and the three that attach two more objects' policies as channels: pos-att (K18, kernels_rollout_pos_att.h /
-//   rollout_pos_att.hip; its fault campaigns K23, kernels_rollout_pos_att_faults.h / rollout_pos_att_faults.hip), position (K19,
-//   kernels_rollout_position.h / rollout_position.hip), simplified attitude (K20, kernels_rollout_attitude_simplified.h /
-//   rollout_attitude_simplified.hip).
+//   affine (K16, kernels_rollout.h / rollout_affine.hip), attitude (K17, kernels_rollout_attitude.h / rollout_attitude.hip),
+//   and the three that attach two more objects' policies as channels (pos-att, position, simplified attitude): their setters
+//   and run functions are rollout_channels.hip.
 // The linear attitude controller (K21, kernels_rollout_attitude_linear.h / rollout_attitude_linear.hip) needs no object.
 // Beside the model an object may hold a noise node set (hjb_rollout_set_noise): hjb_rollout_run_noisy (K25,
 // kernels_rollout_noisy.h / rollout_noisy.hip) flies the affine loop under it, and no other run function reads it.  The sampler's
@@ -12,111 +10,16 @@
 // And it may hold value planes (hjb_rollout_set_values): hjb_rollout_run_greedy (K26, kernels_rollout_greedy.h /
 // rollout_greedy.hip) flies the affine loop by one-step lookahead on them, and no other run function reads them.  Its host twin
 // hjb_rollout_greedy_host (hjbdp_greedy.h) needs no device and no object.
-// Shared here: the attached-channels record and attach_channels (the three attaching setters), check_run / check_traj /
-// check_quaternions (the run functions' refusals, all before any device work), lds_bytes, run_chunks (the chunk loop).
-#include "hjbdp_host.h"
-#include "kernels_rollout.h"
-#include "kernels_rollout_attitude.h"
-#include "kernels_rollout_pos_att.h"
-#include "kernels_rollout_pos_att_faults.h"
-#include "kernels_rollout_position.h"
-#include "kernels_rollout_attitude_simplified.h"
-#include "kernels_rollout_attitude_linear.h"
-#include "kernels_rollout_noisy.h"
-#include "kernels_rollout_greedy.h"
+// Defined here for both host units (rollout_host.h): rfail, check_run / check_traj / check_quaternions (the run functions'
+// refusals, all before any device work), upload, run_chunks (the chunk loop).  No kernel is instantiated in this unit.
+#include "rollout_host.h"
 #include "rollout_dispatch.h"
-#include <memory>
+#include "kernels_rollout_attitude_linear.h"
+#include "kernels_rollout_greedy.h"
 
 using namespace hjbhost;
 
 namespace {
-
-// the model an object holds: the last setter called wins.  The last three keep an Attached record in Rollout::att, the others none
-enum { kModelNone = 0, kModelAffine = 1, kModelAttitude = 2, kModelPosAtt = 3, kModelPosition = 4, kModelAttSimplified = 5 };
-
-// Device allocations with shared ownership: an object's grid, table and labels live as long as the object or a pos-att, position
-// or simplified attitude model that reads them (hjb_rollout_set_pos_att_model / hjb_rollout_set_position_model /
-// hjb_rollout_set_attitude_simplified_model on another object) does.  Freed under the
-// last owner's locks (destroy / set_*model).
-struct DevData {
-    int device = 0;
-    std::vector<void *> allocs;
-    ~DevData() {
-        if (allocs.empty()) return;
-        (void)hipSetDevice(device);
-        for (void *p : allocs) (void)hipFree(p);
-    }
-};
-
-// What a model of three channels holds of the two other objects (y and z, or 2 and 3): their policies' descriptors, with the
-// device data kept alive.  The model's own members sit on top (PosAtt, Position, AttSimplified).
-struct Attached {
-    DPaChan c[2]{};
-    std::shared_ptr<DevData> data[2];
-    int n_planes = 0;               // of the three channels, the fewest
-    virtual ~Attached() = default;
-};
-
-// The pos-att model of channel x's object
-struct PosAtt : Attached {
-    std::shared_ptr<DevData> coef;
-    DPosAtt M{};
-    int max_steps = 0;              // (n_nodes - 1) / (2 substeps)
-    double h = 0;                   // as given (M.hs is h / substeps)
-    // the fault controller of channel x (hjb_rollout_set_pos_att_fault_controller): read by hjb_rollout_run_pos_att_faults alone
-    bool has_xf = false;
-    DPaChan cxf{};
-    std::shared_ptr<DevData> data_xf;
-    int planes_xf = 0;
-};
-
-// The position model of channel x's object
-struct Position : Attached {
-    std::shared_ptr<DevData> table;     // n_sub and the sub-step rows
-    DPosition M{};
-    int max_steps = 0;              // stages the table holds
-};
-
-// The simplified attitude model of channel 1's object
-struct AttSimplified : Attached {
-    DAttSimplified M{};
-    int dynamics = HJB_ATTS_FULL;
-};
-
-struct Rollout {
-    std::mutex mu;                  // one call at a time per object
-    int device = 0, D = 0, idx_bytes = 4, n_planes = 0;
-    int model = kModelNone, integrator = HJB_ATT_TAYLOR;
-    int64_t chunk = (int64_t)1 << 20;
-    bool lds = true;                // option "lds": stage the tables in LDS when they fit (false: never)
-    DRollout R{};                   // device pointers filled by create; model by set_model
-    DAttitude M{};                  // the attitude model (set_attitude_model)
-    std::unique_ptr<Attached> att;  // the PosAtt / Position / AttSimplified of model kModelPosAtt / kModelPosition / kModelAttSimplified
-    std::shared_ptr<DevData> data;
-    // the noise node set (hjb_rollout_set_noise): N.n_nodes > 0 while one is set; read by hjb_rollout_run_noisy alone
-    DNoise N{};
-    std::shared_ptr<DevData> noise;     // N.tab: thresholds, then the masked axes' offsets
-    // the value planes (hjb_rollout_set_values): val_planes > 0 while some are set; read by hjb_rollout_run_greedy alone
-    std::shared_ptr<DevData> values;
-    const void *dvalues = nullptr;      // [nS, val_planes] column-major, float or double
-    int val_planes = 0, val_bytes = 8;
-    hipStream_t stream = nullptr;
-    std::string err;
-};
-
-constexpr int64_t kMaxChunk = (int64_t)1 << 30;
-constexpr size_t kLdsMax = 32 << 10;        // knots + 1/dx + u_table staged in LDS up to this size
-
-int rfail(Rollout *ro, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (ro) ro->err = buf;
-    g_last_error = buf;
-    return code;
-}
 
 void release(Rollout *ro) {
     ro->att.reset();
@@ -135,29 +38,63 @@ int64_t first_bad_label(const void *labels, int64_t count, int64_t lo, int64_t h
     return -1;
 }
 
-// K16's 72 instantiations (label type x method x LDS x D) and the launch of the one asked for
-hipError_t launch_rollout(int idx_bytes, int method, bool lds_on, int D, const DRollout &R, int64_t nc, size_t lds, hipStream_t st,
-                          const double *X0, double *Xf, double *cost, double *Xp, double *Up) {
-    const dim3 b(256), g((unsigned)((nc + 255) / 256));
-    with_label_type(idx_bytes, [&](auto tl) {
-        with_int<HJB_LOOKUP_NEAREST, HJB_LOOKUP_LINEAR>(method, [&](auto m) {
-            with_bool(lds_on, [&](auto l) {
-                with_dim(D, [&](auto d) {
-                    using TL = typename decltype(tl)::type;
-                    constexpr bool LDS = decltype(l)::value;
-                    hipLaunchKernelGGL((k_rollout<decltype(d)::value, TL, decltype(m)::value, LDS>), g, b, LDS ? lds : 0, st, R, nc, X0,
-                                       Xf, cost, Xp, Up);
-                });
-            });
-        });
-    });
-    return hipGetLastError();
+// a pos-att, position or simplified attitude model goes, and with it its hold on the other two channels
+void drop_attached(Rollout *ro) {
+    if (!ro->att) return;
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    ro->att.reset();
+}
+
+// What hjb_rollout_set_noise and hjb_rollout_noise_table refuse of a weight vector (null: equal weights), said in `who`'s name:
+// a weight that is not finite or is negative, weights that sum to 0.  HJB_OK otherwise.
+int check_weights(Rollout *ro, const char *who, int32_t n_nodes, const double *weights) {
+    if (!weights) return HJB_OK;
+    double sum = 0.0;
+    for (int w = 0; w < n_nodes; ++w) {
+        if (!std::isfinite(weights[w]) || weights[w] < 0) return rfail(ro, HJB_E_INVALID, "%s: weight %d is not finite or is negative", who, w);
+        sum = sum + weights[w];
+    }
+    if (!(sum > 0) || !std::isfinite(sum)) return rfail(ro, HJB_E_INVALID, "%s: the %d weights sum to 0 (or their sum overflows)", who, n_nodes);
+    return HJB_OK;
+}
+
+// What hjb_rollout_create (who: "rollout") and hjb_rollout_greedy_host (its own name) refuse of a grid: an axis of fewer than two
+// knots, a knot that is not finite, knots not strictly increasing, sizes that overflow.  -> the states and the knots of all axes
+int check_grid(const char *who, int D, const int32_t *n, const double *knots, int64_t *nS_out, int64_t *n_knots_out) {
+    int64_t nS = 1, n_knots = 0;
+    for (int a = 0; a < D; ++a) {
+        if (n[a] < 2) return rfail(nullptr, HJB_E_INVALID, "%s: axis %d has %d knots (need >= 2)", who, a, n[a]);
+        const double *kk = knots + n_knots;
+        for (int i = 0; i < n[a]; ++i)
+            if (!std::isfinite(kk[i])) return rfail(nullptr, HJB_E_INVALID, "%s: knot %d of axis %d is not finite", who, i, a);
+        for (int i = 0; i + 1 < n[a]; ++i)
+            if (!(kk[i + 1] > kk[i])) return rfail(nullptr, HJB_E_INVALID, "%s: knots of axis %d not strictly increasing (at %d)", who, a, i);
+        n_knots += n[a];
+        if (n_knots > INT32_MAX || nS > kMaxStates / n[a]) return rfail(nullptr, HJB_E_INVALID, "%s: size overflow (grid)", who);
+        nS *= n[a];
+    }
+    *nS_out = nS;
+    *n_knots_out = n_knots;
+    return HJB_OK;
+}
+
+}  // namespace
+
+namespace hjbhost {
+
+int rfail(Rollout *ro, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (ro) ro->err = buf;
+    g_last_error = buf;
+    return code;
 }
 
 bool all_finite(const double *p, int64_t n) { return !p || first_nonfinite(p, n, true) < 0; }
 
-// The argument checks every run function of an object makes before any device work: method, sizes, that the object holds the
-// model this entry point runs (`want`), plane_of_step against the planes all of the model's channels have.
 int check_run(Rollout *ro, int want, int method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj) {
     if (method != HJB_LOOKUP_NEAREST && method != HJB_LOOKUP_LINEAR) return rfail(ro, HJB_E_INVALID, "rollout: method %d", method);
     if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
@@ -183,8 +120,6 @@ int check_run(Rollout *ro, int want, int method, int32_t n_steps, const int32_t 
     return HJB_OK;
 }
 
-// The checks on the trajectories every run function makes next (pre: "rollout", or the entry point's name where there is no
-// object): null X0 / X_final, the sizes of W doubles per trajectory and stage (wname: how the message spells W), a finite X0.
 int check_traj(Rollout *ro, const char *pre, int W, const char *wname, int32_t n_steps, int64_t n_traj, const double *X0,
                const double *X_final) {
     if (!X0 || !X_final) return rfail(ro, HJB_E_INVALID, "%s: null X0 / X_final", pre);
@@ -195,7 +130,6 @@ int check_traj(Rollout *ro, const char *pre, int W, const char *wname, int32_t n
     return HJB_OK;
 }
 
-// K17 and K21 renormalise the quaternion X0[3..6] of a 7-state column after the first step: all zeros would be 0/0
 int check_quaternions(Rollout *ro, const char *pre, int64_t n_traj, const double *X0) {
     for (int64_t i = 0; i < n_traj; ++i) {
         const double *q = X0 + HJB_ATT_W * i + 3;
@@ -206,191 +140,105 @@ int check_quaternions(Rollout *ro, const char *pre, int64_t n_traj, const double
     return HJB_OK;
 }
 
-// a pos-att, position or simplified attitude model goes, and with it its hold on the other two channels
-void drop_attached(Rollout *ro) {
-    if (!ro->att) return;
-    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-    ro->att.reset();
+DAttitude euler_attitude(double J1, double J2, double J3, double h) {
+    DAttitude A{};
+    A.h = h;
+    A.J[0] = J1;
+    A.J[1] = J2;
+    A.J[2] = J3;
+    A.c[0] = (J2 - J3) / J1;                          // spacecraft_dynamics_list :600-620
+    A.c[1] = (J3 - J1) / J2;
+    A.c[2] = (J1 - J2) / J3;
+    return A;
 }
 
-// what K18, K19 and K20 read of an object's policy (kernels_rollout_pos_att.h)
-DPaChan pa_channel(const DRollout &R) {
-    DPaChan c{};
-    for (int a = 0; a < 4; ++a) {
-        c.n[a] = R.n[a];
-        c.koff[a] = R.koff[a];
-        c.uniform[a] = R.uniform[a];
-        c.x0[a] = R.x0[a];
-        c.inv_h[a] = R.inv_h[a];
-        c.stride[a] = R.stride[a];
-    }
-    c.nS = R.nS;
-    c.n_knots = R.n_knots;
-    c.n_labels = R.n_labels;
-    c.index_base = R.index_base;
-    c.knots = R.knots;
-    c.rdx = R.rdx;
-    c.u_table = R.u_table;
-    c.labels = R.labels;
-    return c;
-}
-
-DPaChan on_planes(DPaChan c, const int32_t *plane_of_step) {
-    c.plane_of_step = plane_of_step;
-    return c;
-}
-
-// the LDS bytes of the channels' [knots | 1/dx | u_table], `width` u_table doubles per label
-size_t lds_bytes(std::initializer_list<const DPaChan *> chans, int width) {
-    int64_t nk = 0, nl = 0;
-    for (const DPaChan *c : chans) {
-        nk += c->n_knots;
-        nl += c->n_labels;
-    }
-    return (size_t)(2 * nk + width * nl) * sizeof(double);
-}
-
-// Another object's policy as a channel: a snapshot with a share of its device data, taken under that object's own lock
-struct ChanSnap {
-    DPaChan c{};
-    std::shared_ptr<DevData> data;
-    int D = 0, n_u = 0, device = 0, idx_bytes = 0, n_planes = 0;
-};
-
-ChanSnap snap_channel(Rollout *o) {
-    std::lock_guard<std::mutex> g(o->mu);
-    ChanSnap s;
-    s.c = pa_channel(o->R);
-    s.data = o->data;
-    s.D = o->D;
-    s.n_u = o->R.n_u;
-    s.device = o->device;
-    s.idx_bytes = o->idx_bytes;
-    s.n_planes = o->n_planes;
-    return s;
-}
-
-// a snapshot against the object rx it is attached to (under rx's lock): one device, one label type
-int check_channel(Rollout *rx, const ChanSnap &s, const char *name, const char *rx_name, const char *sharers) {
-    if (s.device != rx->device)
-        return rfail(rx, HJB_E_INVALID, "rollout: %s is on device %d, %s on device %d", name, s.device, rx_name, rx->device);
-    if (s.idx_bytes != rx->idx_bytes)
-        return rfail(rx, HJB_E_INVALID, "rollout: %s has %d-byte labels, %s %d-byte labels (the %s share one label type)", name,
-                     s.idx_bytes, rx_name, rx->idx_bytes, sharers);
+int upload(Rollout *ro, DevData &dd, const void *src, size_t bytes, const void **out) {
+    void *d = nullptr;
+    if (hipMalloc(&d, std::max<size_t>(bytes, 16)) != hipSuccess) return rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", bytes);
+    dd.allocs.push_back(d);
+    if (bytes && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "rollout: upload failed");
+    *out = d;
     return HJB_OK;
 }
 
-// What the setters of a three-channel model share.  rs: the three objects, names: their handles' names in the messages, model:
-// the model's name there; every channel needs D == D and n_u == n_u.  Snapshots the two other channels under their own locks
-// (in order), then takes rs[0]'s lock into lk - the caller holds it to its end - and checks the three against each other;
-// at gets the snapshots and the fewest planes.  On a refusal the snapshots' shares of the other objects' device data go with
-// this frame, under rs[0]'s lock when it was taken and without g_capture_mu: a share frees device memory only as the last owner,
-// that is when the other object was destroyed in between (a refused setter of the earlier form freed the same way).
-int attach_channels(Rollout *const (&rs)[3], const char *const (&names)[3], const char *model, int D, int n_u, Attached &at,
-                    std::unique_lock<std::mutex> &lk) {
-    Rollout *rx = rs[0];
-    if (!rs[0] || !rs[1] || !rs[2]) return rfail(rx, HJB_E_INVALID, "rollout: null handle (three channel objects are required)");
-    if (rs[0] == rs[1] || rs[0] == rs[2] || rs[1] == rs[2]) return rfail(rx, HJB_E_INVALID, "rollout: the same object passed for two channels");
-    const char *const needs = "rollout: the %s model needs D == %d and n_u == %d (%s: D=%d, n_u=%d)";
-    ChanSnap sn[2];
-    for (int t = 0; t < 2; ++t) {
-        sn[t] = snap_channel(rs[1 + t]);
-        if (sn[t].D != D || sn[t].n_u != n_u) return rfail(rx, HJB_E_INVALID, needs, model, D, n_u, names[1 + t], sn[t].D, sn[t].n_u);
-    }
-    lk = std::unique_lock<std::mutex>(rx->mu);
-    if (rx->D != D || rx->R.n_u != n_u) return rfail(rx, HJB_E_INVALID, needs, model, D, n_u, names[0], rx->D, rx->R.n_u);
-    for (int t = 0; t < 2; ++t) {
-        const int bad = check_channel(rx, sn[t], names[1 + t], names[0], "three channels");
-        if (bad) return bad;
-    }
-    at.n_planes = std::min(rx->n_planes, std::min(sn[0].n_planes, sn[1].n_planes));
-    for (int t = 0; t < 2; ++t) {
-        at.c[t] = sn[t].c;
-        at.data[t] = std::move(sn[t].data);
-    }
-    return HJB_OK;
-}
-
-// under rx's lock and g_capture_mu, on rx's device: the model takes the place of (and releases) whatever was attached
-void install_attached(Rollout *rx, std::unique_ptr<Attached> at, int model) {
-    if (rx->stream) (void)hipStreamSynchronize(rx->stream);
-    rx->att = std::move(at);
-    rx->model = model;
-}
-
-// The chunk loop the run functions share: W doubles of state per trajectory; per step n_up control rows (U_path) and n_e more
-// path rows (E_path: the attitude loop's angles, the pos-att loop's Force_Moment).  Per chunk: upload X0, launch(R, nc, lds, lds_on, stream, X0, Xf, cost, Xp, Up, Ep, Fl) (the
-// kernel of the entry point `who`; Fl: nc int32 flags, allocated when `flags` is asked for: the position loop's off_schedule),
-// download X_final / cost / flags and the paths ([nc, rows] on the device -> columns i0 .. i0+nc of
-// [n_traj, rows] on the host); device_ms sums the launches' event times.  plane_of_step may be null for a loop without a policy
-// (hjb_attitude_linear_response): nothing is uploaded then.  pre(i0, nc, stream) runs per chunk after X0's upload and before the
-// launch's first event (hjb_rollout_run_pos_att_faults uploads its per-trajectory inputs there, at the chunk's own offset).
-template <typename Launch, typename Pre>
-int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
-               const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *E_path, int32_t *flags,
-               double *device_ms, Launch launch, Pre pre) {
+int run_chunks(Rollout *ro, const ChunkPlan &plan, const std::function<hipError_t(const Chunk &)> &launch) {
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
-    const int nu = n_up;
-    const int64_t nc_max = std::min(n_traj, ro->chunk);
+    const int W = plan.W;
+    const int32_t n_steps = plan.n_steps;
+    const int64_t n_traj = plan.n_traj, nc_max = std::min(n_traj, ro->chunk);
     const size_t xb = (size_t)nc_max * W * sizeof(double);
-    const size_t xpb = X_path ? (size_t)nc_max * W * ((size_t)n_steps + 1) * sizeof(double) : 0;
-    const size_t upb = U_path ? (size_t)nc_max * nu * (size_t)n_steps * sizeof(double) : 0;
-    const size_t epb = E_path ? (size_t)nc_max * n_e * (size_t)n_steps * sizeof(double) : 0;
-    const size_t cb = cost ? (size_t)nc_max * sizeof(double) : 0;
+    const size_t cb = plan.cost ? (size_t)nc_max * sizeof(double) : 0;
     const size_t pb = (size_t)std::max(n_steps, 1) * sizeof(int32_t);
+    const size_t fb = plan.flags ? (size_t)nc_max * sizeof(int32_t) : 0;
+    size_t rows[kMaxPaths], pathb[kMaxPaths], need = 2 * xb + cb + pb + fb;     // rows: doubles per trajectory of a path asked for
+    for (int p = 0; p < kMaxPaths; ++p) {
+        rows[p] = plan.path[p].host ? (size_t)plan.path[p].rows * (size_t)plan.path[p].stages : 0;
+        pathb[p] = (size_t)nc_max * rows[p] * sizeof(double);
+        need += pathb[p];
+    }
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipMemGetInfo failed");
-    const size_t fb = flags ? (size_t)nc_max * sizeof(int32_t) : 0;
-    const size_t need = 2 * xb + xpb + upb + epb + cb + pb + fb;
     if (need + ((size_t)64 << 20) > fr)
         return rfail(ro, HJB_E_NOMEM, "rollout: a chunk of %lld trajectories needs %zu bytes, %zu free (lower option \"chunk\")",
                      (long long)nc_max, need, fr);
-    void *bufs[8] = {};
+    std::vector<void *> bufs;
     auto done = [&](int code) {
-        for (void *p : bufs) if (p) (void)hipFree(p);
+        for (void *p : bufs) (void)hipFree(p);
         return code;
     };
-    const size_t sizes[8] = {xb, xb, cb, xpb, upb, pb, epb, fb};
-    for (int b = 0; b < 8; ++b)
-        if (sizes[b] && hipMalloc(&bufs[b], sizes[b]) != hipSuccess) return done(rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", sizes[b]));
-    double *dX0 = (double *)bufs[0], *dXf = (double *)bufs[1], *dC = (double *)bufs[2], *dXp = (double *)bufs[3], *dUp = (double *)bufs[4];
-    double *dEp = (double *)bufs[6];
-    int32_t *dFl = (int32_t *)bufs[7];
-    hipStream_t st = ro->stream;
+    size_t failed = 0;                                        // the bytes of the allocation that failed
+    auto dev = [&](size_t bytes) -> void * {                  // null for no bytes, and after a failure
+        void *d = nullptr;
+        if (!bytes || failed) return d;
+        if (hipMalloc(&d, bytes) == hipSuccess) bufs.push_back(d);
+        else failed = bytes;
+        return d;
+    };
+    Chunk c{};
+    double *const dX0 = (double *)dev(xb);
+    c.X0 = dX0;
+    c.Xf = (double *)dev(xb);
+    c.cost = (double *)dev(cb);
+    c.path[0] = (double *)dev(pathb[0]);
+    c.path[1] = (double *)dev(pathb[1]);
+    int32_t *const dplane = (int32_t *)dev(pb);
+    for (int p = 2; p < kMaxPaths; ++p) c.path[p] = (double *)dev(pathb[p]);
+    c.flags = (int32_t *)dev(fb);
+    int32_t *din[kMaxInputs];
+    for (int t = 0; t < kMaxInputs; ++t) c.input[t] = din[t] = (int32_t *)dev(plan.input[t] ? (size_t)nc_max * sizeof(int32_t) : 0);
+    if (failed) return done(rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", failed));
+    hipStream_t st = c.st = ro->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess && n_steps > 0 && plane_of_step) e = hipMemcpyAsync(bufs[5], plane_of_step, pb, hipMemcpyHostToDevice, st);
-    DRollout R = ro->R;
-    R.plane_of_step = (const int32_t *)bufs[5];
-    R.n_steps = n_steps;
-    const size_t lds = (size_t)(2 * (int64_t)R.n_knots + (int64_t)R.n_labels * R.n_u) * sizeof(double);
-    const bool lds_on = ro->lds && lds <= kLdsMax;
+    if (e == hipSuccess && n_steps > 0 && plan.plane_of_step) e = hipMemcpyAsync(dplane, plan.plane_of_step, pb, hipMemcpyHostToDevice, st);
+    c.R = ro->R;
+    c.R.plane_of_step = dplane;
+    c.R.n_steps = n_steps;
+    c.lds = (size_t)(2 * (int64_t)c.R.n_knots + (int64_t)c.R.n_labels * c.R.n_u) * sizeof(double);
+    c.lds_on = ro->lds && c.lds <= kLdsMax;
     double ms_total = 0;
     for (int64_t i0 = 0; e == hipSuccess && i0 < n_traj; i0 += nc_max) {
         const int64_t nc = std::min(nc_max, n_traj - i0);
-        e = hipMemcpyAsync(dX0, X0 + W * i0, (size_t)nc * W * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) break;
-        e = pre(i0, nc, st);
+        c.i0 = i0;
+        c.nc = nc;
+        e = hipMemcpyAsync(dX0, plan.X0 + W * i0, (size_t)nc * W * sizeof(double), hipMemcpyHostToDevice, st);
+        for (int t = 0; e == hipSuccess && t < kMaxInputs; ++t)
+            if (din[t]) e = hipMemcpyAsync(din[t], plan.input[t] + i0, (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, st);
         if (e != hipSuccess) break;
         (void)hipEventRecord(e0, st);
-        e = launch(R, nc, lds, lds_on, st, dX0, dXf, dC, dXp, dUp, dEp, dFl);
+        e = launch(c);
         if (e != hipSuccess) break;
         (void)hipEventRecord(e1, st);
-        e = hipMemcpyAsync(X_final + W * i0, dXf, (size_t)nc * W * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && cost) e = hipMemcpyAsync(cost + i0, dC, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && flags) e = hipMemcpyAsync(flags + i0, dFl, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(plan.X_final + W * i0, c.Xf, (size_t)nc * W * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && plan.cost) e = hipMemcpyAsync(plan.cost + i0, c.cost, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && plan.flags) e = hipMemcpyAsync(plan.flags + i0, c.flags, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, st);
         // paths: [nc, rows] on the device -> columns i0 .. i0+nc of [n_traj, rows] on the host
-        if (e == hipSuccess && X_path)
-            e = hipMemcpy2DAsync(X_path + i0, (size_t)n_traj * sizeof(double), dXp, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double),
-                                 (size_t)W * (n_steps + 1), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && U_path && n_steps > 0)
-            e = hipMemcpy2DAsync(U_path + i0, (size_t)n_traj * sizeof(double), dUp, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double),
-                                 (size_t)nu * n_steps, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && E_path && n_steps > 0)
-            e = hipMemcpy2DAsync(E_path + i0, (size_t)n_traj * sizeof(double), dEp, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double),
-                                 (size_t)n_e * n_steps, hipMemcpyDeviceToHost, st);
+        for (int p = 0; e == hipSuccess && p < kMaxPaths; ++p)
+            if (rows[p])
+                e = hipMemcpy2DAsync(plan.path[p].host + i0, (size_t)n_traj * sizeof(double), c.path[p], (size_t)nc * sizeof(double),
+                                     (size_t)nc * sizeof(double), rows[p], hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         float ms = 0;
         if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
@@ -400,34 +248,13 @@ int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n
     if (e1) (void)hipEventDestroy(e1);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
-        return done(rfail(ro, HJB_E_DEVICE, "%s: %s", who, hipGetErrorString(e)));
+        return done(rfail(ro, HJB_E_DEVICE, "%s: %s", plan.who, hipGetErrorString(e)));
     }
-    if (device_ms) *device_ms = ms_total;
+    if (plan.device_ms) *plan.device_ms = ms_total;
     return done(HJB_OK);
 }
 
-template <typename Launch>
-int run_chunks(Rollout *ro, const char *who, int W, int n_up, int n_e, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
-               const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *E_path, int32_t *flags,
-               double *device_ms, Launch launch) {
-    return run_chunks(ro, who, W, n_up, n_e, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, E_path, flags, device_ms,
-                      launch, [](int64_t, int64_t, hipStream_t) { return hipSuccess; });
-}
-
-// What hjb_rollout_set_noise and hjb_rollout_noise_table refuse of a weight vector (null: equal weights), said in `who`'s name:
-// a weight that is not finite or is negative, weights that sum to 0.  HJB_OK otherwise.
-int check_weights(Rollout *ro, const char *who, int32_t n_nodes, const double *weights) {
-    if (!weights) return HJB_OK;
-    double sum = 0.0;
-    for (int w = 0; w < n_nodes; ++w) {
-        if (!std::isfinite(weights[w]) || weights[w] < 0) return rfail(ro, HJB_E_INVALID, "%s: weight %d is not finite or is negative", who, w);
-        sum = sum + weights[w];
-    }
-    if (!(sum > 0) || !std::isfinite(sum)) return rfail(ro, HJB_E_INVALID, "%s: the %d weights sum to 0 (or their sum overflows)", who, n_nodes);
-    return HJB_OK;
-}
-
-}  // namespace
+}  // namespace hjbhost
 
 extern "C" {
 
@@ -447,17 +274,7 @@ int32_t hjb_rollout_create(int32_t device, int32_t D, const int32_t *n, const do
     if (n_planes < 1) return rfail(nullptr, HJB_E_INVALID, "rollout: n_planes=%d < 1", n_planes);
     if (n_labels < 1) return rfail(nullptr, HJB_E_INVALID, "rollout: n_labels=%d < 1", n_labels);
     int64_t nS = 1, n_knots = 0;
-    for (int a = 0; a < D; ++a) {
-        if (n[a] < 2) return rfail(nullptr, HJB_E_INVALID, "rollout: axis %d has %d knots (need >= 2)", a, n[a]);
-        const double *kk = knots + n_knots;
-        for (int i = 0; i < n[a]; ++i)
-            if (!std::isfinite(kk[i])) return rfail(nullptr, HJB_E_INVALID, "rollout: knot %d of axis %d is not finite", i, a);
-        for (int i = 0; i + 1 < n[a]; ++i)
-            if (!(kk[i + 1] > kk[i])) return rfail(nullptr, HJB_E_INVALID, "rollout: knots of axis %d not strictly increasing (at %d)", a, i);
-        n_knots += n[a];
-        if (n_knots > INT32_MAX || nS > kMaxStates / n[a]) return rfail(nullptr, HJB_E_INVALID, "rollout: size overflow (grid)");
-        nS *= n[a];
-    }
+    if (const int bad_grid = check_grid("rollout", D, n, knots, &nS, &n_knots)) return bad_grid;
     if ((int64_t)n_planes > kMaxStates / nS) return rfail(nullptr, HJB_E_INVALID, "rollout: size overflow (%lld states x %d planes)", (long long)nS, n_planes);
     const int64_t n_lab = nS * n_planes;
     const int64_t n_ut = (int64_t)n_labels * n_u;
@@ -490,54 +307,23 @@ int32_t hjb_rollout_create(int32_t device, int32_t D, const int32_t *n, const do
     ro->D = D;
     ro->idx_bytes = idx_bytes;
     ro->n_planes = n_planes;
-    ro->data = std::make_shared<DevData>();
-    ro->data->device = device;
+    ro->data = std::make_shared<DevData>(device);
     DRollout &R = ro->R;
     R.n_u = n_u;
     R.n_labels = n_labels;
     R.index_base = index_base;
-    R.n_knots = (int32_t)n_knots;
-    R.nS = nS;
-    std::vector<double> kk(knots, knots + n_knots), rdx(n_knots, 0.0);
-    int64_t s = 1, off = 0;
-    for (int a = 0; a < D; ++a) {
-        const double *k = kk.data() + off;
-        for (int i = 0; i + 1 < n[a]; ++i) rdx[off + i] = 1.0 / (k[i + 1] - k[i]);     // as hjb_policy_lookup builds it
-        const double hstep = (k[n[a] - 1] - k[0]) / (n[a] - 1);
-        double dev = 0;
-        for (int i = 0; i < n[a]; ++i) dev = std::max(dev, std::fabs(k[i] - (k[0] + i * hstep)));
-        R.uniform[a] = dev <= 1.5 * hstep ? 1 : 0;
-        R.x0[a] = k[0];
-        R.inv_h[a] = 1.0 / hstep;
-        R.n[a] = n[a];
-        R.koff[a] = (int32_t)off;
-        R.stride[a] = s;
-        s *= n[a];
-        off += n[a];
-    }
-    auto dev_upload = [&](const void *src, size_t bytes, void **out) -> int {
-        void *d = nullptr;
-        if (hipMalloc(&d, std::max<size_t>(bytes, 16)) != hipSuccess) return rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", bytes);
-        ro->data->allocs.push_back(d);
-        if (hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "rollout: upload failed");
-        *out = d;
-        return HJB_OK;
-    };
-    void *dk = nullptr, *dr = nullptr, *du = nullptr, *dl = nullptr;
-    int st = dev_upload(kk.data(), kk.size() * sizeof(double), &dk);
-    if (!st) st = dev_upload(rdx.data(), rdx.size() * sizeof(double), &dr);
-    if (!st) st = dev_upload(u_table, (size_t)n_ut * sizeof(double), &du);
-    if (!st) st = dev_upload(labels, lab_bytes, &dl);
+    std::vector<double> rdx((size_t)n_knots);
+    greedy_grid(D, n, knots, R, rdx.data());                  // the grid description and 1/dx, as hjb_policy_lookup builds it
+    int st = upload(ro, *ro->data, knots, (size_t)n_knots * sizeof(double), (const void **)&R.knots);
+    if (!st) st = upload(ro, *ro->data, rdx.data(), rdx.size() * sizeof(double), (const void **)&R.rdx);
+    if (!st) st = upload(ro, *ro->data, u_table, (size_t)n_ut * sizeof(double), (const void **)&R.u_table);
+    if (!st) st = upload(ro, *ro->data, labels, lab_bytes, &R.labels);
     if (!st && hipStreamCreateWithFlags(&ro->stream, hipStreamNonBlocking) != hipSuccess) st = rfail(ro, HJB_E_DEVICE, "rollout: stream creation failed");
     if (st) {
         release(ro);
         delete ro;
         return st;
     }
-    R.knots = (const double *)dk;
-    R.rdx = (const double *)dr;
-    R.u_table = (const double *)du;
-    R.labels = dl;
     *rollout_out = ro;
     return HJB_OK;
 }
@@ -584,192 +370,12 @@ int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, dou
         return rfail(ro, HJB_E_INVALID, "rollout: integrator %d is not HJB_ATT_TAYLOR / HJB_ATT_RK4", integrator);
     if (!all_finite(q, HJB_ATT_W)) return rfail(ro, HJB_E_INVALID, "rollout: q is not finite");
     if (!all_finite(r, HJB_ATT_U)) return rfail(ro, HJB_E_INVALID, "rollout: r is not finite");
-    DAttitude &M = ro->M;
-    M = DAttitude{};
-    M.h = h;
-    const double J1 = inertia[0], J2 = inertia[1], J3 = inertia[2];
-    M.J[0] = J1;
-    M.J[1] = J2;
-    M.J[2] = J3;
-    M.c[0] = (J2 - J3) / J1;                          // spacecraft_dynamics_list :600-620
-    M.c[1] = (J3 - J1) / J2;
-    M.c[2] = (J1 - J2) / J3;
-    if (q) std::memcpy(M.q, q, sizeof M.q);
-    if (r) std::memcpy(M.r, r, sizeof M.r);
+    ro->M = euler_attitude(inertia[0], inertia[1], inertia[2], h);
+    if (q) std::memcpy(ro->M.q, q, sizeof ro->M.q);
+    if (r) std::memcpy(ro->M.r, r, sizeof ro->M.r);
     ro->integrator = integrator;
     ro->model = kModelAttitude;
     drop_attached(ro);
-    return HJB_OK;
-}
-
-int32_t hjb_rollout_set_pos_att_model(void *rollout_x, void *rollout_y, void *rollout_z, const double *inertia, double mass,
-                                      double t_dist, double h, int32_t substeps, const double *rsw2eci, int32_t n_nodes,
-                                      const double *orbit_coef) {
-    Rollout *rx = (Rollout *)rollout_x, *ry = (Rollout *)rollout_y, *rz = (Rollout *)rollout_z;
-    // the arguments that need no object first (decided without a device), then the objects
-    if (!inertia || !rsw2eci || !orbit_coef) return rfail(rx, HJB_E_INVALID, "rollout: null argument (inertia, rsw2eci and orbit_coef are required)");
-    if (!all_finite(inertia, 9)) return rfail(rx, HJB_E_INVALID, "rollout: inertia is not finite");
-    if (!all_finite(rsw2eci, 9)) return rfail(rx, HJB_E_INVALID, "rollout: rsw2eci is not finite");
-    if (!(std::isfinite(mass) && mass > 0)) return rfail(rx, HJB_E_INVALID, "rollout: mass = %g is not finite and > 0", mass);
-    if (!std::isfinite(t_dist)) return rfail(rx, HJB_E_INVALID, "rollout: t_dist = %g is not finite", t_dist);
-    if (!(std::isfinite(h) && h > 0)) return rfail(rx, HJB_E_INVALID, "rollout: h = %g is not finite and > 0", h);
-    if (substeps < 1) return rfail(rx, HJB_E_INVALID, "rollout: substeps = %d < 1", substeps);
-    if (n_nodes < 1 || (n_nodes - 1) % (2 * (int64_t)substeps) != 0)
-        return rfail(rx, HJB_E_INVALID, "rollout: n_nodes = %d is not 2 * substeps * k + 1 (substeps = %d)", n_nodes, substeps);
-    const int64_t bad = first_nonfinite(orbit_coef, 5 * (int64_t)n_nodes, true);
-    if (bad >= 0) return rfail(rx, HJB_E_INVALID, "rollout: orbit_coef element %lld is not finite", (long long)bad);
-    DPosAtt M{};
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {                       // column-major in, row-major kept
-            M.J[3 * r + c] = inertia[r + 3 * c];
-            M.RSW[3 * r + c] = rsw2eci[r + 3 * c];
-        }
-    const double dj = pa_det3(M.J), dr = pa_det3(M.RSW);
-    if (!(std::isfinite(dj) && dj != 0.0)) return rfail(rx, HJB_E_INVALID, "rollout: inertia is singular (determinant %g)", dj);
-    if (!(std::isfinite(dr) && dr != 0.0)) return rfail(rx, HJB_E_INVALID, "rollout: rsw2eci is singular (determinant %g)", dr);
-    pa_inv3(M.J, M.Jinv);
-    pa_inv3(M.RSW, M.RSWinv);
-    if (!all_finite(M.Jinv, 9)) return rfail(rx, HJB_E_INVALID, "rollout: inertia is singular (its inverse is not finite)");
-    if (!all_finite(M.RSWinv, 9)) return rfail(rx, HJB_E_INVALID, "rollout: rsw2eci is singular (its inverse is not finite)");
-    M.mass = mass;
-    M.t_dist = t_dist;
-    M.hs = h / substeps;
-    M.substeps = substeps;
-    auto pa = std::make_unique<PosAtt>();
-    pa->M = M;
-    pa->h = h;
-    pa->max_steps = (int)((n_nodes - 1) / (2 * (int64_t)substeps));
-    std::unique_lock<std::mutex> g;
-    const int bad_chan = attach_channels({rx, ry, rz}, {"rollout_x", "rollout_y", "rollout_z"}, "pos-att", 4, 4, *pa, g);
-    if (bad_chan) return bad_chan;
-    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-    if (hipSetDevice(rx->device) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "hipSetDevice failed");
-    pa->coef = std::make_shared<DevData>();
-    pa->coef->device = rx->device;
-    const size_t cb = (size_t)5 * n_nodes * sizeof(double);
-    void *d = nullptr;
-    if (hipMalloc(&d, cb) != hipSuccess) return rfail(rx, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", cb);
-    pa->coef->allocs.push_back(d);
-    if (hipMemcpy(d, orbit_coef, cb, hipMemcpyHostToDevice) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "rollout: upload failed");
-    pa->M.coef = (const double *)d;
-    install_attached(rx, std::move(pa), kModelPosAtt);
-    return HJB_OK;
-}
-
-int32_t hjb_rollout_set_pos_att_fault_controller(void *rollout_x, void *rollout_xf) {
-    Rollout *rx = (Rollout *)rollout_x, *rf = (Rollout *)rollout_xf;
-    if (!rx) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    if (rx == rf) return rfail(rx, HJB_E_INVALID, "rollout: the same object passed as channel x and as its fault controller");
-    // the fault controller's snapshot first (its own lock), then channel x's lock
-    ChanSnap sf;
-    if (rf) sf = snap_channel(rf);
-    std::lock_guard<std::mutex> g(rx->mu);
-    if (rx->model != kModelPosAtt || !rx->att)
-        return rfail(rx, HJB_E_INVALID, "rollout: the fault controller attaches to the pos-att model: call hjb_rollout_set_pos_att_model first");
-    if (rf) {
-        if (sf.D != 4 || sf.n_u != 4)
-            return rfail(rx, HJB_E_INVALID, "rollout: the fault controller needs D == 4 and n_u == 4 (rollout_xf: D=%d, n_u=%d)", sf.D, sf.n_u);
-        const int bad = check_channel(rx, sf, "rollout_xf", "rollout_x", "four controllers");
-        if (bad) return bad;
-    }
-    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-    if (hipSetDevice(rx->device) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "hipSetDevice failed");
-    if (rx->stream) (void)hipStreamSynchronize(rx->stream);
-    PosAtt &pa = static_cast<PosAtt &>(*rx->att);
-    pa.has_xf = rf != nullptr;
-    pa.cxf = sf.c;
-    pa.data_xf = std::move(sf.data);                        // replaces (and releases) a fault controller attached earlier
-    pa.planes_xf = sf.n_planes;
-    return HJB_OK;
-}
-
-int32_t hjb_rollout_set_position_model(void *rollout_x, void *rollout_y, void *rollout_z, double tol, int32_t n_steps, int32_t max_sub,
-                                       const int32_t *n_sub, const double *table) {
-    Rollout *rx = (Rollout *)rollout_x, *ry = (Rollout *)rollout_y, *rz = (Rollout *)rollout_z;
-    // the arguments that need no object first (decided without a device), then the objects
-    if (!n_sub || !table) return rfail(rx, HJB_E_INVALID, "rollout: null argument (n_sub and table are required)");
-    if (!(std::isfinite(tol) && tol > 0)) return rfail(rx, HJB_E_INVALID, "rollout: tol = %g is not finite and > 0", tol);
-    if (n_steps < 1) return rfail(rx, HJB_E_INVALID, "rollout: n_steps = %d < 1 (the stages the table holds)", n_steps);
-    if (max_sub < 1 || max_sub > HJB_POS_MAX_SUB)
-        return rfail(rx, HJB_E_INVALID, "rollout: max_sub = %d not in 1..%d", max_sub, HJB_POS_MAX_SUB);
-    for (int k = 0; k < n_steps; ++k)
-        if (n_sub[k] < 1 || n_sub[k] > max_sub)
-            return rfail(rx, HJB_E_INVALID, "rollout: n_sub[%d] = %d not in 1..%d (max_sub)", k, n_sub[k], max_sub);
-    const int64_t n_tab = (int64_t)HJB_POS_ROW * max_sub * n_steps;
-    const int64_t bad = first_nonfinite(table, n_tab, true);
-    if (bad >= 0) return rfail(rx, HJB_E_INVALID, "rollout: table element %lld is not finite", (long long)bad);
-    auto ps = std::make_unique<Position>();
-    ps->M.tol = tol;
-    ps->M.max_sub = max_sub;
-    ps->max_steps = n_steps;
-    std::unique_lock<std::mutex> g;
-    const int bad_chan = attach_channels({rx, ry, rz}, {"rollout_x", "rollout_y", "rollout_z"}, "position", 2, 1, *ps, g);
-    if (bad_chan) return bad_chan;
-    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-    if (hipSetDevice(rx->device) != hipSuccess) return rfail(rx, HJB_E_DEVICE, "hipSetDevice failed");
-    ps->table = std::make_shared<DevData>();
-    ps->table->device = rx->device;
-    const size_t tb = (size_t)n_tab * sizeof(double), nb = (size_t)n_steps * sizeof(int32_t);
-    void *dt = nullptr, *dn = nullptr;
-    if (hipMalloc(&dt, tb) != hipSuccess) return rfail(rx, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", tb);
-    ps->table->allocs.push_back(dt);
-    if (hipMalloc(&dn, nb) != hipSuccess) return rfail(rx, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", nb);
-    ps->table->allocs.push_back(dn);
-    if (hipMemcpy(dt, table, tb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dn, n_sub, nb, hipMemcpyHostToDevice) != hipSuccess)
-        return rfail(rx, HJB_E_DEVICE, "rollout: upload failed");
-    ps->M.table = (const double *)dt;
-    ps->M.n_sub = (const int32_t *)dn;
-    install_attached(rx, std::move(ps), kModelPosition);
-    return HJB_OK;
-}
-
-int32_t hjb_rollout_set_attitude_simplified_model(void *rollout_1, void *rollout_2, void *rollout_3, const double *inertia, double h,
-                                                  int32_t substeps, int32_t dynamics, const double *qw, const double *qt,
-                                                  const double *r) {
-    Rollout *r1 = (Rollout *)rollout_1, *r2 = (Rollout *)rollout_2, *r3 = (Rollout *)rollout_3;
-    // the arguments that need no object first (decided without a device), then the objects
-    if (!inertia) return rfail(r1, HJB_E_INVALID, "rollout: null argument (inertia is required)");
-    if (!all_finite(inertia, 9)) return rfail(r1, HJB_E_INVALID, "rollout: inertia is not finite");
-    if (!(std::isfinite(h) && h > 0)) return rfail(r1, HJB_E_INVALID, "rollout: h = %g is not finite and > 0", h);
-    if (substeps < 1) return rfail(r1, HJB_E_INVALID, "rollout: substeps = %d < 1", substeps);
-    if (dynamics != HJB_ATTS_FULL && dynamics != HJB_ATTS_DIAGONAL)
-        return rfail(r1, HJB_E_INVALID, "rollout: dynamics %d is not HJB_ATTS_FULL / HJB_ATTS_DIAGONAL", dynamics);
-    if (dynamics == HJB_ATTS_DIAGONAL && substeps != 1)
-        return rfail(r1, HJB_E_INVALID, "rollout: substeps = %d with HJB_ATTS_DIAGONAL (one RK4 step per stage: substeps must be 1)", substeps);
-    if (!all_finite(qw, 3)) return rfail(r1, HJB_E_INVALID, "rollout: qw is not finite");
-    if (!all_finite(qt, 3)) return rfail(r1, HJB_E_INVALID, "rollout: qt is not finite");
-    if (!all_finite(r, 3)) return rfail(r1, HJB_E_INVALID, "rollout: r is not finite");
-    DAttSimplified M{};
-    for (int a = 0; a < 3; ++a)
-        for (int c = 0; c < 3; ++c) M.J[3 * a + c] = inertia[a + 3 * c];       // column-major in, row-major kept
-    const double dj = pa_det3(M.J);
-    if (!(std::isfinite(dj) && dj != 0.0)) return rfail(r1, HJB_E_INVALID, "rollout: inertia is singular (determinant %g)", dj);
-    pa_inv3(M.J, M.Jinv);
-    if (!all_finite(M.Jinv, 9)) return rfail(r1, HJB_E_INVALID, "rollout: inertia is singular (its inverse is not finite)");
-    const double J1 = M.J[0], J2 = M.J[4], J3 = M.J[8];
-    if (dynamics == HJB_ATTS_DIAGONAL && !(J1 > 0 && J2 > 0 && J3 > 0))
-        return rfail(r1, HJB_E_INVALID, "rollout: inertia has diagonal (%g, %g, %g), HJB_ATTS_DIAGONAL needs it > 0", J1, J2, J3);
-    M.A.h = h;
-    M.A.J[0] = J1;
-    M.A.J[1] = J2;
-    M.A.J[2] = J3;
-    M.A.c[0] = (J2 - J3) / J1;                        // as hjb_rollout_set_attitude_model forms them
-    M.A.c[1] = (J3 - J1) / J2;
-    M.A.c[2] = (J1 - J2) / J3;
-    if (qw) std::memcpy(M.qw, qw, sizeof M.qw);
-    if (qt) std::memcpy(M.qt, qt, sizeof M.qt);
-    if (r) std::memcpy(M.r, r, sizeof M.r);
-    M.hs = h / substeps;
-    M.substeps = substeps;
-    auto as = std::make_unique<AttSimplified>();
-    as->M = M;
-    as->dynamics = dynamics;
-    std::unique_lock<std::mutex> g;
-    const int bad_chan = attach_channels({r1, r2, r3}, {"rollout_1", "rollout_2", "rollout_3"}, "simplified attitude", 2, 1, *as, g);
-    if (bad_chan) return bad_chan;
-    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-    if (hipSetDevice(r1->device) != hipSuccess) return rfail(r1, HJB_E_DEVICE, "hipSetDevice failed");
-    install_attached(r1, std::move(as), kModelAttSimplified);
     return HJB_OK;
 }
 
@@ -802,13 +408,11 @@ int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const in
     const int D = ro->D;
     const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
     if (bad_traj) return bad_traj;
-    const int idx_bytes = ro->idx_bytes;
-    return run_chunks(ro, "hjb_rollout_run", D, ro->R.n_u, 0, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, nullptr, nullptr,
-                      device_ms,
-                      [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t st, double *dX0, double *dXf, double *dC,
-                          double *dXp, double *dUp, double *, int32_t *) {
-                          return launch_rollout(idx_bytes, method, lds_on, D, R, nc, lds, st, dX0, dXf, dC, dXp, dUp);
-                      });
+    ChunkPlan plan{"hjb_rollout_run", D, n_steps, plane_of_step, n_traj, X0, X_final,
+                   {{X_path, D, n_steps + 1}, {U_path, ro->R.n_u, n_steps}}, cost, device_ms};
+    return run_chunks(ro, plan, [&](const Chunk &c) {
+        return launch_rollout(ro->idx_bytes, method, c.lds_on, D, c.R, c.nc, c.lds, c.st, c.X0, c.Xf, c.cost, c.path[0], c.path[1]);
+    });
 }
 
 int32_t hjb_rollout_set_noise(void *rollout, int32_t n_nodes, const double *offsets, const double *weights) {
@@ -844,14 +448,10 @@ int32_t hjb_rollout_set_noise(void *rollout, int32_t n_nodes, const double *offs
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
     std::shared_ptr<DevData> nd;
-    void *d = nullptr;
+    const void *d = nullptr;
     if (n_nodes > 0) {
-        nd = std::make_shared<DevData>();
-        nd->device = ro->device;
-        const size_t tb = tab.size() * sizeof(double);
-        if (hipMalloc(&d, std::max<size_t>(tb, 16)) != hipSuccess) return rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", tb);
-        nd->allocs.push_back(d);
-        if (tb && hipMemcpy(d, tab.data(), tb, hipMemcpyHostToDevice) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "rollout: upload failed");
+        nd = std::make_shared<DevData>(ro->device);
+        if (const int st = upload(ro, *nd, tab.data(), tab.size() * sizeof(double), &d)) return st;
     }
     if (ro->stream) (void)hipStreamSynchronize(ro->stream);
     ro->noise = std::move(nd);                                // replaces (and releases) a node set given earlier
@@ -886,26 +486,18 @@ int32_t hjb_rollout_run_noisy(void *rollout, int32_t method, int32_t n_steps, co
     const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
     if (bad_traj) return bad_traj;
     if (device_ms) *device_ms = 0.0;
-    const int idx_bytes = ro->idx_bytes;
-    const bool lds_wanted = ro->lds;
     DNoise N = ro->N;
     N.seed = seed;
-    int64_t chunk_i0 = 0;                                     // the chunk's offset in the call: streams count through the call
-    return run_chunks(ro, "hjb_rollout_run_noisy", D, ro->R.n_u, 1, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, W_path,
-                      nullptr, device_ms,
-                      [&](const DRollout &R, int64_t nc, size_t lds, bool, hipStream_t st, double *dX0, double *dXf, double *dC, double *dXp,
-                          double *dUp, double *dWp, int32_t *) {
-                          DNoise Nc = N;
-                          Nc.first = (uint64_t)first_stream + (uint64_t)chunk_i0;
-                          Nc.Wp = dWp;
-                          const size_t lds_all = lds + (size_t)N.n_tab * sizeof(double);
-                          return launch_rollout_noisy(idx_bytes, method, lds_wanted && lds_all <= kLdsMax, D, R, Nc, nc, lds_all, st, dX0,
-                                                      dXf, dC, dXp, dUp);
-                      },
-                      [&](int64_t i0, int64_t, hipStream_t) {
-                          chunk_i0 = i0;
-                          return hipSuccess;
-                      });
+    ChunkPlan plan{"hjb_rollout_run_noisy", D, n_steps, plane_of_step, n_traj, X0, X_final,
+                   {{X_path, D, n_steps + 1}, {U_path, ro->R.n_u, n_steps}, {W_path, 1, n_steps}}, cost, device_ms};
+    return run_chunks(ro, plan, [&](const Chunk &c) {
+        DNoise Nc = N;
+        Nc.first = (uint64_t)first_stream + (uint64_t)c.i0;   // the chunk's offset in the call: streams count through the call
+        Nc.Wp = c.path[2];
+        const size_t lds_all = c.lds + (size_t)N.n_tab * sizeof(double);
+        return launch_rollout_noisy(ro->idx_bytes, method, ro->lds && lds_all <= kLdsMax, D, c.R, Nc, c.nc, lds_all, c.st, c.X0, c.Xf, c.cost,
+                                    c.path[0], c.path[1]);
+    });
 }
 
 int32_t hjb_rollout_noise_table(int32_t n_nodes, const double *weights, double *thresholds) {
@@ -960,17 +552,14 @@ int32_t hjb_rollout_set_values(void *rollout, int32_t dtype, int32_t n_planes, c
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
     std::shared_ptr<DevData> vd;
-    void *d = nullptr;
+    const void *d = nullptr;
     if (n_planes > 0) {
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipMemGetInfo failed");
         if (bytes + ((size_t)64 << 20) > fr)
             return rfail(ro, HJB_E_NOMEM, "%s: %zu bytes of value planes, %zu free on device %d", who, bytes, fr, ro->device);
-        vd = std::make_shared<DevData>();
-        vd->device = ro->device;
-        if (hipMalloc(&d, std::max<size_t>(bytes, 16)) != hipSuccess) return rfail(ro, HJB_E_NOMEM, "rollout: hipMalloc of %zu bytes failed", bytes);
-        vd->allocs.push_back(d);
-        if (hipMemcpy(d, values, bytes, hipMemcpyHostToDevice) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "rollout: upload failed");
+        vd = std::make_shared<DevData>(ro->device);
+        if (const int st = upload(ro, *vd, values, bytes, &d)) return st;
     }
     if (ro->stream) (void)hipStreamSynchronize(ro->stream);
     ro->values = std::move(vd);                               // replaces (and releases) planes given earlier
@@ -1010,40 +599,23 @@ int32_t hjb_rollout_run_greedy(void *rollout, int32_t n_steps, const int32_t *va
     const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
     if (bad_traj) return bad_traj;
     if (device_ms) *device_ms = 0.0;
-    // the two per-step scalars share run_chunks' extra path rows: [L | V], each [n_traj, n_steps]; one of them asked for goes
-    // straight to its buffer, both go through one host block
-    const int n_e = (L_path ? 1 : 0) + (V_path ? 1 : 0);
-    const size_t per = (size_t)n_traj * (size_t)n_steps;
-    std::vector<double> both;
-    double *E_path = L_path ? L_path : V_path;
-    if (n_e == 2) {
-        both.resize(2 * per);
-        E_path = both.data();
-    }
-    const int val_bytes = ro->val_bytes;
-    const void *dvalues = ro->dvalues;
-    const int st = run_chunks(ro, who, D, ro->R.n_u, n_e, n_steps, value_plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, E_path,
-                              nullptr, device_ms,
-                              [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t s, double *dX0, double *dXf, double *dC,
-                                  double *dXp, double *dUp, double *dEp, int32_t *) {
-                                  DGreedy G{};
-                                  G.R = R;
-                                  G.values = dvalues;
-                                  G.nc = nc;
-                                  G.X0 = dX0;
-                                  G.Xf = dXf;
-                                  G.cost = dC;
-                                  G.Xp = dXp;
-                                  G.Up = dUp;
-                                  G.Lp = L_path ? dEp : nullptr;
-                                  G.Vp = V_path ? dEp + (L_path ? (size_t)nc * n_steps : 0) : nullptr;
-                                  return launch_rollout_greedy(val_bytes, lds_on, D, G, lds, s);
-                              });
-    if (st == HJB_OK && n_e == 2) {
-        std::memcpy(L_path, both.data(), per * sizeof(double));
-        std::memcpy(V_path, both.data() + per, per * sizeof(double));
-    }
-    return st;
+    ChunkPlan plan{who, D, n_steps, value_plane_of_step, n_traj, X0, X_final,
+                   {{X_path, D, n_steps + 1}, {U_path, ro->R.n_u, n_steps}, {L_path, 1, n_steps}, {V_path, 1, n_steps}}, cost,
+                   device_ms};
+    return run_chunks(ro, plan, [&](const Chunk &c) {
+        DGreedy G{};
+        G.R = c.R;
+        G.values = ro->dvalues;
+        G.nc = c.nc;
+        G.X0 = c.X0;
+        G.Xf = c.Xf;
+        G.cost = c.cost;
+        G.Xp = c.path[0];
+        G.Up = c.path[1];
+        G.Lp = c.path[2];
+        G.Vp = c.path[3];
+        return launch_rollout_greedy(ro->val_bytes, c.lds_on, D, G, c.lds, c.st);
+    });
 }
 
 int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
@@ -1061,17 +633,7 @@ int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots
     if (n_value_planes > 0 && !values) return rfail(nullptr, HJB_E_INVALID, "%s: null values with n_value_planes=%d", who, n_value_planes);
     if (n_steps < 0 || n_traj < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_steps=%d, n_traj=%lld (both >= 0)", who, n_steps, (long long)n_traj);
     int64_t nS = 1, n_knots = 0;
-    for (int a = 0; a < D; ++a) {
-        if (n[a] < 2) return rfail(nullptr, HJB_E_INVALID, "%s: axis %d has %d knots (need >= 2)", who, a, n[a]);
-        const double *kk = knots + n_knots;
-        for (int i = 0; i < n[a]; ++i)
-            if (!std::isfinite(kk[i])) return rfail(nullptr, HJB_E_INVALID, "%s: knot %d of axis %d is not finite", who, i, a);
-        for (int i = 0; i + 1 < n[a]; ++i)
-            if (!(kk[i + 1] > kk[i])) return rfail(nullptr, HJB_E_INVALID, "%s: knots of axis %d not strictly increasing (at %d)", who, a, i);
-        n_knots += n[a];
-        if (n_knots > INT32_MAX || nS > kMaxStates / n[a]) return rfail(nullptr, HJB_E_INVALID, "%s: size overflow (grid)", who);
-        nS *= n[a];
-    }
+    if (const int bad_grid = check_grid(who, D, n, knots, &nS, &n_knots)) return bad_grid;
     if (!all_finite(u_table, (int64_t)n_labels * n_u)) return rfail(nullptr, HJB_E_INVALID, "%s: u_table is not finite", who);
     if (!all_finite(A, (int64_t)D * D) || !all_finite(B, (int64_t)D * n_u) || !all_finite(c, D) || !all_finite(q, D) || !all_finite(r, n_u))
         return rfail(nullptr, HJB_E_INVALID, "%s: the model (A, B, c, q, r) is not finite", who);
@@ -1116,191 +678,13 @@ int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps,
     int bad_traj = check_traj(ro, "rollout", HJB_ATT_W, "7", n_steps, n_traj, X0, X_final);
     if (!bad_traj) bad_traj = check_quaternions(ro, "rollout", n_traj, X0);
     if (bad_traj) return bad_traj;
-    const int idx_bytes = ro->idx_bytes, integ = ro->integrator;
     const DAttitude M = ro->M;
-    return run_chunks(ro, "hjb_rollout_run_attitude", HJB_ATT_W, HJB_ATT_U, 3, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path,
-                      A_path, nullptr, device_ms,
-                      [&](const DRollout &R, int64_t nc, size_t lds, bool lds_on, hipStream_t st, double *dX0, double *dXf, double *dC,
-                          double *dXp, double *dUp, double *dAp, int32_t *) {
-                          return launch_rollout_attitude(idx_bytes, method, lds_on, integ, R, M, nc, lds, st, dX0, dXf, dC, dXp, dUp, dAp);
-                      });
-}
-
-int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
-                                double *X_final, double *X_path, double *F_path, double *FM_path) {
-    Rollout *ro = (Rollout *)rollout_x;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    const int bad_arg = check_run(ro, kModelPosAtt, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    const PosAtt &pa = static_cast<const PosAtt &>(*ro->att);
-    if (n_steps > pa.max_steps)
-        return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the orbit table covers %d stages ((n_nodes - 1) / (2 substeps))", n_steps,
-                     pa.max_steps);
-    if (n_traj == 0) return HJB_OK;
-    const int bad_traj = check_traj(ro, "rollout", HJB_PA_W, "13", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    const int idx_bytes = ro->idx_bytes;
-    const DPaChan cx0 = pa_channel(ro->R);
-    const size_t lds3 = lds_bytes({&cx0, &pa.c[0], &pa.c[1]}, 4);
-    const bool lds3_on = ro->lds && lds3 <= kLdsMax;
-    return run_chunks(ro, "hjb_rollout_run_pos_att", HJB_PA_W, HJB_PA_F, HJB_PA_FM, n_steps, plane_of_step, n_traj, X0, X_final, nullptr,
-                      X_path, F_path, FM_path, nullptr, nullptr,
-                      [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *, double *dXp,
-                          double *dFp, double *dFMp, int32_t *) {
-                          const int32_t *pl = R.plane_of_step;
-                          DPosAtt M = pa.M;
-                          M.n_steps = R.n_steps;
-                          return launch_rollout_pos_att(idx_bytes, lds3_on, on_planes(cx0, pl), on_planes(pa.c[0], pl), on_planes(pa.c[1], pl),
-                                                        M, nc, lds3, st, dX0, dXf, dXp, dFp, dFMp);
-                      });
-}
-
-int32_t hjb_rollout_run_pos_att_faults(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
-                                       const double *X0, const int32_t *fault_mask, const int32_t *fault_stage,
-                                       const int32_t *switch_stage, double pos_tol, double att_tol, double *X_final, double *impulse,
-                                       int32_t *settle_stage, double *X_path, double *F_path, double *FM_path, double *device_ms) {
-    Rollout *ro = (Rollout *)rollout_x;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    // every refusal before any device work, the outputs untouched
-    const int bad_arg = check_run(ro, kModelPosAtt, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    const PosAtt &pa = static_cast<const PosAtt &>(*ro->att);
-    if (n_steps > pa.max_steps)
-        return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the orbit table covers %d stages ((n_nodes - 1) / (2 substeps))", n_steps,
-                     pa.max_steps);
-    if (pa.has_xf)
-        for (int k = 0; k < n_steps; ++k)
-            if (plane_of_step[k] >= pa.planes_xf)
-                return rfail(ro, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d) (the fault controller's planes)", k,
-                             plane_of_step[k], pa.planes_xf);
-    if (!(pos_tol >= 0)) return rfail(ro, HJB_E_INVALID, "rollout: pos_tol = %g is NaN or negative", pos_tol);
-    if (!(att_tol >= 0)) return rfail(ro, HJB_E_INVALID, "rollout: att_tol = %g is NaN or negative", att_tol);
-    if (n_traj == 0) {
-        if (device_ms) *device_ms = 0.0;
-        return HJB_OK;
-    }
-    const int bad_traj = check_traj(ro, "rollout", HJB_PA_W, "13", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    for (int64_t i = 0; i < n_traj; ++i) {
-        if (fault_mask && (fault_mask[i] & ~0xFFF))
-            return rfail(ro, HJB_E_INVALID, "rollout: fault_mask[%lld] = 0x%x has a bit above 11 (twelve thrusters)", (long long)i,
-                         (unsigned)fault_mask[i]);
-        if (fault_stage && fault_stage[i] < 0)
-            return rfail(ro, HJB_E_INVALID, "rollout: fault_stage[%lld] = %d < 0", (long long)i, fault_stage[i]);
-        if (switch_stage && switch_stage[i] < 0)
-            return rfail(ro, HJB_E_INVALID, "rollout: switch_stage[%lld] = %d < 0", (long long)i, switch_stage[i]);
-        if (switch_stage && switch_stage[i] < n_steps && !pa.has_xf)
-            return rfail(ro, HJB_E_INVALID, "rollout: switch_stage[%lld] = %d hands over within the %d stages, but no fault controller is "
-                         "attached (hjb_rollout_set_pos_att_fault_controller)", (long long)i, switch_stage[i], n_steps);
-    }
-    const int idx_bytes = ro->idx_bytes;
-    const DPaChan cx0 = pa_channel(ro->R);
-    const size_t lds4 = lds_bytes({&cx0, &pa.c[0], &pa.c[1], &pa.cxf}, 4);
-    const bool lds4_on = ro->lds && lds4 <= kLdsMax;
-    DPaFault Q{};
-    Q.h = pa.h;
-    Q.p2 = pos_tol * pos_tol;
-    Q.a2 = att_tol * att_tol;
-    // the per-trajectory inputs on the device: allocated at the first chunk (for the largest), uploaded per chunk at its offset
-    const int32_t *const host_in[3] = {fault_mask, fault_stage, switch_stage};
-    int32_t *dev_in[3] = {nullptr, nullptr, nullptr};
-    const int64_t nc_max = std::min(n_traj, ro->chunk);
-    const int st = run_chunks(ro, "hjb_rollout_run_pos_att_faults", HJB_PA_W, HJB_PA_F, HJB_PA_FM, n_steps, plane_of_step, n_traj, X0, X_final,
-                              impulse, X_path, F_path, FM_path, settle_stage, device_ms,
-                              [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t s, double *dX0, double *dXf, double *dImp, double *dXp,
-                                  double *dFp, double *dFMp, int32_t *dSettle) {
-                                  const int32_t *pl = R.plane_of_step;
-                                  DPosAtt M = pa.M;
-                                  M.n_steps = R.n_steps;
-                                  DPaFault Qc = Q;
-                                  Qc.mask = dev_in[0];
-                                  Qc.fault_stage = dev_in[1];
-                                  Qc.switch_stage = dev_in[2];
-                                  Qc.impulse = dImp;
-                                  Qc.settle = dSettle;
-                                  return launch_rollout_pos_att_faults(idx_bytes, lds4_on, on_planes(cx0, pl), on_planes(pa.c[0], pl),
-                                                                       on_planes(pa.c[1], pl), on_planes(pa.cxf, pl), M, Qc, nc, lds4, s,
-                                                                       dX0, dXf, dXp, dFp, dFMp);
-                              },
-                              [&](int64_t i0, int64_t nc, hipStream_t s) {
-                                  for (int t = 0; t < 3; ++t) {
-                                      if (!host_in[t]) continue;
-                                      hipError_t e = hipSuccess;
-                                      if (!dev_in[t]) e = hipMalloc((void **)&dev_in[t], (size_t)nc_max * sizeof(int32_t));
-                                      if (e == hipSuccess)
-                                          e = hipMemcpyAsync(dev_in[t], host_in[t] + i0, (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, s);
-                                      if (e != hipSuccess) return e;
-                                  }
-                                  return hipSuccess;
-                              });
-    {
-        std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-        (void)hipSetDevice(ro->device);
-        for (int32_t *p : dev_in)
-            if (p) (void)hipFree(p);
-    }
-    return st;
-}
-
-int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
-                                 double *X_final, double *X_path, double *A_path, int32_t *off_schedule) {
-    Rollout *ro = (Rollout *)rollout_x;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    const int bad_arg = check_run(ro, kModelPosition, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    const Position &ps = static_cast<const Position &>(*ro->att);
-    if (n_steps > ps.max_steps)
-        return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the RKF45 table covers %d stages", n_steps, ps.max_steps);
-    if (n_traj == 0) return HJB_OK;
-    // this entry point's own null check (off_schedule is required): check_traj's of X0 / X_final cannot fire after it
-    if (!X0 || !X_final || !off_schedule) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final / off_schedule");
-    const int bad_traj = check_traj(ro, "rollout", HJB_POS_W, "6", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    const int idx_bytes = ro->idx_bytes;
-    const DPaChan cx0 = pa_channel(ro->R);
-    const size_t lds3 = lds_bytes({&cx0, &ps.c[0], &ps.c[1]}, 1);
-    const bool lds3_on = ro->lds && lds3 <= kLdsMax;
-    return run_chunks(ro, "hjb_rollout_run_position", HJB_POS_W, HJB_POS_A, 0, n_steps, plane_of_step, n_traj, X0, X_final, nullptr,
-                      X_path, A_path, nullptr, off_schedule, nullptr,
-                      [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *, double *dXp,
-                          double *dAp, double *, int32_t *dOff) {
-                          const int32_t *pl = R.plane_of_step;
-                          DPosition M = ps.M;
-                          M.n_steps = R.n_steps;
-                          return launch_rollout_position(idx_bytes, lds3_on, on_planes(cx0, pl), on_planes(ps.c[0], pl), on_planes(ps.c[1], pl),
-                                                         M, nc, lds3, st, dX0, dXf, dXp, dAp, dOff);
-                      });
-}
-
-int32_t hjb_rollout_run_attitude_simplified(void *rollout_1, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
-                                            const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
-                                            double *A_path) {
-    Rollout *ro = (Rollout *)rollout_1;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    const int bad_arg = check_run(ro, kModelAttSimplified, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    const AttSimplified &as = static_cast<const AttSimplified &>(*ro->att);
-    if (n_traj == 0) return HJB_OK;
-    const int bad_traj = check_traj(ro, "rollout", HJB_ATT_W, "7", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    const int idx_bytes = ro->idx_bytes;
-    const DPaChan c10 = pa_channel(ro->R);
-    const size_t lds3 = lds_bytes({&c10, &as.c[0], &as.c[1]}, 1);
-    const bool lds3_on = ro->lds && lds3 <= kLdsMax;
-    return run_chunks(ro, "hjb_rollout_run_attitude_simplified", HJB_ATT_W, HJB_ATT_U, 3, n_steps, plane_of_step, n_traj, X0, X_final, cost,
-                      X_path, U_path, A_path, nullptr, nullptr,
-                      [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t st, double *dX0, double *dXf, double *dC, double *dXp,
-                          double *dUp, double *dAp, int32_t *) {
-                          const int32_t *pl = R.plane_of_step;
-                          DAttSimplified M = as.M;
-                          M.n_steps = R.n_steps;
-                          return launch_rollout_attitude_simplified(idx_bytes, lds3_on, as.dynamics, on_planes(c10, pl), on_planes(as.c[0], pl),
-                                                                    on_planes(as.c[1], pl), M, nc, lds3, st, dX0, dXf, dC, dXp, dUp, dAp);
-                      });
+    ChunkPlan plan{"hjb_rollout_run_attitude", HJB_ATT_W, n_steps, plane_of_step, n_traj, X0, X_final,
+                   {{X_path, HJB_ATT_W, n_steps + 1}, {U_path, HJB_ATT_U, n_steps}, {A_path, 3, n_steps}}, cost, device_ms};
+    return run_chunks(ro, plan, [&](const Chunk &c) {
+        return launch_rollout_attitude(ro->idx_bytes, method, c.lds_on, ro->integrator, c.R, M, c.nc, c.lds, c.st, c.X0, c.Xf, c.cost, c.path[0],
+                                       c.path[1], c.path[2]);
+    });
 }
 
 int32_t hjb_attitude_linear_response(int32_t device, const double *inertia, double h, int32_t integrator, const double *K,
@@ -1336,14 +720,7 @@ int32_t hjb_attitude_linear_response(int32_t device, const double *inertia, doub
     if (!bad_traj) bad_traj = check_quaternions(nullptr, who, n_traj, X0);
     if (bad_traj) return bad_traj;
     DAttLinear M{};
-    M.A.h = h;
-    const double J1 = inertia[0], J2 = inertia[1], J3 = inertia[2];
-    M.A.J[0] = J1;
-    M.A.J[1] = J2;
-    M.A.J[2] = J3;
-    M.A.c[0] = (J2 - J3) / J1;                        // as hjb_rollout_set_attitude_model forms them
-    M.A.c[1] = (J3 - J1) / J2;
-    M.A.c[2] = (J1 - J2) / J3;
+    M.A = euler_attitude(inertia[0], inertia[1], inertia[2], h);
     for (int r = 0; r < 3; ++r) {
         for (int c = 0; c < 3; ++c) {                 // column-major in, row-major kept
             M.K[3 * r + c] = K[r + 3 * c];
@@ -1371,14 +748,13 @@ int32_t hjb_attitude_linear_response(int32_t device, const double *inertia, doub
             return rfail(nullptr, HJB_E_DEVICE, "%s: stream creation failed", who);
         }
     }
-    const int st = run_chunks(&ro, who, HJB_ATT_W, HJB_ATT_U, 3, n_steps, nullptr, n_traj, X0, X_final, cost, X_path, U_path, A_path,
-                              nullptr, device_ms,
-                              [&](const DRollout &R, int64_t nc, size_t, bool, hipStream_t s, double *dX0, double *dXf, double *dC,
-                                  double *dXp, double *dUp, double *dAp, int32_t *) {
-                                  DAttLinear Mk = M;
-                                  Mk.n_steps = R.n_steps;
-                                  return launch_rollout_attitude_linear(integrator, cost_form, Mk, nc, s, dX0, dXf, dC, dXp, dUp, dAp);
-                              });
+    ChunkPlan plan{who, HJB_ATT_W, n_steps, nullptr, n_traj, X0, X_final,
+                   {{X_path, HJB_ATT_W, n_steps + 1}, {U_path, HJB_ATT_U, n_steps}, {A_path, 3, n_steps}}, cost, device_ms};
+    const int st = run_chunks(&ro, plan, [&](const Chunk &c) {
+        DAttLinear Mk = M;
+        Mk.n_steps = c.R.n_steps;
+        return launch_rollout_attitude_linear(integrator, cost_form, Mk, c.nc, c.st, c.X0, c.Xf, c.cost, c.path[0], c.path[1], c.path[2]);
+    });
     {
         std::shared_lock<std::shared_mutex> lk(g_capture_mu);
         (void)hipSetDevice(device);

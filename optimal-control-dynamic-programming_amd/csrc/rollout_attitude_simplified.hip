@@ -1,5 +1,5 @@
 // rollout_attitude_simplified.hip - K20's 12 instantiations (kernels_rollout_attitude_simplified.h: label type x LDS x dynamics)
-// in a unit of their own, behind launch_rollout_attitude_simplified (called by hjb_rollout_run_attitude_simplified in rollout.hip).
+// in a unit of their own, behind launch_rollout_attitude_simplified (called by hjb_rollout_run_attitude_simplified in rollout_channels.hip).
 #include "kernels_rollout_attitude_simplified.h"
 #include "rollout_dispatch.h"
 

@@ -1,5 +1,5 @@
 // rollout_pos_att.hip - K18's 6 instantiations (kernels_rollout_pos_att.h: label type x LDS) in a unit of their own, behind
-// launch_rollout_pos_att (called by hjb_rollout_run_pos_att in rollout.hip).
+// launch_rollout_pos_att (called by hjb_rollout_run_pos_att in rollout_channels.hip).
 #include "kernels_rollout_pos_att.h"
 #include "rollout_dispatch.h"
 

@@ -1,5 +1,5 @@
 // rollout_pos_att_faults.hip - K23's 6 instantiations (kernels_rollout_pos_att_faults.h: label type x LDS) in a unit of their own,
-// behind launch_rollout_pos_att_faults (called by hjb_rollout_run_pos_att_faults in rollout.hip).
+// behind launch_rollout_pos_att_faults (called by hjb_rollout_run_pos_att_faults in rollout_channels.hip).
 #include "kernels_rollout_pos_att_faults.h"
 #include "rollout_dispatch.h"
 

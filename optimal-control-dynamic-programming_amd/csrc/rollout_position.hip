@@ -1,5 +1,5 @@
 // rollout_position.hip - K19's 6 instantiations (kernels_rollout_position.h: label type x LDS) in a unit of their own, behind
-// launch_rollout_position (called by hjb_rollout_run_position in rollout.hip).
+// launch_rollout_position (called by hjb_rollout_run_position in rollout_channels.hip).
 #include "kernels_rollout_position.h"
 #include "rollout_dispatch.h"
 

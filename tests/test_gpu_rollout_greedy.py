@@ -75,6 +75,46 @@ def test_a_table_too_large_for_lds_falls_back_to_global_memory(built):
             check_bits(ro.run_greedy(X0, [1, 0], keep_path=True), ref, lds)
 
 
+def test_l_path_and_v_path_each_on_its_own_chunked_and_not(built):
+    """hjb_rollout_run_greedy through ctypes (hjbdp.Rollout.run_greedy asks for L_path and V_path together or not at all): L_path
+    only, V_path only, both and neither, at chunk = 100 (100 + 100 + 57) and unchunked.  Every array asked for is bit-equal to
+    run_greedy(keep_path=True)'s; one not asked for keeps the sentinel it was filled with."""
+    import ctypes as C
+    import hjbdp
+    SENT = -12345.678
+    rng = np.random.default_rng(2627)                                  # (a seed at which the chosen labels vary: asserted below)
+    knots, ut, A, B, c, q, r, V = refs.random_problem(rng, 2, 2, 7, 3, np.float64)
+    X0 = refs.starts(rng, knots, 257)
+    planes = np.array([2, 0, -1, 1, 1], dtype=np.int32)
+    nt, K = 257, int(planes.size)
+    X = np.ascontiguousarray(X0.T, dtype=np.float64)
+    f64p = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    with hjbdp.Rollout(knots, _labels_stub(knots, 7, 1), ut, index_base=1) as ro:
+        ro.set_model(A, B, c=c, q=q, r=r)
+        ro.set_values(V)
+        full = ro.run_greedy(X0, planes, keep_path=True)
+        assert len(np.unique(full["L_path"])) > 1 and len(np.unique(full["V_path"])) > 1        # (neither path is constant)
+        for chunk in (100, 1 << 20):
+            ro.set_option("chunk", chunk)
+            for want in (("L_path",), ("V_path",), ("L_path", "V_path"), ()):
+                out = {"X_final": np.full((nt, 2), SENT), "cost": np.full(nt, SENT), "X_path": np.full(nt * 2 * (K + 1), SENT),
+                       "U_path": np.full(nt * 2 * K, SENT), "L_path": np.full(nt * K, SENT), "V_path": np.full(nt * K, SENT)}
+                opt = lambda key: f64p(out[key]) if key in want else None
+                st = ro.lib.hjb_rollout_run_greedy(ro._ro, K, planes.ctypes.data_as(C.POINTER(C.c_int32)), nt, f64p(X),
+                                                   f64p(out["X_final"]), f64p(out["cost"]), f64p(out["X_path"]), f64p(out["U_path"]),
+                                                   opt("L_path"), opt("V_path"), None)
+                assert st == 0, (chunk, want)
+                assert _same(out["X_final"].T, full["X_final"]) and _same(out["cost"], full["cost"]), (chunk, want)
+                assert _same(out["X_path"].reshape((nt, 2, K + 1), order="F"), full["X_path"]), (chunk, want)
+                assert _same(out["U_path"].reshape((nt, 2, K), order="F"), full["U_path"]), (chunk, want)
+                for key in ("L_path", "V_path"):
+                    got = out[key].reshape((nt, K), order="F")
+                    if key in want:
+                        assert _same(got, full[key].astype(np.float64)), (chunk, want, key)
+                    else:
+                        assert (got == SENT).all(), (chunk, want, key)
+
+
 # ---- 2. one step of the lookahead is the Bellman backup -----------------------------------------------------------------------------
 @pytest.mark.parametrize("variant", [0, None])
 def test_one_step_at_every_grid_node_is_the_backup(built, variant):

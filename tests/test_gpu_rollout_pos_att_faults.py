@@ -229,6 +229,27 @@ def test_chunking_and_optional_outputs(general):
         assert st == 0 and none["device_ms"] == 0.0
 
 
+def test_omitted_per_trajectory_inputs_chunked(general):
+    """chunk = 100 with 257 starts and fault_mask, fault_stage and switch_stage omitted (NULL) one at a time, then all three: every
+    output equals the same call unchunked (a NULL array skipped at the wrong place among the per-trajectory inputs shows here and
+    nowhere else); each single omission flies another campaign than the general case; with all three omitted X_final is
+    hjb_rollout_run_pos_att's"""
+    chans, fault, X0, planes, mask, f_at, s_at, per_S = general["uint16"]
+    rsw, coef, pos_tol, att_tol, tw = per_S[1]
+    given = {"fault_mask": mask, "fault_stage": f_at, "switch_stage": s_at}
+    with _Four(chans + [fault]) as (rx, ry, rz, rf):
+        rx.set_pos_att_model(ry, rz, INERTIA, MASS, T_DIST, H, rsw, coef, 1)
+        rx.set_pos_att_fault_controller(rf)
+        for omit in (("fault_mask",), ("fault_stage",), ("switch_stage",), tuple(given)):
+            kw = {k: v for k, v in given.items() if k not in omit}
+            rx.set_option("chunk", 1 << 20)
+            whole = rx.run_pos_att_faults(X0, planes, pos_tol=pos_tol, att_tol=att_tol, keep_path=True, **kw)
+            assert not _same(whole["F_path"], tw["F_path"]), omit
+            rx.set_option("chunk", 100)
+            _check(rx.run_pos_att_faults(X0, planes, pos_tol=pos_tol, att_tol=att_tol, keep_path=True, **kw), whole)
+        assert _same(whole["X_final"], rx.run_pos_att(X0, planes)["X_final"])
+
+
 def test_starts_that_overflow_during_the_run(built):
     """the K18 test's overflowing starts (position 1e300, rate 1e200, ...) with faults and hand-overs: the run completes, equals
     the twin (NaN = NaN) and reports the overflowed starts as never settled"""
