@@ -228,7 +228,9 @@ int32_t hjb_device_count(void);
  * the environment to change behaviour.  Keys: "fail_tab64_scratch" (value != 0: the float64 table build's scratch
  * allocation fails, so that hjb_create's refusal of an unservable HJB_TAB_F64 problem can be tested),
  * "fail_tabled_alloc" (the (cell, t) table allocation of the table-driven kernels fails: HJB_COST_F64's refusal),
- * "rccl_only_env" (the RCCL loader tries $HJBDP_RCCL_LIB only: a host without librccl). */
+ * "rccl_only_env" (the RCCL loader tries $HJBDP_RCCL_LIB only: a host without librccl),
+ * "fail_graph_capture" (host side only: the stage-loop graph capture of hjb_solve / hjb_solve_batch fails before any HIP
+ * call with HJB_E_DEVICE and "(test hook)" in the text; the handles stay usable). */
 int32_t hjb_test_hook(const char *key, int64_t value);
 
 /* Threading: a handle is not thread-safe - drive each handle from one host thread.  DIFFERENT handles may be

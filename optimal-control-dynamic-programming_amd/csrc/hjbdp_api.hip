@@ -1,4 +1,5 @@
-// hjbdp_api.hip - the single-device C ABI of libhjbdp (include/hjbdp.h): hjb_create .. hjb_solve, options, probe block, policy lookup.
+// hjbdp_api.hip - the single-device C ABI of libhjbdp (include/hjbdp.h): validation, hjb_create / hjb_destroy, options, one stage
+// (hjb_backup_stage*), the probe block, policy lookup, the test hook.  hjb_solve is hjbdp_solve.hip.
 // gfx950 (MI355X) only; no CPU fallback - without a HIP device every compute entry point returns HJB_E_DEVICE.
 #include "hjbdp_host.h"
 #include "kernels_lookup.h"
@@ -66,6 +67,7 @@ int32_t hjb_test_hook(const char *key, int64_t value) {
     if (!strcmp(key, "fail_tab64_scratch")) { g_test_fail_tab64_scratch.store(value != 0); return HJB_OK; }
     if (!strcmp(key, "fail_tabled_alloc")) { g_test_fail_tabled_alloc.store(value != 0); return HJB_OK; }
     if (!strcmp(key, "rccl_only_env")) { g_test_rccl_only_env.store(value != 0); return HJB_OK; }
+    if (!strcmp(key, "fail_graph_capture")) { g_test_fail_graph_capture.store(value != 0); return HJB_OK; }
     return fail(nullptr, HJB_E_INVALID, "hjb_test_hook: unknown key '%s'", key);
 }
 
@@ -553,247 +555,6 @@ int32_t hjb_backup_stage(hjb_handle hh, const void *J_next, void *J_out, void *i
     HIP_TRY(h, hipMemcpy(J_out, h->dJ[1], jb, hipMemcpyDeviceToHost));
     if (idx_out) HIP_TRY(h, hipMemcpy(idx_out, h->d_idx, (size_t)h->n_owned * h->idx_bytes, hipMemcpyDeviceToHost));
     return HJB_OK;
-}
-
-int32_t hjb_solve(hjb_handle hh, const hjb_solve_opts *o, hjb_result *res) {
-    Handle *h = (Handle *)hh;
-    if (!h || !o) return fail(h, HJB_E_INVALID, "null argument");
-    if (o->n_stages < 1) return fail(h, HJB_E_INVALID, "n_stages=%d", o->n_stages);
-    if (h->j_elems != h->n_owned)
-        return fail(h, HJB_E_UNSUPPORTED, "hjb_solve runs whole grids; drive slabs with hjb_backup_stage_device + a halo exchange");
-    if (o->probe && h->dist_nodes > 0)
-        return fail(h, HJB_E_UNSUPPORTED, "the probe block taps the nominal next state: not available while a disturbance is set (hjb_set_disturbance)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    std::shared_lock<std::shared_mutex> unsafe_lk(g_capture_mu);    // allocation, synchronous copies, device sync
-    int st = ensure_work(h);
-    if (st) return st;
-    const int64_t nS = h->n_owned;
-    const size_t jb = (size_t)nS * h->esz;
-    if (!h->stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    hipStream_t stream = h->stream;
-    // optional per-stage capture: kernels write straight into the stage planes
-    char *dJst = nullptr;
-    char *dIst = nullptr;
-    const size_t ib = (size_t)nS * h->idx_bytes;      // bytes of one plane of labels
-    if (o->J_stages) {
-        void *d = nullptr;
-        if (hipMalloc(&d, jb * o->n_stages) != hipSuccess) return fail(h, HJB_E_NOMEM, "cannot hold %d J stages on the device", o->n_stages);
-        dJst = (char *)d;
-        if (hipMemset(dJst, 0, jb * o->n_stages) != hipSuccess) { (void)hipFree(dJst); return fail(h, HJB_E_DEVICE, "hipMemset of the J stage planes failed"); }
-    }
-    if (o->idx_stages) {
-        void *d = nullptr;
-        if (hipMalloc(&d, ib * o->n_stages) != hipSuccess) {
-            if (dJst) (void)hipFree(dJst);
-            return fail(h, HJB_E_NOMEM, "cannot hold %d idx stages on the device", o->n_stages);
-        }
-        dIst = (char *)d;
-        if (hipMemset(dIst, 0, ib * o->n_stages) != hipSuccess) {
-            if (dJst) (void)hipFree(dJst);
-            (void)hipFree(dIst);
-            return fail(h, HJB_E_DEVICE, "hipMemset of the idx stage planes failed");
-        }
-    }
-    // optional probe block (the reference's debug taps): one plane of each requested output per stage
-    DProbe pr{};
-    char *dPg = nullptr, *dPx = nullptr, *dPj = nullptr;
-    const size_t tsz = h->dtype == HJB_F64 ? 8 : 4;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    auto cleanup = [&]() {
-        // hipFree is one of the calls a stream capture elsewhere in the process must not see: hold the shared lock
-        std::shared_lock<std::shared_mutex> lk(g_capture_mu, std::defer_lock);
-        if (!unsafe_lk.owns_lock()) lk.lock();
-        if (ev0) { (void)hipEventDestroy(ev0); ev0 = nullptr; }
-        if (ev1) { (void)hipEventDestroy(ev1); ev1 = nullptr; }
-        if (dJst) { (void)hipFree(dJst); dJst = nullptr; }
-        if (dIst) { (void)hipFree(dIst); dIst = nullptr; }
-        if (dPg) { (void)hipFree(dPg); dPg = nullptr; }
-        if (dPx) { (void)hipFree(dPx); dPx = nullptr; }
-        if (dPj) { (void)hipFree(dPj); dPj = nullptr; }
-    };
-    if (o->probe) {
-        st = make_probe(h, o->probe, &pr);
-        if (st) { cleanup(); return st; }
-        const size_t pb = (size_t)pr.B * tsz;
-        void *d = nullptr;
-        // zero-filled: planes of stages an early stop never runs come back as zeros, like J_stages / idx_stages
-        auto grab = [&](size_t bytes, char **out) {
-            if (hipMalloc(&d, bytes) != hipSuccess) return false;
-            *out = (char *)d;
-            return hipMemset(d, 0, bytes) == hipSuccess;
-        };
-        if (o->probe->g && !grab(pb * o->n_stages, &dPg)) { cleanup(); return fail(h, HJB_E_NOMEM, "probe buffers"); }
-        if (o->probe->x_next && !grab(pb * h->hp.D * o->n_stages, &dPx)) { cleanup(); return fail(h, HJB_E_NOMEM, "probe buffers"); }
-        if (o->probe->j_interp && !grab(pb * o->n_stages, &dPj)) { cleanup(); return fail(h, HJB_E_NOMEM, "probe buffers"); }
-    }
-    const bool every_stage = o->progress && o->progress_every_stage;
-#define SOLVE_TRY(expr)                                                                            \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            cleanup();                                                                             \
-            return fail(h, HJB_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-        }                                                                                          \
-    } while (0)
-    if (o->terminal) SOLVE_TRY(hipMemcpy(h->dJ[0], o->terminal, jb, hipMemcpyHostToDevice));
-    else SOLVE_TRY(hipMemset(h->dJ[0], 0, jb));
-    SOLVE_TRY(sync_setup());             // the sweep runs on the handle's own stream from here (other handles' sweeps are not waited for)
-    // launch-bound sweeps: replay kGraphStages ping-pong launches per hipGraphLaunch
-    const bool graph_ok = h->use_graph && !dJst && !dIst && !o->probe && !every_stage && o->n_stages >= 2 * kGraphStages;
-    // K9: several stages per launch for local 2-D problems (no per-stage outputs, no monitor read-backs)
-    bool tiled = false;
-    if (h->use_temporal && !h->cost64 && !dJst && !dIst && !o->probe && !every_stage && o->monitor_period <= 0 && o->n_stages >= 2 * kTileK && h->forced_variant < 0 && h->dist_nodes == 0) {
-        if (h->tile2d < 0) {
-            const int tst = examine_tile2d(h);
-            if (tst) { cleanup(); return tst; }
-        }
-        tiled = h->tile2d == 1;
-    }
-    if (h->use_temporal == 2 && !tiled) {
-        cleanup();
-        return fail(h, HJB_E_UNSUPPORTED, "option temporal=2: several stages per launch do not apply (needs D=2, whole grid, "
-                    "every query within one cell of its state, no per-stage outputs or monitor, no disturbance, >= %d stages)", 2 * kTileK);
-    }
-    if (h->gexec && h->gexec_tiled != tiled) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-    unsafe_lk.unlock();
-    if (graph_ok && !h->gexec) {
-        std::unique_lock<std::shared_mutex> capture_lk(g_capture_mu);
-        hipGraph_t graph = nullptr;
-        SOLVE_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        int cst = HJB_OK;
-        if (tiled) {          // kGraphStages = 4 launches of kTileK stages, ending in dJ[0]
-            static_assert(kGraphStages % (2 * kTileK) == 0, "a graph must hold an even number of tile launches");
-            for (int i = 0; i < kGraphStages / (2 * kTileK) && cst == HJB_OK; ++i) {
-                cst = launch_tile2d(h, h->dJ[0], h->dJ[1], h->d_idx, kTileK, stream);
-                if (cst == HJB_OK) cst = launch_tile2d(h, h->dJ[1], h->dJ[0], h->d_idx, kTileK, stream);
-            }
-        } else {
-            for (int i = 0; i < kGraphStages / 2 && cst == HJB_OK; ++i) {
-                cst = launch_stage(h, h->dJ[0], h->dJ[1], h->d_idx, stream);
-                if (cst == HJB_OK) cst = launch_stage(h, h->dJ[1], h->dJ[0], h->d_idx, stream);
-            }
-        }
-        h->gexec_tiled = tiled;
-        hipError_t ce = hipStreamEndCapture(stream, &graph);
-        if (cst != HJB_OK || ce != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            cleanup();
-            return fail(h, HJB_E_DEVICE, "stage-loop graph capture failed: %s", hipGetErrorString(ce));
-        }
-        ce = hipGraphInstantiate(&h->gexec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ce != hipSuccess) { cleanup(); return fail(h, HJB_E_DEVICE, "hipGraphInstantiate: %s", hipGetErrorString(ce)); }
-    }
-    SOLVE_TRY(hipEventCreate(&ev0));
-    SOLVE_TRY(hipEventCreate(&ev1));
-    SOLVE_TRY(hipEventRecord(ev0, stream));
-    const void *cur = h->dJ[0];
-    int pp = 1;  // next ping-pong target
-    const char *cur_idx = h->d_idx;
-    int done = 0, early = 0;
-    double fprev = 0, iprev = 0, e = 0, e2 = 0;
-    int k_s = o->n_stages;
-    while (k_s >= 1) {
-        // stages up to and including the next monitor point (or all of them)
-        int stop = 1;
-        if (o->monitor_period > 0) stop = std::max(1, (k_s / o->monitor_period) * o->monitor_period);
-        int run = k_s - stop + 1;
-        if (graph_ok && run >= kGraphStages) {
-            if (pp == 0) {   // make dJ[0] the current buffer: one eager stage
-                st = launch_stage(h, cur, h->dJ[pp], h->d_idx, stream);
-                if (st) { cleanup(); return st; }
-                cur = h->dJ[pp]; pp ^= 1; ++done; --run; --k_s;
-            }
-            while (run >= kGraphStages) {
-                SOLVE_TRY(hipGraphLaunch(h->gexec, stream));
-                done += kGraphStages; run -= kGraphStages; k_s -= kGraphStages;
-            }
-        }
-        while (tiled && run > 0) {                           // K9: up to kTileK stages per launch
-            const int K = std::min(run, kTileK);
-            st = launch_tile2d(h, cur, h->dJ[pp], h->d_idx, K, stream);
-            if (st) { cleanup(); return st; }
-            cur = h->dJ[pp];
-            cur_idx = h->d_idx;
-            pp ^= 1;
-            done += K; run -= K; k_s -= K;
-        }
-        for (; run > 0; --run, --k_s) {
-            void *outJ = dJst ? (void *)(dJst + (size_t)(k_s - 1) * jb) : h->dJ[pp];
-            char *outI = dIst ? dIst + (size_t)(k_s - 1) * ib : h->d_idx;
-            if (o->probe) {                              // taps of stage k_s: tables at the block, J_{k+1} = cur
-                const size_t pb = (size_t)pr.B * tsz;
-                pr.g = dPg ? dPg + (size_t)(k_s - 1) * pb : nullptr;
-                pr.x_next = dPx ? dPx + (size_t)(k_s - 1) * pb * h->hp.D : nullptr;
-                pr.j_interp = dPj ? dPj + (size_t)(k_s - 1) * pb : nullptr;
-                st = launch_probe(h, pr, cur, stream);
-                if (st) { cleanup(); return st; }
-            }
-            st = launch_stage(h, cur, outJ, outI, stream);
-            if (st) { cleanup(); return st; }
-            if (every_stage && !(o->monitor_period > 0 && k_s == stop)) {   // Dynamic_Solver.m:101: one line per stage
-                float ems = 0;
-                (void)hipEventRecord(ev1, stream);
-                (void)hipEventSynchronize(ev1);
-                (void)hipEventElapsedTime(&ems, ev0, ev1);
-                o->progress(o->progress_user, k_s, 0.0, 0.0, ems * 1e-3);
-            }
-            cur = outJ;
-            cur_idx = outI;
-            if (!dJst) pp ^= 1;
-            ++done;
-        }
-        // here k_s == stop - 1; the stage just computed has reference index `stop`
-        if (o->monitor_period > 0 && (stop % o->monitor_period) == 0) {
-            // Solver_pos_att.m:273-285: fsum50 = sum(F.Values(:)), idsum50 = sum(U_Optimal_id(:))
-            st = launch_monitor_sums(h->dtype, o->monitor_single != 0 || h->monitor_single, cur, cur_idx, h->idx_bytes, nS, h->d_partials, h->d_sums, stream);
-            if (st != HJB_OK) { cleanup(); return fail(h, HJB_E_DEVICE, "monitor reduction launch failed"); }
-            double sums[2];
-            unsafe_lk.lock();        // the handle's one lock (cleanup() on a failure below sees it held: no second shared lock)
-            SOLVE_TRY(hipMemcpyAsync(sums, h->d_sums, sizeof sums, hipMemcpyDeviceToHost, stream));
-            SOLVE_TRY(hipStreamSynchronize(stream));
-            unsafe_lk.unlock();
-            // Solver_pos_att.m:276-282: with a single fsum50, `e = fsum50 - fsum50_prev` is a single-precision subtraction
-            // and `abs(e) < tol` compares in single (MATLAB casts the double tol); otherwise everything is double
-            const bool msingle = (o->monitor_single != 0 || h->monitor_single) && h->dtype != HJB_F64;
-            e = msingle ? (double)((float)sums[0] - (float)fprev) : sums[0] - fprev;
-            e2 = sums[1] - iprev;
-            fprev = sums[0];
-            iprev = sums[1];
-            if (o->progress) {
-                float ms = 0;
-                (void)hipEventRecord(ev1, stream);
-                (void)hipEventSynchronize(ev1);
-                (void)hipEventElapsedTime(&ms, ev0, ev1);
-                o->progress(o->progress_user, stop, e, e2, ms * 1e-3);
-            }
-            if (msingle ? (std::fabs((float)e) < (float)o->monitor_tol) : (std::fabs(e) < o->monitor_tol)) { early = 1; break; }
-        }
-    }
-    SOLVE_TRY(hipEventRecord(ev1, stream));
-    SOLVE_TRY(hipEventSynchronize(ev1));
-    float ms = 0;
-    SOLVE_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    unsafe_lk.lock();
-    st = check_status(h, stream);
-    if (st) { cleanup(); return st; }
-    if (o->J_final) SOLVE_TRY(hipMemcpy(o->J_final, cur, jb, hipMemcpyDeviceToHost));
-    if (o->idx_final) SOLVE_TRY(hipMemcpy(o->idx_final, cur_idx, ib, hipMemcpyDeviceToHost));
-    if (dPg) SOLVE_TRY(hipMemcpy(o->probe->g, dPg, (size_t)pr.B * tsz * o->n_stages, hipMemcpyDeviceToHost));
-    if (dPx) SOLVE_TRY(hipMemcpy(o->probe->x_next, dPx, (size_t)pr.B * tsz * h->hp.D * o->n_stages, hipMemcpyDeviceToHost));
-    if (dPj) SOLVE_TRY(hipMemcpy(o->probe->j_interp, dPj, (size_t)pr.B * tsz * o->n_stages, hipMemcpyDeviceToHost));
-    if (o->J_stages) SOLVE_TRY(hipMemcpy(o->J_stages, dJst, jb * o->n_stages, hipMemcpyDeviceToHost));
-    if (o->idx_stages) SOLVE_TRY(hipMemcpy(o->idx_stages, dIst, ib * o->n_stages, hipMemcpyDeviceToHost));
-    cleanup();
-    if (res) {
-        res->stages_done = done;
-        res->stopped_early = early;
-        res->sweep_ms = ms;
-        res->last_e = e;
-        res->last_e2 = e2;
-    }
-    return HJB_OK;
-#undef SOLVE_TRY
 }
 
 int32_t hjb_policy_lookup(int32_t device, int32_t dtype, int32_t D, const int32_t *n, const double *const *knots,

@@ -58,29 +58,33 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
     }
     Handle *h0 = H[0];
     HIP_TRY(h0, hipSetDevice(h0->device));
-    std::shared_lock<std::shared_mutex> unsafe_lk(g_capture_mu);
+    SharedHold unsafe_lk(g_capture_mu);
     for (int i = 0; i < n; ++i) {
         const int st = ensure_work(H[i]);
         if (st) return st;
     }
+    struct Resplit {                          // every handle gets its own parts back, on every way out (declared before the call's
+        const SharedHold &held;               // scratch: it runs after the frees), with nothing of this batch in flight
+        Handle **H;
+        int n, old_split[kCsBatchMax];
+        ~Resplit() {
+            HoldUnlessHeld hold(held);
+            if (H[0]->stream) (void)hipStreamSynchronize(H[0]->stream);
+            for (int i = 0; i < n; ++i) {
+                Handle *h = H[i];
+                if (h->cs_split == old_split[i]) continue;
+                h->cs_split = old_split[i];
+                (void)colsweep_options(h, false);
+                choose_launch(h);
+            }
+        }
+    } resplit{unsafe_lk, H, n, {}};
+    for (int i = 0; i < n; ++i) resplit.old_split[i] = H[i]->cs_split;
     // Parts per column.  A handle's own choice (colsweep_split) is made for a launch that is ALONE on the device: as many parts as
     // fill the wave slots, because such a launch is one wave's chain of round trips.  Every part primes its rows again, so that
     // choice does up to twice the work per column - the right price for latency, the wrong one for a batch, whose launches hold n
     // problems' columns: here the parts are what lets ALL the batch's columns fill about one round of the wave slots
     // (profiles/r06_batch_split.log: the reference's channels, 4 x 450 columns of 20 steps, 10 parts each when alone - 2 to 4 here).
-    int old_split[kCsBatchMax];
-    bool resplit = false;
-    for (int i = 0; i < n; ++i) old_split[i] = H[i]->cs_split;
-    auto restore_split = [&]() {              // every handle gets its own parts back, on every way out
-        if (!resplit) return;
-        for (int i = 0; i < n; ++i) {
-            Handle *h = H[i];
-            if (h->cs_split == old_split[i]) continue;
-            h->cs_split = old_split[i];
-            (void)colsweep_options(h, false);
-            choose_launch(h);
-        }
-    };
     if (!tabled) {
         int64_t columns = 0;
         for (int i = 0; i < n; ++i) {
@@ -93,17 +97,13 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
             Handle *h = H[i];
             if (h->cs_split == 0 && s_batch < (int)h->hcs.split) {      // (an explicit option "cs_split" stands)
                 h->cs_split = s_batch;
-                resplit = true;
                 const int ust = colsweep_options(h, false);
-                if (ust) { restore_split(); return ust; }
+                if (ust) return ust;
                 choose_launch(h);
             }
         }
     }
-    if (!h0->stream) {
-        const hipError_t se = hipStreamCreateWithFlags(&h0->stream, hipStreamNonBlocking);
-        if (se != hipSuccess) { restore_split(); return fail(h0, HJB_E_DEVICE, "hipStreamCreateWithFlags failed: %s", hipGetErrorString(se)); }
-    }
+    if (!h0->stream) HIP_TRY(h0, hipStreamCreateWithFlags(&h0->stream, hipStreamNonBlocking));
     hipStream_t stream = h0->stream;
     DCsBatch hb;
     memset(&hb, 0, sizeof hb);
@@ -117,32 +117,13 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
         gmax = std::max(gmax, (unsigned)h->L.grid);
         const size_t jb = (size_t)h->n_owned * h->esz;
         const hipError_t te = opts[i]->terminal ? hipMemcpy(h->dJ[0], opts[i]->terminal, jb, hipMemcpyHostToDevice) : hipMemset(h->dJ[0], 0, jb);
-        if (te != hipSuccess) { restore_split(); return fail(h, HJB_E_DEVICE, "terminal cost of problem %d: %s", i, hipGetErrorString(te)); }
+        if (te != hipSuccess) return fail(h, HJB_E_DEVICE, "terminal cost of problem %d: %s", i, hipGetErrorString(te));
     }
+    SweepScratch sc(h0, unsafe_lk);
     DCsBatch *dB = nullptr;
-    hipGraphExec_t gexec = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    auto cleanup = [&]() {
-        std::shared_lock<std::shared_mutex> lk(g_capture_mu, std::defer_lock);
-        if (!unsafe_lk.owns_lock()) lk.lock();
-        if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
-        if (ev0) { (void)hipEventDestroy(ev0); ev0 = nullptr; }
-        if (ev1) { (void)hipEventDestroy(ev1); ev1 = nullptr; }
-        if (dB) { (void)hipFree(dB); dB = nullptr; }
-        (void)hipStreamSynchronize(stream);       // (nothing of this batch is in flight when the handles get their own parts back)
-        restore_split();
-    };
-#define BATCH_TRY(expr)                                                                            \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            cleanup();                                                                             \
-            return fail(h0, HJB_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));          \
-        }                                                                                          \
-    } while (0)
-    BATCH_TRY(hipMalloc((void **)&dB, sizeof hb));
-    BATCH_TRY(hipMemcpy(dB, &hb, sizeof hb, hipMemcpyHostToDevice));
-    BATCH_TRY(sync_setup());
+    if (sc.alloc(sizeof hb, false, &dB, "batch record")) return fail(h0, HJB_E_DEVICE, "hipMalloc of the batch record failed");
+    HIP_TRY(h0, hipMemcpy(dB, &hb, sizeof hb, hipMemcpyHostToDevice));
+    HIP_TRY(h0, sync_setup());
     StageArgs a;
     a.grid = gmax;
     a.block = tabled ? (unsigned)h0->L.block : 256u;
@@ -164,95 +145,65 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
     unsafe_lk.unlock();
     // kGraphStages ping-pong launches for the problems of `mask`, starting and ending in buffer 0; re-captured when a problem stops
     auto capture = [&]() -> int {
-        std::unique_lock<std::shared_mutex> capture_lk(g_capture_mu);
-        if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return fail(h0, HJB_E_DEVICE, "hjb_solve_batch: stream capture failed");
-        int cst = HJB_OK;
-        for (int i = 0; i < kGraphStages / 2 && cst == HJB_OK; ++i) {
-            cst = launch(mask, 0);
-            if (cst == HJB_OK) cst = launch(mask, 1);
-        }
-        hipError_t ce = hipStreamEndCapture(stream, &graph);
-        if (cst != HJB_OK || ce != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return fail(h0, HJB_E_DEVICE, "hjb_solve_batch: stage-loop graph capture failed: %s", hipGetErrorString(ce));
-        }
-        ce = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ce != hipSuccess) return fail(h0, HJB_E_DEVICE, "hipGraphInstantiate: %s", hipGetErrorString(ce));
-        gmask = mask;
-        return HJB_OK;
+        sc.drop_graph();
+        const int cst = capture_stage_loop(h0, stream, [&]() {
+            int lst = HJB_OK;
+            for (int i = 0; i < kGraphStages && lst == HJB_OK; ++i) lst = launch(mask, i & 1);
+            return lst;
+        }, &sc.gexec);
+        if (!cst) gmask = mask;
+        return cst;
     };
-    BATCH_TRY(hipEventCreate(&ev0));
-    BATCH_TRY(hipEventCreate(&ev1));
-    BATCH_TRY(hipEventRecord(ev0, stream));
+    HIP_TRY(h0, hipEventCreate(&sc.ev0));
+    HIP_TRY(h0, hipEventCreate(&sc.ev1));
+    HIP_TRY(h0, hipEventRecord(sc.ev0, stream));
     int parity = 0;                         // the buffer that holds the current cost-to-go of every problem still running
     int done[kCsBatchMax] = {0}, early[kCsBatchMax] = {0}, final_parity[kCsBatchMax] = {0};
-    double fprev[kCsBatchMax] = {0}, iprev[kCsBatchMax] = {0}, e[kCsBatchMax] = {0}, e2[kCsBatchMax] = {0};
+    MonitorDiff mon[kCsBatchMax];
     int st = HJB_OK;
     int k_s = o0.n_stages;
     auto count = [&](int stages) { for (int i = 0; i < n; ++i) if ((mask >> i) & 1u) done[i] += stages; };
+    auto eager = [&](int stages) -> int {
+        for (; stages > 0; --stages, --k_s, parity ^= 1, count(1))
+            if (const int lst = launch(mask, parity)) return lst;
+        return HJB_OK;
+    };
     while (k_s >= 1 && mask) {
-        int stop = 1;
-        if (o0.monitor_period > 0) stop = std::max(1, (k_s / o0.monitor_period) * o0.monitor_period);
-        int run = k_s - stop + 1;
-        if (want_graph && run >= kGraphStages) {
-            if (parity == 1) {               // a replay starts in buffer 0: one eager stage
-                st = launch(mask, parity);
-                if (st) { cleanup(); return st; }
-                parity ^= 1; count(1); --run; --k_s;
-            }
-            if (run >= kGraphStages && (!gexec || gmask != mask)) {
-                st = capture();
-                if (st) { cleanup(); return st; }
-            }
-            while (run >= kGraphStages) {
-                BATCH_TRY(hipGraphLaunch(gexec, stream));
-                count(kGraphStages); run -= kGraphStages; k_s -= kGraphStages;
-            }
-        }
-        for (; run > 0; --run, --k_s) {
-            st = launch(mask, parity);
-            if (st) { cleanup(); return st; }
-            parity ^= 1;
-            count(1);
-        }
-        // here k_s == stop - 1: the stage just computed has reference index `stop` (Solver_pos_att.m:273-285, per problem)
-        if (o0.monitor_period > 0 && (stop % o0.monitor_period) == 0) {
+        const SweepBlock b = sweep_block(k_s, o0.monitor_period, want_graph, parity);
+        if ((st = eager(b.eager_first))) return st;                      // a replay starts in buffer 0
+        if (b.replays && (!sc.gexec || gmask != mask) && (st = capture())) return st;
+        for (int g = 0; g < b.replays; ++g, count(kGraphStages), k_s -= kGraphStages) HIP_TRY(h0, hipGraphLaunch(sc.gexec, stream));
+        if ((st = eager(b.tail))) return st;
+        // here k_s == b.stop - 1: the stage just computed has reference index b.stop (Solver_pos_att.m:273-285, per problem)
+        if (monitor_due(b.stop, o0.monitor_period)) {
             double sums[kCsBatchMax][2];
             for (int i = 0; i < n; ++i) {
                 if (!((mask >> i) & 1u)) continue;
                 Handle *h = H[i];
                 if (launch_monitor_sums(h->dtype, opts[i]->monitor_single != 0 || h->monitor_single, h->dJ[parity], h->d_idx, h->idx_bytes, h->n_owned,
-                                        h->d_partials, h->d_sums, stream) != HJB_OK) { cleanup(); return fail(h, HJB_E_DEVICE, "monitor reduction launch failed"); }
+                                        h->d_partials, h->d_sums, stream) != HJB_OK) return fail(h, HJB_E_DEVICE, "monitor reduction launch failed");
             }
             unsafe_lk.lock();
             for (int i = 0; i < n; ++i)
-                if ((mask >> i) & 1u) BATCH_TRY(hipMemcpyAsync(sums[i], H[i]->d_sums, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
-            BATCH_TRY(hipStreamSynchronize(stream));
+                if ((mask >> i) & 1u) HIP_TRY(h0, hipMemcpyAsync(sums[i], H[i]->d_sums, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(h0, hipStreamSynchronize(stream));
             float ms = 0;
             bool timed = false;
             unsafe_lk.unlock();
             for (int i = 0; i < n; ++i) {
                 if (!((mask >> i) & 1u)) continue;
-                Handle *h = H[i];
                 const hjb_solve_opts &o = *opts[i];
-                const bool msingle = (o.monitor_single != 0 || h->monitor_single) && h->dtype != HJB_F64;
-                e[i] = msingle ? (double)((float)sums[i][0] - (float)fprev[i]) : sums[i][0] - fprev[i];
-                e2[i] = sums[i][1] - iprev[i];
-                fprev[i] = sums[i][0];
-                iprev[i] = sums[i][1];
+                const bool stops = mon[i].step(sums[i][0], sums[i][1], (o.monitor_single != 0 || H[i]->monitor_single) && H[i]->dtype != HJB_F64, o.monitor_tol);
                 if (o.progress) {
                     if (!timed) {
-                        (void)hipEventRecord(ev1, stream);
-                        (void)hipEventSynchronize(ev1);
-                        (void)hipEventElapsedTime(&ms, ev0, ev1);
+                        (void)hipEventRecord(sc.ev1, stream);
+                        (void)hipEventSynchronize(sc.ev1);
+                        (void)hipEventElapsedTime(&ms, sc.ev0, sc.ev1);
                         timed = true;
                     }
-                    o.progress(o.progress_user, stop, e[i], e2[i], ms * 1e-3);
+                    o.progress(o.progress_user, b.stop, mon[i].e, mon[i].e2, ms * 1e-3);
                 }
-                if (msingle ? (std::fabs((float)e[i]) < (float)o.monitor_tol) : (std::fabs(e[i]) < o.monitor_tol)) {
+                if (stops) {
                     early[i] = 1;
                     final_parity[i] = parity;
                     mask &= ~(1u << i);           // this problem's sweep ends here: its result stays in the buffer it was just written to
@@ -262,29 +213,20 @@ int32_t hjb_solve_batch(int32_t n, const hjb_handle *hs, const hjb_solve_opts *c
     }
     for (int i = 0; i < n; ++i)
         if (!early[i]) final_parity[i] = parity;
-    BATCH_TRY(hipEventRecord(ev1, stream));
-    BATCH_TRY(hipEventSynchronize(ev1));
+    HIP_TRY(h0, hipEventRecord(sc.ev1, stream));
+    HIP_TRY(h0, hipEventSynchronize(sc.ev1));
     float ms = 0;
-    BATCH_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    HIP_TRY(h0, hipEventElapsedTime(&ms, sc.ev0, sc.ev1));
     unsafe_lk.lock();
     for (int i = 0; i < n; ++i) {
         Handle *h = H[i];
-        st = check_status(h, stream);
-        if (st) { cleanup(); return st; }
+        if ((st = check_status(h, stream))) return st;
         const size_t jb = (size_t)h->n_owned * h->esz, ib = (size_t)h->n_owned * h->idx_bytes;
-        if (opts[i]->J_final) BATCH_TRY(hipMemcpy(opts[i]->J_final, h->dJ[final_parity[i]], jb, hipMemcpyDeviceToHost));
-        if (opts[i]->idx_final) BATCH_TRY(hipMemcpy(opts[i]->idx_final, h->d_idx, ib, hipMemcpyDeviceToHost));
-        if (res && res[i]) {
-            res[i]->stages_done = done[i];
-            res[i]->stopped_early = early[i];
-            res[i]->sweep_ms = ms;
-            res[i]->last_e = e[i];
-            res[i]->last_e2 = e2[i];
-        }
+        if (opts[i]->J_final) HIP_TRY(h0, hipMemcpy(opts[i]->J_final, h->dJ[final_parity[i]], jb, hipMemcpyDeviceToHost));
+        if (opts[i]->idx_final) HIP_TRY(h0, hipMemcpy(opts[i]->idx_final, h->d_idx, ib, hipMemcpyDeviceToHost));
+        if (res && res[i]) *res[i] = hjb_result{done[i], early[i], ms, mon[i].e, mon[i].e2};
     }
-    cleanup();
     return HJB_OK;
-#undef BATCH_TRY
 }
 
 }  // extern "C"

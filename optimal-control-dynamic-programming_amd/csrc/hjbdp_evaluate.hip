@@ -74,7 +74,7 @@ int32_t hjb_evaluate(hjb_handle hh, int32_t n_stages, const void *terminal, cons
                         (long long)(bad % nS), (long long)(bad / nS), (long long)lo, (long long)hi);
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    std::shared_lock<std::shared_mutex> unsafe_lk(g_capture_mu);    // allocation, synchronous copies, device sync
+    SharedHold unsafe_lk(g_capture_mu);    // allocation, synchronous copies, device sync
     bool tabled = false;
     int st = prepare_evaluate(h, &tabled);
     if (!st) st = ensure_work(h);
@@ -82,62 +82,39 @@ int32_t hjb_evaluate(hjb_handle hh, int32_t n_stages, const void *terminal, cons
     const size_t jb = (size_t)nS * h->esz, ib = (size_t)nS * h->idx_bytes;
     if (!h->stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     hipStream_t stream = h->stream;
+    SweepScratch sc(h, unsafe_lk);
     char *dJst = nullptr, *dLab = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    auto cleanup = [&]() {
-        if (ev0) { (void)hipEventDestroy(ev0); ev0 = nullptr; }
-        if (ev1) { (void)hipEventDestroy(ev1); ev1 = nullptr; }
-        if (dJst) { (void)hipFree(dJst); dJst = nullptr; }
-        if (dLab) { (void)hipFree(dLab); dLab = nullptr; }
-    };
-#define EVAL_TRY(expr)                                                                             \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            cleanup();                                                                             \
-            return fail(h, HJB_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-        }                                                                                          \
-    } while (0)
-    if (J_stages) {      // the kernels write straight into the stage planes
-        void *d = nullptr;
-        if (hipMalloc(&d, jb * n_stages) != hipSuccess) return fail(h, HJB_E_NOMEM, "cannot hold %d J stages on the device", n_stages);
-        dJst = (char *)d;
-    }
+    // the kernels write straight into the stage planes
+    if (J_stages && (st = sc.alloc(jb * n_stages, false, &dJst, "cannot hold %d J stages on the device", n_stages))) return st;
     const char *dL = h->d_idx;                                  // a stationary policy sits in the handle's label buffer
     if (labels_per_stage) {
-        void *d = nullptr;
-        if (hipMalloc(&d, ib * n_stages) != hipSuccess) { cleanup(); return fail(h, HJB_E_NOMEM, "cannot hold %d stages of labels on the device", n_stages); }
-        dLab = (char *)d;
+        if ((st = sc.alloc(ib * n_stages, false, &dLab, "cannot hold %d stages of labels on the device", n_stages))) return st;
         dL = dLab;
     }
-    EVAL_TRY(hipMemcpy((void *)dL, labels, ib * nlp, hipMemcpyHostToDevice));
-    if (terminal) EVAL_TRY(hipMemcpy(h->dJ[0], terminal, jb, hipMemcpyHostToDevice));
-    else EVAL_TRY(hipMemset(h->dJ[0], 0, jb));
-    EVAL_TRY(sync_setup());              // the loop runs on the handle's own stream from here
-    EVAL_TRY(hipEventCreate(&ev0));
-    EVAL_TRY(hipEventCreate(&ev1));
-    EVAL_TRY(hipEventRecord(ev0, stream));
+    HIP_TRY(h, hipMemcpy((void *)dL, labels, ib * nlp, hipMemcpyHostToDevice));
+    if (terminal) HIP_TRY(h, hipMemcpy(h->dJ[0], terminal, jb, hipMemcpyHostToDevice));
+    else HIP_TRY(h, hipMemset(h->dJ[0], 0, jb));
+    HIP_TRY(h, sync_setup());              // the loop runs on the handle's own stream from here
+    HIP_TRY(h, hipEventCreate(&sc.ev0));
+    HIP_TRY(h, hipEventCreate(&sc.ev1));
+    HIP_TRY(h, hipEventRecord(sc.ev0, stream));
     const void *cur = h->dJ[0];
     int pp = 1;
     for (int k_s = n_stages; k_s >= 1; --k_s) {                 // the stage with reference index k_s reads label plane k_s - 1
         void *outJ = dJst ? (void *)(dJst + (size_t)(k_s - 1) * jb) : h->dJ[pp];
-        st = launch_evaluate(h, cur, labels_per_stage ? dL + (size_t)(k_s - 1) * ib : dL, outJ, stream);
-        if (st) { cleanup(); return st; }
+        if ((st = launch_evaluate(h, cur, labels_per_stage ? dL + (size_t)(k_s - 1) * ib : dL, outJ, stream))) return st;
         cur = outJ;
         if (!dJst) pp ^= 1;
     }
-    EVAL_TRY(hipEventRecord(ev1, stream));
-    EVAL_TRY(hipEventSynchronize(ev1));
+    HIP_TRY(h, hipEventRecord(sc.ev1, stream));
+    HIP_TRY(h, hipEventSynchronize(sc.ev1));
     float ms = 0;
-    EVAL_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    st = check_status(h, stream);
-    if (st) { cleanup(); return st; }
-    if (J_final) EVAL_TRY(hipMemcpy(J_final, cur, jb, hipMemcpyDeviceToHost));
-    if (J_stages) EVAL_TRY(hipMemcpy(J_stages, dJst, jb * n_stages, hipMemcpyDeviceToHost));
-    cleanup();
+    HIP_TRY(h, hipEventElapsedTime(&ms, sc.ev0, sc.ev1));
+    if ((st = check_status(h, stream))) return st;
+    if (J_final) HIP_TRY(h, hipMemcpy(J_final, cur, jb, hipMemcpyDeviceToHost));
+    if (J_stages) HIP_TRY(h, hipMemcpy(J_stages, dJst, jb * n_stages, hipMemcpyDeviceToHost));
     if (sweep_ms) *sweep_ms = ms;
     return HJB_OK;
-#undef EVAL_TRY
 }
 
 }  // extern "C"

@@ -5,7 +5,8 @@
 //   hjbdp_packed.hip   variant 1's analysis, variants 2 / 4 (outer terms, axis tables, contraction mode), the DNested upload, K15's set-up
 //   hjbdp_colsweep.hip variant 7's host side: plan, XCD map, DPP test, cooperative plan, launch record, split rule
 //   hjbdp_choose.hip   which variant serves, in which form and geometry (Handle::L), and the stage launch
-//   hjbdp_api.hip      hjb_create .. hjb_solve, options, probe, policy lookup (the single-device C ABI)
+//   hjbdp_api.hip      hjb_create .. hjb_backup_stage, options, probe, policy lookup (the single-device C ABI)
+//   hjbdp_solve.hip    hjb_solve (one handle's backward sweep; hjbdp_sweep.h: the monitor rule, its schedule, the graph split)
 //   hjbdp_evaluate.hip hjb_evaluate_stage, hjb_evaluate_stage_device, hjb_evaluate (the cost of a given policy on the grid)
 //   hjbdp_disturb.hip  hjb_set_disturbance (the disturbance a handle's stages carry: kernel variant 8)
 //   hjbdp_batch.hip    hjb_solve_batch (several sweeps of one kernel shape, one launch per stage)
@@ -27,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
@@ -37,6 +39,7 @@
 #include "hjbdp_dev.h"
 #include "hjbdp_launch.h"
 #include "hjbdp_slab.h"
+#include "hjbdp_sweep.h"
 #include "kernels_generic.h"
 #include "kernels_nested.h"
 #include "kernels_packed.h"
@@ -54,7 +57,6 @@
 namespace hjbhost {
 using namespace hjb;
 
-constexpr int kGraphStages = 32;   // even: a replay starts and ends in dJ[0]
 // K15's claim counters: one set per stream a handle launches on (the first kUwSets streams; later ones take the static walk)
 constexpr int kUwSets = 8;
 constexpr int kUwSetWords = 8 * 16;  // one set: per XCD one 64-byte line
@@ -64,6 +66,7 @@ extern thread_local std::string g_last_error;
 extern std::atomic<int> g_test_fail_tab64_scratch;   // "fail_tab64_scratch": the float64 table build's scratch allocation fails
 extern std::atomic<int> g_test_fail_tabled_alloc;    // "fail_tabled_alloc": the (cell, t) table allocation fails
 extern std::atomic<int> g_test_rccl_only_env;        // "rccl_only_env": the RCCL loader tries $HJBDP_RCCL_LIB only
+extern std::atomic<int> g_test_fail_graph_capture;   // "fail_graph_capture": capture_stage_loop fails before any HIP call
 // Handles may be driven from different host threads (one thread per handle).  HIP stream capture is fragile
 // against "unsafe" calls made elsewhere in the process while it records (device-wide synchronisation, synchronous
 // copies, allocation): a capture takes this lock exclusively, every such call takes it shared.  Kernel launches,
@@ -226,6 +229,41 @@ int upload(Handle *h, const std::vector<T> &v, X **out) {
     *out = (X *)d;
     return HJB_OK;
 }
+
+// What one call of a sweep driver holds on the device beside the handle's own buffers: its scratch buffers, its two timing events
+// and, where used, a graph exec.  Declared AFTER the caller's shared hold of g_capture_mu: the destructor frees everything under
+// that hold (hipFree is one of the calls a stream capture elsewhere in the process must not see), or under one of its own while
+// the caller's is released.
+using SharedHold = std::shared_lock<std::shared_mutex>;
+struct HoldUnlessHeld {                  // a shared hold for a scope, unless the caller's `held` owns one (no second one on a thread)
+    SharedHold own{g_capture_mu, std::defer_lock};
+    explicit HoldUnlessHeld(const SharedHold &held) { if (!held.owns_lock()) own.lock(); }
+};
+struct SweepScratch {
+    Handle *h;
+    const SharedHold &held;
+    std::vector<void *> bufs;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipGraphExec_t gexec = nullptr;
+    SweepScratch(Handle *h_, const SharedHold &held_) : h(h_), held(held_) {}
+    SweepScratch(const SweepScratch &) = delete;
+    ~SweepScratch();
+    void drop_graph();                   // gexec destroyed, under the same rule
+    // a buffer of this call (zero: filled with zeros) -> HJB_E_NOMEM with the caller's message, HJB_E_DEVICE if the fill failed
+    template <typename X, typename... A>
+    int alloc(size_t bytes, bool zero, X **out, const char *fmt, A... a) {
+        void *d = nullptr;
+        if (hipMalloc(&d, bytes) != hipSuccess) return fail(h, HJB_E_NOMEM, fmt, a...);
+        bufs.push_back(d);
+        *out = (X *)d;
+        if (zero) HIP_TRY(h, hipMemset(d, 0, bytes));
+        return HJB_OK;
+    }
+};
+// kGraphStages ping-pong launches recorded on `stream` into a graph exec: takes g_capture_mu exclusively (the caller holds it in no
+// form), begins the capture, runs body() - the launches, -> a status -, always ends the capture, instantiates into *out.  Frees
+// nothing of the caller's and has released the lock when it returns; on failure *out is untouched and the error recorded.
+int capture_stage_loop(Handle *h, hipStream_t stream, const std::function<int()> &body, hipGraphExec_t *out);
 
 // hjbdp_setup.hip
 int64_t term_elems(const hjb_problem *p, uint32_t mask);

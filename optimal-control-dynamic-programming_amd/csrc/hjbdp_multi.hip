@@ -148,7 +148,7 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
     }
     const auto t0 = std::chrono::steady_clock::now();
     int cur = 0, done = 0, early = 0;
-    double fprev = 0, iprev = 0, e = 0, e2 = 0;
+    MonitorDiff mon;
     for (int k_s = o->n_stages; k_s >= 1; --k_s, ++done) {
         const int par = done & 1, ppar = par ^ 1;
         // ---- phase A: halo copies of J_{k+1} (buffer `cur`) on the copy streams ------------------------------------
@@ -204,7 +204,7 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
                 if (o->idx_stages)
                     MULTI_TRY(hipMemcpyAsync((char *)o->idx_stages + at * isz, S.whole->d_idx, (size_t)inner * own * isz, hipMemcpyDeviceToHost, S.sc));
             }
-        if (every_stage && !(o->monitor_period > 0 && (k_s % o->monitor_period) == 0)) {    // Dynamic_Solver.m:101: one line per stage
+        if (every_stage && !monitor_due(k_s, o->monitor_period)) {    // Dynamic_Solver.m:101: one line per stage
             for (auto &S : m->slabs) {
                 MULTI_TRY(hipSetDevice(S.device));
                 MULTI_TRY(hipStreamSynchronize(S.sc));
@@ -213,7 +213,7 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
         }
         cur ^= 1;
         // ---- the early-stop monitor (Solver_pos_att.m:273-285): per-slab sums, added on the host ----------------------
-        if (o->monitor_period > 0 && (k_s % o->monitor_period) == 0) {
+        if (monitor_due(k_s, o->monitor_period)) {
             double sj = 0, si = 0;
             for (auto &S : m->slabs) {
                 MULTI_TRY(hipSetDevice(S.device));
@@ -229,9 +229,9 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
                 sj += sums[0];
                 si += sums[1];
             }
-            e = sj - fprev; e2 = si - iprev; fprev = sj; iprev = si;
-            if (o->progress) o->progress(o->progress_user, k_s, e, e2, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-            if (std::fabs(e) < o->monitor_tol) { early = 1; ++done; break; }
+            const bool stop = mon.step(sj, si, false, o->monitor_tol);      // exact float64 sums over the slabs: the double rule
+            if (o->progress) o->progress(o->progress_user, k_s, mon.e, mon.e2, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+            if (stop) { early = 1; ++done; break; }
         }
     }
     for (auto &S : m->slabs) {
@@ -251,13 +251,7 @@ int32_t hjb_solve_multi(hjb_multi m, const hjb_solve_opts *o, hjb_result *res) {
         if (o->J_final) MULTI_TRY(hipMemcpy((char *)o->J_final + plane_b * S.begin, (const char *)S.whole->dJ[cur] + plane_b * S.hlo, plane_b * own, hipMemcpyDeviceToHost));
         if (o->idx_final) MULTI_TRY(hipMemcpy((char *)o->idx_final + (size_t)(inner * S.begin) * isz, S.whole->d_idx, (size_t)inner * own * isz, hipMemcpyDeviceToHost));
     }
-    if (res) {
-        res->stages_done = done;
-        res->stopped_early = early;
-        res->sweep_ms = ms;
-        res->last_e = e;
-        res->last_e2 = e2;
-    }
+    if (res) *res = hjb_result{done, early, ms, mon.e, mon.e2};
     return HJB_OK;
 #undef MULTI_TRY
 }

@@ -483,9 +483,8 @@ int32_t hjb_rank_sweep(hjb_rank r, int32_t n_stages, int32_t monitor_period, dou
     hipEvent_t e0 = nullptr, e1 = nullptr;
     void *J[2] = {dJ0, dJ1};
     int cur = 0, done = 0, early = 0, st = HJB_OK;
-    double fprev = 0.0;
-    // Solver_pos_att.m:276-282 with a single fsum50: the difference and `abs(e) < tol` are single-precision (hjb_solve's rule)
-    const bool msingle = r->monitor_single && r->g.dtype != HJB_F64;
+    MonitorDiff mon;                        // (e2 is not reported here)
+    const bool msingle = r->monitor_single && r->g.dtype != HJB_F64;      // also over several ranks: see hjb_rank_monitor_sums
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, cs) != hipSuccess)
         st = rfail(r, HJB_E_DEVICE, "sweep: event set-up failed: %s", hipGetErrorString(hipGetLastError()));
     const bool post = r->post_exchange && (r->world > 1 || r->loopback);
@@ -495,13 +494,11 @@ int32_t hjb_rank_sweep(hjb_rank r, int32_t n_stages, int32_t monitor_period, dou
         if (st) break;
         cur = 1 - cur;
         ++done;
-        if (monitor_period > 0 && (k_s % monitor_period) == 0) {
+        if (monitor_due(k_s, monitor_period)) {
             double sums[2];
             st = hjb_rank_monitor_sums(r, J[cur], d_idx, compute_stream, sums);
             if (st) break;
-            const double e = msingle ? (double)((float)sums[0] - (float)fprev) : sums[0] - fprev;
-            fprev = sums[0];
-            if (msingle ? (std::fabs((float)e) < (float)monitor_tol) : (std::fabs(e) < monitor_tol)) { early = 1; break; }
+            if (mon.step(sums[0], sums[1], msingle, monitor_tol)) { early = 1; break; }
         }
     }
     if (!st) {

@@ -9,6 +9,7 @@ thread_local std::string g_last_error;
 std::atomic<int> g_test_fail_tab64_scratch{0};
 std::atomic<int> g_test_fail_tabled_alloc{0};
 std::atomic<int> g_test_rccl_only_env{0};
+std::atomic<int> g_test_fail_graph_capture{0};
 std::shared_mutex g_capture_mu;
 
 int fail(Handle *h, int code, const char *fmt, ...) {
@@ -48,6 +49,36 @@ int dev_alloc(Handle *h, size_t bytes, void **out) {
     h->allocs.push_back(d);
     *out = d;
     return HJB_OK;
+}
+
+SweepScratch::~SweepScratch() {
+    HoldUnlessHeld hold(held);
+    if (gexec) (void)hipGraphExecDestroy(gexec);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    for (void *d : bufs) (void)hipFree(d);
+}
+
+void SweepScratch::drop_graph() {
+    HoldUnlessHeld hold(held);
+    if (gexec) (void)hipGraphExecDestroy(gexec);
+    gexec = nullptr;
+}
+
+int capture_stage_loop(Handle *h, hipStream_t stream, const std::function<int()> &body, hipGraphExec_t *out) {
+    if (g_test_fail_graph_capture.load()) return fail(h, HJB_E_DEVICE, "stage-loop graph capture failed (test hook)");
+    std::unique_lock<std::shared_mutex> capture_lk(g_capture_mu);
+    HIP_TRY(h, hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    const int cst = body();
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipError_t ce = hipStreamEndCapture(stream, &graph);
+    int st = HJB_OK;
+    if (cst != HJB_OK || ce != hipSuccess) st = fail(h, HJB_E_DEVICE, "stage-loop graph capture failed: %s", hipGetErrorString(ce));
+    else if ((ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0)) != hipSuccess) st = fail(h, HJB_E_DEVICE, "hipGraphInstantiate: %s", hipGetErrorString(ce));
+    if (graph) (void)hipGraphDestroy(graph);
+    if (!st) *out = exec;
+    return st;
 }
 
 int64_t term_elems(const hjb_problem *p, uint32_t mask) {

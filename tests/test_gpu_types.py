@@ -286,6 +286,87 @@ def test_cost64_table_build_failure_is_loud(env):
         assert bk.info()["cost_dtype"] == _abi.HJB_COST_F64 and bk.info()["kernel_variant"] in (5, 7)
 
 
+GRAPH_FROM = 64          # 2 x kGraphStages: the fewest stages at which hjb_solve / hjb_solve_batch capture and replay the stage loop
+
+
+@pytest.mark.parametrize("temporal", [0, 1], ids=["plain", "k9"])
+def test_graph_capture_failure_leaves_the_handle_usable(env, temporal):
+    """A stage-loop capture that fails (the library's test hook: capture_stage_loop returns before any HIP call) ends hjb_solve
+    with HJB_E_DEVICE and the call's scratch freed - in the plain capture (option temporal 0) and in the K9 tiled one (the
+    default on this local 2-D problem).  The same handle then captures and solves: J and labels equal those of a handle that
+    never replays (option graph 0) bit for bit, and it closes cleanly."""
+    hjbdp, _abi, c_oracle = env
+    from problems import random_problem, random_terminal
+    spec = random_problem(10, (20, 16), (5,), dtype=np.float32, spread=0.02)
+    term = random_terminal(spec, 3)
+    lib = hjbdp.load_library()
+    with hjbdp.Backup(spec) as eager:
+        eager.set_option("graph", 0)
+        eager.set_option("temporal", temporal)
+        ref = eager.solve(GRAPH_FROM, terminal=term)
+    with hjbdp.Backup(spec) as bk:
+        bk.set_option("temporal", temporal)
+        assert lib.hjb_test_hook(b"fail_graph_capture", 1) == _abi.HJB_OK
+        try:
+            with pytest.raises(hjbdp.HjbError) as ei:
+                bk.solve(GRAPH_FROM, terminal=term)
+            assert ei.value.status == _abi.HJB_E_DEVICE and "test hook" in str(ei.value)
+        finally:
+            assert lib.hjb_test_hook(b"fail_graph_capture", 0) == _abi.HJB_OK
+        out = bk.solve(GRAPH_FROM, terminal=term)
+        assert out["stages_done"] == GRAPH_FROM and not out["stopped_early"]
+        assert np.array_equal(out["J"], ref["J"]) and np.array_equal(out["idx"], ref["idx"])
+        if temporal:                             # the default took K9: required, it is the same sweep
+            bk.set_option("temporal", 2)
+            k9 = bk.solve(GRAPH_FROM, terminal=term)
+            assert np.array_equal(k9["J"], ref["J"]) and np.array_equal(k9["idx"], ref["idx"])
+
+
+def test_graph_capture_failure_in_a_batch_gives_the_handles_back(env):
+    """The same failure inside hjb_solve_batch: the call raises, every member's parts per column (option cs_split) read as
+    before it, and the batch then equals the two single solves bit for bit."""
+    import ctypes as C
+    hjbdp, _abi, c_oracle = env
+    from problems import colsweep_problem
+    # the smallest column-sweep shape of tests/test_gpu_batch.py (_loop_colsweep_specs)
+    specs = [colsweep_problem(3058 + i, (45, 5, 4, 4), nU=3, gax=2, big=2.7, levels=1, cost="fast") for i in range(2)]
+    force = [{"variant": 7}] * 2
+    lib = hjbdp.load_library()
+    solo = []
+    for s in specs:
+        with hjbdp.Backup(s, variant=7) as bk:
+            solo.append(bk.solve(GRAPH_FROM))
+    with hjbdp.Backup(specs[0], variant=7) as b0, hjbdp.Backup(specs[1], variant=7) as b1:
+        bks = (b0, b1)
+        parts = [(bk.get_option("cs_split"), bk.info()["grid"]) for bk in bks]
+        opts, keep = (C.POINTER(_abi.hjb_solve_opts) * 2)(), []
+        for i in range(2):
+            o = _abi.hjb_solve_opts()
+            o.n_stages = GRAPH_FROM
+            keep.append(o)
+            opts[i] = C.pointer(o)
+        hs = (C.c_void_p * 2)(b0._h, b1._h)
+        assert lib.hjb_test_hook(b"fail_graph_capture", 1) == _abi.HJB_OK
+        try:
+            with pytest.raises(hjbdp.HjbError) as ei:
+                hjbdp.solve_batch(specs, GRAPH_FROM, options=force)
+            assert ei.value.status == _abi.HJB_E_DEVICE and "test hook" in str(ei.value)
+            assert lib.hjb_solve_batch(2, hs, opts, None) == _abi.HJB_E_DEVICE
+            assert b"test hook" in lib.hjb_last_error(b0._h)
+        finally:
+            assert lib.hjb_test_hook(b"fail_graph_capture", 0) == _abi.HJB_OK
+        assert [(bk.get_option("cs_split"), bk.info()["grid"]) for bk in bks] == parts
+        assert lib.hjb_solve_batch(2, hs, opts, None) == _abi.HJB_OK, lib.hjb_last_error(b0._h)
+        for bk, want in zip(bks, solo):          # the handles of the failed call sweep as before
+            got = bk.solve(GRAPH_FROM)
+            assert np.array_equal(got["J"], want["J"]) and np.array_equal(got["idx"], want["idx"])
+    outs, _, variants, sizes = hjbdp.solve_batch(specs, GRAPH_FROM, options=force)
+    assert variants == [7, 7] and sizes == [2], (variants, sizes)       # one launch chain: hjb_solve_batch took both
+    for got, want in zip(outs, solo):
+        assert got["stages_done"] == GRAPH_FROM and np.isfinite(got["J"]).all()
+        assert np.array_equal(got["J"], want["J"]) and np.array_equal(got["idx"], want["idx"])
+
+
 @pytest.mark.parametrize("j_storage", [None, np.float16])
 def test_float64_cost_terms_every_serving_kernel(env, j_storage):
     """hjb_problem.cost_dtype = HJB_COST_F64: cost terms float64, the stage cost summed in double and rounded once
