@@ -517,8 +517,8 @@ int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_tr
  * than the two (HJB_F16S included: convert on the host); n_planes < 0; null values with n_planes > 0; hjb_rollout_run_greedy with
  * no affine model, with another model set, or with no values unless every plane index is -1; a plane index outside
  * -1 .. n_planes-1; and everything hjb_rollout_run refuses of n_steps, n_traj, X0 and X_final.
- * Out of scope: lookahead under a disturbance (hjb_set_disturbance's E_w / max_w inside the candidate), flying greedy under
- * hjb_rollout_set_noise's sampled noise, the integrated plants of the other models, float16 value planes. */
+ * Lookahead under a disturbance and a greedy flight under hjb_rollout_set_noise's sampled noise: hjb_rollout_run_lookahead below.
+ * Out of scope: the integrated plants of the other models, float16 value planes. */
 int32_t hjb_rollout_set_values(void *rollout, int32_t dtype, int32_t n_planes, const void *values);
 int32_t hjb_rollout_run_greedy(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj,
                                const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
@@ -528,6 +528,64 @@ int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots
                                 const double *r, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
                                 const int32_t *value_plane_of_step, int64_t n_traj, const double *X0, double *X_final,
                                 double *cost, double *X_path, double *U_path, double *L_path, double *V_path);
+
+/* ---- disturbance-aware greedy rollouts: E_w / max_w lookahead, on a nominal or a noisy plant (kernel K27) -----------------------
+ *   u_k(x) = argmin_l  g(x, u_l) + E_w[ J_{k+1}(A x + B u_l + c + e_w) ]      (HJB_DIST_EXPECT: sum_w p_w (.); HJB_DIST_WORST: max_w)
+ * - the controller that is exactly optimal for the problem hjb_set_disturbance poses, evaluated at the state actually visited:
+ * hjb_rollout_run_greedy with the disturbed backup's combine inside every candidate, and optionally hjb_rollout_run_noisy's plant.
+ * hjb_rollout_set_lookahead gives the object a lookahead node set, in hjb_set_disturbance's layout (offsets [D, n_nodes]
+ * column-major, weights [n_nodes], HJB_DIST_EXPECT only, NULL = 1.0 / n_nodes each; n_nodes == 0 detaches).  Weights are used as
+ * given: they are NOT normalised (hjb_set_disturbance's rule in its float64 typing).  The lookahead set is what the controller
+ * believes; the set of hjb_rollout_set_noise is the plant.  They are two independent properties of the object and may differ:
+ * flying a controller designed for one noise under another is a use, not an error.  ONLY hjb_rollout_run_lookahead reads the
+ * lookahead set: every other run function of an object that holds one gives the bits it gave before.
+ * hjb_rollout_run_lookahead steps n_traj trajectories n_steps times under the affine model, one GPU thread each, all in double,
+ * every product rounded.  Step k at the state x (csrc/hjbdp_lookahead.h, shared by the kernel and the host twin):
+ *   1. p = value_plane_of_step[k]: a plane of hjb_rollout_set_values' values, or -1 for the zero function;
+ *   2. the state parts gs and as_a, once: hjb_rollout_run_greedy's;
+ *   3. for label l = 0 .. n_labels-1 in this order: u, g_l and xn_a are hjb_rollout_run_greedy's operations exactly; then
+ *        - an axis outside the lookahead mask (the axes with at least one lookahead offset that is not +-0): its cell and t_a are
+ *          formed from xn_a once per candidate and shared by the nodes; the axis is not touched, not even by + 0.0;
+ *        - per node w = 0 .. n_nodes-1 in order: q_aw = xn_a + e[a][w] on every masked axis, its cell by the exact search clamped
+ *          to [0, n-2] and t = (q_aw - k[cell]) * rdx[cell]; v_w = the N-linear blend of plane p (fma lerps axis 0 first,
+ *          pairwise: hjb_rollout_run_greedy's blend at that point);
+ *        - HJB_DIST_EXPECT: acc = p_0 * v_0 rounded, then acc = fma(p_w, v_w, acc) in node order;
+ *          HJB_DIST_WORST:  acc = v_0, then acc = v_w > acc ? v_w : acc (the first maximum wins, a NaN never replaces);
+ *          plane -1: acc = +0.0 and nothing is read;
+ *        - cand_l = g_l + acc;
+ *   4. best = cand_0; label l >= 1 replaces iff cand_l < best (the first minimum wins, a NaN candidate never replaces);
+ *   5. the chosen label applied: cost += g, x = xn - formed again from the same operands;
+ *   6. fly_noise = 1 only, hjb_rollout_run_noisy's sampler with nothing changed: a Philox block when (k & 3) == 0, the drawn node
+ *      w' of the hjb_rollout_set_noise set, x_a = x_a + d[a][w'] on that set's mask only.  Streams s = first_stream + i count
+ *      through the call whatever option "chunk" says.
+ * So with ONE lookahead node of zero offsets and weight 1 (or NULL weights) and fly_noise = 0 it equals hjb_rollout_run_greedy
+ * bit for bit; one step from a grid node under hjb_set_disturbance's set returns the disturbed backup's label and (HJB_F64) value.
+ * X0, X_final, cost, X_path, U_path, L_path, V_path: hjb_rollout_run_greedy's; W_path [n_traj, n_steps]: the drawn node of every
+ * step, as a double (fly_noise = 1 only).  fly_noise = 0: the plant is nominal, seed and first_stream are ignored.  Options
+ * "chunk" and "lds" as in hjb_rollout_run; the lookahead block [p | e] is read through scalar registers and never staged; in the
+ * LDS form the flight block is staged behind knots, 1/dx and u_table, the 32 KiB rule applied to the sum.
+ * hjb_rollout_lookahead_host runs the same functions on the CPU, with no device and no object: hjb_rollout_greedy_host's
+ * arguments, then the lookahead set (n_nodes >= 1), then optionally the nodes to fly - nodes [n_traj, n_steps] (trajectory
+ * fastest: what hjb_rollout_noise_draw writes; NULL: a nominal plant) of the n_flight_nodes flight offsets [D, n_flight_nodes]
+ * column-major, added on the axes that have an offset that is not +-0.  Its L_path holds the 0-based label.
+ * Refused before any device work, outputs untouched (text: hjb_rollout_last_error) - HJB_E_INVALID: a null handle; a mode other
+ * than the two; n_nodes outside 0..HJB_DIST_MAX_NODES; null offsets with n_nodes > 0; an offset that is not finite; a weight that
+ * is not finite or is negative; weights given with HJB_DIST_WORST; hjb_rollout_run_lookahead with no lookahead set, with fly_noise
+ * other than 0 or 1, with fly_noise = 1 and no noise set, first_stream < 0 or first_stream + n_traj overflowing, with fly_noise = 0
+ * and a W_path, and everything hjb_rollout_run_greedy refuses.
+ * Out of scope: the integrated plants of the other models, float16 value planes, noise that depends on the control or the state. */
+int32_t hjb_rollout_set_lookahead(void *rollout, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights);
+int32_t hjb_rollout_run_lookahead(void *rollout, int32_t fly_noise, int32_t n_steps, const int32_t *value_plane_of_step,
+                                  int64_t n_traj, const double *X0, uint64_t seed, int64_t first_stream, double *X_final,
+                                  double *cost, double *X_path, double *U_path, double *L_path, double *V_path, double *W_path,
+                                  double *device_ms);
+int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u,
+                                   const double *u_table, const double *A, const double *B, const double *c, const double *q,
+                                   const double *r, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
+                                   const int32_t *value_plane_of_step, int64_t n_traj, const double *X0, double *X_final,
+                                   double *cost, double *X_path, double *U_path, double *L_path, double *V_path, int32_t mode,
+                                   int32_t n_nodes, const double *offsets, const double *weights, const int32_t *nodes,
+                                   int32_t n_flight_nodes, const double *flight_offsets);
 
 /* The 6-D attitude closed loop (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run) on the same object.
  * hjb_rollout_set_attitude_model and hjb_rollout_set_model replace each other: the last one set wins.  It needs D == 6, n_u == 3

@@ -128,6 +128,22 @@ int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots
                                 const double *r, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
                                 const int32_t *value_plane_of_step, int64_t n_traj, const double *X0, double *X_final,
                                 double *cost, double *X_path, double *U_path, double *L_path, double *V_path);
+/* the same loop with hjb_set_disturbance's E_w / max_w inside every candidate (kernel K27): a lookahead node set in
+ * hjb_set_disturbance's layout (mode 0 = expect, 1 = worst; n_nodes 0 detaches), flown on a nominal plant (fly_noise 0) or under
+ * hjb_rollout_set_noise's set (fly_noise 1, W_path the drawn nodes); the host twin needs no device and no object (hjbdp.h); usage:
+ * matlab/Dynamic_Solver_hjbdp_get_lookahead_paths.m */
+int32_t hjb_rollout_set_lookahead(void *rollout, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights);
+int32_t hjb_rollout_run_lookahead(void *rollout, int32_t fly_noise, int32_t n_steps, const int32_t *value_plane_of_step,
+                                  int64_t n_traj, const double *X0, uint64_t seed, int64_t first_stream, double *X_final,
+                                  double *cost, double *X_path, double *U_path, double *L_path, double *V_path, double *W_path,
+                                  double *device_ms);
+int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u,
+                                   const double *u_table, const double *A, const double *B, const double *c, const double *q,
+                                   const double *r, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
+                                   const int32_t *value_plane_of_step, int64_t n_traj, const double *X0, double *X_final,
+                                   double *cost, double *X_path, double *U_path, double *L_path, double *V_path, int32_t mode,
+                                   int32_t n_nodes, const double *offsets, const double *weights, const int32_t *nodes,
+                                   int32_t n_flight_nodes, const double *flight_offsets);
 /* the 6-D attitude loop on the same object (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run);
  * usage: matlab/Solver_attitude_hjbdp_get_optimal_paths.m */
 int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, double h, int32_t integrator, const double *q,

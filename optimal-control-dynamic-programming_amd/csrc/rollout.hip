@@ -10,12 +10,16 @@
 // And it may hold value planes (hjb_rollout_set_values): hjb_rollout_run_greedy (K26, kernels_rollout_greedy.h /
 // rollout_greedy.hip) flies the affine loop by one-step lookahead on them, and no other run function reads them.  Its host twin
 // hjb_rollout_greedy_host (hjbdp_greedy.h) needs no device and no object.
+// And a lookahead node set (hjb_rollout_set_lookahead): hjb_rollout_run_lookahead (K27, kernels_rollout_lookahead.h /
+// rollout_lookahead.hip, rollout_lookahead_fly.hip) flies the affine loop by lookahead under that set, on a nominal plant or under
+// the noise set, and no other run function reads it.  Its host twin hjb_rollout_lookahead_host (hjbdp_lookahead.h) needs no device.
 // Defined here for both host units (rollout_host.h): rfail, check_run / check_traj / check_quaternions (the run functions'
 // refusals, all before any device work), upload, run_chunks (the chunk loop).  No kernel is instantiated in this unit.
 #include "rollout_host.h"
 #include "rollout_dispatch.h"
 #include "kernels_rollout_attitude_linear.h"
 #include "kernels_rollout_greedy.h"
+#include "kernels_rollout_lookahead.h"
 
 using namespace hjbhost;
 
@@ -25,6 +29,7 @@ void release(Rollout *ro) {
     ro->att.reset();
     ro->noise.reset();
     ro->values.reset();
+    ro->look.reset();
     ro->data.reset();
     if (ro->stream) (void)hipStreamDestroy(ro->stream);
     ro->stream = nullptr;
@@ -75,6 +80,22 @@ int check_grid(const char *who, int D, const int32_t *n, const double *knots, in
     }
     *nS_out = nS;
     *n_knots_out = n_knots;
+    return HJB_OK;
+}
+
+// What hjb_rollout_set_lookahead and hjb_rollout_lookahead_host refuse of a lookahead node set, hjb_set_disturbance's refusals, in
+// `who`'s name (D < 1: the offsets are left to the caller, who knows D).  HJB_OK otherwise.
+int check_lookahead(Rollout *ro, const char *who, int D, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights) {
+    if (mode != HJB_DIST_EXPECT && mode != HJB_DIST_WORST)
+        return rfail(ro, HJB_E_INVALID, "%s: mode %d is not HJB_DIST_EXPECT / HJB_DIST_WORST", who, mode);
+    if (n_nodes < 0 || n_nodes > HJB_DIST_MAX_NODES) return rfail(ro, HJB_E_INVALID, "%s: n_nodes=%d not in 0..%d", who, n_nodes, HJB_DIST_MAX_NODES);
+    if (n_nodes > 0 && !offsets) return rfail(ro, HJB_E_INVALID, "%s: null offsets with n_nodes=%d", who, n_nodes);
+    if (n_nodes > 0 && weights && mode == HJB_DIST_WORST) return rfail(ro, HJB_E_INVALID, "%s: weights given with HJB_DIST_WORST", who);
+    for (int w = 0; weights && w < n_nodes; ++w)
+        if (!std::isfinite(weights[w]) || weights[w] < 0) return rfail(ro, HJB_E_INVALID, "%s: weight %d is not finite or is negative", who, w);
+    for (int w = 0; w < n_nodes; ++w)
+        for (int a = 0; a < D; ++a)
+            if (!std::isfinite(offsets[a + (int64_t)D * w])) return rfail(ro, HJB_E_INVALID, "%s: offset of axis %d, node %d is not finite", who, a, w);
     return HJB_OK;
 }
 
@@ -660,6 +681,168 @@ int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots
             using TV = std::conditional_t<decltype(f)::value, float, double>;
             greedy_rollout_host<decltype(d)::value, TV>(M, knots, rdx.data(), u_table, static_cast<const TV *>(values), n_steps,
                                                         value_plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, L_path, V_path);
+        });
+    });
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_set_lookahead(void *rollout, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights) {
+    Rollout *ro = (Rollout *)rollout;
+    const char *const who = "hjb_rollout_set_lookahead";
+    // the arguments that need no object first, then the object; every refusal before any device work
+    if (const int bad = check_lookahead(ro, who, 0, mode, n_nodes, offsets, weights)) return bad;
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "%s: null handle", who);
+    std::lock_guard<std::mutex> g(ro->mu);
+    const int D = ro->D;
+    if (const int bad = check_lookahead(ro, who, D, mode, n_nodes, offsets, weights)) return bad;
+    LookSet L{};
+    L.mode = mode;
+    std::vector<double> tab((size_t)n_nodes * (1 + D));
+    const int n_tab = look_table(D, n_nodes, offsets, weights, L, tab.data());
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
+    std::shared_ptr<DevData> nd;
+    const void *d = nullptr;
+    if (n_nodes > 0) {
+        nd = std::make_shared<DevData>(ro->device);
+        if (const int st = upload(ro, *nd, tab.data(), (size_t)n_tab * sizeof(double), &d)) return st;
+    }
+    if (ro->stream) (void)hipStreamSynchronize(ro->stream);
+    ro->look = std::move(nd);                                 // replaces (and releases) a node set given earlier
+    ro->L = L;
+    ro->L.tab = (const double *)d;
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_run_lookahead(void *rollout, int32_t fly_noise, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj,
+                                  const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost, double *X_path,
+                                  double *U_path, double *L_path, double *V_path, double *W_path, double *device_ms) {
+    Rollout *ro = (Rollout *)rollout;
+    const char *const who = "hjb_rollout_run_lookahead";
+    // every refusal before any device work, the outputs untouched; the ones that need no object first
+    if (fly_noise != 0 && fly_noise != 1) return rfail(ro, HJB_E_INVALID, "%s: fly_noise=%d is not 0 or 1", who, fly_noise);
+    if (!fly_noise && W_path) return rfail(ro, HJB_E_INVALID, "%s: W_path given with fly_noise=0 (a nominal plant draws no node)", who);
+    if (fly_noise && first_stream < 0) return rfail(ro, HJB_E_INVALID, "%s: first_stream=%lld < 0", who, (long long)first_stream);
+    if (fly_noise && n_traj > 0 && first_stream > INT64_MAX - n_traj)
+        return rfail(ro, HJB_E_INVALID, "%s: first_stream + n_traj overflows (%lld + %lld)", who, (long long)first_stream, (long long)n_traj);
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
+    if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
+    if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_model", who);
+    if (ro->model != kModelAffine)
+        return rfail(ro, HJB_E_INVALID, "rollout: %s needs the affine model (hjb_rollout_set_model); the object holds another", who);
+    if (ro->L.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_lookahead", who);
+    if (fly_noise && ro->N.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s with fly_noise=1 before hjb_rollout_set_noise", who);
+    if (n_steps > 0 && !value_plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null value_plane_of_step");
+    for (int k = 0; k < n_steps; ++k) {
+        const int32_t p = value_plane_of_step[k];
+        if (p >= 0 && ro->val_planes < 1)
+            return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_values (value_plane_of_step[%d] = %d; only -1 needs no values)",
+                         who, k, p);
+        if (p < -1 || p >= ro->val_planes)
+            return rfail(ro, HJB_E_INVALID, "rollout: value_plane_of_step[%d] = %d outside [-1, %d)", k, p, ro->val_planes);
+    }
+    if (n_traj == 0) {
+        if (device_ms) *device_ms = 0.0;
+        return HJB_OK;
+    }
+    const int D = ro->D;
+    const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
+    if (bad_traj) return bad_traj;
+    if (device_ms) *device_ms = 0.0;
+    DNoise N = ro->N;
+    N.seed = seed;
+    ChunkPlan plan{who, D, n_steps, value_plane_of_step, n_traj, X0, X_final,
+                   {{X_path, D, n_steps + 1}, {U_path, ro->R.n_u, n_steps}, {L_path, 1, n_steps}, {V_path, 1, n_steps}, {W_path, 1, n_steps}},
+                   cost, device_ms};
+    return run_chunks(ro, plan, [&](const Chunk &c) {
+        DLook A{};
+        A.G.R = c.R;
+        A.G.values = ro->dvalues;
+        A.G.nc = c.nc;
+        A.G.X0 = c.X0;
+        A.G.Xf = c.Xf;
+        A.G.cost = c.cost;
+        A.G.Xp = c.path[0];
+        A.G.Up = c.path[1];
+        A.G.Lp = c.path[2];
+        A.G.Vp = c.path[3];
+        A.L = ro->L;
+        if (!fly_noise) return launch_rollout_lookahead(ro->val_bytes, c.lds_on, D, A, c.lds, c.st);
+        A.N = N;
+        A.N.first = (uint64_t)first_stream + (uint64_t)c.i0;  // the chunk's offset in the call: streams count through the call
+        A.N.Wp = c.path[4];
+        const size_t lds_all = c.lds + (size_t)N.n_tab * sizeof(double);
+        return launch_rollout_lookahead_fly(ro->val_bytes, ro->lds && lds_all <= kLdsMax, D, A, lds_all, c.st);
+    });
+}
+
+int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
+                                   const double *A, const double *B, const double *c, const double *q, const double *r, int32_t dtype,
+                                   int32_t n_value_planes, const void *values, int32_t n_steps, const int32_t *value_plane_of_step,
+                                   int64_t n_traj, const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
+                                   double *L_path, double *V_path, int32_t mode, int32_t n_nodes, const double *offsets,
+                                   const double *weights, const int32_t *nodes, int32_t n_flight_nodes, const double *flight_offsets) {
+    const char *const who = "hjb_rollout_lookahead_host";
+    if (D < 1 || D > HJB_MAX_D) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, HJB_MAX_D);
+    if (n_u < 1 || n_u > HJB_ROLLOUT_MAX_U) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: n_u=%d not in 1..%d", who, n_u, HJB_ROLLOUT_MAX_U);
+    if (!n || !knots || !u_table || !A || !B) return rfail(nullptr, HJB_E_INVALID, "%s: null argument (n, knots, u_table, A and B are required)", who);
+    if (n_labels < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_labels=%d < 1", who, n_labels);
+    if (dtype != HJB_F32 && dtype != HJB_F64) return rfail(nullptr, HJB_E_INVALID, "%s: dtype %d is not HJB_F32 / HJB_F64", who, dtype);
+    if (n_value_planes < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_value_planes=%d < 0", who, n_value_planes);
+    if (n_value_planes > 0 && !values) return rfail(nullptr, HJB_E_INVALID, "%s: null values with n_value_planes=%d", who, n_value_planes);
+    if (n_steps < 0 || n_traj < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_steps=%d, n_traj=%lld (both >= 0)", who, n_steps, (long long)n_traj);
+    if (const int bad = check_lookahead(nullptr, who, D, mode, n_nodes, offsets, weights)) return bad;
+    if (n_nodes < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_nodes=%d < 1 (the lookahead needs a node set)", who, n_nodes);
+    if (nodes) {
+        if (n_flight_nodes < 1 || n_flight_nodes > HJB_DIST_MAX_NODES)
+            return rfail(nullptr, HJB_E_INVALID, "%s: n_flight_nodes=%d not in 1..%d", who, n_flight_nodes, HJB_DIST_MAX_NODES);
+        if (!flight_offsets) return rfail(nullptr, HJB_E_INVALID, "%s: nodes given with null flight_offsets", who);
+        if (!all_finite(flight_offsets, (int64_t)D * n_flight_nodes)) return rfail(nullptr, HJB_E_INVALID, "%s: flight_offsets is not finite", who);
+    }
+    int64_t nS = 1, n_knots = 0;
+    if (const int bad_grid = check_grid(who, D, n, knots, &nS, &n_knots)) return bad_grid;
+    if (!all_finite(u_table, (int64_t)n_labels * n_u)) return rfail(nullptr, HJB_E_INVALID, "%s: u_table is not finite", who);
+    if (!all_finite(A, (int64_t)D * D) || !all_finite(B, (int64_t)D * n_u) || !all_finite(c, D) || !all_finite(q, D) || !all_finite(r, n_u))
+        return rfail(nullptr, HJB_E_INVALID, "%s: the model (A, B, c, q, r) is not finite", who);
+    if (n_steps > 0 && !value_plane_of_step) return rfail(nullptr, HJB_E_INVALID, "%s: null value_plane_of_step", who);
+    for (int k = 0; k < n_steps; ++k)
+        if (value_plane_of_step[k] < -1 || value_plane_of_step[k] >= n_value_planes)
+            return rfail(nullptr, HJB_E_INVALID, "%s: value_plane_of_step[%d] = %d outside [-1, %d)", who, k, value_plane_of_step[k], n_value_planes);
+    if (n_traj == 0) return HJB_OK;
+    const int bad_traj = check_traj(nullptr, who, D, "D", n_steps, n_traj, X0, X_final);
+    if (bad_traj) return bad_traj;
+    if (nodes)
+        for (int64_t e = 0; e < n_traj * (int64_t)n_steps; ++e)
+            if (nodes[e] < 0 || nodes[e] >= n_flight_nodes)
+                return rfail(nullptr, HJB_E_INVALID, "%s: nodes element %lld = %d outside [0, %d)", who, (long long)e, nodes[e], n_flight_nodes);
+    GreedyModel M{};
+    std::vector<double> rdx((size_t)n_knots);
+    greedy_grid(D, n, knots, M, rdx.data());
+    M.n_u = n_u;
+    M.n_labels = n_labels;
+    M.has_c = c ? 1 : 0;
+    std::memcpy(M.A, A, sizeof(double) * D * D);
+    std::memcpy(M.B, B, sizeof(double) * D * n_u);
+    if (c) std::memcpy(M.c, c, sizeof(double) * D);
+    if (q) std::memcpy(M.q, q, sizeof(double) * D);
+    if (r) std::memcpy(M.r, r, sizeof(double) * n_u);
+    LookSet L{};
+    L.mode = mode;
+    std::vector<double> tab((size_t)n_nodes * (1 + D));
+    (void)look_table(D, n_nodes, offsets, weights, L, tab.data());
+    L.tab = tab.data();
+    int fmask = 0;                                            // the flight set's mask, as hjb_rollout_set_noise forms it
+    for (int w = 0; nodes && w < n_flight_nodes; ++w)
+        for (int a = 0; a < D; ++a)
+            if (flight_offsets[a + (int64_t)D * w] != 0.0) fmask |= 1 << a;
+    with_bool(dtype == HJB_F32, [&](auto f) {
+        with_dim(D, [&](auto d) {
+            using TV = std::conditional_t<decltype(f)::value, float, double>;
+            lookahead_rollout_host<decltype(d)::value, TV>(M, L, knots, rdx.data(), u_table, static_cast<const TV *>(values), n_steps,
+                                                           value_plane_of_step, n_traj, X0, nodes, fmask, flight_offsets, X_final, cost,
+                                                           X_path, U_path, L_path, V_path);
         });
     });
     return HJB_OK;

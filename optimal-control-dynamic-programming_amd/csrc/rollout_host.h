@@ -7,6 +7,7 @@
 #include "kernels_rollout_attitude.h"
 #include "kernels_rollout_noisy.h"
 #include "kernels_rollout_pos_att.h"
+#include "hjbdp_lookahead.h"
 #include <functional>
 #include <memory>
 
@@ -56,6 +57,9 @@ struct Rollout {
     std::shared_ptr<DevData> values;
     const void *dvalues = nullptr;      // [nS, val_planes] column-major, float or double
     int val_planes = 0, val_bytes = 8;
+    // the lookahead node set (hjb_rollout_set_lookahead): L.n_nodes > 0 while one is set; read by hjb_rollout_run_lookahead alone
+    hjb::LookSet L{};
+    std::shared_ptr<DevData> look;      // L.tab: the weights, then the masked axes' offsets
     hipStream_t stream = nullptr;
     std::string err;
 };
@@ -87,7 +91,7 @@ int upload(Rollout *ro, DevData &dd, const void *src, size_t bytes, const void *
 
 // The chunk loop the run functions share.  A run function fills a ChunkPlan; run_chunks calls its launch once per chunk of at
 // most Rollout::chunk trajectories with that chunk's device buffers.
-constexpr int kMaxPaths = 4, kMaxInputs = 3;
+constexpr int kMaxPaths = 5, kMaxInputs = 3;
 
 struct ChunkPlan {
     const char *who;                // the entry point, for the error text

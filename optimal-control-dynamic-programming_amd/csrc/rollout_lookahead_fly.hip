@@ -1,0 +1,11 @@
+// rollout_lookahead_fly.hip - K27's 24 noisy-plant instantiations (kernels_rollout_lookahead.h: D x value type x LDS, FLY = true) in
+// a unit of their own, behind launch_rollout_lookahead_fly (called by hjb_rollout_run_lookahead in rollout.hip).
+#include "kernels_rollout_lookahead.h"
+
+namespace hjb {
+
+hipError_t launch_rollout_lookahead_fly(int val_bytes, bool lds_on, int D, const DLook &A, size_t lds, hipStream_t st) {
+    return launch_rollout_lookahead_form<true>(val_bytes, lds_on, D, A, lds, st);
+}
+
+}  // namespace hjb

@@ -242,6 +242,15 @@ SYMBOLS = {
     "hjb_rollout_greedy_host": (C.c_int32, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32]
                                 + [C.POINTER(C.c_double)] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
                                                                   C.c_int64] + [C.POINTER(C.c_double)] * 7),
+    # the same loop with the disturbed backup's E_w / max_w inside every candidate, on a nominal or a noisy plant, and its host twin
+    "hjb_rollout_set_lookahead": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "hjb_rollout_run_lookahead": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_double),
+                                              C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 8),
+    "hjb_rollout_lookahead_host": (C.c_int32, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32]
+                                   + [C.POINTER(C.c_double)] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
+                                                                     C.c_int64] + [C.POINTER(C.c_double)] * 7
+                                   + [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32,
+                                      C.POINTER(C.c_double)]),
     "hjb_rollout_set_attitude_model": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_int32, C.POINTER(C.c_double),
                                                    C.POINTER(C.c_double)]),
     "hjb_rollout_run_attitude": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]

@@ -164,6 +164,7 @@ def _value_planes(J, nS):
 
 
 _LOOKUP = {"nearest": _abi.HJB_LOOKUP_NEAREST, "linear": _abi.HJB_LOOKUP_LINEAR}
+_DIST_MODE = {"expect": _abi.HJB_DIST_EXPECT, "worst": _abi.HJB_DIST_WORST}
 _ATT_INTEGRATOR = {"taylor": _abi.HJB_ATT_TAYLOR, "RK4": _abi.HJB_ATT_RK4, "rk4": _abi.HJB_ATT_RK4}
 
 
@@ -356,6 +357,46 @@ class Rollout:
             paths["V_path"] = paths["V_path"][:, 0, :]
         return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
 
+    def set_lookahead(self, offsets, weights=None, mode="expect"):
+        """A lookahead node set for run_lookahead (hjb_rollout_set_lookahead): what Backup.set_disturbance takes - offsets [D, W],
+        weights [W] (mode "expect" only; None = 1 / W each; used as given, not normalised), mode "expect" or "worst".  It is
+        what the controller believes; set_noise's set is the plant, and the two may differ.  run_lookahead alone reads it."""
+        off, w, mode = check_disturbance(self.D, offsets, weights, mode)
+        offc = np.ascontiguousarray(off.reshape(-1, order="F"))
+        self._check(self.lib.hjb_rollout_set_lookahead(self._ro, _DIST_MODE[mode], off.shape[1], _f64p(offc), _f64p(w)))
+
+    def clear_lookahead(self):
+        """Detach the lookahead node set (hjb_rollout_set_lookahead with n_nodes = 0)."""
+        self._check(self.lib.hjb_rollout_set_lookahead(self._ro, _abi.HJB_DIST_EXPECT, 0, None, None))
+
+    def run_lookahead(self, X0, value_plane_of_step, noisy=False, seed=0, first_stream=0, keep_path=False):
+        """run_greedy with the disturbed backup inside every candidate (hjb_rollout_run_lookahead): at every step the row of
+        u_table that minimises g(x, u) + E_w J(A x + B u + c + e_w) (or max_w) over set_lookahead's nodes, J the plane
+        value_plane_of_step[k] of set_values (-1: the zero function).  noisy=False flies the nominal plant (seed and first_stream
+        are not read); noisy=True flies run_noisy's plant under set_noise's nodes, trajectory i on the stream first_stream + i
+        of `seed`.  Returns run_greedy's dict plus W_path [n_traj, n_steps] int32, the drawn nodes (None unless noisy and
+        keep_path)."""
+        D, nu = self.D, self.n_u
+        X = _starts(X0, D)
+        nt = X.shape[0]
+        ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
+        K = int(ps.size)
+        Xf = np.empty((nt, D))
+        cost = np.empty(nt)
+        flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K), ("L_path", 1, K), ("V_path", 1, K),
+                                    ("W_path", 1, K))
+        if not noisy:
+            flat[4], paths["W_path"] = None, None
+        ms = C.c_double(0.0)
+        self._check(self.lib.hjb_rollout_run_lookahead(self._ro, 1 if noisy else 0, K, _i32p(ps), nt, _f64p(X), int(seed) & (2 ** 64 - 1),
+                                                       int(first_stream), _f64p(Xf), _f64p(cost), *map(_f64p, flat), C.byref(ms)))
+        if keep_path:
+            paths["L_path"] = paths["L_path"][:, 0, :].astype(np.int32)
+            paths["V_path"] = paths["V_path"][:, 0, :]
+            if noisy:
+                paths["W_path"] = paths["W_path"][:, 0, :].astype(np.int32)
+        return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
+
     def set_attitude_model(self, inertia, h, integrator="taylor", q=None, r=None):
         """The 6-D attitude loop instead of the affine one (hjb_rollout_set_attitude_model; the last model set wins):
         inertia = (J1, J2, J3), step h, integrator 'taylor' or 'RK4', stage-cost weights q [7] and r [3] (None: zeros).
@@ -542,6 +583,56 @@ def greedy_host(knots, u_table, A, B, J, X0, value_plane_of_step, c=None, q=None
                                                   _f64p(_f64_vec(q, D)), _f64p(_f64_vec(r, nu)), dtype, 0 if v is None else v.size // nS,
                                                   None if v is None else v.ctypes.data, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
                                                   *map(_f64p, flat)))
+    if keep_path:
+        paths["L_path"] = paths["L_path"][:, 0, :].astype(np.int32) + np.int32(index_base)
+        paths["V_path"] = paths["V_path"][:, 0, :]
+    return {"X_final": Xf.T, "cost": cost, **paths}
+
+
+def lookahead_host(knots, u_table, A, B, J, X0, value_plane_of_step, offsets, weights=None, mode="expect", c=None, q=None, r=None,
+                   index_base=0, nodes=None, flight_offsets=None, keep_path=False):
+    """Rollout.run_lookahead on the CPU (hjb_rollout_lookahead_host; no device, no object): greedy_host's arguments, the
+    lookahead set as set_lookahead takes it, and optionally the plant's noise as GIVEN nodes - nodes [n_traj, n_steps] int32
+    (noise_draw's output) into flight_offsets [D, W_f] (set_noise's offsets); None flies the nominal plant.  Returns
+    run_greedy's dict without device_ms; L_path holds label + index_base."""
+    lib = load_library()
+    ks = [np.ascontiguousarray(k, dtype=np.float64).reshape(-1) for k in knots]
+    D = len(ks)
+    n = [len(k) for k in ks]
+    nS = int(np.prod(n, dtype=np.int64)) if ks else 1
+    ut = np.asarray(u_table, dtype=np.float64)
+    ut = ut.reshape(-1, 1) if ut.ndim == 1 else ut
+    n_labels, nu = ut.shape
+    ut = np.ascontiguousarray(ut.reshape(-1, order="F"))
+    kcat = np.ascontiguousarray(np.concatenate(ks) if ks else np.zeros(0))
+    v, dtype = (None, _abi.HJB_F64) if J is None else _value_planes(J, nS)
+    X = _starts(X0, D)
+    nt = X.shape[0]
+    ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
+    K = int(ps.size)
+    off, w, mode = check_disturbance(D, offsets, weights, mode)
+    offc = np.ascontiguousarray(off.reshape(-1, order="F"))
+    nd = fo = None
+    Wf = 0
+    if nodes is not None:
+        if flight_offsets is None:
+            raise ValueError("nodes need flight_offsets [D, W_f]")
+        fo2 = np.array(flight_offsets, dtype=np.float64, ndmin=2).reshape(D, -1)
+        Wf = fo2.shape[1]
+        fo = np.ascontiguousarray(fo2.reshape(-1, order="F"))
+        nd = np.asarray(nodes)
+        if nd.shape != (nt, K) or nd.dtype.kind not in "iu":
+            raise ValueError("nodes must be [n_traj=%d, n_steps=%d] integers, got %r %s" % (nt, K, nd.shape, nd.dtype))
+        nd = np.ascontiguousarray(nd.astype(np.int32).reshape(-1, order="F"))
+    Xf = np.empty((nt, D))
+    cost = np.empty(nt)
+    flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K), ("L_path", 1, K), ("V_path", 1, K))
+    _check(lib, None, lib.hjb_rollout_lookahead_host(D, (C.c_int32 * max(D, 1))(*n), _f64p(kcat), int(n_labels), int(nu), _f64p(ut),
+                                                     _f64p(_f64_colmajor(A, D, D)), _f64p(_f64_colmajor(B, D, nu)), _f64p(_f64_vec(c, D)),
+                                                     _f64p(_f64_vec(q, D)), _f64p(_f64_vec(r, nu)), dtype, 0 if v is None else v.size // nS,
+                                                     None if v is None else v.ctypes.data, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
+                                                     *map(_f64p, flat), _DIST_MODE[mode], off.shape[1], _f64p(offc), _f64p(w), _i32p(nd),
+                                                     int(Wf), _f64p(fo)))
     if keep_path:
         paths["L_path"] = paths["L_path"][:, 0, :].astype(np.int32) + np.int32(index_base)
         paths["V_path"] = paths["V_path"][:, 0, :]

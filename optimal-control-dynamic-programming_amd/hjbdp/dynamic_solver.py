@@ -243,7 +243,8 @@ class Dynamic_Solver:
         (1..N-1).  Returns X [S, N, n] and U [N, n] as get_optimal_paths does (U[N-1] = 0); leaves the closed-loop costs in
         self.greedy_cost [n] - beside self.paths_cost what the stored labels lose to the value function they came from - and
         the kernel's time in self.greedy_paths_ms.  The lookahead is NOMINAL even when self.disturbance is set: J_star then
-        is the disturbed handle's cost-to-go, but the candidate's next state carries no node."""
+        is the disturbed handle's cost-to-go, but the candidate's next state carries no node - get_lookahead_paths is the loop
+        that looks ahead under self.disturbance."""
         from .core import Rollout
         if self.J_star is None or self.u_star_idxs is None:
             raise RuntimeError("run() first")
@@ -269,6 +270,59 @@ class Dynamic_Solver:
         U[:n_st] = out["U_path"][:, 0, :].T
         self.greedy_cost = out["cost"]
         self.greedy_paths_ms = out["device_ms"]
+        return X, U
+
+    def get_lookahead_paths(self, X0s, n_samples=None, seed=0, mode="Nssu", ssu_num=1):
+        """The closed loop of the DISTURBED cost-to-go, on the GPU (hjbdp.Rollout.run_lookahead): get_greedy_paths with
+        self.disturbance's E_w (or max_w, in that set's own mode) inside every candidate - the control of U_mesh that minimises
+        x'Qx + R u^2 + E_w J_{k+1}(A x + B u + d_w) at the state actually visited, the controller the disturbed solve is exactly
+        optimal for.  Planes and `mode` / `ssu_num` as in get_greedy_paths.
+        n_samples None: the nominal plant; returns X [S, N, n] and U [N, n] as get_greedy_paths does and leaves the costs in
+        self.lookahead_cost [n].  n_samples given: every start flown n_samples times under the same nodes, sample j of start i
+        on stream i * n_samples + j of `seed` (get_noisy_paths' numbering; a 'worst' set is sampled uniformly); returns the
+        closed-loop costs [n, n_samples] and leaves their mean, standard deviation and maximum per start in
+        self.lookahead_cost_mean / _std / _max [n].  The kernel's time: self.lookahead_paths_ms."""
+        from .core import Rollout
+        if self.J_star is None or self.u_star_idxs is None:
+            raise RuntimeError("run() first")
+        if self.disturbance is None:
+            raise RuntimeError("get_lookahead_paths needs self.disturbance = (offsets [2, W], weights or None, mode)")
+        offsets, weights = self.disturbance[0], self.disturbance[1]
+        dmode = self.disturbance[2] if len(self.disturbance) > 2 else "expect"
+        N, S = self.N, self.S
+        n_st = N - 1
+        if mode == "ssu":
+            if not 1 <= int(ssu_num) <= n_st:
+                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
+            planes = np.full(n_st, int(ssu_num), dtype=np.int32)
+        elif mode == "Nssu":
+            planes = np.arange(1, N, dtype=np.int32)
+        else:
+            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        if n_samples is not None and int(n_samples) < 1:
+            raise ValueError("n_samples must be at least 1")
+        X0s = np.asarray(X0s, dtype=np.float64).reshape(S, -1)
+        n = X0s.shape[1]
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
+        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
+            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+            ro.set_values(self.J_star)
+            ro.set_lookahead(offsets, weights, dmode)
+            if n_samples is None:
+                out = ro.run_lookahead(X0s, planes, keep_path=True)
+            else:
+                ro.set_noise(offsets, weights)
+                out = ro.run_lookahead(np.repeat(X0s, int(n_samples), axis=1), planes, noisy=True, seed=seed, first_stream=0)
+        self.lookahead_paths_ms = out["device_ms"]
+        if n_samples is not None:
+            cost = out["cost"].reshape(n, int(n_samples))
+            self.lookahead_cost_mean, self.lookahead_cost_std, self.lookahead_cost_max = cost.mean(axis=1), cost.std(axis=1), cost.max(axis=1)
+            return cost
+        X = np.ascontiguousarray(out["X_path"].transpose(1, 2, 0))     # [n, S, N] -> [S, N, n]
+        U = np.zeros((N, n))
+        U[:n_st] = out["U_path"][:, 0, :].T
+        self.lookahead_cost = out["cost"]
         return X, U
 
     @staticmethod

@@ -1,0 +1,56 @@
+"""CPU test: the lookahead rollout kernel's register budget (K27, csrc/kernels_rollout_lookahead.h), read from the code objects
+hipcc produces here for gfx950 (no GPU).  The node loop sits inside the candidate loop inside the step loop; the kernel reads its
+argument record through the argument segment per loop body (csrc/hjbdp_greedy.h, greedy_reread) and the lookahead node block
+through scalar loads, so that no scalar is spilled, and reads a candidate's corners in K26's groups, so that no instantiation
+holds 2^D values.  Every one of the 48 instantiations (D x value type x LDS x FLY) has no vector spill, no scalar spill and no
+private segment, and at most 128 vector registers (four waves per SIMD at 256 threads a block) - except the eight D = 6
+instantiations, which DESIGN.md section 4b names and which are held to 168 (three waves)."""
+import re
+import shutil
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+CSRC = ROOT / "optimal-control-dynamic-programming_amd" / "csrc"
+UNITS = ("rollout_lookahead.hip", "rollout_lookahead_fly.hip")
+FIELDS = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")
+
+
+def three_waves(D, lds, fly):
+    """the instantiations DESIGN.md 4b holds to 168 vector registers: the eight of D = 6 (both value types, staged and not, both
+    plants), which stand at 129 - 136.  Every other one, D = 5 included, is held to 128."""
+    return D == 6
+
+
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    """{(D, value type letter, LDS, FLY): {field: int}} from the metadata notes (.amdhsa.kernels) of the two units"""
+    out = {}
+    tmp = tmp_path_factory.mktemp("lookahead_budget")
+    for unit in UNITS:
+        asm = tmp / (unit + ".s")
+        r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
+                            "-o", str(asm), str(CSRC / unit)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        text = asm.read_text()
+        meta = text[text.index("amdhsa.kernels"):]
+        for blk in re.split(r"\n\s+- \.agpr_count:", meta)[1:]:
+            m = re.search(r"\.name:\s+_ZN3hjb19k_rollout_lookaheadILi(\d)E([fd])Lb([01])ELb([01])EEE", blk)
+            if m:
+                out[(int(m.group(1)), m.group(2), int(m.group(3)), int(m.group(4)))] = {
+                    f: int(re.search(r"\.%s:\s+(\d+)" % f, blk).group(1)) for f in FIELDS}
+    return out
+
+
+def test_every_instantiation_is_built(kernels):
+    assert set(kernels) == {(D, t, l, f) for D in range(1, 7) for t in "fd" for l in (0, 1) for f in (0, 1)}, sorted(kernels)
+
+
+def test_no_instantiation_spills_or_has_a_private_segment(kernels):
+    for key, k in sorted(kernels.items()):
+        assert k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, (key, k)
+        D, _, lds, fly = key
+        assert k["vgpr_count"] <= (168 if three_waves(D, lds, fly) else 128), (key, k)

@@ -21,8 +21,10 @@ Two cases, one JSON line:
       alone, it also writes its line to profiles/rollout_noisy_time.json.
   (j) greedy: the greedy rollout (K26, hjb_rollout_run_greedy) beside K16 'linear' on the same object and starts, see case_greedy;
       alone, it also writes its line to profiles/rollout_greedy_time.json.
+  (k) lookahead: the disturbance-aware greedy rollout (K27, hjb_rollout_run_lookahead) beside K26 and K25, see case_lookahead;
+      alone, it also writes its line to profiles/rollout_lookahead_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy,lookahead] [--out FILE]
 """
 from __future__ import annotations
 
@@ -562,6 +564,75 @@ def case_greedy(host=True, n_traj=1000000):
     return res
 
 
+def case_lookahead(host=True, n_traj=1000000):
+    """(k) lookahead: case_greedy's problem and starts (10^6 trajectories x 129 steps, 100 controls), solved under case_kirk_noisy's
+    9-node Gauss-Hermite set, and in one process on one object: (a) K26 (run_greedy), (b) K27 with ONE lookahead node of zero
+    offsets and a nominal plant (K26's bits), (c) K27 looking ahead under the 9 nodes (expect) on a nominal plant, (d) the same
+    flown under the 9 nodes, and K25 on the stored labels ('linear') under the same seed.  The runs alternate, five rounds after a
+    warm-up round of the same shapes; device_ms (the launches' event times) of all five listed, the medians quoted.
+    Bounds: (b) / (a) <= 1.05 - the bound tools/time_disturbance.py holds the same identity to on K24; (c) / (a) <= 9 - the state
+    parts, the control and the unmasked axes are shared by the nodes, so a node costs no more than a K26 candidate.  `pass`: both.
+    Beside the times the number the feature exists for: the mean closed-loop cost of (d) beside K25's on the stored labels, over
+    the starts whose cost is finite under both.  `host` is not used."""
+    import hjbdp
+    ds = hjbdp.Dynamic_Solver(precision="double")
+    ds.N, ds.dx, ds.du = 130, 35, 100
+    off, w = hjbdp.gaussian_nodes([0.02, 0.05], order=3)
+    ds.disturbance = (off, w, "expect")
+    ds.run()
+    s_r = np.asarray(ds.s_r, dtype=np.float64)
+    rng = np.random.default_rng(1)
+    X0 = rng.uniform(s_r[0], s_r[-1], size=(2, n_traj))
+    K = ds.N - 1
+    planes = np.arange(K)
+    vplanes = np.arange(1, K + 1)                                 # J_star's last plane is the zero terminal
+    res = {"grid": "35x35", "planes": int(K), "labels": "int32", "values": str(ds.J_star.dtype), "n_traj": int(n_traj), "n_steps": int(K),
+           "n_candidates": int(ds.du), "nodes": int(off.shape[1]), "mode": "expect",
+           "noise": "gaussian_nodes(sigma = (0.02, 0.05), order 3) on both axes: the solve's, the lookahead's and the plant's",
+           "timing": "device_ms: event times around the launches; the runs alternate in one process, 5 rounds after a warm-up round"}
+    ms = {"a_k26": [], "b_k27_one_zero_node": [], "c_k27_9_nodes_nominal": [], "d_k27_9_nodes_noisy": [], "k25_stored_labels": []}
+    with hjbdp.Rollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro, \
+            hjbdp.Rollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro1:
+        for r_ in (ro, ro1):
+            r_.set_model(ds.A, ds.B, q=np.diag(ds.Q), r=[ds.R])
+            r_.set_values(ds.J_star)
+        ro.set_lookahead(off, w, "expect")
+        ro.set_noise(off, w)
+        ro1.set_lookahead(np.zeros((2, 1)), [1.0], "expect")
+        for rnd in range(6):
+            a = ro.run_greedy(X0, vplanes)
+            b = ro1.run_lookahead(X0, vplanes)
+            c = ro.run_lookahead(X0, vplanes)
+            d = ro.run_lookahead(X0, vplanes, noisy=True, seed=1)
+            e = ro.run_noisy(X0, planes, seed=1, method="linear")
+            if rnd:                                               # round 0 is the warm-up
+                for key, out in zip(ms, (a, b, c, d, e)):
+                    ms[key].append(out["device_ms"])
+        res["one_zero_node_equals_k26"] = bool(np.array_equal(a["X_final"], b["X_final"], equal_nan=True)
+                                               and np.array_equal(a["cost"], b["cost"], equal_nan=True))
+        ok = np.isfinite(d["cost"]) & np.isfinite(e["cost"])      # Kirk's plant is unstable: starts far from the origin leave the grid
+        res["finite_in_both"] = int(ok.sum())
+        res["k27_noisy_cost_mean"], res["k25_stored_labels_cost_mean"] = float(np.mean(d["cost"][ok])), float(np.mean(e["cost"][ok]))
+        res["k27_cheaper_or_equal_share"] = float(np.mean(d["cost"][ok] <= e["cost"][ok]))
+        inside = ok & (np.abs(d["X_final"]).max(axis=0) < 1.0) & (np.abs(e["X_final"]).max(axis=0) < 1.0)
+        res["regulated_in_both"] = int(inside.sum())              # flights that end near the origin under both controllers
+        res["k27_noisy_cost_mean_regulated"] = float(np.mean(d["cost"][inside]))
+        res["k25_stored_labels_cost_mean_regulated"] = float(np.mean(e["cost"][inside]))
+        okn = np.isfinite(a["cost"]) & np.isfinite(c["cost"])
+        res["nominal_plant_cost_mean"] = {"k26_nominal_lookahead": float(np.mean(a["cost"][okn])), "k27_9_nodes": float(np.mean(c["cost"][okn]))}
+    for key in ms:
+        med = float(np.median(ms[key]))
+        res[key] = {"device_ms": [round(t, 3) for t in ms[key]], "device_ms_median": round(med, 3),
+                    "traj_steps_per_s": n_traj * K / (med * 1e-3)}
+    med = lambda key: res[key]["device_ms_median"]
+    res["b_over_a"], res["b_over_a_bound"] = med("b_k27_one_zero_node") / med("a_k26"), 1.05
+    res["c_over_a"], res["c_over_a_bound"] = med("c_k27_9_nodes_nominal") / med("a_k26"), 9.0
+    res["d_over_c"] = med("d_k27_9_nodes_noisy") / med("c_k27_9_nodes_nominal")
+    res["k27_ns_per_traj_step_candidate_node"] = med("c_k27_9_nodes_nominal") * 1e6 / (n_traj * K * ds.du * off.shape[1])
+    res["pass"] = bool(res["b_over_a"] <= res["b_over_a_bound"] and res["c_over_a"] <= res["c_over_a_bound"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -576,7 +647,7 @@ def main():
         res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude, "pos_att_loop": case_pos_att_loop,
                   "position_loop": case_position_loop, "attitude_simplified_loop": case_attitude_simplified_loop,
                   "attitude_linear_loop": case_attitude_linear_loop, "pos_att_faults": case_pos_att_faults,
-                  "kirk_noisy": case_kirk_noisy, "greedy": case_greedy}[c](host=not a.no_host)
+                  "kirk_noisy": case_kirk_noisy, "greedy": case_greedy, "lookahead": case_lookahead}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.cases == "position_loop" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
@@ -590,6 +661,8 @@ def main():
         (ROOT / "profiles" / "rollout_noisy_time.json").write_text(json.dumps(res) + "\n")
     if a.cases == "greedy" and not a.out:                         # its own record: one line
         (ROOT / "profiles" / "rollout_greedy_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "lookahead" and not a.out:                      # its own record: one line
+        (ROOT / "profiles" / "rollout_lookahead_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
