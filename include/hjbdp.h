@@ -487,6 +487,44 @@ int32_t hjb_rollout_noise_table(int32_t n_nodes, const double *weights, double *
 int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_traj, int32_t n_steps, int32_t n_nodes,
                                const double *thresholds, int32_t *nodes);
 
+/* ---- noisy campaigns: per-start cost statistics of the noisy loop, reduced on the device (kernel K28) ----------------------------
+ * hjb_rollout_run_campaign flies n_starts starts n_samples (M) times each under the node set of hjb_rollout_set_noise, with the
+ * stored-label controller of hjb_rollout_run_noisy, and returns one record of HJB_CAMPAIGN_NSTAT doubles per start.  No array of
+ * the call, on the host or on the device, has a dimension of n_starts * M: the device memory of a call is bounded by option
+ * "chunk" (the lanes of a launch; 8 doubles per block of a launch) and by n_starts ([D + 1 + 8, n_starts] doubles).
+ * Trajectories.  Sample m of start s is hjb_rollout_run_noisy's trajectory from X0[:, s] on stream first_stream + s*M + m of
+ *   `seed`: its cost c, its final state xf and its visited states are the bits hjb_rollout_run_noisy gives for an X0 with every
+ *   start repeated M times.  Option "chunk" changes no bit.
+ * Slot values of a sample.  v0 = c;  v1 = c*c, rounded;  v2 = c;  v3 = c;
+ *   e = 1 iff threshold is given and c > threshold[s];
+ *   l = 1 iff some visited state x_k, k = 0..n_steps, has an axis with !(knots_a[0] <= x_a && x_a <= knots_a[n_a-1]) - evaluated
+ *       on the states as flown; a NaN counts as left;
+ *   t = 1 iff tol is given and |xf_a| <= tol_a on every axis;   v7 = t ? c : +0.0.
+ * Padding.  A padding slot holds v0 = v1 = v7 = +0.0, v2 = +inf, v3 = -inf and counts 0; it flies nothing and draws nothing.
+ * Reduction order, independent of the launch layout (csrc/hjbdp_campaign.h, shared by the kernel and the host reduce):
+ *   G = min(64, smallest power of two >= M).  The samples of a start form blocks of G consecutive samples; the last block is
+ *   padded.  A block's partial is the adjacent-pair tree over its G slots: at level L, element i (a multiple of 2^(L+1)) becomes
+ *   op(v[i], v[i + 2^L]) - sums: a + b;  min: b < a ? b : a;  max: b > a ? b : a.  The start's value is the block partials folded
+ *   left to right in block order: acc = p_0, then acc = op(acc, p_b).  Counts are exact integers.  NaNs follow from these rules
+ *   with no special case.
+ * Output.  stats [HJB_CAMPAIGN_NSTAT = 8, n_starts] column-major: 0 sum, 1 sum of squares, 2 min, 3 max, 4 n_exceed, 5 n_left,
+ *   6 n_settled (the three counts as doubles), 7 sum over the settled samples.  threshold [n_starts] or NULL; tol [D] or NULL.
+ * hjb_rollout_campaign_reduce runs the same reduction on the CPU with no device, on per-trajectory arrays such as
+ * hjb_rollout_run_noisy returns (trajectory s*M + m is sample m of start s): cost [n_starts*M], X_final [D, n_starts*M] or NULL
+ * (required with tol), left [n_starts*M] uint8 (non-zero: left the grid) or NULL (n_left = 0).
+ * Refused before any device work, outputs untouched (text: hjb_rollout_last_error) - HJB_E_INVALID: everything
+ * hjb_rollout_run_noisy refuses (n_starts in the place of n_traj; no noise set; another model set); null stats; n_samples < 1;
+ * n_starts * n_samples or first_stream + n_starts * n_samples overflowing int64; a threshold entry that is NaN; a tol entry that
+ * is NaN or negative.
+ * Out of scope: campaigns of the greedy / lookahead controllers (csrc/hjbdp_campaign.h is written for them to reuse), quantiles
+ * and histograms, campaigns of the integrated plants. */
+#define HJB_CAMPAIGN_NSTAT 8
+int32_t hjb_rollout_run_campaign(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts,
+                                 int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream, const double *threshold,
+                                 const double *tol, double *stats, double *device_ms);
+int32_t hjb_rollout_campaign_reduce(int64_t n_starts, int64_t n_samples, int32_t D, const double *cost, const double *X_final,
+                                    const uint8_t *left, const double *threshold, const double *tol, double *stats);
+
 /* ---- greedy rollouts: the affine loop flown by one-step lookahead on a stored cost-to-go (kernel K26) ---------------------------
  *   u_k(x) = argmin_l  g(x, u_l) + J_{k+1}(A x + B u_l + c)   over the rows u_l of the object's u_table, at the state visited
  * - the textbook DP controller: the other half of what hjb_solve(keep_J) returns.  It reads no label (the object's labels are not

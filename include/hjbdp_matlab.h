@@ -115,6 +115,15 @@ int32_t hjb_rollout_run_noisy(void *rollout, int32_t method, int32_t n_steps, co
 int32_t hjb_rollout_noise_table(int32_t n_nodes, const double *weights, double *thresholds);
 int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_traj, int32_t n_steps, int32_t n_nodes,
                                const double *thresholds, int32_t *nodes);
+/* the noisy loop as a campaign (kernel K28): n_starts starts flown n_samples times each, sample m of start s on stream
+ * first_stream + s * n_samples + m, reduced on the device to stats [8, n_starts] (sum, sum of squares, min, max, n_exceed, n_left,
+ * n_settled, sum over settled; threshold [n_starts] and tol [D] may be NULL); the host reduce needs no device (hjbdp.h); usage:
+ * matlab/Dynamic_Solver_hjbdp_noisy_cost_map.m */
+int32_t hjb_rollout_run_campaign(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts,
+                                 int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream, const double *threshold,
+                                 const double *tol, double *stats, double *device_ms);
+int32_t hjb_rollout_campaign_reduce(int64_t n_starts, int64_t n_samples, int32_t D, const double *cost, const double *X_final,
+                                    const uint8_t *left, const double *threshold, const double *tol, double *stats);
 /* the affine loop flown by one-step lookahead on stored value planes (kernel K26): values [nS, n_planes] column-major, dtype 0 =
  * single, 1 = double (n_planes 0 detaches); value_plane_of_step -1 = the zero terminal; L_path the chosen label + index_base,
  * V_path the minimum, per step; the host twin needs no device and no object (hjbdp.h); usage:

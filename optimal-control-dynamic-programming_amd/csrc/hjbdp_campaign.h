@@ -1,0 +1,133 @@
+// hjbdp_campaign.h - the per-start statistics of a noisy campaign (K28, kernels_rollout_campaign.h): the slot values of one
+// sample, the identities of a padding slot, the adjacent-pair tree of a block and the left-to-right fold of the block partials,
+// shared by the kernel, the host reduce hjb_rollout_campaign_reduce (rollout_campaign_host.hip) and tests/campaign_harness.cpp,
+// which compiles it as plain C++ (no HIP dependency).  Controller-agnostic: these functions see a sample's cost c, its final
+// state xf and whether it left the grid, and nothing of the lookup that flew it.  The contract (stated in include/hjbdp.h):
+//   slot values  v0 = c, v1 = c * c (rounded), v2 = c, v3 = c, v7 = settled ? c : +0.0; the flags e (c > threshold, strict),
+//                l (some visited state outside [first knot, last knot] on some axis, a NaN counts as outside), t (|xf_a| <= tol_a
+//                on every axis); a padding slot holds v0 = v1 = v7 = +0.0, v2 = +inf, v3 = -inf and counts 0;
+//   op           sums a + b; min b < a ? b : a; max b > a ? b : a - `a` the earlier operand;
+//   blocks       G = min(64, the smallest power of two >= M) consecutive samples of a start, the last block padded; a block's
+//                partial is the tree over its G slots: at level L element i (a multiple of 2^(L+1)) becomes op(v[i], v[i + 2^L]);
+//   fold         acc = p_0, then acc = op(acc, p_b) in block order.  Counts are integers.
+// Nothing here depends on how a launch lays the slots out: the kernel runs the same op over wave shuffles.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define HJB_CAMPAIGN_FN __host__ __device__ __forceinline__
+#else
+#define HJB_CAMPAIGN_FN inline
+#endif
+
+namespace hjb {
+
+constexpr int kCampaignMaxGroup = 64;
+
+// the five values of a slot that the tree combines in double (stats 0, 1, 2, 3 and 7); the counts (stats 4, 5, 6) are integers
+struct CampVals {
+    double sum, sumsq, mn, mx, sum_settled;
+};
+
+struct CampCounts {
+    int64_t exceed, left, settled;
+};
+
+HJB_CAMPAIGN_FN double campaign_inf() { return __builtin_huge_val(); }
+
+// G and log2 G of n_samples >= 1 samples per start
+HJB_CAMPAIGN_FN int campaign_group(int64_t n_samples, int *log2_out) {
+    int g = 1, lg = 0;
+    while (g < kCampaignMaxGroup && g < n_samples) {
+        g *= 2;
+        ++lg;
+    }
+    if (log2_out) *log2_out = lg;
+    return g;
+}
+
+HJB_CAMPAIGN_FN CampVals campaign_padding() {
+    CampVals v;
+    v.sum = 0.0;
+    v.sumsq = 0.0;
+    v.mn = campaign_inf();
+    v.mx = -campaign_inf();
+    v.sum_settled = 0.0;
+    return v;
+}
+
+HJB_CAMPAIGN_FN CampVals campaign_slot(double c, bool settled) {
+    CampVals v;
+    v.sum = c;
+    v.sumsq = c * c;
+    v.mn = c;
+    v.mx = c;
+    v.sum_settled = settled ? c : 0.0;
+    return v;
+}
+
+// e: has_threshold false = no threshold given
+HJB_CAMPAIGN_FN bool campaign_exceeds(double c, bool has_threshold, double threshold) { return has_threshold && c > threshold; }
+
+// one axis of one visited state against that axis' first and last knot; a NaN is outside
+HJB_CAMPAIGN_FN bool campaign_outside(double x, double lo, double hi) { return !(lo <= x && x <= hi); }
+
+// t: tol null = none given; |xf_a| <= tol_a on every axis (a NaN xf_a does not settle)
+HJB_CAMPAIGN_FN bool campaign_settled(int D, const double *xf, const double *tol) {
+    if (!tol) return false;
+    bool t = true;
+    for (int a = 0; a < D; ++a) t = t && (__builtin_fabs(xf[a]) <= tol[a]);
+    return t;
+}
+
+// op(a, b), a the earlier operand: what the tree's levels and the fold both apply
+HJB_CAMPAIGN_FN CampVals campaign_op(const CampVals &a, const CampVals &b) {
+    CampVals v;
+    v.sum = a.sum + b.sum;
+    v.sumsq = a.sumsq + b.sumsq;
+    v.mn = b.mn < a.mn ? b.mn : a.mn;
+    v.mx = b.mx > a.mx ? b.mx : a.mx;
+    v.sum_settled = a.sum_settled + b.sum_settled;
+    return v;
+}
+
+// the adjacent-pair tree over v[0 .. G), G a power of two, in place: the partial is v[0] on return
+HJB_CAMPAIGN_FN void campaign_tree(CampVals *v, int G) {
+    for (int half = 1; half < G; half *= 2)
+        for (int i = 0; i + half < G; i += 2 * half) v[i] = campaign_op(v[i], v[i + half]);
+}
+
+// The statistics of one start from its n_samples per-trajectory results (cost [M]; xf [D, M] column-major or null; left [M] or
+// null; threshold: has_threshold false = none; tol [D] or null) into out[8]: the blocks, their trees and the fold, on one thread.
+inline void campaign_reduce_start(int64_t n_samples, int D, const double *cost, const double *xf, const uint8_t *left,
+                                  bool has_threshold, double threshold, const double *tol, double *out) {
+    const int G = campaign_group(n_samples, nullptr);
+    CampVals acc = campaign_padding(), v[kCampaignMaxGroup];
+    CampCounts n = {0, 0, 0};
+    for (int64_t m0 = 0; m0 < n_samples; m0 += G) {
+        for (int j = 0; j < G; ++j) {
+            const int64_t m = m0 + j;
+            if (m >= n_samples) {
+                v[j] = campaign_padding();
+                continue;
+            }
+            const bool t = xf && campaign_settled(D, xf + (int64_t)D * m, tol);
+            v[j] = campaign_slot(cost[m], t);
+            n.exceed += campaign_exceeds(cost[m], has_threshold, threshold) ? 1 : 0;
+            n.left += (left && left[m]) ? 1 : 0;
+            n.settled += t ? 1 : 0;
+        }
+        campaign_tree(v, G);
+        acc = m0 == 0 ? v[0] : campaign_op(acc, v[0]);
+    }
+    out[0] = acc.sum;
+    out[1] = acc.sumsq;
+    out[2] = acc.mn;
+    out[3] = acc.mx;
+    out[4] = (double)n.exceed;
+    out[5] = (double)n.left;
+    out[6] = (double)n.settled;
+    out[7] = acc.sum_settled;
+}
+
+}  // namespace hjb

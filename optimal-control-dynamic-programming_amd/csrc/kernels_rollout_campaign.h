@@ -1,0 +1,197 @@
+// kernels_rollout_campaign.h - K28: the campaign form of K25 (kernels_rollout_noisy.h).  n_starts starts are each flown M times
+// under the object's noise node set by the stored-label controller, and the per-trajectory results are reduced on the device to
+// eight doubles per start (hjb_rollout_run_campaign; the statistics and their order: hjbdp_campaign.h).  No array of a call has
+// a dimension of n_starts * M.
+//
+// The call's samples form blocks of G = min(64, pow2 >= M) consecutive samples of one start (the last block of a start padded);
+// start s owns blocks s * B .. s * B + B - 1, B = ceil(M / G).  A launch takes n_blocks consecutive blocks from block0 on, and its
+// lanes are (block, slot) in order: lane t of the launch is slot t % G of block block0 + t / G.  A wave of 64 lanes therefore holds
+// 64 / G whole blocks and no block straddles a wave.
+//   k_rollout_campaign  one lane per slot.  A live lane (sample m = blk * G + slot < M) flies K25's trajectory from X0[:, s] on the
+//       stream N.first + s * M + m: K25's step restated operation for operation (as K25 restated K16's), without the path stores,
+//       plus the left-the-grid flag on every visited state.  Lanes of padding slots and lanes past the launch's last block fly
+//       nothing and draw nothing, but stay alive: they join the cross-lane steps with the identities.  The block tree is
+//       log2 G levels of wave shuffles (lane i takes lane i + 2^L and applies campaign_op, its own value first: the lanes that
+//       are multiples of 2^(L+1) hold exactly the tree's elements; what the others compute is never read); the counts are three
+//       ballots and a popcount under the segment's mask.  Slot 0 of a block writes its partial, 8 doubles, to Cp.partials.
+//   k_campaign_fold     (rollout_campaign.hip) one thread per start the launch touches: the start's partials of this launch folded
+//       in block order into stats[:, s], which persists across launches - a start whose blocks straddle launches continues from what the earlier
+//       launch left.  The first block of a start initialises the accumulator (acc = p_0).
+// No atomics, and no floating-point order that depends on the schedule: the result is a function of (M, the samples) alone.
+// X0 is read once per start: the lanes of a segment read one address.
+#pragma once
+#include "kernels_rollout_noisy.h"
+#include "hjbdp_campaign.h"
+
+namespace hjb {
+
+struct DCampaign {
+    int64_t n_blocks, block0;         // this launch: blocks block0 .. block0 + n_blocks of the call's block list
+    int64_t B, M;                     // blocks per start, samples per start
+    int32_t G, log2G;
+    int32_t has_tol, reserved_;
+    const double *threshold;          // [n_starts] (global) or null
+    double tol[HJB_MAX_D];
+    double lo[HJB_MAX_D], hi[HJB_MAX_D];      // the first and the last knot of every axis
+    double *partials;                 // [8, n_blocks] (global): the launch's block partials, stats order, counts as doubles
+};
+
+// what the kernel reads: one argument, so that its layout is C++'s (K26's DGreedy, for its reason)
+struct DCampaignArgs {
+    DRollout R;
+    DNoise N;                         // N.first: the CALL's first stream; N.Wp unused
+    DCampaign C;
+    const double *X0;                 // [D, n_starts] (global)
+};
+
+// The record read where it lies, in the kernel argument segment, instead of being held in scalar registers across the step loop
+// (hjbdp_greedy.h's greedy_reread, for K26's reason): DRollout alone is some 170 scalars, and held across the loop beside the
+// loop's own they are spilled to lanes of vector registers - K25, which takes its records by value, spills up to 458 of them.
+// Behind this the scalar loads of a loop body are issued in the body.
+template <typename T>
+__device__ __forceinline__ const T &campaign_reread(const T &r) {
+    const T *p = &r;
+    asm volatile("" : "+s"(p));
+    return *p;
+}
+
+// ... inside a step, where it is needed: from D = 3 on.  Below that the step's scalars fit beside the loop's own, one read of the
+// record per step (`step`) serves the whole body, and the further reads would only lengthen the step (measured: + 10 % at D = 2).
+template <int D, typename T>
+__device__ __forceinline__ const T &campaign_reread_in_step(const T &r, const T &step) {
+    if constexpr (D >= 3) return campaign_reread(r);
+    else return step;
+}
+
+template <int D, typename TL, int METHOD, bool LDS>
+__global__ void __launch_bounds__(256)
+k_rollout_campaign(const DCampaignArgs K) {
+    extern __shared__ double smem[];
+    const double *kn, *rd, *ut, *nt;
+    HJB_ROLLOUT_PLACE(p, K.R, K.R.n_u, smem)
+    HJB_ROLLOUT_STAGE(LDS, p, K.R, kn, rd, ut)
+    if constexpr (LDS) {
+        double *lds_n = HJB_ROLLOUT_PLACE_END(p);
+        for (int e = threadIdx.x; e < K.N.n_tab; e += blockDim.x) lds_n[e] = K.N.tab[e];
+        nt = lds_n;
+        __syncthreads();
+    } else {
+        nt = K.N.tab;
+    }
+    typedef __attribute__((address_space(4))) DCampaignArgs KArgs;
+    const KArgs &K0 = *(const KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    int64_t lb, s, m;
+    int slot, G;
+    bool live;
+    {
+        const KArgs &Kk = campaign_reread(K0);
+        G = Kk.C.G;
+        lb = t >> Kk.C.log2G;                                 // the lane's block in the launch
+        slot = (int)(t & (G - 1));
+        const int64_t gb = Kk.C.block0 + lb;
+        s = gb / Kk.C.B;                                      // the start, and the sample of it
+        m = (gb - s * Kk.C.B) * G + slot;
+        live = lb < Kk.C.n_blocks && m < Kk.C.M;
+    }
+    CampVals v = campaign_padding();
+    bool f_exceed = false, f_left = false, f_settled = false;
+    if (live) {
+        double x[D];
+        uint64_t stream;
+        {
+            const KArgs &Kk = campaign_reread(K0);
+            stream = Kk.N.first + (uint64_t)(s * Kk.C.M + m);
+#pragma unroll
+            for (int a = 0; a < D; ++a) x[a] = Kk.X0[a + (int64_t)D * s];
+#pragma unroll
+            for (int a = 0; a < D; ++a) f_left = f_left || campaign_outside(x[a], Kk.C.lo[a], Kk.C.hi[a]);
+        }
+        uint32_t rw[4] = {0u, 0u, 0u, 0u};
+        double J = 0.0;
+        for (int k = 0; k < campaign_reread(K0).R.n_steps; ++k) {
+            const KArgs &Kl = campaign_reread(K0);            // the lookup's part of the record
+            const TL *__restrict__ lab = static_cast<const TL *>(Kl.R.labels);
+            const int nu = Kl.R.n_u;
+            const int64_t nl = Kl.R.n_labels;
+            HJB_ROLLOUT_LOOKUP(D, HJB_ROLLOUT_MAX_U, METHOD, Kl.R, kn, rd, ut, lab, k, x, nu, nl, u)
+            const KArgs &Kc = campaign_reread_in_step<D>(K0, Kl);      // the cost's
+            double g = Kc.R.q[0] * (x[0] * x[0]);
+#pragma unroll
+            for (int a = 1; a < D; ++a) g = g + Kc.R.q[a] * (x[a] * x[a]);
+#pragma unroll
+            for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j)
+                if (j < nu) g = g + Kc.R.r[j] * (u[j] * u[j]);
+            J = J + g;
+            double xn[D];
+#pragma unroll
+            for (int a = 0; a < D; ++a) {
+                const KArgs &Ka = campaign_reread_in_step<D>(K0, Kl);  // a row of A and of B
+                double acc = Ka.R.A[a] * x[0];
+#pragma unroll
+                for (int b = 1; b < D; ++b) acc = acc + Ka.R.A[a + D * b] * x[b];
+#pragma unroll
+                for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j)
+                    if (j < nu) acc = acc + Ka.R.B[a + D * j] * u[j];
+                if (Ka.R.has_c) acc = acc + Ka.R.c[a];
+                xn[a] = acc;
+            }
+            const KArgs &Kn = campaign_reread_in_step<D>(K0, Kl);      // the noise set and the grid's extent
+            const int n_nodes = Kn.N.n_nodes, n_thr = n_nodes - 1;
+            if ((k & 3) == 0) noise_block(Kn.N.seed, stream, (uint32_t)k >> 2, rw);
+            const int w = noise_node(nt, n_thr, noise_next_word(rw));
+            {
+                const double *row = nt + n_thr + w;           // the next masked axis' offsets, at this lane's node
+#pragma unroll
+                for (int a = 0; a < D; ++a)
+                    if (Kn.N.mask & (1 << a)) {
+                        xn[a] = xn[a] + row[0];
+                        row += n_nodes;
+                    }
+            }
+#pragma unroll
+            for (int a = 0; a < D; ++a) x[a] = xn[a];
+#pragma unroll
+            for (int a = 0; a < D; ++a) f_left = f_left || campaign_outside(x[a], Kn.C.lo[a], Kn.C.hi[a]);
+        }
+        const KArgs &Kk = campaign_reread(K0);
+        double tol[D];
+#pragma unroll
+        for (int a = 0; a < D; ++a) tol[a] = Kk.C.tol[a];
+        f_settled = campaign_settled(D, x, Kk.C.has_tol ? tol : nullptr);
+        f_exceed = campaign_exceeds(J, Kk.C.threshold != nullptr, Kk.C.threshold ? Kk.C.threshold[s] : 0.0);
+        v = campaign_slot(J, f_settled);
+    }
+    // every lane of the wave from here on.  The block tree: level L pairs element i with element i + 2^L
+    for (int half = 1; half < G; half *= 2) {
+        CampVals o;
+        o.sum = __shfl_down(v.sum, half);
+        o.sumsq = __shfl_down(v.sumsq, half);
+        o.mn = __shfl_down(v.mn, half);
+        o.mx = __shfl_down(v.mx, half);
+        o.sum_settled = __shfl_down(v.sum_settled, half);
+        v = campaign_op(v, o);
+    }
+    const unsigned long long b_exceed = __ballot(f_exceed), b_left = __ballot(f_left), b_settled = __ballot(f_settled);
+    const KArgs &Kk = campaign_reread(K0);
+    if (slot == 0 && lb < Kk.C.n_blocks) {
+        const int lane = threadIdx.x & 63;                    // the segment's first lane: G divides 64 and the block size
+        const unsigned long long seg = (G == 64 ? ~0ull : (1ull << G) - 1ull) << lane;
+        double *out = Kk.C.partials + 8 * lb;
+        out[0] = v.sum;
+        out[1] = v.sumsq;
+        out[2] = v.mn;
+        out[3] = v.mx;
+        out[4] = (double)__popcll(b_exceed & seg);
+        out[5] = (double)__popcll(b_left & seg);
+        out[6] = (double)__popcll(b_settled & seg);
+        out[7] = v.sum_settled;
+    }
+}
+
+// rollout_campaign.hip instantiates the 72 kernels (label type x method x LDS x D, as K25) and launches the one asked for, then
+// the fold; lds: the bytes of the channel's tables and the node block together; stats: [8, n_starts] on the device
+hipError_t launch_rollout_campaign(int idx_bytes, int method, bool lds_on, int D, const DRollout &R, const DNoise &N,
+                                   const DCampaign &Cp, size_t lds, hipStream_t st, const double *X0, double *stats);
+
+}  // namespace hjb

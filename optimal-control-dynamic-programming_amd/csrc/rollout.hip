@@ -13,7 +13,9 @@
 // And a lookahead node set (hjb_rollout_set_lookahead): hjb_rollout_run_lookahead (K27, kernels_rollout_lookahead.h /
 // rollout_lookahead.hip, rollout_lookahead_fly.hip) flies the affine loop by lookahead under that set, on a nominal plant or under
 // the noise set, and no other run function reads it.  Its host twin hjb_rollout_lookahead_host (hjbdp_lookahead.h) needs no device.
-// Defined here for both host units (rollout_host.h): rfail, check_run / check_traj / check_quaternions (the run functions'
+// And hjb_rollout_run_campaign (K28, kernels_rollout_campaign.h / rollout_campaign.hip) reduces the noisy flights of the stored labels
+// per start on the device; its host side and the host reduce hjb_rollout_campaign_reduce are rollout_campaign_host.hip.
+// Defined here for the host units (rollout_host.h): rfail, check_run / check_traj / check_quaternions (the run functions'
 // refusals, all before any device work), upload, run_chunks (the chunk loop).  No kernel is instantiated in this unit.
 #include "rollout_host.h"
 #include "rollout_dispatch.h"
@@ -335,6 +337,10 @@ int32_t hjb_rollout_create(int32_t device, int32_t D, const int32_t *n, const do
     R.index_base = index_base;
     std::vector<double> rdx((size_t)n_knots);
     greedy_grid(D, n, knots, R, rdx.data());                  // the grid description and 1/dx, as hjb_policy_lookup builds it
+    for (int a = 0; a < D; ++a) {
+        ro->grid_lo[a] = knots[R.koff[a]];
+        ro->grid_hi[a] = knots[R.koff[a] + n[a] - 1];
+    }
     int st = upload(ro, *ro->data, knots, (size_t)n_knots * sizeof(double), (const void **)&R.knots);
     if (!st) st = upload(ro, *ro->data, rdx.data(), rdx.size() * sizeof(double), (const void **)&R.rdx);
     if (!st) st = upload(ro, *ro->data, u_table, (size_t)n_ut * sizeof(double), (const void **)&R.u_table);

@@ -1,5 +1,6 @@
-// rollout_host.h - what the two host units of the rollouts share (host only; include/hjbdp.h is the public ABI): the object,
-// its refusals, the upload and the chunk loop.  Defined in rollout.hip; rollout_channels.hip is the other reader.
+// rollout_host.h - what the host units of the rollouts share (host only; include/hjbdp.h is the public ABI): the object,
+// its refusals, the upload and the chunk loop.  Defined in rollout.hip; rollout_channels.hip and rollout_campaign_host.hip are the
+// other readers.
 #pragma once
 #include "hjbdp_host.h"
 // the records an object holds: DRollout, DAttitude, DNoise, DPaChan (a unit includes the other kernel headers whose launch it calls)
@@ -47,6 +48,7 @@ struct Rollout {
     int64_t chunk = (int64_t)1 << 20;
     bool lds = true;                // option "lds": stage the tables in LDS when they fit (false: never)
     DRollout R{};                   // device pointers filled by create; model by set_model
+    double grid_lo[HJB_MAX_D] = {}, grid_hi[HJB_MAX_D] = {};   // the first and the last knot of every axis (create): the campaign's extent
     DAttitude M{};                  // the attitude model (set_attitude_model)
     std::unique_ptr<Attached> att;  // the PosAtt / Position / AttSimplified of model kModelPosAtt / kModelPosition / kModelAttSimplified
     std::shared_ptr<DevData> data;

@@ -236,6 +236,11 @@ SYMBOLS = {
     "hjb_rollout_noise_table": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "hjb_rollout_noise_draw": (C.c_int32, [C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                            C.POINTER(C.c_int32)]),
+    # the noisy loop as a campaign: per-start statistics reduced on the device, and the host reduce
+    "hjb_rollout_run_campaign": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
+                                             C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 4),
+    "hjb_rollout_campaign_reduce": (C.c_int32, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                C.POINTER(C.c_uint8)] + [C.POINTER(C.c_double)] * 3),
     # the affine loop flown by one-step lookahead on stored value planes, and its host twin
     "hjb_rollout_set_values": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "hjb_rollout_run_greedy": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64] + [C.POINTER(C.c_double)] * 8),
@@ -279,6 +284,7 @@ HJB_DIST_EXPECT = 0
 HJB_DIST_WORST = 1
 HJB_DIST_MAX_NODES = 128
 HJB_ROLLOUT_MAX_U = 4
+HJB_CAMPAIGN_NSTAT = 8
 HJB_ATT_TAYLOR = 0
 HJB_ATT_RK4 = 1
 HJB_ATTS_FULL = 0

@@ -321,6 +321,25 @@ class Rollout:
             paths["W_path"] = paths["W_path"][:, 0, :].astype(np.int32)
         return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
 
+    def run_campaign(self, X0, plane_of_step, n_samples, seed=0, first_stream=0, method="linear", cost_threshold=None,
+                     settle_tol=None):
+        """Every start of X0 [D, n_starts] flown n_samples times under the node set of set_noise, the costs reduced per start on
+        the GPU (hjb_rollout_run_campaign): sample m of start s is run_noisy's trajectory on stream first_stream + s * n_samples
+        + m of `seed`, and nothing of length n_starts * n_samples exists on either side.  cost_threshold: a scalar or one value
+        per start (n_exceed counts the samples with cost > threshold); settle_tol: a scalar or one value per axis (a sample
+        settled when |x_final| <= tol on every axis).  Returns the dict of campaign_reduce plus device_ms."""
+        D = self.D
+        X = _starts(X0, D)
+        ns = X.shape[0]
+        ps = _int32_vector(plane_of_step, "plane_of_step")
+        thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
+        stats = np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT))
+        ms = C.c_double(0.0)
+        self._check(self.lib.hjb_rollout_run_campaign(self._ro, _LOOKUP[method], int(ps.size), _i32p(ps), ns, int(n_samples), _f64p(X),
+                                                      int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol),
+                                                      _f64p(stats), C.byref(ms)))
+        return {**_campaign_dict(stats, int(n_samples)), "device_ms": ms.value}
+
     def set_values(self, J):
         """Value planes for run_greedy (hjb_rollout_set_values): J float32 or float64, [nS, n_planes] or grid-shaped with a
         trailing plane axis, Fortran order (hjb_solve's J_stages; Dynamic_Solver's J_star).  A property of the object,
@@ -554,6 +573,60 @@ def noise_draw(thresholds, n_traj, n_steps, seed=0, first_stream=0):
     _check(lib, None, lib.hjb_rollout_noise_draw(int(seed) & (2 ** 64 - 1), int(first_stream), int(n_traj), int(n_steps), T.size + 1,
                                                  _f64p(T), _i32p(nodes)))
     return np.ascontiguousarray(nodes.T)
+
+
+def _campaign_bounds(n_starts, D, cost_threshold, settle_tol):
+    """cost_threshold (None, a scalar or [n_starts]) and settle_tol (None, a scalar or [D]) as the library reads them"""
+    thr = None if cost_threshold is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cost_threshold, dtype=np.float64).reshape(-1),
+                                                                                  (n_starts,)))
+    tol = None if settle_tol is None else np.ascontiguousarray(np.broadcast_to(np.asarray(settle_tol, dtype=np.float64).reshape(-1), (D,)))
+    return thr, tol
+
+
+def _campaign_dict(stats, M):
+    """stats [n_starts, 8] as the library wrote it -> the dict run_campaign and campaign_reduce return"""
+    total, sumsq = stats[:, 0], stats[:, 1]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        var = np.maximum((sumsq - total * total / M) / (M - 1), 0.0) if M > 1 else np.zeros(stats.shape[0])
+        n_settled = stats[:, 6].astype(np.int64)
+        mean_settled = np.where(n_settled > 0, stats[:, 7] / np.maximum(n_settled, 1), np.nan)
+    return {"stats": stats, "mean": total / M, "var": var, "std": np.sqrt(var), "min": stats[:, 2], "max": stats[:, 3],
+            "n_exceed": stats[:, 4].astype(np.int64), "n_left": stats[:, 5].astype(np.int64), "n_settled": n_settled,
+            "mean_settled": mean_settled}
+
+
+def campaign_reduce(cost, n_samples, X_final=None, left=None, cost_threshold=None, settle_tol=None):
+    """Rollout.run_campaign's reduction on the CPU (hjb_rollout_campaign_reduce; no device), over per-trajectory results such as
+    run_noisy returns for starts repeated n_samples times: cost [n_starts * n_samples] (trajectory s * n_samples + m is sample m
+    of start s), X_final [D, n_starts * n_samples] (needed with settle_tol), left [n_starts * n_samples] (non-zero: the
+    trajectory left the grid; None counts none).  Returns stats [n_starts, 8] (sum, sum of squares, min, max, n_exceed, n_left,
+    n_settled, sum over settled: the bits run_campaign returns for the same samples), mean, var = (sumsq - sum^2 / M) / (M - 1)
+    clipped at 0 (0 for M = 1), std, min, max, n_exceed / n_left / n_settled (int64) and mean_settled (NaN where none settled)."""
+    lib = load_library()
+    c = np.ascontiguousarray(np.asarray(cost, dtype=np.float64).reshape(-1))
+    M = int(n_samples)
+    if M < 1 or c.size % M:
+        raise ValueError("cost: %d values are not a whole number of %d samples" % (c.size, M))
+    ns = c.size // M
+    D, Xf = 1, None
+    if X_final is not None:
+        Xf2 = np.asarray(X_final, dtype=np.float64)
+        Xf2 = Xf2.reshape(1, -1) if Xf2.ndim == 1 else Xf2
+        if Xf2.shape[1] != c.size:
+            raise ValueError("X_final: %d columns for %d costs" % (Xf2.shape[1], c.size))
+        D, Xf = Xf2.shape[0], np.ascontiguousarray(Xf2.T)
+    lf = None
+    if left is not None:
+        lf = np.ascontiguousarray((np.asarray(left).reshape(-1) != 0).astype(np.uint8))
+        if lf.size != c.size:
+            raise ValueError("left: %d flags for %d costs" % (lf.size, c.size))
+    if settle_tol is not None and Xf is None:
+        raise ValueError("settle_tol needs X_final")
+    thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
+    stats = np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT))
+    _check(lib, None, lib.hjb_rollout_campaign_reduce(ns, M, D, _f64p(c), _f64p(Xf), None if lf is None else lf.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                      _f64p(thr), _f64p(tol), _f64p(stats)))
+    return _campaign_dict(stats, M)
 
 
 def greedy_host(knots, u_table, A, B, J, X0, value_plane_of_step, c=None, q=None, r=None, index_base=0, keep_path=False):

@@ -235,6 +235,61 @@ class Dynamic_Solver:
         self.noisy_paths_ms = out["device_ms"]
         return cost
 
+    def _noisy_policy_rollout(self, who, mode, ssu_num):
+        """What a noisy flight of the stored policy needs (get_noisy_paths' own set-up, stated once for the campaign methods): the
+        planes of `mode` / `ssu_num` and an open hjbdp.Rollout holding the policy, the model and self.disturbance's nodes."""
+        from .core import Rollout
+        if self.u_star_idxs is None:
+            raise RuntimeError("run() first")
+        if self.disturbance is None:
+            raise RuntimeError("%s needs self.disturbance = (offsets [2, W], weights or None, mode)" % who)
+        n_st = self.N - 1
+        if mode == "ssu":
+            if not 1 <= int(ssu_num) <= n_st:
+                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
+            planes = np.full(n_st, int(ssu_num) - 1, dtype=np.int32)
+        elif mode == "Nssu":
+            planes = np.arange(n_st, dtype=np.int32)
+        else:
+            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
+        ro = Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device)
+        try:
+            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+            ro.set_noise(self.disturbance[0], self.disturbance[1])
+        except Exception:
+            ro.close()
+            raise
+        return planes, ro
+
+    def get_noisy_cost_statistics(self, X0s, n_samples, seed=0, mode="Nssu", ssu_num=1, method="linear", cost_threshold=None,
+                                  settle_tol=None):
+        """get_noisy_paths' flights reduced per start on the GPU (hjbdp.Rollout.run_campaign): every start of X0s [S, n] flown
+        n_samples times under self.disturbance's nodes, sample j of start i on stream i * n_samples + j of `seed`
+        (get_noisy_paths' numbering: the same costs), and nothing of length n * n_samples exists on the host or on the device.
+        Returns run_campaign's dict, one entry per start: stats [n, 8], mean, var, std, min, max, n_exceed (cost >
+        cost_threshold), n_left (the flight left the grid), n_settled (|x_final| <= settle_tol on every axis), mean_settled,
+        device_ms.  `mode` / `ssu_num` / `method` as in get_noisy_paths."""
+        if int(n_samples) < 1:
+            raise ValueError("n_samples must be at least 1")
+        planes, ro = self._noisy_policy_rollout("get_noisy_cost_statistics", mode, ssu_num)
+        with ro:
+            return ro.run_campaign(np.asarray(X0s, dtype=np.float64).reshape(self.S, -1), planes, int(n_samples), seed=seed,
+                                   first_stream=0, method=method, cost_threshold=cost_threshold, settle_tol=settle_tol)
+
+    def noisy_cost_map(self, n_samples, seed=0, mode="Nssu", ssu_num=1, method="linear", cost_threshold=None, settle_tol=None):
+        """get_noisy_cost_statistics at every grid node: each entry shaped like the grid, [dx, dx] (stats [dx, dx, 8]), node
+        (i, j) = (s_r[i], s_r[j]) flown from stream (i + dx * j) * n_samples on.  Beside policy_cost() on the same disturbance
+        this is "promised against paid" over the whole grid: policy_cost()'s plane 0 is what the policy promises at a node,
+        the map's mean (and, for a 'worst' set, its max) is what n_samples flights from that node paid."""
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        dx = s_r.size
+        X0s = np.stack([np.tile(s_r, dx), np.repeat(s_r, dx)])                  # axis 0 fastest, as the labels are stored
+        out = self.get_noisy_cost_statistics(X0s, n_samples, seed=seed, mode=mode, ssu_num=ssu_num, method=method,
+                                             cost_threshold=cost_threshold, settle_tol=settle_tol)
+        return {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) else v) for key, v in out.items()}
+
     def get_greedy_paths(self, X0s, mode="Nssu", ssu_num=1):
         """The closed loop of the cost-to-go itself, on the GPU (hjbdp.Rollout.run_greedy): at every step the control of U_mesh
         that minimises x'Qx + R u^2 + J_{k+1}(A x + B u), J_{k+1} the plane of J_star behind the step blended linearly at the

@@ -1,0 +1,192 @@
+"""CPU tests of the noisy campaign's reduction (include/hjbdp.h "noisy campaigns", csrc/hjbdp_campaign.h): the host reduce
+hjb_rollout_campaign_reduce against the numpy restatement (tests/campaign_refs.py) bit for bit, the plain C++ harness over the
+same header, the sum's error against math.fsum, and the refusals of both entry points that need no device."""
+import ctypes as C
+import math
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import campaign_refs as refs
+
+ROOT = Path(__file__).resolve().parent.parent
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+SIZES = (1, 2, 3, 5, 63, 64, 65, 200)
+
+
+@pytest.fixture(scope="module")
+def lib(built):
+    import hjbdp
+    return hjbdp.load_library()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _inputs(M, seed, D=3, ns=4):
+    """seeded per-trajectory results with what the contract singles out: a NaN cost in a low and in a high slot of a block,
+    -0.0, an infinite cost, final states on both sides of the tolerance, left flags"""
+    rng = np.random.default_rng(seed)
+    cost = rng.uniform(-2.0, 50.0, size=(ns, M)) * 10.0 ** rng.integers(-3, 4, size=(ns, M))
+    cost[0, 0] = -0.0
+    if M > 1:
+        cost[1, 0] = np.nan                                     # slot 0 of block 0: the earlier operand at every level
+        cost[2, M - 1] = np.nan                                 # the last live slot: the later operand at every level
+        cost[3, M // 2] = -0.0
+    if M > 4:
+        cost[3, 1] = np.inf
+        cost[0, 3] = -np.inf
+    Xf = rng.uniform(-0.5, 0.5, size=(D, ns * M))
+    Xf[:, rng.integers(0, ns * M, size=max(1, ns * M // 5))] *= 0.1
+    if M > 2:
+        Xf[1, 2] = np.nan
+    left = (rng.uniform(size=ns * M) < 0.3).astype(np.uint8)
+    thr = np.array([5.0, -np.inf, np.inf, 0.0])
+    tol = np.array([0.3, 0.25, 0.35])
+    return cost.reshape(-1), Xf, left, thr, tol
+
+
+@pytest.mark.parametrize("M", SIZES)
+def test_host_reduce_is_bit_equal_to_the_restatement(lib, M):
+    import hjbdp
+    cost, Xf, left, thr, tol = _inputs(M, 100 + M)
+    n = 0
+    for use_thr in (True, False):
+        for use_tol in (True, False):
+            for use_left in (True, False):
+                kw = dict(X_final=Xf, left=left if use_left else None)
+                got = hjbdp.campaign_reduce(cost, M, cost_threshold=thr if use_thr else None, settle_tol=tol if use_tol else None, **kw)
+                want = refs.reduce(cost, M, threshold=thr if use_thr else None, tol=tol if use_tol else None, **kw)
+                assert got["stats"].shape == (4, 8)
+                assert np.array_equal(_bits(got["stats"]), _bits(want)), (M, use_thr, use_tol, use_left, got["stats"], want)
+                if not use_thr:
+                    assert not got["stats"][:, 4].any()
+                if not use_left:
+                    assert not got["stats"][:, 5].any()
+                if not use_tol:
+                    assert not got["stats"][:, 6].any() and np.array_equal(_bits(got["stats"][:, 7]), np.zeros(4, dtype=np.uint64))
+                n += 1
+    assert n == 8
+    # the thresholds are strict, the tolerance is not: set exactly at a sample's cost and at |xf|
+    c2 = cost.reshape(4, M)
+    at = np.array([c2[s, M // 3] if np.isfinite(c2[s, M // 3]) else 1.0 for s in range(4)])
+    got = hjbdp.campaign_reduce(cost, M, X_final=Xf, cost_threshold=at, settle_tol=np.abs(Xf[:, 0]))
+    with np.errstate(invalid="ignore"):
+        assert np.array_equal(got["n_exceed"], (c2 > at[:, None]).sum(axis=1))
+        assert np.array_equal(got["n_settled"], (np.abs(Xf) <= np.abs(Xf[:, :1])).all(axis=0).reshape(4, M).sum(axis=1))
+    assert got["n_settled"][0] >= 1 and got["n_exceed"].dtype == np.int64
+
+
+@pytest.mark.parametrize("M", SIZES)
+def test_sum_is_within_the_pairwise_bound_of_fsum(lib, M):
+    import hjbdp
+    rng = np.random.default_rng(7 + M)
+    cost = rng.uniform(-1.0, 1.0, size=(5, M)) * 10.0 ** rng.integers(-6, 7, size=(5, M))
+    got = hjbdp.campaign_reduce(cost.reshape(-1), M)
+    eps = np.finfo(np.float64).eps
+    for s in range(5):
+        exact = math.fsum(cost[s])
+        bound = M * eps * math.fsum(np.abs(cost[s]))
+        assert abs(got["stats"][s, 0] - exact) <= bound, (M, s, got["stats"][s, 0], exact, bound)
+        assert got["min"][s] == cost[s].min() and got["max"][s] == cost[s].max()
+    # the derived statistics
+    assert np.array_equal(got["mean"], got["stats"][:, 0] / M)
+    if M == 1:
+        assert not got["var"].any() and not got["std"].any()
+    else:
+        assert np.allclose(got["var"], cost.var(axis=1, ddof=1), rtol=1e-6, atol=0) and np.all(got["var"] >= 0)
+        assert np.array_equal(got["std"], np.sqrt(got["var"]))
+    assert np.isnan(got["mean_settled"]).all() and not got["n_settled"].any()
+
+
+def test_plain_cpp_harness_agrees_with_the_restatement(tmp_path):
+    exe = tmp_path / "campaign_harness"
+    r = subprocess.run([HIPCC, "-x", "c++", "-std=c++17", "-O2", "-Wall", "-Werror", "-ffp-contract=off",
+                        "-I%s/optimal-control-dynamic-programming_amd/csrc" % ROOT, "-o", str(exe), "%s/tests/campaign_harness.cpp" % ROOT],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert [ln for ln in lines if not ln.startswith("stats ")] == ["group: ok", "identity: ok", "flags: ok", "tree: ok"], lines
+    rows = [ln.split() for ln in lines if ln.startswith("stats ")]
+    assert [(int(r[1]), int(r[2])) for r in rows] == [(M, s) for M in SIZES for s in range(3)]
+    for row in rows:
+        M, s = int(row[1]), int(row[2])
+        m = np.arange(M)
+        cost = ((m * 37 + s * 11) % 101) / 8.0 - 3.0                        # the harness' inputs, rebuilt
+        Xf = np.stack([((m * 13 + s * 7 + a * 5) % 17) / 16.0 - 0.5 for a in range(2)])
+        left = (m * 5 + s) % 7 == 0
+        want = refs.reduce(cost, M, X_final=Xf, left=left, threshold=[1.0 + s], tol=[0.25, 0.375])
+        assert [int(w, 16) for w in row[3:]] == _bits(want)[0].tolist(), (M, s, row[3:], want)
+
+
+def test_group_sizes():
+    assert [refs.group(M) for M in (1, 2, 3, 4, 5, 63, 64, 65, 200, 1 << 20)] == [1, 2, 4, 4, 8, 64, 64, 64, 64, 64]
+
+
+# ---- refusals --------------------------------------------------------------------------------------------------------------------
+def _err(lib):
+    return lib.hjb_rollout_last_error(None).decode()
+
+
+def test_reduce_refusals_leave_the_outputs_untouched(lib):
+    from hjbdp import _abi
+    dp = lambda *v: (C.c_double * len(v))(*v)
+    cost, xf = dp(1.0, 2.0, 3.0, 4.0), dp(*([0.1] * 8))
+    nan = float("nan")
+    for args, text in (((2, 0, 2, cost, xf, None, None, None), "n_samples=0 < 1"),
+                       ((2, -3, 2, cost, xf, None, None, None), "n_samples=-3 < 1"),
+                       ((2 ** 62, 4, 2, cost, xf, None, None, None), "n_starts * n_samples overflows"),
+                       ((-1, 2, 2, cost, xf, None, None, None), "n_starts=-1 < 0"),
+                       ((2, 2, 0, cost, xf, None, None, None), "D=0 not in 1..6"),
+                       ((2, 2, 7, cost, xf, None, None, None), "D=7 not in 1..6"),
+                       ((2, 2, 2, cost, xf, None, dp(1.0, nan), None), "threshold[1] is NaN"),
+                       ((2, 2, 2, cost, xf, None, None, dp(nan, 1.0)), "tol[0]"),
+                       ((2, 2, 2, cost, xf, None, None, dp(1.0, -1e-300)), "tol[1]"),
+                       ((2, 2, 2, None, xf, None, None, None), "null cost / stats"),
+                       ((2, 2, 2, cost, None, None, None, dp(1.0, 1.0)), "tol given without X_final")):
+        stats = (C.c_double * 16)(*([7.25] * 16))
+        assert lib.hjb_rollout_campaign_reduce(*args, stats) == _abi.HJB_E_INVALID, args[:3]
+        assert text in _err(lib) and "hjb_rollout_campaign_reduce" in _err(lib), (_err(lib), text)
+        assert list(stats) == [7.25] * 16
+    assert lib.hjb_rollout_campaign_reduce(2, 2, 2, cost, xf, None, None, None, None) == _abi.HJB_E_INVALID and "null cost / stats" in _err(lib)
+    # infinite thresholds and a zero tolerance are values, not errors; no starts is no work
+    stats = (C.c_double * 16)(*([7.25] * 16))
+    assert lib.hjb_rollout_campaign_reduce(2, 2, 2, cost, xf, None, dp(float("inf"), -float("inf")), dp(0.0, 0.1), stats) == _abi.HJB_OK
+    assert list(stats)[4] == 0.0 and list(stats)[8 + 4] == 2.0
+    assert lib.hjb_rollout_campaign_reduce(0, 2, 2, None, None, None, None, None, None) == _abi.HJB_OK
+
+
+def test_run_campaign_refusals_that_need_no_object(lib):
+    from hjbdp import _abi
+    d = (C.c_double * 8)(*([0.5] * 8))
+    stats = (C.c_double * 8)(*([7.25] * 8))
+    ms = C.c_double(7.25)
+    for (ns, M, first), text in (((1, 1, -1), "first_stream=-1 < 0"), ((1, 0, 0), "n_samples=0 < 1"), ((1, -5, 0), "n_samples=-5 < 1"),
+                                 ((2 ** 40, 2 ** 40, 0), "n_starts * n_samples overflows"), ((3, 2 ** 61, 2 ** 62), "first_stream + n_starts * n_samples overflows"),
+                                 ((1, 1, 2 ** 63 - 1), "first_stream + n_starts * n_samples overflows")):
+        assert lib.hjb_rollout_run_campaign(None, 1, 0, None, ns, M, d, 0, first, None, None, stats, C.byref(ms)) == _abi.HJB_E_INVALID
+        assert text in _err(lib) and "hjb_rollout_run_campaign" in _err(lib), (_err(lib), text)
+    assert lib.hjb_rollout_run_campaign(None, 1, 0, None, 1, 1, d, 0, 0, None, None, stats, C.byref(ms)) == _abi.HJB_E_INVALID
+    assert "null handle" in _err(lib)
+    assert list(stats) == [7.25] * 8 and ms.value == 7.25
+
+
+def test_python_face_checks_its_arguments(lib):
+    import hjbdp
+    with pytest.raises(ValueError):
+        hjbdp.campaign_reduce(np.zeros(7), 2)
+    with pytest.raises(ValueError):
+        hjbdp.campaign_reduce(np.zeros(4), 2, settle_tol=0.1)
+    with pytest.raises(ValueError):
+        hjbdp.campaign_reduce(np.zeros(4), 2, X_final=np.zeros((2, 3)))
+    with pytest.raises(hjbdp.HjbError):
+        hjbdp.campaign_reduce(np.zeros(4), 2, cost_threshold=[1.0, np.nan])
+    out = hjbdp.campaign_reduce([1.0, 3.0, 2.0, 2.0], 2, X_final=[[0.0, 1.0, 0.0, 0.0]], settle_tol=0.5, cost_threshold=1.5)
+    assert out["mean"].tolist() == [2.0, 2.0] and out["var"].tolist() == [2.0, 0.0] and out["n_exceed"].tolist() == [1, 2]
+    assert out["n_settled"].tolist() == [1, 2] and out["mean_settled"].tolist() == [1.0, 2.0] and out["n_left"].tolist() == [0, 0]

@@ -1,0 +1,80 @@
+"""CPU tests of the noisy campaign's ABI (include/hjbdp.h "noisy campaigns"): the prototypes in both headers and in the ctypes
+table, the constant HJB_CAMPAIGN_NSTAT, the contract's wording, and the MATLAB shim's call sequence and arities.  No GPU."""
+import ctypes as C
+import re
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+CAMPAIGN_FNS = {"hjb_rollout_run_campaign": 13, "hjb_rollout_campaign_reduce": 9}
+SHIM = ROOT / "optimal-control-dynamic-programming_amd" / "matlab" / "Dynamic_Solver_hjbdp_noisy_cost_map.m"
+
+
+@pytest.fixture(scope="module")
+def lib(built):
+    import hjbdp
+    return hjbdp.load_library()
+
+
+def test_campaign_prototypes_are_identical_in_both_headers_and_the_ctypes_table(lib):
+    from hjbdp import _abi
+    from test_abi import _prototypes
+    full = _prototypes((ROOT / "include" / "hjbdp.h").read_text())
+    flat = _prototypes((ROOT / "include" / "hjbdp_matlab.h").read_text())
+    for name, arity in CAMPAIGN_FNS.items():
+        assert name in full and name in flat, name
+        assert full[name] == flat[name], (name, full[name], flat[name])
+        assert len(full[name]) == arity, (name, full[name])
+        assert hasattr(lib, name), name
+        res, args = _abi.SYMBOLS[name]
+        assert res is C.c_int32 and len(args) == arity, name
+    assert full["hjb_rollout_run_campaign"] == ["void*", "int32_t", "int32_t", "int32_t*", "int64_t", "int64_t", "double*", "uint64_t",
+                                                "int64_t", "double*", "double*", "double*", "double*"]
+    assert full["hjb_rollout_campaign_reduce"] == ["int64_t", "int64_t", "int32_t", "double*", "double*", "uint8_t*", "double*", "double*",
+                                                   "double*"]
+    run = _abi.SYMBOLS["hjb_rollout_run_campaign"][1]
+    assert run[0] is C.c_void_p and run[4] is C.c_int64 and run[5] is C.c_int64 and run[7] is C.c_uint64 and run[8] is C.c_int64
+    red = _abi.SYMBOLS["hjb_rollout_campaign_reduce"][1]
+    assert red[:3] == [C.c_int64, C.c_int64, C.c_int32] and red[5] == C.POINTER(C.c_uint8)
+
+
+def test_the_constant_and_the_contract_are_stated_in_the_header(lib):
+    from hjbdp import _abi
+    text = (ROOT / "include" / "hjbdp.h").read_text()
+    m = re.search(r"^#define\s+HJB_CAMPAIGN_NSTAT\s+(\d+)\s*$", text, flags=re.M)
+    assert m and int(m.group(1)) == _abi.HJB_CAMPAIGN_NSTAT == 8
+    for word in ("first_stream + s*M + m", "G = min(64, smallest power of two >= M)", "op(v[i], v[i + 2^L])", "b < a ? b : a",
+                 "b > a ? b : a", "acc = p_0, then acc = op(acc, p_b)", "v2 = +inf, v3 = -inf", "a NaN counts as left",
+                 'Option "chunk" changes no bit', "quantiles", "campaigns of the integrated plants"):
+        assert word in text, word
+    shared = (ROOT / "optimal-control-dynamic-programming_amd" / "csrc" / "hjbdp_campaign.h").read_text()
+    assert "__host__ __device__" in shared and "hip_runtime" not in shared      # the kernel, the host reduce and plain C++ share it
+
+
+def test_python_faces_exist():
+    import hjbdp
+    assert callable(hjbdp.campaign_reduce) and "campaign_reduce" in hjbdp.__all__
+    assert callable(hjbdp.Rollout.run_campaign)
+    assert callable(hjbdp.Dynamic_Solver.get_noisy_cost_statistics) and callable(hjbdp.Dynamic_Solver.noisy_cost_map)
+
+
+def test_matlab_shim_call_sequence():
+    """the shim drives the entry points Dynamic_Solver.noisy_cost_map drives, in its order, each with the flat header's arity"""
+    from test_abi import _matlab_calllibs, _prototypes
+    flat = _prototypes((ROOT / "include" / "hjbdp_matlab.h").read_text())
+    text = SHIM.read_text()
+    calls = _matlab_calllibs(text)
+    names = [n for n, _ in calls]
+    body = [n for n in names if n not in ("hjb_rollout_last_error", "hjb_status_string")]
+    assert body == ["hjb_rollout_create", "hjb_rollout_destroy", "hjb_rollout_set_model", "hjb_rollout_set_noise",
+                    "hjb_rollout_run_campaign"], body
+    for name, nargs in calls:
+        assert nargs == len(flat[name]), (name, nargs, flat[name])
+    assert "hjb_rollout_run_noisy" not in names                                 # no per-trajectory array on the MATLAB side either
+    assert "zeros(8, ns)" in text and "ndgrid(s_r, s_r)" in text and "tested twin: hjbdp/dynamic_solver.py noisy_cost_map" in text
+    twin = (ROOT / "optimal-control-dynamic-programming_amd" / "hjbdp" / "dynamic_solver.py").read_text()
+    twin = twin[twin.index("def _noisy_policy_rollout("):twin.index("def get_greedy_paths(")]
+    for call in ("set_model(", "set_noise(", "run_campaign("):
+        assert call in twin, call
+    assert "run_noisy(" not in twin
