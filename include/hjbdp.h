@@ -516,8 +516,9 @@ int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_tr
  * hjb_rollout_run_noisy refuses (n_starts in the place of n_traj; no noise set; another model set); null stats; n_samples < 1;
  * n_starts * n_samples or first_stream + n_starts * n_samples overflowing int64; a threshold entry that is NaN; a tol entry that
  * is NaN or negative.
- * Out of scope: campaigns of the greedy / lookahead controllers (csrc/hjbdp_campaign.h is written for them to reuse), quantiles
- * and histograms, campaigns of the integrated plants. */
+ * The campaign of the lookahead controller is hjb_rollout_run_lookahead_campaign (kernel K29, below): the same statistics on the
+ * same streams; csrc/hjbdp_campaign.h serves both.
+ * Out of scope: quantiles and histograms, campaigns of the integrated plants. */
 #define HJB_CAMPAIGN_NSTAT 8
 int32_t hjb_rollout_run_campaign(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts,
                                  int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream, const double *threshold,
@@ -624,6 +625,45 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
                                    double *cost, double *X_path, double *U_path, double *L_path, double *V_path, int32_t mode,
                                    int32_t n_nodes, const double *offsets, const double *weights, const int32_t *nodes,
                                    int32_t n_flight_nodes, const double *flight_offsets);
+
+/* ---- lookahead campaigns: per-start cost statistics of the flown lookahead, reduced on the device (kernel K29) ------------------
+ * hjb_rollout_run_lookahead_campaign is hjb_rollout_run_campaign for the controller of hjb_rollout_run_lookahead: n_starts starts
+ * flown n_samples (M) times each, one record of HJB_CAMPAIGN_NSTAT doubles per start.  The controller is the object's value planes
+ * (hjb_rollout_set_values; value_plane_of_step, -1 = the zero function) under the lookahead set of hjb_rollout_set_lookahead; the
+ * plant is the node set of hjb_rollout_set_noise.  The two sets may differ; the nominal greedy controller (K26) under noise is one
+ * zero lookahead node of weight 1.  There is no nominal-plant form: a campaign of a deterministic flight is M copies of one number.
+ * Trajectories.  Sample m of start s is hjb_rollout_run_lookahead's trajectory with fly_noise = 1 from X0[:, s] on stream
+ *   first_stream + s*M + m of `seed`: its cost c, its final state xf and its visited states are the bits hjb_rollout_run_lookahead
+ *   gives for an X0 with every start repeated M times.  Options "chunk" and "lds" change no bit.
+ * Common random numbers.  Sample m of start s flies the same stream under every controller: hjb_rollout_run_campaign and this call
+ *   with one seed, first_stream, n_starts and M draw the same node at every step of every sample, so the per-start means of the two
+ *   controllers can be differenced with the sampling noise largely cancelled.
+ * The statistics, the slot values of a sample, the padding, the reduction order and the output stats [HJB_CAMPAIGN_NSTAT, n_starts]
+ *   are hjb_rollout_run_campaign's (above), word for word; the left-the-grid flag is evaluated on the states as flown, after the noise.
+ *   hjb_rollout_campaign_reduce of hjb_rollout_run_lookahead's per-trajectory outputs gives the same bits.
+ * Device memory of a call: [D + 1 + 8, n_starts] doubles plus 8 doubles per block of a launch; launches of at most option "chunk"
+ *   lanes; a start's blocks may straddle launches.  No array has a dimension of n_starts * M.  Table placement is K27's.
+ * hjb_rollout_lookahead_campaign_host runs the same functions on the CPU, with no device and no object: hjb_rollout_lookahead_host's
+ * problem (D .. value_plane_of_step) and lookahead set (mode, n_nodes >= 1, offsets, weights), then the flight set (n_flight_nodes
+ * >= 1, flight_offsets [D, n_flight_nodes] column-major, flight_weights or NULL = equal: hjb_rollout_set_noise's arguments), then
+ * the campaign's arguments.  It never holds more than one start's samples.
+ * Refused before any device work, outputs untouched (text: hjb_rollout_last_error) - HJB_E_INVALID: everything
+ * hjb_rollout_run_lookahead refuses with fly_noise = 1 (n_starts in the place of n_traj; no lookahead set; no noise set; another
+ * model set; a plane outside the value planes); null stats; n_samples < 1; n_starts * n_samples or first_stream + n_starts *
+ * n_samples overflowing int64; a threshold entry that is NaN; a tol entry that is NaN or negative.  n_starts = 0 is HJB_OK.
+ * Out of scope: quantiles and histograms, a paired-difference statistic computed on the device, sharing the first step's lookahead
+ * among a start's samples, campaigns of the integrated plants, float16 value planes. */
+int32_t hjb_rollout_run_lookahead_campaign(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
+                                           int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
+                                           const double *threshold, const double *tol, double *stats, double *device_ms);
+int32_t hjb_rollout_lookahead_campaign_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u,
+                                            const double *u_table, const double *A, const double *B, const double *c, const double *q,
+                                            const double *r, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
+                                            const int32_t *value_plane_of_step, int32_t mode, int32_t n_nodes, const double *offsets,
+                                            const double *weights, int32_t n_flight_nodes, const double *flight_offsets,
+                                            const double *flight_weights, int64_t n_starts, int64_t n_samples, const double *X0,
+                                            uint64_t seed, int64_t first_stream, const double *threshold, const double *tol,
+                                            double *stats);
 
 /* The 6-D attitude closed loop (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run) on the same object.
  * hjb_rollout_set_attitude_model and hjb_rollout_set_model replace each other: the last one set wins.  It needs D == 6, n_u == 3

@@ -153,6 +153,13 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
                                    double *cost, double *X_path, double *U_path, double *L_path, double *V_path, int32_t mode,
                                    int32_t n_nodes, const double *offsets, const double *weights, const int32_t *nodes,
                                    int32_t n_flight_nodes, const double *flight_offsets);
+/* the flown lookahead as a campaign (kernel K29): hjb_rollout_run_campaign's arguments without the method, for the controller of
+ * hjb_rollout_run_lookahead (value planes under the lookahead set) on the plant of hjb_rollout_set_noise; sample m of start s on
+ * stream first_stream + s * n_samples + m - the stream hjb_rollout_run_campaign gives it, so the two campaigns of one seed fly common
+ * random numbers; stats [8, n_starts] as there (hjbdp.h); usage: matlab/Dynamic_Solver_hjbdp_lookahead_cost_map.m */
+int32_t hjb_rollout_run_lookahead_campaign(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
+                                           int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
+                                           const double *threshold, const double *tol, double *stats, double *device_ms);
 /* the 6-D attitude loop on the same object (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run);
  * usage: matlab/Solver_attitude_hjbdp_get_optimal_paths.m */
 int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, double h, int32_t integrator, const double *q,

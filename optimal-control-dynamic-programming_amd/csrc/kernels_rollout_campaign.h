@@ -194,4 +194,8 @@ k_rollout_campaign(const DCampaignArgs K) {
 hipError_t launch_rollout_campaign(int idx_bytes, int method, bool lds_on, int D, const DRollout &R, const DNoise &N,
                                    const DCampaign &Cp, size_t lds, hipStream_t st, const double *X0, double *stats);
 
+// the fold alone (k_campaign_fold over the starts the launch Cp touches), behind a kernel that wrote Cp.partials on `st`: what
+// launch_rollout_campaign ends in, and what the campaigns of other controllers (K29, kernels_rollout_lookahead_campaign.h) call
+hipError_t launch_campaign_fold(const DCampaign &Cp, hipStream_t st, double *stats);
+
 }  // namespace hjb

@@ -15,6 +15,8 @@
 // the noise set, and no other run function reads it.  Its host twin hjb_rollout_lookahead_host (hjbdp_lookahead.h) needs no device.
 // And hjb_rollout_run_campaign (K28, kernels_rollout_campaign.h / rollout_campaign.hip) reduces the noisy flights of the stored labels
 // per start on the device; its host side and the host reduce hjb_rollout_campaign_reduce are rollout_campaign_host.hip.
+// hjb_rollout_run_lookahead_campaign (K29, kernels_rollout_lookahead_campaign.h) does the same for the lookahead controller; it and
+// its host twin are rollout_lookahead_campaign_host.hip, on check_lookahead_run and look_host_args / look_host_model below.
 // Defined here for the host units (rollout_host.h): rfail, check_run / check_traj / check_quaternions (the run functions'
 // refusals, all before any device work), upload, run_chunks (the chunk loop).  No kernel is instantiated in this unit.
 #include "rollout_host.h"
@@ -50,19 +52,6 @@ void drop_attached(Rollout *ro) {
     if (!ro->att) return;
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     ro->att.reset();
-}
-
-// What hjb_rollout_set_noise and hjb_rollout_noise_table refuse of a weight vector (null: equal weights), said in `who`'s name:
-// a weight that is not finite or is negative, weights that sum to 0.  HJB_OK otherwise.
-int check_weights(Rollout *ro, const char *who, int32_t n_nodes, const double *weights) {
-    if (!weights) return HJB_OK;
-    double sum = 0.0;
-    for (int w = 0; w < n_nodes; ++w) {
-        if (!std::isfinite(weights[w]) || weights[w] < 0) return rfail(ro, HJB_E_INVALID, "%s: weight %d is not finite or is negative", who, w);
-        sum = sum + weights[w];
-    }
-    if (!(sum > 0) || !std::isfinite(sum)) return rfail(ro, HJB_E_INVALID, "%s: the %d weights sum to 0 (or their sum overflows)", who, n_nodes);
-    return HJB_OK;
 }
 
 // What hjb_rollout_create (who: "rollout") and hjb_rollout_greedy_host (its own name) refuse of a grid: an axis of fewer than two
@@ -160,6 +149,86 @@ int check_quaternions(Rollout *ro, const char *pre, int64_t n_traj, const double
             return rfail(ro, HJB_E_INVALID, "%s: X0 column %lld has an all-zero quaternion (0/0 at the first renormalisation)", pre,
                          (long long)i);
     }
+    return HJB_OK;
+}
+
+// What hjb_rollout_set_noise and hjb_rollout_noise_table refuse of a weight vector (null: equal weights), said in `who`'s name:
+// a weight that is not finite or is negative, weights that sum to 0.  HJB_OK otherwise.
+int check_weights(Rollout *ro, const char *who, int32_t n_nodes, const double *weights) {
+    if (!weights) return HJB_OK;
+    double sum = 0.0;
+    for (int w = 0; w < n_nodes; ++w) {
+        if (!std::isfinite(weights[w]) || weights[w] < 0) return rfail(ro, HJB_E_INVALID, "%s: weight %d is not finite or is negative", who, w);
+        sum = sum + weights[w];
+    }
+    if (!(sum > 0) || !std::isfinite(sum)) return rfail(ro, HJB_E_INVALID, "%s: the %d weights sum to 0 (or their sum overflows)", who, n_nodes);
+    return HJB_OK;
+}
+
+int check_lookahead_run(Rollout *ro, const char *who, int fly_noise, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj) {
+    if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
+    if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
+    if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_model", who);
+    if (ro->model != kModelAffine)
+        return rfail(ro, HJB_E_INVALID, "rollout: %s needs the affine model (hjb_rollout_set_model); the object holds another", who);
+    if (ro->L.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_lookahead", who);
+    if (fly_noise && ro->N.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s with fly_noise=1 before hjb_rollout_set_noise", who);
+    if (n_steps > 0 && !value_plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null value_plane_of_step");
+    for (int k = 0; k < n_steps; ++k) {
+        const int32_t p = value_plane_of_step[k];
+        if (p >= 0 && ro->val_planes < 1)
+            return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_values (value_plane_of_step[%d] = %d; only -1 needs no values)",
+                         who, k, p);
+        if (p < -1 || p >= ro->val_planes)
+            return rfail(ro, HJB_E_INVALID, "rollout: value_plane_of_step[%d] = %d outside [-1, %d)", k, p, ro->val_planes);
+    }
+    return HJB_OK;
+}
+
+int look_host_args(const char *who, int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
+                   const double *A, const double *B, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
+                   int64_t n_traj, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights) {
+    if (D < 1 || D > HJB_MAX_D) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, HJB_MAX_D);
+    if (n_u < 1 || n_u > HJB_ROLLOUT_MAX_U) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: n_u=%d not in 1..%d", who, n_u, HJB_ROLLOUT_MAX_U);
+    if (!n || !knots || !u_table || !A || !B) return rfail(nullptr, HJB_E_INVALID, "%s: null argument (n, knots, u_table, A and B are required)", who);
+    if (n_labels < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_labels=%d < 1", who, n_labels);
+    if (dtype != HJB_F32 && dtype != HJB_F64) return rfail(nullptr, HJB_E_INVALID, "%s: dtype %d is not HJB_F32 / HJB_F64", who, dtype);
+    if (n_value_planes < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_value_planes=%d < 0", who, n_value_planes);
+    if (n_value_planes > 0 && !values) return rfail(nullptr, HJB_E_INVALID, "%s: null values with n_value_planes=%d", who, n_value_planes);
+    if (n_steps < 0 || n_traj < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_steps=%d, n_traj=%lld (both >= 0)", who, n_steps, (long long)n_traj);
+    if (const int bad = check_lookahead(nullptr, who, D, mode, n_nodes, offsets, weights)) return bad;
+    if (n_nodes < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_nodes=%d < 1 (the lookahead needs a node set)", who, n_nodes);
+    return HJB_OK;
+}
+
+int look_host_model(const char *who, int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
+                    const double *A, const double *B, const double *c, const double *q, const double *r, int32_t n_value_planes,
+                    int32_t n_steps, const int32_t *value_plane_of_step, int32_t mode, int32_t n_nodes, const double *offsets,
+                    const double *weights, LookHostProblem &P) {
+    int64_t nS = 1, n_knots = 0;
+    if (const int bad_grid = check_grid(who, D, n, knots, &nS, &n_knots)) return bad_grid;
+    if (!all_finite(u_table, (int64_t)n_labels * n_u)) return rfail(nullptr, HJB_E_INVALID, "%s: u_table is not finite", who);
+    if (!all_finite(A, (int64_t)D * D) || !all_finite(B, (int64_t)D * n_u) || !all_finite(c, D) || !all_finite(q, D) || !all_finite(r, n_u))
+        return rfail(nullptr, HJB_E_INVALID, "%s: the model (A, B, c, q, r) is not finite", who);
+    if (n_steps > 0 && !value_plane_of_step) return rfail(nullptr, HJB_E_INVALID, "%s: null value_plane_of_step", who);
+    for (int k = 0; k < n_steps; ++k)
+        if (value_plane_of_step[k] < -1 || value_plane_of_step[k] >= n_value_planes)
+            return rfail(nullptr, HJB_E_INVALID, "%s: value_plane_of_step[%d] = %d outside [-1, %d)", who, k, value_plane_of_step[k], n_value_planes);
+    GreedyModel &M = P.M;
+    P.rdx.assign((size_t)n_knots, 0.0);
+    greedy_grid(D, n, knots, M, P.rdx.data());
+    M.n_u = n_u;
+    M.n_labels = n_labels;
+    M.has_c = c ? 1 : 0;
+    std::memcpy(M.A, A, sizeof(double) * D * D);
+    std::memcpy(M.B, B, sizeof(double) * D * n_u);
+    if (c) std::memcpy(M.c, c, sizeof(double) * D);
+    if (q) std::memcpy(M.q, q, sizeof(double) * D);
+    if (r) std::memcpy(M.r, r, sizeof(double) * n_u);
+    P.L.mode = mode;
+    P.tab.assign((size_t)n_nodes * (1 + D), 0.0);
+    (void)look_table(D, n_nodes, offsets, weights, P.L, P.tab.data());
+    P.L.tab = P.tab.data();
     return HJB_OK;
 }
 
@@ -733,22 +802,7 @@ int32_t hjb_rollout_run_lookahead(void *rollout, int32_t fly_noise, int32_t n_st
         return rfail(ro, HJB_E_INVALID, "%s: first_stream + n_traj overflows (%lld + %lld)", who, (long long)first_stream, (long long)n_traj);
     if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
     std::lock_guard<std::mutex> g(ro->mu);
-    if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
-    if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
-    if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_model", who);
-    if (ro->model != kModelAffine)
-        return rfail(ro, HJB_E_INVALID, "rollout: %s needs the affine model (hjb_rollout_set_model); the object holds another", who);
-    if (ro->L.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_lookahead", who);
-    if (fly_noise && ro->N.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s with fly_noise=1 before hjb_rollout_set_noise", who);
-    if (n_steps > 0 && !value_plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null value_plane_of_step");
-    for (int k = 0; k < n_steps; ++k) {
-        const int32_t p = value_plane_of_step[k];
-        if (p >= 0 && ro->val_planes < 1)
-            return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_values (value_plane_of_step[%d] = %d; only -1 needs no values)",
-                         who, k, p);
-        if (p < -1 || p >= ro->val_planes)
-            return rfail(ro, HJB_E_INVALID, "rollout: value_plane_of_step[%d] = %d outside [-1, %d)", k, p, ro->val_planes);
-    }
+    if (const int bad = check_lookahead_run(ro, who, fly_noise, n_steps, value_plane_of_step, n_traj)) return bad;
     if (n_traj == 0) {
         if (device_ms) *device_ms = 0.0;
         return HJB_OK;
@@ -791,31 +845,19 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
                                    double *L_path, double *V_path, int32_t mode, int32_t n_nodes, const double *offsets,
                                    const double *weights, const int32_t *nodes, int32_t n_flight_nodes, const double *flight_offsets) {
     const char *const who = "hjb_rollout_lookahead_host";
-    if (D < 1 || D > HJB_MAX_D) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, HJB_MAX_D);
-    if (n_u < 1 || n_u > HJB_ROLLOUT_MAX_U) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: n_u=%d not in 1..%d", who, n_u, HJB_ROLLOUT_MAX_U);
-    if (!n || !knots || !u_table || !A || !B) return rfail(nullptr, HJB_E_INVALID, "%s: null argument (n, knots, u_table, A and B are required)", who);
-    if (n_labels < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_labels=%d < 1", who, n_labels);
-    if (dtype != HJB_F32 && dtype != HJB_F64) return rfail(nullptr, HJB_E_INVALID, "%s: dtype %d is not HJB_F32 / HJB_F64", who, dtype);
-    if (n_value_planes < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_value_planes=%d < 0", who, n_value_planes);
-    if (n_value_planes > 0 && !values) return rfail(nullptr, HJB_E_INVALID, "%s: null values with n_value_planes=%d", who, n_value_planes);
-    if (n_steps < 0 || n_traj < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_steps=%d, n_traj=%lld (both >= 0)", who, n_steps, (long long)n_traj);
-    if (const int bad = check_lookahead(nullptr, who, D, mode, n_nodes, offsets, weights)) return bad;
-    if (n_nodes < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_nodes=%d < 1 (the lookahead needs a node set)", who, n_nodes);
+    if (const int bad = look_host_args(who, D, n, knots, n_labels, n_u, u_table, A, B, dtype, n_value_planes, values, n_steps, n_traj, mode,
+                                       n_nodes, offsets, weights))
+        return bad;
     if (nodes) {
         if (n_flight_nodes < 1 || n_flight_nodes > HJB_DIST_MAX_NODES)
             return rfail(nullptr, HJB_E_INVALID, "%s: n_flight_nodes=%d not in 1..%d", who, n_flight_nodes, HJB_DIST_MAX_NODES);
         if (!flight_offsets) return rfail(nullptr, HJB_E_INVALID, "%s: nodes given with null flight_offsets", who);
         if (!all_finite(flight_offsets, (int64_t)D * n_flight_nodes)) return rfail(nullptr, HJB_E_INVALID, "%s: flight_offsets is not finite", who);
     }
-    int64_t nS = 1, n_knots = 0;
-    if (const int bad_grid = check_grid(who, D, n, knots, &nS, &n_knots)) return bad_grid;
-    if (!all_finite(u_table, (int64_t)n_labels * n_u)) return rfail(nullptr, HJB_E_INVALID, "%s: u_table is not finite", who);
-    if (!all_finite(A, (int64_t)D * D) || !all_finite(B, (int64_t)D * n_u) || !all_finite(c, D) || !all_finite(q, D) || !all_finite(r, n_u))
-        return rfail(nullptr, HJB_E_INVALID, "%s: the model (A, B, c, q, r) is not finite", who);
-    if (n_steps > 0 && !value_plane_of_step) return rfail(nullptr, HJB_E_INVALID, "%s: null value_plane_of_step", who);
-    for (int k = 0; k < n_steps; ++k)
-        if (value_plane_of_step[k] < -1 || value_plane_of_step[k] >= n_value_planes)
-            return rfail(nullptr, HJB_E_INVALID, "%s: value_plane_of_step[%d] = %d outside [-1, %d)", who, k, value_plane_of_step[k], n_value_planes);
+    LookHostProblem P;
+    if (const int bad = look_host_model(who, D, n, knots, n_labels, n_u, u_table, A, B, c, q, r, n_value_planes, n_steps, value_plane_of_step,
+                                        mode, n_nodes, offsets, weights, P))
+        return bad;
     if (n_traj == 0) return HJB_OK;
     const int bad_traj = check_traj(nullptr, who, D, "D", n_steps, n_traj, X0, X_final);
     if (bad_traj) return bad_traj;
@@ -823,22 +865,6 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
         for (int64_t e = 0; e < n_traj * (int64_t)n_steps; ++e)
             if (nodes[e] < 0 || nodes[e] >= n_flight_nodes)
                 return rfail(nullptr, HJB_E_INVALID, "%s: nodes element %lld = %d outside [0, %d)", who, (long long)e, nodes[e], n_flight_nodes);
-    GreedyModel M{};
-    std::vector<double> rdx((size_t)n_knots);
-    greedy_grid(D, n, knots, M, rdx.data());
-    M.n_u = n_u;
-    M.n_labels = n_labels;
-    M.has_c = c ? 1 : 0;
-    std::memcpy(M.A, A, sizeof(double) * D * D);
-    std::memcpy(M.B, B, sizeof(double) * D * n_u);
-    if (c) std::memcpy(M.c, c, sizeof(double) * D);
-    if (q) std::memcpy(M.q, q, sizeof(double) * D);
-    if (r) std::memcpy(M.r, r, sizeof(double) * n_u);
-    LookSet L{};
-    L.mode = mode;
-    std::vector<double> tab((size_t)n_nodes * (1 + D));
-    (void)look_table(D, n_nodes, offsets, weights, L, tab.data());
-    L.tab = tab.data();
     int fmask = 0;                                            // the flight set's mask, as hjb_rollout_set_noise forms it
     for (int w = 0; nodes && w < n_flight_nodes; ++w)
         for (int a = 0; a < D; ++a)
@@ -846,7 +872,7 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
     with_bool(dtype == HJB_F32, [&](auto f) {
         with_dim(D, [&](auto d) {
             using TV = std::conditional_t<decltype(f)::value, float, double>;
-            lookahead_rollout_host<decltype(d)::value, TV>(M, L, knots, rdx.data(), u_table, static_cast<const TV *>(values), n_steps,
+            lookahead_rollout_host<decltype(d)::value, TV>(P.M, P.L, knots, P.rdx.data(), u_table, static_cast<const TV *>(values), n_steps,
                                                            value_plane_of_step, n_traj, X0, nodes, fmask, flight_offsets, X_final, cost,
                                                            X_path, U_path, L_path, V_path);
         });

@@ -63,9 +63,13 @@ hipError_t launch_rollout_campaign(int idx_bytes, int method, bool lds_on, int D
     });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_campaign_fold(Cp, st, stats);
+}
+
+hipError_t launch_campaign_fold(const DCampaign &Cp, hipStream_t st, double *stats) {
     // the starts this launch touches: block0 / B .. (block0 + n_blocks - 1) / B
     const int64_t s0 = Cp.block0 / Cp.B, n_fold = (Cp.block0 + Cp.n_blocks - 1) / Cp.B - s0 + 1;
-    hipLaunchKernelGGL(k_campaign_fold, dim3((unsigned)((n_fold + 255) / 256)), b, 0, st, Cp.n_blocks, Cp.block0, Cp.B, s0, n_fold,
+    hipLaunchKernelGGL(k_campaign_fold, dim3((unsigned)((n_fold + 255) / 256)), dim3(256), 0, st, Cp.n_blocks, Cp.block0, Cp.B, s0, n_fold,
                        (const double *)Cp.partials, stats);
     return hipGetLastError();
 }

@@ -10,9 +10,9 @@
 
 using namespace hjbhost;
 
-namespace {
+namespace hjbhost {
 
-// What both entry points refuse of the campaign's sizes, in `who`'s name: n_samples < 1, n_starts * n_samples overflowing
+// What the campaigns' entry points refuse of their sizes, in `who`'s name: n_samples < 1, n_starts * n_samples overflowing
 int check_campaign_sizes(Rollout *ro, const char *who, int64_t n_starts, int64_t n_samples) {
     if (n_samples < 1) return rfail(ro, HJB_E_INVALID, "%s: n_samples=%lld < 1", who, (long long)n_samples);
     if (n_starts > 0 && n_samples > INT64_MAX / n_starts)
@@ -29,37 +29,23 @@ int check_campaign_bounds(Rollout *ro, const char *who, int D, int64_t n_starts,
     return HJB_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t hjb_rollout_run_campaign(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts,
-                                 int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream, const double *threshold,
-                                 const double *tol, double *stats, double *device_ms) {
-    Rollout *ro = (Rollout *)rollout;
-    const char *const who = "hjb_rollout_run_campaign";
-    // every refusal before any device work, the outputs untouched; the ones that need no object first
+// ... and of its streams, with the sizes first: what a run function refuses before it needs an object
+int check_campaign_streams(Rollout *ro, const char *who, int64_t n_starts, int64_t n_samples, int64_t first_stream) {
     if (first_stream < 0) return rfail(ro, HJB_E_INVALID, "%s: first_stream=%lld < 0", who, (long long)first_stream);
     if (const int bad = check_campaign_sizes(ro, who, n_starts, n_samples)) return bad;
     if (n_starts > 0 && first_stream > INT64_MAX - n_starts * n_samples)
         return rfail(ro, HJB_E_INVALID, "%s: first_stream + n_starts * n_samples overflows (%lld + %lld)", who, (long long)first_stream,
                      (long long)(n_starts * n_samples));
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    const int bad_arg = check_run(ro, kModelAffine, method, n_steps, plane_of_step, n_starts);
-    if (bad_arg) return bad_arg;
-    if (ro->N.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_noise", who);
-    if (n_starts == 0) {
-        if (device_ms) *device_ms = 0.0;
-        return HJB_OK;
-    }
-    const int D = ro->D;
-    if (!stats) return rfail(ro, HJB_E_INVALID, "%s: null stats", who);
-    const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_starts, X0, stats);
-    if (bad_traj) return bad_traj;
-    if (const int bad = check_campaign_bounds(ro, who, D, n_starts, threshold, tol)) return bad;
-    if (device_ms) *device_ms = 0.0;
+    return HJB_OK;
+}
 
+// The device side of a campaign call whose arguments have been checked (n_starts >= 1): X0, the thresholds and the planes of the
+// steps uploaded once, the block list walked in launches of at most option "chunk" lanes - `launch` starts the controller's kernel
+// and the fold on the launch's stream - and stats downloaded.  Under ro->mu.
+int run_campaign_launches(Rollout *ro, const char *who, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts, int64_t n_samples,
+                          const double *X0, uint64_t seed, int64_t first_stream, const double *threshold, const double *tol, double *stats,
+                          double *device_ms, const std::function<hipError_t(const CampaignLaunch &)> &launch) {
+    const int D = ro->D;
     DCampaign Cp{};
     Cp.M = n_samples;
     Cp.G = campaign_group(n_samples, &Cp.log2G);
@@ -117,7 +103,7 @@ int32_t hjb_rollout_run_campaign(void *rollout, int32_t method, int32_t n_steps,
         Cp.block0 = b0;
         Cp.n_blocks = std::min(nb_max, n_blocks - b0);
         (void)hipEventRecord(e0, stream);
-        e = launch_rollout_campaign(ro->idx_bytes, method, lds_on, D, R, N, Cp, lds, stream, (const double *)dX0, dstats);
+        e = launch(CampaignLaunch{R, N, Cp, lds, lds_on, stream, (const double *)dX0, dstats});
         if (e != hipSuccess) break;
         (void)hipEventRecord(e1, stream);
         e = hipStreamSynchronize(stream);
@@ -135,6 +121,39 @@ int32_t hjb_rollout_run_campaign(void *rollout, int32_t method, int32_t n_steps,
     }
     if (device_ms) *device_ms = ms_total;
     return HJB_OK;
+}
+
+}  // namespace hjbhost
+
+extern "C" {
+
+int32_t hjb_rollout_run_campaign(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts,
+                                 int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream, const double *threshold,
+                                 const double *tol, double *stats, double *device_ms) {
+    Rollout *ro = (Rollout *)rollout;
+    const char *const who = "hjb_rollout_run_campaign";
+    // every refusal before any device work, the outputs untouched; the ones that need no object first
+    if (const int bad = check_campaign_streams(ro, who, n_starts, n_samples, first_stream)) return bad;
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    const int bad_arg = check_run(ro, kModelAffine, method, n_steps, plane_of_step, n_starts);
+    if (bad_arg) return bad_arg;
+    if (ro->N.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_noise", who);
+    if (n_starts == 0) {
+        if (device_ms) *device_ms = 0.0;
+        return HJB_OK;
+    }
+    const int D = ro->D;
+    if (!stats) return rfail(ro, HJB_E_INVALID, "%s: null stats", who);
+    const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_starts, X0, stats);
+    if (bad_traj) return bad_traj;
+    if (const int bad = check_campaign_bounds(ro, who, D, n_starts, threshold, tol)) return bad;
+    if (device_ms) *device_ms = 0.0;
+
+    return run_campaign_launches(ro, who, n_steps, plane_of_step, n_starts, n_samples, X0, seed, first_stream, threshold, tol, stats, device_ms,
+                                 [&](const CampaignLaunch &c) {
+                                     return launch_rollout_campaign(ro->idx_bytes, method, c.lds_on, ro->D, c.R, c.N, c.C, c.lds, c.st, c.X0, c.stats);
+                                 });
 }
 
 int32_t hjb_rollout_campaign_reduce(int64_t n_starts, int64_t n_samples, int32_t D, const double *cost, const double *X_final,

@@ -1,12 +1,14 @@
 // rollout_host.h - what the host units of the rollouts share (host only; include/hjbdp.h is the public ABI): the object,
-// its refusals, the upload and the chunk loop.  Defined in rollout.hip; rollout_channels.hip and rollout_campaign_host.hip are the
-// other readers.
+// its refusals, the upload and the chunk loop.  Defined in rollout.hip (the campaigns' size and bound checks:
+// rollout_campaign_host.hip); rollout_channels.hip, rollout_campaign_host.hip and rollout_lookahead_campaign_host.hip are the other
+// readers.
 #pragma once
 #include "hjbdp_host.h"
 // the records an object holds: DRollout, DAttitude, DNoise, DPaChan (a unit includes the other kernel headers whose launch it calls)
 #include "kernels_rollout.h"
 #include "kernels_rollout_attitude.h"
 #include "kernels_rollout_noisy.h"
+#include "kernels_rollout_campaign.h"
 #include "kernels_rollout_pos_att.h"
 #include "hjbdp_lookahead.h"
 #include <functional>
@@ -52,14 +54,17 @@ struct Rollout {
     DAttitude M{};                  // the attitude model (set_attitude_model)
     std::unique_ptr<Attached> att;  // the PosAtt / Position / AttSimplified of model kModelPosAtt / kModelPosition / kModelAttSimplified
     std::shared_ptr<DevData> data;
-    // the noise node set (hjb_rollout_set_noise): N.n_nodes > 0 while one is set; read by hjb_rollout_run_noisy alone
+    // the noise node set (hjb_rollout_set_noise): N.n_nodes > 0 while one is set; read by hjb_rollout_run_noisy, _run_campaign,
+    // _run_lookahead (fly_noise) and _run_lookahead_campaign
     DNoise N{};
     std::shared_ptr<DevData> noise;     // N.tab: thresholds, then the masked axes' offsets
-    // the value planes (hjb_rollout_set_values): val_planes > 0 while some are set; read by hjb_rollout_run_greedy alone
+    // the value planes (hjb_rollout_set_values): val_planes > 0 while some are set; read by hjb_rollout_run_greedy, _run_lookahead and
+    // _run_lookahead_campaign
     std::shared_ptr<DevData> values;
     const void *dvalues = nullptr;      // [nS, val_planes] column-major, float or double
     int val_planes = 0, val_bytes = 8;
-    // the lookahead node set (hjb_rollout_set_lookahead): L.n_nodes > 0 while one is set; read by hjb_rollout_run_lookahead alone
+    // the lookahead node set (hjb_rollout_set_lookahead): L.n_nodes > 0 while one is set; read by hjb_rollout_run_lookahead and
+    // _run_lookahead_campaign
     hjb::LookSet L{};
     std::shared_ptr<DevData> look;      // L.tab: the weights, then the masked axes' offsets
     hipStream_t stream = nullptr;
@@ -81,6 +86,60 @@ int check_run(Rollout *ro, int want, int method, int32_t n_steps, const int32_t 
 // object): null X0 / X_final, the sizes of W doubles per trajectory and stage (wname: how the message spells W), a finite X0.
 int check_traj(Rollout *ro, const char *pre, int W, const char *wname, int32_t n_steps, int64_t n_traj, const double *X0,
                const double *X_final);
+
+// What hjb_rollout_run_lookahead and hjb_rollout_run_lookahead_campaign refuse of the object and the value planes, in `who`'s name
+// (n_traj: the trajectories or the starts): negative sizes, no or another model, no lookahead set, fly_noise without a noise set,
+// value_plane_of_step against the planes of hjb_rollout_set_values (-1 needs none).  Under ro->mu.
+int check_lookahead_run(Rollout *ro, const char *who, int fly_noise, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj);
+
+// What hjb_rollout_set_noise, hjb_rollout_noise_table and hjb_rollout_lookahead_campaign_host refuse of a weight vector (null: equal
+// weights), in `who`'s name: a weight that is not finite or is negative, weights that sum to 0.
+int check_weights(Rollout *ro, const char *who, int32_t n_nodes, const double *weights);
+
+// The problem hjb_rollout_lookahead_host and hjb_rollout_lookahead_campaign_host fly, from their common arguments: the refusals in
+// `who`'s name (look_host_args: everything up to the lookahead set; look_host_model: the grid, the tables, the model and the planes
+// of the steps) and the records the twin's loop reads.  L.tab points into tab.
+struct LookHostProblem {
+    hjb::GreedyModel M{};
+    hjb::LookSet L{};
+    std::vector<double> rdx, tab;
+};
+int look_host_args(const char *who, int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
+                   const double *A, const double *B, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
+                   int64_t n_traj, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights);
+int look_host_model(const char *who, int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
+                    const double *A, const double *B, const double *c, const double *q, const double *r, int32_t n_value_planes,
+                    int32_t n_steps, const int32_t *value_plane_of_step, int32_t mode, int32_t n_nodes, const double *offsets,
+                    const double *weights, LookHostProblem &P);
+
+// What the campaigns (hjb_rollout_run_campaign, hjb_rollout_run_lookahead_campaign, their host forms) refuse of their sizes, in
+// `who`'s name: n_samples < 1, n_starts * n_samples overflowing; and of their bounds: a NaN threshold, a NaN or negative tol
+// (n_starts >= 0 and D are the caller's).  Defined in rollout_campaign_host.hip.
+int check_campaign_sizes(Rollout *ro, const char *who, int64_t n_starts, int64_t n_samples);
+int check_campaign_bounds(Rollout *ro, const char *who, int D, int64_t n_starts, const double *threshold, const double *tol);
+// ... and, with the sizes first, of their streams: first_stream < 0, first_stream + n_starts * n_samples overflowing
+int check_campaign_streams(Rollout *ro, const char *who, int64_t n_starts, int64_t n_samples, int64_t first_stream);
+
+// One launch of a campaign call, as run_campaign_launches hands it to the controller's launch function: the object's record with
+// the planes of the steps on the device, the noise set with the call's seed and first stream, the launch's blocks, the LDS
+// bytes of the channel's tables and the node block together (hjb_rollout_run_noisy's rule), X0 [D, n_starts] and stats
+// [8, n_starts] on the device.
+struct CampaignLaunch {
+    hjb::DRollout R;
+    hjb::DNoise N;
+    hjb::DCampaign C;
+    size_t lds;
+    bool lds_on;
+    hipStream_t st;
+    const double *X0;
+    double *stats;
+};
+
+// The device side of a campaign call whose arguments have been checked (n_starts >= 1; rollout_campaign_host.hip): what a call
+// holds on the device is [D + 1 + 8, n_starts] doubles and 8 doubles per block of a launch.
+int run_campaign_launches(Rollout *ro, const char *who, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts, int64_t n_samples,
+                          const double *X0, uint64_t seed, int64_t first_stream, const double *threshold, const double *tol, double *stats,
+                          double *device_ms, const std::function<hipError_t(const CampaignLaunch &)> &launch);
 
 // K17 and K21 renormalise the quaternion X0[3..6] of a 7-state column after the first step: all zeros would be 0/0
 int check_quaternions(Rollout *ro, const char *pre, int64_t n_traj, const double *X0);

@@ -256,6 +256,14 @@ SYMBOLS = {
                                                                      C.c_int64] + [C.POINTER(C.c_double)] * 7
                                    + [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32,
                                       C.POINTER(C.c_double)]),
+    # that loop, flown noisy, as a campaign: hjb_rollout_run_campaign's statistics on its streams, and the host twin
+    "hjb_rollout_run_lookahead_campaign": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
+                                                       C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 4),
+    "hjb_rollout_lookahead_campaign_host": (C.c_int32, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32]
+                                            + [C.POINTER(C.c_double)] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+                                            + [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+                                            + [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+                                            + [C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 3),
     "hjb_rollout_set_attitude_model": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_int32, C.POINTER(C.c_double),
                                                    C.POINTER(C.c_double)]),
     "hjb_rollout_run_attitude": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]

@@ -416,6 +416,25 @@ class Rollout:
                 paths["W_path"] = paths["W_path"][:, 0, :].astype(np.int32)
         return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
 
+    def run_lookahead_campaign(self, X0, value_plane_of_step, n_samples, seed=0, first_stream=0, cost_threshold=None, settle_tol=None):
+        """run_campaign for run_lookahead's controller (hjb_rollout_run_lookahead_campaign): every start of X0 [D, n_starts] flown
+        n_samples times by the lookahead on set_values' planes under set_lookahead's nodes, on the plant of set_noise, the costs
+        reduced per start on the GPU.  Sample m of start s is run_lookahead(noisy=True)'s trajectory on stream first_stream +
+        s * n_samples + m of `seed` - the stream run_campaign gives that sample, so the two campaigns of one seed, first_stream
+        and n_samples fly common random numbers and their per-start means can be differenced with the sampling noise largely
+        cancelled.  cost_threshold, settle_tol and the returned dict: run_campaign's."""
+        D = self.D
+        X = _starts(X0, D)
+        ns = X.shape[0]
+        ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
+        thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
+        stats = np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT))
+        ms = C.c_double(0.0)
+        self._check(self.lib.hjb_rollout_run_lookahead_campaign(self._ro, int(ps.size), _i32p(ps), ns, int(n_samples), _f64p(X),
+                                                                int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol),
+                                                                _f64p(stats), C.byref(ms)))
+        return {**_campaign_dict(stats, int(n_samples)), "device_ms": ms.value}
+
     def set_attitude_model(self, inertia, h, integrator="taylor", q=None, r=None):
         """The 6-D attitude loop instead of the affine one (hjb_rollout_set_attitude_model; the last model set wins):
         inertia = (J1, J2, J3), step h, integrator 'taylor' or 'RK4', stage-cost weights q [7] and r [3] (None: zeros).
@@ -710,6 +729,44 @@ def lookahead_host(knots, u_table, A, B, J, X0, value_plane_of_step, offsets, we
         paths["L_path"] = paths["L_path"][:, 0, :].astype(np.int32) + np.int32(index_base)
         paths["V_path"] = paths["V_path"][:, 0, :]
     return {"X_final": Xf.T, "cost": cost, **paths}
+
+
+def lookahead_campaign_host(knots, u_table, A, B, J, X0, value_plane_of_step, n_samples, offsets, flight_offsets, weights=None,
+                            mode="expect", flight_weights=None, c=None, q=None, r=None, seed=0, first_stream=0, cost_threshold=None,
+                            settle_tol=None):
+    """Rollout.run_lookahead_campaign on the CPU (hjb_rollout_lookahead_campaign_host; no device, no object): lookahead_host's
+    problem and lookahead set (offsets, weights, mode), the plant's node set as set_noise takes it (flight_offsets [D, W_f],
+    flight_weights or None), and run_lookahead_campaign's arguments.  One start's samples at a time: the nodes drawn as
+    noise_draw draws them, the flight as lookahead_host flies it, the statistics as campaign_reduce forms them.  Returns
+    campaign_reduce's dict."""
+    lib = load_library()
+    ks = [np.ascontiguousarray(k, dtype=np.float64).reshape(-1) for k in knots]
+    D = len(ks)
+    n = [len(k) for k in ks]
+    nS = int(np.prod(n, dtype=np.int64)) if ks else 1
+    ut = np.asarray(u_table, dtype=np.float64)
+    ut = ut.reshape(-1, 1) if ut.ndim == 1 else ut
+    n_labels, nu = ut.shape
+    ut = np.ascontiguousarray(ut.reshape(-1, order="F"))
+    kcat = np.ascontiguousarray(np.concatenate(ks) if ks else np.zeros(0))
+    v, dtype = (None, _abi.HJB_F64) if J is None else _value_planes(J, nS)
+    X = _starts(X0, D)
+    ns = X.shape[0]
+    ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
+    off, w, mode = check_disturbance(D, offsets, weights, mode)
+    offc = np.ascontiguousarray(off.reshape(-1, order="F"))
+    fo2 = np.array(flight_offsets, dtype=np.float64, ndmin=2).reshape(D, -1)
+    fo = np.ascontiguousarray(fo2.reshape(-1, order="F"))
+    fw = None if flight_weights is None else _f64_vec(flight_weights, fo2.shape[1])
+    thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
+    stats = np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT))
+    _check(lib, None, lib.hjb_rollout_lookahead_campaign_host(
+        D, (C.c_int32 * max(D, 1))(*n), _f64p(kcat), int(n_labels), int(nu), _f64p(ut), _f64p(_f64_colmajor(A, D, D)),
+        _f64p(_f64_colmajor(B, D, nu)), _f64p(_f64_vec(c, D)), _f64p(_f64_vec(q, D)), _f64p(_f64_vec(r, nu)), dtype,
+        0 if v is None else v.size // nS, None if v is None else v.ctypes.data, int(ps.size), _i32p(ps), _DIST_MODE[mode], off.shape[1],
+        _f64p(offc), _f64p(w), int(fo2.shape[1]), _f64p(fo), _f64p(fw), ns, int(n_samples), _f64p(X), int(seed) & (2 ** 64 - 1),
+        int(first_stream), _f64p(thr), _f64p(tol), _f64p(stats)))
+    return _campaign_dict(stats, int(n_samples))
 
 
 def attitude_linear_response(inertia, h, K, C_gain, X0, n_steps, qc=None, u_limit=None, integrator="RK4", cost_form="quat",

@@ -380,6 +380,66 @@ class Dynamic_Solver:
         self.lookahead_cost = out["cost"]
         return X, U
 
+    def get_lookahead_cost_statistics(self, X0s, n_samples, seed=0, mode="Nssu", ssu_num=1, lookahead="disturbed", cost_threshold=None,
+                                      settle_tol=None):
+        """get_lookahead_paths' noisy flights reduced per start on the GPU (hjbdp.Rollout.run_lookahead_campaign): every start of
+        X0s [S, n] flown n_samples times under self.disturbance's nodes by the one-step lookahead on J_star, sample j of start i
+        on stream i * n_samples + j of `seed` (get_lookahead_paths' numbering: the same costs), and nothing of length
+        n * n_samples exists on the host or on the device.  lookahead 'disturbed': the controller looks ahead under
+        self.disturbance (get_lookahead_paths' controller); 'nominal': under one zero node (get_greedy_paths' controller).  In
+        both self.disturbance is the plant.  The streams pair with get_noisy_cost_statistics / noisy_cost_map: with the same
+        seed and n_samples, sample j of start i draws the same node at every step under the stored labels and under either
+        lookahead (common random numbers), so the per-start means can be differenced with the sampling noise largely cancelled.
+        Returns run_campaign's dict, one entry per start (get_noisy_cost_statistics').  Planes and `mode` / `ssu_num` as in
+        get_lookahead_paths."""
+        from .core import Rollout
+        if self.J_star is None or self.u_star_idxs is None:
+            raise RuntimeError("run() first")
+        if self.disturbance is None:
+            raise RuntimeError("get_lookahead_cost_statistics needs self.disturbance = (offsets [2, W], weights or None, mode)")
+        offsets, weights = self.disturbance[0], self.disturbance[1]
+        dmode = self.disturbance[2] if len(self.disturbance) > 2 else "expect"
+        if lookahead not in ("disturbed", "nominal"):
+            raise ValueError("lookahead must be 'disturbed' or 'nominal'")
+        N, S = self.N, self.S
+        n_st = N - 1
+        if mode == "ssu":
+            if not 1 <= int(ssu_num) <= n_st:
+                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
+            planes = np.full(n_st, int(ssu_num), dtype=np.int32)
+        elif mode == "Nssu":
+            planes = np.arange(1, N, dtype=np.int32)
+        else:
+            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        if int(n_samples) < 1:
+            raise ValueError("n_samples must be at least 1")
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
+        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
+            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+            ro.set_values(self.J_star)
+            if lookahead == "disturbed":
+                ro.set_lookahead(offsets, weights, dmode)
+            else:
+                ro.set_lookahead(np.zeros((S, 1)), [1.0], "expect")
+            ro.set_noise(offsets, weights)
+            return ro.run_lookahead_campaign(np.asarray(X0s, dtype=np.float64).reshape(S, -1), planes, int(n_samples), seed=seed,
+                                             first_stream=0, cost_threshold=cost_threshold, settle_tol=settle_tol)
+
+    def lookahead_cost_map(self, n_samples, seed=0, mode="Nssu", ssu_num=1, lookahead="disturbed", cost_threshold=None, settle_tol=None):
+        """get_lookahead_cost_statistics at every grid node: each entry shaped like the grid, [dx, dx] (stats [dx, dx, 8]), node
+        (i, j) = (s_r[i], s_r[j]) flown from stream (i + dx * j) * n_samples on - noisy_cost_map's starts on noisy_cost_map's
+        streams.  The streams pair with noisy_cost_map: with the same seed and n_samples the two maps fly common random
+        numbers, so this map's mean minus noisy_cost_map's is what the stored labels lose to the value function they came from,
+        node by node, with the sampling noise largely cancelled.  Beside J_star's first plane it is "promised against paid"
+        for the controller the disturbed solve is exactly optimal for."""
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        dx = s_r.size
+        X0s = np.stack([np.tile(s_r, dx), np.repeat(s_r, dx)])                  # axis 0 fastest, as the labels are stored
+        out = self.get_lookahead_cost_statistics(X0s, n_samples, seed=seed, mode=mode, ssu_num=ssu_num, lookahead=lookahead,
+                                                 cost_threshold=cost_threshold, settle_tol=settle_tol)
+        return {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) else v) for key, v in out.items()}
+
     @staticmethod
     def compare_data(obj1, obj2):
         # Dynamic_Solver.m:266-280

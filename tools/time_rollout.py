@@ -25,8 +25,10 @@ Two cases, one JSON line:
       alone, it also writes its line to profiles/rollout_lookahead_time.json.
   (l) campaign: the noisy campaign (K28, hjb_rollout_run_campaign) beside K25 on the same repeated starts, see case_campaign; alone,
       it also writes its line to profiles/rollout_campaign_time.json.
+  (m) lookahead_campaign: the lookahead campaign (K29, hjb_rollout_run_lookahead_campaign) beside K27 flown noisy on the same
+      repeated starts, see case_lookahead_campaign; alone, it also writes its line to profiles/rollout_lookahead_campaign_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy,lookahead,campaign] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy,lookahead,campaign,lookahead_campaign] [--out FILE]
 """
 from __future__ import annotations
 
@@ -697,6 +699,79 @@ def case_campaign(host=True, n_starts=1 << 14, n_samples=64):
     return res
 
 
+def case_lookahead_campaign(host=True, n_starts=1 << 14, n_samples=64):
+    """(m) lookahead_campaign: case_lookahead's problem (Kirk solved under the 9-node Gauss-Hermite set, 100 candidates x 9 nodes a
+    step), 2^14 starts x 64 samples x 129 steps: K29 (hjb_rollout_run_lookahead_campaign: 8 doubles per start come back) beside K27
+    flown noisy (hjb_rollout_run_lookahead with fly_noise = 1 on the same starts repeated 64 times: X_final and cost per trajectory
+    come back, reduced with numpy as get_lookahead_paths does) on one object in one process.  The two alternate, three rounds
+    after a warm-up round of the same shapes; per round the kernel time (device_ms: event times around the launches, K29's fold
+    kernel included) and the whole call's wall time of both, the medians and their ratios quoted.  `pass`: K29's kernel time
+    <= 1.05 x K27's in this run - the added work per lane is 6 shuffle levels of 5 doubles and 3 ballots against 129 x 100 x 9
+    blends, and 5 % is the margin case_campaign's identical bound carries.  It is measured against K27, never against a K29 number.
+    Beside the times, the label campaign (K28) on the same seed: the streams pair, so the per-start difference of the means is
+    taken with common random numbers, over the starts none of whose flights left the grid under either controller.  `host` is
+    not used."""
+    import hjbdp
+    ds = hjbdp.Dynamic_Solver(precision="double")
+    ds.N, ds.dx, ds.du = 130, 35, 100
+    off, w = hjbdp.gaussian_nodes([0.02, 0.05], order=3)
+    ds.disturbance = (off, w, "expect")
+    ds.run()
+    s_r = np.asarray(ds.s_r, dtype=np.float64)
+    rng = np.random.default_rng(1)
+    X = rng.uniform(s_r[0], s_r[-1], size=(2, n_starts))
+    K = ds.N - 1
+    vplanes = np.arange(1, K + 1)                                 # J_star's last plane is the zero terminal
+    ns, M = n_starts, n_samples
+    res = {"grid": "35x35", "planes": int(K), "values": str(ds.J_star.dtype), "n_steps": int(K), "n_candidates": int(ds.du),
+           "nodes": int(off.shape[1]), "mode": "expect", "n_starts": int(ns), "n_samples": int(M), "n_traj": int(ns * M),
+           "noise": "gaussian_nodes(sigma = (0.02, 0.05), order 3) on both axes: the solve's, the lookahead's and the plant's",
+           "timing": "device_ms: event times around the launches (K29: rollout and fold kernels); wall_ms: the whole Python call; "
+                     "the two runs alternate in one process, 3 rounds after a warm-up round"}
+    ms = {"k27": [], "k29": []}
+    wall = {"k27": [], "k29": []}
+    with hjbdp.Rollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro:
+        ro.set_model(ds.A, ds.B, q=np.diag(ds.Q), r=[ds.R])
+        ro.set_values(ds.J_star)
+        ro.set_lookahead(off, w, "expect")
+        ro.set_noise(off, w)
+        for rnd in range(4):
+            t0 = time.perf_counter()
+            b = ro.run_lookahead(np.repeat(X, M, axis=1), vplanes, noisy=True, seed=1)
+            cost = b["cost"].reshape(ns, M)
+            by_numpy = (cost.mean(axis=1), cost.std(axis=1), cost.max(axis=1))
+            t1 = time.perf_counter()
+            c = ro.run_lookahead_campaign(X, vplanes, M, seed=1)
+            t2 = time.perf_counter()
+            if rnd:                                               # round 0 is the warm-up
+                ms["k27"].append(b["device_ms"])
+                ms["k29"].append(c["device_ms"])
+                wall["k27"].append((t1 - t0) * 1e3)
+                wall["k29"].append((t2 - t1) * 1e3)
+        labels = ro.run_campaign(X, np.arange(K), M, seed=1, method="linear")
+    for key in ms:
+        med = float(np.median(ms[key]))
+        res[key] = {"device_ms": [round(t, 3) for t in ms[key]], "device_ms_median": round(med, 3),
+                    "wall_ms": [round(t, 1) for t in wall[key]], "wall_ms_median": round(float(np.median(wall[key])), 1),
+                    "traj_steps_per_s": ns * M * K / (med * 1e-3)}
+    res["k29_over_k27_kernel"] = res["k29"]["device_ms_median"] / res["k27"]["device_ms_median"]
+    res["k29_over_k27_wall"] = res["k29"]["wall_ms_median"] / res["k27"]["wall_ms_median"]
+    res["host_bytes_per_call"] = {"k27": int(ns * M * (2 * 2 + 1) * 8), "k29": int(ns * (2 + 8) * 8)}
+    ok = np.isfinite(cost).all(axis=1) & np.isfinite(labels["mean"])      # starts far from the origin leave the grid on Kirk's unstable loop
+    res["starts_with_every_cost_finite"] = int(ok.sum())
+    res["max_equals_numpy_max"] = bool(np.array_equal(c["max"][ok], by_numpy[2][ok]))
+    res["mean_max_rel_diff_to_numpy"] = float(np.max(np.abs(c["mean"][ok] - by_numpy[0][ok]) / np.abs(by_numpy[0][ok]))) if ok.any() else None
+    kept = ok & (c["n_left"] == 0) & (labels["n_left"] == 0)      # starts none of whose 2 x 64 flights left the grid
+    diff = c["mean"][kept] - labels["mean"][kept]                 # lookahead minus labels per start, common random numbers
+    res["paired_with_k28"] = {"starts_kept_inside_by_both": int(kept.sum()), "lookahead_mean": float(np.mean(c["mean"][kept])),
+                              "labels_mean": float(np.mean(labels["mean"][kept])), "mean_difference": float(np.mean(diff)),
+                              "std_of_difference_over_starts": float(np.std(diff)),
+                              "std_of_lookahead_mean_over_starts": float(np.std(c["mean"][kept]))}
+    res["bound"] = 1.05
+    res["pass"] = bool(res["k29_over_k27_kernel"] <= res["bound"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -711,7 +786,8 @@ def main():
         res[c] = {"kirk": case_kirk, "pos_att": case_pos_att, "attitude": case_attitude, "pos_att_loop": case_pos_att_loop,
                   "position_loop": case_position_loop, "attitude_simplified_loop": case_attitude_simplified_loop,
                   "attitude_linear_loop": case_attitude_linear_loop, "pos_att_faults": case_pos_att_faults,
-                  "kirk_noisy": case_kirk_noisy, "greedy": case_greedy, "lookahead": case_lookahead, "campaign": case_campaign}[c](host=not a.no_host)
+                  "kirk_noisy": case_kirk_noisy, "greedy": case_greedy, "lookahead": case_lookahead, "campaign": case_campaign,
+                  "lookahead_campaign": case_lookahead_campaign}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.cases == "position_loop" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
@@ -729,6 +805,8 @@ def main():
         (ROOT / "profiles" / "rollout_lookahead_time.json").write_text(json.dumps(res) + "\n")
     if a.cases == "campaign" and not a.out:                       # its own record: one line
         (ROOT / "profiles" / "rollout_campaign_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "lookahead_campaign" and not a.out:             # its own record: one line
+        (ROOT / "profiles" / "rollout_lookahead_campaign_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
