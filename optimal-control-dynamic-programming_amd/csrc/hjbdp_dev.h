@@ -84,4 +84,21 @@ __device__ __forceinline__ int32_t ld_label(const void *__restrict__ base, int64
     return (int32_t)((const uint16_t *)base)[i];
 }
 
+// A launch record read where it lies, in the kernel argument segment, instead of being held in scalar registers: r again, as a
+// record the compiler knows nothing about (an empty asm makes its address opaque).  The ONE reread of the rollout kernels (K26 -
+// K29) and of the step functions they share with their host twins (hjbdp_greedy.h, hjbdp_lookahead.h).  The reason is K26's: a
+// record of 100+ scalars (DRollout alone is some 170) kept live across the step, candidate and node loops does not fit the scalar
+// registers beside the loops' own and is spilled to lanes of vector registers - K25, which takes its records by value, spills up
+// to 458 of them.  Behind this the scalar loads of a loop body are issued in the body.  On the host it is r.
+template <typename T>
+__host__ __device__ __forceinline__ const T &record_reread(const T &r) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const T *p = &r;
+    asm volatile("" : "+s"(p));
+    return *p;
+#else
+    return r;
+#endif
+}
+
 }  // namespace hjb

@@ -20,6 +20,7 @@
 #include "../../include/hjbdp.h"
 
 #if defined(__HIPCC__)
+#include "hjbdp_dev.h"
 #define HJB_GREEDY_FN __host__ __device__ __forceinline__
 #else
 #define HJB_GREEDY_FN inline
@@ -97,24 +98,18 @@ HJB_GREEDY_FN int greedy_cell(const double *k, int n, double q, int uniform, dou
     return i;
 }
 
-// M again, as a record the compiler knows nothing about.  On the device the model is read through the kernel's argument segment
-// with scalar loads (kernels_rollout_greedy.h); kept live across the step and candidate loops, its 100+ scalars do not fit the
-// scalar registers beside the loops' own and would be spilled.  Behind this the reads of a loop body are issued in the body.
-template <typename MODEL>
-HJB_GREEDY_FN const MODEL &greedy_reread(const MODEL &M) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const MODEL *p = &M;
-    asm volatile("" : "+s"(p));
-    return *p;
-#else
-    return M;
+// The record M read again where it lies (record_reread, hjbdp_dev.h): on the device the model is read through the kernel's argument
+// segment with scalar loads (kernels_rollout_greedy.h), and the reads of a loop body are issued in the body.  As plain C++ (the
+// harnesses) there is no such segment and nothing to reread.
+#if !defined(__HIPCC__)
+template <typename T>
+inline const T &record_reread(const T &r) { return r; }
 #endif
-}
 
 // ... inside the candidate loop, where it is needed: from D = 3 on.  Below that the loop's scalars fit and stay in registers.
 template <int D, typename MODEL>
 HJB_GREEDY_FN const MODEL &greedy_reread_in_loop(const MODEL &M) {
-    if constexpr (D >= 3) return greedy_reread(M);
+    if constexpr (D >= 3) return record_reread(M);
     else return M;
 }
 
@@ -205,7 +200,7 @@ template <int D, int NU, typename TV, typename MODEL>
 HJB_GREEDY_FN void greedy_step_nu(const MODEL &M0, const double *kn, const double *rd, const double *ut, const TV *plane,
                                   double (&x)[D], double (&u)[HJB_ROLLOUT_MAX_U], double &g, int &label, double &best) {
     double gs, as[D];
-    greedy_state_parts<D>(greedy_reread(M0), x, gs, as);
+    greedy_state_parts<D>(record_reread(M0), x, gs, as);
     double bst = 0.0;
     int lb = 0;
     const int nl = M0.n_labels;
@@ -220,7 +215,7 @@ HJB_GREEDY_FN void greedy_step_nu(const MODEL &M0, const double *kn, const doubl
         }
     }
     double xn[D];
-    g = greedy_control<D, NU>(greedy_reread(M0), ut, lb, gs, as, u, xn);
+    g = greedy_control<D, NU>(record_reread(M0), ut, lb, gs, as, u, xn);
 #pragma unroll
     for (int a = 0; a < D; ++a) x[a] = xn[a];
     label = lb;

@@ -68,7 +68,7 @@ inline int look_table(int D, int n_nodes, const double *offsets, const double *w
 // M again once per node of the node loop, where that is the form: below D = 3 (look_value)
 template <int D, typename MODEL>
 HJB_GREEDY_FN const MODEL &greedy_reread_per_node(const MODEL &M) {
-    if constexpr (D < 3) return greedy_reread(M);
+    if constexpr (D < 3) return record_reread(M);
     else return M;
 }
 
@@ -160,14 +160,14 @@ template <int D, int NU, typename TV, typename MODEL, typename LOOK>
 HJB_GREEDY_FN void look_step_nu(const MODEL &M0, const LOOK &L0, const double *kn, const double *rd, const double *ut, const TV *plane,
                                 double (&x)[D], double (&u)[HJB_ROLLOUT_MAX_U], double &g, int &label, double &best) {
     double gs, as[D];
-    greedy_state_parts<D>(greedy_reread(M0), x, gs, as);
+    greedy_state_parts<D>(record_reread(M0), x, gs, as);
     double bst = 0.0;
     int lb = 0;
     const int nl = M0.n_labels;
     for (int l = 0; l < nl; ++l) {
         double ul[HJB_ROLLOUT_MAX_U], xn[D];
         const double gl = greedy_control<D, NU>(greedy_reread_in_loop<D>(M0), ut, l, gs, as, ul, xn);
-        const double acc = plane ? look_value<D, TV>(greedy_reread(M0), greedy_reread(L0), kn, rd, plane, xn) : 0.0;
+        const double acc = plane ? look_value<D, TV>(record_reread(M0), record_reread(L0), kn, rd, plane, xn) : 0.0;
         const double cand = gl + acc;
         if (l == 0 || cand < bst) {
             bst = cand;
@@ -175,7 +175,7 @@ HJB_GREEDY_FN void look_step_nu(const MODEL &M0, const LOOK &L0, const double *k
         }
     }
     double xn[D];
-    g = greedy_control<D, NU>(greedy_reread(M0), ut, lb, gs, as, u, xn);
+    g = greedy_control<D, NU>(record_reread(M0), ut, lb, gs, as, u, xn);
 #pragma unroll
     for (int a = 0; a < D; ++a) x[a] = xn[a];
     label = lb;

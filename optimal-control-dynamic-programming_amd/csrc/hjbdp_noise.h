@@ -71,6 +71,15 @@ HJB_NOISE_FN int noise_node(const double *T, int n_thr, uint32_t word) {
     return lo;
 }
 
+// The node of step k of a stream, the ONE loop body of the host twins (hjb_rollout_noise_draw, hjb_rollout_lookahead_campaign_host):
+// called for k = 0, 1, 2, ... in order with one r per stream, it makes a Philox call when (k & 3) == 0 and takes one word per
+// step.  The kernels' step (HJB_ROLLOUT_NOISE_STEP, kernels_rollout_noisy.h) is these two statements expanded in place, with its
+// arguments read inside the branch: as a call of this function, every noisy kernel's code object changed.
+HJB_NOISE_FN int noise_step_node(uint64_t seed, uint64_t s, int k, uint32_t (&r)[4], const double *T, int n_thr) {
+    if ((k & 3) == 0) noise_block(seed, s, (uint32_t)k >> 2, r);
+    return noise_node(T, n_thr, noise_next_word(r));
+}
+
 // The thresholds of n_nodes weights (null: 1.0 each) into T[0 .. n_nodes - 2].  Returns the weights' sum S_{W-1}; the caller has
 // checked that every weight is finite and non-negative and refuses a sum of 0.
 inline double noise_table(int n_nodes, const double *weights, double *T) {

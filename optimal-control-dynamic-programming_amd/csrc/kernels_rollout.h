@@ -93,6 +93,31 @@ __device__ __forceinline__ constexpr int trailing_ones(int c) { return (c & 1) ?
         }                                                                                                                       \
     }
 
+// One step's stage cost and affine update, the ONE statement K16, K25 (kernels_rollout_noisy.h) and K28
+// (kernels_rollout_campaign.h) expand: declares g_ = ((q0*(x0*x0) + q1*(x1*x1)) + ...) + r0*(u0*u0) + ... and xn_[D_], xn_a =
+// ((A[a,0]*x0 + A[a,1]*x1) + ...) + B[a,0]*u0 + ... (+ c_a), every product rounded, in this order: what the bit-exact contracts of
+// the three kernels and of hjbdp_greedy.h's two halves (greedy_state_parts, greedy_control) rest on.  Rg_ and Ra_ are EXPRESSIONS
+// for the record (a DRollout): Rg_ is evaluated once, for the cost; Ra_ once per row of A and B, inside the row loop - K28 passes
+// a reread of its launch record for each (campaign_reread_in_step), K16 and K25 their argument.  A macro for HJB_ROLLOUT_LOOKUP's
+// reason; its records are aff_g_ and aff_r_, its loop variables (a, b, j) and acc live inside its own blocks.
+#define HJB_ROLLOUT_AFFINE_STEP(D_, NU_, Rg_, Ra_, x_, u_, nu_, g_, xn_)                                                        \
+    double g_;                                                                                                                  \
+    {                                                                                                                           \
+        const auto &aff_g_ = Rg_;                                                                                               \
+        g_ = aff_g_.q[0] * (x_[0] * x_[0]);                                                                                     \
+        _Pragma("unroll") for (int a = 1; a < D_; ++a) g_ = g_ + aff_g_.q[a] * (x_[a] * x_[a]);                                 \
+        _Pragma("unroll") for (int j = 0; j < NU_; ++j) if (j < nu_) g_ = g_ + aff_g_.r[j] * (u_[j] * u_[j]);                   \
+    }                                                                                                                           \
+    double xn_[D_];                                                                                                             \
+    _Pragma("unroll") for (int a = 0; a < D_; ++a) {                                                                            \
+        const auto &aff_r_ = Ra_;                                                                                               \
+        double acc = aff_r_.A[a] * x_[0];                                                                                       \
+        _Pragma("unroll") for (int b = 1; b < D_; ++b) acc = acc + aff_r_.A[a + D_ * b] * x_[b];                                \
+        _Pragma("unroll") for (int j = 0; j < NU_; ++j) if (j < nu_) acc = acc + aff_r_.B[a + D_ * j] * u_[j];                  \
+        if (aff_r_.has_c) acc = acc + aff_r_.c[a];                                                                              \
+        xn_[a] = acc;                                                                                                           \
+    }
+
 // One channel's tables for the lookup, the ONE staging every rollout kernel uses, in two steps (t_: a name for the channel; c_: a
 // DRollout or a DPaChan; width_: u_table doubles per label).
 //   HJB_ROLLOUT_PLACE: the channel's place in LDS, [knots | 1/dx | u_table] from at_ on; HJB_ROLLOUT_PLACE_END(t_) is where the
@@ -180,25 +205,8 @@ k_rollout(const DRollout R, int64_t nc, const double *__restrict__ X0, double *_
     double J = 0.0;
     for (int k = 0; k < R.n_steps; ++k) {
         HJB_ROLLOUT_LOOKUP(D, HJB_ROLLOUT_MAX_U, METHOD, R, kn, rd, ut, lab, k, x, nu, nl, u)
-        double g = R.q[0] * (x[0] * x[0]);
-#pragma unroll
-        for (int a = 1; a < D; ++a) g = g + R.q[a] * (x[a] * x[a]);
-#pragma unroll
-        for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j)
-            if (j < nu) g = g + R.r[j] * (u[j] * u[j]);
+        HJB_ROLLOUT_AFFINE_STEP(D, HJB_ROLLOUT_MAX_U, R, R, x, u, nu, g, xn)
         J = J + g;
-        double xn[D];
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-            double acc = R.A[a] * x[0];
-#pragma unroll
-            for (int b = 1; b < D; ++b) acc = acc + R.A[a + D * b] * x[b];
-#pragma unroll
-            for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j)
-                if (j < nu) acc = acc + R.B[a + D * j] * u[j];
-            if (R.has_c) acc = acc + R.c[a];
-            xn[a] = acc;
-        }
         if (Up) {
 #pragma unroll
             for (int j = 0; j < HJB_ROLLOUT_MAX_U; ++j)

@@ -33,7 +33,7 @@ struct DGreedy {
     double *Lp, *Vp;                  // [nc, n_steps] chosen label + index_base / the minimum, trajectory fastest, or null
 };
 
-// The kernel reads its argument where it lies, in the argument segment, through greedy_reread (hjbdp_greedy.h): the model per
+// The kernel reads its argument where it lies, in the argument segment, through record_reread (hjbdp_dev.h): the model per
 // step and, from D = 3 on, per loop body of the candidate loop; the output pointers where a step stores.  Held in scalar
 // registers across the candidate loop, as a by-value argument is, the record and the loop's own scalars exceed the register file
 // from D = 2 on and the compiler spills them (to lanes of a vector register; at D = 5 and 6 it also reserved a private segment).
@@ -52,7 +52,7 @@ k_rollout_greedy(const DGreedy G) {
     if (i >= G0.nc) return;
     double x[D];
     {
-        const KGreedy &Gk = greedy_reread(G0);
+        const KGreedy &Gk = record_reread(G0);
         const int64_t nc = Gk.nc;
 #pragma unroll
         for (int a = 0; a < D; ++a) x[a] = Gk.X0[a + (int64_t)D * i];
@@ -62,17 +62,17 @@ k_rollout_greedy(const DGreedy G) {
         }
     }
     double J = 0.0;
-    for (int k = 0; k < greedy_reread(G0).R.n_steps; ++k) {
+    for (int k = 0; k < record_reread(G0).R.n_steps; ++k) {
         double u[HJB_ROLLOUT_MAX_U], g, best;
         int label;
         {
-            const KGreedy &Gk = greedy_reread(G0);
+            const KGreedy &Gk = record_reread(G0);
             const int32_t p = Gk.R.plane_of_step[k];
             const TV *plane = p < 0 ? nullptr : static_cast<const TV *>(Gk.values) + (int64_t)p * Gk.R.nS;
             greedy_step<D, TV>(G0.R, kn, rd, ut, plane, x, u, g, label, best);
         }
         J = J + g;
-        const KGreedy &Gk = greedy_reread(G0);
+        const KGreedy &Gk = record_reread(G0);
         const int nu = Gk.R.n_u;
         const int64_t nc = Gk.nc;
         if (Gk.Up) {
@@ -87,7 +87,7 @@ k_rollout_greedy(const DGreedy G) {
             for (int a = 0; a < D; ++a) Gk.Xp[i + nc * (a + (int64_t)D * (k + 1))] = x[a];
         }
     }
-    const KGreedy &Gk = greedy_reread(G0);
+    const KGreedy &Gk = record_reread(G0);
 #pragma unroll
     for (int a = 0; a < D; ++a) Gk.Xf[a + (int64_t)D * i] = x[a];
     if (Gk.cost) Gk.cost[i] = J;

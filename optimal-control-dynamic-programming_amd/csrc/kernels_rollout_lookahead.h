@@ -9,15 +9,15 @@
 //   2. per candidate: the cell and weight of every axis OUTSIDE the lookahead mask once; per node w, in order, those of the masked
 //      axes at xn_a + e[a][w], the N-linear blend (K26's tree in K26's corner groups) and the combine (p_0 v_0 then fma / first max);
 //   3. the first minimum of g_l + acc, the chosen label applied: cost += g, x = xn;
-//   4. FLY only: K25's steps 2-3 on the object's flight set - a Philox block when (k & 3) == 0, w' = noise_node, x_a += d[a][w'] on
-//      the flight mask alone;
+//   4. FLY only: K25's steps 2-3 on the object's flight set (HJB_ROLLOUT_NOISE_STEP) - a Philox block when (k & 3) == 0, w' =
+//      noise_node, x_a += d[a][w'] on the flight mask alone;
 //   5. paths as K26, and the drawn node per step when N.Wp is given.
 // The two node blocks:
 //   lookahead  [p (W) | e (n_axes x W)] (L.tab), indexed by the node counter only: read through the constant address space into
 //              scalar registers (look_read), never per lane, never staged in LDS;
 //   flight     K25's [T (W_f - 1) | d (W_f x n_axes_f)] (N.tab), read per lane at the lane's own node; in the LDS form it is staged
 //              behind the channel's [knots | 1/dx | u_table], and the host takes the LDS form when the sum fits 32 KiB.
-// The argument record is read where it lies, in the argument segment, through greedy_reread (K26's reason: held in scalar
+// The argument record is read where it lies, in the argument segment, through record_reread (K26's reason: held in scalar
 // registers across three nested loops it would be spilled): per step, per candidate and, inside the node loop, once per node at
 // D = 1 and 2 (held across the candidate loop, or across one candidate's nodes, D = 2 spills 5 - 72 scalars) and per loop body
 // from D = 3 on, as K26.
@@ -46,13 +46,7 @@ k_rollout_lookahead(const DLook A) {
     HJB_ROLLOUT_PLACE(p, A.G.R, A.G.R.n_u, smem)
     HJB_ROLLOUT_STAGE(LDS, p, A.G.R, kn, rd, ut)
     if constexpr (FLY) {
-        if constexpr (LDS) {
-            double *lds_n = HJB_ROLLOUT_PLACE_END(p);
-            for (int e = threadIdx.x; e < A.N.n_tab; e += blockDim.x) lds_n[e] = A.N.tab[e];
-            nt = lds_n;
-        } else {
-            nt = A.N.tab;
-        }
+        HJB_ROLLOUT_STAGE_NOISE(LDS, p, A.N, nt)
     }
     if constexpr (LDS) __syncthreads();
     typedef __attribute__((address_space(4))) DLook KLook;
@@ -61,7 +55,7 @@ k_rollout_lookahead(const DLook A) {
     if (i >= A0.G.nc) return;
     double x[D];
     {
-        const KLook &Ak = greedy_reread(A0);
+        const KLook &Ak = record_reread(A0);
         const int64_t nc = Ak.G.nc;
 #pragma unroll
         for (int a = 0; a < D; ++a) x[a] = Ak.G.X0[a + (int64_t)D * i];
@@ -72,11 +66,11 @@ k_rollout_lookahead(const DLook A) {
     }
     uint32_t rw[4] = {0u, 0u, 0u, 0u};
     double J = 0.0;
-    for (int k = 0; k < greedy_reread(A0).G.R.n_steps; ++k) {
+    for (int k = 0; k < record_reread(A0).G.R.n_steps; ++k) {
         double u[HJB_ROLLOUT_MAX_U], g, best;
         int label;
         {
-            const KLook &Ak = greedy_reread(A0);
+            const KLook &Ak = record_reread(A0);
             const int32_t p = Ak.G.R.plane_of_step[k];
             const TV *plane = p < 0 ? nullptr : static_cast<const TV *>(Ak.G.values) + (int64_t)p * Ak.G.R.nS;
             look_step<D, TV>(A0.G.R, A0.L, kn, rd, ut, plane, x, u, g, label, best);
@@ -84,19 +78,11 @@ k_rollout_lookahead(const DLook A) {
         J = J + g;
         int w = 0;
         if constexpr (FLY) {
-            const KLook &Ak = greedy_reread(A0);
-            if ((k & 3) == 0) noise_block(Ak.N.seed, Ak.N.first + (uint64_t)i, (uint32_t)k >> 2, rw);
-            const int n_thr = Ak.N.n_nodes - 1;
-            w = noise_node(nt, n_thr, noise_next_word(rw));
-            const double *row = nt + n_thr + w;                   // the next masked axis' offsets, at this lane's node
-#pragma unroll
-            for (int a = 0; a < D; ++a)
-                if (Ak.N.mask & (1 << a)) {
-                    x[a] = x[a] + row[0];
-                    row += Ak.N.n_nodes;
-                }
+            const KLook &Ak = record_reread(A0);
+            HJB_ROLLOUT_NOISE_STEP(D, Ak.N.seed, Ak.N.first + (uint64_t)i, k, rw, nt, nt + (Ak.N.n_nodes - 1), Ak.N.n_nodes,
+                                   Ak.N.mask, x, w)
         }
-        const KLook &Ak = greedy_reread(A0);
+        const KLook &Ak = record_reread(A0);
         const int nu = Ak.G.R.n_u;
         const int64_t nc = Ak.G.nc;
         if (Ak.G.Up) {
@@ -114,7 +100,7 @@ k_rollout_lookahead(const DLook A) {
             for (int a = 0; a < D; ++a) Ak.G.Xp[i + nc * (a + (int64_t)D * (k + 1))] = x[a];
         }
     }
-    const KLook &Ak = greedy_reread(A0);
+    const KLook &Ak = record_reread(A0);
 #pragma unroll
     for (int a = 0; a < D; ++a) Ak.G.Xf[a + (int64_t)D * i] = x[a];
     if (Ak.G.cost) Ak.G.cost[i] = J;

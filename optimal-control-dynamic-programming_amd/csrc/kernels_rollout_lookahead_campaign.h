@@ -9,14 +9,14 @@
 // X0[:, s] on the stream N.first + s * M + m - the stream K28 gives the same (s, m), so a label campaign and a lookahead campaign
 // of one seed fly common random numbers.  Every part of the step is called, none restated:
 //   look_step<D, TV> (hjbdp_lookahead.h) on the plane of plane_of_step[k] (-1: the zero function);
-//   K25's sampler (hjbdp_noise.h): a Philox block when (k & 3) == 0, noise_node, the flight set's offsets on the flight mask alone;
+//   K25's drawn-node step (HJB_ROLLOUT_NOISE_STEP, kernels_rollout_noisy.h) on the flight set and the flight mask alone;
 //   the left-the-grid flag (campaign_outside) on every visited state k = 0 .. n_steps, as flown, after the noise.
-// There are no path stores.  After the flight: campaign_slot, the log2 G shuffle levels with campaign_op (own value first), three
-// ballots under the segment mask, slot 0 writes the block's 8 doubles to C.partials; k_campaign_fold (rollout_campaign.hip, K28's,
+// There are no path stores.  After the flight: campaign_slot and K28's block partial (HJB_CAMPAIGN_BLOCK_PARTIAL: the log2 G shuffle
+// levels, three ballots under the segment mask, slot 0's 8 doubles to C.partials); k_campaign_fold (rollout_campaign.hip, K28's,
 // launched through launch_campaign_fold) folds them into stats[:, s].
 // Table placement is K27's: the lookahead block [p | e] through scalar loads (look_read), the flight block per lane and staged in
 // LDS behind knots, 1/dx and u_table under the 32 KiB rule, the launch record where it lies in the argument segment
-// (greedy_reread / campaign_reread): per step for the plane, and again after look_step for the sampler and the extent, so that
+// (record_reread): per step for the plane, and again after look_step for the sampler and the extent, so that
 // nothing of the record is live across the candidate loop.
 #pragma once
 #include "kernels_rollout_campaign.h"
@@ -34,19 +34,6 @@ struct DLookCampaignArgs {
     const double *X0;                 // [D, n_starts] (global)
 };
 
-// K28's lane layout: lane t of the launch is slot t % G of block C.block0 + t / G -> its block in the launch, its slot, its start and
-// its sample; true for a lane that flies (a block of the launch, a sample below M)
-template <typename CAMP>
-__device__ __forceinline__ bool campaign_lane(const CAMP &C, int64_t t, int64_t &lb, int &slot, int &G, int64_t &s, int64_t &m) {
-    G = C.G;
-    lb = t >> C.log2G;
-    slot = (int)(t & (G - 1));
-    const int64_t gb = C.block0 + lb;
-    s = gb / C.B;
-    m = (gb - s * C.B) * G + slot;
-    return lb < C.n_blocks && m < C.M;
-}
-
 template <int D, typename TV, bool LDS>
 __global__ void __launch_bounds__(256)
 k_rollout_lookahead_campaign(const DLookCampaignArgs K) {
@@ -54,20 +41,14 @@ k_rollout_lookahead_campaign(const DLookCampaignArgs K) {
     const double *kn, *rd, *ut, *nt;
     HJB_ROLLOUT_PLACE(p, K.R, K.R.n_u, smem)
     HJB_ROLLOUT_STAGE(LDS, p, K.R, kn, rd, ut)
-    if constexpr (LDS) {
-        double *lds_n = HJB_ROLLOUT_PLACE_END(p);
-        for (int e = threadIdx.x; e < K.N.n_tab; e += blockDim.x) lds_n[e] = K.N.tab[e];
-        nt = lds_n;
-        __syncthreads();
-    } else {
-        nt = K.N.tab;
-    }
+    HJB_ROLLOUT_STAGE_NOISE(LDS, p, K.N, nt)
+    if constexpr (LDS) __syncthreads();
     typedef __attribute__((address_space(4))) DLookCampaignArgs KArgs;
     const KArgs &K0 = *(const KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
     const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     int64_t lb, s, m;
     int slot, G;
-    const bool live = campaign_lane(campaign_reread(K0).C, t, lb, slot, G, s, m);
+    const bool live = campaign_lane(record_reread(K0).C, t, lb, slot, G, s, m);
     CampVals v = campaign_padding();
     bool f_exceed = false, f_settled = false;
     uint32_t n_out = 0u;                                      // 1 once a visited state lay outside the grid, as a word per lane: a vector register,
@@ -76,7 +57,7 @@ k_rollout_lookahead_campaign(const DLookCampaignArgs K) {
         double x[D];
         uint64_t stream;
         {
-            const KArgs &Kk = campaign_reread(K0);
+            const KArgs &Kk = record_reread(K0);
             stream = Kk.N.first + (uint64_t)(s * Kk.C.M + m);
 #pragma unroll
             for (int a = 0; a < D; ++a) x[a] = Kk.X0[a + (int64_t)D * s];
@@ -85,35 +66,28 @@ k_rollout_lookahead_campaign(const DLookCampaignArgs K) {
         }
         uint32_t rw[4] = {0u, 0u, 0u, 0u};
         double J = 0.0;
-        for (int k = 0; k < campaign_reread(K0).R.n_steps; ++k) {
+        for (int k = 0; k < record_reread(K0).R.n_steps; ++k) {
             double u[HJB_ROLLOUT_MAX_U], g, best;
             int label;
             {
-                const KArgs &Kk = campaign_reread(K0);
+                const KArgs &Kk = record_reread(K0);
                 const int32_t p = Kk.R.plane_of_step[k];
                 const TV *plane = p < 0 ? nullptr : static_cast<const TV *>(Kk.values) + (int64_t)p * Kk.R.nS;
                 look_step<D, TV>(K0.R, K0.L, kn, rd, ut, plane, x, u, g, label, best);
             }
             J = J + g;
             {
-                const KArgs &Kn = campaign_reread(K0);            // the flight set
-                if ((k & 3) == 0) noise_block(Kn.N.seed, stream, (uint32_t)k >> 2, rw);
-                const int n_thr = Kn.N.n_nodes - 1;
-                const double *ntk = LDS ? nt : Kn.N.tab;          // the global form holds no pointer to the block across look_step
-                const int w = noise_node(ntk, n_thr, noise_next_word(rw));
-                const double *row = ntk + n_thr + w;              // the next masked axis' offsets, at this lane's node
-#pragma unroll
-                for (int a = 0; a < D; ++a)
-                    if (Kn.N.mask & (1 << a)) {
-                        x[a] = x[a] + row[0];
-                        row += Kn.N.n_nodes;
-                    }
+                const KArgs &Kn = record_reread(K0);              // the flight set
+                int w;
+                // the global form takes the block from the record here: it holds no pointer to it across look_step
+                HJB_ROLLOUT_NOISE_STEP(D, Kn.N.seed, stream, k, rw, (LDS ? nt : Kn.N.tab), (LDS ? nt : Kn.N.tab) + (Kn.N.n_nodes - 1),
+                                       Kn.N.n_nodes, Kn.N.mask, x, w)
             }
-            const KArgs &Kc = campaign_reread(K0);                // the grid's extent
+            const KArgs &Kc = record_reread(K0);              // the grid's extent
 #pragma unroll
             for (int a = 0; a < D; ++a) n_out |= campaign_outside(x[a], Kc.C.lo[a], Kc.C.hi[a]) ? 1u : 0u;
         }
-        const KArgs &Kk = campaign_reread(K0);
+        const KArgs &Kk = record_reread(K0);
         (void)campaign_lane(Kk.C, t, lb, slot, G, s, m);          // the start again: not held across the flight
         double tol[D];
 #pragma unroll
@@ -123,32 +97,9 @@ k_rollout_lookahead_campaign(const DLookCampaignArgs K) {
         v = campaign_slot(J, f_settled);
     }
     // every lane of the wave from here on, its place taken from the record again: nothing of it is held across the flight
-    const KArgs &Kk = campaign_reread(K0);
+    const KArgs &Kk = record_reread(K0);
     (void)campaign_lane(Kk.C, t, lb, slot, G, s, m);
-    // the block tree: level L pairs element i with element i + 2^L
-    for (int half = 1; half < G; half *= 2) {
-        CampVals o;
-        o.sum = __shfl_down(v.sum, half);
-        o.sumsq = __shfl_down(v.sumsq, half);
-        o.mn = __shfl_down(v.mn, half);
-        o.mx = __shfl_down(v.mx, half);
-        o.sum_settled = __shfl_down(v.sum_settled, half);
-        v = campaign_op(v, o);
-    }
-    const unsigned long long b_exceed = __ballot(f_exceed), b_left = __ballot(n_out != 0u), b_settled = __ballot(f_settled);
-    if (slot == 0 && lb < Kk.C.n_blocks) {
-        const int lane = threadIdx.x & 63;                    // the segment's first lane: G divides 64 and the block size
-        const unsigned long long seg = (G == 64 ? ~0ull : (1ull << G) - 1ull) << lane;
-        double *out = Kk.C.partials + 8 * lb;
-        out[0] = v.sum;
-        out[1] = v.sumsq;
-        out[2] = v.mn;
-        out[3] = v.mx;
-        out[4] = (double)__popcll(b_exceed & seg);
-        out[5] = (double)__popcll(b_left & seg);
-        out[6] = (double)__popcll(b_settled & seg);
-        out[7] = v.sum_settled;
-    }
+    HJB_CAMPAIGN_BLOCK_PARTIAL(v, f_exceed, n_out != 0u, f_settled, G, slot, lb, Kk.C)
 }
 
 // rollout_lookahead_campaign.hip instantiates the 24 kernels (D x value type x LDS) and launches the one asked for, then K28's

@@ -618,13 +618,12 @@ int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_tr
     for (int w = 0; w + 1 < n_nodes; ++w)
         if (!(thresholds[w] >= 0 && thresholds[w] <= 4294967296.0) || (w > 0 && thresholds[w] < thresholds[w - 1]))
             return rfail(nullptr, HJB_E_INVALID, "%s: thresholds[%d] = %g is outside [0, 2^32] or below its predecessor", who, w, thresholds[w]);
-    // the kernel's own loop: a Philox call when (k & 3) == 0, one word per step
+    // the kernel's own loop (noise_step_node)
     for (int64_t i = 0; i < n_traj; ++i) {
         const uint64_t s = (uint64_t)first_stream + (uint64_t)i;
         uint32_t rw[4] = {0u, 0u, 0u, 0u};
         for (int k = 0; k < n_steps; ++k) {
-            if ((k & 3) == 0) noise_block(seed, s, (uint32_t)k >> 2, rw);
-            nodes[i + n_traj * k] = noise_node(thresholds, n_nodes - 1, noise_next_word(rw));
+            nodes[i + n_traj * k] = noise_step_node(seed, s, k, rw, thresholds, n_nodes - 1);
         }
     }
     return HJB_OK;

@@ -88,10 +88,8 @@ int32_t hjb_rollout_lookahead_campaign_host(int32_t D, const int32_t *n, const d
                 for (int64_t m = 0; m < n_samples; ++m) {
                     const uint64_t stream = (uint64_t)first_stream + (uint64_t)(s * n_samples + m);
                     uint32_t rw[4] = {0u, 0u, 0u, 0u};
-                    for (int k = 0; k < n_steps; ++k) {       // the kernel's own loop: a Philox call when (k & 3) == 0, one word per step
-                        if ((k & 3) == 0) noise_block(seed, stream, (uint32_t)k >> 2, rw);
-                        nodes[k] = noise_node(thr.data(), n_flight_nodes - 1, noise_next_word(rw));
-                    }
+                    for (int k = 0; k < n_steps; ++k)         // the kernel's own loop
+                        nodes[k] = noise_step_node(seed, stream, k, rw, thr.data(), n_flight_nodes - 1);
                     lookahead_rollout_host<DD, TV>(P.M, P.L, knots, P.rdx.data(), u_table, static_cast<const TV *>(values), n_steps,
                                                    value_plane_of_step, 1, X0 + (int64_t)DD * s, nodes.data(), fmask, flight_offsets,
                                                    xf.data() + (int64_t)DD * m, cost.data() + m, path.data(), nullptr, nullptr, nullptr);
