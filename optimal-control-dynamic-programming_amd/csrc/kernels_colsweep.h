@@ -50,7 +50,7 @@
 #pragma once
 #include <cstddef>
 #include "hjbdp_dev.h"
-#include "kernels_generic.h"
+#include "hjbdp_canon.h"
 #include "kernels_tabled.h"
 #include "kernels_rowwise.h"
 

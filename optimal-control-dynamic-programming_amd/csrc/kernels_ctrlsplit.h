@@ -13,7 +13,7 @@
 // canonical order of the generic kernel: results are bit-identical.
 #pragma once
 #include "hjbdp_dev.h"
-#include "kernels_generic.h"
+#include "hjbdp_canon.h"
 
 namespace hjb {
 
@@ -39,33 +39,18 @@ k_backup_ctrlsplit(const DParams *__restrict__ P, const T *__restrict__ Jn, T *_
     for (int64_t ls = (int64_t)blockIdx.x * waves_per_block + wave; ls < n_owned;
          ls += (int64_t)gridDim.x * waves_per_block) {
         int si[D];
-        {
-            int64_t r = ls;
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-                int na = P->n[a];
-                si[a] = (int)(r % na);
-                r /= na;
-            }
-            si[D - 1] += P->slab_begin;
-        }
+        HJB_STATE_INDEX(D, P, ls, si, a, )
         int cz[HJB_MAX_C] = {0, 0, 0};
         T qpre[D];
 #pragma unroll
         for (int a = 0; a < D; ++a) {
             const DAxis &ax = P->axis[a];
             T q = (T)0;
-            for (int k = 0; k < ax.n_prefix; ++k) {
-                T x = term_value<T, D>(ax.t[k], si, cz);
-                q = (k == 0) ? x : (T)(q + x);
-            }
+            HJB_TERM_SUM(T, q, k, 0, ax.n_prefix, term_value<T, D>(ax.t[k], si, cz))
             qpre[a] = q;
         }
         T gpre = (T)0;
-        for (int k = 0; k < P->n_cost_prefix; ++k) {
-            T x = term_value<T, D>(P->cost[k], si, cz);
-            gpre = (k == 0) ? x : (T)(gpre + x);
-        }
+        HJB_TERM_SUM(T, gpre, k, 0, P->n_cost_prefix, term_value<T, D>(P->cost[k], si, cz))
         T best = (T)INFINITY;
         int best_u = 0x7fffffff;
         bool have = false, first_nan = false;
@@ -89,20 +74,9 @@ k_backup_ctrlsplit(const DParams *__restrict__ P, const T *__restrict__ Jn, T *_
             for (int a = 0; a < D; ++a) {
                 const DAxis &ax = P->axis[a];
                 T q = qpre[a];
-                for (int k = ax.n_prefix; k < ax.n_terms; ++k) {
-                    T x = term_value<T, D>(ax.t[k], si, cj);
-                    q = (k == 0) ? x : (T)(q + x);
-                }
-                const T *kk = static_cast<const T *>(ax.knots);
-                int cell = find_cell<T>(kk, ax.n, q, ax.uniform, (T)ax.x0, (T)ax.inv_h);
-                tw[a] = (T)((T)(q - kk[cell]) * static_cast<const T *>(ax.rdx)[cell]);
-                if (a == D - 1) {
-                    cell -= P->plane0;
-                    if (cell < 0 || cell + 1 >= P->nplanes) {
-                        *P->status = 1;
-                        cell = cell < 0 ? 0 : P->nplanes - 2;
-                    }
-                }
+                HJB_TERM_SUM(T, q, k, ax.n_prefix, ax.n_terms, term_value<T, D>(ax.t[k], si, cj))
+                int cell = canon_locate<T, T, false>(ax, q, tw[a]);
+                if (a == D - 1) { HJB_PLANE_CLAMP(cell, P->plane0, P->nplanes, *P->status = 1) }
                 base += P->jstride[a] * cell;
             }
             T v[1 << D];
@@ -114,17 +88,9 @@ k_backup_ctrlsplit(const DParams *__restrict__ P, const T *__restrict__ Jn, T *_
                     if (c & (1 << a)) off += P->jstride[a];
                 v[c] = Jsrc[off];
             }
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-#pragma unroll
-                for (int j = 0; j < (1 << (D - 1 - a)); ++j)
-                    v[j] = fma_t<T>(tw[a], (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
-            }
+            HJB_LERP_AXES(T, D, v, a, 0, D, tw[a])
             T g = gpre;
-            for (int k = P->n_cost_prefix; k < P->n_cost; ++k) {
-                T x = term_value<T, D>(P->cost[k], si, cj);
-                g = (k == 0) ? x : (T)(g + x);
-            }
+            HJB_TERM_SUM(T, g, k, P->n_cost_prefix, P->n_cost, term_value<T, D>(P->cost[k], si, cj))
             const T tot = (T)(g + v[0]);
             // A NaN total (inf - inf in a runaway sweep) is never a candidate - except that of control 0, which the
             // sequential rule `first || tot < best` of the reference loop takes as the result (checked after the reduction):
@@ -154,17 +120,7 @@ k_backup_ctrlsplit(const DParams *__restrict__ P, const T *__restrict__ Jn, T *_
         }
         if (lane == 0) {
             int64_t label;
-            if (C == 1) {
-                label = best_u;
-            } else if (C == 2) {
-                int64_t j1 = best_u % P->m[1], j0 = best_u / P->m[1];
-                label = j0 + (int64_t)P->m[0] * j1;
-            } else {
-                int64_t j2 = best_u % P->m[2];
-                int64_t rr = best_u / P->m[2];
-                int64_t j1 = rr % P->m[1], j0 = rr / P->m[1];
-                label = j0 + (int64_t)P->m[0] * (j1 + (int64_t)P->m[1] * j2);
-            }
+            HJB_LABEL(label, int64_t, int64_t, C, best_u, P->m[0], P->m[1], P->m[2])
             const int64_t in_plane = ls % P->inner, pl = ls / P->inner;
             Jout[in_plane + P->inner * (pl + P->halo_lo)] = best;
             if (idx_out) st_idx(idx_out, ls, (int32_t)(label + P->index_base), P->idx_bytes);

@@ -6,7 +6,7 @@
 // wins), the W nodes the inner loop.  Per state the control-independent prefixes of the term sums and of the cost are formed once;
 // per control the term sums q_a, the stage cost g and - for the axes no node offsets (DDisturb::axes, a launch constant: wave-uniform
 // branches) - the cell and weight; per node only the offset axes are located again, q_aw = (TQ)(q_a + d[a][w]), then the 2^D corners
-// are gathered (axis-0 neighbours in one load: jstride[0] == 1) and lerped axis 0 first with fma_t, the canonical cascade.
+// are gathered (axis-0 neighbours in one load: jstride[0] == 1) and lerped by HJB_LERP_AXES (hjbdp_canon.h, as every other piece here).
 //   EXPECT: acc = (T)(p_0 v_0), acc = fma(p_w, v_w, acc) in node order.   WORST: acc = v_0, acc = v_w > acc ? v_w : acc.
 //   candidate = (T)(g + acc).  With one node, no offset axis and p_0 = 1 every operation is k_backup_generic's: the same bits.
 // The node offsets and weights sit in one small device block behind a kernel-argument pointer and are indexed by the node counter
@@ -23,7 +23,7 @@
 // Whole grids only (hjb_set_disturbance refuses slab handles): no halo, no plane window.  No LDS.
 #pragma once
 #include "hjbdp_dev.h"
-#include "kernels_evaluate.h"    // eval_term_off, eval_nan, tab_load_pair, fma_t, find_cell
+#include "hjbdp_canon.h"
 
 namespace hjb {
 
@@ -43,16 +43,6 @@ __device__ __forceinline__ TQ dist_term(const DTerm &t, const int (&si)[D], cons
     return as_global<TQ>(t.data)[eval_term_off<IX, false, D>(t, si, cj)];
 }
 
-// cell and weight of query q on axis ax (find_cell, t = (q - k[c]) * rdx[c] formed in TQ and rounded to T once)
-template <typename T, typename TQ>
-__device__ __forceinline__ int dist_locate(const DAxis &ax, TQ q, T &tw) {
-    const TQ *kk = (const TQ *)as_global<TQ>(ax.knots);
-    const TQ *rdx = (const TQ *)as_global<TQ>(ax.rdx);
-    const int cell = find_cell<TQ>(kk, ax.n, q, ax.uniform, (TQ)ax.x0, (TQ)ax.inv_h);
-    tw = (T)((TQ)((TQ)(q - kk[cell]) * rdx[cell]));
-    return cell;
-}
-
 template <typename T, typename TJ, typename TQ, int D, typename IX, bool FIXED>
 __global__ void __launch_bounds__(256)
 k_backup_disturb(const DParams *__restrict__ P, const DParams *__restrict__ PQ, const DDisturb<TQ, T> *__restrict__ DW,
@@ -69,15 +59,7 @@ k_backup_disturb(const DParams *__restrict__ P, const DParams *__restrict__ PQ, 
     IX js[D];
 #pragma unroll
     for (int a = 0; a < D; ++a) js[a] = (IX)P->jstride[a];
-    IX poff[1 << (D - 1)];                                   // element offset of corner pair p inside a cell (axes 1 .. D-1)
-#pragma unroll
-    for (int p = 0; p < (1 << (D - 1)); ++p) {
-        IX o = 0;
-#pragma unroll
-        for (int a = 1; a < D; ++a)
-            if (p & (1 << (a - 1))) o += js[a];
-        poff[p] = o;
-    }
+    HJB_PAIR_OFFSETS(IX, 1 << (D - 1), D, poff, js)
     const IX stride = (IX)gridDim.x * (IX)blockDim.x;
     for (IX ls = (IX)blockIdx.x * (IX)blockDim.x + (IX)threadIdx.x; ls < n_owned; ls += stride) {
         int cj[HJB_MAX_C] = {0, 0, 0};
@@ -123,22 +105,13 @@ k_backup_disturb(const DParams *__restrict__ P, const DParams *__restrict__ PQ, 
             for (int a = 0; a < D; ++a) {
                 const DAxis &ax = PQ->axis[a];
                 TQ q = (TQ)0;
-                for (int k = 0; k < ax.n_prefix; ++k) {
-                    const TQ x = dist_term<TQ, IX, D>(ax.t[k], si, zc);
-                    q = (k == 0) ? x : (TQ)(q + x);
-                }
+                HJB_TERM_SUM(TQ, q, k, 0, ax.n_prefix, dist_term<TQ, IX, D>(ax.t[k], si, zc))
                 qpre[a] = q;
             }
             if (c64) {
-                for (int k = 0; k < P->n_cost_prefix; ++k) {
-                    const double x = dist_term<double, IX, D>(P->cost64[k], si, zc);
-                    gpre64 = (k == 0) ? x : gpre64 + x;
-                }
+                HJB_TERM_SUM(double, gpre64, k, 0, P->n_cost_prefix, dist_term<double, IX, D>(P->cost64[k], si, zc))
             } else {
-                for (int k = 0; k < P->n_cost_prefix; ++k) {
-                    const T x = dist_term<T, IX, D>(P->cost[k], si, zc);
-                    gpre = (k == 0) ? x : (T)(gpre + x);
-                }
+                HJB_TERM_SUM(T, gpre, k, 0, P->n_cost_prefix, dist_term<T, IX, D>(P->cost[k], si, zc))
             }
         }
 
@@ -153,30 +126,21 @@ k_backup_disturb(const DParams *__restrict__ P, const DParams *__restrict__ PQ, 
             for (int a = 0; a < D; ++a) {
                 const DAxis &ax = PQ->axis[a];
                 TQ s = FIXED ? (TQ)0 : qpre[a];
-                for (int k = FIXED ? 0 : ax.n_prefix; k < ax.n_terms; ++k) {
-                    const TQ x = dist_term<TQ, IX, D>(ax.t[k], si, cj);
-                    s = (k == 0) ? x : (TQ)(s + x);
-                }
+                HJB_TERM_SUM(TQ, s, k, FIXED ? 0 : ax.n_prefix, ax.n_terms, dist_term<TQ, IX, D>(ax.t[k], si, cj))
                 q[a] = s;
                 if (!(axes & (1u << a))) {
-                    const int cell = dist_locate<T, TQ>(ax, s, tw[a]);
+                    const int cell = canon_locate<T, TQ, true>(ax, s, tw[a]);
                     base_shared += a == 0 ? (IX)cell : js[a] * (IX)cell;
                 }
             }
             T g;
             if (c64) {
                 double g64 = FIXED ? 0.0 : gpre64;
-                for (int k = FIXED ? 0 : P->n_cost_prefix; k < P->n_cost; ++k) {
-                    const double x = dist_term<double, IX, D>(P->cost64[k], si, cj);
-                    g64 = (k == 0) ? x : g64 + x;
-                }
+                HJB_TERM_SUM(double, g64, k, FIXED ? 0 : P->n_cost_prefix, P->n_cost, dist_term<double, IX, D>(P->cost64[k], si, cj))
                 g = (T)g64;
             } else {
                 g = FIXED ? (T)0 : gpre;
-                for (int k = FIXED ? 0 : P->n_cost_prefix; k < P->n_cost; ++k) {
-                    const T x = dist_term<T, IX, D>(P->cost[k], si, cj);
-                    g = (k == 0) ? x : (T)(g + x);
-                }
+                HJB_TERM_SUM(T, g, k, FIXED ? 0 : P->n_cost_prefix, P->n_cost, dist_term<T, IX, D>(P->cost[k], si, cj))
             }
             T acc = (T)0;
             for (int w = 0; w < W; ++w) {
@@ -185,7 +149,7 @@ k_backup_disturb(const DParams *__restrict__ P, const DParams *__restrict__ PQ, 
 #pragma unroll
                 for (int a = 0; a < D; ++a) {
                     if (axes & (1u << a)) {
-                        const int cell = dist_locate<T, TQ>(PQ->axis[a], (TQ)(q[a] + DW->off[a][w]), tw[a]);
+                        const int cell = canon_locate<T, TQ, true>(PQ->axis[a], (TQ)(q[a] + DW->off[a][w]), tw[a]);
                         base += a == 0 ? (IX)cell : js[a] * (IX)cell;
                     }
                 }
@@ -193,12 +157,7 @@ k_backup_disturb(const DParams *__restrict__ P, const DParams *__restrict__ PQ, 
 #pragma unroll
                 for (int p = 0; p < (1 << (D - 1)); ++p)         // corners 2p, 2p + 1: the axis-0 neighbours, one load
                     tab_load_pair(Jn, (int64_t)(base + poff[p]), v[2 * p], v[2 * p + 1]);
-#pragma unroll
-                for (int a = 0; a < D; ++a) {
-#pragma unroll
-                    for (int j = 0; j < (1 << (D - 1 - a)); ++j)
-                        v[j] = fma_t<T>(tw[a], (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
-                }
+                HJB_LERP_AXES(T, D, v, a, 0, D, tw[a])
                 if (worst) acc = (w == 0) ? v[0] : (v[0] > acc ? v[0] : acc);
                 else acc = (w == 0) ? (T)(pw * v[0]) : fma_t<T>(pw, v[0], acc);
             }
@@ -207,35 +166,13 @@ k_backup_disturb(const DParams *__restrict__ P, const DParams *__restrict__ PQ, 
                 best = tot;
                 best_u = u;
             }
-            if (!FIXED) {       // next control: last control dim fastest, dim 0 slowest
-                if (C == 1) {
-                    ++cj[0];
-                } else if (C == 2) {
-                    if (++cj[1] == P->m[1]) { cj[1] = 0; ++cj[0]; }
-                } else {
-                    if (++cj[2] == P->m[2]) {
-                        cj[2] = 0;
-                        if (++cj[1] == P->m[1]) { cj[1] = 0; ++cj[0]; }
-                    }
-                }
-            }
+            if (!FIXED) { HJB_NEXT_CONTROL(C, cj, P->m[1], P->m[2]) }
         }
         stj<T, TJ>(Jout, (int64_t)ls, best);
         if (!FIXED && idx_out) {
-            // visiting index (dim 0 slowest) -> column-major label (dim 0 fastest)
             int64_t label;
             const int64_t bu = (int64_t)best_u;
-            if (C == 1) {
-                label = bu;
-            } else if (C == 2) {
-                const int64_t j1 = bu % P->m[1], j0 = bu / P->m[1];
-                label = j0 + (int64_t)P->m[0] * j1;
-            } else {
-                const int64_t j2 = bu % P->m[2];
-                const int64_t rr = bu / P->m[2];
-                const int64_t j1 = rr % P->m[1], j0 = rr / P->m[1];
-                label = j0 + (int64_t)P->m[0] * (j1 + (int64_t)P->m[1] * j2);
-            }
+            HJB_LABEL(label, int64_t, int64_t, C, bu, P->m[0], P->m[1], P->m[2])
             st_idx(idx_out, (int64_t)ls, (int32_t)(label + index_base), idx_bytes);
         }
     }

@@ -3,10 +3,10 @@
 // One thread per owned state, axis 0 fastest (label loads and J stores coalesce; neighbouring lanes with equal labels land in
 // neighbouring cells, so the axis-0 corner pairs mostly coalesce too).  The thread reads its label, decodes it column-major
 // (first control dim fastest: the layout the stage kernels WRITE, not their visiting order) and forms exactly the candidate value
-// the stage kernels form for that (state, control): ordered term sums, exact cell search, t = (q - k[c]) * rdx[c], the 2^D corners
-// lerped axis 0 first with fma_t, the ordered cost sum, tot = (T)(g + v[0]).  Bit-identical to the value the backup kernels compare.
+// the stage kernels form for that (state, control), from the same statements (hjbdp_canon.h: HJB_TERM_SUM, HJB_LOCATE, HJB_PLANE_CLAMP,
+// HJB_LERP_AXES), tot = (T)(g + v[0]).  Bit-identical to the value the backup kernels compare.
 //   TABLED: cells and weights come from the handle's stage-invariant (cell, t) tables (kernels_tabled.h; HJB_TAB_F64 handles always:
-//   their tables are built in double, the weight rounded once); otherwise the terms are summed on the fly as k_backup_generic does.
+//   their tables are built in double, the weight rounded once); otherwise the terms are summed and located on the fly.
 //   HJB_COST_F64: state part and control part of the cost summed in double, one rounding (k_backup_tabled).
 // A label outside [index_base, index_base + nU): nothing is read for that state, NaN is stored, *bad_label is set; every other
 // state is unaffected.  A query that leaves the slab raises DParams::status and is clamped, as in the stage kernels.  No LDS.
@@ -24,27 +24,16 @@
 #include <type_traits>
 #include "hjbdp_dev.h"
 #include "hjbdp_walk.h"          // xcd_share
-#include "kernels_generic.h"
-#include "kernels_tabled.h"      // TabEntry, DTabled, tab_load_pair
+#include "hjbdp_canon.h"
+#include "kernels_tabled.h"      // TabEntry, DTabled
 
 namespace hjb {
-
-template <typename T> __device__ __forceinline__ T eval_nan();
-template <> __device__ __forceinline__ float eval_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double eval_nan<double>() { return __builtin_nan(""); }
 
 // the divisors of one launch, by value: n[a] = axis a's size (a < D - 1: what the state index is taken apart by), m[c] = control dim c's
 struct EvalDiv {
     MagicDiv n[HJB_MAX_D];
     MagicDiv m[2];
 };
-
-// a * b of two index quantities (M24: both below 2^24, the product below 2^32)
-template <typename IX, bool M24>
-__device__ __forceinline__ IX eval_mul(IX a, IX b) {
-    if constexpr (M24) return (IX)__umul24((unsigned)a, (unsigned)b);
-    else return a * b;
-}
 
 // q = r / k.d, rem = r - q * k.d
 template <typename IX, bool M24>
@@ -54,23 +43,6 @@ __device__ __forceinline__ IX eval_divmod(IX r, const MagicDiv &k, int &rem) {
     else q = r / (IX)k.d;
     rem = (int)(r - eval_mul<IX, M24>(q, (IX)k.d));
     return q;
-}
-
-// element offset of a term at (state, control); zero strides (the dims the term is broadcast along) cost a scalar compare
-template <typename IX, bool M24, int D>
-__device__ __forceinline__ IX eval_term_off(const DTerm &t, const int (&si)[D], const int (&cj)[HJB_MAX_C]) {
-    IX off = 0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        const int st = t.stride[a];
-        if (st != 0) off += eval_mul<IX, M24>((IX)st, (IX)si[a]);
-    }
-#pragma unroll
-    for (int c = 0; c < HJB_MAX_C; ++c) {
-        const int st = t.stride[D + c];
-        if (st != 0) off += eval_mul<IX, M24>((IX)st, (IX)cj[c]);
-    }
-    return off;
 }
 
 template <typename T, typename TJ, int D, bool TABLED, typename IX, bool M24>
@@ -87,15 +59,7 @@ k_evaluate(const DParams *__restrict__ P, const DTabled *__restrict__ TB, const 
     IX js[D];
 #pragma unroll
     for (int a = 0; a < D; ++a) js[a] = (IX)P->jstride[a];
-    IX poff[1 << (D - 1)];                                   // element offset of corner pair p inside a cell (axes 1 .. D-1)
-#pragma unroll
-    for (int p = 0; p < (1 << (D - 1)); ++p) {
-        IX o = 0;
-#pragma unroll
-        for (int a = 1; a < D; ++a)
-            if (p & (1 << (a - 1))) o += js[a];
-        poff[p] = o;
-    }
+    HJB_PAIR_OFFSETS(IX, 1 << (D - 1), D, poff, js)
     const IX stride = (IX)gridDim.x * (IX)blockDim.x;
     for (IX ls = (IX)xcd_share(blockIdx.x, gridDim.x) * (IX)blockDim.x + (IX)threadIdx.x; ls < n_owned; ls += stride) {
         // (the label minus the base in 64 bits: an int32 label of any value stays what it is)
@@ -153,18 +117,11 @@ k_evaluate(const DParams *__restrict__ P, const DTabled *__restrict__ TB, const 
             } else {
                 const DAxis &ax = P->axis[a];
                 T q = (T)0;
-                for (int k = 0; k < ax.n_terms; ++k) {
-                    const T x = as_global<T>(ax.t[k].data)[eval_term_off<IX, M24, D>(ax.t[k], si, cj)];
-                    q = (k == 0) ? x : (T)(q + x);
-                }
+                HJB_TERM_SUM(T, q, k, 0, ax.n_terms, as_global<T>(ax.t[k].data)[eval_term_off<IX, M24, D>(ax.t[k], si, cj)])
                 const T *kk = static_cast<const T *>(ax.knots);
-                cell = find_cell<T>(kk, ax.n, q, ax.uniform, (T)ax.x0, (T)ax.inv_h);
-                tw[a] = (T)((T)(q - kk[cell]) * static_cast<const T *>(ax.rdx)[cell]);
+                HJB_LOCATE(T, ax, kk, static_cast<const T *>(ax.rdx), q, cell, tw[a], (T));
             }
-            if (a == D - 1) {
-                cell -= plane0;
-                if (cell < 0 || cell + 1 >= nplanes) { left = true; cell = cell < 0 ? 0 : nplanes - 2; }
-            }
+            if (a == D - 1) { HJB_PLANE_CLAMP(cell, plane0, nplanes, left = true) }
             base += a == 0 ? (IX)cell : eval_mul<IX, M24>(js[a], (IX)cell);      // (axis 0 is contiguous in every J layout: jstride[0] == 1)
         }
         if (left) *P->status = 1;
@@ -172,25 +129,14 @@ k_evaluate(const DParams *__restrict__ P, const DTabled *__restrict__ TB, const 
 #pragma unroll
         for (int p = 0; p < (1 << (D - 1)); ++p)             // corners 2p, 2p + 1: the axis-0 neighbours, one load (jstride[0] == 1)
             tab_load_pair(Jn, (int64_t)(base + poff[p]), v[2 * p], v[2 * p + 1]);
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-#pragma unroll
-            for (int j = 0; j < (1 << (D - 1 - a)); ++j)
-                v[j] = fma_t<T>(tw[a], (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
-        }
+        HJB_LERP_AXES(T, D, v, a, 0, D, tw[a])
         T g = (T)0;
         if (c64) {                               // state part, then control part, in double: ONE rounding to the arithmetic type
             double g64 = 0.0;
-            for (int k = 0; k < P->n_cost; ++k) {
-                const double x = as_global<double>(P->cost64[k].data)[eval_term_off<IX, M24, D>(P->cost64[k], si, cj)];
-                g64 = (k == 0) ? x : g64 + x;
-            }
+            HJB_TERM_SUM(double, g64, k, 0, P->n_cost, as_global<double>(P->cost64[k].data)[eval_term_off<IX, M24, D>(P->cost64[k], si, cj)])
             g = (T)g64;
         } else {
-            for (int k = 0; k < P->n_cost; ++k) {
-                const T x = as_global<T>(P->cost[k].data)[eval_term_off<IX, M24, D>(P->cost[k], si, cj)];
-                g = (k == 0) ? x : (T)(g + x);
-            }
+            HJB_TERM_SUM(T, g, k, 0, P->n_cost, as_global<T>(P->cost[k].data)[eval_term_off<IX, M24, D>(P->cost[k], si, cj)])
         }
         stj<T, TJ>(Jout, (int64_t)(ls + out0), (T)(g + v[0]));
     }

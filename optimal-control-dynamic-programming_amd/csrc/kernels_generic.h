@@ -12,45 +12,9 @@
 // for throughput; this one is the safety net and the parity anchor.
 #pragma once
 #include "hjbdp_dev.h"
+#include "hjbdp_canon.h"
 
 namespace hjb {
-
-template <typename T> __device__ __forceinline__ T fma_t(T a, T b, T c);
-template <> __device__ __forceinline__ float fma_t<float>(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-template <> __device__ __forceinline__ double fma_t<double>(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-// clamp(upper_bound(k, q) - 1, 0, n-2), exact for any strictly increasing knots.
-template <typename T>
-__device__ __forceinline__ int find_cell(const T *__restrict__ k, int n, T q, int uniform, T x0, T inv_h) {
-    int i;
-    if (uniform) {
-        T f = (q - x0) * inv_h;
-        T hi = (T)(n - 2);
-        f = f > (T)0 ? f : (T)0;
-        f = f < hi ? f : hi;
-        i = (int)f;
-        while (i > 0 && q < k[i]) --i;
-        while (i < n - 2 && q >= k[i + 1]) ++i;
-    } else {
-        int lo = 0, hi = n - 1;
-        while (hi - lo > 1) {
-            int mid = (lo + hi) >> 1;
-            if (k[mid] <= q) lo = mid; else hi = mid;
-        }
-        i = lo;
-    }
-    return i;
-}
-
-template <typename T, int D>
-__device__ __forceinline__ T term_value(const DTerm &t, const int (&si)[D], const int (&cj)[HJB_MAX_C]) {
-    int64_t off = 0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) off += (int64_t)t.stride[a] * si[a];
-#pragma unroll
-    for (int c = 0; c < HJB_MAX_C; ++c) off += (int64_t)t.stride[D + c] * cj[c];
-    return static_cast<const T *>(t.data)[off];
-}
 
 template <typename T, typename TJ, int D>
 __global__ void __launch_bounds__(256)
@@ -62,33 +26,18 @@ k_backup_generic(const DParams *__restrict__ P, const TJ *__restrict__ Jn, TJ *_
     for (int64_t ls = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; ls < n_owned;
          ls += (int64_t)gridDim.x * blockDim.x) {
         int si[D];
-        {
-            int64_t r = ls;
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-                int na = P->n[a];
-                si[a] = (int)(r % na);
-                r /= na;
-            }
-            si[D - 1] += P->slab_begin;  // tables are indexed by GLOBAL grid indices
-        }
+        HJB_STATE_INDEX(D, P, ls, si, a, )
         int cj[HJB_MAX_C] = {0, 0, 0};
         T qpre[D];
 #pragma unroll
         for (int a = 0; a < D; ++a) {
             const DAxis &ax = P->axis[a];
             T q = (T)0;
-            for (int k = 0; k < ax.n_prefix; ++k) {
-                T x = term_value<T, D>(ax.t[k], si, cj);
-                q = (k == 0) ? x : (T)(q + x);
-            }
+            HJB_TERM_SUM(T, q, k, 0, ax.n_prefix, term_value<T, D>(ax.t[k], si, cj))
             qpre[a] = q;
         }
         T gpre = (T)0;
-        for (int k = 0; k < P->n_cost_prefix; ++k) {
-            T x = term_value<T, D>(P->cost[k], si, cj);
-            gpre = (k == 0) ? x : (T)(gpre + x);
-        }
+        HJB_TERM_SUM(T, gpre, k, 0, P->n_cost_prefix, term_value<T, D>(P->cost[k], si, cj))
 
         T best = (T)0;
         int64_t best_u = 0;
@@ -99,20 +48,9 @@ k_backup_generic(const DParams *__restrict__ P, const TJ *__restrict__ Jn, TJ *_
             for (int a = 0; a < D; ++a) {
                 const DAxis &ax = P->axis[a];
                 T q = qpre[a];
-                for (int k = ax.n_prefix; k < ax.n_terms; ++k) {
-                    T x = term_value<T, D>(ax.t[k], si, cj);
-                    q = (k == 0) ? x : (T)(q + x);
-                }
-                const T *kk = static_cast<const T *>(ax.knots);
-                int cell = find_cell<T>(kk, ax.n, q, ax.uniform, (T)ax.x0, (T)ax.inv_h);
-                tw[a] = (T)((T)(q - kk[cell]) * static_cast<const T *>(ax.rdx)[cell]);
-                if (a == D - 1) {
-                    cell -= P->plane0;
-                    if (cell < 0 || cell + 1 >= P->nplanes) {
-                        *P->status = 1;
-                        cell = cell < 0 ? 0 : P->nplanes - 2;
-                    }
-                }
+                HJB_TERM_SUM(T, q, k, ax.n_prefix, ax.n_terms, term_value<T, D>(ax.t[k], si, cj))
+                int cell = canon_locate<T, T, false>(ax, q, tw[a]);
+                if (a == D - 1) { HJB_PLANE_CLAMP(cell, P->plane0, P->nplanes, *P->status = 1) }
                 base += P->jstride[a] * cell;
             }
             T v[1 << D];
@@ -124,47 +62,18 @@ k_backup_generic(const DParams *__restrict__ P, const TJ *__restrict__ Jn, TJ *_
                     if (c & (1 << a)) off += P->jstride[a];
                 v[c] = ldj<T, TJ>(Jn, off);
             }
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-#pragma unroll
-                for (int j = 0; j < (1 << (D - 1 - a)); ++j)
-                    v[j] = fma_t<T>(tw[a], (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
-            }
+            HJB_LERP_AXES(T, D, v, a, 0, D, tw[a])
             T g = gpre;
-            for (int k = P->n_cost_prefix; k < P->n_cost; ++k) {
-                T x = term_value<T, D>(P->cost[k], si, cj);
-                g = (k == 0) ? x : (T)(g + x);
-            }
+            HJB_TERM_SUM(T, g, k, P->n_cost_prefix, P->n_cost, term_value<T, D>(P->cost[k], si, cj))
             T tot = (T)(g + v[0]);
             if (u == 0 || tot < best) {
                 best = tot;
                 best_u = u;
             }
-            // next control: last control dim fastest, dim 0 slowest
-            if (C == 1) {
-                ++cj[0];
-            } else if (C == 2) {
-                if (++cj[1] == P->m[1]) { cj[1] = 0; ++cj[0]; }
-            } else {
-                if (++cj[2] == P->m[2]) {
-                    cj[2] = 0;
-                    if (++cj[1] == P->m[1]) { cj[1] = 0; ++cj[0]; }
-                }
-            }
+            HJB_NEXT_CONTROL(C, cj, P->m[1], P->m[2])
         }
-        // visiting index (dim 0 slowest) -> column-major label (dim 0 fastest)
         int64_t label;
-        if (C == 1) {
-            label = best_u;
-        } else if (C == 2) {
-            int64_t j1 = best_u % P->m[1], j0 = best_u / P->m[1];
-            label = j0 + (int64_t)P->m[0] * j1;
-        } else {
-            int64_t j2 = best_u % P->m[2];
-            int64_t rr = best_u / P->m[2];
-            int64_t j1 = rr % P->m[1], j0 = rr / P->m[1];
-            label = j0 + (int64_t)P->m[0] * (j1 + (int64_t)P->m[1] * j2);
-        }
+        HJB_LABEL(label, int64_t, int64_t, C, best_u, P->m[0], P->m[1], P->m[2])
         const int64_t in_plane = ls % P->inner, pl = ls / P->inner;
         stj<T, TJ>(Jout, in_plane + P->inner * (pl + P->halo_lo), best);
         if (idx_out) st_idx(idx_out, ls, (int32_t)(label + P->index_base), P->idx_bytes);
@@ -173,7 +82,7 @@ k_backup_generic(const DParams *__restrict__ P, const TJ *__restrict__ Jn, TJ *_
 
 // Stage-invariant per-axis (cell, weight) table over the axis' broadcast domain
 // (used by variant 2).  One thread per domain entry; same canonical arithmetic as
-// the stage kernels: q = ordered term sum, exact cell search, t = (q-k[c])*rdx[c].
+// the stage kernels (hjbdp_canon.h): ordered term sum, locate.
 // dom_size[d] = grid size of dim d if d is in the domain, else 1; entries are laid
 // out column-major over the domain dims in increasing dim order.
 template <typename T, int D>
@@ -200,13 +109,11 @@ k_prep_axis_table(const DParams *__restrict__ P, int a, const int32_t *__restric
         }
         si[D - 1] += P->slab_begin;   // term tables are indexed by GLOBAL grid indices; the domain covers owned planes
         T q = (T)0;
-        for (int k = 0; k < ax.n_terms; ++k) {
-            T x = term_value<T, D>(ax.t[k], si, cj);
-            q = (k == 0) ? x : (T)(q + x);
-        }
+        HJB_TERM_SUM(T, q, k, 0, ax.n_terms, term_value<T, D>(ax.t[k], si, cj))
         const T *kk = static_cast<const T *>(ax.knots);
-        const int cell = find_cell<T>(kk, ax.n, q, ax.uniform, (T)ax.x0, (T)ax.inv_h);
-        const float t = (float)((T)((T)(q - kk[cell]) * static_cast<const T *>(ax.rdx)[cell]));
+        int cell;
+        float t;
+        HJB_LOCATE(T, ax, kk, static_cast<const T *>(ax.rdx), q, cell, t, (float));
         out[e] = make_int2(cell, __float_as_int(t));
     }
 }

@@ -1,13 +1,13 @@
 // kernels_lookup.h - K5: batched policy / value lookup on a grid.
 // One thread per query point.  'linear' uses the sweep's canonical interpolation
-// (exact cell search, t = (q-k[c])*rdx[c], fma lerps axis 0 first); 'nearest' picks,
+// (hjbdp_canon.h: find_cell, HJB_WEIGHT, HJB_LERP_AXES); 'nearest' picks,
 // per axis, the nearer knot of the enclosing cell (upper knot at the midpoint).  Knots,
 // queries and the distances are all in T: with T = float a query near a midpoint can pick
 // the other knot than the host's float64 rule (matlab_compat.interp_nearest_point) would,
 // so NearestPolicy.lookup_many calls the T = double form whatever its values' type.
 #pragma once
 #include "hjbdp_dev.h"
-#include "kernels_generic.h"
+#include "hjbdp_canon.h"
 
 namespace hjb {
 
@@ -35,7 +35,7 @@ k_policy_lookup(DLookup L, const T *__restrict__ V, int64_t nq, const T *__restr
                 if ((T)(q - kk[cell]) >= (T)(kk[cell + 1] - q)) ++cell;
                 tw[a] = (T)0;
             } else {
-                tw[a] = (T)((T)(q - kk[cell]) * static_cast<const T *>(L.rdx[a])[cell]);
+                tw[a] = HJB_WEIGHT(T, q, kk[cell], static_cast<const T *>(L.rdx[a])[cell]);
             }
             base += L.stride[a] * cell;
         }
@@ -52,12 +52,7 @@ k_policy_lookup(DLookup L, const T *__restrict__ V, int64_t nq, const T *__restr
                 if (c & (1 << a)) off += L.stride[a];
             v[c] = V[off];
         }
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-#pragma unroll
-            for (int j = 0; j < (1 << (D - 1 - a)); ++j)
-                v[j] = fma_t<T>(tw[a], (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
-        }
+        HJB_LERP_AXES(T, D, v, a, 0, D, tw[a])
         out[i] = v[0];
     }
 }

@@ -19,7 +19,7 @@
 //     workgroup (one ds_read_b128 per control brings every inner table value).
 #pragma once
 #include "hjbdp_dev.h"
-#include "kernels_generic.h"
+#include "hjbdp_canon.h"
 
 namespace hjb {
 
@@ -183,33 +183,18 @@ k_backup_nested(const DParams *__restrict__ P, const DNested *__restrict__ N, co
     for (int64_t ls = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; ls < n_owned;
          ls += (int64_t)gridDim.x * blockDim.x) {
         int si[D];
-        {
-            int64_t r = ls;
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-                int na = P->n[a];
-                si[a] = (int)(r % na);
-                r /= na;
-            }
-            si[D - 1] += P->slab_begin;
-        }
+        HJB_STATE_INDEX(D, P, ls, si, a, )
         int cj[HJB_MAX_C] = {0, 0, 0};
         T qpre[D];
 #pragma unroll
         for (int a = 0; a < D; ++a) {
             const DAxis &ax = P->axis[a];
             T q = (T)0;
-            for (int k = 0; k < ax.n_prefix; ++k) {
-                T x = term_value<T, D>(ax.t[k], si, cj);
-                q = (k == 0) ? x : (T)(q + x);
-            }
+            HJB_TERM_SUM(T, q, k, 0, ax.n_prefix, term_value<T, D>(ax.t[k], si, cj))
             qpre[a] = q;
         }
         T gpre = (T)0;
-        for (int k = 0; k < P->n_cost_prefix; ++k) {
-            T x = term_value<T, D>(P->cost[k], si, cj);
-            gpre = (k == 0) ? x : (T)(gpre + x);
-        }
+        HJB_TERM_SUM(T, gpre, k, 0, P->n_cost_prefix, term_value<T, D>(P->cost[k], si, cj))
         CellTrack<T> trk[D];
 #pragma unroll
         for (int a = 0; a < D; ++a) track_reset(trk[a]);
@@ -228,27 +213,18 @@ k_backup_nested(const DParams *__restrict__ P, const DNested *__restrict__ N, co
             for (int a = 0; a < D - 1; ++a) {
                 const DAxis &ax = P->axis[a];
                 T q = qpre[a];
-                for (int k = ax.n_prefix; k < N->ax_l0[a]; ++k) {
-                    T x = term_value<T, D>(ax.t[k], si, cj);
-                    q = (k == 0) ? x : (T)(q + x);
-                }
+                HJB_TERM_SUM(T, q, k, ax.n_prefix, N->ax_l0[a], term_value<T, D>(ax.t[k], si, cj))
                 q0[a] = q;
                 if (N->ax_l0[a] == ax.n_terms) {   // fully resolved at this level
                     track_update<T>(trk[a], static_cast<const T *>(ax.knots), static_cast<const T *>(ax.rdx), ax.n, q,
                                     ax.uniform, (T)ax.x0, (T)ax.inv_h);
-                    tw[a] = (T)((T)(q - trk[a].kc) * trk[a].rc);
+                    tw[a] = HJB_WEIGHT(T, q, trk[a].kc, trk[a].rc);
                 }
             }
             T qo0 = qpre[D - 1];
-            for (int k = axl.n_prefix; k < N->ax_l0[D - 1]; ++k) {
-                T x = term_value<T, D>(axl.t[k], si, cj);
-                qo0 = (k == 0) ? x : (T)(qo0 + x);
-            }
+            HJB_TERM_SUM(T, qo0, k, axl.n_prefix, N->ax_l0[D - 1], term_value<T, D>(axl.t[k], si, cj))
             T go0 = gpre;
-            for (int k = P->n_cost_prefix; k < N->cost_l0; ++k) {
-                T x = term_value<T, D>(P->cost[k], si, cj);
-                go0 = (k == 0) ? x : (T)(go0 + x);
-            }
+            HJB_TERM_SUM(T, go0, k, P->n_cost_prefix, N->cost_l0, term_value<T, D>(P->cost[k], si, cj))
           for (int o1 = 0; o1 < m_o1; ++o1, ++uo) {
             if (C == 3) cj[1] = o1; else if (C == 2) cj[0] = o1;
             // ---- level 1: once per outer control step --------------------------
@@ -258,26 +234,17 @@ k_backup_nested(const DParams *__restrict__ P, const DNested *__restrict__ N, co
                 const DAxis &ax = P->axis[a];
                 if (N->ax_l0[a] != ax.n_terms) {
                     T q = q0[a];
-                    for (int k = N->ax_l0[a]; k < ax.n_terms; ++k) {
-                        T x = term_value<T, D>(ax.t[k], si, cj);
-                        q = (k == 0) ? x : (T)(q + x);
-                    }
+                    HJB_TERM_SUM(T, q, k, N->ax_l0[a], ax.n_terms, term_value<T, D>(ax.t[k], si, cj))
                     track_update<T>(trk[a], static_cast<const T *>(ax.knots), static_cast<const T *>(ax.rdx), ax.n, q,
                                     ax.uniform, (T)ax.x0, (T)ax.inv_h);
-                    tw[a] = (T)((T)(q - trk[a].kc) * trk[a].rc);
+                    tw[a] = HJB_WEIGHT(T, q, trk[a].kc, trk[a].rc);
                 }
                 base += P->jstride[a] * trk[a].cell;
             }
             T qo = qo0;
-            for (int k = N->ax_l0[D - 1]; k < ax_kin; ++k) {
-                T x = term_value<T, D>(axl.t[k], si, cj);
-                qo = (k == 0) ? x : (T)(qo + x);
-            }
+            HJB_TERM_SUM(T, qo, k, N->ax_l0[D - 1], ax_kin, term_value<T, D>(axl.t[k], si, cj))
             T go = go0;
-            for (int k = N->cost_l0; k < cost_kin; ++k) {
-                T x = term_value<T, D>(P->cost[k], si, cj);
-                go = (k == 0) ? x : (T)(go + x);
-            }
+            HJB_TERM_SUM(T, go, k, N->cost_l0, cost_kin, term_value<T, D>(P->cost[k], si, cj))
             int ib[kMaxInner] = {0, 0, 0, 0};
             if (any_gen) {
 #pragma unroll
@@ -301,11 +268,8 @@ k_backup_nested(const DParams *__restrict__ P, const DNested *__restrict__ N, co
                     xb = s_tab[(j + 1) * kMaxInner];
                     xr = s_tab[(j + 1) * kMaxInner + kMaxInAx];
                     if (track_update<T>(trk[D - 1], s_k, s_r, nl, q, l_uniform, l_x0, l_invh)) {
-                        lc = trk[D - 1].cell - plane0;
-                        if (lc < 0 || lc + 1 >= nplanes) {
-                            *P->status = 1;
-                            lc = lc < 0 ? 0 : nplanes - 2;
-                        }
+                        lc = trk[D - 1].cell;
+                        HJB_PLANE_CLAMP(lc, plane0, nplanes, *P->status = 1)
                         need_gather = true;
                     }
                     if (need_gather) {
@@ -320,16 +284,11 @@ k_backup_nested(const DParams *__restrict__ P, const DNested *__restrict__ N, co
                                 if (c & (1 << a)) off += P->jstride[a];
                             v[c] = Jn[off];
                         }
-#pragma unroll
-                        for (int a = 0; a < D - 1; ++a) {
-#pragma unroll
-                            for (int jj = 0; jj < (1 << (D - 1 - a)); ++jj)
-                                v[jj] = fma_t<T>(tw[a], (T)(v[2 * jj + 1] - v[2 * jj]), v[2 * jj]);
-                        }
+                        HJB_LERP_AXES(T, D, v, a, 0, D - 1, tw[a])
                         E0 = v[0];
                         dE = (T)(v[1] - v[0]);
                     }
-                    const T t = (T)((T)(q - trk[D - 1].kc) * trk[D - 1].rc);
+                    const T t = HJB_WEIGHT(T, q, trk[D - 1].kc, trk[D - 1].rc);
                     const T tot = (T)(gr + fma_t<T>(t, dE, E0));
                     if (tot < ibest) {
                         ibest = tot;
@@ -353,14 +312,11 @@ k_backup_nested(const DParams *__restrict__ P, const DNested *__restrict__ N, co
                             if (gen[s]) x[s] = gdata[s][ib[s] + j * gstride[s]];
                     }
                     T q = qo;
-                    if (n_ax_in > 0) q = (ax_kin == 0) ? x[0] : (T)(q + x[0]);
+                    if (n_ax_in > 0) HJB_TERM_ADD(T, q, ax_kin == 0, x[0]);
                     if (n_ax_in > 1) q = (T)(q + x[1]);
                     if (track_update<T>(trk[D - 1], s_k, s_r, nl, q, l_uniform, l_x0, l_invh)) {
-                        lc = trk[D - 1].cell - plane0;
-                        if (lc < 0 || lc + 1 >= nplanes) {
-                            *P->status = 1;
-                            lc = lc < 0 ? 0 : nplanes - 2;
-                        }
+                        lc = trk[D - 1].cell;
+                        HJB_PLANE_CLAMP(lc, plane0, nplanes, *P->status = 1)
                         need_gather = true;
                     }
                     if (need_gather) {
@@ -375,19 +331,14 @@ k_backup_nested(const DParams *__restrict__ P, const DNested *__restrict__ N, co
                                 if (c & (1 << a)) off += P->jstride[a];
                             v[c] = Jn[off];
                         }
-    #pragma unroll
-                        for (int a = 0; a < D - 1; ++a) {
-    #pragma unroll
-                            for (int jj = 0; jj < (1 << (D - 1 - a)); ++jj)
-                                v[jj] = fma_t<T>(tw[a], (T)(v[2 * jj + 1] - v[2 * jj]), v[2 * jj]);
-                        }
+                        HJB_LERP_AXES(T, D, v, a, 0, D - 1, tw[a])
                         E0 = v[0];
                         dE = (T)(v[1] - v[0]);
                     }
-                    const T t = (T)((T)(q - trk[D - 1].kc) * trk[D - 1].rc);
+                    const T t = HJB_WEIGHT(T, q, trk[D - 1].kc, trk[D - 1].rc);
                     const T val = fma_t<T>(t, dE, E0);
                     T g = go;
-                    if (n_cost_in > 0) g = (cost_kin == 0) ? x[kMaxInAx] : (T)(g + x[kMaxInAx]);
+                    if (n_cost_in > 0) HJB_TERM_ADD(T, g, cost_kin == 0, x[kMaxInAx]);
                     if (n_cost_in > 1) g = (T)(g + x[kMaxInAx + 1]);
                     const T tot = (T)(g + val);
                     if ((uo == 0 && j == 0) || tot < best) {
@@ -399,16 +350,8 @@ k_backup_nested(const DParams *__restrict__ P, const DNested *__restrict__ N, co
             }
           }  // o1
         }  // o0
-        // visiting order (dim 0 slowest) -> column-major label (dim 0 fastest)
         int64_t label;
-        if (C == 1) {
-            label = best_j;
-        } else if (C == 2) {
-            label = best_uo + (int64_t)P->m[0] * best_j;
-        } else {
-            const int j1 = best_uo % P->m[1], j0 = best_uo / P->m[1];
-            label = j0 + (int64_t)P->m[0] * (j1 + (int64_t)P->m[1] * best_j);
-        }
+        HJB_LABEL_NESTED(label, int64_t, C, best_uo, best_j, P->m[0], P->m[1])
         const int64_t in_plane = ls % P->inner, pl = ls / P->inner;
         Jout[in_plane + P->inner * (pl + P->halo_lo)] = best;
         if (idx_out) st_idx(idx_out, ls, (int32_t)(label + P->index_base), P->idx_bytes);

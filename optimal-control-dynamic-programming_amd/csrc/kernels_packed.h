@@ -453,14 +453,7 @@ k_backup_packed(const DParams *__restrict__ P, const DNested *__restrict__ N, co
         for (int s = 0; s < 2; ++s) {
             if (!valid[s]) continue;
             int label;
-            if (C == 1) {
-                label = best_j[s];
-            } else if (C == 2) {
-                label = best_uo[s] + P->m[0] * best_j[s];
-            } else {
-                const int j1 = best_uo[s] % P->m[1], j0 = best_uo[s] / P->m[1];
-                label = j0 + P->m[0] * (j1 + P->m[1] * best_j[s]);
-            }
+            HJB_LABEL_NESTED(label, int, C, best_uo[s], best_j[s], P->m[0], P->m[1])
             const int in_plane = ls[s] % inner_sz, pl = ls[s] / inner_sz;
             Jout[in_plane + inner_sz * (pl + P->halo_lo)] = best[s];
             if (idx_out) st_idx(idx_out, ls[s], label + P->index_base, P->idx_bytes);

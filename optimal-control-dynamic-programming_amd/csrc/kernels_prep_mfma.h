@@ -16,7 +16,7 @@
 // 1024 sums per 64 SIMD-cycles against 64 per ~2.2, and the cell search that follows dominates either way.
 #pragma once
 #include "hjbdp_dev.h"
-#include "kernels_generic.h"
+#include "hjbdp_canon.h"
 
 namespace hjb {
 

@@ -1,11 +1,11 @@
 // kernels_probe.h - the reference's debug taps as a kernel (test/Dynamic_Solver.m:212-219, `checkstagesXJF`):
 // for a rectangular sub-block of states and ONE control, the stage cost g(x,u), the next-state coordinate of every
 // axis and J_{k+1} interpolated there - the quantities the reference copies out of its J_current_state, X_next_M*
-// and J_F_next tables per stage.  Same canonical arithmetic as the stage kernels (ordered term sums, exact cell
-// search, axis-0-first lerps), one thread per block state; a few hundred states at most, never on the hot path.
+// and J_F_next tables per stage.  The stage kernels' canonical arithmetic, from the same statements (hjbdp_canon.h),
+// one thread per block state; a few hundred states at most, never on the hot path.
 #pragma once
 #include "hjbdp_dev.h"
-#include "kernels_generic.h"
+#include "hjbdp_canon.h"
 
 namespace hjb {
 
@@ -36,26 +36,17 @@ k_probe(const DParams *__restrict__ P, DProbe pr, const TJ *__restrict__ Jn) {
         for (int a = 0; a < D; ++a) {
             const DAxis &ax = P->axis[a];
             T q = (T)0;
-            for (int k = 0; k < ax.n_terms; ++k) {
-                const T x = term_value<T, D>(ax.t[k], si, cj);
-                q = (k == 0) ? x : (T)(q + x);
-            }
+            HJB_TERM_SUM(T, q, k, 0, ax.n_terms, term_value<T, D>(ax.t[k], si, cj))
             if (pr.x_next) static_cast<T *>(pr.x_next)[b + pr.B * a] = q;
             const T *kk = static_cast<const T *>(ax.knots);
-            int cell = find_cell<T>(kk, ax.n, q, ax.uniform, (T)ax.x0, (T)ax.inv_h);
-            tw[a] = (T)((T)(q - kk[cell]) * static_cast<const T *>(ax.rdx)[cell]);
-            if (a == D - 1) {
-                cell -= P->plane0;
-                if (cell < 0 || cell + 1 >= P->nplanes) { bad = true; cell = cell < 0 ? 0 : P->nplanes - 2; }
-            }
+            int cell;
+            HJB_LOCATE(T, ax, kk, static_cast<const T *>(ax.rdx), q, cell, tw[a], (T));
+            if (a == D - 1) { HJB_PLANE_CLAMP(cell, P->plane0, P->nplanes, bad = true) }
             base += P->jstride[a] * cell;
         }
         if (pr.g) {
             T g = (T)0;
-            for (int k = 0; k < P->n_cost; ++k) {
-                const T x = term_value<T, D>(P->cost[k], si, cj);
-                g = (k == 0) ? x : (T)(g + x);
-            }
+            HJB_TERM_SUM(T, g, k, 0, P->n_cost, term_value<T, D>(P->cost[k], si, cj))
             static_cast<T *>(pr.g)[b] = g;
         }
         if (pr.j_interp && Jn) {
@@ -69,12 +60,7 @@ k_probe(const DParams *__restrict__ P, DProbe pr, const TJ *__restrict__ Jn) {
                     if (c & (1 << a)) off += P->jstride[a];
                 v[c] = ldj<T, TJ>(Jn, off);
             }
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-#pragma unroll
-                for (int j = 0; j < (1 << (D - 1 - a)); ++j)
-                    v[j] = fma_t<T>(tw[a], (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
-            }
+            HJB_LERP_AXES(T, D, v, a, 0, D, tw[a])
             static_cast<T *>(pr.j_interp)[b] = v[0];
         }
     }

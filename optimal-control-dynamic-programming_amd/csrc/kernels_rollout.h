@@ -16,7 +16,7 @@
 // hjb_rollout_create, so no read leaves u_table.  Offsets are int64 throughout; stores are plain, trajectory index fastest.
 #pragma once
 #include "hjbdp_dev.h"
-#include "kernels_generic.h"
+#include "hjbdp_canon.h"
 
 namespace hjb {
 

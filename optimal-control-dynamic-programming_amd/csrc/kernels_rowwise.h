@@ -14,7 +14,7 @@
 #pragma once
 #include <type_traits>
 #include "hjbdp_dev.h"
-#include "kernels_generic.h"
+#include "hjbdp_canon.h"
 #include "kernels_tabled.h"
 
 namespace hjb {
@@ -97,10 +97,7 @@ k_backup_rowwise(const DParams *__restrict__ P, const DTabled *__restrict__ TB, 
         }
         int cjz[HJB_MAX_C] = {0, 0, 0};
         T gpre = (T)0;
-        for (int k = 0; k < P->n_cost_prefix; ++k) {
-            const T x = term_value<T, D>(P->cost[k], si, cjz);
-            gpre = (k == 0) ? x : (T)(gpre + x);
-        }
+        HJB_TERM_SUM(T, gpre, k, 0, P->n_cost_prefix, term_value<T, D>(P->cost[k], si, cjz))
         T best = (T)0;
         int best_u = 0;
         int cj[HJB_MAX_C] = {0, 0, 0};
@@ -117,10 +114,7 @@ k_backup_rowwise(const DParams *__restrict__ P, const DTabled *__restrict__ TB, 
                 // from it (row bases, the weights' operand) is scalar arithmetic
                 int cl = __builtin_amdgcn_readfirstlane(as_const<TabEntry<T>>(A.tab)[off].cell);
                 tr[a - 1] = uniform_value(as_const<TabEntry<T>>(A.tab)[off].t);
-                if (a == D - 1) {
-                    cl -= plane0;
-                    if (cl < 0 || cl + 1 >= nplanes) { bad = true; cl = cl < 0 ? 0 : nplanes - 2; }
-                }
+                if (a == D - 1) { HJB_PLANE_CLAMP(cl, plane0, nplanes, bad = true) }
                 rb0 += js[a] * cl;
             }
             if (bad) *P->status = 1;
@@ -144,48 +138,20 @@ k_backup_rowwise(const DParams *__restrict__ P, const DTabled *__restrict__ TB, 
                 v[2 * c + 1] = (T)rowp[c0 + 1u];
             }
             // ---- lerps, canonical order: axis 0 (per-lane weight), then axes 1.. (scalar weights) ----
-#pragma unroll
-            for (int j = 0; j < NR; ++j) v[j] = fma_t<T>(t0, (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
-#pragma unroll
-            for (int a = 1; a < D; ++a) {
-#pragma unroll
-                for (int j = 0; j < (1 << (D - 1 - a)); ++j)
-                    v[j] = fma_t<T>(tr[a - 1], (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
-            }
+            HJB_LERP_AXIS(T, v, NR, t0);
+            HJB_LERP_AXES(T, D, v, a, 1, D, tr[a - 1])
             T g = gpre;
-            for (int k = P->n_cost_prefix; k < P->n_cost; ++k) {
-                const T x = term_value<T, D>(P->cost[k], si, cj);
-                g = (k == 0) ? x : (T)(g + x);
-            }
+            HJB_TERM_SUM(T, g, k, P->n_cost_prefix, P->n_cost, term_value<T, D>(P->cost[k], si, cj))
             const T tot = (T)(g + v[0]);
             if (u == 0 || tot < best) {
                 best = tot;
                 best_u = u;
             }
-            if (C == 1) {
-                ++cj[0];
-            } else if (C == 2) {
-                if (++cj[1] == m1) { cj[1] = 0; ++cj[0]; }
-            } else {
-                if (++cj[2] == m2) {
-                    cj[2] = 0;
-                    if (++cj[1] == m1) { cj[1] = 0; ++cj[0]; }
-                }
-            }
+            HJB_NEXT_CONTROL(C, cj, m1, m2)
         }
         if (valid) {
             int64_t label;
-            if (C == 1) {
-                label = best_u;
-            } else if (C == 2) {
-                const int j1 = best_u % m1, j0 = best_u / m1;
-                label = j0 + (int64_t)P->m[0] * j1;
-            } else {
-                const int j2 = best_u % m2;
-                const int rr = best_u / m2;
-                const int j1 = rr % m1, j0 = rr / m1;
-                label = j0 + (int64_t)P->m[0] * (j1 + (int64_t)m1 * j2);
-            }
+            HJB_LABEL(label, int, int64_t, C, best_u, P->m[0], m1, m2)
             int64_t ls = 0, mul = 1, lj = 0;
 #pragma unroll
             for (int a = 0; a < D; ++a) {
@@ -258,15 +224,7 @@ k_backup_rowlean(const DParams *__restrict__ P, const DTabled *__restrict__ TB, 
     uint32_t js[D];
 #pragma unroll
     for (int a = 0; a < D; ++a) js[a] = (uint32_t)P->jstride[a];
-    uint32_t delta[NR];                                             // corner-row offsets (uniform)
-#pragma unroll
-    for (int c = 0; c < NR; ++c) {
-        uint32_t d = 0;
-#pragma unroll
-        for (int a = 1; a < D; ++a)
-            if (c & (1 << (a - 1))) d += js[a];
-        delta[c] = d;
-    }
+    HJB_PAIR_OFFSETS(uint32_t, NR, D, delta, js)                    // corner-row offsets (uniform)
     const int my_cj[3] = {lane < nU ? s_cj[3 * lane] : 0, lane < nU ? s_cj[3 * lane + 1] : 0, lane < nU ? s_cj[3 * lane + 2] : 0};
 
     for (uint32_t item = xcd_share(blockIdx.x, gridDim.x) * 4u + wave; item < items; item += wstride) {      // (XCD-aware: kernels_tabled.h)
@@ -295,10 +253,7 @@ k_backup_rowlean(const DParams *__restrict__ P, const DTabled *__restrict__ TB, 
         const T t0 = as_global<TabEntry<T>>(TB->ax[0].tab)[aoff0].t;
         int cjz[HJB_MAX_C] = {0, 0, 0};
         T gpre = (T)0;
-        for (int k = 0; k < P->n_cost_prefix; ++k) {
-            const T x = term_value<T, D>(P->cost[k], si, cjz);
-            gpre = (k == 0) ? x : (T)(gpre + x);
-        }
+        HJB_TERM_SUM(T, gpre, k, 0, P->n_cost_prefix, term_value<T, D>(P->cost[k], si, cjz))
         // ---- phase A: lane u prepares control u ------------------------------------------------------
         if (lane < nU) {
             uint32_t rb = 0;
@@ -311,10 +266,7 @@ k_backup_rowlean(const DParams *__restrict__ P, const DTabled *__restrict__ TB, 
                 for (int d = 1; d < D; ++d) off += A.sstride[d] * sl[d];
                 int cl = as_global<TabEntry<T>>(A.tab)[off].cell;
                 s_tw[lane * DR + (a - 1)] = as_global<TabEntry<T>>(A.tab)[off].t;
-                if (a == D - 1) {
-                    cl -= plane0;
-                    if (cl < 0 || cl + 1 >= nplanes) { bad = true; cl = cl < 0 ? 0 : nplanes - 2; }
-                }
+                if (a == D - 1) { HJB_PLANE_CLAMP(cl, plane0, nplanes, bad = true) }
                 rb += js[a] * (uint32_t)cl;
             }
             if (bad) *P->status = 1;
@@ -347,14 +299,11 @@ k_backup_rowlean(const DParams *__restrict__ P, const DTabled *__restrict__ TB, 
             }
             // (packing these lerps two rows per v_pk_fma_f32 was measured slower: 7.3 vs 6.8 ms on C4 - the loaded
             // corners land in unrelated registers and have to be moved into pairs first)
-#pragma unroll
-            for (int j = 0; j < NR; ++j) v[j] = fma_t<T>(t0, (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
+            HJB_LERP_AXIS(T, v, NR, t0);
 #pragma unroll
             for (int a = 1; a < D; ++a) {
                 const T ta = s_tw[u * DR + (a - 1)];
-#pragma unroll
-                for (int j = 0; j < (1 << (D - 1 - a)); ++j)
-                    v[j] = fma_t<T>(ta, (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
+                HJB_LERP_AXIS(T, v, 1 << (D - 1 - a), ta);
             }
             const T interp = v[0];
             T g = gpre;
@@ -363,7 +312,7 @@ k_backup_rowlean(const DParams *__restrict__ P, const DTabled *__restrict__ TB, 
             } else {
                 for (int k = 0; k < ncu; ++k) {
                     const T x = s_cu[u * kLeanMaxCu + k];
-                    g = (!has_prefix && k == 0) ? x : (T)(g + x);
+                    HJB_TERM_ADD(T, g, !has_prefix && k == 0, x);
                 }
             }
             const T tot = (T)(g + interp);
@@ -375,7 +324,7 @@ k_backup_rowlean(const DParams *__restrict__ P, const DTabled *__restrict__ TB, 
         __builtin_amdgcn_wave_barrier();
         if (valid) {
             const int j0 = s_cj[3 * best_u], j1 = s_cj[3 * best_u + 1], j2 = s_cj[3 * best_u + 2];
-            const int label = C == 1 ? j0 : (C == 2 ? j0 + P->m[0] * j1 : j0 + P->m[0] * (j1 + P->m[1] * j2));
+            const int label = C == 1 ? j0 : (C == 2 ? HJB_LABEL_2(int, j0, j1, P->m[0]) : HJB_LABEL_3(int, j0, j1, j2, P->m[0], P->m[1]));
             uint32_t ls = 0, mul = 1, lj = 0;
 #pragma unroll
             for (int a = 0; a < D; ++a) {

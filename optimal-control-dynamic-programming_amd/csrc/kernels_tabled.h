@@ -11,29 +11,11 @@
 #pragma once
 #include "hjbdp_dev.h"
 #include "hjbdp_walk.h"          // xcd_share
-#include "kernels_generic.h"
+#include "hjbdp_canon.h"
 
 namespace hjb {
 
 template <typename T> struct TabEntry { int32_t cell; T t; };   // float: 8 B, double: 16 B
-
-// The two axis-0 neighbours of a corner in ONE load: axis 0 is contiguous in every J layout of this library (DParams::jstride[0] == 1),
-// so corners 2c and 2c + 1 sit side by side - an 8-byte (float32), 4-byte (binary16) or 16-byte (float64) load at element alignment.
-typedef float tab_f2u __attribute__((ext_vector_type(2), aligned(4)));
-typedef _Float16 tab_h2u __attribute__((ext_vector_type(2), aligned(2)));
-typedef double tab_d2u __attribute__((ext_vector_type(2), aligned(8)));
-__device__ __forceinline__ void tab_load_pair(const float *__restrict__ Jn, int64_t off, float &a, float &b) {
-    const tab_f2u p = *reinterpret_cast<const tab_f2u *>(Jn + off);
-    a = p.x; b = p.y;
-}
-__device__ __forceinline__ void tab_load_pair(const _Float16 *__restrict__ Jn, int64_t off, float &a, float &b) {
-    const tab_h2u p = *reinterpret_cast<const tab_h2u *>(Jn + off);
-    a = (float)p.x; b = (float)p.y;
-}
-__device__ __forceinline__ void tab_load_pair(const double *__restrict__ Jn, int64_t off, double &a, double &b) {
-    const tab_d2u p = *reinterpret_cast<const tab_d2u *>(Jn + off);
-    a = p.x; b = p.y;
-}
 
 struct DTabled {
     struct Axis {
@@ -70,15 +52,10 @@ k_prep_axis_table_t(const DParams *__restrict__ P, int a, const int32_t *__restr
         }
         si[D - 1] += P->slab_begin;
         T q = (T)0;
-        for (int k = 0; k < ax.n_terms; ++k) {
-            T x = term_value<T, D>(ax.t[k], si, cj);
-            q = (k == 0) ? x : (T)(q + x);
-        }
-        const T *kk = static_cast<const T *>(ax.knots);
-        const int cell = find_cell<T>(kk, ax.n, q, ax.uniform, (T)ax.x0, (T)ax.inv_h);
+        HJB_TERM_SUM(T, q, k, 0, ax.n_terms, term_value<T, D>(ax.t[k], si, cj))
         TabEntry<T> ent;
-        ent.cell = cell;
-        ent.t = (T)((T)(q - kk[cell]) * static_cast<const T *>(ax.rdx)[cell]);
+        const T *kk = static_cast<const T *>(ax.knots);
+        HJB_LOCATE(T, ax, kk, static_cast<const T *>(ax.rdx), q, ent.cell, ent.t, (T));
         out[e] = ent;
     }
 }
@@ -95,17 +72,7 @@ k_backup_tabled(const DParams *__restrict__ P, const DTabled *__restrict__ TB, c
          ls += (int64_t)gridDim.x * blockDim.x) {
         int si[D];          // global indices (cost term tables)
         int sl[D];          // local index along the last axis (axis tables cover owned planes)
-        {
-            int64_t r = ls;
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-                int na = P->n[a];
-                si[a] = (int)(r % na);
-                sl[a] = si[a];
-                r /= na;
-            }
-            si[D - 1] += P->slab_begin;
-        }
+        HJB_STATE_INDEX(D, P, ls, si, a, sl[a] = si[a])
         int cj[HJB_MAX_C] = {0, 0, 0};
         int64_t aoff[D];
         int cell[D];
@@ -122,10 +89,7 @@ k_backup_tabled(const DParams *__restrict__ P, const DTabled *__restrict__ TB, c
                 const TabEntry<T> e = static_cast<const TabEntry<T> *>(A.tab)[off];
                 cell[a] = e.cell;
                 tw[a] = e.t;
-                if (a == D - 1) {
-                    cell[a] -= plane0;
-                    if (cell[a] < 0 || cell[a] + 1 >= nplanes) { bad0 = true; cell[a] = cell[a] < 0 ? 0 : nplanes - 2; }
-                }
+                if (a == D - 1) { HJB_PLANE_CLAMP(cell[a], plane0, nplanes, bad0 = true) }
             }
         }
         if (bad0) *P->status = 1;
@@ -133,15 +97,9 @@ k_backup_tabled(const DParams *__restrict__ P, const DTabled *__restrict__ TB, c
         double gpre64 = 0.0;                     // cost_dtype F64: the state part of the cost in double (Solver_pos_att.m:800)
         const bool c64 = P->cost_f64 != 0;
         if (c64) {
-            for (int k = 0; k < P->n_cost_prefix; ++k) {
-                const double x = term_value<double, D>(P->cost64[k], si, cj);
-                gpre64 = (k == 0) ? x : gpre64 + x;
-            }
+            HJB_TERM_SUM(double, gpre64, k, 0, P->n_cost_prefix, term_value<double, D>(P->cost64[k], si, cj))
         } else {
-            for (int k = 0; k < P->n_cost_prefix; ++k) {
-                T x = term_value<T, D>(P->cost[k], si, cj);
-                gpre = (k == 0) ? x : (T)(gpre + x);
-            }
+            HJB_TERM_SUM(T, gpre, k, 0, P->n_cost_prefix, term_value<T, D>(P->cost[k], si, cj))
         }
         T best = (T)0;
         int64_t best_u = 0;
@@ -157,10 +115,7 @@ k_backup_tabled(const DParams *__restrict__ P, const DTabled *__restrict__ TB, c
                     const TabEntry<T> e = static_cast<const TabEntry<T> *>(A.tab)[off];
                     int cl = e.cell;
                     tw[a] = e.t;
-                    if (a == D - 1) {
-                        cl -= plane0;
-                        if (cl < 0 || cl + 1 >= nplanes) { *P->status = 1; cl = cl < 0 ? 0 : nplanes - 2; }
-                    }
+                    if (a == D - 1) { HJB_PLANE_CLAMP(cl, plane0, nplanes, *P->status = 1) }
                     cell[a] = cl;
                 }
                 base += P->jstride[a] * cell[a];
@@ -174,54 +129,24 @@ k_backup_tabled(const DParams *__restrict__ P, const DTabled *__restrict__ TB, c
                     if (c & (1 << a)) off += P->jstride[a];
                 v[c] = ldj<T, TJ>(Jn, off);
             }
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-#pragma unroll
-                for (int j = 0; j < (1 << (D - 1 - a)); ++j)
-                    v[j] = fma_t<T>(tw[a], (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
-            }
+            HJB_LERP_AXES(T, D, v, a, 0, D, tw[a])
             T g = gpre;
             if (c64) {                           // the control part added in double, ONE rounding to the arithmetic type
                 double g64 = gpre64;
-                for (int k = P->n_cost_prefix; k < P->n_cost; ++k) {
-                    const double x = term_value<double, D>(P->cost64[k], si, cj);
-                    g64 = (k == 0) ? x : g64 + x;
-                }
+                HJB_TERM_SUM(double, g64, k, P->n_cost_prefix, P->n_cost, term_value<double, D>(P->cost64[k], si, cj))
                 g = (T)g64;
             } else {
-                for (int k = P->n_cost_prefix; k < P->n_cost; ++k) {
-                    T x = term_value<T, D>(P->cost[k], si, cj);
-                    g = (k == 0) ? x : (T)(g + x);
-                }
+                HJB_TERM_SUM(T, g, k, P->n_cost_prefix, P->n_cost, term_value<T, D>(P->cost[k], si, cj))
             }
             const T tot = (T)(g + v[0]);
             if (u == 0 || tot < best) {
                 best = tot;
                 best_u = u;
             }
-            if (C == 1) {
-                ++cj[0];
-            } else if (C == 2) {
-                if (++cj[1] == P->m[1]) { cj[1] = 0; ++cj[0]; }
-            } else {
-                if (++cj[2] == P->m[2]) {
-                    cj[2] = 0;
-                    if (++cj[1] == P->m[1]) { cj[1] = 0; ++cj[0]; }
-                }
-            }
+            HJB_NEXT_CONTROL(C, cj, P->m[1], P->m[2])
         }
         int64_t label;
-        if (C == 1) {
-            label = best_u;
-        } else if (C == 2) {
-            int64_t j1 = best_u % P->m[1], j0 = best_u / P->m[1];
-            label = j0 + (int64_t)P->m[0] * j1;
-        } else {
-            int64_t j2 = best_u % P->m[2];
-            int64_t rr = best_u / P->m[2];
-            int64_t j1 = rr % P->m[1], j0 = rr / P->m[1];
-            label = j0 + (int64_t)P->m[0] * (j1 + (int64_t)P->m[1] * j2);
-        }
+        HJB_LABEL(label, int64_t, int64_t, C, best_u, P->m[0], P->m[1], P->m[2])
         const int64_t in_plane = ls % P->inner, pl = ls / P->inner;
         stj<T, TJ>(Jout, in_plane + P->inner * (pl + P->halo_lo), best);
         if (idx_out) st_idx(idx_out, ls, (int32_t)(label + P->index_base), P->idx_bytes);
@@ -285,15 +210,7 @@ __device__ __forceinline__ void tabled32_body(const DParams *__restrict__ P, con
     int js[D];
 #pragma unroll
     for (int a = 0; a < D; ++a) js[a] = a == 0 ? 1 : (int)P->jstride[a];
-    int poff[1 << (D > 1 ? D - 1 : 0)];                             // element offset of corner pair p inside a cell (axes 1 .. D-1)
-#pragma unroll
-    for (int p = 0; p < (1 << (D > 1 ? D - 1 : 0)); ++p) {
-        int o = 0;
-#pragma unroll
-        for (int a = 1; a < D; ++a)
-            if (p & (1 << (a - 1))) o += js[a];
-        poff[p] = o;
-    }
+    HJB_PAIR_OFFSETS(int, 1 << (D > 1 ? D - 1 : 0), D, poff, js)
     const int m1 = P->m[1], m2 = P->m[2];
     for (int ls = (int)(xcd_share(bx, gx) * blockDim.x + threadIdx.x); ls < n_owned; ls += (int)(gx * blockDim.x)) {
         int si[D], sl[D];
@@ -322,10 +239,7 @@ __device__ __forceinline__ void tabled32_body(const DParams *__restrict__ P, con
             if (!A.has_ctrl) {
                 cell[a] = as_global<TabEntry<T>>(A.tab)[off].cell;
                 tw[a] = as_global<TabEntry<T>>(A.tab)[off].t;
-                if (a == D - 1) {
-                    cell[a] -= plane0;
-                    if (cell[a] < 0 || cell[a] + 1 >= nplanes) { bad0 = true; cell[a] = cell[a] < 0 ? 0 : nplanes - 2; }
-                }
+                if (a == D - 1) { HJB_PLANE_CLAMP(cell[a], plane0, nplanes, bad0 = true) }
             }
         }
         if (bad0) *P->status = 1;
@@ -333,15 +247,9 @@ __device__ __forceinline__ void tabled32_body(const DParams *__restrict__ P, con
         T gpre = (T)0;
         double gpre64 = 0.0;
         if (c64) {
-            for (int k = 0; k < npre; ++k) {
-                const double x = as_global<double>(P->cost64[k].data)[tab32_state_off<double, D>(P->cost64[k], si)];
-                gpre64 = (k == 0) ? x : gpre64 + x;
-            }
+            HJB_TERM_SUM(double, gpre64, k, 0, npre, as_global<double>(P->cost64[k].data)[tab32_state_off<double, D>(P->cost64[k], si)])
         } else {
-            for (int k = 0; k < npre; ++k) {
-                const T x = as_global<T>(P->cost[k].data)[tab32_state_off<T, D>(P->cost[k], si)];
-                gpre = (k == 0) ? x : (T)(gpre + x);
-            }
+            HJB_TERM_SUM(T, gpre, k, 0, npre, as_global<T>(P->cost[k].data)[tab32_state_off<T, D>(P->cost[k], si)])
         }
         int ct_off[kTab32MaxCt];                                    // state part of the control-dependent cost terms' offsets
 #pragma unroll
@@ -371,10 +279,7 @@ __device__ __forceinline__ void tabled32_body(const DParams *__restrict__ P, con
                 if (A.has_ctrl) {
                     int cl = nx_cell[a];
                     tw[a] = nx_t[a];
-                    if (a == D - 1) {
-                        cl -= plane0;
-                        if (cl < 0 || cl + 1 >= nplanes) { *P->status = 1; cl = cl < 0 ? 0 : nplanes - 2; }
-                    }
+                    if (a == D - 1) { HJB_PLANE_CLAMP(cl, plane0, nplanes, *P->status = 1) }
                     cell[a] = cl;
                 }
                 base += js[a] * cell[a];
@@ -383,16 +288,7 @@ __device__ __forceinline__ void tabled32_body(const DParams *__restrict__ P, con
 #pragma unroll
             for (int p = 0; p < (1 << (D > 1 ? D - 1 : 0)); ++p) tab_load_pair(Jn, (int64_t)(base + poff[p]), v[2 * p], v[2 * p + 1]);
             int cjn[HJB_MAX_C] = {cj[0], cj[1], cj[2]};
-            if (C == 1) {
-                ++cjn[0];
-            } else if (C == 2) {
-                if (++cjn[1] == m1) { cjn[1] = 0; ++cjn[0]; }
-            } else {
-                if (++cjn[2] == m2) {
-                    cjn[2] = 0;
-                    if (++cjn[1] == m1) { cjn[1] = 0; ++cjn[0]; }
-                }
-            }
+            HJB_NEXT_CONTROL(C, cjn, m1, m2)
             if (u + 1 < nU) fetch32(cjn);
             T g = gpre;
             if (c64) {                           // the control part added in double, ONE rounding to the arithmetic type
@@ -403,13 +299,10 @@ __device__ __forceinline__ void tabled32_body(const DParams *__restrict__ P, con
                         if (k < nct) {
                             const DTerm &t = P->cost64[npre + k];
                             const double x = as_global<double>(t.data)[ct_off[k] + tab32_ctrl_off(t.stride + D, cj)];
-                            g64 = (npre + k == 0) ? x : g64 + x;
+                            HJB_TERM_ADD(double, g64, npre + k == 0, x);
                         }
                 } else {
-                    for (int k = npre; k < ncost; ++k) {
-                        const double x = term_value<double, D>(P->cost64[k], si, cj);
-                        g64 = (k == 0) ? x : g64 + x;
-                    }
+                    HJB_TERM_SUM(double, g64, k, npre, ncost, term_value<double, D>(P->cost64[k], si, cj))
                 }
                 g = (T)g64;
             } else if (hoist) {
@@ -418,20 +311,12 @@ __device__ __forceinline__ void tabled32_body(const DParams *__restrict__ P, con
                     if (k < nct) {
                         const DTerm &t = P->cost[npre + k];
                         const T x = as_global<T>(t.data)[ct_off[k] + tab32_ctrl_off(t.stride + D, cj)];
-                        g = (npre + k == 0) ? x : (T)(g + x);
+                        HJB_TERM_ADD(T, g, npre + k == 0, x);
                     }
             } else {
-                for (int k = npre; k < ncost; ++k) {
-                    const T x = term_value<T, D>(P->cost[k], si, cj);
-                    g = (k == 0) ? x : (T)(g + x);
-                }
+                HJB_TERM_SUM(T, g, k, npre, ncost, term_value<T, D>(P->cost[k], si, cj))
             }
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-#pragma unroll
-                for (int j = 0; j < (1 << (D - 1 - a)); ++j)
-                    v[j] = fma_t<T>(tw[a], (T)(v[2 * j + 1] - v[2 * j]), v[2 * j]);
-            }
+            HJB_LERP_AXES(T, D, v, a, 0, D, tw[a])
             const T tot = (T)(g + v[0]);
             if (u == 0 || tot < best) {
                 best = tot;
@@ -440,17 +325,7 @@ __device__ __forceinline__ void tabled32_body(const DParams *__restrict__ P, con
             cj[0] = cjn[0]; cj[1] = cjn[1]; cj[2] = cjn[2];
         }
         int label;
-        if (C == 1) {
-            label = best_u;
-        } else if (C == 2) {
-            const int j1 = best_u % m1, j0 = best_u / m1;
-            label = j0 + P->m[0] * j1;
-        } else {
-            const int j2 = best_u % m2;
-            const int rr = best_u / m2;
-            const int j1 = rr % m1, j0 = rr / m1;
-            label = j0 + P->m[0] * (j1 + m1 * j2);
-        }
+        HJB_LABEL(label, int, int, C, best_u, P->m[0], m1, m2)
         const uint32_t inner = (uint32_t)P->inner;
         const uint32_t pl = (uint32_t)ls / inner, in_plane = (uint32_t)ls - pl * inner;
         stj<T, TJ>(Jout, (int64_t)(in_plane + inner * (pl + (uint32_t)P->halo_lo)), best);

@@ -13,7 +13,7 @@
 // one below.  Stage-invariant (cell, t) come from the variant-5 tables; cost terms are evaluated as written.
 #pragma once
 #include "hjbdp_dev.h"
-#include "kernels_generic.h"
+#include "hjbdp_canon.h"
 #include "kernels_tabled.h"
 
 namespace hjb {
@@ -68,10 +68,7 @@ k_tile2d_plan(const DParams *__restrict__ P, const DTabled *__restrict__ TB, Til
         pl.w0 = tab0[o0].t;
         pl.w1 = tab1[o1].t;
         T g = (T)0;
-        for (int k = 0; k < P->n_cost; ++k) {                    // left to right, like every other kernel
-            const T x = term_value<T, 2>(P->cost[k], si, cj);
-            g = (k == 0) ? x : (T)(g + x);
-        }
+        HJB_TERM_SUM(T, g, k, 0, P->n_cost, term_value<T, 2>(P->cost[k], si, cj))
         pl.g = g;
         plan[e] = pl;
     }
@@ -193,10 +190,7 @@ k_backup_tile2d(const DParams *__restrict__ P, const DTabled *__restrict__ TB, c
             const int off1 = A1.sstride[0] * gx + A1.sstride[1] * gy;
             int cj[HJB_MAX_C] = {0, 0, 0};
             T gpre = (T)0;
-            for (int k = 0; k < P->n_cost_prefix; ++k) {
-                const T x = term_value<T, 2>(P->cost[k], si, cj);
-                gpre = (k == 0) ? x : (T)(gpre + x);
-            }
+            HJB_TERM_SUM(T, gpre, k, 0, P->n_cost_prefix, term_value<T, 2>(P->cost[k], si, cj))
             T best = (T)0;
             int best_u = 0;
             for (int u = 0; u < nU; ++u) {
@@ -210,25 +204,13 @@ k_backup_tile2d(const DParams *__restrict__ P, const DTabled *__restrict__ TB, c
                 const T b = fma_t<T>(t0, (T)(v11 - v01), v01);
                 const T r = fma_t<T>(t1, (T)(b - a), a);
                 T g = gpre;
-                for (int k = P->n_cost_prefix; k < P->n_cost; ++k) {
-                    const T x = term_value<T, 2>(P->cost[k], si, cj);
-                    g = (k == 0) ? x : (T)(g + x);
-                }
+                HJB_TERM_SUM(T, g, k, P->n_cost_prefix, P->n_cost, term_value<T, 2>(P->cost[k], si, cj))
                 const T tot = (T)(g + r);
                 if (u == 0 || tot < best) {
                     best = tot;
                     best_u = u;
                 }
-                if (C == 1) {
-                    ++cj[0];
-                } else if (C == 2) {
-                    if (++cj[1] == m1) { cj[1] = 0; ++cj[0]; }
-                } else {
-                    if (++cj[2] == m2) {
-                        cj[2] = 0;
-                        if (++cj[1] == m1) { cj[1] = 0; ++cj[0]; }
-                    }
-                }
+                HJB_NEXT_CONTROL(C, cj, m1, m2)
             }
             const T stored = (T)(TJ)best;                    // what a one-stage launch would have left in memory
             dst[(gy - py0) * kPatchX + (gx - px0)] = stored;
@@ -236,17 +218,7 @@ k_backup_tile2d(const DParams *__restrict__ P, const DTabled *__restrict__ TB, c
                 Jout[gx + (int64_t)n0 * gy] = (TJ)best;
                 if (idx_out) {
                     int64_t label;
-                    if (C == 1) {
-                        label = best_u;
-                    } else if (C == 2) {
-                        const int j1 = best_u % m1, j0 = best_u / m1;
-                        label = j0 + (int64_t)P->m[0] * j1;
-                    } else {
-                        const int j2 = best_u % m2;
-                        const int rr = best_u / m2;
-                        const int j1 = rr % m1, j0 = rr / m1;
-                        label = j0 + (int64_t)P->m[0] * (j1 + (int64_t)m1 * j2);
-                    }
+                    HJB_LABEL(label, int, int64_t, C, best_u, P->m[0], m1, m2)
                     st_idx(idx_out, gx + (int64_t)n0 * gy, (int32_t)(label + P->index_base), P->idx_bytes);
                 }
             }

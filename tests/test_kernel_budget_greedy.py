@@ -1,6 +1,6 @@
 """CPU test: the greedy rollout kernel's register budget (K26, csrc/kernels_rollout_greedy.h), read from the code object hipcc
 produces here for gfx950 (no GPU).  The kernel reads its model through the argument segment, per step and from D = 3 on per loop body, so that no
-scalar is spilled (csrc/hjbdp_greedy.h, greedy_reread); the corners of a candidate are read in groups, so that no instantiation
+scalar is spilled (csrc/hjbdp_greedy.h, greedy_reread_in_loop); the corners of a candidate are read in groups, so that no instantiation
 holds 2^D values.  Both come down to: every one of the 24 instantiations (D x value type x LDS) has no vector spill, no scalar
 spill and no private segment."""
 import re

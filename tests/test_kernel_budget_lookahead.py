@@ -1,6 +1,6 @@
 """CPU test: the lookahead rollout kernel's register budget (K27, csrc/kernels_rollout_lookahead.h), read from the code objects
 hipcc produces here for gfx950 (no GPU).  The node loop sits inside the candidate loop inside the step loop; the kernel reads its
-argument record through the argument segment per loop body (csrc/hjbdp_greedy.h, greedy_reread) and the lookahead node block
+argument record through the argument segment per loop body (csrc/hjbdp_greedy.h, greedy_reread_in_loop) and the lookahead node block
 through scalar loads, so that no scalar is spilled, and reads a candidate's corners in K26's groups, so that no instantiation
 holds 2^D values.  Every one of the 48 instantiations (D x value type x LDS x FLY) has no vector spill, no scalar spill and no
 private segment, and at most 128 vector registers (four waves per SIMD at 256 threads a block) - except the eight D = 6
