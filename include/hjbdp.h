@@ -518,7 +518,9 @@ int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_tr
  * is NaN or negative.
  * The campaign of the lookahead controller is hjb_rollout_run_lookahead_campaign (kernel K29, below): the same statistics on the
  * same streams; csrc/hjbdp_campaign.h serves both.
- * Out of scope: quantiles and histograms, campaigns of the integrated plants. */
+ * The histogram of a start's costs beside these statistics, and the quantiles it gives: hjb_rollout_run_campaign_hist (kernel
+ * K30, below).
+ * Out of scope: campaigns of the integrated plants. */
 #define HJB_CAMPAIGN_NSTAT 8
 int32_t hjb_rollout_run_campaign(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts,
                                  int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream, const double *threshold,
@@ -651,8 +653,8 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
  * hjb_rollout_run_lookahead refuses with fly_noise = 1 (n_starts in the place of n_traj; no lookahead set; no noise set; another
  * model set; a plane outside the value planes); null stats; n_samples < 1; n_starts * n_samples or first_stream + n_starts *
  * n_samples overflowing int64; a threshold entry that is NaN; a tol entry that is NaN or negative.  n_starts = 0 is HJB_OK.
- * Out of scope: quantiles and histograms, a paired-difference statistic computed on the device, sharing the first step's lookahead
- * among a start's samples, campaigns of the integrated plants, float16 value planes. */
+ * Out of scope: a paired-difference statistic computed on the device, sharing the first step's lookahead among a start's samples,
+ * campaigns of the integrated plants, float16 value planes. */
 int32_t hjb_rollout_run_lookahead_campaign(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
                                            int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
                                            const double *threshold, const double *tol, double *stats, double *device_ms);
@@ -664,6 +666,41 @@ int32_t hjb_rollout_lookahead_campaign_host(int32_t D, const int32_t *n, const d
                                             const double *flight_weights, int64_t n_starts, int64_t n_samples, const double *X0,
                                             uint64_t seed, int64_t first_stream, const double *threshold, const double *tol,
                                             double *stats);
+
+/* ---- campaign cost histograms: a per-start fixed-bin histogram of the costs beside the statistics (kernel K30) -----------------
+ * hjb_rollout_run_campaign_hist and hjb_rollout_run_lookahead_campaign_hist are hjb_rollout_run_campaign and
+ * hjb_rollout_run_lookahead_campaign - their arguments, their trajectories, their streams, and stats bit for bit theirs - with a
+ * histogram of every start's n_samples (M) costs.  No array has a dimension of n_starts * M.
+ * Inputs.  n_bins in 1..HJB_CAMPAIGN_MAX_BINS; lo [n_starts] and hi [n_starts], both finite, lo[s] < hi[s].
+ * Scale.  scale_s = (double)n_bins / (hi[s] - lo[s]); it must be finite.
+ * The bin of a sample with cost c (csrc/hjbdp_campaign.h, campaign_bin: one function serves the kernels and the host reduce):
+ *   c < lo        record index 0 (underflow);
+ *   !(c < hi)     record index n_bins + 1 (overflow); a NaN lands here;
+ *   otherwise     b = (c - lo) * scale, the difference and the product each rounded; the index is 1 + min(n_bins - 1, (int)b).
+ * Output.  hist [n_bins + 2, n_starts] column-major, int64 counts; every column sums to n_samples.  Padding slots and lanes past
+ *   a launch's last block count nothing.  Option "chunk" changes no count; for the lookahead campaign option "lds" changes none either.
+ * Why atomics are allowed here: the eight statistics keep their fixed floating-point order.  Integer addition commutes, so integer
+ *   atomics do not break K28's rule: the result is a function of (M, the samples) alone.  The doubles are never accumulated so.
+ * Two passes give an exact range: the streams are counter-based, so a plain campaign's min and max of a start are the min and the
+ *   max of the samples a histogram call with the same seed, first_stream and n_samples bins; lo = min, hi = nextafter(max, +inf)
+ *   leaves the underflow and the overflow empty.
+ * Device memory of a call: the plain campaign's plus [3, n_starts] doubles and hist itself, zeroed once per call on the call's
+ *   stream and accumulated across launches.
+ * hjb_rollout_campaign_hist_reduce is the CPU twin with no device, on a cost array such as hjb_rollout_run_noisy returns: cost
+ *   [n_starts*M], trajectory s*M + m sample m of start s.
+ * Refused before any device work, outputs untouched - HJB_E_INVALID: everything the plain call refuses; n_bins out of range; with
+ * n_starts > 0 a null lo, hi or hist; a lo or hi that is not finite; !(lo < hi); a scale that is not finite.  n_starts = 0 is HJB_OK. */
+#define HJB_CAMPAIGN_MAX_BINS 256
+int32_t hjb_rollout_run_campaign_hist(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts,
+                                      int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream, const double *threshold,
+                                      const double *tol, const double *lo, const double *hi, int32_t n_bins, double *stats, int64_t *hist,
+                                      double *device_ms);
+int32_t hjb_rollout_run_lookahead_campaign_hist(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
+                                                int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
+                                                const double *threshold, const double *tol, const double *lo, const double *hi,
+                                                int32_t n_bins, double *stats, int64_t *hist, double *device_ms);
+int32_t hjb_rollout_campaign_hist_reduce(int64_t n_starts, int64_t n_samples, const double *cost, const double *lo, const double *hi,
+                                         int32_t n_bins, int64_t *hist);
 
 /* The 6-D attitude closed loop (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run) on the same object.
  * hjb_rollout_set_attitude_model and hjb_rollout_set_model replace each other: the last one set wins.  It needs D == 6, n_u == 3

@@ -160,6 +160,21 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
 int32_t hjb_rollout_run_lookahead_campaign(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
                                            int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
                                            const double *threshold, const double *tol, double *stats, double *device_ms);
+/* both campaigns with a histogram of every start's costs beside the statistics (kernel K30): n_bins (1..256) equal bins between
+ * lo [n_starts] and hi [n_starts], hist [n_bins + 2, n_starts] int64 (underflow, the bins, overflow), stats the plain call's bits;
+ * two calls on one seed - a plain campaign for min and max, then this with lo = min, hi = the next double above max - give every
+ * start an exact range (hjbdp.h); the host twin of the binning needs no device; usage:
+ * matlab/Dynamic_Solver_hjbdp_noisy_cost_quantile_map.m */
+int32_t hjb_rollout_run_campaign_hist(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts,
+                                      int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream, const double *threshold,
+                                      const double *tol, const double *lo, const double *hi, int32_t n_bins, double *stats, int64_t *hist,
+                                      double *device_ms);
+int32_t hjb_rollout_run_lookahead_campaign_hist(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
+                                                int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
+                                                const double *threshold, const double *tol, const double *lo, const double *hi,
+                                                int32_t n_bins, double *stats, int64_t *hist, double *device_ms);
+int32_t hjb_rollout_campaign_hist_reduce(int64_t n_starts, int64_t n_samples, const double *cost, const double *lo, const double *hi,
+                                         int32_t n_bins, int64_t *hist);
 /* the 6-D attitude loop on the same object (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run);
  * usage: matlab/Solver_attitude_hjbdp_get_optimal_paths.m */
 int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, double h, int32_t integrator, const double *q,

@@ -11,6 +11,16 @@
 //                partial is the tree over its G slots: at level L element i (a multiple of 2^(L+1)) becomes op(v[i], v[i + 2^L]);
 //   fold         acc = p_0, then acc = op(acc, p_b) in block order.  Counts are integers.
 // Nothing here depends on how a launch lays the slots out: the kernel runs the same op over wave shuffles.
+//
+// The per-start cost histogram (K30, kernels_rollout_campaign_hist.h; hjb_rollout_campaign_hist_reduce): n_bins in
+// 1 .. kCampaignMaxBins equal bins between lo[s] < hi[s] (both finite), scale_s = (double)n_bins / (hi[s] - lo[s]) (finite), and a
+// record of n_bins + 2 int64 counts per start: index 0 the underflow (c < lo), index n_bins + 1 the overflow (!(c < hi): a NaN
+// lands here), otherwise 1 + min(n_bins - 1, (int)((c - lo) * scale)), the difference and the product each rounded
+// (campaign_bin, the one function every caller bins with).  Padding slots and lanes past a launch's last block count nothing, so
+// a start's record sums to M.
+// Why atomics are allowed here: the eight statistics keep their fixed floating-point order.  Integer addition commutes, so integer
+// atomics do not break K28's rule: the result is a function of (M, the samples) alone.  That licence covers the integer counts of
+// the histogram and nothing else: no double is ever accumulated atomically.
 #pragma once
 #include <stdint.h>
 
@@ -128,6 +138,38 @@ inline void campaign_reduce_start(int64_t n_samples, int D, const double *cost, 
     out[5] = (double)n.left;
     out[6] = (double)n.settled;
     out[7] = acc.sum_settled;
+}
+
+// ---- the histogram of a start's costs (K30) ----
+constexpr int kCampaignMaxBins = 256;
+
+// scale_s of a start's range; the caller refuses one that is not finite (campaign_hist_range_ok)
+HJB_CAMPAIGN_FN double campaign_hist_scale(double lo, double hi, int n_bins) { return (double)n_bins / (hi - lo); }
+
+// a start's range as the entry points accept it: lo and hi finite, lo < hi, a finite scale
+HJB_CAMPAIGN_FN bool campaign_hist_range_ok(double lo, double hi, int n_bins) {
+    const double inf = campaign_inf();
+    if (!(lo > -inf && lo < inf && hi > -inf && hi < inf)) return false;
+    if (!(lo < hi)) return false;
+    const double sc = campaign_hist_scale(lo, hi, n_bins);
+    return sc > -inf && sc < inf;
+}
+
+// the record index of a sample of cost c: 0 underflow, 1 .. n_bins the bins, n_bins + 1 overflow (a NaN lands there)
+HJB_CAMPAIGN_FN int campaign_bin(double c, double lo, double hi, double scale, int n_bins) {
+    if (c < lo) return 0;
+    if (!(c < hi)) return n_bins + 1;
+    const double d = c - lo;
+    const double b = d * scale;                               // 0 <= b, and b <= n_bins up to the two roundings
+    const int i = (int)b;
+    return 1 + (i < n_bins - 1 ? i : n_bins - 1);
+}
+
+// one start's record hist[n_bins + 2] from its n_samples costs, on one thread
+inline void campaign_hist_start(int64_t n_samples, const double *cost, double lo, double hi, int n_bins, int64_t *hist) {
+    const double scale = campaign_hist_scale(lo, hi, n_bins);
+    for (int j = 0; j < n_bins + 2; ++j) hist[j] = 0;
+    for (int64_t m = 0; m < n_samples; ++m) ++hist[campaign_bin(cost[m], lo, hi, scale, n_bins)];
 }
 
 }  // namespace hjb

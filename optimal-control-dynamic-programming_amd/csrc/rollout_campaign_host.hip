@@ -44,7 +44,7 @@ int check_campaign_streams(Rollout *ro, const char *who, int64_t n_starts, int64
 // and the fold on the launch's stream - and stats downloaded.  Under ro->mu.
 int run_campaign_launches(Rollout *ro, const char *who, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts, int64_t n_samples,
                           const double *X0, uint64_t seed, int64_t first_stream, const double *threshold, const double *tol, double *stats,
-                          double *device_ms, const std::function<hipError_t(const CampaignLaunch &)> &launch) {
+                          double *device_ms, const std::function<hipError_t(const CampaignLaunch &)> &launch, const CampaignHistCall *hist) {
     const int D = ro->D;
     DCampaign Cp{};
     Cp.M = n_samples;
@@ -64,19 +64,32 @@ int run_campaign_launches(Rollout *ro, const char *who, int32_t n_steps, const i
     const size_t xb = (size_t)n_starts * D * sizeof(double), sb = (size_t)n_starts * HJB_CAMPAIGN_NSTAT * sizeof(double);
     const size_t tb = threshold ? (size_t)n_starts * sizeof(double) : 0, pb = (size_t)nb_max * HJB_CAMPAIGN_NSTAT * sizeof(double);
     const size_t kb = (size_t)std::max(n_steps, 1) * sizeof(int32_t);
+    // the histogram's [lo | hi | scale] and its counts (K30): nothing without one
+    const size_t rb = hist ? (size_t)n_starts * 3 * sizeof(double) : 0, hb = hist ? (size_t)n_starts * (hist->n_bins + 2) * sizeof(int64_t) : 0;
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipMemGetInfo failed");
-    if (xb + sb + tb + pb + kb + ((size_t)64 << 20) > fr)
+    if (xb + sb + tb + pb + kb + rb + hb + ((size_t)64 << 20) > fr)
         return rfail(ro, HJB_E_NOMEM, "%s: %lld starts and launches of %lld blocks need %zu bytes, %zu free (lower option \"chunk\")", who,
-                     (long long)n_starts, (long long)nb_max, xb + sb + tb + pb + kb, fr);
+                     (long long)n_starts, (long long)nb_max, xb + sb + tb + pb + kb + rb + hb, fr);
     DevData dd(ro->device);                                   // freed on every way out
     const void *dX0 = nullptr, *dthr = nullptr, *dplane = nullptr;
     int st = upload(ro, dd, X0, xb, &dX0);
     if (!st && threshold) st = upload(ro, dd, threshold, tb, &dthr);
     if (!st) st = upload(ro, dd, plane_of_step, n_steps > 0 ? kb : 0, &dplane);
+    const void *drange = nullptr;
+    if (!st && hist) {                                        // [3, n_starts]: lo, hi and the scale, formed once, here
+        std::vector<double> range((size_t)n_starts * 3);
+        for (int64_t s = 0; s < n_starts; ++s) {
+            range[3 * s] = hist->lo[s];
+            range[3 * s + 1] = hist->hi[s];
+            range[3 * s + 2] = campaign_hist_scale(hist->lo[s], hist->hi[s], hist->n_bins);
+        }
+        st = upload(ro, dd, range.data(), rb, &drange);
+    }
     if (st) return st;
-    double *dstats = nullptr, *dpart = nullptr;               // written by the kernels before they are read: nothing to copy
-    for (auto buf : {std::make_pair(&dstats, sb), std::make_pair(&dpart, pb)}) {
+    double *dstats = nullptr, *dpart = nullptr, *dhist = nullptr;     // stats, partials: written by the kernels before they are read
+    for (auto buf : {std::make_pair(&dstats, sb), std::make_pair(&dpart, pb), std::make_pair(&dhist, hb)}) {
+        if (!buf.second) continue;
         void *d = nullptr;
         if (hipMalloc(&d, buf.second) != hipSuccess) return rfail(ro, HJB_E_NOMEM, "%s: hipMalloc of %zu bytes failed", who, buf.second);
         dd.allocs.push_back(d);
@@ -93,17 +106,25 @@ int run_campaign_launches(Rollout *ro, const char *who, int32_t n_steps, const i
     R.n_steps = n_steps;
     // the LDS rule of hjb_rollout_run_noisy: the channel's tables and the node block together
     const size_t lds = (size_t)(2 * (int64_t)R.n_knots + (int64_t)R.n_labels * R.n_u + N.n_tab) * sizeof(double);
-    const bool lds_on = ro->lds && lds <= kLdsMax;
+    bool lds_on = ro->lds && lds <= kLdsMax;
+    size_t lds_launch = lds;
+    DCampHist H{};
+    if (hist) {                                               // the accumulation form and its LDS bytes, with the tables' placement
+        lds_launch = campaign_hist_form(Cp.G, hist->n_bins, ro->lds, lds, kLdsMax, &lds_on, &H);
+        H.range = (const double *)drange;
+        H.hist = (unsigned long long *)dhist;
+    }
     hipStream_t stream = ro->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
     double ms_total = 0;
+    if (e == hipSuccess && hist) e = hipMemsetAsync(dhist, 0, hb, stream);    // once per call; the launches accumulate
     for (int64_t b0 = 0; e == hipSuccess && b0 < n_blocks; b0 += nb_max) {    // a start's blocks may straddle two launches
         Cp.block0 = b0;
         Cp.n_blocks = std::min(nb_max, n_blocks - b0);
         (void)hipEventRecord(e0, stream);
-        e = launch(CampaignLaunch{R, N, Cp, lds, lds_on, stream, (const double *)dX0, dstats});
+        e = launch(CampaignLaunch{R, N, Cp, lds_launch, lds_on, stream, (const double *)dX0, dstats, H});
         if (e != hipSuccess) break;
         (void)hipEventRecord(e1, stream);
         e = hipStreamSynchronize(stream);
@@ -112,6 +133,7 @@ int run_campaign_launches(Rollout *ro, const char *who, int32_t n_steps, const i
         ms_total += ms;
     }
     if (e == hipSuccess) e = hipMemcpyAsync(stats, dstats, sb, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && hist) e = hipMemcpyAsync(hist->hist, dhist, hb, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);

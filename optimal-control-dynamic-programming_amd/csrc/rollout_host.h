@@ -9,6 +9,7 @@
 #include "kernels_rollout_attitude.h"
 #include "kernels_rollout_noisy.h"
 #include "kernels_rollout_campaign.h"
+#include "kernels_rollout_campaign_hist.h"
 #include "kernels_rollout_pos_att.h"
 #include "hjbdp_lookahead.h"
 #include <functional>
@@ -123,7 +124,8 @@ int check_campaign_streams(Rollout *ro, const char *who, int64_t n_starts, int64
 // One launch of a campaign call, as run_campaign_launches hands it to the controller's launch function: the object's record with
 // the planes of the steps on the device, the noise set with the call's seed and first stream, the launch's blocks, the LDS
 // bytes of the channel's tables and the node block together (hjb_rollout_run_noisy's rule), X0 [D, n_starts] and stats
-// [8, n_starts] on the device.
+// [8, n_starts] on the device.  In a histogram call (K30) lds is the launch's dynamic LDS bytes and lds_on the tables' placement as
+// campaign_hist_form decided them, and H the histogram's record; H.hist is null in a plain call.
 struct CampaignLaunch {
     hjb::DRollout R;
     hjb::DNoise N;
@@ -133,13 +135,27 @@ struct CampaignLaunch {
     hipStream_t st;
     const double *X0;
     double *stats;
+    hjb::DCampHist H;
 };
 
+// The histogram of a campaign call (K30), on the host: lo, hi [n_starts], n_bins and the output hist [n_bins + 2, n_starts]
+struct CampaignHistCall {
+    const double *lo, *hi;
+    int32_t n_bins;
+    int64_t *hist;
+};
+// What the histogram entry points refuse of it, in `who`'s name (n_starts >= 0 the caller's): n_bins outside 1 ..
+// HJB_CAMPAIGN_MAX_BINS; with n_starts > 0 a null lo, hi or hist, a lo or hi that is not finite, !(lo < hi), a scale that is not finite
+int check_campaign_hist(Rollout *ro, const char *who, int64_t n_starts, const CampaignHistCall &h);
+
 // The device side of a campaign call whose arguments have been checked (n_starts >= 1; rollout_campaign_host.hip): what a call
-// holds on the device is [D + 1 + 8, n_starts] doubles and 8 doubles per block of a launch.
+// holds on the device is [D + 1 + 8, n_starts] doubles and 8 doubles per block of a launch.  With `hist` (K30) the call also holds
+// [3, n_starts] doubles (lo, hi, scale) and hist [n_bins + 2, n_starts] int64, zeroed once on the call's stream before the first
+// launch and downloaded after the last; the launches then carry the histogram's record and form (campaign_hist_form).
 int run_campaign_launches(Rollout *ro, const char *who, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts, int64_t n_samples,
                           const double *X0, uint64_t seed, int64_t first_stream, const double *threshold, const double *tol, double *stats,
-                          double *device_ms, const std::function<hipError_t(const CampaignLaunch &)> &launch);
+                          double *device_ms, const std::function<hipError_t(const CampaignLaunch &)> &launch,
+                          const CampaignHistCall *hist = nullptr);
 
 // K17 and K21 renormalise the quaternion X0[3..6] of a 7-state column after the first step: all zeros would be 0/0
 int check_quaternions(Rollout *ro, const char *pre, int64_t n_traj, const double *X0);

@@ -264,6 +264,15 @@ SYMBOLS = {
                                             + [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
                                             + [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
                                             + [C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 3),
+    # both campaigns with a per-start histogram of the costs beside the statistics, and the host twin of the binning
+    "hjb_rollout_run_campaign_hist": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
+                                                  C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 4
+                                      + [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "hjb_rollout_run_lookahead_campaign_hist": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
+                                                            C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 4
+                                                + [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "hjb_rollout_campaign_hist_reduce": (C.c_int32, [C.c_int64, C.c_int64] + [C.POINTER(C.c_double)] * 3
+                                         + [C.c_int32, C.POINTER(C.c_int64)]),
     "hjb_rollout_set_attitude_model": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_int32, C.POINTER(C.c_double),
                                                    C.POINTER(C.c_double)]),
     "hjb_rollout_run_attitude": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]
@@ -293,6 +302,7 @@ HJB_DIST_WORST = 1
 HJB_DIST_MAX_NODES = 128
 HJB_ROLLOUT_MAX_U = 4
 HJB_CAMPAIGN_NSTAT = 8
+HJB_CAMPAIGN_MAX_BINS = 256
 HJB_ATT_TAYLOR = 0
 HJB_ATT_RK4 = 1
 HJB_ATTS_FULL = 0

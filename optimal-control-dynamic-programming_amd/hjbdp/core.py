@@ -322,12 +322,16 @@ class Rollout:
         return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
 
     def run_campaign(self, X0, plane_of_step, n_samples, seed=0, first_stream=0, method="linear", cost_threshold=None,
-                     settle_tol=None):
+                     settle_tol=None, hist=None):
         """Every start of X0 [D, n_starts] flown n_samples times under the node set of set_noise, the costs reduced per start on
         the GPU (hjb_rollout_run_campaign): sample m of start s is run_noisy's trajectory on stream first_stream + s * n_samples
         + m of `seed`, and nothing of length n_starts * n_samples exists on either side.  cost_threshold: a scalar or one value
         per start (n_exceed counts the samples with cost > threshold); settle_tol: a scalar or one value per axis (a sample
-        settled when |x_final| <= tol on every axis).  Returns the dict of campaign_reduce plus device_ms."""
+        settled when |x_final| <= tol on every axis).  Returns the dict of campaign_reduce plus device_ms.
+        hist = (lo, hi, n_bins), lo and hi scalars or one value per start: the same flights with a histogram of every start's
+        costs beside the statistics (hjb_rollout_run_campaign_hist; the bin rule: campaign_hist_reduce); the dict gains hist
+        [n_starts, n_bins + 2] int64 (underflow, the bins, overflow), hist_lo and hist_hi, and its stats are the plain call's
+        bits.  hist=None is the plain call."""
         D = self.D
         X = _starts(X0, D)
         ns = X.shape[0]
@@ -335,6 +339,13 @@ class Rollout:
         thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
         stats = np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT))
         ms = C.c_double(0.0)
+        if hist is not None:
+            lo, hi, nb, counts = _campaign_hist_args(ns, hist)
+            self._check(self.lib.hjb_rollout_run_campaign_hist(self._ro, _LOOKUP[method], int(ps.size), _i32p(ps), ns, int(n_samples),
+                                                               _f64p(X), int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr),
+                                                               _f64p(tol), _f64p(lo), _f64p(hi), nb, _f64p(stats), _i64p(counts),
+                                                               C.byref(ms)))
+            return {**_campaign_dict(stats, int(n_samples)), "hist": counts, "hist_lo": lo, "hist_hi": hi, "device_ms": ms.value}
         self._check(self.lib.hjb_rollout_run_campaign(self._ro, _LOOKUP[method], int(ps.size), _i32p(ps), ns, int(n_samples), _f64p(X),
                                                       int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol),
                                                       _f64p(stats), C.byref(ms)))
@@ -422,7 +433,8 @@ class Rollout:
         reduced per start on the GPU.  Sample m of start s is run_lookahead(noisy=True)'s trajectory on stream first_stream +
         s * n_samples + m of `seed` - the stream run_campaign gives that sample, so the two campaigns of one seed, first_stream
         and n_samples fly common random numbers and their per-start means can be differenced with the sampling noise largely
-        cancelled.  cost_threshold, settle_tol and the returned dict: run_campaign's."""
+        cancelled.  cost_threshold, settle_tol and the returned dict: run_campaign's.  With a histogram of every start's costs
+        beside the statistics: run_lookahead_campaign_hist."""
         D = self.D
         X = _starts(X0, D)
         ns = X.shape[0]
@@ -434,6 +446,24 @@ class Rollout:
                                                                 int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol),
                                                                 _f64p(stats), C.byref(ms)))
         return {**_campaign_dict(stats, int(n_samples)), "device_ms": ms.value}
+
+    def run_lookahead_campaign_hist(self, X0, value_plane_of_step, n_samples, hist, seed=0, first_stream=0, cost_threshold=None,
+                                    settle_tol=None):
+        """run_lookahead_campaign with a histogram of every start's costs beside the statistics
+        (hjb_rollout_run_lookahead_campaign_hist): hist = (lo, hi, n_bins) and the returned dict as run_campaign(hist=...) has
+        them, the flights, the streams (common random numbers with run_campaign) and the stats run_lookahead_campaign's."""
+        D = self.D
+        X = _starts(X0, D)
+        ns = X.shape[0]
+        ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
+        thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
+        stats = np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT))
+        lo, hi, nb, counts = _campaign_hist_args(ns, hist)
+        ms = C.c_double(0.0)
+        self._check(self.lib.hjb_rollout_run_lookahead_campaign_hist(self._ro, int(ps.size), _i32p(ps), ns, int(n_samples), _f64p(X),
+                                                                     int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol),
+                                                                     _f64p(lo), _f64p(hi), nb, _f64p(stats), _i64p(counts), C.byref(ms)))
+        return {**_campaign_dict(stats, int(n_samples)), "hist": counts, "hist_lo": lo, "hist_hi": hi, "device_ms": ms.value}
 
     def set_attitude_model(self, inertia, h, integrator="taylor", q=None, r=None):
         """The 6-D attitude loop instead of the affine one (hjb_rollout_set_attitude_model; the last model set wins):
@@ -612,6 +642,109 @@ def _campaign_dict(stats, M):
     return {"stats": stats, "mean": total / M, "var": var, "std": np.sqrt(var), "min": stats[:, 2], "max": stats[:, 3],
             "n_exceed": stats[:, 4].astype(np.int64), "n_left": stats[:, 5].astype(np.int64), "n_settled": n_settled,
             "mean_settled": mean_settled}
+
+
+def _i64p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _campaign_hist_args(n_starts, hist):
+    """hist = (lo, hi, n_bins), lo and hi scalars or [n_starts] -> lo, hi as the library reads them, n_bins and the zeroed output
+    [n_starts, n_bins + 2] int64 (the library's [n_bins + 2, n_starts] column-major)"""
+    lo, hi, n_bins = hist
+    nb = int(n_bins)
+    if not 1 <= nb <= _abi.HJB_CAMPAIGN_MAX_BINS:
+        raise ValueError("n_bins must lie in 1..%d" % _abi.HJB_CAMPAIGN_MAX_BINS)
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64).reshape(-1), (n_starts,)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64).reshape(-1), (n_starts,)))
+    return lo, hi, nb, np.zeros((n_starts, nb + 2), dtype=np.int64)
+
+
+def campaign_hist_reduce(cost, n_samples, lo, hi, n_bins):
+    """The binning of Rollout.run_campaign(hist=...) on the CPU (hjb_rollout_campaign_hist_reduce; no device): cost
+    [n_starts * n_samples] (trajectory s * n_samples + m is sample m of start s), lo and hi scalars or one value per start
+    (finite, lo < hi), n_bins in 1..256.  A cost c < lo counts in column 0, one with not c < hi (a NaN too) in column n_bins + 1,
+    any other in column 1 + min(n_bins - 1, int((c - lo) * (n_bins / (hi - lo)))).  Returns hist [n_starts, n_bins + 2] int64:
+    the counts run_campaign(hist=...) returns for the same samples; every row sums to n_samples."""
+    lib = load_library()
+    c = np.ascontiguousarray(np.asarray(cost, dtype=np.float64).reshape(-1))
+    M = int(n_samples)
+    if M < 1 or c.size % M:
+        raise ValueError("cost: %d values are not a whole number of %d samples" % (c.size, M))
+    ns = c.size // M
+    lo, hi, nb, counts = _campaign_hist_args(ns, (lo, hi, n_bins))
+    _check(lib, None, lib.hjb_rollout_campaign_hist_reduce(ns, M, _f64p(c), _f64p(lo), _f64p(hi), nb, _i64p(counts)))
+    return counts
+
+
+def _hist_edges(hist, lo, hi):
+    h = np.asarray(hist, dtype=np.int64)
+    h = h.reshape(1, -1) if h.ndim == 1 else h
+    nb = h.shape[1] - 2
+    if nb < 1:
+        raise ValueError("hist: %d columns are not underflow, at least one bin and overflow" % h.shape[1])
+    lo = np.broadcast_to(np.asarray(lo, dtype=np.float64).reshape(-1), (h.shape[0],))
+    hi = np.broadcast_to(np.asarray(hi, dtype=np.float64).reshape(-1), (h.shape[0],))
+    return h, nb, lo, hi
+
+
+def campaign_quantiles(hist, lo, hi, q, cmin=None, cmax=None):
+    """Upper bounds of order statistics from campaign histograms (pure numpy).  hist [n_starts, n_bins + 2] as
+    run_campaign(hist=...) returns it, lo and hi the ranges it was binned with, q a scalar or a sequence in [0, 1].  With M a
+    row's sum and the rank k = max(1, ceil(q * M)), the result [n_starts, len(q)] is the upper edge lo + j * (hi - lo) / n_bins of
+    the first bin j whose cumulative count - the underflow column counted first - reaches k: the k-th smallest cost lies in
+    that bin, so it is at most the result and more than the result minus one bin width.  cmin / cmax (per start, e.g. the
+    campaign's min and max) clip the result.  NaN where the rank falls in the underflow and no cmin is given, or in the
+    overflow and no cmax is given (with cmin / cmax those give cmin / cmax)."""
+    h, nb, lo, hi = _hist_edges(hist, lo, hi)
+    qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if np.any(~((qs >= 0) & (qs <= 1))):
+        raise ValueError("q must lie in [0, 1]")
+    ns = h.shape[0]
+    M = h.sum(axis=1)
+    cum = np.cumsum(h, axis=1)
+    out = np.full((ns, qs.size), np.nan)
+    for i, qq in enumerate(qs):
+        k = np.maximum(1, np.ceil(qq * M)).astype(np.int64)
+        col = np.argmax(cum >= k[:, None], axis=1)                              # the first column whose cumulative count reaches k
+        inside = (col >= 1) & (col <= nb) & (M > 0)
+        edge = lo + col * (hi - lo) / nb
+        edge = np.where(col == nb, hi, edge)                                    # the last edge is hi itself, not its rounding
+        val = np.where(inside, edge, np.nan)
+        if cmin is not None:
+            val = np.where((col == 0) & (M > 0), np.broadcast_to(np.asarray(cmin, dtype=np.float64).reshape(-1), (ns,)), val)
+        if cmax is not None:
+            val = np.where((col == nb + 1) & (M > 0), np.broadcast_to(np.asarray(cmax, dtype=np.float64).reshape(-1), (ns,)), val)
+        if cmin is not None or cmax is not None:
+            val = np.clip(val, None if cmin is None else np.asarray(cmin, dtype=np.float64).reshape(-1),
+                          None if cmax is None else np.asarray(cmax, dtype=np.float64).reshape(-1))
+        out[:, i] = val
+    return out
+
+
+def campaign_tail_mean(hist, lo, hi, q):
+    """The mean of the samples at or above the q-quantile, estimated from campaign histograms (pure numpy): the samples of rank
+    k = max(1, ceil(q * M)) and above, each taken at its bin's midpoint - an ESTIMATE within one bin width of the exact tail
+    mean, not a bound, and exact in no digit.  hist, lo, hi, q as in campaign_quantiles; returns [n_starts, len(q)].  NaN where
+    a sample of the tail lies in the underflow or the overflow column (it has no midpoint) or the row is empty."""
+    h, nb, lo, hi = _hist_edges(hist, lo, hi)
+    qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if np.any(~((qs >= 0) & (qs <= 1))):
+        raise ValueError("q must lie in [0, 1]")
+    ns = h.shape[0]
+    M = h.sum(axis=1)
+    cum = np.cumsum(h, axis=1)
+    before = cum - h                                                            # samples of lower columns
+    mid = lo[:, None] + (np.arange(nb)[None, :] + 0.5) * ((hi - lo) / nb)[:, None]
+    out = np.full((ns, qs.size), np.nan)
+    for i, qq in enumerate(qs):
+        k = np.maximum(1, np.ceil(qq * M)).astype(np.int64)
+        take = np.clip(cum - np.maximum(before, (k - 1)[:, None]), 0, None)     # of every column, the samples of rank >= k
+        n_tail = M - (k - 1)
+        ok = (M > 0) & (take[:, 0] == 0) & (take[:, nb + 1] == 0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out[:, i] = np.where(ok, (take[:, 1:nb + 1] * mid).sum(axis=1) / np.maximum(n_tail, 1), np.nan)
+    return out
 
 
 def campaign_reduce(cost, n_samples, X_final=None, left=None, cost_threshold=None, settle_tol=None):

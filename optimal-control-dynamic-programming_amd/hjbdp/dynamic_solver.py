@@ -441,6 +441,114 @@ class Dynamic_Solver:
         return {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) else v) for key, v in out.items()}
 
     @staticmethod
+    def _two_pass_quantiles(campaign, n_samples, q, n_bins):
+        """The two passes of the quantile methods.  campaign(hist) flies one campaign of the method's starts, seed and streams
+        (hist None: the plain one).  Pass 1 is the plain campaign: every start's min and max.  Pass 2 flies the same samples
+        again - the streams are counter-based - and bins them between lo = min and hi = nextafter(max, +inf) (hi = lo + 1 where
+        min = max, or where a start's costs are not finite), so the range fits every start exactly: nothing under, nothing over.
+        Returns pass 2's dict (its stats are pass 1's bits) plus quantiles [n, len(q)], clipped to [min, max], and q."""
+        from .core import campaign_quantiles
+        if int(n_samples) < 1:
+            raise ValueError("n_samples must be at least 1")
+        qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+        first = campaign(None)
+        lo = np.array(first["min"], dtype=np.float64)
+        hi = np.nextafter(np.array(first["max"], dtype=np.float64), np.inf)
+        flat = ~(np.isfinite(lo) & np.isfinite(hi) & (lo < hi)) | (first["min"] == first["max"])
+        lo = np.where(np.isfinite(lo), lo, 0.0)
+        hi = np.where(flat, lo + 1.0, hi)
+        out = campaign((lo, hi, int(n_bins)))
+        out["device_ms"] = out["device_ms"] + first["device_ms"]
+        out["quantiles"] = campaign_quantiles(out["hist"], out["hist_lo"], out["hist_hi"], qs, cmin=out["min"], cmax=out["max"])
+        out["q"] = qs
+        return out
+
+    def get_noisy_cost_quantiles(self, X0s, n_samples, q=(0.5, 0.95, 0.99), n_bins=64, seed=0, mode="Nssu", ssu_num=1, method="linear",
+                                 cost_threshold=None, settle_tol=None):
+        """Quantiles of get_noisy_cost_statistics' costs per start, from histograms reduced on the GPU
+        (hjbdp.Rollout.run_campaign with hist): two campaigns on the same seed and streams, the first for every start's min and
+        max, the second binning the same samples in n_bins equal bins between them (_two_pass_quantiles), and nothing of length
+        n * n_samples on the host or on the device.  Returns get_noisy_cost_statistics' dict plus hist [n, n_bins + 2], hist_lo,
+        hist_hi, q and quantiles [n, len(q)]: hjbdp.campaign_quantiles' upper bounds, each at most one bin width (max - min) /
+        n_bins above the order statistic of rank ceil(q * n_samples); q = 1 gives max exactly.  hjbdp.campaign_tail_mean of the
+        same hist estimates the tail mean above a quantile."""
+        planes, ro = self._noisy_policy_rollout("get_noisy_cost_quantiles", mode, ssu_num)
+        X = np.asarray(X0s, dtype=np.float64).reshape(self.S, -1)
+        with ro:
+            return self._two_pass_quantiles(lambda hist: ro.run_campaign(X, planes, int(n_samples), seed=seed, first_stream=0, method=method,
+                                                                         cost_threshold=cost_threshold, settle_tol=settle_tol, hist=hist),
+                                            n_samples, q, n_bins)
+
+    def _grid_starts(self):
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        dx = s_r.size
+        return dx, np.stack([np.tile(s_r, dx), np.repeat(s_r, dx)])             # axis 0 fastest, as the labels are stored
+
+    def noisy_cost_quantile_map(self, n_samples, q=(0.5, 0.95, 0.99), n_bins=64, seed=0, mode="Nssu", ssu_num=1, method="linear",
+                                cost_threshold=None, settle_tol=None):
+        """get_noisy_cost_quantiles at every grid node, beside policy_cost(): each per-start entry shaped like the grid, [dx, dx]
+        (quantiles [dx, dx, len(q)], hist [dx, dx, n_bins + 2]), node (i, j) = (s_r[i], s_r[j]) on noisy_cost_map's streams.
+        Every node's bins lie between that node's own min and max: the cost spans orders of magnitude over the grid."""
+        dx, X0s = self._grid_starts()
+        out = self.get_noisy_cost_quantiles(X0s, n_samples, q=q, n_bins=n_bins, seed=seed, mode=mode, ssu_num=ssu_num, method=method,
+                                            cost_threshold=cost_threshold, settle_tol=settle_tol)
+        return {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) and key != "q" else v)
+                for key, v in out.items()}
+
+    def get_lookahead_cost_quantiles(self, X0s, n_samples, q=(0.5, 0.95, 0.99), n_bins=64, seed=0, mode="Nssu", ssu_num=1,
+                                     lookahead="disturbed", cost_threshold=None, settle_tol=None):
+        """get_noisy_cost_quantiles for get_lookahead_cost_statistics' controller (hjbdp.Rollout.run_lookahead_campaign_hist): the
+        same two passes on the same streams, so the quantiles of the stored labels and of either lookahead come from common
+        random numbers.  `lookahead`, planes and `mode` / `ssu_num` as in get_lookahead_cost_statistics."""
+        from .core import Rollout
+        if self.J_star is None or self.u_star_idxs is None:
+            raise RuntimeError("run() first")
+        if self.disturbance is None:
+            raise RuntimeError("get_lookahead_cost_quantiles needs self.disturbance = (offsets [2, W], weights or None, mode)")
+        offsets, weights = self.disturbance[0], self.disturbance[1]
+        dmode = self.disturbance[2] if len(self.disturbance) > 2 else "expect"
+        if lookahead not in ("disturbed", "nominal"):
+            raise ValueError("lookahead must be 'disturbed' or 'nominal'")
+        N, S = self.N, self.S
+        n_st = N - 1
+        if mode == "ssu":
+            if not 1 <= int(ssu_num) <= n_st:
+                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
+            planes = np.full(n_st, int(ssu_num), dtype=np.int32)
+        elif mode == "Nssu":
+            planes = np.arange(1, N, dtype=np.int32)
+        else:
+            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
+        X = np.asarray(X0s, dtype=np.float64).reshape(S, -1)
+        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
+            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+            ro.set_values(self.J_star)
+            if lookahead == "disturbed":
+                ro.set_lookahead(offsets, weights, dmode)
+            else:
+                ro.set_lookahead(np.zeros((S, 1)), [1.0], "expect")
+            ro.set_noise(offsets, weights)
+
+            def campaign(hist):
+                if hist is None:
+                    return ro.run_lookahead_campaign(X, planes, int(n_samples), seed=seed, first_stream=0, cost_threshold=cost_threshold,
+                                                     settle_tol=settle_tol)
+                return ro.run_lookahead_campaign_hist(X, planes, int(n_samples), hist, seed=seed, first_stream=0,
+                                                      cost_threshold=cost_threshold, settle_tol=settle_tol)
+            return self._two_pass_quantiles(campaign, n_samples, q, n_bins)
+
+    def lookahead_cost_quantile_map(self, n_samples, q=(0.5, 0.95, 0.99), n_bins=64, seed=0, mode="Nssu", ssu_num=1, lookahead="disturbed",
+                                    cost_threshold=None, settle_tol=None):
+        """get_lookahead_cost_quantiles at every grid node: noisy_cost_quantile_map's starts on its streams."""
+        dx, X0s = self._grid_starts()
+        out = self.get_lookahead_cost_quantiles(X0s, n_samples, q=q, n_bins=n_bins, seed=seed, mode=mode, ssu_num=ssu_num,
+                                                lookahead=lookahead, cost_threshold=cost_threshold, settle_tol=settle_tol)
+        return {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) and key != "q" else v)
+                for key, v in out.items()}
+
+    @staticmethod
     def compare_data(obj1, obj2):
         # Dynamic_Solver.m:266-280
         if obj1.J_star is None or obj2.J_star is None or obj1.J_star.size == 0 or obj2.J_star.size == 0:

@@ -27,8 +27,11 @@ Two cases, one JSON line:
       it also writes its line to profiles/rollout_campaign_time.json.
   (m) lookahead_campaign: the lookahead campaign (K29, hjb_rollout_run_lookahead_campaign) beside K27 flown noisy on the same
       repeated starts, see case_lookahead_campaign; alone, it also writes its line to profiles/rollout_lookahead_campaign_time.json.
+  (n) campaign_hist: the campaign histogram (K30, hjb_rollout_run_campaign_hist) beside K28 on the same starts, and the two-pass
+      quantile map beside one plain map, see case_campaign_hist; alone, it also writes its line to
+      profiles/rollout_campaign_hist_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy,lookahead,campaign,lookahead_campaign] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy,lookahead,campaign,lookahead_campaign,campaign_hist] [--out FILE]
 """
 from __future__ import annotations
 
@@ -772,6 +775,93 @@ def case_lookahead_campaign(host=True, n_starts=1 << 14, n_samples=64):
     return res
 
 
+def case_campaign_hist(host=True, n_starts=1 << 14, n_samples=64, n_bins=64):
+    """(n) campaign_hist: case_campaign's problem and node set (Kirk, 9 nodes), 64 bins: K30 (hjb_rollout_run_campaign_hist: the
+    statistics and n_bins + 2 counts per start come back) beside K28 (hjb_rollout_run_campaign) on one object in one process, at
+    case_campaign's two shapes: 2^14 starts x 64 samples and 8 starts x 2^17 samples (both G = 64: a histogram per wave in LDS,
+    one 64-bit global atomic per non-zero bin, start and workgroup).  Every start's range is the two-pass one: lo = the plain
+    campaign's min, hi = the next double above its max ((0, 1) for a start whose costs are not finite or all equal).  The two
+    alternate, five rounds after a warm-up round; per round the kernel time (device_ms: event times around the launches, the fold
+    kernel and the histogram's zeroing included) and the whole call's wall time, the medians and their ratios quoted.  `pass`: the
+    project's bound for a campaign against its base, K30's kernel time <= 1.05 x K28's at 2^14 x 64 in this run; 8 x 2^17 is
+    recorded with no bound, as case_campaign records it.  samples_under_or_over_in_those counts what lies outside an exact range:
+    NaN costs (flights that left the grid on Kirk's unstable loop), which are not ordered and count in the overflow.  Beside them the whole-call time of the two-pass quantile map
+    (Dynamic_Solver.noisy_cost_quantile_map: 35 x 35 nodes x 64 samples, two campaigns) beside one plain noisy_cost_map.  `host` is
+    not used."""
+    import hjbdp
+    ds = hjbdp.Dynamic_Solver(precision="double")
+    ds.N, ds.dx, ds.du = 130, 35, 100
+    ds.run()
+    s_r = np.asarray(ds.s_r, dtype=np.float64)
+    rng = np.random.default_rng(1)
+    X0 = rng.uniform(s_r[0], s_r[-1], size=(2, n_starts))
+    planes = np.arange(ds.N - 1)
+    off, w = hjbdp.gaussian_nodes([0.02, 0.05], order=3)
+    res = {"grid": "35x35", "planes": int(ds.N - 1), "method": "linear", "labels": "int32", "n_steps": int(ds.N - 1),
+           "nodes": int(off.shape[1]), "n_bins": int(n_bins), "noise": "gaussian_nodes(sigma = (0.02, 0.05), order 3) on both axes",
+           "range": "per start: lo = min, hi = nextafter(max) of the plain campaign on the same seed",
+           "timing": "device_ms: event times around the launches (rollout and fold kernels; K30: the histogram's memset too); wall_ms: "
+                     "the whole Python call; the two runs alternate in one process, 5 rounds after a warm-up round"}
+    with hjbdp.Rollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro:
+        ro.set_model(ds.A, ds.B, q=np.diag(ds.Q), r=[ds.R])
+        ro.set_noise(off, w)
+        for name, ns, M in (("many_starts", n_starts, n_samples), ("few_starts", 8, 1 << 17)):
+            X = X0[:, :ns]
+            ms = {"k28": [], "k30": []}
+            wall = {"k28": [], "k30": []}
+            lo = hi = None
+            for rnd in range(6):
+                t0 = time.perf_counter()
+                b = ro.run_campaign(X, planes, M, seed=1, method="linear")
+                t1 = time.perf_counter()
+                if lo is None:
+                    lo, hi = b["min"].copy(), np.nextafter(b["max"], np.inf)
+                    flat = ~(np.isfinite(lo) & np.isfinite(hi) & (lo < hi)) | (b["min"] == b["max"])
+                    lo, hi = np.where(flat, 0.0, lo), np.where(flat, 1.0, hi)
+                    t1 = time.perf_counter()
+                c = ro.run_campaign(X, planes, M, seed=1, method="linear", hist=(lo, hi, n_bins))
+                t2 = time.perf_counter()
+                if rnd:                                           # round 0 is the warm-up
+                    ms["k28"].append(b["device_ms"])
+                    ms["k30"].append(c["device_ms"])
+                    wall["k28"].append((t1 - t0) * 1e3)
+                    wall["k30"].append((t2 - t1) * 1e3)
+            one = {"n_starts": int(ns), "n_samples": int(M), "n_traj": int(ns * M), "blocks_per_start": -(-M // 64)}
+            for key in ms:
+                med = float(np.median(ms[key]))
+                one[key] = {"device_ms": [round(t, 3) for t in ms[key]], "device_ms_median": round(med, 3),
+                            "wall_ms": [round(t, 1) for t in wall[key]], "wall_ms_median": round(float(np.median(wall[key])), 1),
+                            "traj_steps_per_s": ns * M * (ds.N - 1) / (med * 1e-3)}
+            one["k30_over_k28_kernel"] = one["k30"]["device_ms_median"] / one["k28"]["device_ms_median"]
+            one["k30_over_k28_wall"] = one["k30"]["wall_ms_median"] / one["k28"]["wall_ms_median"]
+            one["host_bytes_per_call"] = {"k28": int(ns * (2 + 8) * 8), "k30": int(ns * (2 + 8 + 2 + n_bins + 2) * 8)}
+            one["stats_bit_equal"] = bool(np.array_equal(c["stats"].view(np.uint64), b["stats"].view(np.uint64)))
+            one["every_record_sums_to_n_samples"] = bool(np.all(c["hist"].sum(axis=1) == M))
+            one["starts_with_an_exact_range"] = int((~flat).sum())
+            one["samples_under_or_over_in_those"] = int(c["hist"][~flat][:, [0, -1]].sum())
+            res[name] = one
+    ds.disturbance = (off, w, "expect")                           # the stored (nominal) policy under the node set, as above
+    wall = {"noisy_cost_map": [], "noisy_cost_quantile_map": []}
+    for rnd in range(4):
+        t0 = time.perf_counter()
+        plain = ds.noisy_cost_map(n_samples, seed=1)
+        t1 = time.perf_counter()
+        qmap = ds.noisy_cost_quantile_map(n_samples, n_bins=n_bins, seed=1)
+        t2 = time.perf_counter()
+        if rnd:
+            wall["noisy_cost_map"].append((t1 - t0) * 1e3)
+            wall["noisy_cost_quantile_map"].append((t2 - t1) * 1e3)
+    res["quantile_map"] = {"nodes": int(s_r.size ** 2), "n_samples": int(n_samples), "q": [0.5, 0.95, 0.99],
+                           "wall_ms": {k: [round(t, 1) for t in v] for k, v in wall.items()},
+                           "wall_ms_median": {k: round(float(np.median(v)), 1) for k, v in wall.items()},
+                           "stats_bit_equal": bool(np.array_equal(qmap["stats"].view(np.uint64), plain["stats"].view(np.uint64)))}
+    res["quantile_map"]["two_pass_over_plain_wall"] = (res["quantile_map"]["wall_ms_median"]["noisy_cost_quantile_map"]
+                                                       / res["quantile_map"]["wall_ms_median"]["noisy_cost_map"])
+    res["bound"] = 1.05
+    res["pass"] = bool(res["many_starts"]["k30_over_k28_kernel"] <= res["bound"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -787,7 +877,7 @@ def main():
                   "position_loop": case_position_loop, "attitude_simplified_loop": case_attitude_simplified_loop,
                   "attitude_linear_loop": case_attitude_linear_loop, "pos_att_faults": case_pos_att_faults,
                   "kirk_noisy": case_kirk_noisy, "greedy": case_greedy, "lookahead": case_lookahead, "campaign": case_campaign,
-                  "lookahead_campaign": case_lookahead_campaign}[c](host=not a.no_host)
+                  "lookahead_campaign": case_lookahead_campaign, "campaign_hist": case_campaign_hist}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.cases == "position_loop" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
@@ -807,6 +897,8 @@ def main():
         (ROOT / "profiles" / "rollout_campaign_time.json").write_text(json.dumps(res) + "\n")
     if a.cases == "lookahead_campaign" and not a.out:             # its own record: one line
         (ROOT / "profiles" / "rollout_lookahead_campaign_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "campaign_hist" and not a.out:                  # its own record: one line
+        (ROOT / "profiles" / "rollout_campaign_hist_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
