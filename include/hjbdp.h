@@ -653,8 +653,10 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
  * hjb_rollout_run_lookahead refuses with fly_noise = 1 (n_starts in the place of n_traj; no lookahead set; no noise set; another
  * model set; a plane outside the value planes); null stats; n_samples < 1; n_starts * n_samples or first_stream + n_starts *
  * n_samples overflowing int64; a threshold entry that is NaN; a tol entry that is NaN or negative.  n_starts = 0 is HJB_OK.
- * Out of scope: a paired-difference statistic computed on the device, sharing the first step's lookahead among a start's samples,
- * campaigns of the integrated plants, float16 value planes. */
+ * The paired-difference statistic of two controllers on these streams, computed on the device: hjb_rollout_run_campaign_pair
+ * (kernel K31, below).
+ * Out of scope: sharing the first step's lookahead among a start's samples, campaigns of the integrated plants,
+ * float16 value planes. */
 int32_t hjb_rollout_run_lookahead_campaign(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
                                            int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
                                            const double *threshold, const double *tol, double *stats, double *device_ms);
@@ -701,6 +703,50 @@ int32_t hjb_rollout_run_lookahead_campaign_hist(void *rollout, int32_t n_steps, 
                                                 int32_t n_bins, double *stats, int64_t *hist, double *device_ms);
 int32_t hjb_rollout_campaign_hist_reduce(int64_t n_starts, int64_t n_samples, const double *cost, const double *lo, const double *hi,
                                          int32_t n_bins, int64_t *hist);
+
+/* ---- paired campaigns: per-start statistics of the cost difference of two controllers, reduced on the device (kernel K31) -------
+ * hjb_rollout_run_campaign_pair flies one object's plant - its affine model and the node set of hjb_rollout_set_noise - under two
+ * controllers A and B.  Both controllers fly every sample on the plain campaigns' stream: sample m of start s flies stream
+ * first_stream + s*M + m under A and under B, so the variance of the per-sample difference holds the pairing (the covariance) that
+ * two independently reduced records do not.  No array of the call has a dimension of n_starts * M.
+ * Each controller is one of three kinds:
+ *   HJB_PAIR_LABELS (0)     the stored-label controller of hjb_rollout_run_campaign; planes_x are label planes, method_x is read;
+ *   HJB_PAIR_LOOKAHEAD (1)  the controller of hjb_rollout_run_lookahead_campaign, under the object's hjb_rollout_set_lookahead set;
+ *                           planes_x are value planes (-1: the zero function), method_x is ignored;
+ *   HJB_PAIR_GREEDY (2)     the same with a lookahead set of ONE zero node of weight 1, mode expect: K26's nominal controller; it is
+ *                           bit for bit what hjb_rollout_run_lookahead_campaign gives after hjb_rollout_set_lookahead(zeros(D,1),
+ *                           [1.0], expect).  The object's own lookahead set is neither read nor changed: the host keeps that
+ *                           one-node table on the device itself.
+ * Both sides may have the same kind with different planes or method (per-stage labels against the stationary table; 'nearest'
+ * against 'linear'); a pair of a controller with itself is legal.
+ * Output.  stats_a [8, n_starts]: bit for bit the plain campaign of A with the same arguments, threshold and tol included;
+ *   stats_b [8, n_starts]: the same for B;  stats_d [HJB_CAMPAIGN_PAIR_NSTAT, n_starts] column-major: the record of d = c_B - c_A,
+ *   one rounded subtraction per sample.  A negative d means B paid less.
+ * Slot values of d.  campaign_slot(d, t) with the flags  e = d < 0;  l = d > 0;  t = neither flight left the grid.  A NaN d sets
+ *   neither e nor l.  Padding, G, blocks, the adjacent-pair tree and the left-to-right fold are hjb_rollout_run_campaign's, word
+ *   for word (csrc/hjbdp_campaign.h: CampVals, campaign_op, campaign_tree - there is no second reduction).
+ *   stats_d: 0 sum d;  1 sum d*d, each product rounded;  2 min d;  3 max d;  4 n(B lower);  5 n(A lower);  6 n(both stayed in the
+ *   grid);  7 sum d over those samples.  Counts are exact integers stored as doubles.  There are no atomics anywhere in this call.
+ * Options "chunk" and "lds" change no bit of any of the three records.
+ * Device memory of a call: [D + 1 + 24, n_starts] doubles, 24 doubles per block of a launch, and one double and one byte per lane
+ *   of a launch (the pair scratch through which A's kernel hands its costs and flags to B's).
+ * hjb_rollout_campaign_pair_reduce is the CPU twin with no device (csrc/hjbdp_campaign.h, campaign_pair_start), on per-trajectory
+ *   arrays such as hjb_rollout_run_noisy and hjb_rollout_run_lookahead return: trajectory s*M + m is sample m of start s; cost_a,
+ *   cost_b [n_starts*M]; left_a, left_b [n_starts*M] uint8 (non-zero: left the grid), a NULL left_* means "none left".
+ * Refused before any device work, outputs untouched (text: hjb_rollout_last_error) - HJB_E_INVALID: a kind outside 0..2;
+ * everything the plain campaign of each kind refuses, named with the side in the text ("A:" / "B:"); a null stats_a, stats_b or
+ * stats_d with n_starts > 0; the plain campaigns' refusals of sizes, streams, threshold and tol.  n_starts = 0 is HJB_OK.
+ * Out of scope: a histogram of d, pairs across two objects, pairs on the integrated plants. */
+#define HJB_PAIR_LABELS 0
+#define HJB_PAIR_LOOKAHEAD 1
+#define HJB_PAIR_GREEDY 2
+#define HJB_CAMPAIGN_PAIR_NSTAT 8
+int32_t hjb_rollout_run_campaign_pair(void *rollout, int32_t kind_a, int32_t method_a, const int32_t *planes_a, int32_t kind_b,
+                                      int32_t method_b, const int32_t *planes_b, int32_t n_steps, int64_t n_starts, int64_t n_samples,
+                                      const double *X0, uint64_t seed, int64_t first_stream, const double *threshold, const double *tol,
+                                      double *stats_a, double *stats_b, double *stats_d, double *device_ms);
+int32_t hjb_rollout_campaign_pair_reduce(int64_t n_starts, int64_t n_samples, const double *cost_a, const double *cost_b,
+                                         const uint8_t *left_a, const uint8_t *left_b, double *stats_d);
 
 /* The 6-D attitude closed loop (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run) on the same object.
  * hjb_rollout_set_attitude_model and hjb_rollout_set_model replace each other: the last one set wins.  It needs D == 6, n_u == 3

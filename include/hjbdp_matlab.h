@@ -175,6 +175,17 @@ int32_t hjb_rollout_run_lookahead_campaign_hist(void *rollout, int32_t n_steps, 
                                                 int32_t n_bins, double *stats, int64_t *hist, double *device_ms);
 int32_t hjb_rollout_campaign_hist_reduce(int64_t n_starts, int64_t n_samples, const double *cost, const double *lo, const double *hi,
                                          int32_t n_bins, int64_t *hist);
+/* two controllers A and B on one plant, sample by sample on the plain campaigns' streams (kernel K31): kind 0 = stored labels
+ * (planes are label planes, method read), 1 = the lookahead under the object's set, 2 = the lookahead under one zero node of weight 1
+ * (planes are value planes, method ignored); stats_a and stats_b [8, n_starts] are the plain campaigns' bits, stats_d [8, n_starts] the
+ * record of d = c_B - c_A (sum, sum of squares, min, max, n(B lower), n(A lower), n(both stayed in the grid), sum over those); the
+ * host twin needs no device (hjbdp.h); usage: matlab/Dynamic_Solver_hjbdp_paired_cost_map.m */
+int32_t hjb_rollout_run_campaign_pair(void *rollout, int32_t kind_a, int32_t method_a, const int32_t *planes_a, int32_t kind_b,
+                                      int32_t method_b, const int32_t *planes_b, int32_t n_steps, int64_t n_starts, int64_t n_samples,
+                                      const double *X0, uint64_t seed, int64_t first_stream, const double *threshold, const double *tol,
+                                      double *stats_a, double *stats_b, double *stats_d, double *device_ms);
+int32_t hjb_rollout_campaign_pair_reduce(int64_t n_starts, int64_t n_samples, const double *cost_a, const double *cost_b,
+                                         const uint8_t *left_a, const uint8_t *left_b, double *stats_d);
 /* the 6-D attitude loop on the same object (attitude-control/Solver_attitude.m:744-833, get_optimal_path after run);
  * usage: matlab/Solver_attitude_hjbdp_get_optimal_paths.m */
 int32_t hjb_rollout_set_attitude_model(void *rollout, const double *inertia, double h, int32_t integrator, const double *q,

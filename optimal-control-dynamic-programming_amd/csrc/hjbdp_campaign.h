@@ -21,6 +21,11 @@
 // Why atomics are allowed here: the eight statistics keep their fixed floating-point order.  Integer addition commutes, so integer
 // atomics do not break K28's rule: the result is a function of (M, the samples) alone.  That licence covers the integer counts of
 // the histogram and nothing else: no double is ever accumulated atomically.
+//
+// The paired difference of two controllers on one plant (K31, kernels_rollout_campaign_pair.h; hjb_rollout_campaign_pair_reduce):
+// sample m of a start is flown by A and by B on the same stream, d = c_B - c_A (one rounded subtraction), and the record of d is
+// K28's reduction over campaign_slot(d, t) with the flags e = d < 0 (B paid less), l = d > 0 (A paid less), t = neither flight left
+// the grid; a NaN d sets neither e nor l.  Blocks, padding, tree and fold are the ones above: campaign_pair_start calls them.
 #pragma once
 #include <stdint.h>
 
@@ -170,6 +175,45 @@ inline void campaign_hist_start(int64_t n_samples, const double *cost, double lo
     const double scale = campaign_hist_scale(lo, hi, n_bins);
     for (int j = 0; j < n_bins + 2; ++j) hist[j] = 0;
     for (int64_t m = 0; m < n_samples; ++m) ++hist[campaign_bin(cost[m], lo, hi, scale, n_bins)];
+}
+
+// ---- the paired difference of two controllers' costs (K31) ----
+// d of one sample: B's cost less A's, one rounded subtraction (negative: B paid less)
+HJB_CAMPAIGN_FN double campaign_pair_diff(double cost_a, double cost_b) { return cost_b - cost_a; }
+
+// The difference record of one start from its n_samples costs under A and under B (cost_a, cost_b [M]; left_a, left_b [M] or null:
+// none left) into out[8]: 0 sum d, 1 sum d*d, 2 min d, 3 max d, 4 n(d < 0), 5 n(d > 0), 6 n(both stayed in the grid), 7 sum d over
+// those - campaign_reduce_start's blocks, trees and fold over campaign_slot(d, both_in), on one thread.
+inline void campaign_pair_start(int64_t n_samples, const double *cost_a, const double *cost_b, const uint8_t *left_a,
+                                const uint8_t *left_b, double *out) {
+    const int G = campaign_group(n_samples, nullptr);
+    CampVals acc = campaign_padding(), v[kCampaignMaxGroup];
+    CampCounts n = {0, 0, 0};                                 // exceed: d < 0; left: d > 0; settled: both in
+    for (int64_t m0 = 0; m0 < n_samples; m0 += G) {
+        for (int j = 0; j < G; ++j) {
+            const int64_t m = m0 + j;
+            if (m >= n_samples) {
+                v[j] = campaign_padding();
+                continue;
+            }
+            const double d = campaign_pair_diff(cost_a[m], cost_b[m]);
+            const bool t = !(left_a && left_a[m]) && !(left_b && left_b[m]);
+            v[j] = campaign_slot(d, t);
+            n.exceed += d < 0 ? 1 : 0;
+            n.left += d > 0 ? 1 : 0;
+            n.settled += t ? 1 : 0;
+        }
+        campaign_tree(v, G);
+        acc = m0 == 0 ? v[0] : campaign_op(acc, v[0]);
+    }
+    out[0] = acc.sum;
+    out[1] = acc.sumsq;
+    out[2] = acc.mn;
+    out[3] = acc.mx;
+    out[4] = (double)n.exceed;
+    out[5] = (double)n.left;
+    out[6] = (double)n.settled;
+    out[7] = acc.sum_settled;
 }
 
 }  // namespace hjb

@@ -165,13 +165,14 @@ int check_weights(Rollout *ro, const char *who, int32_t n_nodes, const double *w
     return HJB_OK;
 }
 
-int check_lookahead_run(Rollout *ro, const char *who, int fly_noise, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj) {
+int check_lookahead_run(Rollout *ro, const char *who, int fly_noise, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj,
+                        bool own_set) {
     if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
     if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
     if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_model", who);
     if (ro->model != kModelAffine)
         return rfail(ro, HJB_E_INVALID, "rollout: %s needs the affine model (hjb_rollout_set_model); the object holds another", who);
-    if (ro->L.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_lookahead", who);
+    if (own_set && ro->L.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_lookahead", who);
     if (fly_noise && ro->N.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s with fly_noise=1 before hjb_rollout_set_noise", who);
     if (n_steps > 0 && !value_plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null value_plane_of_step");
     for (int k = 0; k < n_steps; ++k) {

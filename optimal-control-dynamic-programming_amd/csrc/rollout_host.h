@@ -90,8 +90,10 @@ int check_traj(Rollout *ro, const char *pre, int W, const char *wname, int32_t n
 
 // What hjb_rollout_run_lookahead and hjb_rollout_run_lookahead_campaign refuse of the object and the value planes, in `who`'s name
 // (n_traj: the trajectories or the starts): negative sizes, no or another model, no lookahead set, fly_noise without a noise set,
-// value_plane_of_step against the planes of hjb_rollout_set_values (-1 needs none).  Under ro->mu.
-int check_lookahead_run(Rollout *ro, const char *who, int fly_noise, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj);
+// value_plane_of_step against the planes of hjb_rollout_set_values (-1 needs none).  Under ro->mu.  own_set false: the caller
+// brings the lookahead set (HJB_PAIR_GREEDY's one zero node), the object need not hold one.
+int check_lookahead_run(Rollout *ro, const char *who, int fly_noise, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj,
+                        bool own_set = true);
 
 // What hjb_rollout_set_noise, hjb_rollout_noise_table and hjb_rollout_lookahead_campaign_host refuse of a weight vector (null: equal
 // weights), in `who`'s name: a weight that is not finite or is negative, weights that sum to 0.
@@ -156,6 +158,15 @@ int run_campaign_launches(Rollout *ro, const char *who, int32_t n_steps, const i
                           const double *X0, uint64_t seed, int64_t first_stream, const double *threshold, const double *tol, double *stats,
                           double *device_ms, const std::function<hipError_t(const CampaignLaunch &)> &launch,
                           const CampaignHistCall *hist = nullptr);
+
+// The paired campaign (K31, hjb_rollout_run_campaign_pair) walks the same block list in a loop of its own
+// (rollout_campaign_pair_host.hip: run_campaign_pair_launches, a sibling of run_campaign_launches, which keeps its behaviour and its
+// device-memory bound).  Per launch it starts A's flight kernel, then B's, then k_campaign_fold three times, on the object's
+// stream, and synchronises once.  Its record beside a DCampaign is hjb::DCampPair (kernels_rollout_campaign_pair.h): the pair
+// scratch cost [lanes] doubles and left [lanes] bytes, lanes = nb_max * G of a launch and never n_starts * M, the launch's
+// difference partials [8, n_blocks], and the kernel's role (out: store to the scratch; in: load from it and reduce d).  A call holds
+// [D + 1 + 24, n_starts] doubles (X0, the thresholds, three records), 24 doubles per block of a launch, the scratch, two plane lists
+// and, for HJB_PAIR_GREEDY, the one-node lookahead table; its HJB_E_NOMEM text counts all of it.
 
 // K17 and K21 renormalise the quaternion X0[3..6] of a 7-state column after the first step: all zeros would be 0/0
 int check_quaternions(Rollout *ro, const char *pre, int64_t n_traj, const double *X0);

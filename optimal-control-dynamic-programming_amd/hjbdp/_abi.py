@@ -273,6 +273,12 @@ SYMBOLS = {
                                                 + [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "hjb_rollout_campaign_hist_reduce": (C.c_int32, [C.c_int64, C.c_int64] + [C.POINTER(C.c_double)] * 3
                                          + [C.c_int32, C.POINTER(C.c_int64)]),
+    # two controllers on one plant and the plain campaigns' streams: both plain records and the record of the cost difference
+    "hjb_rollout_run_campaign_pair": (C.c_int32, [C.c_void_p] + [C.c_int32, C.c_int32, C.POINTER(C.c_int32)] * 2
+                                      + [C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_uint64, C.c_int64]
+                                      + [C.POINTER(C.c_double)] * 6),
+    "hjb_rollout_campaign_pair_reduce": (C.c_int32, [C.c_int64, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                     C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_double)]),
     "hjb_rollout_set_attitude_model": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_int32, C.POINTER(C.c_double),
                                                    C.POINTER(C.c_double)]),
     "hjb_rollout_run_attitude": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]
@@ -303,6 +309,10 @@ HJB_DIST_MAX_NODES = 128
 HJB_ROLLOUT_MAX_U = 4
 HJB_CAMPAIGN_NSTAT = 8
 HJB_CAMPAIGN_MAX_BINS = 256
+HJB_CAMPAIGN_PAIR_NSTAT = 8
+HJB_PAIR_LABELS = 0
+HJB_PAIR_LOOKAHEAD = 1
+HJB_PAIR_GREEDY = 2
 HJB_ATT_TAYLOR = 0
 HJB_ATT_RK4 = 1
 HJB_ATTS_FULL = 0

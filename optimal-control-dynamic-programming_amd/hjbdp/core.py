@@ -465,6 +465,30 @@ class Rollout:
                                                                      _f64p(lo), _f64p(hi), nb, _f64p(stats), _i64p(counts), C.byref(ms)))
         return {**_campaign_dict(stats, int(n_samples)), "hist": counts, "hist_lo": lo, "hist_hi": hi, "device_ms": ms.value}
 
+    def run_campaign_pair(self, X0, a, b, n_samples, seed=0, first_stream=0, cost_threshold=None, settle_tol=None):
+        """Two controllers a and b on this object's plant (the affine model under set_noise's nodes), every start of X0
+        [D, n_starts] flown n_samples times by each on the plain campaigns' streams - sample m of start s on stream first_stream +
+        s * n_samples + m under both - and the per-sample cost difference d = cost_b - cost_a reduced per start on the GPU
+        (hjb_rollout_run_campaign_pair): the variance of d holds the pairing that two separately reduced records do not.  A
+        controller is ("labels", plane_of_step, method) - run_campaign's - or ("lookahead", value_plane_of_step) -
+        run_lookahead_campaign's, under set_lookahead's nodes - or ("greedy", value_plane_of_step): the lookahead under one
+        zero node of weight 1, whatever set_lookahead holds.  Returns campaign_pair_reduce's dict with a and b the plain
+        campaigns' dicts (their bits) and device_ms; a negative difference means b paid less."""
+        D = self.D
+        X = _starts(X0, D)
+        ns = X.shape[0]
+        (ka, ma, pa), (kb, mb, pb) = _pair_side(a, "a"), _pair_side(b, "b")
+        if pa.size != pb.size:
+            raise ValueError("a and b: %d and %d steps" % (pa.size, pb.size))
+        thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
+        sa, sb, sd = (np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT)) for _ in range(3))
+        ms = C.c_double(0.0)
+        self._check(self.lib.hjb_rollout_run_campaign_pair(self._ro, ka, ma, _i32p(pa), kb, mb, _i32p(pb), int(pa.size), ns, int(n_samples),
+                                                           _f64p(X), int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol),
+                                                           _f64p(sa), _f64p(sb), _f64p(sd), C.byref(ms)))
+        M = int(n_samples)
+        return {"a": _campaign_dict(sa, M), "b": _campaign_dict(sb, M), **_campaign_pair_dict(sd, M), "device_ms": ms.value}
+
     def set_attitude_model(self, inertia, h, integrator="taylor", q=None, r=None):
         """The 6-D attitude loop instead of the affine one (hjb_rollout_set_attitude_model; the last model set wins):
         inertia = (J1, J2, J3), step h, integrator 'taylor' or 'RK4', stage-cost weights q [7] and r [3] (None: zeros).
@@ -779,6 +803,76 @@ def campaign_reduce(cost, n_samples, X_final=None, left=None, cost_threshold=Non
     _check(lib, None, lib.hjb_rollout_campaign_reduce(ns, M, D, _f64p(c), _f64p(Xf), None if lf is None else lf.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                       _f64p(thr), _f64p(tol), _f64p(stats)))
     return _campaign_dict(stats, M)
+
+
+_PAIR_KIND = {"labels": _abi.HJB_PAIR_LABELS, "lookahead": _abi.HJB_PAIR_LOOKAHEAD, "greedy": _abi.HJB_PAIR_GREEDY}
+
+
+def _pair_side(side, name):
+    """("labels", planes, method) / ("lookahead", value_planes) / ("greedy", value_planes) -> kind, method and the planes"""
+    if not isinstance(side, (tuple, list)) or len(side) < 2 or side[0] not in _PAIR_KIND:
+        raise ValueError('%s must be ("labels", planes, method), ("lookahead", value_planes) or ("greedy", value_planes)' % name)
+    if side[0] == "labels":
+        method = side[2] if len(side) > 2 else "linear"
+        if method not in _LOOKUP:
+            raise ValueError("%s: method must be one of %s" % (name, sorted(_LOOKUP)))
+        return _PAIR_KIND["labels"], _LOOKUP[method], _int32_vector(side[1], "plane_of_step")
+    if len(side) != 2:
+        raise ValueError("%s: a %s controller is (%r, value_planes)" % (name, side[0], side[0]))
+    return _PAIR_KIND[side[0]], 0, _int32_vector(side[1], "value_plane_of_step")
+
+
+def _campaign_pair_dict(stats_d, M):
+    """stats_d [n_starts, 8] as the library wrote it -> the difference entries run_campaign_pair and campaign_pair_reduce return"""
+    total, sumsq = stats_d[:, 0], stats_d[:, 1]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        var = np.maximum((sumsq - total * total / M) / (M - 1), 0.0) if M > 1 else np.zeros(stats_d.shape[0])
+        mean = total / M
+        se = np.sqrt(var / M)
+        t = mean / se
+        n_both = stats_d[:, 6].astype(np.int64)
+        mean_both = np.where(n_both > 0, stats_d[:, 7] / np.maximum(n_both, 1), np.nan)
+    n_b, n_a = stats_d[:, 4].astype(np.int64), stats_d[:, 5].astype(np.int64)
+    return {"stats_d": stats_d, "mean_diff": mean, "var_diff": var, "std_diff": np.sqrt(var), "se_diff": se, "t": t,
+            "min_diff": stats_d[:, 2], "max_diff": stats_d[:, 3], "n_b_lower": n_b, "n_a_lower": n_a, "n_tie": M - n_b - n_a,
+            "n_both_in": n_both, "mean_diff_both_in": mean_both}
+
+
+def campaign_pair_reduce(cost_a, cost_b, n_samples, left_a=None, left_b=None):
+    """Rollout.run_campaign_pair's difference record on the CPU (hjb_rollout_campaign_pair_reduce; no device), over per-trajectory
+    costs of two controllers flown on the same streams, such as run_noisy and run_lookahead(noisy=True) return for starts repeated
+    n_samples times: cost_a, cost_b [n_starts * n_samples] (trajectory s * n_samples + m is sample m of start s), left_a, left_b
+    [n_starts * n_samples] (non-zero: that flight left the grid; None: none left).  d = cost_b - cost_a per sample, one rounded
+    subtraction; a negative d means b paid less.  Returns stats_d [n_starts, 8] (sum d, sum d * d, min d, max d, n(b lower),
+    n(a lower), n(both stayed in the grid), sum d over those: the bits run_campaign_pair returns for the same samples),
+    mean_diff, var_diff = (sumsq - sum^2 / M) / (M - 1) clipped at 0 (0 for M = 1), std_diff, se_diff = sqrt(var_diff / M),
+    t = mean_diff / se_diff under numpy's rules (inf or NaN where se_diff is 0), min_diff, max_diff, n_b_lower, n_a_lower,
+    n_tie = M - n_b_lower - n_a_lower - a NaN difference is neither lower and is counted here, as a tie -, n_both_in and
+    mean_diff_both_in (NaN where no sample of the start kept both flights in the grid); a and b, campaign_reduce's dicts of the two
+    cost arrays, and device_ms = 0.0."""
+    lib = load_library()
+    ca = np.ascontiguousarray(np.asarray(cost_a, dtype=np.float64).reshape(-1))
+    cb = np.ascontiguousarray(np.asarray(cost_b, dtype=np.float64).reshape(-1))
+    M = int(n_samples)
+    if ca.size != cb.size:
+        raise ValueError("cost_a and cost_b: %d and %d values" % (ca.size, cb.size))
+    if M < 1 or ca.size % M:
+        raise ValueError("cost: %d values are not a whole number of %d samples" % (ca.size, M))
+    ns = ca.size // M
+    flags = []
+    for name, left in (("left_a", left_a), ("left_b", left_b)):
+        lf = None
+        if left is not None:
+            lf = np.ascontiguousarray((np.asarray(left).reshape(-1) != 0).astype(np.uint8))
+            if lf.size != ca.size:
+                raise ValueError("%s: %d flags for %d costs" % (name, lf.size, ca.size))
+        flags.append(lf)
+    u8p = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
+    stats_d = np.empty((ns, _abi.HJB_CAMPAIGN_PAIR_NSTAT))
+    _check(lib, None, lib.hjb_rollout_campaign_pair_reduce(ns, M, _f64p(ca), _f64p(cb), u8p(flags[0]), u8p(flags[1]), _f64p(stats_d)))
+    # a and b: the plain records of the two cost arrays (campaign_reduce, no threshold and no tolerance); no device ran
+    return {"a": campaign_reduce(ca, M, left=flags[0]), "b": campaign_reduce(cb, M, left=flags[1]), **_campaign_pair_dict(stats_d, M),
+            "device_ms": 0.0}
 
 
 def greedy_host(knots, u_table, A, B, J, X0, value_plane_of_step, c=None, q=None, r=None, index_base=0, keep_path=False):

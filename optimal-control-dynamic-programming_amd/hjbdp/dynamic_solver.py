@@ -548,6 +548,64 @@ class Dynamic_Solver:
         return {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) and key != "q" else v)
                 for key, v in out.items()}
 
+    _PAIR_CONTROLLERS = ("labels", "nominal", "disturbed")
+
+    def get_paired_cost_statistics(self, X0s, n_samples, a="labels", b="disturbed", seed=0, mode="Nssu", ssu_num=1, method="linear",
+                                   cost_threshold=None, settle_tol=None):
+        """Two controllers flown on the same samples and their cost DIFFERENCE reduced per start on the GPU
+        (hjbdp.Rollout.run_campaign_pair): every start of X0s [S, n] flown n_samples times under self.disturbance's nodes by
+        controller a and by controller b, sample j of start i on stream i * n_samples + j of `seed` under both, and nothing of
+        length n * n_samples on the host or on the device.  Controllers: 'labels' (get_noisy_cost_statistics' stored policy, read
+        with `method`), 'disturbed' and 'nominal' (get_lookahead_cost_statistics' two lookaheads on J_star).  The planes, the
+        streams and the start numbering are those methods', so the entries a and b of the result are their dicts, bit for bit.
+        Returns run_campaign_pair's dict, one entry per start: a, b, stats_d [n, 8], mean_diff (b less a: negative where b paid
+        less), var_diff, std_diff, se_diff, t, min_diff, max_diff, n_b_lower, n_a_lower, n_tie, n_both_in, mean_diff_both_in,
+        device_ms - whether the stored labels lose to the value function they came from, with its standard error."""
+        from .core import Rollout
+        if self.J_star is None or self.u_star_idxs is None:
+            raise RuntimeError("run() first")
+        if self.disturbance is None:
+            raise RuntimeError("get_paired_cost_statistics needs self.disturbance = (offsets [2, W], weights or None, mode)")
+        for name, ctl in (("a", a), ("b", b)):
+            if ctl not in self._PAIR_CONTROLLERS:
+                raise ValueError("%s must be one of %s" % (name, ", ".join(repr(c) for c in self._PAIR_CONTROLLERS)))
+        offsets, weights = self.disturbance[0], self.disturbance[1]
+        dmode = self.disturbance[2] if len(self.disturbance) > 2 else "expect"
+        N, S = self.N, self.S
+        n_st = N - 1
+        if mode == "ssu":
+            if not 1 <= int(ssu_num) <= n_st:
+                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
+            label_planes, value_planes = np.full(n_st, int(ssu_num) - 1, dtype=np.int32), np.full(n_st, int(ssu_num), dtype=np.int32)
+        elif mode == "Nssu":
+            label_planes, value_planes = np.arange(n_st, dtype=np.int32), np.arange(1, N, dtype=np.int32)
+        else:
+            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        if int(n_samples) < 1:
+            raise ValueError("n_samples must be at least 1")
+        side = {"labels": ("labels", label_planes, method), "nominal": ("greedy", value_planes), "disturbed": ("lookahead", value_planes)}
+        s_r = np.asarray(self.s_r, dtype=np.float64)
+        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
+        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
+            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+            ro.set_values(self.J_star)
+            ro.set_lookahead(offsets, weights, dmode)
+            ro.set_noise(offsets, weights)
+            return ro.run_campaign_pair(np.asarray(X0s, dtype=np.float64).reshape(S, -1), side[a], side[b], int(n_samples), seed=seed,
+                                        first_stream=0, cost_threshold=cost_threshold, settle_tol=settle_tol)
+
+    def paired_cost_map(self, n_samples, a="labels", b="disturbed", seed=0, mode="Nssu", ssu_num=1, method="linear", cost_threshold=None,
+                        settle_tol=None):
+        """get_paired_cost_statistics at every grid node: each per-start entry shaped like the grid, [dx, dx] (stats_d [dx, dx, 8]; a
+        and b dicts of such entries), node (i, j) = (s_r[i], s_r[j]) flown from stream (i + dx * j) * n_samples on - noisy_cost_map's
+        and lookahead_cost_map's starts on their streams, so a and b equal those maps bit for bit and mean_diff is their means'
+        difference WITH its standard error se_diff and the sign counts, node by node."""
+        dx, X0s = self._grid_starts()
+        out = self.get_paired_cost_statistics(X0s, n_samples, a=a, b=b, seed=seed, mode=mode, ssu_num=ssu_num, method=method,
+                                              cost_threshold=cost_threshold, settle_tol=settle_tol)
+        shape = lambda d: {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) else v) for key, v in d.items()}
+        return {key: (shape(v) if isinstance(v, dict) else v) for key, v in shape(out).items()}
+
     @staticmethod
     def compare_data(obj1, obj2):
         # Dynamic_Solver.m:266-280

@@ -30,8 +30,11 @@ Two cases, one JSON line:
   (n) campaign_hist: the campaign histogram (K30, hjb_rollout_run_campaign_hist) beside K28 on the same starts, and the two-pass
       quantile map beside one plain map, see case_campaign_hist; alone, it also writes its line to
       profiles/rollout_campaign_hist_time.json.
+  (o) campaign_pair: the paired campaign (K31, hjb_rollout_run_campaign_pair: labels 'linear' against the disturbed lookahead) beside
+      K28 and K29 on the same starts, see case_campaign_pair; alone, it also writes its line to
+      profiles/rollout_campaign_pair_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy,lookahead,campaign,lookahead_campaign,campaign_hist] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy,lookahead,campaign,lookahead_campaign,campaign_hist,campaign_pair] [--out FILE]
 """
 from __future__ import annotations
 
@@ -862,6 +865,86 @@ def case_campaign_hist(host=True, n_starts=1 << 14, n_samples=64, n_bins=64):
     return res
 
 
+def case_campaign_pair(host=True, n_starts=1 << 14, n_samples=64):
+    """(o) campaign_pair: case_lookahead_campaign's problem (Kirk solved under the 9-node Gauss-Hermite set, 100 candidates x 9 nodes
+    a step), 2^14 starts x 64 samples x 129 steps: K31 (hjb_rollout_run_campaign_pair with A the stored labels read 'linear' and B
+    the disturbed lookahead: 24 doubles per start come back) beside K28 (hjb_rollout_run_campaign) and K29
+    (hjb_rollout_run_lookahead_campaign) on one object in one process.  The three alternate, three rounds after a warm-up round of
+    the same shapes; per round the kernel time (device_ms: event times around the launches, the fold kernels included) and the
+    whole call's wall time, the medians and their ratios quoted.  `pass`: K31's kernel time <= 1.05 x (K28's + K29's) in this run -
+    the pair adds one store and one load per lane and one more block partial and fold to two flights it does not change, and 5 %
+    is the margin the campaign forms carry against their bases.  It is measured against K28 + K29, never against a K31 number.
+    Beside the times, what the pairing buys, over the starts whose 2 x 64 flights all stayed in the grid: the median of var_diff /
+    (var_a + var_b) (1 would be independent samples), the share of starts with |t| > 2, and the grid-mean mean_diff with its
+    standard error over the starts.  `host` is not used."""
+    import hjbdp
+    ds = hjbdp.Dynamic_Solver(precision="double")
+    ds.N, ds.dx, ds.du = 130, 35, 100
+    off, w = hjbdp.gaussian_nodes([0.02, 0.05], order=3)
+    ds.disturbance = (off, w, "expect")
+    ds.run()
+    s_r = np.asarray(ds.s_r, dtype=np.float64)
+    rng = np.random.default_rng(1)
+    X = rng.uniform(s_r[0], s_r[-1], size=(2, n_starts))
+    K = ds.N - 1
+    lplanes, vplanes = np.arange(K), np.arange(1, K + 1)         # J_star's last plane is the zero terminal
+    ns, M = n_starts, n_samples
+    res = {"grid": "35x35", "planes": int(K), "values": str(ds.J_star.dtype), "n_steps": int(K), "n_candidates": int(ds.du),
+           "nodes": int(off.shape[1]), "mode": "expect", "n_starts": int(ns), "n_samples": int(M), "n_traj": int(ns * M),
+           "a": "labels, linear", "b": "lookahead under the solve's node set",
+           "noise": "gaussian_nodes(sigma = (0.02, 0.05), order 3) on both axes: the solve's, the lookahead's and the plant's",
+           "timing": "device_ms: event times around the launches (rollout and fold kernels); wall_ms: the whole Python call; "
+                     "the three runs alternate in one process, 3 rounds after a warm-up round"}
+    ms = {"k28": [], "k29": [], "k31": []}
+    wall = {"k28": [], "k29": [], "k31": []}
+    with hjbdp.Rollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro:
+        ro.set_model(ds.A, ds.B, q=np.diag(ds.Q), r=[ds.R])
+        ro.set_values(ds.J_star)
+        ro.set_lookahead(off, w, "expect")
+        ro.set_noise(off, w)
+        for rnd in range(4):
+            t0 = time.perf_counter()
+            a = ro.run_campaign(X, lplanes, M, seed=1, method="linear")
+            t1 = time.perf_counter()
+            b = ro.run_lookahead_campaign(X, vplanes, M, seed=1)
+            t2 = time.perf_counter()
+            p = ro.run_campaign_pair(X, ("labels", lplanes, "linear"), ("lookahead", vplanes), M, seed=1)
+            t3 = time.perf_counter()
+            if rnd:                                               # round 0 is the warm-up
+                for key, out, dt in (("k28", a, t1 - t0), ("k29", b, t2 - t1), ("k31", p, t3 - t2)):
+                    ms[key].append(out["device_ms"])
+                    wall[key].append(dt * 1e3)
+    for key in ms:
+        med = float(np.median(ms[key]))
+        res[key] = {"device_ms": [round(t, 3) for t in ms[key]], "device_ms_median": round(med, 3),
+                    "wall_ms": [round(t, 1) for t in wall[key]], "wall_ms_median": round(float(np.median(wall[key])), 1)}
+    base = res["k28"]["device_ms_median"] + res["k29"]["device_ms_median"]
+    res["k28_plus_k29_kernel_ms"] = round(base, 3)
+    res["k31_over_k28_plus_k29_kernel"] = res["k31"]["device_ms_median"] / base
+    res["k31_over_k28_plus_k29_wall"] = res["k31"]["wall_ms_median"] / (res["k28"]["wall_ms_median"] + res["k29"]["wall_ms_median"])
+    res["host_bytes_per_call"] = {"k28": int(ns * (2 + 8) * 8), "k29": int(ns * (2 + 8) * 8), "k31": int(ns * (2 + 24) * 8)}
+    same = lambda x, y: bool(np.array_equal(x.view(np.uint64), y.view(np.uint64)))
+    res["stats_a_bit_equal_k28"] = same(p["a"]["stats"], a["stats"])
+    res["stats_b_bit_equal_k29"] = same(p["b"]["stats"], b["stats"])
+    kept = (p["n_both_in"] == M) & np.isfinite(p["stats_d"][:, 1])         # starts none of whose 2 x 64 flights left the grid
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratio = p["var_diff"][kept] / (p["a"]["var"][kept] + p["b"]["var"][kept])
+        t = p["t"][kept]
+    md = p["mean_diff"][kept]
+    res["what_pairing_buys"] = {"starts_kept_inside_by_both": int(kept.sum()),
+                                "median_var_diff_over_var_a_plus_var_b": float(np.nanmedian(ratio)),
+                                "share_of_starts_with_abs_t_above_2": float(np.mean(np.abs(t) > 2)),
+                                "share_of_starts_b_lower_on_average": float(np.mean(md < 0)),
+                                "labels_mean": float(np.mean(p["a"]["mean"][kept])), "lookahead_mean": float(np.mean(p["b"]["mean"][kept])),
+                                "grid_mean_mean_diff": float(np.mean(md)),
+                                "grid_mean_mean_diff_se_over_starts": float(np.std(md, ddof=1) / np.sqrt(max(int(kept.sum()), 1))),
+                                "median_se_diff_per_start": float(np.median(p["se_diff"][kept])),
+                                "median_unpaired_se_per_start": float(np.median(np.sqrt((p["a"]["var"][kept] + p["b"]["var"][kept]) / M)))}
+    res["bound"] = 1.05
+    res["pass"] = bool(res["k31_over_k28_plus_k29_kernel"] <= res["bound"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -877,7 +960,8 @@ def main():
                   "position_loop": case_position_loop, "attitude_simplified_loop": case_attitude_simplified_loop,
                   "attitude_linear_loop": case_attitude_linear_loop, "pos_att_faults": case_pos_att_faults,
                   "kirk_noisy": case_kirk_noisy, "greedy": case_greedy, "lookahead": case_lookahead, "campaign": case_campaign,
-                  "lookahead_campaign": case_lookahead_campaign, "campaign_hist": case_campaign_hist}[c](host=not a.no_host)
+                  "lookahead_campaign": case_lookahead_campaign, "campaign_hist": case_campaign_hist,
+                  "campaign_pair": case_campaign_pair}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.cases == "position_loop" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
@@ -899,6 +983,8 @@ def main():
         (ROOT / "profiles" / "rollout_lookahead_campaign_time.json").write_text(json.dumps(res) + "\n")
     if a.cases == "campaign_hist" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_campaign_hist_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "campaign_pair" and not a.out:                  # its own record: one line
+        (ROOT / "profiles" / "rollout_campaign_pair_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
