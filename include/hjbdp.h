@@ -101,7 +101,14 @@ typedef struct hjb_problem {
        components x4,x5,x6,x7 of the grid angles (Solver_attitude.m:419-421; arrays over (n[0],n[1],n[2]),
        column-major, problem dtype HJB_F32/HJB_F16S) and the knots of axes 3..5.  This replaces the three
        nS-sized next-angle tables, which do not fit at 51^6.  atan2/asin use the library's own
-       fixed polynomial forms, so that results are reproducible bit for bit across CPUs/GPUs. */
+       fixed polynomial forms, so that results are reproducible bit for bit across CPUs/GPUs.
+       The pitch argument s = -2 (x6 x4 - x7 x5) is clamped to [-1, 1] before the asin (the clamp is ours, the
+       reference would go complex: at pitch +-90 degrees the rounded quaternion gives |s| = 1 + 1..2 ulp), so a
+       grid with a pitch knot at +-pi/2 gives next pitch +-float(pi/2), never NaN; where |s| <= 1 nothing changes.
+       The atan2 reads the signs of its arguments with `< 0`, so a zero of either sign counts as positive: it
+       returns +pi at (y = -0, x < 0) where libm returns -pi, and 0 at (y = +-0, x = -0) where libm returns
+       +-pi, and +0 at (y = -0, x >= 0) where libm returns -0.  Everywhere else it is within 4 ulp of libm.  The tables must be finite and
+       no entry the zero quaternion (0 / 0 is the caller's error). */
     int32_t model;
     int32_t table_dtype;            /* HJB_TAB_DEFAULT (0): next-state terms are arrays of the problem dtype and the
                                        queries are formed, located and weighted in it.  HJB_TAB_F64 (dtype HJB_F32 /

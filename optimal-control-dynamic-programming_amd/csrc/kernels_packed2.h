@@ -106,7 +106,10 @@ __device__ __forceinline__ void model_quat_next(const DParams *__restrict__ P, c
     const float nrm = __builtin_sqrtf(((x4 * x4 + x5 * x5) + x6 * x6) + x7 * x7);   // :477
     x4 = __fdiv_rn(x4, nrm); x5 = __fdiv_rn(x5, nrm); x6 = __fdiv_rn(x6, nrm); x7 = __fdiv_rn(x7, nrm);   // :480-483
     out[0] = canon_atan2f(2.0f * (x6 * x5 + x7 * x4), ((x7 * x7 + x6 * x6) - x5 * x5) - x4 * x4);   // :485-486
-    out[1] = canon_asinf(-2.0f * (x6 * x4 - x7 * x5));                                              // :487
+    // the clamp is ours (the reference would go complex): at pitch +-90 degrees the rounded quaternion gives |s| = 1 + 1..2 ulp
+    float s = -2.0f * (x6 * x4 - x7 * x5);                                                          // :487
+    s = s > 1.0f ? 1.0f : s < -1.0f ? -1.0f : s;
+    out[1] = canon_asinf(s);
     out[2] = canon_atan2f(2.0f * (x5 * x4 + x7 * x6), ((x7 * x7 - x6 * x6) - x5 * x5) + x4 * x4);   // :488-489
 }
 

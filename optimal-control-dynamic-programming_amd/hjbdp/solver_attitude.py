@@ -173,7 +173,7 @@ class Solver_attitude:
         X4n, X5n, X6n, X7n = X4n / nrm, X5n / nrm, X6n / nrm, X7n / nrm
         two = f32(2)
         yaw_n = np.arctan2(two * (X6n * X5n + X7n * X4n), X7n ** 2 + X6n ** 2 - X5n ** 2 - X4n ** 2)      # :485-486
-        pitch_n = np.arcsin(-two * (X6n * X4n - X7n * X5n))                                               # :487
+        pitch_n = np.arcsin(np.clip(-two * (X6n * X4n - X7n * X5n), f32(-1), f32(1)))                     # :487 (the clamp: hjbdp.h)
         roll_n = np.arctan2(two * (X5n * X4n + X7n * X6n), X7n ** 2 - X6n ** 2 - X5n ** 2 + X4n ** 2)     # :488-489
         st6 = (0, 1, 2, 3, 4, 5)
         nxt = [[Term((0,), X1V), Term((1, 2, 6), t1)],

@@ -145,12 +145,13 @@ def backup_states_sparse(abi, spec, keys, vals, states, nthreads=0):
 
 
 def canon_eval(abi, kind, a, b=None):
-    """The fixed polynomial atan2 (kind 'atan2': a = y, b = x) / asin (kind 'asin') of the quaternion model."""
+    """The fixed polynomial atan2 (kind 'atan2': a = y, b = x) / asin (kind 'asin') of the quaternion model; kind 'pitch': asin as
+    the model calls it, its argument clamped to [-1, 1]."""
     l = lib(abi)
     a = np.ascontiguousarray(a, dtype=np.float32)
     b = np.ascontiguousarray(a if b is None else b, dtype=np.float32)
     out = np.empty_like(a)
-    l.orc_canon_eval({"atan2": 0, "asin": 1}[kind], a.size, a.ctypes.data, b.ctypes.data, out.ctypes.data)
+    l.orc_canon_eval({"atan2": 0, "asin": 1, "pitch": 2}[kind], a.size, a.ctypes.data, b.ctypes.data, out.ctypes.data)
     return out
 
 

@@ -137,8 +137,16 @@ static float canon_asinf(float x) {
     return x < 0.0f ? -v : v;
 }
 
+/* The pitch call of the model: the clamp is ours (the reference would go complex) - at pitch +-90 degrees the rounded
+ * quaternion gives |s| = 1 + 1..2 ulp, and canon_asinf would take the square root of a negative number. */
+static float model_pitch(float s) {
+    s = s > 1.0f ? 1.0f : s < -1.0f ? -1.0f : s;
+    return canon_asinf(s);
+}
+
+/* kind 0: canon_atan2f(a, b); 1: canon_asinf(a); 2: model_pitch(a) */
 void orc_canon_eval(int kind, int64_t n, const float *a, const float *b, float *out) {
-    for (int64_t i = 0; i < n; ++i) out[i] = kind == 0 ? canon_atan2f(a[i], b[i]) : canon_asinf(a[i]);
+    for (int64_t i = 0; i < n; ++i) out[i] = kind == 0 ? canon_atan2f(a[i], b[i]) : kind == 1 ? canon_asinf(a[i]) : model_pitch(a[i]);
 }
 
 /* gi: grid indices of the state; W = knots of axes 3..5 (single) */
@@ -154,7 +162,7 @@ static void model_quat_next(const hjb_problem *p, const int *gi, float w1, float
     const float nrm = sqrtf(((x4 * x4 + x5 * x5) + x6 * x6) + x7 * x7); /* :477 */
     x4 = x4 / nrm; x5 = x5 / nrm; x6 = x6 / nrm; x7 = x7 / nrm;         /* :480-483 */
     out3[0] = canon_atan2f(2.0f * (x6 * x5 + x7 * x4), ((x7 * x7 + x6 * x6) - x5 * x5) - x4 * x4);   /* :485-486 */
-    out3[1] = canon_asinf(-2.0f * (x6 * x4 - x7 * x5));                                              /* :487 */
+    out3[1] = model_pitch(-2.0f * (x6 * x4 - x7 * x5));                                              /* :487, clamped */
     out3[2] = canon_atan2f(2.0f * (x5 * x4 + x7 * x6), ((x7 * x7 - x6 * x6) - x5 * x5) + x4 * x4);   /* :488-489 */
 }
 
