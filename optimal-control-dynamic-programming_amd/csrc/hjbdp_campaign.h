@@ -61,6 +61,36 @@ HJB_CAMPAIGN_FN int campaign_group(int64_t n_samples, int *log2_out) {
     return g;
 }
 
+// The launch geometry of a campaign call and the device bytes it holds (host only; the device loop of rollout_campaign_host.hip
+// and tests/campaign_harness.cpp): n_starts >= 1 starts of n_samples >= 1 samples, D axes, n_steps steps, launches of at most
+// `chunk` lanes, `records` records of 8 doubles per start (1; the pair's 3) with as many partial arrays, `plane_lists` lists of the
+// steps' planes (1; the pair's 2), n_bins bins or 0 for no histogram, the pair scratch and HJB_PAIR_GREEDY's one-node table.
+struct CampaignGeometry {
+    int G, log2G;                     // campaign_group's
+    int64_t B, n_blocks;              // blocks per start, blocks of the call (<= n_starts * n_samples)
+    int64_t nb_max, lanes_max;        // blocks and lanes of a launch at most: a launch is never smaller than one block
+    // bytes: X0, the records, the thresholds, the partials, the plane lists (one entry each at least), the histogram's
+    // [lo | hi | scale] and counts, the scratch's one double and one byte per lane of a launch, 16 for the table
+    uint64_t need;
+};
+
+inline CampaignGeometry campaign_geometry(int64_t n_starts, int64_t n_samples, int D, int32_t n_steps, int64_t chunk, int records,
+                                          int plane_lists, bool has_threshold, int n_bins, bool scratch, bool greedy) {
+    CampaignGeometry g;
+    g.G = campaign_group(n_samples, &g.log2G);
+    g.B = (n_samples + g.G - 1) / g.G;
+    g.n_blocks = n_starts * g.B;
+    const int64_t per_launch = chunk / g.G;
+    g.nb_max = per_launch < 1 ? 1 : per_launch;
+    if (g.n_blocks < g.nb_max) g.nb_max = g.n_blocks;
+    g.lanes_max = g.nb_max * g.G;
+    const uint64_t ns = (uint64_t)n_starts, R = (uint64_t)records;
+    g.need = 8 * (uint64_t)D * ns + R * 64 * ns + (has_threshold ? 8 * ns : 0) + R * 64 * (uint64_t)g.nb_max +
+             (uint64_t)plane_lists * 4 * (uint64_t)(n_steps > 1 ? n_steps : 1) + (n_bins ? 24 * ns + 8 * (uint64_t)(n_bins + 2) * ns : 0) +
+             (scratch ? 9 * (uint64_t)g.lanes_max : 0) + (greedy ? 16 : 0);
+    return g;
+}
+
 HJB_CAMPAIGN_FN CampVals campaign_padding() {
     CampVals v;
     v.sum = 0.0;

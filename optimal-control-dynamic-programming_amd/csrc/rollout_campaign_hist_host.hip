@@ -1,9 +1,10 @@
 // rollout_campaign_hist_host.hip - hjb_rollout_run_campaign_hist, hjb_rollout_run_lookahead_campaign_hist and
 // hjb_rollout_campaign_hist_reduce (include/hjbdp.h): the host side of the campaign histograms (K30,
 // kernels_rollout_campaign_hist.h / kernels_rollout_lookahead_campaign_hist.h).  The run functions make the plain campaign's
-// refusals in the plain campaign's order and the histogram's own (check_campaign_hist) before any device work, then K28's device
-// side (run_campaign_launches) with the histogram and K30's launch.  The host reduce bins a cost array with hjbdp_campaign.h's
-// campaign_bin in a plain loop, with no device.  No kernel is instantiated in this unit.
+// refusals in the plain campaign's order and the histogram's own (check_campaign_hist) before any device work - the campaigns' one
+// entry frame (run_campaign_call, rollout_campaign_host.hip) with n_bins refused before an object is needed - then the campaigns'
+// one device loop (run_campaign_launches) with the histogram in the plan and K30's launch.  The host reduce bins a cost array
+// with hjbdp_campaign.h's campaign_bin in a plain loop, with no device.  No kernel is instantiated in this unit.
 #include "rollout_host.h"
 #include "kernels_rollout_lookahead_campaign_hist.h"
 
@@ -34,67 +35,52 @@ static_assert(HJB_CAMPAIGN_MAX_BINS == hjb::kCampaignMaxBins, "the header's boun
 
 extern "C" {
 
+// what a histogram call refuses before it needs an object: n_bins out of range, in check_campaign_hist's text
+static int check_n_bins(Rollout *ro, const char *who, const CampaignHistCall &h) {
+    return h.n_bins < 1 || h.n_bins > HJB_CAMPAIGN_MAX_BINS ? check_campaign_hist(ro, who, 0, h) : HJB_OK;
+}
+
 int32_t hjb_rollout_run_campaign_hist(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts,
                                       int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream, const double *threshold,
                                       const double *tol, const double *lo, const double *hi, int32_t n_bins, double *stats, int64_t *hist,
                                       double *device_ms) {
-    Rollout *ro = (Rollout *)rollout;
-    const char *const who = "hjb_rollout_run_campaign_hist";
+    const CampaignCall call{"hjb_rollout_run_campaign_hist", n_steps, n_starts, n_samples, X0, seed, first_stream, threshold, tol, device_ms};
     const CampaignHistCall h{lo, hi, n_bins, hist};
-    // every refusal before any device work, the outputs untouched; the ones that need no object first
-    if (const int bad = check_campaign_streams(ro, who, n_starts, n_samples, first_stream)) return bad;
-    if (n_bins < 1 || n_bins > HJB_CAMPAIGN_MAX_BINS) return check_campaign_hist(ro, who, 0, h);
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    if (const int bad = check_run(ro, kModelAffine, method, n_steps, plane_of_step, n_starts)) return bad;
-    if (ro->N.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_noise", who);
-    if (n_starts == 0) {
-        if (device_ms) *device_ms = 0.0;
-        return HJB_OK;
-    }
-    const int D = ro->D;
-    if (!stats) return rfail(ro, HJB_E_INVALID, "%s: null stats", who);
-    if (const int bad = check_traj(ro, "rollout", D, "D", n_steps, n_starts, X0, stats)) return bad;
-    if (const int bad = check_campaign_bounds(ro, who, D, n_starts, threshold, tol)) return bad;
-    if (const int bad = check_campaign_hist(ro, who, n_starts, h)) return bad;
-    if (device_ms) *device_ms = 0.0;
-    return run_campaign_launches(
-        ro, who, n_steps, plane_of_step, n_starts, n_samples, X0, seed, first_stream, threshold, tol, stats, device_ms,
-        [&](const CampaignLaunch &c) {
-            return launch_rollout_campaign_hist(ro->idx_bytes, method, c.lds_on, ro->D, c.R, c.N, c.C, c.H, c.lds, c.st, c.X0, c.stats);
+    CampaignPlan plan;
+    plan.stats[0] = stats;
+    plan.planes[0] = plane_of_step;
+    plan.hist = &h;
+    return run_campaign_call(
+        rollout, call, plan, [&](Rollout *ro) { return check_n_bins(ro, call.who, h); },
+        [&](Rollout *ro) {
+            if (const int bad = check_run(ro, kModelAffine, method, n_steps, plane_of_step, n_starts)) return bad;
+            return ro->N.n_nodes < 1 ? rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_noise", call.who) : HJB_OK;
         },
-        &h);
+        [&](const CampaignLaunch &c) {
+            const Rollout *ro = (const Rollout *)rollout;
+            return launch_rollout_campaign_hist(ro->idx_bytes, method, c.lds_on, ro->D, c.R[0], c.N, c.C[0], c.H, c.lds, c.st, c.X0, c.stats[0]);
+        });
 }
 
 int32_t hjb_rollout_run_lookahead_campaign_hist(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
                                                 int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
                                                 const double *threshold, const double *tol, const double *lo, const double *hi,
                                                 int32_t n_bins, double *stats, int64_t *hist, double *device_ms) {
-    Rollout *ro = (Rollout *)rollout;
-    const char *const who = "hjb_rollout_run_lookahead_campaign_hist";
+    const CampaignCall call{"hjb_rollout_run_lookahead_campaign_hist", n_steps, n_starts, n_samples, X0, seed, first_stream, threshold, tol,
+                            device_ms};
     const CampaignHistCall h{lo, hi, n_bins, hist};
-    if (const int bad = check_campaign_streams(ro, who, n_starts, n_samples, first_stream)) return bad;
-    if (n_bins < 1 || n_bins > HJB_CAMPAIGN_MAX_BINS) return check_campaign_hist(ro, who, 0, h);
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    if (const int bad = check_lookahead_run(ro, who, 1, n_steps, value_plane_of_step, n_starts)) return bad;
-    if (n_starts == 0) {
-        if (device_ms) *device_ms = 0.0;
-        return HJB_OK;
-    }
-    const int D = ro->D;
-    if (!stats) return rfail(ro, HJB_E_INVALID, "%s: null stats", who);
-    if (const int bad = check_traj(ro, "rollout", D, "D", n_steps, n_starts, X0, stats)) return bad;
-    if (const int bad = check_campaign_bounds(ro, who, D, n_starts, threshold, tol)) return bad;
-    if (const int bad = check_campaign_hist(ro, who, n_starts, h)) return bad;
-    if (device_ms) *device_ms = 0.0;
-    return run_campaign_launches(
-        ro, who, n_steps, value_plane_of_step, n_starts, n_samples, X0, seed, first_stream, threshold, tol, stats, device_ms,
+    CampaignPlan plan;
+    plan.stats[0] = stats;
+    plan.planes[0] = value_plane_of_step;
+    plan.hist = &h;
+    return run_campaign_call(
+        rollout, call, plan, [&](Rollout *ro) { return check_n_bins(ro, call.who, h); },
+        [&](Rollout *ro) { return check_lookahead_run(ro, call.who, 1, n_steps, value_plane_of_step, n_starts); },
         [&](const CampaignLaunch &c) {
-            const DLookCampaignHistArgs K{{c.R, ro->dvalues, ro->L, c.N, c.C, c.X0}, c.H};
-            return launch_rollout_lookahead_campaign_hist(ro->val_bytes, c.lds_on, D, K, c.lds, c.st, c.stats);
-        },
-        &h);
+            const Rollout *ro = (const Rollout *)rollout;
+            const DLookCampaignHistArgs K{{c.R[0], ro->dvalues, ro->L, c.N, c.C[0], c.X0}, c.H};
+            return launch_rollout_lookahead_campaign_hist(ro->val_bytes, c.lds_on, ro->D, K, c.lds, c.st, c.stats[0]);
+        });
 }
 
 int32_t hjb_rollout_campaign_hist_reduce(int64_t n_starts, int64_t n_samples, const double *cost, const double *lo, const double *hi,

@@ -1,6 +1,6 @@
 // rollout_host.h - what the host units of the rollouts share (host only; include/hjbdp.h is the public ABI): the object,
-// its refusals, the upload and the chunk loop.  Defined in rollout.hip (the campaigns' size and bound checks:
-// rollout_campaign_host.hip); rollout_channels.hip, rollout_campaign_host.hip and rollout_lookahead_campaign_host.hip are the other
+// its refusals, the upload, the chunk loop and the campaigns' entry frame and device loop.  Defined in rollout.hip (the campaigns'
+// checks, frame and loop: rollout_campaign_host.hip); rollout_channels.hip and the four rollout_*campaign*_host.hip are the other
 // readers.
 #pragma once
 #include "hjbdp_host.h"
@@ -123,21 +123,27 @@ int check_campaign_bounds(Rollout *ro, const char *who, int D, int64_t n_starts,
 // ... and, with the sizes first, of their streams: first_stream < 0, first_stream + n_starts * n_samples overflowing
 int check_campaign_streams(Rollout *ro, const char *who, int64_t n_starts, int64_t n_samples, int64_t first_stream);
 
-// One launch of a campaign call, as run_campaign_launches hands it to the controller's launch function: the object's record with
-// the planes of the steps on the device, the noise set with the call's seed and first stream, the launch's blocks, the LDS
-// bytes of the channel's tables and the node block together (hjb_rollout_run_noisy's rule), X0 [D, n_starts] and stats
-// [8, n_starts] on the device.  In a histogram call (K30) lds is the launch's dynamic LDS bytes and lds_on the tables' placement as
-// campaign_hist_form decided them, and H the histogram's record; H.hist is null in a plain call.
+// The launches of a campaign call, as run_campaign_launches hands them to the call's launch function - built once per call, only
+// C[r].block0 and C[r].n_blocks move from launch to launch: the object's record with each plane list on the device (R[1] is the
+// pair's second), the noise set with the call's seed and first stream, one DCampaign per record - one geometry, each its own
+// partials - the LDS bytes of the channel's tables and the node block together (hjb_rollout_run_noisy's rule), X0 [D, n_starts]
+// and every record's stats [8, n_starts] on the device.  In a histogram call (K30) lds is the launch's dynamic LDS bytes and
+// lds_on the tables' placement as campaign_hist_form decided them, and H the histogram's record; H.hist is null otherwise.  In a
+// pair call (K31) pair_cost [lanes] doubles and pair_left [lanes] bytes are the pair scratch, lanes = nb_max * G of a launch and
+// never n_starts * M, and Lg HJB_PAIR_GREEDY's set (one zero node of weight 1; Lg.tab null unless a side is greedy).
 struct CampaignLaunch {
-    hjb::DRollout R;
+    hjb::DRollout R[2];
     hjb::DNoise N;
-    hjb::DCampaign C;
+    hjb::DCampaign C[3];
     size_t lds;
     bool lds_on;
     hipStream_t st;
     const double *X0;
-    double *stats;
+    double *stats[3];
     hjb::DCampHist H;
+    double *pair_cost;
+    uint8_t *pair_left;
+    hjb::LookSet Lg;
 };
 
 // The histogram of a campaign call (K30), on the host: lo, hi [n_starts], n_bins and the output hist [n_bins + 2, n_starts]
@@ -150,23 +156,48 @@ struct CampaignHistCall {
 // HJB_CAMPAIGN_MAX_BINS; with n_starts > 0 a null lo, hi or hist, a lo or hi that is not finite, !(lo < hi), a scale that is not finite
 int check_campaign_hist(Rollout *ro, const char *who, int64_t n_starts, const CampaignHistCall &h);
 
-// The device side of a campaign call whose arguments have been checked (n_starts >= 1; rollout_campaign_host.hip): what a call
-// holds on the device is [D + 1 + 8, n_starts] doubles and 8 doubles per block of a launch.  With `hist` (K30) the call also holds
-// [3, n_starts] doubles (lo, hi, scale) and hist [n_bins + 2, n_starts] int64, zeroed once on the call's stream before the first
-// launch and downloaded after the last; the launches then carry the histogram's record and form (campaign_hist_form).
-int run_campaign_launches(Rollout *ro, const char *who, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts, int64_t n_samples,
-                          const double *X0, uint64_t seed, int64_t first_stream, const double *threshold, const double *tol, double *stats,
-                          double *device_ms, const std::function<hipError_t(const CampaignLaunch &)> &launch,
-                          const CampaignHistCall *hist = nullptr);
+// What the five campaign run functions have in common of their arguments (hjb_rollout_run_campaign, _run_campaign_hist,
+// _run_lookahead_campaign, _run_lookahead_campaign_hist, _run_campaign_pair)
+struct CampaignCall {
+    const char *who;                // the entry point, for the error texts
+    int32_t n_steps;
+    int64_t n_starts, n_samples;
+    const double *X0;
+    uint64_t seed;
+    int64_t first_stream;
+    const double *threshold, *tol;
+    double *device_ms;              // optional: the sum of the launches' event times
+};
 
-// The paired campaign (K31, hjb_rollout_run_campaign_pair) walks the same block list in a loop of its own
-// (rollout_campaign_pair_host.hip: run_campaign_pair_launches, a sibling of run_campaign_launches, which keeps its behaviour and its
-// device-memory bound).  Per launch it starts A's flight kernel, then B's, then k_campaign_fold three times, on the object's
-// stream, and synchronises once.  Its record beside a DCampaign is hjb::DCampPair (kernels_rollout_campaign_pair.h): the pair
-// scratch cost [lanes] doubles and left [lanes] bytes, lanes = nb_max * G of a launch and never n_starts * M, the launch's
-// difference partials [8, n_blocks], and the kernel's role (out: store to the scratch; in: load from it and reduce d).  A call holds
-// [D + 1 + 24, n_starts] doubles (X0, the thresholds, three records), 24 doubles per block of a launch, the scratch, two plane lists
-// and, for HJB_PAIR_GREEDY, the one-node lookahead table; its HJB_E_NOMEM text counts all of it.
+// What a campaign call holds on the device beside X0 and the thresholds: its records with their host outputs (1; the pair's 3:
+// A, B and d), its lists of the steps' planes (1; the pair's 2), the histogram or none, the pair scratch and HJB_PAIR_GREEDY's
+// one-node lookahead table
+struct CampaignPlan {
+    int n_records = 1;
+    double *stats[3] = {};          // [8, n_starts] each, on the host
+    int n_plane_lists = 1;
+    const int32_t *planes[2] = {};  // [n_steps] each, on the host
+    const CampaignHistCall *hist = nullptr;
+    bool pair_scratch = false, greedy = false;
+};
+
+// The device side of a campaign call whose arguments have been checked (n_starts >= 1; rollout_campaign_host.hip), the one loop of
+// all five run functions: X0, the thresholds and the plan's plane lists uploaded once, the call's block list walked in launches
+// of at most option "chunk" lanes (campaign_geometry, hjbdp_campaign.h, whose byte count is the HJB_E_NOMEM bound) - `launch`
+// starts everything that runs between a launch's two events on c.st, and the loop synchronises once per launch - and the plan's
+// records downloaded.  With plan.hist (K30) the call also holds [3, n_starts] doubles (lo, hi, scale) and hist
+// [n_bins + 2, n_starts] int64, zeroed once on the call's stream before the first launch and downloaded after the last.  Under
+// ro->mu.
+int run_campaign_launches(Rollout *ro, const CampaignCall &call, const CampaignPlan &plan,
+                          const std::function<hipError_t(const CampaignLaunch &)> &launch);
+
+// The frame of the five run functions: every refusal before any device work and in one order, the outputs untouched -
+// check_campaign_streams, `no_object` (what the call refuses before it needs an object; may be empty), the null handle, the
+// object's lock, `controller` (check_run and the noise set, or check_lookahead_run, or one of these per side; under the lock),
+// n_starts == 0 (HJB_OK, *device_ms = 0), null stats, check_traj, check_campaign_bounds, check_campaign_hist - then
+// run_campaign_launches.
+int run_campaign_call(void *rollout, const CampaignCall &call, const CampaignPlan &plan, const std::function<int(Rollout *)> &no_object,
+                      const std::function<int(Rollout *)> &controller, const std::function<hipError_t(const CampaignLaunch &)> &launch);
 
 // K17 and K21 renormalise the quaternion X0[3..6] of a 7-state column after the first step: all zeros would be 0/0
 int check_quaternions(Rollout *ro, const char *pre, int64_t n_traj, const double *X0);

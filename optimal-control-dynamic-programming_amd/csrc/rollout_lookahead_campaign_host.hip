@@ -1,8 +1,9 @@
 // rollout_lookahead_campaign_host.hip - hjb_rollout_run_lookahead_campaign and hjb_rollout_lookahead_campaign_host
 // (include/hjbdp.h): the host side of the lookahead campaigns (K29, kernels_rollout_lookahead_campaign.h /
 // rollout_lookahead_campaign.hip).  The run function makes hjb_rollout_run_lookahead's refusals with fly_noise = 1
-// (check_lookahead_run) and K28's of the sizes, the streams and the bounds (check_campaign_*) before any device work, then
-// K28's device side (run_campaign_launches) with K29's launch.  The host twin flies one start's samples at a time with
+// (check_lookahead_run) and K28's of the sizes, the streams and the bounds (check_campaign_*) before any device work - the
+// campaigns' one entry frame (run_campaign_call, rollout_campaign_host.hip) - then their one device loop (run_campaign_launches)
+// with K29's launch.  The host twin flies one start's samples at a time with
 // lookahead_rollout_host (hjbdp_lookahead.h) under the nodes hjbdp_noise.h draws, and reduces them with hjbdp_campaign.h.
 // No kernel is instantiated in this unit.
 #include "rollout_host.h"
@@ -16,27 +17,18 @@ extern "C" {
 int32_t hjb_rollout_run_lookahead_campaign(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
                                            int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
                                            const double *threshold, const double *tol, double *stats, double *device_ms) {
-    Rollout *ro = (Rollout *)rollout;
-    const char *const who = "hjb_rollout_run_lookahead_campaign";
-    // every refusal before any device work, the outputs untouched; the ones that need no object first
-    if (const int bad = check_campaign_streams(ro, who, n_starts, n_samples, first_stream)) return bad;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    if (const int bad = check_lookahead_run(ro, who, 1, n_steps, value_plane_of_step, n_starts)) return bad;
-    if (n_starts == 0) {
-        if (device_ms) *device_ms = 0.0;
-        return HJB_OK;
-    }
-    const int D = ro->D;
-    if (!stats) return rfail(ro, HJB_E_INVALID, "%s: null stats", who);
-    if (const int bad = check_traj(ro, "rollout", D, "D", n_steps, n_starts, X0, stats)) return bad;
-    if (const int bad = check_campaign_bounds(ro, who, D, n_starts, threshold, tol)) return bad;
-    if (device_ms) *device_ms = 0.0;
-    return run_campaign_launches(ro, who, n_steps, value_plane_of_step, n_starts, n_samples, X0, seed, first_stream, threshold, tol, stats,
-                                 device_ms, [&](const CampaignLaunch &c) {
-                                     const DLookCampaignArgs K{c.R, ro->dvalues, ro->L, c.N, c.C, c.X0};
-                                     return launch_rollout_lookahead_campaign(ro->val_bytes, c.lds_on, D, K, c.lds, c.st, c.stats);
-                                 });
+    const CampaignCall call{"hjb_rollout_run_lookahead_campaign", n_steps, n_starts, n_samples, X0, seed, first_stream, threshold, tol, device_ms};
+    CampaignPlan plan;
+    plan.stats[0] = stats;
+    plan.planes[0] = value_plane_of_step;
+    return run_campaign_call(
+        rollout, call, plan, nullptr,
+        [&](Rollout *ro) { return check_lookahead_run(ro, call.who, 1, n_steps, value_plane_of_step, n_starts); },
+        [&](const CampaignLaunch &c) {
+            const Rollout *ro = (const Rollout *)rollout;
+            const DLookCampaignArgs K{c.R[0], ro->dvalues, ro->L, c.N, c.C[0], c.X0};
+            return launch_rollout_lookahead_campaign(ro->val_bytes, c.lds_on, ro->D, K, c.lds, c.st, c.stats[0]);
+        });
 }
 
 int32_t hjb_rollout_lookahead_campaign_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u,

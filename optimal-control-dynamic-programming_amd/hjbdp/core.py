@@ -332,24 +332,30 @@ class Rollout:
         costs beside the statistics (hjb_rollout_run_campaign_hist; the bin rule: campaign_hist_reduce); the dict gains hist
         [n_starts, n_bins + 2] int64 (underflow, the bins, overflow), hist_lo and hist_hi, and its stats are the plain call's
         bits.  hist=None is the plain call."""
-        D = self.D
-        X = _starts(X0, D)
-        ns = X.shape[0]
         ps = _int32_vector(plane_of_step, "plane_of_step")
-        thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
-        stats = np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT))
-        ms = C.c_double(0.0)
+        fn = self.lib.hjb_rollout_run_campaign if hist is None else self.lib.hjb_rollout_run_campaign_hist
+        return self._campaign(fn, (_LOOKUP[method], int(ps.size), _i32p(ps)), X0, n_samples, seed, first_stream, cost_threshold,
+                              settle_tol, hist=hist)
+
+    def _campaign(self, fn, lead, X0, n_samples, seed, first_stream, cost_threshold, settle_tol, hist=None, pair=False):
+        """The one path of the campaign calls: fn(handle, *lead, n_starts, n_samples, X0, seed, first_stream, threshold, tol,
+        [lo, hi, n_bins,] stats [x 3 for a pair], [hist,] device_ms) and the dict of its records.  lead: what the entry point
+        has in front of n_starts - its method, its planes and their count, or the pair's two sides."""
+        X = _starts(X0, self.D)
+        ns, M = X.shape[0], int(n_samples)
+        thr, tol = _campaign_bounds(ns, self.D, cost_threshold, settle_tol)
+        stats = [np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT)) for _ in range(3 if pair else 1)]
+        bins, counts, extra = (), (), {}
         if hist is not None:
-            lo, hi, nb, counts = _campaign_hist_args(ns, hist)
-            self._check(self.lib.hjb_rollout_run_campaign_hist(self._ro, _LOOKUP[method], int(ps.size), _i32p(ps), ns, int(n_samples),
-                                                               _f64p(X), int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr),
-                                                               _f64p(tol), _f64p(lo), _f64p(hi), nb, _f64p(stats), _i64p(counts),
-                                                               C.byref(ms)))
-            return {**_campaign_dict(stats, int(n_samples)), "hist": counts, "hist_lo": lo, "hist_hi": hi, "device_ms": ms.value}
-        self._check(self.lib.hjb_rollout_run_campaign(self._ro, _LOOKUP[method], int(ps.size), _i32p(ps), ns, int(n_samples), _f64p(X),
-                                                      int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol),
-                                                      _f64p(stats), C.byref(ms)))
-        return {**_campaign_dict(stats, int(n_samples)), "device_ms": ms.value}
+            lo, hi, nb, cnt = _campaign_hist_args(ns, hist)
+            bins, counts, extra = (_f64p(lo), _f64p(hi), nb), (_i64p(cnt),), {"hist": cnt, "hist_lo": lo, "hist_hi": hi}
+        ms = C.c_double(0.0)
+        self._check(fn(self._ro, *lead, ns, M, _f64p(X), int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol), *bins,
+                       *map(_f64p, stats), *counts, C.byref(ms)))
+        if pair:
+            return {"a": _campaign_dict(stats[0], M), "b": _campaign_dict(stats[1], M), **_campaign_pair_dict(stats[2], M),
+                    "device_ms": ms.value}
+        return {**_campaign_dict(stats[0], M), **extra, "device_ms": ms.value}
 
     def set_values(self, J):
         """Value planes for run_greedy (hjb_rollout_set_values): J float32 or float64, [nS, n_planes] or grid-shaped with a
@@ -435,35 +441,18 @@ class Rollout:
         and n_samples fly common random numbers and their per-start means can be differenced with the sampling noise largely
         cancelled.  cost_threshold, settle_tol and the returned dict: run_campaign's.  With a histogram of every start's costs
         beside the statistics: run_lookahead_campaign_hist."""
-        D = self.D
-        X = _starts(X0, D)
-        ns = X.shape[0]
         ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
-        thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
-        stats = np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT))
-        ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run_lookahead_campaign(self._ro, int(ps.size), _i32p(ps), ns, int(n_samples), _f64p(X),
-                                                                int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol),
-                                                                _f64p(stats), C.byref(ms)))
-        return {**_campaign_dict(stats, int(n_samples)), "device_ms": ms.value}
+        return self._campaign(self.lib.hjb_rollout_run_lookahead_campaign, (int(ps.size), _i32p(ps)), X0, n_samples, seed, first_stream,
+                              cost_threshold, settle_tol)
 
     def run_lookahead_campaign_hist(self, X0, value_plane_of_step, n_samples, hist, seed=0, first_stream=0, cost_threshold=None,
                                     settle_tol=None):
         """run_lookahead_campaign with a histogram of every start's costs beside the statistics
         (hjb_rollout_run_lookahead_campaign_hist): hist = (lo, hi, n_bins) and the returned dict as run_campaign(hist=...) has
         them, the flights, the streams (common random numbers with run_campaign) and the stats run_lookahead_campaign's."""
-        D = self.D
-        X = _starts(X0, D)
-        ns = X.shape[0]
         ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
-        thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
-        stats = np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT))
-        lo, hi, nb, counts = _campaign_hist_args(ns, hist)
-        ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run_lookahead_campaign_hist(self._ro, int(ps.size), _i32p(ps), ns, int(n_samples), _f64p(X),
-                                                                     int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol),
-                                                                     _f64p(lo), _f64p(hi), nb, _f64p(stats), _i64p(counts), C.byref(ms)))
-        return {**_campaign_dict(stats, int(n_samples)), "hist": counts, "hist_lo": lo, "hist_hi": hi, "device_ms": ms.value}
+        return self._campaign(self.lib.hjb_rollout_run_lookahead_campaign_hist, (int(ps.size), _i32p(ps)), X0, n_samples, seed,
+                              first_stream, cost_threshold, settle_tol, hist=hist)
 
     def run_campaign_pair(self, X0, a, b, n_samples, seed=0, first_stream=0, cost_threshold=None, settle_tol=None):
         """Two controllers a and b on this object's plant (the affine model under set_noise's nodes), every start of X0
@@ -474,20 +463,11 @@ class Rollout:
         run_lookahead_campaign's, under set_lookahead's nodes - or ("greedy", value_plane_of_step): the lookahead under one
         zero node of weight 1, whatever set_lookahead holds.  Returns campaign_pair_reduce's dict with a and b the plain
         campaigns' dicts (their bits) and device_ms; a negative difference means b paid less."""
-        D = self.D
-        X = _starts(X0, D)
-        ns = X.shape[0]
         (ka, ma, pa), (kb, mb, pb) = _pair_side(a, "a"), _pair_side(b, "b")
         if pa.size != pb.size:
             raise ValueError("a and b: %d and %d steps" % (pa.size, pb.size))
-        thr, tol = _campaign_bounds(ns, D, cost_threshold, settle_tol)
-        sa, sb, sd = (np.empty((ns, _abi.HJB_CAMPAIGN_NSTAT)) for _ in range(3))
-        ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run_campaign_pair(self._ro, ka, ma, _i32p(pa), kb, mb, _i32p(pb), int(pa.size), ns, int(n_samples),
-                                                           _f64p(X), int(seed) & (2 ** 64 - 1), int(first_stream), _f64p(thr), _f64p(tol),
-                                                           _f64p(sa), _f64p(sb), _f64p(sd), C.byref(ms)))
-        M = int(n_samples)
-        return {"a": _campaign_dict(sa, M), "b": _campaign_dict(sb, M), **_campaign_pair_dict(sd, M), "device_ms": ms.value}
+        return self._campaign(self.lib.hjb_rollout_run_campaign_pair, (ka, ma, _i32p(pa), kb, mb, _i32p(pb), int(pa.size)), X0, n_samples,
+                              seed, first_stream, cost_threshold, settle_tol, pair=True)
 
     def set_attitude_model(self, inertia, h, integrator="taylor", q=None, r=None):
         """The 6-D attitude loop instead of the affine one (hjb_rollout_set_attitude_model; the last model set wins):

@@ -14,6 +14,8 @@ produced test/obj_1.mat (test/test_coder.m:19-36), used for the parity fixture.
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 
 from .core import Backup
@@ -171,25 +173,13 @@ class Dynamic_Solver:
         closed-loop costs sum_k x'Qx + R u^2 over the N-1 steps are left in self.paths_cost [n].  The policy of stage k_s is
         U_mesh(u_star_idxs(:,:,k_s)) in the problem's precision, looked up in double on the double grid vectors, as
         get_optimal_path does; mode 'ssu' freezes stage ssu_num (1..N-1)."""
-        from .core import Rollout
-        if self.u_star_idxs is None:
-            raise RuntimeError("run() first")
+        opening = self._rollout("get_optimal_paths")
         N, S = self.N, self.S
         n_st = N - 1
-        if mode == "ssu":
-            if not 1 <= int(ssu_num) <= n_st:
-                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
-            planes = np.full(n_st, int(ssu_num) - 1, dtype=np.int32)
-        elif mode == "Nssu":
-            planes = np.arange(n_st, dtype=np.int32)
-        else:
-            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        planes = self._stage_planes(mode, ssu_num)
         X0s = np.asarray(X0s, dtype=np.float64)
         X0s = X0s.reshape(S, -1)
-        s_r = np.asarray(self.s_r, dtype=np.float64)
-        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
-        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
-            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+        with opening as ro:
             out = ro.run(X0s, planes, method=method, keep_path=True)
         X = np.ascontiguousarray(out["X_path"].transpose(1, 2, 0))     # [n, S, N] -> [S, N, n]
         U = np.zeros((N, X0s.shape[1]))
@@ -204,64 +194,63 @@ class Dynamic_Solver:
         Returns the closed-loop costs [n, n_samples] (sum_k x'Qx + R u^2 over the N-1 steps, of the states actually visited) and
         leaves their mean, standard deviation and maximum per start in self.noisy_cost_mean / _std / _max [n].  Beside
         policy_cost() on the same disturbance this is "promised against paid" in two calls."""
-        from .core import Rollout
-        if self.u_star_idxs is None:
-            raise RuntimeError("run() first")
-        if self.disturbance is None:
-            raise RuntimeError("get_noisy_paths needs self.disturbance = (offsets [2, W], weights or None, mode)")
-        offsets, weights = self.disturbance[0], self.disturbance[1]
-        n_st = self.N - 1
-        if mode == "ssu":
-            if not 1 <= int(ssu_num) <= n_st:
-                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
-            planes = np.full(n_st, int(ssu_num) - 1, dtype=np.int32)
-        elif mode == "Nssu":
-            planes = np.arange(n_st, dtype=np.int32)
-        else:
-            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        opening = self._rollout("get_noisy_paths", noise=True)
+        planes = self._stage_planes(mode, ssu_num)
         n_samples = int(n_samples)
         if n_samples < 1:
             raise ValueError("n_samples must be at least 1")
         X0s = np.asarray(X0s, dtype=np.float64).reshape(self.S, -1)
         n = X0s.shape[1]
-        s_r = np.asarray(self.s_r, dtype=np.float64)
-        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
-        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
-            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
-            ro.set_noise(offsets, weights)
+        with opening as ro:
             out = ro.run_noisy(np.repeat(X0s, n_samples, axis=1), planes, seed=seed, first_stream=0, method=method)
         cost = out["cost"].reshape(n, n_samples)
         self.noisy_cost_mean, self.noisy_cost_std, self.noisy_cost_max = cost.mean(axis=1), cost.std(axis=1), cost.max(axis=1)
         self.noisy_paths_ms = out["device_ms"]
         return cost
 
-    def _noisy_policy_rollout(self, who, mode, ssu_num):
-        """What a noisy flight of the stored policy needs (get_noisy_paths' own set-up, stated once for the campaign methods): the
-        planes of `mode` / `ssu_num` and an open hjbdp.Rollout holding the policy, the model and self.disturbance's nodes."""
-        from .core import Rollout
-        if self.u_star_idxs is None:
-            raise RuntimeError("run() first")
-        if self.disturbance is None:
-            raise RuntimeError("%s needs self.disturbance = (offsets [2, W], weights or None, mode)" % who)
-        n_st = self.N - 1
+    def _stage_planes(self, mode, ssu_num, values=False):
+        """The plane every one of the N-1 steps reads, as `mode` / `ssu_num` choose it.  values=False, the label planes: step k
+        (0-based) reads plane k, 'ssu' freezes plane ssu_num - 1.  values=True, the value planes behind the steps: step k reads
+        plane k + 1 of J_star, 'ssu' freezes plane ssu_num."""
+        n_st, first = self.N - 1, int(bool(values))
         if mode == "ssu":
             if not 1 <= int(ssu_num) <= n_st:
                 raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
-            planes = np.full(n_st, int(ssu_num) - 1, dtype=np.int32)
-        elif mode == "Nssu":
-            planes = np.arange(n_st, dtype=np.int32)
-        else:
-            raise ValueError("mode must be 'Nssu' or 'ssu'")
-        s_r = np.asarray(self.s_r, dtype=np.float64)
-        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
-        ro = Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device)
-        try:
-            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
-            ro.set_noise(self.disturbance[0], self.disturbance[1])
-        except Exception:
-            ro.close()
-            raise
-        return planes, ro
+            return np.full(n_st, int(ssu_num) - 1 + first, dtype=np.int32)
+        if mode == "Nssu":
+            return np.arange(first, n_st + first, dtype=np.int32)
+        raise ValueError("mode must be 'Nssu' or 'ssu'")
+
+    def _rollout(self, who, values=False, lookahead=False, noise=False):
+        """What `who` flies on: refuses at once what it cannot fly - no run() yet, no self.disturbance where the flight needs one,
+        an unknown `lookahead` - and returns a context manager that opens an hjbdp.Rollout on the stored policy and closes it on
+        the way out, whatever happens.  On the open object, in this order: set_model; set_values(J_star) with `values`;
+        set_lookahead unless `lookahead` is False - 'disturbed': self.disturbance's set in its own mode, 'nominal': one zero node of weight
+        1; set_noise(self.disturbance's nodes) with `noise`."""
+        from .core import Rollout
+        if self.u_star_idxs is None or (values and self.J_star is None):
+            raise RuntimeError("run() first")
+        if (lookahead is not False or noise) and self.disturbance is None:
+            raise RuntimeError("%s needs self.disturbance = (offsets [2, W], weights or None, mode)" % who)
+        if lookahead is not False and lookahead not in ("disturbed", "nominal"):
+            raise ValueError("lookahead must be 'disturbed' or 'nominal'")
+
+        @contextlib.contextmanager
+        def opened():
+            s_r = np.asarray(self.s_r, dtype=np.float64)
+            u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
+            with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
+                ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+                if values:
+                    ro.set_values(self.J_star)
+                if lookahead == "disturbed":
+                    ro.set_lookahead(self.disturbance[0], self.disturbance[1], self.disturbance[2] if len(self.disturbance) > 2 else "expect")
+                elif lookahead == "nominal":
+                    ro.set_lookahead(np.zeros((self.S, 1)), [1.0], "expect")
+                if noise:
+                    ro.set_noise(self.disturbance[0], self.disturbance[1])
+                yield ro
+        return opened()
 
     def get_noisy_cost_statistics(self, X0s, n_samples, seed=0, mode="Nssu", ssu_num=1, method="linear", cost_threshold=None,
                                   settle_tol=None):
@@ -273,8 +262,9 @@ class Dynamic_Solver:
         device_ms.  `mode` / `ssu_num` / `method` as in get_noisy_paths."""
         if int(n_samples) < 1:
             raise ValueError("n_samples must be at least 1")
-        planes, ro = self._noisy_policy_rollout("get_noisy_cost_statistics", mode, ssu_num)
-        with ro:
+        opening = self._rollout("get_noisy_cost_statistics", noise=True)
+        planes = self._stage_planes(mode, ssu_num)
+        with opening as ro:
             return ro.run_campaign(np.asarray(X0s, dtype=np.float64).reshape(self.S, -1), planes, int(n_samples), seed=seed,
                                    first_stream=0, method=method, cost_threshold=cost_threshold, settle_tol=settle_tol)
 
@@ -283,12 +273,8 @@ class Dynamic_Solver:
         (i, j) = (s_r[i], s_r[j]) flown from stream (i + dx * j) * n_samples on.  Beside policy_cost() on the same disturbance
         this is "promised against paid" over the whole grid: policy_cost()'s plane 0 is what the policy promises at a node,
         the map's mean (and, for a 'worst' set, its max) is what n_samples flights from that node paid."""
-        s_r = np.asarray(self.s_r, dtype=np.float64)
-        dx = s_r.size
-        X0s = np.stack([np.tile(s_r, dx), np.repeat(s_r, dx)])                  # axis 0 fastest, as the labels are stored
-        out = self.get_noisy_cost_statistics(X0s, n_samples, seed=seed, mode=mode, ssu_num=ssu_num, method=method,
-                                             cost_threshold=cost_threshold, settle_tol=settle_tol)
-        return {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) else v) for key, v in out.items()}
+        return self._grid_map(self.get_noisy_cost_statistics(self._grid_starts(), n_samples, seed=seed, mode=mode, ssu_num=ssu_num,
+                                                             method=method, cost_threshold=cost_threshold, settle_tol=settle_tol))
 
     def get_greedy_paths(self, X0s, mode="Nssu", ssu_num=1):
         """The closed loop of the cost-to-go itself, on the GPU (hjbdp.Rollout.run_greedy): at every step the control of U_mesh
@@ -300,25 +286,12 @@ class Dynamic_Solver:
         the kernel's time in self.greedy_paths_ms.  The lookahead is NOMINAL even when self.disturbance is set: J_star then
         is the disturbed handle's cost-to-go, but the candidate's next state carries no node - get_lookahead_paths is the loop
         that looks ahead under self.disturbance."""
-        from .core import Rollout
-        if self.J_star is None or self.u_star_idxs is None:
-            raise RuntimeError("run() first")
+        opening = self._rollout("get_greedy_paths", values=True)
         N, S = self.N, self.S
         n_st = N - 1
-        if mode == "ssu":
-            if not 1 <= int(ssu_num) <= n_st:
-                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
-            planes = np.full(n_st, int(ssu_num), dtype=np.int32)
-        elif mode == "Nssu":
-            planes = np.arange(1, N, dtype=np.int32)
-        else:
-            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        planes = self._stage_planes(mode, ssu_num, values=True)
         X0s = np.asarray(X0s, dtype=np.float64).reshape(S, -1)
-        s_r = np.asarray(self.s_r, dtype=np.float64)
-        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
-        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
-            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
-            ro.set_values(self.J_star)
+        with opening as ro:
             out = ro.run_greedy(X0s, planes, keep_path=True)
         X = np.ascontiguousarray(out["X_path"].transpose(1, 2, 0))     # [n, S, N] -> [S, N, n]
         U = np.zeros((N, X0s.shape[1]))
@@ -337,37 +310,18 @@ class Dynamic_Solver:
         on stream i * n_samples + j of `seed` (get_noisy_paths' numbering; a 'worst' set is sampled uniformly); returns the
         closed-loop costs [n, n_samples] and leaves their mean, standard deviation and maximum per start in
         self.lookahead_cost_mean / _std / _max [n].  The kernel's time: self.lookahead_paths_ms."""
-        from .core import Rollout
-        if self.J_star is None or self.u_star_idxs is None:
-            raise RuntimeError("run() first")
-        if self.disturbance is None:
-            raise RuntimeError("get_lookahead_paths needs self.disturbance = (offsets [2, W], weights or None, mode)")
-        offsets, weights = self.disturbance[0], self.disturbance[1]
-        dmode = self.disturbance[2] if len(self.disturbance) > 2 else "expect"
+        opening = self._rollout("get_lookahead_paths", values=True, lookahead="disturbed", noise=n_samples is not None)
         N, S = self.N, self.S
         n_st = N - 1
-        if mode == "ssu":
-            if not 1 <= int(ssu_num) <= n_st:
-                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
-            planes = np.full(n_st, int(ssu_num), dtype=np.int32)
-        elif mode == "Nssu":
-            planes = np.arange(1, N, dtype=np.int32)
-        else:
-            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        planes = self._stage_planes(mode, ssu_num, values=True)
         if n_samples is not None and int(n_samples) < 1:
             raise ValueError("n_samples must be at least 1")
         X0s = np.asarray(X0s, dtype=np.float64).reshape(S, -1)
         n = X0s.shape[1]
-        s_r = np.asarray(self.s_r, dtype=np.float64)
-        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
-        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
-            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
-            ro.set_values(self.J_star)
-            ro.set_lookahead(offsets, weights, dmode)
+        with opening as ro:
             if n_samples is None:
                 out = ro.run_lookahead(X0s, planes, keep_path=True)
             else:
-                ro.set_noise(offsets, weights)
                 out = ro.run_lookahead(np.repeat(X0s, int(n_samples), axis=1), planes, noisy=True, seed=seed, first_stream=0)
         self.lookahead_paths_ms = out["device_ms"]
         if n_samples is not None:
@@ -392,38 +346,12 @@ class Dynamic_Solver:
         lookahead (common random numbers), so the per-start means can be differenced with the sampling noise largely cancelled.
         Returns run_campaign's dict, one entry per start (get_noisy_cost_statistics').  Planes and `mode` / `ssu_num` as in
         get_lookahead_paths."""
-        from .core import Rollout
-        if self.J_star is None or self.u_star_idxs is None:
-            raise RuntimeError("run() first")
-        if self.disturbance is None:
-            raise RuntimeError("get_lookahead_cost_statistics needs self.disturbance = (offsets [2, W], weights or None, mode)")
-        offsets, weights = self.disturbance[0], self.disturbance[1]
-        dmode = self.disturbance[2] if len(self.disturbance) > 2 else "expect"
-        if lookahead not in ("disturbed", "nominal"):
-            raise ValueError("lookahead must be 'disturbed' or 'nominal'")
-        N, S = self.N, self.S
-        n_st = N - 1
-        if mode == "ssu":
-            if not 1 <= int(ssu_num) <= n_st:
-                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
-            planes = np.full(n_st, int(ssu_num), dtype=np.int32)
-        elif mode == "Nssu":
-            planes = np.arange(1, N, dtype=np.int32)
-        else:
-            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        opening = self._rollout("get_lookahead_cost_statistics", values=True, lookahead=lookahead, noise=True)
+        planes = self._stage_planes(mode, ssu_num, values=True)
         if int(n_samples) < 1:
             raise ValueError("n_samples must be at least 1")
-        s_r = np.asarray(self.s_r, dtype=np.float64)
-        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
-        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
-            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
-            ro.set_values(self.J_star)
-            if lookahead == "disturbed":
-                ro.set_lookahead(offsets, weights, dmode)
-            else:
-                ro.set_lookahead(np.zeros((S, 1)), [1.0], "expect")
-            ro.set_noise(offsets, weights)
-            return ro.run_lookahead_campaign(np.asarray(X0s, dtype=np.float64).reshape(S, -1), planes, int(n_samples), seed=seed,
+        with opening as ro:
+            return ro.run_lookahead_campaign(np.asarray(X0s, dtype=np.float64).reshape(self.S, -1), planes, int(n_samples), seed=seed,
                                              first_stream=0, cost_threshold=cost_threshold, settle_tol=settle_tol)
 
     def lookahead_cost_map(self, n_samples, seed=0, mode="Nssu", ssu_num=1, lookahead="disturbed", cost_threshold=None, settle_tol=None):
@@ -433,12 +361,9 @@ class Dynamic_Solver:
         numbers, so this map's mean minus noisy_cost_map's is what the stored labels lose to the value function they came from,
         node by node, with the sampling noise largely cancelled.  Beside J_star's first plane it is "promised against paid"
         for the controller the disturbed solve is exactly optimal for."""
-        s_r = np.asarray(self.s_r, dtype=np.float64)
-        dx = s_r.size
-        X0s = np.stack([np.tile(s_r, dx), np.repeat(s_r, dx)])                  # axis 0 fastest, as the labels are stored
-        out = self.get_lookahead_cost_statistics(X0s, n_samples, seed=seed, mode=mode, ssu_num=ssu_num, lookahead=lookahead,
-                                                 cost_threshold=cost_threshold, settle_tol=settle_tol)
-        return {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) else v) for key, v in out.items()}
+        return self._grid_map(self.get_lookahead_cost_statistics(self._grid_starts(), n_samples, seed=seed, mode=mode, ssu_num=ssu_num,
+                                                                 lookahead=lookahead, cost_threshold=cost_threshold,
+                                                                 settle_tol=settle_tol))
 
     @staticmethod
     def _two_pass_quantiles(campaign, n_samples, q, n_bins):
@@ -472,65 +397,46 @@ class Dynamic_Solver:
         hist_hi, q and quantiles [n, len(q)]: hjbdp.campaign_quantiles' upper bounds, each at most one bin width (max - min) /
         n_bins above the order statistic of rank ceil(q * n_samples); q = 1 gives max exactly.  hjbdp.campaign_tail_mean of the
         same hist estimates the tail mean above a quantile."""
-        planes, ro = self._noisy_policy_rollout("get_noisy_cost_quantiles", mode, ssu_num)
+        opening = self._rollout("get_noisy_cost_quantiles", noise=True)
+        planes = self._stage_planes(mode, ssu_num)
         X = np.asarray(X0s, dtype=np.float64).reshape(self.S, -1)
-        with ro:
+        with opening as ro:
             return self._two_pass_quantiles(lambda hist: ro.run_campaign(X, planes, int(n_samples), seed=seed, first_stream=0, method=method,
                                                                          cost_threshold=cost_threshold, settle_tol=settle_tol, hist=hist),
                                             n_samples, q, n_bins)
 
     def _grid_starts(self):
+        """Every grid node as a start, [S, dx * dx]: node (i, j) is start i + dx * j"""
         s_r = np.asarray(self.s_r, dtype=np.float64)
         dx = s_r.size
-        return dx, np.stack([np.tile(s_r, dx), np.repeat(s_r, dx)])             # axis 0 fastest, as the labels are stored
+        return np.stack([np.tile(s_r, dx), np.repeat(s_r, dx)])                 # axis 0 fastest, as the labels are stored
+
+    def _grid_map(self, out):
+        """A campaign's dict over _grid_starts' starts with every per-start array shaped like the grid, [dx, dx, ...]; q (the
+        quantile levels) and the scalars stay, the pair's a and b dicts are shaped the same way."""
+        dx = np.asarray(self.s_r).size
+        return {key: (self._grid_map(v) if isinstance(v, dict) else
+                      v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) and key != "q" else v)
+                for key, v in out.items()}
 
     def noisy_cost_quantile_map(self, n_samples, q=(0.5, 0.95, 0.99), n_bins=64, seed=0, mode="Nssu", ssu_num=1, method="linear",
                                 cost_threshold=None, settle_tol=None):
         """get_noisy_cost_quantiles at every grid node, beside policy_cost(): each per-start entry shaped like the grid, [dx, dx]
         (quantiles [dx, dx, len(q)], hist [dx, dx, n_bins + 2]), node (i, j) = (s_r[i], s_r[j]) on noisy_cost_map's streams.
         Every node's bins lie between that node's own min and max: the cost spans orders of magnitude over the grid."""
-        dx, X0s = self._grid_starts()
-        out = self.get_noisy_cost_quantiles(X0s, n_samples, q=q, n_bins=n_bins, seed=seed, mode=mode, ssu_num=ssu_num, method=method,
-                                            cost_threshold=cost_threshold, settle_tol=settle_tol)
-        return {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) and key != "q" else v)
-                for key, v in out.items()}
+        return self._grid_map(self.get_noisy_cost_quantiles(self._grid_starts(), n_samples, q=q, n_bins=n_bins, seed=seed, mode=mode,
+                                                            ssu_num=ssu_num, method=method, cost_threshold=cost_threshold,
+                                                            settle_tol=settle_tol))
 
     def get_lookahead_cost_quantiles(self, X0s, n_samples, q=(0.5, 0.95, 0.99), n_bins=64, seed=0, mode="Nssu", ssu_num=1,
                                      lookahead="disturbed", cost_threshold=None, settle_tol=None):
         """get_noisy_cost_quantiles for get_lookahead_cost_statistics' controller (hjbdp.Rollout.run_lookahead_campaign_hist): the
         same two passes on the same streams, so the quantiles of the stored labels and of either lookahead come from common
         random numbers.  `lookahead`, planes and `mode` / `ssu_num` as in get_lookahead_cost_statistics."""
-        from .core import Rollout
-        if self.J_star is None or self.u_star_idxs is None:
-            raise RuntimeError("run() first")
-        if self.disturbance is None:
-            raise RuntimeError("get_lookahead_cost_quantiles needs self.disturbance = (offsets [2, W], weights or None, mode)")
-        offsets, weights = self.disturbance[0], self.disturbance[1]
-        dmode = self.disturbance[2] if len(self.disturbance) > 2 else "expect"
-        if lookahead not in ("disturbed", "nominal"):
-            raise ValueError("lookahead must be 'disturbed' or 'nominal'")
-        N, S = self.N, self.S
-        n_st = N - 1
-        if mode == "ssu":
-            if not 1 <= int(ssu_num) <= n_st:
-                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
-            planes = np.full(n_st, int(ssu_num), dtype=np.int32)
-        elif mode == "Nssu":
-            planes = np.arange(1, N, dtype=np.int32)
-        else:
-            raise ValueError("mode must be 'Nssu' or 'ssu'")
-        s_r = np.asarray(self.s_r, dtype=np.float64)
-        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
-        X = np.asarray(X0s, dtype=np.float64).reshape(S, -1)
-        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
-            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
-            ro.set_values(self.J_star)
-            if lookahead == "disturbed":
-                ro.set_lookahead(offsets, weights, dmode)
-            else:
-                ro.set_lookahead(np.zeros((S, 1)), [1.0], "expect")
-            ro.set_noise(offsets, weights)
-
+        opening = self._rollout("get_lookahead_cost_quantiles", values=True, lookahead=lookahead, noise=True)
+        planes = self._stage_planes(mode, ssu_num, values=True)
+        X = np.asarray(X0s, dtype=np.float64).reshape(self.S, -1)
+        with opening as ro:
             def campaign(hist):
                 if hist is None:
                     return ro.run_lookahead_campaign(X, planes, int(n_samples), seed=seed, first_stream=0, cost_threshold=cost_threshold,
@@ -542,11 +448,9 @@ class Dynamic_Solver:
     def lookahead_cost_quantile_map(self, n_samples, q=(0.5, 0.95, 0.99), n_bins=64, seed=0, mode="Nssu", ssu_num=1, lookahead="disturbed",
                                     cost_threshold=None, settle_tol=None):
         """get_lookahead_cost_quantiles at every grid node: noisy_cost_quantile_map's starts on its streams."""
-        dx, X0s = self._grid_starts()
-        out = self.get_lookahead_cost_quantiles(X0s, n_samples, q=q, n_bins=n_bins, seed=seed, mode=mode, ssu_num=ssu_num,
-                                                lookahead=lookahead, cost_threshold=cost_threshold, settle_tol=settle_tol)
-        return {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) and key != "q" else v)
-                for key, v in out.items()}
+        return self._grid_map(self.get_lookahead_cost_quantiles(self._grid_starts(), n_samples, q=q, n_bins=n_bins, seed=seed, mode=mode,
+                                                                ssu_num=ssu_num, lookahead=lookahead, cost_threshold=cost_threshold,
+                                                                settle_tol=settle_tol))
 
     _PAIR_CONTROLLERS = ("labels", "nominal", "disturbed")
 
@@ -561,37 +465,16 @@ class Dynamic_Solver:
         Returns run_campaign_pair's dict, one entry per start: a, b, stats_d [n, 8], mean_diff (b less a: negative where b paid
         less), var_diff, std_diff, se_diff, t, min_diff, max_diff, n_b_lower, n_a_lower, n_tie, n_both_in, mean_diff_both_in,
         device_ms - whether the stored labels lose to the value function they came from, with its standard error."""
-        from .core import Rollout
-        if self.J_star is None or self.u_star_idxs is None:
-            raise RuntimeError("run() first")
-        if self.disturbance is None:
-            raise RuntimeError("get_paired_cost_statistics needs self.disturbance = (offsets [2, W], weights or None, mode)")
+        opening = self._rollout("get_paired_cost_statistics", values=True, lookahead="disturbed", noise=True)
         for name, ctl in (("a", a), ("b", b)):
             if ctl not in self._PAIR_CONTROLLERS:
                 raise ValueError("%s must be one of %s" % (name, ", ".join(repr(c) for c in self._PAIR_CONTROLLERS)))
-        offsets, weights = self.disturbance[0], self.disturbance[1]
-        dmode = self.disturbance[2] if len(self.disturbance) > 2 else "expect"
-        N, S = self.N, self.S
-        n_st = N - 1
-        if mode == "ssu":
-            if not 1 <= int(ssu_num) <= n_st:
-                raise ValueError("ssu_num must lie in 1..N-1 = %d" % n_st)
-            label_planes, value_planes = np.full(n_st, int(ssu_num) - 1, dtype=np.int32), np.full(n_st, int(ssu_num), dtype=np.int32)
-        elif mode == "Nssu":
-            label_planes, value_planes = np.arange(n_st, dtype=np.int32), np.arange(1, N, dtype=np.int32)
-        else:
-            raise ValueError("mode must be 'Nssu' or 'ssu'")
+        label_planes, value_planes = self._stage_planes(mode, ssu_num), self._stage_planes(mode, ssu_num, values=True)
         if int(n_samples) < 1:
             raise ValueError("n_samples must be at least 1")
         side = {"labels": ("labels", label_planes, method), "nominal": ("greedy", value_planes), "disturbed": ("lookahead", value_planes)}
-        s_r = np.asarray(self.s_r, dtype=np.float64)
-        u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
-        with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
-            ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
-            ro.set_values(self.J_star)
-            ro.set_lookahead(offsets, weights, dmode)
-            ro.set_noise(offsets, weights)
-            return ro.run_campaign_pair(np.asarray(X0s, dtype=np.float64).reshape(S, -1), side[a], side[b], int(n_samples), seed=seed,
+        with opening as ro:
+            return ro.run_campaign_pair(np.asarray(X0s, dtype=np.float64).reshape(self.S, -1), side[a], side[b], int(n_samples), seed=seed,
                                         first_stream=0, cost_threshold=cost_threshold, settle_tol=settle_tol)
 
     def paired_cost_map(self, n_samples, a="labels", b="disturbed", seed=0, mode="Nssu", ssu_num=1, method="linear", cost_threshold=None,
@@ -600,11 +483,9 @@ class Dynamic_Solver:
         and b dicts of such entries), node (i, j) = (s_r[i], s_r[j]) flown from stream (i + dx * j) * n_samples on - noisy_cost_map's
         and lookahead_cost_map's starts on their streams, so a and b equal those maps bit for bit and mean_diff is their means'
         difference WITH its standard error se_diff and the sign counts, node by node."""
-        dx, X0s = self._grid_starts()
-        out = self.get_paired_cost_statistics(X0s, n_samples, a=a, b=b, seed=seed, mode=mode, ssu_num=ssu_num, method=method,
-                                              cost_threshold=cost_threshold, settle_tol=settle_tol)
-        shape = lambda d: {key: (v.reshape((dx, dx) + v.shape[1:], order="F") if isinstance(v, np.ndarray) else v) for key, v in d.items()}
-        return {key: (shape(v) if isinstance(v, dict) else v) for key, v in shape(out).items()}
+        return self._grid_map(self.get_paired_cost_statistics(self._grid_starts(), n_samples, a=a, b=b, seed=seed, mode=mode,
+                                                              ssu_num=ssu_num, method=method, cost_threshold=cost_threshold,
+                                                              settle_tol=settle_tol))
 
     @staticmethod
     def compare_data(obj1, obj2):

@@ -1,5 +1,5 @@
-// campaign_harness.cpp - csrc/hjbdp_campaign.h as plain C++ (no HIP): its own checks of the group size, the identities, the tree's
-// pairing and the fold, then the statistics of a fixed family of inputs printed as hex words for
+// campaign_harness.cpp - csrc/hjbdp_campaign.h as plain C++ (no HIP): its own checks of the group size, the launch geometry and
+// device bytes of a call (campaign_geometry, against figures worked by hand), the identities, the tree's pairing and the fold, then the statistics of a fixed family of inputs printed as hex words for
 // tests/test_campaign_refs.py to compare with the numpy restatement (tests/campaign_refs.py), which builds the same inputs.
 // Exit status 0 and a line "<name>: ok" per check; a failed check prints what it saw and exits 1.
 #include "hjbdp_campaign.h"
@@ -44,6 +44,34 @@ int main() {
         if (G != Gs[i] || (1 << lg) != G) return fail("group", Ms[i], G);
     }
     std::printf("group: ok\n");
+
+    // the launch geometry and the device bytes of a call: D = 2, 3 starts of 100 samples, 5 steps, launches of at most 128 lanes, a
+    // threshold.  G = 64 (100 > 64), log2 G = 6, B = ceil(100 / 64) = 2, n_blocks = 3 * 2 = 6, nb_max = min(6, max(128 / 64, 1)) = 2,
+    // lanes_max = 2 * 64 = 128.  The bytes, by hand:
+    //   X0 8 * 2 * 3 = 48, one record 64 * 3 = 192, the thresholds 8 * 3 = 24, one partial array 64 * 2 = 128, one plane list 4 * 5 = 20
+    //   plain  48 + 192 + 24 + 128 + 20                                                             = 412
+    //   hist   412 + [lo | hi | scale] 24 * 3 = 72 + counts 8 * (10 + 2) * 3 = 288                   = 772
+    //   pair   48 + 3 * 192 + 24 + 3 * 128 + 2 * 20 + scratch 9 * 128 = 1152 + the greedy table 16   = 2240
+    {
+        const CampaignGeometry p = campaign_geometry(3, 100, 2, 5, 128, 1, 1, true, 0, false, false);
+        if (p.G != 64 || p.log2G != 6 || p.B != 2 || p.n_blocks != 6 || p.nb_max != 2 || p.lanes_max != 128) return fail("plan", p.G, p.nb_max);
+        if (p.need != 412) return fail("plan", 412, (long long)p.need);
+        const CampaignGeometry h = campaign_geometry(3, 100, 2, 5, 128, 1, 1, true, 10, false, false);
+        if (h.need != 772 || h.nb_max != 2) return fail("plan", 772, (long long)h.need);
+        const CampaignGeometry q = campaign_geometry(3, 100, 2, 5, 128, 3, 2, true, 0, true, true);
+        if (q.need != 2240 || q.nb_max != 2 || q.lanes_max != 128) return fail("plan", 2240, (long long)q.need);
+        // without the threshold 24 bytes less; no steps still holds one plane entry per list: 412 - 24 - 20 + 4
+        if (campaign_geometry(3, 100, 2, 0, 128, 1, 1, false, 0, false, false).need != 372) return fail("plan", 372, 0);
+        // a chunk below one block still launches one block; a chunk above the call launches the call's blocks
+        const CampaignGeometry c1 = campaign_geometry(3, 100, 2, 5, 1, 1, 1, true, 0, false, false);
+        if (c1.nb_max != 1 || c1.lanes_max != 64 || c1.need != 412 - 64) return fail("plan", c1.nb_max, (long long)c1.need);
+        if (campaign_geometry(3, 100, 2, 5, 1 << 20, 1, 1, true, 0, false, false).nb_max != 6) return fail("plan", 6, 0);
+        const CampaignGeometry m1 = campaign_geometry(3, 1, 2, 5, 128, 1, 1, true, 0, false, false);
+        if (m1.G != 1 || m1.log2G != 0 || m1.B != 1 || m1.n_blocks != 3 || m1.nb_max != 3 || m1.lanes_max != 3) return fail("plan", m1.G, m1.B);
+        const CampaignGeometry m65 = campaign_geometry(3, 65, 2, 5, 128, 1, 1, true, 0, false, false);
+        if (m65.G != 64 || m65.B != 2) return fail("plan", m65.G, m65.B);
+    }
+    std::printf("plan: ok\n");
 
     // the identities: op(x, padding) is x bit for bit, whatever x holds, -0.0 and the infinities included
     const double inf = std::numeric_limits<double>::infinity();

@@ -112,7 +112,7 @@ def test_plain_cpp_harness_agrees_with_the_restatement(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = r.stdout.splitlines()
-    assert [ln for ln in lines if not ln.startswith("stats ")] == ["group: ok", "identity: ok", "flags: ok", "tree: ok"], lines
+    assert [ln for ln in lines if not ln.startswith("stats ")] == ["group: ok", "plan: ok", "identity: ok", "flags: ok", "tree: ok"], lines
     rows = [ln.split() for ln in lines if ln.startswith("stats ")]
     assert [(int(r[1]), int(r[2])) for r in rows] == [(M, s) for M in SIZES for s in range(3)]
     for row in rows:

@@ -121,8 +121,9 @@ def test_python_faces_exist():
         d.paired_cost_map(4)                                                    # run() first
 
 
-def test_matlab_shim_call_sequence():
+def test_matlab_shim_call_sequence(monkeypatch):
     """the shim drives the entry points Dynamic_Solver.paired_cost_map drives, in its order, each with the flat header's arity"""
+    import solver_recorder as rec
     from test_abi import _matlab_calllibs, _prototypes
     flat = _prototypes((ROOT / "include" / "hjbdp_matlab.h").read_text())
     text = SHIM.read_text()
@@ -137,7 +138,10 @@ def test_matlab_shim_call_sequence():
     assert text.count("zeros(8, ns)") == 3 and "tested twin: hjbdp/dynamic_solver.py paired_cost_map" in text
     assert "matlab/Dynamic_Solver_hjbdp_paired_cost_map.m" in (ROOT / "include" / "hjbdp_matlab.h").read_text()
     assert "Dynamic_Solver_hjbdp_paired_cost_map.m" in (ROOT / "INTEGRATION.md").read_text()
-    twin = (PKG / "hjbdp" / "dynamic_solver.py").read_text()
-    twin = twin[twin.index("def get_paired_cost_statistics("):twin.index("def paired_cost_map(")]
-    order = [twin.index(call) for call in ("set_model(", "set_values(", "set_lookahead(", "set_noise(", "run_campaign_pair(")]
-    assert order == sorted(order)
+    # the twin, by the calls it makes on the object it opens: the shim's, in the shim's order, and never a per-trajectory run
+    out, calls = rec.record(monkeypatch, "paired_cost_map", 4, a="labels", b="nominal")
+    assert rec.as_entry_points(calls) == rec.shim_order(body), calls
+    assert not {"run_noisy", "run_lookahead"} & {name for name, _, _ in calls}
+    assert out["stats_d"].shape == (3, 3, 8) and out["a"]["stats"].shape == (3, 3, 8) and out["b"]["mean"].shape == (3, 3)
+    (X0, a, b, n_samples), = [args for name, args, _ in calls if name == "run_campaign_pair"]
+    assert a[0] == "labels" and a[1].tolist() == [0, 1] and b[0] == "greedy" and b[1].tolist() == [1, 2] and n_samples == 4
