@@ -18,7 +18,8 @@
 // hjb_rollout_run_lookahead_campaign (K29, kernels_rollout_lookahead_campaign.h) does the same for the lookahead controller; it and
 // its host twin are rollout_lookahead_campaign_host.hip, on check_lookahead_run and look_host_args / look_host_model below.
 // Defined here for the host units (rollout_host.h): rfail, check_run / check_traj / check_quaternions (the run functions'
-// refusals, all before any device work), upload, run_chunks (the chunk loop).  No kernel is instantiated in this unit.
+// refusals, all before any device work), upload, run_chunks (the chunk loop) and run_call (the run functions' entry frame: every
+// run function here and in rollout_channels.hip is its plan, its hooks and its launch).  No kernel is instantiated in this unit.
 #include "rollout_host.h"
 #include "rollout_dispatch.h"
 #include "kernels_rollout_attitude_linear.h"
@@ -186,51 +187,75 @@ int check_lookahead_run(Rollout *ro, const char *who, int fly_noise, int32_t n_s
     return HJB_OK;
 }
 
-int look_host_args(const char *who, int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
-                   const double *A, const double *B, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
-                   int64_t n_traj, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights) {
-    if (D < 1 || D > HJB_MAX_D) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, HJB_MAX_D);
-    if (n_u < 1 || n_u > HJB_ROLLOUT_MAX_U) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: n_u=%d not in 1..%d", who, n_u, HJB_ROLLOUT_MAX_U);
-    if (!n || !knots || !u_table || !A || !B) return rfail(nullptr, HJB_E_INVALID, "%s: null argument (n, knots, u_table, A and B are required)", who);
-    if (n_labels < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_labels=%d < 1", who, n_labels);
-    if (dtype != HJB_F32 && dtype != HJB_F64) return rfail(nullptr, HJB_E_INVALID, "%s: dtype %d is not HJB_F32 / HJB_F64", who, dtype);
-    if (n_value_planes < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_value_planes=%d < 0", who, n_value_planes);
-    if (n_value_planes > 0 && !values) return rfail(nullptr, HJB_E_INVALID, "%s: null values with n_value_planes=%d", who, n_value_planes);
-    if (n_steps < 0 || n_traj < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_steps=%d, n_traj=%lld (both >= 0)", who, n_steps, (long long)n_traj);
-    if (const int bad = check_lookahead(nullptr, who, D, mode, n_nodes, offsets, weights)) return bad;
+int affine_host_args(const char *who, const AffineHostArgs &a, int64_t n_traj) {
+    if (a.D < 1 || a.D > HJB_MAX_D) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, a.D, HJB_MAX_D);
+    if (a.n_u < 1 || a.n_u > HJB_ROLLOUT_MAX_U) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: n_u=%d not in 1..%d", who, a.n_u, HJB_ROLLOUT_MAX_U);
+    if (!a.n || !a.knots || !a.u_table || !a.A || !a.B)
+        return rfail(nullptr, HJB_E_INVALID, "%s: null argument (n, knots, u_table, A and B are required)", who);
+    if (a.n_labels < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_labels=%d < 1", who, a.n_labels);
+    if (a.dtype != HJB_F32 && a.dtype != HJB_F64) return rfail(nullptr, HJB_E_INVALID, "%s: dtype %d is not HJB_F32 / HJB_F64", who, a.dtype);
+    if (a.n_value_planes < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_value_planes=%d < 0", who, a.n_value_planes);
+    if (a.n_value_planes > 0 && !a.values) return rfail(nullptr, HJB_E_INVALID, "%s: null values with n_value_planes=%d", who, a.n_value_planes);
+    if (a.n_steps < 0 || n_traj < 0)
+        return rfail(nullptr, HJB_E_INVALID, "%s: n_steps=%d, n_traj=%lld (both >= 0)", who, a.n_steps, (long long)n_traj);
+    return HJB_OK;
+}
+
+int affine_host_model(const char *who, const AffineHostArgs &a, AffineHostProblem &P) {
+    const int D = a.D, n_u = a.n_u;
+    int64_t nS = 1, n_knots = 0;
+    if (const int bad_grid = check_grid(who, D, a.n, a.knots, &nS, &n_knots)) return bad_grid;
+    if (!all_finite(a.u_table, (int64_t)a.n_labels * n_u)) return rfail(nullptr, HJB_E_INVALID, "%s: u_table is not finite", who);
+    if (!all_finite(a.A, (int64_t)D * D) || !all_finite(a.B, (int64_t)D * n_u) || !all_finite(a.c, D) || !all_finite(a.q, D) || !all_finite(a.r, n_u))
+        return rfail(nullptr, HJB_E_INVALID, "%s: the model (A, B, c, q, r) is not finite", who);
+    if (a.n_steps > 0 && !a.value_plane_of_step) return rfail(nullptr, HJB_E_INVALID, "%s: null value_plane_of_step", who);
+    for (int k = 0; k < a.n_steps; ++k)
+        if (a.value_plane_of_step[k] < -1 || a.value_plane_of_step[k] >= a.n_value_planes)
+            return rfail(nullptr, HJB_E_INVALID, "%s: value_plane_of_step[%d] = %d outside [-1, %d)", who, k, a.value_plane_of_step[k],
+                         a.n_value_planes);
+    GreedyModel &M = P.M;
+    P.rdx.assign((size_t)n_knots, 0.0);
+    greedy_grid(D, a.n, a.knots, M, P.rdx.data());
+    M.n_u = n_u;
+    M.n_labels = a.n_labels;
+    M.has_c = a.c ? 1 : 0;
+    std::memcpy(M.A, a.A, sizeof(double) * D * D);
+    std::memcpy(M.B, a.B, sizeof(double) * D * n_u);
+    if (a.c) std::memcpy(M.c, a.c, sizeof(double) * D);
+    if (a.q) std::memcpy(M.q, a.q, sizeof(double) * D);
+    if (a.r) std::memcpy(M.r, a.r, sizeof(double) * n_u);
+    return HJB_OK;
+}
+
+int look_host_args(const char *who, const AffineHostArgs &a, int64_t n_traj, int32_t mode, int32_t n_nodes, const double *offsets,
+                   const double *weights) {
+    if (const int bad = affine_host_args(who, a, n_traj)) return bad;
+    if (const int bad = check_lookahead(nullptr, who, a.D, mode, n_nodes, offsets, weights)) return bad;
     if (n_nodes < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_nodes=%d < 1 (the lookahead needs a node set)", who, n_nodes);
     return HJB_OK;
 }
 
-int look_host_model(const char *who, int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
-                    const double *A, const double *B, const double *c, const double *q, const double *r, int32_t n_value_planes,
-                    int32_t n_steps, const int32_t *value_plane_of_step, int32_t mode, int32_t n_nodes, const double *offsets,
-                    const double *weights, LookHostProblem &P) {
-    int64_t nS = 1, n_knots = 0;
-    if (const int bad_grid = check_grid(who, D, n, knots, &nS, &n_knots)) return bad_grid;
-    if (!all_finite(u_table, (int64_t)n_labels * n_u)) return rfail(nullptr, HJB_E_INVALID, "%s: u_table is not finite", who);
-    if (!all_finite(A, (int64_t)D * D) || !all_finite(B, (int64_t)D * n_u) || !all_finite(c, D) || !all_finite(q, D) || !all_finite(r, n_u))
-        return rfail(nullptr, HJB_E_INVALID, "%s: the model (A, B, c, q, r) is not finite", who);
-    if (n_steps > 0 && !value_plane_of_step) return rfail(nullptr, HJB_E_INVALID, "%s: null value_plane_of_step", who);
-    for (int k = 0; k < n_steps; ++k)
-        if (value_plane_of_step[k] < -1 || value_plane_of_step[k] >= n_value_planes)
-            return rfail(nullptr, HJB_E_INVALID, "%s: value_plane_of_step[%d] = %d outside [-1, %d)", who, k, value_plane_of_step[k], n_value_planes);
-    GreedyModel &M = P.M;
-    P.rdx.assign((size_t)n_knots, 0.0);
-    greedy_grid(D, n, knots, M, P.rdx.data());
-    M.n_u = n_u;
-    M.n_labels = n_labels;
-    M.has_c = c ? 1 : 0;
-    std::memcpy(M.A, A, sizeof(double) * D * D);
-    std::memcpy(M.B, B, sizeof(double) * D * n_u);
-    if (c) std::memcpy(M.c, c, sizeof(double) * D);
-    if (q) std::memcpy(M.q, q, sizeof(double) * D);
-    if (r) std::memcpy(M.r, r, sizeof(double) * n_u);
+int look_host_model(const char *who, const AffineHostArgs &a, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights,
+                    LookHostProblem &P) {
+    if (const int bad = affine_host_model(who, a, P)) return bad;
     P.L.mode = mode;
-    P.tab.assign((size_t)n_nodes * (1 + D), 0.0);
-    (void)look_table(D, n_nodes, offsets, weights, P.L, P.tab.data());
+    P.tab.assign((size_t)n_nodes * (1 + a.D), 0.0);
+    (void)look_table(a.D, n_nodes, offsets, weights, P.L, P.tab.data());
     P.L.tab = P.tab.data();
     return HJB_OK;
+}
+
+int check_streams(Rollout *ro, const char *who, int64_t n_traj, int64_t first_stream) {
+    if (first_stream < 0) return rfail(ro, HJB_E_INVALID, "%s: first_stream=%lld < 0", who, (long long)first_stream);
+    if (n_traj > 0 && first_stream > INT64_MAX - n_traj)
+        return rfail(ro, HJB_E_INVALID, "%s: first_stream + n_traj overflows (%lld + %lld)", who, (long long)first_stream, (long long)n_traj);
+    return HJB_OK;
+}
+
+size_t noisy_lds(const Rollout *ro, bool *on) {
+    const size_t lds = (size_t)(2 * (int64_t)ro->R.n_knots + (int64_t)ro->R.n_labels * ro->R.n_u + ro->N.n_tab) * sizeof(double);
+    *on = ro->lds && lds <= kLdsMax;
+    return lds;
 }
 
 DAttitude euler_attitude(double J1, double J2, double J3, double h) {
@@ -347,7 +372,91 @@ int run_chunks(Rollout *ro, const ChunkPlan &plan, const std::function<hipError_
     return done(HJB_OK);
 }
 
+int run_call(void *rollout, const ChunkPlan &plan, const std::function<int(Rollout *)> &no_object, const std::function<int(Rollout *)> &controller,
+             const std::function<int(Rollout *)> &starts, const std::function<hipError_t(const Chunk &)> &launch) {
+    Rollout *ro = (Rollout *)rollout;
+    if (no_object)
+        if (const int bad = no_object(ro)) return bad;
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
+    std::lock_guard<std::mutex> g(ro->mu);
+    if (const int bad = controller(ro)) return bad;
+    if (plan.n_traj == 0) {
+        if (plan.device_ms) *plan.device_ms = 0.0;
+        return HJB_OK;
+    }
+    if (const int bad = check_traj(ro, "rollout", plan.W, plan.wname, plan.n_steps, plan.n_traj, plan.X0, plan.X_final)) return bad;
+    if (starts)
+        if (const int bad = starts(ro)) return bad;
+    if (plan.device_ms) *plan.device_ms = 0.0;
+    return run_chunks(ro, plan, launch);
+}
+
 }  // namespace hjbhost
+
+namespace {
+
+// The plan every run function of the affine model starts from: D doubles of state, X_path and U_path, the cost.  D and n_u are
+// fixed by hjb_rollout_create, so they are read without the lock; of a null handle, which run_call refuses, nothing is read.
+ChunkPlan affine_plan(const Rollout *ro, const char *who, int32_t n_steps, const int32_t *planes, int64_t n_traj, const double *X0,
+                      double *X_final, double *cost, double *X_path, double *U_path, double *device_ms) {
+    const int D = ro ? ro->D : 0;
+    ChunkPlan plan{{who, D, "D", n_steps, planes, n_traj, X0, X_final, device_ms}};
+    plan.path[0] = {X_path, D, n_steps + 1};
+    plan.path[1] = {U_path, ro ? ro->R.n_u : 0, n_steps};
+    plan.cost = cost;
+    return plan;
+}
+
+// The greedy part of a chunk's launch record (hjb_rollout_run_greedy, hjb_rollout_run_lookahead): paths 0 .. 3 are X, U, L, V
+DGreedy greedy_of_chunk(const Rollout *ro, const Chunk &c) {
+    DGreedy G{};
+    G.R = c.R;
+    G.values = ro->dvalues;
+    G.nc = c.nc;
+    G.X0 = c.X0;
+    G.Xf = c.Xf;
+    G.cost = c.cost;
+    G.Xp = c.path[0];
+    G.Up = c.path[1];
+    G.Lp = c.path[2];
+    G.Vp = c.path[3];
+    return G;
+}
+
+// The object's noise set for a chunk of a call: the call's seed, the chunk's first stream - streams count through the call - and
+// its W_path
+DNoise noise_of_chunk(const Rollout *ro, const Chunk &c, uint64_t seed, int64_t first_stream, double *Wp) {
+    DNoise N = ro->N;
+    N.seed = seed;
+    N.first = (uint64_t)first_stream + (uint64_t)c.i0;
+    N.Wp = Wp;
+    return N;
+}
+
+// The shared tail of hjb_rollout_set_noise, _set_values and _set_lookahead, under ro->mu: `bytes` at src go to the object's device
+// in a DevData of their own (any false: no table, the set is detached), and once the object's stream is idle `holder` takes it,
+// which releases a table given earlier.  -> *dev, the table on the device (null for none); the caller's record fields follow
+// HJB_OK.  `big`: how the HJB_E_NOMEM refusal calls a table large enough to be checked against the free memory first (null: none is).
+int attach_table(Rollout *ro, const char *who, const void *src, size_t bytes, bool any, std::shared_ptr<DevData> &holder, const void **dev,
+                 const char *big = nullptr) {
+    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
+    if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
+    std::shared_ptr<DevData> nd;
+    *dev = nullptr;
+    if (any) {
+        size_t fr = 0, tot = 0;
+        if (big && hipMemGetInfo(&fr, &tot) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipMemGetInfo failed");
+        if (big && bytes + ((size_t)64 << 20) > fr)
+            return rfail(ro, HJB_E_NOMEM, "%s: %zu bytes of %s, %zu free on device %d", who, bytes, big, fr, ro->device);
+        nd = std::make_shared<DevData>(ro->device);
+        if (const int st = upload(ro, *nd, src, bytes, dev)) return st;
+    }
+    if (ro->stream) (void)hipStreamSynchronize(ro->stream);
+    holder = std::move(nd);
+    return HJB_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -495,21 +604,13 @@ int32_t hjb_rollout_set_option(void *rollout, const char *key, int64_t value) {
 
 int32_t hjb_rollout_run(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                         const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *device_ms) {
-    Rollout *ro = (Rollout *)rollout;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    const int bad_arg = check_run(ro, kModelAffine, method, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    if (device_ms) *device_ms = 0.0;
-    if (n_traj == 0) return HJB_OK;
-    const int D = ro->D;
-    const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    ChunkPlan plan{"hjb_rollout_run", D, n_steps, plane_of_step, n_traj, X0, X_final,
-                   {{X_path, D, n_steps + 1}, {U_path, ro->R.n_u, n_steps}}, cost, device_ms};
-    return run_chunks(ro, plan, [&](const Chunk &c) {
-        return launch_rollout(ro->idx_bytes, method, c.lds_on, D, c.R, c.nc, c.lds, c.st, c.X0, c.Xf, c.cost, c.path[0], c.path[1]);
-    });
+    const Rollout *ro = (const Rollout *)rollout;
+    const ChunkPlan plan = affine_plan(ro, "hjb_rollout_run", n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, device_ms);
+    return run_call(
+        rollout, plan, nullptr, [&](Rollout *o) { return check_run(o, kModelAffine, method, n_steps, plane_of_step, n_traj); }, nullptr,
+        [&](const Chunk &c) {
+            return launch_rollout(ro->idx_bytes, method, c.lds_on, plan.W, c.R, c.nc, c.lds, c.st, c.X0, c.Xf, c.cost, c.path[0], c.path[1]);
+        });
 }
 
 int32_t hjb_rollout_set_noise(void *rollout, int32_t n_nodes, const double *offsets, const double *weights) {
@@ -542,16 +643,8 @@ int32_t hjb_rollout_set_noise(void *rollout, int32_t n_nodes, const double *offs
             row += n_nodes;
         }
     }
-    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-    if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
-    std::shared_ptr<DevData> nd;
     const void *d = nullptr;
-    if (n_nodes > 0) {
-        nd = std::make_shared<DevData>(ro->device);
-        if (const int st = upload(ro, *nd, tab.data(), tab.size() * sizeof(double), &d)) return st;
-    }
-    if (ro->stream) (void)hipStreamSynchronize(ro->stream);
-    ro->noise = std::move(nd);                                // replaces (and releases) a node set given earlier
+    if (const int st = attach_table(ro, "hjb_rollout_set_noise", tab.data(), tab.size() * sizeof(double), n_nodes > 0, ro->noise, &d)) return st;
     ro->N = DNoise{};
     ro->N.n_nodes = n_nodes;
     ro->N.mask = mask;
@@ -564,37 +657,23 @@ int32_t hjb_rollout_set_noise(void *rollout, int32_t n_nodes, const double *offs
 int32_t hjb_rollout_run_noisy(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                               const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost, double *X_path,
                               double *U_path, double *W_path, double *device_ms) {
-    Rollout *ro = (Rollout *)rollout;
-    // every refusal before any device work, the outputs untouched; the one that needs no object first
-    if (first_stream < 0) return rfail(ro, HJB_E_INVALID, "hjb_rollout_run_noisy: first_stream=%lld < 0", (long long)first_stream);
-    if (n_traj > 0 && first_stream > INT64_MAX - n_traj)
-        return rfail(ro, HJB_E_INVALID, "hjb_rollout_run_noisy: first_stream + n_traj overflows (%lld + %lld)", (long long)first_stream,
-                     (long long)n_traj);
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    const int bad_arg = check_run(ro, kModelAffine, method, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    if (ro->N.n_nodes < 1) return rfail(ro, HJB_E_INVALID, "rollout: hjb_rollout_run_noisy before hjb_rollout_set_noise");
-    if (n_traj == 0) {
-        if (device_ms) *device_ms = 0.0;
-        return HJB_OK;
-    }
-    const int D = ro->D;
-    const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    if (device_ms) *device_ms = 0.0;
-    DNoise N = ro->N;
-    N.seed = seed;
-    ChunkPlan plan{"hjb_rollout_run_noisy", D, n_steps, plane_of_step, n_traj, X0, X_final,
-                   {{X_path, D, n_steps + 1}, {U_path, ro->R.n_u, n_steps}, {W_path, 1, n_steps}}, cost, device_ms};
-    return run_chunks(ro, plan, [&](const Chunk &c) {
-        DNoise Nc = N;
-        Nc.first = (uint64_t)first_stream + (uint64_t)c.i0;   // the chunk's offset in the call: streams count through the call
-        Nc.Wp = c.path[2];
-        const size_t lds_all = c.lds + (size_t)N.n_tab * sizeof(double);
-        return launch_rollout_noisy(ro->idx_bytes, method, ro->lds && lds_all <= kLdsMax, D, c.R, Nc, c.nc, lds_all, c.st, c.X0, c.Xf, c.cost,
-                                    c.path[0], c.path[1]);
-    });
+    const Rollout *ro = (const Rollout *)rollout;
+    const char *const who = "hjb_rollout_run_noisy";
+    ChunkPlan plan = affine_plan(ro, who, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, device_ms);
+    plan.path[2] = {W_path, 1, n_steps};
+    return run_call(
+        rollout, plan, [&](Rollout *o) { return check_streams(o, who, n_traj, first_stream); },
+        [&](Rollout *o) {
+            if (const int bad = check_run(o, kModelAffine, method, n_steps, plane_of_step, n_traj)) return bad;
+            return o->N.n_nodes < 1 ? rfail(o, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_noise", who) : HJB_OK;
+        },
+        nullptr,
+        [&](const Chunk &c) {
+            bool lds_on;
+            const size_t lds = noisy_lds(ro, &lds_on);
+            return launch_rollout_noisy(ro->idx_bytes, method, lds_on, plan.W, c.R, noise_of_chunk(ro, c, seed, first_stream, c.path[2]), c.nc, lds,
+                                        c.st, c.X0, c.Xf, c.cost, c.path[0], c.path[1]);
+        });
 }
 
 int32_t hjb_rollout_noise_table(int32_t n_nodes, const double *weights, double *thresholds) {
@@ -609,10 +688,8 @@ int32_t hjb_rollout_noise_table(int32_t n_nodes, const double *weights, double *
 int32_t hjb_rollout_noise_draw(uint64_t seed, int64_t first_stream, int64_t n_traj, int32_t n_steps, int32_t n_nodes,
                                const double *thresholds, int32_t *nodes) {
     const char *const who = "hjb_rollout_noise_draw";
-    if (first_stream < 0) return rfail(nullptr, HJB_E_INVALID, "%s: first_stream=%lld < 0", who, (long long)first_stream);
+    if (const int bad = check_streams(nullptr, who, n_traj, first_stream)) return bad;
     if (n_traj < 0 || n_steps < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_traj=%lld, n_steps=%d (both >= 0)", who, (long long)n_traj, n_steps);
-    if (n_traj > 0 && first_stream > INT64_MAX - n_traj)
-        return rfail(nullptr, HJB_E_INVALID, "%s: first_stream + n_traj overflows (%lld + %lld)", who, (long long)first_stream, (long long)n_traj);
     if (n_nodes < 1 || n_nodes > HJB_DIST_MAX_NODES) return rfail(nullptr, HJB_E_INVALID, "%s: n_nodes=%d not in 1..%d", who, n_nodes, HJB_DIST_MAX_NODES);
     if (n_nodes > 1 && !thresholds) return rfail(nullptr, HJB_E_INVALID, "%s: null thresholds", who);
     if (n_traj > 0 && n_steps > 0 && !nodes) return rfail(nullptr, HJB_E_INVALID, "%s: null nodes", who);
@@ -644,21 +721,8 @@ int32_t hjb_rollout_set_values(void *rollout, int32_t dtype, int32_t n_planes, c
     if ((int64_t)n_planes > kMaxStates / nS)
         return rfail(ro, HJB_E_INVALID, "%s: size overflow (%lld states x %d planes)", who, (long long)nS, n_planes);
     const int vb = dtype == HJB_F32 ? 4 : 8;
-    const size_t bytes = (size_t)nS * (size_t)n_planes * vb;
-    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-    if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
-    std::shared_ptr<DevData> vd;
     const void *d = nullptr;
-    if (n_planes > 0) {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipMemGetInfo failed");
-        if (bytes + ((size_t)64 << 20) > fr)
-            return rfail(ro, HJB_E_NOMEM, "%s: %zu bytes of value planes, %zu free on device %d", who, bytes, fr, ro->device);
-        vd = std::make_shared<DevData>(ro->device);
-        if (const int st = upload(ro, *vd, values, bytes, &d)) return st;
-    }
-    if (ro->stream) (void)hipStreamSynchronize(ro->stream);
-    ro->values = std::move(vd);                               // replaces (and releases) planes given earlier
+    if (const int st = attach_table(ro, who, values, (size_t)nS * (size_t)n_planes * vb, n_planes > 0, ro->values, &d, "value planes")) return st;
     ro->dvalues = d;
     ro->val_planes = n_planes;
     ro->val_bytes = vb;
@@ -668,50 +732,14 @@ int32_t hjb_rollout_set_values(void *rollout, int32_t dtype, int32_t n_planes, c
 int32_t hjb_rollout_run_greedy(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj, const double *X0,
                                double *X_final, double *cost, double *X_path, double *U_path, double *L_path, double *V_path,
                                double *device_ms) {
-    Rollout *ro = (Rollout *)rollout;
+    const Rollout *ro = (const Rollout *)rollout;
     const char *const who = "hjb_rollout_run_greedy";
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    // every refusal before any device work, the outputs untouched
-    if (n_steps < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_steps=%d < 0", n_steps);
-    if (n_traj < 0) return rfail(ro, HJB_E_INVALID, "rollout: n_traj=%lld < 0", (long long)n_traj);
-    if (ro->model == kModelNone) return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_model", who);
-    if (ro->model != kModelAffine)
-        return rfail(ro, HJB_E_INVALID, "rollout: %s needs the affine model (hjb_rollout_set_model); the object holds another", who);
-    if (n_steps > 0 && !value_plane_of_step) return rfail(ro, HJB_E_INVALID, "rollout: null value_plane_of_step");
-    for (int k = 0; k < n_steps; ++k) {
-        const int32_t p = value_plane_of_step[k];
-        if (p >= 0 && ro->val_planes < 1)
-            return rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_values (value_plane_of_step[%d] = %d; only -1 needs no values)",
-                         who, k, p);
-        if (p < -1 || p >= ro->val_planes)
-            return rfail(ro, HJB_E_INVALID, "rollout: value_plane_of_step[%d] = %d outside [-1, %d)", k, p, ro->val_planes);
-    }
-    if (n_traj == 0) {
-        if (device_ms) *device_ms = 0.0;
-        return HJB_OK;
-    }
-    const int D = ro->D;
-    const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    if (device_ms) *device_ms = 0.0;
-    ChunkPlan plan{who, D, n_steps, value_plane_of_step, n_traj, X0, X_final,
-                   {{X_path, D, n_steps + 1}, {U_path, ro->R.n_u, n_steps}, {L_path, 1, n_steps}, {V_path, 1, n_steps}}, cost,
-                   device_ms};
-    return run_chunks(ro, plan, [&](const Chunk &c) {
-        DGreedy G{};
-        G.R = c.R;
-        G.values = ro->dvalues;
-        G.nc = c.nc;
-        G.X0 = c.X0;
-        G.Xf = c.Xf;
-        G.cost = c.cost;
-        G.Xp = c.path[0];
-        G.Up = c.path[1];
-        G.Lp = c.path[2];
-        G.Vp = c.path[3];
-        return launch_rollout_greedy(ro->val_bytes, c.lds_on, D, G, c.lds, c.st);
-    });
+    ChunkPlan plan = affine_plan(ro, who, n_steps, value_plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, device_ms);
+    plan.path[2] = {L_path, 1, n_steps};
+    plan.path[3] = {V_path, 1, n_steps};
+    return run_call(
+        rollout, plan, nullptr, [&](Rollout *o) { return check_lookahead_run(o, who, 0, n_steps, value_plane_of_step, n_traj, false); }, nullptr,
+        [&](const Chunk &c) { return launch_rollout_greedy(ro->val_bytes, c.lds_on, plan.W, greedy_of_chunk(ro, c), c.lds, c.st); });
 }
 
 int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
@@ -720,41 +748,17 @@ int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots
                                 int64_t n_traj, const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
                                 double *L_path, double *V_path) {
     const char *const who = "hjb_rollout_greedy_host";
-    if (D < 1 || D > HJB_MAX_D) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, HJB_MAX_D);
-    if (n_u < 1 || n_u > HJB_ROLLOUT_MAX_U) return rfail(nullptr, HJB_E_UNSUPPORTED, "%s: n_u=%d not in 1..%d", who, n_u, HJB_ROLLOUT_MAX_U);
-    if (!n || !knots || !u_table || !A || !B) return rfail(nullptr, HJB_E_INVALID, "%s: null argument (n, knots, u_table, A and B are required)", who);
-    if (n_labels < 1) return rfail(nullptr, HJB_E_INVALID, "%s: n_labels=%d < 1", who, n_labels);
-    if (dtype != HJB_F32 && dtype != HJB_F64) return rfail(nullptr, HJB_E_INVALID, "%s: dtype %d is not HJB_F32 / HJB_F64", who, dtype);
-    if (n_value_planes < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_value_planes=%d < 0", who, n_value_planes);
-    if (n_value_planes > 0 && !values) return rfail(nullptr, HJB_E_INVALID, "%s: null values with n_value_planes=%d", who, n_value_planes);
-    if (n_steps < 0 || n_traj < 0) return rfail(nullptr, HJB_E_INVALID, "%s: n_steps=%d, n_traj=%lld (both >= 0)", who, n_steps, (long long)n_traj);
-    int64_t nS = 1, n_knots = 0;
-    if (const int bad_grid = check_grid(who, D, n, knots, &nS, &n_knots)) return bad_grid;
-    if (!all_finite(u_table, (int64_t)n_labels * n_u)) return rfail(nullptr, HJB_E_INVALID, "%s: u_table is not finite", who);
-    if (!all_finite(A, (int64_t)D * D) || !all_finite(B, (int64_t)D * n_u) || !all_finite(c, D) || !all_finite(q, D) || !all_finite(r, n_u))
-        return rfail(nullptr, HJB_E_INVALID, "%s: the model (A, B, c, q, r) is not finite", who);
-    if (n_steps > 0 && !value_plane_of_step) return rfail(nullptr, HJB_E_INVALID, "%s: null value_plane_of_step", who);
-    for (int k = 0; k < n_steps; ++k)
-        if (value_plane_of_step[k] < -1 || value_plane_of_step[k] >= n_value_planes)
-            return rfail(nullptr, HJB_E_INVALID, "%s: value_plane_of_step[%d] = %d outside [-1, %d)", who, k, value_plane_of_step[k], n_value_planes);
+    const AffineHostArgs a{D, n, knots, n_labels, n_u, u_table, A, B, c, q, r, dtype, n_value_planes, values, n_steps, value_plane_of_step};
+    if (const int bad = affine_host_args(who, a, n_traj)) return bad;
+    AffineHostProblem P;
+    if (const int bad = affine_host_model(who, a, P)) return bad;
     if (n_traj == 0) return HJB_OK;
     const int bad_traj = check_traj(nullptr, who, D, "D", n_steps, n_traj, X0, X_final);
     if (bad_traj) return bad_traj;
-    GreedyModel M{};
-    std::vector<double> rdx((size_t)n_knots);
-    greedy_grid(D, n, knots, M, rdx.data());
-    M.n_u = n_u;
-    M.n_labels = n_labels;
-    M.has_c = c ? 1 : 0;
-    std::memcpy(M.A, A, sizeof(double) * D * D);
-    std::memcpy(M.B, B, sizeof(double) * D * n_u);
-    if (c) std::memcpy(M.c, c, sizeof(double) * D);
-    if (q) std::memcpy(M.q, q, sizeof(double) * D);
-    if (r) std::memcpy(M.r, r, sizeof(double) * n_u);
     with_bool(dtype == HJB_F32, [&](auto f) {
         with_dim(D, [&](auto d) {
             using TV = std::conditional_t<decltype(f)::value, float, double>;
-            greedy_rollout_host<decltype(d)::value, TV>(M, knots, rdx.data(), u_table, static_cast<const TV *>(values), n_steps,
+            greedy_rollout_host<decltype(d)::value, TV>(P.M, knots, P.rdx.data(), u_table, static_cast<const TV *>(values), n_steps,
                                                         value_plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, L_path, V_path);
         });
     });
@@ -774,16 +778,8 @@ int32_t hjb_rollout_set_lookahead(void *rollout, int32_t mode, int32_t n_nodes, 
     L.mode = mode;
     std::vector<double> tab((size_t)n_nodes * (1 + D));
     const int n_tab = look_table(D, n_nodes, offsets, weights, L, tab.data());
-    std::shared_lock<std::shared_mutex> lk(g_capture_mu);
-    if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
-    std::shared_ptr<DevData> nd;
     const void *d = nullptr;
-    if (n_nodes > 0) {
-        nd = std::make_shared<DevData>(ro->device);
-        if (const int st = upload(ro, *nd, tab.data(), (size_t)n_tab * sizeof(double), &d)) return st;
-    }
-    if (ro->stream) (void)hipStreamSynchronize(ro->stream);
-    ro->look = std::move(nd);                                 // replaces (and releases) a node set given earlier
+    if (const int st = attach_table(ro, who, tab.data(), (size_t)n_tab * sizeof(double), n_nodes > 0, ro->look, &d)) return st;
     ro->L = L;
     ro->L.tab = (const double *)d;
     return HJB_OK;
@@ -792,50 +788,30 @@ int32_t hjb_rollout_set_lookahead(void *rollout, int32_t mode, int32_t n_nodes, 
 int32_t hjb_rollout_run_lookahead(void *rollout, int32_t fly_noise, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_traj,
                                   const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost, double *X_path,
                                   double *U_path, double *L_path, double *V_path, double *W_path, double *device_ms) {
-    Rollout *ro = (Rollout *)rollout;
+    const Rollout *ro = (const Rollout *)rollout;
     const char *const who = "hjb_rollout_run_lookahead";
-    // every refusal before any device work, the outputs untouched; the ones that need no object first
-    if (fly_noise != 0 && fly_noise != 1) return rfail(ro, HJB_E_INVALID, "%s: fly_noise=%d is not 0 or 1", who, fly_noise);
-    if (!fly_noise && W_path) return rfail(ro, HJB_E_INVALID, "%s: W_path given with fly_noise=0 (a nominal plant draws no node)", who);
-    if (fly_noise && first_stream < 0) return rfail(ro, HJB_E_INVALID, "%s: first_stream=%lld < 0", who, (long long)first_stream);
-    if (fly_noise && n_traj > 0 && first_stream > INT64_MAX - n_traj)
-        return rfail(ro, HJB_E_INVALID, "%s: first_stream + n_traj overflows (%lld + %lld)", who, (long long)first_stream, (long long)n_traj);
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    if (const int bad = check_lookahead_run(ro, who, fly_noise, n_steps, value_plane_of_step, n_traj)) return bad;
-    if (n_traj == 0) {
-        if (device_ms) *device_ms = 0.0;
-        return HJB_OK;
-    }
-    const int D = ro->D;
-    const int bad_traj = check_traj(ro, "rollout", D, "D", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    if (device_ms) *device_ms = 0.0;
-    DNoise N = ro->N;
-    N.seed = seed;
-    ChunkPlan plan{who, D, n_steps, value_plane_of_step, n_traj, X0, X_final,
-                   {{X_path, D, n_steps + 1}, {U_path, ro->R.n_u, n_steps}, {L_path, 1, n_steps}, {V_path, 1, n_steps}, {W_path, 1, n_steps}},
-                   cost, device_ms};
-    return run_chunks(ro, plan, [&](const Chunk &c) {
-        DLook A{};
-        A.G.R = c.R;
-        A.G.values = ro->dvalues;
-        A.G.nc = c.nc;
-        A.G.X0 = c.X0;
-        A.G.Xf = c.Xf;
-        A.G.cost = c.cost;
-        A.G.Xp = c.path[0];
-        A.G.Up = c.path[1];
-        A.G.Lp = c.path[2];
-        A.G.Vp = c.path[3];
-        A.L = ro->L;
-        if (!fly_noise) return launch_rollout_lookahead(ro->val_bytes, c.lds_on, D, A, c.lds, c.st);
-        A.N = N;
-        A.N.first = (uint64_t)first_stream + (uint64_t)c.i0;  // the chunk's offset in the call: streams count through the call
-        A.N.Wp = c.path[4];
-        const size_t lds_all = c.lds + (size_t)N.n_tab * sizeof(double);
-        return launch_rollout_lookahead_fly(ro->val_bytes, ro->lds && lds_all <= kLdsMax, D, A, lds_all, c.st);
-    });
+    ChunkPlan plan = affine_plan(ro, who, n_steps, value_plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, device_ms);
+    plan.path[2] = {L_path, 1, n_steps};
+    plan.path[3] = {V_path, 1, n_steps};
+    plan.path[4] = {W_path, 1, n_steps};
+    return run_call(
+        rollout, plan,
+        [&](Rollout *o) {
+            if (fly_noise != 0 && fly_noise != 1) return rfail(o, HJB_E_INVALID, "%s: fly_noise=%d is not 0 or 1", who, fly_noise);
+            if (!fly_noise && W_path) return rfail(o, HJB_E_INVALID, "%s: W_path given with fly_noise=0 (a nominal plant draws no node)", who);
+            return fly_noise ? check_streams(o, who, n_traj, first_stream) : HJB_OK;
+        },
+        [&](Rollout *o) { return check_lookahead_run(o, who, fly_noise, n_steps, value_plane_of_step, n_traj); }, nullptr,
+        [&](const Chunk &c) {
+            DLook A{};
+            A.G = greedy_of_chunk(ro, c);
+            A.L = ro->L;
+            if (!fly_noise) return launch_rollout_lookahead(ro->val_bytes, c.lds_on, plan.W, A, c.lds, c.st);
+            A.N = noise_of_chunk(ro, c, seed, first_stream, c.path[4]);
+            bool lds_on;
+            const size_t lds = noisy_lds(ro, &lds_on);
+            return launch_rollout_lookahead_fly(ro->val_bytes, lds_on, plan.W, A, lds, c.st);
+        });
 }
 
 int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
@@ -845,9 +821,8 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
                                    double *L_path, double *V_path, int32_t mode, int32_t n_nodes, const double *offsets,
                                    const double *weights, const int32_t *nodes, int32_t n_flight_nodes, const double *flight_offsets) {
     const char *const who = "hjb_rollout_lookahead_host";
-    if (const int bad = look_host_args(who, D, n, knots, n_labels, n_u, u_table, A, B, dtype, n_value_planes, values, n_steps, n_traj, mode,
-                                       n_nodes, offsets, weights))
-        return bad;
+    const AffineHostArgs a{D, n, knots, n_labels, n_u, u_table, A, B, c, q, r, dtype, n_value_planes, values, n_steps, value_plane_of_step};
+    if (const int bad = look_host_args(who, a, n_traj, mode, n_nodes, offsets, weights)) return bad;
     if (nodes) {
         if (n_flight_nodes < 1 || n_flight_nodes > HJB_DIST_MAX_NODES)
             return rfail(nullptr, HJB_E_INVALID, "%s: n_flight_nodes=%d not in 1..%d", who, n_flight_nodes, HJB_DIST_MAX_NODES);
@@ -855,9 +830,7 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
         if (!all_finite(flight_offsets, (int64_t)D * n_flight_nodes)) return rfail(nullptr, HJB_E_INVALID, "%s: flight_offsets is not finite", who);
     }
     LookHostProblem P;
-    if (const int bad = look_host_model(who, D, n, knots, n_labels, n_u, u_table, A, B, c, q, r, n_value_planes, n_steps, value_plane_of_step,
-                                        mode, n_nodes, offsets, weights, P))
-        return bad;
+    if (const int bad = look_host_model(who, a, mode, n_nodes, offsets, weights, P)) return bad;
     if (n_traj == 0) return HJB_OK;
     const int bad_traj = check_traj(nullptr, who, D, "D", n_steps, n_traj, X0, X_final);
     if (bad_traj) return bad_traj;
@@ -883,23 +856,16 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
 int32_t hjb_rollout_run_attitude(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                                  const double *X0, double *X_final, double *cost, double *X_path, double *U_path, double *A_path,
                                  double *device_ms) {
-    Rollout *ro = (Rollout *)rollout;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    const int bad_arg = check_run(ro, kModelAttitude, method, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    if (device_ms) *device_ms = 0.0;
-    if (n_traj == 0) return HJB_OK;
-    int bad_traj = check_traj(ro, "rollout", HJB_ATT_W, "7", n_steps, n_traj, X0, X_final);
-    if (!bad_traj) bad_traj = check_quaternions(ro, "rollout", n_traj, X0);
-    if (bad_traj) return bad_traj;
-    const DAttitude M = ro->M;
-    ChunkPlan plan{"hjb_rollout_run_attitude", HJB_ATT_W, n_steps, plane_of_step, n_traj, X0, X_final,
-                   {{X_path, HJB_ATT_W, n_steps + 1}, {U_path, HJB_ATT_U, n_steps}, {A_path, 3, n_steps}}, cost, device_ms};
-    return run_chunks(ro, plan, [&](const Chunk &c) {
-        return launch_rollout_attitude(ro->idx_bytes, method, c.lds_on, ro->integrator, c.R, M, c.nc, c.lds, c.st, c.X0, c.Xf, c.cost, c.path[0],
-                                       c.path[1], c.path[2]);
-    });
+    const Rollout *ro = (const Rollout *)rollout;
+    const ChunkPlan plan{{"hjb_rollout_run_attitude", HJB_ATT_W, "7", n_steps, plane_of_step, n_traj, X0, X_final, device_ms},
+                         {{X_path, HJB_ATT_W, n_steps + 1}, {U_path, HJB_ATT_U, n_steps}, {A_path, 3, n_steps}}, cost};
+    return run_call(
+        rollout, plan, nullptr, [&](Rollout *o) { return check_run(o, kModelAttitude, method, n_steps, plane_of_step, n_traj); },
+        [&](Rollout *o) { return check_quaternions(o, "rollout", n_traj, X0); },
+        [&](const Chunk &c) {
+            return launch_rollout_attitude(ro->idx_bytes, method, c.lds_on, ro->integrator, c.R, ro->M, c.nc, c.lds, c.st, c.X0, c.Xf, c.cost,
+                                           c.path[0], c.path[1], c.path[2]);
+        });
 }
 
 int32_t hjb_attitude_linear_response(int32_t device, const double *inertia, double h, int32_t integrator, const double *K,
@@ -963,8 +929,8 @@ int32_t hjb_attitude_linear_response(int32_t device, const double *inertia, doub
             return rfail(nullptr, HJB_E_DEVICE, "%s: stream creation failed", who);
         }
     }
-    ChunkPlan plan{who, HJB_ATT_W, n_steps, nullptr, n_traj, X0, X_final,
-                   {{X_path, HJB_ATT_W, n_steps + 1}, {U_path, HJB_ATT_U, n_steps}, {A_path, 3, n_steps}}, cost, device_ms};
+    ChunkPlan plan{{who, HJB_ATT_W, "7", n_steps, nullptr, n_traj, X0, X_final, device_ms},
+                   {{X_path, HJB_ATT_W, n_steps + 1}, {U_path, HJB_ATT_U, n_steps}, {A_path, 3, n_steps}}, cost};
     const int st = run_chunks(&ro, plan, [&](const Chunk &c) {
         DAttLinear Mk = M;
         Mk.n_steps = c.R.n_steps;

@@ -136,10 +136,7 @@ int run_campaign_launches(Rollout *ro, const CampaignCall &call, const CampaignP
         c.C[r] = Cp;
         c.C[r].partials = dpart[r];
     }
-    // the LDS rule of hjb_rollout_run_noisy: the channel's tables and the node block together
-    const size_t lds = (size_t)(2 * (int64_t)ro->R.n_knots + (int64_t)ro->R.n_labels * ro->R.n_u + c.N.n_tab) * sizeof(double);
-    c.lds_on = ro->lds && lds <= kLdsMax;
-    c.lds = lds;
+    const size_t lds = c.lds = noisy_lds(ro, &c.lds_on);
     if (hist) {                                               // the accumulation form and its LDS bytes, with the tables' placement
         c.lds = campaign_hist_form(Cp.G, hist->n_bins, ro->lds, lds, kLdsMax, &c.lds_on, &c.H);
         c.H.range = (const double *)drange;

@@ -62,19 +62,39 @@ DPaChan pa_channel(const DRollout &R) {
     return c;
 }
 
-DPaChan on_planes(DPaChan c, const int32_t *plane_of_step) {
-    c.plane_of_step = plane_of_step;
-    return c;
+// The channels of a chunk's launch: the object's own policy, the two it has attached and `extra` (the fault controller's; null:
+// three channels), each on the chunk's planes; the LDS bytes of their [knots | 1/dx | u_table], `width` u_table doubles per
+// label, and the placement (option "lds" and the bytes fit kLdsMax).  Under ro->mu.
+struct Channels {
+    DPaChan c[4];
+    size_t lds;
+    bool lds_on;
+};
+
+Channels channels(const Rollout *ro, const Chunk &k, int width, const DPaChan *extra = nullptr) {
+    Channels ch{{pa_channel(ro->R), ro->att->c[0], ro->att->c[1], extra ? *extra : DPaChan{}}};
+    int64_t nk = 0, nl = 0;
+    for (DPaChan &c : ch.c) {
+        c.plane_of_step = k.R.plane_of_step;
+        nk += c.n_knots;
+        nl += c.n_labels;
+    }
+    ch.lds = (size_t)(2 * nk + width * nl) * sizeof(double);
+    ch.lds_on = ro->lds && ch.lds <= kLdsMax;
+    return ch;
 }
 
-// the LDS bytes of the channels' [knots | 1/dx | u_table], `width` u_table doubles per label
-size_t lds_bytes(std::initializer_list<const DPaChan *> chans, int width) {
-    int64_t nk = 0, nl = 0;
-    for (const DPaChan *c : chans) {
-        nk += c->n_knots;
-        nl += c->n_labels;
-    }
-    return (size_t)(2 * nk + width * nl) * sizeof(double);
+// a model's record for a chunk: the stages the call runs
+template <typename TM>
+TM for_chunk(TM M, const Chunk &k) {
+    M.n_steps = k.R.n_steps;
+    return M;
+}
+
+// the model of three channels an object holds, as its run function reads it (check_run has passed: att is of that type)
+template <typename TA>
+const TA &attached(const Rollout *ro) {
+    return static_cast<const TA &>(*ro->att);
 }
 
 // Another object's policy as a channel: a snapshot with a share of its device data, taken under that object's own lock
@@ -164,6 +184,15 @@ int invert3(Rollout *ro, std::initializer_list<Mat3> ms) {
         pa_inv3(m.rows, m.inv);
         if (!all_finite(m.inv, 9)) return rfail(ro, HJB_E_INVALID, "rollout: %s is singular (its inverse is not finite)", m.name);
     }
+    return HJB_OK;
+}
+
+// What both pos-att run functions refuse under the lock: check_run's, then more stages than the orbit table covers
+int check_pos_att_run(Rollout *ro, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj) {
+    if (const int bad = check_run(ro, kModelPosAtt, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj)) return bad;
+    const int max_steps = attached<PosAtt>(ro).max_steps;
+    if (n_steps > max_steps)
+        return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the orbit table covers %d stages ((n_nodes - 1) / (2 substeps))", n_steps, max_steps);
     return HJB_OK;
 }
 
@@ -308,151 +337,111 @@ int32_t hjb_rollout_set_attitude_simplified_model(void *rollout_1, void *rollout
 
 int32_t hjb_rollout_run_pos_att(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
                                 double *X_final, double *X_path, double *F_path, double *FM_path) {
-    Rollout *ro = (Rollout *)rollout_x;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    const int bad_arg = check_run(ro, kModelPosAtt, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    const PosAtt &pa = static_cast<const PosAtt &>(*ro->att);
-    if (n_steps > pa.max_steps)
-        return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the orbit table covers %d stages ((n_nodes - 1) / (2 substeps))", n_steps,
-                     pa.max_steps);
-    if (n_traj == 0) return HJB_OK;
-    const int bad_traj = check_traj(ro, "rollout", HJB_PA_W, "13", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    const DPaChan cx0 = pa_channel(ro->R);
-    const size_t lds3 = lds_bytes({&cx0, &pa.c[0], &pa.c[1]}, 4);
-    const bool lds3_on = ro->lds && lds3 <= kLdsMax;
-    ChunkPlan plan{"hjb_rollout_run_pos_att", HJB_PA_W, n_steps, plane_of_step, n_traj, X0, X_final,
-                   {{X_path, HJB_PA_W, n_steps + 1}, {F_path, HJB_PA_F, n_steps}, {FM_path, HJB_PA_FM, n_steps}}};
-    return run_chunks(ro, plan, [&](const Chunk &c) {
-        const int32_t *pl = c.R.plane_of_step;
-        DPosAtt M = pa.M;
-        M.n_steps = c.R.n_steps;
-        return launch_rollout_pos_att(ro->idx_bytes, lds3_on, on_planes(cx0, pl), on_planes(pa.c[0], pl), on_planes(pa.c[1], pl), M, c.nc, lds3,
-                                      c.st, c.X0, c.Xf, c.path[0], c.path[1], c.path[2]);
-    });
+    const Rollout *ro = (const Rollout *)rollout_x;
+    const ChunkPlan plan{{"hjb_rollout_run_pos_att", HJB_PA_W, "13", n_steps, plane_of_step, n_traj, X0, X_final, nullptr},
+                         {{X_path, HJB_PA_W, n_steps + 1}, {F_path, HJB_PA_F, n_steps}, {FM_path, HJB_PA_FM, n_steps}}};
+    return run_call(
+        rollout_x, plan, nullptr, [&](Rollout *o) { return check_pos_att_run(o, n_steps, plane_of_step, n_traj); }, nullptr,
+        [&](const Chunk &c) {
+            const Channels ch = channels(ro, c, 4);
+            return launch_rollout_pos_att(ro->idx_bytes, ch.lds_on, ch.c[0], ch.c[1], ch.c[2], for_chunk(attached<PosAtt>(ro).M, c), c.nc, ch.lds,
+                                          c.st, c.X0, c.Xf, c.path[0], c.path[1], c.path[2]);
+        });
 }
 
 int32_t hjb_rollout_run_pos_att_faults(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                                        const double *X0, const int32_t *fault_mask, const int32_t *fault_stage,
                                        const int32_t *switch_stage, double pos_tol, double att_tol, double *X_final, double *impulse,
                                        int32_t *settle_stage, double *X_path, double *F_path, double *FM_path, double *device_ms) {
-    Rollout *ro = (Rollout *)rollout_x;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    // every refusal before any device work, the outputs untouched
-    const int bad_arg = check_run(ro, kModelPosAtt, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    const PosAtt &pa = static_cast<const PosAtt &>(*ro->att);
-    if (n_steps > pa.max_steps)
-        return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the orbit table covers %d stages ((n_nodes - 1) / (2 substeps))", n_steps,
-                     pa.max_steps);
-    if (pa.has_xf)
-        for (int k = 0; k < n_steps; ++k)
-            if (plane_of_step[k] >= pa.planes_xf)
-                return rfail(ro, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d) (the fault controller's planes)", k,
-                             plane_of_step[k], pa.planes_xf);
-    if (!(pos_tol >= 0)) return rfail(ro, HJB_E_INVALID, "rollout: pos_tol = %g is NaN or negative", pos_tol);
-    if (!(att_tol >= 0)) return rfail(ro, HJB_E_INVALID, "rollout: att_tol = %g is NaN or negative", att_tol);
-    if (n_traj == 0) {
-        if (device_ms) *device_ms = 0.0;
-        return HJB_OK;
-    }
-    const int bad_traj = check_traj(ro, "rollout", HJB_PA_W, "13", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    for (int64_t i = 0; i < n_traj; ++i) {
-        if (fault_mask && (fault_mask[i] & ~0xFFF))
-            return rfail(ro, HJB_E_INVALID, "rollout: fault_mask[%lld] = 0x%x has a bit above 11 (twelve thrusters)", (long long)i,
-                         (unsigned)fault_mask[i]);
-        if (fault_stage && fault_stage[i] < 0)
-            return rfail(ro, HJB_E_INVALID, "rollout: fault_stage[%lld] = %d < 0", (long long)i, fault_stage[i]);
-        if (switch_stage && switch_stage[i] < 0)
-            return rfail(ro, HJB_E_INVALID, "rollout: switch_stage[%lld] = %d < 0", (long long)i, switch_stage[i]);
-        if (switch_stage && switch_stage[i] < n_steps && !pa.has_xf)
-            return rfail(ro, HJB_E_INVALID, "rollout: switch_stage[%lld] = %d hands over within the %d stages, but no fault controller is "
-                         "attached (hjb_rollout_set_pos_att_fault_controller)", (long long)i, switch_stage[i], n_steps);
-    }
-    const DPaChan cx0 = pa_channel(ro->R);
-    const size_t lds4 = lds_bytes({&cx0, &pa.c[0], &pa.c[1], &pa.cxf}, 4);
-    const bool lds4_on = ro->lds && lds4 <= kLdsMax;
-    DPaFault Q{};
-    Q.h = pa.h;
-    Q.p2 = pos_tol * pos_tol;
-    Q.a2 = att_tol * att_tol;
-    ChunkPlan plan{"hjb_rollout_run_pos_att_faults", HJB_PA_W, n_steps, plane_of_step, n_traj, X0, X_final,
-                   {{X_path, HJB_PA_W, n_steps + 1}, {F_path, HJB_PA_F, n_steps}, {FM_path, HJB_PA_FM, n_steps}}, impulse, device_ms,
-                   settle_stage, {fault_mask, fault_stage, switch_stage}};
-    return run_chunks(ro, plan, [&](const Chunk &c) {
-        const int32_t *pl = c.R.plane_of_step;
-        DPosAtt M = pa.M;
-        M.n_steps = c.R.n_steps;
-        DPaFault Qc = Q;
-        Qc.mask = c.input[0];
-        Qc.fault_stage = c.input[1];
-        Qc.switch_stage = c.input[2];
-        Qc.impulse = c.cost;
-        Qc.settle = c.flags;
-        return launch_rollout_pos_att_faults(ro->idx_bytes, lds4_on, on_planes(cx0, pl), on_planes(pa.c[0], pl), on_planes(pa.c[1], pl),
-                                             on_planes(pa.cxf, pl), M, Qc, c.nc, lds4, c.st, c.X0, c.Xf, c.path[0], c.path[1], c.path[2]);
-    });
+    const Rollout *ro = (const Rollout *)rollout_x;
+    const ChunkPlan plan{{"hjb_rollout_run_pos_att_faults", HJB_PA_W, "13", n_steps, plane_of_step, n_traj, X0, X_final, device_ms},
+                         {{X_path, HJB_PA_W, n_steps + 1}, {F_path, HJB_PA_F, n_steps}, {FM_path, HJB_PA_FM, n_steps}}, impulse, settle_stage,
+                         {fault_mask, fault_stage, switch_stage}};
+    return run_call(
+        rollout_x, plan, nullptr,
+        [&](Rollout *o) {
+            if (const int bad = check_pos_att_run(o, n_steps, plane_of_step, n_traj)) return bad;
+            const PosAtt &pa = attached<PosAtt>(o);
+            if (pa.has_xf)
+                for (int k = 0; k < n_steps; ++k)
+                    if (plane_of_step[k] >= pa.planes_xf)
+                        return rfail(o, HJB_E_INVALID, "rollout: plane_of_step[%d] = %d outside [0, %d) (the fault controller's planes)", k,
+                                     plane_of_step[k], pa.planes_xf);
+            if (!(pos_tol >= 0)) return rfail(o, HJB_E_INVALID, "rollout: pos_tol = %g is NaN or negative", pos_tol);
+            if (!(att_tol >= 0)) return rfail(o, HJB_E_INVALID, "rollout: att_tol = %g is NaN or negative", att_tol);
+            return HJB_OK;
+        },
+        [&](Rollout *o) {
+            const bool has_xf = attached<PosAtt>(o).has_xf;
+            for (int64_t i = 0; i < n_traj; ++i) {
+                if (fault_mask && (fault_mask[i] & ~0xFFF))
+                    return rfail(o, HJB_E_INVALID, "rollout: fault_mask[%lld] = 0x%x has a bit above 11 (twelve thrusters)", (long long)i,
+                                 (unsigned)fault_mask[i]);
+                if (fault_stage && fault_stage[i] < 0)
+                    return rfail(o, HJB_E_INVALID, "rollout: fault_stage[%lld] = %d < 0", (long long)i, fault_stage[i]);
+                if (switch_stage && switch_stage[i] < 0)
+                    return rfail(o, HJB_E_INVALID, "rollout: switch_stage[%lld] = %d < 0", (long long)i, switch_stage[i]);
+                if (switch_stage && switch_stage[i] < n_steps && !has_xf)
+                    return rfail(o, HJB_E_INVALID, "rollout: switch_stage[%lld] = %d hands over within the %d stages, but no fault controller is "
+                                 "attached (hjb_rollout_set_pos_att_fault_controller)", (long long)i, switch_stage[i], n_steps);
+            }
+            return HJB_OK;
+        },
+        [&](const Chunk &c) {
+            const PosAtt &pa = attached<PosAtt>(ro);
+            const Channels ch = channels(ro, c, 4, &pa.cxf);
+            DPaFault Q{};
+            Q.h = pa.h;
+            Q.p2 = pos_tol * pos_tol;
+            Q.a2 = att_tol * att_tol;
+            Q.mask = c.input[0];
+            Q.fault_stage = c.input[1];
+            Q.switch_stage = c.input[2];
+            Q.impulse = c.cost;
+            Q.settle = c.flags;
+            return launch_rollout_pos_att_faults(ro->idx_bytes, ch.lds_on, ch.c[0], ch.c[1], ch.c[2], ch.c[3], for_chunk(pa.M, c), Q, c.nc, ch.lds,
+                                                 c.st, c.X0, c.Xf, c.path[0], c.path[1], c.path[2]);
+        });
 }
 
 int32_t hjb_rollout_run_position(void *rollout_x, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj, const double *X0,
                                  double *X_final, double *X_path, double *A_path, int32_t *off_schedule) {
-    Rollout *ro = (Rollout *)rollout_x;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    const int bad_arg = check_run(ro, kModelPosition, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    const Position &ps = static_cast<const Position &>(*ro->att);
-    if (n_steps > ps.max_steps)
-        return rfail(ro, HJB_E_INVALID, "rollout: n_steps = %d, the RKF45 table covers %d stages", n_steps, ps.max_steps);
-    if (n_traj == 0) return HJB_OK;
-    // this entry point's own null check (off_schedule is required): check_traj's of X0 / X_final cannot fire after it
-    if (!X0 || !X_final || !off_schedule) return rfail(ro, HJB_E_INVALID, "rollout: null X0 / X_final / off_schedule");
-    const int bad_traj = check_traj(ro, "rollout", HJB_POS_W, "6", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    const DPaChan cx0 = pa_channel(ro->R);
-    const size_t lds3 = lds_bytes({&cx0, &ps.c[0], &ps.c[1]}, 1);
-    const bool lds3_on = ro->lds && lds3 <= kLdsMax;
-    ChunkPlan plan{"hjb_rollout_run_position", HJB_POS_W, n_steps, plane_of_step, n_traj, X0, X_final,
-                   {{X_path, HJB_POS_W, n_steps + 1}, {A_path, HJB_POS_A, n_steps}}};
-    plan.flags = off_schedule;
-    return run_chunks(ro, plan, [&](const Chunk &c) {
-        const int32_t *pl = c.R.plane_of_step;
-        DPosition M = ps.M;
-        M.n_steps = c.R.n_steps;
-        return launch_rollout_position(ro->idx_bytes, lds3_on, on_planes(cx0, pl), on_planes(ps.c[0], pl), on_planes(ps.c[1], pl), M, c.nc, lds3,
-                                       c.st, c.X0, c.Xf, c.path[0], c.path[1], c.flags);
-    });
+    const Rollout *ro = (const Rollout *)rollout_x;
+    const ChunkPlan plan{{"hjb_rollout_run_position", HJB_POS_W, "6", n_steps, plane_of_step, n_traj, X0, X_final, nullptr},
+                         {{X_path, HJB_POS_W, n_steps + 1}, {A_path, HJB_POS_A, n_steps}}, nullptr, off_schedule};
+    return run_call(
+        rollout_x, plan, nullptr,
+        [&](Rollout *o) {
+            if (const int bad = check_run(o, kModelPosition, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj)) return bad;
+            const int max_steps = attached<Position>(o).max_steps;
+            if (n_steps > max_steps) return rfail(o, HJB_E_INVALID, "rollout: n_steps = %d, the RKF45 table covers %d stages", n_steps, max_steps);
+            // this entry point's own null check, the last before the empty call, which needs none of the three (off_schedule is
+            // required): check_traj's of X0 / X_final cannot fire after it
+            if (n_traj > 0 && (!X0 || !X_final || !off_schedule)) return rfail(o, HJB_E_INVALID, "rollout: null X0 / X_final / off_schedule");
+            return HJB_OK;
+        },
+        nullptr,
+        [&](const Chunk &c) {
+            const Channels ch = channels(ro, c, 1);
+            return launch_rollout_position(ro->idx_bytes, ch.lds_on, ch.c[0], ch.c[1], ch.c[2], for_chunk(attached<Position>(ro).M, c), c.nc, ch.lds,
+                                           c.st, c.X0, c.Xf, c.path[0], c.path[1], c.flags);
+        });
 }
 
 int32_t hjb_rollout_run_attitude_simplified(void *rollout_1, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                                             const double *X0, double *X_final, double *cost, double *X_path, double *U_path,
                                             double *A_path) {
-    Rollout *ro = (Rollout *)rollout_1;
-    if (!ro) return rfail(nullptr, HJB_E_INVALID, "rollout: null handle");
-    std::lock_guard<std::mutex> g(ro->mu);
-    const int bad_arg = check_run(ro, kModelAttSimplified, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj);
-    if (bad_arg) return bad_arg;
-    const AttSimplified &as = static_cast<const AttSimplified &>(*ro->att);
-    if (n_traj == 0) return HJB_OK;
-    const int bad_traj = check_traj(ro, "rollout", HJB_ATT_W, "7", n_steps, n_traj, X0, X_final);
-    if (bad_traj) return bad_traj;
-    const DPaChan c10 = pa_channel(ro->R);
-    const size_t lds3 = lds_bytes({&c10, &as.c[0], &as.c[1]}, 1);
-    const bool lds3_on = ro->lds && lds3 <= kLdsMax;
-    ChunkPlan plan{"hjb_rollout_run_attitude_simplified", HJB_ATT_W, n_steps, plane_of_step, n_traj, X0, X_final,
-                   {{X_path, HJB_ATT_W, n_steps + 1}, {U_path, HJB_ATT_U, n_steps}, {A_path, 3, n_steps}}, cost};
-    return run_chunks(ro, plan, [&](const Chunk &c) {
-        const int32_t *pl = c.R.plane_of_step;
-        DAttSimplified M = as.M;
-        M.n_steps = c.R.n_steps;
-        return launch_rollout_attitude_simplified(ro->idx_bytes, lds3_on, as.dynamics, on_planes(c10, pl), on_planes(as.c[0], pl),
-                                                  on_planes(as.c[1], pl), M, c.nc, lds3, c.st, c.X0, c.Xf, c.cost, c.path[0], c.path[1],
-                                                  c.path[2]);
-    });
+    const Rollout *ro = (const Rollout *)rollout_1;
+    const ChunkPlan plan{{"hjb_rollout_run_attitude_simplified", HJB_ATT_W, "7", n_steps, plane_of_step, n_traj, X0, X_final, nullptr},
+                         {{X_path, HJB_ATT_W, n_steps + 1}, {U_path, HJB_ATT_U, n_steps}, {A_path, 3, n_steps}}, cost};
+    return run_call(
+        rollout_1, plan, nullptr, [&](Rollout *o) { return check_run(o, kModelAttSimplified, HJB_LOOKUP_NEAREST, n_steps, plane_of_step, n_traj); },
+        nullptr, [&](const Chunk &c) {
+            const AttSimplified &as = attached<AttSimplified>(ro);
+            const Channels ch = channels(ro, c, 1);
+            return launch_rollout_attitude_simplified(ro->idx_bytes, ch.lds_on, as.dynamics, ch.c[0], ch.c[1], ch.c[2], for_chunk(as.M, c), c.nc,
+                                                      ch.lds, c.st, c.X0, c.Xf, c.cost, c.path[0], c.path[1], c.path[2]);
+        });
 }
 
 }  // extern "C"

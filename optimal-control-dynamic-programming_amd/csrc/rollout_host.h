@@ -1,7 +1,10 @@
 // rollout_host.h - what the host units of the rollouts share (host only; include/hjbdp.h is the public ABI): the object,
-// its refusals, the upload, the chunk loop and the campaigns' entry frame and device loop.  Defined in rollout.hip (the campaigns'
-// checks, frame and loop: rollout_campaign_host.hip); rollout_channels.hip and the four rollout_*campaign*_host.hip are the other
-// readers.
+// its refusals, the upload, the chunk loop with the run functions' entry frame (run_call), and the campaigns' entry frame and
+// device loop.  Defined in rollout.hip (the campaigns' checks, frame and loop: rollout_campaign_host.hip); rollout_channels.hip
+// and the four rollout_*campaign*_host.hip are the other readers.
+// The frame of the nine run functions, stated once (run_call): every refusal before any device work and in one order, the
+// outputs untouched - what needs no object, the null handle, the object's lock, the controller's checks, the empty call, the
+// trajectories, what is refused per trajectory - then the chunk loop.  An entry point is its hooks, its plan and its launch.
 #pragma once
 #include "hjbdp_host.h"
 // the records an object holds: DRollout, DAttitude, DNoise, DPaChan (a unit includes the other kernel headers whose launch it calls)
@@ -99,21 +102,45 @@ int check_lookahead_run(Rollout *ro, const char *who, int fly_noise, int32_t n_s
 // weights), in `who`'s name: a weight that is not finite or is negative, weights that sum to 0.
 int check_weights(Rollout *ro, const char *who, int32_t n_nodes, const double *weights);
 
-// The problem hjb_rollout_lookahead_host and hjb_rollout_lookahead_campaign_host fly, from their common arguments: the refusals in
-// `who`'s name (look_host_args: everything up to the lookahead set; look_host_model: the grid, the tables, the model and the planes
-// of the steps) and the records the twin's loop reads.  L.tab points into tab.
-struct LookHostProblem {
-    hjb::GreedyModel M{};
-    hjb::LookSet L{};
-    std::vector<double> rdx, tab;
+// The affine problem of the host twins (hjb_rollout_greedy_host, hjb_rollout_lookahead_host, hjb_rollout_lookahead_campaign_host)
+// as their common arguments give it, and the records the twins' loops read of it.  The refusals are in `who`'s name and in two
+// parts: *_host_args, everything up to the sizes (n_traj: the trajectories or the starts), and *_host_model, the grid, the
+// tables, the model and the planes of the steps, which also fills the records.  look_host_* put the lookahead node set on top of
+// the affine part: its refusals end look_host_args, its table (L.tab points into tab) ends look_host_model.
+struct AffineHostArgs {
+    int32_t D;
+    const int32_t *n;
+    const double *knots;
+    int32_t n_labels, n_u;
+    const double *u_table, *A, *B, *c, *q, *r;
+    int32_t dtype, n_value_planes;
+    const void *values;
+    int32_t n_steps;
+    const int32_t *value_plane_of_step;
 };
-int look_host_args(const char *who, int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
-                   const double *A, const double *B, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
-                   int64_t n_traj, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights);
-int look_host_model(const char *who, int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u, const double *u_table,
-                    const double *A, const double *B, const double *c, const double *q, const double *r, int32_t n_value_planes,
-                    int32_t n_steps, const int32_t *value_plane_of_step, int32_t mode, int32_t n_nodes, const double *offsets,
-                    const double *weights, LookHostProblem &P);
+struct AffineHostProblem {
+    hjb::GreedyModel M{};
+    std::vector<double> rdx;
+};
+struct LookHostProblem : AffineHostProblem {
+    hjb::LookSet L{};
+    std::vector<double> tab;
+};
+int affine_host_args(const char *who, const AffineHostArgs &a, int64_t n_traj);
+int affine_host_model(const char *who, const AffineHostArgs &a, AffineHostProblem &P);
+int look_host_args(const char *who, const AffineHostArgs &a, int64_t n_traj, int32_t mode, int32_t n_nodes, const double *offsets,
+                   const double *weights);
+int look_host_model(const char *who, const AffineHostArgs &a, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights,
+                    LookHostProblem &P);
+
+// What hjb_rollout_run_noisy, hjb_rollout_run_lookahead (fly_noise) and hjb_rollout_noise_draw refuse of their streams, in `who`'s
+// name: first_stream < 0, first_stream + n_traj overflowing
+int check_streams(Rollout *ro, const char *who, int64_t n_traj, int64_t first_stream);
+
+// The noisy LDS rule (hjb_rollout_run_noisy, hjb_rollout_run_lookahead with fly_noise, the campaigns): the object's tables
+// [knots | 1/dx | u_table] and the node block of its noise set together, staged (*on) when option "lds" is on and they fit kLdsMax.
+// -> the bytes
+size_t noisy_lds(const Rollout *ro, bool *on);
 
 // What the campaigns (hjb_rollout_run_campaign, hjb_rollout_run_lookahead_campaign, their host forms) refuse of their sizes, in
 // `who`'s name: n_samples < 1, n_starts * n_samples overflowing; and of their bounds: a NaN threshold, a NaN or negative tol
@@ -126,7 +153,7 @@ int check_campaign_streams(Rollout *ro, const char *who, int64_t n_starts, int64
 // The launches of a campaign call, as run_campaign_launches hands them to the call's launch function - built once per call, only
 // C[r].block0 and C[r].n_blocks move from launch to launch: the object's record with each plane list on the device (R[1] is the
 // pair's second), the noise set with the call's seed and first stream, one DCampaign per record - one geometry, each its own
-// partials - the LDS bytes of the channel's tables and the node block together (hjb_rollout_run_noisy's rule), X0 [D, n_starts]
+// partials - the LDS bytes and the placement of noisy_lds, X0 [D, n_starts]
 // and every record's stats [8, n_starts] on the device.  In a histogram call (K30) lds is the launch's dynamic LDS bytes and
 // lds_on the tables' placement as campaign_hist_form decided them, and H the histogram's record; H.hist is null otherwise.  In a
 // pair call (K31) pair_cost [lanes] doubles and pair_left [lanes] bytes are the pair scratch, lanes = nb_max * G of a launch and
@@ -208,22 +235,26 @@ DAttitude euler_attitude(double J1, double J2, double J3, double h);
 // `bytes` at src on the device (the current one), owned by dd: at least 16 bytes are allocated, nothing is copied for none
 int upload(Rollout *ro, DevData &dd, const void *src, size_t bytes, const void **out);
 
-// The chunk loop the run functions share.  A run function fills a ChunkPlan; run_chunks calls its launch once per chunk of at
-// most Rollout::chunk trajectories with that chunk's device buffers.
+// The chunk loop the run functions share.  A run function fills a ChunkPlan - the RunCall, what its frame reads, and the outputs
+// on top; run_chunks calls its launch once per chunk of at most Rollout::chunk trajectories with that chunk's device buffers.
 constexpr int kMaxPaths = 5, kMaxInputs = 3;
 
-struct ChunkPlan {
+struct RunCall {
     const char *who;                // the entry point, for the error text
     int W;                          // doubles of state per trajectory
+    const char *wname;              // how a message spells W
     int32_t n_steps;
     const int32_t *plane_of_step;   // null for a loop without a policy (hjb_attitude_linear_response): nothing is uploaded then
     int64_t n_traj;
     const double *X0;
     double *X_final;
+    double *device_ms;              // optional: the sum of the launches' event times
+};
+
+struct ChunkPlan : RunCall {
     // per-step outputs, [n_traj, rows * stages] on the host; a null host pointer is an output not asked for
     struct Path { double *host; int rows, stages; } path[kMaxPaths] = {};
     double *cost = nullptr;         // [n_traj], optional
-    double *device_ms = nullptr;    // optional: the sum of the launches' event times
     int32_t *flags = nullptr;       // [n_traj], optional (the position loop's off_schedule, the fault campaigns' settle_stage)
     const int32_t *input[kMaxInputs] = {};      // per-trajectory inputs, [n_traj] each; a null entry is skipped
 };
@@ -244,5 +275,13 @@ struct Chunk {
 // Per chunk: X0 and the inputs uploaded (at the chunk's offset), launch(chunk) between two events, X_final / cost / flags and the
 // paths downloaded (columns i0 .. i0 + nc of the host's [n_traj, rows * stages]).  Holds g_capture_mu shared for the whole call.
 int run_chunks(Rollout *ro, const ChunkPlan &plan, const std::function<hipError_t(const Chunk &)> &launch);
+
+// The frame of the nine run functions of an object: `no_object` (what the call refuses before it needs an object; may be empty),
+// the null handle, the object's lock, `controller` (everything under the lock up to the empty call: check_run or
+// check_lookahead_run, the noise set, the stages a model's table covers, the fault planes, the tolerances), n_traj == 0 (HJB_OK,
+// *device_ms = 0), check_traj, `starts` (what is refused per trajectory; may be empty), *device_ms = 0, run_chunks with `launch`.
+// A plan is made before the lock: of the object it may read what hjb_rollout_create fixed (D, n_u), and of a null handle nothing.
+int run_call(void *rollout, const ChunkPlan &plan, const std::function<int(Rollout *)> &no_object, const std::function<int(Rollout *)> &controller,
+             const std::function<int(Rollout *)> &starts, const std::function<hipError_t(const Chunk &)> &launch);
 
 }  // namespace hjbhost

@@ -40,18 +40,15 @@ int32_t hjb_rollout_lookahead_campaign_host(int32_t D, const int32_t *n, const d
                                             uint64_t seed, int64_t first_stream, const double *threshold, const double *tol, double *stats) {
     const char *const who = "hjb_rollout_lookahead_campaign_host";
     if (const int bad = check_campaign_streams(nullptr, who, n_starts, n_samples, first_stream)) return bad;
-    if (const int bad = look_host_args(who, D, n, knots, n_labels, n_u, u_table, A, B, dtype, n_value_planes, values, n_steps, n_starts, mode,
-                                       n_nodes, offsets, weights))
-        return bad;
+    const AffineHostArgs a{D, n, knots, n_labels, n_u, u_table, A, B, c, q, r, dtype, n_value_planes, values, n_steps, value_plane_of_step};
+    if (const int bad = look_host_args(who, a, n_starts, mode, n_nodes, offsets, weights)) return bad;
     if (n_flight_nodes < 1 || n_flight_nodes > HJB_DIST_MAX_NODES)
         return rfail(nullptr, HJB_E_INVALID, "%s: n_flight_nodes=%d not in 1..%d", who, n_flight_nodes, HJB_DIST_MAX_NODES);
     if (!flight_offsets) return rfail(nullptr, HJB_E_INVALID, "%s: null flight_offsets", who);
     if (!all_finite(flight_offsets, (int64_t)D * n_flight_nodes)) return rfail(nullptr, HJB_E_INVALID, "%s: flight_offsets is not finite", who);
     if (const int bad = check_weights(nullptr, who, n_flight_nodes, flight_weights)) return bad;
     LookHostProblem P;
-    if (const int bad = look_host_model(who, D, n, knots, n_labels, n_u, u_table, A, B, c, q, r, n_value_planes, n_steps, value_plane_of_step,
-                                        mode, n_nodes, offsets, weights, P))
-        return bad;
+    if (const int bad = look_host_model(who, a, mode, n_nodes, offsets, weights, P)) return bad;
     if (n_starts == 0) return HJB_OK;
     if (!stats) return rfail(nullptr, HJB_E_INVALID, "%s: null stats", who);
     if (const int bad = check_traj(nullptr, who, D, "D", n_steps, n_starts, X0, stats)) return bad;

@@ -166,6 +166,9 @@ def _value_planes(J, nS):
 _LOOKUP = {"nearest": _abi.HJB_LOOKUP_NEAREST, "linear": _abi.HJB_LOOKUP_LINEAR}
 _DIST_MODE = {"expect": _abi.HJB_DIST_EXPECT, "worst": _abi.HJB_DIST_WORST}
 _ATT_INTEGRATOR = {"taylor": _abi.HJB_ATT_TAYLOR, "RK4": _abi.HJB_ATT_RK4, "rk4": _abi.HJB_ATT_RK4}
+# the per-step outputs of the 7-state and the 13-state loops: (name, rows, stages - n_steps), as Rollout._run reads them
+_ATT_PATHS = (("X_path", 7, 1), ("U_path", 3, 0), ("A_path", 3, 0))
+_PA_PATHS = (("X_path", 13, 1), ("F_path", 12, 0), ("FM_path", 6, 0))
 
 
 class Rollout:
@@ -275,18 +278,8 @@ class Rollout:
                                                    _f64p(_f64_vec(c, D)), _f64p(_f64_vec(q, D)), _f64p(_f64_vec(r, nu))))
 
     def run(self, X0, plane_of_step, method="linear", keep_path=False):
-        D, nu = self.D, self.n_u
-        X = _starts(X0, D)
-        nt = X.shape[0]
-        ps = _int32_vector(plane_of_step, "plane_of_step")
-        K = int(ps.size)
-        Xf = np.empty((nt, D))
-        cost = np.empty(nt)
-        flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K))
-        ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run(self._ro, _LOOKUP[method], K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
-                                             *map(_f64p, flat), C.byref(ms)))
-        return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
+        return self._run(self.lib.hjb_rollout_run, (_LOOKUP[method],), X0, self.D, plane_of_step, "plane_of_step", keep_path,
+                         (("X_path", self.D, 1), ("U_path", self.n_u, 0)))
 
     def set_noise(self, offsets, weights=None):
         """A node set for run_noisy (hjb_rollout_set_noise): offsets [D, W] (row a: the additive offsets of state axis a), weights
@@ -306,20 +299,9 @@ class Rollout:
         offsets[:, w] added on the axes that have an offset.  Trajectory i of the call reads the Philox4x32-10 stream
         first_stream + i under `seed` (both unsigned 64-bit; chunking does not change a bit).  Returns run's dict plus W_path
         [n_traj, n_steps] int32, the drawn nodes (None unless keep_path)."""
-        D, nu = self.D, self.n_u
-        X = _starts(X0, D)
-        nt = X.shape[0]
-        ps = _int32_vector(plane_of_step, "plane_of_step")
-        K = int(ps.size)
-        Xf = np.empty((nt, D))
-        cost = np.empty(nt)
-        flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K), ("W_path", 1, K))
-        ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run_noisy(self._ro, _LOOKUP[method], K, _i32p(ps), nt, _f64p(X), int(seed) & (2 ** 64 - 1),
-                                                   int(first_stream), _f64p(Xf), _f64p(cost), *map(_f64p, flat), C.byref(ms)))
-        if paths["W_path"] is not None:
-            paths["W_path"] = paths["W_path"][:, 0, :].astype(np.int32)
-        return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
+        return self._run(self.lib.hjb_rollout_run_noisy, (_LOOKUP[method],), X0, self.D, plane_of_step, "plane_of_step", keep_path,
+                         (("X_path", self.D, 1), ("U_path", self.n_u, 0), ("W_path", 1, 0)),
+                         mid=(int(seed) & (2 ** 64 - 1), int(first_stream)))
 
     def run_campaign(self, X0, plane_of_step, n_samples, seed=0, first_stream=0, method="linear", cost_threshold=None,
                      settle_tol=None, hist=None):
@@ -336,6 +318,32 @@ class Rollout:
         fn = self.lib.hjb_rollout_run_campaign if hist is None else self.lib.hjb_rollout_run_campaign_hist
         return self._campaign(fn, (_LOOKUP[method], int(ps.size), _i32p(ps)), X0, n_samples, seed, first_stream, cost_threshold,
                               settle_tol, hist=hist)
+
+    def _run(self, fn, lead, X0, width, planes, plane_name, keep_path, paths, inputs=(), mid=(), cost="cost", flag=None, flag_last=False,
+             null=(), ms=True):
+        """The one path of the run calls: fn(handle, *lead, n_steps, planes, n_traj, X0, *inputs, *mid, X_final, [cost,] [flag,]
+        *paths, [flag,] [device_ms]) and the dict of its outputs.  lead: what the entry point has in front of n_steps - its method
+        or fly_noise; inputs: (values, name) int32 per trajectory; mid: the scalars in front of X_final; paths: (name, rows,
+        stages - n_steps) each, the ones in `null` never asked for; cost, flag: the keys of the [n_traj] double and int32
+        outputs (None: the entry point has none), the flag behind the paths with flag_last."""
+        X = _starts(X0, width)
+        nt = X.shape[0]
+        ps = _int32_vector(planes, plane_name)
+        K = int(ps.size)
+        ins = [_int32_vector(v, name, nt) for v, name in inputs]
+        Xf = np.empty((nt, width))
+        vecs = {key: a for key, a in ((cost, np.empty(nt)), (flag, np.full(nt, -1, np.int32))) if key is not None}
+        flat, views = _path_buffers(nt, keep_path, *((name, rows, K + more) for name, rows, more in paths))
+        for name in null:
+            flat[[p[0] for p in paths].index(name)], views[name] = None, None
+        f = [_i32p(vecs[flag])] if flag else []
+        ms = [C.c_double(0.0)] if ms else []
+        self._check(fn(self._ro, *lead, K, _i32p(ps), nt, _f64p(X), *map(_i32p, ins), *mid, _f64p(Xf), *([_f64p(vecs[cost])] if cost else []),
+                       *([] if flag_last else f), *map(_f64p, flat), *(f if flag_last else []), *map(C.byref, ms)))
+        for name, dtype in (("L_path", np.int32), ("V_path", None), ("W_path", np.int32)):     # the one-row paths: [n_traj, n_steps]
+            if views.get(name) is not None:
+                views[name] = views[name][:, 0, :] if dtype is None else views[name][:, 0, :].astype(dtype)
+        return {"X_final": Xf.T, **vecs, **views, **{"device_ms": m.value for m in ms}}
 
     def _campaign(self, fn, lead, X0, n_samples, seed, first_stream, cost_threshold, settle_tol, hist=None, pair=False):
         """The one path of the campaign calls: fn(handle, *lead, n_starts, n_samples, X0, seed, first_stream, threshold, tol,
@@ -377,21 +385,8 @@ class Rollout:
         next state (-1: the zero function), first minimum.  The labels of the object are not read.  Returns run's dict plus
         L_path [n_traj, n_steps] int32, the chosen labels (index_base added), and V_path [n_traj, n_steps], the minima - the
         cost-to-go the controller believed (both None unless keep_path)."""
-        D, nu = self.D, self.n_u
-        X = _starts(X0, D)
-        nt = X.shape[0]
-        ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
-        K = int(ps.size)
-        Xf = np.empty((nt, D))
-        cost = np.empty(nt)
-        flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K), ("L_path", 1, K), ("V_path", 1, K))
-        ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run_greedy(self._ro, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost), *map(_f64p, flat),
-                                                    C.byref(ms)))
-        if keep_path:
-            paths["L_path"] = paths["L_path"][:, 0, :].astype(np.int32)
-            paths["V_path"] = paths["V_path"][:, 0, :]
-        return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
+        return self._run(self.lib.hjb_rollout_run_greedy, (), X0, self.D, value_plane_of_step, "value_plane_of_step", keep_path,
+                         (("X_path", self.D, 1), ("U_path", self.n_u, 0), ("L_path", 1, 0), ("V_path", 1, 0)))
 
     def set_lookahead(self, offsets, weights=None, mode="expect"):
         """A lookahead node set for run_lookahead (hjb_rollout_set_lookahead): what Backup.set_disturbance takes - offsets [D, W],
@@ -412,26 +407,9 @@ class Rollout:
         are not read); noisy=True flies run_noisy's plant under set_noise's nodes, trajectory i on the stream first_stream + i
         of `seed`.  Returns run_greedy's dict plus W_path [n_traj, n_steps] int32, the drawn nodes (None unless noisy and
         keep_path)."""
-        D, nu = self.D, self.n_u
-        X = _starts(X0, D)
-        nt = X.shape[0]
-        ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
-        K = int(ps.size)
-        Xf = np.empty((nt, D))
-        cost = np.empty(nt)
-        flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K), ("L_path", 1, K), ("V_path", 1, K),
-                                    ("W_path", 1, K))
-        if not noisy:
-            flat[4], paths["W_path"] = None, None
-        ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run_lookahead(self._ro, 1 if noisy else 0, K, _i32p(ps), nt, _f64p(X), int(seed) & (2 ** 64 - 1),
-                                                       int(first_stream), _f64p(Xf), _f64p(cost), *map(_f64p, flat), C.byref(ms)))
-        if keep_path:
-            paths["L_path"] = paths["L_path"][:, 0, :].astype(np.int32)
-            paths["V_path"] = paths["V_path"][:, 0, :]
-            if noisy:
-                paths["W_path"] = paths["W_path"][:, 0, :].astype(np.int32)
-        return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
+        return self._run(self.lib.hjb_rollout_run_lookahead, (1 if noisy else 0,), X0, self.D, value_plane_of_step, "value_plane_of_step",
+                         keep_path, (("X_path", self.D, 1), ("U_path", self.n_u, 0), ("L_path", 1, 0), ("V_path", 1, 0), ("W_path", 1, 0)),
+                         mid=(int(seed) & (2 ** 64 - 1), int(first_stream)), null=() if noisy else ("W_path",))
 
     def run_lookahead_campaign(self, X0, value_plane_of_step, n_samples, seed=0, first_stream=0, cost_threshold=None, settle_tol=None):
         """run_campaign for run_lookahead's controller (hjb_rollout_run_lookahead_campaign): every start of X0 [D, n_starts] flown
@@ -480,17 +458,8 @@ class Rollout:
         """hjb_rollout_run_attitude: X0 [7, n_traj] (X = [w1 w2 w3 q1 q2 q3 q4], q4 scalar).  Returns X_final [7, n_traj],
         cost [n_traj], X_path [n_traj, 7, n_steps+1], U_path [n_traj, 3, n_steps], A_path [n_traj, 3, n_steps] (the yaw, pitch,
         roll in radians each step looked up at; the paths None unless keep_path) and device_ms."""
-        X = _starts(X0, 7)
-        nt = X.shape[0]
-        ps = _int32_vector(plane_of_step, "plane_of_step")
-        K = int(ps.size)
-        Xf = np.empty((nt, 7))
-        cost = np.empty(nt)
-        flat, paths = _path_buffers(nt, keep_path, ("X_path", 7, K + 1), ("U_path", 3, K), ("A_path", 3, K))
-        ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run_attitude(self._ro, _LOOKUP[method], K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
-                                                      *map(_f64p, flat), C.byref(ms)))
-        return {"X_final": Xf.T, "cost": cost, **paths, "device_ms": ms.value}
+        return self._run(self.lib.hjb_rollout_run_attitude, (_LOOKUP[method],), X0, 7, plane_of_step, "plane_of_step", keep_path,
+                         _ATT_PATHS)
 
     def set_pos_att_model(self, rollout_y, rollout_z, inertia, mass, t_dist, h, rsw2eci, orbit_coef, substeps=1):
         """The 13-state pos-att loop (hjb_rollout_set_pos_att_model; the last model set wins) with this object as channel x and
@@ -507,14 +476,9 @@ class Rollout:
         """hjb_rollout_run_pos_att: X0 [13, n_traj] (X = [x(3) v(3) q(4) w(3)], q4 scalar).  plane_of_step None: every stage the
         orbit table covers, on plane 0 (stationary policies).  Returns X_final [13, n_traj] and X_path [n_traj, 13, n_steps+1], F_path [n_traj, 12, n_steps]
         (f0..f11), FM_path [n_traj, 6, n_steps] (a_x a_y a_z U_M); the paths None unless keep_path."""
-        X = _starts(X0, 13)
-        nt = X.shape[0]
-        ps = _int32_vector(np.zeros(self._pa_steps, np.int32) if plane_of_step is None else plane_of_step, "plane_of_step")
-        K = int(ps.size)
-        Xf = np.empty((nt, 13))
-        flat, paths = _path_buffers(nt, keep_path, ("X_path", 13, K + 1), ("F_path", 12, K), ("FM_path", 6, K))
-        self._check(self.lib.hjb_rollout_run_pos_att(self._ro, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), *map(_f64p, flat)))
-        return {"X_final": Xf.T, **paths}
+        planes = np.zeros(self._pa_steps, np.int32) if plane_of_step is None else plane_of_step
+        return self._run(self.lib.hjb_rollout_run_pos_att, (), X0, 13, planes, "plane_of_step", keep_path, _PA_PATHS, cost=None,
+                         ms=False)
 
     def set_pos_att_fault_controller(self, other):
         """hjb_rollout_set_pos_att_fault_controller: attach `other` (a Rollout with D = 4, n_u = 4 = [f0 f1 f6 f7], this object's
@@ -532,21 +496,10 @@ class Rollout:
         |applied force|; settle_stage [n_traj] (int32): the first state index from which the path stays within pos_tol of the
         origin and |q(1:3)| within att_tol to the end, n_steps + 1 if the last state is outside; X_path, F_path (the APPLIED
         forces), FM_path as run_pos_att's, None unless keep_path; device_ms."""
-        X = _starts(X0, 13)
-        nt = X.shape[0]
-        ps = _int32_vector(np.zeros(self._pa_steps, np.int32) if plane_of_step is None else plane_of_step, "plane_of_step")
-        K = int(ps.size)
-        fm, fs, sw = (_int32_vector(v, name, nt) for v, name in ((fault_mask, "fault_mask"), (fault_stage, "fault_stage"),
-                                                                 (switch_stage, "switch_stage")))
-        Xf = np.empty((nt, 13))
-        imp = np.empty(nt)
-        settle = np.empty(nt, np.int32)
-        flat, paths = _path_buffers(nt, keep_path, ("X_path", 13, K + 1), ("F_path", 12, K), ("FM_path", 6, K))
-        ms = C.c_double(0.0)
-        self._check(self.lib.hjb_rollout_run_pos_att_faults(self._ro, K, _i32p(ps), nt, _f64p(X), _i32p(fm), _i32p(fs), _i32p(sw),
-                                                            float(pos_tol), float(att_tol), _f64p(Xf), _f64p(imp), _i32p(settle),
-                                                            *map(_f64p, flat), C.byref(ms)))
-        return {"X_final": Xf.T, "impulse": imp, "settle_stage": settle, **paths, "device_ms": ms.value}
+        planes = np.zeros(self._pa_steps, np.int32) if plane_of_step is None else plane_of_step
+        return self._run(self.lib.hjb_rollout_run_pos_att_faults, (), X0, 13, planes, "plane_of_step", keep_path, _PA_PATHS,
+                         inputs=((fault_mask, "fault_mask"), (fault_stage, "fault_stage"), (switch_stage, "switch_stage")),
+                         mid=(float(pos_tol), float(att_tol)), cost="impulse", flag="settle_stage")
 
     def set_position_model(self, rollout_y, rollout_z, n_sub, table, tol=1e-8):
         """Solver_position's RKF45 loop (hjb_rollout_set_position_model; the last model set wins) with this object as channel x and
@@ -565,15 +518,9 @@ class Rollout:
         """hjb_rollout_run_position: X0 [6, n_traj] (y = [x(3) v(3)]).  plane_of_step None: every stage the table covers, on plane 0
         (stationary policies).  Returns X_final [6, n_traj], off_schedule [n_traj] (int32: the first stage that left rkf45's
         schedule, -1 if none) and X_path [n_traj, 6, n_steps+1], A_path [n_traj, 3, n_steps]; the paths None unless keep_path."""
-        X = _starts(X0, 6)
-        nt = X.shape[0]
-        ps = _int32_vector(np.zeros(self._pos_steps, np.int32) if plane_of_step is None else plane_of_step, "plane_of_step")
-        K = int(ps.size)
-        Xf = np.empty((nt, 6))
-        off = np.full(nt, -1, np.int32)
-        flat, paths = _path_buffers(nt, keep_path, ("X_path", 6, K + 1), ("A_path", 3, K))
-        self._check(self.lib.hjb_rollout_run_position(self._ro, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), *map(_f64p, flat), _i32p(off)))
-        return {"X_final": Xf.T, "off_schedule": off, **paths}
+        planes = np.zeros(self._pos_steps, np.int32) if plane_of_step is None else plane_of_step
+        return self._run(self.lib.hjb_rollout_run_position, (), X0, 6, planes, "plane_of_step", keep_path,
+                         (("X_path", 6, 1), ("A_path", 3, 0)), cost=None, ms=False, flag="off_schedule", flag_last=True)
 
     def set_attitude_simplified_model(self, rollout_2, rollout_3, inertia, h, substeps=1, dynamics="full", qw=None, qt=None, r=None):
         """The simplified attitude loop (hjb_rollout_set_attitude_simplified_model; the last model set wins) with this object as
@@ -592,16 +539,8 @@ class Rollout:
         """hjb_rollout_run_attitude_simplified: X0 [7, n_traj] (X = [w1 w2 w3 q1 q2 q3 q4], q4 scalar).  Returns X_final [7, n_traj],
         cost [n_traj], X_path [n_traj, 7, n_steps+1], U_path [n_traj, 3, n_steps], A_path [n_traj, 3, n_steps] (the three
         theta_i = 2 asin(q_i) in radians each stage looked up at); the paths None unless keep_path."""
-        X = _starts(X0, 7)
-        nt = X.shape[0]
-        ps = _int32_vector(plane_of_step, "plane_of_step")
-        K = int(ps.size)
-        Xf = np.empty((nt, 7))
-        cost = np.empty(nt)
-        flat, paths = _path_buffers(nt, keep_path, ("X_path", 7, K + 1), ("U_path", 3, K), ("A_path", 3, K))
-        self._check(self.lib.hjb_rollout_run_attitude_simplified(self._ro, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
-                                                                 *map(_f64p, flat)))
-        return {"X_final": Xf.T, "cost": cost, **paths}
+        return self._run(self.lib.hjb_rollout_run_attitude_simplified, (), X0, 7, plane_of_step, "plane_of_step", keep_path, _ATT_PATHS,
+                         ms=False)
 
 
 def noise_thresholds(weights, n_nodes=None):
