@@ -107,6 +107,67 @@ def _i32p(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _ptr(x):
+    """A device pointer as the library takes it: of a torch tensor, a DeviceBuffer or an integer; None stays None (a null pointer)."""
+    if x is None:
+        return None
+    return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+
+
+def _stream(s):
+    """A HIP stream handle as the library takes it: 0 is the null pointer."""
+    return int(s) or None
+
+
+def _j_vector(J, dtype, size, what):
+    """J_next or a terminal cost as the library reads it: a flat Fortran-order vector of `dtype`, refused when it does not have
+    `size` elements (None: any size).  what: "J_next" or "terminal", which of the two refusals."""
+    v = np.ascontiguousarray(np.asarray(J, dtype=dtype).reshape(-1, order="F"))
+    if size is not None and v.size != size:
+        raise ValueError("terminal cost must have nS elements" if what == "terminal"
+                         else "J_next has %d elements, the handle's J layout has %d" % (v.size, size))
+    return v
+
+
+class _Handle:
+    """The lifetime and the errors of an object that owns one library handle (Rollout, Backup, MultiBackup, RankSlab).  A
+    subclass states three facts: the attribute that holds its handle, and the library's destroy and last-error functions."""
+    _handle = _destroy = _last_error = None
+
+    def _raise(self, st):
+        h = getattr(self, self._handle)
+        msg = getattr(self.lib, self._last_error)(h if h.value else None)
+        raise HjbError(st, (msg or b"").decode() or self.lib.hjb_status_string(st).decode())
+
+    def _check(self, st):
+        if st != _abi.HJB_OK:
+            self._raise(st)
+
+    def _created(self, st):
+        """The status of the create call: a failure leaves a null handle and raises the error the library keeps for no object."""
+        if st != _abi.HJB_OK:
+            setattr(self, self._handle, C.c_void_p())
+            self._raise(st)
+
+    def close(self):
+        h = getattr(self, self._handle, None)
+        if h and h.value:
+            getattr(self.lib, self._destroy)(h)
+            setattr(self, self._handle, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 # ---- the marshalling of the rollout entry points (pure numpy): each run* is the starts, the planes, the outputs, one library
 # call, the dict -------------------------------------------------------------------------------------------------------------
 def _f64_vec(v, m):
@@ -171,7 +232,7 @@ _ATT_PATHS = (("X_path", 7, 1), ("U_path", 3, 0), ("A_path", 3, 0))
 _PA_PATHS = (("X_path", 13, 1), ("F_path", 12, 0), ("FM_path", 6, 0))
 
 
-class Rollout:
+class Rollout(_Handle):
     """A stored per-stage policy resident on one GPU, for batched fixed-step closed-loop rollouts (hjb_rollout_*):
 
         with Rollout(knots, labels, u_table, index_base=1) as ro:
@@ -187,6 +248,8 @@ class Rollout:
 
     The loops that take one policy per channel (pos-att, position, simplified attitude) are a model set on the first of several
     Rollout objects: Rollout.open_channels opens and closes such a set."""
+
+    _handle, _destroy, _last_error = "_ro", "hjb_rollout_destroy", "hjb_rollout_last_error"
 
     def __init__(self, knots, labels, u_table, index_base=1, device=0):
         self.lib = load_library()
@@ -219,9 +282,7 @@ class Rollout:
                                          int(self.n_planes), lab.ctypes.data, int(self.n_labels), int(self.n_u), _f64p(ut),
                                          C.byref(self._ro))
         self._keep = None
-        if st != _abi.HJB_OK:
-            self._ro = C.c_void_p()
-            self._raise(st)
+        self._created(st)
         self.device = int(device)
 
     @classmethod
@@ -240,31 +301,6 @@ class Rollout:
         finally:
             for ro in ros:
                 ro.close()
-
-    def _raise(self, st):
-        msg = self.lib.hjb_rollout_last_error(self._ro if self._ro.value else None)
-        raise HjbError(st, (msg or b"").decode() or self.lib.hjb_status_string(st).decode())
-
-    def _check(self, st):
-        if st != _abi.HJB_OK:
-            self._raise(st)
-
-    def close(self):
-        if getattr(self, "_ro", None) and self._ro.value:
-            self.lib.hjb_rollout_destroy(self._ro)
-            self._ro = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def set_option(self, key, value):
         """hjb_rollout_set_option.  "chunk" (default 2^20): trajectories per launch, which bounds the device memory of a run.
@@ -1009,18 +1045,86 @@ def device_mem_info(device=0):
     return int(f.value), int(t.value)
 
 
-class Backup:
+def _fill_separable(obj, fn, vecs, dJ, stream):
+    """The body of Backup.fill_separable and RankSlab.fill_separable: the vectors in the spec's arithmetic type, their addresses,
+    one library call.  (dJ is required: None is refused as int() refuses it.)"""
+    vs = [np.ascontiguousarray(v, dtype=obj.spec.dtype) for v in vecs]
+    ptrs = (C.c_void_p * len(vs))(*[v.ctypes.data for v in vs])
+    obj._check(fn(getattr(obj, obj._handle), ptrs, int(_ptr(dJ)), _stream(stream)))
+
+
+def _probe_block(spec, probe, n_planes):
+    """probe = {"lo", "hi", "control", "want"} -> (the zeroed arrays the taps are written to, by name, and the hjb_probe that
+    points at them); n_planes: the trailing stage axis of a sweep, 0 for one stage."""
+    D = spec.D
+    pb = _abi.hjb_probe()
+    ext = []
+    for a in range(D):
+        pb.lo[a], pb.hi[a] = int(probe["lo"][a]), int(probe["hi"][a])
+        ext.append(pb.hi[a] - pb.lo[a])
+    for c in range(spec.C):
+        pb.control[c] = int(probe["control"][c])
+    want = probe.get("want", ("g", "x_next", "j_interp"))
+    tail = (n_planes,) if n_planes else ()
+    out = {}
+    for name, mid in (("g", ()), ("x_next", (D,)), ("j_interp", ())):
+        if name in want:
+            out[name] = np.zeros(tuple(ext) + mid + tail, dtype=spec.dtype, order="F")
+            setattr(pb, name, out[name].ctypes.data)
+    return out, pb
+
+
+def _sweep_args(spec, n_stages, terminal=None, keep_J=False, keep_idx=False, monitor_period=0, monitor_tol=0.0, progress=None,
+                progress_every_stage=False, probe=None, monitor_single=False):
+    """What a sweep call (hjb_solve, hjb_solve_multi, a member of hjb_solve_batch) is handed: -> (the filled hjb_solve_opts, out,
+    keep).  out: the arrays the library writes - J and idx [nS], J_stages and idx_stages [nS, n_stages] in Fortran order,
+    zeroed, or None, probe the taps' arrays or None.  keep: everything the struct points to - out, the terminal vector, the
+    ctypes callback, the probe block; the caller holds it until the library call has returned."""
+    nS, dt, it = spec.nS, spec.j_dtype, spec.idx_np_dtype
+    o = _abi.hjb_solve_opts()
+    o.n_stages, o.monitor_period, o.monitor_tol = int(n_stages), int(monitor_period), float(monitor_tol)
+    o.progress_every_stage, o.monitor_single = 1 if progress_every_stage else 0, 1 if monitor_single else 0
+    out = {}
+    keep = [out]
+    if terminal is not None:
+        t = _j_vector(terminal, dt, nS, "terminal")
+        keep.append(t)
+        o.terminal = t.ctypes.data
+    out["J"], out["idx"] = np.empty(nS, dtype=dt), np.empty(nS, dtype=it)
+    out["J_stages"] = np.zeros((nS, n_stages), dtype=dt, order="F") if keep_J else None
+    out["idx_stages"] = np.zeros((nS, n_stages), dtype=it, order="F") if keep_idx else None
+    o.J_final, o.idx_final = out["J"].ctypes.data, out["idx"].ctypes.data
+    o.J_stages = None if out["J_stages"] is None else out["J_stages"].ctypes.data
+    o.idx_stages = None if out["idx_stages"] is None else out["idx_stages"].ctypes.data
+    if progress is not None:
+        cb = _abi.hjb_progress_fn(lambda user, k_s, e, e2, sec: progress(k_s, e, e2, sec))
+        keep.append(cb)
+        o.progress = cb
+    out["probe"] = None
+    if probe is not None:
+        out["probe"], pb = _probe_block(spec, probe, n_stages)
+        keep.append(pb)
+        o.probe = C.pointer(pb)
+    return o, out, keep
+
+
+def _sweep_result(out, res):
+    """The dict of a sweep: the arrays of _sweep_args and the hjb_result the library filled."""
+    return {"J": out["J"], "idx": out["idx"], "J_stages": out["J_stages"], "idx_stages": out["idx_stages"],
+            "stages_done": res.stages_done, "stopped_early": bool(res.stopped_early), "sweep_ms": res.sweep_ms, "last_e": res.last_e,
+            "last_e2": res.last_e2, "probe": out["probe"]}
+
+
+class Backup(_Handle):
     """A problem resident on one GPU.  Mirrors the C handle one to one."""
+    _handle, _destroy, _last_error = "_h", "hjb_destroy", "hjb_last_error"
 
     def __init__(self, spec: ProblemSpec, device=0, slab=None, variant=None):
         self.lib = load_library()
         self.spec = spec
         self._cprob, self._keep = spec.to_c(slab)
         self._h = C.c_void_p()
-        st = self.lib.hjb_create(C.byref(self._cprob), int(device), C.byref(self._h))
-        if st != _abi.HJB_OK:
-            self._h = C.c_void_p()
-            _check(self.lib, None, st)
+        self._created(self.lib.hjb_create(C.byref(self._cprob), int(device), C.byref(self._h)))
         self.device = int(device)
         if variant is not None:
             self.set_option("variant", variant)
@@ -1031,29 +1135,11 @@ class Backup:
                 self.close()
                 raise
 
-    # -- lifetime ---------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.hjb_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     # -- queries ----------------------------------------------------------
     def info(self):
         """hjb_get_info's fields, plus the disturbance in effect: dist_nodes (0: none), dist_mode ("expect" / "worst" / None), dist_axes."""
         inf = _abi.hjb_info()
-        _check(self.lib, self._h, self.lib.hjb_get_info(self._h, C.byref(inf)))
+        self._check(self.lib.hjb_get_info(self._h, C.byref(inf)))
         out = {k: getattr(inf, k) for k, _ in inf._fields_}
         out["dist_nodes"] = self.get_option("dist_nodes")
         out["dist_mode"] = ("expect", "worst")[self.get_option("dist_mode")] if out["dist_nodes"] else None
@@ -1067,21 +1153,19 @@ class Backup:
         x_next + offsets[:, w].  offsets [D, W], row a for state axis a of THIS handle's spec."""
         off, w, mode = check_disturbance(self.spec.D, offsets, weights, mode)
         offc = np.asfortranarray(off)
-        st = self.lib.hjb_set_disturbance(self._h, _abi.HJB_DIST_WORST if mode == "worst" else _abi.HJB_DIST_EXPECT, off.shape[1],
-                                          offc.ctypes.data_as(C.POINTER(C.c_double)),
-                                          None if w is None else w.ctypes.data_as(C.POINTER(C.c_double)))
-        _check(self.lib, self._h, st)
+        self._check(self.lib.hjb_set_disturbance(self._h, _abi.HJB_DIST_WORST if mode == "worst" else _abi.HJB_DIST_EXPECT, off.shape[1],
+                                                 _f64p(offc), _f64p(w)))
 
     def clear_disturbance(self):
         """Back to the nominal backup: the launch the handle had, the same bits as before."""
-        _check(self.lib, self._h, self.lib.hjb_set_disturbance(self._h, _abi.HJB_DIST_EXPECT, 0, None, None))
+        self._check(self.lib.hjb_set_disturbance(self._h, _abi.HJB_DIST_EXPECT, 0, None, None))
 
     def set_option(self, key, value):
-        _check(self.lib, self._h, self.lib.hjb_set_option(self._h, key.encode(), int(value)))
+        self._check(self.lib.hjb_set_option(self._h, key.encode(), int(value)))
 
     def get_option(self, key):
         v = C.c_int64()
-        _check(self.lib, self._h, self.lib.hjb_get_option(self._h, key.encode(), C.byref(v)))
+        self._check(self.lib.hjb_get_option(self._h, key.encode(), C.byref(v)))
         return int(v.value)
 
     # -- one stage, host buffers -------------------------------------------
@@ -1089,34 +1173,22 @@ class Backup:
         """[J_k, idx] = min(g + F(x_next), [], ctrl): J_next/J_k in the (haloed)
         column-major J layout, idx int32 labels of the owned states."""
         inf = self.info()
-        dt = self.spec.j_dtype
-        Jn = np.ascontiguousarray(np.asarray(J_next, dtype=dt).reshape(-1, order="F"))
-        if Jn.size != inf["j_elems"]:
-            raise ValueError("J_next has %d elements, the handle's J layout has %d" % (Jn.size, inf["j_elems"]))
+        Jn = _j_vector(J_next, self.spec.j_dtype, inf["j_elems"], "J_next")
         Jo = np.empty_like(Jn)
         idx = np.empty(inf["n_states"], dtype=self.spec.idx_np_dtype)
-        st = self.lib.hjb_backup_stage(self._h, Jn.ctypes.data, Jo.ctypes.data, idx.ctypes.data)
-        _check(self.lib, self._h, st)
+        self._check(self.lib.hjb_backup_stage(self._h, Jn.ctypes.data, Jo.ctypes.data, idx.ctypes.data))
         return Jo, idx
 
     # -- one stage, device buffers (torch tensors or raw pointers) -----------
     def backup_stage_device(self, dJ_next, dJ_out, d_idx=None, stream=0):
-        def ptr(x):
-            if x is None:
-                return None
-            return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
-        st = self.lib.hjb_backup_stage_device(self._h, ptr(dJ_next), ptr(dJ_out), ptr(d_idx), int(stream) or None)
-        _check(self.lib, self._h, st)
+        self._check(self.lib.hjb_backup_stage_device(self._h, _ptr(dJ_next), _ptr(dJ_out), _ptr(d_idx), _stream(stream)))
 
     def fill_separable(self, vecs, dJ, stream=0):
         """dJ[s] = ((vecs[0][i0] + vecs[1][i1]) + ...) over the whole grid (hjb_device_fill_separable)."""
-        vs = [np.ascontiguousarray(v, dtype=self.spec.dtype) for v in vecs]
-        ptrs = (C.c_void_p * len(vs))(*[v.ctypes.data for v in vs])
-        dp = int(dJ.data_ptr()) if hasattr(dJ, "data_ptr") else int(dJ)
-        _check(self.lib, self._h, self.lib.hjb_device_fill_separable(self._h, ptrs, dp, int(stream) or None))
+        _fill_separable(self, self.lib.hjb_device_fill_separable, vecs, dJ, stream)
 
     def check_device_status(self, stream=0):
-        _check(self.lib, self._h, self.lib.hjb_check_device_status(self._h, int(stream) or None))
+        self._check(self.lib.hjb_check_device_status(self._h, _stream(stream)))
 
     # -- the whole sweep -----------------------------------------------------
     def solve(self, n_stages, terminal=None, keep_J=False, keep_idx=False, monitor_period=0, monitor_tol=0.0,
@@ -1127,45 +1199,12 @@ class Backup:
         probe = {"lo": [..D], "hi": [..D], "control": [..C], "want": ("g", "x_next", "j_interp")} (0-based,
         half-open) asks for the reference's debug taps (Dynamic_Solver.m:212-219) of every stage: out["probe"]
         holds g [block..., n_stages], x_next [block..., D, n_stages], j_interp [block..., n_stages]."""
-        nS, dt = self.spec.nS, self.spec.j_dtype
-        o = _abi.hjb_solve_opts()
-        o.n_stages = int(n_stages)
-        o.monitor_period = int(monitor_period)
-        o.monitor_tol = float(monitor_tol)
-        keep = []
-        if terminal is not None:
-            t = np.ascontiguousarray(np.asarray(terminal, dtype=dt).reshape(-1, order="F"))
-            if t.size != nS:
-                raise ValueError("terminal cost must have nS elements")
-            keep.append(t)
-            o.terminal = t.ctypes.data
-        J = np.empty(nS, dtype=dt)
-        idx = np.empty(nS, dtype=self.spec.idx_np_dtype)
-        o.J_final, o.idx_final = J.ctypes.data, idx.ctypes.data
-        Js = Is = None
-        if keep_J:
-            Js = np.zeros((nS, n_stages), dtype=dt, order="F")
-            o.J_stages = Js.ctypes.data
-        if keep_idx:
-            Is = np.zeros((nS, n_stages), dtype=self.spec.idx_np_dtype, order="F")
-            o.idx_stages = Is.ctypes.data
-        if progress is not None:
-            cb = _abi.hjb_progress_fn(lambda user, k_s, e, e2, sec: progress(k_s, e, e2, sec))
-            keep.append(cb)
-            o.progress = cb
-        o.progress_every_stage = 1 if progress_every_stage else 0
-        o.monitor_single = 1 if monitor_single else 0
-        pout = None
-        if probe is not None:
-            pout, pb = self._make_probe(probe, n_stages)
-            keep.append(pb)
-            o.probe = C.pointer(pb)
+        o, out, keep = _sweep_args(self.spec, n_stages, terminal=terminal, keep_J=keep_J, keep_idx=keep_idx, monitor_period=monitor_period,
+                                   monitor_tol=monitor_tol, progress=progress, progress_every_stage=progress_every_stage, probe=probe,
+                                   monitor_single=monitor_single)                # keep: alive until hjb_solve has returned
         res = _abi.hjb_result()
-        st = self.lib.hjb_solve(self._h, C.byref(o), C.byref(res))
-        _check(self.lib, self._h, st)
-        return {"J": J, "idx": idx, "J_stages": Js, "idx_stages": Is, "stages_done": res.stages_done,
-                "stopped_early": bool(res.stopped_early), "sweep_ms": res.sweep_ms, "last_e": res.last_e,
-                "last_e2": res.last_e2, "probe": pout}
+        self._check(self.lib.hjb_solve(self._h, C.byref(o), C.byref(res)))
+        return _sweep_result(out, res)
 
     # -- the cost of a GIVEN policy -------------------------------------------
     def _labels(self, labels, shapes):
@@ -1183,23 +1222,15 @@ class Backup:
         labels the result is backup_stage's J, bit for bit."""
         inf = self.info()
         lab = self._labels(labels, [(int(inf["n_states"]),)])
-        dt = self.spec.j_dtype
-        Jn = np.ascontiguousarray(np.asarray(J_next, dtype=dt).reshape(-1, order="F"))
-        if Jn.size != inf["j_elems"]:
-            raise ValueError("J_next has %d elements, the handle's J layout has %d" % (Jn.size, inf["j_elems"]))
+        Jn = _j_vector(J_next, self.spec.j_dtype, inf["j_elems"], "J_next")
         Jo = np.empty_like(Jn)
-        _check(self.lib, self._h, self.lib.hjb_evaluate_stage(self._h, Jn.ctypes.data, lab.ctypes.data, Jo.ctypes.data))
+        self._check(self.lib.hjb_evaluate_stage(self._h, Jn.ctypes.data, lab.ctypes.data, Jo.ctypes.data))
         return Jo
 
     def evaluate_stage_device(self, dJ_next, d_labels, dJ_out, stream=0):
         """hjb_evaluate_stage_device: the same on device buffers (torch tensors, DeviceBuffers or raw pointers), asynchronous.
         A label out of range stores NaN for its state and makes the next check_device_status raise (HJB_E_INVALID)."""
-        def ptr(x):
-            if x is None:
-                return None
-            return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
-        st = self.lib.hjb_evaluate_stage_device(self._h, ptr(dJ_next), ptr(d_labels), ptr(dJ_out), int(stream) or None)
-        _check(self.lib, self._h, st)
+        self._check(self.lib.hjb_evaluate_stage_device(self._h, _ptr(dJ_next), _ptr(d_labels), _ptr(dJ_out), _stream(stream)))
 
     def evaluate(self, n_stages, labels, terminal=None, keep_J=False):
         """The sweep of a fixed policy (hjb_evaluate): n_stages evaluations from `terminal` (None: zeros).  labels [nS]: one
@@ -1210,60 +1241,30 @@ class Backup:
         n_stages = int(n_stages)
         lab = self._labels(labels, [(nS,), (nS, n_stages)])
         per_stage = 1 if np.ndim(labels) == 2 else 0
-        t = None
-        if terminal is not None:
-            t = np.ascontiguousarray(np.asarray(terminal, dtype=dt).reshape(-1, order="F"))
-            if t.size != nS:
-                raise ValueError("terminal cost must have nS elements")
+        t = None if terminal is None else _j_vector(terminal, dt, nS, "terminal")
         J = np.empty(nS, dtype=dt)
         Js = np.zeros((nS, max(n_stages, 0)), dtype=dt, order="F") if keep_J else None
         ms = C.c_double(0.0)
-        st = self.lib.hjb_evaluate(self._h, n_stages, None if t is None else t.ctypes.data, lab.ctypes.data, per_stage,
-                                   J.ctypes.data, None if Js is None else Js.ctypes.data, C.byref(ms))
-        _check(self.lib, self._h, st)
+        self._check(self.lib.hjb_evaluate(self._h, n_stages, None if t is None else t.ctypes.data, lab.ctypes.data, per_stage,
+                                          J.ctypes.data, None if Js is None else Js.ctypes.data, C.byref(ms)))
         return {"J": J, "J_stages": Js, "sweep_ms": ms.value}
-
-    def _make_probe(self, probe, n_planes):
-        D, Cc = self.spec.D, self.spec.C
-        pb = _abi.hjb_probe()
-        ext = []
-        for a in range(D):
-            pb.lo[a], pb.hi[a] = int(probe["lo"][a]), int(probe["hi"][a])
-            ext.append(pb.hi[a] - pb.lo[a])
-        for c in range(Cc):
-            pb.control[c] = int(probe["control"][c])
-        want = probe.get("want", ("g", "x_next", "j_interp"))
-        dt = self.spec.dtype
-        tail = (n_planes,) if n_planes else ()
-        out = {}
-        if "g" in want:
-            out["g"] = np.zeros(tuple(ext) + tail, dtype=dt, order="F")
-            pb.g = out["g"].ctypes.data
-        if "x_next" in want:
-            out["x_next"] = np.zeros(tuple(ext) + (D,) + tail, dtype=dt, order="F")
-            pb.x_next = out["x_next"].ctypes.data
-        if "j_interp" in want:
-            out["j_interp"] = np.zeros(tuple(ext) + tail, dtype=dt, order="F")
-            pb.j_interp = out["j_interp"].ctypes.data
-        return out, pb
 
     def probe_stage(self, probe, J_next=None):
         """One stage of the debug taps from a host J_next (hjb_probe_stage)."""
-        out, pb = self._make_probe(probe, 0)
-        Jn = None
-        if J_next is not None:
-            Jn = np.ascontiguousarray(np.asarray(J_next, dtype=self.spec.j_dtype).reshape(-1, order="F"))
-        elif "j_interp" in out:
+        out, pb = _probe_block(self.spec, probe, 0)
+        if J_next is None and "j_interp" in out:
             raise ValueError("j_interp needs J_next")
-        st = self.lib.hjb_probe_stage(self._h, Jn.ctypes.data if Jn is not None else None, C.byref(pb))
-        _check(self.lib, self._h, st)
+        Jn = None if J_next is None else _j_vector(J_next, self.spec.j_dtype, None, "J_next")     # of any size: this call asks for none
+        self._check(self.lib.hjb_probe_stage(self._h, None if Jn is None else Jn.ctypes.data, C.byref(pb)))
         return out
 
 
-class MultiBackup:
+class MultiBackup(_Handle):
     """A problem partitioned along its last state axis over several devices of THIS process (hjb_create_multi /
     hjb_solve_multi): per stage the halo planes travel device to device while the interior planes are computed.
     `devices` may repeat a device (several slabs on one GPU: how the path is tested on a 1-GPU box)."""
+
+    _handle, _destroy, _last_error = "_m", "hjb_destroy_multi", "hjb_multi_last_error"
 
     def __init__(self, spec: ProblemSpec, devices):
         self.lib = load_library()
@@ -1271,34 +1272,8 @@ class MultiBackup:
         self._cprob, self._keep = spec.to_c()
         self._m = C.c_void_p()
         devs = (C.c_int32 * len(devices))(*[int(d) for d in devices])
-        st = self.lib.hjb_create_multi(C.byref(self._cprob), len(devices), devs, C.byref(self._m))
-        if st != _abi.HJB_OK:
-            self._m = C.c_void_p()
-            msg = self.lib.hjb_multi_last_error(None)
-            raise HjbError(st, (msg or b"").decode() or self.lib.hjb_status_string(st).decode())
+        self._created(self.lib.hjb_create_multi(C.byref(self._cprob), len(devices), devs, C.byref(self._m)))
         self.n_slabs = len(devices)
-
-    def _check(self, st):
-        if st != _abi.HJB_OK:
-            msg = self.lib.hjb_multi_last_error(self._m)
-            raise HjbError(st, (msg or b"").decode() or self.lib.hjb_status_string(st).decode())
-
-    def close(self):
-        if getattr(self, "_m", None) and self._m.value:
-            self.lib.hjb_destroy_multi(self._m)
-            self._m = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def slab_info(self, i):
         v = [C.c_int32() for _ in range(6)]
@@ -1310,52 +1285,29 @@ class MultiBackup:
 
     def solve(self, n_stages, terminal=None, keep_J=False, keep_idx=False, monitor_period=0, monitor_tol=0.0, progress=None,
               progress_every_stage=False):
-        nS, dt = self.spec.nS, self.spec.j_dtype
-        o = _abi.hjb_solve_opts()
-        o.n_stages, o.monitor_period, o.monitor_tol = int(n_stages), int(monitor_period), float(monitor_tol)
-        keep = []
-        if terminal is not None:
-            t = np.ascontiguousarray(np.asarray(terminal, dtype=dt).reshape(-1, order="F"))
-            if t.size != nS:
-                raise ValueError("terminal cost must have nS elements")
-            keep.append(t)
-            o.terminal = t.ctypes.data
-        J = np.empty(nS, dtype=dt)
-        idx = np.empty(nS, dtype=self.spec.idx_np_dtype)
-        o.J_final, o.idx_final = J.ctypes.data, idx.ctypes.data
-        Js = Is = None
-        if keep_J:
-            Js = np.zeros((nS, n_stages), dtype=dt, order="F")
-            o.J_stages = Js.ctypes.data
-        if keep_idx:
-            Is = np.zeros((nS, n_stages), dtype=self.spec.idx_np_dtype, order="F")
-            o.idx_stages = Is.ctypes.data
-        if progress is not None:
-            cb = _abi.hjb_progress_fn(lambda user, k_s, e, e2, sec: progress(k_s, e, e2, sec))
-            keep.append(cb)
-            o.progress = cb
-        o.progress_every_stage = 1 if progress_every_stage else 0
-        res = _abi.hjb_result()
+        o, out, keep = _sweep_args(self.spec, n_stages, terminal=terminal, keep_J=keep_J, keep_idx=keep_idx, monitor_period=monitor_period,
+                                   monitor_tol=monitor_tol, progress=progress, progress_every_stage=progress_every_stage)
+        res = _abi.hjb_result()                                                 # keep: alive until hjb_solve_multi has returned
         self._check(self.lib.hjb_solve_multi(self._m, C.byref(o), C.byref(res)))
-        return {"J": J, "idx": idx, "J_stages": Js, "idx_stages": Is, "stages_done": res.stages_done, "stopped_early": bool(res.stopped_early),
-                "sweep_ms": res.sweep_ms, "last_e": res.last_e, "last_e2": res.last_e2}
+        ret = _sweep_result(out, res)
+        del ret["probe"]                                                        # hjb_solve_multi takes no probe: its dict has no such key
+        return ret
 
 
-class RankSlab:
+class RankSlab(_Handle):
     """One rank's share of a sweep partitioned over `world` processes, one per GPU (hjb_rank_create / hjb_rank_stage):
     the library builds the slab handle and - with overlap and an interior - the interior and strip handles, and enqueues
     a whole stage (interior on the compute stream, strips behind the halos on streams of their own) in one call."""
+
+    _handle, _destroy, _last_error = "_r", "hjb_rank_destroy", "hjb_rank_last_error"
 
     def __init__(self, spec: ProblemSpec, device, rank, world, overlap=True):
         self.lib = load_library()
         self.spec = spec
         self._cprob, self._keep = spec.to_c()
         self._r = C.c_void_p()
-        st = self.lib.hjb_rank_create(C.byref(self._cprob), int(device), int(rank), int(world), 1 if overlap else 0, C.byref(self._r))
-        if st != _abi.HJB_OK:
-            self._r = C.c_void_p()
-            msg = self.lib.hjb_rank_last_error(None)
-            raise HjbError(st, (msg or b"").decode() or self.lib.hjb_status_string(st).decode())
+        self._created(self.lib.hjb_rank_create(C.byref(self._cprob), int(device), int(rank), int(world), 1 if overlap else 0,
+                                               C.byref(self._r)))
         self.refresh()
 
     def refresh(self):
@@ -1365,40 +1317,23 @@ class RankSlab:
         (self.begin, self.end, self.halo_lo, self.halo_hi, self.split, self.kernel_variant, self.need_lo, self.need_hi,
          self.idx_bytes, self.n_planes) = (int(x) for x in v)
 
-    def _check(self, st):
-        if st != _abi.HJB_OK:
-            msg = self.lib.hjb_rank_last_error(self._r)
-            raise HjbError(st, (msg or b"").decode() or self.lib.hjb_status_string(st).decode())
-
     def stage(self, dJ_in, dJ_out, d_idx, compute_stream=0, halo_stream=0):
-        def ptr(x):
-            if x is None:
-                return None
-            return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
-        self._check(self.lib.hjb_rank_stage(self._r, ptr(dJ_in), ptr(dJ_out), ptr(d_idx), int(compute_stream) or None,
-                                            int(halo_stream) or None))
+        self._check(self.lib.hjb_rank_stage(self._r, _ptr(dJ_in), _ptr(dJ_out), _ptr(d_idx), _stream(compute_stream), _stream(halo_stream)))
 
     def fill_separable(self, vecs, dJ, stream=0):
         """dJ (this rank's haloed buffer) = ((vecs[0][i0] + vecs[1][i1]) + ...) on the rank's planes, halos included; vecs are the
         GLOBAL vectors (hjb_rank_fill_separable)."""
-        vs = [np.ascontiguousarray(v, dtype=self.spec.dtype) for v in vecs]
-        ptrs = (C.c_void_p * len(vs))(*[v.ctypes.data for v in vs])
-        dp = int(dJ.data_ptr()) if hasattr(dJ, "data_ptr") else int(dJ)
-        self._check(self.lib.hjb_rank_fill_separable(self._r, ptrs, dp, int(stream) or None))
+        _fill_separable(self, self.lib.hjb_rank_fill_separable, vecs, dJ, stream)
 
     def stage_post(self, dJ_in, dJ_out, d_idx, compute_stream=0, halo_stream=0):
         """The stage with the boundary strips first (hjb_rank_stage_post): their halos are already in dJ_in."""
-        def ptr(x):
-            if x is None:
-                return None
-            return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
-        self._check(self.lib.hjb_rank_stage_post(self._r, ptr(dJ_in), ptr(dJ_out), ptr(d_idx), int(compute_stream) or None,
-                                                 int(halo_stream) or None))
+        self._check(self.lib.hjb_rank_stage_post(self._r, _ptr(dJ_in), _ptr(dJ_out), _ptr(d_idx), _stream(compute_stream),
+                                                 _stream(halo_stream)))
 
     def wait_strips(self, stream):
         """`stream` waits for the last stage's boundary strips; -> True when they cover every plane a neighbour needs."""
         cov = C.c_int32(0)
-        self._check(self.lib.hjb_rank_wait_strips(self._r, int(stream) or None, C.byref(cov)))
+        self._check(self.lib.hjb_rank_wait_strips(self._r, _stream(stream), C.byref(cov)))
         return bool(cov.value)
 
     def set_option(self, key, value):
@@ -1411,18 +1346,7 @@ class RankSlab:
         return int(v.value)
 
     def check_device_status(self, stream=0):
-        self._check(self.lib.hjb_rank_check_status(self._r, int(stream) or None))
-
-    def close(self):
-        if getattr(self, "_r", None) and self._r.value:
-            self.lib.hjb_rank_destroy(self._r)
-            self._r = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._check(self.lib.hjb_rank_check_status(self._r, _stream(stream)))
 
 
 def suggest_axis_order(spec):
@@ -1459,6 +1383,66 @@ def suggest_axis_order(spec):
         lib.hjb_problem_free(b)
 
 
+def _batch_groups(variants, group_axes, specs):
+    """Which problems of a solve_batch call share a launch: the ordered groups of member indices.  variants: every handle's kernel
+    variant; group_axes: its column sweep's group axis (read only where the variant is 7).  Column-sweep problems (variant 7)
+    share by (group axis, float64 cost or not), table-kernel problems (variant 5) of D <= 4 by (J type, D); every other problem
+    is alone."""
+    groups = {}
+    for i, (v, s) in enumerate(zip(variants, specs)):
+        if v == 7:
+            key = ("colsweep", group_axes[i], s.cost_dtype is not None)
+        elif v == 5 and s.D <= 4:
+            key = ("tabled", np.dtype(s.j_dtype).str, s.D)
+        else:
+            key = ("alone", i)
+        groups.setdefault(key, []).append(i)
+    # The table kernel is one state per thread: a batch pays off while ALL its states are resident at once (a launch-bound stage);
+    # beyond one round of the wave slots (256 CUs x 32 waves x 64 lanes) the launches run round after round and three chains on
+    # three streams overlap better than one launch (Solver_attitude.simplified_run's 3 x 3e5 states: 130 ms batched, 82 ms as
+    # chains - profiles/r06_batch_attitude.log).  Such a group is dissolved; its members go behind the groups that stay.
+    for key in [k for k in groups if k[0] == "tabled"]:
+        if len(groups[key]) > 1 and sum(specs[i].nS for i in groups[key]) > 256 * 32 * 64:
+            for i in groups.pop(key):
+                groups[("alone", i)] = [i]
+    return list(groups.values())
+
+
+def _batch_cs_split(specs, variants, own_splits, any_cost64):
+    """Parts per column for the column-sweep problems (variant 7) of a solve_batch call, 0 to leave every handle its own.  A handle
+    alone picks as many parts as fill the device (it is one wave's chain of round trips), and every part primes its rows again: up
+    to twice the work per column.  These problems are in flight TOGETHER, so the parts are what lets all their columns fill about
+    one round of the wave slots - the library does the same inside a batch for the columns it sees; here every chain of the call
+    is counted (profiles/r06_batch_split.log).  own_splits: the cs_split each of those problems chose, in their order (read only
+    as far as the answer needs); any_cost64: one of them has a float64 cost."""
+    cols = sum(-(-s.n[0] // 60) * s.n[2] * s.n[3] for s, v in zip(specs, variants) if v == 7)
+    slots = (5 if any_cost64 else 6) * 4 * 256          # waves per SIMD of the form that runs (86 / 80 registers) x SIMDs
+    split = max(1, slots // max(cols, 1))
+    return split if all(split < own for own in own_splits) else 0
+
+
+def _solve_group(lib, bks, members, n_stages, kw):
+    """One group of solve_batch on the calling thread -> (its members' dicts in order, the sizes of the launches they ran in):
+    several members as ONE hjb_solve_batch call; a member alone in its shape, or a group the library does not take
+    (HJB_E_UNSUPPORTED), as plain sweeps side by side."""
+    from concurrent.futures import ThreadPoolExecutor
+    if len(members) > 1:
+        m = len(members)
+        built = [_sweep_args(bks[i].spec, n_stages, **kw) for i in members]     # alive until hjb_solve_batch has returned
+        ress = [_abi.hjb_result() for _ in members]
+        hs = (C.c_void_p * m)(*[bks[i]._h for i in members])
+        optp = (C.POINTER(_abi.hjb_solve_opts) * m)(*[C.pointer(o) for o, _, _ in built])
+        resp = (C.POINTER(_abi.hjb_result) * m)(*[C.pointer(r) for r in ress])
+        st = lib.hjb_solve_batch(m, hs, optp, resp)
+        if st == _abi.HJB_OK:
+            return [_sweep_result(out, r) for (_, out, _), r in zip(built, ress)], [m]
+        if st != _abi.HJB_E_UNSUPPORTED:
+            _check(lib, None, st)
+        with ThreadPoolExecutor(max_workers=m) as ex:
+            return list(ex.map(lambda i: bks[i].solve(n_stages, **kw), members)), [1] * m
+    return [bks[members[0]].solve(n_stages, **kw)], [1]
+
+
 def solve_batch(specs, n_stages, device=0, monitor_period=0, monitor_tol=0.0, progress=None, monitor_single=False, cs_split=None,
                 options=None):
     """Independent sweeps side by side with as few launch chains as the library can make of them (the four channels of
@@ -1483,84 +1467,24 @@ def solve_batch(specs, n_stages, device=0, monitor_period=0, monitor_tol=0.0, pr
             for k, v in (o or {}).items():
                 bk.set_option(k, v)
         variants = [bk.info()["kernel_variant"] for bk in bks]
-        groups = {}
-        for i, bk in enumerate(bks):
-            if variants[i] == 7:
-                key = ("colsweep", bk.get_option("cs_group_axis"), bk.spec.cost_dtype is not None)
-            elif variants[i] == 5 and bk.spec.D <= 4:
-                key = ("tabled", np.dtype(bk.spec.j_dtype).str, bk.spec.D)
-            else:
-                key = ("alone", i)
-            groups.setdefault(key, []).append(i)
-        # The table kernel is one state per thread: a batch pays off while ALL its states are resident at once (a launch-bound stage);
-        # beyond one round of the wave slots (256 CUs x 32 waves x 64 lanes) the launches run round after round and three chains on
-        # three streams overlap better than one launch (Solver_attitude.simplified_run's 3 x 3e5 states: 130 ms batched, 82 ms as
-        # chains - profiles/r06_batch_attitude.log)
-        for key in [k for k in groups if k[0] == "tabled"]:
-            if len(groups[key]) > 1 and sum(specs[i].nS for i in groups[key]) > 256 * 32 * 64:
-                for i in groups.pop(key):
-                    groups[("alone", i)] = [i]
-        outs = [None] * n
-        if cs_split is None:
-            # Parts per column of the column-sweep problems.  A handle alone picks as many parts as fill the device (it is one wave's
-            # chain of round trips), and every part primes its rows again: up to twice the work per column.  These problems are in
-            # flight TOGETHER, so the parts are what lets all their columns fill about one round of the wave slots - the library does
-            # the same inside a batch for the columns it sees; here every chain of the call is counted (profiles/r06_batch_split.log)
-            cs = [i for i in range(n) if variants[i] == 7]
-            if len(cs) > 1:
-                cols = sum(-(-specs[i].n[0] // 60) * specs[i].n[2] * specs[i].n[3] for i in cs)
-                slots = (5 if any(specs[i].cost_dtype is not None for i in cs) else 6) * 4 * 256          # waves per SIMD of the form that runs (86 / 80 registers) x SIMDs
-                cs_split = max(1, slots // max(cols, 1))
-                cs_split = cs_split if all(cs_split < bks[i].get_option("cs_split") for i in cs) else 0
+        groups = _batch_groups(variants, [bk.get_option("cs_group_axis") if v == 7 else None for bk, v in zip(bks, variants)], specs)
+        cs = [i for i in range(n) if variants[i] == 7]
+        if cs_split is None and len(cs) > 1:
+            cs_split = _batch_cs_split(specs, variants, (bks[i].get_option("cs_split") for i in cs),
+                                       any(specs[i].cost_dtype is not None for i in cs))
 
         def run(members):
-            if cs_split:
-                for i in members:
-                    if variants[i] == 7:
-                        bks[i].set_option("cs_split", int(cs_split))
-            if len(members) > 1:
-                m = len(members)
-                keep, bufs, ress = [], [], []
-                hs = (C.c_void_p * m)(*[bks[i]._h for i in members])
-                optp = (C.POINTER(_abi.hjb_solve_opts) * m)()
-                resp = (C.POINTER(_abi.hjb_result) * m)()
-                for k, i in enumerate(members):
-                    s = specs[i]
-                    o = _abi.hjb_solve_opts()
-                    o.n_stages, o.monitor_period, o.monitor_tol = int(n_stages), int(monitor_period), float(monitor_tol)
-                    J = np.empty(s.nS, dtype=s.j_dtype)
-                    idx = np.empty(s.nS, dtype=s.idx_np_dtype)
-                    o.J_final, o.idx_final = J.ctypes.data, idx.ctypes.data
-                    o.monitor_single = 1 if monitor_single else 0
-                    if progress is not None:
-                        cb = _abi.hjb_progress_fn(lambda user, k_s, e, e2, sec: progress(k_s, e, e2, sec))
-                        keep.append(cb)
-                        o.progress = cb
-                    r = _abi.hjb_result()
-                    keep += [o, r]
-                    optp[k] = C.pointer(o)
-                    resp[k] = C.pointer(r)
-                    bufs.append((J, idx))
-                    ress.append(r)
-                st = lib.hjb_solve_batch(m, hs, optp, resp)
-                if st == _abi.HJB_OK:
-                    for i, (J, idx), r in zip(members, bufs, ress):
-                        outs[i] = {"J": J, "idx": idx, "J_stages": None, "idx_stages": None, "stages_done": r.stages_done,
-                                   "stopped_early": bool(r.stopped_early), "sweep_ms": r.sweep_ms, "last_e": r.last_e, "last_e2": r.last_e2,
-                                   "probe": None}
-                    return [m]
-                if st != _abi.HJB_E_UNSUPPORTED:
-                    _check(lib, None, st)
-            def one(i):                     # alone in its shape (or a group the library did not take): the plain sweep
-                outs[i] = bks[i].solve(n_stages, **kw)
-            if len(members) == 1:
-                one(members[0])
-            else:
-                with ThreadPoolExecutor(max_workers=len(members)) as ex2:
-                    list(ex2.map(one, members))
-            return [1] * len(members)
+            for i in members:
+                if cs_split and variants[i] == 7:
+                    bks[i].set_option("cs_split", int(cs_split))
+            return _solve_group(lib, bks, members, n_stages, kw)
+        outs = [None] * n
+        sizes = []
         with ThreadPoolExecutor(max_workers=max(1, len(groups))) as ex:
-            sizes = [m for ms in ex.map(run, groups.values()) for m in ms]
+            for members, (res, ms) in zip(groups, ex.map(run, groups)):
+                sizes += ms
+                for i, r in zip(members, res):
+                    outs[i] = r
         t_run = time.perf_counter()
     finally:
         for bk in bks:
@@ -1568,6 +1492,24 @@ def solve_batch(specs, n_stages, device=0, monitor_period=0, monitor_tol=0.0, pr
     t_end = time.perf_counter()
     solve_batch.last_phases_ms = {"create": (t_made - t0) * 1e3, "sweep": (t_run - t_made) * 1e3, "close": (t_end - t_run) * 1e3}
     return outs, (t_end - t0) * 1e3, variants, sizes
+
+
+def store_channel_results(solver, built, outs, n_st, keep_policy, u_vector):
+    """Shared end of Solver_position.simplified_run and Solver_attitude.simplified_run: what the three channels' sweeps leave on
+    `solver`.  built[ch] = (spec, the channel's two grid vectors), outs[ch] its sweep's dict.  Per channel F_values and U_idx
+    (1-based) on the grid, sweep_ms, and U<ch+1>_Opt, the 'nearest' policy over U_vector[U_idx - 1]; with keep_policy the labels
+    of all n_st stages U_idx_stages[ch] [n_a, n_b, n_st] and their values U_Opt_stages[ch] = u_vector[labels - 1], else None."""
+    from .solver_position import NearestPolicy
+    solver.U_Opt_stages = solver.U_idx_stages = None
+    if keep_policy:
+        solver.U_idx_stages = [out["idx_stages"].reshape(len(s_a), len(s_b), n_st, order="F") for (_, s_a, s_b), out in zip(built, outs)]
+        solver.U_Opt_stages = [u_vector[ix - 1] for ix in solver.U_idx_stages]
+    for ch, ((_, s_a, s_b), out) in enumerate(zip(built, outs)):
+        shape = (len(s_a), len(s_b))
+        solver.F_values[ch] = out["J"].reshape(shape, order="F")
+        solver.U_idx[ch] = out["idx"].reshape(shape, order="F")
+        solver.sweep_ms[ch] = out["sweep_ms"]
+        setattr(solver, "U%d_Opt" % (ch + 1), NearestPolicy([s_a, s_b], solver.U_vector[solver.U_idx[ch] - 1]))
 
 
 def channel_policy_cost(solver, build, n_stages, stationary):

@@ -19,10 +19,9 @@ import math
 
 import numpy as np
 
-from .core import Backup, channel_policy_cost, solve_batch, solve_many
+from .core import Backup, channel_policy_cost, solve_batch, solve_many, store_channel_results
 from .matlab_compat import deg2rad, linspace
 from .problem import ProblemSpec, Term, channel_disturbance
-from .solver_position import NearestPolicy
 
 f32 = np.float32
 
@@ -95,7 +94,6 @@ class Solver_attitude:
         1-based labels), written by the stage kernel itself (hjb_solve_opts.idx_stages)."""
         n_st = self.N_stage - 1 if n_stages is None else int(n_stages)
         self.F_values, self.U_idx, self.sweep_ms = [None] * 3, [None] * 3, [None] * 3
-        self.U_Opt_stages = self.U_idx_stages = None
         built = [self.build_spec_simplified(ch) for ch in range(3)]
         if keep_policy or not self.batch_channels:
             outs, self.wall_ms, _ = solve_many([b[0] for b in built], n_st, device=self.device,   # channels side by side
@@ -103,17 +101,7 @@ class Solver_attitude:
             self.batch_groups = [1, 1, 1]
         else:                              # ... as ONE launch per stage for the three (hjb_solve_batch)
             outs, self.wall_ms, _, self.batch_groups = solve_batch([b[0] for b in built], n_st, device=self.device)
-        if keep_policy:
-            self.U_idx_stages = [outs[ch]["idx_stages"].reshape(len(built[ch][1]), len(built[ch][2]), n_st, order="F") for ch in range(3)]
-            self.U_Opt_stages = [self.U_vector[ix - 1] for ix in self.U_idx_stages]
-        for ch in range(3):
-            spec, s_w, s_t = built[ch]
-            out = outs[ch]
-            shape = (len(s_w), len(s_t))
-            self.F_values[ch] = out["J"].reshape(shape, order="F")
-            self.U_idx[ch] = out["idx"].reshape(shape, order="F")
-            self.sweep_ms[ch] = out["sweep_ms"]
-            setattr(self, "U%d_Opt" % (ch + 1), NearestPolicy([s_w, s_t], self.U_vector[self.U_idx[ch] - 1]))  # :249-251
+        store_channel_results(self, built, outs, n_st, keep_policy, self.U_vector)          # :249-251
         return self
 
     def policy_cost_simplified(self, n_stages=None, stationary=True):

@@ -18,7 +18,7 @@ import math
 
 import numpy as np
 
-from .core import Backup, channel_policy_cost, solve_many
+from .core import Backup, channel_policy_cost, solve_many, store_channel_results
 from .matlab_compat import interp_nearest_point, sym_linspace_position
 from .problem import ProblemSpec, Term, channel_disturbance
 
@@ -111,20 +111,8 @@ class Solver_position:
         built = [self.build_spec(ch) for ch in range(3)]
         # the three channels are independent sweeps (:132-141 runs them in one loop body): in flight together
         outs, self.wall_ms, _ = solve_many([b[0] for b in built], n_st, device=self.device, keep_idx=bool(keep_policy))
-        self.U_Opt_stages = self.U_idx_stages = None
-        if keep_policy:
-            self.U_idx_stages = [outs[ch]["idx_stages"].reshape(len(built[ch][1]), len(built[ch][2]), n_st, order="F") for ch in range(3)]
-            self.U_Opt_stages = [np.asarray(self.U_vector, dtype=np.float64)[ix - 1] for ix in self.U_idx_stages]
-        for ch in range(3):
-            spec, s_x, s_v = built[ch]
-            out = outs[ch]
-            shape = (len(s_x), len(s_v))
-            self.F_values[ch] = out["J"].reshape(shape, order="F")
-            self.U_idx[ch] = out["idx"].reshape(shape, order="F")
-            self.sweep_ms[ch] = out["sweep_ms"]
-            pol = NearestPolicy([s_x, s_v], self.U_vector[self.U_idx[ch] - 1])
-            setattr(self, "U%d_Opt" % (ch + 1), pol)
-        self.n_mesh_x, self.n_mesh_v = len(s_x), len(s_v)                     # :100,:104
+        store_channel_results(self, built, outs, n_st, keep_policy, np.asarray(self.U_vector, dtype=np.float64))
+        self.n_mesh_x, self.n_mesh_v = len(built[2][1]), len(built[2][2])     # :100,:104
         return self
 
     def policy_cost(self, n_stages=None, stationary=True):
