@@ -151,7 +151,7 @@ def interp_linear(knots, J, q):
     return vals[0]
 
 
-def backup_stage(p: Problem, J_next, chunk_states=None):
+def backup_stage(p: Problem, J_next, chunk_states=None, runner_up=False):
     """One Bellman backup: returns (J_k [n], idx [n] int32 0-based flat control index).
 
     The flat control index enumerates the C control dims column-major (first
@@ -160,26 +160,60 @@ def backup_stage(p: Problem, J_next, chunk_states=None):
     min over dims 9,8,7 (Solver_attitude.m:400-409) prefers the smallest i1, then
     i2, then i3.  With a single control dim both rules coincide.  We implement
     the cascade rule: lexicographic (i1, i2, i3) with i1 most significant.
+
+    chunk_states: evaluate at most about that many states at a time (slices of the FIRST state axis; every operation
+    is elementwise over the states, so the result does not depend on it).  runner_up=True also returns, per state, the
+    smallest total among the controls other than the returned one (+inf when there is one control).
     """
     J_next = np.asarray(J_next, dtype=p.dtype).reshape(p.n)
-    q = [p._sum(p.next_terms[a]) for a in range(p.D)]
-    g = p._sum(p.cost_terms)
-    full = p.n + p.m
-    # evaluate over the full grid (tests keep sizes small)
+    rows = p.n[0]
+    if chunk_states:
+        rows = max(1, min(p.n[0], int(chunk_states) // max(1, p.nS // p.n[0])))
+    Jk = np.empty(p.n, dtype=p.dtype)
+    flat = np.empty(p.n, dtype=np.int32)
+    second = np.empty(p.n, dtype=p.dtype) if runner_up else None
+    for lo in range(0, p.n[0], rows):
+        hi = min(lo + rows, p.n[0])
+        out = _backup_rows(p, J_next, lo, hi, runner_up)
+        Jk[lo:hi], flat[lo:hi] = out[0], out[1]
+        if runner_up:
+            second[lo:hi] = out[2]
+    return (Jk, flat, second) if runner_up else (Jk, flat)
+
+
+def _backup_rows(p, J_next, lo, hi, runner_up):
+    """backup_stage for the states whose first index is in [lo, hi)."""
+    def rows_sum(terms):
+        acc = None
+        for t in terms:
+            e = t.expand(p.G)
+            if e.shape[0] != 1:
+                e = e[lo:hi]
+            acc = e if acc is None else (acc + e).astype(p.dtype, copy=False)
+        return acc
+
+    q = [rows_sum(p.next_terms[a]) for a in range(p.D)]
+    g = rows_sum(p.cost_terms)
+    n = (hi - lo,) + p.n[1:]
+    full = n + p.m
+    # evaluate over the full grid of the rows (tests keep sizes small)
     Jf = interp_linear(p.knots, J_next, [np.broadcast_to(x, full) for x in q])
     tot = (np.broadcast_to(g, full) + Jf).astype(p.dtype, copy=False)
     # first minimum over a ROW-major flatten of the control dims (i1 slowest)
     # = lexicographically smallest (i1, i2, i3) among joint minimisers = cascade
-    tot = np.ascontiguousarray(tot).reshape(p.n + (p.nU,))
+    tot = np.ascontiguousarray(tot).reshape(n + (p.nU,))
     k = np.argmin(tot, axis=-1)
     Jk = np.take_along_axis(tot, k[..., None], axis=-1)[..., 0]
     sub = np.unravel_index(k, p.m)  # (i1, ..., iC), C-order
-    flat = np.zeros(p.n, dtype=np.int64)
+    flat = np.zeros(n, dtype=np.int64)
     mul = 1
     for c in range(p.C):  # column-major flat label (first control dim fastest)
         flat += sub[c].astype(np.int64) * mul
         mul *= p.m[c]
-    return Jk, flat.astype(np.int32)
+    if not runner_up:
+        return Jk, flat.astype(np.int32)
+    np.put_along_axis(tot, k[..., None], np.inf, axis=-1)
+    return Jk, flat.astype(np.int32), tot.min(axis=-1)
 
 
 def sweep(p: Problem, n_stages, terminal=None, keep=False, monitor_period=0, monitor_tol=0.0):
