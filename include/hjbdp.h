@@ -279,8 +279,8 @@ int32_t hjb_set_option(hjb_handle h, const char *key, int64_t value);
  * (1 [default where every index of the problem fits 31 bits]: the table kernel's 32-bit form, 0: its general 64-bit form;
  * reads back the form a launch would take).  "grid" (get: workgroups per launch; set, timing experiments on the grid-stride
  * kernels only: the library's own choice walks a grid larger than the launch in equally long spans - until the next option that
- * re-chooses the launch).  "block" (set, variant 3 only: 256 / 512 / 1024 threads per workgroup = 64 x the states it sweeps side by
- * side; 512 by default where J is staged in LDS). */
+ * re-chooses the launch).  "block" (set, variant 3: 256 / 512 / 1024 threads per workgroup = 64 x the states it sweeps side by
+ * side; 512 by default where J is staged in LDS.  Variant 8: 64 / 128 / 256, same bits - its min form strides by the launch). */
 int32_t hjb_get_option(hjb_handle h, const char *key, int64_t *value);
 
 /* ONE backup, host buffers (exactly the MATLAB statement above):
@@ -422,6 +422,37 @@ int32_t hjb_evaluate(hjb_handle h, int32_t n_stages, const void *terminal, const
 #define HJB_DIST_WORST 1
 #define HJB_DIST_MAX_NODES 128
 int32_t hjb_set_disturbance(hjb_handle h, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights);
+
+/* ---- a control-dependent disturbance in the backup (kernel variant 8, per-control form: K32) --------------------------------------
+ *   J_k(x) = min_u  g(x, u) + E_w / max_w F_{k+1}(x_next(x, u) + d_w(u))
+ * The node set depends on the candidate control: actuator noise, x+ = A x + B (u (1 + eps_w)), has d_w(u) = B u eps_w - "no
+ * control" is noise-free, a large control is uncertain, and the optimal policy becomes cautious.  Additive nodes cannot say that.
+ * Same modes, weights, rounding rules and consequences as hjb_set_disturbance above; only step 1 of its contract changes:
+ *   1. for node w of the candidate with 0-based column-major control label l (the number the stage writes, minus index_base)
+ *      q_aw = (TQ)(q_a + d[a][w][l]).
+ * offsets: [D, n_nodes, n_controls] column-major - offsets[a + D * (w + n_nodes * l)] - each entry rounded once to TQ at the call.
+ * n_controls must equal the handle's nU (it is there so that a table of the wrong size is refused instead of read past).
+ * Steps 2 - 5 are hjb_set_disturbance's word for word: cell and weight, the fma cascade, acc = (T)(p_0 v_0) then fma(p_w, v_w, acc)
+ * or the first maximum, candidate (T)(g + acc).  Every node is evaluated for every control, also for a control whose offsets are
+ * all zero: the bits are defined by the contract, not by a shortcut.  The offset-axis mask ("dist_axes") has bit a set iff some
+ * (w, l) entry of row a is not zero; an axis outside the mask is located once per control, as there.
+ * The setting is of the same kind as hjb_set_disturbance's and lives in the same place: every entry that launches a stage serves it
+ * (hjb_backup_stage(_device), hjb_solve, hjb_solve_flat, hjb_evaluate_stage(_device), hjb_evaluate), hjb_info.kernel_variant reads
+ * 8, the two setters replace each other, and n_nodes == 0 through either detaches (n_controls is then not looked at): the handle
+ * returns to the launch and the bits it had.
+ * Consequences: (i) a table that is constant along l gives J and labels bit for bit those of hjb_set_disturbance with that node set,
+ * under every typing; (ii) one zero node is the undisturbed backup; (iii) for any fixed label l0 the candidate equals
+ * hjb_set_disturbance's candidate under the node set offsets[:, :, l0]; (iv) the fixed-label form (hjb_evaluate*) shares the min
+ * form's candidates: its own labels return its J, any labels values >= it, a label out of range NaN and the flag.
+ * Refused before any device work, the handle left as it was: everything hjb_set_disturbance refuses; HJB_E_INVALID: n_controls < 0
+ * or, with n_nodes > 0, n_controls != nU; HJB_E_UNSUPPORTED: D * n_nodes * nU > 2^26 entries (the table stays within 512 MiB and its
+ * index within 32 bits).  While it is set the same three refusals hold: a probe in hjb_solve, membership in hjb_solve_batch,
+ * option "temporal" = 2.
+ * Options: read-only "dist_ctrl" (1 while the disturbance in effect is this one, else 0); "dist_nodes", "dist_mode", "dist_axes",
+ * "dist_form" and "dist_i32" as above.  Flying under such noise (a rollout with d_w(u)) is not built. */
+#define HJB_CTRL_DIST_MAX_ENTRIES 67108864 /* 2^26 */
+int32_t hjb_set_control_disturbance(hjb_handle h, int32_t mode, int32_t n_nodes, int32_t n_controls, const double *offsets,
+                                    const double *weights);
 
 /* ---- batched closed-loop rollouts of a stored policy (test/Dynamic_Solver.m:108-181 get_optimal_path, 'Nssu' and 'ssu') ----
  * A rollout object holds a per-stage policy on one device: the grid (D <= 6 axes, knots concatenated axis 0 first), the

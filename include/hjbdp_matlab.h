@@ -51,6 +51,10 @@ int32_t hjb_evaluate(void *handle, int32_t n_stages, const void *terminal, const
  * state (offsets [D, n_nodes] column-major; weights [n_nodes], expected value only, NULL = equal); n_nodes 0 detaches.  Every stage
  * the handle launches afterwards carries it; usage: matlab/hjbdp_set_disturbance.m, hjbdp_solve's 'disturbance' pair */
 int32_t hjb_set_disturbance(void *handle, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights);
+/* ... that depends on the candidate control (K32): offsets [D, n_nodes, n_controls] column-major by the 0-based column-major control
+ * label, n_controls = the handle's number of controls; the two setters replace each other; usage: matlab/hjbdp_set_control_disturbance.m */
+int32_t hjb_set_control_disturbance(void *handle, int32_t mode, int32_t n_nodes, int32_t n_controls, const double *offsets,
+                                    const double *weights);
 int32_t hjb_get_info_flat(void *handle, int64_t *out8);
 int32_t hjb_set_option(void *handle, const char *key, int64_t value);
 int32_t hjb_get_option(void *handle, const char *key, int64_t *value);

@@ -341,6 +341,11 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
         return HJB_OK;
     }
     if (!strcmp(key, "block")) {                                     // variant 3: threads per workgroup = 64 x the states a workgroup sweeps side by side
+        if (h->L.variant == 8 && (value == 64 || value == 128 || value == 256)) {      // variant 8 strides by whatever it is launched with (timing, tests)
+            h->L.block = (int)value;
+            launch_changed(h);
+            return HJB_OK;
+        }
         if (h->L.variant != 3 || (value != 256 && value != 512 && value != 1024)) return fail(h, HJB_E_UNSUPPORTED, "block: 256, 512 or 1024 on kernel variant 3");
         h->L.block = (int)value;
         launch_changed(h);
@@ -449,7 +454,7 @@ int32_t hjb_set_option(hjb_handle hh, const char *key, int64_t value) {
         launch_changed(h);           // (the captured launches are the other form)
         return HJB_OK;
     }
-    if (!strcmp(key, "dist_nodes") || !strcmp(key, "dist_mode") || !strcmp(key, "dist_axes") || !strcmp(key, "dist_form"))
+    if (!strcmp(key, "dist_nodes") || !strcmp(key, "dist_mode") || !strcmp(key, "dist_axes") || !strcmp(key, "dist_form") || !strcmp(key, "dist_ctrl"))
         return fail(h, HJB_E_INVALID, "%s is read-only: hjb_set_disturbance sets the disturbance, the form follows from the sizes and dist_i32", key);
     if (!strcmp(key, "eval_form")) return fail(h, HJB_E_INVALID, "eval_form is read-only: the form follows from the sizes, eval_i32, eval_m24 and eval_tables");
     if (!strcmp(key, "eval_tables")) {      // the fixed-label stage's cells and weights: -1 automatic, 0 terms summed on the fly, 1 the (cell, t) tables
@@ -491,6 +496,7 @@ int32_t hjb_get_option(hjb_handle hh, const char *key, int64_t *value) {
     else if (!strcmp(key, "dist_axes")) *value = h->dist_axes;
     else if (!strcmp(key, "dist_form")) *value = dist_runs_i32(h) ? 1 : 0;    // 0 64-bit, 1 32-bit: the next launch's
     else if (!strcmp(key, "dist_i32")) *value = h->dist_i32 ? 1 : 0;
+    else if (!strcmp(key, "dist_ctrl")) *value = h->dist_ctrl ? 1 : 0;        // 1: the disturbance in effect is per control (hjb_set_control_disturbance)
     else if (!strcmp(key, "idx_bytes")) *value = h->idx_bytes;
     else if (!strcmp(key, "temporal")) *value = h->use_temporal;
     else if (!strcmp(key, "chunk_order")) *value = h->dn ? h->hn.chunk_order : 0;

@@ -215,7 +215,8 @@ int launch_stage(Handle *h, const void *dJn, void *dJo, void *didx, hipStream_t 
         case 0: miss = stage_generic(a); break;
         case 8:
             a.idx32 = dist_runs_i32(h);
-            miss = stage_disturb(a, h->tab64, h->tab64 ? h->dp64 : h->dp, h->d_dist, nullptr, nullptr);
+            miss = h->dist_ctrl ? stage_ctrldist(a, h->tab64, h->tab64 ? h->dp64 : h->dp, h->d_dist, h->d_dist_tab, nullptr, nullptr)
+                                : stage_disturb(a, h->tab64, h->tab64 ? h->dp64 : h->dp, h->d_dist, nullptr, nullptr);
             break;
         default:    // never fall through to the generic kernel silently
             return fail(h, HJB_E_DEVICE, "internal: kernel variant %d was not dispatched", L.variant);
@@ -247,7 +248,8 @@ int launch_evaluate(Handle *h, const void *dJn, const void *dlabels, void *dJo, 
     a.idx32 = eval_runs_i32(h);
     if (h->dist_nodes > 0) {                               // the same kernel as the disturbed backup, one candidate per state
         a.idx32 = dist_runs_i32(h);
-        if (stage_disturb(a, h->tab64, h->tab64 ? h->dp64 : h->dp, h->d_dist, dlabels, h->d_status + 1))
+        if (h->dist_ctrl ? stage_ctrldist(a, h->tab64, h->tab64 ? h->dp64 : h->dp, h->d_dist, h->d_dist_tab, dlabels, h->d_status + 1)
+                         : stage_disturb(a, h->tab64, h->tab64 ? h->dp64 : h->dp, h->d_dist, dlabels, h->d_status + 1))
             return fail(h, HJB_E_UNSUPPORTED, "variant 8 has no fixed-label kernel for D=%d, dtype %d", a.D, h->dtype);
         HIP_TRY(h, hipGetLastError());
         return HJB_OK;

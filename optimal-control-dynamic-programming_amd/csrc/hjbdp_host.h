@@ -8,7 +8,7 @@
 //   hjbdp_api.hip      hjb_create .. hjb_backup_stage, options, probe, policy lookup (the single-device C ABI)
 //   hjbdp_solve.hip    hjb_solve (one handle's backward sweep; hjbdp_sweep.h: the monitor rule, its schedule, the graph split)
 //   hjbdp_evaluate.hip hjb_evaluate_stage, hjb_evaluate_stage_device, hjb_evaluate (the cost of a given policy on the grid)
-//   hjbdp_disturb.hip  hjb_set_disturbance (the disturbance a handle's stages carry: kernel variant 8)
+//   hjbdp_disturb.hip  hjb_set_disturbance, hjb_set_control_disturbance (the disturbance a handle's stages carry: kernel variant 8)
 //   hjbdp_batch.hip    hjb_solve_batch (several sweeps of one kernel shape, one launch per stage)
 //   hjbdp_builder.hip  the flat builder API (MATLAB loadlibrary / calllib)
 //   hjbdp_slab.hip     one device's slab of a partitioned grid: its handles, strip streams, and the enqueue of one stage (hjbdp_slab.h: the arithmetic)
@@ -191,6 +191,10 @@ struct Handle {
     uint32_t dist_axes = 0;       // bit a: some node offsets axis a (option "dist_axes")
     bool dist_i32 = true;         // option "dist_i32": 0 = the 64-bit form of the kernel whatever the sizes (A/B timing, tests)
     void *d_dist = nullptr;       // the DDisturb block on the device (allocated by the first call, rewritten by later ones)
+    // ... per control (hjb_set_control_disturbance; kernels_ctrldist.h): the nodes' offsets come from a table behind the block
+    bool dist_ctrl = false;       // option "dist_ctrl" (read-only): the disturbance in effect is the per-control one
+    void *d_dist_tab = nullptr;   // [nU in visiting order][n_nodes][D] in the query type: rewritten in place, reallocated when it grows
+    size_t dist_tab_bytes = 0;    // its capacity
     Launch L;
     int halo_need_lo = 0, halo_need_hi = 0;
     std::string err;

@@ -53,6 +53,8 @@ int stage_evaluate(const StageArgs &a, bool tabled, bool mul24, const void *labe
 // variant 8 (K24, kernels_disturb.h): the stage of a handle with a disturbance.  q64: HJB_TAB_F64 (dpq = the float64 shadow of the axes,
 // else a.dp); dist: the handle's DDisturb block; labels: non-null runs the fixed-label form (a.idx not written, *bad_label as stage_evaluate)
 int stage_disturb(const StageArgs &a, bool q64, const DParams *dpq, const void *dist, const void *labels, int32_t *bad_label);
+// ... its per-control form (K32, kernels_ctrldist.h): table = the handle's per-control offsets [nU visiting order][n_nodes][D] in the query type
+int stage_ctrldist(const StageArgs &a, bool q64, const DParams *dpq, const void *dist, const void *table, const void *labels, int32_t *bad_label);
 int stage_tile2d_plan(int dtype, const DParams *dp, const DTabled *dtb, void *plan, int64_t n_entries);
 
 }  // namespace hjb

@@ -12,7 +12,7 @@ there is no CPU fallback.
 from . import _abi
 from .core import Backup, DeviceBuffer, HjbError, MultiBackup, RankSlab, Rollout, attitude_linear_response, campaign_hist_reduce, campaign_pair_reduce, campaign_quantiles, campaign_reduce, campaign_tail_mean, device_count, device_mem_info, greedy_host, load_library, lookahead_campaign_host, lookahead_host, noise_draw, noise_thresholds, policy_lookup, solve_batch, solve_many, suggest_axis_order
 from .problem import ProblemSpec, Term, permute_state_axes
-from .disturbance import box_nodes, gaussian_nodes
+from .disturbance import actuator_nodes, box_nodes, gaussian_nodes
 from .dynamic_solver import Dynamic_Solver
 from .solver_position import Solver_position
 from .solver_attitude import Solver_attitude

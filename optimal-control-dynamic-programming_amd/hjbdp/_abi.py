@@ -168,6 +168,8 @@ SYMBOLS = {
     "hjb_evaluate": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     # a disturbance in the backup (kernel variant 8): expected-value and worst-case stages
     "hjb_set_disturbance": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # ... that depends on the candidate control (per-control form, K32)
+    "hjb_set_control_disturbance": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # flat builder API (primitives and plain arrays only: what MATLAB's calllib can marshal)
     "hjb_problem_new": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                     C.POINTER(C.c_void_p)]),
@@ -306,6 +308,7 @@ SYMBOLS = {
 HJB_DIST_EXPECT = 0
 HJB_DIST_WORST = 1
 HJB_DIST_MAX_NODES = 128
+HJB_CTRL_DIST_MAX_ENTRIES = 67108864
 HJB_ROLLOUT_MAX_U = 4
 HJB_CAMPAIGN_NSTAT = 8
 HJB_CAMPAIGN_MAX_BINS = 256

@@ -12,7 +12,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _abi
-from .problem import ProblemSpec, check_disturbance
+from .problem import ProblemSpec, check_control_disturbance, check_disturbance
 
 _LIB = None
 LIB_PATH = Path(__file__).resolve().parent / "libhjbdp.so"
@@ -1134,16 +1134,24 @@ class Backup(_Handle):
             except Exception:
                 self.close()
                 raise
+        if spec.control_disturbance is not None:
+            try:
+                self.set_control_disturbance(*spec.control_disturbance)
+            except Exception:
+                self.close()
+                raise
 
     # -- queries ----------------------------------------------------------
     def info(self):
-        """hjb_get_info's fields, plus the disturbance in effect: dist_nodes (0: none), dist_mode ("expect" / "worst" / None), dist_axes."""
+        """hjb_get_info's fields, plus the disturbance in effect: dist_nodes (0: none), dist_mode ("expect" / "worst" / None), dist_axes,
+        dist_ctrl (True: the per-control one, set_control_disturbance)."""
         inf = _abi.hjb_info()
         self._check(self.lib.hjb_get_info(self._h, C.byref(inf)))
         out = {k: getattr(inf, k) for k, _ in inf._fields_}
         out["dist_nodes"] = self.get_option("dist_nodes")
         out["dist_mode"] = ("expect", "worst")[self.get_option("dist_mode")] if out["dist_nodes"] else None
         out["dist_axes"] = self.get_option("dist_axes")
+        out["dist_ctrl"] = bool(self.get_option("dist_ctrl"))
         return out
 
     # -- the disturbance the handle's stages carry (hjb_set_disturbance: kernel variant 8) ----------------------------
@@ -1156,8 +1164,18 @@ class Backup(_Handle):
         self._check(self.lib.hjb_set_disturbance(self._h, _abi.HJB_DIST_WORST if mode == "worst" else _abi.HJB_DIST_EXPECT, off.shape[1],
                                                  _f64p(offc), _f64p(w)))
 
+    def set_control_disturbance(self, offsets, weights=None, mode="expect"):
+        """set_disturbance with a node set per candidate control (hjb_set_control_disturbance): the W next states of the
+        control with 0-based column-major label l are x_next + offsets[:, w, l].  offsets [D, W, nU], or [D, W, *m] (flattened
+        column-major); weights and mode as set_disturbance.  The two settings replace each other; hjbdp.actuator_nodes builds
+        the table of an actuator that delivers u * (1 + eps_w)."""
+        off, w, mode = check_control_disturbance(self.spec.D, self.spec.m, offsets, weights, mode)
+        offc = np.asfortranarray(off)
+        self._check(self.lib.hjb_set_control_disturbance(self._h, _abi.HJB_DIST_WORST if mode == "worst" else _abi.HJB_DIST_EXPECT,
+                                                         off.shape[1], off.shape[2], _f64p(offc), _f64p(w)))
+
     def clear_disturbance(self):
-        """Back to the nominal backup: the launch the handle had, the same bits as before."""
+        """Back to the nominal backup, from either setting: the launch the handle had, the same bits as before."""
         self._check(self.lib.hjb_set_disturbance(self._h, _abi.HJB_DIST_EXPECT, 0, None, None))
 
     def set_option(self, key, value):

@@ -19,6 +19,7 @@ import contextlib
 import numpy as np
 
 from .core import Backup
+from .disturbance import actuator_nodes
 from .matlab_compat import interp_linear_point, linspace
 from .problem import ProblemSpec, Term
 
@@ -44,6 +45,7 @@ class Dynamic_Solver:
         self.precision = precision
         self.device = 0
         self.disturbance = None   # (offsets [2, W], weights or None, 'expect' / 'worst'): run() and policy_cost() under it (ProblemSpec.disturbance)
+        self.actuator_noise = None   # (eps [W], weights or None, 'expect' / 'worst'): the actuator delivers u (1 + eps_w) - run() and policy_cost() under d_w(l) = B U_mesh[l] eps[w] (ProblemSpec.control_disturbance); not with self.disturbance
         # results
         self.s_r = None
         self.u_star = None
@@ -82,7 +84,15 @@ class Dynamic_Solver:
             raise ValueError("precision must be 'single' or 'double'")
         self.s_r = s_r
         self._U_mesh = U_mesh
-        return ProblemSpec([s_r, s_r], [self.du], nxt, cost, dtype=dt, index_base=1, disturbance=self.disturbance)
+        cdist = None
+        if self.actuator_noise is not None:
+            if self.disturbance is not None:
+                raise ValueError("Dynamic_Solver takes `disturbance` or `actuator_noise`, not both")
+            eps, wts = self.actuator_noise[0], self.actuator_noise[1] if len(self.actuator_noise) > 1 else None
+            off, wts = actuator_nodes(B, np.asarray(U_mesh, dtype=np.float64), eps, wts)
+            cdist = (off, wts, self.actuator_noise[2] if len(self.actuator_noise) > 2 else "expect")
+        return ProblemSpec([s_r, s_r], [self.du], nxt, cost, dtype=dt, index_base=1, disturbance=self.disturbance,
+                           control_disturbance=cdist)
 
     def run(self):
         spec = self.build_spec()
@@ -94,7 +104,7 @@ class Dynamic_Solver:
         # (hjb_probe).  MATLAB raises an index error when dx < 57 or du < 105; the mirror leaves the taps None instead
         # (the fixture revision test/test_coder.m has no taps and runs at dx = 35).
         probe = None
-        if self.checkstagesXJF and self.dx >= 57 and self.du >= 105 and self.disturbance is None:    # (the taps are the nominal next state's)
+        if self.checkstagesXJF and self.dx >= 57 and self.du >= 105 and self.disturbance is None and self.actuator_noise is None:    # (the taps are the nominal next state's)
             probe = {"lo": (49, 51), "hi": (55, 57), "control": (104,), "want": ("g", "x_next", "j_interp")}
         with Backup(spec, device=self.device) as bk:
             out = bk.solve(n_st, keep_J=True, keep_idx=True, probe=probe)
@@ -230,6 +240,9 @@ class Dynamic_Solver:
         from .core import Rollout
         if self.u_star_idxs is None or (values and self.J_star is None):
             raise RuntimeError("run() first")
+        if (lookahead is not False or noise) and self.actuator_noise is not None:
+            raise RuntimeError("%s: flying under control-dependent noise (self.actuator_noise) is not built; run() and policy_cost() "
+                               "design and price under it" % who)
         if (lookahead is not False or noise) and self.disturbance is None:
             raise RuntimeError("%s needs self.disturbance = (offsets [2, W], weights or None, mode)" % who)
         if lookahead is not False and lookahead not in ("disturbed", "nominal"):

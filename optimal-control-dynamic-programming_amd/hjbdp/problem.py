@@ -51,10 +51,13 @@ class ProblemSpec:
     (state, control) is their ordered sum in double rounded to float32 once - `single(double expression)` of
     Solver_pos_att.m:800-801 without the nS x nU array (hjbdp.h HJB_COST_F64).
     disturbance: None, or (offsets [D, W], weights [W] or None, mode "expect" / "worst"): additive offsets of the next state
-    the backup takes the expected value or the worst case over (hjbdp.h hjb_set_disturbance; row a belongs to state axis a)."""
+    the backup takes the expected value or the worst case over (hjbdp.h hjb_set_disturbance; row a belongs to state axis a).
+    control_disturbance: None, or (offsets [D, W, nU] or [D, W, *m], weights, mode): the same with a node set per candidate
+    control, offsets[:, w, l] for the 0-based column-major control label l (hjbdp.h hjb_set_control_disturbance).  A field of
+    its own, mutually exclusive with `disturbance`: what reads the 3-tuple `disturbance` never meets a table."""
 
     def __init__(self, knots, m, next_terms, cost_terms, dtype=np.float64, index_base=0, j_storage=None, model=None,
-                 idx_dtype=None, table_dtype=None, cost_dtype=None, disturbance=None):
+                 idx_dtype=None, table_dtype=None, cost_dtype=None, disturbance=None, control_disturbance=None):
         self.dtype = np.dtype(dtype)
         self.cost_dtype = None if cost_dtype is None else np.dtype(cost_dtype)
         if self.cost_dtype is not None and not (self.cost_dtype == np.float64 and self.dtype == np.float32 and model is None):
@@ -109,6 +112,11 @@ class ProblemSpec:
                 raise ValueError("1..%d terms per quantity (none for model axes)" % _abi.HJB_MAX_TERMS)
         self.disturbance = None if disturbance is None else check_disturbance(self.D, *disturbance)
         if self.disturbance is not None and self.model is not None:
+            raise ValueError("a spec with a state model takes no disturbance")
+        self.control_disturbance = None if control_disturbance is None else check_control_disturbance(self.D, self.m, *control_disturbance)
+        if self.control_disturbance is not None and self.disturbance is not None:
+            raise ValueError("a spec takes `disturbance` or `control_disturbance`, not both")
+        if self.control_disturbance is not None and self.model is not None:
             raise ValueError("a spec with a state model takes no disturbance")
         self.index_base = int(index_base)
         self.nS = int(np.prod(self.n))
@@ -189,6 +197,29 @@ def check_disturbance(D, offsets, weights=None, mode="expect"):
     return off, w, mode
 
 
+def check_control_disturbance(D, m, offsets, weights=None, mode="expect"):
+    """(offsets [D, W, nU] float64, weights [W] float64 or None, mode) after the checks hjb_set_control_disturbance makes: the
+    one statement of them on the Python side (ProblemSpec, Backup.set_control_disturbance).  offsets may be given as [D, W, *m]:
+    the control dims are flattened column-major into the label (dim 0 fastest)."""
+    m = tuple(int(x) for x in m)
+    nU = int(np.prod(m))
+    shape = np.shape(offsets)                                     # (the shape is judged before anything is copied)
+    if len(shape) == 2 + len(m) and tuple(shape[2:]) == m:
+        shape = tuple(shape[:2]) + (nU,)
+    if len(shape) != 3 or shape[0] != D or shape[2] != nU or not (1 <= shape[1] <= _abi.HJB_DIST_MAX_NODES):
+        raise ValueError("control-disturbance offsets must be [D=%d, W, nU=%d] (or [D, W, *m]) with 1 <= W <= %d, got %r"
+                         % (D, nU, _abi.HJB_DIST_MAX_NODES, np.shape(offsets)))
+    if D * shape[1] * nU > _abi.HJB_CTRL_DIST_MAX_ENTRIES:
+        raise ValueError("control-disturbance offsets hold %d entries: more than the %d one table holds"
+                         % (D * shape[1] * nU, _abi.HJB_CTRL_DIST_MAX_ENTRIES))
+    off = np.array(offsets, dtype=np.float64).reshape(shape, order="F")
+    # the rest is the node set's own: the checks of check_disturbance on the [D, W] slice of control 0 (mode, weights) and on every entry
+    if not np.all(np.isfinite(off)):
+        raise ValueError("disturbance offsets must be finite")
+    _, w, mode = check_disturbance(D, off[:, :, 0], weights, mode)
+    return off, w, mode
+
+
 def channel_disturbance(disturbance, channel):
     """The solver mirrors' `disturbance` attribute for one channel: None, ONE (offsets, weights, mode) tuple for every channel,
     or a LIST with one such tuple (or None) per channel - rows in the channel's own axis order, as its build_spec lists the axes."""
@@ -220,9 +251,13 @@ def permute_state_axes(spec: ProblemSpec, order):
     dist = spec.disturbance
     if dist is not None:             # the offset rows travel with their axes
         dist = (dist[0][list(order), :], dist[1], dist[2])
+    cdist = spec.control_disturbance
+    if cdist is not None:
+        cdist = (cdist[0][list(order), :, :], cdist[1], cdist[2])
     new = ProblemSpec(knots, spec.m, nxt, cost, dtype=spec.dtype, index_base=spec.index_base,
                       j_storage=None if spec.j_dtype == spec.dtype else spec.j_dtype,
-                      idx_dtype=spec.idx_dtype, table_dtype=spec.table_dtype, cost_dtype=spec.cost_dtype, disturbance=dist)
+                      idx_dtype=spec.idx_dtype, table_dtype=spec.table_dtype, cost_dtype=spec.cost_dtype, disturbance=dist,
+                      control_disturbance=cdist)
     inv = [order.index(a) for a in range(D)]
 
     def to_old(flat):
