@@ -449,7 +449,7 @@ int32_t hjb_set_disturbance(hjb_handle h, int32_t mode, int32_t n_nodes, const d
  * index within 32 bits).  While it is set the same three refusals hold: a probe in hjb_solve, membership in hjb_solve_batch,
  * option "temporal" = 2.
  * Options: read-only "dist_ctrl" (1 while the disturbance in effect is this one, else 0); "dist_nodes", "dist_mode", "dist_axes",
- * "dist_form" and "dist_i32" as above.  Flying under such noise (a rollout with d_w(u)) is not built. */
+ * "dist_form" and "dist_i32" as above.  Flying under such noise: hjb_rollout_run_actuator (kernel K33, below). */
 #define HJB_CTRL_DIST_MAX_ENTRIES 67108864 /* 2^26 */
 int32_t hjb_set_control_disturbance(hjb_handle h, int32_t mode, int32_t n_nodes, int32_t n_controls, const double *offsets,
                                     const double *weights);
@@ -515,8 +515,9 @@ const char *hjb_rollout_last_error(void *rollout);
  * or weights that sum to 0; hjb_rollout_run_noisy with no noise set or with a model other than the affine one, and everything
  * hjb_rollout_run refuses; first_stream < 0 or first_stream + n_traj overflowing.  In the LDS form the node block (thresholds,
  * then the masked axes' offsets) is staged behind knots, 1/dx and u_table; the 32 KiB rule of option "lds" applies to the sum.
- * Out of scope: noise that depends on the control or the state, and continuous distributions (discretise them into nodes:
- * the Gauss-Hermite and box helpers of the host packages). */
+ * Noise that depends on the control (actuator noise): hjb_rollout_run_actuator (kernel K33, below).
+ * Out of scope: noise that depends on the state, and continuous distributions (discretise them into nodes: the Gauss-Hermite and
+ * box helpers of the host packages). */
 int32_t hjb_rollout_set_noise(void *rollout, int32_t n_nodes, const double *offsets, const double *weights);
 int32_t hjb_rollout_run_noisy(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                               const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost, double *X_path,
@@ -565,6 +566,54 @@ int32_t hjb_rollout_run_campaign(void *rollout, int32_t method, int32_t n_steps,
                                  const double *tol, double *stats, double *device_ms);
 int32_t hjb_rollout_campaign_reduce(int64_t n_starts, int64_t n_samples, int32_t D, const double *cost, const double *X_final,
                                     const uint8_t *left, const double *threshold, const double *tol, double *stats);
+
+/* ---- actuator-noise rollouts and campaigns: the affine loop under sampled control-dependent noise (kernels K33, K34) -------------
+ *   x+ = A x + B (u (1 + eps_w)) + c + base_w,   node w of a finite set (eps_w, base_w, p_w) drawn per trajectory and step
+ * - the model class of hjb_set_control_disturbance's actuator table (hjbdp.actuator_nodes: d_w(u) = B (u eps_w) + base_w), so one
+ * node set serves the design (hjb_solve on such a handle), the price (hjb_evaluate) and the flight (here).  Everything in double,
+ * one thread per trajectory, the affine model of hjb_rollout_set_model only.
+ * hjb_rollout_set_actuator_noise gives the object an actuator node set (n_nodes == 0 detaches): eps [n_u, n_nodes] column-major
+ * (eps[j + n_u * w]: the relative error of input j at node w), base [D, n_nodes] column-major or NULL (an additive node set on the
+ * same nodes), weights [n_nodes] or NULL with hjb_rollout_set_noise's meaning, at most HJB_DIST_MAX_NODES nodes.  The set is a
+ * property of the object, independent of hjb_rollout_set_noise's set and of the model; ONLY the two run functions below read it:
+ * every other run function of an object that holds one gives the bits it gave before.
+ * hjb_rollout_run_actuator is hjb_rollout_run_noisy word for word - the lookup, g, cost += g on the COMMANDED u, the affine update
+ * acc_a, and the draw of node w (the same stream first_stream + i, the same thresholds, the same two statements) - with one change.
+ * In the place of x+_a = acc_a + d[a][w]:
+ *   1. an input j is LIVE iff some eps[j][w] is not +-0; for every live input ue_j = u_j * eps[j][w], one rounded product, formed
+ *      once per step and used by every axis;
+ *   2. the noise terms of axis a, in this order: for live j ascending with B[a,j] not +-0, B[a,j] * ue_j (the product rounded); then
+ *      base[a][w] if row a of base has an entry that is not +-0;
+ *   3. an axis with no term: x+_a = acc_a - not touched, not even by adding 0.0;
+ *   4. otherwise n_a = the first term, n_a = n_a + term left to right, x+_a = acc_a + n_a.
+ * Which terms exist is a launch constant: the live-input and base-axis masks are formed by the setter, B[a,j] != 0 is read from the
+ * model in effect at the run (hjb_rollout_set_model may come before or after).  U_path holds the commanded u and W_path the drawn
+ * node; the delivered control u_j + ue_j is not stored.
+ * Consequences: (i) eps all +-0 with a base is hjb_rollout_run_noisy under hjb_rollout_set_noise(base, weights) bit for bit; with
+ * no base (or one that is all +-0) it is hjb_rollout_run bit for bit, W_path still the drawn nodes; (ii) W_path equals
+ * hjb_rollout_noise_draw for the same seed, streams and weights, so an additive and an actuator flight of one seed draw the same
+ * nodes (common random numbers across plants); (iii) with n_u = 1 and HJB_LOOKUP_NEAREST, one step from a grid node x of a double
+ * problem whose next-state terms are A[a,0] x0, A[a,1] x1, .., B[a,0] u lands on fl(q_a + off[a, w, l]), off the table of
+ * hjbdp.actuator_nodes and l the label at x: the point hjb_set_control_disturbance's backup queries for (x, l, w); (iv) on an exactly
+ * posed lattice problem the promised expected and worst-case costs are the costs paid.
+ * hjb_rollout_run_actuator_campaign is hjb_rollout_run_campaign's contract with hjb_rollout_run_actuator in the place of
+ * hjb_rollout_run_noisy: sample m of start s flies stream first_stream + s*M + m; the slots, the padding, the blocks of G, the tree,
+ * the fold and the 8 doubles per start are K28's; no array has a dimension of n_starts * n_samples; options "chunk" and "lds"
+ * change no bit; the statistics are bit for bit hjb_rollout_campaign_reduce of hjb_rollout_run_actuator's own outputs.
+ * Refused before any device work, outputs untouched (text: hjb_rollout_last_error) - HJB_E_INVALID: a null handle; n_nodes outside
+ * 0..HJB_DIST_MAX_NODES; null eps with n_nodes > 0; an eps or base entry that is not finite (named by input or axis and node);
+ * a weight that is not finite or is negative, or weights that sum to 0; the run functions with no actuator set, and everything
+ * hjb_rollout_run_noisy and hjb_rollout_run_campaign refuse.  In the LDS form the node block (thresholds, the live inputs' eps rows,
+ * the base axes' rows, node index fastest) is staged behind knots, 1/dx and u_table; the 32 KiB rule applies to the sum.
+ * Out of scope: lookahead controllers that believe or fly actuator noise; histogram and paired campaigns on this plant; the
+ * integrated plants; a general per-label table d[a][w][l] under HJB_LOOKUP_NEAREST. */
+int32_t hjb_rollout_set_actuator_noise(void *rollout, int32_t n_nodes, const double *eps, const double *base, const double *weights);
+int32_t hjb_rollout_run_actuator(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                 const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost,
+                                 double *X_path, double *U_path, double *W_path, double *device_ms);
+int32_t hjb_rollout_run_actuator_campaign(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step,
+                                          int64_t n_starts, int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
+                                          const double *threshold, const double *tol, double *stats, double *device_ms);
 
 /* ---- greedy rollouts: the affine loop flown by one-step lookahead on a stored cost-to-go (kernel K26) ---------------------------
  *   u_k(x) = argmin_l  g(x, u_l) + J_{k+1}(A x + B u_l + c)   over the rows u_l of the object's u_table, at the state visited

@@ -141,6 +141,16 @@ int32_t hjb_rollout_greedy_host(int32_t D, const int32_t *n, const double *knots
                                 const double *r, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
                                 const int32_t *value_plane_of_step, int64_t n_traj, const double *X0, double *X_final,
                                 double *cost, double *X_path, double *U_path, double *L_path, double *V_path);
+/* the affine loop under actuator noise (kernels K33, K34): x+ = A x + B (u (1 + eps_w)) + c + base_w; eps [n_u, n_nodes] and base
+ * [D, n_nodes] (or NULL) column-major, weights as hjb_rollout_set_noise's (n_nodes 0 detaches); hjb_rollout_run_noisy's and
+ * hjb_rollout_run_campaign's arguments, streams and statistics (hjbdp.h); usage: matlab/Dynamic_Solver_hjbdp_actuator_cost_map.m */
+int32_t hjb_rollout_set_actuator_noise(void *rollout, int32_t n_nodes, const double *eps, const double *base, const double *weights);
+int32_t hjb_rollout_run_actuator(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                 const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost,
+                                 double *X_path, double *U_path, double *W_path, double *device_ms);
+int32_t hjb_rollout_run_actuator_campaign(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step,
+                                          int64_t n_starts, int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
+                                          const double *threshold, const double *tol, double *stats, double *device_ms);
 /* the same loop with hjb_set_disturbance's E_w / max_w inside every candidate (kernel K27): a lookahead node set in
  * hjb_set_disturbance's layout (mode 0 = expect, 1 = worst; n_nodes 0 detaches), flown on a nominal plant (fly_noise 0) or under
  * hjb_rollout_set_noise's set (fly_noise 1, W_path the drawn nodes); the host twin needs no device and no object (hjbdp.h); usage:

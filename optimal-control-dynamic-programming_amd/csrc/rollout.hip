@@ -7,6 +7,9 @@
 // Beside the model an object may hold a noise node set (hjb_rollout_set_noise): hjb_rollout_run_noisy (K25,
 // kernels_rollout_noisy.h / rollout_noisy.hip) flies the affine loop under it, and no other run function reads it.  The sampler's
 // host twins hjb_rollout_noise_table / hjb_rollout_noise_draw (hjbdp_noise.h) need no device.
+// And an actuator node set (hjb_rollout_set_actuator_noise): hjb_rollout_run_actuator (K33, kernels_rollout_actuator.h /
+// rollout_actuator.hip) flies the affine loop under u (1 + eps_w) (+ an additive base) on K25's streams, and
+// hjb_rollout_run_actuator_campaign (K34, rollout_campaign_host.hip) reduces those flights; no other run function reads it.
 // And it may hold value planes (hjb_rollout_set_values): hjb_rollout_run_greedy (K26, kernels_rollout_greedy.h /
 // rollout_greedy.hip) flies the affine loop by one-step lookahead on them, and no other run function reads them.  Its host twin
 // hjb_rollout_greedy_host (hjbdp_greedy.h) needs no device and no object.
@@ -33,6 +36,7 @@ namespace {
 void release(Rollout *ro) {
     ro->att.reset();
     ro->noise.reset();
+    ro->actuator.reset();
     ro->values.reset();
     ro->look.reset();
     ro->data.reset();
@@ -254,6 +258,12 @@ int check_streams(Rollout *ro, const char *who, int64_t n_traj, int64_t first_st
 
 size_t noisy_lds(const Rollout *ro, bool *on) {
     const size_t lds = (size_t)(2 * (int64_t)ro->R.n_knots + (int64_t)ro->R.n_labels * ro->R.n_u + ro->N.n_tab) * sizeof(double);
+    *on = ro->lds && lds <= kLdsMax;
+    return lds;
+}
+
+size_t actuator_lds(const Rollout *ro, bool *on) {
+    const size_t lds = (size_t)(2 * (int64_t)ro->R.n_knots + (int64_t)ro->R.n_labels * ro->R.n_u + ro->Act.n_tab) * sizeof(double);
     *on = ro->lds && lds <= kLdsMax;
     return lds;
 }
@@ -673,6 +683,86 @@ int32_t hjb_rollout_run_noisy(void *rollout, int32_t method, int32_t n_steps, co
             const size_t lds = noisy_lds(ro, &lds_on);
             return launch_rollout_noisy(ro->idx_bytes, method, lds_on, plan.W, c.R, noise_of_chunk(ro, c, seed, first_stream, c.path[2]), c.nc, lds,
                                         c.st, c.X0, c.Xf, c.cost, c.path[0], c.path[1]);
+        });
+}
+
+int32_t hjb_rollout_set_actuator_noise(void *rollout, int32_t n_nodes, const double *eps, const double *base, const double *weights) {
+    Rollout *ro = (Rollout *)rollout;
+    const char *const who = "hjb_rollout_set_actuator_noise";
+    // hjb_rollout_set_noise's shape: the arguments that need no object first, then the object; every refusal before any device work
+    if (n_nodes < 0 || n_nodes > HJB_DIST_MAX_NODES) return rfail(ro, HJB_E_INVALID, "%s: n_nodes=%d not in 0..%d", who, n_nodes, HJB_DIST_MAX_NODES);
+    if (n_nodes > 0 && !eps) return rfail(ro, HJB_E_INVALID, "%s: null eps with n_nodes=%d", who, n_nodes);
+    if (const int bad = n_nodes > 0 ? check_weights(ro, who, n_nodes, weights) : HJB_OK) return bad;
+    if (!ro) return rfail(nullptr, HJB_E_INVALID, "%s: null handle", who);
+    std::lock_guard<std::mutex> g(ro->mu);
+    const int D = ro->D, nu = ro->R.n_u;
+    int live = 0, base_mask = 0;
+    for (int w = 0; w < n_nodes; ++w)
+        for (int j = 0; j < nu; ++j) {
+            const double e = eps[j + (int64_t)nu * w];
+            if (!std::isfinite(e)) return rfail(ro, HJB_E_INVALID, "%s: eps of input %d, node %d is not finite", who, j, w);
+            if (e != 0.0) live |= 1 << j;
+        }
+    for (int w = 0; base && w < n_nodes; ++w)
+        for (int a = 0; a < D; ++a) {
+            const double d = base[a + (int64_t)D * w];
+            if (!std::isfinite(d)) return rfail(ro, HJB_E_INVALID, "%s: base of axis %d, node %d is not finite", who, a, w);
+            if (d != 0.0) base_mask |= 1 << a;
+        }
+    // the node block as K33 reads it: [T (W - 1) | eps rows of the live inputs | base rows of the base axes], node index fastest
+    int n_rows = 0;
+    for (int j = 0; j < nu; ++j) n_rows += (live >> j) & 1;
+    for (int a = 0; a < D; ++a) n_rows += (base_mask >> a) & 1;
+    std::vector<double> tab((size_t)std::max(n_nodes - 1, 0) + (size_t)n_nodes * n_rows);
+    if (n_nodes > 0) {
+        (void)noise_table(n_nodes, weights, tab.data());
+        double *row = tab.data() + (n_nodes - 1);
+        for (int j = 0; j < nu; ++j) {
+            if (!((live >> j) & 1)) continue;
+            for (int w = 0; w < n_nodes; ++w) row[w] = eps[j + (int64_t)nu * w];
+            row += n_nodes;
+        }
+        for (int a = 0; a < D; ++a) {
+            if (!((base_mask >> a) & 1)) continue;
+            for (int w = 0; w < n_nodes; ++w) row[w] = base[a + (int64_t)D * w];
+            row += n_nodes;
+        }
+    }
+    const void *d = nullptr;
+    if (const int st = attach_table(ro, who, tab.data(), tab.size() * sizeof(double), n_nodes > 0, ro->actuator, &d)) return st;
+    ro->Act = DActuator{};
+    ro->Act.n_nodes = n_nodes;
+    ro->Act.live = live;
+    ro->Act.base_mask = base_mask;
+    ro->Act.n_tab = (int32_t)tab.size();
+    ro->Act.tab = (const double *)d;
+    return HJB_OK;
+}
+
+int32_t hjb_rollout_run_actuator(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
+                                 const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost, double *X_path,
+                                 double *U_path, double *W_path, double *device_ms) {
+    const Rollout *ro = (const Rollout *)rollout;
+    const char *const who = "hjb_rollout_run_actuator";
+    ChunkPlan plan = affine_plan(ro, who, n_steps, plane_of_step, n_traj, X0, X_final, cost, X_path, U_path, device_ms);
+    plan.path[2] = {W_path, 1, n_steps};
+    return run_call(
+        rollout, plan, [&](Rollout *o) { return check_streams(o, who, n_traj, first_stream); },
+        [&](Rollout *o) {
+            if (const int bad = check_run(o, kModelAffine, method, n_steps, plane_of_step, n_traj)) return bad;
+            return o->Act.n_nodes < 1 ? rfail(o, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_actuator_noise", who) : HJB_OK;
+        },
+        nullptr,
+        [&](const Chunk &c) {
+            bool lds_on;
+            const size_t lds = actuator_lds(ro, &lds_on);
+            DActuator N = ro->Act;                            // the call's seed, the chunk's first stream and its W_path, as noise_of_chunk
+            N.seed = seed;
+            N.first = (uint64_t)first_stream + (uint64_t)c.i0;
+            N.Wp = c.path[2];
+            N.terms = actuator_terms(plan.W, c.R.n_u, N.live, c.R.B);       // B of the model in effect at this run
+            return launch_rollout_actuator(ro->idx_bytes, method, lds_on, plan.W, c.R, N, c.nc, lds, c.st, c.X0, c.Xf, c.cost, c.path[0],
+                                           c.path[1]);
         });
 }
 

@@ -6,9 +6,12 @@
 // and walks the call's block list in launches of at most option "chunk" lanes.  run_chunks is not used: its record and
 // its transfers are per trajectory, which is what a campaign does away with.  What a plain call holds on the device is
 // [D + 1 + 8, n_starts] doubles and 8 doubles per block of a launch; nothing has a dimension of n_starts * n_samples.
+// hjb_rollout_run_actuator_campaign (K34, kernels_rollout_actuator_campaign.h / rollout_actuator_campaign.hip) is the same frame
+// and loop on the actuator set's plant (CampaignPlan::actuator).
 // The host reduce runs hjbdp_campaign.h's functions in a plain loop, with no device.  No kernel is instantiated in this unit.
 #include "rollout_host.h"
 #include "kernels_rollout_campaign.h"
+#include "kernels_rollout_actuator_campaign.h"
 
 using namespace hjbhost;
 
@@ -136,7 +139,12 @@ int run_campaign_launches(Rollout *ro, const CampaignCall &call, const CampaignP
         c.C[r] = Cp;
         c.C[r].partials = dpart[r];
     }
-    const size_t lds = c.lds = noisy_lds(ro, &c.lds_on);
+    c.Na = ro->Act;                                           // read by an actuator call alone (K34)
+    c.Na.seed = call.seed;
+    c.Na.first = (uint64_t)call.first_stream;
+    c.Na.Wp = nullptr;
+    c.Na.terms = actuator_terms(D, ro->R.n_u, c.Na.live, ro->R.B);  // B of the model in effect at this run
+    const size_t lds = c.lds = plan.actuator ? actuator_lds(ro, &c.lds_on) : noisy_lds(ro, &c.lds_on);
     if (hist) {                                               // the accumulation form and its LDS bytes, with the tables' placement
         c.lds = campaign_hist_form(Cp.G, hist->n_bins, ro->lds, lds, kLdsMax, &c.lds_on, &c.H);
         c.H.range = (const double *)drange;
@@ -222,6 +230,27 @@ int32_t hjb_rollout_run_campaign(void *rollout, int32_t method, int32_t n_steps,
         [&](const CampaignLaunch &c) {
             const Rollout *ro = (const Rollout *)rollout;
             return launch_rollout_campaign(ro->idx_bytes, method, c.lds_on, ro->D, c.R[0], c.N, c.C[0], c.lds, c.st, c.X0, c.stats[0]);
+        });
+}
+
+// K34: hjb_rollout_run_campaign's frame and loop on the actuator set's plant (kernels_rollout_actuator_campaign.h)
+int32_t hjb_rollout_run_actuator_campaign(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_starts,
+                                          int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream, const double *threshold,
+                                          const double *tol, double *stats, double *device_ms) {
+    const CampaignCall call{"hjb_rollout_run_actuator_campaign", n_steps, n_starts, n_samples, X0, seed, first_stream, threshold, tol, device_ms};
+    CampaignPlan plan;
+    plan.stats[0] = stats;
+    plan.planes[0] = plane_of_step;
+    plan.actuator = true;
+    return run_campaign_call(
+        rollout, call, plan, nullptr,
+        [&](Rollout *ro) {
+            if (const int bad = check_run(ro, kModelAffine, method, n_steps, plane_of_step, n_starts)) return bad;
+            return ro->Act.n_nodes < 1 ? rfail(ro, HJB_E_INVALID, "rollout: %s before hjb_rollout_set_actuator_noise", call.who) : HJB_OK;
+        },
+        [&](const CampaignLaunch &c) {
+            const Rollout *ro = (const Rollout *)rollout;
+            return launch_rollout_actuator_campaign(ro->idx_bytes, method, c.lds_on, ro->D, c.R[0], c.Na, c.C[0], c.lds, c.st, c.X0, c.stats[0]);
         });
 }
 

@@ -7,10 +7,11 @@
 // trajectories, what is refused per trajectory - then the chunk loop.  An entry point is its hooks, its plan and its launch.
 #pragma once
 #include "hjbdp_host.h"
-// the records an object holds: DRollout, DAttitude, DNoise, DPaChan (a unit includes the other kernel headers whose launch it calls)
+// the records an object holds: DRollout, DAttitude, DNoise, DActuator, DPaChan (a unit includes the other kernel headers whose launch it calls)
 #include "kernels_rollout.h"
 #include "kernels_rollout_attitude.h"
 #include "kernels_rollout_noisy.h"
+#include "kernels_rollout_actuator.h"
 #include "kernels_rollout_campaign.h"
 #include "kernels_rollout_campaign_hist.h"
 #include "kernels_rollout_pos_att.h"
@@ -62,6 +63,10 @@ struct Rollout {
     // _run_lookahead (fly_noise) and _run_lookahead_campaign
     DNoise N{};
     std::shared_ptr<DevData> noise;     // N.tab: thresholds, then the masked axes' offsets
+    // the actuator node set (hjb_rollout_set_actuator_noise): Act.n_nodes > 0 while one is set; read by hjb_rollout_run_actuator and
+    // _run_actuator_campaign alone
+    hjb::DActuator Act{};
+    std::shared_ptr<DevData> actuator;  // Act.tab: thresholds, then the live inputs' eps rows, then the base axes' rows
     // the value planes (hjb_rollout_set_values): val_planes > 0 while some are set; read by hjb_rollout_run_greedy, _run_lookahead and
     // _run_lookahead_campaign
     std::shared_ptr<DevData> values;
@@ -141,6 +146,9 @@ int check_streams(Rollout *ro, const char *who, int64_t n_traj, int64_t first_st
 // [knots | 1/dx | u_table] and the node block of its noise set together, staged (*on) when option "lds" is on and they fit kLdsMax.
 // -> the bytes
 size_t noisy_lds(const Rollout *ro, bool *on);
+// ... and the same rule for the actuator flights (hjb_rollout_run_actuator, _run_actuator_campaign): the tables and the node block of
+// the actuator set together
+size_t actuator_lds(const Rollout *ro, bool *on);
 
 // What the campaigns (hjb_rollout_run_campaign, hjb_rollout_run_lookahead_campaign, their host forms) refuse of their sizes, in
 // `who`'s name: n_samples < 1, n_starts * n_samples overflowing; and of their bounds: a NaN threshold, a NaN or negative tol
@@ -157,10 +165,13 @@ int check_campaign_streams(Rollout *ro, const char *who, int64_t n_starts, int64
 // and every record's stats [8, n_starts] on the device.  In a histogram call (K30) lds is the launch's dynamic LDS bytes and
 // lds_on the tables' placement as campaign_hist_form decided them, and H the histogram's record; H.hist is null otherwise.  In a
 // pair call (K31) pair_cost [lanes] doubles and pair_left [lanes] bytes are the pair scratch, lanes = nb_max * G of a launch and
-// never n_starts * M, and Lg HJB_PAIR_GREEDY's set (one zero node of weight 1; Lg.tab null unless a side is greedy).
+// never n_starts * M, and Lg HJB_PAIR_GREEDY's set (one zero node of weight 1; Lg.tab null unless a side is greedy).  In an actuator
+// call (K34, CampaignPlan::actuator) Na is the actuator set with the call's seed and first stream and lds / lds_on are
+// actuator_lds'; N is then not read.
 struct CampaignLaunch {
     hjb::DRollout R[2];
     hjb::DNoise N;
+    hjb::DActuator Na;
     hjb::DCampaign C[3];
     size_t lds;
     bool lds_on;
@@ -206,6 +217,7 @@ struct CampaignPlan {
     const int32_t *planes[2] = {};  // [n_steps] each, on the host
     const CampaignHistCall *hist = nullptr;
     bool pair_scratch = false, greedy = false;
+    bool actuator = false;          // K34: the plant is the actuator set (CampaignLaunch::Na)
 };
 
 // The device side of a campaign call whose arguments have been checked (n_starts >= 1; rollout_campaign_host.hip), the one loop of

@@ -243,6 +243,12 @@ SYMBOLS = {
                                              C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 4),
     "hjb_rollout_campaign_reduce": (C.c_int32, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.POINTER(C.c_uint8)] + [C.POINTER(C.c_double)] * 3),
+    # the affine loop under actuator noise (x+ = A x + B (u (1 + eps_w)) + c + base_w), and its campaign
+    "hjb_rollout_set_actuator_noise": (C.c_int32, [C.c_void_p, C.c_int32] + [C.POINTER(C.c_double)] * 3),
+    "hjb_rollout_run_actuator": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_double),
+                                             C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 6),
+    "hjb_rollout_run_actuator_campaign": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
+                                                      C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 4),
     # the affine loop flown by one-step lookahead on stored value planes, and its host twin
     "hjb_rollout_set_values": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "hjb_rollout_run_greedy": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64] + [C.POINTER(C.c_double)] * 8),

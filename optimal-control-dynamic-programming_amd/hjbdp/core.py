@@ -579,6 +579,61 @@ class Rollout(_Handle):
                          ms=False)
 
 
+class ActuatorRollout(Rollout):
+    """A Rollout that can also be flown under ACTUATOR noise (hjb_rollout_set_actuator_noise, hjb_rollout_run_actuator,
+    hjb_rollout_run_actuator_campaign): the plant delivers u * (1 + eps_w) instead of the commanded u.  Everything Rollout has
+    is here unchanged - set_noise, run, run_noisy, run_campaign of an object that holds an actuator set give the bits they gave -
+    and the same C object is behind both.  A class of its own because Rollout's set of run methods is a pinned interface
+    (tests/test_rollout_run_marshalling.py holds it to its nine); this one's marshalling is tests/test_actuator_rollout_refs.py's."""
+
+    def set_actuator_noise(self, eps, weights=None, base=None):
+        """An actuator node set for run_actuator (hjb_rollout_set_actuator_noise): the plant delivers u * (1 + eps_w) instead of
+        the commanded u.  eps [W] (one relative error for every input) or [W, n_u] - the shapes actuator_nodes takes; weights [W]
+        as set_noise's; base: an optional additive node set [D, W] on the same nodes.  So the set a policy was designed under
+        (ProblemSpec(control_disturbance=actuator_nodes(B, u_table, eps, weights, base))) is the set it is flown under.  A property
+        of the object, independent of set_noise's set and of the model; run_actuator and run_actuator_campaign alone read it."""
+        e = np.array(eps, dtype=np.float64)
+        if e.ndim == 1:
+            e = np.repeat(e[:, None], self.n_u, axis=1)
+        if e.ndim != 2 or e.shape[1] != self.n_u or not (1 <= e.shape[0] <= _abi.HJB_DIST_MAX_NODES):
+            raise ValueError("eps must be [W] or [W, n_u=%d] with 1 <= W <= %d, got %r" % (self.n_u, _abi.HJB_DIST_MAX_NODES, e.shape))
+        W = e.shape[0]
+        b = None
+        if base is not None:
+            b = np.array(base, dtype=np.float64, ndmin=2)
+            if b.shape != (self.D, W):
+                raise ValueError("base must be [D=%d, W=%d], got %r" % (self.D, W, b.shape))
+            b = np.ascontiguousarray(b.reshape(-1, order="F"))
+        w = None
+        if weights is not None:
+            w = np.array(weights, dtype=np.float64).reshape(-1)
+            if w.shape != (W,):
+                raise ValueError("weights must be [W=%d], got %r" % (W, w.shape))
+        ec = np.ascontiguousarray(e.reshape(-1))              # [W, n_u] row-major is [n_u, W] column-major
+        self._check(self.lib.hjb_rollout_set_actuator_noise(self._ro, W, _f64p(ec), _f64p(b), _f64p(w)))
+
+    def clear_actuator_noise(self):
+        """Detach the actuator node set (hjb_rollout_set_actuator_noise with n_nodes = 0)."""
+        self._check(self.lib.hjb_rollout_set_actuator_noise(self._ro, 0, None, None, None))
+
+    def run_actuator(self, X0, plane_of_step, seed=0, first_stream=0, method="linear", keep_path=False):
+        """run under the actuator node set of set_actuator_noise (hjb_rollout_run_actuator): run_noisy's loop, stream numbering
+        and sampler, with x+ = A x + B (u (1 + eps_w)) + c + base_w at the drawn node w; the cost is charged on the commanded u.
+        Returns run_noisy's dict: U_path holds the commanded controls, W_path the drawn nodes."""
+        return self._run(self.lib.hjb_rollout_run_actuator, (_LOOKUP[method],), X0, self.D, plane_of_step, "plane_of_step", keep_path,
+                         (("X_path", self.D, 1), ("U_path", self.n_u, 0), ("W_path", 1, 0)),
+                         mid=(int(seed) & (2 ** 64 - 1), int(first_stream)))
+
+    def run_actuator_campaign(self, X0, plane_of_step, n_samples, seed=0, first_stream=0, method="linear", cost_threshold=None,
+                              settle_tol=None):
+        """run_campaign on the plant of set_actuator_noise (hjb_rollout_run_actuator_campaign): sample m of start s is
+        run_actuator's trajectory on stream first_stream + s * n_samples + m of `seed`, reduced per start on the GPU; nothing of
+        length n_starts * n_samples exists on either side.  Returns the dict of campaign_reduce plus device_ms."""
+        ps = _int32_vector(plane_of_step, "plane_of_step")
+        return self._campaign(self.lib.hjb_rollout_run_actuator_campaign, (_LOOKUP[method], int(ps.size), _i32p(ps)), X0, n_samples, seed,
+                              first_stream, cost_threshold, settle_tol)
+
+
 def noise_thresholds(weights, n_nodes=None):
     """The sampler's W - 1 thresholds of a weight vector (hjb_rollout_noise_table; no device): weights [W], or None with
     n_nodes = W for equal weights.  Node w is drawn when T[w-1] <= word < T[w] (T[-1] = 0, T[W-1] = 2^32)."""

@@ -231,13 +231,16 @@ class Dynamic_Solver:
             return np.arange(first, n_st + first, dtype=np.int32)
         raise ValueError("mode must be 'Nssu' or 'ssu'")
 
-    def _rollout(self, who, values=False, lookahead=False, noise=False):
+    def _rollout(self, who, values=False, lookahead=False, noise=False, actuator=False):
         """What `who` flies on: refuses at once what it cannot fly - no run() yet, no self.disturbance where the flight needs one,
         an unknown `lookahead` - and returns a context manager that opens an hjbdp.Rollout on the stored policy and closes it on
-        the way out, whatever happens.  On the open object, in this order: set_model; set_values(J_star) with `values`;
+        the way out, whatever happens (an hjbdp.ActuatorRollout with `actuator`).  On the open object, in this order: set_model; set_values(J_star) with `values`;
         set_lookahead unless `lookahead` is False - 'disturbed': self.disturbance's set in its own mode, 'nominal': one zero node of weight
-        1; set_noise(self.disturbance's nodes) with `noise`."""
-        from .core import Rollout
+        1; set_noise(self.disturbance's nodes) with `noise`; set_actuator_noise(self.actuator_noise's eps and weights) with
+        `actuator` (the flights of get_actuator_paths and its campaign forms, which need self.actuator_noise)."""
+        from .core import ActuatorRollout, Rollout
+        if actuator and self.actuator_noise is None:
+            raise RuntimeError("%s needs self.actuator_noise = (eps [W], weights or None, mode)" % who)
         if self.u_star_idxs is None or (values and self.J_star is None):
             raise RuntimeError("run() first")
         if (lookahead is not False or noise) and self.actuator_noise is not None:
@@ -252,7 +255,7 @@ class Dynamic_Solver:
         def opened():
             s_r = np.asarray(self.s_r, dtype=np.float64)
             u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
-            with Rollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
+            with (ActuatorRollout if actuator else Rollout)([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
                 ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
                 if values:
                     ro.set_values(self.J_star)
@@ -262,6 +265,8 @@ class Dynamic_Solver:
                     ro.set_lookahead(np.zeros((self.S, 1)), [1.0], "expect")
                 if noise:
                     ro.set_noise(self.disturbance[0], self.disturbance[1])
+                if actuator:
+                    ro.set_actuator_noise(self.actuator_noise[0], self.actuator_noise[1] if len(self.actuator_noise) > 1 else None)
                 yield ro
         return opened()
 
@@ -288,6 +293,49 @@ class Dynamic_Solver:
         the map's mean (and, for a 'worst' set, its max) is what n_samples flights from that node paid."""
         return self._grid_map(self.get_noisy_cost_statistics(self._grid_starts(), n_samples, seed=seed, mode=mode, ssu_num=ssu_num,
                                                              method=method, cost_threshold=cost_threshold, settle_tol=settle_tol))
+
+    def get_actuator_paths(self, X0s, n_samples, seed=0, mode="Nssu", ssu_num=1, method="linear"):
+        """The stored policy flown under sampled ACTUATOR noise, on the GPU (hjbdp.ActuatorRollout.run_actuator): every start of X0s
+        [S, n] n_samples times under self.actuator_noise - x+ = A x + B u (1 + eps_w), node w drawn per step with the set's
+        weights; a 'worst' set (no weights) is sampled uniformly.  Sample j of start i runs on stream i * n_samples + j of `seed`
+        (get_noisy_paths' numbering).  Returns the closed-loop costs [n, n_samples] (on the commanded controls and the states
+        actually visited) and leaves their mean, standard deviation and maximum per start in self.actuator_cost_mean / _std /
+        _max [n].  Beside policy_cost() under the same self.actuator_noise this is "promised against paid" in two calls."""
+        opening = self._rollout("get_actuator_paths", actuator=True)
+        planes = self._stage_planes(mode, ssu_num)
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError("n_samples must be at least 1")
+        X0s = np.asarray(X0s, dtype=np.float64).reshape(self.S, -1)
+        n = X0s.shape[1]
+        with opening as ro:
+            out = ro.run_actuator(np.repeat(X0s, n_samples, axis=1), planes, seed=seed, first_stream=0, method=method)
+        cost = out["cost"].reshape(n, n_samples)
+        self.actuator_cost_mean, self.actuator_cost_std, self.actuator_cost_max = cost.mean(axis=1), cost.std(axis=1), cost.max(axis=1)
+        self.actuator_paths_ms = out["device_ms"]
+        return cost
+
+    def get_actuator_cost_statistics(self, X0s, n_samples, seed=0, mode="Nssu", ssu_num=1, method="linear", cost_threshold=None,
+                                     settle_tol=None):
+        """get_actuator_paths' flights reduced per start on the GPU (hjbdp.ActuatorRollout.run_actuator_campaign): the same streams, so
+        the same costs, and nothing of length n * n_samples exists on the host or on the device.  Returns
+        get_noisy_cost_statistics' dict, one entry per start."""
+        if int(n_samples) < 1:
+            raise ValueError("n_samples must be at least 1")
+        opening = self._rollout("get_actuator_cost_statistics", actuator=True)
+        planes = self._stage_planes(mode, ssu_num)
+        with opening as ro:
+            return ro.run_actuator_campaign(np.asarray(X0s, dtype=np.float64).reshape(self.S, -1), planes, int(n_samples), seed=seed,
+                                            first_stream=0, method=method, cost_threshold=cost_threshold, settle_tol=settle_tol)
+
+    def actuator_cost_map(self, n_samples, seed=0, mode="Nssu", ssu_num=1, method="linear", cost_threshold=None, settle_tol=None):
+        """get_actuator_cost_statistics at every grid node: noisy_cost_map's shape and stream numbering - each entry [dx, dx]
+        (stats [dx, dx, 8]), node (i, j) = (s_r[i], s_r[j]) flown from stream (i + dx * j) * n_samples on - under
+        self.actuator_noise's eps and weights (a 'worst' set is sampled uniformly).  Beside policy_cost() this is "promised
+        against paid" over the whole grid for the actuator-noise design: plane 0 of policy_cost() is the promise, the map's mean
+        (for a 'worst' set its max) is what n_samples flights paid."""
+        return self._grid_map(self.get_actuator_cost_statistics(self._grid_starts(), n_samples, seed=seed, mode=mode, ssu_num=ssu_num,
+                                                                method=method, cost_threshold=cost_threshold, settle_tol=settle_tol))
 
     def get_greedy_paths(self, X0s, mode="Nssu", ssu_num=1):
         """The closed loop of the cost-to-go itself, on the GPU (hjbdp.Rollout.run_greedy): at every step the control of U_mesh

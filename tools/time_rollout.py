@@ -33,8 +33,12 @@ Two cases, one JSON line:
   (o) campaign_pair: the paired campaign (K31, hjb_rollout_run_campaign_pair: labels 'linear' against the disturbed lookahead) beside
       K28 and K29 on the same starts, see case_campaign_pair; alone, it also writes its line to
       profiles/rollout_campaign_pair_time.json.
+  (p) kirk_actuator: the actuator-noise rollout (K33, hjb_rollout_run_actuator) beside K25 on the same object, starts and node
+      count, see case_kirk_actuator; alone, it also writes its line to profiles/rollout_actuator_time.json.
+  (q) actuator_campaign: the actuator-noise campaign (K34, hjb_rollout_run_actuator_campaign) beside K28 at case_campaign's two
+      shapes, see case_actuator_campaign; alone, it also writes its line to profiles/rollout_actuator_campaign_time.json.
 Rates are trajectory-steps per second from device_ms (kernel time) of a second run of the same shape (the first is the warm-up).
-    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy,lookahead,campaign,lookahead_campaign,campaign_hist,campaign_pair] [--out FILE]
+    python tools/time_rollout.py [--no-host] [--cases kirk,pos_att,attitude,pos_att_loop,position_loop,attitude_simplified_loop,attitude_linear_loop,pos_att_faults,kirk_noisy,greedy,lookahead,campaign,lookahead_campaign,campaign_hist,campaign_pair,kirk_actuator,actuator_campaign] [--out FILE]
 """
 from __future__ import annotations
 
@@ -945,6 +949,117 @@ def case_campaign_pair(host=True, n_starts=1 << 14, n_samples=64):
     return res
 
 
+def _kirk_actuator_problem():
+    """case_kirk_noisy's problem and 9-node Gauss-Hermite set, and the actuator set on the same nodes and weights: eps = the
+    axis-0 nodes scaled to sigma = 0.1"""
+    import hjbdp
+    ds = hjbdp.Dynamic_Solver(precision="double")
+    ds.N, ds.dx, ds.du = 130, 35, 100
+    ds.run()
+    off, w = hjbdp.gaussian_nodes([0.02, 0.05], order=3)
+    return ds, off, w, off[0] * (0.1 / 0.02)
+
+
+def case_kirk_actuator(host=True, n_traj=1000000):
+    """(p) kirk_actuator: case_kirk_noisy's problem, starts and 9 Gauss-Hermite nodes (10^6 trajectories x 129 steps, 'linear'),
+    K33 (hjb_rollout_run_actuator under eps = the nodes scaled to sigma = 0.1, same weights) beside K25 (hjb_rollout_run_noisy
+    under case_kirk_noisy's own additive set, unchanged) on one object in one process: the two runs alternate, five rounds after a
+    warm-up round of the same shapes, device_ms of all five listed, the medians and their ratio quoted.  `pass`: K33's kernel time
+    <= 1.05 x K25's in this run, the margin of a same-frame variant against its base - at D = 2, n_u = 1 the step adds three
+    rounded multiplies and reads one eps where K25 reads two offsets.  The two draw the same nodes (one seed).  `host` is not
+    used."""
+    import hjbdp
+    ds, off, w, eps = _kirk_actuator_problem()
+    s_r = np.asarray(ds.s_r, dtype=np.float64)
+    rng = np.random.default_rng(1)
+    X0 = rng.uniform(s_r[0], s_r[-1], size=(2, n_traj))
+    planes = np.arange(ds.N - 1)
+    res = {"grid": "35x35", "planes": int(ds.N - 1), "method": "linear", "labels": "int32", "n_traj": int(n_traj), "n_steps": int(ds.N - 1),
+           "nodes": int(off.shape[1]), "noise": "K25: gaussian_nodes(sigma = (0.02, 0.05), order 3) on both axes; K33: eps = its axis-0 "
+           "nodes scaled to sigma = 0.1, the same weights, no base",
+           "timing": "device_ms: event times around the launches; the two runs alternate in one process, 5 rounds after a warm-up round"}
+    ms = {"k25": [], "k33": []}
+    with hjbdp.ActuatorRollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro:
+        ro.set_model(ds.A, ds.B, q=np.diag(ds.Q), r=[ds.R])
+        ro.set_noise(off, w)
+        ro.set_actuator_noise(eps, w)
+        for rnd in range(6):
+            b = ro.run_noisy(X0, planes, seed=1, method="linear")
+            a = ro.run_actuator(X0, planes, seed=1, method="linear")
+            if rnd:                                               # round 0 is the warm-up
+                ms["k25"].append(b["device_ms"])
+                ms["k33"].append(a["device_ms"])
+        ok = np.isfinite(a["cost"]) & np.isfinite(b["cost"])      # starts far from the origin leave the grid on Kirk's unstable loop
+        res["finite_in_both"] = int(ok.sum())
+        res["additive_cost_mean"], res["actuator_cost_mean"] = float(np.mean(b["cost"][ok])), float(np.mean(a["cost"][ok]))
+        few = slice(0, 4096)
+        res["same_nodes_drawn"] = bool(np.array_equal(ro.run_noisy(X0[:, few], planes, seed=1, keep_path=True)["W_path"],
+                                                      ro.run_actuator(X0[:, few], planes, seed=1, keep_path=True)["W_path"]))
+    for key in ms:
+        med = float(np.median(ms[key]))
+        res[key] = {"device_ms": [round(t, 3) for t in ms[key]], "device_ms_median": round(med, 3),
+                    "traj_steps_per_s": n_traj * (ds.N - 1) / (med * 1e-3)}
+    res["k33_over_k25_measured"] = res["k33"]["device_ms_median"] / res["k25"]["device_ms_median"]
+    res["bound"] = 1.05
+    res["pass"] = bool(res["k33_over_k25_measured"] <= res["bound"])
+    return res
+
+
+def case_actuator_campaign(host=True, n_starts=1 << 14, n_samples=64):
+    """(q) actuator_campaign: case_campaign's shapes on case_kirk_actuator's two node sets: K34 (hjb_rollout_run_actuator_campaign)
+    beside K28 (hjb_rollout_run_campaign under the additive set, unchanged) on one object in one process.  The two alternate, five
+    rounds after a warm-up round of the same shapes; per round the kernel time (device_ms: rollout and fold kernels) and the
+    whole call's wall time of both, the medians and their ratios quoted.  `pass`: K34's kernel time <= 1.05 x K28's at 2^14
+    starts x 64 samples.  The second shape, 8 starts x 2^17 samples, is recorded with no bound, as case_campaign records it.
+    `host` is not used."""
+    import hjbdp
+    ds, off, w, eps = _kirk_actuator_problem()
+    s_r = np.asarray(ds.s_r, dtype=np.float64)
+    rng = np.random.default_rng(1)
+    X0 = rng.uniform(s_r[0], s_r[-1], size=(2, n_starts))
+    planes = np.arange(ds.N - 1)
+    res = {"grid": "35x35", "planes": int(ds.N - 1), "method": "linear", "labels": "int32", "n_steps": int(ds.N - 1),
+           "nodes": int(off.shape[1]), "noise": "K28: gaussian_nodes(sigma = (0.02, 0.05), order 3) on both axes; K34: eps = its axis-0 "
+           "nodes scaled to sigma = 0.1, the same weights, no base",
+           "timing": "device_ms: event times around the launches (rollout and fold kernels); wall_ms: the whole Python call; the two "
+                     "runs alternate in one process, 5 rounds after a warm-up round"}
+    with hjbdp.ActuatorRollout([s_r, s_r], ds.u_star_idxs, np.asarray(ds._U_mesh, dtype=np.float64), index_base=1) as ro:
+        ro.set_model(ds.A, ds.B, q=np.diag(ds.Q), r=[ds.R])
+        ro.set_noise(off, w)
+        ro.set_actuator_noise(eps, w)
+        for name, ns, M in (("many_starts", n_starts, n_samples), ("few_starts", 8, 1 << 17)):
+            X = X0[:, :ns]
+            ms = {"k28": [], "k34": []}
+            wall = {"k28": [], "k34": []}
+            for rnd in range(6):
+                t0 = time.perf_counter()
+                b = ro.run_campaign(X, planes, M, seed=1, method="linear")
+                t1 = time.perf_counter()
+                c = ro.run_actuator_campaign(X, planes, M, seed=1, method="linear")
+                t2 = time.perf_counter()
+                if rnd:                                           # round 0 is the warm-up
+                    ms["k28"].append(b["device_ms"])
+                    ms["k34"].append(c["device_ms"])
+                    wall["k28"].append((t1 - t0) * 1e3)
+                    wall["k34"].append((t2 - t1) * 1e3)
+            one = {"n_starts": int(ns), "n_samples": int(M), "n_traj": int(ns * M), "blocks_per_start": -(-M // 64)}
+            for key in ms:
+                med = float(np.median(ms[key]))
+                one[key] = {"device_ms": [round(t, 3) for t in ms[key]], "device_ms_median": round(med, 3),
+                            "wall_ms": [round(t, 1) for t in wall[key]], "wall_ms_median": round(float(np.median(wall[key])), 1),
+                            "traj_steps_per_s": ns * M * (ds.N - 1) / (med * 1e-3)}
+            one["k34_over_k28_kernel"] = one["k34"]["device_ms_median"] / one["k28"]["device_ms_median"]
+            one["k34_over_k28_wall"] = one["k34"]["wall_ms_median"] / one["k28"]["wall_ms_median"]
+            ok = np.isfinite(b["mean"]) & np.isfinite(c["mean"])
+            one["starts_finite_in_both"] = int(ok.sum())
+            one["additive_mean_of_means"] = float(np.mean(b["mean"][ok])) if ok.any() else None
+            one["actuator_mean_of_means"] = float(np.mean(c["mean"][ok])) if ok.any() else None
+            res[name] = one
+    res["bound"] = 1.05
+    res["pass"] = bool(res["many_starts"]["k34_over_k28_kernel"] <= res["bound"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-host", action="store_true")
@@ -961,7 +1076,8 @@ def main():
                   "attitude_linear_loop": case_attitude_linear_loop, "pos_att_faults": case_pos_att_faults,
                   "kirk_noisy": case_kirk_noisy, "greedy": case_greedy, "lookahead": case_lookahead, "campaign": case_campaign,
                   "lookahead_campaign": case_lookahead_campaign, "campaign_hist": case_campaign_hist,
-                  "campaign_pair": case_campaign_pair}[c](host=not a.no_host)
+                  "campaign_pair": case_campaign_pair, "kirk_actuator": case_kirk_actuator,
+                  "actuator_campaign": case_actuator_campaign}[c](host=not a.no_host)
     print(json.dumps(res))
     if a.cases == "position_loop" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_position_time.json").write_text(json.dumps(res) + "\n")
@@ -985,6 +1101,10 @@ def main():
         (ROOT / "profiles" / "rollout_campaign_hist_time.json").write_text(json.dumps(res) + "\n")
     if a.cases == "campaign_pair" and not a.out:                  # its own record: one line
         (ROOT / "profiles" / "rollout_campaign_pair_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "kirk_actuator" and not a.out:                  # its own record: one line
+        (ROOT / "profiles" / "rollout_actuator_time.json").write_text(json.dumps(res) + "\n")
+    if a.cases == "actuator_campaign" and not a.out:              # its own record: one line
+        (ROOT / "profiles" / "rollout_actuator_campaign_time.json").write_text(json.dumps(res) + "\n")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(res, indent=1) + "\n")
