@@ -269,7 +269,8 @@ int32_t hjb_set_option(hjb_handle h, const char *key, int64_t value);
  * "window_planes" (3 or 4: switch a handle that qualifies between modes 5 / 6 and 2 / 3; same results, tests and timing).
  * read a knob back, plus what the column-sweep kernel (variant 7) settled on: "cs_dpp" (1: one load per corner row, the
  * upper axis-0 neighbour taken from the next lane), "cs_groups", "cs_group_axis", "cs_rows" (corner rows per step of the
- * mid-grid column), "cs_coop" (1: the cooperative form is in effect), "cs_coop_why" (why it does not apply: 0 applies,
+ * mid-grid column), "cs_cost_form" (0 general, 1 state terms + one control term, 2 the same summed in float64; -1 when
+ * another variant runs), "cs_coop" (1: the cooperative form is in effect), "cs_coop_why" (why it does not apply: 0 applies,
  * 1 groups, 2 axis 1 sees the window axis, 3 n0 / storage, 4 cells, 5 window knots, 6 axis-0 knots).  Settable (testing,
  * tuning): "cs_dpp", "cs_coop" (1: eight neighbouring columns share their corner rows through LDS, kernels_colcoop.h;
  * off by default - slower on C4), "cs_xcd_mod" (residue modulus of the column -> XCD assignment: 0/1 contiguous ranges,

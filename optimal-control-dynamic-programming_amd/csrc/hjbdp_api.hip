@@ -524,6 +524,7 @@ int32_t hjb_get_option(hjb_handle hh, const char *key, int64_t *value) {
     else if (!strcmp(key, "cs_coop")) *value = (h->L.variant == 7 && h->L.coop_grid > 0) ? 1 : 0;   // the form in effect
     else if (!strcmp(key, "cs_groups")) *value = h->L.variant == 7 ? h->hcs.ng : 0;
     else if (!strcmp(key, "cs_group_axis")) *value = h->L.variant == 7 ? h->hcs.gax : -1;
+    else if (!strcmp(key, "cs_cost_form")) *value = h->L.variant == 7 ? h->L.cost_form : -1;       // the launch record's: 0 general, 1 usual, 2 usual in float64
     else return fail(h, HJB_E_INVALID, "unknown option '%s'", key);
     return HJB_OK;
 }

@@ -7,7 +7,7 @@ namespace hjbhost {
 // the per-(i2, i3) plan, built once on the host from the variant-5 tables of axes 2 and 3 (tiny: n2 * n3 * nU entries)
 template <typename T>
 bool colsweep_plan(Handle *h, int gax, const std::vector<TabEntry<T>> (&tab)[2], const std::vector<std::vector<T>> &cu,
-                   std::vector<int32_t> &plan, int64_t *rows_total, int *ng_max, std::vector<int32_t> &cells) {
+                   std::vector<int32_t> &plan, int64_t *rows_total, int *ng_max, std::vector<int32_t> &cells, int *mid_rows_out) {
     static_assert(sizeof(T) == 4, "plan words are 32-bit");
     const DParams &P = h->hp;
     const int n2 = P.n[2], n3 = P.n[3], nU = (int)h->nU, wax = 5 - gax;
@@ -122,7 +122,7 @@ bool colsweep_plan(Handle *h, int gax, const std::vector<TabEntry<T>> (&tab)[2],
             }
         }
     }
-    h->cs_rows_mid = mid_rows;
+    *mid_rows_out = mid_rows;       // (the caller keeps the picked axis' count: the plans of both axes are built)
     return true;
 }
 
@@ -400,14 +400,16 @@ int ensure_colsweep(Handle *h) {
     int64_t rows[2] = {0, 0};
     int ngm[2] = {1, 1};
     std::vector<int32_t> cells[2];
-    const bool ok3 = colsweep_plan<T>(h, 3, tab, cu, plan[1], &rows[1], &ngm[1], cells[1]);
-    const bool ok2 = colsweep_plan<T>(h, 2, tab, cu, plan[0], &rows[0], &ngm[0], cells[0]);
+    int mid[2] = {0, 0};
+    const bool ok3 = colsweep_plan<T>(h, 3, tab, cu, plan[1], &rows[1], &ngm[1], cells[1], &mid[1]);
+    const bool ok2 = colsweep_plan<T>(h, 2, tab, cu, plan[0], &rows[0], &ngm[0], cells[0], &mid[0]);
     if (!ok2 && !ok3) return HJB_OK;
     const int pick = (ok3 && (!ok2 || ngm[1] < ngm[0] || (ngm[1] == ngm[0] && rows[1] <= rows[0]))) ? 1 : 0;
     DColSweep &CSh = h->hcs;
     memset(&CSh, 0, sizeof CSh);
     CSh.gax = pick ? 3 : 2;
     CSh.ng = ngm[pick];
+    h->cs_rows_mid = mid[pick];
     CSh.g_bytes = (uint32_t)(P.jstride[CSh.gax] * (int64_t)h->esz);
     CSh.w_bytes = (uint32_t)(P.jstride[5 - CSh.gax] * (int64_t)h->esz);
     {
