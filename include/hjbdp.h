@@ -606,8 +606,9 @@ int32_t hjb_rollout_campaign_reduce(int64_t n_starts, int64_t n_samples, int32_t
  * a weight that is not finite or is negative, or weights that sum to 0; the run functions with no actuator set, and everything
  * hjb_rollout_run_noisy and hjb_rollout_run_campaign refuse.  In the LDS form the node block (thresholds, the live inputs' eps rows,
  * the base axes' rows, node index fastest) is staged behind knots, 1/dx and u_table; the 32 KiB rule applies to the sum.
- * Out of scope: lookahead controllers that believe or fly actuator noise; histogram and paired campaigns on this plant; the
- * integrated plants; a general per-label table d[a][w][l] under HJB_LOOKUP_NEAREST. */
+ * Lookahead controllers that believe and fly actuator noise: hjb_rollout_run_control_lookahead (kernels K35, K36, below).
+ * Out of scope: histogram and paired campaigns on this plant; the integrated plants; a general per-label table d[a][w][l] under
+ * HJB_LOOKUP_NEAREST. */
 int32_t hjb_rollout_set_actuator_noise(void *rollout, int32_t n_nodes, const double *eps, const double *base, const double *weights);
 int32_t hjb_rollout_run_actuator(void *rollout, int32_t method, int32_t n_steps, const int32_t *plane_of_step, int64_t n_traj,
                                  const double *X0, uint64_t seed, int64_t first_stream, double *X_final, double *cost,
@@ -756,6 +757,65 @@ int32_t hjb_rollout_lookahead_campaign_host(int32_t D, const int32_t *n, const d
                                             const double *flight_weights, int64_t n_starts, int64_t n_samples, const double *X0,
                                             uint64_t seed, int64_t first_stream, const double *threshold, const double *tol,
                                             double *stats);
+
+/* ---- lookahead under actuator noise: the value function of hjb_set_control_disturbance flown directly (kernels K35, K36) -----------
+ *   u_k(x) = argmin_l  g(x, u_l) + E_w[ J_{k+1}(A x + B u_l + c + e_w(l)) ]     (HJB_DIST_EXPECT; HJB_DIST_WORST: max_w)
+ * - hjb_rollout_run_lookahead with a node set PER CANDIDATE, the controller that is exactly optimal for the problem
+ * hjb_set_control_disturbance poses, flown on a nominal plant or on hjb_rollout_run_actuator's plant, and its campaign.
+ * hjb_rollout_set_control_lookahead gives the object a per-control lookahead node set: offsets [D, n_nodes, n_controls]
+ * column-major, the argument hjb_set_control_disturbance takes (offsets[a + D * (w + n_nodes * l)]: axis a, node w, 0-based label
+ * l); weights and mode as hjb_rollout_set_lookahead's; n_controls must equal the object's label count (n_labels of
+ * hjb_rollout_create), so that a wrong table is refused instead of read past; n_nodes == 0 detaches (n_controls is then not
+ * read).  The set is a property of its own: hjb_rollout_set_lookahead's set is neither read nor changed by it, and ONLY the two
+ * run functions below read it - every other run function of an object that holds one gives the bits it gave before.
+ * hjb_rollout_run_control_lookahead is hjb_rollout_run_lookahead's contract (steps 1 - 5 above; csrc/hjbdp_ctrl_lookahead.h, shared
+ * by the kernels and the host twin) with one change, the one hjb_set_control_disturbance makes to hjb_set_disturbance's:
+ *   node w of the candidate with 0-based label l: q_aw = xn_a + e[a][w][l] on the masked axes; the mask has bit a set iff some
+ *   (w, l) entry of row a is not +-0; an axis outside the mask is located once per candidate and is not touched by + 0.0.
+ * Every node is evaluated for every candidate, a candidate whose offsets are all zero included.  Step 6, fly_noise = 1 only, is
+ * hjb_rollout_run_actuator's plant with nothing changed, on the chosen label's xn and commanded u under the set of
+ * hjb_rollout_set_actuator_noise: the node w' drawn from stream first_stream + i by hjb_rollout_run_noisy's sampler, ue_j = u_j *
+ * eps[j][w'] for the live inputs, the terms of every axis summed left to right, x+_a = xn_a + n_a; the cost is charged on the
+ * commanded u, U_path holds it, W_path the drawn node; which terms exist is formed from the model in effect at the run.  The
+ * lookahead table is what the controller believes, the actuator set is the plant: two independent properties, which may differ.
+ * So a table that is constant along l is hjb_rollout_run_lookahead under offsets[:, :, 0] bit for bit (fly_noise = 0); one zero
+ * node is hjb_rollout_run_greedy; one step from a grid node under hjb_set_control_disturbance's table returns that backup's label
+ * and (HJB_F64) value; and on an exactly posed lattice problem the flown run equals hjb_rollout_run_actuator of the stored labels.
+ * Arguments, outputs and options: hjb_rollout_run_lookahead's, word for word; fly_noise = 0 is the nominal plant, 1 the actuator
+ * set.  The table [p | for l: e (n_axes x n_nodes)] is read through scalar registers and never staged; in the LDS form the actuator
+ * block is staged behind knots, 1/dx and u_table, the 32 KiB rule applied to the sum.  Option "chunk" changes no bit.
+ * hjb_rollout_control_lookahead_host runs the same functions on the CPU, with no device and no object: hjb_rollout_greedy_host's
+ * arguments, then the per-control set (n_nodes >= 1, n_controls == n_labels), then optionally the plant - nodes [n_traj, n_steps]
+ * (what hjb_rollout_noise_draw writes; NULL: a nominal plant) of the n_flight_nodes actuator nodes eps [n_u, n_flight_nodes] and
+ * base [D, n_flight_nodes] (or NULL), hjb_rollout_set_actuator_noise's arguments.  Its L_path holds the 0-based label.
+ * hjb_rollout_run_control_lookahead_campaign is hjb_rollout_run_lookahead_campaign's contract with the flown run above in the place
+ * of hjb_rollout_run_lookahead: sample m of start s flies stream first_stream + s*M + m - the stream
+ * hjb_rollout_run_actuator_campaign gives the same (s, m), so a label campaign on the actuator plant and this one fly common random
+ * numbers; the statistics are bit for bit hjb_rollout_campaign_reduce of hjb_rollout_run_control_lookahead's own outputs; no array
+ * has a dimension of n_starts * n_samples; options "chunk" and "lds" change no bit.
+ * Refused before any device work, outputs untouched (text: hjb_rollout_last_error) - HJB_E_INVALID: everything
+ * hjb_rollout_set_lookahead refuses of mode, n_nodes, offsets and weights; n_controls < 0 or other than the label count; an entry
+ * that is not finite (named by axis, node and control); the run functions with no per-control set, with fly_noise = 1 (the campaign:
+ * always) and no actuator set, and everything hjb_rollout_run_lookahead and hjb_rollout_run_lookahead_campaign refuse of the other
+ * arguments.  HJB_E_UNSUPPORTED: D * n_nodes * n_controls over HJB_CTRL_DIST_MAX_ENTRIES.
+ * Out of scope: histogram and paired campaigns on this controller or plant; a control-dependent belief flown on the additive
+ * hjb_rollout_set_noise plant; the integrated plants. */
+int32_t hjb_rollout_set_control_lookahead(void *rollout, int32_t mode, int32_t n_nodes, int32_t n_controls, const double *offsets,
+                                          const double *weights);
+int32_t hjb_rollout_run_control_lookahead(void *rollout, int32_t fly_noise, int32_t n_steps, const int32_t *value_plane_of_step,
+                                          int64_t n_traj, const double *X0, uint64_t seed, int64_t first_stream, double *X_final,
+                                          double *cost, double *X_path, double *U_path, double *L_path, double *V_path, double *W_path,
+                                          double *device_ms);
+int32_t hjb_rollout_control_lookahead_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u,
+                                           const double *u_table, const double *A, const double *B, const double *c, const double *q,
+                                           const double *r, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
+                                           const int32_t *value_plane_of_step, int64_t n_traj, const double *X0, double *X_final,
+                                           double *cost, double *X_path, double *U_path, double *L_path, double *V_path, int32_t mode,
+                                           int32_t n_nodes, int32_t n_controls, const double *offsets, const double *weights,
+                                           const int32_t *nodes, int32_t n_flight_nodes, const double *eps, const double *base);
+int32_t hjb_rollout_run_control_lookahead_campaign(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
+                                                   int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
+                                                   const double *threshold, const double *tol, double *stats, double *device_ms);
 
 /* ---- campaign cost histograms: a per-start fixed-bin histogram of the costs beside the statistics (kernel K30) -----------------
  * hjb_rollout_run_campaign_hist and hjb_rollout_run_lookahead_campaign_hist are hjb_rollout_run_campaign and

@@ -174,6 +174,27 @@ int32_t hjb_rollout_lookahead_host(int32_t D, const int32_t *n, const double *kn
 int32_t hjb_rollout_run_lookahead_campaign(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
                                            int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
                                            const double *threshold, const double *tol, double *stats, double *device_ms);
+/* the lookahead with a node set per candidate, the value function of hjb_set_control_disturbance flown directly (kernels K35, K36):
+ * offsets [D, n_nodes, n_controls] column-major as hjb_set_control_disturbance takes them, n_controls the object's label count
+ * (n_nodes 0 detaches); the run functions take hjb_rollout_run_lookahead's and hjb_rollout_run_lookahead_campaign's arguments, fly_noise
+ * 1 and the campaign flying hjb_rollout_set_actuator_noise's plant on hjb_rollout_run_actuator_campaign's streams; the host twin needs
+ * no device and no object (hjbdp.h); usage: matlab/Dynamic_Solver_hjbdp_actuator_lookahead_cost_map.m */
+int32_t hjb_rollout_set_control_lookahead(void *rollout, int32_t mode, int32_t n_nodes, int32_t n_controls, const double *offsets,
+                                          const double *weights);
+int32_t hjb_rollout_run_control_lookahead(void *rollout, int32_t fly_noise, int32_t n_steps, const int32_t *value_plane_of_step,
+                                          int64_t n_traj, const double *X0, uint64_t seed, int64_t first_stream, double *X_final,
+                                          double *cost, double *X_path, double *U_path, double *L_path, double *V_path, double *W_path,
+                                          double *device_ms);
+int32_t hjb_rollout_control_lookahead_host(int32_t D, const int32_t *n, const double *knots, int32_t n_labels, int32_t n_u,
+                                           const double *u_table, const double *A, const double *B, const double *c, const double *q,
+                                           const double *r, int32_t dtype, int32_t n_value_planes, const void *values, int32_t n_steps,
+                                           const int32_t *value_plane_of_step, int64_t n_traj, const double *X0, double *X_final,
+                                           double *cost, double *X_path, double *U_path, double *L_path, double *V_path, int32_t mode,
+                                           int32_t n_nodes, int32_t n_controls, const double *offsets, const double *weights,
+                                           const int32_t *nodes, int32_t n_flight_nodes, const double *eps, const double *base);
+int32_t hjb_rollout_run_control_lookahead_campaign(void *rollout, int32_t n_steps, const int32_t *value_plane_of_step, int64_t n_starts,
+                                                   int64_t n_samples, const double *X0, uint64_t seed, int64_t first_stream,
+                                                   const double *threshold, const double *tol, double *stats, double *device_ms);
 /* both campaigns with a histogram of every start's costs beside the statistics (kernel K30): n_bins (1..256) equal bins between
  * lo [n_starts] and hi [n_starts], hist [n_bins + 2, n_starts] int64 (underflow, the bins, overflow), stats the plain call's bits;
  * two calls on one seed - a plain campaign for min and max, then this with lo = min, hi = the next double above max - give every

@@ -20,9 +20,14 @@
 // per start on the device; its host side and the host reduce hjb_rollout_campaign_reduce are rollout_campaign_host.hip.
 // hjb_rollout_run_lookahead_campaign (K29, kernels_rollout_lookahead_campaign.h) does the same for the lookahead controller; it and
 // its host twin are rollout_lookahead_campaign_host.hip, on check_lookahead_run and look_host_args / look_host_model below.
+// And a per-control lookahead node set (hjb_rollout_set_control_lookahead): hjb_rollout_run_control_lookahead (K35) and its
+// campaign (K36) fly the affine loop by lookahead under it, on a nominal plant or under the actuator set; no other run function
+// reads it.  They, the setter and the host twin are rollout_ctrl_lookahead_host.hip.
 // Defined here for the host units (rollout_host.h): rfail, check_run / check_traj / check_quaternions (the run functions'
-// refusals, all before any device work), upload, run_chunks (the chunk loop) and run_call (the run functions' entry frame: every
-// run function here and in rollout_channels.hip is its plan, its hooks and its launch).  No kernel is instantiated in this unit.
+// refusals, all before any device work), check_lookahead, upload, attach_table (the table setters' tail), affine_plan and
+// greedy_of_chunk (the affine run functions' plan and record), run_chunks (the chunk loop) and run_call (the run functions' entry
+// frame: every run function here, in rollout_channels.hip and in rollout_ctrl_lookahead_host.hip is its plan, its hooks and its
+// launch).  No kernel is instantiated in this unit.
 #include "rollout_host.h"
 #include "rollout_dispatch.h"
 #include "kernels_rollout_attitude_linear.h"
@@ -39,6 +44,7 @@ void release(Rollout *ro) {
     ro->actuator.reset();
     ro->values.reset();
     ro->look.reset();
+    ro->ctrl_look.reset();
     ro->data.reset();
     if (ro->stream) (void)hipStreamDestroy(ro->stream);
     ro->stream = nullptr;
@@ -79,6 +85,10 @@ int check_grid(const char *who, int D, const int32_t *n, const double *knots, in
     return HJB_OK;
 }
 
+}  // namespace
+
+namespace hjbhost {
+
 // What hjb_rollout_set_lookahead and hjb_rollout_lookahead_host refuse of a lookahead node set, hjb_set_disturbance's refusals, in
 // `who`'s name (D < 1: the offsets are left to the caller, who knows D).  HJB_OK otherwise.
 int check_lookahead(Rollout *ro, const char *who, int D, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights) {
@@ -94,10 +104,6 @@ int check_lookahead(Rollout *ro, const char *who, int D, int32_t mode, int32_t n
             if (!std::isfinite(offsets[a + (int64_t)D * w])) return rfail(ro, HJB_E_INVALID, "%s: offset of axis %d, node %d is not finite", who, a, w);
     return HJB_OK;
 }
-
-}  // namespace
-
-namespace hjbhost {
 
 int rfail(Rollout *ro, int code, const char *fmt, ...) {
     char buf[512];
@@ -401,10 +407,6 @@ int run_call(void *rollout, const ChunkPlan &plan, const std::function<int(Rollo
     return run_chunks(ro, plan, launch);
 }
 
-}  // namespace hjbhost
-
-namespace {
-
 // The plan every run function of the affine model starts from: D doubles of state, X_path and U_path, the cost.  D and n_u are
 // fixed by hjb_rollout_create, so they are read without the lock; of a null handle, which run_call refuses, nothing is read.
 ChunkPlan affine_plan(const Rollout *ro, const char *who, int32_t n_steps, const int32_t *planes, int64_t n_traj, const double *X0,
@@ -433,6 +435,10 @@ DGreedy greedy_of_chunk(const Rollout *ro, const Chunk &c) {
     return G;
 }
 
+}  // namespace hjbhost
+
+namespace {
+
 // The object's noise set for a chunk of a call: the call's seed, the chunk's first stream - streams count through the call - and
 // its W_path
 DNoise noise_of_chunk(const Rollout *ro, const Chunk &c, uint64_t seed, int64_t first_stream, double *Wp) {
@@ -443,12 +449,16 @@ DNoise noise_of_chunk(const Rollout *ro, const Chunk &c, uint64_t seed, int64_t 
     return N;
 }
 
-// The shared tail of hjb_rollout_set_noise, _set_values and _set_lookahead, under ro->mu: `bytes` at src go to the object's device
+}  // namespace
+
+namespace hjbhost {
+
+// The shared tail of hjb_rollout_set_noise, _set_values, _set_lookahead and _set_control_lookahead, under ro->mu: `bytes` at src go to the object's device
 // in a DevData of their own (any false: no table, the set is detached), and once the object's stream is idle `holder` takes it,
 // which releases a table given earlier.  -> *dev, the table on the device (null for none); the caller's record fields follow
 // HJB_OK.  `big`: how the HJB_E_NOMEM refusal calls a table large enough to be checked against the free memory first (null: none is).
 int attach_table(Rollout *ro, const char *who, const void *src, size_t bytes, bool any, std::shared_ptr<DevData> &holder, const void **dev,
-                 const char *big = nullptr) {
+                 const char *big) {
     std::shared_lock<std::shared_mutex> lk(g_capture_mu);
     if (hipSetDevice(ro->device) != hipSuccess) return rfail(ro, HJB_E_DEVICE, "hipSetDevice failed");
     std::shared_ptr<DevData> nd;
@@ -466,7 +476,7 @@ int attach_table(Rollout *ro, const char *who, const void *src, size_t bytes, bo
     return HJB_OK;
 }
 
-}  // namespace
+}  // namespace hjbhost
 
 extern "C" {
 

@@ -1,7 +1,7 @@
 // rollout_host.h - what the host units of the rollouts share (host only; include/hjbdp.h is the public ABI): the object,
 // its refusals, the upload, the chunk loop with the run functions' entry frame (run_call), and the campaigns' entry frame and
-// device loop.  Defined in rollout.hip (the campaigns' checks, frame and loop: rollout_campaign_host.hip); rollout_channels.hip
-// and the four rollout_*campaign*_host.hip are the other readers.
+// device loop.  Defined in rollout.hip (the campaigns' checks, frame and loop: rollout_campaign_host.hip); rollout_channels.hip,
+// rollout_ctrl_lookahead_host.hip and the four rollout_*campaign*_host.hip are the other readers.
 // The frame of the nine run functions, stated once (run_call): every refusal before any device work and in one order, the
 // outputs untouched - what needs no object, the null handle, the object's lock, the controller's checks, the empty call, the
 // trajectories, what is refused per trajectory - then the chunk loop.  An entry point is its hooks, its plan and its launch.
@@ -15,7 +15,9 @@
 #include "kernels_rollout_campaign.h"
 #include "kernels_rollout_campaign_hist.h"
 #include "kernels_rollout_pos_att.h"
+#include "kernels_rollout_greedy.h"
 #include "hjbdp_lookahead.h"
+#include "hjbdp_ctrl_lookahead.h"
 #include <functional>
 #include <memory>
 
@@ -76,6 +78,10 @@ struct Rollout {
     // _run_lookahead_campaign
     hjb::LookSet L{};
     std::shared_ptr<DevData> look;      // L.tab: the weights, then the masked axes' offsets
+    // the per-control lookahead node set (hjb_rollout_set_control_lookahead): CL.n_nodes > 0 while one is set; read by
+    // hjb_rollout_run_control_lookahead and _run_control_lookahead_campaign alone
+    hjb::CtrlLookSet CL{};
+    std::shared_ptr<DevData> ctrl_look; // CL.tab: the weights, then every label's masked axes' offsets
     hipStream_t stream = nullptr;
     std::string err;
 };
@@ -149,6 +155,19 @@ size_t noisy_lds(const Rollout *ro, bool *on);
 // ... and the same rule for the actuator flights (hjb_rollout_run_actuator, _run_actuator_campaign): the tables and the node block of
 // the actuator set together
 size_t actuator_lds(const Rollout *ro, bool *on);
+
+// What hjb_rollout_set_lookahead, hjb_rollout_set_control_lookahead and the lookaheads' host twins refuse of a lookahead node set,
+// hjb_set_disturbance's refusals, in `who`'s name: the mode, n_nodes outside 0..HJB_DIST_MAX_NODES, null offsets, weights with
+// HJB_DIST_WORST, a weight that is not finite or is negative, and of offsets [D, n_nodes] an entry that is not finite (D < 1: the
+// offsets are left to the caller, who knows their shape)
+int check_lookahead(Rollout *ro, const char *who, int D, int32_t mode, int32_t n_nodes, const double *offsets, const double *weights);
+
+// The shared tail of the setters that give an object a table (noise, values, both lookahead sets), under ro->mu: `bytes` at src
+// go to the object's device in a DevData of their own (any false: no table, the set is detached), and once the object's stream is
+// idle `holder` takes it, which releases a table given earlier.  -> *dev, the table on the device (null for none).  `big`: how the
+// HJB_E_NOMEM refusal calls a table large enough to be checked against the free memory first (null: none is).
+int attach_table(Rollout *ro, const char *who, const void *src, size_t bytes, bool any, std::shared_ptr<DevData> &holder, const void **dev,
+                 const char *big = nullptr);
 
 // What the campaigns (hjb_rollout_run_campaign, hjb_rollout_run_lookahead_campaign, their host forms) refuse of their sizes, in
 // `who`'s name: n_samples < 1, n_starts * n_samples overflowing; and of their bounds: a NaN threshold, a NaN or negative tol
@@ -295,5 +314,12 @@ int run_chunks(Rollout *ro, const ChunkPlan &plan, const std::function<hipError_
 // A plan is made before the lock: of the object it may read what hjb_rollout_create fixed (D, n_u), and of a null handle nothing.
 int run_call(void *rollout, const ChunkPlan &plan, const std::function<int(Rollout *)> &no_object, const std::function<int(Rollout *)> &controller,
              const std::function<int(Rollout *)> &starts, const std::function<hipError_t(const Chunk &)> &launch);
+
+// The plan every run function of the affine model starts from: D doubles of state, X_path and U_path, the cost (of a null handle,
+// which run_call refuses, nothing is read); and the greedy part of a chunk's launch record (hjb_rollout_run_greedy, _run_lookahead,
+// _run_control_lookahead): paths 0 .. 3 are X, U, L, V
+ChunkPlan affine_plan(const Rollout *ro, const char *who, int32_t n_steps, const int32_t *planes, int64_t n_traj, const double *X0,
+                      double *X_final, double *cost, double *X_path, double *U_path, double *device_ms);
+hjb::DGreedy greedy_of_chunk(const Rollout *ro, const Chunk &c);
 
 }  // namespace hjbhost

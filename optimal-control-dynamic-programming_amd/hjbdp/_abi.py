@@ -272,6 +272,18 @@ SYMBOLS = {
                                             + [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
                                             + [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
                                             + [C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 3),
+    # the lookahead with a node set per candidate, on a nominal or the actuator plant, its host twin and its campaign
+    "hjb_rollout_set_control_lookahead": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                                      C.POINTER(C.c_double)]),
+    "hjb_rollout_run_control_lookahead": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64,
+                                                      C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 8),
+    "hjb_rollout_control_lookahead_host": (C.c_int32, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32]
+                                           + [C.POINTER(C.c_double)] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
+                                                                             C.c_int64] + [C.POINTER(C.c_double)] * 7
+                                           + [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                              C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "hjb_rollout_run_control_lookahead_campaign": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
+                                                               C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 4),
     # both campaigns with a per-start histogram of the costs beside the statistics, and the host twin of the binning
     "hjb_rollout_run_campaign_hist": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
                                                   C.POINTER(C.c_double), C.c_uint64, C.c_int64] + [C.POINTER(C.c_double)] * 4

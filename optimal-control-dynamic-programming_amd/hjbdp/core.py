@@ -634,6 +634,51 @@ class ActuatorRollout(Rollout):
                               first_stream, cost_threshold, settle_tol)
 
 
+class ControlLookaheadRollout(ActuatorRollout):
+    """An ActuatorRollout that can also fly the value function of a control-dependent backup directly
+    (hjb_rollout_set_control_lookahead, hjb_rollout_run_control_lookahead, hjb_rollout_run_control_lookahead_campaign): one-step
+    lookahead with a node set PER CANDIDATE, on the nominal plant or on set_actuator_noise's.  Everything ActuatorRollout has is
+    here unchanged, and the same C object is behind all three classes.  A class of its own because the method sets of Rollout and
+    ActuatorRollout are pinned interfaces (tests/test_rollout_run_marshalling.py, tests/test_actuator_rollout_refs.py); this one's
+    marshalling is tests/test_control_lookahead_refs.py's."""
+
+    def set_control_lookahead(self, offsets, weights=None, mode="expect"):
+        """A per-control lookahead node set for run_control_lookahead (hjb_rollout_set_control_lookahead): what
+        Backup.set_control_disturbance takes - offsets [D, W, n_labels] (actuator_nodes' table: offsets[:, w, l] is node w of the
+        candidate with 0-based label l), weights [W] (mode "expect" only; None = 1 / W each; used as given), mode "expect" or
+        "worst".  It is what the controller believes; set_actuator_noise's set is the plant, and the two may differ.  A property of
+        its own: set_lookahead's set is neither read nor changed, and run_control_lookahead and its campaign alone read this one."""
+        off, w, mode = check_control_disturbance(self.D, (self.n_labels,), offsets, weights, mode)
+        offc = np.ascontiguousarray(off.reshape(-1, order="F"))
+        self._check(self.lib.hjb_rollout_set_control_lookahead(self._ro, _DIST_MODE[mode], off.shape[1], off.shape[2], _f64p(offc), _f64p(w)))
+
+    def clear_control_lookahead(self):
+        """Detach the per-control lookahead node set (hjb_rollout_set_control_lookahead with n_nodes = 0)."""
+        self._check(self.lib.hjb_rollout_set_control_lookahead(self._ro, _abi.HJB_DIST_EXPECT, 0, 0, None, None))
+
+    def run_control_lookahead(self, X0, value_plane_of_step, actuator=False, seed=0, first_stream=0, keep_path=False):
+        """run_lookahead with a node set per candidate (hjb_rollout_run_control_lookahead): at every step the row l of u_table that
+        minimises g(x, u_l) + E_w J(A x + B u_l + c + e_w(l)) (or max_w) over set_control_lookahead's nodes, J the plane
+        value_plane_of_step[k] of set_values (-1: the zero function).  actuator=False flies the nominal plant (seed and first_stream
+        are not read); actuator=True flies run_actuator's plant under set_actuator_noise's nodes, trajectory i on the stream
+        first_stream + i of `seed`, the cost charged on the commanded u.  Returns run_lookahead's dict: U_path the commanded
+        controls, W_path [n_traj, n_steps] int32 the drawn nodes (None unless actuator and keep_path)."""
+        return self._run(self.lib.hjb_rollout_run_control_lookahead, (1 if actuator else 0,), X0, self.D, value_plane_of_step,
+                         "value_plane_of_step", keep_path,
+                         (("X_path", self.D, 1), ("U_path", self.n_u, 0), ("L_path", 1, 0), ("V_path", 1, 0), ("W_path", 1, 0)),
+                         mid=(int(seed) & (2 ** 64 - 1), int(first_stream)), null=() if actuator else ("W_path",))
+
+    def run_control_lookahead_campaign(self, X0, value_plane_of_step, n_samples, seed=0, first_stream=0, cost_threshold=None,
+                                       settle_tol=None):
+        """run_lookahead_campaign for run_control_lookahead's controller on the plant of set_actuator_noise
+        (hjb_rollout_run_control_lookahead_campaign): sample m of start s is run_control_lookahead(actuator=True)'s trajectory on
+        stream first_stream + s * n_samples + m of `seed` - the stream run_actuator_campaign gives that sample, so the stored
+        labels and the value function fly common random numbers.  cost_threshold, settle_tol and the returned dict: run_campaign's."""
+        ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
+        return self._campaign(self.lib.hjb_rollout_run_control_lookahead_campaign, (int(ps.size), _i32p(ps)), X0, n_samples, seed,
+                              first_stream, cost_threshold, settle_tol)
+
+
 def noise_thresholds(weights, n_nodes=None):
     """The sampler's W - 1 thresholds of a weight vector (hjb_rollout_noise_table; no device): weights [W], or None with
     n_nodes = W for equal weights.  Node w is drawn when T[w-1] <= word < T[w] (T[-1] = 0, T[W-1] = 2^32)."""
@@ -962,6 +1007,65 @@ def lookahead_host(knots, u_table, A, B, J, X0, value_plane_of_step, offsets, we
                                                      None if v is None else v.ctypes.data, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
                                                      *map(_f64p, flat), _DIST_MODE[mode], off.shape[1], _f64p(offc), _f64p(w), _i32p(nd),
                                                      int(Wf), _f64p(fo)))
+    if keep_path:
+        paths["L_path"] = paths["L_path"][:, 0, :].astype(np.int32) + np.int32(index_base)
+        paths["V_path"] = paths["V_path"][:, 0, :]
+    return {"X_final": Xf.T, "cost": cost, **paths}
+
+
+def control_lookahead_host(knots, u_table, A, B, J, X0, value_plane_of_step, offsets, weights=None, mode="expect", c=None, q=None, r=None,
+                           index_base=0, nodes=None, eps=None, base=None, keep_path=False):
+    """ControlLookaheadRollout.run_control_lookahead on the CPU (hjb_rollout_control_lookahead_host; no device, no object):
+    lookahead_host's arguments with the per-control set as set_control_lookahead takes it (offsets [D, W, n_labels]), and
+    optionally the actuator plant as GIVEN nodes - nodes [n_traj, n_steps] int32 (noise_draw's output) of the set eps [W_f] or
+    [W_f, n_u] and base [D, W_f] or None (set_actuator_noise's arguments); nodes None flies the nominal plant.  Returns
+    run_greedy's dict without device_ms; L_path holds label + index_base, U_path the commanded controls."""
+    lib = load_library()
+    ks = [np.ascontiguousarray(k, dtype=np.float64).reshape(-1) for k in knots]
+    D = len(ks)
+    n = [len(k) for k in ks]
+    nS = int(np.prod(n, dtype=np.int64)) if ks else 1
+    ut = np.asarray(u_table, dtype=np.float64)
+    ut = ut.reshape(-1, 1) if ut.ndim == 1 else ut
+    n_labels, nu = ut.shape
+    ut = np.ascontiguousarray(ut.reshape(-1, order="F"))
+    kcat = np.ascontiguousarray(np.concatenate(ks) if ks else np.zeros(0))
+    v, dtype = (None, _abi.HJB_F64) if J is None else _value_planes(J, nS)
+    X = _starts(X0, D)
+    nt = X.shape[0]
+    ps = _int32_vector(value_plane_of_step, "value_plane_of_step")
+    K = int(ps.size)
+    off, w, mode = check_control_disturbance(D, (n_labels,), offsets, weights, mode)
+    offc = np.ascontiguousarray(off.reshape(-1, order="F"))
+    nd = ec = bc = None
+    Wf = 0
+    if nodes is not None:
+        if eps is None:
+            raise ValueError("nodes need eps [W_f] or [W_f, n_u]")
+        e = np.array(eps, dtype=np.float64)
+        if e.ndim == 1:
+            e = np.repeat(e[:, None], nu, axis=1)
+        if e.ndim != 2 or e.shape[1] != nu:
+            raise ValueError("eps must be [W_f] or [W_f, n_u=%d], got %r" % (nu, e.shape))
+        Wf = e.shape[0]
+        ec = np.ascontiguousarray(e.reshape(-1))              # [W_f, n_u] row-major is [n_u, W_f] column-major
+        if base is not None:
+            b = np.array(base, dtype=np.float64, ndmin=2)
+            if b.shape != (D, Wf):
+                raise ValueError("base must be [D=%d, W_f=%d], got %r" % (D, Wf, b.shape))
+            bc = np.ascontiguousarray(b.reshape(-1, order="F"))
+        nd = np.asarray(nodes)
+        if nd.shape != (nt, K) or nd.dtype.kind not in "iu":
+            raise ValueError("nodes must be [n_traj=%d, n_steps=%d] integers, got %r %s" % (nt, K, nd.shape, nd.dtype))
+        nd = np.ascontiguousarray(nd.astype(np.int32).reshape(-1, order="F"))
+    Xf = np.empty((nt, D))
+    cost = np.empty(nt)
+    flat, paths = _path_buffers(nt, keep_path, ("X_path", D, K + 1), ("U_path", nu, K), ("L_path", 1, K), ("V_path", 1, K))
+    _check(lib, None, lib.hjb_rollout_control_lookahead_host(
+        D, (C.c_int32 * max(D, 1))(*n), _f64p(kcat), int(n_labels), int(nu), _f64p(ut), _f64p(_f64_colmajor(A, D, D)),
+        _f64p(_f64_colmajor(B, D, nu)), _f64p(_f64_vec(c, D)), _f64p(_f64_vec(q, D)), _f64p(_f64_vec(r, nu)), dtype,
+        0 if v is None else v.size // nS, None if v is None else v.ctypes.data, K, _i32p(ps), nt, _f64p(X), _f64p(Xf), _f64p(cost),
+        *map(_f64p, flat), _DIST_MODE[mode], off.shape[1], off.shape[2], _f64p(offc), _f64p(w), _i32p(nd), int(Wf), _f64p(ec), _f64p(bc)))
     if keep_path:
         paths["L_path"] = paths["L_path"][:, 0, :].astype(np.int32) + np.int32(index_base)
         paths["V_path"] = paths["V_path"][:, 0, :]

@@ -244,8 +244,9 @@ class Dynamic_Solver:
         if self.u_star_idxs is None or (values and self.J_star is None):
             raise RuntimeError("run() first")
         if (lookahead is not False or noise) and self.actuator_noise is not None:
-            raise RuntimeError("%s: flying under control-dependent noise (self.actuator_noise) is not built; run() and policy_cost() "
-                               "design and price under it" % who)
+            raise RuntimeError("%s believes and flies an additive node set; under control-dependent noise (self.actuator_noise) the "
+                               "flights are get_actuator_paths (the stored labels) and get_actuator_lookahead_paths (the value "
+                               "function), with their campaign forms" % who)
         if (lookahead is not False or noise) and self.disturbance is None:
             raise RuntimeError("%s needs self.disturbance = (offsets [2, W], weights or None, mode)" % who)
         if lookahead is not False and lookahead not in ("disturbed", "nominal"):
@@ -336,6 +337,92 @@ class Dynamic_Solver:
         (for a 'worst' set its max) is what n_samples flights paid."""
         return self._grid_map(self.get_actuator_cost_statistics(self._grid_starts(), n_samples, seed=seed, mode=mode, ssu_num=ssu_num,
                                                                 method=method, cost_threshold=cost_threshold, settle_tol=settle_tol))
+
+    def _actuator_lookahead_rollout(self, who):
+        """What the three actuator-lookahead flights fly on, beside _rollout (whose lookahead flights keep refusing
+        self.actuator_noise: they believe and fly an additive set): refuses at once no self.actuator_noise and no run() yet, and
+        returns a context manager that opens an hjbdp.ControlLookaheadRollout on the stored policy with set_model,
+        set_values(J_star), set_control_lookahead(the table build_spec gives the backup, in the set's own mode) and
+        set_actuator_noise(eps, weights): what was designed under is what is believed and what is flown."""
+        from .core import ControlLookaheadRollout
+        if self.actuator_noise is None:
+            raise RuntimeError("%s needs self.actuator_noise = (eps [W], weights or None, mode)" % who)
+        if self.u_star_idxs is None or self.J_star is None:
+            raise RuntimeError("run() first")
+
+        @contextlib.contextmanager
+        def opened():
+            off, wts, dist_mode = self.build_spec().control_disturbance
+            s_r = np.asarray(self.s_r, dtype=np.float64)
+            u_table = np.asarray(self._U_mesh).astype(self.J_star.dtype).astype(np.float64)
+            with ControlLookaheadRollout([s_r, s_r], self.u_star_idxs, u_table, index_base=1, device=self.device) as ro:
+                ro.set_model(self.A, self.B, q=np.diag(self.Q), r=[self.R])
+                ro.set_values(self.J_star)
+                ro.set_control_lookahead(off, wts, dist_mode)
+                ro.set_actuator_noise(self.actuator_noise[0], self.actuator_noise[1] if len(self.actuator_noise) > 1 else None)
+                yield ro
+        return opened()
+
+    def get_actuator_lookahead_paths(self, X0s, n_samples=None, seed=0, mode="Nssu", ssu_num=1):
+        """The closed loop of the cost-to-go designed under ACTUATOR noise, on the GPU
+        (hjbdp.ControlLookaheadRollout.run_control_lookahead): get_lookahead_paths for self.actuator_noise - the control of U_mesh
+        that minimises x'Qx + R u^2 + E_w J_{k+1}(A x + B u (1 + eps_w)) (or max_w, in the set's own mode) at the state actually
+        visited, the controller run() under self.actuator_noise is exactly optimal for.  Planes and `mode` / `ssu_num` as in
+        get_greedy_paths.
+        n_samples None: the nominal plant; returns X [S, N, n] and U [N, n] as get_greedy_paths does and leaves the costs in
+        self.actuator_lookahead_cost [n].  n_samples given: every start flown n_samples times on get_actuator_paths' plant,
+        sample j of start i on stream i * n_samples + j of `seed` (get_actuator_paths' numbering: common random numbers with the
+        stored labels); returns the closed-loop costs [n, n_samples], on the commanded controls, and leaves their mean, standard
+        deviation and maximum per start in self.actuator_lookahead_cost_mean / _std / _max [n].  The kernel's time:
+        self.actuator_lookahead_paths_ms."""
+        opening = self._actuator_lookahead_rollout("get_actuator_lookahead_paths")
+        N, S = self.N, self.S
+        n_st = N - 1
+        planes = self._stage_planes(mode, ssu_num, values=True)
+        if n_samples is not None and int(n_samples) < 1:
+            raise ValueError("n_samples must be at least 1")
+        X0s = np.asarray(X0s, dtype=np.float64).reshape(S, -1)
+        n = X0s.shape[1]
+        with opening as ro:
+            if n_samples is None:
+                out = ro.run_control_lookahead(X0s, planes, keep_path=True)
+            else:
+                out = ro.run_control_lookahead(np.repeat(X0s, int(n_samples), axis=1), planes, actuator=True, seed=seed, first_stream=0)
+        self.actuator_lookahead_paths_ms = out["device_ms"]
+        if n_samples is not None:
+            cost = out["cost"].reshape(n, int(n_samples))
+            self.actuator_lookahead_cost_mean, self.actuator_lookahead_cost_std = cost.mean(axis=1), cost.std(axis=1)
+            self.actuator_lookahead_cost_max = cost.max(axis=1)
+            return cost
+        X = np.ascontiguousarray(out["X_path"].transpose(1, 2, 0))     # [n, S, N] -> [S, N, n]
+        U = np.zeros((N, n))
+        U[:n_st] = out["U_path"][:, 0, :].T
+        self.actuator_lookahead_cost = out["cost"]
+        return X, U
+
+    def get_actuator_lookahead_cost_statistics(self, X0s, n_samples, seed=0, mode="Nssu", ssu_num=1, cost_threshold=None, settle_tol=None):
+        """get_actuator_lookahead_paths' flown flights reduced per start on the GPU
+        (hjbdp.ControlLookaheadRollout.run_control_lookahead_campaign): the same streams, so the same costs, and nothing of length
+        n * n_samples exists on the host or on the device.  The streams pair with get_actuator_cost_statistics /
+        actuator_cost_map: with the same seed and n_samples the stored labels and the value function fly common random numbers.
+        Returns get_noisy_cost_statistics' dict, one entry per start."""
+        if int(n_samples) < 1:
+            raise ValueError("n_samples must be at least 1")
+        opening = self._actuator_lookahead_rollout("get_actuator_lookahead_cost_statistics")
+        planes = self._stage_planes(mode, ssu_num, values=True)
+        with opening as ro:
+            return ro.run_control_lookahead_campaign(np.asarray(X0s, dtype=np.float64).reshape(self.S, -1), planes, int(n_samples),
+                                                     seed=seed, first_stream=0, cost_threshold=cost_threshold, settle_tol=settle_tol)
+
+    def actuator_lookahead_cost_map(self, n_samples, seed=0, mode="Nssu", ssu_num=1, cost_threshold=None, settle_tol=None):
+        """get_actuator_lookahead_cost_statistics at every grid node: actuator_cost_map's starts on actuator_cost_map's streams -
+        each entry [dx, dx] (stats [dx, dx, 8]), node (i, j) = (s_r[i], s_r[j]) flown from stream (i + dx * j) * n_samples on.
+        With the same seed and n_samples this map's mean minus actuator_cost_map's is what the interpolated labels lose to the
+        value function they came from under actuator noise, node by node, with the sampling noise largely cancelled; beside
+        J_star's first plane it is "promised against paid" for the controller the design is exactly optimal for."""
+        return self._grid_map(self.get_actuator_lookahead_cost_statistics(self._grid_starts(), n_samples, seed=seed, mode=mode,
+                                                                          ssu_num=ssu_num, cost_threshold=cost_threshold,
+                                                                          settle_tol=settle_tol))
 
     def get_greedy_paths(self, X0s, mode="Nssu", ssu_num=1):
         """The closed loop of the cost-to-go itself, on the GPU (hjbdp.Rollout.run_greedy): at every step the control of U_mesh
